@@ -51,8 +51,8 @@ if ROOT not in sys.path:
 
 import numpy as np  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-SIMDS = 256 * 4           # 256 CUs x 4 SIMD-32: one VALU wave-instruction issues over 2 cycles (same guide)
+HBM_PEAK_GBS = 8000.0     # MI355X: HBM3E 8.0 TB/s spec
+SIMDS = 256 * 4           # 256 CUs x 4 SIMD-32: one VALU wave-instruction issues over 2 cycles
 CONFIGS = {
     # name: (queries, "per_gpu" | "total", truth titles, k, text of BASELINE.json's config)
     "C2": (100_000, "per_gpu", 500_000, 10, "100k synthetic queries x 500k truth titles, tri-gram vocab ~50k, top-10"),
@@ -197,6 +197,46 @@ def resolve_config(name, world, queries=None, truth=None, k=None):
             custom)
 
 
+DUMP_ROWS_BYTES = 16 * 2 ** 20        # --dump-outputs: top-k rows (+ their query indexes) as float64
+DUMP_FEATURES_BYTES = 44 * 2 ** 20    # --dump-outputs: feature rows + their non-finite codes (float32) + query indexes
+
+
+def dump_sample(n_queries, per_query_bytes, budget, seed):
+    """Sorted query indexes whose dumped arrays fit `budget` bytes: all of them, else a fixed sample drawn with `seed`."""
+    limit = max(1, budget // per_query_bytes)
+    if n_queries <= limit:
+        return np.arange(n_queries, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n_queries, size=limit, replace=False)).astype(np.int64)
+
+
+def dump_outputs(directory, rows, pipeline, q_begin, seed):
+    """What the timed path computed in its last step, as .npy files for comparing two builds output for output (< 64 MB):
+    rows.npy             float64[n, k]       top-k truth rows of the queries in rows_query_index.npy (whole job)
+    features.npy         float32[m * k, 66]  feature vectors of the pairs of the queries in features_query_index.npy
+                                             (query-major, candidates in rank order; this rank's shard), with every
+                                             non-finite entry written as 0
+    features_nonfinite.npy float32[m * k, 66]  where those entries were: 0 finite, +1 / -1 NaN with the sign bit clear /
+                                             set (the word features beyond a truth title's word count are NaN, as in
+                                             the reference), +2 / -2 +inf / -inf
+    *_query_index.npy    float64             the queries dumped (all of them, or a fixed sample seeded by --seed)."""
+    from doppel_speller_amd import FEATURES_COUNT
+    os.makedirs(directory, exist_ok=True)
+    k = rows.shape[1]
+    rows_index = dump_sample(rows.shape[0], 8 * k + 8, DUMP_ROWS_BYTES, seed)
+    features_index = dump_sample(pipeline.n_queries, 8 * FEATURES_COUNT * k + 8, DUMP_FEATURES_BYTES, seed + 1)
+    features = pipeline.features_of(features_index)
+    finite = np.isfinite(features)
+    nonfinite = np.where(np.isnan(features), 1.0, 2.0) * np.where(np.signbit(features), -1.0, 1.0)
+    arrays = {"rows": rows[rows_index].astype(np.float64), "rows_query_index": rows_index.astype(np.float64),
+              "features": np.where(finite, features, 0).astype(np.float32),
+              "features_nonfinite": np.where(finite, 0, nonfinite).astype(np.float32),
+              "features_query_index": (q_begin + features_index).astype(np.float64)}
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), array)
+    log(f"outputs of the last timed step written to {directory}: " +
+        ", ".join(f"{name} {list(array.shape)}" for name, array in arrays.items()))
+
+
 def spawn_ranks(gpus):
     """`--gpus N` without a launcher: start N fresh rank processes (one per GPU) BEFORE this process touches the GPU and
     exit with their worst status.  Rank 0 inherits stdout (the JSON line); the other ranks' stdout goes to stderr."""
@@ -234,6 +274,8 @@ def main():
     parser.add_argument("--allow-host-fallback", action="store_true",
                         help="if RCCL cannot be initialised, gather through the host instead of failing (rehearsals)")
     parser.add_argument("--shared-dir", default=None, help="where rank 0 publishes the workload (default /dev/shm)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="rank 0 writes what the last timed step computed to DIR/<name>.npy (dump_outputs)")
     args = parser.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -347,6 +389,7 @@ def main():
 
     timer_j, timer_f = _lib.Timer(device), _lib.Timer(device)
     jaccard_ms, feature_ms, topk_kernel_ms, dense_kernel_ms = [], [], [], []
+    gathered = [None]   # the job's rows after the last step's all-gather (N > 1)
 
     def step(record):
         timer_j.start(stream)
@@ -361,9 +404,9 @@ def main():
             _lib.check(_lib.lib().ds_stream_sync(stream_handle, device), "sync"); log("features done")
         if distributed:
             if communicator.on_device:
-                gather.gather(pipeline.rows_ptr, stream)          # ONE ncclAllGather on the same stream
+                gathered[0] = gather.gather(pipeline.rows_ptr, stream)          # ONE ncclAllGather on the same stream
             else:
-                gather.gather(pipeline.rows())
+                gathered[0] = gather.gather(pipeline.rows())
         if record:
             jaccard_ms.append(timer_j.elapsed_ms())   # synchronises on the stop events
             feature_ms.append(timer_f.elapsed_ms())
@@ -382,6 +425,14 @@ def main():
     stats = pipeline.sync(stream)
     if distributed:
         elapsed = rendezvous.max(elapsed)
+    if args.dump_outputs and rank == 0:   # before anything below launches the kernels again
+        if not distributed:
+            job_rows = pipeline.rows()
+        elif isinstance(gathered[0], np.ndarray):
+            job_rows = gathered[0]
+        else:
+            job_rows = gathered[0].to_host()
+        dump_outputs(args.dump_outputs, job_rows, pipeline, q_begin, args.seed)
     # one more launch, untimed, with the instantiation of the kernel that counts the bytes it requests (same work)
     pipeline.index.option("count_bytes", 1)
     pipeline.enqueue_top_k(stream)
