@@ -178,4 +178,8 @@ struct ds_titles {
     ds::DeviceBuffer<int32_t> unit_queue;  // [64] heads of the features kernel's work queue, one per launch in turn (indexed entry points)
     size_t unit_queue_next = 0;
     bool records_enabled = true;        // ds_titles_option("truth_records", 0) switches them off (160 B per row of HBM)
+    // exact-match hash table of a truth table (ds_exact.hip): int32 rows, capacity = the power of two >= 2n, built on the
+    // first exact-match call; ds_titles_option("exact_table", 0) frees it, "exact_hash_bits" truncates the title hash
+    ds::DeviceBuffer<int32_t> exact_slots;
+    int exact_hash_bits = 64;
 };

@@ -1078,6 +1078,24 @@ int ds_titles_option(ds_titles *titles, const char *name, int64_t value)
         }
         return DS_OK;
     }
+    if (std::strcmp(name, "exact_table") == 0) {     // 0 frees the exact-match table; the next exact-match call rebuilds it
+        if (value == 0) {
+            DS_HIP(hipSetDevice(titles->device));
+            DS_HIP(hipDeviceSynchronize());
+            titles->exact_slots.release();
+        }
+        return DS_OK;
+    }
+    if (std::strcmp(name, "exact_hash_bits") == 0) { // bits of the title hash the exact-match table keeps (tests: collisions)
+        DS_REQUIRE(value >= 1 && value <= 64, "ds_titles_option: exact_hash_bits must lie in 1..64");
+        if (value != titles->exact_hash_bits) {
+            DS_HIP(hipSetDevice(titles->device));
+            DS_HIP(hipDeviceSynchronize());
+            titles->exact_slots.release();
+            titles->exact_hash_bits = static_cast<int>(value);
+        }
+        return DS_OK;
+    }
     ds::set_error("ds_titles_option: unknown option '%s'", name);
     return DS_E_ARG;
 }

@@ -179,6 +179,17 @@ int ds_device_name(int device, char *name, size_t capacity)
     return DS_OK;
 }
 
+int ds_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes)
+{
+    DS_REQUIRE(free_bytes != nullptr && total_bytes != nullptr, "ds_device_memory: null output");
+    DS_HIP(hipSetDevice(device));
+    size_t free_now = 0, total = 0;
+    DS_HIP(hipMemGetInfo(&free_now, &total));
+    *free_bytes = static_cast<int64_t>(free_now);
+    *total_bytes = static_cast<int64_t>(total);
+    return DS_OK;
+}
+
 }  // extern "C"
 
 // ---- tiled index ---------------------------------------------------------------------------------------------------

@@ -220,3 +220,14 @@ def find_close_matches(queries, truth, rows, threshold=LEVENSHTEIN_RATIO_THRESHO
                                            int(space_code), _lib.pointer(sort_key), int(threshold),
                                            _lib.pointer(ratios), _lib.pointer(best_row)), "ds_close_matches")
     return ratios, best_row
+
+
+def exact_matches(truth, queries, n_queries=None):
+    """The exact stage of Prediction (predict.py:97-113) for the first n_queries rows of the query TitleTable: int32[n],
+    the last truth row whose encoded title equals the query's, -1 where none does (ds_exact_matches).  The truth table's
+    hash table is built by the first call and kept (truth.option("exact_table", 0) frees it)."""
+    n_queries = queries.n if n_queries is None else int(n_queries)
+    out = np.empty(n_queries, dtype=np.int32)
+    _lib.check(_lib.lib().ds_exact_matches(truth.handle, queries.handle, n_queries,
+                                           _lib.pointer(out) if n_queries else ctypes.c_void_p(0)), "ds_exact_matches")
+    return out

@@ -42,6 +42,7 @@ class CandidatePipeline:
         self._predictions = None
         self._pairs = None
         self._matches = None
+        self._exact = None
 
     def enqueue_top_k(self, stream=None):
         self.index.top_k_device(self.d_rowptr.ptr, self.d_cols.ptr, self.d_maxint.ptr, self.n_queries, self.k,
@@ -70,6 +71,22 @@ class CandidatePipeline:
         """(ratios uint8[Q, k], best_row int32[Q]) of the last `enqueue_close_matches`."""
         ratios, best, _ = self._close
         return ratios.to_host(), best.to_host()
+
+    def enqueue_exact_matches(self, stream=None):
+        """The exact stage (predict.py:97-113): per query the last truth row with the same transformed title, or -1.
+        After `enqueue_close_matches` it also overrides that step's best row wherever an exact match exists, so that
+        `enqueue_remaining_pairs` drops the exact and the fuzzy matches in one pass.  The truth table's hash table is
+        built by the first call."""
+        if self._exact is None:
+            self._exact = _lib.DeviceArray((max(self.n_queries, 1),), np.int32, self.device)
+        best = self._close[1].ptr if self._close is not None else ctypes.c_void_p(0)
+        _lib.check(_lib.lib().ds_exact_matches_device(self.truth_titles.handle, self.query_titles.handle, 0,
+                                                      self.n_queries, self._exact.ptr, best,
+                                                      ctypes.c_void_p(stream or 0)), "ds_exact_matches_device")
+
+    def exact_matches(self):
+        """int32[Q]: the truth row of every query's exact match (-1: none) of the last `enqueue_exact_matches`."""
+        return self._exact.to_host()[:self.n_queries]
 
     def enqueue_remaining_pairs(self, stream=None):
         """Next row f-2 (predict.py:172-183): drop the queries the fuzzy step matched (`enqueue_close_matches` first)

@@ -1,0 +1,369 @@
+"""Prediction.generate_test_predictions (doppelspeller/predict.py:256-300) end to end on the GPU: one answer per title.
+
+The four stages of the reference, in its order of priority:
+
+    1. exact    the transformed title is a truth title (predict.py:97-113; the last truth row of a title wins)
+    2. close    the fuzzy ratio of a top-n candidate is above the Levenshtein threshold (:140-183)
+    3. model    the tree ensemble on the features of the remaining queries' candidates (:185-254)
+    4. none     title_id -1 (settings.TRAIN_NOT_FOUND_VALUE, :256-272)
+
+Per chunk of queries every stage runs on the device (Jaccard top-k, close matches, the exact override, the pair list of
+the remaining queries, construct_features, the forest, the match selection); the per-query results come back once.
+The truth side (inverted index, encoded titles, word counts, the exact-match table) is built once by the constructor.
+
+Differences from the reference, on purpose:
+  - `truth_title_ids` must be unique: the reference keeps two dicts (title -> id, id -> title) whose meaning is only
+    defined for unique ids.
+  - `closest_search_single_title` returns the exact or close match when there is one; the reference raises there
+    (`_find_matches_using_model` is reached with no rows and `np.vstack([])` fails).
+"""
+import ctypes
+import time
+
+import numpy as np
+
+from . import _lib
+from .distributed import slice_queries
+from .feature_engineering import (ALLOWED_CHARACTERS, FEATURES_COUNT, LEVENSHTEIN_RATIO_THRESHOLD, SORT_KEY, SPACE_CODE,
+                                  TitleTable, encode_collection, truth_word_counts)
+from .match_maker import NativeProblem, TruthIndex
+
+PREDICTION_PROBABILITY_THRESHOLD = 0.9   # settings.py:76
+TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
+N_GRAM = 3                               # settings.py:15
+STAGE_NONE, STAGE_EXACT, STAGE_CLOSE, STAGE_MODEL = 0, 1, 2, 3
+# device bytes per query and candidate of one chunk: features (66 float32), prediction, top-k row, ratio, pair (q, t)
+_BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
+
+_CODE_OF = np.zeros(256, dtype=np.uint8)      # ASCII byte -> code of encode_title (feature_engineering.py:298-307)
+_ALLOWED = np.zeros(256, dtype=bool)          # the characters a transformed title may hold (the fill '-' is not one)
+for _code, _character in enumerate(ALLOWED_CHARACTERS):
+    _CODE_OF[ord(_character)] = _code
+    _ALLOWED[ord(_character)] = _code != 0
+
+
+def _validate_chunk(chunk_queries):
+    if chunk_queries is not None and (isinstance(chunk_queries, bool) or not isinstance(chunk_queries, (int, np.integer))
+                                      or chunk_queries <= 0):
+        raise ValueError(f"chunk_queries must be a positive integer or None, not {chunk_queries!r}")
+
+
+def validate_truth(truth_titles, truth_title_ids, top_n):
+    """The constructor's checks (no library needed): int64 ids, one per title, unique and non-negative."""
+    ids = np.asarray(truth_title_ids)
+    if ids.ndim != 1 or len(truth_titles) != ids.shape[0]:
+        raise ValueError(f"{len(truth_titles)} truth titles but {ids.reshape(-1).shape[0]} title ids")
+    if ids.shape[0] and not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f"truth title ids must be integers, not {ids.dtype}")
+    ids = ids.astype(np.int64)
+    if ids.shape[0] and ids.min() < 0:
+        raise ValueError("truth title ids must be non-negative (-1 is the 'not found' answer)")
+    if np.unique(ids).shape[0] != ids.shape[0]:
+        raise ValueError("truth title ids must be unique")
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or top_n < 1:
+        raise ValueError(f"top_n must be a positive integer, not {top_n!r}")
+    if top_n > ids.shape[0]:
+        raise ValueError(f"top_n = {top_n} exceeds the {ids.shape[0]} truth titles")
+    return ids
+
+
+def validate_queries(titles, test_index):
+    """generate_test_predictions' checks: int64 test indexes, one per title, unique."""
+    if test_index is None:
+        return np.arange(len(titles), dtype=np.int64)
+    index = np.asarray(test_index)
+    if index.ndim != 1 or index.shape[0] != len(titles):
+        raise ValueError(f"{len(titles)} titles but {index.reshape(-1).shape[0]} test indexes")
+    if index.shape[0] and not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"test indexes must be integers, not {index.dtype}")
+    index = index.astype(np.int64)
+    if np.unique(index).shape[0] != index.shape[0]:
+        raise ValueError("test indexes must be unique")
+    return index
+
+
+def combine_stages(exact_row, close_row, model_row):
+    """Per query (match row, stage) from the three stages' rows (-1 = no match), in the reference's priority: a query
+    an earlier stage matched never reaches a later one (predict.py:120-121, :183)."""
+    exact_row, close_row, model_row = (np.asarray(a, dtype=np.int64) for a in (exact_row, close_row, model_row))
+    row = np.where(exact_row >= 0, exact_row, np.where(close_row >= 0, close_row, model_row))
+    stage = np.where(exact_row >= 0, STAGE_EXACT,
+                     np.where(close_row >= 0, STAGE_CLOSE, np.where(model_row >= 0, STAGE_MODEL, STAGE_NONE)))
+    return np.where(row >= 0, row, -1), stage.astype(np.int8)
+
+
+def finalize_output(test_index, match_row, truth_title_ids):
+    """_finalize_output (predict.py:256-272): a DataFrame [title_id, test_index], one row per test index sorted by it,
+    title_id = the matched truth row's id or -1."""
+    import pandas as pd
+    test_index = np.asarray(test_index, dtype=np.int64)
+    match_row = np.asarray(match_row, dtype=np.int64)
+    ids = np.asarray(truth_title_ids, dtype=np.int64)
+    title_id = np.full(match_row.shape[0], TRAIN_NOT_FOUND_VALUE, dtype=np.int64)
+    found = match_row >= 0
+    title_id[found] = ids[match_row[found]]
+    order = np.argsort(test_index, kind="stable")
+    return pd.DataFrame({"title_id": title_id[order], "test_index": test_index[order]}).reset_index(drop=True)
+
+
+def _pack(titles):
+    """ASCII byte strings -> (uint8 characters, int64 offsets[n + 1])."""
+    encoded = [t.encode("ascii") for t in titles]
+    offsets = np.zeros(len(encoded) + 1, dtype=np.int64)
+    np.cumsum([len(e) for e in encoded], out=offsets[1:])
+    chars = np.frombuffer(b"".join(encoded), dtype=np.uint8) if offsets[-1] else np.zeros(1, dtype=np.uint8)
+    return np.ascontiguousarray(chars), offsets
+
+
+def column_table(vocabulary_keys):
+    """int32[2^24]: the column of every tri-gram key of the vocabulary (big-endian bytes), -1 for the others."""
+    table = np.full(1 << 24, -1, dtype=np.int32)
+    table[np.asarray(vocabulary_keys, dtype=np.int64)] = np.arange(len(vocabulary_keys), dtype=np.int32)
+    return table
+
+
+def query_rows(chars, offsets, vocabulary_keys, idf32, idf64, n_gram=N_GRAM, columns=None):
+    """The query side of the native index build (ds_problem_create, 'query rows') against a truth-only vocabulary:
+    (q_rowptr, q_cols, q_maxint) as `NativeProblem(truth, queries)` computes them, with the columns renumbered into
+    the truth's own vocabulary.  Both number their columns in ascending n-gram order, so a query's truth columns keep
+    their order; an n-gram the truth set lacks has an empty posting list (dropped here: it adds nothing to the
+    intersection) and the largest truth idf (kept in max_intersection_possible, match_maker.py:149-153,197), which
+    is summed in the same ascending n-gram order, in float64.  columns: column_table(vocabulary_keys), when kept."""
+    assert n_gram == 3, "vocabulary keys hold tri-grams"
+    n = offsets.shape[0] - 1
+    lengths = np.diff(offsets)
+    counts = np.maximum(lengths - (n_gram - 1), 0)
+    owner = np.repeat(np.arange(n, dtype=np.int64), counts)
+    start = np.arange(owner.shape[0], dtype=np.int64) - np.repeat(np.cumsum(counts) - counts, counts) + \
+        np.repeat(offsets[:-1], counts)
+    padded = np.concatenate((chars[:int(offsets[-1])], np.zeros(n_gram, np.uint8))).astype(np.int64)
+    keys = (padded[start] << 16) | (padded[start + 1] << 8) | padded[start + 2]
+    unique = np.unique((owner << 24) | keys)            # distinct n-grams per query, ascending
+    owner, keys = unique >> 24, unique & 0xffffff
+    column = (column_table(vocabulary_keys) if columns is None else columns)[keys]
+    known = column >= 0
+    column = np.where(known, column, 0)
+    max_idf = float(np.max(idf64)) if idf64.shape[0] else 0.0
+    value = np.where(known, np.asarray(idf64)[column], max_idf)
+    nonzero = np.where(known, np.asarray(idf32)[column] != 0, np.float32(max_idf) != 0)   # explicit zeros vanish (:118)
+    listed = known & nonzero
+    q_cols = column[listed].astype(np.int32)
+    q_rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(owner[listed], minlength=n), out=q_rowptr[1:])
+    # float64 sums in ascending n-gram order: a [n, width] matrix padded with zeros at the end of each row
+    owner, value = owner[nonzero], value[nonzero]
+    per_query = np.bincount(owner, minlength=n)
+    rank = np.arange(owner.shape[0]) - np.repeat(np.cumsum(per_query) - per_query, per_query)
+    matrix = np.zeros((n, int(per_query.max()) if n and owner.shape[0] else 0), dtype=np.float64, order="F")
+    matrix[owner, rank] = value
+    q_maxint = np.zeros(n, dtype=np.float64)
+    for j in range(matrix.shape[1]):
+        q_maxint = q_maxint + matrix[:, j]
+    return q_rowptr, q_cols, q_maxint
+
+
+class Prediction:
+    """Prediction(truth_titles, truth_title_ids, model).generate_test_predictions(titles) -> the reference's
+    final_output: a DataFrame [title_id, test_index] sorted by test_index, -1 where no stage found a match.
+
+    truth_titles / titles: raw strings, put through transform_titles unless transform=False (then they must already
+    be transformed titles: lower-case letters, digits and single spaces).  model: a ForestModel (the booster of
+    predict.py:80-82).  chunk_queries: queries per device pass (default: what a quarter of the free HBM holds); the
+    answer does not depend on it.  After a call, `details` holds per query match_row, title_id, stage (0 none,
+    1 exact, 2 close, 3 model) and probability (1.0 for exact and close matches, the model's best candidate
+    otherwise, NaN when the query never reached the model), and `timings` the milliseconds of every stage."""
+
+    def __init__(self, truth_titles, truth_title_ids, model, top_n=100, device=0, transform=True,
+                 levenshtein_threshold=LEVENSHTEIN_RATIO_THRESHOLD,
+                 probability_threshold=PREDICTION_PROBABILITY_THRESHOLD, chunk_queries=None):
+        truth_titles = list(truth_titles)
+        self.truth_title_ids = validate_truth(truth_titles, truth_title_ids, top_n)
+        _validate_chunk(chunk_queries)
+        if model is None or not hasattr(model, "predict_device"):
+            raise ValueError("model must be a ForestModel")
+        self.model = model
+        self.top_n = int(top_n)
+        self.device = device
+        self.transform = transform
+        self.levenshtein_threshold = int(levenshtein_threshold)
+        self.probability_threshold = float(probability_threshold)
+        self.chunk_queries = chunk_queries
+        self.details = None
+        self.timings = {}
+
+        self.truth_titles = self._transform(truth_titles)
+        chars, offsets = _pack(self.truth_titles)
+        self._check_characters(chars, offsets, "truth")
+        problem = NativeProblem.from_flat(chars, offsets, np.zeros(1, np.uint8), np.zeros(1, np.int64), N_GRAM)
+        arrays = problem.arrays()
+        self._vocabulary_keys, self._idf32, self._idf64 = arrays["vocabulary_keys"], arrays["idf32"], arrays["idf64"]
+        self._columns = column_table(self._vocabulary_keys)
+        self.index = TruthIndex(arrays["rowptr"], arrays["truth_idx"], arrays["idf32"], arrays["sums32"], device)
+        problem.close()
+        enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+        counts = truth_word_counts(chars, offsets, separators=(ord(" "),))
+        self.truth_table = TitleTable(enc, lengths, counts, device)
+        self.n_truth = len(self.truth_titles)
+        self._sort_key = _lib.DeviceArray.from_host(np.ascontiguousarray(SORT_KEY, dtype=np.uint8), device)
+
+    def _transform(self, titles):
+        from .text import transform_titles
+        titles = [str(t) for t in titles]
+        return transform_titles(titles) if self.transform else titles
+
+    @staticmethod
+    def _check_characters(chars, offsets, what):
+        used = chars[:int(offsets[-1])]
+        if used.shape[0] and not _ALLOWED[used].all():
+            bad = bytes(sorted(set(used[~_ALLOWED[used]].tolist()))).decode("latin-1")
+            raise ValueError(f"{what} titles hold characters a transformed title cannot hold: {bad!r}")
+
+    def _default_chunk(self):
+        free, total = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib().ds_device_memory(self.device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
+        return max(1, int(free.value // 4 // (_BYTES_PER_PAIR * self.top_n + 64)))
+
+    def generate_test_predictions(self, titles, test_index=None):
+        """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
+        titles = list(titles)
+        test_index = validate_queries(titles, test_index)
+        self.details = self._run(titles, test_index)
+        return finalize_output(test_index, self.details["match_row"].to_numpy(), self.truth_title_ids)
+
+    def closest_search_single_title(self, title):
+        """cli.py:64-84 (generate_test_predictions(single_prediction=True)): the best match of one title as a dict
+        with the keys of predict.py:35-41.  Stage priority exact, close, model; the model stage takes the candidate with
+        the highest probability, no threshold, the first in top-n order on a tie (predict.py:239-242)."""
+        stripped = str(title).strip()
+        if not stripped:
+            raise ValueError("empty title")
+        details = self._run([stripped], np.zeros(1, dtype=np.int64), single=True)
+        self.details = details
+        row = int(details["match_row"].iloc[0])
+        return {"test_index": 0, "transformed_title": self._last_queries[0],
+                "match_transformed_title": self.truth_titles[row] if row >= 0 else None,
+                "title_id": int(self.truth_title_ids[row]) if row >= 0 else TRAIN_NOT_FOUND_VALUE,
+                "prediction": float(details["probability"].iloc[0])}
+
+    def _run(self, titles, test_index, single=False):
+        import pandas as pd
+        timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "remaining_pairs",
+                                 "features", "model", "select_matches", "copy_back"), 0.0)
+        started = time.perf_counter()
+        queries = self._transform(titles)
+        self._last_queries = queries
+        n = len(queries)
+        match_row = np.full(n, -1, dtype=np.int64)
+        stage = np.zeros(n, dtype=np.int8)
+        probability = np.full(n, np.nan, dtype=np.float32)
+        if n == 0:
+            self.timings = timings
+            return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": match_row,
+                                 "stage": stage, "probability": probability})
+        chars, offsets = _pack(queries)
+        self._check_characters(chars, offsets, "query")
+        q_rowptr, q_cols, q_maxint = query_rows(chars, offsets, self._vocabulary_keys, self._idf32, self._idf64,
+                                               columns=self._columns)
+        enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+        query_table = TitleTable(enc, lengths, None, self.device)
+        chunk = min(n, self.chunk_queries or self._default_chunk())
+        k, device = self.top_n, self.device
+        buffers = dict(rows=_lib.DeviceArray((chunk * k,), np.int32, device),
+                       ratios=_lib.DeviceArray((chunk * k,), np.uint8, device),
+                       best=_lib.DeviceArray((chunk,), np.int32, device),
+                       exact=_lib.DeviceArray((chunk,), np.int32, device),
+                       pair_q=_lib.DeviceArray((chunk * k,), np.int32, device),
+                       pair_t=_lib.DeviceArray((chunk * k,), np.int32, device),
+                       counts=_lib.DeviceArray((int(_lib.lib().ds_remaining_pairs_counts_size(chunk)),), np.int64, device),
+                       features=_lib.DeviceArray((chunk * k, FEATURES_COUNT), np.float32, device),
+                       predictions=_lib.DeviceArray((chunk * k,), np.float32, device),
+                       match_query=_lib.DeviceArray((chunk,), np.int32, device),
+                       match_row=_lib.DeviceArray((chunk,), np.int32, device))
+        timings["host_prepare"] = (time.perf_counter() - started) * 1000.0
+        events = {name: _lib.Timer(device) for name in timings if name not in ("host_prepare", "copy_back")}
+        for first in range(0, n, chunk):
+            last = min(n, first + chunk)
+            self._chunk(query_table, q_rowptr, q_cols, q_maxint, first, last, buffers, events, timings,
+                               match_row, stage, probability, single)
+        title_id = np.where(match_row >= 0, self.truth_title_ids[np.maximum(match_row, 0)], TRAIN_NOT_FOUND_VALUE)
+        self.timings = timings
+        return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
+                             "probability": probability})
+
+    def _chunk(self, query_table, q_rowptr, q_cols, q_maxint, first, last, b, events, timings, match_row, stage,
+               probability, single):
+        lib, k, n = _lib.lib(), self.top_n, last - first
+        stream = ctypes.c_void_p(0)
+        rowptr, cols, maxint = slice_queries(q_rowptr, q_cols, q_maxint, first, last)
+        d_rowptr = _lib.DeviceArray.from_host(rowptr, self.device)
+        d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), self.device)
+        d_maxint = _lib.DeviceArray.from_host(maxint, self.device)
+
+        def timed(name, enqueue):
+            events[name].start()
+            enqueue()
+            events[name].stop()
+
+        # 1. Jaccard top-k (synchronised: ds_jaccard_sync reports errors and settles the queries it resolves late)
+        timed("top_k", lambda: self.index.top_k_device(d_rowptr.ptr, d_cols.ptr, d_maxint.ptr, n, k, b["rows"].ptr))
+        self.index.sync()
+        timings["top_k"] += events["top_k"].elapsed_ms()
+        # 2. close matches, 3. the exact stage overrides their best row, 4. the pairs of the queries still unmatched
+        timed("close_matches", lambda: _lib.check(lib.ds_close_matches_device(
+            query_table.handle, self.truth_table.handle, b["rows"].ptr, first, k, n, SPACE_CODE, self._sort_key.ptr,
+            self.levenshtein_threshold, b["ratios"].ptr, b["best"].ptr, stream), "ds_close_matches_device"))
+        timed("exact_matches", lambda: _lib.check(lib.ds_exact_matches_device(
+            self.truth_table.handle, query_table.handle, first, n, b["exact"].ptr, b["best"].ptr, stream),
+            "ds_exact_matches_device"))
+        timed("remaining_pairs", lambda: _lib.check(lib.ds_remaining_pairs_device(
+            b["best"].ptr, b["rows"].ptr, n, k, first, b["pair_q"].ptr, b["pair_t"].ptr, b["counts"].ptr, stream),
+            "ds_remaining_pairs_device"))
+        _lib.check(lib.ds_stream_sync(stream, self.device), "sync")
+        totals = np.empty(2, dtype=np.int64)
+        _lib.check(lib.ds_memcpy_d2h(_lib.pointer(totals), b["counts"].ptr, 16, self.device), "d2h")
+        n_remaining, n_pairs = int(totals[0]), int(totals[1])
+        # 5. features of the remaining pairs, 6. the forest, 7. one match per remaining query
+        timed("features", lambda: _lib.check(lib.ds_construct_features_indexed_device(
+            query_table.handle, self.truth_table.handle, b["pair_q"].ptr, b["pair_t"].ptr, 0, k, SPACE_CODE,
+            self.n_truth, n_pairs, b["features"].ptr, stream), "ds_construct_features_indexed_device"))
+        timed("model", lambda: self.model.predict_device(b["features"].ptr, n_pairs, None, b["predictions"].ptr))
+        timed("select_matches", lambda: _lib.check(lib.ds_select_matches_device(
+            b["pair_q"].ptr, b["pair_t"].ptr, b["predictions"].ptr, n_remaining, k, self.probability_threshold,
+            b["match_query"].ptr, b["match_row"].ptr, stream), "ds_select_matches_device"))
+        for name in ("close_matches", "exact_matches", "remaining_pairs", "features", "model", "select_matches"):
+            timings[name] += events[name].elapsed_ms()
+
+        # one copy back of the per-query results
+        copy_started = time.perf_counter()
+
+        def fetch(name, count, dtype):
+            out = np.empty(count, dtype=dtype)
+            if count:
+                _lib.check(lib.ds_memcpy_d2h(_lib.pointer(out), b[name].ptr, out.nbytes, self.device), "d2h")
+            return out
+        exact = fetch("exact", n, np.int32)
+        best = fetch("best", n, np.int32)            # exact rows where they exist, else the close step's best row
+        match_query = fetch("match_query", n_remaining, np.int32)
+        model_rows = fetch("match_row", n_remaining, np.int32)
+        predictions = fetch("predictions", n_pairs, np.float32).reshape(n_remaining, k)
+        timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+
+        close = np.where(exact >= 0, -1, best)
+        model = np.full(n, -1, dtype=np.int32)
+        local = match_query.astype(np.int64) - first
+        model[local] = model_rows
+        rows, stages = combine_stages(exact, close, model)
+        chunk_probability = np.full(n, np.nan, dtype=np.float32)
+        chunk_probability[rows >= 0] = 1.0
+        if n_remaining:
+            chunk_probability[local] = predictions.max(axis=1)
+        if single and n_remaining:
+            # cli.py / predict.py:239-242: the model stage of one title takes the best candidate with no threshold,
+            # the first in top-n order when several hold the maximum
+            pair_t = fetch("pair_t", n_pairs, np.int32).reshape(n_remaining, k)
+            where = int(np.argmax(predictions[0]))
+            rows[local[0]] = pair_t[0, where]
+            stages[local[0]] = STAGE_MODEL
+        match_row[first:last] = rows
+        stage[first:last] = stages
+        probability[first:last] = chunk_probability

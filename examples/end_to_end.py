@@ -57,6 +57,11 @@ def main(n_truth=20000, n_queries=2000, top_n=10):
     print(f"index build + top-k: {t1 - t0:.2f}s   close matches + features + model: {t2 - t1:.2f}s")
     print(f"fuzzy step alone decided {found} queries; feature matrix {features.shape}; "
           f"best model score per query: mean {probabilities.max(axis=1).mean():.3f}")
+
+    # the same question answered by the driver: one title_id (or -1) per query, every stage on the device
+    ids = np.arange(len(truth), dtype=np.int64)
+    answer = ds.Prediction(raw_truth, ids, model, top_n=top_n).generate_test_predictions(raw_queries)
+    print(f"Prediction: {(answer['title_id'] >= 0).sum()} of {len(answer)} queries matched")
     return rows, best_row, features, probabilities
 
 

@@ -52,6 +52,8 @@ int ds_version(void);
 const char *ds_build_id(void);
 int ds_device_count(int *count);
 int ds_device_name(int device, char *name, size_t capacity);
+/* Free and total HBM of a device in bytes right now (hipMemGetInfo): callers size their batches with it. */
+int ds_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes);
 
 /* ---- truth index:  MatchMaker.__init__ product (match_maker.py:99-107) ------------------------------------------ */
 /* rowptr[V+1], truth_idx[nnz]: the V x N inverted index of match_maker.py:122-133 in CSR form (row g = n-gram
@@ -187,6 +189,22 @@ int ds_remaining_pairs_device(const int32_t *d_best_row, const int32_t *d_rows, 
 int ds_select_matches_device(const int32_t *d_pair_q, const int32_t *d_pair_t, const float *d_predictions,
                              int64_t n_remaining, int32_t k, float threshold, int32_t *d_match_query,
                              int32_t *d_match_row, void *stream);
+
+/* ---- exact matches: Prediction._find_exact_matches (predict.py:74-113) ---------------------------------------------
+ * exact_row[q] = the truth row whose encoded title (length and bytes of the ds_titles rows) equals query row q's, the
+ * LAST such row when several truth rows hold the title (the reference's {title: title_id} dict is filled in truth
+ * order), -1 when none does.  The truth table's hash table (int32 rows, capacity = the power of two >= 2N: at most
+ * 16 bytes per truth row) is built on the first call and kept on the handle; DS_E_HIP when it does not fit the free
+ * HBM.  ds_titles_option(truth, "exact_table", 0) frees it; "exact_hash_bits" (1..64, default 64) keeps only the low
+ * bits of the title hash (titles are always compared byte by byte; fewer bits only make the probe sequences longer);
+ * changing it rebuilds the table on the next call.  Host pointers: */
+int ds_exact_matches(ds_titles *truth, ds_titles *queries, int64_t n_queries, int32_t *exact_row);
+/* Query rows [q_first, q_first + n_queries) of the query table, d_exact_row[0 .. n_queries) in HBM; enqueued on
+ * `stream`.  When d_best_row is not NULL, d_best_row[q] = d_exact_row[q] wherever an exact match exists (the other
+ * entries are left alone): called after ds_close_matches_device, ds_remaining_pairs_device then drops the exact and the
+ * fuzzy matches in one pass. */
+int ds_exact_matches_device(ds_titles *truth, ds_titles *queries, int64_t q_first, int64_t n_queries,
+                            int32_t *d_exact_row, int32_t *d_best_row, void *stream);
 
 /* ---- next row f-3: native index build ----------------------------------------------------------------------------
  * Replaces the Python / lil_matrix loops of MatchMaker.__init__ (doppelspeller/match_maker.py:84-181) and
