@@ -240,8 +240,18 @@ def device_count():
     return int(count.value) if status == 0 else 0
 
 
-def pointer(array):
-    return ctypes.c_void_p(array.ctypes.data)
+def pointer(value):
+    """The ctypes.c_void_p of a C ABI argument: a host array's data (None: NULL), a device address (c_void_p, int or
+    DeviceArray) or a stream (None or 0: the null stream)."""
+    if value is None:
+        return ctypes.c_void_p(0)
+    if isinstance(value, ctypes.c_void_p):
+        return value
+    if isinstance(value, DeviceArray):
+        return value.ptr
+    if hasattr(value, "ctypes"):
+        return value.ctypes.data_as(ctypes.c_void_p)     # holds a reference to the array while the pointer lives
+    return ctypes.c_void_p(int(value))
 
 
 class DeviceArray:
@@ -258,7 +268,7 @@ class DeviceArray:
         self.ptr = raw
 
     @classmethod
-    def view(cls, pointer, shape, dtype, device=0):
+    def view(cls, address, shape, dtype, device=0):
         """A typed view of device memory owned by somebody else (never freed here)."""
         import numpy as np
         out = cls.__new__(cls)
@@ -266,7 +276,7 @@ class DeviceArray:
         out.dtype = np.dtype(dtype)
         out.device = device
         out.nbytes = int(np.prod(out.shape, dtype=np.int64)) * out.dtype.itemsize
-        out.ptr = pointer if isinstance(pointer, ctypes.c_void_p) else ctypes.c_void_p(int(pointer))
+        out.ptr = pointer(address)
         out.owned = False
         return out
 
@@ -278,10 +288,12 @@ class DeviceArray:
         check(lib().ds_memcpy_h2d(out.ptr, pointer(array), array.nbytes, device), "ds_memcpy_h2d")
         return out
 
-    def to_host(self):
+    def to_host(self, count=None):
+        """The whole array, or only its first `count` elements along the leading axis."""
         import numpy as np
-        out = np.empty(self.shape, dtype=self.dtype)
-        check(lib().ds_memcpy_d2h(pointer(out), self.ptr, self.nbytes, self.device), "ds_memcpy_d2h")
+        out = np.empty(self.shape if count is None else (int(count),) + self.shape[1:], dtype=self.dtype)
+        if out.nbytes:
+            check(lib().ds_memcpy_d2h(pointer(out), self.ptr, out.nbytes, self.device), "ds_memcpy_d2h")
         return out
 
     def free(self):
@@ -304,10 +316,10 @@ class Timer:
         check(lib().ds_timer_create(device, ctypes.byref(self.handle)), "ds_timer_create")
 
     def start(self, stream=None):
-        check(lib().ds_timer_start(self.handle, ctypes.c_void_p(stream or 0)), "ds_timer_start")
+        check(lib().ds_timer_start(self.handle, pointer(stream)), "ds_timer_start")
 
     def stop(self, stream=None):
-        check(lib().ds_timer_stop(self.handle, ctypes.c_void_p(stream or 0)), "ds_timer_stop")
+        check(lib().ds_timer_stop(self.handle, pointer(stream)), "ds_timer_stop")
 
     def elapsed_ms(self):
         ms = ctypes.c_float(0)

@@ -322,7 +322,7 @@ class RcclCommunicator:
             out = _lib.DeviceArray((self.world_size * send.shape[0],) + tuple(send.shape[1:]), send.dtype, self.device)
         count = int(np.prod(send.shape, dtype=np.int64))
         self._check(self.rccl.ncclAllGather(send.ptr, out.ptr, count, _NCCL_TYPES[send.dtype], self.comm,
-                                            ctypes.c_void_p(stream or 0)), "ncclAllGather")
+                                            _lib.pointer(stream)), "ncclAllGather")
         return out
 
     def close(self):
@@ -363,11 +363,7 @@ class RowGather:
             return np.concatenate([gathered[r * self.longest:r * self.longest + size]
                                    for r, size in enumerate(self.sizes)])
         lib, row_bytes = _lib.lib(), self.k * 4
-        if isinstance(local_rows, _lib.DeviceArray):
-            pointer = local_rows.ptr
-        else:
-            pointer = local_rows if isinstance(local_rows, ctypes.c_void_p) else ctypes.c_void_p(int(local_rows))
-        stream_pointer = ctypes.c_void_p(stream or 0)
+        pointer, stream_pointer = _lib.pointer(local_rows), _lib.pointer(stream)
         send = _lib.DeviceArray.view(pointer, (self.longest, self.k), np.int32, self.device)
         if not self.even:
             _lib.check(lib.ds_memcpy_d2d_async(self.padded.ptr, pointer, self.local * row_bytes, self.device,

@@ -51,10 +51,6 @@ def get_truth_words_counts(title, words_counter):
     return out
 
 
-def _optional_pointer(array):
-    return ctypes.c_void_p(array.ctypes.data) if array is not None else ctypes.c_void_p(0)
-
-
 def encode_collection(flat, offsets, code_of=None, stride=MAX_CHARACTERS_ALLOWED_IN_THE_TITLE):
     """encode_title (feature_engineering.py:298-307) for a whole collection in one native, threaded call
     (ds_encode_titles): titles = flat[offsets[i]:offsets[i + 1]] (bytes), code_of = uint8[256] character -> code table (None:
@@ -64,9 +60,9 @@ def encode_collection(flat, offsets, code_of=None, stride=MAX_CHARACTERS_ALLOWED
     lengths = np.empty(count, dtype=np.uint8)
     flat = np.ascontiguousarray(flat, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    _lib.check(_lib.lib().ds_encode_titles(_optional_pointer(flat), _optional_pointer(offsets), count,
-                                           _optional_pointer(code_of), stride, _optional_pointer(enc),
-                                           _optional_pointer(lengths)), "ds_encode_titles")
+    _lib.check(_lib.lib().ds_encode_titles(_lib.pointer(flat), _lib.pointer(offsets), count,
+                                           _lib.pointer(code_of), stride, _lib.pointer(enc),
+                                           _lib.pointer(lengths)), "ds_encode_titles")
     return enc, lengths
 
 
@@ -80,8 +76,8 @@ def truth_word_counts(flat, offsets, separators=(SPACE_CODE,)):
     table[list(separators)] = 1
     flat = np.ascontiguousarray(flat, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    _lib.check(_lib.lib().ds_truth_word_counts(_optional_pointer(flat), _optional_pointer(offsets), count,
-                                               _optional_pointer(table), _optional_pointer(out)), "ds_truth_word_counts")
+    _lib.check(_lib.lib().ds_truth_word_counts(_lib.pointer(flat), _lib.pointer(offsets), count,
+                                               _lib.pointer(table), _lib.pointer(out)), "ds_truth_word_counts")
     return out
 
 
@@ -142,9 +138,8 @@ class TitleTable:
         self.n, self.stride = self.enc.shape
         self.device = device
         self.handle = ctypes.c_void_p()
-        counts_ptr = ctypes.c_void_p(0) if self.word_counts is None else _lib.pointer(self.word_counts)
         _lib.check(_lib.lib().ds_titles_create(_lib.pointer(self.enc), self.stride, _lib.pointer(self.lengths),
-                                               counts_ptr, self.n, device, ctypes.byref(self.handle)),
+                                               _lib.pointer(self.word_counts), self.n, device, ctypes.byref(self.handle)),
                    "ds_titles_create")
 
     def option(self, name, value):
@@ -229,5 +224,5 @@ def exact_matches(truth, queries, n_queries=None):
     n_queries = queries.n if n_queries is None else int(n_queries)
     out = np.empty(n_queries, dtype=np.int32)
     _lib.check(_lib.lib().ds_exact_matches(truth.handle, queries.handle, n_queries,
-                                           _lib.pointer(out) if n_queries else ctypes.c_void_p(0)), "ds_exact_matches")
+                                           _lib.pointer(out if n_queries else None)), "ds_exact_matches")
     return out

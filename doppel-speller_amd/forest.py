@@ -15,10 +15,6 @@ import numpy as np
 from . import _lib
 
 
-def _ptr(array):
-    return array.ctypes.data_as(ctypes.c_void_p)
-
-
 class ForestModel:
     def __init__(self, feature, threshold, yes, no, missing, tree_offsets, n_features, base_margin=0.0, device=0):
         self.arrays = dict(feature=np.ascontiguousarray(feature, dtype=np.int32),
@@ -32,8 +28,8 @@ class ForestModel:
         self.device = device
         self.handle = ctypes.c_void_p()
         a = self.arrays
-        _lib.check(_lib.lib().ds_forest_create(_ptr(a["feature"]), _ptr(a["threshold"]), _ptr(a["yes"]), _ptr(a["no"]),
-                                               _ptr(a["missing"]), _ptr(a["tree_offsets"]), self.n_trees,
+        _lib.check(_lib.lib().ds_forest_create(_lib.pointer(a["feature"]), _lib.pointer(a["threshold"]), _lib.pointer(a["yes"]), _lib.pointer(a["no"]),
+                                               _lib.pointer(a["missing"]), _lib.pointer(a["tree_offsets"]), self.n_trees,
                                                self.n_features, ctypes.c_float(a["base_margin"]), device,
                                                ctypes.byref(self.handle)), "ds_forest_create")
 
@@ -119,16 +115,15 @@ class ForestModel:
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         assert rows.ndim == 2 and rows.shape[1] == self.n_features
         out = np.empty(rows.shape[0], dtype=np.float32)
-        null = ctypes.c_void_p(0)
-        _lib.check(_lib.lib().ds_forest_predict(self.handle, _ptr(rows), rows.shape[0],
-                                                _ptr(out) if output_margin else null,
-                                                null if output_margin else _ptr(out)), "ds_forest_predict")
+        _lib.check(_lib.lib().ds_forest_predict(self.handle, _lib.pointer(rows), rows.shape[0],
+                                                _lib.pointer(out if output_margin else None),
+                                                _lib.pointer(None if output_margin else out)), "ds_forest_predict")
         return out
 
     def predict_device(self, d_rows, n, d_margins=None, d_probabilities=None, stream=None):
-        as_ptr = lambda x: ctypes.c_void_p(0) if x is None else (x if isinstance(x, ctypes.c_void_p) else ctypes.c_void_p(int(x)))
-        _lib.check(_lib.lib().ds_forest_predict_device(self.handle, as_ptr(d_rows), n, as_ptr(d_margins),
-                                                       as_ptr(d_probabilities), ctypes.c_void_p(stream or 0)),
+        pointer = _lib.pointer
+        _lib.check(_lib.lib().ds_forest_predict_device(self.handle, pointer(d_rows), n, pointer(d_margins),
+                                                       pointer(d_probabilities), pointer(stream)),
                    "ds_forest_predict_device")
 
     def close(self):

@@ -87,15 +87,15 @@ class TruthIndex:
         return out
 
     def top_k_device(self, d_q_rowptr, d_q_cols, d_q_maxint, n_queries, k, d_out_rows, stream=None):
-        """Enqueue on `stream` with every operand already in HBM (raw device pointers as ints / c_void_p)."""
-        as_ptr = lambda x: x if isinstance(x, ctypes.c_void_p) else ctypes.c_void_p(int(x))
+        """Enqueue on `stream` with every operand already in HBM (DeviceArray, or raw device pointers as ints / c_void_p)."""
+        pointer = _lib.pointer
         _lib.check(_lib.lib().ds_jaccard_topk_device(
-            self.handle, as_ptr(d_q_rowptr), as_ptr(d_q_cols), as_ptr(d_q_maxint), n_queries, k, as_ptr(d_out_rows),
-            ctypes.c_void_p(stream or 0)), "ds_jaccard_topk_device")
+            self.handle, pointer(d_q_rowptr), pointer(d_q_cols), pointer(d_q_maxint), n_queries, k, pointer(d_out_rows),
+            pointer(stream)), "ds_jaccard_topk_device")
 
     def sync(self, stream=None):
         stats = (ctypes.c_int64 * 32)()
-        _lib.check(_lib.lib().ds_jaccard_sync(self.handle, ctypes.c_void_p(stream or 0), stats), "ds_jaccard_sync")
+        _lib.check(_lib.lib().ds_jaccard_sync(self.handle, _lib.pointer(stream), stats), "ds_jaccard_sync")
         names = ("setup", "list_pointers", "scatter_dense", "scan_dense", "select", "exact", "scatter_sparse",
                  "collect_sparse")
         return {"dense_queries": stats[0], "error_queries": stats[1], "exact_candidates": stats[2],
@@ -112,7 +112,7 @@ class TruthIndex:
     def status(self, n_queries, stream=None):
         """int32[n_queries] of the last call: 0 fast kernel, 1 literal kernel, 2 fewer than k rows, 3 bad column."""
         out = np.empty(n_queries, dtype=np.int32)
-        _lib.check(_lib.lib().ds_jaccard_status(self.handle, ctypes.c_void_p(stream or 0), _lib.pointer(out),
+        _lib.check(_lib.lib().ds_jaccard_status(self.handle, _lib.pointer(stream), _lib.pointer(out),
                                                 n_queries), "ds_jaccard_status")
         return out
 
@@ -126,10 +126,6 @@ class TruthIndex:
             self.close()
         except Exception:
             pass
-
-
-def _ptr(array):
-    return array.ctypes.data_as(ctypes.c_void_p)
 
 
 class NativeProblem:
@@ -158,8 +154,8 @@ class NativeProblem:
         t_offsets = np.ascontiguousarray(t_offsets, dtype=np.int64)
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64)
         self.handle = ctypes.c_void_p()
-        _lib.check(_lib.lib().ds_problem_create(_ptr(t_chars), _ptr(t_offsets), t_offsets.shape[0] - 1, _ptr(q_chars),
-                                                _ptr(q_offsets), q_offsets.shape[0] - 1, n_gram,
+        _lib.check(_lib.lib().ds_problem_create(_lib.pointer(t_chars), _lib.pointer(t_offsets), t_offsets.shape[0] - 1, _lib.pointer(q_chars),
+                                                _lib.pointer(q_offsets), q_offsets.shape[0] - 1, n_gram,
                                                 ctypes.byref(self.handle)), "ds_problem_create")
         info = (ctypes.c_int64 * 8)()
         _lib.check(_lib.lib().ds_problem_info(self.handle, info), "ds_problem_info")

@@ -3,148 +3,175 @@
 Mirrors the two hot loops of Prediction.generate_test_predictions (predict.py:126-127 and :215-219) without the
 host round trip between them: the top-k rows written by the Jaccard kernels are consumed in HBM by the feature kernel
 (pair i = (query i // k, truth row rows[i])).  Inputs are uploaded once; `step()` only enqueues kernels.
+
+This class is the one owner of the device stage sequence: bench.py and the tests build it from a synthetic workload,
+Prediction builds it with `over` on its own truth side and loads one chunk of queries at a time.
 """
 import ctypes
 
 import numpy as np
 
 from . import _lib
+from .distributed import slice_queries
 from .feature_engineering import FEATURES_COUNT, LEVENSHTEIN_RATIO_THRESHOLD, SORT_KEY, SPACE_CODE, TitleTable
+from .match_maker import TruthIndex
 
 PREDICTION_PROBABILITY_THRESHOLD = 0.9  # settings.py:76
-from .match_maker import TruthIndex
+# device bytes per query and candidate: features (66 float32), prediction, top-k row, ratio, pair (q, t)
+BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
 
 
 class CandidatePipeline:
     def __init__(self, workload, k, device=0, q_begin=0, q_end=None, rows_ptr=None):
         """workload: an object with the fields of synth.make_workload.  Queries [q_begin, q_end) are this GPU's shard.
         rows_ptr: optional device pointer of an int32[q, k] buffer owned by the caller; allocated here when omitted."""
-        from .distributed import slice_queries
-        self.k = k
-        self.device = device
         q_end = workload.n_queries if q_end is None else q_end
-        self.n_queries = q_end - q_begin
-        self.n_truth = workload.n_truth
-        self.index = TruthIndex(workload.rowptr, workload.truth_idx, workload.idf32, workload.sums32, device)
-        self.truth_titles = TitleTable(workload.t_enc, workload.t_len, workload.t_counts, device)
-        self.query_titles = TitleTable(workload.q_enc[q_begin:q_end], workload.q_len[q_begin:q_end], None, device)
-        rowptr, cols, maxint = slice_queries(workload.q_rowptr, workload.q_cols, workload.q_maxint, q_begin, q_end)
-        self.d_rowptr = _lib.DeviceArray.from_host(rowptr, device)
-        self.d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), device)
-        self.d_maxint = _lib.DeviceArray.from_host(maxint, device)
+        self._setup(TruthIndex(workload.rowptr, workload.truth_idx, workload.idf32, workload.sums32, device),
+                    TitleTable(workload.t_enc, workload.t_len, workload.t_counts, device),
+                    TitleTable(workload.q_enc[q_begin:q_end], workload.q_len[q_begin:q_end], None, device),
+                    k, q_end - q_begin, device, rows_ptr)
+        self.load_queries(*slice_queries(workload.q_rowptr, workload.q_cols, workload.q_maxint, q_begin, q_end), 0)
+
+    @classmethod
+    def over(cls, index, truth_titles, query_titles, k, capacity, device=0):
+        """A pipeline on a truth index and title tables owned by the caller (shared, never closed here), with the
+        buffers of every stage allocated now for `capacity` queries; `load_queries` loads each chunk."""
+        out = cls.__new__(cls)
+        out._setup(index, truth_titles, query_titles, k, capacity, device, None)
+        out._allocate_stages()
+        return out
+
+    def _setup(self, index, truth_titles, query_titles, k, capacity, device, rows_ptr):
+        self.index, self.truth_titles, self.query_titles = index, truth_titles, query_titles
+        self.k, self.capacity, self.device = k, capacity, device
+        self.n_truth = truth_titles.n
+        self.n_queries, self.q_first = capacity, 0
         self._rows = None
         if rows_ptr is None:
-            self._rows = _lib.DeviceArray((self.n_queries, k), np.int32, device)
-            rows_ptr = self._rows.ptr
-        self.rows_ptr = rows_ptr if isinstance(rows_ptr, ctypes.c_void_p) else ctypes.c_void_p(int(rows_ptr))
-        self.d_features = _lib.DeviceArray((self.n_queries * k, FEATURES_COUNT), np.float32, device)
-        self._close = None
-        self._predictions = None
-        self._pairs = None
-        self._matches = None
-        self._exact = None
+            self._rows = _lib.DeviceArray((capacity, k), np.int32, device)
+        self.rows_ptr = _lib.pointer(self._rows if rows_ptr is None else rows_ptr)
+        self.d_features = _lib.DeviceArray((capacity * k, FEATURES_COUNT), np.float32, device)
+        self._close = self._exact = self._pairs = self._predictions = self._matches = None
+
+    def _allocate_stages(self):
+        """The outputs of the stages after top-k (by `over`, or by the first of their enqueues)."""
+        if self._close is not None:
+            return
+        n, device = self.capacity, self.device
+        size = int(_lib.lib().ds_remaining_pairs_counts_size(n))
+        self._close = (_lib.DeviceArray((n, self.k), np.uint8, device), _lib.DeviceArray((n,), np.int32, device),
+                       _lib.DeviceArray.from_host(np.ascontiguousarray(SORT_KEY, dtype=np.uint8), device))
+        self._exact = _lib.DeviceArray((max(n, 1),), np.int32, device)
+        self._pairs = (_lib.DeviceArray((n * self.k,), np.int32, device),
+                       _lib.DeviceArray((n * self.k,), np.int32, device), _lib.DeviceArray((size,), np.int64, device))
+        self._predictions = _lib.DeviceArray((n * self.k,), np.float32, device)
+        self._matches = (_lib.DeviceArray((n,), np.int32, device), _lib.DeviceArray((n,), np.int32, device))
+
+    def load_queries(self, q_rowptr, q_cols, q_maxint, first, last=None):
+        """Upload the CSR rows of queries [first, last) (default: to the end) of the query table: the next chunk."""
+        last = q_rowptr.shape[0] - 1 if last is None else last
+        if not 0 <= last - first <= self.capacity:
+            raise ValueError(f"queries [{first}, {last}) do not fit the {self.capacity} the buffers hold")
+        rowptr, cols, maxint = slice_queries(q_rowptr, q_cols, q_maxint, first, last)
+        self.d_rowptr = _lib.DeviceArray.from_host(rowptr, self.device)
+        self.d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), self.device)
+        self.d_maxint = _lib.DeviceArray.from_host(maxint, self.device)
+        self.n_queries, self.q_first = last - first, first
 
     def enqueue_top_k(self, stream=None):
-        self.index.top_k_device(self.d_rowptr.ptr, self.d_cols.ptr, self.d_maxint.ptr, self.n_queries, self.k,
-                                self.rows_ptr, stream)
+        self.index.top_k_device(self.d_rowptr, self.d_cols, self.d_maxint, self.n_queries, self.k, self.rows_ptr,
+                                stream)
 
     def enqueue_features(self, stream=None):
         _lib.check(_lib.lib().ds_construct_features_indexed_device(
-            self.query_titles.handle, self.truth_titles.handle, ctypes.c_void_p(0), self.rows_ptr, 0, self.k,
-            SPACE_CODE, self.n_truth, self.n_queries * self.k, self.d_features.ptr, ctypes.c_void_p(stream or 0)),
+            self.query_titles.handle, self.truth_titles.handle, _lib.pointer(None), self.rows_ptr, self.q_first,
+            self.k, SPACE_CODE, self.n_truth, self.n_queries * self.k, self.d_features.ptr, _lib.pointer(stream)),
             "ds_construct_features_indexed_device")
 
     def enqueue_close_matches(self, stream=None, threshold=LEVENSHTEIN_RATIO_THRESHOLD):
         """Next row f-1 in the same device-resident flow (predict.py:140-183): the fuzzy ratio of every (query,
         candidate) pair and the unique best candidate per query, read from the top-k rows in HBM."""
-        if self._close is None:
-            self._close = (_lib.DeviceArray((self.n_queries, self.k), np.uint8, self.device),
-                           _lib.DeviceArray((self.n_queries,), np.int32, self.device),
-                           _lib.DeviceArray.from_host(np.ascontiguousarray(SORT_KEY, dtype=np.uint8), self.device))
+        self._allocate_stages()
         ratios, best, sort_key = self._close
         _lib.check(_lib.lib().ds_close_matches_device(
-            self.query_titles.handle, self.truth_titles.handle, self.rows_ptr, 0, self.k, self.n_queries, SPACE_CODE,
-            sort_key.ptr, int(threshold), ratios.ptr, best.ptr, ctypes.c_void_p(stream or 0)),
+            self.query_titles.handle, self.truth_titles.handle, self.rows_ptr, self.q_first, self.k, self.n_queries,
+            SPACE_CODE, sort_key.ptr, int(threshold), ratios.ptr, best.ptr, _lib.pointer(stream)),
             "ds_close_matches_device")
 
     def close_matches(self):
         """(ratios uint8[Q, k], best_row int32[Q]) of the last `enqueue_close_matches`."""
-        ratios, best, _ = self._close
-        return ratios.to_host(), best.to_host()
+        return self._close[0].to_host(self.n_queries), self.best_rows()
+
+    def best_rows(self):
+        """int32[Q]: the best row of `close_matches`, overridden by the exact match where `enqueue_exact_matches`
+        found one after it."""
+        return self._close[1].to_host(self.n_queries)
 
     def enqueue_exact_matches(self, stream=None):
         """The exact stage (predict.py:97-113): per query the last truth row with the same transformed title, or -1.
         After `enqueue_close_matches` it also overrides that step's best row wherever an exact match exists, so that
         `enqueue_remaining_pairs` drops the exact and the fuzzy matches in one pass.  The truth table's hash table is
         built by the first call."""
-        if self._exact is None:
-            self._exact = _lib.DeviceArray((max(self.n_queries, 1),), np.int32, self.device)
-        best = self._close[1].ptr if self._close is not None else ctypes.c_void_p(0)
-        _lib.check(_lib.lib().ds_exact_matches_device(self.truth_titles.handle, self.query_titles.handle, 0,
-                                                      self.n_queries, self._exact.ptr, best,
-                                                      ctypes.c_void_p(stream or 0)), "ds_exact_matches_device")
+        closed = self._close is not None
+        self._allocate_stages()
+        _lib.check(_lib.lib().ds_exact_matches_device(self.truth_titles.handle, self.query_titles.handle, self.q_first,
+                                                      self.n_queries, self._exact.ptr,
+                                                      self._close[1].ptr if closed else _lib.pointer(None),
+                                                      _lib.pointer(stream)), "ds_exact_matches_device")
 
     def exact_matches(self):
         """int32[Q]: the truth row of every query's exact match (-1: none) of the last `enqueue_exact_matches`."""
-        return self._exact.to_host()[:self.n_queries]
+        return self._exact.to_host(self.n_queries)
 
     def enqueue_remaining_pairs(self, stream=None):
         """Next row f-2 (predict.py:172-183): drop the queries the fuzzy step matched (`enqueue_close_matches` first)
-        and compact the (query row, truth row) pairs of the others, in order, on the device."""
-        if self._pairs is None:
-            size = int(_lib.lib().ds_remaining_pairs_counts_size(self.n_queries))
-            self._pairs = (_lib.DeviceArray((self.n_queries * self.k,), np.int32, self.device),
-                           _lib.DeviceArray((self.n_queries * self.k,), np.int32, self.device),
-                           _lib.DeviceArray((size,), np.int64, self.device))
+        and compact the (query row, truth row) pairs of the others, in order, on the device.  The query rows are
+        absolute rows of the query table (q_first + local row)."""
         pair_q, pair_t, counts = self._pairs
-        _lib.check(_lib.lib().ds_remaining_pairs_device(self._close[1].ptr, self.rows_ptr, self.n_queries, self.k, 0,
-                                                        pair_q.ptr, pair_t.ptr, counts.ptr,
-                                                        ctypes.c_void_p(stream or 0)), "ds_remaining_pairs_device")
+        _lib.check(_lib.lib().ds_remaining_pairs_device(self._close[1].ptr, self.rows_ptr, self.n_queries, self.k,
+                                                        self.q_first, pair_q.ptr, pair_t.ptr, counts.ptr,
+                                                        _lib.pointer(stream)), "ds_remaining_pairs_device")
 
     def remaining_counts(self, stream=None):
         """(remaining queries, pairs) of the last `enqueue_remaining_pairs` (synchronises the stream)."""
-        _lib.check(_lib.lib().ds_stream_sync(ctypes.c_void_p(stream or 0), self.device), "sync")
-        out = np.empty(2, dtype=np.int64)
-        _lib.check(_lib.lib().ds_memcpy_d2h(_lib.pointer(out), self._pairs[2].ptr, 16, self.device), "d2h")
-        return int(out[0]), int(out[1])
+        _lib.check(_lib.lib().ds_stream_sync(_lib.pointer(stream), self.device), "sync")
+        n_remaining, n_pairs = self._pairs[2].to_host(2)
+        return int(n_remaining), int(n_pairs)
 
     def remaining_pairs(self, n_pairs):
         pair_q, pair_t, _ = self._pairs
-        return pair_q.to_host()[:n_pairs], pair_t.to_host()[:n_pairs]
+        return pair_q.to_host(n_pairs), pair_t.to_host(n_pairs)
 
     def enqueue_features_remaining(self, n_pairs, stream=None):
         """construct_features on the compacted pair list only (predict.py:195-219), into the first n_pairs rows."""
         pair_q, pair_t, _ = self._pairs
         _lib.check(_lib.lib().ds_construct_features_indexed_device(
             self.query_titles.handle, self.truth_titles.handle, pair_q.ptr, pair_t.ptr, 0, self.k, SPACE_CODE,
-            self.n_truth, n_pairs, self.d_features.ptr, ctypes.c_void_p(stream or 0)),
+            self.n_truth, n_pairs, self.d_features.ptr, _lib.pointer(stream)),
             "ds_construct_features_indexed_device")
 
     def enqueue_predict(self, model, stream=None, n_pairs=None):
         """Next row f-4: the tree ensemble (predict.py:229-234) on the feature matrix resident in HBM."""
-        if self._predictions is None:
-            self._predictions = _lib.DeviceArray((self.n_queries * self.k,), np.float32, self.device)
+        self._allocate_stages()
         n_pairs = self.n_queries * self.k if n_pairs is None else n_pairs
-        model.predict_device(self.d_features.ptr, n_pairs, None, self._predictions.ptr, stream)
+        model.predict_device(self.d_features, n_pairs, None, self._predictions, stream)
 
     def enqueue_select_matches(self, n_remaining, threshold=PREDICTION_PROBABILITY_THRESHOLD, stream=None):
         """predict.py:246-252 on the predictions of the compacted pairs: per remaining query the single pair with the
         maximum prediction above the threshold."""
-        if self._matches is None:
-            self._matches = (_lib.DeviceArray((self.n_queries,), np.int32, self.device),
-                             _lib.DeviceArray((self.n_queries,), np.int32, self.device))
         pair_q, pair_t, _ = self._pairs
         _lib.check(_lib.lib().ds_select_matches_device(pair_q.ptr, pair_t.ptr, self._predictions.ptr, n_remaining, self.k,
                                                        float(threshold), self._matches[0].ptr, self._matches[1].ptr,
-                                                       ctypes.c_void_p(stream or 0)), "ds_select_matches_device")
+                                                       _lib.pointer(stream)), "ds_select_matches_device")
 
     def matches(self, n_remaining):
         """(query rows, matched truth row or -1) of the last `enqueue_select_matches`."""
-        return self._matches[0].to_host()[:n_remaining], self._matches[1].to_host()[:n_remaining]
+        return self._matches[0].to_host(n_remaining), self._matches[1].to_host(n_remaining)
 
     def predictions(self, n_pairs=None):
-        out = self._predictions.to_host()
-        return out.reshape(self.n_queries, self.k) if n_pairs is None else out[:n_pairs]
+        if n_pairs is None:
+            return self._predictions.to_host(self.n_queries * self.k).reshape(self.n_queries, self.k)
+        return self._predictions.to_host(n_pairs)
 
     def step(self, stream=None):
         self.enqueue_top_k(stream)

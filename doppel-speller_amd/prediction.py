@@ -23,17 +23,14 @@ import time
 import numpy as np
 
 from . import _lib
-from .distributed import slice_queries
-from .feature_engineering import (ALLOWED_CHARACTERS, FEATURES_COUNT, LEVENSHTEIN_RATIO_THRESHOLD, SORT_KEY, SPACE_CODE,
-                                  TitleTable, encode_collection, truth_word_counts)
+from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
+                                  truth_word_counts)
 from .match_maker import NativeProblem, TruthIndex
+from .pipeline import BYTES_PER_PAIR, PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline
 
-PREDICTION_PROBABILITY_THRESHOLD = 0.9   # settings.py:76
 TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
 N_GRAM = 3                               # settings.py:15
 STAGE_NONE, STAGE_EXACT, STAGE_CLOSE, STAGE_MODEL = 0, 1, 2, 3
-# device bytes per query and candidate of one chunk: features (66 float32), prediction, top-k row, ratio, pair (q, t)
-_BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
 
 _CODE_OF = np.zeros(256, dtype=np.uint8)      # ASCII byte -> code of encode_title (feature_engineering.py:298-307)
 _ALLOWED = np.zeros(256, dtype=bool)          # the characters a transformed title may hold (the fill '-' is not one)
@@ -203,8 +200,6 @@ class Prediction:
         enc, lengths = encode_collection(chars, offsets, _CODE_OF)
         counts = truth_word_counts(chars, offsets, separators=(ord(" "),))
         self.truth_table = TitleTable(enc, lengths, counts, device)
-        self.n_truth = len(self.truth_titles)
-        self._sort_key = _lib.DeviceArray.from_host(np.ascontiguousarray(SORT_KEY, dtype=np.uint8), device)
 
     def _transform(self, titles):
         from .text import transform_titles
@@ -221,7 +216,7 @@ class Prediction:
     def _default_chunk(self):
         free, total = ctypes.c_int64(0), ctypes.c_int64(0)
         _lib.check(_lib.lib().ds_device_memory(self.device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
-        return max(1, int(free.value // 4 // (_BYTES_PER_PAIR * self.top_n + 64)))
+        return max(1, int(free.value // 4 // (BYTES_PER_PAIR * self.top_n + 64)))
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
@@ -267,37 +262,21 @@ class Prediction:
         enc, lengths = encode_collection(chars, offsets, _CODE_OF)
         query_table = TitleTable(enc, lengths, None, self.device)
         chunk = min(n, self.chunk_queries or self._default_chunk())
-        k, device = self.top_n, self.device
-        buffers = dict(rows=_lib.DeviceArray((chunk * k,), np.int32, device),
-                       ratios=_lib.DeviceArray((chunk * k,), np.uint8, device),
-                       best=_lib.DeviceArray((chunk,), np.int32, device),
-                       exact=_lib.DeviceArray((chunk,), np.int32, device),
-                       pair_q=_lib.DeviceArray((chunk * k,), np.int32, device),
-                       pair_t=_lib.DeviceArray((chunk * k,), np.int32, device),
-                       counts=_lib.DeviceArray((int(_lib.lib().ds_remaining_pairs_counts_size(chunk)),), np.int64, device),
-                       features=_lib.DeviceArray((chunk * k, FEATURES_COUNT), np.float32, device),
-                       predictions=_lib.DeviceArray((chunk * k,), np.float32, device),
-                       match_query=_lib.DeviceArray((chunk,), np.int32, device),
-                       match_row=_lib.DeviceArray((chunk,), np.int32, device))
+        pipeline = CandidatePipeline.over(self.index, self.truth_table, query_table, self.top_n, chunk, self.device)
         timings["host_prepare"] = (time.perf_counter() - started) * 1000.0
-        events = {name: _lib.Timer(device) for name in timings if name not in ("host_prepare", "copy_back")}
+        events = {name: _lib.Timer(self.device) for name in timings if name not in ("host_prepare", "copy_back")}
         for first in range(0, n, chunk):
             last = min(n, first + chunk)
-            self._chunk(query_table, q_rowptr, q_cols, q_maxint, first, last, buffers, events, timings,
-                               match_row, stage, probability, single)
+            pipeline.load_queries(q_rowptr, q_cols, q_maxint, first, last)
+            self._chunk(pipeline, events, timings, match_row, stage, probability, single)
         title_id = np.where(match_row >= 0, self.truth_title_ids[np.maximum(match_row, 0)], TRAIN_NOT_FOUND_VALUE)
         self.timings = timings
         return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
                              "probability": probability})
 
-    def _chunk(self, query_table, q_rowptr, q_cols, q_maxint, first, last, b, events, timings, match_row, stage,
-               probability, single):
-        lib, k, n = _lib.lib(), self.top_n, last - first
-        stream = ctypes.c_void_p(0)
-        rowptr, cols, maxint = slice_queries(q_rowptr, q_cols, q_maxint, first, last)
-        d_rowptr = _lib.DeviceArray.from_host(rowptr, self.device)
-        d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), self.device)
-        d_maxint = _lib.DeviceArray.from_host(maxint, self.device)
+    def _chunk(self, pipeline, events, timings, match_row, stage, probability, single):
+        k, first, n = self.top_n, pipeline.q_first, pipeline.n_queries
+        last = first + n
 
         def timed(name, enqueue):
             events[name].start()
@@ -305,47 +284,27 @@ class Prediction:
             events[name].stop()
 
         # 1. Jaccard top-k (synchronised: ds_jaccard_sync reports errors and settles the queries it resolves late)
-        timed("top_k", lambda: self.index.top_k_device(d_rowptr.ptr, d_cols.ptr, d_maxint.ptr, n, k, b["rows"].ptr))
-        self.index.sync()
+        timed("top_k", pipeline.enqueue_top_k)
+        pipeline.sync()
         timings["top_k"] += events["top_k"].elapsed_ms()
         # 2. close matches, 3. the exact stage overrides their best row, 4. the pairs of the queries still unmatched
-        timed("close_matches", lambda: _lib.check(lib.ds_close_matches_device(
-            query_table.handle, self.truth_table.handle, b["rows"].ptr, first, k, n, SPACE_CODE, self._sort_key.ptr,
-            self.levenshtein_threshold, b["ratios"].ptr, b["best"].ptr, stream), "ds_close_matches_device"))
-        timed("exact_matches", lambda: _lib.check(lib.ds_exact_matches_device(
-            self.truth_table.handle, query_table.handle, first, n, b["exact"].ptr, b["best"].ptr, stream),
-            "ds_exact_matches_device"))
-        timed("remaining_pairs", lambda: _lib.check(lib.ds_remaining_pairs_device(
-            b["best"].ptr, b["rows"].ptr, n, k, first, b["pair_q"].ptr, b["pair_t"].ptr, b["counts"].ptr, stream),
-            "ds_remaining_pairs_device"))
-        _lib.check(lib.ds_stream_sync(stream, self.device), "sync")
-        totals = np.empty(2, dtype=np.int64)
-        _lib.check(lib.ds_memcpy_d2h(_lib.pointer(totals), b["counts"].ptr, 16, self.device), "d2h")
-        n_remaining, n_pairs = int(totals[0]), int(totals[1])
+        timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=self.levenshtein_threshold))
+        timed("exact_matches", pipeline.enqueue_exact_matches)
+        timed("remaining_pairs", pipeline.enqueue_remaining_pairs)
+        n_remaining, n_pairs = pipeline.remaining_counts()
         # 5. features of the remaining pairs, 6. the forest, 7. one match per remaining query
-        timed("features", lambda: _lib.check(lib.ds_construct_features_indexed_device(
-            query_table.handle, self.truth_table.handle, b["pair_q"].ptr, b["pair_t"].ptr, 0, k, SPACE_CODE,
-            self.n_truth, n_pairs, b["features"].ptr, stream), "ds_construct_features_indexed_device"))
-        timed("model", lambda: self.model.predict_device(b["features"].ptr, n_pairs, None, b["predictions"].ptr))
-        timed("select_matches", lambda: _lib.check(lib.ds_select_matches_device(
-            b["pair_q"].ptr, b["pair_t"].ptr, b["predictions"].ptr, n_remaining, k, self.probability_threshold,
-            b["match_query"].ptr, b["match_row"].ptr, stream), "ds_select_matches_device"))
+        timed("features", lambda: pipeline.enqueue_features_remaining(n_pairs))
+        timed("model", lambda: pipeline.enqueue_predict(self.model, n_pairs=n_pairs))
+        timed("select_matches", lambda: pipeline.enqueue_select_matches(n_remaining, self.probability_threshold))
         for name in ("close_matches", "exact_matches", "remaining_pairs", "features", "model", "select_matches"):
             timings[name] += events[name].elapsed_ms()
 
         # one copy back of the per-query results
         copy_started = time.perf_counter()
-
-        def fetch(name, count, dtype):
-            out = np.empty(count, dtype=dtype)
-            if count:
-                _lib.check(lib.ds_memcpy_d2h(_lib.pointer(out), b[name].ptr, out.nbytes, self.device), "d2h")
-            return out
-        exact = fetch("exact", n, np.int32)
-        best = fetch("best", n, np.int32)            # exact rows where they exist, else the close step's best row
-        match_query = fetch("match_query", n_remaining, np.int32)
-        model_rows = fetch("match_row", n_remaining, np.int32)
-        predictions = fetch("predictions", n_pairs, np.float32).reshape(n_remaining, k)
+        exact = pipeline.exact_matches()
+        best = pipeline.best_rows()            # exact rows where they exist, else the close step's best row
+        match_query, model_rows = pipeline.matches(n_remaining)
+        predictions = pipeline.predictions(n_pairs).reshape(n_remaining, k)
         timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
 
         close = np.where(exact >= 0, -1, best)
@@ -360,7 +319,7 @@ class Prediction:
         if single and n_remaining:
             # cli.py / predict.py:239-242: the model stage of one title takes the best candidate with no threshold,
             # the first in top-n order when several hold the maximum
-            pair_t = fetch("pair_t", n_pairs, np.int32).reshape(n_remaining, k)
+            pair_t = pipeline.remaining_pairs(n_pairs)[1].reshape(n_remaining, k)
             where = int(np.argmax(predictions[0]))
             rows[local[0]] = pair_t[0, where]
             stages[local[0]] = STAGE_MODEL

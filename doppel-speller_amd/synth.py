@@ -36,6 +36,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, MAX_CHARACTERS_ALLOWED_IN_THE_TITLE, NUMBER_OF_WORDS_FEATURES,
                                   encode_collection, truth_word_counts)  # noqa: F401 - re-exported for tests
 
@@ -152,10 +153,6 @@ def host_threads():
     return wanted if wanted >= 1 else min(32, len(os.sched_getaffinity(0)))
 
 
-def _ptr(array):
-    return ctypes.c_void_p(array.ctypes.data) if array is not None else ctypes.c_void_p(0)
-
-
 def _tables(vocabulary):
     """The distributions of the recipe as cumulative tables (the native side only searches them)."""
     # words per title: clip(1 + Poisson(2.5), 1, 20)
@@ -184,33 +181,33 @@ def _tables(vocabulary):
 
 
 def _vocabulary_arguments(tables):
-    return (_ptr(tables["word_chars"]), _ptr(tables["word_lengths"]), tables["word_chars"].shape[0], len(_SUFFIXES),
-            _ptr(tables["zipf"]), _ptr(tables["words"]), _ptr(tables["suffix"]), _ptr(tables["hapax"]),
-            _ptr(tables["shares"]), host_threads())
+    return (_lib.pointer(tables["word_chars"]), _lib.pointer(tables["word_lengths"]), tables["word_chars"].shape[0], len(_SUFFIXES),
+            _lib.pointer(tables["zipf"]), _lib.pointer(tables["words"]), _lib.pointer(tables["suffix"]), _lib.pointer(tables["hapax"]),
+            _lib.pointer(tables["shares"]), host_threads())
 
 
 def _make_titles(tables, seed, count, purpose=0):
     """`count` fresh titles of stream (seed, purpose) -> (flat codes, offsets)."""
     lengths = np.zeros(count, dtype=np.int32)
     arguments = (seed, purpose, 0, count) + _vocabulary_arguments(tables)
-    assert _generator().synth_titles(*arguments, _ptr(lengths), None, None) == 0
+    assert _generator().synth_titles(*arguments, _lib.pointer(lengths), None, None) == 0
     offsets = np.zeros(count + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
     flat = np.zeros(max(1, int(offsets[-1])), dtype=np.uint8)
-    assert _generator().synth_titles(*arguments, None, _ptr(offsets), _ptr(flat)) == 0
+    assert _generator().synth_titles(*arguments, None, _lib.pointer(offsets), _lib.pointer(flat)) == 0
     return flat[:int(offsets[-1])], offsets
 
 
 def _make_queries(tables, seed, source, t_flat, t_off):
     count = source.shape[0]
     lengths = np.zeros(count, dtype=np.int32)
-    arguments = (seed, count, _ptr(source), _ptr(t_flat), _ptr(t_off), _ptr(tables["neighbours"])) + \
+    arguments = (seed, count, _lib.pointer(source), _lib.pointer(t_flat), _lib.pointer(t_off), _lib.pointer(tables["neighbours"])) + \
         _vocabulary_arguments(tables)
-    assert _generator().synth_queries(*arguments, _ptr(lengths), None, None) == 0
+    assert _generator().synth_queries(*arguments, _lib.pointer(lengths), None, None) == 0
     offsets = np.zeros(count + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
     flat = np.zeros(max(1, int(offsets[-1])), dtype=np.uint8)
-    assert _generator().synth_queries(*arguments, None, _ptr(offsets), _ptr(flat)) == 0
+    assert _generator().synth_queries(*arguments, None, _lib.pointer(offsets), _lib.pointer(flat)) == 0
     return flat[:int(offsets[-1])], offsets
 
 

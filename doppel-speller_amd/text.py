@@ -3,7 +3,6 @@ and encodings are derived from it.  `transform_titles` is the batch form: the Un
 common.py:25-26) stays with Python's `unicodedata` and is skipped for ASCII titles, the byte work (:26-38) runs natively
 (`ds_transform_titles`, host code in libdoppel_amd.so).  The line-by-line restatement of the reference function lives
 with the tests' CPU restatements, not in the product."""
-import ctypes
 import unicodedata
 
 import numpy as np
@@ -28,7 +27,7 @@ def transform_titles(titles):
     chars = np.frombuffer(b"".join(encoded), dtype=np.uint8) if offsets[-1] else np.zeros(1, dtype=np.uint8)
     out_chars = np.empty(int(offsets[-1]) + len(encoded) * N_GRAMS + 1, dtype=np.uint8)
     out_offsets = np.empty(len(encoded) + 1, dtype=np.int64)
-    pointer = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    pointer = _lib.pointer
     _lib.check(_lib.lib().ds_transform_titles(pointer(np.ascontiguousarray(chars)), pointer(offsets), len(encoded),
                                               MAX_CHARACTERS_ALLOWED_IN_THE_TITLE, N_GRAMS, pointer(out_chars),
                                               pointer(out_offsets)), "ds_transform_titles")

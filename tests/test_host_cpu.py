@@ -83,6 +83,19 @@ def test_sequential_sums_are_left_to_right():
         assert np.float32(total) == got[i]
 
 
+def test_pointer_of_every_kind_of_argument():
+    """_lib.pointer: host arrays, NULL, device addresses and streams all become the c_void_p the C ABI takes."""
+    from doppel_speller_amd import _lib
+    array = np.arange(4, dtype=np.int32)
+    assert _lib.pointer(array).value == array.ctypes.data
+    assert _lib.pointer(None).value is None and _lib.pointer(0).value is None        # NULL / the null stream
+    address = ctypes.c_void_p(0x7f0000001000)
+    assert _lib.pointer(address) is address
+    assert _lib.pointer(0x7f0000001000).value == _lib.pointer(np.int64(0x7f0000001000)).value == 0x7f0000001000
+    view = _lib.DeviceArray.view(0x7f0000002000, (3, 2), np.float32)                  # never freed: owned elsewhere
+    assert _lib.pointer(view).value == 0x7f0000002000 and view.nbytes == 24
+
+
 def test_match_maker_host_side_matches_captured_structures(golden_match_maker, monkeypatch):
     """MatchMaker's host construction against the structures captured from the reference (no GPU needed)."""
     import pandas as pd
