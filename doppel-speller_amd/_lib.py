@@ -8,7 +8,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
-            "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip")
+            "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip",
+            "ds_train.hip")
 _lib = None
 
 
@@ -152,6 +153,12 @@ def _declare(handle):
         "ds_forest_create": [p, p, p, p, p, p, c.c_int32, c.c_int32, c.c_float, c.c_int, c.POINTER(p)],
         "ds_forest_predict": [p, p, c.c_int64, p, p],
         "ds_forest_predict_device": [p, p, c.c_int64, p, p, p],
+        "ds_trainer_create": [p, c.c_int64, c.c_int32, p, p, c.c_int32, c.c_double, c.c_double, c.c_double, c.c_double,
+                              c.c_int, c.POINTER(p)],
+        "ds_trainer_set_labels": [p, p],
+        "ds_trainer_set_eval": [p, p, p, c.c_int64],
+        "ds_trainer_step": [p, p, p, c.POINTER(c.c_int64)],
+        "ds_trainer_read": [p, p, p, p, p, p],
         "ds_malloc": [c.POINTER(p), c.c_size_t, c.c_int],
         "ds_free": [p, c.c_int],
         "ds_memcpy_h2d": [p, p, c.c_size_t, c.c_int],
@@ -174,7 +181,8 @@ def _declare(handle):
         function.restype = c.c_int
     handle.ds_remaining_pairs_counts_size.argtypes = [c.c_int64]
     handle.ds_remaining_pairs_counts_size.restype = c.c_int64
-    for name in ("ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy"):
+    for name in ("ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy",
+                 "ds_trainer_destroy"):
         function = getattr(handle, name)
         function.argtypes = [p]
         function.restype = None
@@ -189,7 +197,8 @@ EXPORTED_SYMBOLS = (
     "ds_levenshtein_ratio_batch", "ds_levenshtein_ratio", "ds_close_matches", "ds_close_matches_device", "ds_remaining_pairs_counts_size", "ds_remaining_pairs_device",
     "ds_select_matches_device", "ds_exact_matches", "ds_exact_matches_device", "ds_problem_create",
     "ds_problem_destroy", "ds_problem_info", "ds_problem_arrays", "ds_transform_titles", "ds_encode_titles", "ds_truth_word_counts", "ds_forest_create", "ds_forest_destroy",
-    "ds_forest_predict", "ds_forest_predict_device", "ds_malloc", "ds_free", "ds_memcpy_h2d", "ds_memcpy_d2h", "ds_memset",
+    "ds_forest_predict", "ds_forest_predict_device", "ds_trainer_create", "ds_trainer_destroy", "ds_trainer_set_labels",
+    "ds_trainer_set_eval", "ds_trainer_step", "ds_trainer_read", "ds_malloc", "ds_free", "ds_memcpy_h2d", "ds_memcpy_d2h", "ds_memset",
     "ds_stream_sync", "ds_memcpy_d2d_async", "ds_stream_create", "ds_stream_destroy", "ds_timer_create", "ds_timer_destroy", "ds_timer_start", "ds_timer_stop",
     "ds_timer_elapsed_ms")
 

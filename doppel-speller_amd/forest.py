@@ -110,6 +110,38 @@ class ForestModel:
         return cls(a["feature"], a["threshold"], a["yes"], a["no"], a["missing"], a["tree_offsets"], n_features,
                    a["base_margin"], device)
 
+    @classmethod
+    def from_trees(cls, trees, n_features, base_margin=0.0, device=0):
+        """One model from per-tree dicts of feature / threshold / yes / no / missing arrays (tree-relative ids)."""
+        offsets = np.zeros(len(trees) + 1, np.int64)
+        offsets[1:] = np.cumsum([tree["feature"].shape[0] for tree in trees])
+        cat = lambda key, dtype: np.concatenate([tree[key] for tree in trees]).astype(dtype) if trees else np.zeros(0, dtype)
+        return cls(cat("feature", np.int32), cat("threshold", np.float32), cat("yes", np.int32), cat("no", np.int32),
+                   cat("missing", np.int32), offsets, n_features, base_margin, device)
+
+    def save(self, path):
+        """The flat arrays in one .npz (the reference pickles its booster, train.py:134-135)."""
+        a = self.arrays
+        with open(path, "wb") as handle:
+            np.savez(handle, feature=a["feature"], threshold=a["threshold"], yes=a["yes"], no=a["no"],
+                     missing=a["missing"], tree_offsets=a["tree_offsets"],
+                     base_margin=np.float64(a["base_margin"]), n_features=np.int64(self.n_features))
+
+    @classmethod
+    def load(cls, path, device=0):
+        with np.load(path, allow_pickle=False) as saved:
+            a = {key: saved[key] for key in saved.files}
+        return cls(a["feature"], a["threshold"], a["yes"], a["no"], a["missing"], a["tree_offsets"],
+                   int(a["n_features"]), float(a["base_margin"]), device)
+
+    def feature_importance(self):
+        """float64[n_features]: the number of splits on each feature over the sum of them (train.py
+        get_xgb_feats_importance: Booster.get_fscore normalised); zeros when no tree splits."""
+        splits = self.arrays["feature"]
+        counts = np.bincount(splits[splits >= 0], minlength=self.n_features).astype(np.float64)
+        total = counts.sum()
+        return counts / total if total else counts
+
     def predict(self, rows, output_margin=False):
         """model.predict(xgb.DMatrix(rows)) for a host float32[n, n_features] matrix."""
         rows = np.ascontiguousarray(rows, dtype=np.float32)

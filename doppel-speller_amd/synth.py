@@ -364,3 +364,20 @@ def make_forest(seed=DEFAULT_SEED, n_trees=300, depth=6, n_features=66):
     return dict(feature=feature.reshape(-1), threshold=threshold.reshape(-1), yes=yes.reshape(-1), no=no.reshape(-1),
                 missing=missing.reshape(-1), tree_offsets=np.arange(n_trees + 1, dtype=np.int64) * size,
                 base_margin=0.0, n_features=n_features)
+
+
+def training_pairs(w, k=10, device=0):
+    """A labelled feature matrix from a workload, the way train.py's data is shaped: each query's top-k truth rows by
+    Jaccard similarity as candidate pairs, their construct_features rows, and label 1 where the truth row is the one
+    the query was derived from (`actual_row`).  Returns (features float32[q * k, 66], labels float32[q * k])."""
+    from .feature_engineering import SPACE_CODE, TitleTable, construct_features_indexed
+    from .match_maker import TruthIndex
+    index = TruthIndex(w.rowptr, w.truth_idx, w.idf32, w.sums32, device=device)
+    rows = index.top_k(w.q_rowptr, w.q_cols, w.q_maxint, k)
+    pair_q = np.repeat(np.arange(w.n_queries, dtype=np.int32), k)
+    pair_t = rows.reshape(-1).astype(np.int32)
+    truth = TitleTable(w.t_enc, w.t_len, w.t_counts, device=device)
+    queries = TitleTable(w.q_enc, w.q_len, device=device)
+    features = construct_features_indexed(queries, truth, pair_q, pair_t, SPACE_CODE, w.n_truth)
+    labels = (pair_t == w.actual_row[pair_q]).astype(np.float32)
+    return features, labels

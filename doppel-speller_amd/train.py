@@ -1,0 +1,266 @@
+"""The reference's train-model step (doppelspeller/train.py): an xgboost booster trained on the construct_features
+columns with the custom objective `weighted_log_loss`, early-stopped on `custom_error` of an evaluation set.
+
+ForestTrainer grows the trees on the GPU (csrc/ds_train.hip, C ABI ds_trainer_*) by histogram gradient boosting with
+depth-wise growth, the rule of xgboost's `hist` method restated in DESIGN.md ("Training"); the result is a ForestModel.
+Parity with xgboost itself is unpinned, as for the forest.  The cuts are computed here, on the host, once per matrix.
+"""
+import concurrent.futures
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .forest import ForestModel
+
+FEATURES_MAX = 96                      # ds_forest.hip kForestFeaturesMax: a trained model must load into ForestModel
+MAX_DEPTH_MAX = 8                      # ds_train.hip kTrainMaxDepth
+FALSE_POSITIVE_PENALTY_FACTOR = 5      # settings.py
+PREDICTION_PROBABILITY_THRESHOLD = 0.9  # settings.py
+
+# node states of ds_trainer_step's heap
+_ABSENT, _SPLIT, _LEAF = 0, 2, 3
+
+
+def feature_cuts(column, max_bin=256):
+    """Cut values of one float32 column: the sorted distinct non-NaN values without the smallest when there are at most
+    max_bin - 1 of them, else the distinct values of v[floor(j * n / (max_bin - 1))], j = 1 .. max_bin - 2, of the sorted
+    values v (with multiplicity) that differ from v[0].  -0.0 counts as +0.0."""
+    column = np.asarray(column, dtype=np.float32)
+    values = np.sort(column[~np.isnan(column)] + np.float32(0.0))
+    if values.shape[0] == 0:
+        return np.zeros(0, np.float32)
+    distinct_mask = np.empty(values.shape[0], bool)
+    distinct_mask[0] = True
+    np.not_equal(values[1:], values[:-1], out=distinct_mask[1:])
+    if np.count_nonzero(distinct_mask) <= max_bin - 1:
+        return values[distinct_mask][1:]
+    n = values.shape[0]
+    picks = values[(np.arange(1, max_bin - 1, dtype=np.int64) * n) // (max_bin - 1)]
+    picks = np.unique(picks)
+    return picks[picks != values[0]].astype(np.float32)
+
+
+def compute_cuts(features, max_bin=256, threads=None):
+    """(cuts float32, cut_offsets int32[n_features + 1]) of a float32[n, n_features] matrix, columns side by side on
+    `threads` host threads (numpy's sort releases the GIL); the result does not depend on the thread count."""
+    features = np.asarray(features, dtype=np.float32)
+    columns = [features[:, f] for f in range(features.shape[1])]
+    with concurrent.futures.ThreadPoolExecutor(max_workers=threads or min(16, max(1, len(columns)))) as pool:
+        per_feature = list(pool.map(lambda column: feature_cuts(column, max_bin), columns))
+    offsets = np.zeros(len(per_feature) + 1, np.int32)
+    offsets[1:] = np.cumsum([c.shape[0] for c in per_feature])
+    cuts = np.concatenate(per_feature).astype(np.float32) if per_feature else np.zeros(0, np.float32)
+    return cuts, offsets
+
+
+def _positive_int(name, value, low=1, high=None):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < low or \
+            (high is not None and value > high):
+        bound = f"in [{low}, {high}]" if high is not None else f">= {low}"
+        raise ValueError(f"{name} must be an integer {bound}, not {value!r}")
+    return int(value)
+
+
+def _real(name, value, positive=False):
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number, not {value!r}") from None
+    if not np.isfinite(value) or value < 0 or (positive and value == 0):
+        raise ValueError(f"{name} must be a finite {'positive' if positive else 'non-negative'} number, not {value!r}")
+    return value
+
+
+def _matrix_and_labels(features, target, what):
+    features = np.asarray(features)
+    if features.ndim != 2:
+        raise ValueError(f"{what} features must be a 2-D matrix, not shape {features.shape}")
+    if not (np.issubdtype(features.dtype, np.floating) or np.issubdtype(features.dtype, np.integer)):
+        raise ValueError(f"{what} features must be numbers, not {features.dtype}")
+    if features.shape[0] < 1:
+        raise ValueError(f"{what} features need at least one row")
+    if not 1 <= features.shape[1] <= FEATURES_MAX:
+        raise ValueError(f"{what} features have {features.shape[1]} columns, the model takes 1 to {FEATURES_MAX}")
+    target = np.asarray(target)
+    if target.ndim != 1 or target.shape[0] != features.shape[0]:
+        raise ValueError(f"{features.shape[0]} {what} rows but {target.reshape(-1).shape[0]} labels")
+    if target.dtype == object or not np.isin(target, (0, 1)).all():
+        raise ValueError(f"{what} labels must all be 0 or 1")
+    return np.ascontiguousarray(features, dtype=np.float32), np.ascontiguousarray(target, dtype=np.float32)
+
+
+def validate_fit(features, target, eval_features=None, eval_target=None, num_boost_round=1000,
+                 early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
+                 max_bin=256):
+    """fit's checks (no library needed) -> (features, target, eval_features, eval_target, params) as float32 arrays."""
+    features, target = _matrix_and_labels(features, target, "training")
+    if (eval_features is None) != (eval_target is None):
+        raise ValueError("eval_features and eval_target go together")
+    if eval_features is not None:
+        eval_features, eval_target = _matrix_and_labels(eval_features, eval_target, "evaluation")
+        if eval_features.shape[1] != features.shape[1]:
+            raise ValueError(f"evaluation features have {eval_features.shape[1]} columns, training features "
+                             f"{features.shape[1]}")
+    params = dict(num_boost_round=_positive_int("num_boost_round", num_boost_round),
+                  early_stopping_rounds=_positive_int("early_stopping_rounds", early_stopping_rounds),
+                  max_depth=_positive_int("max_depth", max_depth, 1, MAX_DEPTH_MAX),
+                  eta=_real("eta", eta, positive=True), min_child_weight=_real("min_child_weight", min_child_weight),
+                  reg_lambda=_real("reg_lambda", reg_lambda), beta=_real("beta", beta, positive=True),
+                  max_bin=_positive_int("max_bin", max_bin, 2, 256))
+    if params["reg_lambda"] == 0 and params["min_child_weight"] == 0:
+        raise ValueError("reg_lambda and min_child_weight cannot both be 0 (an empty child would divide by zero)")
+    return features, target, eval_features, eval_target, params
+
+
+class ForestTrainer:
+    """xgb.train(params={max_depth, eta, min_child_weight}, obj=weighted_log_loss, feval=custom_error,
+    early_stopping_rounds) on the GPU.
+
+        model = ForestTrainer().fit(features, target, eval_features, eval_target)
+
+    After fit, `best_iteration` is the round (from 0) of the first minimum of the evaluation error and `history` the
+    error of every round; the model holds the first best_iteration + 1 trees (the reference predicts with
+    ntree_limit=best_ntree_limit).  Without an evaluation set every round is kept.  The step form: begin(...), then
+    step() grows one tree and returns the round's evaluation error (None without an evaluation set)."""
+
+    def __init__(self, device=0):
+        self.device = device
+        self.handle = None
+        self.trees = []
+        self.history = []
+        self.best_iteration = None
+
+    def begin(self, features, target, eval_features=None, eval_target=None, max_depth=5, eta=0.1,
+              min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256):
+        features, target, eval_features, eval_target, params = validate_fit(
+            features, target, eval_features, eval_target, max_depth=max_depth, eta=eta,
+            min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin)
+        self.close()
+        self.params = params
+        self.n, self.n_features = features.shape
+        self.n_eval = 0 if eval_features is None else eval_features.shape[0]
+        self.cuts, self.cut_offsets = compute_cuts(features, params["max_bin"])
+        self.trees, self.history, self.best_iteration = [], [], None
+        handle = ctypes.c_void_p()
+        library = _lib.lib()
+        _lib.check(library.ds_trainer_create(_lib.pointer(features), self.n, self.n_features, _lib.pointer(self.cuts),
+                                             _lib.pointer(self.cut_offsets), params["max_depth"], params["eta"],
+                                             params["min_child_weight"], params["reg_lambda"], params["beta"],
+                                             self.device, ctypes.byref(handle)), "ds_trainer_create")
+        self.handle = handle
+        _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
+        if eval_features is not None:
+            _lib.check(library.ds_trainer_set_eval(self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
+                                                   self.n_eval), "ds_trainer_set_eval")
+        slots = (2 << params["max_depth"]) - 1
+        self._info = np.zeros((slots, 4), np.int32)
+        self._leaf = np.zeros(slots, np.float32)
+        return self
+
+    def step(self):
+        """Grow one tree; returns the evaluation error after it (None without an evaluation set)."""
+        if not self.handle:
+            raise RuntimeError("ForestTrainer.step before begin")
+        error = ctypes.c_int64(-1)
+        _lib.check(_lib.lib().ds_trainer_step(self.handle, _lib.pointer(self._info), _lib.pointer(self._leaf),
+                                              ctypes.byref(error)), "ds_trainer_step")
+        self.last_heap = (self._info.copy(), self._leaf.copy())   # ds_trainer_step's heap order, for tests
+        self.trees.append(self._tree(self._info, self._leaf))
+        value = int(error.value) if self.n_eval else None
+        self.history.append(value)
+        return value
+
+    def _tree(self, info, leaf):
+        """Heap-ordered nodes -> ForestModel arrays of one tree (breadth-first ids: children after their parent)."""
+        order, ids = [0], {0: 0}
+        for node in order:
+            if info[node, 0] == _SPLIT:
+                for child in (2 * node + 1, 2 * node + 2):
+                    ids[child] = len(order)
+                    order.append(child)
+        size = len(order)
+        tree = dict(feature=np.full(size, -1, np.int32), threshold=np.zeros(size, np.float32),
+                    yes=np.zeros(size, np.int32), no=np.zeros(size, np.int32), missing=np.zeros(size, np.int32))
+        for i, node in enumerate(order):
+            state, feature, bin_, default_left = (int(v) for v in info[node])
+            if state == _SPLIT:
+                left, right = ids[2 * node + 1], ids[2 * node + 2]
+                tree["feature"][i] = feature
+                tree["threshold"][i] = self.cuts[self.cut_offsets[feature] + bin_ - 1]   # bins < b  <=>  x < cut
+                tree["yes"][i], tree["no"][i] = left, right
+                tree["missing"][i] = left if default_left else right
+            else:
+                assert state == _LEAF, f"node {node}: state {state}"
+                tree["threshold"][i] = leaf[node]
+        return tree
+
+    def model(self, n_trees=None):
+        """ForestModel of the first n_trees trees (default: all grown so far)."""
+        trees = self.trees[:len(self.trees) if n_trees is None else n_trees]
+        return ForestModel.from_trees(trees, self.n_features, device=self.device)
+
+    def fit(self, features, target, eval_features=None, eval_target=None, num_boost_round=1000,
+            early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
+            max_bin=256):
+        rounds = validate_fit(features, target, eval_features, eval_target, num_boost_round, early_stopping_rounds,
+                              max_depth, eta, min_child_weight, reg_lambda, beta, max_bin)[4]
+        self.begin(features, target, eval_features, eval_target, max_depth, eta, min_child_weight, reg_lambda, beta,
+                   max_bin)
+        best, best_error = None, None
+        for round_ in range(rounds["num_boost_round"]):
+            error = self.step()
+            if error is None:
+                continue
+            if best_error is None or error < best_error:
+                best, best_error = round_, error
+            if round_ - best >= rounds["early_stopping_rounds"]:
+                break
+        self.best_iteration = best if best is not None else len(self.trees) - 1
+        return self.model(self.best_iteration + 1)
+
+    def _read(self, **wanted):
+        out = {name: np.empty(shape, dtype) for name, (shape, dtype) in wanted.items()}
+        p = lambda name: _lib.pointer(out.get(name))
+        _lib.check(_lib.lib().ds_trainer_read(self.handle, p("margins"), p("probabilities"), p("gradients"), p("bins"),
+                                              p("eval_margins")), "ds_trainer_read")
+        return out
+
+    def margins(self):
+        """Training margins after the trees so far (float32[n])."""
+        return self._read(margins=(self.n, np.float32))["margins"]
+
+    def eval_margins(self):
+        return self._read(eval_margins=(self.n_eval, np.float32))["eval_margins"]
+
+    def probabilities(self):
+        """The float32 probabilities the last step took its gradients at."""
+        return self._read(probabilities=(self.n, np.float32))["probabilities"]
+
+    def gradients(self):
+        """int64[n, 2]: the last step's quantized (gradient, hessian), rint(x * 2^30)."""
+        return self._read(gradients=((self.n, 2), np.int64))["gradients"]
+
+    def bins(self):
+        """uint8[n_features, n]: the device's bins (255 = missing)."""
+        return self._read(bins=((self.n_features, self.n), np.uint8))["bins"]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().ds_trainer_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def evaluation_error_matrix(model, features, target, threshold=PREDICTION_PROBABILITY_THRESHOLD):
+    """(true positives, true negatives, false positives, false negatives) of the model's predictions at `threshold`
+    (train.py:get_evaluation_error_matrix)."""
+    predicted = model.predict(np.ascontiguousarray(features, dtype=np.float32)) > threshold
+    actual = np.asarray(target).reshape(-1) != 0
+    return (int(np.count_nonzero(predicted & actual)), int(np.count_nonzero(~predicted & ~actual)),
+            int(np.count_nonzero(predicted & ~actual)), int(np.count_nonzero(~predicted & actual)))

@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""The reference's `train-model` step followed by `generate-predictions`, on the GPU and on synthetic data:
+
+    workload -> top-k candidate pairs -> construct_features -> labels from the known source row
+             -> ForestTrainer.fit (weighted log loss, early stopping on the custom error) -> save
+             -> Prediction on a second workload with other queries
+
+It prints the fraction of correct final answers of the trained model next to that of the random stand-in ensemble
+(synth.make_forest) that the other examples use.  Building the training set from raw train titles with generated
+misspellings (FeatureEngineering.generate_train_and_evaluation_data_sets) is not part of this example.
+
+    python examples/train_model.py [n_truth] [n_queries] [top_n] [model.npz]
+"""
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import doppel_speller_amd as ds  # noqa: E402
+from doppel_speller_amd import synth  # noqa: E402
+
+
+def accuracy(model, w, top_n):
+    """Fraction of the workload's queries whose final answer is right: the source title's id, or -1 for a query made
+    up from scratch."""
+    truth = synth._to_strings(w.t_flat, w.t_off)
+    queries = synth._to_strings(w.q_flat, w.q_off)
+    answer = ds.Prediction(truth, w.title_id, model, top_n=top_n).generate_test_predictions(queries)
+    expected = np.where(w.actual_row >= 0, w.title_id[np.maximum(w.actual_row, 0)], -1)
+    return float(np.mean(answer.sort_values("test_index")["title_id"].to_numpy() == expected))
+
+
+def main(n_truth=20000, n_queries=4000, top_n=10, path=None):
+    train = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
+    evaluation = synth.make_workload(n_truth, n_queries // 4, seed=11, query_seed=102)
+    held_out = synth.make_workload(n_truth, n_queries, seed=11, query_seed=103)
+
+    features, labels = synth.training_pairs(train, top_n)
+    eval_features, eval_labels = synth.training_pairs(evaluation, top_n)
+    t0 = time.perf_counter()
+    trainer = ds.ForestTrainer()
+    model = trainer.fit(features, labels, eval_features, eval_labels)
+    t1 = time.perf_counter()
+    print(f"training: {features.shape[0]} pairs ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
+          f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error {trainer.history[trainer.best_iteration]})")
+    tp, tn, fp, fn = ds.evaluation_error_matrix(model, eval_features, eval_labels)
+    print(f"evaluation pairs: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
+    top = np.argsort(-model.feature_importance())[:5]
+    print("most used features:", ", ".join(f"f{f} {model.feature_importance()[f]:.3f}" for f in top))
+
+    path = path or os.path.join(tempfile.mkdtemp(prefix="ds_model_"), "model.npz")
+    model.save(path)
+    model = ds.ForestModel.load(path)
+    print(f"saved and reloaded {path}: {model.n_trees} trees")
+
+    stand_in = synth.make_forest(n_trees=100)
+    random_model = ds.ForestModel(stand_in["feature"], stand_in["threshold"], stand_in["yes"], stand_in["no"],
+                                  stand_in["missing"], stand_in["tree_offsets"], stand_in["n_features"],
+                                  stand_in["base_margin"])
+    trained, random_ = accuracy(model, held_out, top_n), accuracy(random_model, held_out, top_n)
+    print(f"correct final answers on {n_queries} held-out queries: trained {trained:.3f}, random ensemble {random_:.3f}")
+    return trained, random_
+
+
+if __name__ == "__main__":
+    arguments = sys.argv[1:]
+    main(*[int(a) for a in arguments[:3]], *arguments[3:4])

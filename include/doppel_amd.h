@@ -42,6 +42,7 @@ typedef struct ds_titles ds_titles; /* table of encoded titles resident in HBM *
 typedef struct ds_timer ds_timer;   /* pair of HIP events */
 typedef struct ds_problem ds_problem; /* host-side product of the native index build (next row f-3) */
 typedef struct ds_forest ds_forest;   /* tree ensemble resident in HBM (next row f-4) */
+typedef struct ds_trainer ds_trainer; /* gradient-boosted tree trainer resident in HBM (train.py) */
 
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char *ds_last_error(void);
@@ -257,6 +258,31 @@ void ds_forest_destroy(ds_forest *forest);
 int ds_forest_predict(ds_forest *forest, const float *rows, int64_t n, float *margins, float *probabilities);
 int ds_forest_predict_device(ds_forest *forest, const float *d_rows, int64_t n, float *d_margins,
                              float *d_probabilities, void *stream);
+
+/* ---- training of the match model: xgb.train(obj=weighted_log_loss, feval=custom_error) (doppelspeller/train.py) ----
+ * Histogram gradient boosting, depth-wise, one tree per ds_trainer_step (DESIGN.md "Training").  features is the
+ * float32[n][n_features] training matrix (NaN = missing), copied and binned on the device at create time: cuts[
+ * cut_offsets[f] .. cut_offsets[f + 1]) are feature f's strictly ascending cut values (at most 254 each), bin(x) = the
+ * number of cuts <= x.  Gradients of the weighted log loss with beta; eta, min_child_weight and reg_lambda as in
+ * xgboost; base_score 0.5 (base margin 0).  max_depth 1..8, n_features 1..96.  Labels are 0 or 1. */
+int ds_trainer_create(const float *features, int64_t n, int32_t n_features, const float *cuts,
+                      const int32_t *cut_offsets, int32_t max_depth, double eta, double min_child_weight,
+                      double reg_lambda, double beta, int device, ds_trainer **out);
+void ds_trainer_destroy(ds_trainer *trainer);
+int ds_trainer_set_labels(ds_trainer *trainer, const float *labels);
+/* Optional evaluation set (before the first round): binned with the training cuts, routed through every new tree;
+ * each step then reports train.py's custom error on it. */
+int ds_trainer_set_eval(ds_trainer *trainer, const float *features, const float *labels, int64_t n);
+/* Grows one tree and adds it to the training (and evaluation) margins.  The tree comes back in heap order
+ * (children of node i: 2i + 1, 2i + 2; 2^(max_depth + 1) - 1 slots): node_info[4i .. 4i + 4) = (state: 0 absent,
+ * 2 split, 3 leaf; feature; bin b: bins < b go left; missing goes left), node_leaf[i] = the leaf value.
+ * eval_error (nullable) = the custom error after this round, -1 without an evaluation set.  One host sync. */
+int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, int64_t *eval_error);
+/* Read-back for tests, every pointer nullable: training margins float[n] (base margin + leaves so far), the
+ * probabilities float[n] and quantized (gradient, hessian) int64[n][2] of the last step, the bins uint8[n_features][n]
+ * (feature-major, 255 = missing) and the evaluation margins float[n_eval]. */
+int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, int64_t *gradients, uint8_t *bins,
+                    float *eval_margins);
 
 /* ---- device memory / stream / timing plumbing (so tests and bench.py can keep inputs resident in HBM) ----------- */
 int ds_malloc(void **ptr, size_t bytes, int device);
