@@ -18,7 +18,7 @@ class DoppelError(Exception):
 
 
 def library_path():
-    # DS_LIBRARY selects another build of the same sources (tuning sweeps: scripts/sweep_variants.sh)
+    # DS_LIBRARY selects another build of the same sources (A/B measurements: scripts/build_variant.sh)
     return os.environ.get("DS_LIBRARY") or os.path.join(_HERE, "libdoppel_amd.so")
 
 

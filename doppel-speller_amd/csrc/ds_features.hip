@@ -166,30 +166,21 @@ __device__ uint8_t levenshtein_wave(WaveScratch &w, const uint8_t *a, int la, co
 // whole-title comparisons) or uses ~20 of them (one window start per lane).  Two pairs share a wavefront: every
 // instruction now serves two pairs.  Lanes 0-31 work on one pair, lanes 32-63 on another, each with its own scratch;
 // control flow may diverge between the halves (different word counts and lengths), never inside one.
-#ifndef DS_FEAT_GROUP
-#define DS_FEAT_GROUP 32   // lanes per pair: 32 (two pairs per wave) or 16 (four)
-#endif
-#ifndef DS_FEAT_WAVES
-#define DS_FEAT_WAVES 4    // waves per workgroup of ds_construct_features_kernel
-#endif
-constexpr int kGroup = DS_FEAT_GROUP, kPairsPerWave = 64 / kGroup, kFeatKernelWaves = DS_FEAT_WAVES;
-static_assert((kGroup == 16 || kGroup == 32) && kGroup > DS_WORDS, "a pair's lanes: one per truth word at least");
+constexpr int kGroup = 32;            // lanes per pair (two pairs per wave)
+constexpr int kPairsPerWave = 64 / kGroup;
+constexpr int kFeatKernelWaves = 4;   // waves per workgroup of ds_construct_features_kernel
+static_assert(kGroup > DS_WORDS, "a pair's lanes: one per truth word at least");
 
 // the ballot bits of this lane's group
 __device__ __forceinline__ uint32_t group_ballot(bool predicate, int group)
 {
-    if constexpr (kGroup == 32) return static_cast<uint32_t>(__ballot(predicate) >> (group * kGroup));
-    return static_cast<uint32_t>(__ballot(predicate) >> (group * kGroup)) & ((1u << (kGroup & 31)) - 1u);
+    return static_cast<uint32_t>(__ballot(predicate) >> (group * kGroup));
 }
 
 __device__ __forceinline__ void build_masks_g(PairScratch &w, const uint8_t *pattern, int m, int gl)
 {
     w.masks[gl] = 0ull;
     w.masks[gl + kGroup] = 0ull;
-    if constexpr (kGroup == 16) {
-        w.masks[gl + 32] = 0ull;
-        w.masks[gl + 48] = 0ull;
-    }
     wave_sync();
     for (int j = gl; j < m; j += kGroup) atomicOr(&w.masks[pattern[j]], 1ull << j);
     wave_sync();
@@ -340,21 +331,17 @@ __global__ __launch_bounds__(256) void ds_truth_records_kernel(const uint8_t *en
 
 // kRecords: the truth rows come with their TruthRecord (indexed entry points); without them (the 9-argument entry point: the
 // caller's own arrays, every pair its own copy of both titles) the kernel derives everything itself.
-#ifndef DS_FEAT_POP
-#define DS_FEAT_POP 2           // units a wave takes off the work queue at a time
-#endif
-#ifndef DS_FEAT_MIN_WAVES
-#define DS_FEAT_MIN_WAVES 5   // waves per SIMD the register allocation leaves room for (measured: 4 / 5 / 6 -> C2 1.78 / 1.70 / 1.73 ms, top-100 13.0 / 12.2 / 12.7)
-#endif
+constexpr int kFeatPop = 2;         // units a wave takes off the work queue at a time
+constexpr int kFeatMinWaves = 5;    // waves per SIMD the register allocation leaves room for (measured: 4 / 5 / 6 -> C2 1.78 / 1.70 / 1.73 ms, top-100 13.0 / 12.2 / 12.7)
 template <bool kRecords>
-__global__ __launch_bounds__(kFeatKernelWaves * 64, DS_FEAT_MIN_WAVES) void ds_construct_features_kernel(FeatureArgs a)
+__global__ __launch_bounds__(kFeatKernelWaves * 64, kFeatMinWaves) void ds_construct_features_kernel(FeatureArgs a)
 {
     __shared__ PairScratch scratch[kFeatKernelWaves * kPairsPerWave];
     __shared__ __align__(4) uint8_t ratio_table[kRatioEntries];
     for (int i = threadIdx.x; i < kRatioEntries / 4; i += kFeatKernelWaves * 64)
         reinterpret_cast<uint32_t *>(ratio_table)[i] = reinterpret_cast<const uint32_t *>(g_ratio_table)[i];
     __syncthreads();
-    const int lane = threadIdx.x & 63, group = kGroup == 32 ? lane >> 5 : lane >> 4, gl = lane & (kGroup - 1);
+    const int lane = threadIdx.x & 63, group = lane >> 5, gl = lane & (kGroup - 1);
     PairScratch &w = scratch[(threadIdx.x >> 6) * kPairsPerWave + group];
     const int64_t wave_global = static_cast<int64_t>(blockIdx.x) * kFeatKernelWaves + (threadIdx.x >> 6);
     const int64_t wave_count = static_cast<int64_t>(gridDim.x) * kFeatKernelWaves;
@@ -368,11 +355,11 @@ __global__ __launch_bounds__(kFeatKernelWaves * 64, DS_FEAT_MIN_WAVES) void ds_c
     int64_t taken_next = 0, taken_end = 0;  // the units this wave has taken off the queue and not worked through yet
     for (int64_t unit = wave_global;; unit += wave_count) {
         if (a.unit_queue != nullptr) {  // the waves pull their units from a queue: nobody idles while units are left --
-            if (taken_next >= taken_end) {  // DS_FEAT_POP at a time: every pop is an atomic on ONE address (100,000 units: the
+            if (taken_next >= taken_end) {  // kFeatPop at a time: every pop is an atomic on ONE address (100,000 units: the
                 int next = 0;               // queue itself was a third of C2's launch at one unit per pop, profiles/r05_tuning.txt)
-                if (lane == 0) next = atomicAdd(a.unit_queue, DS_FEAT_POP);
+                if (lane == 0) next = atomicAdd(a.unit_queue, kFeatPop);
                 taken_next = __builtin_amdgcn_readfirstlane(next);
-                taken_end = taken_next + DS_FEAT_POP;
+                taken_end = taken_next + kFeatPop;
             }
             unit = taken_next++;
         }
@@ -386,13 +373,9 @@ __global__ __launch_bounds__(kFeatKernelWaves * 64, DS_FEAT_MIN_WAVES) void ds_c
         const int64_t qi = a.pair_q ? a.pair_q[pair] : (a.k > 0 ? a.q_first + pair / a.k : pair);
         const int64_t ti = a.pair_t ? a.pair_t[pair] : pair;
         if (qi < 0 || qi >= a.n_q || ti < 0 || ti >= a.n_t) {  // e.g. a -1 row of a failed top-k
-            if constexpr (kGroup == 32) {
-                out[gl] = nan;
-                out[kGroup + gl] = nan;
-                if (gl < 2) out[64 + gl] = nan;
-            } else {
-                for (int i = gl; i < DS_FEATURES_COUNT; i += kGroup) out[i] = nan;
-            }
+            out[gl] = nan;
+            out[kGroup + gl] = nan;
+            if (gl < 2) out[64 + gl] = nan;
             continue;
         }
         const int lt = a.t_len[ti];                                                        // :102
@@ -564,15 +547,9 @@ __global__ __launch_bounds__(kFeatKernelWaves * 64, DS_FEAT_MIN_WAVES) void ds_c
             w.features[5] = static_cast<float>(recon_ratio);
         }
         wave_sync();
-        if constexpr (kGroup == 32) {
-            out[gl] = w.features[gl];
-            out[kGroup + gl] = w.features[kGroup + gl];
-            if (gl < 2) out[64 + gl] = w.features[64 + gl];
-        } else {
-#pragma unroll
-            for (int i = 0; i < DS_FEATURES_COUNT; i += kGroup)
-                if (i + gl < DS_FEATURES_COUNT) out[i + gl] = w.features[i + gl];
-        }
+        out[gl] = w.features[gl];
+        out[kGroup + gl] = w.features[kGroup + gl];
+        if (gl < 2) out[64 + gl] = w.features[64 + gl];
         }
     }
 }
@@ -958,7 +935,7 @@ static int launch_features(const FeatureArgs &args, int device, hipStream_t stre
     if (args.unit_queue != nullptr) {
         // as many workgroups as the device holds at once (5 per CU: registers and 31 KiB of LDS each); the queue does the rest
         DS_HIP(hipMemsetAsync(args.unit_queue, 0, sizeof(int32_t), stream));
-        grid = static_cast<int>(std::min<int64_t>((units + kFeatKernelWaves - 1) / kFeatKernelWaves, 256 * DS_FEAT_MIN_WAVES));
+        grid = static_cast<int>(std::min<int64_t>((units + kFeatKernelWaves - 1) / kFeatKernelWaves, 256 * kFeatMinWaves));
     } else {
         // Persistent waves, every one with the SAME number of units (+- 1): 32,768 waves at most, and as many fewer as keep the
         // last round full (100,000 units on 65,536 waves would take two rounds with a third of the chip idle in the second).
@@ -1001,16 +978,13 @@ static int ensure_truth_records(ds_titles *truth, uint32_t n_truth, uint8_t spac
 }
 
 // consecutive pairs one wave works through (two at a time): the k candidates of a query (k <= 16), a divisor of k between 8 and 16, or 10
-#ifndef DS_FEAT_UNIT
-#define DS_FEAT_UNIT 16
-#endif
 static int32_t pairs_per_unit(int32_t k)
 {
     if (k <= 0) return 8;
-    if (k <= DS_FEAT_UNIT) return k;
-    for (int32_t d = DS_FEAT_UNIT; d >= (DS_FEAT_UNIT + 1) / 2; --d)
+    if (k <= 16) return k;
+    for (int32_t d = 16; d >= 8; --d)
         if (k % d == 0) return d;
-    return DS_FEAT_UNIT < 10 ? DS_FEAT_UNIT : 10;
+    return 10;
 }
 
 }  // namespace ds

@@ -86,9 +86,8 @@ struct JaccardArgs {
     int32_t literal_only;       // index holds values outside the fast kernel's assumptions: hand every query over
     int32_t rows_sorted;        // the index's internal row order ascends with sums32 (ds_index_create): tiles are visited from the
                                 // query's own sums32 outwards and skipped once out of the threshold's reach
-    int32_t select_min;         // candidates that trigger a selection: max(DS_SELECT_K * k, DS_SELECT_MIN), computed by the host
+    int32_t select_min;         // candidates that trigger a selection: max(k, 16), computed by the host
     int32_t select_growth;      // next selection at select_growth / 2 times the kept candidates
-    int32_t debug;              // timing experiments only (DS_DEBUG)
     int64_t n_quads;            // posting quads in the index (bounds of `postings`)
     int64_t nnz;                // postings in the index (bounds of `row_cols`)
     float sums_min;
@@ -105,14 +104,11 @@ enum { kCtlQueue = 0, kCtlSlowCount = 1, kCtlErrors = 2, kCtlExact = 3, kCtlSele
 // whole workgroup at the tile's second barrier, so they are paid once per epoch instead of once per tile.  The tile of
 // an entry within its epoch travels in the spare high bits of its 16-bit local row (2 bits for 12288-row tiles, 1 for
 // 28672-row tiles).  Thresholds only change at epoch ends (every entry is refined under the bounds it was scored with).
-#ifndef DS_EPOCH_TILES
-#define DS_EPOCH_TILES 1
-#endif
 constexpr int kEpochTiles = DS_EPOCH_TILES;
 static_assert(kEpochTiles >= 1 && kEpochTiles <= 256 && (kEpochTiles & (kEpochTiles - 1)) == 0, "epoch: a power of two, at most 256 tiles");
 // longer epochs than the spare bits allow keep the entry's tile in a byte of its own (64 more bytes of LDS per wave)
 constexpr bool kEpochInBytes = static_cast<long long>(kTile + 2) * kEpochTiles > 65536;
-constexpr int kEpochShift = kEpochInBytes || kEpochTiles == 1 ? 16 : (kEpochTiles == 2 ? 15 : 14);
+constexpr int kEpochShift = kEpochInBytes ? 16 : 14;
 static_assert(kEpochInBytes || kTile + 2 <= (1 << kEpochShift), "a local row (or a padding row, kTile + 1) and the epoch bits share 16 bits");
 // LDS carve-up of the fast kernel (bytes)
 constexpr int kScoreWords = kTile / 2 + 16;  // two 16-bit scores per word + the trash word of the padding entries
@@ -145,10 +141,6 @@ constexpr int kOffQuadBase = kOffQuadPrefix + kMaxQueryColumns * 4;             
 // posting quads are requested) before the barrier that ends the current tile, while slower waves still read the
 // current one; a copy's start bits are zeroed one tile ahead of the ORs that fill it (no barrier of its own).
 constexpr int kDirItems = 64, kDirColumns = 64;
-#ifndef DS_MAP_AHEAD
-#define DS_MAP_AHEAD 1
-#endif
-constexpr bool kMapAhead = DS_MAP_AHEAD != 0;
 constexpr int kOffDirEntry = kOffQuadBase + kMaxQueryColumns * 4;
 constexpr int kOffDirMask = kOffDirEntry + 2 * kDirColumns * 8;
 constexpr int kOffDirCount = kOffDirMask + 2 * kDirItems * 8;
@@ -166,12 +158,6 @@ static_assert(kMaxQueryColumns == 128, "two ballots cover the query's columns");
 constexpr int kKeep = (kCandidates + kThreads - 1) / kThreads;  // candidate entries a thread holds while compacting
 constexpr int kSelectTrigger = kCandidates - kSelectSlack;
 constexpr int kWaves = kThreads / 64;
-#ifndef DS_ROUND
-#define DS_ROUND 3
-#endif
-#ifndef DS_SCAN_BATCH
-#define DS_SCAN_BATCH 1
-#endif
 constexpr float kFixedOne = 65000.f;  // fixed-point value of the query's total IDF mass (+ n <= 128 roundings < 2^16)
 constexpr int kProbeMaxK = kThreads / 4;  // threshold bootstrap from one sample per thread: k well below the sample count
 static_assert(2 * kThreads <= kCandidates - kSelectSlack, "two samples per thread fit the candidate buffer");
@@ -433,11 +419,9 @@ __device__ __forceinline__ bool in_bounds(int32_t *control, int site, int64_t in
     do {                                                                   \
         if (a.phase != nullptr && tid == 0) atomicAdd(&a.control[slot], value); \
     } while (0)
-#define DS_DEBUG_BIT(bit) ((a.debug & (bit)) != 0)
 #else
 #define DS_STAMP(slot) do { } while (0)
 #define DS_COUNT(slot, value) do { } while (0)
-#define DS_DEBUG_BIT(bit) false
 #endif
 
 // kCountBytes: the instantiation that also counts the bytes it requests from global memory (ds_index_option
@@ -676,9 +660,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
             if (mine) {
                 const uint32_t entry = wave_raw[lane];
                 const float raw = static_cast<float>(entry >> 16) * from_fixed;
-                if constexpr (kEpochTiles == 1) {
-                    t = static_cast<int32_t>(raw_tile_base + (entry & 0xffffu));
-                } else if constexpr (kEpochInBytes) {
+                if constexpr (kEpochInBytes) {
                     t = static_cast<int32_t>(raw_tile_base + static_cast<int64_t>(wave_raw_tile[lane]) * kTile + (entry & 0xffffu));
                 } else {
                     const uint32_t low = entry & 0xffffu;
@@ -736,7 +718,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
         // What the END of a sparse tile prepares for the next one (same epoch, same list-pointer block): its item directory
         // in the other copy and the posting quads of this wave's first round, requested before the barrier that ends the
         // tile -- their latency passes while the wave waits there and starts the next tile.
-        constexpr int kRound = DS_ROUND;
+        constexpr int kRound = 3;
         bool ahead = false;  // workgroup-uniform: the previous tile built this tile's item map
         // the registers of a wave's round (quads, per-posting info, fixed-point IDF, lane has a quad)
         uint2 quad[kRound], quad_info[kRound];
@@ -952,7 +934,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
             // The NEXT tile's item map is built while this tile's posting quads are on their way (below) when the next tile
             // belongs to the same epoch -- same thresholds, same essential columns -- and its list pointers are cached:
             // by ONE wave (the waves take turns), into the other copy of the directory.
-            const bool map_ahead = kMapAhead && !epoch_end && b + 1 < block_end;
+            const bool map_ahead = !epoch_end && b + 1 < block_end;
             const uint32_t tile_copy = dir_copy;
             if (!map_ahead) {
                 // Nobody builds ahead in this tile: the other copy's start bits are zeroed for whoever builds the next
@@ -1028,7 +1010,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
 #pragma unroll
             for (int u = 0; u < kRound; ++u) live[u] = false;
             const int count_before = count_at_step;
-            for (int round = (sparse && DS_DEBUG_BIT(1)) ? n_items : 0; wave + round * kWaves < n_items; round += kRound) {
+            for (int round = 0; wave + round * kWaves < n_items; round += kRound) {
                 const bool keep = sparse && wave + (round + kRound) * kWaves >= n_items;  // this wave's last round
                 kept_round = round;
                 request_round(tile_copy, use_directory, total_quads, n_items, round, keep, sparse, quad, quad_info, quad_value, live);
@@ -1044,7 +1026,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                 for (int u = 0; u < kRound; ++u) {
                     // exec-masked on purpose: unconditional atomics of idle lanes on trash words measured slower
                     // (30.3 against 29.8 ms, profiles/r02_tuning.txt)
-                    if (!live[u] || (sparse && DS_DEBUG_BIT(64))) continue;
+                    if (!live[u]) continue;
                     const uint32_t shifted = quad_value[u] << ((quad[u].x >> 11) & 16u);  // the quad's half: bit 15 of any posting
                     atomicAdd(&iscores[quad[u].x & 0x7fffu], shifted);
                     atomicAdd(&iscores[(quad[u].x >> 16) & 0x7fffu], shifted);
@@ -1107,7 +1089,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         uint32_t before[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) before[e] = 0u;
-                        if (live[u] && !DS_DEBUG_BIT(16)) {
+                        if (live[u]) {
                             // ONE exec-masked region per quad (idle lanes stay off the LDS); the padding entries of a
                             // list's last quad take from the trash word instead of being branched around one by one
 #pragma unroll
@@ -1116,7 +1098,6 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         }
 #pragma unroll
                         for (int e = 0; e < 4; ++e) taken[e] = (before[e] >> shift) & 0xffffu;
-                        if (DS_DEBUG_BIT(2)) continue;
 #ifdef DS_DIAGNOSTICS
                         if (a.phase != nullptr) {  // selectivity of the row-independent gate, counted in FRONT of it (every wave-quad)
                             int touched = 0, level1 = 0;
@@ -1149,7 +1130,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                     }
                 };
                 collect();  // the wave's last round, still in registers
-                for (int round = DS_DEBUG_BIT(1) ? n_items : 0; round < kept_round; round += kRound) {  // the earlier ones
+                for (int round = 0; round < kept_round; round += kRound) {  // the earlier ones
 #pragma unroll
                     for (int u = 0; u < kRound; ++u) {
                         const int at = wave + (round + u) * kWaves;
@@ -1279,14 +1260,14 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                     // candidates: a flood can come at any time, and with the admission floor every overflow is recoverable.)
                     constexpr bool recoverable = true;
                     // A thread reads eight rows (one uint4 of packed scores) per iteration.
-                    constexpr int kBatch = DS_SCAN_BATCH;
+                    constexpr int kBatch = 1;
                     // the trip count is workgroup-uniform (a wave keeps all its lanes through the loop: the raw-entry
                     // buffer is addressed by lane); rows beyond the tile's end are masked by `valid`
                     // no row whose fixed-point score lies below this can satisfy score + mass >= pre (mass < pre by construction
                     // once a threshold exists, so untouched rows -- score 0 -- never pass then)
                     const float any_units = uniform((here.pre - here.mass) * to_fixed_low - 1.f);
                     const uint32_t any_fixed = any_units > 0.f ? static_cast<uint32_t>(any_units < 65535.f ? any_units : 65535.f) : 0u;
-                    const int scan_steps = (DS_DEBUG_BIT(8) && b > 0) ? 0 : (r1 - r0 + kBatch * kThreads * 8 - 1) / (kBatch * kThreads * 8);
+                    const int scan_steps = (r1 - r0 + kBatch * kThreads * 8 - 1) / (kBatch * kThreads * 8);
                     for (int step = 0; step < scan_steps; ++step) {
                         const int base = r0 + tid * 8 + step * kBatch * kThreads * 8;
 #pragma unroll
@@ -1302,7 +1283,6 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                             uint32_t fx[8];
 #pragma unroll
                             for (int e = 0; e < 8; ++e) fx[e] = (words[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-                            if (DS_DEBUG_BIT(4) && b > 0) continue;
                             const float mass4[4] = {here.mass, here.mass, here.mass, here.mass};
                             // the tile's smallest sums32 stands in for the rows' own (no global read in a scan: the rows are in
                             // sums32 order, a tile's range is narrow; the refinement tests the survivors with their own)
@@ -2471,23 +2451,14 @@ int launch(ds_index *index, const int64_t *d_q_rowptr, const int32_t *d_q_cols, 
     args.k = k;
     args.sparse_quads = 4096;  // measured on C2: 2048..8192 is the flat optimum for 28672-row tiles (profiles/r01_i_tuning.txt)
     args.sums_min = index->sums_min;
-    args.debug = 0;
     args.literal_only = index->literal_only ? 1 : 0;
     args.rows_sorted = index->rows_sorted ? 1 : 0;
     // first / minimum candidate count that triggers a selection: measured with the epochs (profiles/r03_tuning.txt), C2 top-10:
     // 4k|64 19.75, 4k|32 19.63, 3k|16 19.54, 2k|32 19.59, 2k|16 19.67 ms; top-100: 4k 28.89, 3k 28.67, 2k 28.38 ms
     // Round 5, on the final kernels (profiles/r05_tuning.txt section 12): a selection as soon as k candidates are buffered and again
     // at 1.5 times what the last one kept (was 3 k and 2 times): top-100 -1.9 %, C3 shape -3.2 %, C5 shape -3.1 %, C2 +-0.
-    int select_min = 16, select_k = 1;
+    args.select_min = std::max(k, 16);
     args.select_growth = 3;
-#ifdef DS_DIAGNOSTICS   // tuning knobs of the diagnostics build only (a stray variable must not change the product's behaviour)
-    if (const char *limit = getenv("DS_SPARSE_QUADS"); limit != nullptr) args.sparse_quads = atoi(limit);
-    if (const char *v = getenv("DS_SELECT_MIN"); v != nullptr) select_min = atoi(v);
-    if (const char *v = getenv("DS_SELECT_K"); v != nullptr) select_k = atoi(v);
-    if (const char *v = getenv("DS_SELECT_GROWTH"); v != nullptr) args.select_growth = atoi(v);
-    if (const char *debug = getenv("DS_DEBUG"); debug != nullptr) args.debug = atoi(debug);
-#endif
-    args.select_min = std::max(std::max(select_k, 1) * k, std::max(select_min, k));
     args.n_quads = index->n_quads;
 
     const int grid = static_cast<int>(std::min<int64_t>(Q, int64_t(index->compute_units) * kWorkgroupsPerCu));

@@ -4,25 +4,10 @@
 // tiles) the wide geometry is 2.6 % ahead (profiles/r02_tuning.txt).
 #include "doppel_amd.h"
 #define DS_GEOMETRY_NAME narrow
-#ifndef DS_NARROW_THREADS
-#define DS_NARROW_THREADS 256
-#endif
-#ifndef DS_NARROW_WGS_PER_CU
-#define DS_NARROW_WGS_PER_CU 4
-#endif
-#ifndef DS_NARROW_CANDIDATES
-#define DS_NARROW_CANDIDATES 768  // 832 before the item directory took 1.6 KiB of LDS
-#endif
-#ifndef DS_NARROW_PTR_TILES
-#define DS_NARROW_PTR_TILES 1
-#endif
 #define DS_TILE_ROWS ds::kNarrowTileRows
-#define DS_THREADS DS_NARROW_THREADS
-#define DS_WGS_PER_CU DS_NARROW_WGS_PER_CU
-#define DS_CANDIDATES DS_NARROW_CANDIDATES
-#define DS_PTR_TILES DS_NARROW_PTR_TILES
-#ifndef DS_NARROW_EPOCH
-#define DS_NARROW_EPOCH 4  // measured on C2: 20.78 (1) / 20.47 (2) / 19.87 (4) / 19.70 (8, 800 candidates) / 19.98 ms (16); top-100: 28.96 (4) / 31.7 (8) / 34.3 ms (16)
-#endif
-#define DS_EPOCH_TILES DS_NARROW_EPOCH
+#define DS_THREADS 256
+#define DS_WGS_PER_CU 4
+#define DS_CANDIDATES 768  // 832 before the item directory took 1.6 KiB of LDS
+#define DS_PTR_TILES 1
+#define DS_EPOCH_TILES 4  // measured on C2: 20.78 (1) / 20.47 (2) / 19.87 (4) / 19.70 (8, 800 candidates) / 19.98 ms (16); top-100: 28.96 (4) / 31.7 (8) / 34.3 ms (16)
 #include "ds_jaccard_impl.inc"

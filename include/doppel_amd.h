@@ -81,8 +81,8 @@ int ds_index_image_digest(const int64_t *rowptr, const int32_t *truth_idx, const
  * "query_order" (1 / 0, default 1): the fast kernel's work queue hands out the queries with most columns first (a device-side
  * counting sort; 0 = the caller's order; answers do not depend on it).
  * The product's launches read NOTHING from the environment.  Environment read by ds_index_create / the host builds only
- * (tests and A/B measurements): DS_HOST_THREADS, DS_BUILD_LOG=1, DS_SORT_ROWS=0, DS_GEOMETRY=narrow|wide.  The kernels'
- * tuning knobs (DS_SPARSE_QUADS, DS_SELECT_*, DS_DEBUG, DS_PHASE_TIMERS / DS_PHASE_DUMP) exist in -DDS_DIAGNOSTICS builds only. */
+ * (tests and A/B measurements): DS_HOST_THREADS, DS_BUILD_LOG=1, DS_SORT_ROWS=0, DS_GEOMETRY=narrow|wide.  The phase timers
+ * (DS_PHASE_TIMERS=1 / DS_PHASE_DUMP) exist in -DDS_DIAGNOSTICS builds only. */
 int ds_index_option(ds_index *index, const char *name, int64_t value);
 /* info[0]=N info[1]=V info[2]=nnz info[3]=tile size info[4]=tiles info[5]=device bytes info[6]=padded postings
  * info[7]=bytes of the forward index (row starts uint32 while nnz < 2^32, columns uint16 while V <= 65536), part of info[5] */

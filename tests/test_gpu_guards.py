@@ -219,8 +219,8 @@ def test_candidate_overflow_inside_an_epoch_is_redone_and_counted(oracle, tied, 
         assert stats["dense_reasons"]["overflow_sparse"] + stats["dense_reasons"]["ties"] == 1
         if stats["dense_reasons"]["overflow_sparse"] == 1:
             # the give-up bound itself (`++sparse_retries > 5`): five redos are counted, the sixth overflow hands the query over.
-            # (With the admission floor the bound is a safety net: scripts/redo_bound_probe.py -- up to 10,000 distinct rows above
-            # the cut in one tile, rising or falling with the row index -- ends after 1..3 redos or as "ties"; none reaches it.)
+            # (With the admission floor the bound is a safety net: in a probe with up to 10,000 distinct rows above the cut
+            # in one tile, rising or falling with the row index, every query ended after 1..3 redos or as "ties"; none reached it.)
             assert stats["sparse_redos"] == 5, stats["sparse_redos"]
         else:   # the admission floor's check ended it first ("ties": the k best themselves tie at the pivot): fewer redos
             assert stats["sparse_redos"] <= 5, stats["sparse_redos"]

@@ -12,7 +12,7 @@ from hypothesis import HealthCheck, given, settings, strategies as st  # noqa: E
 
 pytestmark = pytest.mark.gpu
 
-# A soak run (scripts/r05/soak.sh) raises the number of examples and lets hypothesis draw fresh ones:
+# A soak run raises the number of examples and lets hypothesis draw fresh ones:
 # DS_PROPERTY_EXAMPLES=1000 python -m pytest tests/test_gpu_property.py -m gpu
 _SOAK = int(os.environ.get("DS_PROPERTY_EXAMPLES", "0"))
 
