@@ -112,6 +112,27 @@ def _pack(titles):
     return np.ascontiguousarray(chars), offsets
 
 
+def transform_or_keep(titles, transform):
+    """The titles as str, put through transform_titles when `transform`."""
+    from .text import transform_titles
+    titles = [str(t) for t in titles]
+    return transform_titles(titles) if transform else titles
+
+
+def check_characters(chars, offsets, what):
+    used = chars[:int(offsets[-1])]
+    if used.shape[0] and not _ALLOWED[used].all():
+        bad = bytes(sorted(set(used[~_ALLOWED[used]].tolist()))).decode("latin-1")
+        raise ValueError(f"{what} titles hold characters a transformed title cannot hold: {bad!r}")
+
+
+def default_chunk(device, bytes_per_query):
+    """Queries per device pass: what a quarter of the device's free HBM holds at `bytes_per_query`."""
+    free, total = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().ds_device_memory(device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
+    return max(1, int(free.value // 4 // bytes_per_query))
+
+
 def column_table(vocabulary_keys):
     """int32[2^24]: the column of every tri-gram key of the vocabulary (big-endian bytes), -1 for the others."""
     table = np.full(1 << 24, -1, dtype=np.int32)
@@ -159,6 +180,28 @@ def query_rows(chars, offsets, vocabulary_keys, idf32, idf64, n_gram=N_GRAM, col
     return q_rowptr, q_cols, q_maxint
 
 
+class TruthSide:
+    """The device-resident truth side of a set of transformed titles: the vocabulary of the native index build, the
+    Jaccard index (TruthIndex), the encoded titles with their word counts (TitleTable), and what `query_rows` needs to
+    number a query's n-grams in that vocabulary."""
+
+    def __init__(self, transformed_titles, device=0):
+        chars, offsets = _pack(transformed_titles)
+        check_characters(chars, offsets, "truth")
+        problem = NativeProblem.from_flat(chars, offsets, np.zeros(1, np.uint8), np.zeros(1, np.int64), N_GRAM)
+        arrays = problem.arrays()
+        self.vocabulary_keys, self.idf32, self.idf64 = arrays["vocabulary_keys"], arrays["idf32"], arrays["idf64"]
+        self.columns = column_table(self.vocabulary_keys)
+        self.index = TruthIndex(arrays["rowptr"], arrays["truth_idx"], arrays["idf32"], arrays["sums32"], device)
+        problem.close()
+        enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+        counts = truth_word_counts(chars, offsets, separators=(ord(" "),))
+        self.table = TitleTable(enc, lengths, counts, device)
+
+    def query_rows(self, chars, offsets):
+        return query_rows(chars, offsets, self.vocabulary_keys, self.idf32, self.idf64, columns=self.columns)
+
+
 class Prediction:
     """Prediction(truth_titles, truth_title_ids, model).generate_test_predictions(titles) -> the reference's
     final_output: a DataFrame [title_id, test_index] sorted by test_index, -1 where no stage found a match.
@@ -189,34 +232,19 @@ class Prediction:
         self.timings = {}
 
         self.truth_titles = self._transform(truth_titles)
-        chars, offsets = _pack(self.truth_titles)
-        self._check_characters(chars, offsets, "truth")
-        problem = NativeProblem.from_flat(chars, offsets, np.zeros(1, np.uint8), np.zeros(1, np.int64), N_GRAM)
-        arrays = problem.arrays()
-        self._vocabulary_keys, self._idf32, self._idf64 = arrays["vocabulary_keys"], arrays["idf32"], arrays["idf64"]
-        self._columns = column_table(self._vocabulary_keys)
-        self.index = TruthIndex(arrays["rowptr"], arrays["truth_idx"], arrays["idf32"], arrays["sums32"], device)
-        problem.close()
-        enc, lengths = encode_collection(chars, offsets, _CODE_OF)
-        counts = truth_word_counts(chars, offsets, separators=(ord(" "),))
-        self.truth_table = TitleTable(enc, lengths, counts, device)
+        truth = TruthSide(self.truth_titles, device)
+        self._vocabulary_keys, self._idf32, self._idf64 = truth.vocabulary_keys, truth.idf32, truth.idf64
+        self._columns, self.index, self.truth_table = truth.columns, truth.index, truth.table
 
     def _transform(self, titles):
-        from .text import transform_titles
-        titles = [str(t) for t in titles]
-        return transform_titles(titles) if self.transform else titles
+        return transform_or_keep(titles, self.transform)
 
     @staticmethod
     def _check_characters(chars, offsets, what):
-        used = chars[:int(offsets[-1])]
-        if used.shape[0] and not _ALLOWED[used].all():
-            bad = bytes(sorted(set(used[~_ALLOWED[used]].tolist()))).decode("latin-1")
-            raise ValueError(f"{what} titles hold characters a transformed title cannot hold: {bad!r}")
+        check_characters(chars, offsets, what)
 
     def _default_chunk(self):
-        free, total = ctypes.c_int64(0), ctypes.c_int64(0)
-        _lib.check(_lib.lib().ds_device_memory(self.device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
-        return max(1, int(free.value // 4 // (BYTES_PER_PAIR * self.top_n + 64)))
+        return default_chunk(self.device, BYTES_PER_PAIR * self.top_n + 64)
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""

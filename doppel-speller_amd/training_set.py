@@ -1,0 +1,328 @@
+"""FeatureEngineering.generate_train_and_evaluation_data_sets (doppelspeller/feature_engineering.py:172-378 and
+feature_engineering_prepare.py) on the GPU: the training and evaluation sets of the match model from raw titles.
+
+    FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
+        .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
+
+what ForestTrainer.fit takes.  The rows, in the reference's order (feature_engineering_prepare.py:25-57,
+feature_engineering.py:207-274):
+
+    kind 2 (negative)   train rows with id -1, in row order: `sample_n` of their top-n candidates, target 0;
+    kind 3 (positive)   per distinct id, in order of first appearance, the LAST train row with that id: `sample_n`
+                        candidates, the own truth row in place of the last one when the sample misses it, target 1
+                        exactly on the own row;
+    kind 1 (generated)  truth rows whose transformed title is longer than 9 characters: the misspelled title against
+                        the row itself, target 1.
+
+The device stages: Jaccard top-n of the kind 2 / 3 train rows (TruthIndex), the sample of each (ds_training_pairs_device),
+the misspellings (ds_misspell_titles), construct_features of every row into one matrix (two launches).  The split
+(_get_evaluation_indexes, feature_engineering.py:277-296) runs on the host with NumPy.  The reference's unseeded
+`random` is replaced by per-(seed, purpose, index) streams: the result is a function of the inputs
+and `seed`, and does not depend on `chunk_queries`.
+
+Differences from the reference, on purpose: `truth_title_ids` must be unique (as for Prediction); a train id that is
+not a truth id is a ValueError (the reference raises KeyError); a kind with fewer rows than its evaluation share is a
+ValueError naming the kind (the reference's np.random.choice fails there).
+"""
+import ctypes
+import time
+
+import numpy as np
+
+from . import _lib
+from .distributed import slice_queries
+from .feature_engineering import (ALLOWED_CHARACTERS, FEATURES_COUNT, MAX_CHARACTERS_ALLOWED_IN_THE_TITLE, SPACE_CODE,
+                                  TitleTable, encode_collection)
+from .prediction import (TRAIN_NOT_FOUND_VALUE, TruthSide, _CODE_OF, _pack, _validate_chunk, check_characters,
+                         default_chunk, transform_or_keep, validate_truth)
+
+KIND_GENERATED, KIND_NEGATIVE, KIND_POSITIVE = 1, 2, 3          # constants.py:46-48
+EVALUATION_FRACTIONS = {"generated": 0.05, "negative": 0.10, "positive": 0.05}   # settings.py:47-49
+GENERATED_MIN_LENGTH = 9                                          # feature_engineering.py:183-184: longer than 9
+MAX_SAMPLE = 16                                                   # the sampler keeps its swap map in registers
+_TEXT_OF = np.frombuffer(ALLOWED_CHARACTERS.encode("ascii"), dtype=np.uint8)
+
+
+def _integer(name, value, low, high=None):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < low or \
+            (high is not None and value > high):
+        bound = f" and at most {high}" if high is not None else ""
+        raise ValueError(f"{name} must be an integer of at least {low}{bound}, not {value!r}")
+    return int(value)
+
+
+def validate_training(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n, sample_n, seed,
+                      fractions):
+    """The constructor's checks (no library needed).  Returns (truth ids, train ids, truth row of every train row
+    (-1: not found))."""
+    truth_ids = validate_truth(truth_titles, truth_title_ids, top_n)
+    ids = np.asarray(train_title_ids)
+    if ids.ndim != 1 or len(train_titles) != ids.shape[0]:
+        raise ValueError(f"{len(train_titles)} train titles but {ids.reshape(-1).shape[0]} train title ids")
+    if ids.shape[0] and not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f"train title ids must be integers, not {ids.dtype}")
+    ids = ids.astype(np.int64)
+    if ids.shape[0] and ids.min() < TRAIN_NOT_FOUND_VALUE:
+        raise ValueError("train title ids must be truth title ids or -1 (not found)")
+    _integer("sample_n", sample_n, 1, MAX_SAMPLE)
+    if sample_n > top_n:
+        raise ValueError(f"sample_n = {sample_n} exceeds top_n = {top_n}")
+    _integer("seed", seed, 0, (1 << 64) - 1)
+    for name, fraction in fractions.items():
+        if isinstance(fraction, bool) or not isinstance(fraction, (int, float, np.floating, np.integer)) or \
+                not 0.0 <= float(fraction) < 1.0:
+            raise ValueError(f"the evaluation fraction of {name} rows must lie in [0, 1), not {fraction!r}")
+    order = np.argsort(truth_ids, kind="stable")
+    found = ids >= 0
+    ordered = truth_ids[order]                                # validate_truth: at least top_n >= 1 truth ids
+    at = np.minimum(np.searchsorted(ordered, ids[found]), ordered.shape[0] - 1)
+    unknown = ordered[at] != ids[found]
+    if unknown.any():
+        raise ValueError(f"{int(unknown.sum())} train title ids are not truth title ids "
+                         f"(first: {int(ids[found][unknown][0])})")
+    truth_rows = np.full(ids.shape[0], -1, dtype=np.int64)
+    truth_rows[found] = order[at]
+    return truth_ids, ids, truth_rows
+
+
+def row_plan(truth_rows):
+    """The train rows that produce training rows (feature_engineering_prepare.py:33-55 read through the dicts of
+    feature_engineering.py:207-274): (negative rows in row order, per distinct truth row in order of first appearance
+    the last train row holding it)."""
+    truth_rows = np.asarray(truth_rows, dtype=np.int64)
+    negative = np.nonzero(truth_rows < 0)[0]
+    rows = np.nonzero(truth_rows >= 0)[0]
+    values = truth_rows[rows]
+    _, first = np.unique(values, return_index=True)
+    _, last_reversed = np.unique(values[::-1], return_index=True)
+    last = rows[values.shape[0] - 1 - last_reversed]          # same (sorted) value order as `first`
+    positive = last[np.argsort(first, kind="stable")]
+    return negative.astype(np.int64), positive.astype(np.int64)
+
+
+def evaluation_split(kind, seed, fractions=None):
+    """_get_evaluation_indexes (feature_engineering.py:277-296) with np.random.default_rng(seed): int(N * fraction)
+    rows of each kind drawn without replacement (generated, negative, positive, in that order).  Returns (train rows,
+    evaluation rows), both ascending."""
+    fractions = dict(EVALUATION_FRACTIONS, **(fractions or {}))
+    kind = np.asarray(kind)
+    n = kind.shape[0]
+    rng = np.random.default_rng(seed)
+    chosen = []
+    for name, code in (("generated", KIND_GENERATED), ("negative", KIND_NEGATIVE), ("positive", KIND_POSITIVE)):
+        candidates = np.nonzero(kind == code)[0]
+        size = int(n * fractions[name])
+        if size > candidates.shape[0]:
+            raise ValueError(f"the evaluation set needs {size} {name} rows, there are {candidates.shape[0]}")
+        chosen.append(rng.choice(candidates, size, replace=False))
+    evaluation = np.unique(np.concatenate(chosen)).astype(np.int64)
+    train = np.setdiff1d(np.arange(n, dtype=np.int64), evaluation)
+    return train, evaluation
+
+
+class _DeviceTitles:
+    """A ds_titles table made on the device (ds_misspell_titles)."""
+
+    def __init__(self, handle, n):
+        self.handle, self.n = handle, n
+
+    def read(self):
+        """The rows as (uint8[n, 255] codes, uint8[n] lengths)."""
+        enc = np.empty((self.n, MAX_CHARACTERS_ALLOWED_IN_THE_TITLE), dtype=np.uint8)
+        lengths = np.empty(self.n, dtype=np.uint8)
+        _lib.check(_lib.lib().ds_titles_read(self.handle, _lib.pointer(enc), _lib.pointer(lengths)), "ds_titles_read")
+        return enc, lengths
+
+    def strings(self):
+        enc, lengths = self.read()
+        return [_TEXT_OF[enc[i, :lengths[i]]].tobytes().decode("ascii") for i in range(self.n)]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().ds_titles_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def misspell_table(source, rows, seed, device=0, stream=None):
+    """ds_misspell_titles: a device table whose row i misspells row rows[i] of the TitleTable `source` (rows None:
+    every row, in order)."""
+    n = source.n if rows is None else int(np.asarray(rows).shape[0])
+    d_rows = None if rows is None else _lib.DeviceArray.from_host(np.ascontiguousarray(rows, dtype=np.int32), device)
+    handle = ctypes.c_void_p()
+    _lib.check(_lib.lib().ds_misspell_titles(source.handle, _lib.pointer(d_rows), n, ctypes.c_uint64(seed),
+                                             _lib.pointer(stream), ctypes.byref(handle)), "ds_misspell_titles")
+    return _DeviceTitles(handle, n)
+
+
+def generate_misspelled_names(titles, seed=0, device=0):
+    """generate_misspelled_name (feature_engineering_prepare.py:165-173) of every transformed title, title i drawn from
+    the purpose-1 stream of index i: a list of str."""
+    titles = [str(t) for t in titles]
+    _integer("seed", seed, 0, (1 << 64) - 1)
+    for title in titles:
+        if not 3 <= len(title) <= MAX_CHARACTERS_ALLOWED_IN_THE_TITLE or not title.strip():
+            raise ValueError(f"not a transformed title (3..255 characters, not all spaces): {title!r}")
+    if not titles:
+        return []
+    chars, offsets = _pack(titles)
+    check_characters(chars, offsets, "the")
+    enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+    return misspell_table(TitleTable(enc, lengths, None, device), None, seed, device).strings()
+
+
+class FeatureEngineering:
+    """FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids).
+    generate_train_and_evaluation_data_sets() -> (train, train_target, evaluation, evaluation_target), float32.
+
+    Titles are raw strings put through transform_titles unless transform=False.  train_title_ids: the truth id of
+    every train title, -1 where it has none.  top_n: candidates per train title (settings.py:59, 100), sample_n: of
+    which sampled (settings.py:58, 10; at most 16).  seed: the streams of the misspellings and the samples, and the
+    NumPy generator of the split.  chunk_queries: train titles per top-n pass (default: what a quarter of the free HBM
+    holds); the result does not depend on it.  evaluation_fractions: {"generated", "negative", "positive"} -> share
+    of ALL rows drawn into the evaluation set (settings.py:47-49).
+
+    After a call: `rows` (DataFrame: kind, query_index = train row for kinds 2 / 3 and truth row for kind 1,
+    truth_row, target, evaluation), `misspelled_titles` (the queries of the kind 1 rows, in order), `features` (every
+    row's construct_features) and `timings` (milliseconds per stage)."""
+
+    def __init__(self, truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0,
+                 device=0, transform=True, chunk_queries=None, evaluation_fractions=None):
+        truth_titles, train_titles = list(truth_titles), list(train_titles)
+        unknown = set(evaluation_fractions or {}) - set(EVALUATION_FRACTIONS)
+        if unknown:
+            raise ValueError(f"unknown evaluation fractions {sorted(unknown)}; known: {sorted(EVALUATION_FRACTIONS)}")
+        self.evaluation_fractions = dict(EVALUATION_FRACTIONS, **(evaluation_fractions or {}))
+        self.truth_title_ids, self.train_title_ids, self.train_truth_rows = validate_training(
+            truth_titles, truth_title_ids, train_titles, train_title_ids, top_n, sample_n, seed,
+            self.evaluation_fractions)
+        _validate_chunk(chunk_queries)
+        self.top_n, self.sample_n, self.seed = int(top_n), int(sample_n), int(seed)
+        self.device, self.transform, self.chunk_queries = device, transform, chunk_queries
+        self._raw_truth, self._raw_train = truth_titles, train_titles
+        self._truth = None
+        self.rows = self.misspelled_titles = self.features = None
+        self.timings = {}
+
+    def generate_train_and_evaluation_data_sets(self):
+        """feature_engineering.py:321-378: (train, train_target, evaluation, evaluation_target)."""
+        import pandas as pd
+        timings = dict.fromkeys(("host_prepare", "truth_side", "top_k", "sample_pairs", "misspell", "features",
+                                 "copy_back", "split"), 0.0)
+        started = time.perf_counter()
+        device, k, sample_n = self.device, self.top_n, self.sample_n
+        if self._truth is None:
+            self.truth_titles = transform_or_keep(self._raw_truth, self.transform)
+            self.train_titles = transform_or_keep(self._raw_train, self.transform)
+            timings["host_prepare"] += (time.perf_counter() - started) * 1000.0
+            mark = time.perf_counter()
+            self._truth = TruthSide(self.truth_titles, device)
+            timings["truth_side"] = (time.perf_counter() - mark) * 1000.0
+        truth = self._truth
+        n_truth = truth.table.n
+
+        # ---- which train rows, in what order (kinds 2 and 3), and which truth rows are misspelled (kind 1)
+        mark = time.perf_counter()
+        negative, positive = row_plan(self.train_truth_rows)
+        selected = np.concatenate((negative, positive))
+        n_selected = selected.shape[0]
+        own = self.train_truth_rows[selected].astype(np.int32)
+        truth_lengths = np.array([len(t) for t in self.truth_titles], dtype=np.int64)
+        generated = np.nonzero(truth_lengths > GENERATED_MIN_LENGTH)[0].astype(np.int32)
+        n_pairs = n_selected * sample_n
+        n_rows = n_pairs + generated.shape[0]
+        query_table = None
+        if n_selected:
+            chars, offsets = _pack([self.train_titles[i] for i in selected])
+            check_characters(chars, offsets, "train")
+            q_rowptr, q_cols, q_maxint = truth.query_rows(chars, offsets)
+            enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+            query_table = TitleTable(enc, lengths, None, device)
+        d_features = _lib.DeviceArray((max(n_rows, 1), FEATURES_COUNT), np.float32, device)
+        timings["host_prepare"] += (time.perf_counter() - mark) * 1000.0
+
+        # ---- top-n and the sample of every selected train row, one chunk of rows at a time
+        timer = _lib.Timer(device)
+        pair_t = np.zeros(0, np.int32)
+        target = np.zeros(0, np.float32)
+        if n_selected:
+            chunk = min(n_selected, self.chunk_queries or default_chunk(device, 4 * k + 64))
+            d_rows = _lib.DeviceArray((chunk, k), np.int32, device)
+            d_index = _lib.DeviceArray.from_host(selected.astype(np.int64), device)
+            d_own = _lib.DeviceArray.from_host(own, device)
+            d_pair_q = _lib.DeviceArray((n_pairs,), np.int32, device)
+            d_pair_t = _lib.DeviceArray((n_pairs,), np.int32, device)
+            d_target = _lib.DeviceArray((n_pairs,), np.float32, device)
+            for first in range(0, n_selected, chunk):
+                last = min(n_selected, first + chunk)
+                rowptr, cols, maxint = slice_queries(q_rowptr, q_cols, q_maxint, first, last)
+                d_rowptr = _lib.DeviceArray.from_host(rowptr, device)
+                d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), device)
+                d_maxint = _lib.DeviceArray.from_host(maxint, device)
+                timer.start()
+                truth.index.top_k_device(d_rowptr, d_cols, d_maxint, last - first, k, d_rows)
+                timer.stop()
+                truth.index.sync()
+                timings["top_k"] += timer.elapsed_ms()
+                timer.start()
+                _lib.check(_lib.lib().ds_training_pairs_device(
+                    d_rows.ptr, last - first, k, sample_n, ctypes.c_void_p(d_index.ptr.value + 8 * first),
+                    ctypes.c_void_p(d_own.ptr.value + 4 * first), ctypes.c_uint64(self.seed), first, d_pair_q.ptr,
+                    d_pair_t.ptr, d_target.ptr, None), "ds_training_pairs_device")
+                timer.stop()
+                timings["sample_pairs"] += timer.elapsed_ms()
+
+        # ---- the misspelled truth titles, on the device
+        misspelled = None
+        if generated.shape[0]:
+            mark = time.perf_counter()
+            misspelled = misspell_table(truth.table, generated, self.seed, device)
+            timings["misspell"] = (time.perf_counter() - mark) * 1000.0
+
+        # ---- construct_features of every row into one matrix: kinds 2 and 3 against the train titles, kind 1 against
+        # the misspelled titles
+        timer.start()
+        if n_selected:
+            _lib.check(_lib.lib().ds_construct_features_indexed_device(
+                query_table.handle, truth.table.handle, d_pair_q.ptr, d_pair_t.ptr, 0, sample_n, SPACE_CODE, n_truth,
+                n_pairs, d_features.ptr, None), "ds_construct_features_indexed_device")
+        if misspelled is not None:
+            d_gen_q = _lib.DeviceArray.from_host(np.arange(generated.shape[0], dtype=np.int32), device)
+            d_gen_t = _lib.DeviceArray.from_host(generated, device)
+            _lib.check(_lib.lib().ds_construct_features_indexed_device(
+                misspelled.handle, truth.table.handle, d_gen_q.ptr, d_gen_t.ptr, 0, 1, SPACE_CODE, n_truth,
+                generated.shape[0], ctypes.c_void_p(d_features.ptr.value + n_pairs * FEATURES_COUNT * 4), None),
+                "ds_construct_features_indexed_device")
+        timer.stop()
+        timings["features"] = timer.elapsed_ms()
+
+        mark = time.perf_counter()
+        features = d_features.to_host(n_rows)
+        if n_selected:
+            pair_t, target = d_pair_t.to_host(), d_target.to_host()
+        self.misspelled_titles = misspelled.strings() if misspelled is not None else []
+        timings["copy_back"] = (time.perf_counter() - mark) * 1000.0
+
+        # ---- rows and the split
+        mark = time.perf_counter()
+        kind = np.concatenate((np.full(negative.shape[0] * sample_n, KIND_NEGATIVE, np.uint8),
+                               np.full(positive.shape[0] * sample_n, KIND_POSITIVE, np.uint8),
+                               np.full(generated.shape[0], KIND_GENERATED, np.uint8)))
+        query_index = np.concatenate((np.repeat(selected, sample_n), generated.astype(np.int64)))
+        truth_row = np.concatenate((pair_t.astype(np.int64), generated.astype(np.int64)))
+        target = np.concatenate((target, np.ones(generated.shape[0], np.float32)))
+        train_rows, evaluation_rows = evaluation_split(kind, self.seed, self.evaluation_fractions)
+        evaluation = np.zeros(n_rows, dtype=bool)
+        evaluation[evaluation_rows] = True
+        self.rows = pd.DataFrame({"kind": kind, "query_index": query_index, "truth_row": truth_row, "target": target,
+                                  "evaluation": evaluation})
+        self.features = features
+        out = (features[train_rows], target[train_rows], features[evaluation_rows], target[evaluation_rows])
+        timings["split"] = (time.perf_counter() - mark) * 1000.0
+        self.timings = timings
+        return out

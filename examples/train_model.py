@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """The reference's `train-model` step followed by `generate-predictions`, on the GPU and on synthetic data:
 
-    workload -> top-k candidate pairs -> construct_features -> labels from the known source row
+    truth titles + train titles with their ids (-1: made up)
+             -> FeatureEngineering.generate_train_and_evaluation_data_sets (generated misspellings, top-100 candidates
+                sampled 10 per train title, construct_features, the evaluation split)
              -> ForestTrainer.fit (weighted log loss, early stopping on the custom error) -> save
              -> Prediction on a second workload with other queries
 
-It prints the fraction of correct final answers of the trained model next to that of the random stand-in ensemble
-(synth.make_forest) that the other examples use.  Building the training set from raw train titles with generated
-misspellings (FeatureEngineering.generate_train_and_evaluation_data_sets) is not part of this example.
+It prints the fraction of correct final answers of that model next to a model trained on synth.training_pairs (the
+top-k pairs of the train queries labelled with their known source row) and the random stand-in ensemble
+(synth.make_forest) that the other examples use.
 
     python examples/train_model.py [n_truth] [n_queries] [top_n] [model.npz]
+
+top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
 """
 import os
 import sys
@@ -33,21 +37,35 @@ def accuracy(model, w, top_n):
     return float(np.mean(answer.sort_values("test_index")["title_id"].to_numpy() == expected))
 
 
+def _stand_in():
+    stand_in = synth.make_forest(n_trees=100)
+    return ds.ForestModel(stand_in["feature"], stand_in["threshold"], stand_in["yes"], stand_in["no"],
+                          stand_in["missing"], stand_in["tree_offsets"], stand_in["n_features"], stand_in["base_margin"])
+
+
 def main(n_truth=20000, n_queries=4000, top_n=10, path=None):
     train = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     evaluation = synth.make_workload(n_truth, n_queries // 4, seed=11, query_seed=102)
     held_out = synth.make_workload(n_truth, n_queries, seed=11, query_seed=103)
 
-    features, labels = synth.training_pairs(train, top_n)
-    eval_features, eval_labels = synth.training_pairs(evaluation, top_n)
+    # the training set the reference's way: from the raw titles and the train titles' ids
+    truth_titles = synth._to_strings(train.t_flat, train.t_off)
+    train_titles = synth._to_strings(train.q_flat, train.q_off)
+    train_ids = np.where(train.actual_row >= 0, train.title_id[np.maximum(train.actual_row, 0)], -1)
+    fe = ds.FeatureEngineering(truth_titles, train.title_id, train_titles, train_ids)
+    features, labels, eval_features, eval_labels = fe.generate_train_and_evaluation_data_sets()
+    kinds = fe.rows["kind"].value_counts().sort_index().to_dict()
+    print(f"training set: {fe.rows.shape[0]} rows (generated / negative / positive: {kinds.get(1, 0)} / "
+          f"{kinds.get(2, 0)} / {kinds.get(3, 0)}), {eval_features.shape[0]} held out for evaluation; "
+          + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.timings.items()))
     t0 = time.perf_counter()
     trainer = ds.ForestTrainer()
     model = trainer.fit(features, labels, eval_features, eval_labels)
     t1 = time.perf_counter()
-    print(f"training: {features.shape[0]} pairs ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
+    print(f"training: {features.shape[0]} rows ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
           f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error {trainer.history[trainer.best_iteration]})")
     tp, tn, fp, fn = ds.evaluation_error_matrix(model, eval_features, eval_labels)
-    print(f"evaluation pairs: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
+    print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
     top = np.argsort(-model.feature_importance())[:5]
     print("most used features:", ", ".join(f"f{f} {model.feature_importance()[f]:.3f}" for f in top))
 
@@ -56,13 +74,15 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None):
     model = ds.ForestModel.load(path)
     print(f"saved and reloaded {path}: {model.n_trees} trees")
 
-    stand_in = synth.make_forest(n_trees=100)
-    random_model = ds.ForestModel(stand_in["feature"], stand_in["threshold"], stand_in["yes"], stand_in["no"],
-                                  stand_in["missing"], stand_in["tree_offsets"], stand_in["n_features"],
-                                  stand_in["base_margin"])
-    trained, random_ = accuracy(model, held_out, top_n), accuracy(random_model, held_out, top_n)
-    print(f"correct final answers on {n_queries} held-out queries: trained {trained:.3f}, random ensemble {random_:.3f}")
-    return trained, random_
+    # the earlier stand-in training set: the train queries' top-k pairs labelled with their source row
+    pairs, pair_labels = synth.training_pairs(train, top_n)
+    eval_pairs, eval_pair_labels = synth.training_pairs(evaluation, top_n)
+    pairs_model = ds.ForestTrainer().fit(pairs, pair_labels, eval_pairs, eval_pair_labels)
+
+    trained, from_pairs, random_ = (accuracy(m, held_out, top_n) for m in (model, pairs_model, _stand_in()))
+    print(f"correct final answers on {n_queries} held-out queries: FeatureEngineering set {trained:.3f}, "
+          f"training_pairs set {from_pairs:.3f}, random ensemble {random_:.3f}")
+    return trained, from_pairs, random_
 
 
 if __name__ == "__main__":

@@ -284,6 +284,29 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
 int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, int64_t *gradients, uint8_t *bins,
                     float *eval_margins);
 
+/* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
+ * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
+ * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
+ * (mod 2^64), the first two outputs thrown away; below(n) = the high 64 bits of x * n; randint(a, b) = a + below(b - a + 1),
+ * choice(seq) = seq[below(len)], sample(pop, k) = partial Fisher-Yates; the draws in the reference's order (DESIGN.md
+ * section 8).
+ *
+ * ds_misspell_titles: *out = a new table (stride 255, no word counts) whose row i is generate_misspelled_name
+ * (feature_engineering_prepare.py:165-173, transform_title included) of source row d_rows[i] (d_rows NULL: row i), drawn
+ * from the purpose-1 stream of that source row.  Rows of the source must be transformed titles (3..255 codes 1..37, not
+ * all spaces) and d_rows in range: DS_E_ARG otherwise.  Enqueued on `stream`, which is synchronised before returning. */
+int ds_misspell_titles(ds_titles *source, const int32_t *d_rows, int64_t n, uint64_t seed, void *stream, ds_titles **out);
+/* Copies a table back: enc[n * stride], len[n] (either may be NULL).  Synchronous. */
+int ds_titles_read(const ds_titles *titles, uint8_t *enc, uint8_t *len);
+/* get_closest_matches_per_training_row (feature_engineering_prepare.py:25-57) for n_queries train rows: d_rows[q * top_n
+ * ..) = the top_n candidates of row q in get_closest_matches order (ds_jaccard_topk_device); sample sample_n (1..16, <=
+ * top_n) of the positions with the purpose-2 stream of d_stream_index[q]; where d_own_row[q] >= 0 and the sample misses it,
+ * it replaces the last sampled candidate.  Pair p = (q_first + q) * sample_n + j: d_pair_q[p] = q_first + q, d_pair_t[p] =
+ * the truth row, d_target[p] = 1.0 where that row is d_own_row[q], else 0.  Asynchronous on `stream`. */
+int ds_training_pairs_device(const int32_t *d_rows, int64_t n_queries, int32_t top_n, int32_t sample_n,
+                             const int64_t *d_stream_index, const int32_t *d_own_row, uint64_t seed, int64_t q_first,
+                             int32_t *d_pair_q, int32_t *d_pair_t, float *d_target, void *stream);
+
 /* ---- device memory / stream / timing plumbing (so tests and bench.py can keep inputs resident in HBM) ----------- */
 int ds_malloc(void **ptr, size_t bytes, int device);
 int ds_free(void *ptr, int device);
