@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip",
-            "ds_train.hip", "ds_training.hip")
+            "ds_train.hip", "ds_training.hip", "ds_queries.hip")
 _lib = None
 
 
@@ -162,6 +162,9 @@ def _declare(handle):
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
+        "ds_prepare_titles": [p, p, c.c_int64, c.c_int32, c.c_int, p, c.POINTER(p), p],
+        "ds_query_space_create": [p, p, p, c.c_int64, c.c_int, c.POINTER(p)],
+        "ds_query_rows_device": [p, p, c.c_int64, c.c_int64, p, p, p, c.c_int64, p],
         "ds_malloc": [c.POINTER(p), c.c_size_t, c.c_int],
         "ds_free": [p, c.c_int],
         "ds_memcpy_h2d": [p, p, c.c_size_t, c.c_int],
@@ -185,7 +188,7 @@ def _declare(handle):
     handle.ds_remaining_pairs_counts_size.argtypes = [c.c_int64]
     handle.ds_remaining_pairs_counts_size.restype = c.c_int64
     for name in ("ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy",
-                 "ds_trainer_destroy"):
+                 "ds_trainer_destroy", "ds_query_space_destroy"):
         function = getattr(handle, name)
         function.argtypes = [p]
         function.restype = None
@@ -202,7 +205,8 @@ EXPORTED_SYMBOLS = (
     "ds_problem_destroy", "ds_problem_info", "ds_problem_arrays", "ds_transform_titles", "ds_encode_titles", "ds_truth_word_counts", "ds_forest_create", "ds_forest_destroy",
     "ds_forest_predict", "ds_forest_predict_device", "ds_trainer_create", "ds_trainer_destroy", "ds_trainer_set_labels",
     "ds_trainer_set_eval", "ds_trainer_step", "ds_trainer_read", "ds_misspell_titles", "ds_titles_read",
-    "ds_training_pairs_device", "ds_malloc", "ds_free", "ds_memcpy_h2d", "ds_memcpy_d2h", "ds_memset",
+    "ds_training_pairs_device", "ds_prepare_titles", "ds_query_space_create", "ds_query_space_destroy",
+    "ds_query_rows_device", "ds_malloc", "ds_free", "ds_memcpy_h2d", "ds_memcpy_d2h", "ds_memset",
     "ds_stream_sync", "ds_memcpy_d2d_async", "ds_stream_create", "ds_stream_destroy", "ds_timer_create", "ds_timer_destroy", "ds_timer_start", "ds_timer_stop",
     "ds_timer_elapsed_ms")
 

@@ -19,6 +19,7 @@ from .match_maker import TruthIndex
 PREDICTION_PROBABILITY_THRESHOLD = 0.9  # settings.py:76
 # device bytes per query and candidate: features (66 float32), prediction, top-k row, ratio, pair (q, t)
 BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
+MAX_GRAMS = 253                         # tri-grams of a 255-character title: columns of one query row at most
 
 
 class CandidatePipeline:
@@ -77,6 +78,23 @@ class CandidatePipeline:
         self.d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), self.device)
         self.d_maxint = _lib.DeviceArray.from_host(maxint, self.device)
         self.n_queries, self.q_first = last - first, first
+
+    def load_queries_device(self, space, first, last, stream=None):
+        """The CSR rows of queries [first, last) of the query table derived on the device against `space` (a
+        prediction.QuerySpace: ds_query_rows_device), into buffers allocated once for `capacity` queries."""
+        n = last - first
+        if not 0 <= n <= self.capacity:
+            raise ValueError(f"queries [{first}, {last}) do not fit the {self.capacity} the buffers hold")
+        if getattr(self, "_query_rows", None) is None:
+            self._query_rows = (_lib.DeviceArray((self.capacity + 1,), np.int64, self.device),
+                                _lib.DeviceArray((max(1, self.capacity * MAX_GRAMS),), np.int32, self.device),
+                                _lib.DeviceArray((max(1, self.capacity),), np.float64, self.device))
+        rowptr, cols, maxint = self._query_rows
+        _lib.check(_lib.lib().ds_query_rows_device(space.handle, self.query_titles.handle, first, n, rowptr.ptr, cols.ptr,
+                                                   maxint.ptr, cols.shape[0], _lib.pointer(stream)),
+                   "ds_query_rows_device")
+        self.d_rowptr, self.d_cols, self.d_maxint = rowptr, cols, maxint
+        self.n_queries, self.q_first = n, first
 
     def enqueue_top_k(self, stream=None):
         self.index.top_k_device(self.d_rowptr, self.d_cols, self.d_maxint, self.n_queries, self.k, self.rows_ptr,

@@ -19,6 +19,7 @@ Differences from the reference, on purpose:
 """
 import ctypes
 import time
+import unicodedata
 
 import numpy as np
 
@@ -26,10 +27,11 @@ from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
                                   truth_word_counts)
 from .match_maker import NativeProblem, TruthIndex
-from .pipeline import BYTES_PER_PAIR, PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline
+from .pipeline import BYTES_PER_PAIR, MAX_GRAMS, PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline
 
 TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
 N_GRAM = 3                               # settings.py:15
+PREPARE_QUERIES = ("device", "host")
 STAGE_NONE, STAGE_EXACT, STAGE_CLOSE, STAGE_MODEL = 0, 1, 2, 3
 
 _CODE_OF = np.zeros(256, dtype=np.uint8)      # ASCII byte -> code of encode_title (feature_engineering.py:298-307)
@@ -122,8 +124,108 @@ def transform_or_keep(titles, transform):
 def check_characters(chars, offsets, what):
     used = chars[:int(offsets[-1])]
     if used.shape[0] and not _ALLOWED[used].all():
-        bad = bytes(sorted(set(used[~_ALLOWED[used]].tolist()))).decode("latin-1")
-        raise ValueError(f"{what} titles hold characters a transformed title cannot hold: {bad!r}")
+        _refuse_characters(sorted(set(used[~_ALLOWED[used]].tolist())), what)
+
+
+def _refuse_characters(bad, what):
+    bad = bytes(bad).decode("latin-1")
+    raise ValueError(f"{what} titles hold characters a transformed title cannot hold: {bad!r}")
+
+
+def _validate_prepare(prepare_queries):
+    if not isinstance(prepare_queries, str) or prepare_queries not in PREPARE_QUERIES:
+        raise ValueError(f"prepare_queries must be one of {PREPARE_QUERIES}, not {prepare_queries!r}")
+
+
+class DeviceTitles:
+    """The query table made on the device by `prepare_queries` (ds_prepare_titles): encode_title rows of the
+    transformed titles, stride 255, no word counts.  `.handle` / `.n` as a TitleTable."""
+
+    def __init__(self, handle, n, device):
+        self.handle, self.n, self.stride, self.device = handle, n, 255, device
+        self.prepare_ms = 0.0
+
+    def transformed(self, rows):
+        """The transformed titles of the given rows as str, read back from the device (ds_titles_read)."""
+        enc = np.empty((self.n, self.stride), dtype=np.uint8)
+        lengths = np.empty(self.n, dtype=np.uint8)
+        _lib.check(_lib.lib().ds_titles_read(self.handle, _lib.pointer(enc), _lib.pointer(lengths)), "ds_titles_read")
+        return [ALLOWED_CHARACTERS_BYTES[enc[r, :lengths[r]]].tobytes().decode("ascii") for r in rows]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().ds_titles_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ALLOWED_CHARACTERS_BYTES = np.frombuffer(ALLOWED_CHARACTERS.encode("ascii"), dtype=np.uint8)
+
+
+def prepare_queries(titles, transform, device=0):
+    """The query table of `titles` made on the device: transform_titles (when `transform`) and encode_collection in one
+    kernel (ds_prepare_titles), with the host path's checks and errors, in its order: a non-ASCII title without
+    `transform` (UnicodeEncodeError), characters a transformed title cannot hold (check_characters' ValueError), a
+    title longer than 255 characters without `transform` (DoppelError).  The host keeps the Unicode step (NFD +
+    ASCII, transform_titles) for the non-ASCII titles only, and one join.  -> DeviceTitles."""
+    titles = [str(t) for t in titles]
+    joined = "".join(titles)
+    if not joined.isascii():
+        if transform:
+            titles = [t if t.isascii() else unicodedata.normalize("NFD", t).encode("ascii", "ignore").decode("ascii")
+                      for t in titles]
+            joined = "".join(titles)
+        else:
+            for title in titles:          # _pack's error: the first title that is not ASCII
+                title.encode("ascii")
+    chars = np.frombuffer(joined.encode("ascii"), dtype=np.uint8) if joined else np.zeros(1, dtype=np.uint8)
+    offsets = np.zeros(len(titles) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, titles), dtype=np.int64, count=len(titles)), out=offsets[1:])
+    handle = ctypes.c_void_p()
+    report = np.zeros(4, dtype=np.int64)
+    started = time.perf_counter()
+    status = _lib.lib().ds_prepare_titles(_lib.pointer(chars), _lib.pointer(offsets), len(titles), int(bool(transform)),
+                                          device, _lib.pointer(None), ctypes.byref(handle), _lib.pointer(report))
+    out = DeviceTitles(handle, len(titles), device) if status == 0 else None
+    if out is not None:
+        out.prepare_ms = (time.perf_counter() - started) * 1000.0      # upload + kernel + synchronise
+    mask = int(report[0].view(np.uint64)) | (int(report[1].view(np.uint64)) << 64)
+    if mask:
+        if out is not None:
+            out.close()
+        _refuse_characters([b for b in range(128) if (mask >> b) & 1], "query")
+    _lib.check(status, "ds_prepare_titles")
+    return out
+
+
+class QuerySpace:
+    """The truth vocabulary in HBM for `ds_query_rows_device` (ds_query_space_create): dense column table, idf arrays."""
+
+    def __init__(self, vocabulary_keys, idf32, idf64, device=0):
+        keys = np.ascontiguousarray(vocabulary_keys, dtype=np.uint32)
+        idf32 = np.ascontiguousarray(idf32, dtype=np.float32)
+        idf64 = np.ascontiguousarray(idf64, dtype=np.float64)
+        self.device = device
+        self.handle = ctypes.c_void_p()
+        _lib.check(_lib.lib().ds_query_space_create(_lib.pointer(keys), _lib.pointer(idf32), _lib.pointer(idf64),
+                                                    keys.shape[0], device, ctypes.byref(self.handle)),
+                   "ds_query_space_create")
+
+    def close(self):
+        if self.handle:
+            _lib.lib().ds_query_space_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def default_chunk(device, bytes_per_query):
@@ -197,6 +299,7 @@ class TruthSide:
         enc, lengths = encode_collection(chars, offsets, _CODE_OF)
         counts = truth_word_counts(chars, offsets, separators=(ord(" "),))
         self.table = TitleTable(enc, lengths, counts, device)
+        self.space = QuerySpace(self.vocabulary_keys, self.idf32, self.idf64, device)
 
     def query_rows(self, chars, offsets):
         return query_rows(chars, offsets, self.vocabulary_keys, self.idf32, self.idf64, columns=self.columns)
@@ -211,14 +314,18 @@ class Prediction:
     predict.py:80-82).  chunk_queries: queries per device pass (default: what a quarter of the free HBM holds); the
     answer does not depend on it.  After a call, `details` holds per query match_row, title_id, stage (0 none,
     1 exact, 2 close, 3 model) and probability (1.0 for exact and close matches, the model's best candidate
-    otherwise, NaN when the query never reached the model), and `timings` the milliseconds of every stage."""
+    otherwise, NaN when the query never reached the model), and `timings` the milliseconds of every stage.
+    prepare_queries: "device" (default) transforms and encodes the query titles and derives their Jaccard rows on the
+    device (`prepare_queries`, CandidatePipeline.load_queries_device); "host" does it on the host (transform_titles,
+    query_rows, encode_collection).  Both give the same answers, details and errors."""
 
     def __init__(self, truth_titles, truth_title_ids, model, top_n=100, device=0, transform=True,
                  levenshtein_threshold=LEVENSHTEIN_RATIO_THRESHOLD,
-                 probability_threshold=PREDICTION_PROBABILITY_THRESHOLD, chunk_queries=None):
+                 probability_threshold=PREDICTION_PROBABILITY_THRESHOLD, chunk_queries=None, prepare_queries="device"):
         truth_titles = list(truth_titles)
         self.truth_title_ids = validate_truth(truth_titles, truth_title_ids, top_n)
         _validate_chunk(chunk_queries)
+        _validate_prepare(prepare_queries)
         if model is None or not hasattr(model, "predict_device"):
             raise ValueError("model must be a ForestModel")
         self.model = model
@@ -228,6 +335,7 @@ class Prediction:
         self.levenshtein_threshold = int(levenshtein_threshold)
         self.probability_threshold = float(probability_threshold)
         self.chunk_queries = chunk_queries
+        self.prepare_queries = prepare_queries
         self.details = None
         self.timings = {}
 
@@ -235,6 +343,7 @@ class Prediction:
         truth = TruthSide(self.truth_titles, device)
         self._vocabulary_keys, self._idf32, self._idf64 = truth.vocabulary_keys, truth.idf32, truth.idf64
         self._columns, self.index, self.truth_table = truth.columns, truth.index, truth.table
+        self._space = truth.space
 
     def _transform(self, titles):
         return transform_or_keep(titles, self.transform)
@@ -243,8 +352,9 @@ class Prediction:
     def _check_characters(chars, offsets, what):
         check_characters(chars, offsets, what)
 
-    def _default_chunk(self):
-        return default_chunk(self.device, BYTES_PER_PAIR * self.top_n + 64)
+    def _default_chunk(self, device_rows=False):
+        # device_rows: the pipeline's own query CSR at capacity (rowptr, 253 columns, q_maxint per query)
+        return default_chunk(self.device, BYTES_PER_PAIR * self.top_n + 64 + (8 + 4 * MAX_GRAMS + 8) * device_rows)
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
@@ -263,7 +373,9 @@ class Prediction:
         details = self._run([stripped], np.zeros(1, dtype=np.int64), single=True)
         self.details = details
         row = int(details["match_row"].iloc[0])
-        return {"test_index": 0, "transformed_title": self._last_queries[0],
+        queries = self._last_queries
+        transformed = queries.transformed([0])[0] if isinstance(queries, DeviceTitles) else queries[0]
+        return {"test_index": 0, "transformed_title": transformed,
                 "match_transformed_title": self.truth_titles[row] if row >= 0 else None,
                 "title_id": int(self.truth_title_ids[row]) if row >= 0 else TRAIN_NOT_FOUND_VALUE,
                 "prediction": float(details["probability"].iloc[0])}
@@ -272,30 +384,48 @@ class Prediction:
         import pandas as pd
         timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "remaining_pairs",
                                  "features", "model", "select_matches", "copy_back"), 0.0)
+        device_path = self.prepare_queries == "device"
+        if device_path:
+            timings["prepare_queries"] = 0.0
         started = time.perf_counter()
-        queries = self._transform(titles)
-        self._last_queries = queries
-        n = len(queries)
+        n = len(titles)
         match_row = np.full(n, -1, dtype=np.int64)
         stage = np.zeros(n, dtype=np.int8)
         probability = np.full(n, np.nan, dtype=np.float32)
+        if device_path:
+            self._last_queries = None
+            if n:
+                query_table = prepare_queries(titles, self.transform, self.device)
+                timings["prepare_queries"] = query_table.prepare_ms
+                self._last_queries = query_table
+        else:
+            queries = self._transform(titles)
+            self._last_queries = queries
         if n == 0:
             self.timings = timings
             return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": match_row,
                                  "stage": stage, "probability": probability})
-        chars, offsets = _pack(queries)
-        self._check_characters(chars, offsets, "query")
-        q_rowptr, q_cols, q_maxint = query_rows(chars, offsets, self._vocabulary_keys, self._idf32, self._idf64,
-                                               columns=self._columns)
-        enc, lengths = encode_collection(chars, offsets, _CODE_OF)
-        query_table = TitleTable(enc, lengths, None, self.device)
-        chunk = min(n, self.chunk_queries or self._default_chunk())
+        if not device_path:
+            chars, offsets = _pack(queries)
+            self._check_characters(chars, offsets, "query")
+            q_rowptr, q_cols, q_maxint = query_rows(chars, offsets, self._vocabulary_keys, self._idf32, self._idf64,
+                                                   columns=self._columns)
+            enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+            query_table = TitleTable(enc, lengths, None, self.device)
+        chunk = min(n, self.chunk_queries or self._default_chunk(device_path))
         pipeline = CandidatePipeline.over(self.index, self.truth_table, query_table, self.top_n, chunk, self.device)
-        timings["host_prepare"] = (time.perf_counter() - started) * 1000.0
-        events = {name: _lib.Timer(self.device) for name in timings if name not in ("host_prepare", "copy_back")}
+        timings["host_prepare"] = (time.perf_counter() - started) * 1000.0 - timings.get("prepare_queries", 0.0)
+        events = {name: _lib.Timer(self.device) for name in timings
+                  if name not in ("host_prepare", "copy_back")}
         for first in range(0, n, chunk):
             last = min(n, first + chunk)
-            pipeline.load_queries(q_rowptr, q_cols, q_maxint, first, last)
+            if device_path:
+                events["prepare_queries"].start()
+                pipeline.load_queries_device(self._space, first, last)
+                events["prepare_queries"].stop()
+                timings["prepare_queries"] += events["prepare_queries"].elapsed_ms()
+            else:
+                pipeline.load_queries(q_rowptr, q_cols, q_maxint, first, last)
             self._chunk(pipeline, events, timings, match_row, stage, probability, single)
         title_id = np.where(match_row >= 0, self.truth_title_ids[np.maximum(match_row, 0)], TRAIN_NOT_FOUND_VALUE)
         self.timings = timings

@@ -43,6 +43,7 @@ typedef struct ds_timer ds_timer;   /* pair of HIP events */
 typedef struct ds_problem ds_problem; /* host-side product of the native index build (next row f-3) */
 typedef struct ds_forest ds_forest;   /* tree ensemble resident in HBM (next row f-4) */
 typedef struct ds_trainer ds_trainer; /* gradient-boosted tree trainer resident in HBM (train.py) */
+typedef struct ds_query_space ds_query_space; /* truth vocabulary of the query-rows kernels, resident in HBM */
 
 /* ---- library ---------------------------------------------------------------------------------------------------- */
 const char *ds_last_error(void);
@@ -306,6 +307,32 @@ int ds_titles_read(const ds_titles *titles, uint8_t *enc, uint8_t *len);
 int ds_training_pairs_device(const int32_t *d_rows, int64_t n_queries, int32_t top_n, int32_t sample_n,
                              const int64_t *d_stream_index, const int32_t *d_own_row, uint64_t seed, int64_t q_first,
                              int32_t *d_pair_q, int32_t *d_pair_t, float *d_target, void *stream);
+
+/* ---- query side of Prediction on the device ("Query preparation") ---------------------------------
+ * ds_prepare_titles: the n raw titles chars[offsets[i] .. offsets[i + 1]) (host pointers, offsets[0] = 0) are uploaded and
+ * put through the byte work of ds_transform_titles (transform = 1: lower case, '-' -> ' ', keep [a-z0-9] and ASCII white
+ * space, collapse runs of ' ', strip, cut to 255, strip, '0'-pad to 3) or taken as they are (transform = 0), then encoded
+ * as ds_encode_titles with encode_title's codes (' ' 1, a-z 2..27, 0-9 28..37, any other byte 0) into *out = a new table
+ * (stride 255, no word counts).  report[0..1] = 128-bit mask (bit b of the low / high word: byte b, resp. 64 + b) of the
+ * bytes < 128 outside those 37 characters in the encoded titles (transform = 1) or in the raw ones (transform = 0), which
+ * the caller refuses; report[2] = the first title longer than 255 characters with transform = 0, report[3] = the first
+ * title holding a byte >= 128 (the Unicode step was skipped), -1 when there is none.  Either of the last two: DS_E_ARG and
+ * no table, the report still filled.  Enqueued on `stream`, which is synchronised before returning. */
+int ds_prepare_titles(const uint8_t *chars, const int64_t *offsets, int64_t n, int32_t transform, int device, void *stream,
+                      ds_titles **out, int64_t report[4]);
+/* The truth vocabulary of the native index build (ds_problem_arrays: strictly ascending big-endian tri-gram keys, idf32,
+ * idf64) as a dense int32[37^3] column table, the idf arrays and max(idf64) in HBM. */
+int ds_query_space_create(const uint32_t *vocabulary_keys, const float *idf32, const double *idf64, int64_t V, int device,
+                          ds_query_space **out);
+void ds_query_space_destroy(ds_query_space *space);
+/* The Jaccard query rows of titles [first, first + n) of a table of encoded transformed titles, against the space's
+ * vocabulary, bit-identical to the query rows of ds_problem_create(truth, queries) renumbered into the truth vocabulary:
+ * the distinct tri-grams of a title in ascending byte order; a known one is listed in d_cols and adds idf64 to d_maxint
+ * when its idf32 != 0; an unknown one is never listed and adds max(idf64) when float32(max(idf64)) != 0; d_maxint[q] is
+ * the left-to-right float64 sum in that order.  Chunk-local CSR: d_rowptr[n + 1] (d_rowptr[0] = 0), d_cols ascending;
+ * cols_capacity >= 253 * n.  Asynchronous on `stream`. */
+int ds_query_rows_device(const ds_query_space *space, const ds_titles *titles, int64_t first, int64_t n, int64_t *d_rowptr,
+                         int32_t *d_cols, double *d_maxint, int64_t cols_capacity, void *stream);
 
 /* ---- device memory / stream / timing plumbing (so tests and bench.py can keep inputs resident in HBM) ----------- */
 int ds_malloc(void **ptr, size_t bytes, int device);
