@@ -10,6 +10,48 @@ MISSING = 255
 ABSENT, SPLIT, LEAF = 0, 2, 3
 
 
+def make_data(n, nf, seed):
+    """Test features with NaNs, ties, a constant and an all-NaN column, +-0 and +-inf; labels from a noisy rule."""
+    rng = np.random.RandomState(seed)
+    x = rng.randn(n, nf).astype(np.float32)
+    if nf > 1:
+        x[:, 1] = np.round(x[:, 1] * 2)
+    if nf > 2:
+        x[rng.rand(n) < 0.2, 2] = np.nan
+    if nf > 3:
+        x[:, 3] = 7.0
+    if nf > 4:
+        x[:, 4] = np.nan
+    if nf > 5:
+        x[:, 5] = np.where(rng.rand(n) < 0.5, np.float32(-0.0), np.float32(0.0))
+        x[rng.rand(n) < 0.05, 5] = np.inf
+        x[rng.rand(n) < 0.05, 5] = -np.inf
+    score = x[:, 0] + 0.5 * np.nan_to_num(x[:, min(2, nf - 1)]) + 0.3 * rng.randn(n)
+    y = (score > 0.8).astype(np.float32)
+    return x, y
+
+
+# The trainer's limits (DESIGN.md "Training"): depth 8 and 96 features.  At levels 6 and 7 the histogram kernel
+# builds 32 and 64 nodes in 16-node groups, and the split kernel gives level 7 a second workgroup of 64 nodes.
+DEEP = dict(max_depth=8, eta=0.3, min_child_weight=0.5, reg_lambda=1.0)
+
+
+def deep_wide_data(n=60000, seed=7):
+    """make_data(n, 96, seed) with column 95 a bit-identical copy of column 0: its candidates tie with feature 0's in
+    every node, in the last feature group, and must lose every tie."""
+    x, y = make_data(n, 96, seed)
+    x[:, 95] = x[:, 0]
+    return x, y
+
+
+def deep_paths(tree):
+    """Counts of what a depth-8 heap tree reaches: (splits at heap ids 95..126, the children of level 5's second
+    16-node group; splits at 191..254, the second 64-node workgroup of level 7; leaves at level 8, ids 255..510)."""
+    state = tree["state"]
+    return (int(np.count_nonzero(state[95:127] == SPLIT)), int(np.count_nonzero(state[191:255] == SPLIT)),
+            int(np.count_nonzero(state[255:511] == LEAF)))
+
+
 def cuts_of(column, max_bin=256):
     column = np.asarray(column, dtype=np.float32)
     present = column[column == column]

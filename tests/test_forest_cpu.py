@@ -36,7 +36,8 @@ def random_rows(seed, n, n_features=66):
     rng = np.random.RandomState(seed)
     rows = rng.uniform(0, 100, (n, n_features)).astype(np.float32)
     rows[rng.rand(n, n_features) < 0.3] = np.nan            # construct_features pads with NaN (:121-123)
-    rows[:, :6] = rng.randint(0, 100, (n, 6))
+    integers = min(6, n_features - 1)                        # at least one column keeps its NaNs
+    rows[:, :integers] = rng.randint(0, 100, (n, integers))
     return rows
 
 

@@ -56,3 +56,45 @@ def test_predictions_inside_the_device_pipeline(oracle):
     features = pipeline.features()
     _, probabilities = oracle.forest_predict(model.arrays, features)
     assert np.allclose(pipeline.predictions().reshape(-1), probabilities, rtol=3e-7, atol=0)
+
+
+def test_forest_kernel_past_one_grid_pass(oracle):
+    """ds_forest_predict_device caps its grid at 256 x 16 workgroups of 256 rows: 1,048,576 rows per grid-stride pass.
+    2.1M rows take three passes, and the last one ends in a partial workgroup."""
+    import doppel_speller_amd as ds
+    n = 2_100_000
+    assert n > 2 * 4096 * 256 and n % 256 != 0
+    model = ds.ForestModel.from_xgboost_dump(random_dump(71, n_trees=60, n_features=8), 8)
+    rows = random_rows(72, n, n_features=8)
+    margins, probabilities = oracle.forest_predict(model.arrays, rows)
+    assert np.array_equal(model.predict(rows, output_margin=True).view(np.uint32), margins.view(np.uint32))
+    assert np.allclose(model.predict(rows), probabilities, rtol=3e-7, atol=0)
+
+
+@pytest.mark.parametrize("nf", [1, 47, 48, 96])
+def test_forest_kernel_at_every_lds_layout(oracle, nf):
+    """The rows of a workgroup are staged in 256 x (nf + 1) floats of LDS: nf = 47 fills the default 48 KiB exactly,
+    nf = 48 is the first size that needs the hipFuncSetAttribute opt-in, 96 (99 KiB) the largest model."""
+    import doppel_speller_amd as ds
+    lds = 256 * (nf + 1) * 4
+    assert (lds > 48 * 1024) == (nf >= 48) and (nf != 47 or lds == 48 * 1024)
+    model = ds.ForestModel.from_xgboost_dump(random_dump(80 + nf, n_trees=40, n_features=nf, depth=8), nf)
+    assert np.any(model.arrays["feature"] == nf - 1)          # the last staged column is read
+    rows = random_rows(90 + nf, 3001, n_features=nf)
+    assert np.isnan(rows).any()
+    margins, probabilities = oracle.forest_predict(model.arrays, rows)
+    assert np.array_equal(model.predict(rows, output_margin=True).view(np.uint32), margins.view(np.uint32))
+    assert np.allclose(model.predict(rows), probabilities, rtol=3e-7, atol=0)
+
+
+def test_forest_without_trees(oracle):
+    """ds_forest_create admits a model of zero trees: every margin is the float32 base margin."""
+    import doppel_speller_amd as ds
+    model = ds.ForestModel.from_trees([], 5, base_margin=0.3)
+    assert model.n_trees == 0
+    rows = random_rows(3, 700, n_features=5)
+    expected = np.full(700, np.float32(0.3))
+    margins, probabilities = oracle.forest_predict(model.arrays, rows)
+    assert np.array_equal(margins.view(np.uint32), expected.view(np.uint32))
+    assert np.array_equal(model.predict(rows, output_margin=True).view(np.uint32), expected.view(np.uint32))
+    assert np.allclose(model.predict(rows), probabilities, rtol=3e-7, atol=0)

@@ -92,3 +92,71 @@ def test_everything_or_nothing_remaining():
     _lib.check(lib.ds_remaining_pairs_device(None, None, 0, k, 0, None, None, counts.ptr, ctypes.c_void_p(0)), "pairs")
     _lib.check(lib.ds_stream_sync(None, 0), "sync")
     assert counts.to_host()[:2].tolist() == [0, 0]
+
+
+def mixed_best_rows(n, seed):
+    """best_row per query: random (about half unmatched, < 0), with whole 1024-query blocks all matched and all
+    unmatched in between, and the last block left random."""
+    rng = np.random.RandomState(seed)
+    best = np.where(rng.rand(n) < 0.5, -1, rng.randint(0, 1 << 30, n)).astype(np.int32)
+    blocks = (n + 1023) // 1024
+    for b in range(0, blocks - 1, 3):
+        best[b * 1024:(b + 1) * 1024] = -1 if (b // 3) % 2 else 17
+    return best
+
+
+@pytest.mark.parametrize("n_queries", [1_048_576, 1_048_577, 2_600_000])
+@pytest.mark.parametrize("k", [1, 7])
+def test_remaining_pairs_past_one_scan_pass(oracle, n_queries, k):
+    """The block-count scan is one workgroup of 1024 threads: over 1024 blocks of 1024 queries (> 1,048,576 queries)
+    it loops and carries the running sum from one pass to the next."""
+    from doppel_speller_amd import _lib
+    lib = _lib.lib()
+    q_first = 5_000_000
+    n_blocks = (n_queries + 1023) // 1024
+    assert n_blocks >= 1024                      # 1,048,576 queries fill the first pass exactly, more need a second
+    best = mixed_best_rows(n_queries, n_queries + k)
+    rows = np.random.RandomState(k).randint(0, 1 << 30, (n_queries, k)).astype(np.int32)
+    expected_q, expected_t = oracle.remaining_pairs(best, rows)
+    n_remaining = int((best < 0).sum())
+    d_best, d_rows = _lib.DeviceArray.from_host(best), _lib.DeviceArray.from_host(rows)
+    pair_q, pair_t = _lib.DeviceArray((n_queries * k,), np.int32), _lib.DeviceArray((n_queries * k,), np.int32)
+    counts = _lib.DeviceArray((int(lib.ds_remaining_pairs_counts_size(n_queries)),), np.int64)
+    assert counts.shape[0] == 2 + n_blocks
+    _lib.check(lib.ds_remaining_pairs_device(d_best.ptr, d_rows.ptr, n_queries, k, q_first, pair_q.ptr, pair_t.ptr,
+                                             counts.ptr, ctypes.c_void_p(0)), "pairs")
+    _lib.check(lib.ds_stream_sync(None, 0), "sync")
+    got = counts.to_host()
+    assert got[:2].tolist() == [n_remaining, n_remaining * k] and expected_q.shape[0] == n_remaining * k
+    # after the two totals: per block, the remaining queries before it (the exclusive scan, carried across passes)
+    per_block = np.add.reduceat((best < 0).astype(np.int64), np.arange(0, n_queries, 1024))
+    assert np.array_equal(got[2:], np.cumsum(per_block) - per_block)
+    assert np.array_equal(pair_q.to_host()[:n_remaining * k], q_first + expected_q)
+    assert np.array_equal(pair_t.to_host()[:n_remaining * k], expected_t)
+
+
+def test_select_matches_past_a_million_queries_with_ties(oracle):
+    """n_remaining > 2^20 with predictions drawn from six float32 values: ties at the maximum are common, and one
+    threshold equals one of the values (a maximum there is not above it)."""
+    from doppel_speller_amd import _lib
+    k, n = 7, (1 << 20) + 333
+    rng = np.random.RandomState(12)
+    values = np.array([0.05, 0.3, 0.9, 0.93, 0.97, 0.99], dtype=np.float32)
+    predictions = values[rng.randint(0, values.shape[0], n * k)]
+    pair_q = np.repeat(rng.randint(0, 1 << 30, n).astype(np.int32), k)
+    pair_t = rng.randint(0, 1 << 30, n * k).astype(np.int32)
+    d = [_lib.DeviceArray.from_host(x) for x in (pair_q, pair_t, predictions)]
+    out_q, out_t = _lib.DeviceArray((n,), np.int32), _lib.DeviceArray((n,), np.int32)
+    grid = predictions.reshape(n, k)
+    top = grid.max(axis=1)
+    single = (grid == top[:, None]).sum(axis=1) == 1
+    assert (~single).sum() > n // 10                              # ties at the maximum
+    for threshold in (0.9, 0.97, 0.5):
+        _lib.check(_lib.lib().ds_select_matches_device(d[0].ptr, d[1].ptr, d[2].ptr, n, k, threshold, out_q.ptr,
+                                                       out_t.ptr, ctypes.c_void_p(0)), "select")
+        _lib.check(_lib.lib().ds_stream_sync(None, 0), "sync")
+        expected_q, expected_t = oracle.select_matches(pair_q, pair_t, predictions, k, threshold)
+        assert np.array_equal(out_q.to_host(), expected_q) and np.array_equal(out_t.to_host(), expected_t), threshold
+        assert (expected_t >= 0).any() and (expected_t < 0).any()
+        if np.float32(threshold) in values:                       # single maxima exactly at the threshold: no match
+            assert (single & (top == np.float32(threshold))).any()

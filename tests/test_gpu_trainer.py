@@ -4,29 +4,9 @@ import numpy as np
 import pytest
 
 import forest_train_oracle as oracle
+from forest_train_oracle import make_data
 
 pytestmark = pytest.mark.gpu
-
-
-def make_data(n, nf, seed):
-    """Features with NaNs, ties, a constant and an all-NaN column, +-0 and +-inf; labels from a noisy rule."""
-    rng = np.random.RandomState(seed)
-    x = rng.randn(n, nf).astype(np.float32)
-    if nf > 1:
-        x[:, 1] = np.round(x[:, 1] * 2)
-    if nf > 2:
-        x[rng.rand(n) < 0.2, 2] = np.nan
-    if nf > 3:
-        x[:, 3] = 7.0
-    if nf > 4:
-        x[:, 4] = np.nan
-    if nf > 5:
-        x[:, 5] = np.where(rng.rand(n) < 0.5, np.float32(-0.0), np.float32(0.0))
-        x[rng.rand(n) < 0.05, 5] = np.inf
-        x[rng.rand(n) < 0.05, 5] = -np.inf
-    score = x[:, 0] + 0.5 * np.nan_to_num(x[:, min(2, nf - 1)]) + 0.3 * rng.randn(n)
-    y = (score > 0.8).astype(np.float32)
-    return x, y
 
 
 def heap_equal(device, expected):
@@ -74,24 +54,23 @@ CONFIGS = [  # n, features, depth, lambda, min_child_weight, eta
 ]
 
 
-@pytest.mark.parametrize("n,nf,depth,lam,mcw,eta", CONFIGS)
-def test_trees_margins_and_errors_match_the_oracle(n, nf, depth, lam, mcw, eta):
-    import doppel_speller_amd as ds
-    x, y = make_data(n, nf, n + depth)
-    ex, ey = make_data(max(1, n // 3), nf, n + depth + 1)
-    trainer = ds.ForestTrainer().begin(x, y, ex, ey, max_depth=depth, eta=eta, min_child_weight=mcw, reg_lambda=lam)
-    per_feature = oracle.cuts(x)
+def check_rounds(trainer, x, y, ex, ey, rounds, depth, eta, mcw, lam, max_bin=256):
+    """Grow `rounds` trees on a begun trainer and compare every round with the oracle: the heap tree, the gradients,
+    the training and evaluation margins (against the leaf sums and ForestModel.predict, bit for bit) and the
+    evaluation error.  Returns the oracle's trees."""
+    per_feature = oracle.cuts(x, max_bin)
     node_bins = oracle.bins(x, per_feature)
     counts = np.array([c.size for c in per_feature])
-    leafsum = np.zeros(n, np.float32)
-    split_rounds = 0
-    for round_ in range(30):
+    leafsum = np.zeros(x.shape[0], np.float32)
+    trees = []
+    for round_ in range(rounds):
         error = trainer.step()
         p = trainer.probabilities()
         gh = trainer.gradients()
         assert np.array_equal(gh, oracle.gradients(p, y, 5.0)), round_
         tree, leaves = oracle.grow_tree(node_bins, counts, gh, depth, eta, mcw, lam)
-        split_rounds += heap_equal(trainer.last_heap, tree) > 1
+        heap_equal(trainer.last_heap, tree)
+        trees.append(tree)
         leafsum = (leafsum + leaves).astype(np.float32)
         model = trainer.model()
         margins = trainer.margins()
@@ -100,6 +79,17 @@ def test_trees_margins_and_errors_match_the_oracle(n, nf, depth, lam, mcw, eta):
         assert np.array_equal(trainer.eval_margins().view(np.uint32),
                               model.predict(ex, output_margin=True).view(np.uint32)), round_
         assert error == oracle.custom_error(model.predict(ex), ey), round_
+    return trees
+
+
+@pytest.mark.parametrize("n,nf,depth,lam,mcw,eta", CONFIGS)
+def test_trees_margins_and_errors_match_the_oracle(n, nf, depth, lam, mcw, eta):
+    import doppel_speller_amd as ds
+    x, y = make_data(n, nf, n + depth)
+    ex, ey = make_data(max(1, n // 3), nf, n + depth + 1)
+    trainer = ds.ForestTrainer().begin(x, y, ex, ey, max_depth=depth, eta=eta, min_child_weight=mcw, reg_lambda=lam)
+    trees = check_rounds(trainer, x, y, ex, ey, 30, depth, eta, mcw, lam)
+    split_rounds = sum(int(np.count_nonzero(tree["state"] != oracle.ABSENT)) > 1 for tree in trees)
     if n >= 1000:
         assert split_rounds == 30                  # the comparison covered real trees, not single leaves
 
