@@ -718,10 +718,11 @@ __global__ __launch_bounds__(kFeatWaves * 64) void ds_close_ratio_kernel(CloseAr
         if (qi >= 0 && qi < a.n_q && ti >= 0 && ti < a.n_t) {
             const int lx = a.q_len[qi], ly = a.t_len[ti];
             const int total = lx + ly, delta = lx > ly ? lx - ly : ly - lx;
-            // predict.py:141-151 length pre-filter, float64 in source order
+            // predict.py:141-151 length pre-filter, float64 in source order (two empty titles, total == 0: 0/0 is NaN, no NaN is below the
+            // threshold, and the ratio of two empty strings is 100 -- the oracle's reading; the reference itself raises there)
             const bool may_match =
-                total > 0 && !((static_cast<double>(total - delta) / static_cast<double>(total)) * 100.0 <
-                               static_cast<double>(a.threshold));
+                total == 0 || !((static_cast<double>(total - delta) / static_cast<double>(total)) * 100.0 <
+                                static_cast<double>(a.threshold));
             if (may_match) {
                 wave_sync();
                 for (int i = lane; i < lx; i += 64) w.q[i] = a.q_enc[qi * a.q_stride + i];
@@ -978,6 +979,8 @@ static int ensure_truth_records(ds_titles *truth, uint32_t n_truth, uint8_t spac
 }
 
 // consecutive pairs one wave works through (two at a time): the k candidates of a query (k <= 16), a divisor of k between 8 and 16, or 10
+// (tests/title_cases.py restates this rule and tests/test_title_cases_cpu.py compares the restatement with the TEXT of this
+// function: change both together)
 static int32_t pairs_per_unit(int32_t k)
 {
     if (k <= 0) return 8;

@@ -147,7 +147,9 @@ int ds_titles_option(ds_titles *titles, const char *name, int64_t value);
 int ds_construct_features_indexed(ds_titles *queries, ds_titles *truth, const int32_t *pair_q, const int32_t *pair_t,
                                   uint8_t space_code, uint32_t n_truth, int64_t n, float *out);
 /* Device-resident variant for the fused pipeline: d_pair_t = the top-k rows written by ds_jaccard_topk_device,
- * pair i belongs to query row q_first + i / k when d_pair_q is NULL.  d_out = float32[n*66] in HBM. */
+ * pair i belongs to query row q_first + i / k when d_pair_q is NULL.  d_out = float32[n*66] in HBM.
+ * A pair whose query row or truth row lies outside its table (negative, or >= the table's rows: e.g. the -1 rows of a
+ * top-k that failed) is not an error: its 66 outputs are the quiet NaN 0x7fc00000, and no title is read for it. */
 int ds_construct_features_indexed_device(ds_titles *queries, ds_titles *truth, const int32_t *d_pair_q,
                                          const int32_t *d_pair_t, int64_t q_first, int32_t k, uint8_t space_code,
                                          uint32_t n_truth, int64_t n, float *d_out, void *stream);
@@ -168,7 +170,11 @@ int ds_levenshtein_ratio(const uint8_t *a, int la, const uint8_t *b, int lb);
  * best_row[q] = the candidate with the highest ratio > threshold if exactly one reaches it (predict.py:172-176), else
  * -1.  sort_key[256] = order of the character codes under Python's sorted() (the code points).  python-Levenshtein is
  * not part of the reference tree: its published definition is restated (parity pinned against the tests' CPU
- * restatement only). */
+ * restatement only).
+ * ds_close_matches_device: the rows are in HBM, d_best_row may be NULL (ratios only); enqueued on `stream`.  A candidate
+ * row outside the truth table (negative or >= its rows), or a query row outside the query table, has ratio 0 and is
+ * never the best row (threshold >= 0: the best ratio has to exceed it).  Two empty titles have ratio 100 (the reference
+ * divides by zero there). */
 int ds_close_matches(ds_titles *queries, ds_titles *truth, const int32_t *pair_t, int32_t k, int64_t n_queries,
                      uint8_t space_code, const uint8_t *sort_key, int32_t threshold, uint8_t *ratios,
                      int32_t *best_row);

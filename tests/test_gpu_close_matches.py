@@ -4,20 +4,9 @@ the real third-party library)."""
 import numpy as np
 import pytest
 
+from title_cases import best_from_ratios as _best_from_ratios
+
 pytestmark = pytest.mark.gpu
-
-
-def _best_from_ratios(ratios, rows, threshold):
-    best = np.full(ratios.shape[0], -1, dtype=np.int32)
-    for q in range(ratios.shape[0]):
-        above = ratios[q] > threshold
-        if not above.any():
-            continue
-        top = ratios[q][above].max()
-        hits = np.nonzero(ratios[q] == top)[0]
-        if hits.shape[0] == 1:
-            best[q] = rows[q, hits[0]]
-    return best
 
 
 def test_close_matches_synthetic(oracle):
