@@ -10,6 +10,8 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
     ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
+    train_model(truth_titles, truth_title_ids, train_titles, train_title_ids)   -> model, feature importances, the
+        evaluation error matrix (train.train_model: the two steps above in one call, the feature matrix kept in HBM)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -24,6 +26,7 @@ from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
 from .forest import ForestModel  # noqa: F401
 from .prediction import Prediction  # noqa: F401
-from .training_set import FeatureEngineering, generate_misspelled_names  # noqa: F401
-from .train import ForestTrainer, compute_cuts, evaluation_error_matrix  # noqa: F401
+from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
+from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
+                    evaluation_error_matrix, train_model)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip",
-            "ds_train.hip", "ds_training.hip", "ds_queries.hip")
+            "ds_train.hip", "ds_training.hip", "ds_queries.hip", "ds_cuts.hip")
 _lib = None
 
 
@@ -159,6 +159,12 @@ def _declare(handle):
         "ds_trainer_set_eval": [p, p, p, c.c_int64],
         "ds_trainer_step": [p, p, p, c.POINTER(c.c_int64)],
         "ds_trainer_read": [p, p, p, p, p, p],
+        "ds_feature_cuts_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_int, p],
+        "ds_cuts_option": [c.c_char_p, c.c_int64],
+        "ds_trainer_create_device": [p, c.c_int64, c.c_int32, p, p, c.c_int32, c.c_double, c.c_double, c.c_double,
+                                     c.c_double, c.c_int, c.POINTER(p)],
+        "ds_trainer_set_eval_device": [p, p, p, c.c_int64],
+        "ds_gather_rows_device": [p, c.c_int32, p, c.c_int64, c.c_int64, p, p],
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
@@ -208,7 +214,8 @@ EXPORTED_SYMBOLS = (
     "ds_training_pairs_device", "ds_prepare_titles", "ds_query_space_create", "ds_query_space_destroy",
     "ds_query_rows_device", "ds_malloc", "ds_free", "ds_memcpy_h2d", "ds_memcpy_d2h", "ds_memset",
     "ds_stream_sync", "ds_memcpy_d2d_async", "ds_stream_create", "ds_stream_destroy", "ds_timer_create", "ds_timer_destroy", "ds_timer_start", "ds_timer_stop",
-    "ds_timer_elapsed_ms")
+    "ds_timer_elapsed_ms", "ds_feature_cuts_device", "ds_cuts_option", "ds_trainer_create_device",
+    "ds_trainer_set_eval_device", "ds_gather_rows_device")
 
 
 def lib():

@@ -1,0 +1,388 @@
+// The cut values of the trainer's bins (train.py feature_cuts / compute_cuts, DESIGN.md section 9 "Cuts") from a
+// float32[n][nf] matrix that already lies in HBM: ds_feature_cuts_device.  Bit-identical to compute_cuts.
+//
+// Every comparison is made on integer keys, never on floats, so denormals and infinities cannot depend on a float mode:
+//   key(x) = 0xFFFFFFFF for a NaN (no other value maps there: NaNs sort last), else with -0.0 read as +0.0 the bits of
+//   x with all bits flipped when the sign is set and only the sign bit flipped otherwise (ascending keys = ascending x).
+//
+// Per group of columns, one launch per phase, no workgroup waits for another:
+//   1. ds_cuts_key_kernel      row tiles of 64 rows through LDS -> column-major keys[g][n]; per column the number m of
+//                              non-NaN values and the OR and the AND of its keys (one atomic each per workgroup and column)
+//   2. four passes of an LSD radix sort by 8-bit digits, keys only, columns in blockIdx.y:
+//        ds_cuts_count_kernel    digit counts of a tile of kSortTile keys -> table[column][digit][tile]
+//        ds_cuts_scan_kernel     exclusive scan of that table per column, in place
+//        ds_cuts_scatter_kernel  stable scatter: rank inside a wave from __ballot over the digit's bits, across the
+//                                waves of the workgroup through LDS, tiles of 256 keys in order
+//      A pass whose digit is the same in every key of a column ((OR ^ AND) has a zero byte there) is skipped for that
+//      column by all three kernels; the column's keys then stay in the buffer they are in.
+//   3. ds_cuts_pick_kernel     on the sorted keys of a column: heads (key[i] != key[i - 1], i < m) counted and compacted
+//                              in order; at most max_bin - 1 of them: the distinct values without the smallest, else the
+//                              picks key[(j * m) / (max_bin - 1)], j = 1 .. max_bin - 2, without repeats and without
+//                              values equal to key[0] -> table[nf][254] and a count per column; the host packs them.
+// All sums are integer sums and every position is a function of the keys alone: the result does not depend on the
+// schedule, on the run or on the column group.
+//
+// Memory: the two key buffers of a group take 8 B per row and column, its count table 1 KiB per tile and column.  The
+// group is the largest number of columns for which these stay under a QUARTER of the HBM that is free at the call
+// (at least one column); ds_cuts_option("column_group", g) forces g columns per group for tests.
+#include <algorithm>
+#include <atomic>
+
+#include "ds_common.h"
+
+namespace ds {
+
+constexpr int kCutsFeaturesMax = 96;     // = kTrainFeaturesMax
+constexpr int kCutsMax = 254;            // = kTrainCutsMax
+constexpr int kKeyTileRows = 64;
+constexpr int kKeyThreads = 256;
+constexpr int kSortThreads = 256;
+constexpr int kSortWaves = kSortThreads / 64;
+constexpr int kSortTile = 8192;          // keys of one column per workgroup and pass
+constexpr int kScanThreads = 1024;
+
+__device__ inline uint32_t cut_key(uint32_t bits)
+{
+    if ((bits & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;   // NaN
+    if (bits == 0x80000000u) bits = 0u;                            // -0.0 counts as +0.0
+    return (bits & 0x80000000u) ? ~bits : bits ^ 0x80000000u;
+}
+
+__device__ inline uint32_t cut_value_bits(uint32_t key) { return (key & 0x80000000u) ? key ^ 0x80000000u : ~key; }
+
+// Is the digit of `pass` the same in every key of the column, and in which of the two buffers do the column's keys
+// lie before that pass (1: the second one)?
+__device__ inline bool pass_skipped(uint32_t differing, int pass) { return ((differing >> (8 * pass)) & 0xffu) == 0u; }
+__device__ inline int passes_done(uint32_t differing, int pass)
+{
+    int done = 0;
+    for (int p = 0; p < pass; ++p) done += pass_skipped(differing, p) ? 0 : 1;
+    return done;
+}
+
+// ---- 1. keys ---------------------------------------------------------------------------------------------------------
+// Wave w of a workgroup owns the columns w, w + 4, ... of the group, lane l row l of the tile: a column's keys of a
+// tile are one coalesced 256-byte store, and its count, OR and AND in LDS belong to that wave alone.
+__global__ __launch_bounds__(kKeyThreads) void ds_cuts_key_kernel(const uint32_t *rows, int64_t n, int32_t nf, int32_t c0,
+                                                                   int32_t g, uint32_t *keys, uint32_t *col_m,
+                                                                   uint32_t *col_or, uint32_t *col_and)
+{
+    __shared__ uint32_t s_tile[kKeyTileRows * (kCutsFeaturesMax + 1)];
+    __shared__ uint32_t s_m[kCutsFeaturesMax], s_or[kCutsFeaturesMax], s_and[kCutsFeaturesMax];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int stride = nf | 1;   // odd: the 64 rows of a column fall on different banks
+    for (int f = threadIdx.x; f < g; f += kKeyThreads) {
+        s_m[f] = 0u;
+        s_or[f] = 0u;
+        s_and[f] = 0xffffffffu;
+    }
+    for (int64_t first = static_cast<int64_t>(blockIdx.x) * kKeyTileRows; first < n;
+         first += static_cast<int64_t>(gridDim.x) * kKeyTileRows) {
+        const int rows_here = static_cast<int>(n - first < kKeyTileRows ? n - first : kKeyTileRows);
+        __syncthreads();
+        for (int e = threadIdx.x; e < rows_here * nf; e += kKeyThreads) {   // coalesced row-major read
+            const int r = e / nf;
+            s_tile[r * stride + (e - r * nf)] = rows[first * nf + e];
+        }
+        __syncthreads();
+        const bool valid = lane < rows_here;
+        for (int f = wave; f < g; f += kKeyThreads / 64) {
+            const uint32_t key = valid ? cut_key(s_tile[lane * stride + c0 + f]) : 0xffffffffu;
+            if (valid) keys[static_cast<int64_t>(f) * n + first + lane] = key;
+            uint32_t any = valid ? key : 0u, all = key;
+            for (int offset = 32; offset > 0; offset >>= 1) {
+                any |= __shfl_xor(any, offset);
+                all &= __shfl_xor(all, offset);
+            }
+            const uint32_t present = __popcll(__ballot(key != 0xffffffffu));
+            if (lane == 0) {
+                s_m[f] += present;
+                s_or[f] |= any;
+                s_and[f] &= all;
+            }
+        }
+    }
+    __syncthreads();
+    for (int f = threadIdx.x; f < g; f += kKeyThreads) {
+        if (s_m[f]) atomicAdd(&col_m[f], s_m[f]);
+        atomicOr(&col_or[f], s_or[f]);
+        atomicAnd(&col_and[f], s_and[f]);
+    }
+}
+
+// ---- 2. the radix sort -------------------------------------------------------------------------------------------------
+// The lanes of the wave that are valid and hold the same 8-bit digit as this lane (meaningless for an invalid lane).
+__device__ inline unsigned long long digit_peers(uint32_t digit, bool valid)
+{
+    unsigned long long peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (digit >> b) & 1u;
+        const unsigned long long set = __ballot(valid && bit);
+        peers &= bit ? set : ~set;
+    }
+    return peers;
+}
+
+__global__ __launch_bounds__(kSortThreads) void ds_cuts_count_kernel(const uint32_t *keys_a, const uint32_t *keys_b,
+                                                                      int64_t n, int32_t pass, const uint32_t *col_or,
+                                                                      const uint32_t *col_and, uint32_t *table,
+                                                                      int64_t tiles)
+{
+    __shared__ uint32_t s_hist[256];
+    const int col = blockIdx.y, lane = threadIdx.x & 63;
+    const uint32_t differing = col_or[col] ^ col_and[col];
+    if (pass_skipped(differing, pass)) return;
+    const uint32_t *src = ((passes_done(differing, pass) & 1) ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
+    s_hist[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t begin = static_cast<int64_t>(blockIdx.x) * kSortTile, end = min(n, begin + kSortTile);
+    for (int64_t base = begin; base < end; base += kSortThreads) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < end;
+        const uint32_t digit = valid ? (src[i] >> (8 * pass)) & 0xffu : 0u;
+        const unsigned long long peers = digit_peers(digit, valid);
+        if (valid && lane == __ffsll(static_cast<long long>(peers)) - 1) atomicAdd(&s_hist[digit], __popcll(peers));
+    }
+    __syncthreads();
+    table[(static_cast<int64_t>(col) * 256 + threadIdx.x) * tiles + blockIdx.x] = s_hist[threadIdx.x];
+}
+
+// Exclusive prefix of `value` over the kScanThreads threads of a workgroup, and the total.
+__device__ inline uint32_t block_exclusive(uint32_t value, uint32_t *s_waves, uint32_t &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inclusive = value;
+    for (int offset = 1; offset < 64; offset <<= 1) {
+        const uint32_t other = __shfl_up(inclusive, offset);
+        if (lane >= offset) inclusive += other;
+    }
+    __syncthreads();   // the previous call's wave sums have been read
+    if (lane == 63) s_waves[wave] = inclusive;
+    __syncthreads();
+    uint32_t before = 0u;
+    total = 0u;
+    for (int w = 0; w < kScanThreads / 64; ++w) {
+        const uint32_t sum = s_waves[w];
+        before += w < wave ? sum : 0u;
+        total += sum;
+    }
+    return before + inclusive - value;
+}
+
+// table[column][digit][tile] -> the first position of (digit, tile) in the column's next buffer
+__global__ __launch_bounds__(kScanThreads) void ds_cuts_scan_kernel(uint32_t *table, int64_t tiles, int32_t pass,
+                                                                     const uint32_t *col_or, const uint32_t *col_and)
+{
+    __shared__ uint32_t s_waves[kScanThreads / 64];
+    const int col = blockIdx.x;
+    if (pass_skipped(col_or[col] ^ col_and[col], pass)) return;
+    uint32_t *mine = table + static_cast<int64_t>(col) * 256 * tiles;
+    const int64_t count = 256 * tiles;
+    uint32_t running = 0u;
+    for (int64_t base = 0; base < count; base += kScanThreads) {
+        const int64_t i = base + threadIdx.x;
+        const uint32_t value = i < count ? mine[i] : 0u;
+        uint32_t total;
+        const uint32_t before = block_exclusive(value, s_waves, total);
+        if (i < count) mine[i] = running + before;
+        running += total;
+    }
+}
+
+__global__ __launch_bounds__(kSortThreads) void ds_cuts_scatter_kernel(uint32_t *keys_a, uint32_t *keys_b, int64_t n,
+                                                                        int32_t pass, const uint32_t *col_or,
+                                                                        const uint32_t *col_and, const uint32_t *table,
+                                                                        int64_t tiles)
+{
+    __shared__ uint32_t s_next[256];                    // the next position of each digit for this workgroup
+    __shared__ uint32_t s_wave_count[kSortWaves][256];  // keys of each digit in each wave of the current 256 keys
+    const int col = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t differing = col_or[col] ^ col_and[col];
+    if (pass_skipped(differing, pass)) return;
+    const bool from_b = passes_done(differing, pass) & 1;
+    const uint32_t *src = (from_b ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
+    uint32_t *dst = (from_b ? keys_a : keys_b) + static_cast<int64_t>(col) * n;
+    s_next[threadIdx.x] = table[(static_cast<int64_t>(col) * 256 + threadIdx.x) * tiles + blockIdx.x];
+    for (int w = 0; w < kSortWaves; ++w) s_wave_count[w][threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t begin = static_cast<int64_t>(blockIdx.x) * kSortTile, end = min(n, begin + kSortTile);
+    for (int64_t base = begin; base < end; base += kSortThreads) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < end;
+        const uint32_t key = valid ? src[i] : 0u;
+        const uint32_t digit = (key >> (8 * pass)) & 0xffu;
+        const unsigned long long peers = digit_peers(digit, valid);
+        const uint32_t rank = __popcll(peers & ((1ull << lane) - 1ull));
+        if (valid && rank == 0u) s_wave_count[wave][digit] = __popcll(peers);
+        __syncthreads();
+        if (valid) {
+            uint32_t position = s_next[digit] + rank;
+            for (int w = 0; w < kSortWaves; ++w) position += w < wave ? s_wave_count[w][digit] : 0u;
+            if (position < n) dst[position] = key;   // always true for counts of the same keys
+        }
+        __syncthreads();
+        uint32_t sum = 0u;
+        for (int w = 0; w < kSortWaves; ++w) {
+            sum += s_wave_count[w][threadIdx.x];
+            s_wave_count[w][threadIdx.x] = 0u;
+        }
+        s_next[threadIdx.x] += sum;
+        __syncthreads();
+    }
+}
+
+// ---- 3. the cuts of a sorted column ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(kScanThreads) void ds_cuts_pick_kernel(const uint32_t *keys_a, const uint32_t *keys_b,
+                                                                     int64_t n, const uint32_t *col_or,
+                                                                     const uint32_t *col_and, const uint32_t *col_m,
+                                                                     int32_t max_bin, uint32_t *cut_table,
+                                                                     int32_t *cut_counts)
+{
+    __shared__ uint32_t s_waves[kScanThreads / 64];
+    const int col = blockIdx.x;
+    const uint32_t differing = col_or[col] ^ col_and[col];
+    const uint32_t *sorted = ((passes_done(differing, 4) & 1) ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
+    uint32_t *out = cut_table + static_cast<int64_t>(col) * kCutsMax;
+    const int64_t m = col_m[col];
+    if (m == 0) {
+        if (threadIdx.x == 0) cut_counts[col] = 0;
+        return;
+    }
+    // heads in order: head number h >= 1 (from 0) is a candidate cut while h <= 254
+    uint32_t heads = 0u;
+    for (int64_t base = 0; base < m; base += kScanThreads) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < m;
+        const uint32_t key = valid ? sorted[i] : 0u;
+        const bool head = valid && (i == 0 || key != sorted[i - 1]);
+        uint32_t total;
+        const uint32_t number = heads + block_exclusive(head ? 1u : 0u, s_waves, total);
+        if (head && number >= 1u && number <= static_cast<uint32_t>(kCutsMax)) out[number - 1] = cut_value_bits(key);
+        heads += total;
+    }
+    if (heads <= static_cast<uint32_t>(max_bin - 1)) {
+        if (threadIdx.x == 0) cut_counts[col] = static_cast<int32_t>(heads) - 1;
+        return;
+    }
+    __syncthreads();   // the picks overwrite the heads
+    const int64_t j = threadIdx.x + 1;
+    bool take = false;
+    uint32_t key = 0u;
+    if (j <= max_bin - 2) {
+        key = sorted[(j * m) / (max_bin - 1)];
+        take = key != sorted[0] && key != sorted[((j - 1) * m) / (max_bin - 1)];
+    }
+    uint32_t total;
+    const uint32_t at = block_exclusive(take ? 1u : 0u, s_waves, total);
+    if (take) out[at] = cut_value_bits(key);
+    if (threadIdx.x == 0) cut_counts[col] = static_cast<int32_t>(total);
+}
+
+}  // namespace ds
+
+namespace {
+
+std::atomic<int64_t> g_column_group{0};   // 0: sized from the free HBM
+
+}  // namespace
+
+extern "C" {
+
+int ds_cuts_option(const char *name, int64_t value)
+{
+    DS_REQUIRE(name != nullptr, "ds_cuts_option: null name");
+    if (std::strcmp(name, "column_group") == 0) {
+        DS_REQUIRE(value >= 0 && value <= ds::kCutsFeaturesMax, "ds_cuts_option: column_group = %lld out of range [0, %d]",
+                   (long long)value, ds::kCutsFeaturesMax);
+        g_column_group = value;
+        return DS_OK;
+    }
+    ds::set_error("ds_cuts_option: unknown option '%s'", name);
+    return DS_E_ARG;
+}
+
+int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_features, int32_t max_bin, float *cuts,
+                           int32_t *cut_offsets, int device, void *stream)
+{
+    DS_REQUIRE(d_features && cuts && cut_offsets, "ds_feature_cuts_device: null pointer");
+    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "ds_feature_cuts_device: n = %lld rows out of range [1, 2^31)", (long long)n);
+    DS_REQUIRE(n_features >= 1 && n_features <= ds::kCutsFeaturesMax,
+               "ds_feature_cuts_device: n_features = %d out of range [1, %d]", n_features, ds::kCutsFeaturesMax);
+    DS_REQUIRE(max_bin >= 2 && max_bin <= 256, "ds_feature_cuts_device: max_bin = %d out of range [2, 256]", max_bin);
+    DS_HIP(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t tiles = (n + ds::kSortTile - 1) / ds::kSortTile;
+    const int64_t column_bytes = 8 * n + 1024 * tiles;
+    size_t free_bytes = 0, total_bytes = 0;
+    DS_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
+    if (static_cast<size_t>(column_bytes) + (size_t(64) << 20) > free_bytes) {
+        ds::set_error("ds_feature_cuts_device: one column needs %lld bytes of HBM, %zu are free", (long long)column_bytes,
+                      free_bytes);
+        return DS_E_HIP;
+    }
+    int64_t group = g_column_group.load();
+    if (group == 0) group = static_cast<int64_t>(free_bytes / 4) / column_bytes;
+    group = std::max<int64_t>(1, std::min<int64_t>(group, n_features));
+
+    ds::DeviceBuffer<uint32_t> keys_a, keys_b, table, column_state, cut_table;
+    ds::DeviceBuffer<int32_t> cut_counts;
+    int status = keys_a.allocate(static_cast<size_t>(group * n));
+    if (status == DS_OK) status = keys_b.allocate(static_cast<size_t>(group * n));
+    if (status == DS_OK) status = table.allocate(static_cast<size_t>(group * 256 * tiles));
+    if (status == DS_OK) status = column_state.allocate(3 * ds::kCutsFeaturesMax);   // m, OR, AND of the group's columns
+    if (status == DS_OK) status = cut_table.allocate(static_cast<size_t>(n_features) * ds::kCutsMax);
+    if (status == DS_OK) status = cut_counts.allocate(n_features);
+    if (status != DS_OK) return status;
+    uint32_t *col_m = column_state.ptr, *col_or = col_m + ds::kCutsFeaturesMax, *col_and = col_or + ds::kCutsFeaturesMax;
+    int compute_units = 256;
+    hipDeviceProp_t props;
+    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
+        compute_units = props.multiProcessorCount;
+    const int64_t row_tiles = (n + ds::kKeyTileRows - 1) / ds::kKeyTileRows;
+    const unsigned key_grid = static_cast<unsigned>(std::min<int64_t>(row_tiles, int64_t(compute_units) * 8));
+    for (int32_t c0 = 0; c0 < n_features; c0 += static_cast<int32_t>(group)) {
+        const int32_t g = static_cast<int32_t>(std::min<int64_t>(group, n_features - c0));
+        DS_HIP(hipMemsetAsync(col_m, 0, sizeof(uint32_t) * 2 * ds::kCutsFeaturesMax, s));
+        DS_HIP(hipMemsetAsync(col_and, 0xff, sizeof(uint32_t) * ds::kCutsFeaturesMax, s));
+        hipLaunchKernelGGL(ds::ds_cuts_key_kernel, dim3(key_grid), dim3(ds::kKeyThreads), 0, s,
+                           reinterpret_cast<const uint32_t *>(d_features), n, n_features, c0, g, keys_a.ptr, col_m, col_or,
+                           col_and);
+        DS_HIP(hipGetLastError());
+        for (int32_t pass = 0; pass < 4; ++pass) {
+            hipLaunchKernelGGL(ds::ds_cuts_count_kernel, dim3(static_cast<unsigned>(tiles), g), dim3(ds::kSortThreads), 0,
+                               s, keys_a.ptr, keys_b.ptr, n, pass, col_or, col_and, table.ptr, tiles);
+            DS_HIP(hipGetLastError());
+            hipLaunchKernelGGL(ds::ds_cuts_scan_kernel, dim3(g), dim3(ds::kScanThreads), 0, s, table.ptr, tiles, pass,
+                               col_or, col_and);
+            DS_HIP(hipGetLastError());
+            hipLaunchKernelGGL(ds::ds_cuts_scatter_kernel, dim3(static_cast<unsigned>(tiles), g), dim3(ds::kSortThreads),
+                               0, s, keys_a.ptr, keys_b.ptr, n, pass, col_or, col_and, table.ptr, tiles);
+            DS_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(ds::ds_cuts_pick_kernel, dim3(g), dim3(ds::kScanThreads), 0, s, keys_a.ptr, keys_b.ptr, n,
+                           col_or, col_and, col_m, max_bin, cut_table.ptr + static_cast<size_t>(c0) * ds::kCutsMax,
+                           cut_counts.ptr + c0);
+        DS_HIP(hipGetLastError());
+    }
+    std::vector<uint32_t> host_table(static_cast<size_t>(n_features) * ds::kCutsMax);
+    std::vector<int32_t> host_counts(n_features);
+    DS_HIP(hipMemcpyAsync(host_table.data(), cut_table.ptr, host_table.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DS_HIP(hipMemcpyAsync(host_counts.data(), cut_counts.ptr, host_counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
+                          s));
+    DS_HIP(hipStreamSynchronize(s));
+    cut_offsets[0] = 0;
+    for (int32_t f = 0; f < n_features; ++f) {
+        const int32_t count = host_counts[f];
+        if (count < 0 || count > ds::kCutsMax) {
+            ds::set_error("ds_feature_cuts_device: feature %d came back with %d cuts", f, count);
+            return DS_E_HIP;
+        }
+        std::memcpy(cuts + cut_offsets[f], host_table.data() + static_cast<size_t>(f) * ds::kCutsMax,
+                    sizeof(uint32_t) * count);
+        cut_offsets[f + 1] = cut_offsets[f] + count;
+    }
+    return DS_OK;
+}
+
+}  // extern "C"

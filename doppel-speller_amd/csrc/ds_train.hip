@@ -359,6 +359,28 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_eval_kernel(const uint8_
     if (threadIdx.x == 0 && s_error) atomicAdd(error, s_error);
 }
 
+// ---- row gather of a float32[n_src][nf] matrix in HBM (the split of the training set) ------------------------------
+__global__ __launch_bounds__(kRowThreads) void ds_gather_check_kernel(const int64_t *rows, int64_t n_rows, int64_t n_src,
+                                                                       int32_t *errors)
+{
+    for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n_rows;
+         r += static_cast<int64_t>(gridDim.x) * kRowThreads)
+        if (rows[r] < 0 || rows[r] >= n_src) atomicAdd(errors, 1);
+}
+
+// one dword per thread: consecutive lanes read and write consecutive dwords of a row
+__global__ __launch_bounds__(kRowThreads) void ds_gather_rows_kernel(const uint32_t *src, int32_t nf, const int64_t *rows,
+                                                                      int64_t n_rows, int64_t n_src, uint32_t *dst)
+{
+    const int64_t total = n_rows * nf;
+    for (int64_t e = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; e < total;
+         e += static_cast<int64_t>(gridDim.x) * kRowThreads) {
+        const int64_t r = e / nf, row = rows[r];
+        if (row < 0 || row >= n_src) continue;   // refused by ds_gather_check_kernel before this launch; never read
+        dst[e] = src[row * nf + (e - r * nf)];
+    }
+}
+
 }  // namespace ds
 
 struct ds_trainer {
@@ -393,19 +415,20 @@ namespace {
 
 int64_t heap_nodes(int32_t depth) { return (int64_t(2) << depth) - 1; }
 
-// bins of a float32[n][nf] host matrix (uploaded through a temporary buffer) into `out`
-int bin_matrix(ds_trainer *t, const float *rows, int64_t n, ds::DeviceBuffer<uint8_t> &out)
+// bins of a float32[n][nf] matrix into `out`: a host matrix is uploaded through a temporary buffer, a matrix in HBM
+// (in_hbm, complete before the call) is read where it lies and not kept
+int bin_matrix(ds_trainer *t, const float *rows, bool in_hbm, int64_t n, ds::DeviceBuffer<uint8_t> &out)
 {
     ds::DeviceBuffer<float> staged;
-    int status = staged.upload(rows, static_cast<size_t>(n) * t->nf);
+    int status = in_hbm ? DS_OK : staged.upload(rows, static_cast<size_t>(n) * t->nf);
     if (status == DS_OK) status = out.allocate(static_cast<size_t>(n) * t->nf);
     if (status != DS_OK) return status;
     const int64_t tiles = (n + ds::kBinTileRows - 1) / ds::kBinTileRows;
     const int grid = static_cast<int>(std::min<int64_t>(tiles, int64_t(t->compute_units) * 4));
-    hipLaunchKernelGGL(ds::ds_train_bin_kernel, dim3(grid), dim3(ds::kRowThreads), 0, t->stream, staged.ptr, n, t->nf,
-                       t->cuts.ptr, t->cut_offsets.ptr, out.ptr);
+    hipLaunchKernelGGL(ds::ds_train_bin_kernel, dim3(grid), dim3(ds::kRowThreads), 0, t->stream,
+                       in_hbm ? rows : staged.ptr, n, t->nf, t->cuts.ptr, t->cut_offsets.ptr, out.ptr);
     DS_HIP(hipGetLastError());
-    DS_HIP(hipStreamSynchronize(t->stream));   // `staged` is freed on return
+    DS_HIP(hipStreamSynchronize(t->stream));   // `staged` is freed on return; the caller's matrix is no longer read
     return DS_OK;
 }
 
@@ -426,38 +449,36 @@ int row_grid(const ds_trainer *t, int64_t n)
                                                                    int64_t(t->compute_units) * 8)));
 }
 
-}  // namespace
-
-extern "C" {
-
-int ds_trainer_create(const float *features, int64_t n, int32_t n_features, const float *cuts,
-                      const int32_t *cut_offsets, int32_t max_depth, double eta, double min_child_weight,
-                      double reg_lambda, double beta, int device, ds_trainer **out)
+// ds_trainer_create (`who`, features on the host) and ds_trainer_create_device (features in HBM)
+int create_trainer(const char *who, const float *features, bool in_hbm, int64_t n, int32_t n_features, const float *cuts,
+                   const int32_t *cut_offsets, int32_t max_depth, double eta, double min_child_weight, double reg_lambda,
+                   double beta, int device, ds_trainer **out)
 {
-    DS_REQUIRE(out != nullptr, "ds_trainer_create: out is null");
+    DS_REQUIRE(out != nullptr, "%s: out is null", who);
     *out = nullptr;
-    DS_REQUIRE(features && cuts && cut_offsets, "ds_trainer_create: null input");
-    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "ds_trainer_create: n = %lld rows out of range [1, 2^31)", (long long)n);
+    DS_REQUIRE(features && cuts && cut_offsets, "%s: null input", who);
+    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
     DS_REQUIRE(n_features >= 1 && n_features <= ds::kTrainFeaturesMax,
-               "ds_trainer_create: n_features = %d out of range [1, %d]", n_features, ds::kTrainFeaturesMax);
-    DS_REQUIRE(max_depth >= 1 && max_depth <= ds::kTrainMaxDepth, "ds_trainer_create: max_depth = %d out of range [1, %d]",
+               "%s: n_features = %d out of range [1, %d]", who, n_features, ds::kTrainFeaturesMax);
+    DS_REQUIRE(max_depth >= 1 && max_depth <= ds::kTrainMaxDepth, "%s: max_depth = %d out of range [1, %d]", who,
                max_depth, ds::kTrainMaxDepth);
     DS_REQUIRE(eta > 0 && eta < 1e30 && min_child_weight >= 0 && min_child_weight < 1e30 && reg_lambda >= 0 &&
                    reg_lambda < 1e30 && beta > 0 && beta < 1e30 && reg_lambda + min_child_weight > 0,
-               "ds_trainer_create: eta, beta must be positive, min_child_weight, reg_lambda non-negative and not both 0");
-    DS_REQUIRE(cut_offsets[0] == 0, "ds_trainer_create: cut_offsets[0] must be 0");
+               "%s: eta, beta must be positive, min_child_weight, reg_lambda non-negative and not both 0", who);
+    DS_REQUIRE(cut_offsets[0] == 0, "%s: cut_offsets[0] must be 0", who);
     for (int32_t f = 0; f < n_features; ++f) {
         const int32_t count = cut_offsets[f + 1] - cut_offsets[f];
-        DS_REQUIRE(count >= 0 && count <= ds::kTrainCutsMax, "ds_trainer_create: feature %d has %d cuts (at most %d)",
+        DS_REQUIRE(count >= 0 && count <= ds::kTrainCutsMax, "%s: feature %d has %d cuts (at most %d)", who,
                    f, count, ds::kTrainCutsMax);
         for (int32_t i = cut_offsets[f]; i < cut_offsets[f + 1]; ++i)
             DS_REQUIRE(cuts[i] == cuts[i] && (i == cut_offsets[f] || cuts[i - 1] < cuts[i]),
-                       "ds_trainer_create: the cuts of feature %d are not strictly ascending", f);
+                       "%s: the cuts of feature %d are not strictly ascending", who, f);
     }
     const int64_t hist_bytes = ((int64_t(1) << max_depth) - 1) * n_features * 512 * 8;
-    const int64_t bytes = n * n_features * 5 + n * 36 + hist_bytes;   // bins + staged rows, per-row state, histograms
+    // bins (+ the staged rows of a host matrix), per-row state, histograms
+    const int64_t bytes = n * n_features * (in_hbm ? 1 : 5) + n * 36 + hist_bytes;
     DS_HIP(hipSetDevice(device));
-    if (int status = check_free(bytes, "ds_trainer_create"); status != DS_OK) return status;
+    if (int status = check_free(bytes, who); status != DS_OK) return status;
     ds_trainer *t = new ds_trainer();
     t->device = device;
     t->n = n;
@@ -468,12 +489,12 @@ int ds_trainer_create(const float *features, int64_t n, int32_t n_features, cons
     if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
         t->compute_units = props.multiProcessorCount;
     int status = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) == hipSuccess ? DS_OK : DS_E_HIP;
-    if (status != DS_OK) ds::set_error("ds_trainer_create: hipStreamCreate failed");
+    if (status != DS_OK) ds::set_error("%s: hipStreamCreate failed", who);
     if (status == DS_OK) status = t->cut_offsets.upload(cut_offsets, static_cast<size_t>(n_features) + 1);
     if (status == DS_OK) status = t->cuts.allocate(std::max<size_t>(1, static_cast<size_t>(cut_offsets[n_features])));
     if (status == DS_OK && cut_offsets[n_features] > 0)
         status = t->cuts.upload(cuts, static_cast<size_t>(cut_offsets[n_features]));
-    if (status == DS_OK) status = bin_matrix(t, features, n, t->bins);
+    if (status == DS_OK) status = bin_matrix(t, features, in_hbm, n, t->bins);
     if (status == DS_OK) status = t->labels.allocate(n);
     if (status == DS_OK) status = t->leafsum.allocate(n);
     if (status == DS_OK) status = t->probabilities.allocate(n);
@@ -499,6 +520,46 @@ int ds_trainer_create(const float *features, int64_t n, int32_t n_features, cons
     return DS_OK;
 }
 
+// ds_trainer_set_eval (`who`, features on the host) and ds_trainer_set_eval_device (features in HBM)
+int set_eval(const char *who, ds_trainer *trainer, const float *features, bool in_hbm, const float *labels, int64_t n)
+{
+    DS_REQUIRE(trainer && features && labels, "%s: null argument", who);
+    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
+    DS_REQUIRE(trainer->rounds == 0, "%s: the evaluation set must be given before the first round", who);
+    for (int64_t r = 0; r < n; ++r)
+        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "%s: label %lld is not 0 or 1", who, (long long)r);
+    DS_HIP(hipSetDevice(trainer->device));
+    if (int status = check_free(n * trainer->nf * (in_hbm ? 1 : 5) + n * 8, who); status != DS_OK) return status;
+    int status = bin_matrix(trainer, features, in_hbm, n, trainer->eval_bins);
+    if (status == DS_OK) status = trainer->eval_labels.upload(labels, n);
+    if (status == DS_OK) status = trainer->eval_leafsum.allocate(n);
+    if (status != DS_OK) return status;
+    DS_HIP(hipMemsetAsync(trainer->eval_leafsum.ptr, 0, sizeof(float) * n, trainer->stream));
+    DS_HIP(hipStreamSynchronize(trainer->stream));
+    trainer->n_eval = n;
+    return DS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ds_trainer_create(const float *features, int64_t n, int32_t n_features, const float *cuts,
+                      const int32_t *cut_offsets, int32_t max_depth, double eta, double min_child_weight,
+                      double reg_lambda, double beta, int device, ds_trainer **out)
+{
+    return create_trainer("ds_trainer_create", features, false, n, n_features, cuts, cut_offsets, max_depth, eta,
+                          min_child_weight, reg_lambda, beta, device, out);
+}
+
+int ds_trainer_create_device(const float *d_features, int64_t n, int32_t n_features, const float *cuts,
+                             const int32_t *cut_offsets, int32_t max_depth, double eta, double min_child_weight,
+                             double reg_lambda, double beta, int device, ds_trainer **out)
+{
+    return create_trainer("ds_trainer_create_device", d_features, true, n, n_features, cuts, cut_offsets, max_depth, eta,
+                          min_child_weight, reg_lambda, beta, device, out);
+}
+
 void ds_trainer_destroy(ds_trainer *trainer)
 {
     if (!trainer) return;
@@ -521,20 +582,47 @@ int ds_trainer_set_labels(ds_trainer *trainer, const float *labels)
 
 int ds_trainer_set_eval(ds_trainer *trainer, const float *features, const float *labels, int64_t n)
 {
-    DS_REQUIRE(trainer && features && labels, "ds_trainer_set_eval: null argument");
-    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "ds_trainer_set_eval: n = %lld rows out of range [1, 2^31)", (long long)n);
-    DS_REQUIRE(trainer->rounds == 0, "ds_trainer_set_eval: the evaluation set must be given before the first round");
-    for (int64_t r = 0; r < n; ++r)
-        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "ds_trainer_set_eval: label %lld is not 0 or 1", (long long)r);
-    DS_HIP(hipSetDevice(trainer->device));
-    if (int status = check_free(n * trainer->nf * 5 + n * 8, "ds_trainer_set_eval"); status != DS_OK) return status;
-    int status = bin_matrix(trainer, features, n, trainer->eval_bins);
-    if (status == DS_OK) status = trainer->eval_labels.upload(labels, n);
-    if (status == DS_OK) status = trainer->eval_leafsum.allocate(n);
-    if (status != DS_OK) return status;
-    DS_HIP(hipMemsetAsync(trainer->eval_leafsum.ptr, 0, sizeof(float) * n, trainer->stream));
-    DS_HIP(hipStreamSynchronize(trainer->stream));
-    trainer->n_eval = n;
+    return set_eval("ds_trainer_set_eval", trainer, features, false, labels, n);
+}
+
+int ds_trainer_set_eval_device(ds_trainer *trainer, const float *d_features, const float *labels, int64_t n)
+{
+    return set_eval("ds_trainer_set_eval_device", trainer, d_features, true, labels, n);
+}
+
+int ds_gather_rows_device(const float *d_src, int32_t n_features, const int64_t *d_rows, int64_t n_rows, int64_t n_src,
+                          float *d_dst, void *stream)
+{
+    DS_REQUIRE(n_features >= 1 && n_features <= ds::kTrainFeaturesMax,
+               "ds_gather_rows_device: n_features = %d out of range [1, %d]", n_features, ds::kTrainFeaturesMax);
+    DS_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX, "ds_gather_rows_device: n_rows = %lld out of range [0, 2^31)",
+               (long long)n_rows);
+    DS_REQUIRE(n_src >= 1 && n_src <= INT32_MAX, "ds_gather_rows_device: n_src = %lld out of range [1, 2^31)",
+               (long long)n_src);
+    if (n_rows == 0) return DS_OK;
+    DS_REQUIRE(d_src && d_rows && d_dst, "ds_gather_rows_device: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ds::DeviceBuffer<int32_t> error;
+    if (int status = error.allocate(1); status != DS_OK) return status;
+    int32_t errors = 0;
+    DS_HIP(hipMemsetAsync(error.ptr, 0, sizeof(int32_t), s));
+    const auto grid = [](int64_t items) {
+        return dim3(static_cast<unsigned>(std::min<int64_t>((items + ds::kRowThreads - 1) / ds::kRowThreads, 256 * 16)));
+    };
+    hipLaunchKernelGGL(ds::ds_gather_check_kernel, grid(n_rows), dim3(ds::kRowThreads), 0, s, d_rows, n_rows, n_src,
+                       error.ptr);
+    DS_HIP(hipGetLastError());
+    DS_HIP(hipMemcpyAsync(&errors, error.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DS_HIP(hipStreamSynchronize(s));
+    if (errors != 0) {
+        ds::set_error("ds_gather_rows_device: %d row indexes are out of range [0, %lld)", errors, (long long)n_src);
+        return DS_E_ARG;
+    }
+    hipLaunchKernelGGL(ds::ds_gather_rows_kernel, grid(n_rows * n_features), dim3(ds::kRowThreads), 0, s,
+                       reinterpret_cast<const uint32_t *>(d_src), n_features, d_rows, n_rows, n_src,
+                       reinterpret_cast<uint32_t *>(d_dst));
+    DS_HIP(hipGetLastError());
+    DS_HIP(hipStreamSynchronize(s));
     return DS_OK;
 }
 

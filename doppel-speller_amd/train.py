@@ -3,10 +3,16 @@ columns with the custom objective `weighted_log_loss`, early-stopped on `custom_
 
 ForestTrainer grows the trees on the GPU (csrc/ds_train.hip, C ABI ds_trainer_*) by histogram gradient boosting with
 depth-wise growth, the rule of xgboost's `hist` method restated in DESIGN.md ("Training"); the result is a ForestModel.
-Parity with xgboost itself is unpinned, as for the forest.  The cuts are computed here, on the host, once per matrix.
+Parity with xgboost itself is unpinned, as for the forest.  The cuts are computed once per matrix: on the host
+(compute_cuts) for a host matrix, on the device (compute_cuts_device, csrc/ds_cuts.hip) for a matrix that lies in HBM.
+
+train_model(...) is the reference's one call: the training and evaluation sets from the raw titles, the booster, the
+evaluation error matrix and the feature importances, with the feature matrix never leaving HBM.
 """
 import concurrent.futures
 import ctypes
+import inspect
+import time
 
 import numpy as np
 
@@ -52,6 +58,44 @@ def compute_cuts(features, max_bin=256, threads=None):
     offsets[1:] = np.cumsum([c.shape[0] for c in per_feature])
     cuts = np.concatenate(per_feature).astype(np.float32) if per_feature else np.zeros(0, np.float32)
     return cuts, offsets
+
+
+def compute_cuts_device(d_features, n, max_bin=256, n_features=None, device=None, stream=None):
+    """compute_cuts of the first n rows of a contiguous float32[n, n_features] matrix in HBM (a DeviceArray, or an
+    address with n_features given), sorted on the device (ds_feature_cuts_device): the same (cuts, cut_offsets), bit
+    for bit.  The matrix must be complete on `stream`."""
+    n_features = _device_columns(d_features, n_features)
+    n = _positive_int("n", n, 1, (1 << 31) - 1)
+    max_bin = _positive_int("max_bin", max_bin, 2, 256)
+    if isinstance(d_features, _lib.DeviceArray) and n > d_features.shape[0]:
+        raise ValueError(f"n = {n} exceeds the matrix's {d_features.shape[0]} rows")
+    device = getattr(d_features, "device", 0) if device is None else device
+    cuts = np.empty(n_features * 254, np.float32)
+    offsets = np.empty(n_features + 1, np.int32)
+    _lib.check(_lib.lib().ds_feature_cuts_device(_lib.pointer(d_features), n, n_features, max_bin, _lib.pointer(cuts),
+                                                 _lib.pointer(offsets), device, _lib.pointer(stream)),
+               "ds_feature_cuts_device")
+    return cuts[:offsets[-1]].copy(), offsets
+
+
+def cuts_option(name, value):
+    """ds_cuts_option, for tests: cuts_option("column_group", g) sorts g columns at a time (0: sized from free HBM)."""
+    _lib.check(_lib.lib().ds_cuts_option(name.encode(), int(value)), "ds_cuts_option")
+
+
+def _device_columns(d_features, n_features):
+    """The column count of a matrix in HBM: the DeviceArray's second dimension, or what the caller says."""
+    if d_features is None:
+        raise ValueError("the device feature matrix is missing")
+    if n_features is None:
+        shape = getattr(d_features, "shape", None)
+        if shape is None or len(shape) != 2:
+            raise ValueError("n_features is needed for a device matrix that is not a 2-D DeviceArray")
+        n_features = shape[1]
+    n_features = _positive_int("n_features", n_features)
+    if n_features > FEATURES_MAX:
+        raise ValueError(f"the device features have {n_features} columns, the model takes 1 to {FEATURES_MAX}")
+    return n_features
 
 
 def _positive_int(name, value, low=1, high=None):
@@ -102,6 +146,14 @@ def validate_fit(features, target, eval_features=None, eval_target=None, num_boo
         if eval_features.shape[1] != features.shape[1]:
             raise ValueError(f"evaluation features have {eval_features.shape[1]} columns, training features "
                              f"{features.shape[1]}")
+    params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
+                                 beta, max_bin)
+    return features, target, eval_features, eval_target, params
+
+
+def validate_parameters(num_boost_round=1000, early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0,
+                        reg_lambda=1.0, beta=5.0, max_bin=256):
+    """The parameter checks of fit and fit_device -> params."""
     params = dict(num_boost_round=_positive_int("num_boost_round", num_boost_round),
                   early_stopping_rounds=_positive_int("early_stopping_rounds", early_stopping_rounds),
                   max_depth=_positive_int("max_depth", max_depth, 1, MAX_DEPTH_MAX),
@@ -110,7 +162,42 @@ def validate_fit(features, target, eval_features=None, eval_target=None, num_boo
                   max_bin=_positive_int("max_bin", max_bin, 2, 256))
     if params["reg_lambda"] == 0 and params["min_child_weight"] == 0:
         raise ValueError("reg_lambda and min_child_weight cannot both be 0 (an empty child would divide by zero)")
-    return features, target, eval_features, eval_target, params
+    return params
+
+
+def _device_labels(n, target, what):
+    n = _positive_int(f"the number of {what} rows", n, 1, (1 << 31) - 1)
+    target = np.asarray(target)
+    if target.ndim != 1 or target.shape[0] != n:
+        raise ValueError(f"{n} {what} rows but {target.reshape(-1).shape[0]} labels")
+    if target.dtype == object or not np.isin(target, (0, 1)).all():
+        raise ValueError(f"{what} labels must all be 0 or 1")
+    return n, np.ascontiguousarray(target, dtype=np.float32)
+
+
+def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
+                        early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
+                        max_bin=256, n_features=None):
+    """fit_device's checks (no library needed) -> (n, target, n_eval, eval_target, n_features, params): validate_fit
+    for matrices in HBM, of which only the shapes are known here."""
+    n_features = _device_columns(d_features, n_features)
+    n, target = _device_labels(n, target, "training")
+    if (d_eval_features is None) != (eval_target is None):
+        raise ValueError("d_eval_features and eval_target go together")
+    if d_eval_features is not None:
+        columns = _device_columns(d_eval_features, n_features if getattr(d_eval_features, "shape", None) is None
+                                  else None)
+        if columns != n_features:
+            raise ValueError(f"evaluation features have {columns} columns, training features {n_features}")
+        n_eval, eval_target = _device_labels(n_eval, eval_target, "evaluation")
+    else:
+        n_eval = 0
+    for array, rows, what in ((d_features, n, "training"), (d_eval_features, n_eval, "evaluation")):
+        if isinstance(array, _lib.DeviceArray) and rows > array.shape[0]:
+            raise ValueError(f"{rows} {what} rows exceed the device matrix's {array.shape[0]}")
+    params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
+                                 beta, max_bin)
+    return n, target, n_eval, eval_target, n_features, params
 
 
 class ForestTrainer:
@@ -157,6 +244,54 @@ class ForestTrainer:
         self._info = np.zeros((slots, 4), np.int32)
         self._leaf = np.zeros(slots, np.float32)
         return self
+
+    def begin_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, max_depth=5,
+                     eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, n_features=None):
+        """begin for matrices that already lie in HBM: contiguous float32[n, n_features] DeviceArrays (or addresses,
+        with n_features given), complete before the call; labels are host arrays.  The cuts come from
+        compute_cuts_device, the bins from the same kernel as begin's, so every later call works as after begin.  The
+        matrices are not kept and may be freed afterwards."""
+        n, target, n_eval, eval_target, n_features, params = validate_fit_device(
+            d_features, n, target, d_eval_features, n_eval, eval_target, max_depth=max_depth, eta=eta,
+            min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin,
+            n_features=n_features)
+        self.close()
+        self.params = params
+        self.n, self.n_features, self.n_eval = n, n_features, n_eval
+        self.timings = {}
+        mark = time.perf_counter()
+        self.cuts, self.cut_offsets = compute_cuts_device(d_features, n, params["max_bin"], n_features, self.device)
+        self.timings["cuts"] = (time.perf_counter() - mark) * 1000.0
+        self.trees, self.history, self.best_iteration = [], [], None
+        mark = time.perf_counter()
+        handle = ctypes.c_void_p()
+        library = _lib.lib()
+        _lib.check(library.ds_trainer_create_device(
+            _lib.pointer(d_features), self.n, self.n_features, _lib.pointer(self.cuts), _lib.pointer(self.cut_offsets),
+            params["max_depth"], params["eta"], params["min_child_weight"], params["reg_lambda"], params["beta"],
+            self.device, ctypes.byref(handle)), "ds_trainer_create_device")
+        self.handle = handle
+        _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
+        if n_eval:
+            _lib.check(library.ds_trainer_set_eval_device(self.handle, _lib.pointer(d_eval_features),
+                                                          _lib.pointer(eval_target), self.n_eval),
+                       "ds_trainer_set_eval_device")
+        self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
+        slots = (2 << params["max_depth"]) - 1
+        self._info = np.zeros((slots, 4), np.int32)
+        self._leaf = np.zeros(slots, np.float32)
+        return self
+
+    def fit_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
+                   early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
+                   max_bin=256, n_features=None):
+        """fit for matrices in HBM (begin_device, then fit's rounds and early stopping)."""
+        rounds = validate_fit_device(d_features, n, target, d_eval_features, n_eval, eval_target, num_boost_round,
+                                     early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda, beta, max_bin,
+                                     n_features)[5]
+        self.begin_device(d_features, n, target, d_eval_features, n_eval, eval_target, max_depth, eta,
+                          min_child_weight, reg_lambda, beta, max_bin, n_features)
+        return self._boost(rounds)
 
     def step(self):
         """Grow one tree; returns the evaluation error after it (None without an evaluation set)."""
@@ -207,6 +342,9 @@ class ForestTrainer:
                               max_depth, eta, min_child_weight, reg_lambda, beta, max_bin)[4]
         self.begin(features, target, eval_features, eval_target, max_depth, eta, min_child_weight, reg_lambda, beta,
                    max_bin)
+        return self._boost(rounds)
+
+    def _boost(self, rounds):
         best, best_error = None, None
         for round_ in range(rounds["num_boost_round"]):
             error = self.step()
@@ -260,7 +398,65 @@ class ForestTrainer:
 def evaluation_error_matrix(model, features, target, threshold=PREDICTION_PROBABILITY_THRESHOLD):
     """(true positives, true negatives, false positives, false negatives) of the model's predictions at `threshold`
     (train.py:get_evaluation_error_matrix)."""
-    predicted = model.predict(np.ascontiguousarray(features, dtype=np.float32)) > threshold
+    return _error_matrix(model.predict(np.ascontiguousarray(features, dtype=np.float32)), target, threshold)
+
+
+def _error_matrix(probabilities, target, threshold):
+    predicted = probabilities > threshold
     actual = np.asarray(target).reshape(-1) != 0
     return (int(np.count_nonzero(predicted & actual)), int(np.count_nonzero(~predicted & ~actual)),
             int(np.count_nonzero(predicted & ~actual)), int(np.count_nonzero(~predicted & actual)))
+
+
+class TrainModelResult:
+    """What train_model returns: `model` (ForestModel of best_iteration + 1 trees), `feature_importance` (the
+    reference's return value: ForestModel.feature_importance()), `error_matrix` ((tp, tn, fp, fn) on the evaluation set
+    at 0.9, what the reference logs; None without an evaluation set), `best_iteration`, `history`, `rows` (the
+    DataFrame of FeatureEngineering.rows) and `timings` (milliseconds per stage, "total" for the call)."""
+
+    def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings):
+        self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
+        self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
+
+
+def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
+                transform=True, evaluation_fractions=None, **fit_parameters):
+    """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
+    ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
+    HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
+    fit_parameters: those of ForestTrainer.fit (num_boost_round, early_stopping_rounds, max_depth, eta, ...).
+    Everything is validated before any device work.  Evaluation fractions of 0 for all three kinds train without an
+    evaluation set: every round is kept and error_matrix is None."""
+    from .training_set import FeatureEngineering
+    started = time.perf_counter()
+    unknown = set(fit_parameters) - set(inspect.signature(validate_parameters).parameters)
+    if unknown:
+        raise ValueError(f"unknown fit parameters {sorted(unknown)}")
+    validate_parameters(**fit_parameters)
+    fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
+                            sample_n=sample_n, seed=seed, device=device, transform=transform,
+                            evaluation_fractions=evaluation_fractions)
+    sets = fe.generate_device_data_sets()
+    timings = dict(fe.timings)
+    trainer = ForestTrainer(device)
+    mark = time.perf_counter()
+    has_eval = sets.n_evaluation > 0
+    model = trainer.fit_device(sets.train, sets.n_train, sets.train_target, sets.evaluation if has_eval else None,
+                               sets.n_evaluation, sets.evaluation_target if has_eval else None, **fit_parameters)
+    fit_ms = (time.perf_counter() - mark) * 1000.0
+    timings["cuts"], timings["bin"] = trainer.timings["cuts"], trainer.timings["bin"]
+    timings["boost"] = fit_ms - timings["cuts"] - timings["bin"]
+    mark = time.perf_counter()
+    error_matrix = None
+    if has_eval:
+        d_probabilities = _lib.DeviceArray((sets.n_evaluation,), np.float32, device)
+        model.predict_device(sets.evaluation, sets.n_evaluation, None, d_probabilities)
+        error_matrix = _error_matrix(d_probabilities.to_host(), sets.evaluation_target,
+                                     PREDICTION_PROBABILITY_THRESHOLD)
+        d_probabilities.free()
+    timings["evaluate"] = (time.perf_counter() - mark) * 1000.0
+    best_iteration, history = trainer.best_iteration, list(trainer.history)
+    trainer.close()
+    sets.free()
+    timings["total"] = (time.perf_counter() - started) * 1000.0
+    return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings)

@@ -176,6 +176,38 @@ def generate_misspelled_names(titles, seed=0, device=0):
     return misspell_table(TitleTable(enc, lengths, None, device), None, seed, device).strings()
 
 
+class DeviceDataSets:
+    """The training and evaluation sets with their feature matrices in HBM (FeatureEngineering.
+    generate_device_data_sets): `train` / `evaluation` are DeviceArrays float32[max(rows, 1), 66] of which the first
+    n_train / n_evaluation rows count, `train_target` / `evaluation_target` host float32 labels.  `features` is the
+    full matrix (n_rows rows) when it was kept, else None."""
+
+    def __init__(self, train, n_train, train_target, evaluation, n_evaluation, evaluation_target, misspelled, features,
+                 n_rows):
+        self.train, self.n_train, self.train_target = train, int(n_train), train_target
+        self.evaluation, self.n_evaluation, self.evaluation_target = evaluation, int(n_evaluation), evaluation_target
+        self.features, self.n_rows = features, int(n_rows)
+        self._misspelled = misspelled
+
+    def to_host(self):
+        """(train, train_target, evaluation, evaluation_target) as generate_train_and_evaluation_data_sets returns
+        them."""
+        return (self.train.to_host(self.n_train), self.train_target, self.evaluation.to_host(self.n_evaluation),
+                self.evaluation_target)
+
+    def misspelled_titles(self):
+        """The queries of the kind 1 rows, in order, decoded from the device table."""
+        return self._misspelled.strings() if self._misspelled is not None else []
+
+    def free(self):
+        """Frees the matrices in HBM (the labels stay)."""
+        for array in (self.train, self.evaluation, self.features):
+            if array is not None:
+                array.free()
+        if self._misspelled is not None:
+            self._misspelled.close()
+
+
 class FeatureEngineering:
     """FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids).
     generate_train_and_evaluation_data_sets() -> (train, train_target, evaluation, evaluation_target), float32.
@@ -189,7 +221,8 @@ class FeatureEngineering:
 
     After a call: `rows` (DataFrame: kind, query_index = train row for kinds 2 / 3 and truth row for kind 1,
     truth_row, target, evaluation), `misspelled_titles` (the queries of the kind 1 rows, in order), `features` (every
-    row's construct_features) and `timings` (milliseconds per stage)."""
+    row's construct_features) and `timings` (milliseconds per stage).  generate_device_data_sets() is the form that
+    leaves the matrices in HBM (DeviceDataSets)."""
 
     def __init__(self, truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0,
                  device=0, transform=True, chunk_queries=None, evaluation_fractions=None):
@@ -211,9 +244,92 @@ class FeatureEngineering:
 
     def generate_train_and_evaluation_data_sets(self):
         """feature_engineering.py:321-378: (train, train_target, evaluation, evaluation_target)."""
-        import pandas as pd
         timings = dict.fromkeys(("host_prepare", "truth_side", "top_k", "sample_pairs", "misspell", "features",
                                  "copy_back", "split"), 0.0)
+        stage = self._device_stages(timings)
+        d_features, n_rows, misspelled = stage["d_features"], stage["n_rows"], stage["misspelled"]
+
+        mark = time.perf_counter()
+        features = d_features.to_host(n_rows)
+        pair_t, target = self._pairs_to_host(stage)
+        self.misspelled_titles = misspelled.strings() if misspelled is not None else []
+        timings["copy_back"] = (time.perf_counter() - mark) * 1000.0
+
+        # ---- rows and the split
+        mark = time.perf_counter()
+        target, train_rows, evaluation_rows = self._rows_and_split(stage, pair_t, target)
+        self.features = features
+        out = (features[train_rows], target[train_rows], features[evaluation_rows], target[evaluation_rows])
+        timings["split"] = (time.perf_counter() - mark) * 1000.0
+        self.timings = timings
+        return out
+
+    def generate_device_data_sets(self, keep_features=False):
+        """generate_train_and_evaluation_data_sets with the feature matrix left in HBM -> DeviceDataSets: the same
+        stages up to and including the features launches; the pairs' truth rows and targets come back (8 B per row)
+        and fill `rows` exactly as on the host path; evaluation_split needs only the kinds; its two index arrays are
+        uploaded and two ds_gather_rows_device calls make the contiguous training and evaluation matrices.  The full
+        matrix is freed unless keep_features (then DeviceDataSets.features holds it).  The misspelled titles stay
+        encoded on the device (DeviceDataSets.misspelled_titles() decodes them on demand); `features` and
+        `misspelled_titles` of this object stay None on this path.  `timings` has no copy_back of the features; it
+        gains `gather`."""
+        timings = dict.fromkeys(("host_prepare", "truth_side", "top_k", "sample_pairs", "misspell", "features",
+                                 "copy_back", "split", "gather"), 0.0)
+        stage = self._device_stages(timings)
+        d_features, n_rows, device = stage["d_features"], stage["n_rows"], self.device
+
+        mark = time.perf_counter()
+        pair_t, target = self._pairs_to_host(stage)
+        timings["copy_back"] = (time.perf_counter() - mark) * 1000.0
+        mark = time.perf_counter()
+        target, train_rows, evaluation_rows = self._rows_and_split(stage, pair_t, target)
+        self.features = self.misspelled_titles = None
+        timings["split"] = (time.perf_counter() - mark) * 1000.0
+
+        mark = time.perf_counter()
+        parts = []
+        for rows in (train_rows, evaluation_rows):
+            d_part = _lib.DeviceArray((max(rows.shape[0], 1), FEATURES_COUNT), np.float32, device)
+            if rows.shape[0]:
+                d_index = _lib.DeviceArray.from_host(rows.astype(np.int64), device)
+                _lib.check(_lib.lib().ds_gather_rows_device(d_features.ptr, FEATURES_COUNT, d_index.ptr, rows.shape[0],
+                                                            n_rows, d_part.ptr, None), "ds_gather_rows_device")
+                d_index.free()
+            parts.append(d_part)
+        if not keep_features:
+            d_features.free()
+        timings["gather"] = (time.perf_counter() - mark) * 1000.0
+        self.timings = timings
+        return DeviceDataSets(parts[0], train_rows.shape[0], target[train_rows], parts[1], evaluation_rows.shape[0],
+                              target[evaluation_rows], stage["misspelled"], d_features if keep_features else None, n_rows)
+
+    def _pairs_to_host(self, stage):
+        """The sampled pairs' truth rows and targets (8 B per row of kinds 2 and 3)."""
+        if not stage["n_selected"]:
+            return np.zeros(0, np.int32), np.zeros(0, np.float32)
+        return stage["d_pair_t"].to_host(), stage["d_target"].to_host()
+
+    def _rows_and_split(self, stage, pair_t, target):
+        """Fills `rows`; returns (every row's target, train rows, evaluation rows)."""
+        import pandas as pd
+        negative, positive, generated, selected = (stage[k] for k in ("negative", "positive", "generated", "selected"))
+        sample_n = self.sample_n
+        kind = np.concatenate((np.full(negative.shape[0] * sample_n, KIND_NEGATIVE, np.uint8),
+                               np.full(positive.shape[0] * sample_n, KIND_POSITIVE, np.uint8),
+                               np.full(generated.shape[0], KIND_GENERATED, np.uint8)))
+        query_index = np.concatenate((np.repeat(selected, sample_n), generated.astype(np.int64)))
+        truth_row = np.concatenate((pair_t.astype(np.int64), generated.astype(np.int64)))
+        target = np.concatenate((target, np.ones(generated.shape[0], np.float32)))
+        train_rows, evaluation_rows = evaluation_split(kind, self.seed, self.evaluation_fractions)
+        evaluation = np.zeros(stage["n_rows"], dtype=bool)
+        evaluation[evaluation_rows] = True
+        self.rows = pd.DataFrame({"kind": kind, "query_index": query_index, "truth_row": truth_row, "target": target,
+                                  "evaluation": evaluation})
+        return target, train_rows, evaluation_rows
+
+    def _device_stages(self, timings):
+        """The stages both forms share, up to and including the features launches: every row's construct_features in
+        one matrix in HBM."""
         started = time.perf_counter()
         device, k, sample_n = self.device, self.top_n, self.sample_n
         if self._truth is None:
@@ -248,8 +364,6 @@ class FeatureEngineering:
 
         # ---- top-n and the sample of every selected train row, one chunk of rows at a time
         timer = _lib.Timer(device)
-        pair_t = np.zeros(0, np.int32)
-        target = np.zeros(0, np.float32)
         if n_selected:
             chunk = min(n_selected, self.chunk_queries or default_chunk(device, 4 * k + 64))
             d_rows = _lib.DeviceArray((chunk, k), np.int32, device)
@@ -301,28 +415,6 @@ class FeatureEngineering:
         timer.stop()
         timings["features"] = timer.elapsed_ms()
 
-        mark = time.perf_counter()
-        features = d_features.to_host(n_rows)
-        if n_selected:
-            pair_t, target = d_pair_t.to_host(), d_target.to_host()
-        self.misspelled_titles = misspelled.strings() if misspelled is not None else []
-        timings["copy_back"] = (time.perf_counter() - mark) * 1000.0
-
-        # ---- rows and the split
-        mark = time.perf_counter()
-        kind = np.concatenate((np.full(negative.shape[0] * sample_n, KIND_NEGATIVE, np.uint8),
-                               np.full(positive.shape[0] * sample_n, KIND_POSITIVE, np.uint8),
-                               np.full(generated.shape[0], KIND_GENERATED, np.uint8)))
-        query_index = np.concatenate((np.repeat(selected, sample_n), generated.astype(np.int64)))
-        truth_row = np.concatenate((pair_t.astype(np.int64), generated.astype(np.int64)))
-        target = np.concatenate((target, np.ones(generated.shape[0], np.float32)))
-        train_rows, evaluation_rows = evaluation_split(kind, self.seed, self.evaluation_fractions)
-        evaluation = np.zeros(n_rows, dtype=bool)
-        evaluation[evaluation_rows] = True
-        self.rows = pd.DataFrame({"kind": kind, "query_index": query_index, "truth_row": truth_row, "target": target,
-                                  "evaluation": evaluation})
-        self.features = features
-        out = (features[train_rows], target[train_rows], features[evaluation_rows], target[evaluation_rows])
-        timings["split"] = (time.perf_counter() - mark) * 1000.0
-        self.timings = timings
-        return out
+        return dict(d_features=d_features, n_rows=n_rows, n_selected=n_selected, negative=negative, positive=positive,
+                    generated=generated, selected=selected, misspelled=misspelled,
+                    d_pair_t=d_pair_t if n_selected else None, d_target=d_target if n_selected else None)

@@ -11,9 +11,11 @@ It prints the fraction of correct final answers of that model next to a model tr
 top-k pairs of the train queries labelled with their known source row) and the random stand-in ensemble
 (synth.make_forest) that the other examples use.
 
-    python examples/train_model.py [n_truth] [n_queries] [top_n] [model.npz]
+    python examples/train_model.py [--one-call] [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
+--one-call trains with ds.train_model(...), the same steps in one call with the feature matrix kept in HBM; the model
+is the same.
 """
 import os
 import sys
@@ -43,7 +45,7 @@ def _stand_in():
                           stand_in["missing"], stand_in["tree_offsets"], stand_in["n_features"], stand_in["base_margin"])
 
 
-def main(n_truth=20000, n_queries=4000, top_n=10, path=None):
+def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False):
     train = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     evaluation = synth.make_workload(n_truth, n_queries // 4, seed=11, query_seed=102)
     held_out = synth.make_workload(n_truth, n_queries, seed=11, query_seed=103)
@@ -52,22 +54,37 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None):
     truth_titles = synth._to_strings(train.t_flat, train.t_off)
     train_titles = synth._to_strings(train.q_flat, train.q_off)
     train_ids = np.where(train.actual_row >= 0, train.title_id[np.maximum(train.actual_row, 0)], -1)
-    fe = ds.FeatureEngineering(truth_titles, train.title_id, train_titles, train_ids)
-    features, labels, eval_features, eval_labels = fe.generate_train_and_evaluation_data_sets()
-    kinds = fe.rows["kind"].value_counts().sort_index().to_dict()
-    print(f"training set: {fe.rows.shape[0]} rows (generated / negative / positive: {kinds.get(1, 0)} / "
-          f"{kinds.get(2, 0)} / {kinds.get(3, 0)}), {eval_features.shape[0]} held out for evaluation; "
-          + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.timings.items()))
-    t0 = time.perf_counter()
-    trainer = ds.ForestTrainer()
-    model = trainer.fit(features, labels, eval_features, eval_labels)
-    t1 = time.perf_counter()
-    print(f"training: {features.shape[0]} rows ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
-          f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error {trainer.history[trainer.best_iteration]})")
-    tp, tn, fp, fn = ds.evaluation_error_matrix(model, eval_features, eval_labels)
-    print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
-    top = np.argsort(-model.feature_importance())[:5]
-    print("most used features:", ", ".join(f"f{f} {model.feature_importance()[f]:.3f}" for f in top))
+    if one_call:
+        t0 = time.perf_counter()
+        result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids)
+        t1 = time.perf_counter()
+        model = result.model
+        kinds = result.rows["kind"].value_counts().sort_index().to_dict()
+        print(f"train_model: {result.rows.shape[0]} rows (generated / negative / positive: {kinds.get(1, 0)} / "
+              f"{kinds.get(2, 0)} / {kinds.get(3, 0)}), {len(result.history)} rounds in {t1 - t0:.2f}s in all, best "
+              f"round {result.best_iteration} (custom error {result.history[result.best_iteration]}); "
+              + ", ".join(f"{k} {v:.1f} ms" for k, v in result.timings.items()))
+        tp, tn, fp, fn = result.error_matrix
+        print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
+        top = np.argsort(-result.feature_importance)[:5]
+        print("most used features:", ", ".join(f"f{f} {result.feature_importance[f]:.3f}" for f in top))
+    else:
+        fe = ds.FeatureEngineering(truth_titles, train.title_id, train_titles, train_ids)
+        features, labels, eval_features, eval_labels = fe.generate_train_and_evaluation_data_sets()
+        kinds = fe.rows["kind"].value_counts().sort_index().to_dict()
+        print(f"training set: {fe.rows.shape[0]} rows (generated / negative / positive: {kinds.get(1, 0)} / "
+              f"{kinds.get(2, 0)} / {kinds.get(3, 0)}), {eval_features.shape[0]} held out for evaluation; "
+              + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.timings.items()))
+        t0 = time.perf_counter()
+        trainer = ds.ForestTrainer()
+        model = trainer.fit(features, labels, eval_features, eval_labels)
+        t1 = time.perf_counter()
+        print(f"training: {features.shape[0]} rows ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
+              f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error {trainer.history[trainer.best_iteration]})")
+        tp, tn, fp, fn = ds.evaluation_error_matrix(model, eval_features, eval_labels)
+        print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
+        top = np.argsort(-model.feature_importance())[:5]
+        print("most used features:", ", ".join(f"f{f} {model.feature_importance()[f]:.3f}" for f in top))
 
     path = path or os.path.join(tempfile.mkdtemp(prefix="ds_model_"), "model.npz")
     model.save(path)
@@ -86,5 +103,5 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None):
 
 
 if __name__ == "__main__":
-    arguments = sys.argv[1:]
-    main(*[int(a) for a in arguments[:3]], *arguments[3:4])
+    arguments = [a for a in sys.argv[1:] if a != "--one-call"]
+    main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:])

@@ -291,6 +291,34 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
 int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, int64_t *gradients, uint8_t *bins,
                     float *eval_margins);
 
+/* ---- the train-model step without a host copy of the feature matrix ("One call") ----------------
+ * ds_feature_cuts_device: compute_cuts of a contiguous float32[n][n_features] matrix in HBM, bit-identical to the host
+ * rule for any input: per column the non-NaN values with -0.0 read as +0.0; at most max_bin - 1 distinct ones: the sorted
+ * distinct values without the smallest; else v[(j * m) / (max_bin - 1)], j = 1 .. max_bin - 2, of the m sorted values v,
+ * without repeats and without values equal to v[0].  cuts (host, room for n_features * 254) receives cut_offsets[n_features]
+ * values and cut_offsets (host, n_features + 1) their starts; nothing beyond those is written.  n in [1, 2^31),
+ * n_features in [1, 96], max_bin in [2, 256].  Enqueued on `stream`, which is synchronised before returning; the matrix
+ * must be complete on that stream.  ds_cuts_option("column_group", g) is for tests: g > 0 sorts g columns at a time
+ * instead of what a quarter of the free HBM holds (0: back to that); the result does not depend on it. */
+int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_features, int32_t max_bin, float *cuts,
+                           int32_t *cut_offsets, int device, void *stream);
+int ds_cuts_option(const char *name, int64_t value);
+/* ds_trainer_create / ds_trainer_set_eval for a contiguous float32[n][n_features] matrix that already lies in HBM on
+ * `device` (the trainer's device for the evaluation set): no staged copy, the same binning kernel and so the same bins.
+ * The caller must have finished writing the matrix (synchronise the stream that wrote it) before the call.  The entry
+ * synchronises before it returns and keeps no pointer to the matrix, which may be freed afterwards.  Labels are host
+ * pointers as in the host entries. */
+int ds_trainer_create_device(const float *d_features, int64_t n, int32_t n_features, const float *cuts,
+                             const int32_t *cut_offsets, int32_t max_depth, double eta, double min_child_weight,
+                             double reg_lambda, double beta, int device, ds_trainer **out);
+int ds_trainer_set_eval_device(ds_trainer *trainer, const float *d_features, const float *labels, int64_t n);
+/* d_dst[i][..] = d_src[d_rows[i]][..] for i < n_rows: rows of n_features (1..96) float32, all pointers in the HBM of the
+ * current device, d_rows in any order, repeats allowed.  A row index outside [0, n_src) is found by a check on the device
+ * before the gather is launched: DS_E_ARG, no source row read and d_dst untouched.  n_rows = 0 does nothing.  Enqueued on
+ * `stream`, which is synchronised before returning. */
+int ds_gather_rows_device(const float *d_src, int32_t n_features, const int64_t *d_rows, int64_t n_rows, int64_t n_src,
+                          float *d_dst, void *stream);
+
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
  * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
