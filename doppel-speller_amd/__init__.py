@@ -7,6 +7,7 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
                        truth_words_counts, space_code, number_of_truth_titles, dummy, response)   (in place)
     FEATURES_COUNT, encode_title, get_truth_words_counts
     Prediction(truth_titles, truth_title_ids, model).generate_test_predictions(titles)   -> final_output (predict.py)
+        .ranked_matches(titles, n)   -> the best n candidates per title in order, with scores (this project's own)
     ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
@@ -25,7 +26,7 @@ from .feature_engineering import (  # noqa: F401
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
 from .forest import ForestModel  # noqa: F401
-from .prediction import Prediction  # noqa: F401
+from .prediction import RANKED_COLUMNS, Candidates, Prediction, validate_rank  # noqa: F401
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, train_model)

@@ -19,6 +19,7 @@ from .match_maker import TruthIndex
 PREDICTION_PROBABILITY_THRESHOLD = 0.9  # settings.py:76
 # device bytes per query and candidate: features (66 float32), prediction, top-k row, ratio, pair (q, t)
 BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
+BYTES_PER_RANK = 4 + 4 + 1 + 1          # one slot of the rank output: row, probability, ratio, stage
 MAX_GRAMS = 253                         # tri-grams of a 255-character title: columns of one query row at most
 
 
@@ -53,6 +54,7 @@ class CandidatePipeline:
         self.rows_ptr = _lib.pointer(self._rows if rows_ptr is None else rows_ptr)
         self.d_features = _lib.DeviceArray((capacity * k, FEATURES_COUNT), np.float32, device)
         self._close = self._exact = self._pairs = self._predictions = self._matches = None
+        self._ranked, self._ranked_n = None, 0
 
     def _allocate_stages(self):
         """The outputs of the stages after top-k (by `over`, or by the first of their enqueues)."""
@@ -181,6 +183,31 @@ class CandidatePipeline:
         _lib.check(_lib.lib().ds_select_matches_device(pair_q.ptr, pair_t.ptr, self._predictions.ptr, n_remaining, self.k,
                                                        float(threshold), self._matches[0].ptr, self._matches[1].ptr,
                                                        _lib.pointer(stream)), "ds_select_matches_device")
+
+    def enqueue_rank_matches(self, n, stream=None):
+        """The best n candidates of every query in order (ds_rank_matches_device): the exact or close match first, then
+        the others by the model's probability, over this pipeline's own buffers: the top-k rows, the predictions of
+        `enqueue_predict` on all pairs, the ratios and best rows of `enqueue_close_matches` and the exact rows of
+        `enqueue_exact_matches`.  The outputs are allocated by the first call, for `capacity` queries of n slots."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= self.k:
+            raise ValueError(f"n must be an integer in [1, k = {self.k}], not {n!r}")
+        self._allocate_stages()
+        if self._ranked is None or self._ranked[0].shape[0] < self.capacity * n:
+            size, device = max(1, self.capacity * int(n)), self.device
+            self._ranked = (_lib.DeviceArray((size,), np.int32, device), _lib.DeviceArray((size,), np.float32, device),
+                            _lib.DeviceArray((size,), np.uint8, device), _lib.DeviceArray((size,), np.int8, device))
+        self._ranked_n = int(n)
+        _lib.check(_lib.lib().ds_rank_matches_device(
+            self.rows_ptr, self._predictions.ptr, self._close[0].ptr, self._exact.ptr, self._close[1].ptr,
+            self.n_queries, self.k, self._ranked_n, self.n_truth, *(a.ptr for a in self._ranked), _lib.pointer(stream)),
+            "ds_rank_matches_device")
+
+    def ranked(self, n):
+        """(rows int32[Q, n], probabilities float32[Q, n], ratios uint8[Q, n], stages int8[Q, n]) of the last
+        `enqueue_rank_matches(n)`: only the n slots per query are copied back."""
+        if n != self._ranked_n:
+            raise ValueError(f"the last enqueue_rank_matches ranked {self._ranked_n} slots per query, not {n}")
+        return tuple(a.to_host(self.n_queries * n).reshape(self.n_queries, n) for a in self._ranked)
 
     def matches(self, n_remaining):
         """(query rows, matched truth row or -1) of the last `enqueue_select_matches`."""

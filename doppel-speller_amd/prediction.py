@@ -17,6 +17,7 @@ Differences from the reference, on purpose:
   - `closest_search_single_title` returns the exact or close match when there is one; the reference raises there
     (`_find_matches_using_model` is reached with no rows and `np.vstack([])` fails).
 """
+import collections
 import ctypes
 import time
 import unicodedata
@@ -27,12 +28,17 @@ from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
                                   truth_word_counts)
 from .match_maker import NativeProblem, TruthIndex
-from .pipeline import BYTES_PER_PAIR, MAX_GRAMS, PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline
+from .pipeline import (BYTES_PER_PAIR, BYTES_PER_RANK, MAX_GRAMS, PREDICTION_PROBABILITY_THRESHOLD,
+                       CandidatePipeline)
 
 TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
 N_GRAM = 3                               # settings.py:15
 PREPARE_QUERIES = ("device", "host")
 STAGE_NONE, STAGE_EXACT, STAGE_CLOSE, STAGE_MODEL = 0, 1, 2, 3
+RANKED_COLUMNS = ("test_index", "rank", "title_id", "match_row", "probability", "levenshtein_ratio", "stage")
+# what ranked_matches(keep_candidates=True) keeps of a call, per query: the top-n rows, their fuzzy ratios and model
+# probabilities, the exact row and the close row (-1: none; the close row also where the exact stage matched)
+Candidates = collections.namedtuple("Candidates", ("rows", "ratios", "probabilities", "exact", "close"))
 
 _CODE_OF = np.zeros(256, dtype=np.uint8)      # ASCII byte -> code of encode_title (feature_engineering.py:298-307)
 _ALLOWED = np.zeros(256, dtype=bool)          # the characters a transformed title may hold (the fill '-' is not one)
@@ -79,6 +85,31 @@ def validate_queries(titles, test_index):
     if np.unique(index).shape[0] != index.shape[0]:
         raise ValueError("test indexes must be unique")
     return index
+
+
+def validate_rank(n, top_n):
+    """ranked_matches' check of `n` (no library needed): a positive integer up to the top_n candidates of a query."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"n must be a positive integer, not {n!r}")
+    if n > top_n:
+        raise ValueError(f"n = {n} exceeds the top_n = {top_n} candidates of a title")
+    return int(n)
+
+
+def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_ids):
+    """ranked_matches' answer from the [Q, n] slots of the rank stage: one line per filled slot (stage != 0), sorted by
+    test_index, then rank (slot + 1: the filled slots of a query come first)."""
+    import pandas as pd
+    test_index = np.asarray(test_index, dtype=np.int64)
+    query, slot = np.nonzero(np.asarray(stages) != STAGE_NONE)
+    order = np.argsort(test_index[query], kind="stable")
+    query, slot = query[order], slot[order]
+    match_row = np.asarray(rows)[query, slot].astype(np.int64)
+    return pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
+                         "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
+                         "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
+                         "levenshtein_ratio": np.asarray(ratios, dtype=np.uint8)[query, slot],
+                         "stage": np.asarray(stages, dtype=np.int8)[query, slot]}, columns=list(RANKED_COLUMNS))
 
 
 def combine_stages(exact_row, close_row, model_row):
@@ -337,6 +368,7 @@ class Prediction:
         self.chunk_queries = chunk_queries
         self.prepare_queries = prepare_queries
         self.details = None
+        self.candidates = None
         self.timings = {}
 
         self.truth_titles = self._transform(truth_titles)
@@ -352,9 +384,11 @@ class Prediction:
     def _check_characters(chars, offsets, what):
         check_characters(chars, offsets, what)
 
-    def _default_chunk(self, device_rows=False):
+    def _default_chunk(self, device_rows=False, rank_slots=0):
         # device_rows: the pipeline's own query CSR at capacity (rowptr, 253 columns, q_maxint per query)
-        return default_chunk(self.device, BYTES_PER_PAIR * self.top_n + 64 + (8 + 4 * MAX_GRAMS + 8) * device_rows)
+        # rank_slots: the slots per query of the rank stage's output
+        return default_chunk(self.device, BYTES_PER_PAIR * self.top_n + 64 + (8 + 4 * MAX_GRAMS + 8) * device_rows +
+                             BYTES_PER_RANK * rank_slots)
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
@@ -380,18 +414,58 @@ class Prediction:
                 "title_id": int(self.truth_title_ids[row]) if row >= 0 else TRAIN_NOT_FOUND_VALUE,
                 "prediction": float(details["probability"].iloc[0])}
 
+    def ranked_matches(self, titles, n=5, test_index=None, keep_candidates=False):
+        """The best `n` candidates of every title, in order, with their scores: a DataFrame in long form [test_index,
+        rank (from 1), title_id, match_row, probability, levenshtein_ratio, stage] sorted by test_index, then rank, one
+        line per filled slot (a title with fewer than n candidates has fewer lines).
+
+        The exact match of a title, else its close match, comes first with probability 1.0 (rank 1 is then the answer
+        of generate_test_predictions); the other candidates of the Jaccard top_n follow at stage 3, by the model's
+        probability descending, the earlier candidate first on a tie.  Every candidate is scored, also those of a
+        title an earlier stage matched; the order is made on the device (CandidatePipeline.enqueue_rank_matches) and n
+        entries per title come back.  keep_candidates: `candidates` then holds the call's intermediates (Candidates:
+        rows int32[Q, top_n], ratios uint8[Q, top_n], probabilities float32[Q, top_n], exact int32[Q], close
+        int32[Q]) in the order of `titles`, to re-rank by another rule; else it is None.  `details` is left alone."""
+        n = validate_rank(n, self.top_n)
+        titles = list(titles)
+        test_index = validate_queries(titles, test_index)
+        timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model", "rank",
+                                 "copy_back"), 0.0)
+        count, k = len(titles), self.top_n
+        slots = (np.full((count, n), -1, dtype=np.int32), np.full((count, n), np.nan, dtype=np.float32),
+                 np.zeros((count, n), dtype=np.uint8), np.zeros((count, n), dtype=np.int8))
+        kept = Candidates(np.empty((count, k), np.int32), np.empty((count, k), np.uint8), np.empty((count, k), np.float32),
+                          np.empty(count, np.int32), np.empty(count, np.int32)) if keep_candidates else None
+        for pipeline, events in self._chunks(titles, timings, rank_slots=n):
+            self._rank_chunk(pipeline, events, timings, n, slots, kept)
+        self.timings = timings
+        self.candidates = kept
+        return ranked_frame(test_index, *slots, self.truth_title_ids)
+
     def _run(self, titles, test_index, single=False):
         import pandas as pd
         timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "remaining_pairs",
                                  "features", "model", "select_matches", "copy_back"), 0.0)
+        n = len(titles)
+        match_row = np.full(n, -1, dtype=np.int64)
+        stage = np.zeros(n, dtype=np.int8)
+        probability = np.full(n, np.nan, dtype=np.float32)
+        for pipeline, events in self._chunks(titles, timings):
+            self._chunk(pipeline, events, timings, match_row, stage, probability, single)
+        title_id = np.where(match_row >= 0, self.truth_title_ids[np.maximum(match_row, 0)], TRAIN_NOT_FOUND_VALUE)
+        self.timings = timings
+        return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
+                             "probability": probability})
+
+    def _chunks(self, titles, timings, rank_slots=0):
+        """The one loop over the queries: prepares the titles (on the device or on the host), then yields (pipeline,
+        events) with each chunk loaded in turn, events holding one Timer per device stage of `timings`.  Fills
+        timings' host_prepare and prepare_queries; yields nothing for no titles."""
         device_path = self.prepare_queries == "device"
         if device_path:
             timings["prepare_queries"] = 0.0
         started = time.perf_counter()
         n = len(titles)
-        match_row = np.full(n, -1, dtype=np.int64)
-        stage = np.zeros(n, dtype=np.int8)
-        probability = np.full(n, np.nan, dtype=np.float32)
         if device_path:
             self._last_queries = None
             if n:
@@ -402,9 +476,7 @@ class Prediction:
             queries = self._transform(titles)
             self._last_queries = queries
         if n == 0:
-            self.timings = timings
-            return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": match_row,
-                                 "stage": stage, "probability": probability})
+            return
         if not device_path:
             chars, offsets = _pack(queries)
             self._check_characters(chars, offsets, "query")
@@ -412,7 +484,7 @@ class Prediction:
                                                    columns=self._columns)
             enc, lengths = encode_collection(chars, offsets, _CODE_OF)
             query_table = TitleTable(enc, lengths, None, self.device)
-        chunk = min(n, self.chunk_queries or self._default_chunk(device_path))
+        chunk = min(n, self.chunk_queries or self._default_chunk(device_path, rank_slots))
         pipeline = CandidatePipeline.over(self.index, self.truth_table, query_table, self.top_n, chunk, self.device)
         timings["host_prepare"] = (time.perf_counter() - started) * 1000.0 - timings.get("prepare_queries", 0.0)
         events = {name: _lib.Timer(self.device) for name in timings
@@ -426,11 +498,42 @@ class Prediction:
                 timings["prepare_queries"] += events["prepare_queries"].elapsed_ms()
             else:
                 pipeline.load_queries(q_rowptr, q_cols, q_maxint, first, last)
-            self._chunk(pipeline, events, timings, match_row, stage, probability, single)
-        title_id = np.where(match_row >= 0, self.truth_title_ids[np.maximum(match_row, 0)], TRAIN_NOT_FOUND_VALUE)
-        self.timings = timings
-        return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
-                             "probability": probability})
+            yield pipeline, events
+
+    def _rank_chunk(self, pipeline, events, timings, n, slots, kept):
+        first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
+
+        def timed(name, enqueue):
+            events[name].start()
+            enqueue()
+            events[name].stop()
+
+        # 1. Jaccard top-k (synchronised, as in _chunk)
+        timed("top_k", pipeline.enqueue_top_k)
+        pipeline.sync()
+        timings["top_k"] += events["top_k"].elapsed_ms()
+        # 2. close matches, 3. the exact stage overrides their best row, 4. features and 5. the forest on ALL pairs,
+        # 6. the best n per query in order
+        timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=self.levenshtein_threshold))
+        timed("exact_matches", pipeline.enqueue_exact_matches)
+        timed("features", pipeline.enqueue_features)
+        timed("model", lambda: pipeline.enqueue_predict(self.model))
+        timed("rank", lambda: pipeline.enqueue_rank_matches(n))
+
+        # 7. one copy back of n entries per query (synchronises the null stream the stages ran on)
+        copy_started = time.perf_counter()
+        for out, chunk in zip(slots, pipeline.ranked(n)):
+            out[first:last] = chunk
+        if kept is not None:
+            exact, best = pipeline.exact_matches(), pipeline.best_rows()
+            kept.rows[first:last] = pipeline.rows()
+            kept.ratios[first:last] = pipeline.close_matches()[0]
+            kept.probabilities[first:last] = pipeline.predictions()
+            kept.exact[first:last] = exact
+            kept.close[first:last] = np.where(exact >= 0, -1, best)
+        timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+        for name in ("close_matches", "exact_matches", "features", "model", "rank"):
+            timings[name] += events[name].elapsed_ms()
 
     def _chunk(self, pipeline, events, timings, match_row, stage, probability, single):
         k, first, n = self.top_n, pipeline.q_first, pipeline.n_queries

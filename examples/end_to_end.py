@@ -60,8 +60,14 @@ def main(n_truth=20000, n_queries=2000, top_n=10):
 
     # the same question answered by the driver: one title_id (or -1) per query, every stage on the device
     ids = np.arange(len(truth), dtype=np.int64)
-    answer = ds.Prediction(raw_truth, ids, model, top_n=top_n).generate_test_predictions(raw_queries)
+    prediction = ds.Prediction(raw_truth, ids, model, top_n=top_n)
+    answer = prediction.generate_test_predictions(raw_queries)
     print(f"Prediction: {(answer['title_id'] >= 0).sum()} of {len(answer)} queries matched")
+
+    # a review queue for the titles left at -1: their best three candidates in order, with the scores
+    unmatched = answer.loc[answer["title_id"] < 0, "test_index"].to_numpy()[:3]
+    ranked = prediction.ranked_matches([raw_queries[i] for i in unmatched], n=min(3, top_n), test_index=unmatched)
+    print(ranked.to_string(index=False))
     return rows, best_row, features, probabilities
 
 

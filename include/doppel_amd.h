@@ -198,6 +198,29 @@ int ds_select_matches_device(const int32_t *d_pair_q, const int32_t *d_pair_t, c
                              int64_t n_remaining, int32_t k, float threshold, int32_t *d_match_query,
                              int32_t *d_match_row, void *stream);
 
+/* ---- ranked matches: the best n of a query's k candidates, in order, with their scores ---------
+ * The project's own rule; the reference keeps one answer per title (predict.py:239-242).  Per query q, over the
+ * candidates j = 0 .. k-1 with truth row c_j = d_rows[q*k + j], probability p_j = d_predictions[q*k + j] (finite and
+ * non-negative) and ratio r_j = d_ratios[q*k + j]:
+ *   head   d_exact_row[q] when >= 0 (stage 1), else d_best_row[q] when >= 0 (stage 2), else none.  It takes slot 0 with
+ *          probability 1.0 (what the reference stores for exact and close matches, predict.py:108,179) and the ratio of
+ *          the first candidate that equals it; absent from the candidates (twins of rank >= k are left out of the
+ *          index) an exact head has ratio 100 and a close head ratio 0;
+ *   rest   every candidate with 0 <= c_j < n_truth and c_j != head, stage 3, ordered by the float32 BITS of p_j
+ *          descending, then j ascending (a pure function of the inputs).  Other candidates are skipped;
+ *   slots  the list is cut to n; an unfilled slot holds row -1, probability quiet NaN (0x7fc00000), ratio 0, stage 0.
+ * The outputs are [n_queries][n] arrays in HBM; every slot is written.  d_exact_row and d_best_row may each be NULL ("no
+ * such stage"); after ds_close_matches_device and ds_exact_matches_device on the same d_best_row, pass both.  DS_E_ARG: any
+ * other null pointer, k < 1, n outside 1..k, a negative count.  n_queries == 0 launches nothing.  Any k works: up to
+ * "lds_keys" candidates are ranked in LDS by counting, longer lists by n rounds of selection from HBM, with the same
+ * result.  ds_rank_option("lds_keys", v), v in [0, 512] (default 512), is for tests: it moves that limit (0: always
+ * select).  Asynchronous on `stream`. */
+int ds_rank_matches_device(const int32_t *d_rows, const float *d_predictions, const uint8_t *d_ratios,
+                           const int32_t *d_exact_row, const int32_t *d_best_row, int64_t n_queries, int32_t k,
+                           int32_t n, int64_t n_truth, int32_t *d_out_row, float *d_out_probability,
+                           uint8_t *d_out_ratio, int8_t *d_out_stage, void *stream);
+int ds_rank_option(const char *name, int64_t value);
+
 /* ---- exact matches: Prediction._find_exact_matches (predict.py:74-113) ---------------------------------------------
  * exact_row[q] = the truth row whose encoded title (length and bytes of the ds_titles rows) equals query row q's, the
  * LAST such row when several truth rows hold the title (the reference's {title: title_id} dict is filled in truth
