@@ -8,6 +8,9 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
     FEATURES_COUNT, encode_title, get_truth_words_counts
     Prediction(truth_titles, truth_title_ids, model).generate_test_predictions(titles)   -> final_output (predict.py)
         .ranked_matches(titles, n)   -> the best n candidates per title in order, with scores (this project's own)
+        .exhaustive_matches(titles, n)   -> the best n rows of the WHOLE truth set per title by the model alone, and
+            where the Jaccard top_n put each of them (this project's own: tells a miss of the candidate stage from a
+            miss of the model); closest_search_single_title(title, exhaustive=True) answers from it
     ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
@@ -26,7 +29,8 @@ from .feature_engineering import (  # noqa: F401
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
 from .forest import ForestModel  # noqa: F401
-from .prediction import RANKED_COLUMNS, Candidates, Prediction, validate_rank  # noqa: F401
+from .prediction import (EXHAUSTIVE_COLUMNS, RANKED_COLUMNS, Candidates, Prediction, validate_exhaustive,  # noqa: F401
+                         validate_rank)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, train_model)

@@ -20,6 +20,7 @@ PREDICTION_PROBABILITY_THRESHOLD = 0.9  # settings.py:76
 # device bytes per query and candidate: features (66 float32), prediction, top-k row, ratio, pair (q, t)
 BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
 BYTES_PER_RANK = 4 + 4 + 1 + 1          # one slot of the rank output: row, probability, ratio, stage
+EXHAUSTIVE_MAX_N = 64                   # slots per query of the exhaustive stage at most (ds_exhaustive_rank_device)
 MAX_GRAMS = 253                         # tri-grams of a 255-character title: columns of one query row at most
 
 
@@ -55,6 +56,7 @@ class CandidatePipeline:
         self.d_features = _lib.DeviceArray((capacity * k, FEATURES_COUNT), np.float32, device)
         self._close = self._exact = self._pairs = self._predictions = self._matches = None
         self._ranked, self._ranked_n = None, 0
+        self._exhaustive, self._exhaustive_n = None, 0
 
     def _allocate_stages(self):
         """The outputs of the stages after top-k (by `over`, or by the first of their enqueues)."""
@@ -208,6 +210,30 @@ class CandidatePipeline:
         if n != self._ranked_n:
             raise ValueError(f"the last enqueue_rank_matches ranked {self._ranked_n} slots per query, not {n}")
         return tuple(a.to_host(self.n_queries * n).reshape(self.n_queries, n) for a in self._ranked)
+
+    def enqueue_exhaustive(self, model, n, stream=None):
+        """The best n rows of the WHOLE truth table per query by the model alone (ds_exhaustive_rank_device): tiles of
+        pairs through the features and forest kernels, folded into n running keys per query, with no use of the top-k
+        rows and no exact or close override.  The stage allocates its workspace per call and frees it before it
+        returns, so `stream` is synchronised at the end.  The outputs are allocated by the first call, for `capacity`
+        queries of n slots."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= EXHAUSTIVE_MAX_N:
+            raise ValueError(f"n must be an integer in [1, {EXHAUSTIVE_MAX_N}], not {n!r}")
+        if self._exhaustive is None or self._exhaustive[0].shape[0] < self.capacity * n:
+            size, device = max(1, self.capacity * int(n)), self.device
+            self._exhaustive = (_lib.DeviceArray((size,), np.int32, device), _lib.DeviceArray((size,), np.float32, device))
+        self._exhaustive_n = int(n)
+        _lib.check(_lib.lib().ds_exhaustive_rank_device(
+            self.query_titles.handle, self.truth_titles.handle, model.handle, self.q_first, self.n_queries,
+            self._exhaustive_n, SPACE_CODE, self.n_truth, *(a.ptr for a in self._exhaustive), _lib.pointer(stream)),
+            "ds_exhaustive_rank_device")
+
+    def exhaustive(self, n):
+        """(rows int32[Q, n], probabilities float32[Q, n]) of the last `enqueue_exhaustive(model, n)`; a slot with no
+        row (fewer than n truth titles) holds -1 and NaN."""
+        if n != self._exhaustive_n:
+            raise ValueError(f"the last enqueue_exhaustive kept {self._exhaustive_n} slots per query, not {n}")
+        return tuple(a.to_host(self.n_queries * n).reshape(self.n_queries, n) for a in self._exhaustive)
 
     def matches(self, n_remaining):
         """(query rows, matched truth row or -1) of the last `enqueue_select_matches`."""

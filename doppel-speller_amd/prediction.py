@@ -28,7 +28,7 @@ from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
                                   truth_word_counts)
 from .match_maker import NativeProblem, TruthIndex
-from .pipeline import (BYTES_PER_PAIR, BYTES_PER_RANK, MAX_GRAMS, PREDICTION_PROBABILITY_THRESHOLD,
+from .pipeline import (BYTES_PER_PAIR, BYTES_PER_RANK, EXHAUSTIVE_MAX_N, MAX_GRAMS, PREDICTION_PROBABILITY_THRESHOLD,
                        CandidatePipeline)
 
 TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
@@ -36,6 +36,7 @@ N_GRAM = 3                               # settings.py:15
 PREPARE_QUERIES = ("device", "host")
 STAGE_NONE, STAGE_EXACT, STAGE_CLOSE, STAGE_MODEL = 0, 1, 2, 3
 RANKED_COLUMNS = ("test_index", "rank", "title_id", "match_row", "probability", "levenshtein_ratio", "stage")
+EXHAUSTIVE_COLUMNS = ("test_index", "rank", "title_id", "match_row", "probability", "jaccard_position")
 # what ranked_matches(keep_candidates=True) keeps of a call, per query: the top-n rows, their fuzzy ratios and model
 # probabilities, the exact row and the close row (-1: none; the close row also where the exact stage matched)
 Candidates = collections.namedtuple("Candidates", ("rows", "ratios", "probabilities", "exact", "close"))
@@ -110,6 +111,45 @@ def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_id
                          "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
                          "levenshtein_ratio": np.asarray(ratios, dtype=np.uint8)[query, slot],
                          "stage": np.asarray(stages, dtype=np.int8)[query, slot]}, columns=list(RANKED_COLUMNS))
+
+
+def validate_exhaustive(n, n_truth):
+    """exhaustive_matches' check of `n` (no library needed): a positive integer up to 64 and up to the truth titles."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"n must be a positive integer, not {n!r}")
+    if n > min(EXHAUSTIVE_MAX_N, n_truth):
+        raise ValueError(f"n = {n} exceeds the smaller of {EXHAUSTIVE_MAX_N} and the {n_truth} truth titles")
+    return int(n)
+
+
+def jaccard_positions(rows, top_rows):
+    """int32[Q, n]: where each of `rows` [Q, n] stands in its query's Jaccard rows `top_rows` [Q, top_n] (the first such
+    column), -1 where it does not, and for an unfilled slot (row < 0)."""
+    rows, top_rows = np.asarray(rows), np.asarray(top_rows)
+    out = np.full(rows.shape, -1, dtype=np.int32)
+    block = 4096                                    # queries at a time: block * n * top_n booleans
+    for first in range(0, rows.shape[0], block):
+        same = rows[first:first + block, :, None] == top_rows[first:first + block, None, :]
+        same &= (rows[first:first + block] >= 0)[:, :, None]
+        out[first:first + block] = np.where(same.any(axis=2), same.argmax(axis=2), -1)
+    return out
+
+
+def exhaustive_frame(test_index, rows, probabilities, top_rows, truth_title_ids):
+    """exhaustive_matches' answer from the [Q, n] slots of the exhaustive stage and the [Q, top_n] Jaccard rows: one line
+    per filled slot (row >= 0), sorted by test_index, then rank (slot + 1: the filled slots of a query come first)."""
+    import pandas as pd
+    test_index = np.asarray(test_index, dtype=np.int64)
+    rows = np.asarray(rows)
+    positions = jaccard_positions(rows, top_rows)
+    query, slot = np.nonzero(rows >= 0)
+    order = np.argsort(test_index[query], kind="stable")
+    query, slot = query[order], slot[order]
+    match_row = rows[query, slot].astype(np.int64)
+    return pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
+                         "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
+                         "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
+                         "jaccard_position": positions[query, slot]}, columns=list(EXHAUSTIVE_COLUMNS))
 
 
 def combine_stages(exact_row, close_row, model_row):
@@ -397,14 +437,25 @@ class Prediction:
         self.details = self._run(titles, test_index)
         return finalize_output(test_index, self.details["match_row"].to_numpy(), self.truth_title_ids)
 
-    def closest_search_single_title(self, title):
+    def closest_search_single_title(self, title, exhaustive=False):
         """cli.py:64-84 (generate_test_predictions(single_prediction=True)): the best match of one title as a dict
         with the keys of predict.py:35-41.  Stage priority exact, close, model; the model stage takes the candidate with
-        the highest probability, no threshold, the first in top-n order on a tie (predict.py:239-242)."""
+        the highest probability, no threshold, the first in top-n order on a tie (predict.py:239-242).
+        exhaustive: the model stage takes the best row of the WHOLE truth set instead (what the reference's README
+        describes: `exhaustive_matches` with n = 1, the lowest row on a tie); exact and close matches keep their
+        priority."""
         stripped = str(title).strip()
         if not stripped:
             raise ValueError("empty title")
         details = self._run([stripped], np.zeros(1, dtype=np.int64), single=True)
+        if exhaustive and int(details["stage"].iloc[0]) not in (STAGE_EXACT, STAGE_CLOSE):
+            timings = dict(self.timings)
+            best = self.exhaustive_matches([stripped], n=1)
+            timings["exhaustive"] = self.timings["exhaustive"]
+            self.timings = timings
+            details.loc[0, ["match_row", "title_id"]] = int(best["match_row"].iloc[0]), int(best["title_id"].iloc[0])
+            details["stage"] = np.int8(STAGE_MODEL)
+            details["probability"] = np.float32(best["probability"].iloc[0])
         self.details = details
         row = int(details["match_row"].iloc[0])
         queries = self._last_queries
@@ -441,6 +492,43 @@ class Prediction:
         self.timings = timings
         self.candidates = kept
         return ranked_frame(test_index, *slots, self.truth_title_ids)
+
+    def exhaustive_matches(self, titles, n=5, test_index=None):
+        """The best `n` rows of the WHOLE truth set for every title by the model alone, next to where the candidate
+        stage put them: a DataFrame in long form [test_index, rank (from 1), title_id, match_row, probability
+        (float32), jaccard_position (int32)] sorted by test_index, then rank.
+
+        Every (title, truth title) pair is scored: features and forest on the device, a tile of pairs at a time, folded
+        into n rows per title by the probability's float32 bits descending, the lower row first on a tie
+        (CandidatePipeline.enqueue_exhaustive).  There is no exact or close override here.  jaccard_position is the
+        column of match_row among the title's Jaccard top_n rows, -1 when the candidate stage did not produce it: a
+        rank-1 row at -1 is a miss of the candidate stage, not of the model.  n: up to 64 and up to the truth titles.
+        `details` and `candidates` are left alone."""
+        n = validate_exhaustive(n, len(self.truth_titles))
+        titles = list(titles)
+        test_index = validate_queries(titles, test_index)
+        timings = dict.fromkeys(("host_prepare", "top_k", "exhaustive", "copy_back"), 0.0)
+        count = len(titles)
+        rows = np.full((count, n), -1, dtype=np.int32)
+        probabilities = np.full((count, n), np.nan, dtype=np.float32)
+        top_rows = np.full((count, self.top_n), -1, dtype=np.int32)
+        for pipeline, events in self._chunks(titles, timings):
+            first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
+            events["top_k"].start()
+            pipeline.enqueue_top_k()
+            events["top_k"].stop()
+            pipeline.sync()
+            events["exhaustive"].start()
+            pipeline.enqueue_exhaustive(self.model, n)
+            events["exhaustive"].stop()
+            copy_started = time.perf_counter()
+            rows[first:last], probabilities[first:last] = pipeline.exhaustive(n)
+            top_rows[first:last] = pipeline.rows()
+            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+            for name in ("top_k", "exhaustive"):
+                timings[name] += events[name].elapsed_ms()
+        self.timings = timings
+        return exhaustive_frame(test_index, rows, probabilities, top_rows, self.truth_title_ids)
 
     def _run(self, titles, test_index, single=False):
         import pandas as pd

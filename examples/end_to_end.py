@@ -63,6 +63,11 @@ def main(n_truth=20000, n_queries=2000, top_n=10):
     prediction = ds.Prediction(raw_truth, ids, model, top_n=top_n)
     answer = prediction.generate_test_predictions(raw_queries)
     print(f"Prediction: {(answer['title_id'] >= 0).sum()} of {len(answer)} queries matched")
+    # the row the model likes best over the WHOLE truth set, per title: where it was not among the Jaccard top_n
+    # (jaccard_position -1) the candidate stage missed it, not the model
+    best = prediction.exhaustive_matches(raw_queries, n=1)
+    print(f"exhaustive rank-1 row inside the Jaccard top-{top_n}: {(best['jaccard_position'] >= 0).sum()} of {len(best)} "
+          f"queries ({(best['jaccard_position'] >= 0).mean():.3f})")
 
     # a review queue for the titles left at -1: their best three candidates in order, with the scores
     unmatched = answer.loc[answer["title_id"] < 0, "test_index"].to_numpy()[:3]

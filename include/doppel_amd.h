@@ -221,6 +221,44 @@ int ds_rank_matches_device(const int32_t *d_rows, const float *d_predictions, co
                            uint8_t *d_out_ratio, int8_t *d_out_stage, void *stream);
 int ds_rank_option(const char *name, int64_t value);
 
+/* ---- exhaustive matches: the best n rows of the WHOLE truth table by the model ------------------
+ * The project's own stage (the reference's README promises it, its code scores the Jaccard top_n only): the model alone,
+ * with no candidate stage in front and no exact or close override.  Per query, over every truth row t with probability
+ * p_t (finite and non-negative):
+ *   key    (float32 BITS of p_t << 32) | (0xffffffff - t): never 0 for a row below 2^31, so 0 stands for "empty";
+ *   best   the n largest keys, descending: by the probability's bits descending, then by t ascending.  The keys of a
+ *          query are distinct, so the result is a pure function of the inputs, whatever the tiling or the schedule;
+ *   slots  an unfilled slot (fewer than n truth rows) holds row -1 and probability quiet NaN (0x7fc00000).
+ * n lies in 1..64.  DS_E_ARG, with nothing launched: a null pointer or handle, n outside 1..64, a negative count.
+ *
+ * ds_exhaustive_fold_device: the fold alone, on probabilities of the caller's (the entry the kernel tests drive).
+ * d_probabilities is [n_queries][tile_rows] in HBM, column j of every query being truth row row_first + j;
+ * d_running is [n_queries][n] keys in HBM, descending, 0 = empty (all 0 before the first fold).  After the call it holds
+ * the n largest keys of what it held and the tile's.  Every truth row is folded once; the order and the sizes of the tiles
+ * do not matter.  row_first + tile_rows <= 2^31.  n_queries == 0 or tile_rows == 0 launches nothing.  Enqueued on
+ * `stream`; a tile of more than 4096 - n rows takes partial lists in HBM, allocated by the call and freed before it
+ * returns, behind a synchronisation of `stream`. */
+int ds_exhaustive_fold_device(const float *d_probabilities, int64_t n_queries, int64_t tile_rows, int64_t row_first,
+                              int32_t n, uint64_t *d_running /* [n_queries][n] keys, 0 = empty */, void *stream);
+/* d_out_row[q*n + s] / d_out_probability[q*n + s] = the row and the probability of key s of query q, (-1, quiet NaN)
+ * for an empty key.  Every slot is written.  n_queries == 0 launches nothing.  Asynchronous on `stream`. */
+int ds_exhaustive_finish_device(const uint64_t *d_running, int64_t n_queries, int32_t n, int32_t *d_out_row,
+                                float *d_out_probability, void *stream);
+/* The whole stage, for rows [q_first, q_first + n_queries) of `queries` against all rows of `truth` (a table with word
+ * counts): per tile of pairs -- consecutive queries x consecutive truth rows -- a pair list, the features of
+ * ds_construct_features_indexed_device (space_code, n_truth as there), the probabilities of ds_forest_predict_device and
+ * the fold; then ds_exhaustive_finish_device into d_out_row / d_out_probability, [n_queries][n] in HBM.  At no time more
+ * than one tile of pairs exists.  The workspace (276 bytes per pair of a tile, 8 n bytes per query, the fold's partial
+ * lists) is allocated by the call and freed before it returns: `stream` is synchronised at the end.  A tile holds
+ * "tile_pairs" pairs at most: by default what a quarter of the HBM free at the call holds, and no more than 2^24 pairs
+ * (1.1e9 features; 4.7 GB).  n_queries == 0 launches nothing and writes nothing.
+ * ds_exhaustive_option("tile_pairs", v), v in [0, 2^24], is for tests: the pairs of a tile, 0 = the default.  The
+ * result does not depend on it. */
+int ds_exhaustive_rank_device(ds_titles *queries, ds_titles *truth, ds_forest *forest, int64_t q_first,
+                              int64_t n_queries, int32_t n, uint8_t space_code, uint32_t n_truth,
+                              int32_t *d_out_row, float *d_out_probability, void *stream);
+int ds_exhaustive_option(const char *name, int64_t value);   /* "tile_pairs": for tests, 0 = default */
+
 /* ---- exact matches: Prediction._find_exact_matches (predict.py:74-113) ---------------------------------------------
  * exact_row[q] = the truth row whose encoded title (length and bytes of the ds_titles rows) equals query row q's, the
  * LAST such row when several truth rows hold the title (the reference's {title: title_id} dict is filled in truth

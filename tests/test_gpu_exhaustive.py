@@ -1,0 +1,218 @@
+"""The exhaustive stage and Prediction.exhaustive_matches on the GPU: 2,000 synthetic truth titles, 16 queries, a forest of
+100 trees.  The expected value is the restated rule (tests/exhaustive_cases.py) on the device's own probabilities of all
+16 x 2,000 pairs through entry points that existed before (construct_features_indexed, ForestModel.predict), whose feature
+rows are compared with the oracle's; the tilings, preparations and chunks that must not change the frame; the answers
+of closest_search_single_title; the consistency with ranked_matches on a truth set small enough to list whole."""
+import numpy as np
+import pytest
+
+import doppel_speller_amd as ds
+import exhaustive_cases as ec
+from doppel_speller_amd import _lib, prediction, synth
+from doppel_speller_amd.feature_engineering import truth_word_counts
+
+pytestmark = pytest.mark.gpu
+
+N_TRUTH, N_QUERIES, TOP_N = 2000, 16, 10
+
+
+def _model():
+    forest = synth.make_forest(n_trees=100)
+    return ds.ForestModel(forest["feature"], forest["threshold"], forest["yes"], forest["no"], forest["missing"],
+                          forest["tree_offsets"], forest["n_features"], forest["base_margin"])
+
+
+@pytest.fixture(scope="module")
+def problem():
+    w = synth.make_workload(N_TRUTH, N_QUERIES)
+    truth = synth._to_strings(w.t_flat, w.t_off)
+    queries = synth._to_strings(w.q_flat, w.q_off)
+    queries[3] = truth[1234]                       # a verbatim truth title among the queries
+    for q, (a, b) in ((5, (10, 20)), (11, (300, 1700))):   # halves of two truth titles: no exact and no close match
+        queries[q] = " ".join(truth[a].split()[:2] + truth[b].split()[-2:])
+    ids = np.arange(N_TRUTH, dtype=np.int64) * 3 + 7
+    model = _model()
+    p = ds.Prediction(truth, ids, model, top_n=TOP_N, transform=False)
+    # the device's own feature rows and probabilities of ALL pairs, through the entry points that were there before
+    q_enc, q_len = ds.encode_titles(queries)
+    pair_q = np.repeat(np.arange(N_QUERIES, dtype=np.int32), N_TRUTH)
+    pair_t = np.tile(np.arange(N_TRUTH, dtype=np.int32), N_QUERIES)
+    features = ds.construct_features_indexed(ds.TitleTable(q_enc, q_len), p.truth_table, pair_q, pair_t, ds.SPACE_CODE,
+                                             N_TRUTH)
+    probabilities = model.predict(features).reshape(N_QUERIES, N_TRUTH)
+    for array in (features, probabilities):
+        array.setflags(write=False)
+    return dict(truth=truth, queries=queries, ids=ids, model=model, p=p, q_enc=q_enc, q_len=q_len, pair_q=pair_q,
+                pair_t=pair_t, features=features, probabilities=probabilities)
+
+
+@pytest.fixture
+def tile_pairs():
+    """Sets the "tile_pairs" option for a test and puts the default back."""
+    def choose(value):
+        _lib.check(_lib.lib().ds_exhaustive_option(b"tile_pairs", value), "ds_exhaustive_option")
+    try:
+        yield choose
+    finally:
+        choose(0)
+
+
+def _same_frame(a, b):
+    return list(a.columns) == list(b.columns) and a.dtypes.tolist() == b.dtypes.tolist() and all(
+        np.array_equal(np.ascontiguousarray(a[c].to_numpy()).view(np.uint8),
+                       np.ascontiguousarray(b[c].to_numpy()).view(np.uint8)) for c in a.columns)
+
+
+def _slots(frame, n_queries, n):
+    """(rows int32[Q, n], probabilities float32[Q, n]) of a frame whose queries all filled their n slots."""
+    assert len(frame) == n_queries * n
+    assert np.array_equal(frame["test_index"].to_numpy(), np.repeat(np.arange(n_queries), n))
+    assert np.array_equal(frame["rank"].to_numpy(), np.tile(np.arange(1, n + 1), n_queries))
+    return (frame["match_row"].to_numpy().astype(np.int32).reshape(n_queries, n),
+            frame["probability"].to_numpy().reshape(n_queries, n))
+
+
+def test_the_feature_rows_are_the_oracles(problem, oracle):
+    """The chain stays anchored to the reference: the feature rows behind the expected probabilities, bit for bit."""
+    truth = problem["truth"]
+    t_enc, t_len = ds.encode_titles(truth)
+    counts = truth_word_counts(*prediction._pack(truth), separators=(ord(" "),))
+    pair_q, pair_t = problem["pair_q"], problem["pair_t"]
+    reference = oracle.construct_features(problem["q_len"][pair_q], t_len[pair_t], problem["q_enc"][pair_q], t_enc[pair_t],
+                                          counts[pair_t], ds.SPACE_CODE, N_TRUTH)
+    assert np.array_equal(problem["features"].view(np.uint32), reference.view(np.uint32))
+    probabilities = problem["probabilities"]
+    assert np.isfinite(probabilities).all() and (probabilities >= 0).all()
+
+
+@pytest.mark.parametrize("n", [1, 5, 64])
+def test_every_tiling_gives_the_restated_rule(problem, tile_pairs, n):
+    """777: a query spans three tiles, the tile is no multiple of 16; 2,000: a query per tile; 7,000: 3.5 queries' worth,
+    three queries per tile and a ragged last group; 0: the default (all 16 queries in one tile)."""
+    p = problem["p"]
+    expected = ec.best_rows(problem["probabilities"], n)
+    frames = []
+    for value in (777, N_TRUTH, 7 * N_TRUTH // 2, 0):
+        tile_pairs(value)
+        frame = p.exhaustive_matches(problem["queries"], n=n)
+        assert ec.same_best(_slots(frame, N_QUERIES, n), expected), value
+        frames.append(frame)
+        assert _same_frame(frames[0], frame), value
+    frame = frames[0]
+    assert tuple(frame.columns) == prediction.EXHAUSTIVE_COLUMNS
+    assert np.array_equal(frame["title_id"].to_numpy(), problem["ids"][frame["match_row"].to_numpy()])
+    assert set(p.timings) == {"host_prepare", "prepare_queries", "top_k", "exhaustive", "copy_back"}
+    assert p.timings["exhaustive"] > 0 and p.timings["top_k"] > 0
+
+
+def test_the_stage_through_the_pipeline(problem, tile_pairs):
+    """CandidatePipeline.enqueue_exhaustive / exhaustive on a sub-range of the query table, and the jaccard positions of
+    the frame against the top-k rows of the same pipeline."""
+    p = problem["p"]
+    table = ds.TitleTable(problem["q_enc"], problem["q_len"])
+    pipeline = ds.CandidatePipeline.over(p.index, p.truth_table, table, TOP_N, 8)
+    pipeline.n_queries, pipeline.q_first = 5, 9                      # queries 9 .. 13
+    tile_pairs(3001)
+    pipeline.enqueue_exhaustive(problem["model"], 7)
+    got = pipeline.exhaustive(7)
+    assert got[0].dtype == np.int32 and got[1].dtype == np.float32
+    assert ec.same_best(got, ec.best_rows(problem["probabilities"][9:14], 7))
+    with pytest.raises(ValueError, match="kept 7 slots"):
+        pipeline.exhaustive(5)
+    for bad in (0, 65, True, 2.0):
+        with pytest.raises(ValueError, match="^n must"):
+            pipeline.enqueue_exhaustive(problem["model"], bad)
+
+
+def test_jaccard_position_is_the_column_of_the_top_k(problem):
+    p = problem["p"]
+    frame = p.exhaustive_matches(problem["queries"], n=64)
+    p.ranked_matches(problem["queries"], n=1, keep_candidates=True)
+    top_rows = p.candidates.rows
+    position = frame["jaccard_position"].to_numpy()
+    assert position.dtype == np.int32
+    for q, row, at in zip(frame["test_index"], frame["match_row"], position):
+        where = np.nonzero(top_rows[q] == row)[0]
+        assert at == (where[0] if where.shape[0] else -1), (q, row)
+    assert (position >= 0).any() and (position < 0).any()
+
+
+def test_preparation_chunks_and_order_do_not_change_the_frame(problem):
+    p, queries = problem["p"], problem["queries"]
+    frame = p.exhaustive_matches(queries, n=5)
+    details, candidates = p.details, p.candidates
+    try:
+        for chunk in (1, 5, None):
+            p.chunk_queries = chunk
+            for prepare in ("host", "device"):
+                p.prepare_queries = prepare
+                assert _same_frame(frame, p.exhaustive_matches(queries, n=5)), (chunk, prepare)
+                assert ("prepare_queries" in p.timings) == (prepare == "device")
+    finally:
+        p.chunk_queries, p.prepare_queries = None, "device"
+    assert p.details is details and p.candidates is candidates        # left alone
+    permutation = np.random.RandomState(4).permutation(N_QUERIES)
+    permuted = p.exhaustive_matches([queries[i] for i in permutation], n=5, test_index=permutation)
+    assert _same_frame(frame, permuted)
+
+    empty = p.exhaustive_matches([], n=5)
+    assert tuple(empty.columns) == prediction.EXHAUSTIVE_COLUMNS and len(empty) == 0
+    assert empty.dtypes.tolist() == frame.dtypes.tolist() and p.timings["exhaustive"] == 0.0
+
+
+def test_closest_search_single_title(problem):
+    p, queries, truth, ids = problem["p"], problem["queries"], problem["truth"], problem["ids"]
+    expected = ec.best_rows(problem["probabilities"], 1)
+    p.ranked_matches(queries, n=1, keep_candidates=True)
+    c = p.candidates
+    # a verbatim truth title: the exact match, whatever the model likes best
+    last = max(row for row, title in enumerate(truth) if title == truth[1234])
+    for exhaustive in (False, True):
+        answer = p.closest_search_single_title(truth[1234], exhaustive=exhaustive)
+        assert answer["title_id"] == ids[last] and answer["prediction"] == 1.0, exhaustive
+        assert answer["match_transformed_title"] == truth[1234]
+    # titles no earlier stage matches: the exhaustive rank-1 row; without the flag the best of the top_n, as before
+    undecided = np.nonzero((c.exact < 0) & (c.close < 0))[0]
+    assert {5, 11} <= set(undecided.tolist())
+    for q in undecided[:3]:
+        answer = p.closest_search_single_title(queries[q], exhaustive=True)
+        assert set(answer) == {"test_index", "transformed_title", "match_transformed_title", "title_id", "prediction"}
+        assert answer["title_id"] == ids[expected[0][q, 0]], q
+        assert np.float32(answer["prediction"]).view(np.uint32) == expected[1][q, 0].view(np.uint32), q
+        assert answer["match_transformed_title"] == truth[expected[0][q, 0]] and answer["transformed_title"] == queries[q]
+        assert int(p.details["stage"].iloc[0]) == 3 and int(p.details["match_row"].iloc[0]) == expected[0][q, 0]
+        assert "exhaustive" in p.timings and "select_matches" in p.timings
+        best = int(np.argmax(c.probabilities[q]))                      # the first of the maxima (predict.py:239-242)
+        before = p.closest_search_single_title(queries[q])
+        assert before == p.closest_search_single_title(queries[q], exhaustive=False)
+        assert before["title_id"] == ids[c.rows[q, best]], q
+        assert np.float32(before["prediction"]).view(np.uint32) == c.probabilities[q, best].view(np.uint32), q
+        assert "exhaustive" not in p.timings
+        assert expected[1][q, 0] >= c.probabilities[q, best]
+
+
+def test_consistency_with_ranked_matches_on_a_small_truth_set(problem):
+    """48 truth titles, top_n = 10, n = 48: the exhaustive list holds every truth row, so every Jaccard candidate appears
+    in it with the probability bits ranked_matches gave it, at the jaccard_position of its column."""
+    truth, queries = problem["truth"][:48], problem["queries"]
+    ids = np.arange(48, dtype=np.int64) + 500
+    p = ds.Prediction(truth, ids, problem["model"], top_n=TOP_N, transform=False)
+    with pytest.raises(ValueError, match="48 truth titles"):
+        p.exhaustive_matches(queries, n=49)
+    frame = p.exhaustive_matches(queries, n=48)
+    rows, probabilities = _slots(frame, N_QUERIES, 48)
+    assert (np.sort(rows, axis=1) == np.arange(48)).all()
+    position = frame["jaccard_position"].to_numpy().reshape(N_QUERIES, 48)
+    p.ranked_matches(queries, n=1, keep_candidates=True)
+    c = p.candidates
+    for q in range(N_QUERIES):
+        for column, (row, probability) in enumerate(zip(c.rows[q], c.probabilities[q])):
+            slot = int(np.nonzero(rows[q] == row)[0][0])
+            assert probabilities[q, slot].view(np.uint32) == probability.view(np.uint32), (q, column)
+            assert position[q, slot] == column, (q, column)
+        assert (position[q] >= 0).sum() == TOP_N
+        assert probabilities[q, 0] >= c.probabilities[q].max()
+    # the order is the rule's: bits descending, rows ascending among equal bits
+    bits = probabilities.view(np.uint32).astype(np.int64)
+    keys = (bits << 32) | (0xffffffff - rows.astype(np.int64))
+    assert (np.diff(keys, axis=1) < 0).all()
