@@ -39,7 +39,12 @@ def best_rows_python(probabilities, n, row_first=0):
 
 def best_keys(probabilities, n, row_first=0):
     """uint64[Q, n]: the running list the fold leaves, (bits << 32) | (0xffffffff - row) descending, 0 = empty."""
-    row, probability = best_rows(probabilities, n, row_first)
+    return keys_of(best_rows(probabilities, n, row_first))
+
+
+def keys_of(best):
+    """best_keys from the lists best_rows has already returned (a long table is sorted once)."""
+    row, probability = best
     bits = np.ascontiguousarray(probability).view(np.uint32).astype(np.uint64)
     keys = (bits << np.uint64(32)) | (np.uint64(0xffffffff) - np.maximum(row, 0).astype(np.uint64))
     return np.where(row >= 0, keys, np.uint64(0))
@@ -83,6 +88,46 @@ def make_probabilities(n_queries, n_rows, kind, seed=0, marks=()):
             if 0 <= mark < n_rows:
                 values[:, mark] = 0.875
     return np.ascontiguousarray(values, dtype=np.float32)
+
+
+def planted_units(rows):
+    """The order in which make_planted's values fall over the sorted `rows`, before the shuffle: pairs of equal values
+    (the lower row first; the partner lies half the list further on, as far away as the rows allow) and single rows."""
+    rows = sorted(int(r) for r in rows)
+    half = len(rows) // 2
+    paired = set(range(0, half, 2))
+    return [(rows[i], rows[i + half]) for i in sorted(paired)] + \
+           [(rows[i],) for i in range(len(rows)) if i not in paired and i - half not in paired]
+
+
+def make_planted(n_rows, n, seed, rows=None):
+    """float32[1, n_rows] whose n best rows are known without a sort, and those rows int32[1, n] in the order of the rule.
+    The backdrop is the "few" kind halved (0, 1/8, 1/4, 3/8: ties everywhere, none can win).  On top, n values >= 0.5 at
+    `rows` (n distinct rows of the caller's; default: spread evenly, rows 0 and n_rows - 1 among them).  The units of
+    planted_units(rows) are shuffled and take descending values 0.5 + k / 256, so both rows of a pair hold the SAME bits
+    and the lower row must come first, however far apart the two are."""
+    rng = np.random.RandomState(seed)
+    values = make_probabilities(1, n_rows, "few", seed=seed) * np.float32(0.5)
+    if rows is None:
+        rows = [0] if n == 1 else [s * (n_rows - 1) // (n - 1) for s in range(n)]
+    assert len(set(rows)) == len(rows) == n <= min(n_rows, 64) and 0 <= min(rows) and max(rows) < n_rows
+    units = planted_units(rows)
+    units = [units[u] for u in rng.permutation(len(units))]
+    winners = []
+    for position, unit in enumerate(units):
+        values[0, list(unit)] = np.float32(0.5 + (len(units) - position) / 256.0)
+        winners += unit
+    return values, np.array([winners], dtype=np.int32)
+
+
+def fold_levels(n_rows, n, slice_keys=4096):
+    """Slices per query at every level of the fold of one tile of n_rows rows: level 0 holds the rows and the running list
+    of n keys, every further level the n keys of each slice of the level before, until one slice is left."""
+    slices, keys = [], n_rows + n
+    while not slices or slices[-1] > 1:
+        slices.append(-(-keys // slice_keys))
+        keys = slices[-1] * n
+    return slices
 
 
 def split(n_rows, calls):

@@ -1,5 +1,6 @@
 """Exhaustive matches without a GPU: the NumPy restatement of the rule (tests/exhaustive_cases.py) against a plain-Python
-transcription with sorted(), exhaustive_matches' argument checks, the frame it builds, and the C ABI surface."""
+transcription with sorted(), the planted tables of the GPU tests against both, the grid caps those tests reach past against
+the kernel's source, exhaustive_matches' argument checks, the frame it builds, and the C ABI surface."""
 import os
 import re
 
@@ -56,6 +57,85 @@ def test_split_covers_the_rows_with_a_ragged_last_call():
             assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
             if calls > 1 and n_rows > calls:
                 assert len(ranges) > 1 and ranges[-1][1] - ranges[-1][0] < ranges[0][1] - ranges[0][0]
+
+
+@pytest.mark.parametrize("n", [1, 5, 64])
+def test_planted_winners_are_what_the_rule_returns(n):
+    """make_planted's closed form against best_rows and best_rows_python: default rows, the caller's rows, two calls."""
+    n_rows = 20000
+    chosen = [0, n_rows - 1] + [4095 + 211 * j for j in range(n - 2)] if n > 1 else [n_rows - 1]
+    for rows in (None, chosen):
+        probabilities, winners = ec.make_planted(n_rows, n, seed=n, rows=rows)
+        assert probabilities.shape == (1, n_rows) and probabilities.dtype == np.float32
+        assert winners.shape == (1, n) and winners.dtype == np.int32
+        spread = [0] if n == 1 else [s * (n_rows - 1) // (n - 1) for s in range(n)]     # the documented default
+        assert sorted(winners[0].tolist()) == sorted(rows if rows else spread)
+        assert rows or n == 1 or {0, n_rows - 1} <= set(winners[0].tolist())
+        planted = probabilities[0, winners[0]]
+        assert (planted >= 0.5).all() and (np.delete(probabilities[0], winners[0]) < 0.5).all()
+        assert (np.diff(planted) <= 0).all()
+        best = ec.best_rows(probabilities, n)
+        assert np.array_equal(best[0], winners) and np.array_equal(best[1][0], planted)
+        assert ec.as_lists(best) == ec.best_rows_python(probabilities, n)
+        assert np.array_equal(ec.keys_of(best), ec.best_keys(probabilities, n))
+        # the pairs: the same bits at two rows, the lower row first and right in front of the other
+        units = ec.planted_units(winners[0])
+        pairs = [unit for unit in units if len(unit) == 2]
+        assert len(pairs) == (n // 2 + 1) // 2 and sum(len(unit) for unit in units) == n
+        at = {row: slot for slot, row in enumerate(winners[0].tolist())}
+        for low, high in pairs:
+            assert low < high and at[high] == at[low] + 1 and probabilities[0, low] == probabilities[0, high]
+        assert len(set(planted.tolist())) == len(units)
+        # with the table moved by row_first the winners move with it
+        assert np.array_equal(ec.best_rows(probabilities, n, 1000)[0], winners + 1000)
+
+
+def test_the_caps_the_gpu_tests_reach_past_are_the_sources():
+    """The shapes of test_gpu_exhaustive_kernel.py and test_gpu_exhaustive.py are chosen from the grid caps and the fold
+    arithmetic of csrc/ds_exhaustive.hip.  Whoever moves one of them learns here that those tests no longer reach past it."""
+    import test_gpu_exhaustive as stage_tests
+    import test_gpu_exhaustive_kernel as kernel_tests
+    source = open(os.path.join(ROOT, "doppel-speller_amd", "csrc", "ds_exhaustive.hip")).read()
+
+    def constant(name):
+        found = re.search(r"constexpr (?:int|int64_t) %s = ([^;]+);" % name, source)
+        assert found, name
+        return found.group(1).strip()
+
+    assert int(constant("kFoldThreads")) == kernel_tests.FOLD_THREADS
+    assert int(constant("kFoldKeysPerThread")) == kernel_tests.KEYS_PER_THREAD
+    assert constant("kSliceKeys") == "kFoldThreads * kFoldKeysPerThread"
+    assert kernel_tests.SLICE_KEYS == kernel_tests.FOLD_THREADS * kernel_tests.KEYS_PER_THREAD == 4096
+    assert int(constant("kExhaustiveMaxN")) == kernel_tests.MAX_N == pipeline.EXHAUSTIVE_MAX_N
+    assert constant("kTilePairsMax") == "int64_t(1) << 24" and kernel_tests.TILE_PAIRS_MAX == 1 << 24
+
+    # the three capped grids, each in the function that launches the kernel
+    def grid_cap(after, kernel):
+        body = source[source.index(after):]
+        body = body[:body.index(kernel)]
+        caps = re.findall(r"std::min<int64_t>\(([^;]*), 256 \* (\d+)\)\);", body)
+        assert len(caps) == 1, (after, caps)
+        return caps[0][0], 256 * int(caps[0][1])
+
+    assert len(re.findall(r"std::min<int64_t>\([^;]*, 256 \* \d+\)", source)) == 3
+    assert grid_cap("static int fold(", "hipLaunchKernelGGL(ds_exhaustive_select_kernel") == \
+        ("args.n_blocks", kernel_tests.SELECT_BLOCKS_MAX)
+    assert grid_cap("int ds_exhaustive_finish_device(", "hipLaunchKernelGGL(ds::ds_exhaustive_finish_kernel") == \
+        ("(n_slots + 255) / 256", kernel_tests.FINISH_SLOTS_MAX // 256)
+    assert grid_cap("int ds_exhaustive_rank_device(", "hipLaunchKernelGGL(ds::ds_exhaustive_pairs_kernel") == \
+        ("(here + 255) / 256", stage_tests.PAIRS_KERNEL_PAIRS_MAX // 256)
+    assert (kernel_tests.SELECT_BLOCKS_MAX, kernel_tests.FINISH_SLOTS_MAX, stage_tests.PAIRS_KERNEL_PAIRS_MAX) == \
+        (16384, 1048576, 1048576)
+    # the kernels stride by what they were launched with: a workgroup of the pairs and finish kernels is 256 threads
+    assert "i += gridDim.x * 256u)" in source and "i += static_cast<int64_t>(gridDim.x) * 256)" in source
+    assert "block += gridDim.x)" in source
+
+    # the fold arithmetic behind the level tests: slices per level of one query
+    top = kernel_tests.TILE_PAIRS_MAX
+    assert ec.fold_levels(top - 64, 64) == [4096, 64, 1]
+    assert ec.fold_levels(top - 63, 64) == ec.fold_levels(top, 64) == [4097, 65, 2, 1]
+    assert ec.fold_levels(300000, 64) == [74, 2, 1] and ec.fold_levels(300000, 5) == [74, 1]
+    assert ec.fold_levels(100, 64) == [1] and ec.fold_levels(4100, 5) == [2, 1] and ec.fold_levels(4091, 5) == [1]
 
 
 @pytest.fixture

@@ -2,7 +2,8 @@
 100 trees.  The expected value is the restated rule (tests/exhaustive_cases.py) on the device's own probabilities of all
 16 x 2,000 pairs through entry points that existed before (construct_features_indexed, ForestModel.predict), whose feature
 rows are compared with the oracle's; the tilings, preparations and chunks that must not change the frame; the answers
-of closest_search_single_title; the consistency with ranked_matches on a truth set small enough to list whole."""
+of closest_search_single_title; the consistency with ranked_matches on a truth set small enough to list whole.  A second
+problem of 70,000 truth titles puts 1,120,000 pairs into one tile, past the grid of ds_exhaustive_pairs_kernel."""
 import numpy as np
 import pytest
 
@@ -14,6 +15,10 @@ from doppel_speller_amd.feature_engineering import truth_word_counts
 pytestmark = pytest.mark.gpu
 
 N_TRUTH, N_QUERIES, TOP_N = 2000, 16, 10
+N_TRUTH_LARGE = 70000
+# pairs the grid of ds_exhaustive_pairs_kernel covers: the rest by its stride (tests/test_exhaustive_cpu.py holds it
+# against csrc/ds_exhaustive.hip)
+PAIRS_KERNEL_PAIRS_MAX = 256 * 16 * 256
 
 
 def _model():
@@ -44,6 +49,30 @@ def problem():
         array.setflags(write=False)
     return dict(truth=truth, queries=queries, ids=ids, model=model, p=p, q_enc=q_enc, q_len=q_len, pair_q=pair_q,
                 pair_t=pair_t, features=features, probabilities=probabilities)
+
+
+@pytest.fixture(scope="module")
+def large_problem():
+    """70,000 truth titles x the 16 queries.  The expected probabilities a query at a time through the older entry points,
+    the features (18 MB per query) dropped at once; their rows are anchored to the oracle by the small problem and by
+    test_gpu_features_forms.py."""
+    w = synth.make_workload(N_TRUTH_LARGE, N_QUERIES)
+    truth = synth._to_strings(w.t_flat, w.t_off)
+    queries = synth._to_strings(w.q_flat, w.q_off)
+    queries[3] = truth[61234]
+    for q, (a, b) in ((5, (10, 20)), (11, (300, 69000))):
+        queries[q] = " ".join(truth[a].split()[:2] + truth[b].split()[-2:])
+    model = _model()
+    p = ds.Prediction(truth, np.arange(N_TRUTH_LARGE, dtype=np.int64) * 3 + 7, model, top_n=TOP_N, transform=False)
+    table = ds.TitleTable(*ds.encode_titles(queries))
+    pair_t = np.arange(N_TRUTH_LARGE, dtype=np.int32)
+    probabilities = np.stack([model.predict(ds.construct_features_indexed(
+        table, p.truth_table, np.full(N_TRUTH_LARGE, q, dtype=np.int32), pair_t, ds.SPACE_CODE, N_TRUTH_LARGE))
+        for q in range(N_QUERIES)])
+    assert probabilities.shape == (N_QUERIES, N_TRUTH_LARGE) and probabilities.dtype == np.float32
+    assert np.isfinite(probabilities).all() and (probabilities >= 0).all()
+    probabilities.setflags(write=False)
+    return dict(queries=queries, p=p, probabilities=probabilities)
 
 
 @pytest.fixture
@@ -103,6 +132,24 @@ def test_every_tiling_gives_the_restated_rule(problem, tile_pairs, n):
     assert np.array_equal(frame["title_id"].to_numpy(), problem["ids"][frame["match_row"].to_numpy()])
     assert set(p.timings) == {"host_prepare", "prepare_queries", "top_k", "exhaustive", "copy_back"}
     assert p.timings["exhaustive"] > 0 and p.timings["top_k"] > 0
+
+
+@pytest.mark.parametrize("n", [5, 64])
+def test_tiles_past_the_pairs_kernels_grid(large_problem, tile_pairs, n):
+    """0: all 16 queries in one tile of 1,120,000 pairs, 71,424 more than the pairs kernel's grid covers; 15 queries'
+    worth: such a tile, then a single query; 5 queries' worth: groups of 5, 5, 5, 1; 65,536: a query spans two row tiles,
+    the second of 4,464 rows, the first a two-level fold of 17 slices."""
+    p = large_problem["p"]
+    assert N_QUERIES * N_TRUTH_LARGE == 1120000 > PAIRS_KERNEL_PAIRS_MAX < 15 * N_TRUTH_LARGE
+    assert ec.fold_levels(65536, n) == [17, 1] and N_TRUTH_LARGE - 65536 == 4464
+    expected = ec.best_rows(large_problem["probabilities"], n)
+    frames = []
+    for value in (0, 15 * N_TRUTH_LARGE, 5 * N_TRUTH_LARGE, 65536):
+        tile_pairs(value)
+        frame = p.exhaustive_matches(large_problem["queries"], n=n)
+        assert ec.same_best(_slots(frame, N_QUERIES, n), expected), value
+        frames.append(frame)
+        assert _same_frame(frames[0], frame), value
 
 
 def test_the_stage_through_the_pipeline(problem, tile_pairs):

@@ -1,6 +1,8 @@
 """ds_exhaustive_fold_device and ds_exhaustive_finish_device through the C ABI, on crafted probabilities, against the NumPy
 restatement of the rule (tests/exhaustive_cases.py), bit for bit: every shape folded in 1, 2 and 7 calls, ties across slice
-and call boundaries, fewer rows than slots, the level structure of a long tile, the argument errors."""
+and call boundaries, fewer rows than slots, the level structure of a long tile, the argument errors; query counts past the
+select and finish kernels' grid caps, and a tile of 2^24 rows that takes every level the fold can reach below 8 GB of
+probabilities (a fifth level needs a tile of nearly 2^31 rows and is left out)."""
 import numpy as np
 import pytest
 
@@ -9,14 +11,20 @@ from doppel_speller_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
+# What the shapes below are chosen from (tests/test_exhaustive_cpu.py holds them against csrc/ds_exhaustive.hip)
+FOLD_THREADS, KEYS_PER_THREAD = 256, 16
 SLICE_KEYS = 4096              # keys one workgroup of ds_exhaustive_select_kernel holds (kSliceKeys)
+MAX_N = 64
+SELECT_BLOCKS_MAX = 256 * 64   # workgroups of ds_exhaustive_select_kernel at most: the rest by its block loop
+FINISH_SLOTS_MAX = 256 * 16 * 256   # slots ds_exhaustive_finish_kernel's grid covers: the rest by its stride
+TILE_PAIRS_MAX = 1 << 24       # rows of one query ds_exhaustive_rank_device asks the fold for at most
 
 
-def _fold(probabilities, n, calls, row_first=0):
-    """The running keys and the finished slots after folding the table in `calls` calls."""
+def _fold(probabilities, n, calls, row_first=0, ranges=None):
+    """The running keys and the finished slots after folding the table in `calls` calls (or in the calls of `ranges`)."""
     n_queries, n_rows = probabilities.shape
     running = _lib.DeviceArray.from_host(np.zeros((n_queries, n), dtype=np.uint64))
-    for first, last in ec.split(n_rows, calls):
+    for first, last in ranges or ec.split(n_rows, calls):
         tile = _lib.DeviceArray.from_host(np.ascontiguousarray(probabilities[:, first:last]))
         _lib.check(_lib.lib().ds_exhaustive_fold_device(tile.ptr, n_queries, last - first, row_first + first, n,
                                                         running.ptr, _lib.pointer(None)), "ds_exhaustive_fold_device")
@@ -81,6 +89,93 @@ def test_a_tile_long_enough_for_every_level(n):
         keys, slots = _fold(probabilities, n, calls)
         assert ec.same_best(slots, expected), calls
         assert np.array_equal(keys, ec.best_keys(probabilities, n)), calls
+
+
+@pytest.mark.parametrize("n, n_rows", [(1, 100), (5, 100), (64, 100), (64, 40)])
+def test_query_counts_past_the_select_grid_one_slice_per_query(n, n_rows):
+    """16,384 + 5 queries of one slice each: the last five workgroups take a second block, with the LDS words of their first
+    one.  At n = 64 the 1,048,896 slots are past the finish kernel's grid as well.  40 rows at n = 64: every block runs dry
+    after 40 (or 21 and 40) rounds, breaks out and zero-fills, on the second trip too."""
+    n_queries = SELECT_BLOCKS_MAX + 5
+    assert ec.fold_levels(n_rows, n) == [1]
+    if n == 64:
+        assert n_queries * n == 1048896 > FINISH_SLOTS_MAX
+    for kind in ("few", "equal", "straddle"):
+        for calls in (1, 2):
+            probabilities = ec.make_probabilities(n_queries, n_rows, kind, seed=n_rows + n, marks=_marks(n_rows, calls))
+            expected = ec.best_rows(probabilities, n)
+            keys, slots = _fold(probabilities, n, calls)
+            what = (kind, calls)
+            assert np.array_equal(keys, ec.keys_of(expected)), what
+            assert ec.same_best(slots, expected), what
+            if n_rows < n:
+                assert (slots[0][:, n_rows:] == -1).all() and (keys[:, n_rows:] == 0).all() and (keys[:, :n_rows] != 0).all()
+
+
+@pytest.mark.parametrize("kind", ["few", "straddle"])
+def test_query_counts_past_the_select_grid_two_slices_per_query(kind):
+    """8,200 queries x 4,100 rows, n = 5: 4,105 keys are two slices per query, so level 0 is 16,400 blocks on 16,384
+    workgroups and level 1 is 8,200.  "straddle" puts the maximum either side of row 4,095 / 4,096 and of the boundary of
+    the two calls (2,051, no multiple of 4,096).  Most of the time is NumPy's: 33.6M values made and sorted on the host."""
+    n_queries, n_rows, n, chunk = 8200, 4100, 5, 1025
+    assert ec.fold_levels(n_rows, n) == [2, 1] and n_queries * 2 == 16400 > SELECT_BLOCKS_MAX
+    assert ec.split(n_rows, 2) == [(0, 2051), (2051, 4100)]
+    marks = _marks(n_rows, 1) + _marks(n_rows, 2)
+    assert {4095, 4096, 2050, 2051} <= set(marks)
+    probabilities = np.concatenate([ec.make_probabilities(chunk, n_rows, kind, seed=q, marks=marks)
+                                    for q in range(0, n_queries, chunk)])
+    assert probabilities.shape == (n_queries, n_rows)
+    parts = [ec.best_rows(probabilities[q:q + chunk], n) for q in range(0, n_queries, chunk)]    # 34 MB of keys at a time
+    expected = tuple(np.concatenate([part[i] for part in parts]) for i in (0, 1))
+    if kind == "straddle":
+        assert (expected[0] == [0, 2050, 2051, 4095, 4096]).all()
+    for calls in (1, 2):
+        keys, slots = _fold(probabilities, n, calls)
+        assert ec.same_best(slots, expected), calls
+        assert np.array_equal(keys, ec.keys_of(expected)), calls
+
+
+def _planted_rows(n_rows, first_call=()):
+    """64 rows for make_planted in a table folded as `first_call` rows of a small first call (none: one call) and one tile
+    of the rest: the first call's rows; in the tile, key 0, the last key, the keys either side of 2^24 - 64, and keys
+    j * 2^18 + 61 j + 7 (j = 1 ...: a level-1 slice each when n = 64, a different place in its level-0 slice each)."""
+    base = max(first_call) + 1 if first_call else 0
+    rows = list(first_call) + [base, n_rows - 1] + \
+        [base + key for key in (TILE_PAIRS_MAX - 65, TILE_PAIRS_MAX - 64) if base + key < n_rows - 1]
+    rows += [base + (j << 18) + 61 * j + 7 for j in range(1, MAX_N - len(rows) + 1)]
+    assert len(set(rows)) == len(rows) == MAX_N and max(rows) == n_rows - 1
+    return rows
+
+
+@pytest.mark.parametrize("n_rows, first_call, levels", [
+    (TILE_PAIRS_MAX - 64, (), [4096, 64, 1]),           # every slice of every level exactly full
+    (TILE_PAIRS_MAX, (), [4097, 65, 2, 1]),             # level-0 slice 4,096 holds the (empty) running list alone
+    (100 + TILE_PAIRS_MAX, (0, 57, 99), [4097, 65, 2, 1])])   # ... and now three keys that belong among the 64
+def test_every_level_of_the_fold_with_planted_winners(n_rows, first_call, levels):
+    """One query, n = 64, a tile of up to 2^24 rows (what ds_exhaustive_rank_device asks for at most): three levels, and
+    four, where level 2 has two slices and writes the first partial buffer while it reads the second.  The 64 winners are
+    planted (ec.make_planted) at keys j * 2^18 + 61 j + 7, a level-1 slice each, but for the slots spent on the first and
+    last rows, the keys either side of 2^24 - 64 and the first call's rows: 64, 62 and 59 of the level-1 slices of the
+    three cases hold a winner.  Equal values come in pairs whose rows lie 2^23 apart.  In the single call of 2^24 rows
+    level-0 slice 4,096, level-1 slice 64 and level-2 slice 1 hold the empty running list and pass on nothing.  In the
+    last case rows 0 .. 99 are folded first, so the running list holds three winners when the tile of 2^24 rows comes:
+    they travel alone through those three slices.  Most of the time is NumPy's: the sort of 16.7M keys behind best_rows."""
+    tile_first = max(first_call) + 1 if first_call else 0
+    assert ec.fold_levels(n_rows - tile_first, MAX_N) == levels and n_rows - tile_first <= TILE_PAIRS_MAX
+    rows = _planted_rows(n_rows, first_call)
+    assert {0, n_rows - 1, tile_first + TILE_PAIRS_MAX - 65} <= set(rows)
+    assert len({(row - tile_first) >> 18 for row in rows if row >= tile_first}) == MAX_N - (0 if n_rows < TILE_PAIRS_MAX
+                                                                                          else 5 if first_call else 2)
+    assert all(len(unit) == 1 or unit[1] - unit[0] >= 1 << 18 for unit in ec.planted_units(rows))
+    assert sum(len(unit) == 2 for unit in ec.planted_units(rows)) == 16
+    probabilities, winners = ec.make_planted(n_rows, MAX_N, seed=len(levels), rows=rows)
+    expected = ec.best_rows(probabilities, MAX_N)
+    assert np.array_equal(expected[0], winners)
+    ranges = [(0, tile_first), (tile_first, n_rows)] if first_call else None
+    keys, slots = _fold(probabilities, MAX_N, 1, ranges=ranges)
+    assert np.array_equal(slots[0], winners)
+    assert ec.same_best(slots, expected)
+    assert np.array_equal(keys, ec.keys_of(expected))
 
 
 def test_argument_errors():
