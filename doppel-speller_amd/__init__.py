@@ -11,6 +11,10 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         .exhaustive_matches(titles, n)   -> the best n rows of the WHOLE truth set per title by the model alone, and
             where the Jaccard top_n put each of them (this project's own: tells a miss of the candidate stage from a
             miss of the model); closest_search_single_title(title, exhaustive=True) answers from it
+        .evaluate(titles, actual_title_ids)   -> the counts of get-predictions-accuracy (cli.py) and custom_error
+        .threshold_sweep(titles, actual_title_ids, levenshtein_thresholds, probability_thresholds)   -> those counts
+            for every pair of the two thresholds, from one scoring pass (this project's own)
+    predictions_accuracy(predicted_title_ids, actual_title_ids)   -> the same counts from two id arrays
     ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
@@ -29,8 +33,8 @@ from .feature_engineering import (  # noqa: F401
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
 from .forest import ForestModel  # noqa: F401
-from .prediction import (EXHAUSTIVE_COLUMNS, RANKED_COLUMNS, Candidates, Prediction, validate_exhaustive,  # noqa: F401
-                         validate_rank)
+from .prediction import (EXHAUSTIVE_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS, Candidates, Prediction,  # noqa: F401
+                         predictions_accuracy, validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, train_model)

@@ -755,6 +755,58 @@ __global__ void ds_close_best_kernel(CloseArgs a)
     a.best_row[q] = (where >= 0 && count == 1) ? a.pair_t[q * a.k + where] : -1;
 }
 
+// The ratio of ds_close_ratio_kernel taken apart, for a sweep over the threshold ("Threshold sweep"):
+// at an integer threshold t the ratio is 0 when t > d, r when r > t, else s, with d = the floor of the length pre-filter's
+// value (x < t for an integer t is floor(x) < t; total == 0: 100, the reading above), r = the ratio of the titles and s = the
+// ratio of the token-sorted titles.  What no t in [t_min, t_max] can read is skipped and written as 0: r and s when
+// d < t_min, s when r > t_max.  One wavefront per pair; a pair outside the tables gives 0, 0, 0.
+struct PartsArgs {
+    CloseArgs close;          // ratios, best_row and threshold are not used
+    uint8_t *d, *r, *s;       // [n] each
+    int32_t t_min, t_max;
+};
+
+__global__ __launch_bounds__(kFeatWaves * 64) void ds_close_parts_kernel(PartsArgs p)
+{
+    __shared__ WaveScratch scratch[kFeatWaves];
+    __shared__ uint8_t sort_key[256];
+    const CloseArgs &a = p.close;
+    sort_key[threadIdx.x] = a.sort_key[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    WaveScratch &w = scratch[threadIdx.x >> 6];
+    const int64_t wave_global = static_cast<int64_t>(blockIdx.x) * kFeatWaves + (threadIdx.x >> 6);
+    const int64_t wave_count = static_cast<int64_t>(gridDim.x) * kFeatWaves;
+    for (int64_t pair = wave_global; pair < a.n; pair += wave_count) {
+        const int64_t qi = a.q_first + pair / a.k;
+        const int64_t ti = a.pair_t[pair];
+        int d = 0, r = 0, s = 0;
+        if (qi >= 0 && qi < a.n_q && ti >= 0 && ti < a.n_t) {
+            const int lx = a.q_len[qi], ly = a.t_len[ti];
+            const int total = lx + ly, delta = lx > ly ? lx - ly : ly - lx;
+            // the pre-filter's value in float64 in source order, as ds_close_ratio_kernel compares it; it lies in [0, 100]
+            d = total == 0 ? 100 : static_cast<int>((static_cast<double>(total - delta) / static_cast<double>(total)) * 100.0);
+            if (d >= p.t_min) {
+                wave_sync();
+                for (int i = lane; i < lx; i += 64) w.q[i] = a.q_enc[qi * a.q_stride + i];
+                for (int i = lane; i < ly; i += 64) w.t[i] = a.t_enc[ti * a.t_stride + i];
+                wave_sync();
+                r = rounded_ratio(lcs_wave(w, w.q, lx, w.t, ly, lane), total);
+                if (r <= p.t_max) {
+                    const int sx = token_sort_wave(w, w.q, lx, a.space_code, sort_key, w.recon, lane);
+                    const int sy = token_sort_wave(w, w.t, ly, a.space_code, sort_key, w.qw, lane);
+                    s = rounded_ratio(lcs_wave(w, w.recon, sx, w.qw, sy, lane), sx + sy);
+                }
+            }
+        }
+        if (lane == 0) {
+            p.d[pair] = static_cast<uint8_t>(d);
+            p.r[pair] = static_cast<uint8_t>(r);
+            p.s[pair] = static_cast<uint8_t>(s);
+        }
+    }
+}
+
 
 // ---- host-pointer entry point: packed, pinned, chunked (see ds_construct_features below) -------------------------------
 constexpr int64_t kStageChunk = 16384;                                  // pairs per chunk
@@ -1208,6 +1260,34 @@ int ds_close_matches_device(ds_titles *queries, ds_titles *truth, const int32_t 
                            static_cast<hipStream_t>(stream), args);
         DS_HIP(hipGetLastError());
     }
+    return DS_OK;
+}
+
+int ds_close_parts_device(ds_titles *queries, ds_titles *truth, const int32_t *d_rows, int64_t q_first, int32_t k,
+                          int64_t n_queries, uint8_t space_code, const uint8_t *d_sort_key, int32_t t_min, int32_t t_max,
+                          uint8_t *d_d, uint8_t *d_r, uint8_t *d_s, void *stream)
+{
+    DS_REQUIRE(queries && truth, "ds_close_parts_device: null table");
+    DS_REQUIRE(queries->device == truth->device, "ds_close_parts_device: tables on different devices");
+    DS_REQUIRE(k >= 1 && n_queries >= 0, "ds_close_parts_device: bad k / query count");
+    DS_REQUIRE(0 <= t_min && t_min <= t_max && t_max <= 100,
+               "ds_close_parts_device: thresholds [%d, %d] must lie in [0, 100], the lower one first", t_min, t_max);
+    DS_REQUIRE(n_queries <= INT64_MAX / k, "ds_close_parts_device: too many pairs");
+    if (n_queries == 0) return DS_OK;
+    DS_REQUIRE(d_rows && d_sort_key && d_d && d_r && d_s, "ds_close_parts_device: null pointer");
+    DS_HIP(hipSetDevice(truth->device));
+    ds::PartsArgs args{};
+    ds::CloseArgs &close = args.close;
+    close.q_enc = queries->enc.ptr; close.q_len = queries->len.ptr; close.t_enc = truth->enc.ptr;
+    close.t_len = truth->len.ptr; close.pair_q = nullptr; close.pair_t = d_rows; close.sort_key = d_sort_key;
+    close.q_stride = queries->stride; close.t_stride = truth->stride; close.n_q = queries->n; close.n_t = truth->n;
+    close.n = n_queries * k; close.q_first = q_first; close.k = k; close.space_code = space_code;
+    args.d = d_d; args.r = d_r; args.s = d_s; args.t_min = t_min; args.t_max = t_max;
+    const int64_t blocks_needed = (close.n + ds::kFeatWaves - 1) / ds::kFeatWaves;
+    const int grid = static_cast<int>(std::min<int64_t>(blocks_needed, 256 * 32));
+    hipLaunchKernelGGL(ds::ds_close_parts_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0,
+                       static_cast<hipStream_t>(stream), args);
+    DS_HIP(hipGetLastError());
     return DS_OK;
 }
 

@@ -20,6 +20,7 @@ PREDICTION_PROBABILITY_THRESHOLD = 0.9  # settings.py:76
 # device bytes per query and candidate: features (66 float32), prediction, top-k row, ratio, pair (q, t)
 BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
 BYTES_PER_RANK = 4 + 4 + 1 + 1          # one slot of the rank output: row, probability, ratio, stage
+BYTES_PER_PARTS = 3                     # the close ratio taken apart, per pair: d, r, s
 EXHAUSTIVE_MAX_N = 64                   # slots per query of the exhaustive stage at most (ds_exhaustive_rank_device)
 MAX_GRAMS = 253                         # tri-grams of a 255-character title: columns of one query row at most
 
@@ -57,6 +58,7 @@ class CandidatePipeline:
         self._close = self._exact = self._pairs = self._predictions = self._matches = None
         self._ranked, self._ranked_n = None, 0
         self._exhaustive, self._exhaustive_n = None, 0
+        self._parts = None
 
     def _allocate_stages(self):
         """The outputs of the stages after top-k (by `over`, or by the first of their enqueues)."""
@@ -234,6 +236,36 @@ class CandidatePipeline:
         if n != self._exhaustive_n:
             raise ValueError(f"the last enqueue_exhaustive kept {self._exhaustive_n} slots per query, not {n}")
         return tuple(a.to_host(self.n_queries * n).reshape(self.n_queries, n) for a in self._exhaustive)
+
+    def enqueue_close_parts(self, t_min, t_max, stream=None):
+        """The close ratio of every (query, candidate) pair taken apart (ds_close_parts_device), so that it can be read at
+        any Levenshtein threshold in [t_min, t_max] afterwards; what no threshold of that range can read is skipped.  The
+        three outputs are allocated by the first call, for `capacity` queries."""
+        self._allocate_stages()
+        if self._parts is None:
+            self._parts = tuple(_lib.DeviceArray((self.capacity, self.k), np.uint8, self.device) for _ in range(3))
+        _lib.check(_lib.lib().ds_close_parts_device(
+            self.query_titles.handle, self.truth_titles.handle, self.rows_ptr, self.q_first, self.k, self.n_queries,
+            SPACE_CODE, self._close[2].ptr, int(t_min), int(t_max), *(a.ptr for a in self._parts), _lib.pointer(stream)),
+            "ds_close_parts_device")
+
+    def close_parts(self):
+        """(d, r, s), uint8[Q, k] each, of the last `enqueue_close_parts`: the ratio at an integer threshold t is 0 when
+        t > d, r when r > t, else s."""
+        return tuple(a.to_host(self.n_queries) for a in self._parts)
+
+    def enqueue_threshold_sweep(self, actual_rows, lev, prob, counts, stream=None):
+        """The outcome counters of every (Levenshtein threshold, probability threshold) cell for this chunk's queries,
+        ADDED to `counts` (ds_threshold_sweep_device), over this pipeline's own buffers: the top-k rows, the parts of
+        `enqueue_close_parts`, the predictions of `enqueue_predict` on all pairs and the exact rows of
+        `enqueue_exact_matches`.  actual_rows: int32[Q] in HBM, the truth row each query should get, -1 for none; lev:
+        int32[T] and prob: float32[U] in HBM, strictly ascending; counts: int64[T * U * 4] in HBM."""
+        if self._parts is None:
+            raise ValueError("enqueue_close_parts comes first")
+        _lib.check(_lib.lib().ds_threshold_sweep_device(
+            self.rows_ptr, *(a.ptr for a in self._parts), self._predictions.ptr, self._exact.ptr,
+            _lib.pointer(actual_rows), self.n_queries, self.k, _lib.pointer(lev), lev.shape[0], _lib.pointer(prob),
+            prob.shape[0], _lib.pointer(counts), _lib.pointer(stream)), "ds_threshold_sweep_device")
 
     def matches(self, n_remaining):
         """(query rows, matched truth row or -1) of the last `enqueue_select_matches`."""

@@ -28,8 +28,8 @@ from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
                                   truth_word_counts)
 from .match_maker import NativeProblem, TruthIndex
-from .pipeline import (BYTES_PER_PAIR, BYTES_PER_RANK, EXHAUSTIVE_MAX_N, MAX_GRAMS, PREDICTION_PROBABILITY_THRESHOLD,
-                       CandidatePipeline)
+from .pipeline import (BYTES_PER_PAIR, BYTES_PER_PARTS, BYTES_PER_RANK, EXHAUSTIVE_MAX_N, MAX_GRAMS,
+                       PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline)
 
 TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
 N_GRAM = 3                               # settings.py:15
@@ -37,6 +37,10 @@ PREPARE_QUERIES = ("device", "host")
 STAGE_NONE, STAGE_EXACT, STAGE_CLOSE, STAGE_MODEL = 0, 1, 2, 3
 RANKED_COLUMNS = ("test_index", "rank", "title_id", "match_row", "probability", "levenshtein_ratio", "stage")
 EXHAUSTIVE_COLUMNS = ("test_index", "rank", "title_id", "match_row", "probability", "jaccard_position")
+SWEEP_COLUMNS = ("levenshtein_threshold", "probability_threshold", "correctly_matched", "incorrectly_matched",
+                 "correctly_not_found", "incorrectly_not_found", "custom_error")
+ACCURACY_KEYS = SWEEP_COLUMNS[2:]
+SWEEP_MAX_LEVENSHTEIN, SWEEP_MAX_PROBABILITY = 101, 256      # thresholds per axis at most (ds_threshold_sweep_device)
 # what ranked_matches(keep_candidates=True) keeps of a call, per query: the top-n rows, their fuzzy ratios and model
 # probabilities, the exact row and the close row (-1: none; the close row also where the exact stage matched)
 Candidates = collections.namedtuple("Candidates", ("rows", "ratios", "probabilities", "exact", "close"))
@@ -150,6 +154,79 @@ def exhaustive_frame(test_index, rows, probabilities, top_rows, truth_title_ids)
                          "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
                          "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
                          "jaccard_position": positions[query, slot]}, columns=list(EXHAUSTIVE_COLUMNS))
+
+
+def predictions_accuracy(predicted_title_ids, actual_title_ids):
+    """get-predictions-accuracy (cli.py:107-128) on two aligned id arrays, -1 = not found: a dict of correctly_matched,
+    incorrectly_matched, correctly_not_found, incorrectly_not_found and custom_error = incorrectly_not_found +
+    5 * incorrectly_matched."""
+    predicted, actual = np.asarray(predicted_title_ids), np.asarray(actual_title_ids)
+    if predicted.ndim != 1 or predicted.shape != actual.shape:
+        raise ValueError(f"{predicted.reshape(-1).shape[0]} predicted ids but {actual.reshape(-1).shape[0]} actual ids")
+    found, same = predicted != TRAIN_NOT_FOUND_VALUE, predicted == actual
+    counts = [int((found & same).sum()), int((found & ~same).sum()), int((~found & same).sum()),
+              int((~found & ~same).sum())]
+    return dict(zip(ACCURACY_KEYS, counts + [counts[3] + 5 * counts[1]]))
+
+
+def _integers(values, what):
+    values = np.asarray(values)
+    if values.ndim != 1:
+        raise ValueError(f"{what} must be one-dimensional")
+    if values.shape[0] and (values.dtype == bool or not np.issubdtype(values.dtype, np.integer)):
+        raise ValueError(f"{what} must be integers, not {values.dtype}")
+    return values.astype(np.int64)
+
+
+def validate_sweep(levenshtein_thresholds, probability_thresholds, actual_title_ids, truth_title_ids, n_titles):
+    """threshold_sweep's checks (no library needed) -> (lev int32[T], prob float32[U], shown float64[U], actual_row
+    int32[n_titles]).  The thresholds come back sorted and without repeats: 1..101 integers in [0, 100], and 1..256
+    finite numbers that are compared as float32 (`shown` holds, for each, the first given number with that float32
+    value).  actual_row is the truth row of every actual id, -1 for the id -1; any other id that is not one of
+    truth_title_ids is refused by name."""
+    lev = _integers(levenshtein_thresholds, "levenshtein_thresholds")
+    if lev.shape[0] == 0 or lev.min() < 0 or lev.max() > 100:
+        raise ValueError("levenshtein_thresholds must hold integers in [0, 100], one at least")
+    lev = np.unique(lev).astype(np.int32)
+    if lev.shape[0] > SWEEP_MAX_LEVENSHTEIN:
+        raise ValueError(f"{lev.shape[0]} levenshtein_thresholds, {SWEEP_MAX_LEVENSHTEIN} at most")
+    given = np.asarray(probability_thresholds)
+    if given.ndim != 1 or given.shape[0] == 0 or given.dtype == bool or not (
+            np.issubdtype(given.dtype, np.floating) or np.issubdtype(given.dtype, np.integer)):
+        raise ValueError("probability_thresholds must be a one-dimensional sequence of numbers, one at least")
+    given = given.astype(np.float64)
+    with np.errstate(over="ignore"):
+        prob = given.astype(np.float32)
+    if not np.isfinite(prob).all():
+        raise ValueError("probability_thresholds must be finite")
+    prob, first = np.unique(prob, return_index=True)
+    if prob.shape[0] > SWEEP_MAX_PROBABILITY:
+        raise ValueError(f"{prob.shape[0]} probability_thresholds, {SWEEP_MAX_PROBABILITY} at most")
+    actual = _integers(actual_title_ids, "actual_title_ids")
+    if actual.shape[0] != n_titles:
+        raise ValueError(f"{n_titles} titles but {actual.shape[0]} actual title ids")
+    ids = np.asarray(truth_title_ids, dtype=np.int64)
+    order = np.argsort(ids, kind="stable")
+    at = np.minimum(np.searchsorted(ids[order], actual), max(ids.shape[0] - 1, 0))
+    row = order[at] if ids.shape[0] else np.zeros(actual.shape[0], dtype=np.int64)
+    known = (ids[row] == actual) if ids.shape[0] else np.zeros(actual.shape[0], dtype=bool)
+    missing = actual != TRAIN_NOT_FOUND_VALUE
+    if (missing & ~known).any():
+        raise ValueError(f"actual title id {int(actual[missing & ~known][0])} is neither "
+                         f"{TRAIN_NOT_FOUND_VALUE} nor an id of the truth set")
+    return lev, prob, given[first], np.where(missing, row, -1).astype(np.int32)
+
+
+def sweep_frame(lev, shown, counts):
+    """threshold_sweep's answer from the counters int64[T, U, 4]: one line per cell, sorted by both thresholds."""
+    import pandas as pd
+    counts = np.asarray(counts, dtype=np.int64).reshape(len(lev), len(shown), 4)
+    columns = {"levenshtein_threshold": np.repeat(np.asarray(lev, dtype=np.int64), len(shown)),
+               "probability_threshold": np.tile(np.asarray(shown, dtype=np.float64), len(lev))}
+    for c, name in enumerate(ACCURACY_KEYS[:4]):
+        columns[name] = counts[:, :, c].reshape(-1)
+    columns["custom_error"] = (counts[:, :, 3] + 5 * counts[:, :, 1]).reshape(-1)
+    return pd.DataFrame(columns, columns=list(SWEEP_COLUMNS))
 
 
 def combine_stages(exact_row, close_row, model_row):
@@ -424,11 +501,11 @@ class Prediction:
     def _check_characters(chars, offsets, what):
         check_characters(chars, offsets, what)
 
-    def _default_chunk(self, device_rows=False, rank_slots=0):
+    def _default_chunk(self, device_rows=False, rank_slots=0, parts=False):
         # device_rows: the pipeline's own query CSR at capacity (rowptr, 253 columns, q_maxint per query)
-        # rank_slots: the slots per query of the rank stage's output
-        return default_chunk(self.device, BYTES_PER_PAIR * self.top_n + 64 + (8 + 4 * MAX_GRAMS + 8) * device_rows +
-                             BYTES_PER_RANK * rank_slots)
+        # rank_slots: the slots per query of the rank stage's output; parts: the close ratio taken apart, per pair
+        return default_chunk(self.device, (BYTES_PER_PAIR + BYTES_PER_PARTS * parts) * self.top_n + 64 +
+                             (8 + 4 * MAX_GRAMS + 8) * device_rows + BYTES_PER_RANK * rank_slots)
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
@@ -530,6 +607,72 @@ class Prediction:
         self.timings = timings
         return exhaustive_frame(test_index, rows, probabilities, top_rows, self.truth_title_ids)
 
+    def threshold_sweep(self, titles, actual_title_ids, levenshtein_thresholds=None, probability_thresholds=None,
+                        test_index=None):
+        """How the answers of generate_test_predictions(titles) would compare with `actual_title_ids` at every pair of
+        (levenshtein_threshold, probability_threshold): a DataFrame in long form [levenshtein_threshold,
+        probability_threshold, correctly_matched, incorrectly_matched, correctly_not_found, incorrectly_not_found,
+        custom_error], one line per cell, sorted by the first two columns (get-predictions-accuracy, cli.py:107-128,
+        for each cell).
+
+        actual_title_ids: per title the id it should get, -1 for a title with no match.  The thresholds (None: this
+        instance's own value) are sorted and de-duplicated: up to 101 integers in [0, 100] and up to 256 numbers,
+        compared as float32 like probability_threshold.  Every pair is scored once, whatever the grid: top-k, the close
+        ratio taken apart (CandidatePipeline.enqueue_close_parts), the exact stage, features and forest on all pairs;
+        then one kernel replays the decision rule for every cell and counts (enqueue_threshold_sweep).  The counters
+        stay on the device between the chunks and come back once.  `details` and `candidates` are left alone."""
+        titles = list(titles)
+        validate_queries(titles, test_index)
+        lev, prob, shown, actual_row = validate_sweep(
+            [self.levenshtein_threshold] if levenshtein_thresholds is None else levenshtein_thresholds,
+            [self.probability_threshold] if probability_thresholds is None else probability_thresholds,
+            actual_title_ids, self.truth_title_ids, len(titles))
+        timings = dict.fromkeys(("host_prepare", "top_k", "close_parts", "exact_matches", "features", "model", "sweep",
+                                 "copy_back"), 0.0)
+        counts = np.zeros(lev.shape[0] * prob.shape[0] * 4, dtype=np.int64)
+        grid = None
+        for pipeline, events in self._chunks(titles, timings, parts=True):
+            if grid is None:
+                grid = (_lib.DeviceArray.from_host(lev, self.device), _lib.DeviceArray.from_host(prob, self.device),
+                        _lib.DeviceArray.from_host(counts, self.device))
+            self._sweep_chunk(pipeline, events, timings, int(lev[0]), int(lev[-1]), actual_row, grid)
+        if grid is not None:
+            copy_started = time.perf_counter()
+            counts = grid[2].to_host()                # synchronises the null stream the stages ran on
+            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+        self.timings = timings
+        return sweep_frame(lev, shown, counts)
+
+    def evaluate(self, titles, actual_title_ids, test_index=None):
+        """The accuracy of generate_test_predictions(titles) against `actual_title_ids` at this instance's thresholds,
+        as `predictions_accuracy` reports it: the one cell of `threshold_sweep`."""
+        line = self.threshold_sweep(titles, actual_title_ids, test_index=test_index).iloc[0]
+        return {name: int(line[name]) for name in ACCURACY_KEYS}
+
+    def _sweep_chunk(self, pipeline, events, timings, t_min, t_max, actual_row, grid):
+        first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
+        lev, prob, counts = grid
+
+        def timed(name, enqueue):
+            events[name].start()
+            enqueue()
+            events[name].stop()
+
+        # 1. Jaccard top-k (synchronised, as in _chunk)
+        timed("top_k", pipeline.enqueue_top_k)
+        pipeline.sync()
+        timings["top_k"] += events["top_k"].elapsed_ms()
+        # 2. the close ratio taken apart, 3. the exact stage, 4. features and 5. the forest on ALL pairs, 6. the rule
+        # replayed per cell (the sweep entry synchronises once, to check the grid's values)
+        actual = _lib.DeviceArray.from_host(actual_row[first:last], self.device)
+        timed("close_parts", lambda: pipeline.enqueue_close_parts(t_min, t_max))
+        timed("exact_matches", pipeline.enqueue_exact_matches)
+        timed("features", pipeline.enqueue_features)
+        timed("model", lambda: pipeline.enqueue_predict(self.model))
+        timed("sweep", lambda: pipeline.enqueue_threshold_sweep(actual, lev, prob, counts))
+        for name in ("close_parts", "exact_matches", "features", "model", "sweep"):
+            timings[name] += events[name].elapsed_ms()
+
     def _run(self, titles, test_index, single=False):
         import pandas as pd
         timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "remaining_pairs",
@@ -545,7 +688,7 @@ class Prediction:
         return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
                              "probability": probability})
 
-    def _chunks(self, titles, timings, rank_slots=0):
+    def _chunks(self, titles, timings, rank_slots=0, parts=False):
         """The one loop over the queries: prepares the titles (on the device or on the host), then yields (pipeline,
         events) with each chunk loaded in turn, events holding one Timer per device stage of `timings`.  Fills
         timings' host_prepare and prepare_queries; yields nothing for no titles."""
@@ -572,7 +715,7 @@ class Prediction:
                                                    columns=self._columns)
             enc, lengths = encode_collection(chars, offsets, _CODE_OF)
             query_table = TitleTable(enc, lengths, None, self.device)
-        chunk = min(n, self.chunk_queries or self._default_chunk(device_path, rank_slots))
+        chunk = min(n, self.chunk_queries or self._default_chunk(device_path, rank_slots, parts))
         pipeline = CandidatePipeline.over(self.index, self.truth_table, query_table, self.top_n, chunk, self.device)
         timings["host_prepare"] = (time.perf_counter() - started) * 1000.0 - timings.get("prepare_queries", 0.0)
         events = {name: _lib.Timer(self.device) for name in timings

@@ -73,6 +73,17 @@ def main(n_truth=20000, n_queries=2000, top_n=10):
     unmatched = answer.loc[answer["title_id"] < 0, "test_index"].to_numpy()[:3]
     ranked = prediction.ranked_matches([raw_queries[i] for i in unmatched], n=min(3, top_n), test_index=unmatched)
     print(ranked.to_string(index=False))
+
+    # how good are the answers?  The workload knows the truth title every query was made from (-1: from none): the counts
+    # of the reference's get-predictions-accuracy at this instance's thresholds, then the same for a grid of both
+    # thresholds from one scoring pass, and the cell with the smallest custom error
+    actual = workload.actual_row                                             # ids are the truth rows here
+    print("evaluate:", prediction.evaluate(raw_queries, actual))
+    sweep = prediction.threshold_sweep(raw_queries, actual, levenshtein_thresholds=range(86, 100, 2),
+                                       probability_thresholds=np.linspace(0.5, 0.95, 10))
+    best = sweep.loc[sweep["custom_error"].idxmin()]
+    print(f"smallest custom error of {len(sweep)} cells: {int(best['custom_error'])} at levenshtein_threshold "
+          f"{int(best['levenshtein_threshold'])}, probability_threshold {best['probability_threshold']:.2f}")
     return rows, best_row, features, probabilities
 
 

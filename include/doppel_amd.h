@@ -259,6 +259,38 @@ int ds_exhaustive_rank_device(ds_titles *queries, ds_titles *truth, ds_forest *f
                               int32_t *d_out_row, float *d_out_probability, void *stream);
 int ds_exhaustive_option(const char *name, int64_t value);   /* "tile_pairs": for tests, 0 = default */
 
+/* ---- threshold sweep: the accuracy counters of cli.py:107-120 for a grid of both thresholds ----
+ * ds_close_parts_device: the ratio of ds_close_matches_device taken apart, so that it can be read at any integer
+ * threshold t afterwards: value(t) = 0 when t > d, r when r > t, else s, and the pair counts as close iff value(t) > t.
+ * d = the floor of the length pre-filter's value (100 for two empty titles), r = the rounded ratio of the titles, s = that
+ * of the token-sorted titles; uint8[n_queries * k] each in HBM, pair i = (query row q_first + i / k, truth row d_rows[i]).
+ * What no t in [t_min, t_max] can read is not computed and written as 0: r and s when d < t_min, s when r > t_max.  A row
+ * outside either table gives 0, 0, 0.  0 <= t_min <= t_max <= 100.  Asynchronous on `stream`. */
+int ds_close_parts_device(ds_titles *queries, ds_titles *truth, const int32_t *d_rows, int64_t q_first, int32_t k,
+                          int64_t n_queries, uint8_t space_code, const uint8_t *d_sort_key, int32_t t_min, int32_t t_max,
+                          uint8_t *d_d, uint8_t *d_r, uint8_t *d_s, void *stream);
+/* ds_threshold_sweep_device: for every cell (t = d_lev[i], u = d_prob[j]) the decision rule of Prediction on n_queries
+ * queries of k candidates each, and d_counts[(i * U + j) * 4 + c] += the queries of outcome c.  A stage's row counts
+ * when it is >= 0:
+ *   exact  d_exact[q];
+ *   close  the maximum value(t) among the candidates with value(t) > t, and d_rows of its holder when there is one only;
+ *   model  the maximum of d_predictions[q * k ..) (float32; a NaN in front: none, behind it: passed over), and d_rows of
+ *          its holder when there is one only and the maximum is > u (float32 compare);
+ *   none   -1.
+ * c = 0: a prediction equal to d_actual_row[q]; 1: a prediction that differs; 2: none and d_actual_row[q] < 0; 3: none
+ * and d_actual_row[q] >= 0.  The counters are ADDED to (integer atomics: any order gives the same sums), so the chunks of
+ * one evaluation accumulate; the caller zeroes them first.  d_lev: 1..101 integers in [0, 100], strictly ascending;
+ * d_prob: 1..256 finite floats, strictly ascending; both in HBM, read back and checked by the call (one synchronisation
+ * of `stream`), DS_E_ARG with nothing launched otherwise, as for k < 1 or a null pointer.  n_queries == 0 launches
+ * nothing.  The kernel is enqueued on `stream`.
+ * ds_sweep_option("queries_per_group", v) is for tests: the queries per workgroup below the cap of 256 workgroups
+ * (0 = the default, 64); the result does not depend on it. */
+int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const uint8_t *d_r, const uint8_t *d_s,
+                              const float *d_predictions, const int32_t *d_exact, const int32_t *d_actual_row,
+                              int64_t n_queries, int32_t k, const int32_t *d_lev, int32_t T, const float *d_prob,
+                              int32_t U, int64_t *d_counts, void *stream);
+int ds_sweep_option(const char *name, int64_t value);
+
 /* ---- exact matches: Prediction._find_exact_matches (predict.py:74-113) ---------------------------------------------
  * exact_row[q] = the truth row whose encoded title (length and bytes of the ds_titles rows) equals query row q's, the
  * LAST such row when several truth rows hold the title (the reference's {title: title_id} dict is filled in truth
