@@ -7,7 +7,12 @@
     training_rows.npz    FeatureEngineering._prepare_training_input_data (feature_engineering.py:207-274) on a slice of
                          the example data (3,000 truth titles, ~440 train rows with repeated ids and -1 rows): every
                          row's (kind, title, truth title, target), and per train row whether its top-100 has a near-tie
-                         at the cut (the `margin_ok` test of make_golden.py).
+                         at the cut (the `margin_ok` test of make_golden.py);
+    misspell_matrix.npz  generate_misspelled_name of the edge titles and of more crafted ones (digits only at 255
+                         characters, a space where the cut falls, short titles with digits), each MATRIX_REPEATS times
+                         with a stream of its own: per case the title, the answer, the names of the edit functions the
+                         reference applied, whether each returned its input unchanged, and the string handed to
+                         transform_title.
 
 It runs the reference's own function bodies under make_golden.py's shims (numba as pass-through decorators), with
 `random` in feature_engineering_prepare replaced by a replay object that draws from the port's stream (DESIGN.md
@@ -105,6 +110,63 @@ def _edge_titles():
     assert len(titles) >= 40 and len(set(titles)) == len(titles)
     assert len(cut(254)) == 254 and len(cut(255)) == 255
     return titles
+
+
+MATRIX_REPEATS = 64
+EDITS = ("swap_word", "add_letter", "remove_letter", "replace_letter", "add_space", "remove_space")
+
+
+def _matrix_titles():
+    """The edge titles and the ones that reach what they cannot: long titles of digits only, a space where the cut to
+    255 falls, short titles with a digit, long titles of one-letter words, more one-word titles."""
+    one_letter_words = " ".join("abcdefghijklmnopqrstuvwxyz"[i % 26] for i in range(128))
+    more = [
+        "1" * 255, "1 " * 127 + "1",                                                    # long, digits and spaces only
+        "k" * 253 + " k", "k" * 252 + " kk", "k" * 251 + " kkk", "k" * 254 + "b",       # a space at the cut
+        "ab 1", "0 0", "a 1", "1 2", "7777",                                            # short, digits
+        one_letter_words, one_letter_words[:253], "g" * 253 + "7", "h" * 126 + " " + "j" * 126 + "5",
+        "qwe", "rtyu", "12345", "zxcvbnm",                                              # one word
+    ]
+    titles = _edge_titles() + more
+    assert len(one_letter_words) == 255 and len(more[-6]) == 254 and len(more[-5]) == 254
+    assert all(3 <= len(t) <= 255 for t in titles) and len(set(titles)) == len(titles)
+    return titles
+
+
+def _misspell_matrix(prepare, replay):
+    """Every title of _matrix_titles MATRIX_REPEATS times, case i from the purpose-1 stream of i.  Per case: the
+    reference's answer, the functions it applied in order, whether each returned its input, and the string that went
+    into transform_title."""
+    log = []
+
+    def logged(name, function):
+        def call(x, length):
+            result = function(x, length)
+            log.append((name, result == x, result))
+            return result
+        return call
+
+    plain = {name: getattr(prepare, name) for name in EDITS}
+    for name, function in plain.items():
+        setattr(prepare, name, logged(name, function))
+    cases = [title for title in _matrix_titles() for _ in range(MATRIX_REPEATS)]
+    expected, functions, edited = [], [], []
+    unchanged = np.zeros((len(cases), 2), dtype=bool)
+    try:
+        for index, title in enumerate(cases):
+            del log[:]
+            replay.use(1, index)
+            expected.append(prepare.generate_misspelled_name(title))
+            assert 1 <= len(log) <= 2
+            functions.append(",".join(entry[0] for entry in log))
+            unchanged[index, :len(log)] = [entry[1] for entry in log]
+            edited.append(log[-1][2])
+    finally:
+        for name, function in plain.items():
+            setattr(prepare, name, function)
+    _save(f"{HERE}/misspell_matrix.npz", titles=_utf8(cases), expected=_utf8(expected), functions=_utf8(functions),
+          unchanged=unchanged, edited=_utf8(edited), seed=np.uint64(SEED), repeats=np.int32(MATRIX_REPEATS))
+    return len(cases)
 
 
 def _train_slice(train_lines, truth_ids, rng):
@@ -215,8 +277,11 @@ def main():
           truth_title=_utf8([r[2] for r in rows]), target=np.array([r[3] for r in rows], dtype=np.uint8),
           near_tie=~margin_ok)
     shutil.rmtree(data_dir)
+
+    # ---- misspell_matrix.npz: many draws per edge title, with the functions the reference applied
+    n_cases = _misspell_matrix(feature_engineering_prepare, replay)
     print(f"misspell_cases.npz: {len(titles)} titles; training_rows.npz: {len(rows)} rows, "
-          f"{int((~margin_ok).sum())} train rows with near-ties")
+          f"{int((~margin_ok).sum())} train rows with near-ties; misspell_matrix.npz: {n_cases} cases")
 
 
 if __name__ == "__main__":

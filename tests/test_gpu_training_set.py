@@ -83,7 +83,8 @@ def test_misspelling_rejects_what_is_not_a_transformed_title():
 
 
 @pytest.mark.parametrize("top_n, sample_n", [(top_n, sample_n) for top_n in (10, 17, 100) for sample_n in (1, 10, 16)
-                                              if sample_n <= top_n])
+                                              if sample_n <= top_n]
+                         + [(1, 1), (2, 2), (16, 16), (11, 3)])      # sample_n == top_n: the last step draws below(1)
 def test_sampler_equals_the_oracle(top_n, sample_n):
     from doppel_speller_amd import _lib
     rng = np.random.RandomState(top_n * 100 + sample_n)

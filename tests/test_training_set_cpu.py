@@ -2,6 +2,7 @@
 reference's own functions produced (tests/golden/make_golden_training.py), the evaluation split, and the checks
 FeatureEngineering makes before any device work."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -194,3 +195,112 @@ def test_misspelled_names_checks_without_the_library(monkeypatch):
             ds.generate_misspelled_names(bad)
     with pytest.raises(ValueError, match="seed"):
         ds.generate_misspelled_names(["abc"], seed=-3)
+
+
+# ---- the misspelling matrix: many draws per edge title, with the edit functions the reference applied ---------------
+EDITS = ("swap_word", "add_letter", "remove_letter", "replace_letter", "add_space", "remove_space")
+TITLE_CLASSES = {
+    "long": lambda t: len(t) >= 253,
+    "short": lambda t: len(t) <= 4,
+    "digits": lambda t: all(ch in " 0123456789" for ch in t),
+    "one word": lambda t: " " not in t,
+}
+# (class, edit, changed) cells that no title of the class can reach, each with its reason; every other cell of the
+# 4 x 6 x 2 table must occur MIN_PER_CELL times among the recorded cases
+NEVER = "cannot happen"
+UNLIKELY = "needs 11 draws in a row on a space"
+IMPOSSIBLE_CELLS = {
+    # no edit makes a letter out of a digit or a space, and both functions only accept a letter (:107, :121)
+    ("digits", "add_letter", True): NEVER,
+    ("digits", "replace_letter", True): NEVER,
+    # a one-word title gains a space only through add_space, and only one of add_space / remove_space is drawn (:168)
+    ("one word", "remove_space", True): NEVER,
+    # remove_letter returns its input only after 11 draws that all land on a space (:94-97).  A transformed title has
+    # single spaces between words and no edit puts two spaces side by side before remove_letter runs (add_space
+    # refuses a place next to a space, :133), so fewer than half of the characters are spaces: less than 2^-11 per
+    # call for any title, and for a one-word title (no space, or one after add_space among >= 3 characters) < 3^-11
+    ("long", "remove_letter", False): UNLIKELY,
+    ("short", "remove_letter", False): UNLIKELY,
+    ("digits", "remove_letter", False): UNLIKELY,
+    ("one word", "remove_letter", False): UNLIKELY,
+}
+MIN_PER_CELL = 3
+
+
+@pytest.fixture(scope="module")
+def matrix():
+    g = dict(np.load(os.path.join(GOLDEN, "misspell_matrix.npz"), allow_pickle=False))
+    g["titles"], g["expected"], g["edited"] = _strings(g["titles"]), _strings(g["expected"]), _strings(g["edited"])
+    g["functions"] = [f.split(",") for f in _strings(g["functions"])]
+    return g
+
+
+def _collapsed(text):
+    """Runs of spaces as one, stripped: transform_title (common.py:30) before the cut, for [a-z0-9 ] text."""
+    return re.sub(" +", " ", text).strip()
+
+
+def test_matrix_layout(matrix):
+    titles, repeats = matrix["titles"], int(matrix["repeats"])
+    assert repeats >= 64 and len(titles) % repeats == 0 and len(titles) >= 3000
+    assert all(len(set(titles[i:i + repeats])) == 1 for i in range(0, len(titles), repeats))
+    assert len(set(titles)) == len(titles) // repeats
+    assert matrix["unchanged"].shape == (len(titles), 2)
+    for functions, unchanged in zip(matrix["functions"], matrix["unchanged"]):
+        assert 1 <= len(functions) <= 2 and set(functions) <= set(EDITS) and len(set(functions)) == len(functions)
+        assert len(functions) == 2 or not unchanged[1]
+    for required in ("1" * 255, "1 " * 127 + "1", "k" * 253 + " k", "k" * 252 + " kk", "ab 1", "0 0", "a 1"):
+        assert required in titles
+    assert any(len(t) == 255 and all(len(w) == 1 for w in t.split(" ")) for t in titles)
+    assert any(len(t) == 254 and t[-1].isdigit() for t in titles)
+
+
+def test_oracle_equals_the_reference_on_the_matrix(matrix):
+    seed = int(matrix["seed"])
+    got = [ts.misspell(title, seed, index) for index, title in enumerate(matrix["titles"])]
+    bad = [i for i, (a, b) in enumerate(zip(got, matrix["expected"])) if a != b]
+    assert not bad, [(i, matrix["titles"][i], matrix["functions"][i], got[i], matrix["expected"][i]) for i in bad[:5]]
+
+
+def test_matrix_covers_every_possible_cell(matrix):
+    """Every (title class, edit, changed / returned unchanged) cell that a title of the class can reach occurs at least
+    MIN_PER_CELL times in what the reference recorded; the others are listed in IMPOSSIBLE_CELLS with their reason."""
+    count = {(name, edit, changed): 0 for name in TITLE_CLASSES for edit in EDITS for changed in (True, False)}
+    for title, functions, unchanged in zip(matrix["titles"], matrix["functions"], matrix["unchanged"]):
+        for name, belongs in TITLE_CLASSES.items():
+            if belongs(title):
+                for edit, same in zip(functions, unchanged):
+                    count[(name, edit, not bool(same))] += 1
+    print("\nclass      edit             changed  unchanged")
+    for name in TITLE_CLASSES:
+        for edit in EDITS:
+            notes = [f"{'changed' if c else 'unchanged'}: {IMPOSSIBLE_CELLS[(name, edit, c)]}"
+                     for c in (True, False) if (name, edit, c) in IMPOSSIBLE_CELLS]
+            print(f"{name:10s} {edit:16s} {count[(name, edit, True)]:7d} {count[(name, edit, False)]:10d}  "
+                  + "; ".join(notes))
+    assert set(IMPOSSIBLE_CELLS) <= set(count) and len(count) == 48
+    for cell, reason in IMPOSSIBLE_CELLS.items():
+        if reason == NEVER:
+            assert count[cell] == 0, cell
+    short = {cell: n for cell, n in count.items() if cell not in IMPOSSIBLE_CELLS and n < MIN_PER_CELL}
+    assert not short, short
+
+
+def test_matrix_reaches_the_cut_the_second_strip_and_the_padding(matrix):
+    grown = {256: 0, 257: 0}
+    second_strip = padded = 0
+    for title, functions, unchanged, edited, expected in zip(matrix["titles"], matrix["functions"], matrix["unchanged"],
+                                                             matrix["edited"], matrix["expected"]):
+        inserting = [f for f, same in zip(functions, unchanged) if f in ("add_letter", "add_space") and not same]
+        if len(title) >= 253 and len(inserting) == 2 and len(edited) == len(title) + 2 and len(edited) in grown:
+            grown[len(edited)] += 1                               # two inserting edits, then the cut
+            assert len(expected) <= 255 and edited.startswith(expected)
+        stripped = _collapsed(edited)
+        if len(stripped) > 255 and stripped[254] == " ":          # the cut leaves a trailing space
+            second_strip += 1
+            assert expected == stripped[:254] and len(expected) < 255
+        if len(stripped) < 3:
+            padded += 1
+            assert expected == "0" * (3 - len(stripped)) + stripped and len(expected) == 3
+    print(f"\ngrown to 256: {grown[256]}, to 257: {grown[257]}; second strip: {second_strip}; padded: {padded}")
+    assert grown[256] >= 3 and grown[257] >= 3 and second_strip >= 3 and padded >= 3
