@@ -14,6 +14,9 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         .evaluate(titles, actual_title_ids)   -> the counts of get-predictions-accuracy (cli.py) and custom_error
         .threshold_sweep(titles, actual_title_ids, levenshtein_thresholds, probability_thresholds)   -> those counts
             for every pair of the two thresholds, from one scoring pass (this project's own)
+        .duplicate_groups(levenshtein_threshold, probability_threshold)   -> the groups of truth titles that are
+            duplicates of each other: the connected components of the exact, close and model links among the truth
+            set's own rows, found on the device (this project's own)
     predictions_accuracy(predicted_title_ids, actual_title_ids)   -> the same counts from two id arrays
     ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
@@ -33,8 +36,9 @@ from .feature_engineering import (  # noqa: F401
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
 from .forest import ForestModel  # noqa: F401
-from .prediction import (EXHAUSTIVE_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS, Candidates, Prediction,  # noqa: F401
-                         predictions_accuracy, validate_exhaustive, validate_rank, validate_sweep)
+from .prediction import (DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS, LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS,  # noqa: F401
+                         Candidates, Prediction, duplicate_frame, predictions_accuracy, validate_duplicates,
+                         validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, train_model)

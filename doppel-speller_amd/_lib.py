@@ -10,7 +10,7 @@ _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip",
             "ds_train.hip", "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip",
-            "ds_sweep.hip")
+            "ds_sweep.hip", "ds_duplicates.hip")
 _lib = None
 
 
@@ -152,6 +152,10 @@ def _declare(handle):
         "ds_close_parts_device": [p, p, p, c.c_int64, c.c_int32, c.c_int64, c.c_uint8, p, c.c_int32, c.c_int32, p, p, p, p],
         "ds_threshold_sweep_device": [p, p, p, p, p, p, p, c.c_int64, c.c_int32, p, c.c_int32, p, c.c_int32, p, p],
         "ds_sweep_option": [c.c_char_p, c.c_int64],
+        "ds_duplicate_begin_device": [p, c.c_int64, p, p],
+        "ds_duplicate_links_device": [p, p, p, p, c.c_int64, c.c_int64, c.c_int32, c.c_int64, c.c_int32, c.c_float, p, p, p, p],
+        "ds_duplicate_finish_device": [p, c.c_int64, p, p, p],
+        "ds_duplicates_option": [c.c_char_p, c.c_int64],
         "ds_exact_matches": [p, p, c.c_int64, p],
         "ds_exact_matches_device": [p, p, c.c_int64, c.c_int64, p, p, p],
         "ds_problem_create": [p, p, c.c_int64, p, p, c.c_int64, c.c_int32, c.POINTER(p)],
@@ -227,7 +231,8 @@ EXPORTED_SYMBOLS = (
     "ds_timer_elapsed_ms", "ds_feature_cuts_device", "ds_cuts_option", "ds_trainer_create_device",
     "ds_trainer_set_eval_device", "ds_gather_rows_device", "ds_rank_matches_device", "ds_rank_option",
     "ds_exhaustive_fold_device", "ds_exhaustive_finish_device", "ds_exhaustive_rank_device", "ds_exhaustive_option",
-    "ds_close_parts_device", "ds_threshold_sweep_device", "ds_sweep_option")
+    "ds_close_parts_device", "ds_threshold_sweep_device", "ds_sweep_option", "ds_duplicate_begin_device",
+    "ds_duplicate_links_device", "ds_duplicate_finish_device", "ds_duplicates_option")
 
 
 def lib():

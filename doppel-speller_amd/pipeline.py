@@ -59,6 +59,7 @@ class CandidatePipeline:
         self._ranked, self._ranked_n = None, 0
         self._exhaustive, self._exhaustive_n = None, 0
         self._parts = None
+        self._reasons = None
 
     def _allocate_stages(self):
         """The outputs of the stages after top-k (by `over`, or by the first of their enqueues)."""
@@ -266,6 +267,30 @@ class CandidatePipeline:
             self.rows_ptr, *(a.ptr for a in self._parts), self._predictions.ptr, self._exact.ptr,
             _lib.pointer(actual_rows), self.n_queries, self.k, _lib.pointer(lev), lev.shape[0], _lib.pointer(prob),
             prob.shape[0], _lib.pointer(counts), _lib.pointer(stream)), "ds_threshold_sweep_device")
+
+    def enqueue_duplicate_links(self, parent, counts, levenshtein_threshold, probability_threshold, use_model,
+                                reasons=False, stream=None):
+        """The links among this chunk's rows and their candidates joined into the union-find forest `parent`
+        (ds_duplicate_links_device), for a pipeline whose query table IS its truth table, over this pipeline's own
+        buffers: the top-k rows, the ratios of `enqueue_close_matches`, the exact rows of `enqueue_exact_matches` and,
+        with `use_model`, the predictions of `enqueue_predict` on all pairs.  parent: int32[n_truth] in HBM, counts:
+        int64[3] in HBM (exact, close, model links), both started by ds_duplicate_begin_device and ADDED to.  reasons:
+        keep the reason of every slot for `duplicate_reasons` (the buffer is allocated by the first call that asks)."""
+        self._allocate_stages()
+        if reasons and self._reasons is None:
+            self._reasons = _lib.DeviceArray((self.capacity, self.k), np.uint8, self.device)
+        _lib.check(_lib.lib().ds_duplicate_links_device(
+            self.rows_ptr, self._close[0].ptr, self._predictions.ptr if use_model else _lib.pointer(None),
+            self._exact.ptr, self.q_first, self.n_queries, self.k, self.n_truth, int(levenshtein_threshold),
+            float(probability_threshold), _lib.pointer(parent), self._reasons.ptr if reasons else _lib.pointer(None),
+            _lib.pointer(counts), _lib.pointer(stream)), "ds_duplicate_links_device")
+
+    def duplicate_reasons(self):
+        """uint8[Q, k] of the last `enqueue_duplicate_links(reasons=True)`: bit 0 close, bit 1 model, 0 for a slot that
+        links nothing."""
+        if self._reasons is None:
+            raise ValueError("enqueue_duplicate_links(reasons=True) comes first")
+        return self._reasons.to_host(self.n_queries)
 
     def matches(self, n_remaining):
         """(query rows, matched truth row or -1) of the last `enqueue_select_matches`."""

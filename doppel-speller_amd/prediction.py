@@ -40,6 +40,9 @@ EXHAUSTIVE_COLUMNS = ("test_index", "rank", "title_id", "match_row", "probabilit
 SWEEP_COLUMNS = ("levenshtein_threshold", "probability_threshold", "correctly_matched", "incorrectly_matched",
                  "correctly_not_found", "incorrectly_not_found", "custom_error")
 ACCURACY_KEYS = SWEEP_COLUMNS[2:]
+DUPLICATE_COLUMNS = ("group_id", "group_size", "title_id", "row")
+LINK_COLUMNS = ("row", "match_row", "title_id", "match_title_id", "levenshtein_ratio", "probability", "stage")
+REASON_CLOSE, REASON_MODEL = 1, 2        # bits of a slot's reason (ds_duplicate_links_device)
 SWEEP_MAX_LEVENSHTEIN, SWEEP_MAX_PROBABILITY = 101, 256      # thresholds per axis at most (ds_threshold_sweep_device)
 # what ranked_matches(keep_candidates=True) keeps of a call, per query: the top-n rows, their fuzzy ratios and model
 # probabilities, the exact row and the close row (-1: none; the close row also where the exact stage matched)
@@ -227,6 +230,67 @@ def sweep_frame(lev, shown, counts):
         columns[name] = counts[:, :, c].reshape(-1)
     columns["custom_error"] = (counts[:, :, 3] + 5 * counts[:, :, 1]).reshape(-1)
     return pd.DataFrame(columns, columns=list(SWEEP_COLUMNS))
+
+
+def validate_duplicates(levenshtein_threshold, probability_threshold):
+    """duplicate_groups' checks of its thresholds (no library needed) -> (int, float): an integer in [0, 100] (a bool is
+    refused) and a finite number, which is compared as float32 like probability_threshold."""
+    if isinstance(levenshtein_threshold, bool) or not isinstance(levenshtein_threshold, (int, np.integer)) or \
+            not 0 <= levenshtein_threshold <= 100:
+        raise ValueError(f"levenshtein_threshold must be an integer in [0, 100], not {levenshtein_threshold!r}")
+    if isinstance(probability_threshold, (bool, np.bool_)) or \
+            not isinstance(probability_threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f"probability_threshold must be a finite number, not {probability_threshold!r}")
+    with np.errstate(over="ignore"):
+        finite = np.isfinite(np.float32(probability_threshold))
+    if not finite:
+        raise ValueError(f"probability_threshold must be a finite number, not {probability_threshold!r}")
+    return int(levenshtein_threshold), float(probability_threshold)
+
+
+def duplicate_frame(labels, sizes, truth_title_ids):
+    """duplicate_groups' answer from the labels (a row's group = the lowest row of it) and sizes int32[n_truth] of the
+    finish step: one line per row whose group holds two rows at least, sorted by the group's lowest row, then by row;
+    group_id is the title id of that lowest row."""
+    import pandas as pd
+    labels, sizes = np.asarray(labels).astype(np.int64), np.asarray(sizes).astype(np.int64)
+    ids = np.asarray(truth_title_ids, dtype=np.int64)
+    row = np.nonzero(sizes >= 2)[0].astype(np.int64)
+    row = row[np.argsort(labels[row], kind="stable")]
+    return pd.DataFrame({"group_id": ids[labels[row]], "group_size": sizes[row], "title_id": ids[row], "row": row},
+                        columns=list(DUPLICATE_COLUMNS))
+
+
+def links_frame(chunks, truth_title_ids, n_truth):
+    """duplicate_groups' `links` from what each chunk copied back: (q_first, rows int32[Q, k], ratios uint8[Q, k],
+    probabilities float32[Q, k] or None, exact int32[Q], reasons uint8[Q, k]).  One line per exact link (stage 1, ratio
+    100, probability NaN) and per slot with a non-zero reason (stage 2 when close, else 3), sorted by row, then the
+    exact link first, then by slot.  A link seen from both of its rows appears twice."""
+    import pandas as pd
+    ids = np.asarray(truth_title_ids, dtype=np.int64)
+    parts = {name: [] for name in ("row", "match_row", "levenshtein_ratio", "probability", "stage")}
+    for q_first, rows, ratios, probabilities, exact, reasons in chunks:
+        count, k = rows.shape
+        own = q_first + np.arange(count, dtype=np.int64)
+        exact = exact.astype(np.int64)
+        linked = np.nonzero((exact >= 0) & (exact < n_truth) & (exact != own))[0]
+        query, slot = np.nonzero(reasons)
+        order = np.argsort(np.concatenate((linked * (k + 1), query * (k + 1) + slot + 1)), kind="stable")
+        slot_probability = np.full(query.shape[0], np.nan, np.float32) if probabilities is None else \
+            probabilities[query, slot].astype(np.float32)
+        slot_stage = np.where(reasons[query, slot] & REASON_CLOSE, STAGE_CLOSE, STAGE_MODEL).astype(np.int8)
+        parts["row"].append(np.concatenate((own[linked], own[query]))[order])
+        parts["match_row"].append(np.concatenate((exact[linked], rows[query, slot].astype(np.int64)))[order])
+        parts["levenshtein_ratio"].append(
+            np.concatenate((np.full(linked.shape[0], 100, np.uint8), ratios[query, slot].astype(np.uint8)))[order])
+        parts["probability"].append(
+            np.concatenate((np.full(linked.shape[0], np.nan, np.float32), slot_probability))[order])
+        parts["stage"].append(np.concatenate((np.full(linked.shape[0], STAGE_EXACT, np.int8), slot_stage))[order])
+    empty = {"row": np.int64, "match_row": np.int64, "levenshtein_ratio": np.uint8, "probability": np.float32,
+             "stage": np.int8}
+    columns = {name: np.concatenate(held) if held else np.zeros(0, empty[name]) for name, held in parts.items()}
+    columns["title_id"], columns["match_title_id"] = ids[columns["row"]], ids[columns["match_row"]]
+    return pd.DataFrame(columns, columns=list(LINK_COLUMNS))
 
 
 def combine_stages(exact_row, close_row, model_row):
@@ -486,6 +550,8 @@ class Prediction:
         self.prepare_queries = prepare_queries
         self.details = None
         self.candidates = None
+        self.link_counts = None
+        self.links = None
         self.timings = {}
 
         self.truth_titles = self._transform(truth_titles)
@@ -648,6 +714,81 @@ class Prediction:
         as `predictions_accuracy` reports it: the one cell of `threshold_sweep`."""
         line = self.threshold_sweep(titles, actual_title_ids, test_index=test_index).iloc[0]
         return {name: int(line[name]) for name in ACCURACY_KEYS}
+
+    def duplicate_groups(self, levenshtein_threshold=None, probability_threshold=None, model_links=True,
+                         return_links=False):
+        """The groups of truth titles that are duplicates of each other: a DataFrame [group_id, group_size, title_id,
+        row], one line per truth row whose group holds two rows at least, sorted by the group's lowest row, then by row;
+        group_id is the title_id of that lowest row.
+
+        Every truth title is scored against its own Jaccard top_n as a query would be (the row itself normally takes
+        one of the top_n slots, so a row sees top_n - 1 others).  Two rows are linked when they hold the same transformed
+        title (the exact stage), when their fuzzy ratio is above levenshtein_threshold (the close stage) or, with
+        model_links, when the model's probability for the pair is above probability_threshold; a threshold of None is
+        this instance's own.  The groups are the connected components of the links: a row belongs to the group of any
+        row it is linked to, directly or through others.  They are found on the device by a union-find that lives across
+        the chunks (CandidatePipeline.enqueue_duplicate_links); labels, sizes and counters come back once.  With
+        model_links=False neither features nor forest run.
+
+        After a call `link_counts` holds the exact links, the slots that are close and the slots only the model links
+        ({"exact", "close", "model"}; a link seen from both of its rows counts twice), and `links` is None or, with
+        return_links, a DataFrame [row, match_row, title_id, match_title_id, levenshtein_ratio, probability, stage]:
+        one line per exact link (stage 1, ratio 100, probability NaN) and per linking slot (stage 2 when close, else 3),
+        sorted by row, the exact link first, then by slot; nothing is merged.  `details` and `candidates` are left
+        alone.  The errors are those of generate_test_predictions(truth_titles)."""
+        lev, prob = validate_duplicates(self.levenshtein_threshold if levenshtein_threshold is None else levenshtein_threshold,
+                                        self.probability_threshold if probability_threshold is None else probability_threshold)
+        timings = dict.fromkeys(("host_prepare", "prepare_queries", "top_k", "close_matches", "exact_matches", "features",
+                                 "model", "links", "finish", "copy_back"), 0.0)
+        started = time.perf_counter()
+        n = len(self.truth_titles)
+        chunk = min(n, self.chunk_queries or self._default_chunk(device_rows=True))
+        pipeline = CandidatePipeline.over(self.index, self.truth_table, self.truth_table, self.top_n, chunk, self.device)
+        parent, counts = _lib.DeviceArray((n,), np.int32, self.device), _lib.DeviceArray((3,), np.int64, self.device)
+        labels, sizes = _lib.DeviceArray((n,), np.int32, self.device), _lib.DeviceArray((n,), np.int32, self.device)
+        _lib.check(_lib.lib().ds_duplicate_begin_device(parent.ptr, n, counts.ptr, _lib.pointer(None)),
+                   "ds_duplicate_begin_device")
+        events = {name: _lib.Timer(self.device) for name in timings if name not in ("host_prepare", "copy_back")}
+        timings["host_prepare"] = (time.perf_counter() - started) * 1000.0
+        stages = ["close_matches", "exact_matches"] + (["features", "model"] if model_links else []) + ["links"]
+        kept = []
+
+        def timed(name, enqueue):
+            events[name].start()
+            enqueue()
+            events[name].stop()
+
+        for first in range(0, n, chunk):
+            timed("prepare_queries", lambda: pipeline.load_queries_device(self._space, first, min(n, first + chunk)))
+            # 1. Jaccard top-k (synchronised, as in _chunk)
+            timed("top_k", pipeline.enqueue_top_k)
+            pipeline.sync()
+            # 2. close matches, 3. the exact stage, 4. features and 5. the forest on ALL pairs, 6. the links
+            timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=lev))
+            timed("exact_matches", pipeline.enqueue_exact_matches)
+            if model_links:
+                timed("features", pipeline.enqueue_features)
+                timed("model", lambda: pipeline.enqueue_predict(self.model))
+            timed("links", lambda: pipeline.enqueue_duplicate_links(parent, counts, lev, prob, model_links,
+                                                                    reasons=return_links))
+            for name in ["prepare_queries", "top_k"] + stages:
+                timings[name] += events[name].elapsed_ms()
+            if return_links:
+                copy_started = time.perf_counter()
+                kept.append((first, pipeline.rows(), pipeline.close_matches()[0],
+                             pipeline.predictions() if model_links else None, pipeline.exact_matches(),
+                             pipeline.duplicate_reasons()))
+                timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+        timed("finish", lambda: _lib.check(_lib.lib().ds_duplicate_finish_device(
+            parent.ptr, n, labels.ptr, sizes.ptr, _lib.pointer(None)), "ds_duplicate_finish_device"))
+        timings["finish"] = events["finish"].elapsed_ms()
+        copy_started = time.perf_counter()
+        host_labels, host_sizes, host_counts = labels.to_host(), sizes.to_host(), counts.to_host()
+        timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+        self.timings = timings
+        self.link_counts = dict(zip(("exact", "close", "model"), (int(c) for c in host_counts)))
+        self.links = links_frame(kept, self.truth_title_ids, n) if return_links else None
+        return duplicate_frame(host_labels, host_sizes, self.truth_title_ids)
 
     def _sweep_chunk(self, pipeline, events, timings, t_min, t_max, actual_row, grid):
         first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries

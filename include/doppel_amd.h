@@ -291,6 +291,47 @@ int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const u
                               int32_t U, int64_t *d_counts, void *stream);
 int ds_sweep_option(const char *name, int64_t value);
 
+/* ---- duplicate groups: the connected components of the truth set under its own links -----------
+ * The project's own stage: the truth table is its own query table, the stages above score every row against its k
+ * candidates, and the rows that score as one entity are joined into groups.  The state is a union-find forest
+ * int32 d_parent[n_truth] in HBM, owned by the caller: d_parent[i] <= i always, d_parent[i] == i marks a root.  n_truth
+ * is below 2^31.  All calls of one run go on one stream.
+ *
+ * ds_duplicate_begin_device: d_parent[i] = i and d_counts[0..3) = 0.  With n_truth == 0 no kernel is launched; the
+ * counters are zeroed all the same (a memset on `stream`), so that what the caller reads back is defined.
+ *
+ * ds_duplicate_links_device: query rows [q_first, q_first + n_queries) of the truth table, slot j of query q (absolute
+ * row a = q_first + q) holding t = d_rows[q*k + j]:
+ *   skipped  t < 0, t >= n_truth or t == a;
+ *   close    d_ratios[q*k + j] > levenshtein_threshold;
+ *   model    d_predictions != NULL and d_predictions[q*k + j] > probability_threshold (float32; a NaN is not above);
+ *   reason   d_reason[q*k + j] = close | model << 1, 0 for a skipped slot; every slot is written (d_reason may be NULL);
+ *   links    a non-zero reason joins a and t; when d_exact != NULL and e = d_exact[q] has 0 <= e < n_truth and e != a, a
+ *            and e are joined as well (identical titles meet in the last row that holds them: twins form one group
+ *            even where the index left twins of rank >= k out of the candidates);
+ *   counts   d_counts[0] += the exact links, [1] += the slots with close, [2] += the slots with model and not close
+ *            (integer atomics: any order gives the same sums).
+ * Joining is lock-free: both roots are found with path halving and the LARGER root is hooked under the smaller one by
+ * one compare-and-swap, tried again from the value it returns when it loses.  The root of a component therefore ends as
+ * its lowest row, whatever the schedule, the chunking or the order of the links.  Calls accumulate into d_parent.
+ * DS_E_ARG, with nothing launched: any other null pointer, k < 1, a negative count, rows that are not rows of the truth
+ * table (q_first + n_queries > n_truth), a threshold outside [0, 100], a probability threshold that is not finite.
+ * n_queries == 0 or n_truth == 0 launches nothing.
+ *
+ * ds_duplicate_finish_device: d_label[i] = the root of i (its group's lowest row), d_size[i] = the rows with that label;
+ * every entry of both is written.  d_parent is compressed on the way (every entry points at its root): the groups stay
+ * the same and more links may follow.
+ *
+ * ds_duplicates_option("max_blocks", v), v in [0, 2^20], is for tests: the cap of every grid of this stage, which
+ * strides beyond it (0 = the default, 2048); the result does not depend on it.  Asynchronous on `stream`. */
+int ds_duplicate_begin_device(int32_t *d_parent, int64_t n_truth, int64_t *d_counts, void *stream);
+int ds_duplicate_links_device(const int32_t *d_rows, const uint8_t *d_ratios, const float *d_predictions,
+                              const int32_t *d_exact, int64_t q_first, int64_t n_queries, int32_t k, int64_t n_truth,
+                              int32_t levenshtein_threshold, float probability_threshold, int32_t *d_parent,
+                              uint8_t *d_reason, int64_t *d_counts, void *stream);
+int ds_duplicate_finish_device(int32_t *d_parent, int64_t n_truth, int32_t *d_label, int32_t *d_size, void *stream);
+int ds_duplicates_option(const char *name, int64_t value);
+
 /* ---- exact matches: Prediction._find_exact_matches (predict.py:74-113) ---------------------------------------------
  * exact_row[q] = the truth row whose encoded title (length and bytes of the ds_titles rows) equals query row q's, the
  * LAST such row when several truth rows hold the title (the reference's {title: title_id} dict is filled in truth
