@@ -17,7 +17,12 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         .duplicate_groups(levenshtein_threshold, probability_threshold)   -> the groups of truth titles that are
             duplicates of each other: the connected components of the exact, close and model links among the truth
             set's own rows, found on the device (this project's own)
+        .explain(titles)   -> for every title its best candidate by the model and why: the contribution of each of
+            the 66 features to that pair's margin (TreeSHAP, or Saabas), computed on the device (this project's own);
+            FEATURE_NAMES names the columns, top_contributions(contributions, n) picks the largest per row
     predictions_accuracy(predicted_title_ids, actual_title_ids)   -> the same counts from two id arrays
+    ForestModel.fit_cover(rows) / set_cover(cover) / predict_contributions(rows)   -> node cover and per-feature
+        contributions of a model (xgboost's pred_contribs / approx_contribs)
     ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
@@ -31,14 +36,14 @@ there is no CPU fallback -- importing works without the library, calling anythin
 from . import _lib  # noqa: F401
 from ._lib import DoppelError, build_library, library_path  # noqa: F401
 from .feature_engineering import (  # noqa: F401
-    FEATURES_COUNT, TitleTable, construct_features, construct_features_indexed, encode_title, encode_titles,
+    FEATURES_COUNT, FEATURE_NAMES, TitleTable, construct_features, construct_features_indexed, encode_title, encode_titles,
     get_truth_words_counts, levenshtein_ratio_batch, find_close_matches, exact_matches, ALLOWED_CHARACTERS, SPACE_CODE, SORT_KEY)
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
-from .forest import ForestModel  # noqa: F401
+from .forest import ForestModel, validate_cover  # noqa: F401
 from .prediction import (DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS, LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS,  # noqa: F401
-                         Candidates, Prediction, duplicate_frame, predictions_accuracy, validate_duplicates,
-                         validate_exhaustive, validate_rank, validate_sweep)
+                         EXPLAIN_COLUMNS, Candidates, Prediction, duplicate_frame, predictions_accuracy,
+                         top_contributions, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, train_model)

@@ -10,7 +10,7 @@ _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip",
             "ds_train.hip", "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip",
-            "ds_sweep.hip", "ds_duplicates.hip")
+            "ds_sweep.hip", "ds_duplicates.hip", "ds_contributions.hip")
 _lib = None
 
 
@@ -167,6 +167,14 @@ def _declare(handle):
         "ds_forest_create": [p, p, p, p, p, p, c.c_int32, c.c_int32, c.c_float, c.c_int, c.POINTER(p)],
         "ds_forest_predict": [p, p, c.c_int64, p, p],
         "ds_forest_predict_device": [p, p, c.c_int64, p, p, p],
+        "ds_forest_cover_device": [p, p, c.c_int64, p],
+        "ds_forest_cover_set": [p, p],
+        "ds_forest_cover_read": [p, p],
+        "ds_forest_cover_clear": [p],
+        "ds_forest_option": [p, c.c_char_p, c.c_int64],
+        "ds_forest_contributions_device": [p, p, c.c_int64, p, c.c_int, p],
+        "ds_forest_contributions": [p, p, c.c_int64, p, c.c_int],
+        "ds_best_pairs_device": [p, p, c.c_int64, c.c_int32, p, p, p, p, p],
         "ds_trainer_create": [p, c.c_int64, c.c_int32, p, p, c.c_int32, c.c_double, c.c_double, c.c_double, c.c_double,
                               c.c_int, c.POINTER(p)],
         "ds_trainer_set_labels": [p, p],
@@ -232,7 +240,9 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_set_eval_device", "ds_gather_rows_device", "ds_rank_matches_device", "ds_rank_option",
     "ds_exhaustive_fold_device", "ds_exhaustive_finish_device", "ds_exhaustive_rank_device", "ds_exhaustive_option",
     "ds_close_parts_device", "ds_threshold_sweep_device", "ds_sweep_option", "ds_duplicate_begin_device",
-    "ds_duplicate_links_device", "ds_duplicate_finish_device", "ds_duplicates_option")
+    "ds_duplicate_links_device", "ds_duplicate_finish_device", "ds_duplicates_option", "ds_forest_cover_device",
+    "ds_forest_cover_set", "ds_forest_cover_read", "ds_forest_cover_clear", "ds_forest_option",
+    "ds_forest_contributions_device", "ds_forest_contributions", "ds_best_pairs_device")
 
 
 def lib():

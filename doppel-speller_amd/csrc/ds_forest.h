@@ -1,0 +1,54 @@
+// The tree ensemble as it lives in HBM and on the host, shared by ds_forest.hip (prediction) and ds_contributions.hip
+// (node cover and per-feature contributions).
+#pragma once
+
+#include "ds_common.h"
+
+namespace ds {
+
+constexpr int kForestThreads = 256;
+constexpr int kForestFeaturesMax = 96;  // LDS staging: kForestThreads x n_features floats (66 for this reference)
+constexpr int kContributionsMaxDepth = 16;  // splits on a root-to-leaf path at most (ds_forest_contributions*)
+
+// One element of a root-to-leaf path: all of the path's splits on one feature merged.  A row follows the element when
+// its value v is NaN and nan_follows, or is not NaN and !(v < lo) && !(v >= hi) (a NaN bound stands for "no bound").
+struct PathElement {
+    int32_t feature;
+    uint32_t nan_follows;
+    float lo, hi;
+    double zero_fraction;      // product of cover[child] / cover[parent] over the merged splits
+    double zero_reciprocal;    // 1 / zero_fraction
+};
+
+}  // namespace ds
+
+struct ds_forest {
+    int device = 0;
+    int32_t n_trees = 0, n_features = 0;
+    int64_t n_nodes = 0;
+    float base_margin = 0.f;
+    ds::DeviceBuffer<int4> nodes;          // (feature or -1, yes, no, missing) per node, tree-relative child ids
+    ds::DeviceBuffer<float> threshold;     // split condition, or the leaf value
+    ds::DeviceBuffer<int64_t> tree_offsets;
+    // the same model on the host (what the path decomposition of ds_contributions.hip reads)
+    std::vector<int4> h_nodes;
+    std::vector<float> h_threshold;
+    std::vector<int64_t> h_offsets;
+    // node cover (ds_contributions.hip): none, counted on the device (integer counters in HBM) or installed by the caller
+    enum CoverState { kCoverNone = 0, kCoverCounted = 1, kCoverSet = 2 };
+    int cover_state = kCoverNone;
+    std::vector<double> cover;                      // kCoverSet: the caller's values
+    ds::DeviceBuffer<unsigned long long> counts;    // kCoverCounted: rows that reached each node
+    int shape_checked = 0;                          // 0 not yet, 1 every tree is a proper binary tree
+    std::vector<int32_t> parent;                    // global parent node of every node, -1 for a root or an unreachable node
+    int64_t max_blocks = 0;                         // ds_forest_option("max_blocks"): 0 = the default of each stage
+    // what the contributions kernels read, derived from the cover when they are first asked for
+    bool prepared = false;
+    int64_t n_paths = 0;
+    int32_t max_elements = 0;
+    double bias = 0.0;
+    ds::DeviceBuffer<int32_t> path_start;           // [n_paths + 1] first element of every path
+    ds::DeviceBuffer<double> path_leaf;             // [n_paths] leaf value
+    ds::DeviceBuffer<ds::PathElement> elements;
+    ds::DeviceBuffer<double> node_mean;             // [n_nodes] cover-weighted mean leaf value of the subtree
+};

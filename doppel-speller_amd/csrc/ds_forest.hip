@@ -12,22 +12,9 @@
 // One thread per row: the rows of a workgroup are staged in LDS (row-major 66-float reads would be uncoalesced), the
 // node arrays (a few hundred KiB for a typical model) stay L2-resident and are walked by all rows of a wavefront in
 // the same tree at the same time.
-#include "ds_common.h"
-
-struct ds_forest {
-    int device = 0;
-    int32_t n_trees = 0, n_features = 0;
-    int64_t n_nodes = 0;
-    float base_margin = 0.f;
-    ds::DeviceBuffer<int4> nodes;          // (feature or -1, yes, no, missing) per node, tree-relative child ids
-    ds::DeviceBuffer<float> threshold;     // split condition, or the leaf value
-    ds::DeviceBuffer<int64_t> tree_offsets;
-};
+#include "ds_forest.h"
 
 namespace ds {
-
-constexpr int kForestThreads = 256;
-constexpr int kForestFeaturesMax = 96;  // LDS staging: kForestThreads x n_features floats (66 for this reference)
 
 struct ForestArgs {
     const int4 *nodes;
@@ -116,6 +103,8 @@ int ds_forest_create(const int32_t *feature, const float *threshold, const int32
     forest->n_features = n_features;
     forest->n_nodes = n_nodes;
     forest->base_margin = base_margin;
+    forest->h_threshold.assign(threshold, threshold + n_nodes);
+    forest->h_offsets.assign(tree_offsets, tree_offsets + n_trees + 1);
     int status = forest->nodes.upload(nodes.data(), nodes.size());
     if (status == DS_OK && nodes.empty()) status = forest->nodes.allocate(1);
     if (status == DS_OK) status = forest->threshold.upload(threshold, static_cast<size_t>(n_nodes));
@@ -125,6 +114,7 @@ int ds_forest_create(const int32_t *feature, const float *threshold, const int32
         delete forest;
         return status;
     }
+    forest->h_nodes = std::move(nodes);
     *out = forest;
     return DS_OK;
 }

@@ -16,6 +16,13 @@ NUMBER_OF_CHARACTERS_DATA_TYPE = np.uint8                      # settings.py:67
 MAX_CHARACTERS_ALLOWED_IN_THE_TITLE = 255                      # settings.py:68
 ENCODING_FLOAT_TYPE = np.float32                               # settings.py:71
 FEATURES_COUNT = 6 + (4 * NUMBER_OF_WORDS_FEATURES)            # feature_engineering.py:67
+# what each column of construct_features holds (feature_engineering.py:164-169), in this project's words
+FEATURE_NAMES = (("title_characters", "truth_characters", "title_words", "truth_words", "title_ratio",
+                  "rebuilt_title_ratio")
+                 + tuple(f"word_{w + 1}_best_ratio" for w in range(NUMBER_OF_WORDS_FEATURES))
+                 + tuple(f"word_{w + 1}_characters" for w in range(NUMBER_OF_WORDS_FEATURES))
+                 + tuple(f"word_{w + 1}_idf" for w in range(NUMBER_OF_WORDS_FEATURES))
+                 + tuple(f"word_{w + 1}_idf_rank" for w in range(NUMBER_OF_WORDS_FEATURES)))
 ALLOWED_CHARACTERS = "- abcdefghijklmnopqrstuvwxyz0123456789"  # feature_engineering.py:200 ('-' = fill, code 0)
 _ENCODING = {character: index for index, character in enumerate(ALLOWED_CHARACTERS)}
 SPACE_CODE = _ENCODING[" "]                                    # feature_engineering.py:203

@@ -15,6 +15,51 @@ import numpy as np
 from . import _lib
 
 
+def validate_cover(cover, n_nodes):
+    """set_cover's checks (no library needed) -> float64[n_nodes]: one finite value above 0 per node."""
+    try:
+        cover = np.asarray(cover, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("cover must be an array of numbers") from None
+    if cover.shape != (n_nodes,):
+        raise ValueError(f"cover has shape {cover.shape}, the model has {n_nodes} nodes")
+    if not np.isfinite(cover).all():
+        raise ValueError(f"cover[{int(np.flatnonzero(~np.isfinite(cover))[0])}] is not finite")
+    if (cover <= 0).any():
+        at = int(np.flatnonzero(cover <= 0)[0])
+        raise ValueError(f"cover[{at}] = {cover[at]} is not above 0")
+    return np.ascontiguousarray(cover)
+
+
+def cover_from_counts(counts, arrays, prior=0.0):
+    """fit_cover's host step: float64[n_nodes] from the rows counted per node.  `prior` is a pseudo-count per leaf,
+    added to the leaf and to every ancestor of it, so that a parent stays the sum of its two children.  Without a prior
+    a node no row reached is refused by name: the contributions would divide by its cover."""
+    prior = float(prior)
+    if not np.isfinite(prior) or prior < 0:
+        raise ValueError(f"prior must be a finite non-negative number, not {prior!r}")
+    cover = np.asarray(counts).astype(np.float64)
+    feature, offsets = arrays["feature"], arrays["tree_offsets"]
+    if cover.shape != feature.shape:
+        raise ValueError(f"{cover.shape[0]} counts for {feature.shape[0]} nodes")
+    if prior > 0:
+        leaves = np.zeros(feature.shape[0], dtype=np.float64)       # leaves below each node
+        for t in range(offsets.shape[0] - 1):
+            begin, end = int(offsets[t]), int(offsets[t + 1])
+            for i in range(end - 1, begin - 1, -1):                 # children come after their parent
+                if feature[i] < 0:
+                    leaves[i] = 1.0
+                else:
+                    leaves[i] = leaves[begin + arrays["yes"][i]] + leaves[begin + arrays["no"][i]]
+        cover = cover + prior * leaves
+    elif (cover <= 0).any():
+        at = int(np.flatnonzero(cover <= 0)[0])
+        tree = int(np.searchsorted(offsets, at, side="right") - 1)
+        raise ValueError(f"no row reached node {at - int(offsets[tree])} of tree {tree} (node {at} of the model): "
+                         "count more rows or give a prior > 0")
+    return cover
+
+
 class ForestModel:
     def __init__(self, feature, threshold, yes, no, missing, tree_offsets, n_features, base_margin=0.0, device=0):
         self.arrays = dict(feature=np.ascontiguousarray(feature, dtype=np.int32),
@@ -26,6 +71,7 @@ class ForestModel:
         self.n_features = int(n_features)
         self.n_trees = self.arrays["tree_offsets"].shape[0] - 1
         self.device = device
+        self.cover = None
         self.handle = ctypes.c_void_p()
         a = self.arrays
         _lib.check(_lib.lib().ds_forest_create(_lib.pointer(a["feature"]), _lib.pointer(a["threshold"]), _lib.pointer(a["yes"]), _lib.pointer(a["no"]),
@@ -122,17 +168,118 @@ class ForestModel:
     def save(self, path):
         """The flat arrays in one .npz (the reference pickles its booster, train.py:134-135)."""
         a = self.arrays
+        extra = {} if self.cover is None else {"cover": self.cover}     # a model without cover: the file of before
         with open(path, "wb") as handle:
             np.savez(handle, feature=a["feature"], threshold=a["threshold"], yes=a["yes"], no=a["no"],
                      missing=a["missing"], tree_offsets=a["tree_offsets"],
-                     base_margin=np.float64(a["base_margin"]), n_features=np.int64(self.n_features))
+                     base_margin=np.float64(a["base_margin"]), n_features=np.int64(self.n_features), **extra)
 
     @classmethod
     def load(cls, path, device=0):
         with np.load(path, allow_pickle=False) as saved:
             a = {key: saved[key] for key in saved.files}
-        return cls(a["feature"], a["threshold"], a["yes"], a["no"], a["missing"], a["tree_offsets"],
-                   int(a["n_features"]), float(a["base_margin"]), device)
+        model = cls(a["feature"], a["threshold"], a["yes"], a["no"], a["missing"], a["tree_offsets"],
+                    int(a["n_features"]), float(a["base_margin"]), device)
+        if "cover" in a:
+            model.set_cover(a["cover"])
+        return model
+
+    @staticmethod
+    def xgboost_cover(model_json, ntree_limit=None):
+        """float64[n_nodes]: the `sum_hessian` of every node of a `Booster.save_model('model.json')`, in the node order
+        of parse_xgboost_model_json, for set_cover (what xgboost's own pred_contribs weighs with)."""
+        if isinstance(model_json, (str, bytes)):
+            model_json = json.loads(model_json)
+        trees = model_json["learner"]["gradient_booster"]["model"]["trees"]
+        if ntree_limit:
+            trees = trees[:ntree_limit]
+        parts = [np.asarray(tree["sum_hessian"], dtype=np.float64) for tree in trees]
+        return np.concatenate(parts) if parts else np.zeros(0, np.float64)
+
+    @property
+    def n_nodes(self):
+        return int(self.arrays["feature"].shape[0])
+
+    def set_cover(self, cover):
+        """Install the node cover (float64[n_nodes], every entry finite and above 0; None removes it): the weight of
+        the background rows that reach each node, which predict_contributions weighs the branches with."""
+        if cover is None:
+            _lib.check(_lib.lib().ds_forest_cover_clear(self.handle), "ds_forest_cover_clear")
+            self.cover = None
+            return
+        cover = validate_cover(cover, self.n_nodes)
+        _lib.check(_lib.lib().ds_forest_cover_set(self.handle, _lib.pointer(cover)), "ds_forest_cover_set")
+        self.cover = cover
+
+    def fit_cover(self, rows, prior=0.0):
+        """The cover counted from a host float32[n, n_features] matrix (see fit_cover_device)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.n_features:
+            raise ValueError(f"rows must be a [n, {self.n_features}] matrix, not shape {rows.shape}")
+        cover_from_counts(np.ones(self.n_nodes), self.arrays, prior)        # prior's own check, before any device work
+        d_rows = _lib.DeviceArray.from_host(rows if rows.shape[0] else np.zeros((1, self.n_features), np.float32),
+                                            self.device)
+        try:
+            return self.fit_cover_device(d_rows, rows.shape[0], prior)
+        finally:
+            d_rows.free()
+
+    def fit_cover_device(self, d_rows, n, prior=0.0):
+        """Count the first n rows of a float32[n, n_features] matrix in HBM through every tree on the device
+        (ds_forest_cover_device: exact integer counts per node) and install the result as the cover.  prior: a
+        pseudo-count per leaf, added on the host to the leaf and all of its ancestors.  Without one, a node no row
+        reached is a ValueError that names it (the model then keeps the cover it had).  Returns the cover."""
+        cover_from_counts(np.ones(self.n_nodes), self.arrays, prior)
+        counts = self.count_cover_device(d_rows, n)
+        previous = self.cover
+        try:
+            cover = cover_from_counts(counts, self.arrays, prior)
+        except ValueError:
+            self.set_cover(previous)
+            raise
+        self.set_cover(cover)
+        return cover
+
+    def count_cover_device(self, d_rows, n, accumulate=False, stream=None):
+        """float64[n_nodes]: the rows of the matrix in HBM that reach each node, counted on the device into the
+        forest's counters (from zero, or on top of the last count when `accumulate`).  The counters stay the forest's
+        cover until set_cover replaces them."""
+        library = _lib.lib()
+        if not accumulate:
+            _lib.check(library.ds_forest_cover_clear(self.handle), "ds_forest_cover_clear")
+        _lib.check(library.ds_forest_cover_device(self.handle, _lib.pointer(d_rows), int(n), _lib.pointer(stream)),
+                   "ds_forest_cover_device")
+        self.cover = None
+        return self.read_cover()
+
+    def read_cover(self):
+        """float64[n_nodes] as the library holds it (ds_forest_cover_read): the installed cover, or the counters."""
+        out = np.empty(self.n_nodes, dtype=np.float64)
+        _lib.check(_lib.lib().ds_forest_cover_read(self.handle, _lib.pointer(out)), "ds_forest_cover_read")
+        return out
+
+    def option(self, name, value):
+        """ds_forest_option, for tests: option("max_blocks", v) caps the grids of the cover and contributions kernels."""
+        _lib.check(_lib.lib().ds_forest_option(self.handle, name.encode(), int(value)), "ds_forest_option")
+
+    def predict_contributions(self, rows, approximate=False):
+        """float64[n, n_features + 1] for a host float32[n, n_features] matrix: per row the contribution of every
+        feature to the margin and, last, the bias (xgboost's predict(pred_contribs=True): path-dependent TreeSHAP;
+        approximate=True: approx_contribs, Saabas).  Needs a cover (set_cover / fit_cover)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        assert rows.ndim == 2 and rows.shape[1] == self.n_features
+        out = np.empty((rows.shape[0], self.n_features + 1), dtype=np.float64)
+        _lib.check(_lib.lib().ds_forest_contributions(self.handle, _lib.pointer(rows), rows.shape[0],
+                                                      _lib.pointer(out), int(bool(approximate))),
+                   "ds_forest_contributions")
+        return out
+
+    def predict_contributions_device(self, d_rows, n, d_out, approximate=False, stream=None):
+        """predict_contributions for n rows in HBM into d_out (float64[n, n_features + 1] in HBM), enqueued on
+        `stream`."""
+        _lib.check(_lib.lib().ds_forest_contributions_device(self.handle, _lib.pointer(d_rows), int(n),
+                                                             _lib.pointer(d_out), int(bool(approximate)),
+                                                             _lib.pointer(stream)), "ds_forest_contributions_device")
 
     def feature_importance(self):
         """float64[n_features]: the number of splits on each feature over the sum of them (train.py

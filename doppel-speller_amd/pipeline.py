@@ -22,6 +22,9 @@ BYTES_PER_PAIR = FEATURES_COUNT * 4 + 4 + 4 + 1 + 8
 BYTES_PER_RANK = 4 + 4 + 1 + 1          # one slot of the rank output: row, probability, ratio, stage
 BYTES_PER_PARTS = 3                     # the close ratio taken apart, per pair: d, r, s
 EXHAUSTIVE_MAX_N = 64                   # slots per query of the exhaustive stage at most (ds_exhaustive_rank_device)
+# what the explain stage holds per query: best pair (8), its row, probability, count and margin (4 each), the gathered
+# features (66 float32) and the contributions (67 float64)
+BYTES_PER_EXPLAIN = 8 + 4 * 4 + FEATURES_COUNT * 4 + (FEATURES_COUNT + 1) * 8
 MAX_GRAMS = 253                         # tri-grams of a 255-character title: columns of one query row at most
 
 
@@ -60,6 +63,7 @@ class CandidatePipeline:
         self._exhaustive, self._exhaustive_n = None, 0
         self._parts = None
         self._reasons = None
+        self._explain = None
 
     def _allocate_stages(self):
         """The outputs of the stages after top-k (by `over`, or by the first of their enqueues)."""
@@ -291,6 +295,38 @@ class CandidatePipeline:
         if self._reasons is None:
             raise ValueError("enqueue_duplicate_links(reasons=True) comes first")
         return self._reasons.to_host(self.n_queries)
+
+    def enqueue_explain(self, model, approximate=False, stream=None):
+        """Why the model scored each query's best candidate as it did, over this pipeline's own buffers: the best pair
+        per query by the predictions of `enqueue_predict` on all pairs (ds_best_pairs_device: the highest probability,
+        the first in top-k order on a tie), its feature row gathered from those of `enqueue_features`
+        (ds_gather_rows_device), the margin of that row and its contributions (model.predict_contributions_device).
+        The outputs are allocated by the first call, for `capacity` queries.  The gather synchronises `stream`."""
+        self._allocate_stages()
+        if self._explain is None:
+            n, device, width = max(1, self.capacity), self.device, FEATURES_COUNT
+            self._explain = dict(pair=_lib.DeviceArray((n,), np.int64, device), row=_lib.DeviceArray((n,), np.int32, device),
+                                 probability=_lib.DeviceArray((n,), np.float32, device),
+                                 count=_lib.DeviceArray((n,), np.int32, device),
+                                 margin=_lib.DeviceArray((n,), np.float32, device),
+                                 features=_lib.DeviceArray((n, width), np.float32, device),
+                                 contributions=_lib.DeviceArray((n, width + 1), np.float64, device))
+        e, library, n = self._explain, _lib.lib(), self.n_queries
+        _lib.check(library.ds_best_pairs_device(self.rows_ptr, self._predictions.ptr, n, self.k, e["pair"].ptr,
+                                                e["row"].ptr, e["probability"].ptr, e["count"].ptr,
+                                                _lib.pointer(stream)), "ds_best_pairs_device")
+        _lib.check(library.ds_gather_rows_device(self.d_features.ptr, FEATURES_COUNT, e["pair"].ptr, n, n * self.k,
+                                                 e["features"].ptr, _lib.pointer(stream)), "ds_gather_rows_device")
+        model.predict_device(e["features"], n, e["margin"], None, stream)
+        model.predict_contributions_device(e["features"], n, e["contributions"], approximate, stream)
+
+    def explained(self):
+        """Of the last `enqueue_explain`, per query: (row int32[Q], probability float32[Q], count int32[Q] of the
+        candidates that hold that probability, margin float32[Q], features float32[Q, 66], contributions
+        float64[Q, 67], the bias last)."""
+        e, n = self._explain, self.n_queries
+        return tuple(e[name].to_host(n) for name in ("row", "probability", "count", "margin", "features",
+                                                     "contributions"))
 
     def matches(self, n_remaining):
         """(query rows, matched truth row or -1) of the last `enqueue_select_matches`."""

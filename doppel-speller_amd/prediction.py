@@ -28,7 +28,7 @@ from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
                                   truth_word_counts)
 from .match_maker import NativeProblem, TruthIndex
-from .pipeline import (BYTES_PER_PAIR, BYTES_PER_PARTS, BYTES_PER_RANK, EXHAUSTIVE_MAX_N, MAX_GRAMS,
+from .pipeline import (BYTES_PER_EXPLAIN, BYTES_PER_PAIR, BYTES_PER_PARTS, BYTES_PER_RANK, EXHAUSTIVE_MAX_N, MAX_GRAMS,
                        PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline)
 
 TRAIN_NOT_FOUND_VALUE = -1               # settings.py:80
@@ -42,6 +42,7 @@ SWEEP_COLUMNS = ("levenshtein_threshold", "probability_threshold", "correctly_ma
 ACCURACY_KEYS = SWEEP_COLUMNS[2:]
 DUPLICATE_COLUMNS = ("group_id", "group_size", "title_id", "row")
 LINK_COLUMNS = ("row", "match_row", "title_id", "match_title_id", "levenshtein_ratio", "probability", "stage")
+EXPLAIN_COLUMNS = ("test_index", "match_row", "title_id", "probability", "margin", "bias", "stage", "answer_row")
 REASON_CLOSE, REASON_MODEL = 1, 2        # bits of a slot's reason (ds_duplicate_links_device)
 SWEEP_MAX_LEVENSHTEIN, SWEEP_MAX_PROBABILITY = 101, 256      # thresholds per axis at most (ds_threshold_sweep_device)
 # what ranked_matches(keep_candidates=True) keeps of a call, per query: the top-n rows, their fuzzy ratios and model
@@ -291,6 +292,31 @@ def links_frame(chunks, truth_title_ids, n_truth):
     columns = {name: np.concatenate(held) if held else np.zeros(0, empty[name]) for name, held in parts.items()}
     columns["title_id"], columns["match_title_id"] = ids[columns["row"]], ids[columns["match_row"]]
     return pd.DataFrame(columns, columns=list(LINK_COLUMNS))
+
+
+def top_contributions(contributions, n=5):
+    """(indices int64[Q, n], values float64[Q, n]): per row of `contributions` [Q, F] its n entries of the largest
+    magnitude, the largest first, the lower index first on a tie.  n is cut to F."""
+    contributions = np.asarray(contributions, dtype=np.float64)
+    if contributions.ndim != 2:
+        raise ValueError(f"contributions must be a [Q, F] matrix, not shape {contributions.shape}")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"n must be a positive integer, not {n!r}")
+    order = np.argsort(-np.abs(contributions), axis=1, kind="stable")[:, :min(int(n), contributions.shape[1])]
+    return order.astype(np.int64), np.take_along_axis(contributions, order, axis=1)
+
+
+def explain_frame(test_index, match_row, probability, margin, bias, stage, answer_row, truth_title_ids):
+    """explain's answer, one line per title in the order of the call."""
+    import pandas as pd
+    match_row = np.asarray(match_row, dtype=np.int64)
+    ids = np.asarray(truth_title_ids, dtype=np.int64)
+    return pd.DataFrame({"test_index": np.asarray(test_index, dtype=np.int64), "match_row": match_row,
+                         "title_id": ids[match_row] if match_row.shape[0] else np.zeros(0, np.int64),
+                         "probability": np.asarray(probability, dtype=np.float32),
+                         "margin": np.asarray(margin, dtype=np.float32), "bias": np.asarray(bias, dtype=np.float64),
+                         "stage": np.asarray(stage, dtype=np.int8),
+                         "answer_row": np.asarray(answer_row, dtype=np.int64)}, columns=list(EXPLAIN_COLUMNS))
 
 
 def combine_stages(exact_row, close_row, model_row):
@@ -552,6 +578,8 @@ class Prediction:
         self.candidates = None
         self.link_counts = None
         self.links = None
+        self.contributions = None
+        self.explained_features = None
         self.timings = {}
 
         self.truth_titles = self._transform(truth_titles)
@@ -567,11 +595,13 @@ class Prediction:
     def _check_characters(chars, offsets, what):
         check_characters(chars, offsets, what)
 
-    def _default_chunk(self, device_rows=False, rank_slots=0, parts=False):
+    def _default_chunk(self, device_rows=False, rank_slots=0, parts=False, explain=False):
         # device_rows: the pipeline's own query CSR at capacity (rowptr, 253 columns, q_maxint per query)
         # rank_slots: the slots per query of the rank stage's output; parts: the close ratio taken apart, per pair
+        # explain: the best pair of a query, its gathered features and its contributions
         return default_chunk(self.device, (BYTES_PER_PAIR + BYTES_PER_PARTS * parts) * self.top_n + 64 +
-                             (8 + 4 * MAX_GRAMS + 8) * device_rows + BYTES_PER_RANK * rank_slots)
+                             (8 + 4 * MAX_GRAMS + 8) * device_rows + BYTES_PER_RANK * rank_slots +
+                             BYTES_PER_EXPLAIN * explain)
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
@@ -672,6 +702,70 @@ class Prediction:
                 timings[name] += events[name].elapsed_ms()
         self.timings = timings
         return exhaustive_frame(test_index, rows, probabilities, top_rows, self.truth_title_ids)
+
+    def explain(self, titles, test_index=None, approximate=False):
+        """For every title the model's best candidate and why the model scored it so: a DataFrame [test_index,
+        match_row, title_id, probability (float32), margin (float32), bias (float64), stage, answer_row], one line per
+        title in the order of `titles`.
+
+        The best candidate is the pair of the title's Jaccard top_n with the highest probability, the first in top-n
+        order on a tie (predict.py:239-242); it is explained whether or not an earlier stage matched the title and
+        whether or not it clears the probability threshold.  stage and answer_row are what generate_test_predictions
+        answers for the title (answer_row -1: none), so a reader sees whether the explained pair is the answer.
+        After a call `contributions` holds float64[Q, 66]: the share of each feature in the pair's margin (margin =
+        bias + the sum of a line, up to the float32 rounding of the margin; FEATURE_NAMES names the columns,
+        top_contributions picks the largest), and `explained_features` float32[Q, 66] the feature values themselves,
+        both in the order of `titles`.  approximate: Saabas' method in place of TreeSHAP
+        (ForestModel.predict_contributions).  Every stage runs on the device (CandidatePipeline.enqueue_explain);
+        per title one pair's numbers come back.  The model needs a cover (ForestModel.fit_cover / set_cover,
+        train_model(cover=True)): ValueError otherwise, before any device work.  `details` and `candidates` are left
+        alone."""
+        if getattr(self.model, "cover", None) is None:
+            raise ValueError("the model has no cover: ForestModel.fit_cover, set_cover or train_model(cover=True) first")
+        titles = list(titles)
+        test_index = validate_queries(titles, test_index)
+        timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model",
+                                 "contributions", "copy_back"), 0.0)
+        count, width = len(titles), self.model.n_features
+        match_row, answer_row = np.full(count, -1, dtype=np.int64), np.full(count, -1, dtype=np.int64)
+        probability, margin = np.full(count, np.nan, dtype=np.float32), np.full(count, np.nan, dtype=np.float32)
+        stage = np.zeros(count, dtype=np.int8)
+        features = np.empty((count, width), dtype=np.float32)
+        contributions = np.empty((count, width + 1), dtype=np.float64)
+        for pipeline, events in self._chunks(titles, timings, explain=True):
+            first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
+
+            def timed(name, enqueue):
+                events[name].start()
+                enqueue()
+                events[name].stop()
+
+            # 1. Jaccard top-k (synchronised, as in _chunk)
+            timed("top_k", pipeline.enqueue_top_k)
+            pipeline.sync()
+            # 2. close matches, 3. the exact stage, 4. features and 5. the forest on ALL pairs, 6. the best pair per
+            # query, its features gathered, its margin and its contributions
+            timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=self.levenshtein_threshold))
+            timed("exact_matches", pipeline.enqueue_exact_matches)
+            timed("features", pipeline.enqueue_features)
+            timed("model", lambda: pipeline.enqueue_predict(self.model))
+            timed("contributions", lambda: pipeline.enqueue_explain(self.model, approximate))
+            # 7. one copy back of one pair per query (synchronises the null stream the stages ran on)
+            copy_started = time.perf_counter()
+            rows, best, held, margins, features[first:last], contributions[first:last] = pipeline.explained()
+            exact, close = pipeline.exact_matches(), pipeline.best_rows()
+            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+            for name in ("top_k", "close_matches", "exact_matches", "features", "model", "contributions"):
+                timings[name] += events[name].elapsed_ms()
+            # the answer of generate_test_predictions: the model matches only with a single best pair above the threshold
+            model_row = np.where((best > np.float32(self.probability_threshold)) & (held == 1), rows, -1)
+            answer_row[first:last], stage[first:last] = combine_stages(exact, np.where(exact >= 0, -1, close), model_row)
+            match_row[first:last], probability[first:last], margin[first:last] = rows, best, margins
+        self.timings = timings
+        self.contributions = np.ascontiguousarray(contributions[:, :width])
+        self.explained_features = features
+        return explain_frame(test_index, match_row, probability, margin, contributions[:, width], stage, answer_row,
+                             self.truth_title_ids)
 
     def threshold_sweep(self, titles, actual_title_ids, levenshtein_thresholds=None, probability_thresholds=None,
                         test_index=None):
@@ -829,7 +923,7 @@ class Prediction:
         return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
                              "probability": probability})
 
-    def _chunks(self, titles, timings, rank_slots=0, parts=False):
+    def _chunks(self, titles, timings, rank_slots=0, parts=False, explain=False):
         """The one loop over the queries: prepares the titles (on the device or on the host), then yields (pipeline,
         events) with each chunk loaded in turn, events holding one Timer per device stage of `timings`.  Fills
         timings' host_prepare and prepare_queries; yields nothing for no titles."""
@@ -856,7 +950,7 @@ class Prediction:
                                                    columns=self._columns)
             enc, lengths = encode_collection(chars, offsets, _CODE_OF)
             query_table = TitleTable(enc, lengths, None, self.device)
-        chunk = min(n, self.chunk_queries or self._default_chunk(device_path, rank_slots, parts))
+        chunk = min(n, self.chunk_queries or self._default_chunk(device_path, rank_slots, parts, explain))
         pipeline = CandidatePipeline.over(self.index, self.truth_table, query_table, self.top_n, chunk, self.device)
         timings["host_prepare"] = (time.perf_counter() - started) * 1000.0 - timings.get("prepare_queries", 0.0)
         events = {name: _lib.Timer(self.device) for name in timings

@@ -420,13 +420,17 @@ class TrainModelResult:
 
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
-                transform=True, evaluation_fractions=None, **fit_parameters):
+                transform=True, evaluation_fractions=None, cover=False, **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
     fit_parameters: those of ForestTrainer.fit (num_boost_round, early_stopping_rounds, max_depth, eta, ...).
     Everything is validated before any device work.  Evaluation fractions of 0 for all three kinds train without an
-    evaluation set: every round is kept and error_matrix is None."""
+    evaluation set: every round is kept and error_matrix is None.
+    cover: also count the training matrix through the finished trees while it is still in HBM
+    (ForestModel.fit_cover_device), so that the returned model can explain its predictions
+    (predict_contributions, Prediction.explain); `timings` then has a "cover" entry.  The trees are the same either
+    way."""
     from .training_set import FeatureEngineering
     started = time.perf_counter()
     unknown = set(fit_parameters) - set(inspect.signature(validate_parameters).parameters)
@@ -455,6 +459,15 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
                                      PREDICTION_PROBABILITY_THRESHOLD)
         d_probabilities.free()
     timings["evaluate"] = (time.perf_counter() - mark) * 1000.0
+    if cover:
+        mark = time.perf_counter()
+        try:
+            model.fit_cover_device(sets.train, sets.n_train)
+        except ValueError:          # a node no training row reached: free what the call holds before it leaves
+            trainer.close()
+            sets.free()
+            raise
+        timings["cover"] = (time.perf_counter() - mark) * 1000.0
     best_iteration, history = trainer.best_iteration, list(trainer.history)
     trainer.close()
     sets.free()

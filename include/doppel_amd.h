@@ -400,6 +400,54 @@ int ds_forest_predict(ds_forest *forest, const float *rows, int64_t n, float *ma
 int ds_forest_predict_device(ds_forest *forest, const float *d_rows, int64_t n, float *d_margins,
                              float *d_probabilities, void *stream);
 
+/* ---- contributions: why the model gave a row its margin ("Contributions") -------------------------
+ * Node cover = the weight of the background rows that reach a node, float64[n_nodes] in the forest's node order.  A
+ * forest holds none (as created), a count made on the device, or values installed by the caller.
+ *
+ * ds_forest_cover_device: walks n dense float32[n, n_features] rows in HBM through every tree by the rule of
+ * ds_forest_predict_device and adds 1 to a 64-bit integer counter of every node a row visits: exact, whatever the
+ * schedule.  Successive calls accumulate; the first call after ds_forest_create, ds_forest_cover_set or
+ * ds_forest_cover_clear starts from zero (and drops installed values).  Enqueued on `stream`.  n == 0 launches nothing.
+ * ds_forest_cover_set: installs `cover` (host, n_nodes values; each finite and > 0, else DS_E_ARG) in place of any count.
+ * ds_forest_cover_read: the installed values, or the counters as float64 (synchronises the device); DS_E_ARG with the
+ * text "no cover" when the forest has none.  ds_forest_cover_clear: back to none.
+ * Cover and contributions need every tree to be a proper binary tree: yes != no, missing one of the two, one parent per
+ * node (DS_E_ARG otherwise; ds_forest_create itself accepts more).
+ * ds_forest_option(forest, "max_blocks", v), v in [0, 2^20], is for tests: the cap of the grids of the cover and the
+ * contributions kernels, which stride beyond it (0 = the defaults); no result depends on it.
+ *
+ * ds_forest_contributions_device: d_out = float64[n, n_features + 1] in HBM.  Column f of a row is the contribution of
+ * feature f to the row's margin, summed over the trees in tree order; the last column is the bias: base_margin plus,
+ * per tree, the cover-weighted mean of its leaves (mean(node) = sum over the two children of cover[child] / cover[node]
+ * * mean(child)).  A row's columns sum to its margin up to rounding.
+ *   approximate = 0  path-dependent TreeSHAP (Lundberg, Erion and Lee 2018, Algorithm 2; xgboost's pred_contribs): the
+ *                    one fraction of a split follows the prediction rule (NaN -> missing, value < threshold -> yes,
+ *                    else no), the zero fraction of a child is cover[child] / cover[parent].
+ *   approximate = 1  Saabas (xgboost's approx_contribs): along the row's own path every split adds mean(child) -
+ *                    mean(node) to its feature.
+ * float64 throughout, no floating-point atomics: the same bits run after run and for any max_blocks.  A feature no tree
+ * splits on gets exactly 0.0; a single-leaf tree adds its leaf to the bias only.  DS_E_ARG: no cover ("no cover"), a
+ * node on a path whose cover is not positive (a count no row reached), a tree more than 16 splits deep (the message
+ * names the tree; the limit applies here, not at ds_forest_create).  n == 0 is DS_OK.  The path tables are derived
+ * from the cover by the first call after it changed (host work and uploads; the counters are read back behind a
+ * synchronisation); after that a call only enqueues one kernel on `stream`.
+ * ds_forest_contributions: the same for host arrays. */
+int ds_forest_cover_device(ds_forest *forest, const float *d_rows, int64_t n, void *stream);
+int ds_forest_cover_set(ds_forest *forest, const double *cover);
+int ds_forest_cover_read(ds_forest *forest, double *cover);
+int ds_forest_cover_clear(ds_forest *forest);
+int ds_forest_option(ds_forest *forest, const char *name, int64_t value);
+int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64_t n, double *d_out, int approximate,
+                                   void *stream);
+int ds_forest_contributions(ds_forest *forest, const float *rows, int64_t n, double *out, int approximate);
+/* Per query of k consecutive candidates the one with the highest probability, the first on a tie (predict.py:239-242; a
+ * NaN never replaces an earlier candidate): d_best_pair[q] = q * k + its slot (an index for ds_gather_rows_device),
+ * d_best_row[q] = d_rows[that pair], d_best_probability[q], d_best_count[q] = the candidates that hold that
+ * probability.  Asynchronous on `stream`; n_queries == 0 launches nothing. */
+int ds_best_pairs_device(const int32_t *d_rows, const float *d_probabilities, int64_t n_queries, int32_t k,
+                         int64_t *d_best_pair, int32_t *d_best_row, float *d_best_probability, int32_t *d_best_count,
+                         void *stream);
+
 /* ---- training of the match model: xgb.train(obj=weighted_log_loss, feval=custom_error) (doppelspeller/train.py) ----
  * Histogram gradient boosting, depth-wise, one tree per ds_trainer_step (DESIGN.md "Training").  features is the
  * float32[n][n_features] training matrix (NaN = missing), copied and binned on the device at create time: cuts[
