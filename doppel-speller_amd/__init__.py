@@ -28,6 +28,11 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
     train_model(truth_titles, truth_title_ids, train_titles, train_title_ids)   -> model, feature importances, the
         evaluation error matrix (train.train_model: the two steps above in one call, the feature matrix kept in HBM)
+    cross_validate(features, target, parameter_grid(max_depth=[4, 5], eta=[0.1, 0.3]), n_folds=5)   -> the out-of-fold
+        custom error of every parameter set and round, the best set and its model refit on all rows; the K folds x P
+        sets are boosters of one batch on the device (ForestTrainerBatch), sharing bins, launches and the host sync
+    tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters)   -> the same
+        from raw titles, folds by train title, the feature matrix kept in HBM (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -47,4 +52,6 @@ from .prediction import (DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS, LINK_COLUMNS, RA
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, train_model)
+from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
+                     select_parameters, tune_model_parameters)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -8,9 +8,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
-            "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip",
-            "ds_train.hip", "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip",
-            "ds_sweep.hip", "ds_duplicates.hip", "ds_contributions.hip")
+            "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
+            "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
+            "ds_duplicates.hip", "ds_contributions.hip")
 _lib = None
 
 
@@ -187,6 +187,12 @@ def _declare(handle):
                                      c.c_double, c.c_int, c.POINTER(p)],
         "ds_trainer_set_eval_device": [p, p, p, c.c_int64],
         "ds_gather_rows_device": [p, c.c_int32, p, c.c_int64, c.c_int64, p, p],
+        "ds_trainer_batch_create": [p, c.c_int64, c.c_int32, p, p, p, p, c.c_int32, c.c_int32, p, p, c.c_int, c.POINTER(p)],
+        "ds_trainer_batch_create_device": [p, c.c_int64, c.c_int32, p, p, p, p, c.c_int32, c.c_int32, p, p, c.c_int,
+                                           c.POINTER(p)],
+        "ds_trainer_batch_step": [p, p, p, p, p],
+        "ds_trainer_batch_read": [p, c.c_int32, p, p, p, p],
+        "ds_trainer_batch_option": [c.c_char_p, c.c_int64],
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
@@ -207,19 +213,20 @@ def _declare(handle):
         "ds_timer_stop": [p, p],
         "ds_timer_elapsed_ms": [p, c.POINTER(c.c_float)],
     }
-    for name, argtypes in signatures.items():
-        if not hasattr(handle, name) and os.environ.get("DS_ALLOW_STALE_LIBRARY") == "1":
-            continue  # an older library named by DS_LIBRARY for an A/B measurement: entry points added since are simply absent
-        function = getattr(handle, name)
-        function.argtypes = argtypes
-        function.restype = c.c_int
-    handle.ds_remaining_pairs_counts_size.argtypes = [c.c_int64]
-    handle.ds_remaining_pairs_counts_size.restype = c.c_int64
-    for name in ("ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy",
-                 "ds_trainer_destroy", "ds_query_space_destroy"):
-        function = getattr(handle, name)
-        function.argtypes = [p]
-        function.restype = None
+    # an older library named by DS_LIBRARY for an A/B measurement: entry points added since are simply absent
+    stale_allowed = os.environ.get("DS_ALLOW_STALE_LIBRARY") == "1"
+    returns_int64 = {"ds_remaining_pairs_counts_size": [c.c_int64],
+                     "ds_trainer_batch_bytes": [c.c_int64, c.c_int32, c.c_int32, c.c_int32]}
+    returns_nothing = {name: [p] for name in (
+        "ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy",
+        "ds_trainer_destroy", "ds_query_space_destroy", "ds_trainer_batch_destroy")}
+    for group, restype in ((signatures, c.c_int), (returns_int64, c.c_int64), (returns_nothing, None)):
+        for name, argtypes in group.items():
+            if stale_allowed and not hasattr(handle, name):
+                continue
+            function = getattr(handle, name)
+            function.argtypes = argtypes
+            function.restype = restype
     return handle
 
 
@@ -242,7 +249,9 @@ EXPORTED_SYMBOLS = (
     "ds_close_parts_device", "ds_threshold_sweep_device", "ds_sweep_option", "ds_duplicate_begin_device",
     "ds_duplicate_links_device", "ds_duplicate_finish_device", "ds_duplicates_option", "ds_forest_cover_device",
     "ds_forest_cover_set", "ds_forest_cover_read", "ds_forest_cover_clear", "ds_forest_option",
-    "ds_forest_contributions_device", "ds_forest_contributions", "ds_best_pairs_device")
+    "ds_forest_contributions_device", "ds_forest_contributions", "ds_best_pairs_device", "ds_trainer_batch_create",
+    "ds_trainer_batch_create_device", "ds_trainer_batch_destroy", "ds_trainer_batch_step", "ds_trainer_batch_read",
+    "ds_trainer_batch_bytes", "ds_trainer_batch_option")
 
 
 def lib():

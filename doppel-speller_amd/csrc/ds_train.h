@@ -1,0 +1,314 @@
+// The training rule's device code, shared by the single trainer (ds_train.hip) and the batched trainer
+// (ds_train_batch.hip): constants, node and parameter records and the body of every kernel of a round.  A body reads
+// blockIdx.x / blockIdx.y as its kernel documents and takes pointers to ONE model's state; the batched kernels add the
+// model as a further grid dimension and offset the pointers.  Both trainers so grow the same trees from the same code.
+#pragma once
+
+#include "ds_common.h"
+
+namespace ds {
+
+constexpr int kTrainFeaturesMax = 96;     // = kForestFeaturesMax: a trained model must load into ds_forest
+constexpr int kTrainMaxDepth = 8;
+constexpr int kTrainCutsMax = 254;        // max_bin 256: bins 0..254, 255 = missing
+constexpr int kMissingBin = 255;
+constexpr int kHistSlots = 16;            // (feature, node) histograms per workgroup: 16 x 256 x 16 B = 64 KiB of LDS
+constexpr int kHistThreads = 512;
+constexpr int kRowThreads = 256;
+constexpr int kBinTileRows = 64;
+constexpr double kQuantum = 1073741824.0; // 2^30
+constexpr double kRtEps = 1e-6;           // xgboost's kRtEps: a split must gain more than this
+
+enum NodeState : int32_t { kAbsent = 0, kPending = 1, kSplit = 2, kLeaf = 3 };
+
+struct Node {
+    int32_t state, feature, bin, default_left;
+    float leaf;
+    int32_t pad;
+};
+
+struct TrainParams {
+    int32_t max_depth;
+    double eta, min_child_weight, reg_lambda, beta;
+};
+
+// Host side, ds_train.hip: bins of a float32[n][nf] matrix into `out` with the cuts in HBM.  A host matrix is uploaded
+// through a temporary buffer, a matrix in HBM (in_hbm, complete before the call) is read where it lies and not kept.
+// Synchronises `stream` before it returns.
+int train_bin_matrix(hipStream_t stream, int compute_units, const float *rows, bool in_hbm, int64_t n, int32_t nf,
+                     const float *d_cuts, const int32_t *d_cut_offsets, DeviceBuffer<uint8_t> &out);
+// DS_E_HIP with both numbers in the message when `bytes` (+ 64 MiB of head room) are not free on the current device
+int train_check_free(int64_t bytes, const char *what);
+// the checks of cuts / cut_offsets that every create entry makes
+int train_check_cuts(const char *who, int32_t n_features, const float *cuts, const int32_t *cut_offsets);
+
+// ---- gradients of weighted_log_loss at the current margins ---------------------------------------------------------
+// kFolds: a row with fold[r] == held_out does not train: its (g, h) is (0, 0); everything else is written as for any row
+template <bool kFolds>
+__device__ inline void train_gradient_rows(const float *leafsum, const float *labels, int64_t n, float base_margin,
+                                           double beta, float *probabilities, long long *gh, int32_t *node_of,
+                                           const uint8_t *fold, int32_t held_out)
+{
+    for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
+         r += static_cast<int64_t>(gridDim.x) * kRowThreads) {
+        const float margin = base_margin + leafsum[r];
+        const float p = 1.0f / (1.0f + expf(-margin));   // ds_forest.hip's rule
+        const double y = labels[r], pd = p;
+        const double w = beta + y - beta * y;
+        const double g = pd * w - y;
+        const double h = pd * (1.0 - pd) * w;
+        const bool trains = !kFolds || static_cast<int32_t>(fold[r]) != held_out;
+        probabilities[r] = p;
+        gh[2 * r] = trains ? static_cast<long long>(rint(g * kQuantum)) : 0ll;
+        gh[2 * r + 1] = trains ? static_cast<long long>(rint(h * kQuantum)) : 0ll;
+        node_of[r] = 0;
+    }
+}
+
+// Which child of a split parent gets its histogram built (the one with fewer rows, the left one on a tie); the other
+// one is parent - built.
+__device__ inline bool is_built(const int32_t *counts, int32_t node)
+{
+    const bool left = (node & 1) == 1;
+    const int32_t sibling = left ? node + 1 : node - 1;
+    return left ? counts[node] <= counts[sibling] : counts[node] < counts[sibling];
+}
+
+// ---- histograms of one level ---------------------------------------------------------------------------------------
+// Level d >= 1 builds one child per split parent of level d - 1 (slot j <-> the j-th parent of that level); level 0
+// builds the root.  blockIdx.y = (feature group, node group): nodes_per_group x features_per_group <= kHistSlots
+// histograms in LDS, summed with 64-bit LDS adds, flushed with 64-bit global adds (zeros skipped).
+// kFolds: rows with fold[r] == held_out carry (0, 0) and are skipped, and a workgroup none of whose slots has a node
+// to build returns before it reads a row; neither changes a bit of the sums.
+template <bool kFolds>
+__device__ inline void train_histogram_group(const uint8_t *bins, const long long *gh, const int32_t *node_of,
+                                             const int32_t *counts, const Node *nodes, int64_t n, int32_t nf,
+                                             int32_t level, int32_t n_built, int32_t nodes_per_group,
+                                             int32_t features_per_group, int32_t feature_groups,
+                                             unsigned long long *hist, const uint8_t *fold, int32_t held_out)
+{
+    __shared__ unsigned long long s_hist[kHistSlots * 256 * 2];
+    __shared__ int32_t s_node[kHistSlots];   // heap id of the built node of each slot, -1 for none
+    const int feature_group = blockIdx.y % feature_groups, node_group = blockIdx.y / feature_groups;
+    const int f0 = feature_group * features_per_group;
+    const int f_count = min(features_per_group, nf - f0);
+    const int j0 = node_group * nodes_per_group;
+    const int j_count = min(nodes_per_group, n_built - j0);
+    int32_t node_here = -1;
+    if (static_cast<int>(threadIdx.x) < j_count) {
+        if (level == 0) {
+            node_here = 0;
+        } else {
+            const int32_t parent = (1 << (level - 1)) - 1 + j0 + threadIdx.x;
+            if (nodes[parent].state == kSplit)
+                node_here = is_built(counts, 2 * parent + 1) ? 2 * parent + 1 : 2 * parent + 2;
+        }
+        s_node[threadIdx.x] = node_here;
+    }
+    if (kFolds) {
+        if (!__syncthreads_or(node_here >= 0)) return;   // the same answer in every thread
+    }
+    for (int i = threadIdx.x; i < kHistSlots * 512; i += kHistThreads) s_hist[i] = 0ull;
+    __syncthreads();
+    const int32_t level_first = (1 << level) - 1;
+    const int64_t chunk = (n + gridDim.x - 1) / gridDim.x;
+    const int64_t begin = blockIdx.x * chunk, end = min(n, begin + chunk);
+    for (int64_t r = begin + threadIdx.x; r < end; r += kHistThreads) {
+        const int32_t node = node_of[r];
+        if (node < level_first) continue;   // -1: finished
+        if (kFolds && static_cast<int32_t>(fold[r]) == held_out) continue;
+        const int j = level == 0 ? 0 : ((node - 1) >> 1) - ((1 << (level - 1)) - 1) - j0;
+        if (j < 0 || j >= j_count || s_node[j] != node) continue;
+        const long long g = gh[2 * r], h = gh[2 * r + 1];
+        for (int k = 0; k < f_count; ++k) {
+            const int bin = bins[static_cast<int64_t>(f0 + k) * n + r];
+            unsigned long long *slot = s_hist + ((k * nodes_per_group + j) * 256 + bin) * 2;
+            atomicAdd(slot, static_cast<unsigned long long>(g));
+            atomicAdd(slot + 1, static_cast<unsigned long long>(h));
+        }
+    }
+    __syncthreads();
+    const size_t node_stride = static_cast<size_t>(nf) * 512;
+    for (int i = threadIdx.x; i < f_count * j_count * 512; i += kHistThreads) {
+        const int k = i / (j_count * 512), rest = i - k * j_count * 512, j = rest / 512, e = rest - j * 512;
+        const unsigned long long value = s_hist[(k * nodes_per_group + j) * 512 + e];
+        if (value == 0ull || s_node[j] < 0) continue;
+        atomicAdd(hist + s_node[j] * node_stride + static_cast<size_t>(f0 + k) * 512 + e, value);
+    }
+}
+
+__device__ inline double node_gain(double g, double h, double lambda) { return g * g / (h + lambda); }
+
+struct Candidate {            // the best split of one (node, feature)
+    double gain;              // -inf: no valid candidate
+    long long left_g, left_h, total_g, total_h;
+    int32_t bin, missing_left;
+};
+
+// ---- split choice, part 1: one workgroup per (node of the level, feature), one thread per bin ----------------------
+// blockIdx.x = the node's index in its level, blockIdx.y = the feature.
+// A node whose histogram was not built gets parent - built sibling (exact) first.  Prefix sums by an LDS scan; each
+// thread b - 1 tries boundary b with the missing rows right, then left; the workgroup keeps the largest gain, the
+// lower b on a tie.
+__device__ inline void train_split_feature(long long *hist, const int32_t *counts, const Node *nodes,
+                                           const int32_t *cut_offsets, int32_t nf, int32_t level,
+                                           const TrainParams &params, Candidate *candidates)
+{
+    __shared__ long long s_g[256], s_h[256];
+    __shared__ double s_gain[256];
+    __shared__ int32_t s_key[256];   // 2 * b + missing_left of the thread's best, INT32_MAX for none
+    const int32_t node = (1 << level) - 1 + blockIdx.x;
+    if (level > 0 && nodes[(node - 1) >> 1].state != kSplit) return;   // the node does not exist
+    const int f = blockIdx.y, t = threadIdx.x;
+    const size_t node_stride = static_cast<size_t>(nf) * 512, at = static_cast<size_t>(f) * 512 + 2 * t;
+    long long g, h;
+    if (level == 0 || is_built(counts, node)) {
+        g = hist[node * node_stride + at];
+        h = hist[node * node_stride + at + 1];
+    } else {
+        const int32_t parent = (node - 1) >> 1, sibling = (node & 1) ? node + 1 : node - 1;
+        g = hist[parent * node_stride + at] - hist[sibling * node_stride + at];
+        h = hist[parent * node_stride + at + 1] - hist[sibling * node_stride + at + 1];
+        hist[node * node_stride + at] = g;
+        hist[node * node_stride + at + 1] = h;
+    }
+    s_g[t] = g;
+    s_h[t] = h;
+    __syncthreads();
+    for (int offset = 1; offset < 256; offset <<= 1) {   // inclusive scan: s_g[t] = sum of bins 0 .. t
+        const long long add_g = t >= offset ? s_g[t - offset] : 0, add_h = t >= offset ? s_h[t - offset] : 0;
+        __syncthreads();
+        s_g[t] += add_g;
+        s_h[t] += add_h;
+        __syncthreads();
+    }
+    const long long total_g = s_g[255], total_h = s_h[255];
+    const long long missing_g = total_g - s_g[254], missing_h = total_h - s_h[254];
+    const double lambda = params.reg_lambda, mcw = params.min_child_weight;
+    const double G = static_cast<double>(total_g) / kQuantum, H = static_cast<double>(total_h) / kQuantum;
+    const double parent_gain = node_gain(G, H, lambda);
+    const int b = t + 1, n_bins = cut_offsets[f + 1] - cut_offsets[f] + 1;
+    double best = -INFINITY;
+    int32_t key = INT32_MAX;
+    if (b < n_bins) {
+        for (int missing_left = 0; missing_left < 2; ++missing_left) {   // missing right first
+            const long long lg = s_g[t] + (missing_left ? missing_g : 0), lh = s_h[t] + (missing_left ? missing_h : 0);
+            const double GL = static_cast<double>(lg) / kQuantum, HL = static_cast<double>(lh) / kQuantum;
+            const double GR = static_cast<double>(total_g - lg) / kQuantum;
+            const double HR = static_cast<double>(total_h - lh) / kQuantum;
+            if (HL < mcw || HR < mcw) continue;
+            const double gain = node_gain(GL, HL, lambda) + node_gain(GR, HR, lambda) - parent_gain;
+            if (gain > best) {
+                best = gain;
+                key = 2 * b + missing_left;
+            }
+        }
+    }
+    s_gain[t] = best;
+    s_key[t] = key;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {   // larger gain, then the lower key (b, then missing right)
+        if (t < half) {
+            const double other = s_gain[t + half];
+            if (other > s_gain[t] || (other == s_gain[t] && s_key[t + half] < s_key[t])) {
+                s_gain[t] = other;
+                s_key[t] = s_key[t + half];
+            }
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    Candidate out;
+    out.gain = s_key[0] == INT32_MAX ? -INFINITY : s_gain[0];
+    out.bin = s_key[0] == INT32_MAX ? 0 : s_key[0] >> 1;
+    out.missing_left = s_key[0] == INT32_MAX ? 0 : s_key[0] & 1;
+    out.left_g = out.bin > 0 ? s_g[out.bin - 1] + (out.missing_left ? missing_g : 0) : 0;
+    out.left_h = out.bin > 0 ? s_h[out.bin - 1] + (out.missing_left ? missing_h : 0) : 0;
+    out.total_g = total_g;
+    out.total_h = total_h;
+    candidates[static_cast<size_t>(blockIdx.x) * nf + f] = out;
+}
+
+// ---- split choice, part 2: one thread per node of the level over its features' candidates ---------------------------
+__device__ inline void train_split_nodes(const Candidate *candidates, Node *nodes, int32_t nf, int32_t level,
+                                         const TrainParams &params)
+{
+    const int32_t index = blockIdx.x * 64 + threadIdx.x;
+    if (index >= (1 << level)) return;
+    const int32_t node = (1 << level) - 1 + index;
+    if (level > 0 && nodes[(node - 1) >> 1].state != kSplit) return;
+    const Candidate *mine = candidates + static_cast<size_t>(index) * nf;
+    int winner = 0;
+    for (int k = 1; k < nf; ++k)   // strictly greater: a tie keeps the lower feature
+        if (mine[k].gain > mine[winner].gain) winner = k;
+    const double lambda = params.reg_lambda;
+    auto leaf_value = [&](long long qg, long long qh) {
+        const double g = static_cast<double>(qg) / kQuantum, h = static_cast<double>(qh) / kQuantum;
+        return static_cast<float>((-g / (h + lambda)) * params.eta);
+    };
+    const Candidate &best = mine[winner];
+    const long long G = best.total_g, H = best.total_h;
+    Node &out = nodes[node];
+    out.feature = -1;
+    out.bin = 0;
+    out.default_left = 0;
+    out.leaf = 0.f;
+    if (best.gain > kRtEps) {
+        out.state = kSplit;
+        out.feature = winner;
+        out.bin = best.bin;
+        out.default_left = best.missing_left;
+        const bool last = level + 1 == params.max_depth;
+        Node &left = nodes[2 * node + 1], &right = nodes[2 * node + 2];
+        left.state = right.state = last ? kLeaf : kPending;
+        left.feature = right.feature = -1;
+        left.leaf = last ? leaf_value(best.left_g, best.left_h) : 0.f;
+        right.leaf = last ? leaf_value(G - best.left_g, H - best.left_h) : 0.f;
+    } else {
+        out.state = kLeaf;
+        out.leaf = leaf_value(G, H);
+    }
+}
+
+// ---- row partition: rows of split nodes move to a child, rows that reach a leaf add it to their margin -------------
+__device__ inline void train_partition_rows(const uint8_t *bins, const Node *nodes, int64_t n, int32_t level,
+                                            int32_t *node_of, float *leafsum, int32_t *counts)
+{
+    __shared__ int32_t s_counts[2 << kTrainMaxDepth];
+    const int32_t level_first = (1 << level) - 1, next_first = 2 * level_first + 1, next_width = 1 << (level + 1);
+    for (int i = threadIdx.x; i < next_width; i += kRowThreads) s_counts[i] = 0;
+    __syncthreads();
+    for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
+         r += static_cast<int64_t>(gridDim.x) * kRowThreads) {
+        int32_t node = node_of[r];
+        if (node < level_first) continue;
+        Node rec = nodes[node];
+        if (rec.state == kSplit) {
+            const int bin = bins[static_cast<int64_t>(rec.feature) * n + r];
+            const bool left = bin == kMissingBin ? rec.default_left != 0 : bin < rec.bin;
+            node = 2 * node + (left ? 1 : 2);
+            rec = nodes[node];
+        }
+        if (rec.state == kLeaf) {
+            leafsum[r] = leafsum[r] + rec.leaf;
+            node_of[r] = -1;
+        } else {
+            node_of[r] = node;
+            atomicAdd(&s_counts[node - next_first], 1);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < next_width; i += kRowThreads)
+        if (s_counts[i]) atomicAdd(&counts[next_first + i], s_counts[i]);
+}
+
+// train.py:fast_custom_error of one row at its margin: 1 for a missed positive, 5 for a false positive
+__device__ inline unsigned long long train_row_error(float margin, float label)
+{
+    const float p = 1.0f / (1.0f + expf(-margin));
+    const bool positive = static_cast<double>(p) > 0.9;   // settings.py PREDICTION_PROBABILITY_THRESHOLD
+    if (label != 0.f) return positive ? 0 : 1;
+    return positive ? 5 : 0;                               // FALSE_POSITIVE_PENALTY_FACTOR
+}
+
+}  // namespace ds

@@ -1,0 +1,460 @@
+// Batched training for cross-validation and parameter search ("Cross-validation and tuning"):
+// M boosters over ONE binned matrix, each with its own parameters and its own held-out fold, grown by the rule of
+// ds_train.hip (the same device code, ds_train.h) with the model as a further grid dimension.  One round launches each
+// kernel once for all active models and syncs with the host once.
+//
+// Shared by the models of a batch:
+//   bins      uint8[nf][n]   as ds_train.hip's, from the cuts of the whole matrix
+//   labels    float[n]
+//   fold      uint8[n]       0 .. K-1
+//   models    BatchModel[M]  parameters and the held-out fold h (-1: none) of every model
+// Per model m, at m * the array's stride: gh int64[n][2], node_of int32[n], leafsum float[n], probabilities float[n],
+//   hist int64[2^D - 1][nf][256][2], nodes Node[2^(D+1) - 1], counts int32[2^(D+1) - 1], candidates [2^(D-1)][nf] and
+//   error uint64, D = the largest max_depth of the batch.
+// Row r trains in model m iff fold[r] != h_m.  A held-out row carries (g, h) = (0, 0), is skipped by the histogram
+// kernel, is routed through every new tree like any row, and counts in the model's error after the round.
+#include <atomic>
+
+#include "ds_train.h"
+
+namespace ds {
+
+constexpr int kBatchModelsMax = 256;
+constexpr int kBatchFoldsMax = 255;
+constexpr float kBatchBaseMargin = 0.f;   // base_score 0.5, as ds_trainer
+
+struct BatchModel {
+    TrainParams params;
+    int32_t held_out, pad;
+};
+
+struct BatchView {   // what every kernel of a round gets; model m's part of a per-model array starts at m * its stride
+    const uint8_t *bins;
+    const float *labels;
+    const uint8_t *fold;
+    const int32_t *cut_offsets;
+    const BatchModel *models;
+    const int32_t *active;        // the models of this step: blockIdx.z (or the last grid dimension) indexes it
+    long long *gh;                // stride 2n
+    int32_t *node_of;             // stride n
+    float *leafsum, *probabilities;   // stride n
+    long long *hist;              // stride hist_stride
+    Node *nodes;                  // stride slots
+    int32_t *counts;              // stride slots
+    Candidate *candidates;        // stride candidate_stride
+    unsigned long long *errors;   // stride 1
+    int64_t n, hist_stride, candidate_stride;
+    int32_t nf, slots;
+};
+
+// ---- start of a round: zero the active models' histograms (levels below their own max_depth), heaps, counts, errors -
+__global__ __launch_bounds__(kRowThreads) void ds_batch_clear_kernel(BatchView v)
+{
+    const int32_t m = v.active[blockIdx.y];
+    const int64_t at = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x;
+    const int64_t step = static_cast<int64_t>(gridDim.x) * kRowThreads;
+    const int64_t pairs = ((int64_t(1) << v.models[m].params.max_depth) - 1) * v.nf * 256;   // (g, h) of one bin
+    ulonglong2 *hist = reinterpret_cast<ulonglong2 *>(v.hist + m * v.hist_stride);
+    for (int64_t i = at; i < pairs; i += step) hist[i] = make_ulonglong2(0ull, 0ull);
+    uint32_t *nodes = reinterpret_cast<uint32_t *>(v.nodes + static_cast<int64_t>(m) * v.slots);
+    for (int64_t i = at; i < int64_t(v.slots) * (sizeof(Node) / 4); i += step) nodes[i] = 0u;
+    int32_t *counts = v.counts + static_cast<int64_t>(m) * v.slots;
+    for (int64_t i = at; i < v.slots; i += step) counts[i] = 0;
+    if (at == 0) v.errors[m] = 0ull;
+}
+
+__global__ __launch_bounds__(kRowThreads) void ds_batch_gradient_kernel(BatchView v)
+{
+    const int32_t m = v.active[blockIdx.y];
+    const BatchModel &model = v.models[m];
+    train_gradient_rows<true>(v.leafsum + m * v.n, v.labels, v.n, kBatchBaseMargin, model.params.beta,
+                              v.probabilities + m * v.n, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.fold,
+                              model.held_out);
+}
+
+// blockIdx.x = the chunk of rows, blockIdx.y = (feature group, node group) as in ds_train.hip, blockIdx.z = the model
+__global__ __launch_bounds__(kHistThreads) void ds_batch_histogram_kernel(BatchView v, int32_t level, int32_t n_built,
+                                                                           int32_t nodes_per_group,
+                                                                           int32_t features_per_group,
+                                                                           int32_t feature_groups)
+{
+    const int32_t m = v.active[blockIdx.z];
+    const BatchModel &model = v.models[m];
+    if (level >= model.params.max_depth) return;   // the model's tree is finished: nothing pending
+    train_histogram_group<true>(v.bins, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.counts + int64_t(m) * v.slots,
+                                v.nodes + int64_t(m) * v.slots, v.n, v.nf, level, n_built, nodes_per_group,
+                                features_per_group, feature_groups,
+                                reinterpret_cast<unsigned long long *>(v.hist + m * v.hist_stride), v.fold,
+                                model.held_out);
+}
+
+// blockIdx.x = the node's index in its level, blockIdx.y = the feature, blockIdx.z = the model
+__global__ __launch_bounds__(256) void ds_batch_split_feature_kernel(BatchView v, int32_t level)
+{
+    const int32_t m = v.active[blockIdx.z];
+    const BatchModel &model = v.models[m];
+    if (level >= model.params.max_depth) return;
+    train_split_feature(v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots, v.nodes + int64_t(m) * v.slots,
+                        v.cut_offsets, v.nf, level, model.params, v.candidates + m * v.candidate_stride);
+}
+
+// blockIdx.x = 64 nodes of the level, blockIdx.y = the model
+__global__ __launch_bounds__(64) void ds_batch_split_kernel(BatchView v, int32_t level)
+{
+    const int32_t m = v.active[blockIdx.y];
+    const BatchModel &model = v.models[m];
+    if (level >= model.params.max_depth) return;
+    train_split_nodes(v.candidates + m * v.candidate_stride, v.nodes + int64_t(m) * v.slots, v.nf, level, model.params);
+}
+
+__global__ __launch_bounds__(kRowThreads) void ds_batch_partition_kernel(BatchView v, int32_t level)
+{
+    const int32_t m = v.active[blockIdx.y];
+    if (level >= v.models[m].params.max_depth) return;
+    train_partition_rows(v.bins, v.nodes + int64_t(m) * v.slots, v.n, level, v.node_of + m * v.n, v.leafsum + m * v.n,
+                         v.counts + int64_t(m) * v.slots);
+}
+
+// ---- held-out error: ds_train_eval_kernel's rule over the rows of the model's held-out fold, at the margins that the
+// partition kernel has just updated
+__global__ __launch_bounds__(kRowThreads) void ds_batch_error_kernel(BatchView v)
+{
+    __shared__ unsigned long long s_error;
+    const int32_t m = v.active[blockIdx.y];
+    const int32_t held_out = v.models[m].held_out;
+    if (held_out < 0) return;
+    if (threadIdx.x == 0) s_error = 0;
+    __syncthreads();
+    const float *leafsum = v.leafsum + m * v.n;
+    unsigned long long mine = 0;
+    for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < v.n;
+         r += static_cast<int64_t>(gridDim.x) * kRowThreads)
+        if (static_cast<int32_t>(v.fold[r]) == held_out) mine += train_row_error(kBatchBaseMargin + leafsum[r], v.labels[r]);
+    if (mine) atomicAdd(&s_error, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_error) atomicAdd(v.errors + m, s_error);
+}
+
+}  // namespace ds
+
+struct ds_trainer_batch {
+    int device = 0;
+    int64_t n = 0;
+    int32_t nf = 0, n_models = 0, max_depth = 0, slots = 0;
+    std::vector<ds::BatchModel> models;
+    hipStream_t stream = nullptr;
+    ds::DeviceBuffer<uint8_t> bins, fold;
+    ds::DeviceBuffer<float> labels, leafsum, probabilities, cuts;
+    ds::DeviceBuffer<int32_t> cut_offsets, node_of, counts, active;
+    ds::DeviceBuffer<long long> gh, hist;
+    ds::DeviceBuffer<ds::Node> nodes;
+    ds::DeviceBuffer<ds::Candidate> candidates;
+    ds::DeviceBuffer<unsigned long long> errors;
+    ds::DeviceBuffer<ds::BatchModel> d_models;
+    ds::Node *pinned_nodes = nullptr;          // [n_models][slots]
+    unsigned long long *pinned_errors = nullptr;
+    int32_t *pinned_active = nullptr;
+    ds::BatchView view{};
+    int compute_units = 256;
+    ~ds_trainer_batch()
+    {
+        if (pinned_nodes) (void)hipHostFree(pinned_nodes);
+        if (pinned_errors) (void)hipHostFree(pinned_errors);
+        if (pinned_active) (void)hipHostFree(pinned_active);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+std::atomic<int64_t> g_max_blocks{0};   // ds_trainer_batch_option("max_blocks"): 0 = no cap
+
+int64_t heap_nodes(int32_t depth) { return (int64_t(2) << depth) - 1; }
+int64_t hist_entries(int32_t depth, int32_t nf) { return ((int64_t(1) << depth) - 1) * nf * 512; }
+int64_t candidate_entries(int32_t depth, int32_t nf) { return (int64_t(1) << (depth - 1)) * nf; }
+
+int64_t capped(int64_t blocks)
+{
+    const int64_t cap = g_max_blocks.load();
+    return std::max<int64_t>(1, cap > 0 ? std::min(blocks, cap) : blocks);
+}
+
+unsigned row_grid(const ds_trainer_batch *b, int64_t items)
+{
+    return static_cast<unsigned>(capped(std::min<int64_t>((items + ds::kRowThreads - 1) / ds::kRowThreads,
+                                                          int64_t(b->compute_units) * 8)));
+}
+
+bool ranges_ok(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth)
+{
+    return n >= 1 && n <= INT32_MAX && n_features >= 1 && n_features <= ds::kTrainFeaturesMax && n_models >= 1 &&
+           n_models <= ds::kBatchModelsMax && max_depth >= 1 && max_depth <= ds::kTrainMaxDepth;
+}
+
+int create_batch(const char *who, const float *features, bool in_hbm, int64_t n, int32_t n_features, const float *cuts,
+                 const int32_t *cut_offsets, const float *labels, const uint8_t *fold, int32_t n_folds, int32_t n_models,
+                 const double *params, const int32_t *held_out, int device, ds_trainer_batch **out)
+{
+    DS_REQUIRE(out != nullptr, "%s: out is null", who);
+    *out = nullptr;
+    DS_REQUIRE(features != nullptr, "%s: features is null", who);
+    DS_REQUIRE(cuts != nullptr, "%s: cuts is null", who);
+    DS_REQUIRE(cut_offsets != nullptr, "%s: cut_offsets is null", who);
+    DS_REQUIRE(labels != nullptr, "%s: labels is null", who);
+    DS_REQUIRE(fold != nullptr, "%s: fold is null", who);
+    DS_REQUIRE(params != nullptr, "%s: params is null", who);
+    DS_REQUIRE(held_out != nullptr, "%s: held_out is null", who);
+    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
+    DS_REQUIRE(n_features >= 1 && n_features <= ds::kTrainFeaturesMax, "%s: n_features = %d out of range [1, %d]", who,
+               n_features, ds::kTrainFeaturesMax);
+    DS_REQUIRE(n_models >= 1 && n_models <= ds::kBatchModelsMax, "%s: n_models = %d out of range [1, %d]", who, n_models,
+               ds::kBatchModelsMax);
+    DS_REQUIRE(n_folds >= 1 && n_folds <= ds::kBatchFoldsMax, "%s: n_folds = %d out of range [1, %d]", who, n_folds,
+               ds::kBatchFoldsMax);
+    std::vector<ds::BatchModel> models(n_models);
+    int32_t depth = 1;
+    for (int32_t m = 0; m < n_models; ++m) {
+        const double *p = params + 5 * m;
+        DS_REQUIRE(p[0] >= 1 && p[0] <= ds::kTrainMaxDepth && p[0] == static_cast<double>(static_cast<int32_t>(p[0])),
+                   "%s: params of model %d: max_depth = %g is not an integer in [1, %d]", who, m, p[0],
+                   ds::kTrainMaxDepth);
+        DS_REQUIRE(p[1] > 0 && p[1] < 1e30 && p[2] >= 0 && p[2] < 1e30 && p[3] >= 0 && p[3] < 1e30 && p[4] > 0 &&
+                       p[4] < 1e30 && p[2] + p[3] > 0,
+                   "%s: params of model %d: eta, beta must be positive, min_child_weight, reg_lambda non-negative and "
+                   "not both 0", who, m);
+        DS_REQUIRE(held_out[m] >= -1 && held_out[m] < n_folds, "%s: held_out[%d] = %d out of range [-1, %d)", who, m,
+                   held_out[m], n_folds);
+        models[m] = ds::BatchModel{ds::TrainParams{static_cast<int32_t>(p[0]), p[1], p[2], p[3], p[4]}, held_out[m], 0};
+        depth = std::max(depth, models[m].params.max_depth);
+    }
+    if (int status = ds::train_check_cuts(who, n_features, cuts, cut_offsets); status != DS_OK) return status;
+    for (int64_t r = 0; r < n; ++r)
+        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "%s: labels: label %lld is not 0 or 1", who, (long long)r);
+    for (int64_t r = 0; r < n; ++r)
+        DS_REQUIRE(fold[r] < n_folds, "%s: fold[%lld] = %d is not below n_folds = %d", who, (long long)r, fold[r],
+                   n_folds);
+    const int64_t bytes = ds_trainer_batch_bytes(n, n_features, n_models, depth) + (in_hbm ? 0 : n * n_features * 4);
+    DS_HIP(hipSetDevice(device));
+    if (int status = ds::train_check_free(bytes, who); status != DS_OK) return status;
+    ds_trainer_batch *b = new ds_trainer_batch();
+    b->device = device;
+    b->n = n;
+    b->nf = n_features;
+    b->n_models = n_models;
+    b->max_depth = depth;
+    b->slots = static_cast<int32_t>(heap_nodes(depth));
+    b->models = models;
+    hipDeviceProp_t props;
+    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
+        b->compute_units = props.multiProcessorCount;
+    const size_t M = static_cast<size_t>(n_models), rows = static_cast<size_t>(n);
+    int status = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess ? DS_OK : DS_E_HIP;
+    if (status != DS_OK) ds::set_error("%s: hipStreamCreate failed", who);
+    if (status == DS_OK) status = b->cut_offsets.upload(cut_offsets, static_cast<size_t>(n_features) + 1);
+    if (status == DS_OK) status = b->cuts.allocate(std::max<size_t>(1, static_cast<size_t>(cut_offsets[n_features])));
+    if (status == DS_OK && cut_offsets[n_features] > 0)
+        status = b->cuts.upload(cuts, static_cast<size_t>(cut_offsets[n_features]));
+    if (status == DS_OK)
+        status = ds::train_bin_matrix(b->stream, b->compute_units, features, in_hbm, n, n_features, b->cuts.ptr,
+                                      b->cut_offsets.ptr, b->bins);
+    if (status == DS_OK) status = b->labels.upload(labels, rows);
+    if (status == DS_OK) status = b->fold.upload(fold, rows);
+    if (status == DS_OK) status = b->d_models.upload(models.data(), M);
+    if (status == DS_OK) status = b->active.allocate(M);
+    if (status == DS_OK) status = b->leafsum.allocate(M * rows);
+    if (status == DS_OK) status = b->probabilities.allocate(M * rows);
+    if (status == DS_OK) status = b->node_of.allocate(M * rows);
+    if (status == DS_OK) status = b->gh.allocate(2 * M * rows);
+    if (status == DS_OK) status = b->hist.allocate(M * static_cast<size_t>(hist_entries(depth, n_features)));
+    if (status == DS_OK) status = b->counts.allocate(M * b->slots);
+    if (status == DS_OK) status = b->nodes.allocate(M * b->slots);
+    if (status == DS_OK) status = b->candidates.allocate(M * static_cast<size_t>(candidate_entries(depth, n_features)));
+    if (status == DS_OK) status = b->errors.allocate(M);
+    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&b->pinned_nodes), sizeof(ds::Node) * M * b->slots) !=
+                               hipSuccess) status = DS_E_HIP;
+    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&b->pinned_errors), sizeof(unsigned long long) * M) !=
+                               hipSuccess) status = DS_E_HIP;
+    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&b->pinned_active), sizeof(int32_t) * M) != hipSuccess)
+        status = DS_E_HIP;
+    // every per-row array starts defined: the read-back of a model that has not stepped yet returns zeros
+    if (status == DS_OK && hipMemsetAsync(b->leafsum.ptr, 0, b->leafsum.bytes(), b->stream) != hipSuccess) status = DS_E_HIP;
+    if (status == DS_OK && hipMemsetAsync(b->probabilities.ptr, 0, b->probabilities.bytes(), b->stream) != hipSuccess)
+        status = DS_E_HIP;
+    if (status == DS_OK && hipMemsetAsync(b->gh.ptr, 0, b->gh.bytes(), b->stream) != hipSuccess) status = DS_E_HIP;
+    if (status == DS_OK && hipStreamSynchronize(b->stream) != hipSuccess) status = DS_E_HIP;
+    if (status != DS_OK) {
+        delete b;
+        return status;
+    }
+    ds::BatchView &v = b->view;
+    v.bins = b->bins.ptr;
+    v.labels = b->labels.ptr;
+    v.fold = b->fold.ptr;
+    v.cut_offsets = b->cut_offsets.ptr;
+    v.models = b->d_models.ptr;
+    v.active = b->active.ptr;
+    v.gh = b->gh.ptr;
+    v.node_of = b->node_of.ptr;
+    v.leafsum = b->leafsum.ptr;
+    v.probabilities = b->probabilities.ptr;
+    v.hist = b->hist.ptr;
+    v.nodes = b->nodes.ptr;
+    v.counts = b->counts.ptr;
+    v.candidates = b->candidates.ptr;
+    v.errors = b->errors.ptr;
+    v.n = n;
+    v.hist_stride = hist_entries(depth, n_features);
+    v.candidate_stride = candidate_entries(depth, n_features);
+    v.nf = n_features;
+    v.slots = b->slots;
+    *out = b;
+    return DS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth)
+{
+    if (!ranges_ok(n, n_features, n_models, max_depth)) return -1;
+    const int64_t per_model = n * 28 + hist_entries(max_depth, n_features) * 8 +
+                              heap_nodes(max_depth) * int64_t(sizeof(ds::Node) + 4) +
+                              candidate_entries(max_depth, n_features) * int64_t(sizeof(ds::Candidate)) +
+                              int64_t(sizeof(ds::BatchModel)) + 12;
+    return n * n_features + n * 5 + per_model * n_models;
+}
+
+int ds_trainer_batch_create(const float *features, int64_t n, int32_t n_features, const float *cuts,
+                            const int32_t *cut_offsets, const float *labels, const uint8_t *fold, int32_t n_folds,
+                            int32_t n_models, const double *params, const int32_t *held_out, int device,
+                            ds_trainer_batch **out)
+{
+    return create_batch("ds_trainer_batch_create", features, false, n, n_features, cuts, cut_offsets, labels, fold,
+                        n_folds, n_models, params, held_out, device, out);
+}
+
+int ds_trainer_batch_create_device(const float *d_features, int64_t n, int32_t n_features, const float *cuts,
+                                   const int32_t *cut_offsets, const float *labels, const uint8_t *fold, int32_t n_folds,
+                                   int32_t n_models, const double *params, const int32_t *held_out, int device,
+                                   ds_trainer_batch **out)
+{
+    return create_batch("ds_trainer_batch_create_device", d_features, true, n, n_features, cuts, cut_offsets, labels,
+                        fold, n_folds, n_models, params, held_out, device, out);
+}
+
+void ds_trainer_batch_destroy(ds_trainer_batch *batch)
+{
+    if (!batch) return;
+    (void)hipSetDevice(batch->device);
+    delete batch;
+}
+
+int ds_trainer_batch_option(const char *name, int64_t value)
+{
+    DS_REQUIRE(name != nullptr, "ds_trainer_batch_option: name is null");
+    DS_REQUIRE(std::strcmp(name, "max_blocks") == 0, "ds_trainer_batch_option: unknown option '%s'", name);
+    DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_trainer_batch_option: max_blocks = %lld out of range [0, 2^31)",
+               (long long)value);
+    g_max_blocks.store(value);
+    return DS_OK;
+}
+
+int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_t *node_info, float *node_leaf,
+                          int64_t *errors)
+{
+    DS_REQUIRE(batch && node_info && node_leaf && errors, "ds_trainer_batch_step: null argument");
+    ds_trainer_batch *b = batch;
+    int32_t n_active = 0, depth = 0;
+    for (int32_t m = 0; m < b->n_models; ++m) {
+        if (active && !active[m]) continue;
+        b->pinned_active[n_active++] = m;
+        depth = std::max(depth, b->models[m].params.max_depth);
+    }
+    if (n_active == 0) return DS_OK;
+    DS_HIP(hipSetDevice(b->device));
+    hipStream_t stream = b->stream;
+    const ds::BatchView &v = b->view;
+    const int64_t n = b->n;
+    const unsigned models = static_cast<unsigned>(n_active);
+    DS_HIP(hipMemcpyAsync(b->active.ptr, b->pinned_active, sizeof(int32_t) * n_active, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(ds::ds_batch_clear_kernel, dim3(row_grid(b, v.hist_stride / 2), models), dim3(ds::kRowThreads), 0,
+                       stream, v);
+    DS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ds::ds_batch_gradient_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream, v);
+    DS_HIP(hipGetLastError());
+    for (int32_t level = 0; level < depth; ++level) {   // to the largest max_depth among the active models
+        const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
+        const int32_t nodes_per_group = std::min(n_built, ds::kHistSlots);
+        const int32_t features_per_group = std::min<int32_t>(b->nf, ds::kHistSlots / nodes_per_group);
+        const int32_t feature_groups = (b->nf + features_per_group - 1) / features_per_group;
+        const int32_t node_groups = (n_built + nodes_per_group - 1) / nodes_per_group;
+        const int64_t groups = int64_t(feature_groups) * node_groups * n_active;
+        // ds_trainer_step's shape with the models counted in: about 4 workgroups per CU in all, each over >= 2048 rows
+        const int64_t chunks = capped(std::min<int64_t>((n + 2047) / 2048,
+                                                        (int64_t(b->compute_units) * 4 + groups - 1) / groups));
+        hipLaunchKernelGGL(ds::ds_batch_histogram_kernel,
+                           dim3(static_cast<unsigned>(chunks), feature_groups * node_groups, models),
+                           dim3(ds::kHistThreads), 0, stream, v, level, n_built, nodes_per_group, features_per_group,
+                           feature_groups);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds::ds_batch_split_feature_kernel, dim3(1u << level, b->nf, models), dim3(256), 0, stream, v,
+                           level);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds::ds_batch_split_kernel, dim3(((1u << level) + 63) / 64, models), dim3(64), 0, stream, v,
+                           level);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds::ds_batch_partition_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream,
+                           v, level);
+        DS_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ds::ds_batch_error_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream, v);
+    DS_HIP(hipGetLastError());
+    for (int32_t a = 0; a < n_active;) {   // the active models' heaps only: one copy per run of neighbouring models
+        int32_t end = a + 1;
+        while (end < n_active && b->pinned_active[end] == b->pinned_active[end - 1] + 1) ++end;
+        const size_t first = static_cast<size_t>(b->pinned_active[a]) * b->slots;
+        DS_HIP(hipMemcpyAsync(b->pinned_nodes + first, b->nodes.ptr + first, sizeof(ds::Node) * (end - a) * b->slots,
+                              hipMemcpyDeviceToHost, stream));
+        a = end;
+    }
+    DS_HIP(hipMemcpyAsync(b->pinned_errors, b->errors.ptr, b->errors.bytes(), hipMemcpyDeviceToHost, stream));
+    DS_HIP(hipStreamSynchronize(stream));   // the step's one host sync
+    for (int32_t a = 0; a < n_active; ++a) {
+        const int64_t m = b->pinned_active[a];
+        for (int64_t i = 0; i < b->slots; ++i) {
+            const ds::Node &node = b->pinned_nodes[m * b->slots + i];
+            int32_t *info = node_info + (m * b->slots + i) * 4;
+            info[0] = node.state;
+            info[1] = node.feature;
+            info[2] = node.bin;
+            info[3] = node.default_left;
+            node_leaf[m * b->slots + i] = node.leaf;
+        }
+        errors[m] = b->models[m].held_out >= 0 ? static_cast<int64_t>(b->pinned_errors[m]) : -1;
+    }
+    return DS_OK;
+}
+
+int ds_trainer_batch_read(ds_trainer_batch *batch, int32_t model, float *margins, float *probabilities,
+                          int64_t *gradients, uint8_t *bins)
+{
+    DS_REQUIRE(batch != nullptr, "ds_trainer_batch_read: batch is null");
+    DS_REQUIRE(model >= 0 && model < batch->n_models, "ds_trainer_batch_read: model = %d out of range [0, %d)", model,
+               batch->n_models);
+    ds_trainer_batch *b = batch;
+    DS_HIP(hipSetDevice(b->device));
+    DS_HIP(hipStreamSynchronize(b->stream));
+    const size_t n = static_cast<size_t>(b->n), m = static_cast<size_t>(model);
+    if (probabilities)
+        DS_HIP(hipMemcpy(probabilities, b->probabilities.ptr + m * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (gradients) DS_HIP(hipMemcpy(gradients, b->gh.ptr + 2 * m * n, sizeof(int64_t) * 2 * n, hipMemcpyDeviceToHost));
+    if (bins) DS_HIP(hipMemcpy(bins, b->bins.ptr, n * b->nf, hipMemcpyDeviceToHost));
+    if (margins) {
+        DS_HIP(hipMemcpy(margins, b->leafsum.ptr + m * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < n; ++r) margins[r] = ds::kBatchBaseMargin + margins[r];
+    }
+    return DS_OK;
+}
+
+}  // extern "C"

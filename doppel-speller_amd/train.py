@@ -200,6 +200,32 @@ def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, e
     return n, target, n_eval, eval_target, n_features, params
 
 
+def heap_tree(info, leaf, cuts, cut_offsets):
+    """Heap-ordered nodes of ds_trainer_step / ds_trainer_batch_step -> ForestModel arrays of one tree (breadth-first
+    ids: children after their parent).  Slots beyond the tree's own depth are absent and never visited."""
+    order, ids = [0], {0: 0}
+    for node in order:
+        if info[node, 0] == _SPLIT:
+            for child in (2 * node + 1, 2 * node + 2):
+                ids[child] = len(order)
+                order.append(child)
+    size = len(order)
+    tree = dict(feature=np.full(size, -1, np.int32), threshold=np.zeros(size, np.float32),
+                yes=np.zeros(size, np.int32), no=np.zeros(size, np.int32), missing=np.zeros(size, np.int32))
+    for i, node in enumerate(order):
+        state, feature, bin_, default_left = (int(v) for v in info[node])
+        if state == _SPLIT:
+            left, right = ids[2 * node + 1], ids[2 * node + 2]
+            tree["feature"][i] = feature
+            tree["threshold"][i] = cuts[cut_offsets[feature] + bin_ - 1]   # bins < b  <=>  x < cut
+            tree["yes"][i], tree["no"][i] = left, right
+            tree["missing"][i] = left if default_left else right
+        else:
+            assert state == _LEAF, f"node {node}: state {state}"
+            tree["threshold"][i] = leaf[node]
+    return tree
+
+
 class ForestTrainer:
     """xgb.train(params={max_depth, eta, min_child_weight}, obj=weighted_log_loss, feval=custom_error,
     early_stopping_rounds) on the GPU.
@@ -307,28 +333,8 @@ class ForestTrainer:
         return value
 
     def _tree(self, info, leaf):
-        """Heap-ordered nodes -> ForestModel arrays of one tree (breadth-first ids: children after their parent)."""
-        order, ids = [0], {0: 0}
-        for node in order:
-            if info[node, 0] == _SPLIT:
-                for child in (2 * node + 1, 2 * node + 2):
-                    ids[child] = len(order)
-                    order.append(child)
-        size = len(order)
-        tree = dict(feature=np.full(size, -1, np.int32), threshold=np.zeros(size, np.float32),
-                    yes=np.zeros(size, np.int32), no=np.zeros(size, np.int32), missing=np.zeros(size, np.int32))
-        for i, node in enumerate(order):
-            state, feature, bin_, default_left = (int(v) for v in info[node])
-            if state == _SPLIT:
-                left, right = ids[2 * node + 1], ids[2 * node + 2]
-                tree["feature"][i] = feature
-                tree["threshold"][i] = self.cuts[self.cut_offsets[feature] + bin_ - 1]   # bins < b  <=>  x < cut
-                tree["yes"][i], tree["no"][i] = left, right
-                tree["missing"][i] = left if default_left else right
-            else:
-                assert state == _LEAF, f"node {node}: state {state}"
-                tree["threshold"][i] = leaf[node]
-        return tree
+        """Heap-ordered nodes -> ForestModel arrays of one tree (heap_tree with this trainer's cuts)."""
+        return heap_tree(info, leaf, self.cuts, self.cut_offsets)
 
     def model(self, n_trees=None):
         """ForestModel of the first n_trees trees (default: all grown so far)."""

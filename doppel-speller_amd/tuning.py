@@ -1,0 +1,462 @@
+"""Cross-validation and parameter search for the match model ("Cross-validation and tuning").
+
+ForestTrainerBatch grows many boosters over ONE binned matrix on the GPU (csrc/ds_train_batch.hip, C ABI
+ds_trainer_batch_*): every model has its own parameters and its own held-out fold, and one round launches each kernel
+once for all of them.  cross_validate runs K folds x P parameter sets on it with xgb.cv's rule (the per-round sum of the
+folds' integer errors, the first minimum, early stopping on that sum) and refits the chosen set on all rows;
+tune_model_parameters does so from raw titles with the feature matrix never leaving HBM.
+"""
+import ctypes
+import inspect
+import itertools
+import time
+
+import numpy as np
+
+from . import _lib
+from .forest import ForestModel
+from .train import (_device_columns, _device_labels, _matrix_and_labels, _positive_int, compute_cuts,
+                    compute_cuts_device, heap_tree, validate_parameters)
+
+MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
+FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
+PARAMETER_NAMES = ("max_depth", "eta", "min_child_weight", "reg_lambda", "beta")
+_DEFAULTS = {name: inspect.signature(validate_parameters).parameters[name].default for name in PARAMETER_NAMES}
+
+
+def _parameter_set(parameters, what="parameters"):
+    """One dict of the five booster parameters, defaults filled in, checked by validate_parameters."""
+    if not isinstance(parameters, dict):
+        raise ValueError(f"{what} must be a dict of {PARAMETER_NAMES}, not {parameters!r}")
+    unknown = set(parameters) - set(PARAMETER_NAMES)
+    if unknown:
+        raise ValueError(f"unknown {what} {sorted(unknown)}; known: {list(PARAMETER_NAMES)}")
+    checked = validate_parameters(**dict(_DEFAULTS, **parameters))
+    return {name: checked[name] for name in PARAMETER_NAMES}
+
+
+def _parameter_sets(parameters):
+    sets = [parameters] if isinstance(parameters, dict) else list(parameters) if parameters is not None else []
+    if not sets:
+        raise ValueError("parameters must be a parameter dict or a non-empty list of them")
+    sets = [_parameter_set(one) for one in sets]
+    keys = [tuple(one[name] for name in PARAMETER_NAMES) for one in sets]
+    if len(set(keys)) != len(keys):
+        raise ValueError("parameters holds the same parameter set twice")
+    return sets
+
+
+def parameter_grid(**lists):
+    """The Cartesian product of max_depth, eta, min_child_weight, reg_lambda and beta (a scalar counts as a list of
+    one, a parameter left out takes its default) as a list of parameter dicts.  The order is fixed: the parameters
+    vary in the order just named, the LAST-named one fastest (itertools.product).  Every set is checked by
+    validate_parameters; a value given twice, which would make two equal sets, is refused."""
+    unknown = set(lists) - set(PARAMETER_NAMES)
+    if unknown:
+        raise ValueError(f"unknown parameters {sorted(unknown)}; known: {list(PARAMETER_NAMES)}")
+    axes = []
+    for name in PARAMETER_NAMES:
+        values = lists.get(name, _DEFAULTS[name])
+        values = list(values) if isinstance(values, (list, tuple, np.ndarray)) else [values]
+        if not values:
+            raise ValueError(f"{name} has no values")
+        axes.append(values)
+    return _parameter_sets([dict(zip(PARAMETER_NAMES, combination)) for combination in itertools.product(*axes)])
+
+
+def fold_assignment(groups, n_folds, seed=0, n=None):
+    """uint8[n]: the fold of every row.  The distinct group values in ascending order are permuted by
+    np.random.default_rng(seed).permutation; the group at position i of the permuted order gets fold i % n_folds, so
+    rows of one group share a fold, the folds' sizes in groups differ by at most one, and the result depends on the
+    values of `groups` alone, not on the order of the rows.  groups=None: every one of the n rows is its own group."""
+    n_folds = _positive_int("n_folds", n_folds, 2, FOLDS_MAX)
+    seed = _positive_int("seed", seed, 0)
+    if groups is None:
+        if n is None:
+            raise ValueError("without groups the number of rows is needed: fold_assignment(None, n_folds, seed, n=rows)")
+        n_groups = _positive_int("n", n, 1)
+        inverse = np.arange(n_groups)
+    else:
+        groups = np.asarray(groups)
+        if groups.ndim != 1 or groups.shape[0] < 1:
+            raise ValueError(f"groups must be a non-empty 1-D array, not shape {groups.shape}")
+        if n is not None and groups.shape[0] != n:
+            raise ValueError(f"{n} rows but {groups.shape[0]} groups")
+        distinct, inverse = np.unique(groups, return_inverse=True)
+        n_groups = distinct.shape[0]
+    if n_folds > n_groups:
+        raise ValueError(f"n_folds = {n_folds} exceeds the {n_groups} groups")
+    fold_of_group = np.empty(n_groups, np.uint8)
+    fold_of_group[np.random.default_rng(seed).permutation(n_groups)] = np.arange(n_groups) % n_folds
+    return fold_of_group[inverse.reshape(-1)]
+
+
+def _replay(curve, early_stopping_rounds):
+    """(best_iteration, error, rounds) of one summed curve under the stepping rule: the first minimum; the set stops
+    after the first round with round - best >= early_stopping_rounds (None: never), later entries are not looked at."""
+    best = 0
+    for round_, error in enumerate(curve):
+        if error < curve[best]:
+            best = round_
+        if early_stopping_rounds is not None and round_ - best >= early_stopping_rounds:
+            return best, int(curve[best]), round_ + 1
+    return best, int(curve[best]), len(curve)
+
+
+def select_parameters(histories, early_stopping_rounds=None):
+    """xgb.cv's choice, on the host.  histories[p][k] = the held-out error of fold k after every round of parameter set
+    p (the K curves of a set have one length; sets may differ).  Per set the summed curve is the per-round sum of its
+    folds' errors -- the out-of-fold error over the whole matrix, an integer -- best_iteration its first minimum and
+    error that minimum, looking no further than the round at which early_stopping_rounds would have stopped the set.
+    The chosen set has the lowest error; a tie goes to the smaller best_iteration, then to the earlier set.
+    Returns dict(chosen, best_iteration[p], error[p], rounds[p], history[p])."""
+    if early_stopping_rounds is not None:
+        early_stopping_rounds = _positive_int("early_stopping_rounds", early_stopping_rounds)
+    if len(histories) == 0:
+        raise ValueError("histories is empty")
+    out = dict(best_iteration=[], error=[], rounds=[], history=[])
+    for p, folds in enumerate(histories):
+        lengths = {len(curve) for curve in folds}
+        if len(folds) == 0 or len(lengths) != 1 or 0 in lengths:
+            raise ValueError(f"parameter set {p}: the folds' curves must be non-empty and of one length")
+        summed = [int(sum(int(curve[r]) for curve in folds)) for r in range(lengths.pop())]
+        best, error, rounds = _replay(summed, early_stopping_rounds)
+        out["best_iteration"].append(best)
+        out["error"].append(error)
+        out["rounds"].append(rounds)
+        out["history"].append(summed[:rounds])
+    out["chosen"] = min(range(len(histories)), key=lambda p: (out["error"][p], out["best_iteration"][p], p))
+    return out
+
+
+def validate_models(models, n_folds):
+    """The model list of ForestTrainerBatch.begin -> (params float64[M, 5], held_out int32[M], parameter dicts)."""
+    models = list(models) if models is not None else []
+    if not 1 <= len(models) <= MODELS_MAX:
+        raise ValueError(f"a batch takes 1 to {MODELS_MAX} models, not {len(models)}")
+    sets, held = [], []
+    for m, model in enumerate(models):
+        if not isinstance(model, dict):
+            raise ValueError(f"model {m} must be a dict, not {model!r}")
+        sets.append(_parameter_set({k: v for k, v in model.items() if k != "held_out"}, f"parameters of model {m}"))
+        held.append(_positive_int(f"held_out of model {m}", model.get("held_out", -1), -1, n_folds - 1))
+    params = np.array([[one[name] for name in PARAMETER_NAMES] for one in sets], np.float64)
+    return np.ascontiguousarray(params), np.array(held, np.int32), sets
+
+
+def _validate_fold(fold, n):
+    fold = np.asarray(fold)
+    if fold.ndim != 1 or fold.shape[0] != n:
+        raise ValueError(f"{n} rows but {fold.reshape(-1).shape[0]} fold entries")
+    if not np.issubdtype(fold.dtype, np.integer) or fold.min() < 0 or fold.max() >= FOLDS_MAX:
+        raise ValueError(f"fold must hold integers in [0, {FOLDS_MAX})")
+    return np.ascontiguousarray(fold, dtype=np.uint8), int(fold.max()) + 1
+
+
+def batch_bytes(n, n_features, n_models, max_depth):
+    """ds_trainer_batch_bytes: the HBM a batch of n_models models over n x n_features needs (a host matrix adds its
+    staged copy, 4 * n * n_features)."""
+    return int(_lib.lib().ds_trainer_batch_bytes(n, n_features, n_models, max_depth))
+
+
+def batch_option(name, value):
+    """ds_trainer_batch_option, for tests: batch_option("max_blocks", b) caps the row grids (0: default)."""
+    _lib.check(_lib.lib().ds_trainer_batch_option(name.encode(), int(value)), "ds_trainer_batch_option")
+
+
+class ForestTrainerBatch:
+    """Many ForestTrainers over one binned matrix, stepped together.
+
+        batch = ForestTrainerBatch().begin(features, target, fold, models)
+        errors = batch.step()            # one round of every model; errors[m] = held-out error, None without a fold
+
+    models: dicts {max_depth, eta, min_child_weight, reg_lambda, beta, held_out}; row r trains in model m iff
+    fold[r] != held_out (-1, the default: every row trains).  The cuts are those of the WHOLE matrix, so a model's trees
+    are ForestTrainer's on its training rows with those cuts.  step(active) touches only the models with active[m] true.
+    trees[m], history[m] (errors; None entries without a fold), model(m, n_trees), margins(m) (all rows),
+    probabilities(m), gradients(m), bins(), last_heap[m] as ForestTrainer's."""
+
+    def __init__(self, device=0):
+        self.device = device
+        self.handle = None
+        self.trees, self.history, self.last_heap = [], [], []
+        self.timings = {}
+
+    def begin(self, features, target, fold, models, max_bin=256, cuts=None):
+        features, target = _matrix_and_labels(features, target, "training")
+        return self._begin(features, False, features.shape[0], features.shape[1], target, fold, models, max_bin, cuts)
+
+    def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None):
+        """begin for a contiguous float32[n, n_features] matrix that lies complete in HBM (a DeviceArray, or an address
+        with n_features given).  It is read where it lies, never copied to the host, and not kept."""
+        n_features = _device_columns(d_features, n_features)
+        n, target = _device_labels(n, target, "training")
+        if isinstance(d_features, _lib.DeviceArray) and n > d_features.shape[0]:
+            raise ValueError(f"{n} training rows exceed the device matrix's {d_features.shape[0]}")
+        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts)
+
+    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts):
+        fold, n_folds = _validate_fold(fold, n)
+        params, held_out, sets = validate_models(models, FOLDS_MAX)
+        if held_out.max() >= n_folds:
+            raise ValueError(f"held_out = {int(held_out.max())} but fold holds only 0 .. {n_folds - 1}")
+        max_bin = _positive_int("max_bin", max_bin, 2, 256)
+        self.close()
+        self.timings = {}
+        mark = time.perf_counter()
+        if cuts is None:
+            cuts = compute_cuts_device(features, n, max_bin, n_features, self.device) if in_hbm else \
+                compute_cuts(features, max_bin)
+        self.cuts, self.cut_offsets = cuts
+        self.timings["cuts"] = (time.perf_counter() - mark) * 1000.0
+        self.n, self.n_features, self.n_models, self.n_folds = n, n_features, len(sets), n_folds
+        self.parameters, self.held_out = sets, held_out
+        self.max_depth = int(params[:, 0].max())
+        self.trees = [[] for _ in sets]
+        self.history = [[] for _ in sets]
+        self.last_heap = [None] * len(sets)
+        mark = time.perf_counter()
+        handle = ctypes.c_void_p()
+        library = _lib.lib()
+        create = library.ds_trainer_batch_create_device if in_hbm else library.ds_trainer_batch_create
+        _lib.check(create(_lib.pointer(features), n, n_features, _lib.pointer(self.cuts), _lib.pointer(self.cut_offsets),
+                          _lib.pointer(target), _lib.pointer(fold), n_folds, self.n_models, _lib.pointer(params),
+                          _lib.pointer(held_out), self.device, ctypes.byref(handle)),
+                   "ds_trainer_batch_create_device" if in_hbm else "ds_trainer_batch_create")
+        self.handle = handle
+        self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
+        slots = (2 << self.max_depth) - 1          # the heaps of every model have the largest max_depth's slots
+        self._info = np.zeros((self.n_models, slots, 4), np.int32)
+        self._leaf = np.zeros((self.n_models, slots), np.float32)
+        self._errors = np.zeros(self.n_models, np.int64)
+        return self
+
+    def step(self, active=None):
+        """One round of the active models (default: all).  Returns a list with the held-out error of every model that
+        stepped and has a held-out fold, None for the others."""
+        if not self.handle:
+            raise RuntimeError("ForestTrainerBatch.step before begin")
+        if active is None:
+            mask = np.ones(self.n_models, np.uint8)
+        else:
+            mask = np.ascontiguousarray(np.asarray(active).astype(bool), dtype=np.uint8)
+            if mask.shape != (self.n_models,):
+                raise ValueError(f"active must have {self.n_models} entries, not shape {mask.shape}")
+        _lib.check(_lib.lib().ds_trainer_batch_step(self.handle, _lib.pointer(mask), _lib.pointer(self._info),
+                                                    _lib.pointer(self._leaf), _lib.pointer(self._errors)),
+                   "ds_trainer_batch_step")
+        out = [None] * self.n_models
+        for m in np.nonzero(mask)[0]:
+            self.last_heap[m] = (self._info[m].copy(), self._leaf[m].copy())
+            self.trees[m].append(heap_tree(self._info[m], self._leaf[m], self.cuts, self.cut_offsets))
+            out[m] = int(self._errors[m]) if self.held_out[m] >= 0 else None
+            self.history[m].append(out[m])
+        return out
+
+    def model(self, m, n_trees=None):
+        """ForestModel of the first n_trees trees of model m (default: all grown so far)."""
+        trees = self.trees[m][:len(self.trees[m]) if n_trees is None else n_trees]
+        return ForestModel.from_trees(trees, self.n_features, device=self.device)
+
+    def _read(self, m, **wanted):
+        out = {name: np.empty(shape, dtype) for name, (shape, dtype) in wanted.items()}
+        p = lambda name: _lib.pointer(out.get(name))
+        _lib.check(_lib.lib().ds_trainer_batch_read(self.handle, int(m), p("margins"), p("probabilities"),
+                                                    p("gradients"), p("bins")), "ds_trainer_batch_read")
+        return out
+
+    def margins(self, m):
+        """Model m's margins of ALL rows after its trees so far (float32[n])."""
+        return self._read(m, margins=(self.n, np.float32))["margins"]
+
+    def probabilities(self, m):
+        return self._read(m, probabilities=(self.n, np.float32))["probabilities"]
+
+    def gradients(self, m):
+        """int64[n, 2] of model m's last step; (0, 0) in its held-out rows."""
+        return self._read(m, gradients=((self.n, 2), np.int64))["gradients"]
+
+    def bins(self):
+        return self._read(0, bins=((self.n_features, self.n), np.uint8))["bins"]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().ds_trainer_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrossValidation:
+    """What cross_validate returns: `results` (DataFrame, one line per parameter set in the given order: the five
+    parameters, best_iteration, error, rounds, fold_errors at the best round), `history[p]` (the summed curve),
+    `fold_history[p][k]`, `parameters` (the sets), `chosen` (the index of the best set), `best_parameters`,
+    `best_iteration`, `folds` (uint8[n]), `timings` (ms: cuts, bin, boost, refit, total) and, with refit, `model`.
+    tune_model_parameters adds `rows` and `feature_importance`."""
+
+    def __init__(self, **fields):
+        self.model = self.rows = self.feature_importance = None
+        self.__dict__.update(fields)
+
+
+def validate_cross_validation(parameters, n_folds=5, seed=0, num_boost_round=1000, early_stopping_rounds=50,
+                              max_bin=256, models_per_batch=None):
+    """cross_validate's checks of everything but the data (no library needed) -> (parameter sets, sets per batch)."""
+    sets = _parameter_sets(parameters)
+    n_folds = _positive_int("n_folds", n_folds, 2, FOLDS_MAX)
+    _positive_int("seed", seed, 0)
+    validate_parameters(num_boost_round=num_boost_round, early_stopping_rounds=early_stopping_rounds, max_bin=max_bin)
+    if models_per_batch is not None:
+        models_per_batch = _positive_int("models_per_batch", models_per_batch, 1, MODELS_MAX)
+        if models_per_batch < n_folds:
+            raise ValueError(f"models_per_batch = {models_per_batch} is below n_folds = {n_folds}: a batch holds whole "
+                             "parameter sets")
+        return sets, models_per_batch // n_folds
+    return sets, None
+
+
+def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device):
+    """Whole parameter sets (K models each) per batch: what 80 % of the free HBM holds, 256 models at most."""
+    free, total = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().ds_device_memory(device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
+    budget = int(free.value * 0.8) - (0 if in_hbm else 4 * n * n_features)
+    depth = max(one["max_depth"] for one in sets)
+    count = max(1, min(len(sets), MODELS_MAX // n_folds))
+    while count > 1 and batch_bytes(n, n_features, count * n_folds, depth) > budget:
+        count -= 1
+    return count
+
+
+def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0, num_boost_round=1000,
+                   early_stopping_rounds=50, max_bin=256, refit=True, device=0, models_per_batch=None):
+    """K-fold cross-validation of one parameter set or a list of them (parameter_grid) on the GPU -> CrossValidation.
+
+    features: a host matrix, or a DeviceArray float32[>= n, n_features] in HBM of which the first len(target) rows
+    count (never copied to the host).  The folds come from fold_assignment(groups, n_folds, seed).  Every set runs
+    n_folds models, model k holding fold k out, all stepped together in batches of whole sets.  A set is stepped until
+    round - best >= early_stopping_rounds on its SUMMED curve or until num_boost_round; then its models go inactive
+    while other sets continue.  models_per_batch=None sizes the batches from the free HBM; the result does not depend
+    on it.  The cuts are computed once, the bins once per batch.  refit: the chosen set is trained on ALL rows for
+    best_iteration + 1 rounds; with the whole matrix's cuts that is ForestTrainer().fit(features, target,
+    num_boost_round=best_iteration + 1, **best_parameters), bit for bit."""
+    started = time.perf_counter()
+    sets, per_batch = validate_cross_validation(parameters, n_folds, seed, num_boost_round, early_stopping_rounds,
+                                                max_bin, models_per_batch)
+    in_hbm = isinstance(features, _lib.DeviceArray)
+    if in_hbm:
+        n_features = _device_columns(features, None)
+        n, target = _device_labels(np.asarray(target).reshape(-1).shape[0], target, "training")
+        if n > features.shape[0]:
+            raise ValueError(f"{n} labels exceed the device matrix's {features.shape[0]} rows")
+        device = features.device
+    else:
+        features, target = _matrix_and_labels(features, target, "training")
+        n, n_features = features.shape
+    folds = fold_assignment(groups, n_folds, seed, n)
+    if per_batch is None:
+        per_batch = _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device)
+    timings = dict.fromkeys(("cuts", "bin", "boost", "refit"), 0.0)
+    mark = time.perf_counter()
+    cuts = compute_cuts_device(features, n, max_bin, n_features, device) if in_hbm else compute_cuts(features, max_bin)
+    timings["cuts"] = (time.perf_counter() - mark) * 1000.0
+
+    def begin(models):
+        batch = ForestTrainerBatch(device)
+        if in_hbm:
+            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts)
+        else:
+            batch.begin(features, target, folds, models, max_bin, cuts)
+        timings["bin"] += batch.timings["bin"]
+        return batch
+
+    fold_history = [None] * len(sets)
+    for first in range(0, len(sets), per_batch):
+        chunk = sets[first:first + per_batch]
+        batch = begin([dict(one, held_out=k) for one in chunk for k in range(n_folds)])
+        try:
+            mark = time.perf_counter()
+            summed, best = [[] for _ in chunk], [0] * len(chunk)
+            running = np.ones(len(chunk), bool)
+            for round_ in range(num_boost_round):
+                errors = batch.step(np.repeat(running, n_folds))
+                for s in np.nonzero(running)[0]:
+                    summed[s].append(sum(errors[s * n_folds:(s + 1) * n_folds]))
+                    if summed[s][-1] < summed[s][best[s]]:
+                        best[s] = round_
+                    if round_ - best[s] >= early_stopping_rounds:
+                        running[s] = False
+                if not running.any():
+                    break
+            for s in range(len(chunk)):
+                fold_history[first + s] = [list(batch.history[s * n_folds + k]) for k in range(n_folds)]
+            timings["boost"] += (time.perf_counter() - mark) * 1000.0
+        finally:
+            batch.close()
+    chosen = select_parameters(fold_history, early_stopping_rounds)
+    import pandas as pd
+    results = pd.DataFrame(sets)
+    results["best_iteration"], results["error"], results["rounds"] = \
+        chosen["best_iteration"], chosen["error"], chosen["rounds"]
+    results["fold_errors"] = [[curve[chosen["best_iteration"][p]] for curve in fold_history[p]]
+                              for p in range(len(sets))]
+    best_set = chosen["chosen"]
+    out = CrossValidation(results=results, history=chosen["history"], fold_history=fold_history, parameters=sets,
+                          chosen=best_set, best_parameters=dict(sets[best_set]),
+                          best_iteration=chosen["best_iteration"][best_set], folds=folds, timings=timings)
+    if refit:
+        mark = time.perf_counter()
+        batch = begin([dict(sets[best_set], held_out=-1)])
+        try:
+            for _ in range(out.best_iteration + 1):
+                batch.step()
+            out.model = batch.model(0)
+        finally:
+            batch.close()
+        timings["refit"] = (time.perf_counter() - mark) * 1000.0
+    timings["total"] = (time.perf_counter() - started) * 1000.0
+    return out
+
+
+def row_groups(rows):
+    """One group per (kind, query_index) of FeatureEngineering.rows: the candidates sampled for one train title, or
+    the generated row of one truth title, never straddle folds."""
+    return (rows["kind"].to_numpy().astype(np.int64) << 40) | rows["query_index"].to_numpy().astype(np.int64)
+
+
+def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters, n_folds=5, top_n=100,
+                          sample_n=10, seed=0, device=0, transform=True, cover=False, **cv_arguments):
+    """Parameter search from raw titles in one call: FeatureEngineering(..., no evaluation split).
+    generate_device_data_sets() -> cross_validate on the matrix in HBM, folds by row_groups -> the refit model.
+    cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch.  Returns cross_validate's result
+    with `rows` (FeatureEngineering.rows), `feature_importance` and the FeatureEngineering stages in `timings`.
+    cover: also count the model's cover on the matrix while it is in HBM (ForestModel.fit_cover_device), so that the
+    model can explain its predictions; `timings` then has "cover".  Everything is validated before any device work and
+    everything held in HBM is freed on every exit path."""
+    from .training_set import FeatureEngineering
+    started = time.perf_counter()
+    unknown = set(cv_arguments) - {"num_boost_round", "early_stopping_rounds", "max_bin", "models_per_batch"}
+    if unknown:
+        raise ValueError(f"unknown cross-validation arguments {sorted(unknown)}")
+    validate_cross_validation(parameters, n_folds, seed, **cv_arguments)
+    fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
+                            sample_n=sample_n, seed=seed, device=device, transform=transform,
+                            evaluation_fractions=dict(generated=0.0, negative=0.0, positive=0.0))
+    sets = fe.generate_device_data_sets()
+    try:
+        matrix = _lib.DeviceArray.view(sets.train.ptr, (sets.n_train, sets.train.shape[1]), np.float32, device)
+        out = cross_validate(matrix, sets.train_target, parameters, n_folds=n_folds, groups=row_groups(fe.rows),
+                             seed=seed, refit=True, device=device, **cv_arguments)
+        if cover:
+            mark = time.perf_counter()
+            out.model.fit_cover_device(sets.train, sets.n_train)
+            out.timings["cover"] = (time.perf_counter() - mark) * 1000.0
+    finally:
+        sets.free()
+    out.timings = dict(fe.timings, **out.timings)
+    out.rows, out.feature_importance = fe.rows, out.model.feature_importance()
+    out.timings["total"] = (time.perf_counter() - started) * 1000.0
+    return out

@@ -43,6 +43,7 @@ typedef struct ds_timer ds_timer;   /* pair of HIP events */
 typedef struct ds_problem ds_problem; /* host-side product of the native index build (next row f-3) */
 typedef struct ds_forest ds_forest;   /* tree ensemble resident in HBM (next row f-4) */
 typedef struct ds_trainer ds_trainer; /* gradient-boosted tree trainer resident in HBM (train.py) */
+typedef struct ds_trainer_batch ds_trainer_batch; /* many such trainers over one binned matrix (cross-validation) */
 typedef struct ds_query_space ds_query_space; /* truth vocabulary of the query-rows kernels, resident in HBM */
 
 /* ---- library ---------------------------------------------------------------------------------------------------- */
@@ -500,6 +501,49 @@ int ds_trainer_set_eval_device(ds_trainer *trainer, const float *d_features, con
  * `stream`, which is synchronised before returning. */
 int ds_gather_rows_device(const float *d_src, int32_t n_features, const int64_t *d_rows, int64_t n_rows, int64_t n_src,
                           float *d_dst, void *stream);
+
+/* ---- batched training: cross-validation and parameter search ("Cross-validation and tuning") -------
+ * One batch holds one binned training matrix and n_models (1..256) boosters, each grown by ds_trainer_step's rule with its
+ * own parameters and its own held-out fold.  features, cuts, cut_offsets as for ds_trainer_create(_device): the cuts are
+ * those of the WHOLE matrix.  labels float[n] (0 or 1) and fold uint8[n] (every value below n_folds, 1..255) are host
+ * arrays.  params[5m .. 5m + 5) = max_depth (integral, 1..8), eta, min_child_weight, reg_lambda, beta of model m, in
+ * ds_trainer_create's ranges; held_out[m] in [-1, n_folds).  Row r trains in model m iff fold[r] != held_out[m] (-1: every
+ * row trains): a held-out row has gradient and hessian 0, adds nothing to any histogram, and is routed through every new
+ * tree, which adds its leaf to the row's float32 leaf sum like any row's.  Model m's trees are so those of
+ * ds_trainer_step on its training rows alone with the same cuts.  Any argument out of range or null: DS_E_ARG, nothing
+ * launched, *out = NULL.  A batch that does not fit the free HBM (ds_trainer_batch_bytes, + 4 * n * n_features for the
+ * staged copy of a host matrix) is refused with DS_E_HIP and a message that names both numbers.  The _device form reads a
+ * matrix that lies complete in HBM and keeps no pointer to it. */
+int ds_trainer_batch_create(const float *features, int64_t n, int32_t n_features, const float *cuts,
+                            const int32_t *cut_offsets, const float *labels, const uint8_t *fold, int32_t n_folds,
+                            int32_t n_models, const double *params, const int32_t *held_out, int device,
+                            ds_trainer_batch **out);
+int ds_trainer_batch_create_device(const float *d_features, int64_t n, int32_t n_features, const float *cuts,
+                                   const int32_t *cut_offsets, const float *labels, const uint8_t *fold, int32_t n_folds,
+                                   int32_t n_models, const double *params, const int32_t *held_out, int device,
+                                   ds_trainer_batch **out);
+void ds_trainer_batch_destroy(ds_trainer_batch *batch);
+/* One round of every model m with active[m] != 0 (host array of n_models bytes; NULL: all of them): each kernel of the
+ * round is launched once for all active models, levels run to the largest max_depth among them, one host sync.  The
+ * trees come back as ds_trainer_step's heaps with slots = 2^(D + 1) - 1, D = the LARGEST max_depth of the batch, whatever
+ * a model's own: node_info int32[n_models][slots][4], node_leaf float[n_models][slots].  errors int64[n_models]: train.py's
+ * custom error (missed positives + 5 * false positives at p > 0.9) of model m's held-out rows at their margins after the
+ * round, -1 for held_out[m] = -1.  An inactive model is not touched: its state stays as it was and its entries of the
+ * three outputs are not written; the active ones behave as if it did not exist.  No active model: nothing is done. */
+int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_t *node_info, float *node_leaf,
+                          int64_t *errors);
+/* Read-back for tests, every pointer nullable: one model's margins float[n] of ALL rows, the probabilities float[n] and
+ * quantized (gradient, hessian) int64[n][2] of its last step (zeros before its first), and the shared bins
+ * uint8[n_features][n]. */
+int ds_trainer_batch_read(ds_trainer_batch *batch, int32_t model, float *margins, float *probabilities,
+                          int64_t *gradients, uint8_t *bins);
+/* The bytes of HBM that ds_trainer_batch_create_device needs for n_models models whose largest max_depth is max_depth:
+ * n * n_features + 5 n shared, and per model 28 n + (2^max_depth - 1) * n_features * 4096 + a few KiB.  -1 for
+ * arguments outside the limits above. */
+int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth);
+/* For tests: ds_trainer_batch_option("max_blocks", b) caps every grid of this stage that runs over rows at b workgroups,
+ * which stride beyond it (0: back to the default).  The results do not depend on it. */
+int ds_trainer_batch_option(const char *name, int64_t value);
 
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
