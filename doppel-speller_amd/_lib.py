@@ -181,6 +181,7 @@ def _declare(handle):
         "ds_trainer_set_eval": [p, p, p, c.c_int64],
         "ds_trainer_step": [p, p, p, c.POINTER(c.c_int64)],
         "ds_trainer_read": [p, p, p, p, p, p],
+        "ds_trainer_set_sampling": [p, c.c_double, c.c_double, c.c_double, c.c_uint64],
         "ds_feature_cuts_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_int, p],
         "ds_cuts_option": [c.c_char_p, c.c_int64],
         "ds_trainer_create_device": [p, c.c_int64, c.c_int32, p, p, c.c_int32, c.c_double, c.c_double, c.c_double,
@@ -193,6 +194,7 @@ def _declare(handle):
         "ds_trainer_batch_step": [p, p, p, p, p],
         "ds_trainer_batch_read": [p, c.c_int32, p, p, p, p],
         "ds_trainer_batch_option": [c.c_char_p, c.c_int64],
+        "ds_trainer_batch_set_sampling": [p, p, p],
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
@@ -251,7 +253,7 @@ EXPORTED_SYMBOLS = (
     "ds_forest_cover_set", "ds_forest_cover_read", "ds_forest_cover_clear", "ds_forest_option",
     "ds_forest_contributions_device", "ds_forest_contributions", "ds_best_pairs_device", "ds_trainer_batch_create",
     "ds_trainer_batch_create_device", "ds_trainer_batch_destroy", "ds_trainer_batch_step", "ds_trainer_batch_read",
-    "ds_trainer_batch_bytes", "ds_trainer_batch_option")
+    "ds_trainer_batch_bytes", "ds_trainer_batch_option", "ds_trainer_set_sampling", "ds_trainer_batch_set_sampling")
 
 
 def lib():

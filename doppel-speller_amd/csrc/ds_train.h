@@ -32,6 +32,35 @@ struct TrainParams {
     double eta, min_child_weight, reg_lambda, beta;
 };
 
+// ---- row and column subsampling ("Subsampling") ------------------------------------------------
+// The purposes of the sampling streams (include/doppel_amd.h; 1 and 2 are ds_training.hip's).
+constexpr uint64_t kPurposeSampleRow = 3, kPurposeSampleTree = 4, kPurposeSampleLevel = 5;
+
+struct TrainSampling {
+    double subsample, colsample_bytree, colsample_bylevel;   // each in (0, 1]
+    uint64_t seed;
+    __host__ __device__ bool any() const { return subsample < 1.0 || colsample_bytree < 1.0 || colsample_bylevel < 1.0; }
+};
+
+// The first kept (third) output of the splitmix64 stream of (seed, purpose, index): ds_training.hip's Rng after its
+// constructor, one next().
+__host__ __device__ inline uint64_t sample_key(uint64_t seed, uint64_t purpose, uint64_t index)
+{
+    uint64_t z = seed * 0x9e3779b97f4a7c15ull + index * 0xd1342543de82ef95ull + purpose * 0xaf251af3b0f025b5ull +
+                 3ull * 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// The model's `tree`-th tree (from 0) trains on its training row `row` (from 0, counted among the rows that train)
+__device__ inline bool sample_row(const TrainSampling &sampling, int64_t tree, int64_t row)
+{
+    const uint64_t x = sample_key(sampling.seed, kPurposeSampleRow,
+                                  (static_cast<uint64_t>(tree) << 32) | static_cast<uint64_t>(row));
+    return static_cast<double>(x >> 11) * 0x1.0p-53 < sampling.subsample;
+}
+
 // Host side, ds_train.hip: bins of a float32[n][nf] matrix into `out` with the cuts in HBM.  A host matrix is uploaded
 // through a temporary buffer, a matrix in HBM (in_hbm, complete before the call) is read where it lies and not kept.
 // Synchronises `stream` before it returns.
@@ -44,10 +73,15 @@ int train_check_cuts(const char *who, int32_t n_features, const float *cuts, con
 
 // ---- gradients of weighted_log_loss at the current margins ---------------------------------------------------------
 // kFolds: a row with fold[r] == held_out does not train: its (g, h) is (0, 0); everything else is written as for any row
-template <bool kFolds>
+// kSampled: with subsample < 1 a training row is drawn for this tree (sample_row) and an undrawn one is treated like a
+// held-out row.  The draw is indexed by the row's number among the model's TRAINING rows: r itself without folds, else
+// r - (held-out rows before r) = r - held_before[r / 64] - (held-out rows of r's wave in lower lanes); a wave's rows are
+// 64 consecutive ones from a multiple of 64, whatever the grid.  held_before is null for a model that holds nothing out.
+template <bool kFolds, bool kSampled = false>
 __device__ inline void train_gradient_rows(const float *leafsum, const float *labels, int64_t n, float base_margin,
                                            double beta, float *probabilities, long long *gh, int32_t *node_of,
-                                           const uint8_t *fold, int32_t held_out)
+                                           const uint8_t *fold, int32_t held_out, const TrainSampling *sampling = nullptr,
+                                           int64_t tree = 0, const uint32_t *held_before = nullptr)
 {
     for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
          r += static_cast<int64_t>(gridDim.x) * kRowThreads) {
@@ -57,7 +91,15 @@ __device__ inline void train_gradient_rows(const float *leafsum, const float *la
         const double w = beta + y - beta * y;
         const double g = pd * w - y;
         const double h = pd * (1.0 - pd) * w;
-        const bool trains = !kFolds || static_cast<int32_t>(fold[r]) != held_out;
+        bool trains = !kFolds || static_cast<int32_t>(fold[r]) != held_out;
+        if (kSampled && sampling->subsample < 1.0) {   // the same answer in every row of a model
+            int64_t row = r;
+            if (kFolds && held_before != nullptr) {
+                const unsigned long long held = __ballot(!trains);   // lanes past n have left the loop: no bits
+                row = r - held_before[r >> 6] - __popcll(held & ((1ull << (threadIdx.x & 63)) - 1ull));
+            }
+            trains = trains && sample_row(*sampling, tree, row);
+        }
         probabilities[r] = p;
         gh[2 * r] = trains ? static_cast<long long>(rint(g * kQuantum)) : 0ll;
         gh[2 * r + 1] = trains ? static_cast<long long>(rint(h * kQuantum)) : 0ll;
@@ -80,7 +122,8 @@ __device__ inline bool is_built(const int32_t *counts, int32_t node)
 // histograms in LDS, summed with 64-bit LDS adds, flushed with 64-bit global adds (zeros skipped).
 // kFolds: rows with fold[r] == held_out carry (0, 0) and are skipped, and a workgroup none of whose slots has a node
 // to build returns before it reads a row; neither changes a bit of the sums.
-template <bool kFolds>
+// kSampled: a row whose (g, h) is (0, 0) -- an undrawn row -- is skipped as well; it would add zeros.
+template <bool kFolds, bool kSampled = false>
 __device__ inline void train_histogram_group(const uint8_t *bins, const long long *gh, const int32_t *node_of,
                                              const int32_t *counts, const Node *nodes, int64_t n, int32_t nf,
                                              int32_t level, int32_t n_built, int32_t nodes_per_group,
@@ -120,6 +163,7 @@ __device__ inline void train_histogram_group(const uint8_t *bins, const long lon
         const int j = level == 0 ? 0 : ((node - 1) >> 1) - ((1 << (level - 1)) - 1) - j0;
         if (j < 0 || j >= j_count || s_node[j] != node) continue;
         const long long g = gh[2 * r], h = gh[2 * r + 1];
+        if (kSampled && (g | h) == 0ll) continue;
         for (int k = 0; k < f_count; ++k) {
             const int bin = bins[static_cast<int64_t>(f0 + k) * n + r];
             unsigned long long *slot = s_hist + ((k * nodes_per_group + j) * 256 + bin) * 2;
@@ -150,9 +194,14 @@ struct Candidate {            // the best split of one (node, feature)
 // A node whose histogram was not built gets parent - built sibling (exact) first.  Prefix sums by an LDS scan; each
 // thread b - 1 tries boundary b with the missing rows right, then left; the workgroup keeps the largest gain, the
 // lower b on a tie.
+// kSampled: a feature with level_mask[f] == 0 (outside the level's feature set) offers no boundary, like a feature
+// with a single bin; its histogram is still completed by the subtraction and its totals still written, because a
+// later level may include the feature and the node's leaf value comes from the totals of whichever feature wins.
+template <bool kSampled = false>
 __device__ inline void train_split_feature(long long *hist, const int32_t *counts, const Node *nodes,
                                            const int32_t *cut_offsets, int32_t nf, int32_t level,
-                                           const TrainParams &params, Candidate *candidates)
+                                           const TrainParams &params, Candidate *candidates,
+                                           const uint8_t *level_mask = nullptr)
 {
     __shared__ long long s_g[256], s_h[256];
     __shared__ double s_gain[256];
@@ -190,7 +239,7 @@ __device__ inline void train_split_feature(long long *hist, const int32_t *count
     const int b = t + 1, n_bins = cut_offsets[f + 1] - cut_offsets[f] + 1;
     double best = -INFINITY;
     int32_t key = INT32_MAX;
-    if (b < n_bins) {
+    if (b < n_bins && (!kSampled || level_mask[f] != 0)) {
         for (int missing_left = 0; missing_left < 2; ++missing_left) {   // missing right first
             const long long lg = s_g[t] + (missing_left ? missing_g : 0), lh = s_h[t] + (missing_left ? missing_h : 0);
             const double GL = static_cast<double>(lg) / kQuantum, HL = static_cast<double>(lh) / kQuantum;
@@ -300,6 +349,52 @@ __device__ inline void train_partition_rows(const uint8_t *bins, const Node *nod
     __syncthreads();
     for (int i = threadIdx.x; i < next_width; i += kRowThreads)
         if (s_counts[i]) atomicAdd(&counts[next_first + i], s_counts[i]);
+}
+
+// ---- feature sets of one tree: one workgroup of kMaskThreads >= nf threads, thread f = feature f ---------------------
+// mask[d * kTrainFeaturesMax + f] = 1 iff feature f is in the set of level d < max_depth.  The tree's set: the k_tree =
+// max(1, floor(colsample_bytree * nf)) features with the smallest key of the TREE stream, index (tree << 32) | f, ties
+// to the lower f; level d's set: the k_level = max(1, floor(colsample_bylevel * k_tree)) features of the tree's set with
+// the smallest key of the LEVEL stream, index (tree << 32) | (d << 8) | f.  A fraction of 1 takes the whole set, no draw.
+constexpr int kMaskThreads = 128;
+constexpr int kMaskBytes = kTrainMaxDepth * kTrainFeaturesMax;
+
+__device__ inline void train_feature_masks(const TrainSampling &sampling, int64_t tree, int32_t nf, int32_t max_depth,
+                                           uint8_t *mask)
+{
+    __shared__ uint64_t s_key[kTrainFeaturesMax];
+    __shared__ uint8_t s_tree[kTrainFeaturesMax];
+    const int f = threadIdx.x;
+    const bool mine = f < nf;
+    const uint64_t base = static_cast<uint64_t>(tree) << 32;
+    const int k_tree = max(1, static_cast<int>(floor(sampling.colsample_bytree * nf)));
+    bool in_tree = mine;
+    if (sampling.colsample_bytree < 1.0) {
+        const uint64_t key = sample_key(sampling.seed, kPurposeSampleTree, base | static_cast<uint64_t>(f));
+        if (mine) s_key[f] = key;
+        __syncthreads();
+        int rank = 0;
+        for (int g = 0; g < nf; ++g) rank += s_key[g] < key || (s_key[g] == key && g < f);
+        in_tree = mine && rank < k_tree;
+        __syncthreads();
+    }
+    if (mine) s_tree[f] = in_tree;
+    __syncthreads();
+    const int k_level = max(1, static_cast<int>(floor(sampling.colsample_bylevel * k_tree)));
+    for (int d = 0; d < max_depth; ++d) {
+        bool in_level = in_tree;
+        if (sampling.colsample_bylevel < 1.0) {
+            const uint64_t key = sample_key(sampling.seed, kPurposeSampleLevel,
+                                            base | (static_cast<uint64_t>(d) << 8) | static_cast<uint64_t>(f));
+            if (mine) s_key[f] = key;
+            __syncthreads();
+            int rank = 0;
+            for (int g = 0; g < nf; ++g) rank += s_tree[g] && (s_key[g] < key || (s_key[g] == key && g < f));
+            in_level = in_tree && rank < k_level;
+            __syncthreads();
+        }
+        if (mine) mask[d * kTrainFeaturesMax + f] = in_level ? 1 : 0;
+    }
 }
 
 // train.py:fast_custom_error of one row at its margin: 1 for a missed positive, 5 for a false positive

@@ -81,6 +81,39 @@ __global__ __launch_bounds__(256) void ds_train_split_feature_kernel(long long *
     train_split_feature(hist, counts, nodes, cut_offsets, nf, level, params, candidates);
 }
 
+// ---- the same round with row and column subsampling (ds_trainer_set_sampling): the kSampled bodies -------------------
+__global__ __launch_bounds__(kMaskThreads) void ds_train_feature_mask_kernel(TrainSampling sampling, int64_t tree,
+                                                                              int32_t nf, int32_t max_depth,
+                                                                              uint8_t *mask)
+{
+    train_feature_masks(sampling, tree, nf, max_depth, mask);
+}
+
+__global__ __launch_bounds__(kRowThreads) void ds_train_gradient_sampled_kernel(
+    const float *leafsum, const float *labels, int64_t n, float base_margin, double beta, float *probabilities,
+    long long *gh, int32_t *node_of, TrainSampling sampling, int64_t tree)
+{
+    train_gradient_rows<false, true>(leafsum, labels, n, base_margin, beta, probabilities, gh, node_of, nullptr, -1,
+                                     &sampling, tree, nullptr);
+}
+
+__global__ __launch_bounds__(kHistThreads) void ds_train_histogram_sampled_kernel(
+    const uint8_t *bins, const long long *gh, const int32_t *node_of, const int32_t *counts, const Node *nodes,
+    int64_t n, int32_t nf, int32_t level, int32_t n_built, int32_t nodes_per_group, int32_t features_per_group,
+    int32_t feature_groups, unsigned long long *hist)
+{
+    train_histogram_group<false, true>(bins, gh, node_of, counts, nodes, n, nf, level, n_built, nodes_per_group,
+                                       features_per_group, feature_groups, hist, nullptr, -1);
+}
+
+__global__ __launch_bounds__(256) void ds_train_split_feature_sampled_kernel(
+    long long *hist, const int32_t *counts, const Node *nodes, const int32_t *cut_offsets, int32_t nf, int32_t level,
+    TrainParams params, Candidate *candidates, const uint8_t *mask)
+{
+    train_split_feature<true>(hist, counts, nodes, cut_offsets, nf, level, params, candidates,
+                              mask + level * kTrainFeaturesMax);
+}
+
 __global__ __launch_bounds__(64) void ds_train_split_kernel(const Candidate *candidates, Node *nodes, int32_t nf,
                                                              int32_t level, TrainParams params)
 {
@@ -204,6 +237,9 @@ struct ds_trainer {
     ds::DeviceBuffer<ds::Node> nodes;
     ds::DeviceBuffer<ds::Candidate> candidates;   // [2^(max_depth - 1)][nf]: the best split per (node, feature)
     ds::DeviceBuffer<unsigned long long> error;
+    bool sampled = false;                         // ds_trainer_set_sampling with a fraction below 1
+    ds::TrainSampling sampling{1.0, 1.0, 1.0, 0};
+    ds::DeviceBuffer<uint8_t> masks;              // [kTrainMaxDepth][kTrainFeaturesMax]: the feature sets of the round
     std::vector<int32_t> host_offsets;
     ds::Node *pinned_nodes = nullptr;
     unsigned long long *pinned_error = nullptr;
@@ -366,6 +402,28 @@ int ds_trainer_set_eval_device(ds_trainer *trainer, const float *d_features, con
     return set_eval("ds_trainer_set_eval_device", trainer, d_features, true, labels, n);
 }
 
+int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsample_bytree, double colsample_bylevel,
+                            uint64_t sample_seed)
+{
+    DS_REQUIRE(trainer != nullptr, "ds_trainer_set_sampling: trainer is null");
+    const double fractions[3] = {subsample, colsample_bytree, colsample_bylevel};
+    const char *names[3] = {"subsample", "colsample_bytree", "colsample_bylevel"};
+    for (int i = 0; i < 3; ++i)
+        DS_REQUIRE(fractions[i] > 0 && fractions[i] <= 1, "ds_trainer_set_sampling: %s = %g out of range (0, 1]",
+                   names[i], fractions[i]);
+    DS_REQUIRE(trainer->rounds == 0, "ds_trainer_set_sampling: the sampling must be set before the first round");
+    DS_REQUIRE(subsample == 1 || trainer->params.reg_lambda > 0,
+               "ds_trainer_set_sampling: subsample < 1 needs reg_lambda > 0 (a round may draw no row)");
+    const ds::TrainSampling sampling{subsample, colsample_bytree, colsample_bylevel, sample_seed};
+    if (sampling.any() && trainer->masks.ptr == nullptr) {
+        DS_HIP(hipSetDevice(trainer->device));
+        if (int status = trainer->masks.allocate(ds::kMaskBytes); status != DS_OK) return status;
+    }
+    trainer->sampling = sampling;
+    trainer->sampled = sampling.any();
+    return DS_OK;
+}
+
 int ds_gather_rows_device(const float *d_src, int32_t n_features, const int64_t *d_rows, int64_t n_rows, int64_t n_src,
                           float *d_dst, void *stream)
 {
@@ -415,9 +473,18 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
     DS_HIP(hipMemsetAsync(t->nodes.ptr, 0, t->nodes.bytes(), stream));
     DS_HIP(hipMemsetAsync(t->counts.ptr, 0, t->counts.bytes(), stream));
     DS_HIP(hipMemsetAsync(t->error.ptr, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(ds::ds_train_gradient_kernel, dim3(row_grid(t, n)), dim3(ds::kRowThreads), 0, stream,
-                       t->leafsum.ptr, t->labels.ptr, n, t->base_margin, t->params.beta, t->probabilities.ptr,
-                       t->gh.ptr, t->node_of.ptr);
+    if (t->sampled) {   // the feature sets of this tree's levels, then the gradients of the rows drawn for it
+        hipLaunchKernelGGL(ds::ds_train_feature_mask_kernel, dim3(1), dim3(ds::kMaskThreads), 0, stream, t->sampling,
+                           t->rounds, t->nf, depth, t->masks.ptr);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds::ds_train_gradient_sampled_kernel, dim3(row_grid(t, n)), dim3(ds::kRowThreads), 0, stream,
+                           t->leafsum.ptr, t->labels.ptr, n, t->base_margin, t->params.beta, t->probabilities.ptr,
+                           t->gh.ptr, t->node_of.ptr, t->sampling, t->rounds);
+    } else {
+        hipLaunchKernelGGL(ds::ds_train_gradient_kernel, dim3(row_grid(t, n)), dim3(ds::kRowThreads), 0, stream,
+                           t->leafsum.ptr, t->labels.ptr, n, t->base_margin, t->params.beta, t->probabilities.ptr,
+                           t->gh.ptr, t->node_of.ptr);
+    }
     DS_HIP(hipGetLastError());
     for (int32_t level = 0; level < depth; ++level) {
         const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
@@ -430,14 +497,20 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
         // global adds per workgroup) stays a small part
         const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048,
                                                                       (int64_t(t->compute_units) * 4 + groups - 1) / groups));
-        hipLaunchKernelGGL(ds::ds_train_histogram_kernel, dim3(static_cast<unsigned>(chunks), groups),
+        hipLaunchKernelGGL(t->sampled ? ds::ds_train_histogram_sampled_kernel : ds::ds_train_histogram_kernel,
+                           dim3(static_cast<unsigned>(chunks), groups),
                            dim3(ds::kHistThreads), 0, stream, t->bins.ptr, t->gh.ptr, t->node_of.ptr, t->counts.ptr,
                            t->nodes.ptr, n, t->nf, level, n_built, nodes_per_group, features_per_group, feature_groups,
                            reinterpret_cast<unsigned long long *>(t->hist.ptr));
         DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_train_split_feature_kernel, dim3(1u << level, t->nf), dim3(256), 0, stream,
-                           t->hist.ptr, t->counts.ptr, t->nodes.ptr, t->cut_offsets.ptr, t->nf, level, t->params,
-                           t->candidates.ptr);
+        if (t->sampled)
+            hipLaunchKernelGGL(ds::ds_train_split_feature_sampled_kernel, dim3(1u << level, t->nf), dim3(256), 0, stream,
+                               t->hist.ptr, t->counts.ptr, t->nodes.ptr, t->cut_offsets.ptr, t->nf, level, t->params,
+                               t->candidates.ptr, t->masks.ptr);
+        else
+            hipLaunchKernelGGL(ds::ds_train_split_feature_kernel, dim3(1u << level, t->nf), dim3(256), 0, stream,
+                               t->hist.ptr, t->counts.ptr, t->nodes.ptr, t->cut_offsets.ptr, t->nf, level, t->params,
+                               t->candidates.ptr);
         DS_HIP(hipGetLastError());
         hipLaunchKernelGGL(ds::ds_train_split_kernel, dim3(((1u << level) + 63) / 64), dim3(64), 0, stream,
                            t->candidates.ptr, t->nodes.ptr, t->nf, level, t->params);

@@ -13,6 +13,16 @@
 //   error uint64, D = the largest max_depth of the batch.
 // Row r trains in model m iff fold[r] != h_m.  A held-out row carries (g, h) = (0, 0), is skipped by the histogram
 // kernel, is routed through every new tree like any row, and counts in the model's error after the round.
+//
+// Subsampling (ds_trainer_batch_set_sampling; DESIGN.md section 9, "Subsampling"): every model has its own fractions,
+// seed and tree count.  Once a model of the batch samples, a step launches the kSampled instantiations for ALL active
+// models; a model whose fractions are 1 draws nothing in them and grows the trees of the plain ones.  Added state:
+//   sampling     TrainSampling[M]   trees int32[M]: the trees every model has grown before this step (host -> device
+//                                   with the active list, no further sync)
+//   masks        uint8[M][kTrainMaxDepth][kTrainFeaturesMax]  the feature sets of the round, one workgroup per model
+//   held_before  uint32[slots][ceil(n / 64)]  rows of a held-out fold before row 64 w, one slot per fold that a model
+//                                   with subsample < 1 holds out: the draw of row r is indexed by r's number among the
+//                                   model's training rows, so that the model is ds_trainer's on those rows alone
 #include <atomic>
 
 #include "ds_train.h"
@@ -45,6 +55,15 @@ struct BatchView {   // what every kernel of a round gets; model m's part of a p
     unsigned long long *errors;   // stride 1
     int64_t n, hist_stride, candidate_stride;
     int32_t nf, slots;
+};
+
+struct BatchSamplingView {
+    const TrainSampling *sampling;
+    const int32_t *trees;
+    const uint32_t *held_before;   // stride held_stride per slot
+    const int32_t *held_slot;      // per model: its slot of held_before, -1 for none
+    uint8_t *masks;                // stride kMaskBytes
+    int64_t held_stride;
 };
 
 // ---- start of a round: zero the active models' histograms (levels below their own max_depth), heaps, counts, errors -
@@ -86,6 +105,53 @@ __global__ __launch_bounds__(kHistThreads) void ds_batch_histogram_kernel(BatchV
                                 features_per_group, feature_groups,
                                 reinterpret_cast<unsigned long long *>(v.hist + m * v.hist_stride), v.fold,
                                 model.held_out);
+}
+
+// ---- the kSampled forms of the three kernels above, and the feature sets of the round: blockIdx.x = the model -------
+__global__ __launch_bounds__(kMaskThreads) void ds_batch_feature_mask_kernel(BatchView v, BatchSamplingView s)
+{
+    const int32_t m = v.active[blockIdx.x];
+    train_feature_masks(s.sampling[m], s.trees[m], v.nf, v.models[m].params.max_depth,
+                        s.masks + static_cast<int64_t>(m) * kMaskBytes);
+}
+
+__global__ __launch_bounds__(kRowThreads) void ds_batch_gradient_sampled_kernel(BatchView v, BatchSamplingView s)
+{
+    const int32_t m = v.active[blockIdx.y];
+    const BatchModel &model = v.models[m];
+    const int32_t slot = s.held_slot[m];
+    train_gradient_rows<true, true>(v.leafsum + m * v.n, v.labels, v.n, kBatchBaseMargin, model.params.beta,
+                                    v.probabilities + m * v.n, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.fold,
+                                    model.held_out, s.sampling + m, s.trees[m],
+                                    slot >= 0 ? s.held_before + slot * s.held_stride : nullptr);
+}
+
+__global__ __launch_bounds__(kHistThreads) void ds_batch_histogram_sampled_kernel(BatchView v, int32_t level,
+                                                                                   int32_t n_built,
+                                                                                   int32_t nodes_per_group,
+                                                                                   int32_t features_per_group,
+                                                                                   int32_t feature_groups)
+{
+    const int32_t m = v.active[blockIdx.z];
+    const BatchModel &model = v.models[m];
+    if (level >= model.params.max_depth) return;
+    train_histogram_group<true, true>(v.bins, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.counts + int64_t(m) * v.slots,
+                                      v.nodes + int64_t(m) * v.slots, v.n, v.nf, level, n_built, nodes_per_group,
+                                      features_per_group, feature_groups,
+                                      reinterpret_cast<unsigned long long *>(v.hist + m * v.hist_stride), v.fold,
+                                      model.held_out);
+}
+
+__global__ __launch_bounds__(256) void ds_batch_split_feature_sampled_kernel(BatchView v, BatchSamplingView s,
+                                                                              int32_t level)
+{
+    const int32_t m = v.active[blockIdx.z];
+    const BatchModel &model = v.models[m];
+    if (level >= model.params.max_depth) return;
+    train_split_feature<true>(v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots,
+                              v.nodes + int64_t(m) * v.slots, v.cut_offsets, v.nf, level, model.params,
+                              v.candidates + m * v.candidate_stride,
+                              s.masks + static_cast<int64_t>(m) * kMaskBytes + level * kTrainFeaturesMax);
 }
 
 // blockIdx.x = the node's index in its level, blockIdx.y = the feature, blockIdx.z = the model
@@ -156,8 +222,18 @@ struct ds_trainer_batch {
     int32_t *pinned_active = nullptr;
     ds::BatchView view{};
     int compute_units = 256;
+    // subsampling (ds_trainer_batch_set_sampling)
+    bool stepped = false, sampled = false;
+    std::vector<int32_t> tree_count;           // the trees every model has grown
+    ds::DeviceBuffer<ds::TrainSampling> d_sampling;
+    ds::DeviceBuffer<int32_t> d_trees, d_held_slot;
+    ds::DeviceBuffer<uint32_t> d_held_before;
+    ds::DeviceBuffer<uint8_t> masks;
+    int32_t *pinned_trees = nullptr;
+    ds::BatchSamplingView sampling_view{};
     ~ds_trainer_batch()
     {
+        if (pinned_trees) (void)hipHostFree(pinned_trees);
         if (pinned_nodes) (void)hipHostFree(pinned_nodes);
         if (pinned_errors) (void)hipHostFree(pinned_errors);
         if (pinned_active) (void)hipHostFree(pinned_active);
@@ -244,6 +320,7 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
     b->max_depth = depth;
     b->slots = static_cast<int32_t>(heap_nodes(depth));
     b->models = models;
+    b->tree_count.assign(n_models, 0);
     hipDeviceProp_t props;
     if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
         b->compute_units = props.multiProcessorCount;
@@ -360,6 +437,71 @@ int ds_trainer_batch_option(const char *name, int64_t value)
     return DS_OK;
 }
 
+int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractions, const uint64_t *sample_seeds)
+{
+    DS_REQUIRE(batch != nullptr, "ds_trainer_batch_set_sampling: batch is null");
+    DS_REQUIRE(fractions != nullptr, "ds_trainer_batch_set_sampling: fractions is null");
+    DS_REQUIRE(sample_seeds != nullptr, "ds_trainer_batch_set_sampling: sample_seeds is null");
+    ds_trainer_batch *b = batch;
+    const char *names[3] = {"subsample", "colsample_bytree", "colsample_bylevel"};
+    std::vector<ds::TrainSampling> sampling(b->n_models);
+    std::vector<int32_t> held_slot(b->n_models, -1), slot_of_fold(ds::kBatchFoldsMax, -1), slot_folds;
+    bool any = false;
+    for (int32_t m = 0; m < b->n_models; ++m) {
+        const double *f = fractions + 3 * m;
+        for (int i = 0; i < 3; ++i)
+            DS_REQUIRE(f[i] > 0 && f[i] <= 1, "ds_trainer_batch_set_sampling: model %d: %s = %g out of range (0, 1]", m,
+                       names[i], f[i]);
+        DS_REQUIRE(f[0] == 1 || b->models[m].params.reg_lambda > 0,
+                   "ds_trainer_batch_set_sampling: model %d: subsample < 1 needs reg_lambda > 0 (a round may draw no row)",
+                   m);
+        sampling[m] = ds::TrainSampling{f[0], f[1], f[2], sample_seeds[m]};
+        any = any || sampling[m].any();
+        const int32_t held_out = b->models[m].held_out;
+        if (f[0] < 1 && held_out >= 0) {
+            if (slot_of_fold[held_out] < 0) {
+                slot_of_fold[held_out] = static_cast<int32_t>(slot_folds.size());
+                slot_folds.push_back(held_out);
+            }
+            held_slot[m] = slot_of_fold[held_out];
+        }
+    }
+    DS_REQUIRE(!b->stepped, "ds_trainer_batch_set_sampling: the sampling must be set before the first step");
+    if (!any) {   // every fraction is 1: the plain kernels, whatever was set before
+        b->sampled = false;
+        return DS_OK;
+    }
+    DS_HIP(hipSetDevice(b->device));
+    const size_t M = static_cast<size_t>(b->n_models), waves = static_cast<size_t>((b->n + 63) / 64);
+    std::vector<uint32_t> held_before(std::max<size_t>(1, slot_folds.size() * waves), 0u);
+    if (!slot_folds.empty()) {   // rows of every wanted fold before each 64th row, from the folds the batch holds
+        std::vector<uint8_t> fold(static_cast<size_t>(b->n));
+        DS_HIP(hipMemcpy(fold.data(), b->fold.ptr, fold.size(), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> seen(ds::kBatchFoldsMax + 1, 0u);
+        for (size_t r = 0; r < fold.size(); ++r) {
+            if ((r & 63) == 0)
+                for (size_t slot = 0; slot < slot_folds.size(); ++slot)
+                    held_before[slot * waves + (r >> 6)] = seen[slot_folds[slot]];
+            ++seen[fold[r]];
+        }
+    }
+    int status = b->d_sampling.upload(sampling.data(), M);
+    if (status == DS_OK) status = b->d_held_slot.upload(held_slot.data(), M);
+    if (status == DS_OK) status = b->d_held_before.upload(held_before.data(), held_before.size());
+    if (status == DS_OK && b->d_trees.ptr == nullptr) status = b->d_trees.allocate(M);
+    if (status == DS_OK && b->masks.ptr == nullptr) status = b->masks.allocate(M * ds::kMaskBytes);
+    if (status == DS_OK && b->pinned_trees == nullptr &&
+        hipHostMalloc(reinterpret_cast<void **>(&b->pinned_trees), sizeof(int32_t) * M) != hipSuccess) {
+        ds::set_error("ds_trainer_batch_set_sampling: hipHostMalloc failed");
+        status = DS_E_HIP;
+    }
+    if (status != DS_OK) return status;
+    b->sampling_view = ds::BatchSamplingView{b->d_sampling.ptr, b->d_trees.ptr, b->d_held_before.ptr, b->d_held_slot.ptr,
+                                             b->masks.ptr, static_cast<int64_t>(waves)};
+    b->sampled = true;
+    return DS_OK;
+}
+
 int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_t *node_info, float *node_leaf,
                           int64_t *errors)
 {
@@ -381,7 +523,19 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     hipLaunchKernelGGL(ds::ds_batch_clear_kernel, dim3(row_grid(b, v.hist_stride / 2), models), dim3(ds::kRowThreads), 0,
                        stream, v);
     DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_batch_gradient_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream, v);
+    const ds::BatchSamplingView &sv = b->sampling_view;
+    if (b->sampled) {   // every model's own tree count indexes its streams, not the steps of the batch
+        std::memcpy(b->pinned_trees, b->tree_count.data(), sizeof(int32_t) * b->n_models);
+        DS_HIP(hipMemcpyAsync(b->d_trees.ptr, b->pinned_trees, sizeof(int32_t) * b->n_models, hipMemcpyHostToDevice,
+                              stream));
+        hipLaunchKernelGGL(ds::ds_batch_feature_mask_kernel, dim3(models), dim3(ds::kMaskThreads), 0, stream, v, sv);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds::ds_batch_gradient_sampled_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0,
+                           stream, v, sv);
+    } else {
+        hipLaunchKernelGGL(ds::ds_batch_gradient_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream,
+                           v);
+    }
     DS_HIP(hipGetLastError());
     for (int32_t level = 0; level < depth; ++level) {   // to the largest max_depth among the active models
         const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
@@ -393,13 +547,17 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
         // ds_trainer_step's shape with the models counted in: about 4 workgroups per CU in all, each over >= 2048 rows
         const int64_t chunks = capped(std::min<int64_t>((n + 2047) / 2048,
                                                         (int64_t(b->compute_units) * 4 + groups - 1) / groups));
-        hipLaunchKernelGGL(ds::ds_batch_histogram_kernel,
+        hipLaunchKernelGGL(b->sampled ? ds::ds_batch_histogram_sampled_kernel : ds::ds_batch_histogram_kernel,
                            dim3(static_cast<unsigned>(chunks), feature_groups * node_groups, models),
                            dim3(ds::kHistThreads), 0, stream, v, level, n_built, nodes_per_group, features_per_group,
                            feature_groups);
         DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_batch_split_feature_kernel, dim3(1u << level, b->nf, models), dim3(256), 0, stream, v,
-                           level);
+        if (b->sampled)
+            hipLaunchKernelGGL(ds::ds_batch_split_feature_sampled_kernel, dim3(1u << level, b->nf, models), dim3(256), 0,
+                               stream, v, sv, level);
+        else
+            hipLaunchKernelGGL(ds::ds_batch_split_feature_kernel, dim3(1u << level, b->nf, models), dim3(256), 0, stream,
+                               v, level);
         DS_HIP(hipGetLastError());
         hipLaunchKernelGGL(ds::ds_batch_split_kernel, dim3(((1u << level) + 63) / 64, models), dim3(64), 0, stream, v,
                            level);
@@ -420,8 +578,10 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     }
     DS_HIP(hipMemcpyAsync(b->pinned_errors, b->errors.ptr, b->errors.bytes(), hipMemcpyDeviceToHost, stream));
     DS_HIP(hipStreamSynchronize(stream));   // the step's one host sync
+    b->stepped = true;
     for (int32_t a = 0; a < n_active; ++a) {
         const int64_t m = b->pinned_active[a];
+        ++b->tree_count[m];
         for (int64_t i = 0; i < b->slots; ++i) {
             const ds::Node &node = b->pinned_nodes[m * b->slots + i];
             int32_t *info = node_info + (m * b->slots + i) * 4;

@@ -116,6 +116,19 @@ def _real(name, value, positive=False):
     return value
 
 
+def _fraction(name, value):
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number in (0, 1], not {value!r}") from None
+    if not 0 < value <= 1:          # refuses NaN too
+        raise ValueError(f"{name} must be a number in (0, 1], not {value!r}")
+    return value
+
+
+SAMPLING_NAMES = ("subsample", "colsample_bytree", "colsample_bylevel", "sample_seed")
+
+
 def _matrix_and_labels(features, target, what):
     features = np.asarray(features)
     if features.ndim != 2:
@@ -136,7 +149,7 @@ def _matrix_and_labels(features, target, what):
 
 def validate_fit(features, target, eval_features=None, eval_target=None, num_boost_round=1000,
                  early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                 max_bin=256):
+                 max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0):
     """fit's checks (no library needed) -> (features, target, eval_features, eval_target, params) as float32 arrays."""
     features, target = _matrix_and_labels(features, target, "training")
     if (eval_features is None) != (eval_target is None):
@@ -147,22 +160,35 @@ def validate_fit(features, target, eval_features=None, eval_target=None, num_boo
             raise ValueError(f"evaluation features have {eval_features.shape[1]} columns, training features "
                              f"{features.shape[1]}")
     params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
-                                 beta, max_bin)
+                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed)
     return features, target, eval_features, eval_target, params
 
 
 def validate_parameters(num_boost_round=1000, early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0,
-                        reg_lambda=1.0, beta=5.0, max_bin=256):
-    """The parameter checks of fit and fit_device -> params."""
+                        reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
+                        colsample_bylevel=1.0, sample_seed=0):
+    """The parameter checks of fit and fit_device -> params.  subsample, colsample_bytree and colsample_bylevel are
+    fractions in (0, 1] ("Subsampling"); sample_seed in [0, 2^63) seeds their draws and is not the
+    `seed` of the training set and the folds."""
     params = dict(num_boost_round=_positive_int("num_boost_round", num_boost_round),
                   early_stopping_rounds=_positive_int("early_stopping_rounds", early_stopping_rounds),
                   max_depth=_positive_int("max_depth", max_depth, 1, MAX_DEPTH_MAX),
                   eta=_real("eta", eta, positive=True), min_child_weight=_real("min_child_weight", min_child_weight),
                   reg_lambda=_real("reg_lambda", reg_lambda), beta=_real("beta", beta, positive=True),
-                  max_bin=_positive_int("max_bin", max_bin, 2, 256))
+                  max_bin=_positive_int("max_bin", max_bin, 2, 256),
+                  subsample=_fraction("subsample", subsample),
+                  colsample_bytree=_fraction("colsample_bytree", colsample_bytree),
+                  colsample_bylevel=_fraction("colsample_bylevel", colsample_bylevel),
+                  sample_seed=_positive_int("sample_seed", sample_seed, 0, (1 << 63) - 1))
     if params["reg_lambda"] == 0 and params["min_child_weight"] == 0:
         raise ValueError("reg_lambda and min_child_weight cannot both be 0 (an empty child would divide by zero)")
+    if params["reg_lambda"] == 0 and params["subsample"] < 1:
+        raise ValueError("subsample < 1 needs reg_lambda > 0 (a round that draws no row would divide by zero)")
     return params
+
+
+def _samples(params):
+    return any(params[name] < 1 for name in SAMPLING_NAMES[:3])
 
 
 def _device_labels(n, target, what):
@@ -177,7 +203,8 @@ def _device_labels(n, target, what):
 
 def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
                         early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                        max_bin=256, n_features=None):
+                        max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
+                        sample_seed=0):
     """fit_device's checks (no library needed) -> (n, target, n_eval, eval_target, n_features, params): validate_fit
     for matrices in HBM, of which only the shapes are known here."""
     n_features = _device_columns(d_features, n_features)
@@ -196,7 +223,7 @@ def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, e
         if isinstance(array, _lib.DeviceArray) and rows > array.shape[0]:
             raise ValueError(f"{rows} {what} rows exceed the device matrix's {array.shape[0]}")
     params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
-                                 beta, max_bin)
+                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed)
     return n, target, n_eval, eval_target, n_features, params
 
 
@@ -227,8 +254,8 @@ def heap_tree(info, leaf, cuts, cut_offsets):
 
 
 class ForestTrainer:
-    """xgb.train(params={max_depth, eta, min_child_weight}, obj=weighted_log_loss, feval=custom_error,
-    early_stopping_rounds) on the GPU.
+    """xgb.train(params={max_depth, eta, min_child_weight, subsample, colsample_bytree, colsample_bylevel},
+    obj=weighted_log_loss, feval=custom_error, early_stopping_rounds) on the GPU.
 
         model = ForestTrainer().fit(features, target, eval_features, eval_target)
 
@@ -245,10 +272,12 @@ class ForestTrainer:
         self.best_iteration = None
 
     def begin(self, features, target, eval_features=None, eval_target=None, max_depth=5, eta=0.1,
-              min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256):
+              min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
+              colsample_bylevel=1.0, sample_seed=0):
         features, target, eval_features, eval_target, params = validate_fit(
             features, target, eval_features, eval_target, max_depth=max_depth, eta=eta,
-            min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin)
+            min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin, subsample=subsample,
+            colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, sample_seed=sample_seed)
         self.close()
         self.params = params
         self.n, self.n_features = features.shape
@@ -262,6 +291,7 @@ class ForestTrainer:
                                              params["min_child_weight"], params["reg_lambda"], params["beta"],
                                              self.device, ctypes.byref(handle)), "ds_trainer_create")
         self.handle = handle
+        self._set_sampling(params)
         _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
         if eval_features is not None:
             _lib.check(library.ds_trainer_set_eval(self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
@@ -271,8 +301,16 @@ class ForestTrainer:
         self._leaf = np.zeros(slots, np.float32)
         return self
 
+    def _set_sampling(self, params):
+        """The fractions and the seed to the library, when a fraction is below 1 (all 1: nothing to set)."""
+        if _samples(params):
+            _lib.check(_lib.lib().ds_trainer_set_sampling(self.handle, params["subsample"], params["colsample_bytree"],
+                                                          params["colsample_bylevel"], params["sample_seed"]),
+                       "ds_trainer_set_sampling")
+
     def begin_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, max_depth=5,
-                     eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, n_features=None):
+                     eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, n_features=None,
+                     subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0):
         """begin for matrices that already lie in HBM: contiguous float32[n, n_features] DeviceArrays (or addresses,
         with n_features given), complete before the call; labels are host arrays.  The cuts come from
         compute_cuts_device, the bins from the same kernel as begin's, so every later call works as after begin.  The
@@ -280,7 +318,8 @@ class ForestTrainer:
         n, target, n_eval, eval_target, n_features, params = validate_fit_device(
             d_features, n, target, d_eval_features, n_eval, eval_target, max_depth=max_depth, eta=eta,
             min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin,
-            n_features=n_features)
+            n_features=n_features, subsample=subsample, colsample_bytree=colsample_bytree,
+            colsample_bylevel=colsample_bylevel, sample_seed=sample_seed)
         self.close()
         self.params = params
         self.n, self.n_features, self.n_eval = n, n_features, n_eval
@@ -297,6 +336,7 @@ class ForestTrainer:
             params["max_depth"], params["eta"], params["min_child_weight"], params["reg_lambda"], params["beta"],
             self.device, ctypes.byref(handle)), "ds_trainer_create_device")
         self.handle = handle
+        self._set_sampling(params)
         _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
         if n_eval:
             _lib.check(library.ds_trainer_set_eval_device(self.handle, _lib.pointer(d_eval_features),
@@ -310,13 +350,15 @@ class ForestTrainer:
 
     def fit_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
                    early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                   max_bin=256, n_features=None):
+                   max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
+                   sample_seed=0):
         """fit for matrices in HBM (begin_device, then fit's rounds and early stopping)."""
         rounds = validate_fit_device(d_features, n, target, d_eval_features, n_eval, eval_target, num_boost_round,
                                      early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda, beta, max_bin,
-                                     n_features)[5]
+                                     n_features, subsample, colsample_bytree, colsample_bylevel, sample_seed)[5]
         self.begin_device(d_features, n, target, d_eval_features, n_eval, eval_target, max_depth, eta,
-                          min_child_weight, reg_lambda, beta, max_bin, n_features)
+                          min_child_weight, reg_lambda, beta, max_bin, n_features, subsample, colsample_bytree,
+                          colsample_bylevel, sample_seed)
         return self._boost(rounds)
 
     def step(self):
@@ -343,11 +385,12 @@ class ForestTrainer:
 
     def fit(self, features, target, eval_features=None, eval_target=None, num_boost_round=1000,
             early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-            max_bin=256):
+            max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0):
         rounds = validate_fit(features, target, eval_features, eval_target, num_boost_round, early_stopping_rounds,
-                              max_depth, eta, min_child_weight, reg_lambda, beta, max_bin)[4]
+                              max_depth, eta, min_child_weight, reg_lambda, beta, max_bin, subsample, colsample_bytree,
+                              colsample_bylevel, sample_seed)[4]
         self.begin(features, target, eval_features, eval_target, max_depth, eta, min_child_weight, reg_lambda, beta,
-                   max_bin)
+                   max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed)
         return self._boost(rounds)
 
     def _boost(self, rounds):

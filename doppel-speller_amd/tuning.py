@@ -15,32 +15,43 @@ import numpy as np
 
 from . import _lib
 from .forest import ForestModel
-from .train import (_device_columns, _device_labels, _matrix_and_labels, _positive_int, compute_cuts,
+from .train import (SAMPLING_NAMES, _device_columns, _device_labels, _matrix_and_labels, _positive_int, compute_cuts,
                     compute_cuts_device, heap_tree, validate_parameters)
 
 MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
 FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
 PARAMETER_NAMES = ("max_depth", "eta", "min_child_weight", "reg_lambda", "beta")
-_DEFAULTS = {name: inspect.signature(validate_parameters).parameters[name].default for name in PARAMETER_NAMES}
+# the subsampling parameters (train.SAMPLING_NAMES): a parameter set carries them only when some set of its list names one
+_DEFAULTS = {name: inspect.signature(validate_parameters).parameters[name].default
+             for name in PARAMETER_NAMES + SAMPLING_NAMES}
 
 
-def _parameter_set(parameters, what="parameters"):
-    """One dict of the five booster parameters, defaults filled in, checked by validate_parameters."""
+def _names_sampling(sets):
+    return any(isinstance(one, dict) and name in one for one in sets for name in SAMPLING_NAMES)
+
+
+def _parameter_set(parameters, what="parameters", sampling=None):
+    """One dict of the five booster parameters, defaults filled in, checked by validate_parameters; with `sampling`
+    (default: when the dict names one of SAMPLING_NAMES) the four subsampling parameters follow them."""
+    known = PARAMETER_NAMES + SAMPLING_NAMES
     if not isinstance(parameters, dict):
-        raise ValueError(f"{what} must be a dict of {PARAMETER_NAMES}, not {parameters!r}")
-    unknown = set(parameters) - set(PARAMETER_NAMES)
+        raise ValueError(f"{what} must be a dict of {known}, not {parameters!r}")
+    unknown = set(parameters) - set(known)
     if unknown:
-        raise ValueError(f"unknown {what} {sorted(unknown)}; known: {list(PARAMETER_NAMES)}")
+        raise ValueError(f"unknown {what} {sorted(unknown)}; known: {list(known)}")
+    if sampling is None:
+        sampling = _names_sampling([parameters])
     checked = validate_parameters(**dict(_DEFAULTS, **parameters))
-    return {name: checked[name] for name in PARAMETER_NAMES}
+    return {name: checked[name] for name in (known if sampling else PARAMETER_NAMES)}
 
 
 def _parameter_sets(parameters):
     sets = [parameters] if isinstance(parameters, dict) else list(parameters) if parameters is not None else []
     if not sets:
         raise ValueError("parameters must be a parameter dict or a non-empty list of them")
-    sets = [_parameter_set(one) for one in sets]
-    keys = [tuple(one[name] for name in PARAMETER_NAMES) for one in sets]
+    sampling = _names_sampling(sets)
+    sets = [_parameter_set(one, sampling=sampling) for one in sets]
+    keys = [tuple(one.values()) for one in sets]
     if len(set(keys)) != len(keys):
         raise ValueError("parameters holds the same parameter set twice")
     return sets
@@ -50,18 +61,23 @@ def parameter_grid(**lists):
     """The Cartesian product of max_depth, eta, min_child_weight, reg_lambda and beta (a scalar counts as a list of
     one, a parameter left out takes its default) as a list of parameter dicts.  The order is fixed: the parameters
     vary in the order just named, the LAST-named one fastest (itertools.product).  Every set is checked by
-    validate_parameters; a value given twice, which would make two equal sets, is refused."""
-    unknown = set(lists) - set(PARAMETER_NAMES)
+    validate_parameters; a value given twice, which would make two equal sets, is refused.
+    When one of subsample, colsample_bytree, colsample_bylevel and sample_seed is given, the four join the product
+    after beta, in that order, and every dict carries all nine; otherwise the dicts have the five keys alone."""
+    names = PARAMETER_NAMES + SAMPLING_NAMES
+    unknown = set(lists) - set(names)
     if unknown:
-        raise ValueError(f"unknown parameters {sorted(unknown)}; known: {list(PARAMETER_NAMES)}")
+        raise ValueError(f"unknown parameters {sorted(unknown)}; known: {list(names)}")
+    if not _names_sampling([lists]):
+        names = PARAMETER_NAMES
     axes = []
-    for name in PARAMETER_NAMES:
+    for name in names:
         values = lists.get(name, _DEFAULTS[name])
         values = list(values) if isinstance(values, (list, tuple, np.ndarray)) else [values]
         if not values:
             raise ValueError(f"{name} has no values")
         axes.append(values)
-    return _parameter_sets([dict(zip(PARAMETER_NAMES, combination)) for combination in itertools.product(*axes)])
+    return _parameter_sets([dict(zip(names, combination)) for combination in itertools.product(*axes)])
 
 
 def fold_assignment(groups, n_folds, seed=0, n=None):
@@ -135,10 +151,12 @@ def validate_models(models, n_folds):
     if not 1 <= len(models) <= MODELS_MAX:
         raise ValueError(f"a batch takes 1 to {MODELS_MAX} models, not {len(models)}")
     sets, held = [], []
+    sampling = _names_sampling(models)      # some model names a subsampling parameter: every set carries the four
     for m, model in enumerate(models):
         if not isinstance(model, dict):
             raise ValueError(f"model {m} must be a dict, not {model!r}")
-        sets.append(_parameter_set({k: v for k, v in model.items() if k != "held_out"}, f"parameters of model {m}"))
+        sets.append(_parameter_set({k: v for k, v in model.items() if k != "held_out"}, f"parameters of model {m}",
+                                   sampling))
         held.append(_positive_int(f"held_out of model {m}", model.get("held_out", -1), -1, n_folds - 1))
     params = np.array([[one[name] for name in PARAMETER_NAMES] for one in sets], np.float64)
     return np.ascontiguousarray(params), np.array(held, np.int32), sets
@@ -170,7 +188,8 @@ class ForestTrainerBatch:
         batch = ForestTrainerBatch().begin(features, target, fold, models)
         errors = batch.step()            # one round of every model; errors[m] = held-out error, None without a fold
 
-    models: dicts {max_depth, eta, min_child_weight, reg_lambda, beta, held_out}; row r trains in model m iff
+    models: dicts {max_depth, eta, min_child_weight, reg_lambda, beta, held_out} and, optionally, {subsample,
+    colsample_bytree, colsample_bylevel, sample_seed} (every model its own); row r trains in model m iff
     fold[r] != held_out (-1, the default: every row trains).  The cuts are those of the WHOLE matrix, so a model's trees
     are ForestTrainer's on its training rows with those cuts.  step(active) touches only the models with active[m] true.
     trees[m], history[m] (errors; None entries without a fold), model(m, n_trees), margins(m) (all rows),
@@ -224,6 +243,11 @@ class ForestTrainerBatch:
                           _lib.pointer(held_out), self.device, ctypes.byref(handle)),
                    "ds_trainer_batch_create_device" if in_hbm else "ds_trainer_batch_create")
         self.handle = handle
+        if any(one.get(name, 1.0) < 1 for one in sets for name in SAMPLING_NAMES[:3]):
+            fractions = np.array([[one[name] for name in SAMPLING_NAMES[:3]] for one in sets], np.float64)
+            seeds = np.array([one["sample_seed"] for one in sets], np.uint64)
+            _lib.check(library.ds_trainer_batch_set_sampling(self.handle, _lib.pointer(fractions), _lib.pointer(seeds)),
+                       "ds_trainer_batch_set_sampling")
         self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
         slots = (2 << self.max_depth) - 1          # the heaps of every model have the largest max_depth's slots
         self._info = np.zeros((self.n_models, slots, 4), np.int32)
@@ -293,7 +317,8 @@ class ForestTrainerBatch:
 
 class CrossValidation:
     """What cross_validate returns: `results` (DataFrame, one line per parameter set in the given order: the five
-    parameters, best_iteration, error, rounds, fold_errors at the best round), `history[p]` (the summed curve),
+    parameters -- then the four subsampling ones when a set names one --, best_iteration, error, rounds, fold_errors at
+    the best round), `history[p]` (the summed curve),
     `fold_history[p][k]`, `parameters` (the sets), `chosen` (the index of the best set), `best_parameters`,
     `best_iteration`, `folds` (uint8[n]), `timings` (ms: cuts, bin, boost, refit, total) and, with refit, `model`.
     tune_model_parameters adds `rows` and `feature_importance`."""
@@ -340,7 +365,8 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     n_folds models, model k holding fold k out, all stepped together in batches of whole sets.  A set is stepped until
     round - best >= early_stopping_rounds on its SUMMED curve or until num_boost_round; then its models go inactive
     while other sets continue.  models_per_batch=None sizes the batches from the free HBM; the result does not depend
-    on it.  The cuts are computed once, the bins once per batch.  refit: the chosen set is trained on ALL rows for
+    on it.  The cuts are computed once, the bins once per batch.  A set with subsampling parameters uses its
+    sample_seed in every fold.  refit: the chosen set is trained on ALL rows for
     best_iteration + 1 rounds; with the whole matrix's cuts that is ForestTrainer().fit(features, target,
     num_boost_round=best_iteration + 1, **best_parameters), bit for bit."""
     started = time.perf_counter()

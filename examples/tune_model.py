@@ -8,7 +8,10 @@
 It prints the `results` table (one line per parameter set: the out-of-fold custom error at its best round), the chosen
 set and the stages' times.
 
-    python examples/tune_model.py [n_truth] [n_queries] [n_folds]
+    python examples/tune_model.py [--subsample 0.5,1] [--colsample-bytree 0.5,1] [n_truth] [n_queries] [n_folds]
+
+--subsample and --colsample-bytree take comma-separated fractions in (0, 1] and add them to the grid as further axes
+(row and column subsampling, ForestTrainer's parameters of those names); without them the grid is the plain one.
 """
 import os
 import sys
@@ -20,12 +23,14 @@ import doppel_speller_amd as ds  # noqa: E402
 from doppel_speller_amd import synth  # noqa: E402
 
 
-def main(n_truth=20000, n_queries=4000, n_folds=5):
+def main(n_truth=20000, n_queries=4000, n_folds=5, subsample=None, colsample_bytree=None):
     w = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     truth_titles = synth._to_strings(w.t_flat, w.t_off)
     train_titles = synth._to_strings(w.q_flat, w.q_off)
     train_ids = np.where(w.actual_row >= 0, w.title_id[np.maximum(w.actual_row, 0)], -1)
-    grid = ds.parameter_grid(max_depth=[3, 5], eta=[0.1, 0.3], beta=[2.0, 5.0])
+    sampling = {name: values for name, values in (("subsample", subsample), ("colsample_bytree", colsample_bytree))
+                if values}
+    grid = ds.parameter_grid(max_depth=[3, 5], eta=[0.1, 0.3], beta=[2.0, 5.0], **sampling)
     tuned = ds.tune_model_parameters(truth_titles, w.title_id, train_titles, train_ids, grid, n_folds=n_folds,
                                      transform=False, num_boost_round=300, early_stopping_rounds=30)
     print(tuned.results.to_string())
@@ -35,5 +40,21 @@ def main(n_truth=20000, n_queries=4000, n_folds=5):
     return tuned
 
 
+def _arguments(argv):
+    """(positional arguments, {option: list of fractions}) of the command line."""
+    positional, options = [], {}
+    argv = list(argv)
+    while argv:
+        argument = argv.pop(0)
+        if argument in ("--subsample", "--colsample-bytree"):
+            if not argv:
+                raise SystemExit(f"{argument} needs a comma-separated list of fractions")
+            options[argument[2:].replace("-", "_")] = [float(value) for value in argv.pop(0).split(",")]
+        else:
+            positional.append(int(argument))
+    return positional, options
+
+
 if __name__ == "__main__":
-    main(*(int(argument) for argument in sys.argv[1:4]))
+    numbers, lists = _arguments(sys.argv[1:])
+    main(*numbers[:3], **lists)

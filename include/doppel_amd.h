@@ -473,6 +473,23 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
  * (feature-major, 255 = missing) and the evaluation margins float[n_eval]. */
 int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, int64_t *gradients, uint8_t *bins,
                     float *eval_margins);
+/* Row and column subsampling ("Subsampling"), valid only before the first ds_trainer_step.  The
+ * three fractions lie in (0, 1]; all 1 (the state after create) runs the unsampled kernels.  The draws come from the
+ * streams of "Randomness" below with seed = sample_seed, the first kept output x of a stream, and t = the trees grown so
+ * far: purpose 3 (DS_SAMPLE_PURPOSE_ROW), index (t << 32) | r: training row r trains in tree t iff
+ * (x >> 11) * 2^-53 < subsample, r counted among the rows that train (in a batch: the rows outside the model's held-out
+ * fold, in row order); purpose 4 (DS_SAMPLE_PURPOSE_TREE), index (t << 32) | f: the tree uses the
+ * max(1, floor(colsample_bytree * n_features)) features with the smallest x, ties to the lower f; purpose 5
+ * (DS_SAMPLE_PURPOSE_LEVEL), index (t << 32) | (d << 8) | f: level d uses the max(1, floor(colsample_bylevel * k_tree))
+ * features of the tree's set with the smallest x.  A fraction of 1 draws nothing.  An undrawn row is a held-out row for
+ * that tree: gradient and hessian 0 (also in ds_trainer_read), in no histogram, routed through the tree.  A feature
+ * outside a level's set offers no split there.  DS_E_ARG for a null trainer, a fraction outside (0, 1], a call after a
+ * step, or subsample < 1 with reg_lambda = 0; a null trainer is refused before any device is touched. */
+#define DS_SAMPLE_PURPOSE_ROW 3
+#define DS_SAMPLE_PURPOSE_TREE 4
+#define DS_SAMPLE_PURPOSE_LEVEL 5
+int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsample_bytree, double colsample_bylevel,
+                            uint64_t sample_seed);
 
 /* ---- the train-model step without a host copy of the feature matrix ("One call") ----------------
  * ds_feature_cuts_device: compute_cuts of a contiguous float32[n][n_features] matrix in HBM, bit-identical to the host
@@ -541,6 +558,14 @@ int ds_trainer_batch_read(ds_trainer_batch *batch, int32_t model, float *margins
  * n * n_features + 5 n shared, and per model 28 n + (2^max_depth - 1) * n_features * 4096 + a few KiB.  -1 for
  * arguments outside the limits above. */
 int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth);
+/* ds_trainer_set_sampling for every model of a batch, valid only before the first ds_trainer_batch_step:
+ * fractions[3m .. 3m + 3) = subsample, colsample_bytree, colsample_bylevel of model m, sample_seeds[m] its seed.  Every
+ * model counts its own trees: a step in which it is inactive does not advance its streams.  A model's draws are those of
+ * ds_trainer on its training rows alone, so are its trees.  Models with and without sampling share the launches of a
+ * step, which keeps its one host sync; with every fraction 1 the unsampled kernels run.  Adds under 1 KiB per model, and
+ * n / 16 bytes per fold that a model with subsample < 1 holds out.  DS_E_ARG as for ds_trainer_set_sampling, with the
+ * model named. */
+int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractions, const uint64_t *sample_seeds);
 /* For tests: ds_trainer_batch_option("max_blocks", b) caps every grid of this stage that runs over rows at b workgroups,
  * which stride beyond it (0: back to the default).  The results do not depend on it. */
 int ds_trainer_batch_option(const char *name, int64_t value);
