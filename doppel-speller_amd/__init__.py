@@ -33,6 +33,9 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         sets are boosters of one batch on the device (ForestTrainerBatch), sharing bins, launches and the host sync
     tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters)   -> the same
         from raw titles, folds by train title, the feature matrix kept in HBM (this project's own)
+    ForestTrainer.fit(..., eval_metrics=("auc", "logloss")), cross_validate(..., metrics=("auc",), select_by="auc")   ->
+        the reference's per-round train-auc / evaluation-auc log and the objective's own loss, computed on the device from
+        the margins; roc_auc(scores, target) / auc_counts(scores, target) for any score vector (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -50,8 +53,8 @@ from .prediction import (DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS, LINK_COLUMNS, RA
                          EXPLAIN_COLUMNS, Candidates, Prediction, duplicate_frame, predictions_accuracy,
                          top_contributions, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
-from .train import (ForestTrainer, TrainModelResult, compute_cuts, compute_cuts_device,  # noqa: F401
-                    evaluation_error_matrix, train_model)
+from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
+                    evaluation_error_matrix, roc_auc, train_model)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -10,7 +10,7 @@ _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
             "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
-            "ds_duplicates.hip", "ds_contributions.hip")
+            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip")
 _lib = None
 
 
@@ -195,6 +195,14 @@ def _declare(handle):
         "ds_trainer_batch_read": [p, c.c_int32, p, p, p, p],
         "ds_trainer_batch_option": [c.c_char_p, c.c_int64],
         "ds_trainer_batch_set_sampling": [p, p, p],
+        "ds_auc_device": [p, p, c.c_int64, p, p],
+        "ds_auc": [p, p, c.c_int64, p, c.c_int],
+        "ds_weighted_logloss_device": [p, p, c.c_int64, c.c_double, p, p],
+        "ds_metrics_option": [c.c_char_p, c.c_int64],
+        "ds_trainer_set_metrics": [p, c.c_uint32],
+        "ds_trainer_metrics": [p, p],
+        "ds_trainer_batch_set_metrics": [p, c.c_uint32],
+        "ds_trainer_batch_metrics": [p, p],
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
@@ -218,7 +226,8 @@ def _declare(handle):
     # an older library named by DS_LIBRARY for an A/B measurement: entry points added since are simply absent
     stale_allowed = os.environ.get("DS_ALLOW_STALE_LIBRARY") == "1"
     returns_int64 = {"ds_remaining_pairs_counts_size": [c.c_int64],
-                     "ds_trainer_batch_bytes": [c.c_int64, c.c_int32, c.c_int32, c.c_int32]}
+                     "ds_trainer_batch_bytes": [c.c_int64, c.c_int32, c.c_int32, c.c_int32],
+                     "ds_trainer_batch_metrics_bytes": [c.c_int64, c.c_int32, c.c_int32]}
     returns_nothing = {name: [p] for name in (
         "ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy",
         "ds_trainer_destroy", "ds_query_space_destroy", "ds_trainer_batch_destroy")}
@@ -253,7 +262,9 @@ EXPORTED_SYMBOLS = (
     "ds_forest_cover_set", "ds_forest_cover_read", "ds_forest_cover_clear", "ds_forest_option",
     "ds_forest_contributions_device", "ds_forest_contributions", "ds_best_pairs_device", "ds_trainer_batch_create",
     "ds_trainer_batch_create_device", "ds_trainer_batch_destroy", "ds_trainer_batch_step", "ds_trainer_batch_read",
-    "ds_trainer_batch_bytes", "ds_trainer_batch_option", "ds_trainer_set_sampling", "ds_trainer_batch_set_sampling")
+    "ds_trainer_batch_bytes", "ds_trainer_batch_option", "ds_trainer_set_sampling", "ds_trainer_batch_set_sampling",
+    "ds_auc_device", "ds_auc", "ds_weighted_logloss_device", "ds_metrics_option", "ds_trainer_set_metrics",
+    "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes")
 
 
 def lib():

@@ -4,6 +4,7 @@
 // Every comparison is made on integer keys, never on floats, so denormals and infinities cannot depend on a float mode:
 //   key(x) = 0xFFFFFFFF for a NaN (no other value maps there: NaNs sort last), else with -0.0 read as +0.0 the bits of
 //   x with all bits flipped when the sign is set and only the sign bit flipped otherwise (ascending keys = ascending x).
+// The key and the sort (phase 2) live in ds_radix.h, which the metrics (ds_metrics.hip) include as well.
 //
 // Per group of columns, one launch per phase, no workgroup waits for another:
 //   1. ds_cuts_key_kernel      row tiles of 64 rows through LDS -> column-major keys[g][n]; per column the number m of
@@ -28,7 +29,7 @@
 #include <algorithm>
 #include <atomic>
 
-#include "ds_common.h"
+#include "ds_radix.h"
 
 namespace ds {
 
@@ -36,29 +37,6 @@ constexpr int kCutsFeaturesMax = 96;     // = kTrainFeaturesMax
 constexpr int kCutsMax = 254;            // = kTrainCutsMax
 constexpr int kKeyTileRows = 64;
 constexpr int kKeyThreads = 256;
-constexpr int kSortThreads = 256;
-constexpr int kSortWaves = kSortThreads / 64;
-constexpr int kSortTile = 8192;          // keys of one column per workgroup and pass
-constexpr int kScanThreads = 1024;
-
-__device__ inline uint32_t cut_key(uint32_t bits)
-{
-    if ((bits & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;   // NaN
-    if (bits == 0x80000000u) bits = 0u;                            // -0.0 counts as +0.0
-    return (bits & 0x80000000u) ? ~bits : bits ^ 0x80000000u;
-}
-
-__device__ inline uint32_t cut_value_bits(uint32_t key) { return (key & 0x80000000u) ? key ^ 0x80000000u : ~key; }
-
-// Is the digit of `pass` the same in every key of the column, and in which of the two buffers do the column's keys
-// lie before that pass (1: the second one)?
-__device__ inline bool pass_skipped(uint32_t differing, int pass) { return ((differing >> (8 * pass)) & 0xffu) == 0u; }
-__device__ inline int passes_done(uint32_t differing, int pass)
-{
-    int done = 0;
-    for (int p = 0; p < pass; ++p) done += pass_skipped(differing, p) ? 0 : 1;
-    return done;
-}
 
 // ---- 1. keys ---------------------------------------------------------------------------------------------------------
 // Wave w of a workgroup owns the columns w, w + 4, ... of the group, lane l row l of the tile: a column's keys of a
@@ -110,127 +88,7 @@ __global__ __launch_bounds__(kKeyThreads) void ds_cuts_key_kernel(const uint32_t
     }
 }
 
-// ---- 2. the radix sort -------------------------------------------------------------------------------------------------
-// The lanes of the wave that are valid and hold the same 8-bit digit as this lane (meaningless for an invalid lane).
-__device__ inline unsigned long long digit_peers(uint32_t digit, bool valid)
-{
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (digit >> b) & 1u;
-        const unsigned long long set = __ballot(valid && bit);
-        peers &= bit ? set : ~set;
-    }
-    return peers;
-}
-
-__global__ __launch_bounds__(kSortThreads) void ds_cuts_count_kernel(const uint32_t *keys_a, const uint32_t *keys_b,
-                                                                      int64_t n, int32_t pass, const uint32_t *col_or,
-                                                                      const uint32_t *col_and, uint32_t *table,
-                                                                      int64_t tiles)
-{
-    __shared__ uint32_t s_hist[256];
-    const int col = blockIdx.y, lane = threadIdx.x & 63;
-    const uint32_t differing = col_or[col] ^ col_and[col];
-    if (pass_skipped(differing, pass)) return;
-    const uint32_t *src = ((passes_done(differing, pass) & 1) ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
-    s_hist[threadIdx.x] = 0u;
-    __syncthreads();
-    const int64_t begin = static_cast<int64_t>(blockIdx.x) * kSortTile, end = min(n, begin + kSortTile);
-    for (int64_t base = begin; base < end; base += kSortThreads) {
-        const int64_t i = base + threadIdx.x;
-        const bool valid = i < end;
-        const uint32_t digit = valid ? (src[i] >> (8 * pass)) & 0xffu : 0u;
-        const unsigned long long peers = digit_peers(digit, valid);
-        if (valid && lane == __ffsll(static_cast<long long>(peers)) - 1) atomicAdd(&s_hist[digit], __popcll(peers));
-    }
-    __syncthreads();
-    table[(static_cast<int64_t>(col) * 256 + threadIdx.x) * tiles + blockIdx.x] = s_hist[threadIdx.x];
-}
-
-// Exclusive prefix of `value` over the kScanThreads threads of a workgroup, and the total.
-__device__ inline uint32_t block_exclusive(uint32_t value, uint32_t *s_waves, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inclusive = value;
-    for (int offset = 1; offset < 64; offset <<= 1) {
-        const uint32_t other = __shfl_up(inclusive, offset);
-        if (lane >= offset) inclusive += other;
-    }
-    __syncthreads();   // the previous call's wave sums have been read
-    if (lane == 63) s_waves[wave] = inclusive;
-    __syncthreads();
-    uint32_t before = 0u;
-    total = 0u;
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const uint32_t sum = s_waves[w];
-        before += w < wave ? sum : 0u;
-        total += sum;
-    }
-    return before + inclusive - value;
-}
-
-// table[column][digit][tile] -> the first position of (digit, tile) in the column's next buffer
-__global__ __launch_bounds__(kScanThreads) void ds_cuts_scan_kernel(uint32_t *table, int64_t tiles, int32_t pass,
-                                                                     const uint32_t *col_or, const uint32_t *col_and)
-{
-    __shared__ uint32_t s_waves[kScanThreads / 64];
-    const int col = blockIdx.x;
-    if (pass_skipped(col_or[col] ^ col_and[col], pass)) return;
-    uint32_t *mine = table + static_cast<int64_t>(col) * 256 * tiles;
-    const int64_t count = 256 * tiles;
-    uint32_t running = 0u;
-    for (int64_t base = 0; base < count; base += kScanThreads) {
-        const int64_t i = base + threadIdx.x;
-        const uint32_t value = i < count ? mine[i] : 0u;
-        uint32_t total;
-        const uint32_t before = block_exclusive(value, s_waves, total);
-        if (i < count) mine[i] = running + before;
-        running += total;
-    }
-}
-
-__global__ __launch_bounds__(kSortThreads) void ds_cuts_scatter_kernel(uint32_t *keys_a, uint32_t *keys_b, int64_t n,
-                                                                        int32_t pass, const uint32_t *col_or,
-                                                                        const uint32_t *col_and, const uint32_t *table,
-                                                                        int64_t tiles)
-{
-    __shared__ uint32_t s_next[256];                    // the next position of each digit for this workgroup
-    __shared__ uint32_t s_wave_count[kSortWaves][256];  // keys of each digit in each wave of the current 256 keys
-    const int col = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t differing = col_or[col] ^ col_and[col];
-    if (pass_skipped(differing, pass)) return;
-    const bool from_b = passes_done(differing, pass) & 1;
-    const uint32_t *src = (from_b ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
-    uint32_t *dst = (from_b ? keys_a : keys_b) + static_cast<int64_t>(col) * n;
-    s_next[threadIdx.x] = table[(static_cast<int64_t>(col) * 256 + threadIdx.x) * tiles + blockIdx.x];
-    for (int w = 0; w < kSortWaves; ++w) s_wave_count[w][threadIdx.x] = 0u;
-    __syncthreads();
-    const int64_t begin = static_cast<int64_t>(blockIdx.x) * kSortTile, end = min(n, begin + kSortTile);
-    for (int64_t base = begin; base < end; base += kSortThreads) {
-        const int64_t i = base + threadIdx.x;
-        const bool valid = i < end;
-        const uint32_t key = valid ? src[i] : 0u;
-        const uint32_t digit = (key >> (8 * pass)) & 0xffu;
-        const unsigned long long peers = digit_peers(digit, valid);
-        const uint32_t rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0u) s_wave_count[wave][digit] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            uint32_t position = s_next[digit] + rank;
-            for (int w = 0; w < kSortWaves; ++w) position += w < wave ? s_wave_count[w][digit] : 0u;
-            if (position < n) dst[position] = key;   // always true for counts of the same keys
-        }
-        __syncthreads();
-        uint32_t sum = 0u;
-        for (int w = 0; w < kSortWaves; ++w) {
-            sum += s_wave_count[w][threadIdx.x];
-            s_wave_count[w][threadIdx.x] = 0u;
-        }
-        s_next[threadIdx.x] += sum;
-        __syncthreads();
-    }
-}
+// ---- 2. the radix sort: ds_radix.h ----------------------------------------------------------------------------------
 
 // ---- 3. the cuts of a sorted column ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(kScanThreads) void ds_cuts_pick_kernel(const uint32_t *keys_a, const uint32_t *keys_b,
@@ -349,17 +207,8 @@ int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_feature
                            reinterpret_cast<const uint32_t *>(d_features), n, n_features, c0, g, keys_a.ptr, col_m, col_or,
                            col_and);
         DS_HIP(hipGetLastError());
-        for (int32_t pass = 0; pass < 4; ++pass) {
-            hipLaunchKernelGGL(ds::ds_cuts_count_kernel, dim3(static_cast<unsigned>(tiles), g), dim3(ds::kSortThreads), 0,
-                               s, keys_a.ptr, keys_b.ptr, n, pass, col_or, col_and, table.ptr, tiles);
-            DS_HIP(hipGetLastError());
-            hipLaunchKernelGGL(ds::ds_cuts_scan_kernel, dim3(g), dim3(ds::kScanThreads), 0, s, table.ptr, tiles, pass,
-                               col_or, col_and);
-            DS_HIP(hipGetLastError());
-            hipLaunchKernelGGL(ds::ds_cuts_scatter_kernel, dim3(static_cast<unsigned>(tiles), g), dim3(ds::kSortThreads),
-                               0, s, keys_a.ptr, keys_b.ptr, n, pass, col_or, col_and, table.ptr, tiles);
-            DS_HIP(hipGetLastError());
-        }
+        if (int sorted = ds::radix_sort_columns(s, keys_a.ptr, keys_b.ptr, n, g, col_or, col_and, table.ptr); sorted != DS_OK)
+            return sorted;
         hipLaunchKernelGGL(ds::ds_cuts_pick_kernel, dim3(g), dim3(ds::kScanThreads), 0, s, keys_a.ptr, keys_b.ptr, n,
                            col_or, col_and, col_m, max_bin, cut_table.ptr + static_cast<size_t>(c0) * ds::kCutsMax,
                            cut_counts.ptr + c0);

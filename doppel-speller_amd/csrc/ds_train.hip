@@ -14,6 +14,7 @@
 // schedule and from run to run.
 // The rule's device code lives in ds_train.h, shared with the batched trainer (ds_train_batch.hip); the kernels here
 // run it for one model.
+#include "ds_metrics.h"
 #include "ds_train.h"
 
 namespace ds {
@@ -244,8 +245,18 @@ struct ds_trainer {
     ds::Node *pinned_nodes = nullptr;
     unsigned long long *pinned_error = nullptr;
     int compute_units = 256;
+    // per-round metrics (ds_trainer_set_metrics): column 0 = the training set, column 1 = the evaluation set
+    uint32_t metric_flags = 0;
+    ds::DeviceBuffer<int32_t> metric_rows;                  // per set: its negative rows, then its positive rows
+    ds::DeviceBuffer<ds::MetricColumn> metric_columns;      // [2]
+    ds::DeviceBuffer<unsigned long long> metric_counters;   // [2][kMetricCounters]
+    ds::MetricScratch metric_scratch;                       // sized for the set with more negatives
+    ds::MetricColumn metric_host[2]{};
+    unsigned long long *pinned_metrics = nullptr;
+    int64_t metric_cache[2][6];
     ~ds_trainer()
     {
+        if (pinned_metrics) (void)hipHostFree(pinned_metrics);
         if (pinned_nodes) (void)hipHostFree(pinned_nodes);
         if (pinned_error) (void)hipHostFree(pinned_error);
         if (stream) (void)hipStreamDestroy(stream);
@@ -338,6 +349,7 @@ int set_eval(const char *who, ds_trainer *trainer, const float *features, bool i
     DS_REQUIRE(trainer && features && labels, "%s: null argument", who);
     DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
     DS_REQUIRE(trainer->rounds == 0, "%s: the evaluation set must be given before the first round", who);
+    DS_REQUIRE(trainer->metric_flags == 0, "%s: the evaluation set must be given before ds_trainer_set_metrics", who);
     for (int64_t r = 0; r < n; ++r)
         DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "%s: label %lld is not 0 or 1", who, (long long)r);
     DS_HIP(hipSetDevice(trainer->device));
@@ -382,6 +394,7 @@ void ds_trainer_destroy(ds_trainer *trainer)
 int ds_trainer_set_labels(ds_trainer *trainer, const float *labels)
 {
     DS_REQUIRE(trainer && labels, "ds_trainer_set_labels: null argument");
+    DS_REQUIRE(trainer->metric_flags == 0, "ds_trainer_set_labels: the labels must be set before ds_trainer_set_metrics");
     for (int64_t r = 0; r < trainer->n; ++r)
         DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "ds_trainer_set_labels: label %lld is not 0 or 1", (long long)r);
     DS_HIP(hipSetDevice(trainer->device));
@@ -421,6 +434,74 @@ int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsam
     }
     trainer->sampling = sampling;
     trainer->sampled = sampling.any();
+    return DS_OK;
+}
+
+int ds_trainer_set_metrics(ds_trainer *trainer, uint32_t flags)
+{
+    DS_REQUIRE(trainer != nullptr, "ds_trainer_set_metrics: trainer is null");
+    DS_REQUIRE((flags & ~(ds::kMetricAuc | ds::kMetricLogloss)) == 0u, "ds_trainer_set_metrics: unknown bits in flags = %u",
+               flags);
+    DS_REQUIRE(trainer->rounds == 0, "ds_trainer_set_metrics: the metrics must be set before the first round");
+    ds_trainer *t = trainer;
+    for (int set = 0; set < 2; ++set)
+        for (int i = 0; i < 6; ++i) t->metric_cache[set][i] = -1;
+    if (flags == 0u) {
+        t->metric_flags = 0u;
+        return DS_OK;
+    }
+    DS_REQUIRE(t->has_labels, "ds_trainer_set_metrics: no labels (ds_trainer_set_labels)");
+    DS_HIP(hipSetDevice(t->device));
+    DS_HIP(hipStreamSynchronize(t->stream));
+    // the lists of negative and positive rows of both sets, from the labels the trainer holds
+    const int64_t sizes[2] = {t->n, t->n_eval};
+    const float *d_labels[2] = {t->labels.ptr, t->eval_labels.ptr};
+    const float *d_scores[2] = {t->leafsum.ptr, t->eval_leafsum.ptr};
+    std::vector<int32_t> rows(static_cast<size_t>(t->n + t->n_eval));
+    std::vector<float> labels;
+    int64_t first[2] = {0, t->n}, negatives[2] = {0, 0};
+    for (int set = 0; set < 2; ++set) {
+        labels.resize(static_cast<size_t>(sizes[set]));
+        if (sizes[set] > 0)
+            DS_HIP(hipMemcpy(labels.data(), d_labels[set], sizeof(float) * sizes[set], hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < sizes[set]; ++r) negatives[set] += labels[r] == 0.f ? 1 : 0;
+        int64_t at_neg = first[set], at_pos = first[set] + negatives[set];
+        for (int64_t r = 0; r < sizes[set]; ++r) rows[labels[r] == 0.f ? at_neg++ : at_pos++] = static_cast<int32_t>(r);
+    }
+    const int64_t n_keys = (flags & ds::kMetricAuc) ? std::max(negatives[0], negatives[1]) : 0;
+    if (int status = check_free(4 * int64_t(rows.size()) + ds::MetricScratch::bytes(n_keys, 1), "ds_trainer_set_metrics");
+        status != DS_OK)
+        return status;
+    int status = t->metric_rows.upload(rows.data(), rows.size());
+    if (status == DS_OK) status = t->metric_columns.allocate(2);
+    if (status == DS_OK) status = t->metric_counters.allocate(2 * ds::kMetricCounters);
+    if (status == DS_OK) status = t->metric_scratch.allocate(n_keys, 1);
+    if (status == DS_OK && t->pinned_metrics == nullptr &&
+        hipHostMalloc(reinterpret_cast<void **>(&t->pinned_metrics), sizeof(unsigned long long) * 2 * ds::kMetricCounters) !=
+            hipSuccess) {
+        ds::set_error("ds_trainer_set_metrics: hipHostMalloc failed");
+        status = DS_E_HIP;
+    }
+    if (status != DS_OK) return status;
+    for (int set = 0; set < 2; ++set) {
+        const int32_t *list = t->metric_rows.ptr + first[set];
+        t->metric_host[set] = ds::MetricColumn{d_scores[set], list, list + negatives[set],
+                                               static_cast<int32_t>(negatives[set]),
+                                               static_cast<int32_t>(sizes[set] - negatives[set]), t->base_margin, 0,
+                                               t->params.beta};
+    }
+    DS_HIP(hipMemcpy(t->metric_columns.ptr, t->metric_host, sizeof(t->metric_host), hipMemcpyHostToDevice));
+    DS_HIP(hipMemset(t->metric_counters.ptr, 0, t->metric_counters.bytes()));
+    t->metric_flags = flags;
+    return DS_OK;
+}
+
+int ds_trainer_metrics(ds_trainer *trainer, int64_t out[2][6])
+{
+    DS_REQUIRE(trainer && out, "ds_trainer_metrics: null argument");
+    for (int set = 0; set < 2; ++set)
+        for (int i = 0; i < 6; ++i)
+            out[set][i] = trainer->metric_flags && trainer->rounds > 0 ? trainer->metric_cache[set][i] : -1;
     return DS_OK;
 }
 
@@ -527,6 +608,19 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
     }
     DS_HIP(hipMemcpyAsync(t->pinned_nodes, t->nodes.ptr, sizeof(ds::Node) * slots, hipMemcpyDeviceToHost, stream));
     DS_HIP(hipMemcpyAsync(t->pinned_error, t->error.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (t->metric_flags) {   // over the margins the partition and eval kernels have just written
+        for (int set = 0; set < (t->n_eval > 0 ? 2 : 1); ++set) {
+            const ds::MetricColumn &column = t->metric_host[set];
+            if (int status = ds::metrics_enqueue(stream, t->compute_units, t->metric_flags, t->metric_columns.ptr + set,
+                                                 nullptr, 1, column.n_neg, column.n_pos,
+                                                 int64_t(column.n_neg) + column.n_pos, t->metric_scratch,
+                                                 t->metric_counters.ptr + set * ds::kMetricCounters, 0);
+                status != DS_OK)
+                return status;
+        }
+        DS_HIP(hipMemcpyAsync(t->pinned_metrics, t->metric_counters.ptr, t->metric_counters.bytes(),
+                              hipMemcpyDeviceToHost, stream));
+    }
     DS_HIP(hipStreamSynchronize(stream));   // the round's one host sync
     for (int64_t i = 0; i < slots; ++i) {
         const ds::Node &node = t->pinned_nodes[i];
@@ -537,6 +631,10 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
         node_leaf[i] = node.leaf;
     }
     if (eval_error) *eval_error = t->n_eval > 0 ? static_cast<int64_t>(*t->pinned_error) : -1;
+    if (t->metric_flags)
+        for (int set = 0; set < (t->n_eval > 0 ? 2 : 1); ++set)
+            ds::metrics_row(t->metric_flags, t->pinned_metrics + set * ds::kMetricCounters, t->metric_host[set].n_neg,
+                            t->metric_host[set].n_pos, t->metric_cache[set]);
     ++t->rounds;
     return DS_OK;
 }

@@ -23,8 +23,16 @@
 //   held_before  uint32[slots][ceil(n / 64)]  rows of a held-out fold before row 64 w, one slot per fold that a model
 //                                   with subsample < 1 holds out: the draw of row r is indexed by r's number among the
 //                                   model's training rows, so that the model is ds_trainer's on those rows alone
+//
+// Metrics (ds_trainer_batch_set_metrics; DESIGN.md section 9, "Metrics"): AUC and log loss of every active model over the
+// rows of its held-out fold, by the kernels of ds_metrics.hip with the active models in blockIdx.y.  Added state:
+//   metric_rows     int32[<= n]       per fold that a model holds out: its negative rows, then its positive rows
+//   metric_columns  MetricColumn[M]   model m's margins with the lists of its held-out fold
+//   metric_scratch                    two key buffers and a count table per model, for the largest fold's negatives
+//   metric_counters uint64[M][6]      copied back whole with the step's other results; the host keeps the active models'
 #include <atomic>
 
+#include "ds_metrics.h"
 #include "ds_train.h"
 
 namespace ds {
@@ -231,8 +239,19 @@ struct ds_trainer_batch {
     ds::DeviceBuffer<uint8_t> masks;
     int32_t *pinned_trees = nullptr;
     ds::BatchSamplingView sampling_view{};
+    // metrics (ds_trainer_batch_set_metrics)
+    uint32_t metric_flags = 0;
+    ds::DeviceBuffer<int32_t> metric_rows;
+    ds::DeviceBuffer<ds::MetricColumn> metric_columns;
+    ds::DeviceBuffer<unsigned long long> metric_counters;
+    ds::MetricScratch metric_scratch;
+    std::vector<ds::MetricColumn> metric_host;
+    std::vector<int64_t> metric_cache;         // [n_models][6], -1 until a model's first step
+    int64_t metric_keys = 0, metric_pos = 0, metric_fold_rows = 0;   // the largest over the held-out folds
+    unsigned long long *pinned_metrics = nullptr;
     ~ds_trainer_batch()
     {
+        if (pinned_metrics) (void)hipHostFree(pinned_metrics);
         if (pinned_trees) (void)hipHostFree(pinned_trees);
         if (pinned_nodes) (void)hipHostFree(pinned_nodes);
         if (pinned_errors) (void)hipHostFree(pinned_errors);
@@ -502,6 +521,98 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
     return DS_OK;
 }
 
+int64_t ds_trainer_batch_metrics_bytes(int64_t n, int32_t n_models, int32_t n_folds)
+{
+    if (n < 1 || n > INT32_MAX || n_models < 1 || n_models > ds::kBatchModelsMax || n_folds < 1 ||
+        n_folds > ds::kBatchFoldsMax)
+        return -1;
+    const int64_t keys = (n + n_folds - 1) / n_folds;
+    return 4 * n + ds::MetricScratch::bytes(keys, n_models) +
+           int64_t(n_models) * int64_t(sizeof(ds::MetricColumn) + sizeof(unsigned long long) * ds::kMetricCounters);
+}
+
+int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags)
+{
+    DS_REQUIRE(batch != nullptr, "ds_trainer_batch_set_metrics: batch is null");
+    DS_REQUIRE((flags & ~(ds::kMetricAuc | ds::kMetricLogloss)) == 0u,
+               "ds_trainer_batch_set_metrics: unknown bits in flags = %u", flags);
+    ds_trainer_batch *b = batch;
+    DS_REQUIRE(!b->stepped, "ds_trainer_batch_set_metrics: the metrics must be set before the first step");
+    b->metric_cache.assign(static_cast<size_t>(b->n_models) * 6, -1);
+    if (flags == 0u) {
+        b->metric_flags = 0u;
+        return DS_OK;
+    }
+    DS_HIP(hipSetDevice(b->device));
+    // per fold that a model holds out: its negative rows, then its positive rows, in row order
+    const size_t rows = static_cast<size_t>(b->n), M = static_cast<size_t>(b->n_models);
+    std::vector<uint8_t> fold(rows);
+    std::vector<float> labels(rows);
+    DS_HIP(hipMemcpy(fold.data(), b->fold.ptr, rows, hipMemcpyDeviceToHost));
+    DS_HIP(hipMemcpy(labels.data(), b->labels.ptr, rows * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<int64_t> neg(ds::kBatchFoldsMax + 1, 0), pos(ds::kBatchFoldsMax + 1, 0), first(ds::kBatchFoldsMax + 1, 0);
+    std::vector<uint8_t> wanted(ds::kBatchFoldsMax + 1, 0);
+    for (const ds::BatchModel &model : b->models)
+        if (model.held_out >= 0) wanted[model.held_out] = 1;
+    for (size_t r = 0; r < rows; ++r) ++(labels[r] == 0.f ? neg : pos)[fold[r]];
+    int64_t listed = 0;
+    b->metric_keys = b->metric_pos = b->metric_fold_rows = 0;
+    for (int k = 0; k <= ds::kBatchFoldsMax; ++k) {
+        if (!wanted[k]) continue;
+        first[k] = listed;
+        listed += neg[k] + pos[k];
+        b->metric_keys = std::max(b->metric_keys, neg[k]);
+        b->metric_pos = std::max(b->metric_pos, pos[k]);
+        b->metric_fold_rows = std::max(b->metric_fold_rows, neg[k] + pos[k]);
+    }
+    if (!(flags & ds::kMetricAuc)) b->metric_keys = 0;
+    std::vector<int32_t> lists(std::max<size_t>(1, static_cast<size_t>(listed)));
+    std::vector<int64_t> at_neg(first), at_pos(first);
+    for (int k = 0; k <= ds::kBatchFoldsMax; ++k) at_pos[k] += neg[k];
+    for (size_t r = 0; r < rows; ++r)
+        if (wanted[fold[r]]) lists[(labels[r] == 0.f ? at_neg : at_pos)[fold[r]]++] = static_cast<int32_t>(r);
+    if (int status = ds::train_check_free(4 * listed + ds::MetricScratch::bytes(b->metric_keys, b->n_models),
+                                          "ds_trainer_batch_set_metrics");
+        status != DS_OK)
+        return status;
+    int status = b->metric_rows.upload(lists.data(), lists.size());
+    if (status == DS_OK) status = b->metric_columns.allocate(M);
+    if (status == DS_OK) status = b->metric_counters.allocate(M * ds::kMetricCounters);
+    if (status == DS_OK) status = b->metric_scratch.allocate(b->metric_keys, b->n_models);
+    if (status == DS_OK && b->pinned_metrics == nullptr &&
+        hipHostMalloc(reinterpret_cast<void **>(&b->pinned_metrics), sizeof(unsigned long long) * M * ds::kMetricCounters) !=
+            hipSuccess) {
+        ds::set_error("ds_trainer_batch_set_metrics: hipHostMalloc failed");
+        status = DS_E_HIP;
+    }
+    if (status != DS_OK) return status;
+    b->metric_host.assign(M, ds::MetricColumn{});
+    for (size_t m = 0; m < M; ++m) {
+        const int32_t k = b->models[m].held_out;
+        ds::MetricColumn &column = b->metric_host[m];
+        column.scores = b->leafsum.ptr + m * rows;
+        column.base_margin = ds::kBatchBaseMargin;
+        column.beta = b->models[m].params.beta;
+        if (k < 0) continue;   // no held-out rows: empty lists, and the host reports -1
+        column.neg_rows = b->metric_rows.ptr + first[k];
+        column.pos_rows = column.neg_rows + neg[k];
+        column.n_neg = static_cast<int32_t>(neg[k]);
+        column.n_pos = static_cast<int32_t>(pos[k]);
+    }
+    DS_HIP(hipMemcpy(b->metric_columns.ptr, b->metric_host.data(), sizeof(ds::MetricColumn) * M, hipMemcpyHostToDevice));
+    DS_HIP(hipMemset(b->metric_counters.ptr, 0, b->metric_counters.bytes()));
+    b->metric_flags = flags;
+    return DS_OK;
+}
+
+int ds_trainer_batch_metrics(ds_trainer_batch *batch, int64_t *out)
+{
+    DS_REQUIRE(batch && out, "ds_trainer_batch_metrics: null argument");
+    for (int64_t i = 0; i < int64_t(batch->n_models) * 6; ++i)
+        out[i] = batch->metric_flags ? batch->metric_cache[static_cast<size_t>(i)] : -1;
+    return DS_OK;
+}
+
 int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_t *node_info, float *node_leaf,
                           int64_t *errors)
 {
@@ -577,6 +688,15 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
         a = end;
     }
     DS_HIP(hipMemcpyAsync(b->pinned_errors, b->errors.ptr, b->errors.bytes(), hipMemcpyDeviceToHost, stream));
+    if (b->metric_flags) {   // over the margins the partition kernels have just written
+        if (int status = ds::metrics_enqueue(stream, b->compute_units, b->metric_flags, b->metric_columns.ptr,
+                                             b->active.ptr, n_active, b->metric_keys, b->metric_pos, b->metric_fold_rows,
+                                             b->metric_scratch, b->metric_counters.ptr, g_max_blocks.load());
+            status != DS_OK)
+            return status;
+        DS_HIP(hipMemcpyAsync(b->pinned_metrics, b->metric_counters.ptr, b->metric_counters.bytes(),
+                              hipMemcpyDeviceToHost, stream));
+    }
     DS_HIP(hipStreamSynchronize(stream));   // the step's one host sync
     b->stepped = true;
     for (int32_t a = 0; a < n_active; ++a) {
@@ -592,6 +712,9 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
             node_leaf[m * b->slots + i] = node.leaf;
         }
         errors[m] = b->models[m].held_out >= 0 ? static_cast<int64_t>(b->pinned_errors[m]) : -1;
+        if (b->metric_flags && b->models[m].held_out >= 0)
+            ds::metrics_row(b->metric_flags, b->pinned_metrics + m * ds::kMetricCounters, b->metric_host[m].n_neg,
+                            b->metric_host[m].n_pos, b->metric_cache.data() + m * 6);
     }
     return DS_OK;
 }

@@ -128,6 +128,119 @@ def _fraction(name, value):
 
 SAMPLING_NAMES = ("subsample", "colsample_bytree", "colsample_bylevel", "sample_seed")
 
+# ---- metrics of the margins ("Metrics"; csrc/ds_metrics.hip) -----------------------------------
+METRIC_NAMES = ("auc", "logloss")
+METRIC_FLAGS = {"auc": 1, "logloss": 2}          # DS_METRIC_AUC, DS_METRIC_LOGLOSS
+LOGLOSS_QUANTUM = 1 << 20                        # a row's log loss is summed in units of 2^-20
+COUNT_NAMES = ("concordant", "ties", "positives", "negatives", "logloss_sum", "rows")
+
+
+def validate_metrics(metrics, what="eval_metrics"):
+    """A tuple or list of distinct names from METRIC_NAMES -> the tuple, in METRIC_NAMES' order."""
+    if isinstance(metrics, (str, bytes)) or not isinstance(metrics, (tuple, list)):
+        raise ValueError(f"{what} must be a tuple drawn from {METRIC_NAMES}, not {metrics!r}")
+    for name in metrics:
+        if not isinstance(name, str) or name not in METRIC_NAMES:
+            raise ValueError(f"{what} holds {name!r}; known: {METRIC_NAMES}")
+    if len(set(metrics)) != len(metrics):
+        raise ValueError(f"{what} names a metric twice: {metrics!r}")
+    return tuple(name for name in METRIC_NAMES if name in metrics)
+
+
+def metric_flags(metrics):
+    return sum(METRIC_FLAGS[name] for name in metrics)
+
+
+def auc_numerator(counts):
+    """2 * concordant + ties: with the class sizes fixed, AUCs compare as these integers do."""
+    return 2 * int(counts[0]) + int(counts[1])
+
+
+def auc_value(counts):
+    """(2 concordant + ties) / (2 |P| |N|) of (concordant, ties, positives, negatives, ...); NaN when a class is empty."""
+    pairs = int(counts[2]) * int(counts[3])
+    return auc_numerator(counts) / (2 * pairs) if pairs > 0 else float("nan")
+
+
+def logloss_value(counts):
+    """sum / 2^20 / rows of (..., logloss_sum, rows); NaN without rows."""
+    total, rows = int(counts[-2]), int(counts[-1])
+    return total / LOGLOSS_QUANTUM / rows if rows > 0 else float("nan")
+
+
+def metric_values(counts, metrics):
+    """{name: value} of one set's six integers (ds_trainer_metrics) for the metrics requested."""
+    out = {}
+    if "auc" in metrics:
+        out["auc"] = auc_value(counts)
+    if "logloss" in metrics:
+        out["logloss"] = logloss_value(counts)
+    return out
+
+
+def metrics_option(name, value):
+    """ds_metrics_option, for tests: metrics_option("max_blocks", b) caps the metric kernels' row grids (0: default)."""
+    _lib.check(_lib.lib().ds_metrics_option(name.encode(), int(value)), "ds_metrics_option")
+
+
+def auc_counts(scores, target, device=0):
+    """(concordant, ties, positives, negatives, nan_rows) of float32 scores against 0/1 labels, counted on the device
+    (ds_auc / ds_auc_device): scores may be a host array or a 1-D DeviceArray (then the labels are uploaded next to it).
+    The order is that of the scores' integer keys: -0.0 equals +0.0, a NaN score belongs to neither class."""
+    out = np.zeros(5, np.int64)
+    if isinstance(scores, _lib.DeviceArray):
+        if len(scores.shape) != 1 or scores.dtype != np.float32:
+            raise ValueError(f"device scores must be a 1-D float32 DeviceArray, not {scores.dtype}{scores.shape}")
+        n, target = _device_labels(scores.shape[0], target, "scored")
+        d_target = _lib.DeviceArray.from_host(target, scores.device)
+        try:
+            _lib.check(_lib.lib().ds_auc_device(scores.ptr, d_target.ptr, n, _lib.pointer(out), None), "ds_auc_device")
+        finally:
+            d_target.free()
+        return tuple(int(v) for v in out)
+    scores = np.asarray(scores)
+    if scores.ndim != 1 or scores.shape[0] < 1 or not (np.issubdtype(scores.dtype, np.floating) or
+                                                       np.issubdtype(scores.dtype, np.integer)):
+        raise ValueError(f"scores must be a non-empty 1-D array of numbers, not {scores.dtype}{scores.shape}")
+    n, target = _device_labels(scores.shape[0], target, "scored")
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    _lib.check(_lib.lib().ds_auc(_lib.pointer(scores), _lib.pointer(target), n, _lib.pointer(out), device), "ds_auc")
+    return tuple(int(v) for v in out)
+
+
+def logloss_counts(margins, target, beta=5.0, device=0):
+    """(fixed-point sum, rows) of the weighted log loss of float32 margins against 0/1 labels, summed on the device
+    (ds_weighted_logloss_device); margins may be a host array or a 1-D float32 DeviceArray.  logloss_value gives
+    sum / 2^20 / rows."""
+    beta = _real("beta", beta, positive=True)
+    on_device = isinstance(margins, _lib.DeviceArray)
+    if on_device:
+        if len(margins.shape) != 1 or margins.dtype != np.float32:
+            raise ValueError(f"device margins must be a 1-D float32 DeviceArray, not {margins.dtype}{margins.shape}")
+        device = margins.device
+    else:
+        margins = np.asarray(margins)
+        if margins.ndim != 1 or not (np.issubdtype(margins.dtype, np.floating) or
+                                     np.issubdtype(margins.dtype, np.integer)):
+            raise ValueError(f"margins must be a 1-D array of numbers, not {margins.dtype}{margins.shape}")
+    n, target = _device_labels(margins.shape[0], target, "scored")
+    d_margins = margins if on_device else _lib.DeviceArray.from_host(margins.astype(np.float32), device)
+    d_target = _lib.DeviceArray.from_host(target, device)
+    out = np.zeros(2, np.int64)
+    try:
+        _lib.check(_lib.lib().ds_weighted_logloss_device(d_margins.ptr, d_target.ptr, n, beta, _lib.pointer(out), None),
+                   "ds_weighted_logloss_device")
+    finally:
+        d_target.free()
+        if not on_device:
+            d_margins.free()
+    return int(out[0]), int(out[1])
+
+
+def roc_auc(scores, target, device=0):
+    """The area under the ROC curve of auc_counts(scores, target): NaN when a class is empty."""
+    return auc_value(auc_counts(scores, target, device))
+
 
 def _matrix_and_labels(features, target, what):
     features = np.asarray(features)
@@ -149,7 +262,8 @@ def _matrix_and_labels(features, target, what):
 
 def validate_fit(features, target, eval_features=None, eval_target=None, num_boost_round=1000,
                  early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                 max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0):
+                 max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0,
+                 eval_metrics=()):
     """fit's checks (no library needed) -> (features, target, eval_features, eval_target, params) as float32 arrays."""
     features, target = _matrix_and_labels(features, target, "training")
     if (eval_features is None) != (eval_target is None):
@@ -160,16 +274,18 @@ def validate_fit(features, target, eval_features=None, eval_target=None, num_boo
             raise ValueError(f"evaluation features have {eval_features.shape[1]} columns, training features "
                              f"{features.shape[1]}")
     params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
-                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed)
+                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed,
+                                 eval_metrics)
     return features, target, eval_features, eval_target, params
 
 
 def validate_parameters(num_boost_round=1000, early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0,
                         reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
-                        colsample_bylevel=1.0, sample_seed=0):
+                        colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
     """The parameter checks of fit and fit_device -> params.  subsample, colsample_bytree and colsample_bylevel are
     fractions in (0, 1] ("Subsampling"); sample_seed in [0, 2^63) seeds their draws and is not the
-    `seed` of the training set and the folds."""
+    `seed` of the training set and the folds.  eval_metrics: a tuple drawn from METRIC_NAMES, reported per round
+    ("Metrics"); it changes no tree."""
     params = dict(num_boost_round=_positive_int("num_boost_round", num_boost_round),
                   early_stopping_rounds=_positive_int("early_stopping_rounds", early_stopping_rounds),
                   max_depth=_positive_int("max_depth", max_depth, 1, MAX_DEPTH_MAX),
@@ -179,7 +295,8 @@ def validate_parameters(num_boost_round=1000, early_stopping_rounds=50, max_dept
                   subsample=_fraction("subsample", subsample),
                   colsample_bytree=_fraction("colsample_bytree", colsample_bytree),
                   colsample_bylevel=_fraction("colsample_bylevel", colsample_bylevel),
-                  sample_seed=_positive_int("sample_seed", sample_seed, 0, (1 << 63) - 1))
+                  sample_seed=_positive_int("sample_seed", sample_seed, 0, (1 << 63) - 1),
+                  eval_metrics=validate_metrics(eval_metrics))
     if params["reg_lambda"] == 0 and params["min_child_weight"] == 0:
         raise ValueError("reg_lambda and min_child_weight cannot both be 0 (an empty child would divide by zero)")
     if params["reg_lambda"] == 0 and params["subsample"] < 1:
@@ -204,7 +321,7 @@ def _device_labels(n, target, what):
 def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
                         early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
                         max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
-                        sample_seed=0):
+                        sample_seed=0, eval_metrics=()):
     """fit_device's checks (no library needed) -> (n, target, n_eval, eval_target, n_features, params): validate_fit
     for matrices in HBM, of which only the shapes are known here."""
     n_features = _device_columns(d_features, n_features)
@@ -223,7 +340,8 @@ def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, e
         if isinstance(array, _lib.DeviceArray) and rows > array.shape[0]:
             raise ValueError(f"{rows} {what} rows exceed the device matrix's {array.shape[0]}")
     params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
-                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed)
+                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed,
+                                 eval_metrics)
     return n, target, n_eval, eval_target, n_features, params
 
 
@@ -262,7 +380,13 @@ class ForestTrainer:
     After fit, `best_iteration` is the round (from 0) of the first minimum of the evaluation error and `history` the
     error of every round; the model holds the first best_iteration + 1 trees (the reference predicts with
     ntree_limit=best_ntree_limit).  Without an evaluation set every round is kept.  The step form: begin(...), then
-    step() grows one tree and returns the round's evaluation error (None without an evaluation set)."""
+    step() grows one tree and returns the round's evaluation error (None without an evaluation set).
+
+    eval_metrics=("auc", "logloss") also reports, per round, the reference's log: `metrics_history` gains one value per
+    key "train-auc", "evaluation-auc", "train-logloss", "evaluation-logloss" (evaluation keys only with an evaluation
+    set) and `metric_counts` the integers they come from ({"train": (concordant, ties, positives, negatives,
+    logloss_sum, rows), "evaluation": ...} per round, -1 for a metric not requested).  They are computed on the device
+    from the margins of ALL rows of a set and change neither the trees nor the early stopping."""
 
     def __init__(self, device=0):
         self.device = device
@@ -270,14 +394,18 @@ class ForestTrainer:
         self.trees = []
         self.history = []
         self.best_iteration = None
+        self.eval_metrics = ()
+        self.metrics_history = {}
+        self.metric_counts = []
 
     def begin(self, features, target, eval_features=None, eval_target=None, max_depth=5, eta=0.1,
               min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
-              colsample_bylevel=1.0, sample_seed=0):
+              colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
         features, target, eval_features, eval_target, params = validate_fit(
             features, target, eval_features, eval_target, max_depth=max_depth, eta=eta,
             min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin, subsample=subsample,
-            colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, sample_seed=sample_seed)
+            colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, sample_seed=sample_seed,
+            eval_metrics=eval_metrics)
         self.close()
         self.params = params
         self.n, self.n_features = features.shape
@@ -296,6 +424,7 @@ class ForestTrainer:
         if eval_features is not None:
             _lib.check(library.ds_trainer_set_eval(self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
                                                    self.n_eval), "ds_trainer_set_eval")
+        self._set_metrics(params)
         slots = (2 << params["max_depth"]) - 1
         self._info = np.zeros((slots, 4), np.int32)
         self._leaf = np.zeros(slots, np.float32)
@@ -308,9 +437,20 @@ class ForestTrainer:
                                                           params["colsample_bylevel"], params["sample_seed"]),
                        "ds_trainer_set_sampling")
 
+    def _set_metrics(self, params):
+        """The metrics to the library once the labels and the evaluation set are in place (none: nothing to set)."""
+        self.eval_metrics = params["eval_metrics"]
+        names = [f"{set_}-{metric}" for metric in self.eval_metrics
+                 for set_ in (("train", "evaluation") if self.n_eval else ("train",))]
+        self.metrics_history, self.metric_counts = {name: [] for name in names}, []
+        self._metric_counts = np.full((2, 6), -1, np.int64)
+        if self.eval_metrics:
+            _lib.check(_lib.lib().ds_trainer_set_metrics(self.handle, metric_flags(self.eval_metrics)),
+                       "ds_trainer_set_metrics")
+
     def begin_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, max_depth=5,
                      eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, n_features=None,
-                     subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0):
+                     subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
         """begin for matrices that already lie in HBM: contiguous float32[n, n_features] DeviceArrays (or addresses,
         with n_features given), complete before the call; labels are host arrays.  The cuts come from
         compute_cuts_device, the bins from the same kernel as begin's, so every later call works as after begin.  The
@@ -319,7 +459,7 @@ class ForestTrainer:
             d_features, n, target, d_eval_features, n_eval, eval_target, max_depth=max_depth, eta=eta,
             min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin,
             n_features=n_features, subsample=subsample, colsample_bytree=colsample_bytree,
-            colsample_bylevel=colsample_bylevel, sample_seed=sample_seed)
+            colsample_bylevel=colsample_bylevel, sample_seed=sample_seed, eval_metrics=eval_metrics)
         self.close()
         self.params = params
         self.n, self.n_features, self.n_eval = n, n_features, n_eval
@@ -342,6 +482,7 @@ class ForestTrainer:
             _lib.check(library.ds_trainer_set_eval_device(self.handle, _lib.pointer(d_eval_features),
                                                           _lib.pointer(eval_target), self.n_eval),
                        "ds_trainer_set_eval_device")
+        self._set_metrics(params)
         self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
         slots = (2 << params["max_depth"]) - 1
         self._info = np.zeros((slots, 4), np.int32)
@@ -351,14 +492,15 @@ class ForestTrainer:
     def fit_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
                    early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
                    max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
-                   sample_seed=0):
+                   sample_seed=0, eval_metrics=()):
         """fit for matrices in HBM (begin_device, then fit's rounds and early stopping)."""
         rounds = validate_fit_device(d_features, n, target, d_eval_features, n_eval, eval_target, num_boost_round,
                                      early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda, beta, max_bin,
-                                     n_features, subsample, colsample_bytree, colsample_bylevel, sample_seed)[5]
+                                     n_features, subsample, colsample_bytree, colsample_bylevel, sample_seed,
+                                     eval_metrics)[5]
         self.begin_device(d_features, n, target, d_eval_features, n_eval, eval_target, max_depth, eta,
                           min_child_weight, reg_lambda, beta, max_bin, n_features, subsample, colsample_bytree,
-                          colsample_bylevel, sample_seed)
+                          colsample_bylevel, sample_seed, eval_metrics)
         return self._boost(rounds)
 
     def step(self):
@@ -372,6 +514,15 @@ class ForestTrainer:
         self.trees.append(self._tree(self._info, self._leaf))
         value = int(error.value) if self.n_eval else None
         self.history.append(value)
+        if self.eval_metrics:
+            _lib.check(_lib.lib().ds_trainer_metrics(self.handle, _lib.pointer(self._metric_counts)),
+                       "ds_trainer_metrics")
+            sets = ("train", "evaluation") if self.n_eval else ("train",)
+            self.metric_counts.append({set_: tuple(int(v) for v in self._metric_counts[i])
+                                       for i, set_ in enumerate(sets)})
+            for i, set_ in enumerate(sets):
+                for metric, number in metric_values(self._metric_counts[i], self.eval_metrics).items():
+                    self.metrics_history[f"{set_}-{metric}"].append(number)
         return value
 
     def _tree(self, info, leaf):
@@ -385,12 +536,12 @@ class ForestTrainer:
 
     def fit(self, features, target, eval_features=None, eval_target=None, num_boost_round=1000,
             early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-            max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0):
+            max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
         rounds = validate_fit(features, target, eval_features, eval_target, num_boost_round, early_stopping_rounds,
                               max_depth, eta, min_child_weight, reg_lambda, beta, max_bin, subsample, colsample_bytree,
-                              colsample_bylevel, sample_seed)[4]
+                              colsample_bylevel, sample_seed, eval_metrics)[4]
         self.begin(features, target, eval_features, eval_target, max_depth, eta, min_child_weight, reg_lambda, beta,
-                   max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed)
+                   max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed, eval_metrics)
         return self._boost(rounds)
 
     def _boost(self, rounds):
@@ -461,11 +612,14 @@ class TrainModelResult:
     """What train_model returns: `model` (ForestModel of best_iteration + 1 trees), `feature_importance` (the
     reference's return value: ForestModel.feature_importance()), `error_matrix` ((tp, tn, fp, fn) on the evaluation set
     at 0.9, what the reference logs; None without an evaluation set), `best_iteration`, `history`, `rows` (the
-    DataFrame of FeatureEngineering.rows) and `timings` (milliseconds per stage, "total" for the call)."""
+    DataFrame of FeatureEngineering.rows), `timings` (milliseconds per stage, "total" for the call) and, when
+    eval_metrics were requested, `metrics_history` (ForestTrainer.metrics_history; None otherwise)."""
 
-    def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings):
+    def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings,
+                 metrics_history=None):
         self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
         self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
+        self.metrics_history = metrics_history
 
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
@@ -473,7 +627,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
-    fit_parameters: those of ForestTrainer.fit (num_boost_round, early_stopping_rounds, max_depth, eta, ...).
+    fit_parameters: those of ForestTrainer.fit (num_boost_round, early_stopping_rounds, max_depth, eta, ...,
+    eval_metrics=("auc", "logloss") for the reference's per-round train-auc / evaluation-auc log).
     Everything is validated before any device work.  Evaluation fractions of 0 for all three kinds train without an
     evaluation set: every round is kept and error_matrix is None.
     cover: also count the training matrix through the finished trees while it is still in HBM
@@ -518,7 +673,10 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
             raise
         timings["cover"] = (time.perf_counter() - mark) * 1000.0
     best_iteration, history = trainer.best_iteration, list(trainer.history)
+    metrics_history = {key: list(values) for key, values in trainer.metrics_history.items()} \
+        if trainer.eval_metrics else None
     trainer.close()
     sets.free()
     timings["total"] = (time.perf_counter() - started) * 1000.0
-    return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings)
+    return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings,
+                            metrics_history=metrics_history)

@@ -15,8 +15,9 @@ import numpy as np
 
 from . import _lib
 from .forest import ForestModel
-from .train import (SAMPLING_NAMES, _device_columns, _device_labels, _matrix_and_labels, _positive_int, compute_cuts,
-                    compute_cuts_device, heap_tree, validate_parameters)
+from .train import (METRIC_NAMES, SAMPLING_NAMES, _device_columns, _device_labels, _matrix_and_labels, _positive_int,
+                    auc_numerator, compute_cuts, compute_cuts_device, heap_tree, metric_flags, metric_values,
+                    validate_metrics, validate_parameters)
 
 MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
 FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
@@ -107,6 +108,54 @@ def fold_assignment(groups, n_folds, seed=0, n=None):
     return fold_of_group[inverse.reshape(-1)]
 
 
+SELECT_BY = ("error",) + METRIC_NAMES
+
+
+def validate_selection(metrics=(), select_by="error"):
+    """cross_validate's `metrics` and `select_by` -> (metrics in METRIC_NAMES' order, select_by)."""
+    metrics = validate_metrics(metrics, "metrics")
+    if not isinstance(select_by, str) or select_by not in SELECT_BY:
+        raise ValueError(f"select_by must be one of {SELECT_BY}, not {select_by!r}")
+    if select_by != "error" and select_by not in metrics:
+        raise ValueError(f"select_by = {select_by!r} needs that metric: metrics = {metrics!r} does not request it")
+    return metrics, select_by
+
+
+def pooled_counts(fold_counts):
+    """The out-of-fold integers of one round: the sums over the folds of (concordant, ties, positives * negatives,
+    logloss_sum, rows) from each fold's (concordant, ties, positives, negatives, logloss_sum, rows); an entry whose
+    metric was not requested (-1 in a fold) is -1."""
+    folds = [tuple(int(v) for v in one) for one in fold_counts]
+    auc = all(one[0] >= 0 for one in folds)
+    logloss = all(one[4] >= 0 for one in folds)
+    return (sum(one[0] for one in folds) if auc else -1, sum(one[1] for one in folds) if auc else -1,
+            sum(one[2] * one[3] for one in folds) if auc else -1,
+            sum(one[4] for one in folds) if logloss else -1, sum(one[5] for one in folds) if logloss else -1)
+
+
+def pooled_values(pooled):
+    """{auc, logloss} of pooled_counts: auc = sum(2 c + t) / (2 sum(P N)), logloss = sum / 2^20 / rows: ratios of
+    integer sums, the same whatever the order of the folds."""
+    out = {}
+    if pooled[0] >= 0:
+        out["auc"] = (2 * pooled[0] + pooled[1]) / (2 * pooled[2]) if pooled[2] > 0 else float("nan")
+    if pooled[3] >= 0:
+        out["logloss"] = pooled[3] / float(1 << 20) / pooled[4] if pooled[4] > 0 else float("nan")
+    return out
+
+
+def _selection_score(select_by, errors, fold_counts):
+    """The integer that a round is judged by, smaller = better: the summed error; minus the pooled AUC numerator
+    sum(2 c + t); the pooled log-loss sum.  The denominators (pairs, rows) are those of the folds and the labels, the
+    same for every parameter set and round, so the numerators order the values exactly."""
+    if select_by == "error":
+        return int(sum(int(e) for e in errors))
+    pooled = pooled_counts(fold_counts)
+    if pooled[0 if select_by == "auc" else 3] < 0:
+        raise ValueError(f"select_by = {select_by!r}, but the metric counts do not hold that metric")
+    return -(2 * pooled[0] + pooled[1]) if select_by == "auc" else pooled[3]
+
+
 def _replay(curve, early_stopping_rounds):
     """(best_iteration, error, rounds) of one summed curve under the stepping rule: the first minimum; the set stops
     after the first round with round - best >= early_stopping_rounds (None: never), later entries are not looked at."""
@@ -119,29 +168,61 @@ def _replay(curve, early_stopping_rounds):
     return best, int(curve[best]), len(curve)
 
 
-def select_parameters(histories, early_stopping_rounds=None):
+def select_parameters(histories, early_stopping_rounds=None, select_by="error", metric_counts=None):
     """xgb.cv's choice, on the host.  histories[p][k] = the held-out error of fold k after every round of parameter set
     p (the K curves of a set have one length; sets may differ).  Per set the summed curve is the per-round sum of its
     folds' errors -- the out-of-fold error over the whole matrix, an integer -- best_iteration its first minimum and
     error that minimum, looking no further than the round at which early_stopping_rounds would have stopped the set.
     The chosen set has the lowest error; a tie goes to the smaller best_iteration, then to the earlier set.
-    Returns dict(chosen, best_iteration[p], error[p], rounds[p], history[p])."""
+    Returns dict(chosen, best_iteration[p], error[p], rounds[p], history[p]).
+
+    metric_counts[p][k][r] = the six integers (train.COUNT_NAMES) of fold k's held-out rows after round r.  With them
+    the result gains metrics_history[p] = {"auc": [...], "logloss": [...]}, the pooled out-of-fold value of every round
+    looked at (pooled_values).  select_by = "auc" (maximise) or "logloss" (minimise) runs the same rule -- first best
+    round, early stopping, ties to the smaller best_iteration, then the earlier set -- on that metric's pooled curve
+    instead of the error's, comparing its integer numerators (_selection_score); error[p] and history[p] stay the
+    summed error, error[p] taken at the best_iteration so chosen, and score[p] is the numerator there."""
     if early_stopping_rounds is not None:
         early_stopping_rounds = _positive_int("early_stopping_rounds", early_stopping_rounds)
+    if not isinstance(select_by, str) or select_by not in SELECT_BY:
+        raise ValueError(f"select_by must be one of {SELECT_BY}, not {select_by!r}")
+    if select_by != "error" and metric_counts is None:
+        raise ValueError(f"select_by = {select_by!r} needs that metric: no metric was requested")
     if len(histories) == 0:
         raise ValueError("histories is empty")
+    if metric_counts is not None and len(metric_counts) != len(histories):
+        raise ValueError(f"{len(histories)} parameter sets but metric counts of {len(metric_counts)}")
     out = dict(best_iteration=[], error=[], rounds=[], history=[])
+    if metric_counts is not None:
+        out["metrics_history"] = []
+    if select_by != "error":
+        out["score"] = []
     for p, folds in enumerate(histories):
         lengths = {len(curve) for curve in folds}
         if len(folds) == 0 or len(lengths) != 1 or 0 in lengths:
             raise ValueError(f"parameter set {p}: the folds' curves must be non-empty and of one length")
-        summed = [int(sum(int(curve[r]) for curve in folds)) for r in range(lengths.pop())]
-        best, error, rounds = _replay(summed, early_stopping_rounds)
+        length = lengths.pop()
+        summed = [int(sum(int(curve[r]) for curve in folds)) for r in range(length)]
+        if metric_counts is not None and (len(metric_counts[p]) != len(folds) or
+                                          {len(curve) for curve in metric_counts[p]} != {length}):
+            raise ValueError(f"parameter set {p}: the metric counts must have the shape of the folds' curves")
+        if select_by == "error":
+            best, error, rounds = _replay(summed, early_stopping_rounds)
+        else:
+            scores = [_selection_score(select_by, None, [curve[r] for curve in metric_counts[p]])
+                      for r in range(length)]
+            best, score, rounds = _replay(scores, early_stopping_rounds)
+            error = summed[best]
+            out["score"].append(score)
         out["best_iteration"].append(best)
         out["error"].append(error)
         out["rounds"].append(rounds)
         out["history"].append(summed[:rounds])
-    out["chosen"] = min(range(len(histories)), key=lambda p: (out["error"][p], out["best_iteration"][p], p))
+        if metric_counts is not None:
+            values = [pooled_values(pooled_counts([curve[r] for curve in metric_counts[p]])) for r in range(rounds)]
+            out["metrics_history"].append({name: [one[name] for one in values] for name in (values[0] if values else ())})
+    judged = out["error"] if select_by == "error" else out["score"]
+    out["chosen"] = min(range(len(histories)), key=lambda p: (judged[p], out["best_iteration"][p], p))
     return out
 
 
@@ -177,6 +258,11 @@ def batch_bytes(n, n_features, n_models, max_depth):
     return int(_lib.lib().ds_trainer_batch_bytes(n, n_features, n_models, max_depth))
 
 
+def batch_metrics_bytes(n, n_models, n_folds):
+    """ds_trainer_batch_metrics_bytes: the HBM that per-round metrics add to a batch with folds of equal size."""
+    return int(_lib.lib().ds_trainer_batch_metrics_bytes(n, n_models, n_folds))
+
+
 def batch_option(name, value):
     """ds_trainer_batch_option, for tests: batch_option("max_blocks", b) caps the row grids (0: default)."""
     _lib.check(_lib.lib().ds_trainer_batch_option(name.encode(), int(value)), "ds_trainer_batch_option")
@@ -193,28 +279,35 @@ class ForestTrainerBatch:
     fold[r] != held_out (-1, the default: every row trains).  The cuts are those of the WHOLE matrix, so a model's trees
     are ForestTrainer's on its training rows with those cuts.  step(active) touches only the models with active[m] true.
     trees[m], history[m] (errors; None entries without a fold), model(m, n_trees), margins(m) (all rows),
-    probabilities(m), gradients(m), bins(), last_heap[m] as ForestTrainer's."""
+    probabilities(m), gradients(m), bins(), last_heap[m] as ForestTrainer's.
+
+    begin(..., metrics=("auc", "logloss")) also computes, in every step and on the device, the metrics of each active
+    model over the rows of its HELD-OUT fold: metric_counts[m] gains the round's (concordant, ties, positives, negatives,
+    logloss_sum, rows) and metrics_history[m][name] its value (-1s and None for a model without a fold)."""
 
     def __init__(self, device=0):
         self.device = device
         self.handle = None
         self.trees, self.history, self.last_heap = [], [], []
+        self.metrics, self.metrics_history, self.metric_counts = (), [], []
         self.timings = {}
 
-    def begin(self, features, target, fold, models, max_bin=256, cuts=None):
+    def begin(self, features, target, fold, models, max_bin=256, cuts=None, metrics=()):
         features, target = _matrix_and_labels(features, target, "training")
-        return self._begin(features, False, features.shape[0], features.shape[1], target, fold, models, max_bin, cuts)
+        return self._begin(features, False, features.shape[0], features.shape[1], target, fold, models, max_bin, cuts,
+                           metrics)
 
-    def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None):
+    def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None, metrics=()):
         """begin for a contiguous float32[n, n_features] matrix that lies complete in HBM (a DeviceArray, or an address
         with n_features given).  It is read where it lies, never copied to the host, and not kept."""
         n_features = _device_columns(d_features, n_features)
         n, target = _device_labels(n, target, "training")
         if isinstance(d_features, _lib.DeviceArray) and n > d_features.shape[0]:
             raise ValueError(f"{n} training rows exceed the device matrix's {d_features.shape[0]}")
-        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts)
+        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts, metrics)
 
-    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts):
+    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts, metrics=()):
+        metrics = validate_metrics(metrics, "metrics")
         fold, n_folds = _validate_fold(fold, n)
         params, held_out, sets = validate_models(models, FOLDS_MAX)
         if held_out.max() >= n_folds:
@@ -248,6 +341,13 @@ class ForestTrainerBatch:
             seeds = np.array([one["sample_seed"] for one in sets], np.uint64)
             _lib.check(library.ds_trainer_batch_set_sampling(self.handle, _lib.pointer(fractions), _lib.pointer(seeds)),
                        "ds_trainer_batch_set_sampling")
+        self.metrics = metrics
+        self.metrics_history = [{name: [] for name in metrics} for _ in sets]
+        self.metric_counts = [[] for _ in sets]
+        self._metric_counts = np.full((self.n_models, 6), -1, np.int64)
+        if metrics:
+            _lib.check(library.ds_trainer_batch_set_metrics(self.handle, metric_flags(metrics)),
+                       "ds_trainer_batch_set_metrics")
         self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
         slots = (2 << self.max_depth) - 1          # the heaps of every model have the largest max_depth's slots
         self._info = np.zeros((self.n_models, slots, 4), np.int32)
@@ -269,8 +369,17 @@ class ForestTrainerBatch:
         _lib.check(_lib.lib().ds_trainer_batch_step(self.handle, _lib.pointer(mask), _lib.pointer(self._info),
                                                     _lib.pointer(self._leaf), _lib.pointer(self._errors)),
                    "ds_trainer_batch_step")
+        if self.metrics:
+            _lib.check(_lib.lib().ds_trainer_batch_metrics(self.handle, _lib.pointer(self._metric_counts)),
+                       "ds_trainer_batch_metrics")
         out = [None] * self.n_models
         for m in np.nonzero(mask)[0]:
+            if self.metrics:
+                held = self.held_out[m] >= 0
+                self.metric_counts[m].append(tuple(int(v) for v in self._metric_counts[m]))
+                values = metric_values(self._metric_counts[m], self.metrics) if held else {}
+                for name in self.metrics:
+                    self.metrics_history[m][name].append(values.get(name))
             self.last_heap[m] = (self._info[m].copy(), self._leaf[m].copy())
             self.trees[m].append(heap_tree(self._info[m], self._leaf[m], self.cuts, self.cut_offsets))
             out[m] = int(self._errors[m]) if self.held_out[m] >= 0 else None
@@ -321,6 +430,9 @@ class CrossValidation:
     the best round), `history[p]` (the summed curve),
     `fold_history[p][k]`, `parameters` (the sets), `chosen` (the index of the best set), `best_parameters`,
     `best_iteration`, `folds` (uint8[n]), `timings` (ms: cuts, bin, boost, refit, total) and, with refit, `model`.
+    With metrics: `metrics_history[p]` ({"auc": [...], "logloss": [...]}: per round the pooled out-of-fold value of set
+    p), `fold_metric_counts[p][k]` (per round the six integers of fold k), `select_by`, and the columns `auc` and/or
+    `logloss` of `results` at best_iteration.
     tune_model_parameters adds `rows` and `feature_importance`."""
 
     def __init__(self, **fields):
@@ -329,9 +441,10 @@ class CrossValidation:
 
 
 def validate_cross_validation(parameters, n_folds=5, seed=0, num_boost_round=1000, early_stopping_rounds=50,
-                              max_bin=256, models_per_batch=None):
+                              max_bin=256, models_per_batch=None, metrics=(), select_by="error"):
     """cross_validate's checks of everything but the data (no library needed) -> (parameter sets, sets per batch)."""
     sets = _parameter_sets(parameters)
+    validate_selection(metrics, select_by)
     n_folds = _positive_int("n_folds", n_folds, 2, FOLDS_MAX)
     _positive_int("seed", seed, 0)
     validate_parameters(num_boost_round=num_boost_round, early_stopping_rounds=early_stopping_rounds, max_bin=max_bin)
@@ -344,20 +457,23 @@ def validate_cross_validation(parameters, n_folds=5, seed=0, num_boost_round=100
     return sets, None
 
 
-def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device):
-    """Whole parameter sets (K models each) per batch: what 80 % of the free HBM holds, 256 models at most."""
+def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics=()):
+    """Whole parameter sets (K models each) per batch: what 80 % of the free HBM holds, 256 models at most.  With
+    metrics their scratch (batch_metrics_bytes) comes off the budget."""
     free, total = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.check(_lib.lib().ds_device_memory(device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
     budget = int(free.value * 0.8) - (0 if in_hbm else 4 * n * n_features)
     depth = max(one["max_depth"] for one in sets)
     count = max(1, min(len(sets), MODELS_MAX // n_folds))
-    while count > 1 and batch_bytes(n, n_features, count * n_folds, depth) > budget:
+    extra = (lambda models: batch_metrics_bytes(n, models, n_folds)) if metrics else (lambda models: 0)
+    while count > 1 and batch_bytes(n, n_features, count * n_folds, depth) + extra(count * n_folds) > budget:
         count -= 1
     return count
 
 
 def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0, num_boost_round=1000,
-                   early_stopping_rounds=50, max_bin=256, refit=True, device=0, models_per_batch=None):
+                   early_stopping_rounds=50, max_bin=256, refit=True, device=0, models_per_batch=None, metrics=(),
+                   select_by="error"):
     """K-fold cross-validation of one parameter set or a list of them (parameter_grid) on the GPU -> CrossValidation.
 
     features: a host matrix, or a DeviceArray float32[>= n, n_features] in HBM of which the first len(target) rows
@@ -368,10 +484,17 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     on it.  The cuts are computed once, the bins once per batch.  A set with subsampling parameters uses its
     sample_seed in every fold.  refit: the chosen set is trained on ALL rows for
     best_iteration + 1 rounds; with the whole matrix's cuts that is ForestTrainer().fit(features, target,
-    num_boost_round=best_iteration + 1, **best_parameters), bit for bit."""
+    num_boost_round=best_iteration + 1, **best_parameters), bit for bit.
+
+    metrics=("auc", "logloss"): every step also computes these over each model's held-out rows, on the device (DESIGN.md
+    section 9, "Metrics"); the result gains metrics_history[p] (the pooled out-of-fold value per round: auc =
+    sum_k (2 c_k + t_k) / (2 sum_k P_k N_k), logloss = sum_k sum_k / 2^20 / sum_k rows_k) and the columns `auc` /
+    `logloss` of `results`.  select_by = "auc" (maximise) or "logloss" (minimise) steps, stops and chooses on that curve
+    instead of the error's, by its integer numerators; "error" (the default) is the rule above whatever the metrics."""
     started = time.perf_counter()
     sets, per_batch = validate_cross_validation(parameters, n_folds, seed, num_boost_round, early_stopping_rounds,
-                                                max_bin, models_per_batch)
+                                                max_bin, models_per_batch, metrics, select_by)
+    metrics, select_by = validate_selection(metrics, select_by)
     in_hbm = isinstance(features, _lib.DeviceArray)
     if in_hbm:
         n_features = _device_columns(features, None)
@@ -384,25 +507,26 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
         n, n_features = features.shape
     folds = fold_assignment(groups, n_folds, seed, n)
     if per_batch is None:
-        per_batch = _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device)
+        per_batch = _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics)
     timings = dict.fromkeys(("cuts", "bin", "boost", "refit"), 0.0)
     mark = time.perf_counter()
     cuts = compute_cuts_device(features, n, max_bin, n_features, device) if in_hbm else compute_cuts(features, max_bin)
     timings["cuts"] = (time.perf_counter() - mark) * 1000.0
 
-    def begin(models):
+    def begin(models, metrics=()):
         batch = ForestTrainerBatch(device)
         if in_hbm:
-            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts)
+            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts, metrics)
         else:
-            batch.begin(features, target, folds, models, max_bin, cuts)
+            batch.begin(features, target, folds, models, max_bin, cuts, metrics)
         timings["bin"] += batch.timings["bin"]
         return batch
 
     fold_history = [None] * len(sets)
+    fold_counts = [None] * len(sets)
     for first in range(0, len(sets), per_batch):
         chunk = sets[first:first + per_batch]
-        batch = begin([dict(one, held_out=k) for one in chunk for k in range(n_folds)])
+        batch = begin([dict(one, held_out=k) for one in chunk for k in range(n_folds)], metrics)
         try:
             mark = time.perf_counter()
             summed, best = [[] for _ in chunk], [0] * len(chunk)
@@ -410,7 +534,9 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
             for round_ in range(num_boost_round):
                 errors = batch.step(np.repeat(running, n_folds))
                 for s in np.nonzero(running)[0]:
-                    summed[s].append(sum(errors[s * n_folds:(s + 1) * n_folds]))
+                    models = range(s * n_folds, (s + 1) * n_folds)
+                    summed[s].append(_selection_score(select_by, errors[s * n_folds:(s + 1) * n_folds],
+                                                      [batch.metric_counts[m][-1] for m in models] if metrics else None))
                     if summed[s][-1] < summed[s][best[s]]:
                         best[s] = round_
                     if round_ - best[s] >= early_stopping_rounds:
@@ -419,18 +545,24 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
                     break
             for s in range(len(chunk)):
                 fold_history[first + s] = [list(batch.history[s * n_folds + k]) for k in range(n_folds)]
+                if metrics:
+                    fold_counts[first + s] = [list(batch.metric_counts[s * n_folds + k]) for k in range(n_folds)]
             timings["boost"] += (time.perf_counter() - mark) * 1000.0
         finally:
             batch.close()
-    chosen = select_parameters(fold_history, early_stopping_rounds)
+    chosen = select_parameters(fold_history, early_stopping_rounds, select_by, fold_counts if metrics else None)
     import pandas as pd
     results = pd.DataFrame(sets)
     results["best_iteration"], results["error"], results["rounds"] = \
         chosen["best_iteration"], chosen["error"], chosen["rounds"]
     results["fold_errors"] = [[curve[chosen["best_iteration"][p]] for curve in fold_history[p]]
                               for p in range(len(sets))]
+    for name in metrics:
+        results[name] = [chosen["metrics_history"][p][name][chosen["best_iteration"][p]] for p in range(len(sets))]
     best_set = chosen["chosen"]
-    out = CrossValidation(results=results, history=chosen["history"], fold_history=fold_history, parameters=sets,
+    extra = dict(metrics_history=chosen["metrics_history"], fold_metric_counts=fold_counts, select_by=select_by) \
+        if metrics else {}
+    out = CrossValidation(**extra, results=results, history=chosen["history"], fold_history=fold_history, parameters=sets,
                           chosen=best_set, best_parameters=dict(sets[best_set]),
                           best_iteration=chosen["best_iteration"][best_set], folds=folds, timings=timings)
     if refit:
@@ -457,14 +589,15 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
                           sample_n=10, seed=0, device=0, transform=True, cover=False, **cv_arguments):
     """Parameter search from raw titles in one call: FeatureEngineering(..., no evaluation split).
     generate_device_data_sets() -> cross_validate on the matrix in HBM, folds by row_groups -> the refit model.
-    cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch.  Returns cross_validate's result
+    cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch, metrics, select_by.  Returns cross_validate's result
     with `rows` (FeatureEngineering.rows), `feature_importance` and the FeatureEngineering stages in `timings`.
     cover: also count the model's cover on the matrix while it is in HBM (ForestModel.fit_cover_device), so that the
     model can explain its predictions; `timings` then has "cover".  Everything is validated before any device work and
     everything held in HBM is freed on every exit path."""
     from .training_set import FeatureEngineering
     started = time.perf_counter()
-    unknown = set(cv_arguments) - {"num_boost_round", "early_stopping_rounds", "max_bin", "models_per_batch"}
+    unknown = set(cv_arguments) - {"num_boost_round", "early_stopping_rounds", "max_bin", "models_per_batch", "metrics",
+                                   "select_by"}
     if unknown:
         raise ValueError(f"unknown cross-validation arguments {sorted(unknown)}")
     validate_cross_validation(parameters, n_folds, seed, **cv_arguments)

@@ -11,11 +11,14 @@ It prints the fraction of correct final answers of that model next to a model tr
 top-k pairs of the train queries labelled with their known source row) and the random stand-in ensemble
 (synth.make_forest) that the other examples use.
 
-    python examples/train_model.py [--one-call] [n_truth] [n_queries] [top_n] [model.npz]
+    python examples/train_model.py [--one-call] [--metrics auc,logloss] [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
 --one-call trains with ds.train_model(...), the same steps in one call with the feature matrix kept in HBM; the model
 is the same.
+--metrics prints the reference's per-round log line (xgboost's, with eval_metric 'auc' and the watch list train /
+evaluation): train-auc and evaluation-auc -- and train-logloss / evaluation-logloss, the objective's own loss -- next to
+the custom error, all computed on the device; the model is the same with and without it.
 """
 import os
 import sys
@@ -45,7 +48,16 @@ def _stand_in():
                           stand_in["missing"], stand_in["tree_offsets"], stand_in["n_features"], stand_in["base_margin"])
 
 
-def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False):
+def print_rounds(metrics_history, history):
+    """One line per round in xgboost's form: [round] <set>-<metric>:<value> ... evaluation-custom-error:<error>"""
+    for round_, error in enumerate(history):
+        parts = [f"{key}:{values[round_]:.6f}" for key, values in metrics_history.items()]
+        if error is not None:
+            parts.append(f"evaluation-custom-error:{error}")
+        print(f"[{round_}]\t" + "\t".join(parts))
+
+
+def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=()):
     train = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     evaluation = synth.make_workload(n_truth, n_queries // 4, seed=11, query_seed=102)
     held_out = synth.make_workload(n_truth, n_queries, seed=11, query_seed=103)
@@ -56,9 +68,11 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False):
     train_ids = np.where(train.actual_row >= 0, train.title_id[np.maximum(train.actual_row, 0)], -1)
     if one_call:
         t0 = time.perf_counter()
-        result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids)
+        result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics))
         t1 = time.perf_counter()
         model = result.model
+        if metrics:
+            print_rounds(result.metrics_history, result.history)
         kinds = result.rows["kind"].value_counts().sort_index().to_dict()
         print(f"train_model: {result.rows.shape[0]} rows (generated / negative / positive: {kinds.get(1, 0)} / "
               f"{kinds.get(2, 0)} / {kinds.get(3, 0)}), {len(result.history)} rounds in {t1 - t0:.2f}s in all, best "
@@ -77,8 +91,10 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False):
               + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.timings.items()))
         t0 = time.perf_counter()
         trainer = ds.ForestTrainer()
-        model = trainer.fit(features, labels, eval_features, eval_labels)
+        model = trainer.fit(features, labels, eval_features, eval_labels, eval_metrics=tuple(metrics))
         t1 = time.perf_counter()
+        if metrics:
+            print_rounds(trainer.metrics_history, trainer.history)
         print(f"training: {features.shape[0]} rows ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
               f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error {trainer.history[trainer.best_iteration]})")
         tp, tn, fp, fn = ds.evaluation_error_matrix(model, eval_features, eval_labels)
@@ -104,4 +120,11 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False):
 
 if __name__ == "__main__":
     arguments = [a for a in sys.argv[1:] if a != "--one-call"]
-    main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:])
+    wanted = ()
+    if "--metrics" in arguments:
+        at = arguments.index("--metrics")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--metrics needs a comma-separated list drawn from auc,logloss")
+        wanted = tuple(arguments[at + 1].split(","))
+        del arguments[at:at + 2]
+    main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted)

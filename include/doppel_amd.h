@@ -570,6 +570,57 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
  * which stride beyond it (0: back to the default).  The results do not depend on it. */
 int ds_trainer_batch_option(const char *name, int64_t value);
 
+/* ---- metrics of a booster's margins, computed on the device ("Metrics") ---------------------------
+ * AUC is taken over float32 MARGINS by integer key: NaN -> 0xFFFFFFFF, else with -0.0 read as +0.0 the bits with all
+ * bits flipped when the sign is set and only the sign bit flipped otherwise (the order of the cuts).  With P the rows of
+ * label 1 and N those of label 0 whose score is not a NaN, concordant = #{(p, n): key_p > key_n}, ties = #{(p, n):
+ * key_p == key_n} and auc = (2 concordant + ties) / (2 |P| |N|), undefined when a class is empty.  A row with a NaN
+ * score belongs to neither class.  The weighted log loss of a row is y * softplus(-m) + beta * (1 - y) * softplus(m) in
+ * float64 from its float32 margin m, softplus(x) = max(x, 0) + log1p(exp(-|x|)); it saturates at 2^11 (a NaN term too)
+ * and is quantised as rint(term * 2^20); the value reported is sum / 2^20 / rows.  With y in {0, 1} only the product that
+ * does not vanish is computed, so an infinite margin on the row's own side costs 0 (not 0 * inf) and one on the other
+ * side the cap.  Every number is an integer sum: the
+ * same for any schedule and from run to run.
+ *
+ * ds_auc_device: out = (concordant, ties, positives, negatives, nan_rows) of d_scores[n] with d_labels[n] (0 = negative,
+ * anything else positive), both in HBM, n in [1, 2^31).  The negatives' keys are sorted by the radix sort of the cuts;
+ * scratch: 4 n bytes of row lists and 8 bytes + 1/8 byte of tables per negative, checked against the free HBM.
+ * Enqueued on `stream` and synchronised before returning.  ds_auc does the same for host arrays on `device`.
+ * ds_weighted_logloss_device: out = (fixed-point sum, rows) of d_margins[n] with d_labels[n].
+ * For tests: ds_metrics_option("max_blocks", b) caps every grid of the metric kernels that runs over rows at b
+ * workgroups, which stride beyond it (0: back to the default; the grids of the sort are one workgroup per tile of keys).
+ * The results do not depend on it. */
+#define DS_METRIC_AUC 1u
+#define DS_METRIC_LOGLOSS 2u
+int ds_auc_device(const float *d_scores, const float *d_labels, int64_t n, int64_t out[5], void *stream);
+int ds_auc(const float *scores, const float *labels, int64_t n, int64_t out[5], int device);
+int ds_weighted_logloss_device(const float *d_margins, const float *d_labels, int64_t n, double beta, int64_t out[2],
+                               void *stream);
+int ds_metrics_option(const char *name, int64_t value);
+/* Per-round metrics of a trainer: flags = DS_METRIC_AUC | DS_METRIC_LOGLOSS (0 switches them off).  Valid only before
+ * the first step and after the labels (and the evaluation set, if any) are set; DS_E_ARG otherwise and for unknown bits.
+ * The scratch -- the lists of negative and positive rows (4 bytes per row), the sort buffers for the larger set's
+ * negatives, the counters -- is allocated here and only here.  Every later ds_trainer_step then enqueues the metric
+ * kernels after the round's own, over the training margins (ALL training rows, whatever the subsampling) and over the
+ * evaluation margins, and their counters come back with the round's one host sync.  Without flags a step launches,
+ * copies and allocates exactly what it did before.
+ * ds_trainer_metrics: the last step's values, from the host: out[0] for the training set, out[1] for the evaluation
+ * set, each (concordant, ties, positives, negatives, logloss_sum, rows); -1 for a metric not requested, a set that does
+ * not exist, or before the first step. */
+int ds_trainer_set_metrics(ds_trainer *trainer, uint32_t flags);
+int ds_trainer_metrics(ds_trainer *trainer, int64_t out[2][6]);
+/* The same for a batch, over the rows of every model's HELD-OUT fold: valid only before the first step of the batch.
+ * The rows of a fold are listed once (negatives, then positives); every step gathers the keys of the active models'
+ * held-out negatives from their margins and sorts them with the models in the grid's second dimension, so that the sort
+ * buffers hold about n / n_folds keys per model.  The step keeps its one host sync.
+ * ds_trainer_batch_metrics: out[m] as above for every model after ITS last active step; -1 for held_out = -1 and before
+ * the model's first step.
+ * ds_trainer_batch_metrics_bytes: the HBM this adds for folds of equal size (the largest fold sets the buffers: 4 n for
+ * the lists, per model 8 bytes per key and 1 KiB per 8192 keys); -1 for arguments out of range. */
+int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags);
+int ds_trainer_batch_metrics(ds_trainer_batch *batch, int64_t *out);
+int64_t ds_trainer_batch_metrics_bytes(int64_t n, int32_t n_models, int32_t n_folds);
+
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
  * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
