@@ -442,7 +442,8 @@ int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64
                                    void *stream);
 int ds_forest_contributions(ds_forest *forest, const float *rows, int64_t n, double *out, int approximate);
 /* Per query of k consecutive candidates the one with the highest probability, the first on a tie (predict.py:239-242; a
- * NaN never replaces an earlier candidate): d_best_pair[q] = q * k + its slot (an index for ds_gather_rows_device),
+ * NaN never replaces an earlier candidate, and a NaN in slot 0 is never replaced itself: it stays the best, with count
+ * 1, whatever follows): d_best_pair[q] = q * k + its slot (an index for ds_gather_rows_device),
  * d_best_row[q] = d_rows[that pair], d_best_probability[q], d_best_count[q] = the candidates that hold that
  * probability.  Asynchronous on `stream`; n_queries == 0 launches nothing. */
 int ds_best_pairs_device(const int32_t *d_rows, const float *d_probabilities, int64_t n_queries, int32_t k,
