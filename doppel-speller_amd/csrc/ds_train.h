@@ -1,7 +1,9 @@
-// The training rule's device code, shared by the single trainer (ds_train.hip) and the batched trainer
-// (ds_train_batch.hip): constants, node and parameter records and the body of every kernel of a round.  A body reads
-// blockIdx.x / blockIdx.y as its kernel documents and takes pointers to ONE model's state; the batched kernels add the
-// model as a further grid dimension and offset the pointers.  Both trainers so grow the same trees from the same code.
+// The training rule's device and host code shared by the single trainer (ds_train.hip, ds_trainer_*) and the batched
+// trainer (ds_train_batch.hip, ds_trainer_batch_*): constants, node and parameter records, the view of a round's state,
+// the body of every kernel of a round, and the host helpers of both (defined in ds_train.hip).  A body reads blockIdx.x /
+// blockIdx.y as its kernel documents and takes pointers to ONE model's state.  The round's kernels (ds_train.hip) take a
+// TrainView, add the model as a further grid dimension and offset the pointers; train_round_enqueue launches them for
+// both trainers.  The single trainer is a view of one model with nothing held out and no fold array.
 #pragma once
 
 #include "ds_common.h"
@@ -61,15 +63,99 @@ __device__ inline bool sample_row(const TrainSampling &sampling, int64_t tree, i
     return static_cast<double>(x >> 11) * 0x1.0p-53 < sampling.subsample;
 }
 
-// Host side, ds_train.hip: bins of a float32[n][nf] matrix into `out` with the cuts in HBM.  A host matrix is uploaded
-// through a temporary buffer, a matrix in HBM (in_hbm, complete before the call) is read where it lies and not kept.
-// Synchronises `stream` before it returns.
+// ---- the state of a round: M models over one binned matrix, model m's part of a per-model array at m * its stride ----
+constexpr float kTrainBaseMargin = 0.f;   // base_score 0.5
+
+struct Candidate;   // the best split of one (node, feature), below
+
+struct TrainModel {
+    TrainParams params;
+    int32_t held_out, pad;        // the fold whose rows do not train, -1 for none
+};
+
+struct TrainView {   // what every kernel of a round gets
+    const uint8_t *bins;
+    const float *labels;
+    const uint8_t *fold;          // null without folds: the kFolds = false kernels never read it
+    const int32_t *cut_offsets;
+    const TrainModel *models;     // in HBM, with `active`; both null in a view of ONE model: model 0, the record `only`
+    const int32_t *active;        // the models of this step: blockIdx.z (or the last grid dimension) indexes it
+    long long *gh;                // stride 2n
+    int32_t *node_of;             // stride n
+    float *leafsum, *probabilities;   // stride n
+    long long *hist;              // stride hist_stride
+    Node *nodes;                  // stride slots
+    int32_t *counts;              // stride slots
+    Candidate *candidates;        // stride candidate_stride
+    unsigned long long *errors;   // stride 1
+    int64_t n, hist_stride, candidate_stride;
+    int32_t nf, slots;
+    TrainModel only;              // the one model of a view without `active`: read from the kernel arguments, as the
+                                  // single trainer's parameters always were; at 10^5 rows its round is launch-bound
+    __device__ int32_t model_index(unsigned i) const { return active != nullptr ? active[i] : 0; }
+    __device__ TrainModel model(int32_t m) const
+    {
+        if (active != nullptr) return models[m];
+        return only;
+    }
+};
+
+struct TrainSamplingView {   // sampling == nullptr: of a view of ONE model, whose record is `only` and tree count `tree`
+    const TrainSampling *sampling;
+    const int32_t *trees;          // the trees every model has grown before this step
+    const uint32_t *held_before;   // stride held_stride per slot; null without folds
+    const int32_t *held_slot;      // per model: its slot of held_before, -1 for none; null without folds
+    uint8_t *masks;                // stride kMaskBytes
+    int64_t held_stride;
+    TrainSampling only;
+    int32_t tree;
+    __device__ TrainSampling record(int32_t m) const
+    {
+        if (sampling != nullptr) return sampling[m];
+        return only;
+    }
+    __device__ int32_t tree_of(int32_t m) const { return sampling != nullptr ? trees[m] : tree; }
+};
+
+inline int64_t heap_nodes(int32_t depth) { return (int64_t(2) << depth) - 1; }
+inline int64_t hist_entries(int32_t depth, int32_t nf) { return ((int64_t(1) << depth) - 1) * nf * 512; }
+inline int64_t candidate_entries(int32_t depth, int32_t nf) { return (int64_t(1) << (depth - 1)) * nf; }
+
+// ---- host side, defined in ds_train.hip ------------------------------------------------------------------------------
+// Bins of a float32[n][nf] matrix into `out` with the cuts in HBM.  A host matrix is uploaded through a temporary buffer,
+// a matrix in HBM (in_hbm, complete before the call) is read where it lies and not kept.  Synchronises `stream` before it
+// returns.
 int train_bin_matrix(hipStream_t stream, int compute_units, const float *rows, bool in_hbm, int64_t n, int32_t nf,
                      const float *d_cuts, const int32_t *d_cut_offsets, DeviceBuffer<uint8_t> &out);
 // DS_E_HIP with both numbers in the message when `bytes` (+ 64 MiB of head room) are not free on the current device
 int train_check_free(int64_t bytes, const char *what);
-// the checks of cuts / cut_offsets that every create entry makes
+// The checks that every create entry (`who`) makes.  train_check_params names the batch's model, model < 0: no model;
+// max_depth is checked by the entry, whose argument it is (an integer in one, a double of the params array in the other).
+int train_check_shape(const char *who, int64_t n, int32_t n_features);
+int train_check_params(const char *who, int32_t model, double eta, double min_child_weight, double reg_lambda,
+                       double beta);
 int train_check_cuts(const char *who, int32_t n_features, const float *cuts, const int32_t *cut_offsets);
+// every label is 0 or 1; `what` ("" or "labels: ") names the argument where an entry has more than one array
+int train_check_labels(const char *who, const char *what, const float *labels, int64_t n);
+// the three fractions in (0, 1]; reg_lambda > 0 where rows are drawn; model as for train_check_params
+int train_check_fractions(const char *who, int32_t model, const double *fractions);
+int train_check_subsample(const char *who, int32_t model, double subsample, double reg_lambda);
+// What a create entry sets up on the current device: its stream, the cuts in HBM and the compute-unit count
+int train_create_setup(const char *who, int device, int32_t n_features, const float *cuts, const int32_t *cut_offsets,
+                       hipStream_t *stream, DeviceBuffer<float> &d_cuts, DeviceBuffer<int32_t> &d_cut_offsets,
+                       int *compute_units);
+// The grid of a kernel that strides over `items` rows: at most 8 workgroups per CU, and at most the test cap
+// (ds_trainer_batch_option("max_blocks"), 0 = none) where one is set.  The results do not depend on it.
+void train_set_max_blocks(int64_t blocks);
+int64_t train_max_blocks();
+unsigned train_row_grid(int compute_units, int64_t items);
+// Enqueues one round for the n_active models of v.active on `stream` and does not synchronise: clear, the gradients
+// (with `sampling`: the feature masks, then the gradients of the rows drawn), then per level < depth (the largest
+// max_depth among the active models) histogram, split-feature, split and partition.  `folds`: v.fold holds rows out.
+int train_round_enqueue(hipStream_t stream, const TrainView &v, const TrainSamplingView *sampling, int32_t n_active,
+                        int32_t depth, bool folds, int compute_units);
+// a heap of `slots` nodes copied back from the device -> node_info int32[slots][4] and node_leaf float[slots]
+void train_unpack_heap(const Node *heap, int64_t slots, int32_t *node_info, float *node_leaf);
 
 // ---- gradients of weighted_log_loss at the current margins ---------------------------------------------------------
 // kFolds: a row with fold[r] == held_out does not train: its (g, h) is (0, 0); everything else is written as for any row

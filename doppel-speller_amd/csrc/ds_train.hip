@@ -6,14 +6,18 @@
 //   bins      uint8[nf][n]   feature-major: bin b < 255 of a value, 255 = NaN (the missing bin)
 //   gh        int64[n][2]    quantized gradient and hessian of the current round, rint(g * 2^30), rint(h * 2^30)
 //   node_of   int32[n]       heap id of the node a row sits in while a tree grows (-1: its leaf is already added)
-//   leafsum   float[n]       sum of the leaves of the trees so far, in tree order (margin = base_margin + leafsum)
+//   leafsum   float[n]       sum of the leaves of the trees so far, in tree order (margin = kTrainBaseMargin + leafsum)
 //   hist      int64[2^D - 1][nf][256][2]  per split candidate node (heap order, levels 0..D-1): (sum qg, sum qh)
 //                            per bin; entry 255 = the missing bin
 //   nodes     Node[2^(D+1) - 1] the tree being grown, heap order (children of i: 2i + 1, 2i + 2)
 // Integer sums do not depend on the order of their terms: histograms, splits and trees are identical under any
 // schedule and from run to run.
-// The rule's device code lives in ds_train.h, shared with the batched trainer (ds_train_batch.hip); the kernels here
-// run it for one model.
+// The rule's device code lives in ds_train.h.  This file holds the kernels of a round, which run it for the models of a
+// TrainView, the one launcher of a round (train_round_enqueue) and the host checks and helpers of both trainers, and the
+// single trainer: a view of one model with nothing held out.  The batched trainer (ds_train_batch.hip) launches the same
+// kernels through the same launcher with the model as a further grid dimension.
+#include <atomic>
+
 #include "ds_metrics.h"
 #include "ds_train.h"
 
@@ -56,76 +60,97 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_bin_kernel(const float *
     }
 }
 
-// ---- the kernels of a round: ds_train.h's bodies for the one model of a ds_trainer --------------------------------
-__global__ __launch_bounds__(kRowThreads) void ds_train_gradient_kernel(const float *leafsum, const float *labels,
-                                                                         int64_t n, float base_margin, double beta,
-                                                                         float *probabilities, long long *gh,
-                                                                         int32_t *node_of)
+// ---- the kernels of a round: ds_train.h's bodies for the models of a TrainView, of either trainer --------------------
+// The model is v.active[the last grid dimension] (model 0 of a one-model view); the blocks of a model that has passed its own max_depth return at once.
+// kFolds = false (the single trainer) reads no fold byte; kSampled = false reads nothing of the sampling view.
+
+// start of a round: zero the active models' histograms (levels below their own max_depth), heaps, counts, errors
+__global__ __launch_bounds__(kRowThreads) void ds_train_clear_kernel(TrainView v)
 {
-    train_gradient_rows<false>(leafsum, labels, n, base_margin, beta, probabilities, gh, node_of, nullptr, -1);
+    const int32_t m = v.model_index(blockIdx.y);
+    const int64_t at = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x;
+    const int64_t step = static_cast<int64_t>(gridDim.x) * kRowThreads;
+    const int64_t pairs = ((int64_t(1) << v.model(m).params.max_depth) - 1) * v.nf * 256;   // (g, h) of one bin
+    ulonglong2 *hist = reinterpret_cast<ulonglong2 *>(v.hist + m * v.hist_stride);
+    for (int64_t i = at; i < pairs; i += step) hist[i] = make_ulonglong2(0ull, 0ull);
+    uint32_t *nodes = reinterpret_cast<uint32_t *>(v.nodes + static_cast<int64_t>(m) * v.slots);
+    for (int64_t i = at; i < int64_t(v.slots) * (sizeof(Node) / 4); i += step) nodes[i] = 0u;
+    int32_t *counts = v.counts + static_cast<int64_t>(m) * v.slots;
+    for (int64_t i = at; i < v.slots; i += step) counts[i] = 0;
+    if (at == 0) v.errors[m] = 0ull;
 }
 
-__global__ __launch_bounds__(kHistThreads) void ds_train_histogram_kernel(
-    const uint8_t *bins, const long long *gh, const int32_t *node_of, const int32_t *counts, const Node *nodes,
-    int64_t n, int32_t nf, int32_t level, int32_t n_built, int32_t nodes_per_group, int32_t features_per_group,
-    int32_t feature_groups, unsigned long long *hist)
+// the feature sets of the round: blockIdx.x = the model
+__global__ __launch_bounds__(kMaskThreads) void ds_train_feature_mask_kernel(TrainView v, TrainSamplingView s)
 {
-    train_histogram_group<false>(bins, gh, node_of, counts, nodes, n, nf, level, n_built, nodes_per_group,
-                                 features_per_group, feature_groups, hist, nullptr, -1);
+    const int32_t m = v.model_index(blockIdx.x);
+    const TrainSampling sampling = s.record(m);   // in registers, as in the gradient kernel
+    train_feature_masks(sampling, s.tree_of(m), v.nf, v.model(m).params.max_depth,
+                        s.masks + static_cast<int64_t>(m) * kMaskBytes);
 }
 
-__global__ __launch_bounds__(256) void ds_train_split_feature_kernel(long long *hist, const int32_t *counts,
-                                                                      const Node *nodes, const int32_t *cut_offsets,
-                                                                      int32_t nf, int32_t level, TrainParams params,
-                                                                      Candidate *candidates)
+// blockIdx.x = a stride of rows, blockIdx.y = the model
+template <bool kFolds, bool kSampled>
+__global__ __launch_bounds__(kRowThreads) void ds_train_gradient_kernel(TrainView v, TrainSamplingView s)
 {
-    train_split_feature(hist, counts, nodes, cut_offsets, nf, level, params, candidates);
+    const int32_t m = v.model_index(blockIdx.y);
+    const TrainModel model = v.model(m);
+    TrainSampling sampling{};   // a copy in registers: through the pointer the body's row loop re-reads it past its stores
+    if (kSampled) sampling = s.record(m);
+    const uint32_t *held_before = nullptr;
+    if (kFolds && kSampled && s.held_slot[m] >= 0) held_before = s.held_before + s.held_slot[m] * s.held_stride;
+    train_gradient_rows<kFolds, kSampled>(v.leafsum + m * v.n, v.labels, v.n, kTrainBaseMargin, model.params.beta,
+                                          v.probabilities + m * v.n, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.fold,
+                                          model.held_out, kSampled ? &sampling : nullptr,
+                                          kSampled ? s.tree_of(m) : 0, held_before);
 }
 
-// ---- the same round with row and column subsampling (ds_trainer_set_sampling): the kSampled bodies -------------------
-__global__ __launch_bounds__(kMaskThreads) void ds_train_feature_mask_kernel(TrainSampling sampling, int64_t tree,
-                                                                              int32_t nf, int32_t max_depth,
-                                                                              uint8_t *mask)
+// blockIdx.x = the chunk of rows, blockIdx.y = (feature group, node group), blockIdx.z = the model
+template <bool kFolds, bool kSampled>
+__global__ __launch_bounds__(kHistThreads) void ds_train_histogram_kernel(TrainView v, int32_t level, int32_t n_built,
+                                                                           int32_t nodes_per_group,
+                                                                           int32_t features_per_group,
+                                                                           int32_t feature_groups)
 {
-    train_feature_masks(sampling, tree, nf, max_depth, mask);
+    const int32_t m = v.model_index(blockIdx.z);
+    const TrainModel model = v.model(m);
+    if (level >= model.params.max_depth) return;   // the model's tree is finished: nothing pending
+    train_histogram_group<kFolds, kSampled>(v.bins, v.gh + 2 * m * v.n, v.node_of + m * v.n,
+                                            v.counts + int64_t(m) * v.slots, v.nodes + int64_t(m) * v.slots, v.n, v.nf,
+                                            level, n_built, nodes_per_group, features_per_group, feature_groups,
+                                            reinterpret_cast<unsigned long long *>(v.hist + m * v.hist_stride), v.fold,
+                                            model.held_out);
 }
 
-__global__ __launch_bounds__(kRowThreads) void ds_train_gradient_sampled_kernel(
-    const float *leafsum, const float *labels, int64_t n, float base_margin, double beta, float *probabilities,
-    long long *gh, int32_t *node_of, TrainSampling sampling, int64_t tree)
+// blockIdx.x = the node's index in its level, blockIdx.y = the feature, blockIdx.z = the model
+template <bool kSampled>
+__global__ __launch_bounds__(256) void ds_train_split_feature_kernel(TrainView v, TrainSamplingView s, int32_t level)
 {
-    train_gradient_rows<false, true>(leafsum, labels, n, base_margin, beta, probabilities, gh, node_of, nullptr, -1,
-                                     &sampling, tree, nullptr);
+    const int32_t m = v.model_index(blockIdx.z);
+    const TrainModel model = v.model(m);
+    if (level >= model.params.max_depth) return;
+    train_split_feature<kSampled>(v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots,
+                                  v.nodes + int64_t(m) * v.slots, v.cut_offsets, v.nf, level, model.params,
+                                  v.candidates + m * v.candidate_stride,
+                                  kSampled ? s.masks + static_cast<int64_t>(m) * kMaskBytes + level * kTrainFeaturesMax
+                                           : nullptr);
 }
 
-__global__ __launch_bounds__(kHistThreads) void ds_train_histogram_sampled_kernel(
-    const uint8_t *bins, const long long *gh, const int32_t *node_of, const int32_t *counts, const Node *nodes,
-    int64_t n, int32_t nf, int32_t level, int32_t n_built, int32_t nodes_per_group, int32_t features_per_group,
-    int32_t feature_groups, unsigned long long *hist)
+// blockIdx.x = 64 nodes of the level, blockIdx.y = the model
+__global__ __launch_bounds__(64) void ds_train_split_kernel(TrainView v, int32_t level)
 {
-    train_histogram_group<false, true>(bins, gh, node_of, counts, nodes, n, nf, level, n_built, nodes_per_group,
-                                       features_per_group, feature_groups, hist, nullptr, -1);
+    const int32_t m = v.model_index(blockIdx.y);
+    const TrainModel model = v.model(m);
+    if (level >= model.params.max_depth) return;
+    train_split_nodes(v.candidates + m * v.candidate_stride, v.nodes + int64_t(m) * v.slots, v.nf, level, model.params);
 }
 
-__global__ __launch_bounds__(256) void ds_train_split_feature_sampled_kernel(
-    long long *hist, const int32_t *counts, const Node *nodes, const int32_t *cut_offsets, int32_t nf, int32_t level,
-    TrainParams params, Candidate *candidates, const uint8_t *mask)
+__global__ __launch_bounds__(kRowThreads) void ds_train_partition_kernel(TrainView v, int32_t level)
 {
-    train_split_feature<true>(hist, counts, nodes, cut_offsets, nf, level, params, candidates,
-                              mask + level * kTrainFeaturesMax);
-}
-
-__global__ __launch_bounds__(64) void ds_train_split_kernel(const Candidate *candidates, Node *nodes, int32_t nf,
-                                                             int32_t level, TrainParams params)
-{
-    train_split_nodes(candidates, nodes, nf, level, params);
-}
-
-__global__ __launch_bounds__(kRowThreads) void ds_train_partition_kernel(const uint8_t *bins, const Node *nodes,
-                                                                          int64_t n, int32_t level, int32_t *node_of,
-                                                                          float *leafsum, int32_t *counts)
-{
-    train_partition_rows(bins, nodes, n, level, node_of, leafsum, counts);
+    const int32_t m = v.model_index(blockIdx.y);
+    if (level >= v.model(m).params.max_depth) return;
+    train_partition_rows(v.bins, v.nodes + int64_t(m) * v.slots, v.n, level, v.node_of + m * v.n, v.leafsum + m * v.n,
+                         v.counts + int64_t(m) * v.slots);
 }
 
 // ---- evaluation rows: add the new tree, then the custom error of train.py:fast_custom_error ------------------------
@@ -178,7 +203,7 @@ __global__ __launch_bounds__(kRowThreads) void ds_gather_rows_kernel(const uint3
     }
 }
 
-// ---- host helpers shared with ds_train_batch.hip (declared in ds_train.h) ------------------------------------------
+// ---- host code of both trainers (declared in ds_train.h) -------------------------------------------------------------
 int train_bin_matrix(hipStream_t stream, int compute_units, const float *rows, bool in_hbm, int64_t n, int32_t nf,
                      const float *d_cuts, const int32_t *d_cut_offsets, DeviceBuffer<uint8_t> &out)
 {
@@ -220,6 +245,168 @@ int train_check_cuts(const char *who, int32_t n_features, const float *cuts, con
     return DS_OK;
 }
 
+int train_check_shape(const char *who, int64_t n, int32_t n_features)
+{
+    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
+    DS_REQUIRE(n_features >= 1 && n_features <= kTrainFeaturesMax, "%s: n_features = %d out of range [1, %d]", who,
+               n_features, kTrainFeaturesMax);
+    return DS_OK;
+}
+
+namespace {
+
+// the part of a refusal that names the batch's model: `format` with its index, nothing for model < 0
+struct ModelName {
+    char text[32] = "";
+    ModelName(const char *format, int32_t model)
+    {
+        if (model >= 0) std::snprintf(text, sizeof(text), format, model);
+    }
+};
+
+}  // namespace
+
+int train_check_params(const char *who, int32_t model, double eta, double min_child_weight, double reg_lambda,
+                       double beta)
+{
+    const ModelName name("params of model %d: ", model);
+    DS_REQUIRE(eta > 0 && eta < 1e30 && min_child_weight >= 0 && min_child_weight < 1e30 && reg_lambda >= 0 &&
+                   reg_lambda < 1e30 && beta > 0 && beta < 1e30 && reg_lambda + min_child_weight > 0,
+               "%s: %seta, beta must be positive, min_child_weight, reg_lambda non-negative and not both 0", who,
+               name.text);
+    return DS_OK;
+}
+
+int train_check_labels(const char *who, const char *what, const float *labels, int64_t n)
+{
+    for (int64_t r = 0; r < n; ++r)
+        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "%s: %slabel %lld is not 0 or 1", who, what, (long long)r);
+    return DS_OK;
+}
+
+int train_check_fractions(const char *who, int32_t model, const double *fractions)
+{
+    const ModelName name("model %d: ", model);
+    const char *names[3] = {"subsample", "colsample_bytree", "colsample_bylevel"};
+    for (int i = 0; i < 3; ++i)
+        DS_REQUIRE(fractions[i] > 0 && fractions[i] <= 1, "%s: %s%s = %g out of range (0, 1]", who, name.text, names[i],
+                   fractions[i]);
+    return DS_OK;
+}
+
+int train_check_subsample(const char *who, int32_t model, double subsample, double reg_lambda)
+{
+    const ModelName name("model %d: ", model);
+    DS_REQUIRE(subsample == 1 || reg_lambda > 0, "%s: %ssubsample < 1 needs reg_lambda > 0 (a round may draw no row)", who,
+               name.text);
+    return DS_OK;
+}
+
+int train_create_setup(const char *who, int device, int32_t n_features, const float *cuts, const int32_t *cut_offsets,
+                       hipStream_t *stream, DeviceBuffer<float> &d_cuts, DeviceBuffer<int32_t> &d_cut_offsets,
+                       int *compute_units)
+{
+    hipDeviceProp_t props;
+    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
+        *compute_units = props.multiProcessorCount;
+    if (hipStreamCreateWithFlags(stream, hipStreamNonBlocking) != hipSuccess) {
+        set_error("%s: hipStreamCreate failed", who);
+        return DS_E_HIP;
+    }
+    int status = d_cut_offsets.upload(cut_offsets, static_cast<size_t>(n_features) + 1);
+    if (status == DS_OK) status = d_cuts.allocate(std::max<size_t>(1, static_cast<size_t>(cut_offsets[n_features])));
+    if (status == DS_OK && cut_offsets[n_features] > 0)
+        status = d_cuts.upload(cuts, static_cast<size_t>(cut_offsets[n_features]));
+    return status;
+}
+
+void train_unpack_heap(const Node *heap, int64_t slots, int32_t *node_info, float *node_leaf)
+{
+    for (int64_t i = 0; i < slots; ++i) {
+        const Node &node = heap[i];
+        node_info[4 * i] = node.state;
+        node_info[4 * i + 1] = node.feature;
+        node_info[4 * i + 2] = node.bin;
+        node_info[4 * i + 3] = node.default_left;
+        node_leaf[i] = node.leaf;
+    }
+}
+
+// ---- one round of either trainer --------------------------------------------------------------------------------------
+namespace {
+
+std::atomic<int64_t> g_max_blocks{0};   // ds_trainer_batch_option("max_blocks"): 0 = no cap
+
+int64_t capped(int64_t blocks)
+{
+    const int64_t cap = g_max_blocks.load();
+    return std::max<int64_t>(1, cap > 0 ? std::min(blocks, cap) : blocks);
+}
+
+template <bool kFolds, bool kSampled>
+int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingView &s, int32_t n_active, int32_t depth,
+                  int compute_units)
+{
+    const unsigned models = static_cast<unsigned>(n_active);
+    const dim3 rows(train_row_grid(compute_units, v.n), models);
+    hipLaunchKernelGGL(ds_train_clear_kernel, dim3(train_row_grid(compute_units, v.hist_stride / 2), models),
+                       dim3(kRowThreads), 0, stream, v);
+    DS_HIP(hipGetLastError());
+    if (kSampled) {   // the feature sets of this tree's levels, before the gradients of the rows drawn for it
+        hipLaunchKernelGGL(ds_train_feature_mask_kernel, dim3(models), dim3(kMaskThreads), 0, stream, v, s);
+        DS_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL((ds_train_gradient_kernel<kFolds, kSampled>), rows, dim3(kRowThreads), 0, stream, v, s);
+    DS_HIP(hipGetLastError());
+    for (int32_t level = 0; level < depth; ++level) {
+        const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
+        const int32_t nodes_per_group = std::min(n_built, kHistSlots);
+        const int32_t features_per_group = std::min<int32_t>(v.nf, kHistSlots / nodes_per_group);
+        const int32_t feature_groups = (v.nf + features_per_group - 1) / features_per_group;
+        const int32_t node_groups = (n_built + nodes_per_group - 1) / nodes_per_group;
+        const int64_t groups = int64_t(feature_groups) * node_groups * n_active;
+        // about 4 workgroups per CU in all, counted over the models, each over at least 2048 rows: the LDS adds dominate,
+        // the flush (<= 8192 global adds per workgroup) stays a small part
+        const int64_t chunks = capped(std::min<int64_t>((v.n + 2047) / 2048,
+                                                        (int64_t(compute_units) * 4 + groups - 1) / groups));
+        hipLaunchKernelGGL((ds_train_histogram_kernel<kFolds, kSampled>),
+                           dim3(static_cast<unsigned>(chunks), feature_groups * node_groups, models), dim3(kHistThreads),
+                           0, stream, v, level, n_built, nodes_per_group, features_per_group, feature_groups);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds_train_split_feature_kernel<kSampled>, dim3(1u << level, v.nf, models), dim3(256), 0,
+                           stream, v, s, level);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds_train_split_kernel, dim3(((1u << level) + 63) / 64, models), dim3(64), 0, stream, v,
+                           level);
+        DS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ds_train_partition_kernel, rows, dim3(kRowThreads), 0, stream, v, level);
+        DS_HIP(hipGetLastError());
+    }
+    return DS_OK;
+}
+
+}  // namespace
+
+void train_set_max_blocks(int64_t blocks) { g_max_blocks.store(blocks); }
+int64_t train_max_blocks() { return g_max_blocks.load(); }
+
+unsigned train_row_grid(int compute_units, int64_t items)
+{
+    return static_cast<unsigned>(capped(std::min<int64_t>((items + kRowThreads - 1) / kRowThreads,
+                                                          int64_t(compute_units) * 8)));
+}
+
+int train_round_enqueue(hipStream_t stream, const TrainView &v, const TrainSamplingView *sampling, int32_t n_active,
+                        int32_t depth, bool folds, int compute_units)
+{
+    const TrainSamplingView none{};
+    if (sampling != nullptr)
+        return folds ? enqueue_round<true, true>(stream, v, *sampling, n_active, depth, compute_units)
+                     : enqueue_round<false, true>(stream, v, *sampling, n_active, depth, compute_units);
+    return folds ? enqueue_round<true, false>(stream, v, none, n_active, depth, compute_units)
+                 : enqueue_round<false, false>(stream, v, none, n_active, depth, compute_units);
+}
+
 }  // namespace ds
 
 struct ds_trainer {
@@ -227,7 +414,6 @@ struct ds_trainer {
     int64_t n = 0, n_eval = 0;
     int32_t nf = 0;
     ds::TrainParams params{};
-    float base_margin = 0.f;
     bool has_labels = false;
     int64_t rounds = 0;
     hipStream_t stream = nullptr;
@@ -238,9 +424,10 @@ struct ds_trainer {
     ds::DeviceBuffer<ds::Node> nodes;
     ds::DeviceBuffer<ds::Candidate> candidates;   // [2^(max_depth - 1)][nf]: the best split per (node, feature)
     ds::DeviceBuffer<unsigned long long> error;
+    ds::TrainView view{};                         // of this one model (`only`), strides = the array sizes, no folds
     bool sampled = false;                         // ds_trainer_set_sampling with a fraction below 1
-    ds::TrainSampling sampling{1.0, 1.0, 1.0, 0};
     ds::DeviceBuffer<uint8_t> masks;              // [kTrainMaxDepth][kTrainFeaturesMax]: the feature sets of the round
+    ds::TrainSamplingView sampling_view{};
     std::vector<int32_t> host_offsets;
     ds::Node *pinned_nodes = nullptr;
     unsigned long long *pinned_error = nullptr;
@@ -265,7 +452,7 @@ struct ds_trainer {
 
 namespace {
 
-int64_t heap_nodes(int32_t depth) { return (int64_t(2) << depth) - 1; }
+using ds::heap_nodes;
 
 int bin_matrix(ds_trainer *t, const float *rows, bool in_hbm, int64_t n, ds::DeviceBuffer<uint8_t> &out)
 {
@@ -273,12 +460,6 @@ int bin_matrix(ds_trainer *t, const float *rows, bool in_hbm, int64_t n, ds::Dev
 }
 
 int check_free(int64_t bytes, const char *what) { return ds::train_check_free(bytes, what); }
-
-int row_grid(const ds_trainer *t, int64_t n)
-{
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>((n + ds::kRowThreads - 1) / ds::kRowThreads,
-                                                                   int64_t(t->compute_units) * 8)));
-}
 
 // ds_trainer_create (`who`, features on the host) and ds_trainer_create_device (features in HBM)
 int create_trainer(const char *who, const float *features, bool in_hbm, int64_t n, int32_t n_features, const float *cuts,
@@ -288,16 +469,13 @@ int create_trainer(const char *who, const float *features, bool in_hbm, int64_t 
     DS_REQUIRE(out != nullptr, "%s: out is null", who);
     *out = nullptr;
     DS_REQUIRE(features && cuts && cut_offsets, "%s: null input", who);
-    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
-    DS_REQUIRE(n_features >= 1 && n_features <= ds::kTrainFeaturesMax,
-               "%s: n_features = %d out of range [1, %d]", who, n_features, ds::kTrainFeaturesMax);
+    if (int status = ds::train_check_shape(who, n, n_features); status != DS_OK) return status;
     DS_REQUIRE(max_depth >= 1 && max_depth <= ds::kTrainMaxDepth, "%s: max_depth = %d out of range [1, %d]", who,
                max_depth, ds::kTrainMaxDepth);
-    DS_REQUIRE(eta > 0 && eta < 1e30 && min_child_weight >= 0 && min_child_weight < 1e30 && reg_lambda >= 0 &&
-                   reg_lambda < 1e30 && beta > 0 && beta < 1e30 && reg_lambda + min_child_weight > 0,
-               "%s: eta, beta must be positive, min_child_weight, reg_lambda non-negative and not both 0", who);
+    if (int status = ds::train_check_params(who, -1, eta, min_child_weight, reg_lambda, beta); status != DS_OK)
+        return status;
     if (int status = ds::train_check_cuts(who, n_features, cuts, cut_offsets); status != DS_OK) return status;
-    const int64_t hist_bytes = ((int64_t(1) << max_depth) - 1) * n_features * 512 * 8;
+    const int64_t hist_bytes = ds::hist_entries(max_depth, n_features) * 8;
     // bins (+ the staged rows of a host matrix), per-row state, histograms
     const int64_t bytes = n * n_features * (in_hbm ? 1 : 5) + n * 36 + hist_bytes;
     DS_HIP(hipSetDevice(device));
@@ -308,15 +486,8 @@ int create_trainer(const char *who, const float *features, bool in_hbm, int64_t 
     t->nf = n_features;
     t->params = ds::TrainParams{max_depth, eta, min_child_weight, reg_lambda, beta};
     t->host_offsets.assign(cut_offsets, cut_offsets + n_features + 1);
-    hipDeviceProp_t props;
-    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
-        t->compute_units = props.multiProcessorCount;
-    int status = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) == hipSuccess ? DS_OK : DS_E_HIP;
-    if (status != DS_OK) ds::set_error("%s: hipStreamCreate failed", who);
-    if (status == DS_OK) status = t->cut_offsets.upload(cut_offsets, static_cast<size_t>(n_features) + 1);
-    if (status == DS_OK) status = t->cuts.allocate(std::max<size_t>(1, static_cast<size_t>(cut_offsets[n_features])));
-    if (status == DS_OK && cut_offsets[n_features] > 0)
-        status = t->cuts.upload(cuts, static_cast<size_t>(cut_offsets[n_features]));
+    int status = ds::train_create_setup(who, device, n_features, cuts, cut_offsets, &t->stream, t->cuts, t->cut_offsets,
+                                        &t->compute_units);
     if (status == DS_OK) status = bin_matrix(t, features, in_hbm, n, t->bins);
     if (status == DS_OK) status = t->labels.allocate(n);
     if (status == DS_OK) status = t->leafsum.allocate(n);
@@ -326,7 +497,7 @@ int create_trainer(const char *who, const float *features, bool in_hbm, int64_t 
     if (status == DS_OK) status = t->hist.allocate(static_cast<size_t>(hist_bytes / 8));
     if (status == DS_OK) status = t->counts.allocate(heap_nodes(max_depth));
     if (status == DS_OK) status = t->nodes.allocate(heap_nodes(max_depth));
-    if (status == DS_OK) status = t->candidates.allocate((size_t(1) << (max_depth - 1)) * n_features);
+    if (status == DS_OK) status = t->candidates.allocate(static_cast<size_t>(ds::candidate_entries(max_depth, n_features)));
     if (status == DS_OK) status = t->error.allocate(1);
     if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&t->pinned_nodes),
                                          sizeof(ds::Node) * heap_nodes(max_depth)) != hipSuccess) status = DS_E_HIP;
@@ -339,6 +510,11 @@ int create_trainer(const char *who, const float *features, bool in_hbm, int64_t 
         delete t;
         return status;
     }
+    t->view = ds::TrainView{t->bins.ptr, t->labels.ptr, nullptr, t->cut_offsets.ptr, nullptr, nullptr,
+                            t->gh.ptr, t->node_of.ptr, t->leafsum.ptr, t->probabilities.ptr, t->hist.ptr, t->nodes.ptr,
+                            t->counts.ptr, t->candidates.ptr, t->error.ptr, n, hist_bytes / 8,
+                            ds::candidate_entries(max_depth, n_features), n_features,
+                            static_cast<int32_t>(heap_nodes(max_depth)), ds::TrainModel{t->params, -1, 0}};
     *out = t;
     return DS_OK;
 }
@@ -350,8 +526,7 @@ int set_eval(const char *who, ds_trainer *trainer, const float *features, bool i
     DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
     DS_REQUIRE(trainer->rounds == 0, "%s: the evaluation set must be given before the first round", who);
     DS_REQUIRE(trainer->metric_flags == 0, "%s: the evaluation set must be given before ds_trainer_set_metrics", who);
-    for (int64_t r = 0; r < n; ++r)
-        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "%s: label %lld is not 0 or 1", who, (long long)r);
+    if (int status = ds::train_check_labels(who, "", labels, n); status != DS_OK) return status;
     DS_HIP(hipSetDevice(trainer->device));
     if (int status = check_free(n * trainer->nf * (in_hbm ? 1 : 5) + n * 8, who); status != DS_OK) return status;
     int status = bin_matrix(trainer, features, in_hbm, n, trainer->eval_bins);
@@ -395,8 +570,8 @@ int ds_trainer_set_labels(ds_trainer *trainer, const float *labels)
 {
     DS_REQUIRE(trainer && labels, "ds_trainer_set_labels: null argument");
     DS_REQUIRE(trainer->metric_flags == 0, "ds_trainer_set_labels: the labels must be set before ds_trainer_set_metrics");
-    for (int64_t r = 0; r < trainer->n; ++r)
-        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "ds_trainer_set_labels: label %lld is not 0 or 1", (long long)r);
+    if (int status = ds::train_check_labels("ds_trainer_set_labels", "", labels, trainer->n); status != DS_OK)
+        return status;
     DS_HIP(hipSetDevice(trainer->device));
     DS_HIP(hipMemcpyAsync(trainer->labels.ptr, labels, sizeof(float) * trainer->n, hipMemcpyHostToDevice,
                           trainer->stream));
@@ -419,21 +594,20 @@ int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsam
                             uint64_t sample_seed)
 {
     DS_REQUIRE(trainer != nullptr, "ds_trainer_set_sampling: trainer is null");
+    ds_trainer *t = trainer;
     const double fractions[3] = {subsample, colsample_bytree, colsample_bylevel};
-    const char *names[3] = {"subsample", "colsample_bytree", "colsample_bylevel"};
-    for (int i = 0; i < 3; ++i)
-        DS_REQUIRE(fractions[i] > 0 && fractions[i] <= 1, "ds_trainer_set_sampling: %s = %g out of range (0, 1]",
-                   names[i], fractions[i]);
-    DS_REQUIRE(trainer->rounds == 0, "ds_trainer_set_sampling: the sampling must be set before the first round");
-    DS_REQUIRE(subsample == 1 || trainer->params.reg_lambda > 0,
-               "ds_trainer_set_sampling: subsample < 1 needs reg_lambda > 0 (a round may draw no row)");
+    if (int status = ds::train_check_fractions("ds_trainer_set_sampling", -1, fractions); status != DS_OK) return status;
+    DS_REQUIRE(t->rounds == 0, "ds_trainer_set_sampling: the sampling must be set before the first round");
+    if (int status = ds::train_check_subsample("ds_trainer_set_sampling", -1, subsample, t->params.reg_lambda);
+        status != DS_OK)
+        return status;
     const ds::TrainSampling sampling{subsample, colsample_bytree, colsample_bylevel, sample_seed};
-    if (sampling.any() && trainer->masks.ptr == nullptr) {
-        DS_HIP(hipSetDevice(trainer->device));
-        if (int status = trainer->masks.allocate(ds::kMaskBytes); status != DS_OK) return status;
+    if (sampling.any() && t->masks.ptr == nullptr) {
+        DS_HIP(hipSetDevice(t->device));
+        if (int status = t->masks.allocate(ds::kMaskBytes); status != DS_OK) return status;
     }
-    trainer->sampling = sampling;
-    trainer->sampled = sampling.any();
+    t->sampling_view = ds::TrainSamplingView{nullptr, nullptr, nullptr, nullptr, t->masks.ptr, 0, sampling, 0};
+    t->sampled = sampling.any();   // every fraction 1: the plain kernels, whatever was set before
     return DS_OK;
 }
 
@@ -487,7 +661,7 @@ int ds_trainer_set_metrics(ds_trainer *trainer, uint32_t flags)
         const int32_t *list = t->metric_rows.ptr + first[set];
         t->metric_host[set] = ds::MetricColumn{d_scores[set], list, list + negatives[set],
                                                static_cast<int32_t>(negatives[set]),
-                                               static_cast<int32_t>(sizes[set] - negatives[set]), t->base_margin, 0,
+                                               static_cast<int32_t>(sizes[set] - negatives[set]), ds::kTrainBaseMargin, 0,
                                                t->params.beta};
     }
     DS_HIP(hipMemcpy(t->metric_columns.ptr, t->metric_host, sizeof(t->metric_host), hipMemcpyHostToDevice));
@@ -548,65 +722,19 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
     ds_trainer *t = trainer;
     DS_HIP(hipSetDevice(t->device));
     const int32_t depth = t->params.max_depth;
-    const int64_t slots = heap_nodes(depth), n = t->n;
     hipStream_t stream = t->stream;
-    DS_HIP(hipMemsetAsync(t->hist.ptr, 0, t->hist.bytes(), stream));
-    DS_HIP(hipMemsetAsync(t->nodes.ptr, 0, t->nodes.bytes(), stream));
-    DS_HIP(hipMemsetAsync(t->counts.ptr, 0, t->counts.bytes(), stream));
-    DS_HIP(hipMemsetAsync(t->error.ptr, 0, sizeof(unsigned long long), stream));
-    if (t->sampled) {   // the feature sets of this tree's levels, then the gradients of the rows drawn for it
-        hipLaunchKernelGGL(ds::ds_train_feature_mask_kernel, dim3(1), dim3(ds::kMaskThreads), 0, stream, t->sampling,
-                           t->rounds, t->nf, depth, t->masks.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_train_gradient_sampled_kernel, dim3(row_grid(t, n)), dim3(ds::kRowThreads), 0, stream,
-                           t->leafsum.ptr, t->labels.ptr, n, t->base_margin, t->params.beta, t->probabilities.ptr,
-                           t->gh.ptr, t->node_of.ptr, t->sampling, t->rounds);
-    } else {
-        hipLaunchKernelGGL(ds::ds_train_gradient_kernel, dim3(row_grid(t, n)), dim3(ds::kRowThreads), 0, stream,
-                           t->leafsum.ptr, t->labels.ptr, n, t->base_margin, t->params.beta, t->probabilities.ptr,
-                           t->gh.ptr, t->node_of.ptr);
-    }
-    DS_HIP(hipGetLastError());
-    for (int32_t level = 0; level < depth; ++level) {
-        const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
-        const int32_t nodes_per_group = std::min(n_built, ds::kHistSlots);
-        const int32_t features_per_group = std::min<int32_t>(t->nf, ds::kHistSlots / nodes_per_group);
-        const int32_t feature_groups = (t->nf + features_per_group - 1) / features_per_group;
-        const int32_t node_groups = (n_built + nodes_per_group - 1) / nodes_per_group;
-        const int32_t groups = feature_groups * node_groups;
-        // about 4 workgroups per CU in all, each over at least 2048 rows: the LDS adds dominate, the flush (<= 8192
-        // global adds per workgroup) stays a small part
-        const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048,
-                                                                      (int64_t(t->compute_units) * 4 + groups - 1) / groups));
-        hipLaunchKernelGGL(t->sampled ? ds::ds_train_histogram_sampled_kernel : ds::ds_train_histogram_kernel,
-                           dim3(static_cast<unsigned>(chunks), groups),
-                           dim3(ds::kHistThreads), 0, stream, t->bins.ptr, t->gh.ptr, t->node_of.ptr, t->counts.ptr,
-                           t->nodes.ptr, n, t->nf, level, n_built, nodes_per_group, features_per_group, feature_groups,
-                           reinterpret_cast<unsigned long long *>(t->hist.ptr));
-        DS_HIP(hipGetLastError());
-        if (t->sampled)
-            hipLaunchKernelGGL(ds::ds_train_split_feature_sampled_kernel, dim3(1u << level, t->nf), dim3(256), 0, stream,
-                               t->hist.ptr, t->counts.ptr, t->nodes.ptr, t->cut_offsets.ptr, t->nf, level, t->params,
-                               t->candidates.ptr, t->masks.ptr);
-        else
-            hipLaunchKernelGGL(ds::ds_train_split_feature_kernel, dim3(1u << level, t->nf), dim3(256), 0, stream,
-                               t->hist.ptr, t->counts.ptr, t->nodes.ptr, t->cut_offsets.ptr, t->nf, level, t->params,
-                               t->candidates.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_train_split_kernel, dim3(((1u << level) + 63) / 64), dim3(64), 0, stream,
-                           t->candidates.ptr, t->nodes.ptr, t->nf, level, t->params);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_train_partition_kernel, dim3(row_grid(t, n)), dim3(ds::kRowThreads), 0, stream,
-                           t->bins.ptr, t->nodes.ptr, n, level, t->node_of.ptr, t->leafsum.ptr, t->counts.ptr);
-        DS_HIP(hipGetLastError());
-    }
+    if (t->sampled) t->sampling_view.tree = static_cast<int32_t>(t->rounds);   // this tree's number indexes its streams
+    if (int status = ds::train_round_enqueue(stream, t->view, t->sampled ? &t->sampling_view : nullptr, 1, depth, false,
+                                             t->compute_units);
+        status != DS_OK)
+        return status;
     if (t->n_eval > 0) {
-        hipLaunchKernelGGL(ds::ds_train_eval_kernel, dim3(row_grid(t, t->n_eval)), dim3(ds::kRowThreads), 0, stream,
-                           t->eval_bins.ptr, t->nodes.ptr, t->n_eval, t->eval_labels.ptr, t->base_margin,
-                           t->eval_leafsum.ptr, t->error.ptr);
+        hipLaunchKernelGGL(ds::ds_train_eval_kernel, dim3(ds::train_row_grid(t->compute_units, t->n_eval)),
+                           dim3(ds::kRowThreads), 0, stream, t->eval_bins.ptr, t->nodes.ptr, t->n_eval,
+                           t->eval_labels.ptr, ds::kTrainBaseMargin, t->eval_leafsum.ptr, t->error.ptr);
         DS_HIP(hipGetLastError());
     }
-    DS_HIP(hipMemcpyAsync(t->pinned_nodes, t->nodes.ptr, sizeof(ds::Node) * slots, hipMemcpyDeviceToHost, stream));
+    DS_HIP(hipMemcpyAsync(t->pinned_nodes, t->nodes.ptr, t->nodes.bytes(), hipMemcpyDeviceToHost, stream));
     DS_HIP(hipMemcpyAsync(t->pinned_error, t->error.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     if (t->metric_flags) {   // over the margins the partition and eval kernels have just written
         for (int set = 0; set < (t->n_eval > 0 ? 2 : 1); ++set) {
@@ -622,14 +750,7 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
                               hipMemcpyDeviceToHost, stream));
     }
     DS_HIP(hipStreamSynchronize(stream));   // the round's one host sync
-    for (int64_t i = 0; i < slots; ++i) {
-        const ds::Node &node = t->pinned_nodes[i];
-        node_info[4 * i] = node.state;
-        node_info[4 * i + 1] = node.feature;
-        node_info[4 * i + 2] = node.bin;
-        node_info[4 * i + 3] = node.default_left;
-        node_leaf[i] = node.leaf;
-    }
+    ds::train_unpack_heap(t->pinned_nodes, heap_nodes(depth), node_info, node_leaf);
     if (eval_error) *eval_error = t->n_eval > 0 ? static_cast<int64_t>(*t->pinned_error) : -1;
     if (t->metric_flags)
         for (int set = 0; set < (t->n_eval > 0 ? 2 : 1); ++set)
@@ -653,7 +774,7 @@ int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, i
     if (bins) DS_HIP(hipMemcpy(bins, t->bins.ptr, n * t->nf, hipMemcpyDeviceToHost));
     auto add_base = [&](float *out, const float *d_sum, size_t count) -> int {
         DS_HIP(hipMemcpy(out, d_sum, sizeof(float) * count, hipMemcpyDeviceToHost));
-        for (size_t r = 0; r < count; ++r) out[r] = t->base_margin + out[r];   // ds_forest.hip: base + sum of leaves
+        for (size_t r = 0; r < count; ++r) out[r] = ds::kTrainBaseMargin + out[r];   // ds_forest.hip: base + sum of leaves
         return DS_OK;
     };
     if (margins) {

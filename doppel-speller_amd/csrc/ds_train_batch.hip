@@ -1,13 +1,14 @@
 // Batched training for cross-validation and parameter search ("Cross-validation and tuning"):
-// M boosters over ONE binned matrix, each with its own parameters and its own held-out fold, grown by the rule of
-// ds_train.hip (the same device code, ds_train.h) with the model as a further grid dimension.  One round launches each
-// kernel once for all active models and syncs with the host once.
+// M boosters over ONE binned matrix, each with its own parameters and its own held-out fold, grown by the kernels and
+// the launcher of ds_train.hip (train_round_enqueue over a TrainView, ds_train.h) with the model as a further grid
+// dimension.  One round launches each kernel once for all active models and syncs with the host once.  This file holds
+// what only the batch has: the folds, the active list, the held-out error and the per-model sampling and metrics.
 //
 // Shared by the models of a batch:
 //   bins      uint8[nf][n]   as ds_train.hip's, from the cuts of the whole matrix
 //   labels    float[n]
 //   fold      uint8[n]       0 .. K-1
-//   models    BatchModel[M]  parameters and the held-out fold h (-1: none) of every model
+//   models    TrainModel[M]  parameters and the held-out fold h (-1: none) of every model
 // Per model m, at m * the array's stride: gh int64[n][2], node_of int32[n], leafsum float[n], probabilities float[n],
 //   hist int64[2^D - 1][nf][256][2], nodes Node[2^(D+1) - 1], counts int32[2^(D+1) - 1], candidates [2^(D-1)][nf] and
 //   error uint64, D = the largest max_depth of the batch.
@@ -15,7 +16,7 @@
 // kernel, is routed through every new tree like any row, and counts in the model's error after the round.
 //
 // Subsampling (ds_trainer_batch_set_sampling; DESIGN.md section 9, "Subsampling"): every model has its own fractions,
-// seed and tree count.  Once a model of the batch samples, a step launches the kSampled instantiations for ALL active
+// seed and tree count.  Once a model of the batch samples, a step launches the kSampled kernels for ALL active
 // models; a model whose fractions are 1 draws nothing in them and grows the trees of the plain ones.  Added state:
 //   sampling     TrainSampling[M]   trees int32[M]: the trees every model has grown before this step (host -> device
 //                                   with the active list, no further sync)
@@ -30,8 +31,6 @@
 //   metric_columns  MetricColumn[M]   model m's margins with the lists of its held-out fold
 //   metric_scratch                    two key buffers and a count table per model, for the largest fold's negatives
 //   metric_counters uint64[M][6]      copied back whole with the step's other results; the host keeps the active models'
-#include <atomic>
-
 #include "ds_metrics.h"
 #include "ds_train.h"
 
@@ -39,159 +38,10 @@ namespace ds {
 
 constexpr int kBatchModelsMax = 256;
 constexpr int kBatchFoldsMax = 255;
-constexpr float kBatchBaseMargin = 0.f;   // base_score 0.5, as ds_trainer
-
-struct BatchModel {
-    TrainParams params;
-    int32_t held_out, pad;
-};
-
-struct BatchView {   // what every kernel of a round gets; model m's part of a per-model array starts at m * its stride
-    const uint8_t *bins;
-    const float *labels;
-    const uint8_t *fold;
-    const int32_t *cut_offsets;
-    const BatchModel *models;
-    const int32_t *active;        // the models of this step: blockIdx.z (or the last grid dimension) indexes it
-    long long *gh;                // stride 2n
-    int32_t *node_of;             // stride n
-    float *leafsum, *probabilities;   // stride n
-    long long *hist;              // stride hist_stride
-    Node *nodes;                  // stride slots
-    int32_t *counts;              // stride slots
-    Candidate *candidates;        // stride candidate_stride
-    unsigned long long *errors;   // stride 1
-    int64_t n, hist_stride, candidate_stride;
-    int32_t nf, slots;
-};
-
-struct BatchSamplingView {
-    const TrainSampling *sampling;
-    const int32_t *trees;
-    const uint32_t *held_before;   // stride held_stride per slot
-    const int32_t *held_slot;      // per model: its slot of held_before, -1 for none
-    uint8_t *masks;                // stride kMaskBytes
-    int64_t held_stride;
-};
-
-// ---- start of a round: zero the active models' histograms (levels below their own max_depth), heaps, counts, errors -
-__global__ __launch_bounds__(kRowThreads) void ds_batch_clear_kernel(BatchView v)
-{
-    const int32_t m = v.active[blockIdx.y];
-    const int64_t at = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x;
-    const int64_t step = static_cast<int64_t>(gridDim.x) * kRowThreads;
-    const int64_t pairs = ((int64_t(1) << v.models[m].params.max_depth) - 1) * v.nf * 256;   // (g, h) of one bin
-    ulonglong2 *hist = reinterpret_cast<ulonglong2 *>(v.hist + m * v.hist_stride);
-    for (int64_t i = at; i < pairs; i += step) hist[i] = make_ulonglong2(0ull, 0ull);
-    uint32_t *nodes = reinterpret_cast<uint32_t *>(v.nodes + static_cast<int64_t>(m) * v.slots);
-    for (int64_t i = at; i < int64_t(v.slots) * (sizeof(Node) / 4); i += step) nodes[i] = 0u;
-    int32_t *counts = v.counts + static_cast<int64_t>(m) * v.slots;
-    for (int64_t i = at; i < v.slots; i += step) counts[i] = 0;
-    if (at == 0) v.errors[m] = 0ull;
-}
-
-__global__ __launch_bounds__(kRowThreads) void ds_batch_gradient_kernel(BatchView v)
-{
-    const int32_t m = v.active[blockIdx.y];
-    const BatchModel &model = v.models[m];
-    train_gradient_rows<true>(v.leafsum + m * v.n, v.labels, v.n, kBatchBaseMargin, model.params.beta,
-                              v.probabilities + m * v.n, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.fold,
-                              model.held_out);
-}
-
-// blockIdx.x = the chunk of rows, blockIdx.y = (feature group, node group) as in ds_train.hip, blockIdx.z = the model
-__global__ __launch_bounds__(kHistThreads) void ds_batch_histogram_kernel(BatchView v, int32_t level, int32_t n_built,
-                                                                           int32_t nodes_per_group,
-                                                                           int32_t features_per_group,
-                                                                           int32_t feature_groups)
-{
-    const int32_t m = v.active[blockIdx.z];
-    const BatchModel &model = v.models[m];
-    if (level >= model.params.max_depth) return;   // the model's tree is finished: nothing pending
-    train_histogram_group<true>(v.bins, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.counts + int64_t(m) * v.slots,
-                                v.nodes + int64_t(m) * v.slots, v.n, v.nf, level, n_built, nodes_per_group,
-                                features_per_group, feature_groups,
-                                reinterpret_cast<unsigned long long *>(v.hist + m * v.hist_stride), v.fold,
-                                model.held_out);
-}
-
-// ---- the kSampled forms of the three kernels above, and the feature sets of the round: blockIdx.x = the model -------
-__global__ __launch_bounds__(kMaskThreads) void ds_batch_feature_mask_kernel(BatchView v, BatchSamplingView s)
-{
-    const int32_t m = v.active[blockIdx.x];
-    train_feature_masks(s.sampling[m], s.trees[m], v.nf, v.models[m].params.max_depth,
-                        s.masks + static_cast<int64_t>(m) * kMaskBytes);
-}
-
-__global__ __launch_bounds__(kRowThreads) void ds_batch_gradient_sampled_kernel(BatchView v, BatchSamplingView s)
-{
-    const int32_t m = v.active[blockIdx.y];
-    const BatchModel &model = v.models[m];
-    const int32_t slot = s.held_slot[m];
-    train_gradient_rows<true, true>(v.leafsum + m * v.n, v.labels, v.n, kBatchBaseMargin, model.params.beta,
-                                    v.probabilities + m * v.n, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.fold,
-                                    model.held_out, s.sampling + m, s.trees[m],
-                                    slot >= 0 ? s.held_before + slot * s.held_stride : nullptr);
-}
-
-__global__ __launch_bounds__(kHistThreads) void ds_batch_histogram_sampled_kernel(BatchView v, int32_t level,
-                                                                                   int32_t n_built,
-                                                                                   int32_t nodes_per_group,
-                                                                                   int32_t features_per_group,
-                                                                                   int32_t feature_groups)
-{
-    const int32_t m = v.active[blockIdx.z];
-    const BatchModel &model = v.models[m];
-    if (level >= model.params.max_depth) return;
-    train_histogram_group<true, true>(v.bins, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.counts + int64_t(m) * v.slots,
-                                      v.nodes + int64_t(m) * v.slots, v.n, v.nf, level, n_built, nodes_per_group,
-                                      features_per_group, feature_groups,
-                                      reinterpret_cast<unsigned long long *>(v.hist + m * v.hist_stride), v.fold,
-                                      model.held_out);
-}
-
-__global__ __launch_bounds__(256) void ds_batch_split_feature_sampled_kernel(BatchView v, BatchSamplingView s,
-                                                                              int32_t level)
-{
-    const int32_t m = v.active[blockIdx.z];
-    const BatchModel &model = v.models[m];
-    if (level >= model.params.max_depth) return;
-    train_split_feature<true>(v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots,
-                              v.nodes + int64_t(m) * v.slots, v.cut_offsets, v.nf, level, model.params,
-                              v.candidates + m * v.candidate_stride,
-                              s.masks + static_cast<int64_t>(m) * kMaskBytes + level * kTrainFeaturesMax);
-}
-
-// blockIdx.x = the node's index in its level, blockIdx.y = the feature, blockIdx.z = the model
-__global__ __launch_bounds__(256) void ds_batch_split_feature_kernel(BatchView v, int32_t level)
-{
-    const int32_t m = v.active[blockIdx.z];
-    const BatchModel &model = v.models[m];
-    if (level >= model.params.max_depth) return;
-    train_split_feature(v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots, v.nodes + int64_t(m) * v.slots,
-                        v.cut_offsets, v.nf, level, model.params, v.candidates + m * v.candidate_stride);
-}
-
-// blockIdx.x = 64 nodes of the level, blockIdx.y = the model
-__global__ __launch_bounds__(64) void ds_batch_split_kernel(BatchView v, int32_t level)
-{
-    const int32_t m = v.active[blockIdx.y];
-    const BatchModel &model = v.models[m];
-    if (level >= model.params.max_depth) return;
-    train_split_nodes(v.candidates + m * v.candidate_stride, v.nodes + int64_t(m) * v.slots, v.nf, level, model.params);
-}
-
-__global__ __launch_bounds__(kRowThreads) void ds_batch_partition_kernel(BatchView v, int32_t level)
-{
-    const int32_t m = v.active[blockIdx.y];
-    if (level >= v.models[m].params.max_depth) return;
-    train_partition_rows(v.bins, v.nodes + int64_t(m) * v.slots, v.n, level, v.node_of + m * v.n, v.leafsum + m * v.n,
-                         v.counts + int64_t(m) * v.slots);
-}
 
 // ---- held-out error: ds_train_eval_kernel's rule over the rows of the model's held-out fold, at the margins that the
 // partition kernel has just updated
-__global__ __launch_bounds__(kRowThreads) void ds_batch_error_kernel(BatchView v)
+__global__ __launch_bounds__(kRowThreads) void ds_batch_error_kernel(TrainView v)
 {
     __shared__ unsigned long long s_error;
     const int32_t m = v.active[blockIdx.y];
@@ -203,7 +53,7 @@ __global__ __launch_bounds__(kRowThreads) void ds_batch_error_kernel(BatchView v
     unsigned long long mine = 0;
     for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < v.n;
          r += static_cast<int64_t>(gridDim.x) * kRowThreads)
-        if (static_cast<int32_t>(v.fold[r]) == held_out) mine += train_row_error(kBatchBaseMargin + leafsum[r], v.labels[r]);
+        if (static_cast<int32_t>(v.fold[r]) == held_out) mine += train_row_error(kTrainBaseMargin + leafsum[r], v.labels[r]);
     if (mine) atomicAdd(&s_error, mine);
     __syncthreads();
     if (threadIdx.x == 0 && s_error) atomicAdd(v.errors + m, s_error);
@@ -215,7 +65,7 @@ struct ds_trainer_batch {
     int device = 0;
     int64_t n = 0;
     int32_t nf = 0, n_models = 0, max_depth = 0, slots = 0;
-    std::vector<ds::BatchModel> models;
+    std::vector<ds::TrainModel> models;
     hipStream_t stream = nullptr;
     ds::DeviceBuffer<uint8_t> bins, fold;
     ds::DeviceBuffer<float> labels, leafsum, probabilities, cuts;
@@ -224,11 +74,11 @@ struct ds_trainer_batch {
     ds::DeviceBuffer<ds::Node> nodes;
     ds::DeviceBuffer<ds::Candidate> candidates;
     ds::DeviceBuffer<unsigned long long> errors;
-    ds::DeviceBuffer<ds::BatchModel> d_models;
+    ds::DeviceBuffer<ds::TrainModel> d_models;
     ds::Node *pinned_nodes = nullptr;          // [n_models][slots]
     unsigned long long *pinned_errors = nullptr;
     int32_t *pinned_active = nullptr;
-    ds::BatchView view{};
+    ds::TrainView view{};
     int compute_units = 256;
     // subsampling (ds_trainer_batch_set_sampling)
     bool stepped = false, sampled = false;
@@ -238,7 +88,7 @@ struct ds_trainer_batch {
     ds::DeviceBuffer<uint32_t> d_held_before;
     ds::DeviceBuffer<uint8_t> masks;
     int32_t *pinned_trees = nullptr;
-    ds::BatchSamplingView sampling_view{};
+    ds::TrainSamplingView sampling_view{};
     // metrics (ds_trainer_batch_set_metrics)
     uint32_t metric_flags = 0;
     ds::DeviceBuffer<int32_t> metric_rows;
@@ -262,23 +112,9 @@ struct ds_trainer_batch {
 
 namespace {
 
-std::atomic<int64_t> g_max_blocks{0};   // ds_trainer_batch_option("max_blocks"): 0 = no cap
-
-int64_t heap_nodes(int32_t depth) { return (int64_t(2) << depth) - 1; }
-int64_t hist_entries(int32_t depth, int32_t nf) { return ((int64_t(1) << depth) - 1) * nf * 512; }
-int64_t candidate_entries(int32_t depth, int32_t nf) { return (int64_t(1) << (depth - 1)) * nf; }
-
-int64_t capped(int64_t blocks)
-{
-    const int64_t cap = g_max_blocks.load();
-    return std::max<int64_t>(1, cap > 0 ? std::min(blocks, cap) : blocks);
-}
-
-unsigned row_grid(const ds_trainer_batch *b, int64_t items)
-{
-    return static_cast<unsigned>(capped(std::min<int64_t>((items + ds::kRowThreads - 1) / ds::kRowThreads,
-                                                          int64_t(b->compute_units) * 8)));
-}
+using ds::candidate_entries;
+using ds::heap_nodes;
+using ds::hist_entries;
 
 bool ranges_ok(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth)
 {
@@ -299,32 +135,26 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
     DS_REQUIRE(fold != nullptr, "%s: fold is null", who);
     DS_REQUIRE(params != nullptr, "%s: params is null", who);
     DS_REQUIRE(held_out != nullptr, "%s: held_out is null", who);
-    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
-    DS_REQUIRE(n_features >= 1 && n_features <= ds::kTrainFeaturesMax, "%s: n_features = %d out of range [1, %d]", who,
-               n_features, ds::kTrainFeaturesMax);
+    if (int status = ds::train_check_shape(who, n, n_features); status != DS_OK) return status;
     DS_REQUIRE(n_models >= 1 && n_models <= ds::kBatchModelsMax, "%s: n_models = %d out of range [1, %d]", who, n_models,
                ds::kBatchModelsMax);
     DS_REQUIRE(n_folds >= 1 && n_folds <= ds::kBatchFoldsMax, "%s: n_folds = %d out of range [1, %d]", who, n_folds,
                ds::kBatchFoldsMax);
-    std::vector<ds::BatchModel> models(n_models);
+    std::vector<ds::TrainModel> models(n_models);
     int32_t depth = 1;
     for (int32_t m = 0; m < n_models; ++m) {
         const double *p = params + 5 * m;
         DS_REQUIRE(p[0] >= 1 && p[0] <= ds::kTrainMaxDepth && p[0] == static_cast<double>(static_cast<int32_t>(p[0])),
                    "%s: params of model %d: max_depth = %g is not an integer in [1, %d]", who, m, p[0],
                    ds::kTrainMaxDepth);
-        DS_REQUIRE(p[1] > 0 && p[1] < 1e30 && p[2] >= 0 && p[2] < 1e30 && p[3] >= 0 && p[3] < 1e30 && p[4] > 0 &&
-                       p[4] < 1e30 && p[2] + p[3] > 0,
-                   "%s: params of model %d: eta, beta must be positive, min_child_weight, reg_lambda non-negative and "
-                   "not both 0", who, m);
+        if (int status = ds::train_check_params(who, m, p[1], p[2], p[3], p[4]); status != DS_OK) return status;
         DS_REQUIRE(held_out[m] >= -1 && held_out[m] < n_folds, "%s: held_out[%d] = %d out of range [-1, %d)", who, m,
                    held_out[m], n_folds);
-        models[m] = ds::BatchModel{ds::TrainParams{static_cast<int32_t>(p[0]), p[1], p[2], p[3], p[4]}, held_out[m], 0};
+        models[m] = ds::TrainModel{ds::TrainParams{static_cast<int32_t>(p[0]), p[1], p[2], p[3], p[4]}, held_out[m], 0};
         depth = std::max(depth, models[m].params.max_depth);
     }
     if (int status = ds::train_check_cuts(who, n_features, cuts, cut_offsets); status != DS_OK) return status;
-    for (int64_t r = 0; r < n; ++r)
-        DS_REQUIRE(labels[r] == 0.f || labels[r] == 1.f, "%s: labels: label %lld is not 0 or 1", who, (long long)r);
+    if (int status = ds::train_check_labels(who, "labels: ", labels, n); status != DS_OK) return status;
     for (int64_t r = 0; r < n; ++r)
         DS_REQUIRE(fold[r] < n_folds, "%s: fold[%lld] = %d is not below n_folds = %d", who, (long long)r, fold[r],
                    n_folds);
@@ -340,16 +170,9 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
     b->slots = static_cast<int32_t>(heap_nodes(depth));
     b->models = models;
     b->tree_count.assign(n_models, 0);
-    hipDeviceProp_t props;
-    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
-        b->compute_units = props.multiProcessorCount;
     const size_t M = static_cast<size_t>(n_models), rows = static_cast<size_t>(n);
-    int status = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess ? DS_OK : DS_E_HIP;
-    if (status != DS_OK) ds::set_error("%s: hipStreamCreate failed", who);
-    if (status == DS_OK) status = b->cut_offsets.upload(cut_offsets, static_cast<size_t>(n_features) + 1);
-    if (status == DS_OK) status = b->cuts.allocate(std::max<size_t>(1, static_cast<size_t>(cut_offsets[n_features])));
-    if (status == DS_OK && cut_offsets[n_features] > 0)
-        status = b->cuts.upload(cuts, static_cast<size_t>(cut_offsets[n_features]));
+    int status = ds::train_create_setup(who, device, n_features, cuts, cut_offsets, &b->stream, b->cuts, b->cut_offsets,
+                                        &b->compute_units);
     if (status == DS_OK)
         status = ds::train_bin_matrix(b->stream, b->compute_units, features, in_hbm, n, n_features, b->cuts.ptr,
                                       b->cut_offsets.ptr, b->bins);
@@ -382,27 +205,10 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
         delete b;
         return status;
     }
-    ds::BatchView &v = b->view;
-    v.bins = b->bins.ptr;
-    v.labels = b->labels.ptr;
-    v.fold = b->fold.ptr;
-    v.cut_offsets = b->cut_offsets.ptr;
-    v.models = b->d_models.ptr;
-    v.active = b->active.ptr;
-    v.gh = b->gh.ptr;
-    v.node_of = b->node_of.ptr;
-    v.leafsum = b->leafsum.ptr;
-    v.probabilities = b->probabilities.ptr;
-    v.hist = b->hist.ptr;
-    v.nodes = b->nodes.ptr;
-    v.counts = b->counts.ptr;
-    v.candidates = b->candidates.ptr;
-    v.errors = b->errors.ptr;
-    v.n = n;
-    v.hist_stride = hist_entries(depth, n_features);
-    v.candidate_stride = candidate_entries(depth, n_features);
-    v.nf = n_features;
-    v.slots = b->slots;
+    b->view = ds::TrainView{b->bins.ptr, b->labels.ptr, b->fold.ptr, b->cut_offsets.ptr, b->d_models.ptr, b->active.ptr,
+                            b->gh.ptr, b->node_of.ptr, b->leafsum.ptr, b->probabilities.ptr, b->hist.ptr, b->nodes.ptr,
+                            b->counts.ptr, b->candidates.ptr, b->errors.ptr, n, hist_entries(depth, n_features),
+                            candidate_entries(depth, n_features), n_features, b->slots};
     *out = b;
     return DS_OK;
 }
@@ -417,7 +223,7 @@ int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, 
     const int64_t per_model = n * 28 + hist_entries(max_depth, n_features) * 8 +
                               heap_nodes(max_depth) * int64_t(sizeof(ds::Node) + 4) +
                               candidate_entries(max_depth, n_features) * int64_t(sizeof(ds::Candidate)) +
-                              int64_t(sizeof(ds::BatchModel)) + 12;
+                              int64_t(sizeof(ds::TrainModel)) + 12;
     return n * n_features + n * 5 + per_model * n_models;
 }
 
@@ -452,7 +258,7 @@ int ds_trainer_batch_option(const char *name, int64_t value)
     DS_REQUIRE(std::strcmp(name, "max_blocks") == 0, "ds_trainer_batch_option: unknown option '%s'", name);
     DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_trainer_batch_option: max_blocks = %lld out of range [0, 2^31)",
                (long long)value);
-    g_max_blocks.store(value);
+    ds::train_set_max_blocks(value);
     return DS_OK;
 }
 
@@ -462,18 +268,15 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
     DS_REQUIRE(fractions != nullptr, "ds_trainer_batch_set_sampling: fractions is null");
     DS_REQUIRE(sample_seeds != nullptr, "ds_trainer_batch_set_sampling: sample_seeds is null");
     ds_trainer_batch *b = batch;
-    const char *names[3] = {"subsample", "colsample_bytree", "colsample_bylevel"};
     std::vector<ds::TrainSampling> sampling(b->n_models);
     std::vector<int32_t> held_slot(b->n_models, -1), slot_of_fold(ds::kBatchFoldsMax, -1), slot_folds;
     bool any = false;
     for (int32_t m = 0; m < b->n_models; ++m) {
         const double *f = fractions + 3 * m;
-        for (int i = 0; i < 3; ++i)
-            DS_REQUIRE(f[i] > 0 && f[i] <= 1, "ds_trainer_batch_set_sampling: model %d: %s = %g out of range (0, 1]", m,
-                       names[i], f[i]);
-        DS_REQUIRE(f[0] == 1 || b->models[m].params.reg_lambda > 0,
-                   "ds_trainer_batch_set_sampling: model %d: subsample < 1 needs reg_lambda > 0 (a round may draw no row)",
-                   m);
+        if (int status = ds::train_check_fractions("ds_trainer_batch_set_sampling", m, f); status != DS_OK) return status;
+        if (int status = ds::train_check_subsample("ds_trainer_batch_set_sampling", m, f[0], b->models[m].params.reg_lambda);
+            status != DS_OK)
+            return status;
         sampling[m] = ds::TrainSampling{f[0], f[1], f[2], sample_seeds[m]};
         any = any || sampling[m].any();
         const int32_t held_out = b->models[m].held_out;
@@ -515,7 +318,7 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
         status = DS_E_HIP;
     }
     if (status != DS_OK) return status;
-    b->sampling_view = ds::BatchSamplingView{b->d_sampling.ptr, b->d_trees.ptr, b->d_held_before.ptr, b->d_held_slot.ptr,
+    b->sampling_view = ds::TrainSamplingView{b->d_sampling.ptr, b->d_trees.ptr, b->d_held_before.ptr, b->d_held_slot.ptr,
                                              b->masks.ptr, static_cast<int64_t>(waves)};
     b->sampled = true;
     return DS_OK;
@@ -552,7 +355,7 @@ int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags)
     DS_HIP(hipMemcpy(labels.data(), b->labels.ptr, rows * sizeof(float), hipMemcpyDeviceToHost));
     std::vector<int64_t> neg(ds::kBatchFoldsMax + 1, 0), pos(ds::kBatchFoldsMax + 1, 0), first(ds::kBatchFoldsMax + 1, 0);
     std::vector<uint8_t> wanted(ds::kBatchFoldsMax + 1, 0);
-    for (const ds::BatchModel &model : b->models)
+    for (const ds::TrainModel &model : b->models)
         if (model.held_out >= 0) wanted[model.held_out] = 1;
     for (size_t r = 0; r < rows; ++r) ++(labels[r] == 0.f ? neg : pos)[fold[r]];
     int64_t listed = 0;
@@ -591,7 +394,7 @@ int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags)
         const int32_t k = b->models[m].held_out;
         ds::MetricColumn &column = b->metric_host[m];
         column.scores = b->leafsum.ptr + m * rows;
-        column.base_margin = ds::kBatchBaseMargin;
+        column.base_margin = ds::kTrainBaseMargin;
         column.beta = b->models[m].params.beta;
         if (k < 0) continue;   // no held-out rows: empty lists, and the host reports -1
         column.neg_rows = b->metric_rows.ptr + first[k];
@@ -627,57 +430,20 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     if (n_active == 0) return DS_OK;
     DS_HIP(hipSetDevice(b->device));
     hipStream_t stream = b->stream;
-    const ds::BatchView &v = b->view;
-    const int64_t n = b->n;
-    const unsigned models = static_cast<unsigned>(n_active);
+    const ds::TrainView &v = b->view;
     DS_HIP(hipMemcpyAsync(b->active.ptr, b->pinned_active, sizeof(int32_t) * n_active, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(ds::ds_batch_clear_kernel, dim3(row_grid(b, v.hist_stride / 2), models), dim3(ds::kRowThreads), 0,
-                       stream, v);
-    DS_HIP(hipGetLastError());
-    const ds::BatchSamplingView &sv = b->sampling_view;
     if (b->sampled) {   // every model's own tree count indexes its streams, not the steps of the batch
         std::memcpy(b->pinned_trees, b->tree_count.data(), sizeof(int32_t) * b->n_models);
         DS_HIP(hipMemcpyAsync(b->d_trees.ptr, b->pinned_trees, sizeof(int32_t) * b->n_models, hipMemcpyHostToDevice,
                               stream));
-        hipLaunchKernelGGL(ds::ds_batch_feature_mask_kernel, dim3(models), dim3(ds::kMaskThreads), 0, stream, v, sv);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_batch_gradient_sampled_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0,
-                           stream, v, sv);
-    } else {
-        hipLaunchKernelGGL(ds::ds_batch_gradient_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream,
-                           v);
     }
-    DS_HIP(hipGetLastError());
-    for (int32_t level = 0; level < depth; ++level) {   // to the largest max_depth among the active models
-        const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
-        const int32_t nodes_per_group = std::min(n_built, ds::kHistSlots);
-        const int32_t features_per_group = std::min<int32_t>(b->nf, ds::kHistSlots / nodes_per_group);
-        const int32_t feature_groups = (b->nf + features_per_group - 1) / features_per_group;
-        const int32_t node_groups = (n_built + nodes_per_group - 1) / nodes_per_group;
-        const int64_t groups = int64_t(feature_groups) * node_groups * n_active;
-        // ds_trainer_step's shape with the models counted in: about 4 workgroups per CU in all, each over >= 2048 rows
-        const int64_t chunks = capped(std::min<int64_t>((n + 2047) / 2048,
-                                                        (int64_t(b->compute_units) * 4 + groups - 1) / groups));
-        hipLaunchKernelGGL(b->sampled ? ds::ds_batch_histogram_sampled_kernel : ds::ds_batch_histogram_kernel,
-                           dim3(static_cast<unsigned>(chunks), feature_groups * node_groups, models),
-                           dim3(ds::kHistThreads), 0, stream, v, level, n_built, nodes_per_group, features_per_group,
-                           feature_groups);
-        DS_HIP(hipGetLastError());
-        if (b->sampled)
-            hipLaunchKernelGGL(ds::ds_batch_split_feature_sampled_kernel, dim3(1u << level, b->nf, models), dim3(256), 0,
-                               stream, v, sv, level);
-        else
-            hipLaunchKernelGGL(ds::ds_batch_split_feature_kernel, dim3(1u << level, b->nf, models), dim3(256), 0, stream,
-                               v, level);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_batch_split_kernel, dim3(((1u << level) + 63) / 64, models), dim3(64), 0, stream, v,
-                           level);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds::ds_batch_partition_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream,
-                           v, level);
-        DS_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ds::ds_batch_error_kernel, dim3(row_grid(b, n), models), dim3(ds::kRowThreads), 0, stream, v);
+    if (int status = ds::train_round_enqueue(stream, v, b->sampled ? &b->sampling_view : nullptr, n_active, depth, true,
+                                             b->compute_units);
+        status != DS_OK)
+        return status;
+    hipLaunchKernelGGL(ds::ds_batch_error_kernel,
+                       dim3(ds::train_row_grid(b->compute_units, b->n), static_cast<unsigned>(n_active)),
+                       dim3(ds::kRowThreads), 0, stream, v);
     DS_HIP(hipGetLastError());
     for (int32_t a = 0; a < n_active;) {   // the active models' heaps only: one copy per run of neighbouring models
         int32_t end = a + 1;
@@ -691,7 +457,7 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     if (b->metric_flags) {   // over the margins the partition kernels have just written
         if (int status = ds::metrics_enqueue(stream, b->compute_units, b->metric_flags, b->metric_columns.ptr,
                                              b->active.ptr, n_active, b->metric_keys, b->metric_pos, b->metric_fold_rows,
-                                             b->metric_scratch, b->metric_counters.ptr, g_max_blocks.load());
+                                             b->metric_scratch, b->metric_counters.ptr, ds::train_max_blocks());
             status != DS_OK)
             return status;
         DS_HIP(hipMemcpyAsync(b->pinned_metrics, b->metric_counters.ptr, b->metric_counters.bytes(),
@@ -702,15 +468,8 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     for (int32_t a = 0; a < n_active; ++a) {
         const int64_t m = b->pinned_active[a];
         ++b->tree_count[m];
-        for (int64_t i = 0; i < b->slots; ++i) {
-            const ds::Node &node = b->pinned_nodes[m * b->slots + i];
-            int32_t *info = node_info + (m * b->slots + i) * 4;
-            info[0] = node.state;
-            info[1] = node.feature;
-            info[2] = node.bin;
-            info[3] = node.default_left;
-            node_leaf[m * b->slots + i] = node.leaf;
-        }
+        ds::train_unpack_heap(b->pinned_nodes + m * b->slots, b->slots, node_info + m * b->slots * 4,
+                              node_leaf + m * b->slots);
         errors[m] = b->models[m].held_out >= 0 ? static_cast<int64_t>(b->pinned_errors[m]) : -1;
         if (b->metric_flags && b->models[m].held_out >= 0)
             ds::metrics_row(b->metric_flags, b->pinned_metrics + m * ds::kMetricCounters, b->metric_host[m].n_neg,
@@ -735,7 +494,7 @@ int ds_trainer_batch_read(ds_trainer_batch *batch, int32_t model, float *margins
     if (bins) DS_HIP(hipMemcpy(bins, b->bins.ptr, n * b->nf, hipMemcpyDeviceToHost));
     if (margins) {
         DS_HIP(hipMemcpy(margins, b->leafsum.ptr + m * n, sizeof(float) * n, hipMemcpyDeviceToHost));
-        for (size_t r = 0; r < n; ++r) margins[r] = ds::kBatchBaseMargin + margins[r];
+        for (size_t r = 0; r < n; ++r) margins[r] = ds::kTrainBaseMargin + margins[r];
     }
     return DS_OK;
 }

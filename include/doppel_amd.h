@@ -567,8 +567,9 @@ int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, 
  * n / 16 bytes per fold that a model with subsample < 1 holds out.  DS_E_ARG as for ds_trainer_set_sampling, with the
  * model named. */
 int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractions, const uint64_t *sample_seeds);
-/* For tests: ds_trainer_batch_option("max_blocks", b) caps every grid of this stage that runs over rows at b workgroups,
- * which stride beyond it (0: back to the default).  The results do not depend on it. */
+/* For tests: ds_trainer_batch_option("max_blocks", b) caps every grid of a training round that runs over rows at b
+ * workgroups, which stride beyond it (0: back to the default).  It also caps the round of ds_trainer_step, which launches
+ * the same kernels.  The results do not depend on it. */
 int ds_trainer_batch_option(const char *name, int64_t value);
 
 /* ---- metrics of a booster's margins, computed on the device ("Metrics") ---------------------------

@@ -11,10 +11,10 @@ batch's boost time per round, and 60 x the single trainer's per-round time.
 
 `single` is ForestTrainer on all rows at depth 5, the median of 10 rounds after 2: the figure of section 9's table.
 
-    python scripts/cv_timings.py [rows] [rounds] [--batch-only] [--once] [--single-only]
+    python scripts/cv_timings.py [rows] [rounds] [--batch-only] [--once] [--single-only] [--subsample=F]
 
 --batch-only leaves out the sequential path, --once runs each path a single time without a warm-up (for a kernel trace),
---single-only stops after the single trainer's figure.
+--single-only stops after the single trainer's figure, --subsample=F adds the single trainer's figure with subsample F.
 """
 import os
 import statistics
@@ -34,7 +34,7 @@ def data(n, nf=66, seed=3):
     return x, y
 
 
-def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False):
+def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False, subsample=None):
     x, y = data(n)
     grid = ds.parameter_grid(max_depth=[4, 5], eta=[0.1, 0.3], beta=[1.0, 2.0, 5.0])
     folds = ds.fold_assignment(None, 5, 0, n)
@@ -58,8 +58,8 @@ def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False):
                 trainer.close()
         return time.perf_counter() - mark, boost
 
-    def single():
-        trainer = ds.ForestTrainer().begin(x, y, x[:n // 10], y[:n // 10])
+    def single(**sampling):
+        trainer = ds.ForestTrainer().begin(x, y, x[:n // 10], y[:n // 10], **sampling)
         times = []
         for round_ in range(12):
             mark = time.perf_counter()
@@ -67,10 +67,13 @@ def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False):
             times.append((time.perf_counter() - mark) * 1000.0)
         trainer.close()
         times = times[2:]
-        print(f"single     n={n}: {statistics.median(times):.3f} ms per round ({min(times):.3f}-{max(times):.3f}), "
+        label = "".join(f" {name}={value}" for name, value in sampling.items())
+        print(f"single     n={n}{label}: {statistics.median(times):.3f} ms per round ({min(times):.3f}-{max(times):.3f}), "
               f"x 60 = {statistics.median(times) * 60:.1f} ms", flush=True)
 
     single()
+    if subsample is not None:
+        single(subsample=subsample)
     if single_only:
         return
     runs = {"batch": [], "sequential": []}
@@ -90,5 +93,6 @@ def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False):
 
 if __name__ == "__main__":
     arguments = [a for a in sys.argv[1:] if not a.startswith("--")]
-    main(*(int(a) for a in arguments[:2]), batch_only="--batch-only" in sys.argv,
-         once="--once" in sys.argv, single_only="--single-only" in sys.argv)
+    subsamples = [float(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--subsample=")]
+    main(*(int(a) for a in arguments[:2]), batch_only="--batch-only" in sys.argv, once="--once" in sys.argv,
+         single_only="--single-only" in sys.argv, subsample=subsamples[0] if subsamples else None)

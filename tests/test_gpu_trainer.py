@@ -174,3 +174,40 @@ def test_trained_model_beats_the_all_negative_answer():
     assert trained < 0.5 * all_negative
     tp, tn, fp, fn = ds.evaluation_error_matrix(model, hx, hy)
     assert tp + tn + fp + fn == hy.shape[0] and tp + fn == all_negative and fn + 5 * fp == trained
+
+
+@pytest.mark.parametrize("sampling", [{}, dict(subsample=0.5, colsample_bytree=0.6, colsample_bylevel=0.6)],
+                         ids=["plain", "sampled"])
+def test_a_capped_grid_changes_no_byte(sampling):
+    """ds_trainer_step runs the round's kernels under the same grid cap as the batch: with 3 workgroups per grid every
+    row kernel (clear, gradient, partition, evaluation) strides over its 5003 rows more than once and the histogram
+    kernel takes 3 chunks, at two feature groups on level 0.  No byte of any round may depend on it."""
+    import doppel_speller_amd as ds
+    from doppel_speller_amd import tuning
+    x, y = make_data(5003, 17, 41)
+    ex, ey = x[:700], y[:700]
+
+    def run():
+        trainer = ds.ForestTrainer().begin(x, y, ex, ey, max_depth=5, **sampling)
+        rounds = []
+        for _ in range(6):
+            error = trainer.step()
+            rounds.append((trainer.last_heap[0].tobytes(), trainer.last_heap[1].tobytes(), trainer.margins().tobytes(),
+                           trainer.eval_margins().tobytes(), trainer.probabilities().tobytes(),
+                           trainer.gradients().tobytes(), error))
+        deepest = any(np.any(tree_info[15:31, 0] == oracle.SPLIT) for tree_info in
+                      (np.frombuffer(r[0], np.int32).reshape(-1, 4) for r in rounds))
+        trainer.close()
+        return rounds, deepest
+
+    free, deepest = run()
+    assert deepest                                  # level 4 has split: the depth is real
+    tuning.batch_option("max_blocks", 3)
+    try:
+        capped, _ = run()
+    finally:
+        tuning.batch_option("max_blocks", 0)
+    for round_, (a, b) in enumerate(zip(free, capped)):
+        for name, one, other in zip(("info", "leaf", "margins", "eval_margins", "probabilities", "gradients", "error"),
+                                    a, b):
+            assert one == other, (round_, name)
