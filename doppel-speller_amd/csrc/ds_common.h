@@ -30,18 +30,6 @@ constexpr int kSignatureWords = kSignatureBits / 32;
 constexpr int kRowRecordWords = 8;          // 32-byte row record: signature, sums32, duplicate rank
 constexpr int kControlWords = 32;            // int32 control block in HBM (queue heads, counters)
 
-// 8-bit lower bound of a positive float: 4 exponent bits (2^-3 .. 2^12) and 4 mantissa bits, truncated.
-// decode(encode(x)) <= x for every x >= 0; code 0 decodes to 0; a row never gets the padding code 0xff (values from 7936 up share 0xfe).
-inline uint32_t encode_sums8(float x)
-{
-    if (!(x >= 0.125f)) return 0u;
-    uint32_t bits;
-    memcpy(&bits, &x, sizeof(bits));
-    const int exponent = static_cast<int>(bits >> 23) - 124;  // 2^-3 -> 0
-    if (exponent > 15) return 0xfeu;  // 0xff is the padding entries' code (never reachable in the collect sweep)
-    return std::min<uint32_t>(0xfeu, (static_cast<uint32_t>(exponent) << 4) | ((bits >> 19) & 0xfu));
-}
-
 // splitmix64 finaliser: a bijective 64-bit mixer (row-set hashes of the index build)
 inline uint64_t mix64(uint64_t x)
 {
@@ -116,7 +104,7 @@ struct ds_index {
     float sums_min = 0.f;
     ds::DeviceBuffer<uint32_t> col_ptr;    // [n_columns][n_tiles + 1], unit = quads of 4 postings (column-major)
     ds::DeviceBuffer<uint16_t> postings;   // [n_quads * 4] (parity << 15) | (tile-local row >> 1); per (column, tile): even rows, padding, odd rows, padding
-    ds::DeviceBuffer<uint16_t> posting_sums; // [n_quads * 4] per posting: 8-bit lower bound of sums32[row] << 8 | signature bits 0..7
+    ds::DeviceBuffer<uint16_t> posting_sums; // [n_quads * 4] per posting: the row's signature bits 0..15 (membership of the 16 densest columns); 0 for padding entries
     ds::DeviceBuffer<float> idf32;         // [n_columns]
     ds::DeviceBuffer<float> sums32;        // [n_truth] in INTERNAL row order (rows sorted by sums32; word 6 of a row record = the caller's row)
     ds::DeviceBuffer<float> tile_sums_min; // [n_tiles] min(sums32) over the rows of each tile

@@ -125,7 +125,7 @@ constexpr int kOffRank = kOffFixed + kMaxQueryColumns * 4;    // three byte arra
 constexpr int kOffOrder = kOffRank + kMaxQueryColumns;
 constexpr int kOffSigBit = kOffOrder + kMaxQueryColumns;
 constexpr int kOffMassTable = kOffSigBit + kMaxQueryColumns;
-constexpr int kOffPtr = kOffMassTable + 256 * 6;  // need32[256] then mass16[256]
+constexpr int kOffPtr = kOffMassTable + 256 * 4;  // mass_low[256] then mass_high[256] (16 bits each), or the radix histogram
 constexpr int kOffHist = kOffMassTable;  // the radix histogram shares the mass table: every selection is followed by
                                          // a rebuild of the table before its next use
 constexpr int kOffQuadPrefix = kOffPtr + kMaxQueryColumns * (kPtrTiles + 1) * 4;  // per tile: quads before column j
@@ -314,12 +314,6 @@ __device__ __forceinline__ uint32_t max_of_packed4(const uint32_t (&v)[4])
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(a, b));
 }
 
-// Inverse of encode_sums8: a lower bound of sums32[row] from the 8-bit code stored with every posting.
-__device__ __forceinline__ float decode_sums8(uint32_t code)
-{
-    return code == 0u ? 0.f : __uint_as_float((((code >> 4) + 124u) << 23) | ((code & 0xfu) << 19));
-}
-
 // Loose test: can the row still qualify if every skipped (non-essential) column matched as well?
 __device__ __forceinline__ bool may_qualify(float s, float sums, const Bounds &b)
 {
@@ -454,11 +448,11 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
     float *bit_idf = reinterpret_cast<float *>(lds + kOffBitIdf);     // IDF of the query column owning signature bit g
     uint32_t *fixed = reinterpret_cast<uint32_t *>(lds + kOffFixed);  // idf[j] in the query's fixed-point scale
     uint32_t *iscores = reinterpret_cast<uint32_t *>(lds);  // score tile: 16-bit fixed-point sums, row r in half (r & 1) of word r >> 1
-    // need32[256] (by 8-bit sums code) and mass16[256] (by signature bits 0..7): the integer tables of the collect
-    // sweep's row test, rebuilt after a selection.  need32[255] -- the code of the lists' padding entries, which take
-    // whatever the trash word holds -- is beyond every score.
-    uint32_t *need32 = reinterpret_cast<uint32_t *>(lds + kOffMassTable);
-    uint16_t *mass16 = reinterpret_cast<uint16_t *>(lds + kOffMassTable + 256 * 4);
+    // mass_low[256] (by a posting's membership bits 0..7) and mass_high[256] (by bits 8..15): the integer tables of the
+    // collect sweep's row test, rebuilt after a selection.  A row's need is the tile's gate.  The lists' padding entries
+    // and the idle lanes take whatever the trash word holds: the sweep tells them by their word (kPadWord), never by a table.
+    uint16_t *mass_low = reinterpret_cast<uint16_t *>(lds + kOffMassTable);
+    uint16_t *mass_high = mass_low + 256;
     uint32_t *ptr_cache = reinterpret_cast<uint32_t *>(lds + kOffPtr);  // [column][span + 1], kMaxQueryColumns * (kPtrTiles + 1) words
     uint32_t *quad_prefix = reinterpret_cast<uint32_t *>(lds + kOffQuadPrefix);
     uint32_t *quad_base = reinterpret_cast<uint32_t *>(lds + kOffQuadBase);
@@ -621,8 +615,8 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                                          // selection also raises the admission floor
         int floor_shift = 0;             // ... to what should fill (kSelectTrigger - 64) >> floor_shift entries: every repetition
                                          // of the same rows halves it (the rest of an epoch brings more rows)
-        bool tables_fresh = false;       // the tables were rebuilt at this tile's start: mass16[255] is read once, behind a barrier
-        uint32_t mass_units_max = 0;     // mass16[255], the largest entry: the collect sweep's gate never goes below it
+        bool tables_fresh = false;       // the tables were rebuilt at this tile's start: mass_low[255] is read once, behind a barrier
+        uint32_t mass_units_max = 0;     // mass_low[255], the largest entry: the collect sweep's gate never goes below it
         const float to_fixed_low = uniform(to_fixed * (1.f - 9.5367431640625e-07f));  // < 1 / from_fixed: products round down
         const float to_fixed_high = uniform(to_fixed * (1.f + 9.5367431640625e-07f));  // > 1 / from_fixed: products round up
         int non_essential = 0;
@@ -782,29 +776,31 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                 if (tid < 4) ctrl[kLTileMask + tid] = static_cast<int32_t>(ctrl[kLSigMask + tid]);  // (an int32: word = word would copy the accessor)
                 if (tid == 4) ctrl[kLTileSkip] = non_essential;
                 if (tid < 256) {
-                    const uint32_t skipped8 = static_cast<uint32_t>(ctrl[kLSigMask]) & 0xffu;
-                    // single precision throughout: the sums below are off by < 16 roundings of terms <= the full mass (1e-6 of
-                    // it), which the factor covers; the unit conversions go through to_fixed_high / to_fixed_low, which
-                    // over- and undercut 1 / from_fixed by more than the roundings of the products (no fp64, no divisions)
-                    float rest = bounds.mass, some = 0.f;
+                    const uint32_t skipped16 = static_cast<uint32_t>(ctrl[kLSigMask]) & 0xffffu;
+                    // A posting carries its row's signature bits 0..15.  The collect sweep tests rows in the integer domain of
+                    // the fixed-point scores, the tile's gate being every row's need:
+                    //   score + mass_low[bits 0..7] - mass_high[bits 8..15] >= tile gate
+                    // mass_low[x]  = the full skipped mass (rounded up, the skipped columns beyond bit 15 counted as held) minus
+                    //                the skipped columns of bits 0..7 that x does NOT hold (rounded down),
+                    // mass_high[x] = the skipped columns of bits 8..15 that x does NOT hold (rounded down).
+                    // Both tables count what a row LACKS, so every entry shares the slack of the largest one, mass_low[255] (a
+                    // row that holds everything): when the gate has to be raised to that entry, the test turns into "score >=
+                    // what the row lacks", which still rejects only rows below the full mass (< pre).  No entry is capped.
+                    // Single precision throughout: the sums are off by < 8 roundings of terms <= the full mass, which the
+                    // factor covers; the unit conversions go through to_fixed_high / to_fixed_low, which over- and undercut
+                    // 1 / from_fixed by more than the roundings of the products (no fp64, no divisions).  The rows that pass
+                    // are a superset of those of `passes`.
+                    float lacks_low = 0.f, lacks_high = 0.f;
                     for (int g = 0; g < 8; ++g) {
-                        if (!((skipped8 >> g) & 1u)) continue;
-                        rest -= bit_idf[g];
-                        if ((tid >> g) & 1) some += bit_idf[g];
+                        if (((skipped16 >> g) & 1u) && !((tid >> g) & 1)) lacks_low += bit_idf[g];
+                        if (((skipped16 >> (g + 8)) & 1u) && !((tid >> g) & 1)) lacks_high += bit_idf[g + 8];
                     }
-                    if (rest < 0.f) rest = 0.f;
-                    // rounded up, and never above the full mass (which already carries its own slack)
-                    const float value = (rest + some) * (1.f + 3.814697265625e-06f) + 1e-30f;
-                    const float mass = value < bounds.mass ? value : bounds.mass;
-                    // The collect sweep tests rows in the integer domain of the fixed-point scores:
-                    //   score + mass16[signature bits 0..7] >= max(tile gate, need32[8-bit sums code])
-                    // mass16 is rounded up and need32 down by more than the float test's own roundings, so the rows
-                    // that pass are a superset of those of `passes` (no conversions, no float decoding per posting).
-                    const float mass_units = mass * to_fixed_high + 2.5f;
-                    mass16[tid] = static_cast<uint16_t>(mass_units < 65535.f ? mass_units : 65535.f);
-                    const float need_units = bounds.coef * (decode_sums8(tid) + maxint32) * to_fixed_low - 2.5f;
-                    need32[tid] = tid == 255 ? 0x7fffffffu
-                                             : static_cast<uint32_t>(need_units < 0.f ? 0.f : (need_units < 65535.f ? need_units : 65535.f));
+                    const float full_units = bounds.mass * to_fixed_high + 2.5f;
+                    const uint32_t full = static_cast<uint32_t>(full_units < 65535.f ? full_units : 65535.f);
+                    const uint32_t low = static_cast<uint32_t>(lacks_low * (1.f - 3.814697265625e-06f) * to_fixed_low);
+                    const uint32_t high = static_cast<uint32_t>(lacks_high * (1.f - 3.814697265625e-06f) * to_fixed_low);
+                    mass_low[tid] = static_cast<uint16_t>(full - min(low, full));
+                    mass_high[tid] = static_cast<uint16_t>(min(high, 65535u));
                 }
             }
             const bool sparse = tight && sparse_mode;
@@ -918,8 +914,8 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                     alive[u] = at < items && locate_in(copy, directory, total, at, first, value[u]) &&
                                DS_OK_INDEX(3, first, a.n_quads);
                     q[u] = alive[u] ? load_quad(quads, first) : make_uint2(kPadQuad, kPadQuad);
-                    if (keep)  // idle lanes carry the padding code 255: their (zero) scores never pass the collect sweep's test
-                        info[u] = alive[u] ? load_quad(sums_quads, first) : make_uint2(0xff00ff00u, 0xff00ff00u);
+                    if (keep)  // idle lanes carry the padding quad: the collect sweep's test turns its word away
+                        info[u] = alive[u] ? load_quad(sums_quads, first) : make_uint2(0u, 0u);
                     if constexpr (kCountBytes) {  // 8 bytes per quad, 8 more for the row info of a kept round
                         const unsigned long long loaded = __ballot(alive[u]);
                         if (count_sparse && lane == 0)
@@ -1056,13 +1052,13 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                 // Cheap integer pre-test on the taken fixed-point scores: a row can only pass `s + mass >= pre` if its
                 // score reaches (pre - mass) in fixed-point units (rounded down, minus slack: a superset of the float
                 // test).  Most quads have no such row and skip the per-row decoding and table lookups altogether.
-                // A row whose score is zero here (another posting of the row took it first) has nothing but its mass16:
-                // the gate is kept at or above the largest mass16 so that such a row fails `have >= need` without a
+                // A row whose score is zero here (another posting of the row took it first) has nothing but its mass entry:
+                // the gate is kept at or above the largest one (mass_low[255]) so that such a row fails `have >= need` without a
                 // test of its own.  (It can still pass when it owns every skipped column AND the gate had to be
                 // raised, i.e. pre - mass is within the tables' 4 units of rounding slack; the refinement rejects it.)
                 if (__builtin_expect(tables_fresh, 0)) {
                     tables_fresh = false;
-                    mass_units_max = uniform(static_cast<uint32_t>(mass16[255]));
+                    mass_units_max = uniform(static_cast<uint32_t>(mass_low[255]));
                 }
                 const uint32_t gate_fixed = [&]() {  // the tile's row-independent bound `here.pre`, rounded down (float32:
                     // to_fixed_low undercuts 1 / from_fixed by more than the roundings of the product)
@@ -1079,7 +1075,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         const uint32_t shift = (quad[u].x >> 11) & 16u;  // the quad's half
                         const uint32_t info[4] = {quad_info[u].x & 0xffffu, quad_info[u].x >> 16, quad_info[u].y & 0xffffu,
                                                   quad_info[u].y >> 16};
-                        // pass <=> score + mass16 >= need <=> score >= need - mass16 (>= 0: see the gate).  (Rounds 2-3 issued the
+                        // pass <=> score + mass_low - mass_high >= gate <=> score >= gate - mass_low + mass_high (>= 0: see the gate).  (Rounds 2-3 issued the
                         // eight table look-ups of a quad in FRONT of its atomics, for every quad; batching a round's twelve
                         // atomics on top of the two-level test gained nothing: profiles/r04_tuning.txt.)
                         uint32_t least[4];
@@ -1103,7 +1099,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                             int touched = 0, level1 = 0;
                             for (int e = 0; e < 4; ++e) {
                                 touched += taken[e] != 0u;
-                                level1 += taken[e] != 0u && taken[e] + mass16[255] >= gate_fixed;
+                                level1 += taken[e] != 0u && taken[e] + mass_units_max >= gate_fixed;
                             }
                             for (int d = 32; d > 0; d >>= 1) { touched += __shfl_xor(touched, d); level1 += __shfl_xor(level1, d); }
                             if (lane == 0) { atomicAdd(&a.control[20], touched); atomicAdd(&a.control[21], level1);
@@ -1111,7 +1107,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         }
 #endif
                         // Level 1, no look-up: every entry of the two tables is bounded by the gate and the largest mass
-                        // (least[e] >= gate_fixed - mass16[255]), so a quad whose four scores all stay below that bound has
+                        // (least[e] >= gate_fixed - mass_low[255]), so a quad whose four scores all stay below that bound has
                         // no row for the exact test.  With the rows in sums32 order the tile's gate is sharp: 73 % (C2) /
                         // 83 % (C5 shape) of the wave-quads end here (diagnostics build, profiles/r04_phase_table_*).
                         // (the largest of the four by packed 16-bit maxima of the words as the atomics returned them, then the
@@ -1119,11 +1115,11 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         if (__ballot(((max_of_packed4(before) >> shift) & 0xffffu) >= gate_fixed - mass_units_max) == 0) continue;
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            least[e] = max(gate_fixed, need32[info[e] >> 8]) - mass16[info[e] & 0xffu];
+                            least[e] = gate_fixed - mass_low[info[e] & 0xffu] + mass_high[info[e] >> 8];
                         bool pass[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            pass[e] = taken[e] >= least[e];  // padding entries carry code 255: never; zero scores: see the gate
+                        for (int e = 0; e < 4; ++e)  // padding entries and idle lanes (the trash word's score is not zero): never; zero scores: see the gate
+                            pass[e] = (taken[e] >= least[e]) & (word[e] != kPadWord);
                         if (__ballot(pass[0] | pass[1] | pass[2] | pass[3]) == 0) continue;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) append_raw(pass[e], taken[e], (word[e] << 1) | (shift >> 4));
@@ -1137,7 +1133,7 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         uint32_t first = 0, value = 0;
                         live[u] = at < n_items && locate(at, first, value) && DS_OK_INDEX(3, first, a.n_quads);
                         quad[u] = live[u] ? load_quad(quads, first) : make_uint2(kPadQuad, kPadQuad);
-                        quad_info[u] = live[u] ? load_quad(sums_quads, first) : make_uint2(0xff00ff00u, 0xff00ff00u);
+                        quad_info[u] = live[u] ? load_quad(sums_quads, first) : make_uint2(0u, 0u);
                         if constexpr (kCountBytes) {
                             const unsigned long long loaded = __ballot(live[u]);
                             if (lane == 0) atomicAdd(requested, static_cast<unsigned long long>(__popcll(loaded)) * 16u);
@@ -1360,8 +1356,22 @@ __global__ __launch_bounds__(kThreads, kWorkgroupsPerCu * kThreads / 256) void d
                         const double c = cut_value / (1.0 + cut_value) * (1.0 - 9.5367431640625e-07);
                         new_coef = round_down_positive(c);
                         new_cut = round_down_positive(cut_value);
-                        const double p = static_cast<double>(new_coef) *
-                                         (static_cast<double>(a.sums_min) + static_cast<double>(maxint32)) *
+                        // The smallest sums32 a row that can still qualify may have: jaccard = s / (sums + maxint - s) and
+                        // s <= sums32[row], so the denominator is at least maxint and jaccard <= sums32 / maxint -- a row with
+                        // sums32 < cut * maxint cannot qualify in whatever tile it lies (the band test at the epoch's end relies
+                        // on the same inequality, with the same relative slack of 1e-5).  PRECONDITION, the band test's own:
+                        // sums32[row] is the total of the row's columns (match_maker.py:174), short of it by float32 rounding
+                        // at most.  ds_index_create admits rows whose sums32 lies up to 1e-4 below their total to this kernel;
+                        // the slack of 1e-5 and the cut's own margin cover a relative shortfall d as long as cut * (2 * d - 1e-5)
+                        // stays below the margin (s <= sums32 * (1 + d) gives jaccard <= cut * (1 + 2 * d) at the band's edge):
+                        // about 5e-6, the rounding of a float32 total, not that whole range.  Every
+                        // row that can qualify therefore needs s >= coef * (cut * maxint + maxint) = cut * maxint, (1 + cut)
+                        // times the bound from the index's smallest sums32 alone.  `pre` stays an UPPER-bound test only ("a row
+                        // whose upper bound lies below pre cannot qualify"); nothing reads it as a lower estimate.
+                        const double band_edge = static_cast<double>(new_cut) * static_cast<double>(maxint32) * (1.0 - 1e-5);
+                        const double sums_floor = band_edge > static_cast<double>(a.sums_min) ? band_edge
+                                                                                              : static_cast<double>(a.sums_min);
+                        const double p = static_cast<double>(new_coef) * (sums_floor + static_cast<double>(maxint32)) *
                                          (1.0 - 9.5367431640625e-07);
                         new_pre = p > static_cast<double>(FLT_MIN) ? round_down_positive(p) : FLT_MIN;
                     }

@@ -472,14 +472,15 @@ int build_index_image(const int64_t *rowptr, const int32_t *truth_idx, const flo
                     const int64_t t = truth_idx[p];
                     const uint32_t local = static_cast<uint32_t>(t - tile_first);
                     uint64_t &at = write[local & 1u];
-                    posting_sums[at] = static_cast<uint16_t>((ds::encode_sums8(sums32[t]) << 8) |
-                                                              (records[static_cast<size_t>(t) * ds::kRowRecordWords] & 0xffu));
+                    // 16 membership bits travel with every posting: the row's signature bits 0..15 (no per-posting sums code:
+                    // the rows are in sums32 order, the tile's smallest sums32 stands in for every row's own)
+                    posting_sums[at] = static_cast<uint16_t>(records[static_cast<size_t>(t) * ds::kRowRecordWords] & 0xffffu);
                     postings[at++] = static_cast<uint16_t>(((local & 1u) << 15) | (local >> 1));
                 }
-                for (int part = 0; part < 2; ++part)  // padding: the word behind the tile, code 255
+                for (int part = 0; part < 2; ++part)  // padding: the word behind the tile (which the collect sweep tells by itself)
                     for (uint64_t i = write[part]; i < part_end[part]; ++i) {
                         postings[i] = static_cast<uint16_t>((part << 15) | pad_word);
-                        posting_sums[i] = static_cast<uint16_t>(0xff00);
+                        posting_sums[i] = static_cast<uint16_t>(0);
                     }
             }
         }

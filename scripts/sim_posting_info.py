@@ -13,40 +13,15 @@ usage: sim_posting_info.py <truth titles> <k> [queries]      (~2 min at 500k x 1
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
-from doppel_speller_amd import synth  # noqa: E402
+from sim_common import code8_lower_bound, index_model  # noqa: E402
 
 N, K = int(sys.argv[1]), int(sys.argv[2])
 Q = int(sys.argv[3]) if len(sys.argv) > 3 else 100
-TILE = 12288 if N <= 10_000_000 else 28672
-w = synth.make_workload(N, 2000, seed=20260101)
-rowptr, tidx, idf32, sums32 = (np.asarray(x) for x in (w.rowptr, w.truth_idx, w.idf32, w.sums32))
-order = np.argsort(sums32, kind="stable")
-pos = np.empty(N, np.int64)
-pos[order] = np.arange(N)
-sums_sorted = sums32[order]
-ntiles = (N + TILE - 1) // TILE
-tile_min = sums_sorted[np.arange(ntiles) * TILE]
-tile_max = sums_sorted[np.minimum(N, (np.arange(ntiles) + 1) * TILE) - 1]
-tile_of_row = pos // TILE
-tile_min_of_row = tile_min[tile_of_row].astype(np.float64)   # no per-row sums information at all: the tile's smallest
-df = np.diff(rowptr)
-dense_rank = np.empty(len(df), np.int64)
-dense_rank[np.argsort(-df, kind="stable")] = np.arange(len(df))          # 0 = the densest column of the index
-has_sig = (dense_rank < 128) & (df * 256 >= N)
-
-
-def code8_lower_bound(x):
-    """decode(encode_sums8(x)) of csrc/ds_common.h: 4-bit exponent (2^-3 .. 2^12), 4-bit mantissa, truncated."""
-    bits = x.astype(np.float32).view(np.uint32)
-    exponent = (bits >> 23).astype(np.int64) - 124
-    code = np.where(x < 0.125, 0, np.minimum(0xfe, (np.clip(exponent, 0, 15) << 4) | ((bits >> 19) & 0xf)))
-    code = np.where(exponent > 15, 0xfe, code)
-    out = ((((code >> 4) + 124).astype(np.uint32) << 23) | ((code & 0xf).astype(np.uint32) << 19)).view(np.float32)
-    return np.where(code == 0, 0.0, out).astype(np.float64)
-
-
+m = index_model(N, 2000)
+w, rowptr, tidx, idf32, sums32, TILE, pos, sums_sorted, ntiles, tile_min, tile_max, tile_of_row, tile_min_of_row, df, dense_rank, has_sig = (getattr(m, name) for name in
+    "w rowptr tidx idf32 sums32 TILE pos sums_sorted ntiles tile_min tile_max tile_of_row tile_min_of_row df dense_rank has_sig".split())
 sums_lb8 = code8_lower_bound(sums32)
 variants = [(b, s, t) for t in ("selection", "tile") for s in ("code8", "exact", "tilemin") for b in (8, 16, 32, 128)]
 raw = {v: 0 for v in variants}
