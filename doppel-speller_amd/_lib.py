@@ -10,7 +10,7 @@ _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
             "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
-            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip")
+            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip")
 _lib = None
 
 
@@ -123,6 +123,9 @@ def _declare(handle):
         "ds_device_name": [c.c_int, c.c_char_p, c.c_size_t],
         "ds_device_memory": [c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64)],
         "ds_index_create": [p, p, p, p, c.c_int64, c.c_int64, c.c_int, c.POINTER(p)],
+        "ds_index_create_device": [p, p, p, p, c.c_int64, c.c_int64, c.c_int, c.POINTER(p)],
+        "ds_index_read": [p, c.c_char_p, p, c.c_size_t, c.POINTER(c.c_size_t)],
+        "ds_index_build_option": [c.c_char_p, c.c_int64],
         "ds_index_info": [p, c.POINTER(c.c_int64)],
         "ds_index_duplicate_ranks": [p, p, p, c.c_int64, c.c_int64, p],
         "ds_index_image_digest": [p, p, p, p, c.c_int64, c.c_int64, c.c_int64, p],
@@ -264,7 +267,8 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_batch_create_device", "ds_trainer_batch_destroy", "ds_trainer_batch_step", "ds_trainer_batch_read",
     "ds_trainer_batch_bytes", "ds_trainer_batch_option", "ds_trainer_set_sampling", "ds_trainer_batch_set_sampling",
     "ds_auc_device", "ds_auc", "ds_weighted_logloss_device", "ds_metrics_option", "ds_trainer_set_metrics",
-    "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes")
+    "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes",
+    "ds_index_create_device", "ds_index_read", "ds_index_build_option")
 
 
 def lib():

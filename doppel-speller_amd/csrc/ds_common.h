@@ -30,8 +30,8 @@ constexpr int kSignatureWords = kSignatureBits / 32;
 constexpr int kRowRecordWords = 8;          // 32-byte row record: signature, sums32, duplicate rank
 constexpr int kControlWords = 32;            // int32 control block in HBM (queue heads, counters)
 
-// splitmix64 finaliser: a bijective 64-bit mixer (row-set hashes of the index build)
-inline uint64_t mix64(uint64_t x)
+// splitmix64 finaliser: a bijective 64-bit mixer (row-set hashes of the index build, on the host and on the device)
+__host__ __device__ inline uint64_t mix64(uint64_t x)
 {
     x ^= x >> 30;
     x *= 0xbf58476d1ce4e5b9ull;
@@ -46,6 +46,7 @@ enum QueryStatus : int32_t { kQueryDone = 0, kQuerySlow = 1, kQueryErrorTopN = 2
 void set_error(const char *format, ...);
 void duplicate_ranks(const int64_t *rowptr, const int32_t *truth_idx, const float *sums32, int64_t V, int64_t N,
                      uint16_t *rank_out);
+int64_t choose_tile_rows(int64_t N);   // tile size of an index of N rows (DS_GEOMETRY overrides)
 int hip_failed(hipError_t error, const char *what, const char *file, int line);
 
 #define DS_HIP(call)                                                          \

@@ -146,6 +146,18 @@ void duplicate_ranks(const int64_t *rowptr, const int32_t *truth_idx, const floa
     });
 }
 
+// The tile size of an index of N rows: shared by the host build and the device build (ds_index_build.hip).
+int64_t choose_tile_rows(int64_t N)
+{
+    // geometry: narrow tiles for truth sets of up to kNarrowMaxTruth rows (DS_GEOMETRY=wide|narrow overrides, for tests)
+    int64_t tile_rows = N <= ds::kNarrowMaxTruth ? ds::kNarrowTileRows : ds::kWideTileRows;
+    if (const char *geometry = getenv("DS_GEOMETRY"); geometry != nullptr) {
+        if (std::strcmp(geometry, "wide") == 0) tile_rows = ds::kWideTileRows;
+        if (std::strcmp(geometry, "narrow") == 0) tile_rows = ds::kNarrowTileRows;
+    }
+    return tile_rows;
+}
+
 }  // namespace ds
 
 extern "C" {
@@ -222,17 +234,6 @@ struct IndexImage {
     std::vector<uint16_t> row_cols16;
     bool wide_start = false, wide_cols = false;
 };
-
-int64_t choose_tile_rows(int64_t N)
-{
-    // geometry: narrow tiles for truth sets of up to kNarrowMaxTruth rows (DS_GEOMETRY=wide|narrow overrides, for tests)
-    int64_t tile_rows = N <= ds::kNarrowMaxTruth ? ds::kNarrowTileRows : ds::kWideTileRows;
-    if (const char *geometry = getenv("DS_GEOMETRY"); geometry != nullptr) {
-        if (std::strcmp(geometry, "wide") == 0) tile_rows = ds::kWideTileRows;
-        if (std::strcmp(geometry, "narrow") == 0) tile_rows = ds::kNarrowTileRows;
-    }
-    return tile_rows;
-}
 
 int build_index_image(const int64_t *rowptr, const int32_t *truth_idx, const float *idf32, const float *sums32,
                       int64_t V, int64_t N, int64_t tile_rows, IndexImage &image)
@@ -555,7 +556,7 @@ int ds_index_create(const int64_t *rowptr, const int32_t *truth_idx, const float
     IndexImage image;
     const auto started = std::chrono::steady_clock::now();
     {
-        const int built = build_index_image(rowptr, truth_idx, idf32, sums32, V, N, N > 0 ? choose_tile_rows(N) : 0, image);
+        const int built = build_index_image(rowptr, truth_idx, idf32, sums32, V, N, N > 0 ? ds::choose_tile_rows(N) : 0, image);
         if (built != DS_OK) return built;
     }
     const int64_t n_tiles = image.n_tiles, tile_rows = image.tile_rows, nnz = image.nnz;

@@ -43,10 +43,30 @@ def sequential_sums(values, lengths, dtype):
     return out
 
 
-class TruthIndex:
-    """The truth inverted index of match_maker.py:122-133 resident in HBM (ds_index_create)."""
+INDEX_BUILDS = ("host", "device")
 
-    def __init__(self, rowptr, truth_idx, idf32, sums32, device=0):
+
+def validate_index_build(build, name="build"):
+    if not isinstance(build, str) or build not in INDEX_BUILDS:
+        raise ValueError(f"{name} must be one of {INDEX_BUILDS}, not {build!r}")
+
+
+# ds_index_read: the arrays of an index and their element types (row_start / row_cols: by the widths in "scalars")
+IMAGE_ARRAYS = {"col_ptr": np.uint32, "postings": np.uint16, "posting_sums": np.uint16, "records": np.uint32,
+                "sums32": np.float32, "tile_sums_min": np.float32, "tile_sums_max": np.float32, "sig_column": np.int8,
+                "row_start": None, "row_cols": None, "idf32": np.float32}
+IMAGE_SCALARS = ("n_tiles", "n_quads", "sums_min_bits", "literal_only", "rows_sorted", "row_start_bytes",
+                 "row_cols_bytes", "tile_rows")
+
+
+class TruthIndex:
+    """The truth inverted index of match_maker.py:122-133 resident in HBM.  build: "host" (ds_index_create: a threaded
+    host build, then uploads) or "device" (ds_index_create_device: the CSR is uploaded and everything else derived
+    in HBM); both leave the same bytes in HBM."""
+
+    def __init__(self, rowptr, truth_idx, idf32, sums32, device=0, build="host"):
+        validate_index_build(build)
+        self.build = build
         self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
         self.truth_idx = np.ascontiguousarray(truth_idx, dtype=np.int32)
         self.idf32 = np.ascontiguousarray(idf32, dtype=np.float32)
@@ -57,10 +77,31 @@ class TruthIndex:
         if self.idf32.shape[0] != self.n_columns:
             raise ValueError("idf32 must have one entry per column")
         self.handle = ctypes.c_void_p()
-        _lib.check(_lib.lib().ds_index_create(
+        create = _lib.lib().ds_index_create if build == "host" else _lib.lib().ds_index_create_device
+        _lib.check(create(
             _lib.pointer(self.rowptr), _lib.pointer(self.truth_idx), _lib.pointer(self.idf32),
             _lib.pointer(self.sums32), self.n_columns, self.n_truth, device, ctypes.byref(self.handle)),
-            "ds_index_create")
+            "ds_index_create" if build == "host" else "ds_index_create_device")
+
+    def read(self, name, dtype):
+        """One array of the index as it lies in HBM (ds_index_read), flat."""
+        size = ctypes.c_size_t(0)
+        _lib.lib().ds_index_read(self.handle, name.encode(), None, 0, ctypes.byref(size))   # sizes the buffer
+        out = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+        _lib.check(_lib.lib().ds_index_read(self.handle, name.encode(), _lib.pointer(out), out.nbytes,
+                                            ctypes.byref(size)), "ds_index_read")
+        return out
+
+    def image(self):
+        """Every array the index holds in HBM as NumPy arrays, plus its scalar fields (IMAGE_SCALARS)."""
+        scalars = dict(zip(IMAGE_SCALARS, self.read("scalars", np.int64).tolist()))
+        widths = {"row_start": np.int64 if scalars["row_start_bytes"] == 8 else np.uint32,
+                  "row_cols": np.int32 if scalars["row_cols_bytes"] == 4 else np.uint16}
+        out = {name: self.read(name, dtype or widths[name]) for name, dtype in IMAGE_ARRAYS.items()}
+        out["col_ptr"] = out["col_ptr"].reshape(self.n_columns, scalars["n_tiles"] + 1)
+        out["records"] = out["records"].reshape(self.n_truth, 8)
+        out.update(scalars)
+        return out
 
     def info(self):
         raw = (ctypes.c_int64 * 8)()

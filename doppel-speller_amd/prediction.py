@@ -27,7 +27,7 @@ import numpy as np
 from . import _lib
 from .feature_engineering import (ALLOWED_CHARACTERS, LEVENSHTEIN_RATIO_THRESHOLD, TitleTable, encode_collection,
                                   truth_word_counts)
-from .match_maker import NativeProblem, TruthIndex
+from .match_maker import NativeProblem, TruthIndex, validate_index_build
 from .pipeline import (BYTES_PER_EXPLAIN, BYTES_PER_PAIR, BYTES_PER_PARTS, BYTES_PER_RANK, EXHAUSTIVE_MAX_N, MAX_GRAMS,
                        PREDICTION_PROBABILITY_THRESHOLD, CandidatePipeline)
 
@@ -523,16 +523,21 @@ def query_rows(chars, offsets, vocabulary_keys, idf32, idf64, n_gram=N_GRAM, col
 class TruthSide:
     """The device-resident truth side of a set of transformed titles: the vocabulary of the native index build, the
     Jaccard index (TruthIndex), the encoded titles with their word counts (TitleTable), and what `query_rows` needs to
-    number a query's n-grams in that vocabulary."""
+    number a query's n-grams in that vocabulary.  build_index: "host" or "device", where the Jaccard index is built
+    (TruthIndex); `index_build_ms` is the wall clock of that call."""
 
-    def __init__(self, transformed_titles, device=0):
+    def __init__(self, transformed_titles, device=0, build_index="host"):
+        validate_index_build(build_index, "build_index")
         chars, offsets = _pack(transformed_titles)
         check_characters(chars, offsets, "truth")
         problem = NativeProblem.from_flat(chars, offsets, np.zeros(1, np.uint8), np.zeros(1, np.int64), N_GRAM)
         arrays = problem.arrays()
         self.vocabulary_keys, self.idf32, self.idf64 = arrays["vocabulary_keys"], arrays["idf32"], arrays["idf64"]
         self.columns = column_table(self.vocabulary_keys)
-        self.index = TruthIndex(arrays["rowptr"], arrays["truth_idx"], arrays["idf32"], arrays["sums32"], device)
+        started = time.perf_counter()
+        self.index = TruthIndex(arrays["rowptr"], arrays["truth_idx"], arrays["idf32"], arrays["sums32"], device,
+                                build=build_index)
+        self.index_build_ms = (time.perf_counter() - started) * 1000.0    # the create call: it ends synchronised
         problem.close()
         enc, lengths = encode_collection(chars, offsets, _CODE_OF)
         counts = truth_word_counts(chars, offsets, separators=(ord(" "),))
@@ -555,15 +560,18 @@ class Prediction:
     otherwise, NaN when the query never reached the model), and `timings` the milliseconds of every stage.
     prepare_queries: "device" (default) transforms and encodes the query titles and derives their Jaccard rows on the
     device (`prepare_queries`, CandidatePipeline.load_queries_device); "host" does it on the host (transform_titles,
-    query_rows, encode_collection).  Both give the same answers, details and errors."""
+    query_rows, encode_collection).  Both give the same answers, details and errors.
+    build_index: "host" (default) or "device": where the truth index is built (TruthIndex); the index is the same."""
 
     def __init__(self, truth_titles, truth_title_ids, model, top_n=100, device=0, transform=True,
                  levenshtein_threshold=LEVENSHTEIN_RATIO_THRESHOLD,
-                 probability_threshold=PREDICTION_PROBABILITY_THRESHOLD, chunk_queries=None, prepare_queries="device"):
+                 probability_threshold=PREDICTION_PROBABILITY_THRESHOLD, chunk_queries=None, prepare_queries="device",
+                 build_index="host"):
         truth_titles = list(truth_titles)
         self.truth_title_ids = validate_truth(truth_titles, truth_title_ids, top_n)
         _validate_chunk(chunk_queries)
         _validate_prepare(prepare_queries)
+        validate_index_build(build_index, "build_index")
         if model is None or not hasattr(model, "predict_device"):
             raise ValueError("model must be a ForestModel")
         self.model = model
@@ -583,7 +591,8 @@ class Prediction:
         self.timings = {}
 
         self.truth_titles = self._transform(truth_titles)
-        truth = TruthSide(self.truth_titles, device)
+        truth = TruthSide(self.truth_titles, device, build_index=build_index)
+        self.index_build_ms = truth.index_build_ms
         self._vocabulary_keys, self._idf32, self._idf64 = truth.vocabulary_keys, truth.idf32, truth.idf64
         self._columns, self.index, self.truth_table = truth.columns, truth.index, truth.table
         self._space = truth.space

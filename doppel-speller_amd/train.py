@@ -623,7 +623,7 @@ class TrainModelResult:
 
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
-                transform=True, evaluation_fractions=None, cover=False, **fit_parameters):
+                transform=True, evaluation_fractions=None, cover=False, build_index="host", **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -634,7 +634,7 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     cover: also count the training matrix through the finished trees while it is still in HBM
     (ForestModel.fit_cover_device), so that the returned model can explain its predictions
     (predict_contributions, Prediction.explain); `timings` then has a "cover" entry.  The trees are the same either
-    way."""
+    way.  build_index: "host" or "device", where the truth index is built (TruthSide)."""
     from .training_set import FeatureEngineering
     started = time.perf_counter()
     unknown = set(fit_parameters) - set(inspect.signature(validate_parameters).parameters)
@@ -643,7 +643,7 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     validate_parameters(**fit_parameters)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
-                            evaluation_fractions=evaluation_fractions)
+                            evaluation_fractions=evaluation_fractions, build_index=build_index)
     sets = fe.generate_device_data_sets()
     timings = dict(fe.timings)
     trainer = ForestTrainer(device)

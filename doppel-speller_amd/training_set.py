@@ -33,6 +33,7 @@ from . import _lib
 from .distributed import slice_queries
 from .feature_engineering import (ALLOWED_CHARACTERS, FEATURES_COUNT, MAX_CHARACTERS_ALLOWED_IN_THE_TITLE, SPACE_CODE,
                                   TitleTable, encode_collection)
+from .match_maker import validate_index_build
 from .prediction import (TRAIN_NOT_FOUND_VALUE, TruthSide, _CODE_OF, _pack, _validate_chunk, check_characters,
                          default_chunk, transform_or_keep, validate_truth)
 
@@ -217,7 +218,7 @@ class FeatureEngineering:
     which sampled (settings.py:58, 10; at most 16).  seed: the streams of the misspellings and the samples, and the
     NumPy generator of the split.  chunk_queries: train titles per top-n pass (default: what a quarter of the free HBM
     holds); the result does not depend on it.  evaluation_fractions: {"generated", "negative", "positive"} -> share
-    of ALL rows drawn into the evaluation set (settings.py:47-49).
+    of ALL rows drawn into the evaluation set (settings.py:47-49).  build_index: "host" or "device", passed to TruthSide.
 
     After a call: `rows` (DataFrame: kind, query_index = train row for kinds 2 / 3 and truth row for kind 1,
     truth_row, target, evaluation), `misspelled_titles` (the queries of the kind 1 rows, in order), `features` (every
@@ -225,7 +226,8 @@ class FeatureEngineering:
     leaves the matrices in HBM (DeviceDataSets)."""
 
     def __init__(self, truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0,
-                 device=0, transform=True, chunk_queries=None, evaluation_fractions=None):
+                 device=0, transform=True, chunk_queries=None, evaluation_fractions=None, build_index="host"):
+        validate_index_build(build_index, "build_index")
         truth_titles, train_titles = list(truth_titles), list(train_titles)
         unknown = set(evaluation_fractions or {}) - set(EVALUATION_FRACTIONS)
         if unknown:
@@ -238,6 +240,7 @@ class FeatureEngineering:
         self.top_n, self.sample_n, self.seed = int(top_n), int(sample_n), int(seed)
         self.device, self.transform, self.chunk_queries = device, transform, chunk_queries
         self._raw_truth, self._raw_train = truth_titles, train_titles
+        self.build_index = build_index
         self._truth = None
         self.rows = self.misspelled_titles = self.features = None
         self.timings = {}
@@ -337,7 +340,7 @@ class FeatureEngineering:
             self.train_titles = transform_or_keep(self._raw_train, self.transform)
             timings["host_prepare"] += (time.perf_counter() - started) * 1000.0
             mark = time.perf_counter()
-            self._truth = TruthSide(self.truth_titles, device)
+            self._truth = TruthSide(self.truth_titles, device, build_index=self.build_index)
             timings["truth_side"] = (time.perf_counter() - mark) * 1000.0
         truth = self._truth
         n_truth = truth.table.n

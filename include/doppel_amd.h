@@ -66,6 +66,32 @@ int ds_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes);
  * process, at most 32); DS_BUILD_LOG=1 prints its phase times on stderr. */
 int ds_index_create(const int64_t *rowptr, const int32_t *truth_idx, const float *idf32, const float *sums32,
                     int64_t V, int64_t N, int device, ds_index **out);
+/* The same index built on the device (ds_index_build.hip): same arguments, same checks, same error codes and
+ * messages, and for the same input and tile size every array and scalar of the index equals what ds_index_create
+ * uploads, byte for byte (radix sorts and scans only: no position depends on the arrival order of an atomic).  It
+ * uploads rowptr, truth_idx, idf32 and sums32 and derives the rest in HBM; only the choice of the signature columns
+ * (from rowptr) and the range test of idf32 stay on the host.  A posting list that is not strictly ascending within
+ * [0, N) is refused by a kernel of its own before any other kernel reads the rows.  Returns synchronised.
+ * Honours DS_SORT_ROWS=0 and DS_GEOMETRY as ds_index_create does.
+ * Limits: nnz >= 2^32 - 1 needs 64-bit row starts, which only ds_index_create builds: DS_E_ARG.  Peak scratch, with
+ * M = nnz, T = tiles, K = ceil(max(M, N) / 2048):
+ *   16 max(M, N) + 1024 K + 8 M + 52 N + 4 V (T + 1) + 8 V + 8 ceil(max(M + 1, 256 K, V (T + 1), N + 1) / 2048) + 40 bytes
+ * (two sort buffers, the digit table, truth_idx and the even-row scan, the per-row arrays, the cell starts, rowptr, the
+ * scan spine).  Scratch plus the index's own arrays (postings at their upper bound M / 4 + 2 min(M, V T) quads) plus
+ * 64 MiB are checked against the free HBM before anything is allocated or launched: DS_E_HIP, nothing left allocated. */
+int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, const float *idf32, const float *sums32,
+                           int64_t V, int64_t N, int device, ds_index **out);
+/* Copies one array of an index (built either way) to the host.  name: "col_ptr" uint32[V][tiles + 1], "postings" and
+ * "posting_sums" uint16[4 * quads], "records" uint32[N][8], "sums32" float[N + 8] (internal order, 8 zeros behind),
+ * "tile_sums_min" / "tile_sums_max" float[tiles], "sig_column" int8[V], "row_start" uint32[N + 1] (int64 when
+ * scalars[5] = 8), "row_cols" uint16[nnz] (int32 when scalars[6] = 4), "idf32" float[V], and "scalars" int64[8] =
+ * n_tiles, n_quads, bits of sums_min, literal_only, rows_sorted, bytes of a row start, bytes of a forward column, tile
+ * rows.  *bytes is always set to the array's size; an unknown name, a null dst or capacity < *bytes gives DS_E_ARG. */
+int ds_index_read(const ds_index *index, const char *name, void *dst, size_t capacity, size_t *bytes);
+/* Switches of the device build, for tests.  "duplicate_hash_bits" (0..64, default 0 = all): ds_index_create_device
+ * keeps only that many low bits of both row hashes of the duplicate ranks, so that distinct rows share hash groups
+ * and the rule "a member is compared with the group's largest row, never with another member" decides the ranks. */
+int ds_index_build_option(const char *name, int64_t value);
 void ds_index_destroy(ds_index *index);
 /* Host-only part of ds_index_create, exported for tests: rank_out[t] = number of truth rows with the same column set
  * and the same sums32 bits as row t but a larger row index (saturating at 65535).  fast_arg_top_k returns the k
