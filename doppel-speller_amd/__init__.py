@@ -17,6 +17,9 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         .duplicate_groups(levenshtein_threshold, probability_threshold)   -> the groups of truth titles that are
             duplicates of each other: the connected components of the exact, close and model links among the truth
             set's own rows, found on the device (this project's own)
+        .one_to_one_matches(titles, n)   -> one answer per title with every truth title given to one title at most: the
+            stable matching of the titles' ranked slots, found on the device (this project's own; for linking one
+            de-duplicated file against another)
         .explain(titles)   -> for every title its best candidate by the model and why: the contribution of each of
             the 66 features to that pair's margin (TreeSHAP, or Saabas), computed on the device (this project's own);
             FEATURE_NAMES names the columns, top_contributions(contributions, n) picks the largest per row
@@ -49,9 +52,10 @@ from .feature_engineering import (  # noqa: F401
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
 from .forest import ForestModel, validate_cover  # noqa: F401
-from .prediction import (DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS, LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS,  # noqa: F401
-                         EXPLAIN_COLUMNS, Candidates, Prediction, duplicate_frame, predictions_accuracy,
-                         top_contributions, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
+from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS,  # noqa: F401
+                         LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS, EXPLAIN_COLUMNS, Candidates, Prediction,
+                         assignment_frame, duplicate_frame, predictions_accuracy, top_contributions,
+                         validate_assignment, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, roc_auc, train_model)

@@ -10,7 +10,7 @@ _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
             "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
-            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip")
+            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip", "ds_assign.hip")
 _lib = None
 
 
@@ -159,6 +159,9 @@ def _declare(handle):
         "ds_duplicate_links_device": [p, p, p, p, c.c_int64, c.c_int64, c.c_int32, c.c_int64, c.c_int32, c.c_float, p, p, p, p],
         "ds_duplicate_finish_device": [p, c.c_int64, p, p, p],
         "ds_duplicates_option": [c.c_char_p, c.c_int64],
+        "ds_assign_edges_device": [p, p, p, p, c.c_int64, c.c_int64, c.c_int64, c.c_int32, c.c_int64, c.c_float, p, p, p],
+        "ds_assign_solve_device": [p, p, c.c_int64, c.c_int32, c.c_int64, p, p, p, p, p, p, p],
+        "ds_assign_option": [c.c_char_p, c.c_int64],
         "ds_exact_matches": [p, p, c.c_int64, p],
         "ds_exact_matches_device": [p, p, c.c_int64, c.c_int64, p, p, p],
         "ds_problem_create": [p, p, c.c_int64, p, p, c.c_int64, c.c_int32, c.POINTER(p)],
@@ -268,7 +271,8 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_batch_bytes", "ds_trainer_batch_option", "ds_trainer_set_sampling", "ds_trainer_batch_set_sampling",
     "ds_auc_device", "ds_auc", "ds_weighted_logloss_device", "ds_metrics_option", "ds_trainer_set_metrics",
     "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes",
-    "ds_index_create_device", "ds_index_read", "ds_index_build_option")
+    "ds_index_create_device", "ds_index_read", "ds_index_build_option", "ds_assign_edges_device",
+    "ds_assign_solve_device", "ds_assign_option")
 
 
 def lib():

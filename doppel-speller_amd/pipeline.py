@@ -218,6 +218,21 @@ class CandidatePipeline:
             raise ValueError(f"the last enqueue_rank_matches ranked {self._ranked_n} slots per query, not {n}")
         return tuple(a.to_host(self.n_queries * n).reshape(self.n_queries, n) for a in self._ranked)
 
+    def enqueue_assign_edges(self, keys, rows, probability_threshold, stream=None):
+        """The one-to-one stage's view of this chunk's ranked slots (ds_assign_edges_device), after
+        `enqueue_rank_matches(n)`, over its outputs: per slot the key of its edge (0: no edge) and its row, written into
+        the call-wide `keys` uint64[Q, n] and `rows` int32[Q, n] in HBM at this chunk's first title (`q_first`).  A
+        model slot is an edge when its probability is above `probability_threshold` (float32)."""
+        if self._ranked is None or not self._ranked_n:
+            raise ValueError("enqueue_rank_matches comes first")
+        if tuple(keys.shape) != tuple(rows.shape) or len(keys.shape) != 2 or keys.shape[1] != self._ranked_n:
+            raise ValueError(f"keys {tuple(keys.shape)} and rows {tuple(rows.shape)} must both be "
+                             f"[titles, n = {self._ranked_n}]")
+        _lib.check(_lib.lib().ds_assign_edges_device(
+            *(a.ptr for a in self._ranked), self.q_first, self.n_queries, keys.shape[0], self._ranked_n, self.n_truth,
+            float(probability_threshold), _lib.pointer(keys), _lib.pointer(rows), _lib.pointer(stream)),
+            "ds_assign_edges_device")
+
     def enqueue_exhaustive(self, model, n, stream=None):
         """The best n rows of the WHOLE truth table per query by the model alone (ds_exhaustive_rank_device): tiles of
         pairs through the features and forest kernels, folded into n running keys per query, with no use of the top-k

@@ -43,6 +43,10 @@ ACCURACY_KEYS = SWEEP_COLUMNS[2:]
 DUPLICATE_COLUMNS = ("group_id", "group_size", "title_id", "row")
 LINK_COLUMNS = ("row", "match_row", "title_id", "match_title_id", "levenshtein_ratio", "probability", "stage")
 EXPLAIN_COLUMNS = ("test_index", "match_row", "title_id", "probability", "margin", "bias", "stage", "answer_row")
+ASSIGNMENT_COLUMNS = ("test_index", "match_row", "title_id", "stage", "probability", "levenshtein_ratio", "rank",
+                      "first_choice_row", "displaced")
+ASSIGNMENT_COUNTS = ("edges", "matched", "displaced", "displaced_unmatched", "proposals", "rounds")
+ASSIGN_RESERVE_BYTES = 64 << 20          # HBM left free for the kernels that follow, as the native stages leave
 REASON_CLOSE, REASON_MODEL = 1, 2        # bits of a slot's reason (ds_duplicate_links_device)
 SWEEP_MAX_LEVENSHTEIN, SWEEP_MAX_PROBABILITY = 101, 256      # thresholds per axis at most (ds_threshold_sweep_device)
 # what ranked_matches(keep_candidates=True) keeps of a call, per query: the top-n rows, their fuzzy ratios and model
@@ -292,6 +296,48 @@ def links_frame(chunks, truth_title_ids, n_truth):
     columns = {name: np.concatenate(held) if held else np.zeros(0, empty[name]) for name, held in parts.items()}
     columns["title_id"], columns["match_title_id"] = ids[columns["row"]], ids[columns["match_row"]]
     return pd.DataFrame(columns, columns=list(LINK_COLUMNS))
+
+
+def validate_assignment(n, top_n, probability_threshold):
+    """one_to_one_matches' checks of `n` and its threshold (no library needed) -> (int, float): n as validate_rank, the
+    threshold a finite number as validate_duplicates (it is compared as float32)."""
+    n = validate_rank(n, top_n)
+    return n, validate_duplicates(0, probability_threshold)[1]
+
+
+def assignment_bytes(n_titles, n, n_truth):
+    """The HBM the one-to-one stage holds across a call: key and row of every slot, the key every truth row holds, and
+    per title the slot it stands at and its three outputs."""
+    return 12 * int(n_titles) * int(n) + 8 * int(n_truth) + 16 * int(n_titles)
+
+
+def assignment_frame(test_index, match_row, match_slot, first_row, rows, probabilities, ratios, stages, truth_title_ids):
+    """one_to_one_matches' `assignment` from the solver's per-title outputs and the [Q, n] slots of the rank stage: one
+    line per title in the order of the call.  The scores are those of the matched slot (rank = slot + 1); a title with
+    no match has match_row -1, title_id -1, stage 0, probability NaN, ratio 0 and rank 0.  displaced: the title has a
+    first choice and did not get it."""
+    import pandas as pd
+    match_row, match_slot = np.asarray(match_row, dtype=np.int64), np.asarray(match_slot, dtype=np.int64)
+    first_row = np.asarray(first_row, dtype=np.int64)
+    ids = np.asarray(truth_title_ids, dtype=np.int64)
+    count = match_row.shape[0]
+    found = match_row >= 0
+    query, slot = np.nonzero(found)[0], match_slot[found]
+    title_id = np.full(count, TRAIN_NOT_FOUND_VALUE, dtype=np.int64)
+    title_id[found] = ids[match_row[found]]
+    stage = np.zeros(count, dtype=np.int8)
+    probability = np.full(count, np.nan, dtype=np.float32)
+    ratio = np.zeros(count, dtype=np.uint8)
+    if query.shape[0]:
+        if not np.array_equal(np.asarray(rows)[query, slot], match_row[found]):
+            raise ValueError("match_slot does not hold match_row")
+        stage[found] = np.asarray(stages, dtype=np.int8)[query, slot]
+        probability[found] = np.asarray(probabilities, dtype=np.float32)[query, slot]
+        ratio[found] = np.asarray(ratios, dtype=np.uint8)[query, slot]
+    return pd.DataFrame({"test_index": np.asarray(test_index, dtype=np.int64), "match_row": match_row,
+                         "title_id": title_id, "stage": stage, "probability": probability, "levenshtein_ratio": ratio,
+                         "rank": np.where(found, match_slot + 1, 0).astype(np.int64), "first_choice_row": first_row,
+                         "displaced": (first_row >= 0) & (match_row != first_row)}, columns=list(ASSIGNMENT_COLUMNS))
 
 
 def top_contributions(contributions, n=5):
@@ -588,6 +634,8 @@ class Prediction:
         self.links = None
         self.contributions = None
         self.explained_features = None
+        self.assignment = None
+        self.assignment_counts = None
         self.timings = {}
 
         self.truth_titles = self._transform(truth_titles)
@@ -674,6 +722,79 @@ class Prediction:
         self.timings = timings
         self.candidates = kept
         return ranked_frame(test_index, *slots, self.truth_title_ids)
+
+    def one_to_one_matches(self, titles, n=5, test_index=None, probability_threshold=None):
+        """One answer per title, each truth title given to one title at most: the frame of generate_test_predictions,
+        DataFrame [title_id, test_index] sorted by test_index, -1 where a title got nothing, and no title_id other than
+        -1 twice.  For linking one de-duplicated file against another.
+
+        Every title has the `n` ranked slots of ranked_matches(titles, n).  A slot is an edge when it is the exact or the
+        close match, or a model candidate with a probability above `probability_threshold` (None: this instance's own;
+        float32 compare).  A truth row keeps the best claim on it: exact over close over model, then the higher ratio or
+        probability, then the earlier title of `titles`.  A title that loses a row goes on to its next edge, where it may
+        displace somebody else in turn: deferred acceptance with the titles proposing, run on the device to its fixed
+        point (CandidatePipeline.enqueue_assign_edges per chunk, ds_assign_solve_device once).  The result is the
+        title-optimal stable matching; since a title's slots descend in score it is also what taking all edges in
+        descending order of score, each when its title and its row are still free, would give.  It does not depend on
+        chunk_queries or on the schedule; it does depend on the ORDER of `titles`, on equal scores.
+
+        Where it differs from generate_test_predictions even when no two titles want the same row: the reference
+        answers "none" when several candidates hold the maximum (the close stage, predict.py:158-161, and the model
+        stage, predict.py:244-249); here the ranked slots break such a tie by the earlier candidate, so a title whose best
+        model candidates tie above the threshold is matched.  A close tie has no head and its candidates stand as model
+        candidates, under the probability threshold.
+
+        After a call `assignment` holds, per title in the order of `titles`, [test_index, match_row, title_id, stage,
+        probability, levenshtein_ratio, rank, first_choice_row, displaced]: the scores of the matched slot (rank = slot
+        + 1, 0 for none; a matched exact or close head has probability 1.0), the row of the title's first edge (-1: it
+        has none) and whether it got another answer than that.  `assignment_counts` holds edges, matched, displaced,
+        displaced_unmatched (pure functions of the input) and proposals, rounds (diagnostics of the schedule).
+        `details`, `candidates`, `links` and `contributions` are left alone."""
+        n, threshold = validate_assignment(
+            n, self.top_n, self.probability_threshold if probability_threshold is None else probability_threshold)
+        titles = list(titles)
+        test_index = validate_queries(titles, test_index)
+        timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model", "rank",
+                                 "assign_edges", "assign", "copy_back"), 0.0)
+        count, n_truth = len(titles), len(self.truth_titles)
+        slots = (np.full((count, n), -1, dtype=np.int32), np.full((count, n), np.nan, dtype=np.float32),
+                 np.zeros((count, n), dtype=np.uint8), np.zeros((count, n), dtype=np.int8))
+        outputs = tuple(np.full(count, -1, dtype=np.int32) for _ in range(3))
+        counts = np.zeros(len(ASSIGNMENT_COUNTS), dtype=np.int64)
+        if count:
+            needed = assignment_bytes(count, n, n_truth)
+            free, total = ctypes.c_int64(0), ctypes.c_int64(0)
+            _lib.check(_lib.lib().ds_device_memory(self.device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
+            if needed + ASSIGN_RESERVE_BYTES > free.value:
+                raise _lib.DoppelError(f"one_to_one_matches: {count} titles of {n} slots against {n_truth} truth titles "
+                                       f"need {needed} bytes of HBM, {free.value} are free")
+            make = lambda shape, dtype: _lib.DeviceArray(shape, dtype, self.device)
+            keys, rows = make((count, n), np.uint64), make((count, n), np.int32)
+            held, standing = make((max(n_truth, 1),), np.uint64), make((count,), np.int32)
+            device_outputs = tuple(make((count,), np.int32) for _ in range(3))
+            device_counts = make((len(ASSIGNMENT_COUNTS),), np.int64)
+        for pipeline, events in self._chunks(titles, timings, rank_slots=n):
+            self._rank_chunk(pipeline, events, timings, n, slots, None)
+            # 8. the keys of this chunk's slots into the call-wide arrays (the ranked buffers still hold the chunk)
+            events["assign_edges"].start()
+            pipeline.enqueue_assign_edges(keys, rows, threshold)
+            events["assign_edges"].stop()
+            timings["assign_edges"] += events["assign_edges"].elapsed_ms()
+            last_events = events
+        if count:
+            last_events["assign"].start()
+            _lib.check(_lib.lib().ds_assign_solve_device(
+                rows.ptr, keys.ptr, count, n, n_truth, held.ptr, standing.ptr, *(a.ptr for a in device_outputs),
+                device_counts.ptr, _lib.pointer(None)), "ds_assign_solve_device")
+            last_events["assign"].stop()
+            copy_started = time.perf_counter()
+            outputs, counts = tuple(a.to_host() for a in device_outputs), device_counts.to_host()
+            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+            timings["assign"] = last_events["assign"].elapsed_ms()
+        self.timings = timings
+        self.assignment = assignment_frame(test_index, *outputs, *slots, self.truth_title_ids)
+        self.assignment_counts = dict(zip(ASSIGNMENT_COUNTS, (int(c) for c in counts)))
+        return finalize_output(test_index, outputs[0], self.truth_title_ids)
 
     def exhaustive_matches(self, titles, n=5, test_index=None):
         """The best `n` rows of the WHOLE truth set for every title by the model alone, next to where the candidate

@@ -7,7 +7,9 @@
 using only this package (reference: doppelspeller/predict.py:107-262).  Data and model are synthetic stand-ins: the
 example data set and the pickled xgboost model of the reference are not part of this repository.
 
-    python examples/end_to_end.py [n_truth] [n_queries] [top_n]
+    python examples/end_to_end.py [n_truth] [n_queries] [top_n] [--one-to-one]
+
+--one-to-one adds a step for linking two de-duplicated files: every truth title given to one query at most.
 """
 import os
 import sys
@@ -20,7 +22,7 @@ import doppel_speller_amd as ds  # noqa: E402
 from doppel_speller_amd import synth  # noqa: E402
 
 
-def main(n_truth=20000, n_queries=2000, top_n=10):
+def main(n_truth=20000, n_queries=2000, top_n=10, one_to_one=False):
     workload = synth.make_workload(n_truth, n_queries, seed=11)
     raw_truth = [t.upper().replace(" ", "  ") + "." for t in synth._to_strings(workload.t_flat, workload.t_off)]
     raw_queries = [t.title() for t in synth._to_strings(workload.q_flat, workload.q_off)]
@@ -84,8 +86,14 @@ def main(n_truth=20000, n_queries=2000, top_n=10):
     best = sweep.loc[sweep["custom_error"].idxmin()]
     print(f"smallest custom error of {len(sweep)} cells: {int(best['custom_error'])} at levenshtein_threshold "
           f"{int(best['levenshtein_threshold'])}, probability_threshold {best['probability_threshold']:.2f}")
+    if one_to_one:
+        # the same titles with every truth title given to one query at most: a query that loses its first choice goes on
+        # to its next candidate, which may displace somebody else in turn
+        linked = prediction.one_to_one_matches(raw_queries, n=min(5, top_n))
+        print(f"one-to-one: {(linked['title_id'] >= 0).sum()} of {len(linked)} queries matched, no title_id twice:",
+              prediction.assignment_counts)
     return rows, best_row, features, probabilities
 
 
 if __name__ == "__main__":
-    main(*[int(a) for a in sys.argv[1:4]])
+    main(*[int(a) for a in sys.argv[1:] if a != "--one-to-one"][:3], one_to_one="--one-to-one" in sys.argv[1:])

@@ -359,6 +359,60 @@ int ds_duplicate_links_device(const int32_t *d_rows, const uint8_t *d_ratios, co
 int ds_duplicate_finish_device(int32_t *d_parent, int64_t n_truth, int32_t *d_label, int32_t *d_size, void *stream);
 int ds_duplicates_option(const char *name, int64_t value);
 
+/* ---- one-to-one matches: each truth row given to one title at most ---------------------------------
+ * The project's own stage: the ranked slots of ds_rank_matches_device, for ALL titles of a call (n_total < 2^31, n slots
+ * each), turned into one matching by deferred acceptance with the titles proposing.
+ *
+ * Edges.  Slot s of title q holding t = row[q*n + s] is an edge to truth row t when
+ *   0 <= t < n_truth;
+ *   its stage is 1 (exact) or 2 (close); or its stage is 3, its probability > probability_threshold (float32 compare; a NaN
+ *   is not above) and the probability's sign bit is clear;
+ *   no earlier slot of q is an edge to t (ds_rank_matches_device never repeats a row; a caller of this ABI can).
+ * Every other slot is no edge.  The key of an edge, uint64, 0 = no edge:
+ *   class << 62 | payload << 31 | (2^31 - 1 - q)      q: the title's number in the whole call
+ *   class 3 / 2 / 1 for stage 1 / 2 / 3, payload 0 / the ratio (0..100) / the float32 bits of the probability (< 2^31).
+ * A truth row prefers the larger key: exact over close over model, the higher ratio or probability inside a class, the
+ * earlier title on equal scores.  Two edges into one row come from different titles, so the keys at a row are distinct.
+ * A title prefers its edges in slot order.  The result is the title-optimal stable matching: no edge (q, t) outside it has
+ * q preferring t to what it got (or q unmatched) and t's key for q above the key t holds (or t free).  It is unique, and it
+ * does not depend on the order of the proposals, hence not on the schedule, the chunking or the options below.  Where a
+ * title's edges are in descending (class, payload) order -- ds_rank_matches_device's are -- it equals the greedy matching:
+ * all edges by (class, payload) descending, q ascending, slot ascending, an edge taken when its title and row are free.
+ *
+ * ds_assign_edges_device: one chunk's slots, d_row / d_probability / d_ratio / d_stage [n_queries][n] as the rank stage
+ * leaves them, titles [q_first, q_first + n_queries) of the call's n_total.  Writes the key AND the row of every slot of
+ * the chunk into the call-wide d_edge_key / d_edge_row [n_total][n] at q_first * n (the rows are copied as they are, so
+ * the chunk's buffers may be reused at once and the solver reads two arrays it owns).  Asynchronous on `stream`.
+ * DS_E_ARG, with nothing launched: a null pointer, n < 1, a negative count, q_first + n_queries > n_total,
+ * n_total >= 2^31, n_truth outside [0, 2^31), a threshold that is not finite.  n_queries == 0 launches nothing.
+ *
+ * ds_assign_solve_device: zeroes d_held (uint64[n_truth], the key each row holds), d_next (int32[n_queries], the slot a
+ * title stands at) and d_counts, runs rounds to the fixed point, then writes per title
+ *   d_match_row   the row it holds, -1: none        d_match_slot  the slot of that edge, -1
+ *   d_first_row   the row of its first edge, -1 when it has no edge
+ * and d_counts, int64[6]: [0] edges, [1] matched titles, [2] displaced titles (first_row >= 0 and match_row != first_row),
+ * [3] the displaced titles left unmatched, [4] proposals (the atomics that raised a held entry), [5] rounds in which a
+ * title was active.  [0..4) and the per-title outputs are a pure function of the edges; [4] and [5] depend on the schedule
+ * and are diagnostics.  A slot whose key is not 0 but whose row lies outside [0, n_truth) is no edge here either.
+ * A round is one launch, one lane per title: a title whose held[row] == key at its slot is idle, so is an exhausted one;
+ * any other walks forward from its slot, skips non-edges and rows that hold more than its key, offers its key with a 64-bit
+ * atomicMax elsewhere and stops where the value returned is below its key.  Rounds repeat until one in which no title was
+ * active; the activity counters come back every "rounds_per_sync" rounds.  SYNCHRONISES `stream`: more than once on the way
+ * (one read-back per batch of rounds) and at the end, so the outputs are complete when the call returns.  It allocates
+ * 4 * rounds_per_sync bytes for the counters and frees them before it returns.
+ * DS_E_ARG, with nothing launched: a null pointer, n < 1, n_queries < 0 or >= 2^31, n_truth outside [0, 2^31).
+ * n_queries == 0 launches no kernel and leaves d_counts at zero.
+ *
+ * ds_assign_option is for tests: "rounds_per_sync" in [1, 1024] (default 8), "max_blocks" in [0, 2^20]: the cap of every
+ * grid of this stage, which strides beyond it (0 = the default, 2048).  The result depends on neither. */
+int ds_assign_edges_device(const int32_t *d_row, const float *d_probability, const uint8_t *d_ratio, const int8_t *d_stage,
+                           int64_t q_first, int64_t n_queries, int64_t n_total, int32_t n, int64_t n_truth,
+                           float probability_threshold, uint64_t *d_edge_key, int32_t *d_edge_row, void *stream);
+int ds_assign_solve_device(const int32_t *d_edge_row, const uint64_t *d_edge_key, int64_t n_queries, int32_t n,
+                           int64_t n_truth, uint64_t *d_held, int32_t *d_next, int32_t *d_match_row,
+                           int32_t *d_match_slot, int32_t *d_first_row, int64_t *d_counts, void *stream);
+int ds_assign_option(const char *name, int64_t value);
+
 /* ---- exact matches: Prediction._find_exact_matches (predict.py:74-113) ---------------------------------------------
  * exact_row[q] = the truth row whose encoded title (length and bytes of the ds_titles rows) equals query row q's, the
  * LAST such row when several truth rows hold the title (the reference's {title: title_id} dict is filled in truth
