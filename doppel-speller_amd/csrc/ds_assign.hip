@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 
@@ -177,11 +178,7 @@ __global__ __launch_bounds__(kAssignThreads) void ds_assign_finish_kernel(
         n_displaced += __popcll(__ballot(displaced));
         n_left += __popcll(__ballot(displaced && !matched));
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t low = __shfl_xor(static_cast<uint32_t>(n_edges), d, 64);
-        const uint32_t high = __shfl_xor(static_cast<uint32_t>(n_edges >> 32), d, 64);
-        n_edges += (static_cast<unsigned long long>(high) << 32) | low;
-    }
+    n_edges = wave_sum(n_edges);
     if ((threadIdx.x & 63) == 0) {
         if (n_edges) atomicAdd(counts + 0, n_edges);
         if (n_matched) atomicAdd(counts + 1, static_cast<unsigned long long>(n_matched));

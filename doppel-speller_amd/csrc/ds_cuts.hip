@@ -67,11 +67,7 @@ __global__ __launch_bounds__(kKeyThreads) void ds_cuts_key_kernel(const uint32_t
         for (int f = wave; f < g; f += kKeyThreads / 64) {
             const uint32_t key = valid ? cut_key(s_tile[lane * stride + c0 + f]) : 0xffffffffu;
             if (valid) keys[static_cast<int64_t>(f) * n + first + lane] = key;
-            uint32_t any = valid ? key : 0u, all = key;
-            for (int offset = 32; offset > 0; offset >>= 1) {
-                any |= __shfl_xor(any, offset);
-                all &= __shfl_xor(all, offset);
-            }
+            const uint32_t any = wave_or(valid ? key : 0u), all = wave_and(key);
             const uint32_t present = __popcll(__ballot(key != 0xffffffffu));
             if (lane == 0) {
                 s_m[f] += present;
@@ -115,7 +111,7 @@ __global__ __launch_bounds__(kScanThreads) void ds_cuts_pick_kernel(const uint32
         const uint32_t key = valid ? sorted[i] : 0u;
         const bool head = valid && (i == 0 || key != sorted[i - 1]);
         uint32_t total;
-        const uint32_t number = heads + block_exclusive(head ? 1u : 0u, s_waves, total);
+        const uint32_t number = heads + block_exclusive<kScanThreads>(head ? 1u : 0u, s_waves, total);
         if (head && number >= 1u && number <= static_cast<uint32_t>(kCutsMax)) out[number - 1] = cut_value_bits(key);
         heads += total;
     }
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(kScanThreads) void ds_cuts_pick_kernel(const uint32
         take = key != sorted[0] && key != sorted[((j - 1) * m) / (max_bin - 1)];
     }
     uint32_t total;
-    const uint32_t at = block_exclusive(take ? 1u : 0u, s_waves, total);
+    const uint32_t at = block_exclusive<kScanThreads>(take ? 1u : 0u, s_waves, total);
     if (take) out[at] = cut_value_bits(key);
     if (threadIdx.x == 0) cut_counts[col] = static_cast<int32_t>(total);
 }

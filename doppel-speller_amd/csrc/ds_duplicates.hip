@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 
@@ -75,16 +76,6 @@ __device__ __forceinline__ void duplicate_union(int32_t *parent, int32_t a, int3
         a = seen;
         b = lo;
     }
-}
-
-__device__ __forceinline__ unsigned long long duplicate_wave_sum(unsigned long long value)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t low = __shfl_xor(static_cast<uint32_t>(value), d, 64);
-        const uint32_t high = __shfl_xor(static_cast<uint32_t>(value >> 32), d, 64);
-        value += (static_cast<unsigned long long>(high) << 32) | low;
-    }
-    return value;
 }
 
 __global__ __launch_bounds__(kDuplicateThreads) void ds_duplicate_begin_kernel(int32_t *__restrict__ parent, int32_t n_truth)
@@ -133,9 +124,9 @@ __global__ __launch_bounds__(kDuplicateThreads) void ds_duplicate_links_kernel(L
             }
         }
     }
-    n_exact = duplicate_wave_sum(n_exact);
-    n_close = duplicate_wave_sum(n_close);
-    n_model = duplicate_wave_sum(n_model);
+    n_exact = wave_sum(n_exact);
+    n_close = wave_sum(n_close);
+    n_model = wave_sum(n_model);
     if ((threadIdx.x & 63) == 0) {
         if (n_exact) atomicAdd(a.counts + 0, n_exact);
         if (n_close) atomicAdd(a.counts + 1, n_close);

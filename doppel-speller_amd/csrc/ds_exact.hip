@@ -17,25 +17,15 @@
 
 namespace ds {
 
-__device__ inline uint64_t exact_mix(uint64_t x)  // splitmix64 finaliser (mix64 of ds_common.h, device side)
-{
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    return x;
-}
-
-// 64-bit hash of (length, bytes): 8 bytes at a time through the mixer
+// 64-bit hash of (length, bytes): 8 bytes at a time through mix64 (ds_common.h)
 __device__ inline uint64_t title_hash(const uint8_t *title, int length)
 {
-    uint64_t h = exact_mix(0x9e3779b97f4a7c15ull ^ static_cast<uint64_t>(length));
+    uint64_t h = mix64(0x9e3779b97f4a7c15ull ^ static_cast<uint64_t>(length));
     for (int i = 0; i < length; i += 8) {
         uint64_t word = 0;
         const int end = i + 8 < length ? i + 8 : length;
         for (int j = i; j < end; ++j) word |= static_cast<uint64_t>(title[j]) << (8 * (j - i));
-        h = exact_mix(h ^ word);
+        h = mix64(h ^ word);
     }
     return h;
 }

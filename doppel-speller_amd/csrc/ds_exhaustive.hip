@@ -22,6 +22,7 @@
 #include <atomic>
 
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 
@@ -40,17 +41,6 @@ static std::atomic<int64_t> g_tile_pairs{0};                    // 0: the defaul
 __device__ __forceinline__ uint64_t exhaustive_key(float probability, int64_t row)
 {
     return (static_cast<uint64_t>(__float_as_uint(probability)) << 32) | (0xffffffffu - static_cast<uint32_t>(row));
-}
-
-__device__ __forceinline__ uint64_t fold_wave_max(uint64_t value)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t low = __shfl_xor(static_cast<uint32_t>(value), d, 64);
-        const uint32_t high = __shfl_xor(static_cast<uint32_t>(value >> 32), d, 64);
-        const uint64_t other = (static_cast<uint64_t>(high) << 32) | low;
-        value = other > value ? other : value;
-    }
-    return value;
 }
 
 // pair i of the tile: query q_first + i / rows, truth row row_first + i % rows  (n_pairs = queries of the tile x rows < 2^31)
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(kFoldThreads) void ds_exhaustive_select_kernel(Fold
                 const uint64_t key = keys[r];
                 best = (key < below && key > best) ? key : best;
             }
-            best = fold_wave_max(best);
+            best = wave_max(best);
             // one barrier per round: a wave that reads round r's words has passed round r's barrier, and nobody writes them
             // again before round r + 2, behind round r + 1's barrier
             if (lane == 0) wave_best[filled & 1][wave] = best;

@@ -3,7 +3,7 @@
 // Also ds_index_read (any array of any index back to the host) and ds_index_build_option.
 //
 // Every write position is a function of the input alone: the orders come from stable LSD radix sorts (8-bit digits,
-// ranks inside a wave from __ballot, across the waves through LDS, as ds_radix.h) and exclusive scans; no position is
+// ranks inside a wave from __ballot, across the waves through LDS: ds_wave.h) and exclusive scans; no position is
 // handed out by an atomic.  The only atomics are an atomicMin of the lowest bad column and an atomicOr of a flag.
 //
 // Stages (M = nnz postings, N rows, V columns, T tiles, stride = T + 1):
@@ -31,6 +31,7 @@
 #include <memory>
 
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 namespace {
@@ -74,28 +75,6 @@ __device__ inline unsigned long long scan_load(const uint32_t *in, const uint64_
     return keys ? (~keys[i] & 1ull) : in[i];
 }
 
-__device__ inline unsigned long long build_block_exclusive(unsigned long long value, unsigned long long *s_waves,
-                                                           unsigned long long &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inclusive = value;
-    for (int offset = 1; offset < 64; offset <<= 1) {
-        const unsigned long long other = __shfl_up(inclusive, offset);
-        if (lane >= offset) inclusive += other;
-    }
-    __syncthreads();   // the previous call's wave sums have been read
-    if (lane == 63) s_waves[wave] = inclusive;
-    __syncthreads();
-    unsigned long long before = 0ull;
-    total = 0ull;
-    for (int w = 0; w < kBuildThreads / 64; ++w) {
-        const unsigned long long sum = s_waves[w];
-        before += w < wave ? sum : 0ull;
-        total += sum;
-    }
-    return before + inclusive - value;
-}
-
 __global__ __launch_bounds__(kBuildThreads) void ds_build_scan_reduce_kernel(const uint32_t *in, const uint64_t *keys,
                                                                               int64_t n_in, unsigned long long *spine)
 {
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(kBuildThreads) void ds_build_scan_reduce_kernel(con
     const int64_t begin = static_cast<int64_t>(blockIdx.x) * kBuildTile;
     unsigned long long mine = 0ull, total;
     for (int j = 0; j < kBuildTile / kBuildThreads; ++j) mine += scan_load(in, keys, begin + j * kBuildThreads + threadIdx.x, n_in);
-    (void)build_block_exclusive(mine, s_waves, total);
+    (void)block_exclusive<kBuildThreads>(mine, s_waves, total);
     if (threadIdx.x == 0) spine[blockIdx.x] = total;
 }
 
@@ -116,7 +95,7 @@ __global__ __launch_bounds__(kBuildThreads) void ds_build_scan_spine_kernel(unsi
         const int64_t i = base + threadIdx.x;
         const unsigned long long value = i < blocks ? spine[i] : 0ull;
         unsigned long long total;
-        const unsigned long long before = build_block_exclusive(value, s_waves, total);
+        const unsigned long long before = block_exclusive<kBuildThreads>(value, s_waves, total);
         if (i < blocks) spine[i] = running + before;
         running += total;
     }
@@ -134,24 +113,10 @@ __global__ __launch_bounds__(kBuildThreads) void ds_build_scan_apply_kernel(cons
         const int64_t i = begin + j * kBuildThreads + threadIdx.x;
         const unsigned long long value = scan_load(in, keys, i, n_in);
         unsigned long long total;
-        const unsigned long long before = build_block_exclusive(value, s_waves, total);
+        const unsigned long long before = block_exclusive<kBuildThreads>(value, s_waves, total);
         if (i < n_out) out[i] = static_cast<uint32_t>(running + before);
         running += total;
     }
-}
-
-// The lanes of the wave that are valid and hold the same 8-bit digit as this lane (as digit_peers of ds_radix.h, whose
-// header also instantiates the 32-bit sort kernels of its two users: not included here).
-__device__ inline unsigned long long build_digit_peers(uint32_t digit, bool valid)
-{
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (digit >> b) & 1u;
-        const unsigned long long set = __ballot(valid && bit);
-        peers &= bit ? set : ~set;
-    }
-    return peers;
 }
 
 // ---- stable LSD radix sort of 64-bit items, keys only -----------------------------------------------------------------
@@ -168,18 +133,8 @@ __global__ __launch_bounds__(kBuildThreads) void ds_build_sort_count_kernel(cons
                                                                              uint32_t *table, int64_t tiles)
 {
     __shared__ uint32_t s_hist[256];
-    const int lane = threadIdx.x & 63;
-    s_hist[threadIdx.x] = 0u;
-    __syncthreads();
     const int64_t begin = static_cast<int64_t>(blockIdx.x) * kBuildTile, end = min(n, begin + kBuildTile);
-    for (int64_t base = begin; base < end; base += kBuildThreads) {
-        const int64_t i = base + threadIdx.x;
-        const bool valid = i < end;
-        const uint32_t digit = valid ? build_digit(src[i], field, shift) : 0u;
-        const unsigned long long peers = build_digit_peers(digit, valid);
-        if (valid && lane == __ffsll(static_cast<long long>(peers)) - 1) atomicAdd(&s_hist[digit], __popcll(peers));
-    }
-    __syncthreads();
+    radix_count_tile<kBuildThreads>(src, begin, end, [=](uint64_t item) { return build_digit(item, field, shift); }, s_hist);
     table[static_cast<int64_t>(threadIdx.x) * tiles + blockIdx.x] = s_hist[threadIdx.x];
 }
 
@@ -189,34 +144,10 @@ __global__ __launch_bounds__(kBuildThreads) void ds_build_sort_scatter_kernel(co
 {
     __shared__ uint32_t s_next[256];                          // the next position of each digit for this workgroup
     __shared__ uint32_t s_wave_count[kBuildThreads / 64][256];  // items of each digit in each wave of the current 256
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     s_next[threadIdx.x] = table[static_cast<int64_t>(threadIdx.x) * tiles + blockIdx.x];
-    for (int w = 0; w < kBuildThreads / 64; ++w) s_wave_count[w][threadIdx.x] = 0u;
-    __syncthreads();
     const int64_t begin = static_cast<int64_t>(blockIdx.x) * kBuildTile, end = min(n, begin + kBuildTile);
-    for (int64_t base = begin; base < end; base += kBuildThreads) {
-        const int64_t i = base + threadIdx.x;
-        const bool valid = i < end;
-        const uint64_t item = valid ? src[i] : 0ull;
-        const uint32_t digit = valid ? build_digit(item, field, shift) : 0u;
-        const unsigned long long peers = build_digit_peers(digit, valid);
-        const uint32_t rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0u) s_wave_count[wave][digit] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int64_t position = static_cast<int64_t>(s_next[digit]) + rank;
-            for (int w = 0; w < kBuildThreads / 64; ++w) position += w < wave ? s_wave_count[w][digit] : 0u;
-            if (position < n) dst[position] = item;   // always true for counts of the same items
-        }
-        __syncthreads();
-        uint32_t sum = 0u;
-        for (int w = 0; w < kBuildThreads / 64; ++w) {
-            sum += s_wave_count[w][threadIdx.x];
-            s_wave_count[w][threadIdx.x] = 0u;
-        }
-        s_next[threadIdx.x] += sum;
-        __syncthreads();
-    }
+    radix_scatter_tile<kBuildThreads>(src, dst, begin, end, n, [=](uint64_t item) { return build_digit(item, field, shift); },
+                                      s_next, s_wave_count);
 }
 
 // ---- row order -------------------------------------------------------------------------------------------------------

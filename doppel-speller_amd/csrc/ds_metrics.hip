@@ -27,12 +27,6 @@ namespace ds {
 constexpr int kMetricThreads = 256;
 constexpr uint32_t kPaddingKey = 0xffffffffu;
 
-__device__ inline unsigned long long wave_sum(unsigned long long value)
-{
-    for (int offset = 32; offset > 0; offset >>= 1) value += __shfl_xor(value, offset);
-    return value;
-}
-
 __device__ inline uint32_t margin_key(const MetricColumn &column, int32_t row)
 {
     return cut_key(__float_as_uint(column.base_margin + column.scores[row]));
@@ -76,11 +70,9 @@ __global__ __launch_bounds__(kMetricThreads) void ds_metric_key_kernel(const Met
         }
         mine[i] = key;
     }
-    for (int offset = 32; offset > 0; offset >>= 1) {
-        any |= __shfl_xor(any, offset);
-        all &= __shfl_xor(all, offset);
-        nan += __shfl_xor(nan, offset);
-    }
+    any = wave_or(any);
+    all = wave_and(all);
+    nan = wave_sum(nan);
     if (lane == 0) {
         atomicOr(&s_or, any);
         atomicAnd(&s_and, all);

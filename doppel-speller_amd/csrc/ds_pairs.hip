@@ -13,6 +13,7 @@
 // index pairs ds_construct_features_indexed_device consumes -- the top-k rows never leave HBM.
 // ds_select_matches_device: one thread per remaining query over its k predictions.
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 
@@ -21,42 +22,27 @@ constexpr int kPairBlock = 1024;  // queries per workgroup of the compaction
 __global__ __launch_bounds__(kPairBlock) void ds_pairs_count_kernel(const int32_t *best_row, int64_t n_queries,
                                                                     int64_t *block_counts)
 {
-    __shared__ int wave_counts[kPairBlock / 64];
+    __shared__ int s_waves[kPairBlock / 64];
     const int64_t q = static_cast<int64_t>(blockIdx.x) * kPairBlock + threadIdx.x;
     const bool remaining = q < n_queries && best_row[q] < 0;
-    const int count = __popcll(__ballot(remaining));
-    if ((threadIdx.x & 63) == 0) wave_counts[threadIdx.x >> 6] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int w = 0; w < kPairBlock / 64; ++w) total += wave_counts[w];
-        block_counts[blockIdx.x] = total;
-    }
+    int total;
+    (void)block_exclusive<kPairBlock>(remaining ? 1 : 0, s_waves, total);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
 }
 
 // exclusive scan of the block counts in place (one workgroup; the number of blocks is Q / 1024), totals in counts[0..1]
 __global__ __launch_bounds__(1024) void ds_pairs_scan_kernel(int64_t *block_counts, int64_t n_blocks, int32_t k,
                                                              int64_t *counts)
 {
-    __shared__ int64_t partial[1024];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
+    __shared__ int64_t s_waves[1024 / 64];
+    int64_t carry = 0;
     for (int64_t base = 0; base < n_blocks; base += 1024) {
         const int64_t i = base + threadIdx.x;
         const int64_t mine = i < n_blocks ? block_counts[i] : 0;
-        partial[threadIdx.x] = mine;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {  // Hillis-Steele inclusive scan
-            const int64_t add = static_cast<int>(threadIdx.x) >= d ? partial[threadIdx.x - d] : 0;
-            __syncthreads();
-            partial[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < n_blocks) block_counts[i] = carry + partial[threadIdx.x] - mine;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += partial[1023];
-        __syncthreads();
+        int64_t total;
+        const int64_t before = block_exclusive<1024>(mine, s_waves, total);
+        if (i < n_blocks) block_counts[i] = carry + before;
+        carry += total;
     }
     if (threadIdx.x == 0) {
         counts[0] = carry;
@@ -69,20 +55,13 @@ __global__ __launch_bounds__(kPairBlock) void ds_pairs_write_kernel(const int32_
                                                                     const int64_t *block_offsets, int32_t *pair_q,
                                                                     int32_t *pair_t)
 {
-    __shared__ int wave_counts[kPairBlock / 64];
+    __shared__ int s_waves[kPairBlock / 64];
     __shared__ int32_t kept_query[kPairBlock];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t q = static_cast<int64_t>(blockIdx.x) * kPairBlock + threadIdx.x;
     const bool remaining = q < n_queries && best_row[q] < 0;
-    const unsigned long long votes = __ballot(remaining);
-    if (lane == 0) wave_counts[wave] = __popcll(votes);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int w = 0; w < kPairBlock / 64; ++w) {
-        before += w < wave ? wave_counts[w] : 0;
-        total += wave_counts[w];
-    }
-    if (remaining) kept_query[before + __popcll(votes & ((1ull << lane) - 1ull))] = static_cast<int32_t>(q);
+    int total;
+    const int before = block_exclusive<kPairBlock>(remaining ? 1 : 0, s_waves, total);
+    if (remaining) kept_query[before] = static_cast<int32_t>(q);
     __syncthreads();
     // the block's remaining queries, k candidates each: consecutive threads write consecutive pairs
     const int64_t first_pair = block_offsets[blockIdx.x] * k;

@@ -14,6 +14,7 @@
 // vocabulary) gives the columns.  One lane adds the float64 chain in ascending n-gram order.  The counting instance
 // writes the row lengths and q_maxint, one workgroup scans the lengths into rowptr, the fill instance writes the columns.
 #include "ds_common.h"
+#include "ds_wave.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,7 +26,7 @@ constexpr int kRowBytes = 256;                     // LDS row of a title being t
 constexpr int kAlphabet = 37;                      // ' ', 0-9, a-z
 constexpr int kDenseKeys = kAlphabet * kAlphabet * kAlphabet;
 constexpr int kMaxGrams = DS_MAX_CHARS - 2;        // tri-grams of a 255-character title
-constexpr int kScanThreads = 1024;
+constexpr int kRowptrScanThreads = 1024;
 constexpr uint32_t kPadKey = 0xffffffffu;
 
 struct PrepareReport {
@@ -62,12 +63,6 @@ __host__ inline int rank_of_byte(uint32_t c)
     if (c >= '0' && c <= '9') return static_cast<int>(c - '0') + 1;
     if (c >= 'a' && c <= 'z') return static_cast<int>(c - 'a') + 11;
     return -1;
-}
-
-__device__ inline uint32_t wave_or(uint32_t value)
-{
-    for (int offset = 32; offset > 0; offset >>= 1) value |= __shfl_xor(value, offset);
-    return value;
 }
 
 __global__ __launch_bounds__(kQueryBlock) void ds_prepare_titles_kernel(const uint8_t *__restrict__ chars,
@@ -236,29 +231,18 @@ __global__ __launch_bounds__(kQueryBlock) void ds_query_rows_kernel(const uint8_
 }
 
 // rowptr[1 .. n] holds the row lengths: inclusive scan in place, rowptr[0] = 0.  One workgroup.
-__global__ __launch_bounds__(kScanThreads) void ds_query_rowptr_scan_kernel(int64_t *rowptr, int64_t n)
+__global__ __launch_bounds__(kRowptrScanThreads) void ds_query_rowptr_scan_kernel(int64_t *rowptr, int64_t n)
 {
-    __shared__ int64_t partial[kScanThreads / 64];
-    const int lane = static_cast<int>(threadIdx.x) & 63, wave = static_cast<int>(threadIdx.x) >> 6;
+    __shared__ int64_t s_waves[kRowptrScanThreads / 64];
     if (threadIdx.x == 0) rowptr[0] = 0;
     int64_t carry = 0;
-    for (int64_t base = 0; base < n; base += kScanThreads) {
+    for (int64_t base = 0; base < n; base += kRowptrScanThreads) {
         const int64_t i = base + threadIdx.x;
-        long long value = i < n ? rowptr[1 + i] : 0;
-        for (int offset = 1; offset < 64; offset <<= 1) {
-            const long long up = __shfl_up(value, offset);
-            if (lane >= offset) value += up;
-        }
-        if (lane == 63) partial[wave] = value;
-        __syncthreads();
-        int64_t before = carry, total = carry;
-        for (int w = 0; w < kScanThreads / 64; ++w) {
-            if (w < wave) before += partial[w];
-            total += partial[w];
-        }
-        if (i < n) rowptr[1 + i] = before + value;
-        carry = total;
-        __syncthreads();
+        const int64_t value = i < n ? rowptr[1 + i] : 0;
+        int64_t total;
+        const int64_t before = block_exclusive<kRowptrScanThreads>(value, s_waves, total);
+        if (i < n) rowptr[1 + i] = carry + before + value;   // inclusive = exclusive + the lane's own value
+        carry += total;
     }
 }
 
@@ -417,7 +401,7 @@ int ds_query_rows_device(const ds_query_space *space, const ds_titles *titles, i
                        first, space->dense.ptr, space->idf32.ptr, space->idf64.ptr, space->max_idf,
                        static_cast<int>(space->unknown_counts), d_rowptr, d_cols, d_maxint);
     DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_query_rowptr_scan_kernel, dim3(1), dim3(ds::kScanThreads), 0, s, d_rowptr, n);
+    hipLaunchKernelGGL(ds::ds_query_rowptr_scan_kernel, dim3(1), dim3(ds::kRowptrScanThreads), 0, s, d_rowptr, n);
     DS_HIP(hipGetLastError());
     hipLaunchKernelGGL(ds::ds_query_rows_kernel<true>, grid, block, 0, s, titles->enc.ptr, titles->len.ptr, titles->stride,
                        first, space->dense.ptr, space->idf32.ptr, space->idf64.ptr, space->max_idf,

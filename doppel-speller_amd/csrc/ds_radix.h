@@ -14,12 +14,14 @@
 // A pass whose digit is the same in every key of a column ((OR ^ AND) of the column's keys has a zero byte there) is
 // skipped for that column by all three kernels; the column's keys then stay in the buffer they are in.  After the four
 // passes column c lies in keys_b when passes_done(col_or[c] ^ col_and[c], 4) is odd, else in keys_a.
-// All sums are integer sums and every position is a function of the keys alone.
+// All sums are integer sums and every position is a function of the keys alone.  The tile bodies of the count and the
+// scatter, and the workgroup scan, are those of ds_wave.h; the kernels here choose buffers, tile and digit.
 #pragma once
 
 #include <algorithm>
 
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 
@@ -50,19 +52,6 @@ __host__ __device__ inline int passes_done(uint32_t differing, int pass)
     return done;
 }
 
-// The lanes of the wave that are valid and hold the same 8-bit digit as this lane (meaningless for an invalid lane).
-__device__ inline unsigned long long digit_peers(uint32_t digit, bool valid)
-{
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (digit >> b) & 1u;
-        const unsigned long long set = __ballot(valid && bit);
-        peers &= bit ? set : ~set;
-    }
-    return peers;
-}
-
 static __global__ __launch_bounds__(kSortThreads) void ds_cuts_count_kernel(const uint32_t *keys_a, const uint32_t *keys_b,
                                                                              int64_t n, int32_t pass,
                                                                              const uint32_t *col_or,
@@ -70,44 +59,13 @@ static __global__ __launch_bounds__(kSortThreads) void ds_cuts_count_kernel(cons
                                                                              int64_t tiles)
 {
     __shared__ uint32_t s_hist[256];
-    const int col = blockIdx.y, lane = threadIdx.x & 63;
+    const int col = blockIdx.y;
     const uint32_t differing = col_or[col] ^ col_and[col];
     if (pass_skipped(differing, pass)) return;
     const uint32_t *src = ((passes_done(differing, pass) & 1) ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
-    s_hist[threadIdx.x] = 0u;
-    __syncthreads();
     const int64_t begin = static_cast<int64_t>(blockIdx.x) * kSortTile, end = min(n, begin + kSortTile);
-    for (int64_t base = begin; base < end; base += kSortThreads) {
-        const int64_t i = base + threadIdx.x;
-        const bool valid = i < end;
-        const uint32_t digit = valid ? (src[i] >> (8 * pass)) & 0xffu : 0u;
-        const unsigned long long peers = digit_peers(digit, valid);
-        if (valid && lane == __ffsll(static_cast<long long>(peers)) - 1) atomicAdd(&s_hist[digit], __popcll(peers));
-    }
-    __syncthreads();
+    radix_count_tile<kSortThreads>(src, begin, end, [pass](uint32_t key) { return (key >> (8 * pass)) & 0xffu; }, s_hist);
     table[(static_cast<int64_t>(col) * 256 + threadIdx.x) * tiles + blockIdx.x] = s_hist[threadIdx.x];
-}
-
-// Exclusive prefix of `value` over the kScanThreads threads of a workgroup, and the total.
-__device__ inline uint32_t block_exclusive(uint32_t value, uint32_t *s_waves, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inclusive = value;
-    for (int offset = 1; offset < 64; offset <<= 1) {
-        const uint32_t other = __shfl_up(inclusive, offset);
-        if (lane >= offset) inclusive += other;
-    }
-    __syncthreads();   // the previous call's wave sums have been read
-    if (lane == 63) s_waves[wave] = inclusive;
-    __syncthreads();
-    uint32_t before = 0u;
-    total = 0u;
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const uint32_t sum = s_waves[w];
-        before += w < wave ? sum : 0u;
-        total += sum;
-    }
-    return before + inclusive - value;
 }
 
 // table[column][digit][tile] -> the first position of (digit, tile) in the column's next buffer
@@ -125,7 +83,7 @@ static __global__ __launch_bounds__(kScanThreads) void ds_cuts_scan_kernel(uint3
         const int64_t i = base + threadIdx.x;
         const uint32_t value = i < count ? mine[i] : 0u;
         uint32_t total;
-        const uint32_t before = block_exclusive(value, s_waves, total);
+        const uint32_t before = block_exclusive<kScanThreads>(value, s_waves, total);
         if (i < count) mine[i] = running + before;
         running += total;
     }
@@ -139,39 +97,16 @@ static __global__ __launch_bounds__(kSortThreads) void ds_cuts_scatter_kernel(ui
 {
     __shared__ uint32_t s_next[256];                    // the next position of each digit for this workgroup
     __shared__ uint32_t s_wave_count[kSortWaves][256];  // keys of each digit in each wave of the current 256 keys
-    const int col = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = blockIdx.y;
     const uint32_t differing = col_or[col] ^ col_and[col];
     if (pass_skipped(differing, pass)) return;
     const bool from_b = passes_done(differing, pass) & 1;
     const uint32_t *src = (from_b ? keys_b : keys_a) + static_cast<int64_t>(col) * n;
     uint32_t *dst = (from_b ? keys_a : keys_b) + static_cast<int64_t>(col) * n;
     s_next[threadIdx.x] = table[(static_cast<int64_t>(col) * 256 + threadIdx.x) * tiles + blockIdx.x];
-    for (int w = 0; w < kSortWaves; ++w) s_wave_count[w][threadIdx.x] = 0u;
-    __syncthreads();
     const int64_t begin = static_cast<int64_t>(blockIdx.x) * kSortTile, end = min(n, begin + kSortTile);
-    for (int64_t base = begin; base < end; base += kSortThreads) {
-        const int64_t i = base + threadIdx.x;
-        const bool valid = i < end;
-        const uint32_t key = valid ? src[i] : 0u;
-        const uint32_t digit = (key >> (8 * pass)) & 0xffu;
-        const unsigned long long peers = digit_peers(digit, valid);
-        const uint32_t rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0u) s_wave_count[wave][digit] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            uint32_t position = s_next[digit] + rank;
-            for (int w = 0; w < kSortWaves; ++w) position += w < wave ? s_wave_count[w][digit] : 0u;
-            if (position < n) dst[position] = key;   // always true for counts of the same keys
-        }
-        __syncthreads();
-        uint32_t sum = 0u;
-        for (int w = 0; w < kSortWaves; ++w) {
-            sum += s_wave_count[w][threadIdx.x];
-            s_wave_count[w][threadIdx.x] = 0u;
-        }
-        s_next[threadIdx.x] += sum;
-        __syncthreads();
-    }
+    radix_scatter_tile<kSortThreads>(src, dst, begin, end, n, [pass](uint32_t key) { return (key >> (8 * pass)) & 0xffu; },
+                                     s_next, s_wave_count);
 }
 
 inline int64_t radix_tiles(int64_t n) { return (n + kSortTile - 1) / kSortTile; }

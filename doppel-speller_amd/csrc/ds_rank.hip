@@ -22,6 +22,7 @@
 #include <atomic>
 
 #include "ds_common.h"
+#include "ds_wave.h"
 
 namespace ds {
 
@@ -51,17 +52,6 @@ __device__ __forceinline__ uint64_t rank_key(int32_t row, float probability, int
 {
     const bool valid = row >= 0 && row < n_truth && row != head;
     return valid ? (static_cast<uint64_t>(__float_as_uint(probability)) << 32) | static_cast<uint32_t>(~j) : 0ull;
-}
-
-__device__ __forceinline__ uint64_t wave_max(uint64_t value)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t low = __shfl_xor(static_cast<uint32_t>(value), d, 64);
-        const uint32_t high = __shfl_xor(static_cast<uint32_t>(value >> 32), d, 64);
-        const uint64_t other = (static_cast<uint64_t>(high) << 32) | low;
-        value = other > value ? other : value;
-    }
-    return value;
 }
 
 // slot 0 of a query with a head (one lane); first_j: the first candidate that equals the head, k when none does
