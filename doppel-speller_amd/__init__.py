@@ -39,6 +39,10 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
     ForestTrainer.fit(..., eval_metrics=("auc", "logloss")), cross_validate(..., metrics=("auc",), select_by="auc")   ->
         the reference's per-round train-auc / evaluation-auc log and the objective's own loss, computed on the device from
         the margins; roc_auc(scores, target) / auc_counts(scores, target) for any score vector (this project's own)
+    ForestTrainer.fit(..., init_model=model), train_model(..., init_model=), cross_validate(..., init_model=),
+        tune_model_parameters(..., init_model=)   -> continue boosting from an existing ForestModel (xgb.train's
+        xgb_model=): k rounds continued for m more are exactly k + m rounds; `initial_error(s)` is the init model's own
+        error; ForestModel.head(n) / extended(trees) cut and join forests (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -58,7 +62,7 @@ from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMN
                          validate_assignment, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
 from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
-                    evaluation_error_matrix, roc_auc, train_model)
+                    evaluation_error_matrix, roc_auc, train_model, validate_init_model)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
 from .text import transform_title, transform_titles  # noqa: F401

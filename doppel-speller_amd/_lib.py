@@ -209,6 +209,10 @@ def _declare(handle):
         "ds_trainer_metrics": [p, p],
         "ds_trainer_batch_set_metrics": [p, c.c_uint32],
         "ds_trainer_batch_metrics": [p, p],
+        "ds_trainer_seed": [p, p, p, p, c.POINTER(c.c_int64)],
+        "ds_trainer_seed_device": [p, p, p, p, c.POINTER(c.c_int64), p],
+        "ds_trainer_batch_seed": [p, p, p, p],
+        "ds_trainer_batch_seed_device": [p, p, p, p, p],
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
@@ -272,7 +276,8 @@ EXPORTED_SYMBOLS = (
     "ds_auc_device", "ds_auc", "ds_weighted_logloss_device", "ds_metrics_option", "ds_trainer_set_metrics",
     "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes",
     "ds_index_create_device", "ds_index_read", "ds_index_build_option", "ds_assign_edges_device",
-    "ds_assign_solve_device", "ds_assign_option")
+    "ds_assign_solve_device", "ds_assign_option", "ds_trainer_seed", "ds_trainer_seed_device", "ds_trainer_batch_seed",
+    "ds_trainer_batch_seed_device")
 
 
 def lib():

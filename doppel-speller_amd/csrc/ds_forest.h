@@ -20,6 +20,28 @@ struct PathElement {
     double zero_reciprocal;    // 1 / zero_fraction
 };
 
+// The prediction rule for one row (ds_forest.hip's header): the float32 sum of the leaves the row reaches in the first
+// n_trees trees, from zero in tree order, without the base margin.  `row` holds the row's n_features values (in LDS).
+// Shared by ds_forest_kernel and by ds_train_seed_kernel (ds_train.hip), which starts a trainer's margins from a forest.
+__device__ inline float forest_leaf_sum(const int4 *nodes, const float *threshold, const int64_t *tree_offsets,
+                                        int32_t n_trees, const float *row)
+{
+    float sum = 0.f;  // xgboost: PredValue sums the leaves from zero, the base margin is added to that sum
+    for (int32_t t = 0; t < n_trees; ++t) {
+        const int64_t root = tree_offsets[t];
+        int64_t node = root;
+        int4 info = nodes[node];
+        while (info.x >= 0) {
+            const float value = row[info.x];
+            const int next = (value != value) ? info.w : (value < threshold[node] ? info.y : info.z);
+            node = root + next;
+            info = nodes[node];
+        }
+        sum = sum + threshold[node];
+    }
+    return sum;
+}
+
 }  // namespace ds
 
 struct ds_forest {

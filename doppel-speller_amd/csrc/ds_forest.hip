@@ -43,20 +43,7 @@ __global__ __launch_bounds__(kForestThreads) void ds_forest_kernel(ForestArgs a)
         __syncthreads();
         if (static_cast<int>(threadIdx.x) < rows_here) {
             const float *row = staged + threadIdx.x * stride;
-            float margin = 0.f;  // xgboost: PredValue sums the leaves from zero, the base margin is added to that sum
-            for (int32_t t = 0; t < a.n_trees; ++t) {
-                const int64_t root = a.tree_offsets[t];
-                int64_t node = root;
-                int4 info = a.nodes[node];
-                while (info.x >= 0) {
-                    const float value = row[info.x];
-                    const int next = (value != value) ? info.w : (value < a.threshold[node] ? info.y : info.z);
-                    node = root + next;
-                    info = a.nodes[node];
-                }
-                margin = margin + a.threshold[node];
-            }
-            margin = a.base_margin + margin;
+            const float margin = a.base_margin + forest_leaf_sum(a.nodes, a.threshold, a.tree_offsets, a.n_trees, row);
             if (a.margins) a.margins[first + threadIdx.x] = margin;
             if (a.probabilities) a.probabilities[first + threadIdx.x] = 1.0f / (1.0f + expf(-margin));
         }

@@ -156,6 +156,17 @@ int train_round_enqueue(hipStream_t stream, const TrainView &v, const TrainSampl
                         int32_t depth, bool folds, int compute_units);
 // a heap of `slots` nodes copied back from the device -> node_info int32[slots][4] and node_leaf float[slots]
 void train_unpack_heap(const Node *heap, int64_t slots, int32_t *node_info, float *node_leaf);
+// ---- continuing from a model ("Continuing from a model") --------------------------------------
+// What every seed entry (`who`) refuses of the forest: null, another device, another feature count, a base margin that
+// is not kTrainBaseMargin
+int train_check_seed_forest(const char *who, const ds_forest *forest, int device, int32_t n_features);
+// Enqueues ds_train_seed_kernel on `stream` and does not synchronise: leafsum[m * stride + r] = the forest's leaf sum of
+// row r of the raw float32[n][n_features] matrix, for every m < n_models.  A matrix in HBM is read where it lies; a host
+// matrix goes through `staged` in chunks of at most kSeedChunkBytes, which the caller keeps (with the matrix) until it
+// has synchronised the stream.
+constexpr int64_t kSeedChunkBytes = int64_t(64) << 20;
+int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *forest, const float *rows, bool in_hbm,
+                       int64_t n, float *leafsum, int32_t n_models, int64_t stride, DeviceBuffer<float> &staged);
 
 // ---- gradients of weighted_log_loss at the current margins ---------------------------------------------------------
 // kFolds: a row with fold[r] == held_out does not train: its (g, h) is (0, 0); everything else is written as for any row

@@ -16,8 +16,11 @@
 // TrainView, the one launcher of a round (train_round_enqueue) and the host checks and helpers of both trainers, and the
 // single trainer: a view of one model with nothing held out.  The batched trainer (ds_train_batch.hip) launches the same
 // kernels through the same launcher with the model as a further grid dimension.
+// Continuing from a model (ds_trainer_seed, DESIGN.md section 9 "Continuing from a model"): before the first round
+// ds_train_seed_kernel sets leafsum to a forest's leaf sums of the RAW rows, and the trees count on from the forest's.
 #include <atomic>
 
+#include "ds_forest.h"
 #include "ds_metrics.h"
 #include "ds_train.h"
 
@@ -181,6 +184,59 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_eval_kernel(const uint8_
     if (threadIdx.x == 0 && s_error) atomicAdd(error, s_error);
 }
 
+// ---- continuing from a model: a forest's leaf sums of the RAW rows, before the first round ---------------------------
+// The init model's thresholds need not be cuts of this matrix, so it is walked over the float32 features and not over the
+// bins.  One thread per row, the rows of a workgroup staged in LDS as in ds_forest_kernel, but at an odd stride
+// (n_features | 1): thread t reads word t * stride + f, and an odd stride spreads a wave's 64 rows over all 64 banks
+// for any feature count.  The sum is forest_leaf_sum's, what ds_forest_kernel holds before it adds the base margin; it
+// goes to the leaf sums of all n_models models of the view (stride apart), held-out rows included.
+struct SeedArgs {
+    const int4 *nodes;
+    const float *threshold;
+    const int64_t *tree_offsets;
+    const float *rows;
+    float *leafsum;
+    int64_t n, stride;
+    int32_t n_trees, n_features, n_models;
+};
+
+__global__ __launch_bounds__(kRowThreads) void ds_train_seed_kernel(SeedArgs a)
+{
+    extern __shared__ float s_rows[];   // [kRowThreads][n_features | 1]
+    const int stride = a.n_features | 1;
+    for (int64_t first = static_cast<int64_t>(blockIdx.x) * kRowThreads; first < a.n;
+         first += static_cast<int64_t>(gridDim.x) * kRowThreads) {
+        const int rows_here = static_cast<int>(a.n - first < kRowThreads ? a.n - first : kRowThreads);
+        __syncthreads();
+        for (int e = threadIdx.x; e < rows_here * a.n_features; e += kRowThreads) {   // coalesced row-major read
+            const int r = e / a.n_features, f = e - r * a.n_features;
+            s_rows[r * stride + f] = a.rows[first * a.n_features + e];
+        }
+        __syncthreads();
+        if (static_cast<int>(threadIdx.x) < rows_here) {
+            const float sum = forest_leaf_sum(a.nodes, a.threshold, a.tree_offsets, a.n_trees, s_rows + threadIdx.x * stride);
+            float *out = a.leafsum + first + threadIdx.x;
+            for (int32_t m = 0; m < a.n_models; ++m) out[m * a.stride] = sum;
+        }
+    }
+}
+
+// the custom error of n rows at their margins as they stand (the initial error of a seeded trainer's evaluation set)
+__global__ __launch_bounds__(kRowThreads) void ds_train_error_kernel(const float *leafsum, const float *labels, int64_t n,
+                                                                      float base_margin, unsigned long long *error)
+{
+    __shared__ unsigned long long s_error;
+    if (threadIdx.x == 0) s_error = 0;
+    __syncthreads();
+    unsigned long long mine = 0;
+    for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
+         r += static_cast<int64_t>(gridDim.x) * kRowThreads)
+        mine += train_row_error(base_margin + leafsum[r], labels[r]);
+    if (mine) atomicAdd(&s_error, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_error) atomicAdd(error, s_error);
+}
+
 // ---- row gather of a float32[n_src][nf] matrix in HBM (the split of the training set) ------------------------------
 __global__ __launch_bounds__(kRowThreads) void ds_gather_check_kernel(const int64_t *rows, int64_t n_rows, int64_t n_src,
                                                                        int32_t *errors)
@@ -332,6 +388,44 @@ void train_unpack_heap(const Node *heap, int64_t slots, int32_t *node_info, floa
     }
 }
 
+int train_check_seed_forest(const char *who, const ds_forest *forest, int device, int32_t n_features)
+{
+    DS_REQUIRE(forest != nullptr, "%s: forest is null", who);
+    DS_REQUIRE(forest->device == device, "%s: the forest lives on device %d, the trainer on device %d", who,
+               forest->device, device);
+    DS_REQUIRE(forest->n_features == n_features, "%s: the forest has %d features, the trainer %d", who,
+               forest->n_features, n_features);
+    DS_REQUIRE(forest->base_margin == kTrainBaseMargin,
+               "%s: the forest's base margin is %g, a trainer continues only from base margin %g (base_score 0.5)", who,
+               forest->base_margin, kTrainBaseMargin);
+    return DS_OK;
+}
+
+int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *forest, const float *rows, bool in_hbm,
+                       int64_t n, float *leafsum, int32_t n_models, int64_t stride, DeviceBuffer<float> &staged)
+{
+    const int32_t nf = forest->n_features;
+    const int64_t chunk_rows = in_hbm ? n : std::min<int64_t>(n, std::max<int64_t>(1, kSeedChunkBytes / (4 * int64_t(nf))));
+    if (!in_hbm) {
+        if (int status = staged.allocate(static_cast<size_t>(chunk_rows) * nf); status != DS_OK) return status;
+    }
+    const size_t lds = static_cast<size_t>(kRowThreads) * (nf | 1) * sizeof(float);
+    if (lds > 48 * 1024)
+        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_train_seed_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    for (int64_t first = 0; first < n; first += chunk_rows) {
+        const int64_t here = std::min(chunk_rows, n - first);
+        if (!in_hbm)   // after the kernel of the chunk before, in stream order
+            DS_HIP(hipMemcpyAsync(staged.ptr, rows + first * nf, sizeof(float) * here * nf, hipMemcpyHostToDevice, stream));
+        const SeedArgs args{forest->nodes.ptr, forest->threshold.ptr, forest->tree_offsets.ptr,
+                            in_hbm ? rows : staged.ptr, leafsum + first, here, stride, forest->n_trees, nf, n_models};
+        hipLaunchKernelGGL(ds_train_seed_kernel, dim3(train_row_grid(compute_units, here)), dim3(kRowThreads), lds,
+                           stream, args);
+        DS_HIP(hipGetLastError());
+    }
+    return DS_OK;
+}
+
 // ---- one round of either trainer --------------------------------------------------------------------------------------
 namespace {
 
@@ -414,8 +508,9 @@ struct ds_trainer {
     int64_t n = 0, n_eval = 0;
     int32_t nf = 0;
     ds::TrainParams params{};
-    bool has_labels = false;
+    bool has_labels = false, seeded = false;      // seeded: ds_trainer_seed has started the margins from a forest
     int64_t rounds = 0;
+    int32_t tree_base = 0;                        // the trees of that forest: the number of this trainer's first tree
     hipStream_t stream = nullptr;
     ds::DeviceBuffer<uint8_t> bins, eval_bins;
     ds::DeviceBuffer<float> labels, eval_labels, leafsum, eval_leafsum, probabilities, cuts;
@@ -525,6 +620,7 @@ int set_eval(const char *who, ds_trainer *trainer, const float *features, bool i
     DS_REQUIRE(trainer && features && labels, "%s: null argument", who);
     DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", who, (long long)n);
     DS_REQUIRE(trainer->rounds == 0, "%s: the evaluation set must be given before the first round", who);
+    DS_REQUIRE(!trainer->seeded, "%s: the evaluation set must be given before the trainer is seeded", who);
     DS_REQUIRE(trainer->metric_flags == 0, "%s: the evaluation set must be given before ds_trainer_set_metrics", who);
     if (int status = ds::train_check_labels(who, "", labels, n); status != DS_OK) return status;
     DS_HIP(hipSetDevice(trainer->device));
@@ -536,6 +632,58 @@ int set_eval(const char *who, ds_trainer *trainer, const float *features, bool i
     DS_HIP(hipMemsetAsync(trainer->eval_leafsum.ptr, 0, sizeof(float) * n, trainer->stream));
     DS_HIP(hipStreamSynchronize(trainer->stream));
     trainer->n_eval = n;
+    return DS_OK;
+}
+
+// what ds_trainer_seed enqueues: the leaf sums of both sets, then the evaluation set's error at them
+int enqueue_seed(ds_trainer *t, const ds_forest *forest, const float *features, const float *eval_features, bool in_hbm,
+                 hipStream_t stream, ds::DeviceBuffer<float> &staged, ds::DeviceBuffer<float> &eval_staged)
+{
+    if (int status = ds::train_seed_enqueue(stream, t->compute_units, forest, features, in_hbm, t->n, t->leafsum.ptr, 1,
+                                            t->n, staged);
+        status != DS_OK)
+        return status;
+    if (t->n_eval == 0) return DS_OK;
+    if (int status = ds::train_seed_enqueue(stream, t->compute_units, forest, eval_features, in_hbm, t->n_eval,
+                                            t->eval_leafsum.ptr, 1, t->n_eval, eval_staged);
+        status != DS_OK)
+        return status;
+    DS_HIP(hipMemsetAsync(t->error.ptr, 0, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(ds::ds_train_error_kernel, dim3(ds::train_row_grid(t->compute_units, t->n_eval)),
+                       dim3(ds::kRowThreads), 0, stream, t->eval_leafsum.ptr, t->eval_labels.ptr, t->n_eval,
+                       ds::kTrainBaseMargin, t->error.ptr);
+    DS_HIP(hipGetLastError());
+    DS_HIP(hipMemcpyAsync(t->pinned_error, t->error.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    return DS_OK;
+}
+
+// ds_trainer_seed (`who`, matrices on the host) and ds_trainer_seed_device (matrices in HBM, complete on `stream`)
+int seed_trainer(const char *who, ds_trainer *t, const ds_forest *forest, const float *features, const float *eval_features,
+                 bool in_hbm, int64_t *initial_error, hipStream_t stream)
+{
+    DS_REQUIRE(t != nullptr, "%s: trainer is null", who);
+    if (int status = ds::train_check_seed_forest(who, forest, t->device, t->nf); status != DS_OK) return status;
+    DS_REQUIRE(features != nullptr, "%s: features is null", who);
+    DS_REQUIRE(t->has_labels, "%s: no labels (ds_trainer_set_labels)", who);
+    DS_REQUIRE((eval_features != nullptr) == (t->n_eval > 0),
+               "%s: eval_features goes with the trainer's evaluation set (%lld rows)", who, (long long)t->n_eval);
+    DS_REQUIRE(t->rounds == 0, "%s: the trainer must be seeded before the first round", who);
+    DS_REQUIRE(!t->seeded, "%s: the trainer is already seeded", who);
+    DS_HIP(hipSetDevice(t->device));
+    if (!in_hbm) {   // one chunk per set at the most
+        stream = t->stream;
+        const int64_t rows = t->n + t->n_eval;
+        if (int status = check_free(std::min(rows * t->nf * 4, 2 * ds::kSeedChunkBytes), who); status != DS_OK)
+            return status;
+    }
+    ds::DeviceBuffer<float> staged, eval_staged;
+    t->seeded = true;   // whatever happens below: a trainer whose margins may be partly written is not seeded again
+    const int status = enqueue_seed(t, forest, features, eval_features, in_hbm, stream, staged, eval_staged);
+    const hipError_t synced = hipStreamSynchronize(stream);   // the call's one host sync; the staged chunks live until here
+    if (status != DS_OK) return status;
+    DS_HIP(synced);
+    t->tree_base = forest->n_trees;
+    if (initial_error) *initial_error = t->n_eval > 0 ? static_cast<int64_t>(*t->pinned_error) : -1;
     return DS_OK;
 }
 
@@ -609,6 +757,19 @@ int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsam
     t->sampling_view = ds::TrainSamplingView{nullptr, nullptr, nullptr, nullptr, t->masks.ptr, 0, sampling, 0};
     t->sampled = sampling.any();   // every fraction 1: the plain kernels, whatever was set before
     return DS_OK;
+}
+
+int ds_trainer_seed(ds_trainer *trainer, const ds_forest *forest, const float *features, const float *eval_features,
+                    int64_t *initial_error)
+{
+    return seed_trainer("ds_trainer_seed", trainer, forest, features, eval_features, false, initial_error, nullptr);
+}
+
+int ds_trainer_seed_device(ds_trainer *trainer, const ds_forest *forest, const float *d_features,
+                           const float *d_eval_features, int64_t *initial_error, void *stream)
+{
+    return seed_trainer("ds_trainer_seed_device", trainer, forest, d_features, d_eval_features, true, initial_error,
+                        static_cast<hipStream_t>(stream));
 }
 
 int ds_trainer_set_metrics(ds_trainer *trainer, uint32_t flags)
@@ -723,7 +884,8 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
     DS_HIP(hipSetDevice(t->device));
     const int32_t depth = t->params.max_depth;
     hipStream_t stream = t->stream;
-    if (t->sampled) t->sampling_view.tree = static_cast<int32_t>(t->rounds);   // this tree's number indexes its streams
+    // this tree's number indexes its streams: a seeded trainer counts on from the forest's trees
+    if (t->sampled) t->sampling_view.tree = t->tree_base + static_cast<int32_t>(t->rounds);
     if (int status = ds::train_round_enqueue(stream, t->view, t->sampled ? &t->sampling_view : nullptr, 1, depth, false,
                                              t->compute_units);
         status != DS_OK)

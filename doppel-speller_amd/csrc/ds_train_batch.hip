@@ -31,6 +31,12 @@
 //   metric_columns  MetricColumn[M]   model m's margins with the lists of its held-out fold
 //   metric_scratch                    two key buffers and a count table per model, for the largest fold's negatives
 //   metric_counters uint64[M][6]      copied back whole with the step's other results; the host keeps the active models'
+//
+// Continuing from a model (ds_trainer_batch_seed; DESIGN.md section 9, "Continuing from a model"): before the first step
+// ds_train_seed_kernel walks a forest over the RAW matrix once per row and writes the leaf sum into all M leafsum columns;
+// ds_batch_error_kernel then gives every model's held-out error at those margins, and every model's tree count starts at
+// the forest's.
+#include "ds_forest.h"
 #include "ds_metrics.h"
 #include "ds_train.h"
 
@@ -81,7 +87,7 @@ struct ds_trainer_batch {
     ds::TrainView view{};
     int compute_units = 256;
     // subsampling (ds_trainer_batch_set_sampling)
-    bool stepped = false, sampled = false;
+    bool stepped = false, sampled = false, seeded = false;
     std::vector<int32_t> tree_count;           // the trees every model has grown
     ds::DeviceBuffer<ds::TrainSampling> d_sampling;
     ds::DeviceBuffer<int32_t> d_trees, d_held_slot;
@@ -213,6 +219,53 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
     return DS_OK;
 }
 
+// what ds_trainer_batch_seed enqueues: the leaf sums of every model, then every model's held-out error at them
+int enqueue_seed(ds_trainer_batch *b, const ds_forest *forest, const float *features, bool in_hbm, hipStream_t stream,
+                 ds::DeviceBuffer<float> &staged)
+{
+    if (int status = ds::train_seed_enqueue(stream, b->compute_units, forest, features, in_hbm, b->n, b->leafsum.ptr,
+                                            b->n_models, b->n, staged);
+        status != DS_OK)
+        return status;
+    for (int32_t m = 0; m < b->n_models; ++m) b->pinned_active[m] = m;   // the error kernel reads its models from here
+    DS_HIP(hipMemcpyAsync(b->active.ptr, b->pinned_active, sizeof(int32_t) * b->n_models, hipMemcpyHostToDevice, stream));
+    DS_HIP(hipMemsetAsync(b->errors.ptr, 0, b->errors.bytes(), stream));
+    hipLaunchKernelGGL(ds::ds_batch_error_kernel,
+                       dim3(ds::train_row_grid(b->compute_units, b->n), static_cast<unsigned>(b->n_models)),
+                       dim3(ds::kRowThreads), 0, stream, b->view);
+    DS_HIP(hipGetLastError());
+    DS_HIP(hipMemcpyAsync(b->pinned_errors, b->errors.ptr, b->errors.bytes(), hipMemcpyDeviceToHost, stream));
+    return DS_OK;
+}
+
+// ds_trainer_batch_seed (`who`, the matrix on the host) and ds_trainer_batch_seed_device (in HBM, complete on `stream`)
+int seed_batch(const char *who, ds_trainer_batch *b, const ds_forest *forest, const float *features, bool in_hbm,
+               int64_t *initial_errors, hipStream_t stream)
+{
+    DS_REQUIRE(b != nullptr, "%s: batch is null", who);
+    if (int status = ds::train_check_seed_forest(who, forest, b->device, b->nf); status != DS_OK) return status;
+    DS_REQUIRE(features != nullptr, "%s: features is null", who);
+    DS_REQUIRE(!b->stepped, "%s: the batch must be seeded before the first step", who);
+    DS_REQUIRE(!b->seeded, "%s: the batch is already seeded", who);
+    DS_HIP(hipSetDevice(b->device));
+    if (!in_hbm) {
+        stream = b->stream;
+        if (int status = ds::train_check_free(std::min(b->n * b->nf * 4, ds::kSeedChunkBytes), who); status != DS_OK)
+            return status;
+    }
+    ds::DeviceBuffer<float> staged;
+    b->seeded = true;   // whatever happens below: a batch whose margins may be partly written is not seeded again
+    const int status = enqueue_seed(b, forest, features, in_hbm, stream, staged);
+    const hipError_t synced = hipStreamSynchronize(stream);   // the call's one host sync; the staged chunk lives until here
+    if (status != DS_OK) return status;
+    DS_HIP(synced);
+    b->tree_count.assign(b->n_models, forest->n_trees);   // every model's first tree has the forest's count as its number
+    if (initial_errors)
+        for (int32_t m = 0; m < b->n_models; ++m)
+            initial_errors[m] = b->models[m].held_out >= 0 ? static_cast<int64_t>(b->pinned_errors[m]) : -1;
+    return DS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -322,6 +375,19 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
                                              b->masks.ptr, static_cast<int64_t>(waves)};
     b->sampled = true;
     return DS_OK;
+}
+
+int ds_trainer_batch_seed(ds_trainer_batch *batch, const ds_forest *forest, const float *features,
+                          int64_t *initial_errors)
+{
+    return seed_batch("ds_trainer_batch_seed", batch, forest, features, false, initial_errors, nullptr);
+}
+
+int ds_trainer_batch_seed_device(ds_trainer_batch *batch, const ds_forest *forest, const float *d_features,
+                                 int64_t *initial_errors, void *stream)
+{
+    return seed_batch("ds_trainer_batch_seed_device", batch, forest, d_features, true, initial_errors,
+                      static_cast<hipStream_t>(stream));
 }
 
 int64_t ds_trainer_batch_metrics_bytes(int64_t n, int32_t n_models, int32_t n_folds)

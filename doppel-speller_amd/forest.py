@@ -165,6 +165,53 @@ class ForestModel:
         return cls(cat("feature", np.int32), cat("threshold", np.float32), cat("yes", np.int32), cat("no", np.int32),
                    cat("missing", np.int32), offsets, n_features, base_margin, device)
 
+    TREE_KEYS = ("feature", "threshold", "yes", "no", "missing")
+
+    @staticmethod
+    def head_arrays(arrays, n_trees):
+        """The flat arrays of the first n_trees trees of `arrays` (no library needed)."""
+        total = arrays["tree_offsets"].shape[0] - 1
+        if isinstance(n_trees, bool) or not isinstance(n_trees, (int, np.integer)) or not 0 <= n_trees <= total:
+            raise ValueError(f"n_trees must be an integer in [0, {total}], not {n_trees!r}")
+        end = int(arrays["tree_offsets"][n_trees])
+        out = {key: arrays[key][:end].copy() for key in ForestModel.TREE_KEYS}
+        return dict(out, tree_offsets=arrays["tree_offsets"][:int(n_trees) + 1].copy(), base_margin=arrays["base_margin"])
+
+    @staticmethod
+    def extended_arrays(arrays, trees):
+        """The flat arrays of `arrays`' trees followed by `trees`, per-tree dicts as from_trees takes them (no library
+        needed)."""
+        trees = list(trees)
+        dtypes = dict(feature=np.int32, threshold=np.float32, yes=np.int32, no=np.int32, missing=np.int32)
+        sizes = [np.asarray(tree["feature"]).shape[0] for tree in trees]
+        out = {key: np.concatenate([arrays[key]] + [np.asarray(tree[key], dtype=dtypes[key]) for tree in trees])
+               for key in ForestModel.TREE_KEYS}
+        offsets = np.concatenate([arrays["tree_offsets"],
+                                  arrays["tree_offsets"][-1] + np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+        return dict(out, tree_offsets=offsets, base_margin=arrays["base_margin"])
+
+    @staticmethod
+    def tree_list(arrays):
+        """The per-tree dicts (views) of flat arrays: what from_trees and extended take."""
+        offsets = arrays["tree_offsets"]
+        return [{key: arrays[key][int(offsets[t]):int(offsets[t + 1])] for key in ForestModel.TREE_KEYS}
+                for t in range(offsets.shape[0] - 1)]
+
+    def _from_arrays(self, a):
+        return type(self)(a["feature"], a["threshold"], a["yes"], a["no"], a["missing"], a["tree_offsets"],
+                          self.n_features, a["base_margin"], self.device)
+
+    def head(self, n_trees):
+        """A new model of the first n_trees trees (0 .. self.n_trees; 0: the empty forest, whose margin is the base
+        margin), without a cover."""
+        return self._from_arrays(self.head_arrays(self.arrays, n_trees))
+
+    def extended(self, trees):
+        """A new model of this model's trees followed by `trees`, per-tree dicts as from_trees takes them (those of
+        another model: tree_list(other.arrays)).  The result has this model's base margin and NO cover: a cover
+        describes the forest it was counted for."""
+        return self._from_arrays(self.extended_arrays(self.arrays, trees))
+
     def save(self, path):
         """The flat arrays in one .npz (the reference pickles its booster, train.py:134-135)."""
         a = self.arrays

@@ -304,6 +304,25 @@ def validate_parameters(num_boost_round=1000, early_stopping_rounds=50, max_dept
     return params
 
 
+def validate_init_model(init_model, n_features, device=None):
+    """The checks of an `init_model` argument (no device work) -> the model.  It must be an open ForestModel with the
+    matrix's n_features and base margin 0 -- base_score 0.5, the trainer's own, which ForestTrainer's models and
+    xgboost imports with the default base_score have -- and, when `device` is given, live on that device.  Its depth
+    and tree count are free; a model of zero trees is legal ("Continuing from a model")."""
+    if not isinstance(init_model, ForestModel):
+        raise ValueError(f"init_model must be a ForestModel, not {type(init_model).__name__}")
+    if not init_model.handle:
+        raise ValueError("init_model is closed")
+    if init_model.n_features != n_features:
+        raise ValueError(f"init_model has {init_model.n_features} features, the training features {n_features}")
+    if init_model.arrays["base_margin"] != 0.0:
+        raise ValueError(f"init_model has base margin {init_model.arrays['base_margin']!r}; training continues only from "
+                         "base margin 0 (base_score 0.5)")
+    if device is not None and init_model.device != device:
+        raise ValueError(f"init_model lives on device {init_model.device}, the trainer on device {device}")
+    return init_model
+
+
 def _samples(params):
     return any(params[name] < 1 for name in SAMPLING_NAMES[:3])
 
@@ -386,7 +405,15 @@ class ForestTrainer:
     key "train-auc", "evaluation-auc", "train-logloss", "evaluation-logloss" (evaluation keys only with an evaluation
     set) and `metric_counts` the integers they come from ({"train": (concordant, ties, positives, negatives,
     logloss_sum, rows), "evaluation": ...} per round, -1 for a metric not requested).  They are computed on the device
-    from the margins of ALL rows of a set and change neither the trees nor the early stopping."""
+    from the margins of ALL rows of a set and change neither the trees nor the early stopping.
+
+    init_model=<ForestModel> continues boosting from that model (xgb.train(..., xgb_model=booster); DESIGN.md section 9,
+    "Continuing from a model"): the margins start at the model's, evaluated on the raw features on the device, and the
+    new trees are those a trainer would grow that had grown the model's trees itself.  `trees` and `history` hold the
+    NEW rounds, `initial_error` the evaluation error of the init model (None without an evaluation set), model(n) the
+    init trees followed by the first n new ones.  Early stopping looks at the new rounds only (the first minimum of
+    `history`; initial_error is no candidate), and `best_iteration` counts all trees: init trees + the best new round,
+    so that the model returned has best_iteration + 1 trees as ever.  See validate_init_model for what is accepted."""
 
     def __init__(self, device=0):
         self.device = device
@@ -394,18 +421,22 @@ class ForestTrainer:
         self.trees = []
         self.history = []
         self.best_iteration = None
+        self.init_model = None
+        self.initial_error = None
         self.eval_metrics = ()
         self.metrics_history = {}
         self.metric_counts = []
 
     def begin(self, features, target, eval_features=None, eval_target=None, max_depth=5, eta=0.1,
               min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
-              colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
+              colsample_bylevel=1.0, sample_seed=0, eval_metrics=(), init_model=None):
         features, target, eval_features, eval_target, params = validate_fit(
             features, target, eval_features, eval_target, max_depth=max_depth, eta=eta,
             min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin, subsample=subsample,
             colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, sample_seed=sample_seed,
             eval_metrics=eval_metrics)
+        if init_model is not None:
+            validate_init_model(init_model, features.shape[1], self.device)
         self.close()
         self.params = params
         self.n, self.n_features = features.shape
@@ -424,6 +455,7 @@ class ForestTrainer:
         if eval_features is not None:
             _lib.check(library.ds_trainer_set_eval(self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
                                                    self.n_eval), "ds_trainer_set_eval")
+        self._seed(init_model, features, eval_features, False)
         self._set_metrics(params)
         slots = (2 << params["max_depth"]) - 1
         self._info = np.zeros((slots, 4), np.int32)
@@ -436,6 +468,22 @@ class ForestTrainer:
             _lib.check(_lib.lib().ds_trainer_set_sampling(self.handle, params["subsample"], params["colsample_bytree"],
                                                           params["colsample_bylevel"], params["sample_seed"]),
                        "ds_trainer_set_sampling")
+
+    def _seed(self, init_model, features, eval_features, in_hbm):
+        """Start the margins from init_model (None: from zero, nothing to do) once labels and evaluation set are in."""
+        self.init_model, self.initial_error = init_model, None
+        if init_model is None:
+            return
+        error = ctypes.c_int64(-1)
+        library = _lib.lib()
+        if in_hbm:
+            _lib.check(library.ds_trainer_seed_device(self.handle, init_model.handle, _lib.pointer(features),
+                                                      _lib.pointer(eval_features), ctypes.byref(error), None),
+                       "ds_trainer_seed_device")
+        else:
+            _lib.check(library.ds_trainer_seed(self.handle, init_model.handle, _lib.pointer(features),
+                                               _lib.pointer(eval_features), ctypes.byref(error)), "ds_trainer_seed")
+        self.initial_error = int(error.value) if self.n_eval else None
 
     def _set_metrics(self, params):
         """The metrics to the library once the labels and the evaluation set are in place (none: nothing to set)."""
@@ -450,7 +498,8 @@ class ForestTrainer:
 
     def begin_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, max_depth=5,
                      eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, n_features=None,
-                     subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
+                     subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=(),
+                     init_model=None):
         """begin for matrices that already lie in HBM: contiguous float32[n, n_features] DeviceArrays (or addresses,
         with n_features given), complete before the call; labels are host arrays.  The cuts come from
         compute_cuts_device, the bins from the same kernel as begin's, so every later call works as after begin.  The
@@ -460,6 +509,8 @@ class ForestTrainer:
             min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin,
             n_features=n_features, subsample=subsample, colsample_bytree=colsample_bytree,
             colsample_bylevel=colsample_bylevel, sample_seed=sample_seed, eval_metrics=eval_metrics)
+        if init_model is not None:
+            validate_init_model(init_model, n_features, self.device)
         self.close()
         self.params = params
         self.n, self.n_features, self.n_eval = n, n_features, n_eval
@@ -482,6 +533,7 @@ class ForestTrainer:
             _lib.check(library.ds_trainer_set_eval_device(self.handle, _lib.pointer(d_eval_features),
                                                           _lib.pointer(eval_target), self.n_eval),
                        "ds_trainer_set_eval_device")
+        self._seed(init_model, d_features, d_eval_features if n_eval else None, True)
         self._set_metrics(params)
         self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
         slots = (2 << params["max_depth"]) - 1
@@ -492,7 +544,7 @@ class ForestTrainer:
     def fit_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
                    early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
                    max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
-                   sample_seed=0, eval_metrics=()):
+                   sample_seed=0, eval_metrics=(), init_model=None):
         """fit for matrices in HBM (begin_device, then fit's rounds and early stopping)."""
         rounds = validate_fit_device(d_features, n, target, d_eval_features, n_eval, eval_target, num_boost_round,
                                      early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda, beta, max_bin,
@@ -500,7 +552,7 @@ class ForestTrainer:
                                      eval_metrics)[5]
         self.begin_device(d_features, n, target, d_eval_features, n_eval, eval_target, max_depth, eta,
                           min_child_weight, reg_lambda, beta, max_bin, n_features, subsample, colsample_bytree,
-                          colsample_bylevel, sample_seed, eval_metrics)
+                          colsample_bylevel, sample_seed, eval_metrics, init_model)
         return self._boost(rounds)
 
     def step(self):
@@ -530,18 +582,22 @@ class ForestTrainer:
         return heap_tree(info, leaf, self.cuts, self.cut_offsets)
 
     def model(self, n_trees=None):
-        """ForestModel of the first n_trees trees (default: all grown so far)."""
+        """ForestModel of the first n_trees trees grown here (default: all so far), after the init model's if there is
+        one."""
         trees = self.trees[:len(self.trees) if n_trees is None else n_trees]
+        if self.init_model is not None:
+            return self.init_model.extended(trees)
         return ForestModel.from_trees(trees, self.n_features, device=self.device)
 
     def fit(self, features, target, eval_features=None, eval_target=None, num_boost_round=1000,
             early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-            max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
+            max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=(),
+            init_model=None):
         rounds = validate_fit(features, target, eval_features, eval_target, num_boost_round, early_stopping_rounds,
                               max_depth, eta, min_child_weight, reg_lambda, beta, max_bin, subsample, colsample_bytree,
                               colsample_bylevel, sample_seed, eval_metrics)[4]
         self.begin(features, target, eval_features, eval_target, max_depth, eta, min_child_weight, reg_lambda, beta,
-                   max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed, eval_metrics)
+                   max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed, eval_metrics, init_model)
         return self._boost(rounds)
 
     def _boost(self, rounds):
@@ -554,8 +610,9 @@ class ForestTrainer:
                 best, best_error = round_, error
             if round_ - best >= rounds["early_stopping_rounds"]:
                 break
-        self.best_iteration = best if best is not None else len(self.trees) - 1
-        return self.model(self.best_iteration + 1)
+        best = best if best is not None else len(self.trees) - 1           # among the rounds grown here
+        self.best_iteration = (self.init_model.n_trees if self.init_model is not None else 0) + best
+        return self.model(best + 1)
 
     def _read(self, **wanted):
         out = {name: np.empty(shape, dtype) for name, (shape, dtype) in wanted.items()}
@@ -613,17 +670,22 @@ class TrainModelResult:
     reference's return value: ForestModel.feature_importance()), `error_matrix` ((tp, tn, fp, fn) on the evaluation set
     at 0.9, what the reference logs; None without an evaluation set), `best_iteration`, `history`, `rows` (the
     DataFrame of FeatureEngineering.rows), `timings` (milliseconds per stage, "total" for the call) and, when
-    eval_metrics were requested, `metrics_history` (ForestTrainer.metrics_history; None otherwise)."""
+    eval_metrics were requested, `metrics_history` (ForestTrainer.metrics_history; None otherwise).  With init_model:
+    `initial_error`, the evaluation error of the init model (None otherwise and without an evaluation set); `model`,
+    `feature_importance` and a counted cover are those of the WHOLE forest, `history` that of the new rounds and
+    `best_iteration` counts all trees (ForestTrainer)."""
 
     def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings,
-                 metrics_history=None):
+                 metrics_history=None, initial_error=None):
         self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
         self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
         self.metrics_history = metrics_history
+        self.initial_error = initial_error
 
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
-                transform=True, evaluation_fractions=None, cover=False, build_index="host", **fit_parameters):
+                transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
+                **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -634,13 +696,18 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     cover: also count the training matrix through the finished trees while it is still in HBM
     (ForestModel.fit_cover_device), so that the returned model can explain its predictions
     (predict_contributions, Prediction.explain); `timings` then has a "cover" entry.  The trees are the same either
-    way.  build_index: "host" or "device", where the truth index is built (TruthSide)."""
+    way.  build_index: "host" or "device", where the truth index is built (TruthSide).
+    init_model: a ForestModel of FEATURES_COUNT features to continue from (ForestTrainer; validate_init_model): the
+    device chain is the same, seeded from the matrices in HBM, and the result gains `initial_error`."""
+    from .feature_engineering import FEATURES_COUNT
     from .training_set import FeatureEngineering
     started = time.perf_counter()
     unknown = set(fit_parameters) - set(inspect.signature(validate_parameters).parameters)
     if unknown:
         raise ValueError(f"unknown fit parameters {sorted(unknown)}")
     validate_parameters(**fit_parameters)
+    if init_model is not None:
+        validate_init_model(init_model, FEATURES_COUNT, device)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=evaluation_fractions, build_index=build_index)
@@ -650,7 +717,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     mark = time.perf_counter()
     has_eval = sets.n_evaluation > 0
     model = trainer.fit_device(sets.train, sets.n_train, sets.train_target, sets.evaluation if has_eval else None,
-                               sets.n_evaluation, sets.evaluation_target if has_eval else None, **fit_parameters)
+                               sets.n_evaluation, sets.evaluation_target if has_eval else None, init_model=init_model,
+                               **fit_parameters)
     fit_ms = (time.perf_counter() - mark) * 1000.0
     timings["cuts"], timings["bin"] = trainer.timings["cuts"], trainer.timings["bin"]
     timings["boost"] = fit_ms - timings["cuts"] - timings["bin"]
@@ -672,11 +740,11 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
             sets.free()
             raise
         timings["cover"] = (time.perf_counter() - mark) * 1000.0
-    best_iteration, history = trainer.best_iteration, list(trainer.history)
+    best_iteration, history, initial_error = trainer.best_iteration, list(trainer.history), trainer.initial_error
     metrics_history = {key: list(values) for key, values in trainer.metrics_history.items()} \
         if trainer.eval_metrics else None
     trainer.close()
     sets.free()
     timings["total"] = (time.perf_counter() - started) * 1000.0
     return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings,
-                            metrics_history=metrics_history)
+                            metrics_history=metrics_history, initial_error=initial_error)

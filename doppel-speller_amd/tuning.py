@@ -17,7 +17,7 @@ from . import _lib
 from .forest import ForestModel
 from .train import (METRIC_NAMES, SAMPLING_NAMES, _device_columns, _device_labels, _matrix_and_labels, _positive_int,
                     auc_numerator, compute_cuts, compute_cuts_device, heap_tree, metric_flags, metric_values,
-                    validate_metrics, validate_parameters)
+                    validate_init_model, validate_metrics, validate_parameters)
 
 MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
 FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
@@ -283,31 +283,40 @@ class ForestTrainerBatch:
 
     begin(..., metrics=("auc", "logloss")) also computes, in every step and on the device, the metrics of each active
     model over the rows of its HELD-OUT fold: metric_counts[m] gains the round's (concordant, ties, positives, negatives,
-    logloss_sum, rows) and metrics_history[m][name] its value (-1s and None for a model without a fold)."""
+    logloss_sum, rows) and metrics_history[m][name] its value (-1s and None for a model without a fold).
+
+    begin(..., init_model=<ForestModel>) starts EVERY model from that model ("Continuing from a
+    model"): the forest is evaluated once per row of the raw matrix on the device, `initial_errors[m]` is its error on
+    model m's held-out rows (None without a fold), trees[m] and history[m] hold the new rounds, model(m, n) the init
+    trees followed by the first n new ones, and model m stays ForestTrainer(init_model=...)'s on its training rows."""
 
     def __init__(self, device=0):
         self.device = device
         self.handle = None
         self.trees, self.history, self.last_heap = [], [], []
         self.metrics, self.metrics_history, self.metric_counts = (), [], []
+        self.init_model, self.initial_errors = None, []
         self.timings = {}
 
-    def begin(self, features, target, fold, models, max_bin=256, cuts=None, metrics=()):
+    def begin(self, features, target, fold, models, max_bin=256, cuts=None, metrics=(), init_model=None):
         features, target = _matrix_and_labels(features, target, "training")
         return self._begin(features, False, features.shape[0], features.shape[1], target, fold, models, max_bin, cuts,
-                           metrics)
+                           metrics, init_model)
 
-    def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None, metrics=()):
+    def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None, metrics=(),
+                     init_model=None):
         """begin for a contiguous float32[n, n_features] matrix that lies complete in HBM (a DeviceArray, or an address
         with n_features given).  It is read where it lies, never copied to the host, and not kept."""
         n_features = _device_columns(d_features, n_features)
         n, target = _device_labels(n, target, "training")
         if isinstance(d_features, _lib.DeviceArray) and n > d_features.shape[0]:
             raise ValueError(f"{n} training rows exceed the device matrix's {d_features.shape[0]}")
-        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts, metrics)
+        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts, metrics, init_model)
 
-    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts, metrics=()):
+    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts, metrics=(), init_model=None):
         metrics = validate_metrics(metrics, "metrics")
+        if init_model is not None:
+            validate_init_model(init_model, n_features, self.device)
         fold, n_folds = _validate_fold(fold, n)
         params, held_out, sets = validate_models(models, FOLDS_MAX)
         if held_out.max() >= n_folds:
@@ -341,6 +350,17 @@ class ForestTrainerBatch:
             seeds = np.array([one["sample_seed"] for one in sets], np.uint64)
             _lib.check(library.ds_trainer_batch_set_sampling(self.handle, _lib.pointer(fractions), _lib.pointer(seeds)),
                        "ds_trainer_batch_set_sampling")
+        self.init_model, self.initial_errors = init_model, [None] * len(sets)
+        if init_model is not None:
+            errors = np.full(self.n_models, -1, np.int64)
+            if in_hbm:
+                _lib.check(library.ds_trainer_batch_seed_device(self.handle, init_model.handle, _lib.pointer(features),
+                                                                _lib.pointer(errors), None),
+                           "ds_trainer_batch_seed_device")
+            else:
+                _lib.check(library.ds_trainer_batch_seed(self.handle, init_model.handle, _lib.pointer(features),
+                                                         _lib.pointer(errors)), "ds_trainer_batch_seed")
+            self.initial_errors = [int(errors[m]) if held_out[m] >= 0 else None for m in range(self.n_models)]
         self.metrics = metrics
         self.metrics_history = [{name: [] for name in metrics} for _ in sets]
         self.metric_counts = [[] for _ in sets]
@@ -387,8 +407,11 @@ class ForestTrainerBatch:
         return out
 
     def model(self, m, n_trees=None):
-        """ForestModel of the first n_trees trees of model m (default: all grown so far)."""
+        """ForestModel of the first n_trees trees of model m grown here (default: all so far), after the init model's
+        if there is one."""
         trees = self.trees[m][:len(self.trees[m]) if n_trees is None else n_trees]
+        if self.init_model is not None:
+            return self.init_model.extended(trees)
         return ForestModel.from_trees(trees, self.n_features, device=self.device)
 
     def _read(self, m, **wanted):
@@ -433,6 +456,9 @@ class CrossValidation:
     With metrics: `metrics_history[p]` ({"auc": [...], "logloss": [...]}: per round the pooled out-of-fold value of set
     p), `fold_metric_counts[p][k]` (per round the six integers of fold k), `select_by`, and the columns `auc` and/or
     `logloss` of `results` at best_iteration.
+    With init_model: `initial_errors[p]`, the pooled out-of-fold error of the init model under set p's folds (the same
+    number for every set: the baseline that "did continuing help" is judged against) and the column `initial_error`;
+    rounds, curves and best_iteration count the NEW rounds, and `model` has the init trees before them.
     tune_model_parameters adds `rows` and `feature_importance`."""
 
     def __init__(self, **fields):
@@ -473,7 +499,7 @@ def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics=()):
 
 def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0, num_boost_round=1000,
                    early_stopping_rounds=50, max_bin=256, refit=True, device=0, models_per_batch=None, metrics=(),
-                   select_by="error"):
+                   select_by="error", init_model=None):
     """K-fold cross-validation of one parameter set or a list of them (parameter_grid) on the GPU -> CrossValidation.
 
     features: a host matrix, or a DeviceArray float32[>= n, n_features] in HBM of which the first len(target) rows
@@ -490,7 +516,12 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     section 9, "Metrics"); the result gains metrics_history[p] (the pooled out-of-fold value per round: auc =
     sum_k (2 c_k + t_k) / (2 sum_k P_k N_k), logloss = sum_k sum_k / 2^20 / sum_k rows_k) and the columns `auc` /
     `logloss` of `results`.  select_by = "auc" (maximise) or "logloss" (minimise) steps, stops and chooses on that curve
-    instead of the error's, by its integer numerators; "error" (the default) is the rule above whatever the metrics."""
+    instead of the error's, by its integer numerators; "error" (the default) is the rule above whatever the metrics.
+
+    init_model: every fold of every set starts from that ForestModel ("Continuing from a model").
+    Rounds, curves and best_iteration count the new rounds; `initial_errors` gives the init model's pooled out-of-fold
+    error per set; the refit is ForestTrainer().fit(features, target, num_boost_round=best_iteration + 1,
+    init_model=init_model, **best_parameters), bit for bit."""
     started = time.perf_counter()
     sets, per_batch = validate_cross_validation(parameters, n_folds, seed, num_boost_round, early_stopping_rounds,
                                                 max_bin, models_per_batch, metrics, select_by)
@@ -505,6 +536,8 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     else:
         features, target = _matrix_and_labels(features, target, "training")
         n, n_features = features.shape
+    if init_model is not None:
+        validate_init_model(init_model, n_features, device)
     folds = fold_assignment(groups, n_folds, seed, n)
     if per_batch is None:
         per_batch = _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics)
@@ -516,14 +549,15 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     def begin(models, metrics=()):
         batch = ForestTrainerBatch(device)
         if in_hbm:
-            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts, metrics)
+            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts, metrics, init_model)
         else:
-            batch.begin(features, target, folds, models, max_bin, cuts, metrics)
+            batch.begin(features, target, folds, models, max_bin, cuts, metrics, init_model)
         timings["bin"] += batch.timings["bin"]
         return batch
 
     fold_history = [None] * len(sets)
     fold_counts = [None] * len(sets)
+    initial_errors = [None] * len(sets)
     for first in range(0, len(sets), per_batch):
         chunk = sets[first:first + per_batch]
         batch = begin([dict(one, held_out=k) for one in chunk for k in range(n_folds)], metrics)
@@ -545,6 +579,8 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
                     break
             for s in range(len(chunk)):
                 fold_history[first + s] = [list(batch.history[s * n_folds + k]) for k in range(n_folds)]
+                if init_model is not None:
+                    initial_errors[first + s] = sum(batch.initial_errors[s * n_folds:(s + 1) * n_folds])
                 if metrics:
                     fold_counts[first + s] = [list(batch.metric_counts[s * n_folds + k]) for k in range(n_folds)]
             timings["boost"] += (time.perf_counter() - mark) * 1000.0
@@ -562,6 +598,9 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     best_set = chosen["chosen"]
     extra = dict(metrics_history=chosen["metrics_history"], fold_metric_counts=fold_counts, select_by=select_by) \
         if metrics else {}
+    if init_model is not None:
+        results["initial_error"] = initial_errors
+        extra["initial_errors"] = initial_errors
     out = CrossValidation(**extra, results=results, history=chosen["history"], fold_history=fold_history, parameters=sets,
                           chosen=best_set, best_parameters=dict(sets[best_set]),
                           best_iteration=chosen["best_iteration"][best_set], folds=folds, timings=timings)
@@ -586,14 +625,17 @@ def row_groups(rows):
 
 
 def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters, n_folds=5, top_n=100,
-                          sample_n=10, seed=0, device=0, transform=True, cover=False, **cv_arguments):
+                          sample_n=10, seed=0, device=0, transform=True, cover=False, init_model=None,
+                          **cv_arguments):
     """Parameter search from raw titles in one call: FeatureEngineering(..., no evaluation split).
     generate_device_data_sets() -> cross_validate on the matrix in HBM, folds by row_groups -> the refit model.
     cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch, metrics, select_by.  Returns cross_validate's result
     with `rows` (FeatureEngineering.rows), `feature_importance` and the FeatureEngineering stages in `timings`.
     cover: also count the model's cover on the matrix while it is in HBM (ForestModel.fit_cover_device), so that the
-    model can explain its predictions; `timings` then has "cover".  Everything is validated before any device work and
-    everything held in HBM is freed on every exit path."""
+    model can explain its predictions; `timings` then has "cover".  init_model: cross_validate's, a ForestModel of
+    FEATURES_COUNT features that every fold, set and the refit continue from.  Everything is validated before any
+    device work and everything held in HBM is freed on every exit path."""
+    from .feature_engineering import FEATURES_COUNT
     from .training_set import FeatureEngineering
     started = time.perf_counter()
     unknown = set(cv_arguments) - {"num_boost_round", "early_stopping_rounds", "max_bin", "models_per_batch", "metrics",
@@ -601,6 +643,8 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
     if unknown:
         raise ValueError(f"unknown cross-validation arguments {sorted(unknown)}")
     validate_cross_validation(parameters, n_folds, seed, **cv_arguments)
+    if init_model is not None:
+        validate_init_model(init_model, FEATURES_COUNT, device)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=dict(generated=0.0, negative=0.0, positive=0.0))
@@ -608,7 +652,7 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
     try:
         matrix = _lib.DeviceArray.view(sets.train.ptr, (sets.n_train, sets.train.shape[1]), np.float32, device)
         out = cross_validate(matrix, sets.train_target, parameters, n_folds=n_folds, groups=row_groups(fe.rows),
-                             seed=seed, refit=True, device=device, **cv_arguments)
+                             seed=seed, refit=True, device=device, init_model=init_model, **cv_arguments)
         if cover:
             mark = time.perf_counter()
             out.model.fit_cover_device(sets.train, sets.n_train)

@@ -11,7 +11,8 @@ It prints the fraction of correct final answers of that model next to a model tr
 top-k pairs of the train queries labelled with their known source row) and the random stand-in ensemble
 (synth.make_forest) that the other examples use.
 
-    python examples/train_model.py [--one-call] [--metrics auc,logloss] [n_truth] [n_queries] [top_n] [model.npz]
+    python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH] [n_truth] [n_queries]
+                                   [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
 --one-call trains with ds.train_model(...), the same steps in one call with the feature matrix kept in HBM; the model
@@ -19,6 +20,9 @@ is the same.
 --metrics prints the reference's per-round log line (xgboost's, with eval_metric 'auc' and the watch list train /
 evaluation): train-auc and evaluation-auc -- and train-logloss / evaluation-logloss, the objective's own loss -- next to
 the custom error, all computed on the device; the model is the same with and without it.
+--init-model PATH continues boosting from the ForestModel saved at PATH (an earlier run's model.npz) instead of
+starting from an empty forest: the new trees follow that model's, and the evaluation error of the init model is
+printed next to the best new round's.
 """
 import os
 import sys
@@ -57,7 +61,11 @@ def print_rounds(metrics_history, history):
         print(f"[{round_}]\t" + "\t".join(parts))
 
 
-def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=()):
+def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None):
+    init = ds.ForestModel.load(init_model) if init_model else None
+    init_trees = init.n_trees if init else 0
+    if init:
+        print(f"continuing from {init_model}: {init_trees} trees")
     train = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     evaluation = synth.make_workload(n_truth, n_queries // 4, seed=11, query_seed=102)
     held_out = synth.make_workload(n_truth, n_queries, seed=11, query_seed=103)
@@ -68,7 +76,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
     train_ids = np.where(train.actual_row >= 0, train.title_id[np.maximum(train.actual_row, 0)], -1)
     if one_call:
         t0 = time.perf_counter()
-        result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics))
+        result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics),
+                                init_model=init)
         t1 = time.perf_counter()
         model = result.model
         if metrics:
@@ -76,7 +85,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         kinds = result.rows["kind"].value_counts().sort_index().to_dict()
         print(f"train_model: {result.rows.shape[0]} rows (generated / negative / positive: {kinds.get(1, 0)} / "
               f"{kinds.get(2, 0)} / {kinds.get(3, 0)}), {len(result.history)} rounds in {t1 - t0:.2f}s in all, best "
-              f"round {result.best_iteration} (custom error {result.history[result.best_iteration]}); "
+              f"round {result.best_iteration} (custom error {result.history[result.best_iteration - init_trees]}"
+              + (f", init model {result.initial_error}" if init else "") + "); "
               + ", ".join(f"{k} {v:.1f} ms" for k, v in result.timings.items()))
         tp, tn, fp, fn = result.error_matrix
         print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
@@ -91,12 +101,14 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
               + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.timings.items()))
         t0 = time.perf_counter()
         trainer = ds.ForestTrainer()
-        model = trainer.fit(features, labels, eval_features, eval_labels, eval_metrics=tuple(metrics))
+        model = trainer.fit(features, labels, eval_features, eval_labels, eval_metrics=tuple(metrics), init_model=init)
         t1 = time.perf_counter()
         if metrics:
             print_rounds(trainer.metrics_history, trainer.history)
         print(f"training: {features.shape[0]} rows ({int(labels.sum())} positive), {len(trainer.trees)} rounds in "
-              f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error {trainer.history[trainer.best_iteration]})")
+              f"{t1 - t0:.2f}s, best round {trainer.best_iteration} (custom error "
+              f"{trainer.history[trainer.best_iteration - init_trees]}"
+              + (f", init model {trainer.initial_error}" if init else "") + ")")
         tp, tn, fp, fn = ds.evaluation_error_matrix(model, eval_features, eval_labels)
         print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
         top = np.argsort(-model.feature_importance())[:5]
@@ -127,4 +139,12 @@ if __name__ == "__main__":
             raise SystemExit("--metrics needs a comma-separated list drawn from auc,logloss")
         wanted = tuple(arguments[at + 1].split(","))
         del arguments[at:at + 2]
-    main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted)
+    init_path = None
+    if "--init-model" in arguments:
+        at = arguments.index("--init-model")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--init-model needs the path of a saved ForestModel")
+        init_path = arguments[at + 1]
+        del arguments[at:at + 2]
+    main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted,
+         init_model=init_path)

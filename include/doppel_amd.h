@@ -703,6 +703,40 @@ int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags);
 int ds_trainer_batch_metrics(ds_trainer_batch *batch, int64_t *out);
 int64_t ds_trainer_batch_metrics_bytes(int64_t n, int32_t n_models, int32_t n_folds);
 
+/* ---- continuing from a model: xgb.train(..., xgb_model=booster) ("Continuing from a model") -------
+ * ds_trainer_seed starts a trainer's margins from `forest` instead of from zero.  A trainer keeps only bins, and the
+ * forest's thresholds need not be cuts of this matrix, so the call takes the RAW float32[n][n_features] training matrix
+ * again (and the evaluation matrix, float32[n_eval][n_features], exactly when the trainer has an evaluation set): one
+ * kernel walks every tree of the forest per row by the rule of ds_forest_predict_device (NaN -> missing, else value <
+ * threshold) and writes the float32 sum of the leaves, from zero in tree order, as the row's leaf sum.  After the call
+ * the training margins are those of ds_forest_predict(forest, ...), bit for bit, every later ds_trainer_step grows the
+ * tree a trainer would grow that had grown the forest's trees itself, and the sampling tree number t of
+ * ds_trainer_set_sampling starts at the forest's tree count.  So k rounds, then a trainer seeded with those k trees and
+ * stepped m times, give exactly the trees of k + m rounds.
+ * *initial_error (nullable) = the custom error of the evaluation set at the seeded margins, -1 without an evaluation
+ * set; it comes back with the call's one host sync.
+ * Legal once per trainer, after ds_trainer_set_labels and ds_trainer_set_eval and before the first ds_trainer_step (the
+ * evaluation set can no longer be given afterwards).  The forest must live on the trainer's device, have its n_features
+ * and have base margin 0 (base_score 0.5), the trainer's own; its depth and tree count are free, zero trees are legal
+ * (the margins stay 0).  DS_E_ARG with a message, nothing launched and no state changed: a null pointer, a second call,
+ * a call after a step or before the labels, eval_features that does not go with the evaluation set, another device,
+ * feature count or base margin.  A host matrix is uploaded in chunks of at most 64 MiB; no second full copy is held.
+ * ds_trainer_seed_device: the same for matrices that lie complete in HBM; the kernels are enqueued on `stream`, which is
+ * synchronised before returning.  The matrices are not kept.
+ * ds_trainer_batch_seed(_device): the same for a batch.  The forest is evaluated once per row and the sum written to
+ * the leaf sums of all n_models models, held-out rows included; every model's tree count starts at the forest's.
+ * initial_errors int64[n_models] (nullable): the custom error of model m's held-out rows at the seeded margins, -1 for
+ * held_out[m] = -1.  Legal once, before the first ds_trainer_batch_step.
+ * A trainer or batch that is never seeded launches, allocates and copies exactly what it did before. */
+int ds_trainer_seed(ds_trainer *trainer, const ds_forest *forest, const float *features, const float *eval_features,
+                    int64_t *initial_error);
+int ds_trainer_seed_device(ds_trainer *trainer, const ds_forest *forest, const float *d_features,
+                           const float *d_eval_features, int64_t *initial_error, void *stream);
+int ds_trainer_batch_seed(ds_trainer_batch *batch, const ds_forest *forest, const float *features,
+                          int64_t *initial_errors);
+int ds_trainer_batch_seed_device(ds_trainer_batch *batch, const ds_forest *forest, const float *d_features,
+                                 int64_t *initial_errors, void *stream);
+
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
  * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
