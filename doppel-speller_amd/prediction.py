@@ -18,6 +18,7 @@ Differences from the reference, on purpose:
     (`_find_matches_using_model` is reached with no rows and `np.vstack([])` fails).
 """
 import collections
+import contextlib
 import ctypes
 import time
 import unicodedata
@@ -58,12 +59,20 @@ _ALLOWED = np.zeros(256, dtype=bool)          # the characters a transformed tit
 for _code, _character in enumerate(ALLOWED_CHARACTERS):
     _CODE_OF[ord(_character)] = _code
     _ALLOWED[ord(_character)] = _code != 0
+ALLOWED_CHARACTERS_BYTES = np.frombuffer(ALLOWED_CHARACTERS.encode("ascii"), dtype=np.uint8)      # code -> ASCII byte
+
+
+def _positive_integer(value, name, or_none=False):
+    """`value` as an int; a bool, another type or a value below 1 is refused by `name` (None passes with or_none)."""
+    if value is None and or_none:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"{name} must be a positive integer{' or None' if or_none else ''}, not {value!r}")
+    return int(value)
 
 
 def _validate_chunk(chunk_queries):
-    if chunk_queries is not None and (isinstance(chunk_queries, bool) or not isinstance(chunk_queries, (int, np.integer))
-                                      or chunk_queries <= 0):
-        raise ValueError(f"chunk_queries must be a positive integer or None, not {chunk_queries!r}")
+    _positive_integer(chunk_queries, "chunk_queries", or_none=True)
 
 
 def validate_truth(truth_titles, truth_title_ids, top_n):
@@ -78,9 +87,7 @@ def validate_truth(truth_titles, truth_title_ids, top_n):
         raise ValueError("truth title ids must be non-negative (-1 is the 'not found' answer)")
     if np.unique(ids).shape[0] != ids.shape[0]:
         raise ValueError("truth title ids must be unique")
-    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or top_n < 1:
-        raise ValueError(f"top_n must be a positive integer, not {top_n!r}")
-    if top_n > ids.shape[0]:
+    if _positive_integer(top_n, "top_n") > ids.shape[0]:
         raise ValueError(f"top_n = {top_n} exceeds the {ids.shape[0]} truth titles")
     return ids
 
@@ -102,11 +109,30 @@ def validate_queries(titles, test_index):
 
 def validate_rank(n, top_n):
     """ranked_matches' check of `n` (no library needed): a positive integer up to the top_n candidates of a query."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-        raise ValueError(f"n must be a positive integer, not {n!r}")
-    if n > top_n:
+    if _positive_integer(n, "n") > top_n:
         raise ValueError(f"n = {n} exceeds the top_n = {top_n} candidates of a title")
     return int(n)
+
+
+def title_ids_of(rows, truth_title_ids):
+    """int64: the title id of every truth row of `rows`, -1 (TRAIN_NOT_FOUND_VALUE) where the row is -1."""
+    rows = np.asarray(rows, dtype=np.int64)
+    title_id = np.full(rows.shape[0], TRAIN_NOT_FOUND_VALUE, dtype=np.int64)
+    title_id[rows >= 0] = np.asarray(truth_title_ids, dtype=np.int64)[rows[rows >= 0]]
+    return title_id
+
+
+def _filled_slots(test_index, filled):
+    """(query, slot) of the true entries of `filled` [Q, n] in the order of a long frame: by test index, then slot."""
+    query, slot = np.nonzero(filled)
+    order = np.argsort(test_index[query], kind="stable")
+    return query[order], slot[order]
+
+
+def _rank_slots(count, n):
+    """The unfilled [count, n] slots of the rank stage: rows, probabilities, ratios, stages."""
+    return (np.full((count, n), -1, dtype=np.int32), np.full((count, n), np.nan, dtype=np.float32),
+            np.zeros((count, n), dtype=np.uint8), np.zeros((count, n), dtype=np.int8))
 
 
 def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_ids):
@@ -114,9 +140,7 @@ def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_id
     test_index, then rank (slot + 1: the filled slots of a query come first)."""
     import pandas as pd
     test_index = np.asarray(test_index, dtype=np.int64)
-    query, slot = np.nonzero(np.asarray(stages) != STAGE_NONE)
-    order = np.argsort(test_index[query], kind="stable")
-    query, slot = query[order], slot[order]
+    query, slot = _filled_slots(test_index, np.asarray(stages) != STAGE_NONE)
     match_row = np.asarray(rows)[query, slot].astype(np.int64)
     return pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
                          "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
@@ -127,9 +151,7 @@ def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_id
 
 def validate_exhaustive(n, n_truth):
     """exhaustive_matches' check of `n` (no library needed): a positive integer up to 64 and up to the truth titles."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-        raise ValueError(f"n must be a positive integer, not {n!r}")
-    if n > min(EXHAUSTIVE_MAX_N, n_truth):
+    if _positive_integer(n, "n") > min(EXHAUSTIVE_MAX_N, n_truth):
         raise ValueError(f"n = {n} exceeds the smaller of {EXHAUSTIVE_MAX_N} and the {n_truth} truth titles")
     return int(n)
 
@@ -154,9 +176,7 @@ def exhaustive_frame(test_index, rows, probabilities, top_rows, truth_title_ids)
     test_index = np.asarray(test_index, dtype=np.int64)
     rows = np.asarray(rows)
     positions = jaccard_positions(rows, top_rows)
-    query, slot = np.nonzero(rows >= 0)
-    order = np.argsort(test_index[query], kind="stable")
-    query, slot = query[order], slot[order]
+    query, slot = _filled_slots(test_index, rows >= 0)
     match_row = rows[query, slot].astype(np.int64)
     return pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
                          "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
@@ -319,12 +339,9 @@ def assignment_frame(test_index, match_row, match_slot, first_row, rows, probabi
     import pandas as pd
     match_row, match_slot = np.asarray(match_row, dtype=np.int64), np.asarray(match_slot, dtype=np.int64)
     first_row = np.asarray(first_row, dtype=np.int64)
-    ids = np.asarray(truth_title_ids, dtype=np.int64)
     count = match_row.shape[0]
     found = match_row >= 0
     query, slot = np.nonzero(found)[0], match_slot[found]
-    title_id = np.full(count, TRAIN_NOT_FOUND_VALUE, dtype=np.int64)
-    title_id[found] = ids[match_row[found]]
     stage = np.zeros(count, dtype=np.int8)
     probability = np.full(count, np.nan, dtype=np.float32)
     ratio = np.zeros(count, dtype=np.uint8)
@@ -335,7 +352,8 @@ def assignment_frame(test_index, match_row, match_slot, first_row, rows, probabi
         probability[found] = np.asarray(probabilities, dtype=np.float32)[query, slot]
         ratio[found] = np.asarray(ratios, dtype=np.uint8)[query, slot]
     return pd.DataFrame({"test_index": np.asarray(test_index, dtype=np.int64), "match_row": match_row,
-                         "title_id": title_id, "stage": stage, "probability": probability, "levenshtein_ratio": ratio,
+                         "title_id": title_ids_of(match_row, truth_title_ids), "stage": stage,
+                         "probability": probability, "levenshtein_ratio": ratio,
                          "rank": np.where(found, match_slot + 1, 0).astype(np.int64), "first_choice_row": first_row,
                          "displaced": (first_row >= 0) & (match_row != first_row)}, columns=list(ASSIGNMENT_COLUMNS))
 
@@ -346,9 +364,8 @@ def top_contributions(contributions, n=5):
     contributions = np.asarray(contributions, dtype=np.float64)
     if contributions.ndim != 2:
         raise ValueError(f"contributions must be a [Q, F] matrix, not shape {contributions.shape}")
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-        raise ValueError(f"n must be a positive integer, not {n!r}")
-    order = np.argsort(-np.abs(contributions), axis=1, kind="stable")[:, :min(int(n), contributions.shape[1])]
+    n = _positive_integer(n, "n")
+    order = np.argsort(-np.abs(contributions), axis=1, kind="stable")[:, :min(n, contributions.shape[1])]
     return order.astype(np.int64), np.take_along_axis(contributions, order, axis=1)
 
 
@@ -380,11 +397,7 @@ def finalize_output(test_index, match_row, truth_title_ids):
     title_id = the matched truth row's id or -1."""
     import pandas as pd
     test_index = np.asarray(test_index, dtype=np.int64)
-    match_row = np.asarray(match_row, dtype=np.int64)
-    ids = np.asarray(truth_title_ids, dtype=np.int64)
-    title_id = np.full(match_row.shape[0], TRAIN_NOT_FOUND_VALUE, dtype=np.int64)
-    found = match_row >= 0
-    title_id[found] = ids[match_row[found]]
+    title_id = title_ids_of(match_row, truth_title_ids)
     order = np.argsort(test_index, kind="stable")
     return pd.DataFrame({"title_id": title_id[order], "test_index": test_index[order]}).reset_index(drop=True)
 
@@ -448,9 +461,6 @@ class DeviceTitles:
             pass
 
 
-ALLOWED_CHARACTERS_BYTES = np.frombuffer(ALLOWED_CHARACTERS.encode("ascii"), dtype=np.uint8)
-
-
 def prepare_queries(titles, transform, device=0):
     """The query table of `titles` made on the device: transform_titles (when `transform`) and encode_collection in one
     kernel (ds_prepare_titles), with the host path's checks and errors, in its order: a non-ASCII title without
@@ -512,11 +522,16 @@ class QuerySpace:
             pass
 
 
-def default_chunk(device, bytes_per_query):
-    """Queries per device pass: what a quarter of the device's free HBM holds at `bytes_per_query`."""
+def free_bytes(device):
+    """The free HBM of the device now."""
     free, total = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.check(_lib.lib().ds_device_memory(device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
-    return max(1, int(free.value // 4 // bytes_per_query))
+    return int(free.value)
+
+
+def default_chunk(device, bytes_per_query):
+    """Queries per device pass: what a quarter of the device's free HBM holds at `bytes_per_query`."""
+    return max(1, free_bytes(device) // 4 // bytes_per_query)
 
 
 def column_table(vocabulary_keys):
@@ -594,6 +609,36 @@ class TruthSide:
         return query_rows(chars, offsets, self.vocabulary_keys, self.idf32, self.idf64, columns=self.columns)
 
 
+class StageClock:
+    """The milliseconds of a call's stages, added to `timings` by name: a device stage between the two events of a
+    _lib.Timer of its own (made when the stage first runs: one that never runs keeps its 0.0), a host stage by the wall
+    clock."""
+
+    def __init__(self, timings, device=0):
+        self.timings, self._device, self._timers, self._pending = timings, device, {}, []
+
+    def device(self, name, enqueue):
+        """Runs enqueue() between the events of stage `name` on the null stream; `collect` reads the time."""
+        if name not in self._timers:
+            self._timers[name] = _lib.Timer(self._device)
+        self._timers[name].start()
+        enqueue()
+        self._timers[name].stop()
+        self._pending.append(name)
+
+    def collect(self):
+        """Adds the time of every stage run since the last collect, in their order (each read waits for the stage)."""
+        pending, self._pending = self._pending, []
+        for name in pending:
+            self.timings[name] += self._timers[name].elapsed_ms()
+
+    @contextlib.contextmanager
+    def host(self, name):
+        started = time.perf_counter()
+        yield
+        self.timings[name] += (time.perf_counter() - started) * 1000.0
+
+
 class Prediction:
     """Prediction(truth_titles, truth_title_ids, model).generate_test_predictions(titles) -> the reference's
     final_output: a DataFrame [title_id, test_index] sorted by test_index, -1 where no stage found a match.
@@ -638,19 +683,10 @@ class Prediction:
         self.assignment_counts = None
         self.timings = {}
 
-        self.truth_titles = self._transform(truth_titles)
-        truth = TruthSide(self.truth_titles, device, build_index=build_index)
-        self.index_build_ms = truth.index_build_ms
-        self._vocabulary_keys, self._idf32, self._idf64 = truth.vocabulary_keys, truth.idf32, truth.idf64
-        self._columns, self.index, self.truth_table = truth.columns, truth.index, truth.table
-        self._space = truth.space
-
-    def _transform(self, titles):
-        return transform_or_keep(titles, self.transform)
-
-    @staticmethod
-    def _check_characters(chars, offsets, what):
-        check_characters(chars, offsets, what)
+        self.truth_titles = transform_or_keep(truth_titles, transform)
+        self._truth = TruthSide(self.truth_titles, device, build_index=build_index)
+        self.index, self.truth_table = self._truth.index, self._truth.table
+        self.index_build_ms = self._truth.index_build_ms
 
     def _default_chunk(self, device_rows=False, rank_slots=0, parts=False, explain=False):
         # device_rows: the pipeline's own query CSR at capacity (rowptr, 253 columns, q_maxint per query)
@@ -713,12 +749,9 @@ class Prediction:
         timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model", "rank",
                                  "copy_back"), 0.0)
         count, k = len(titles), self.top_n
-        slots = (np.full((count, n), -1, dtype=np.int32), np.full((count, n), np.nan, dtype=np.float32),
-                 np.zeros((count, n), dtype=np.uint8), np.zeros((count, n), dtype=np.int8))
         kept = Candidates(np.empty((count, k), np.int32), np.empty((count, k), np.uint8), np.empty((count, k), np.float32),
                           np.empty(count, np.int32), np.empty(count, np.int32)) if keep_candidates else None
-        for pipeline, events in self._chunks(titles, timings, rank_slots=n):
-            self._rank_chunk(pipeline, events, timings, n, slots, kept)
+        slots, _ = self._rank(titles, timings, n, kept)
         self.timings = timings
         self.candidates = kept
         return ranked_frame(test_index, *slots, self.truth_title_ids)
@@ -757,40 +790,32 @@ class Prediction:
         timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model", "rank",
                                  "assign_edges", "assign", "copy_back"), 0.0)
         count, n_truth = len(titles), len(self.truth_titles)
-        slots = (np.full((count, n), -1, dtype=np.int32), np.full((count, n), np.nan, dtype=np.float32),
-                 np.zeros((count, n), dtype=np.uint8), np.zeros((count, n), dtype=np.int8))
         outputs = tuple(np.full(count, -1, dtype=np.int32) for _ in range(3))
         counts = np.zeros(len(ASSIGNMENT_COUNTS), dtype=np.int64)
         if count:
-            needed = assignment_bytes(count, n, n_truth)
-            free, total = ctypes.c_int64(0), ctypes.c_int64(0)
-            _lib.check(_lib.lib().ds_device_memory(self.device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
-            if needed + ASSIGN_RESERVE_BYTES > free.value:
+            needed, free = assignment_bytes(count, n, n_truth), free_bytes(self.device)
+            if needed + ASSIGN_RESERVE_BYTES > free:
                 raise _lib.DoppelError(f"one_to_one_matches: {count} titles of {n} slots against {n_truth} truth titles "
-                                       f"need {needed} bytes of HBM, {free.value} are free")
+                                       f"need {needed} bytes of HBM, {free} are free")
             make = lambda shape, dtype: _lib.DeviceArray(shape, dtype, self.device)
             keys, rows = make((count, n), np.uint64), make((count, n), np.int32)
             held, standing = make((max(n_truth, 1),), np.uint64), make((count,), np.int32)
             device_outputs = tuple(make((count,), np.int32) for _ in range(3))
             device_counts = make((len(ASSIGNMENT_COUNTS),), np.int64)
-        for pipeline, events in self._chunks(titles, timings, rank_slots=n):
-            self._rank_chunk(pipeline, events, timings, n, slots, None)
+
+        def edges(pipeline, clock):
             # 8. the keys of this chunk's slots into the call-wide arrays (the ranked buffers still hold the chunk)
-            events["assign_edges"].start()
-            pipeline.enqueue_assign_edges(keys, rows, threshold)
-            events["assign_edges"].stop()
-            timings["assign_edges"] += events["assign_edges"].elapsed_ms()
-            last_events = events
+            clock.device("assign_edges", lambda: pipeline.enqueue_assign_edges(keys, rows, threshold))
+            clock.collect()
+
+        slots, clock = self._rank(titles, timings, n, tail=edges)
         if count:
-            last_events["assign"].start()
-            _lib.check(_lib.lib().ds_assign_solve_device(
+            clock.device("assign", lambda: _lib.check(_lib.lib().ds_assign_solve_device(
                 rows.ptr, keys.ptr, count, n, n_truth, held.ptr, standing.ptr, *(a.ptr for a in device_outputs),
-                device_counts.ptr, _lib.pointer(None)), "ds_assign_solve_device")
-            last_events["assign"].stop()
-            copy_started = time.perf_counter()
-            outputs, counts = tuple(a.to_host() for a in device_outputs), device_counts.to_host()
-            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
-            timings["assign"] = last_events["assign"].elapsed_ms()
+                device_counts.ptr, _lib.pointer(None)), "ds_assign_solve_device"))
+            with clock.host("copy_back"):
+                outputs, counts = tuple(a.to_host() for a in device_outputs), device_counts.to_host()
+            clock.collect()
         self.timings = timings
         self.assignment = assignment_frame(test_index, *outputs, *slots, self.truth_title_ids)
         self.assignment_counts = dict(zip(ASSIGNMENT_COUNTS, (int(c) for c in counts)))
@@ -815,21 +840,14 @@ class Prediction:
         rows = np.full((count, n), -1, dtype=np.int32)
         probabilities = np.full((count, n), np.nan, dtype=np.float32)
         top_rows = np.full((count, self.top_n), -1, dtype=np.int32)
-        for pipeline, events in self._chunks(titles, timings):
+        for pipeline, clock in self._chunks(titles, timings):
             first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
-            events["top_k"].start()
-            pipeline.enqueue_top_k()
-            events["top_k"].stop()
-            pipeline.sync()
-            events["exhaustive"].start()
-            pipeline.enqueue_exhaustive(self.model, n)
-            events["exhaustive"].stop()
-            copy_started = time.perf_counter()
-            rows[first:last], probabilities[first:last] = pipeline.exhaustive(n)
-            top_rows[first:last] = pipeline.rows()
-            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
-            for name in ("top_k", "exhaustive"):
-                timings[name] += events[name].elapsed_ms()
+            self._top_k(pipeline, clock)
+            clock.device("exhaustive", lambda: pipeline.enqueue_exhaustive(self.model, n))
+            with clock.host("copy_back"):
+                rows[first:last], probabilities[first:last] = pipeline.exhaustive(n)
+                top_rows[first:last] = pipeline.rows()
+            clock.collect()
         self.timings = timings
         return exhaustive_frame(test_index, rows, probabilities, top_rows, self.truth_title_ids)
 
@@ -862,31 +880,16 @@ class Prediction:
         stage = np.zeros(count, dtype=np.int8)
         features = np.empty((count, width), dtype=np.float32)
         contributions = np.empty((count, width + 1), dtype=np.float64)
-        for pipeline, events in self._chunks(titles, timings, explain=True):
+        for pipeline, clock in self._chunks(titles, timings, explain=True):
             first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
-
-            def timed(name, enqueue):
-                events[name].start()
-                enqueue()
-                events[name].stop()
-
-            # 1. Jaccard top-k (synchronised, as in _chunk)
-            timed("top_k", pipeline.enqueue_top_k)
-            pipeline.sync()
-            # 2. close matches, 3. the exact stage, 4. features and 5. the forest on ALL pairs, 6. the best pair per
-            # query, its features gathered, its margin and its contributions
-            timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=self.levenshtein_threshold))
-            timed("exact_matches", pipeline.enqueue_exact_matches)
-            timed("features", pipeline.enqueue_features)
-            timed("model", lambda: pipeline.enqueue_predict(self.model))
-            timed("contributions", lambda: pipeline.enqueue_explain(self.model, approximate))
+            # 1.-5. every pair scored, 6. the best pair per query, its features gathered, its margin and its contributions
+            self._score_chunk(pipeline, clock, self.levenshtein_threshold)
+            clock.device("contributions", lambda: pipeline.enqueue_explain(self.model, approximate))
             # 7. one copy back of one pair per query (synchronises the null stream the stages ran on)
-            copy_started = time.perf_counter()
-            rows, best, held, margins, features[first:last], contributions[first:last] = pipeline.explained()
-            exact, close = pipeline.exact_matches(), pipeline.best_rows()
-            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
-            for name in ("top_k", "close_matches", "exact_matches", "features", "model", "contributions"):
-                timings[name] += events[name].elapsed_ms()
+            with clock.host("copy_back"):
+                rows, best, held, margins, features[first:last], contributions[first:last] = pipeline.explained()
+                exact, close = pipeline.exact_matches(), pipeline.best_rows()
+            clock.collect()
             # the answer of generate_test_predictions: the model matches only with a single best pair above the threshold
             model_row = np.where((best > np.float32(self.probability_threshold)) & (held == 1), rows, -1)
             answer_row[first:last], stage[first:last] = combine_stages(exact, np.where(exact >= 0, -1, close), model_row)
@@ -921,15 +924,20 @@ class Prediction:
                                  "copy_back"), 0.0)
         counts = np.zeros(lev.shape[0] * prob.shape[0] * 4, dtype=np.int64)
         grid = None
-        for pipeline, events in self._chunks(titles, timings, parts=True):
+        for pipeline, clock in self._chunks(titles, timings, parts=True):
             if grid is None:
                 grid = (_lib.DeviceArray.from_host(lev, self.device), _lib.DeviceArray.from_host(prob, self.device),
                         _lib.DeviceArray.from_host(counts, self.device))
-            self._sweep_chunk(pipeline, events, timings, int(lev[0]), int(lev[-1]), actual_row, grid)
+            actual = _lib.DeviceArray.from_host(actual_row[pipeline.q_first:pipeline.q_first + pipeline.n_queries],
+                                                self.device)
+            # 1.-5. every pair scored with the close ratio taken apart, 6. the rule replayed per cell (the sweep entry
+            # synchronises once, to check the grid's values)
+            self._score_chunk(pipeline, clock, parts=(int(lev[0]), int(lev[-1])))
+            clock.device("sweep", lambda: pipeline.enqueue_threshold_sweep(actual, *grid))
+            clock.collect()
         if grid is not None:
-            copy_started = time.perf_counter()
-            counts = grid[2].to_host()                # synchronises the null stream the stages ran on
-            timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+            with clock.host("copy_back"):
+                counts = grid[2].to_host()            # synchronises the null stream the stages ran on
         self.timings = timings
         return sweep_frame(lev, shown, counts)
 
@@ -964,79 +972,35 @@ class Prediction:
                                         self.probability_threshold if probability_threshold is None else probability_threshold)
         timings = dict.fromkeys(("host_prepare", "prepare_queries", "top_k", "close_matches", "exact_matches", "features",
                                  "model", "links", "finish", "copy_back"), 0.0)
-        started = time.perf_counter()
         n = len(self.truth_titles)
-        chunk = min(n, self.chunk_queries or self._default_chunk(device_rows=True))
-        pipeline = CandidatePipeline.over(self.index, self.truth_table, self.truth_table, self.top_n, chunk, self.device)
-        parent, counts = _lib.DeviceArray((n,), np.int32, self.device), _lib.DeviceArray((3,), np.int64, self.device)
-        labels, sizes = _lib.DeviceArray((n,), np.int32, self.device), _lib.DeviceArray((n,), np.int32, self.device)
-        _lib.check(_lib.lib().ds_duplicate_begin_device(parent.ptr, n, counts.ptr, _lib.pointer(None)),
-                   "ds_duplicate_begin_device")
-        events = {name: _lib.Timer(self.device) for name in timings if name not in ("host_prepare", "copy_back")}
-        timings["host_prepare"] = (time.perf_counter() - started) * 1000.0
-        stages = ["close_matches", "exact_matches"] + (["features", "model"] if model_links else []) + ["links"]
-        kept = []
-
-        def timed(name, enqueue):
-            events[name].start()
-            enqueue()
-            events[name].stop()
-
-        for first in range(0, n, chunk):
-            timed("prepare_queries", lambda: pipeline.load_queries_device(self._space, first, min(n, first + chunk)))
-            # 1. Jaccard top-k (synchronised, as in _chunk)
-            timed("top_k", pipeline.enqueue_top_k)
-            pipeline.sync()
-            # 2. close matches, 3. the exact stage, 4. features and 5. the forest on ALL pairs, 6. the links
-            timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=lev))
-            timed("exact_matches", pipeline.enqueue_exact_matches)
-            if model_links:
-                timed("features", pipeline.enqueue_features)
-                timed("model", lambda: pipeline.enqueue_predict(self.model))
-            timed("links", lambda: pipeline.enqueue_duplicate_links(parent, counts, lev, prob, model_links,
-                                                                    reasons=return_links))
-            for name in ["prepare_queries", "top_k"] + stages:
-                timings[name] += events[name].elapsed_ms()
+        parent, kept = None, []
+        for pipeline, clock in self._chunks(None, timings, table=self.truth_table):      # the truth rows are the queries
+            if parent is None:
+                with clock.host("host_prepare"):
+                    make = lambda shape, dtype: _lib.DeviceArray(shape, dtype, self.device)
+                    parent, counts, labels, sizes = (make((n,), np.int32), make((3,), np.int64), make((n,), np.int32),
+                                                     make((n,), np.int32))
+                    _lib.check(_lib.lib().ds_duplicate_begin_device(parent.ptr, n, counts.ptr, _lib.pointer(None)),
+                               "ds_duplicate_begin_device")
+            # 1.-5. every pair scored (close and exact only without model_links), 6. the links
+            self._score_chunk(pipeline, clock, lev, score_all=model_links)
+            clock.device("links", lambda: pipeline.enqueue_duplicate_links(parent, counts, lev, prob, model_links,
+                                                                           reasons=return_links))
+            clock.collect()
             if return_links:
-                copy_started = time.perf_counter()
-                kept.append((first, pipeline.rows(), pipeline.close_matches()[0],
-                             pipeline.predictions() if model_links else None, pipeline.exact_matches(),
-                             pipeline.duplicate_reasons()))
-                timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
-        timed("finish", lambda: _lib.check(_lib.lib().ds_duplicate_finish_device(
+                with clock.host("copy_back"):
+                    kept.append((pipeline.q_first, pipeline.rows(), pipeline.close_matches()[0],
+                                 pipeline.predictions() if model_links else None, pipeline.exact_matches(),
+                                 pipeline.duplicate_reasons()))
+        clock.device("finish", lambda: _lib.check(_lib.lib().ds_duplicate_finish_device(
             parent.ptr, n, labels.ptr, sizes.ptr, _lib.pointer(None)), "ds_duplicate_finish_device"))
-        timings["finish"] = events["finish"].elapsed_ms()
-        copy_started = time.perf_counter()
-        host_labels, host_sizes, host_counts = labels.to_host(), sizes.to_host(), counts.to_host()
-        timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+        clock.collect()
+        with clock.host("copy_back"):
+            host_labels, host_sizes, host_counts = labels.to_host(), sizes.to_host(), counts.to_host()
         self.timings = timings
         self.link_counts = dict(zip(("exact", "close", "model"), (int(c) for c in host_counts)))
         self.links = links_frame(kept, self.truth_title_ids, n) if return_links else None
         return duplicate_frame(host_labels, host_sizes, self.truth_title_ids)
-
-    def _sweep_chunk(self, pipeline, events, timings, t_min, t_max, actual_row, grid):
-        first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
-        lev, prob, counts = grid
-
-        def timed(name, enqueue):
-            events[name].start()
-            enqueue()
-            events[name].stop()
-
-        # 1. Jaccard top-k (synchronised, as in _chunk)
-        timed("top_k", pipeline.enqueue_top_k)
-        pipeline.sync()
-        timings["top_k"] += events["top_k"].elapsed_ms()
-        # 2. the close ratio taken apart, 3. the exact stage, 4. features and 5. the forest on ALL pairs, 6. the rule
-        # replayed per cell (the sweep entry synchronises once, to check the grid's values)
-        actual = _lib.DeviceArray.from_host(actual_row[first:last], self.device)
-        timed("close_parts", lambda: pipeline.enqueue_close_parts(t_min, t_max))
-        timed("exact_matches", pipeline.enqueue_exact_matches)
-        timed("features", pipeline.enqueue_features)
-        timed("model", lambda: pipeline.enqueue_predict(self.model))
-        timed("sweep", lambda: pipeline.enqueue_threshold_sweep(actual, lev, prob, counts))
-        for name in ("close_parts", "exact_matches", "features", "model", "sweep"):
-            timings[name] += events[name].elapsed_ms()
 
     def _run(self, titles, test_index, single=False):
         import pandas as pd
@@ -1046,123 +1010,115 @@ class Prediction:
         match_row = np.full(n, -1, dtype=np.int64)
         stage = np.zeros(n, dtype=np.int8)
         probability = np.full(n, np.nan, dtype=np.float32)
-        for pipeline, events in self._chunks(titles, timings):
-            self._chunk(pipeline, events, timings, match_row, stage, probability, single)
-        title_id = np.where(match_row >= 0, self.truth_title_ids[np.maximum(match_row, 0)], TRAIN_NOT_FOUND_VALUE)
+        for pipeline, clock in self._chunks(titles, timings):
+            self._chunk(pipeline, clock, match_row, stage, probability, single)
         self.timings = timings
-        return pd.DataFrame({"test_index": test_index, "match_row": match_row, "title_id": title_id, "stage": stage,
+        return pd.DataFrame({"test_index": test_index, "match_row": match_row,
+                             "title_id": title_ids_of(match_row, self.truth_title_ids), "stage": stage,
                              "probability": probability})
 
-    def _chunks(self, titles, timings, rank_slots=0, parts=False, explain=False):
+    def _chunks(self, titles, timings, rank_slots=0, parts=False, explain=False, table=None):
         """The one loop over the queries: prepares the titles (on the device or on the host), then yields (pipeline,
-        events) with each chunk loaded in turn, events holding one Timer per device stage of `timings`.  Fills
-        timings' host_prepare and prepare_queries; yields nothing for no titles."""
-        device_path = self.prepare_queries == "device"
+        clock) with each chunk loaded in turn, clock being the call's StageClock on `timings`.  Fills timings'
+        host_prepare and prepare_queries (a chunk's query rows stay pending on the clock, so the host goes on to enqueue
+        top-k while they are derived: `_top_k` reads them); yields nothing for no titles.
+        table: a query table made already (then `titles` is not looked at): its rows are derived on the device whatever
+        `prepare_queries` says."""
+        device_path = table is not None or self.prepare_queries == "device"
         if device_path:
             timings["prepare_queries"] = 0.0
         started = time.perf_counter()
-        n = len(titles)
-        if device_path:
-            self._last_queries = None
+        n = len(titles) if table is None else table.n
+        if table is None and device_path:
+            self._last_queries = table = prepare_queries(titles, self.transform, self.device) if n else None
             if n:
-                query_table = prepare_queries(titles, self.transform, self.device)
-                timings["prepare_queries"] = query_table.prepare_ms
-                self._last_queries = query_table
-        else:
-            queries = self._transform(titles)
-            self._last_queries = queries
+                timings["prepare_queries"] = table.prepare_ms
+        elif table is None:
+            self._last_queries = queries = transform_or_keep(titles, self.transform)
         if n == 0:
             return
         if not device_path:
             chars, offsets = _pack(queries)
-            self._check_characters(chars, offsets, "query")
-            q_rowptr, q_cols, q_maxint = query_rows(chars, offsets, self._vocabulary_keys, self._idf32, self._idf64,
-                                                   columns=self._columns)
+            check_characters(chars, offsets, "query")
+            q_rowptr, q_cols, q_maxint = self._truth.query_rows(chars, offsets)
             enc, lengths = encode_collection(chars, offsets, _CODE_OF)
-            query_table = TitleTable(enc, lengths, None, self.device)
+            table = TitleTable(enc, lengths, None, self.device)
         chunk = min(n, self.chunk_queries or self._default_chunk(device_path, rank_slots, parts, explain))
-        pipeline = CandidatePipeline.over(self.index, self.truth_table, query_table, self.top_n, chunk, self.device)
+        pipeline = CandidatePipeline.over(self.index, self.truth_table, table, self.top_n, chunk, self.device)
         timings["host_prepare"] = (time.perf_counter() - started) * 1000.0 - timings.get("prepare_queries", 0.0)
-        events = {name: _lib.Timer(self.device) for name in timings
-                  if name not in ("host_prepare", "copy_back")}
+        clock = StageClock(timings, self.device)
         for first in range(0, n, chunk):
             last = min(n, first + chunk)
             if device_path:
-                events["prepare_queries"].start()
-                pipeline.load_queries_device(self._space, first, last)
-                events["prepare_queries"].stop()
-                timings["prepare_queries"] += events["prepare_queries"].elapsed_ms()
+                clock.device("prepare_queries", lambda: pipeline.load_queries_device(self._truth.space, first, last))
             else:
                 pipeline.load_queries(q_rowptr, q_cols, q_maxint, first, last)
-            yield pipeline, events
+            yield pipeline, clock
 
-    def _rank_chunk(self, pipeline, events, timings, n, slots, kept):
-        first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
-
-        def timed(name, enqueue):
-            events[name].start()
-            enqueue()
-            events[name].stop()
-
-        # 1. Jaccard top-k (synchronised, as in _chunk)
-        timed("top_k", pipeline.enqueue_top_k)
+    def _top_k(self, pipeline, clock):
+        """Jaccard top-k, synchronised (ds_jaccard_sync reports errors and settles the queries it resolves late); its
+        time and that of the chunk's query rows are read once it is through."""
+        clock.device("top_k", pipeline.enqueue_top_k)
         pipeline.sync()
-        timings["top_k"] += events["top_k"].elapsed_ms()
-        # 2. close matches, 3. the exact stage overrides their best row, 4. features and 5. the forest on ALL pairs,
-        # 6. the best n per query in order
-        timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=self.levenshtein_threshold))
-        timed("exact_matches", pipeline.enqueue_exact_matches)
-        timed("features", pipeline.enqueue_features)
-        timed("model", lambda: pipeline.enqueue_predict(self.model))
-        timed("rank", lambda: pipeline.enqueue_rank_matches(n))
+        clock.collect()
 
-        # 7. one copy back of n entries per query (synchronises the null stream the stages ran on)
-        copy_started = time.perf_counter()
-        for out, chunk in zip(slots, pipeline.ranked(n)):
-            out[first:last] = chunk
-        if kept is not None:
-            exact, best = pipeline.exact_matches(), pipeline.best_rows()
-            kept.rows[first:last] = pipeline.rows()
-            kept.ratios[first:last] = pipeline.close_matches()[0]
-            kept.probabilities[first:last] = pipeline.predictions()
-            kept.exact[first:last] = exact
-            kept.close[first:last] = np.where(exact >= 0, -1, best)
-        timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
-        for name in ("close_matches", "exact_matches", "features", "model", "rank"):
-            timings[name] += events[name].elapsed_ms()
+    def _score_chunk(self, pipeline, clock, levenshtein_threshold=None, parts=None, score_all=True):
+        """The stages every scoring call starts a chunk with: 1. Jaccard top-k (synchronised), 2. close matches at the
+        threshold (or, with parts = (t_min, t_max), the close ratio taken apart), 3. the exact stage overrides their
+        best row and, with score_all, 4. features and 5. the forest on ALL pairs.  All but top-k stay pending on the
+        clock."""
+        self._top_k(pipeline, clock)
+        if parts is None:
+            clock.device("close_matches", lambda: pipeline.enqueue_close_matches(threshold=levenshtein_threshold))
+        else:
+            clock.device("close_parts", lambda: pipeline.enqueue_close_parts(*parts))
+        clock.device("exact_matches", pipeline.enqueue_exact_matches)
+        if score_all:
+            clock.device("features", pipeline.enqueue_features)
+            clock.device("model", lambda: pipeline.enqueue_predict(self.model))
 
-    def _chunk(self, pipeline, events, timings, match_row, stage, probability, single):
+    def _rank(self, titles, timings, n, kept=None, tail=None):
+        """The device work of ranked_matches, which one_to_one_matches shares: per chunk every pair scored, 6. the best n
+        per query in order, 7. one copy back into the [Q, n] slots (and into `kept`), then tail(pipeline, clock) while
+        the ranked buffers still hold the chunk.  -> (slots, the call's clock: None without titles)."""
+        slots, clock = _rank_slots(len(titles), n), None
+        for pipeline, clock in self._chunks(titles, timings, rank_slots=n):
+            first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
+            self._score_chunk(pipeline, clock, self.levenshtein_threshold)
+            clock.device("rank", lambda: pipeline.enqueue_rank_matches(n))
+            with clock.host("copy_back"):       # n entries per query (synchronises the null stream the stages ran on)
+                for out, chunk in zip(slots, pipeline.ranked(n)):
+                    out[first:last] = chunk
+                if kept is not None:
+                    exact, best = pipeline.exact_matches(), pipeline.best_rows()
+                    kept.rows[first:last] = pipeline.rows()
+                    kept.ratios[first:last] = pipeline.close_matches()[0]
+                    kept.probabilities[first:last] = pipeline.predictions()
+                    kept.exact[first:last] = exact
+                    kept.close[first:last] = np.where(exact >= 0, -1, best)
+            clock.collect()
+            if tail is not None:
+                tail(pipeline, clock)
+        return slots, clock
+
+    def _chunk(self, pipeline, clock, match_row, stage, probability, single):
         k, first, n = self.top_n, pipeline.q_first, pipeline.n_queries
         last = first + n
-
-        def timed(name, enqueue):
-            events[name].start()
-            enqueue()
-            events[name].stop()
-
-        # 1. Jaccard top-k (synchronised: ds_jaccard_sync reports errors and settles the queries it resolves late)
-        timed("top_k", pipeline.enqueue_top_k)
-        pipeline.sync()
-        timings["top_k"] += events["top_k"].elapsed_ms()
-        # 2. close matches, 3. the exact stage overrides their best row, 4. the pairs of the queries still unmatched
-        timed("close_matches", lambda: pipeline.enqueue_close_matches(threshold=self.levenshtein_threshold))
-        timed("exact_matches", pipeline.enqueue_exact_matches)
-        timed("remaining_pairs", pipeline.enqueue_remaining_pairs)
+        # 1. top-k, 2. close matches, 3. the exact stage, 4. the pairs of the queries still unmatched
+        self._score_chunk(pipeline, clock, self.levenshtein_threshold, score_all=False)
+        clock.device("remaining_pairs", pipeline.enqueue_remaining_pairs)
         n_remaining, n_pairs = pipeline.remaining_counts()
         # 5. features of the remaining pairs, 6. the forest, 7. one match per remaining query
-        timed("features", lambda: pipeline.enqueue_features_remaining(n_pairs))
-        timed("model", lambda: pipeline.enqueue_predict(self.model, n_pairs=n_pairs))
-        timed("select_matches", lambda: pipeline.enqueue_select_matches(n_remaining, self.probability_threshold))
-        for name in ("close_matches", "exact_matches", "remaining_pairs", "features", "model", "select_matches"):
-            timings[name] += events[name].elapsed_ms()
+        clock.device("features", lambda: pipeline.enqueue_features_remaining(n_pairs))
+        clock.device("model", lambda: pipeline.enqueue_predict(self.model, n_pairs=n_pairs))
+        clock.device("select_matches", lambda: pipeline.enqueue_select_matches(n_remaining, self.probability_threshold))
+        clock.collect()
 
-        # one copy back of the per-query results
-        copy_started = time.perf_counter()
-        exact = pipeline.exact_matches()
-        best = pipeline.best_rows()            # exact rows where they exist, else the close step's best row
-        match_query, model_rows = pipeline.matches(n_remaining)
-        predictions = pipeline.predictions(n_pairs).reshape(n_remaining, k)
-        timings["copy_back"] += (time.perf_counter() - copy_started) * 1000.0
+        with clock.host("copy_back"):          # one copy back of the per-query results
+            exact = pipeline.exact_matches()
+            best = pipeline.best_rows()        # exact rows where they exist, else the close step's best row
+            match_query, model_rows = pipeline.matches(n_remaining)
+            predictions = pipeline.predictions(n_pairs).reshape(n_remaining, k)
 
         close = np.where(exact >= 0, -1, best)
         model = np.full(n, -1, dtype=np.int32)
