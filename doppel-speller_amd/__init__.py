@@ -26,7 +26,8 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
     predictions_accuracy(predicted_title_ids, actual_title_ids)   -> the same counts from two id arrays
     ForestModel.fit_cover(rows) / set_cover(cover) / predict_contributions(rows)   -> node cover and per-feature
         contributions of a model (xgboost's pred_contribs / approx_contribs)
-    ForestTrainer().fit(features, target, eval_features, eval_target)   -> ForestModel (train.py)
+    ForestTrainer().fit(features, target, eval_features, eval_target, **parameters)   -> ForestModel (train.py; the
+        booster parameters by keyword: train.validate_parameters)
     FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids)
         .generate_train_and_evaluation_data_sets()   -> (train, train_target, evaluation, evaluation_target)
     train_model(truth_titles, truth_title_ids, train_titles, train_title_ids)   -> model, feature importances, the

@@ -183,26 +183,34 @@ def metrics_option(name, value):
     _lib.check(_lib.lib().ds_metrics_option(name.encode(), int(value)), "ds_metrics_option")
 
 
+def _scores(values, what, non_empty=False):
+    """The scores of auc_counts / margins of logloss_counts, checked: a 1-D float32 DeviceArray, or a host array."""
+    if isinstance(values, _lib.DeviceArray):
+        if len(values.shape) != 1 or values.dtype != np.float32:
+            raise ValueError(f"device {what} must be a 1-D float32 DeviceArray, not {values.dtype}{values.shape}")
+        return values
+    values = np.asarray(values)
+    if values.ndim != 1 or (non_empty and values.shape[0] < 1) or \
+            not (np.issubdtype(values.dtype, np.floating) or np.issubdtype(values.dtype, np.integer)):
+        raise ValueError(f"{what} must be a {'non-empty ' if non_empty else ''}1-D array of numbers, not "
+                         f"{values.dtype}{values.shape}")
+    return values
+
+
 def auc_counts(scores, target, device=0):
     """(concordant, ties, positives, negatives, nan_rows) of float32 scores against 0/1 labels, counted on the device
     (ds_auc / ds_auc_device): scores may be a host array or a 1-D DeviceArray (then the labels are uploaded next to it).
     The order is that of the scores' integer keys: -0.0 equals +0.0, a NaN score belongs to neither class."""
     out = np.zeros(5, np.int64)
+    scores = _scores(scores, "scores", non_empty=True)
+    n, target = _device_labels(scores.shape[0], target, "scored")
     if isinstance(scores, _lib.DeviceArray):
-        if len(scores.shape) != 1 or scores.dtype != np.float32:
-            raise ValueError(f"device scores must be a 1-D float32 DeviceArray, not {scores.dtype}{scores.shape}")
-        n, target = _device_labels(scores.shape[0], target, "scored")
         d_target = _lib.DeviceArray.from_host(target, scores.device)
         try:
             _lib.check(_lib.lib().ds_auc_device(scores.ptr, d_target.ptr, n, _lib.pointer(out), None), "ds_auc_device")
         finally:
             d_target.free()
         return tuple(int(v) for v in out)
-    scores = np.asarray(scores)
-    if scores.ndim != 1 or scores.shape[0] < 1 or not (np.issubdtype(scores.dtype, np.floating) or
-                                                       np.issubdtype(scores.dtype, np.integer)):
-        raise ValueError(f"scores must be a non-empty 1-D array of numbers, not {scores.dtype}{scores.shape}")
-    n, target = _device_labels(scores.shape[0], target, "scored")
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     _lib.check(_lib.lib().ds_auc(_lib.pointer(scores), _lib.pointer(target), n, _lib.pointer(out), device), "ds_auc")
     return tuple(int(v) for v in out)
@@ -213,16 +221,10 @@ def logloss_counts(margins, target, beta=5.0, device=0):
     (ds_weighted_logloss_device); margins may be a host array or a 1-D float32 DeviceArray.  logloss_value gives
     sum / 2^20 / rows."""
     beta = _real("beta", beta, positive=True)
+    margins = _scores(margins, "margins")
     on_device = isinstance(margins, _lib.DeviceArray)
     if on_device:
-        if len(margins.shape) != 1 or margins.dtype != np.float32:
-            raise ValueError(f"device margins must be a 1-D float32 DeviceArray, not {margins.dtype}{margins.shape}")
         device = margins.device
-    else:
-        margins = np.asarray(margins)
-        if margins.ndim != 1 or not (np.issubdtype(margins.dtype, np.floating) or
-                                     np.issubdtype(margins.dtype, np.integer)):
-            raise ValueError(f"margins must be a 1-D array of numbers, not {margins.dtype}{margins.shape}")
     n, target = _device_labels(margins.shape[0], target, "scored")
     d_margins = margins if on_device else _lib.DeviceArray.from_host(margins.astype(np.float32), device)
     d_target = _lib.DeviceArray.from_host(target, device)
@@ -242,6 +244,21 @@ def roc_auc(scores, target, device=0):
     return auc_value(auc_counts(scores, target, device))
 
 
+def _labels(n, target, what):
+    """One 0/1 label for each of the n `what` rows -> float32[n]."""
+    target = np.asarray(target)
+    if target.ndim != 1 or target.shape[0] != n:
+        raise ValueError(f"{n} {what} rows but {target.reshape(-1).shape[0]} labels")
+    if target.dtype == object or not np.isin(target, (0, 1)).all():
+        raise ValueError(f"{what} labels must all be 0 or 1")
+    return np.ascontiguousarray(target, dtype=np.float32)
+
+
+def _device_labels(n, target, what):
+    n = _positive_int(f"the number of {what} rows", n, 1, (1 << 31) - 1)
+    return n, _labels(n, target, what)
+
+
 def _matrix_and_labels(features, target, what):
     features = np.asarray(features)
     if features.ndim != 2:
@@ -252,19 +269,13 @@ def _matrix_and_labels(features, target, what):
         raise ValueError(f"{what} features need at least one row")
     if not 1 <= features.shape[1] <= FEATURES_MAX:
         raise ValueError(f"{what} features have {features.shape[1]} columns, the model takes 1 to {FEATURES_MAX}")
-    target = np.asarray(target)
-    if target.ndim != 1 or target.shape[0] != features.shape[0]:
-        raise ValueError(f"{features.shape[0]} {what} rows but {target.reshape(-1).shape[0]} labels")
-    if target.dtype == object or not np.isin(target, (0, 1)).all():
-        raise ValueError(f"{what} labels must all be 0 or 1")
-    return np.ascontiguousarray(features, dtype=np.float32), np.ascontiguousarray(target, dtype=np.float32)
+    target = _labels(features.shape[0], target, what)
+    return np.ascontiguousarray(features, dtype=np.float32), target
 
 
-def validate_fit(features, target, eval_features=None, eval_target=None, num_boost_round=1000,
-                 early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                 max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0,
-                 eval_metrics=()):
-    """fit's checks (no library needed) -> (features, target, eval_features, eval_target, params) as float32 arrays."""
+def validate_fit(features, target, eval_features=None, eval_target=None, **parameters):
+    """fit's checks (no library needed) -> (features, target, eval_features, eval_target, params) as float32 arrays.
+    parameters: validate_parameters' own, by keyword; a name it does not know is its TypeError."""
     features, target = _matrix_and_labels(features, target, "training")
     if (eval_features is None) != (eval_target is None):
         raise ValueError("eval_features and eval_target go together")
@@ -273,16 +284,15 @@ def validate_fit(features, target, eval_features=None, eval_target=None, num_boo
         if eval_features.shape[1] != features.shape[1]:
             raise ValueError(f"evaluation features have {eval_features.shape[1]} columns, training features "
                              f"{features.shape[1]}")
-    params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
-                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed,
-                                 eval_metrics)
-    return features, target, eval_features, eval_target, params
+    return features, target, eval_features, eval_target, validate_parameters(**parameters)
 
 
 def validate_parameters(num_boost_round=1000, early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0,
                         reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
                         colsample_bylevel=1.0, sample_seed=0, eval_metrics=()):
-    """The parameter checks of fit and fit_device -> params.  subsample, colsample_bytree and colsample_bylevel are
+    """The booster parameters, checked -> params.  This signature is the ONE list of their names and defaults:
+    validate_fit, validate_fit_device and ForestTrainer's begin and fit forms take them as **parameters and hand them
+    here, tuning and train_model read the names from it.  subsample, colsample_bytree and colsample_bylevel are
     fractions in (0, 1] ("Subsampling"); sample_seed in [0, 2^63) seeds their draws and is not the
     `seed` of the training set and the folds.  eval_metrics: a tuple drawn from METRIC_NAMES, reported per round
     ("Metrics"); it changes no tree."""
@@ -324,23 +334,12 @@ def validate_init_model(init_model, n_features, device=None):
 
 
 def _samples(params):
-    return any(params[name] < 1 for name in SAMPLING_NAMES[:3])
+    """Whether a parameter set draws rows or columns: a fraction below 1 (a set that carries none draws nothing)."""
+    return any(params.get(name, 1.0) < 1 for name in SAMPLING_NAMES[:3])
 
 
-def _device_labels(n, target, what):
-    n = _positive_int(f"the number of {what} rows", n, 1, (1 << 31) - 1)
-    target = np.asarray(target)
-    if target.ndim != 1 or target.shape[0] != n:
-        raise ValueError(f"{n} {what} rows but {target.reshape(-1).shape[0]} labels")
-    if target.dtype == object or not np.isin(target, (0, 1)).all():
-        raise ValueError(f"{what} labels must all be 0 or 1")
-    return n, np.ascontiguousarray(target, dtype=np.float32)
-
-
-def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
-                        early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                        max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
-                        sample_seed=0, eval_metrics=()):
+def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, *, n_features=None,
+                        **parameters):
     """fit_device's checks (no library needed) -> (n, target, n_eval, eval_target, n_features, params): validate_fit
     for matrices in HBM, of which only the shapes are known here."""
     n_features = _device_columns(d_features, n_features)
@@ -358,10 +357,7 @@ def validate_fit_device(d_features, n, target, d_eval_features=None, n_eval=0, e
     for array, rows, what in ((d_features, n, "training"), (d_eval_features, n_eval, "evaluation")):
         if isinstance(array, _lib.DeviceArray) and rows > array.shape[0]:
             raise ValueError(f"{rows} {what} rows exceed the device matrix's {array.shape[0]}")
-    params = validate_parameters(num_boost_round, early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda,
-                                 beta, max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed,
-                                 eval_metrics)
-    return n, target, n_eval, eval_target, n_features, params
+    return n, target, n_eval, eval_target, n_features, validate_parameters(**parameters)
 
 
 def heap_tree(info, leaf, cuts, cut_offsets):
@@ -390,16 +386,91 @@ def heap_tree(info, leaf, cuts, cut_offsets):
     return tree
 
 
-class ForestTrainer:
+class FirstMinimum:
+    """The stopping rule of every training loop (ForestTrainer.fit, cross_validate, select_parameters): `best` is the
+    round of the FIRST minimum of the values seen, `value` that minimum; see(round_, value) says whether the loop stops
+    after this round, which it does once round_ - best >= patience (None: never)."""
+
+    def __init__(self, patience=None):
+        self.patience, self.best, self.value = patience, None, None
+
+    def see(self, round_, value):
+        if self.best is None or value < self.value:
+            self.best, self.value = round_, value
+        return self.patience is not None and round_ - self.best >= self.patience
+
+
+def _call(entry, in_hbm, *arguments):
+    """One checked call of a library entry that has a form for a matrix in HBM, named `<entry>_device`."""
+    entry += "_device" if in_hbm else ""
+    _lib.check(getattr(_lib.lib(), entry)(*arguments), entry)
+
+
+def _step_form(parameters):
+    """begin and begin_device grow no round: to them the two round names are unknown names."""
+    for name in ("num_boost_round", "early_stopping_rounds"):
+        if name in parameters:
+            raise TypeError(f"begin and begin_device got an unexpected keyword argument {name!r}")
+    return parameters
+
+
+class _TrainerHandle:
+    """What ForestTrainer and ForestTrainerBatch (tuning.py) do alike with their library object.  ENTRIES is the prefix
+    of its entries' names, READS the buffers of its read entry in argument order."""
+    ENTRIES, READS = None, ()
+
+    def _model(self, trees, n_trees):
+        """ForestModel of the first n_trees of `trees` (None: all), after the init model's if there is one."""
+        trees = trees[:len(trees) if n_trees is None else n_trees]
+        if self.init_model is not None:
+            return self.init_model.extended(trees)
+        return ForestModel.from_trees(trees, self.n_features, device=self.device)
+
+    def _set_metrics(self, metrics, rows):
+        """The buffer that every step's counts are read into (`rows` sets or models) and the metrics to the library,
+        once the labels and the held-out rows are in place (none: nothing to set)."""
+        self._metric_counts = np.full((rows, 6), -1, np.int64)
+        if metrics:
+            _lib.check(getattr(_lib.lib(), self.ENTRIES + "_set_metrics")(self.handle, metric_flags(metrics)),
+                       self.ENTRIES + "_set_metrics")
+
+    def _read(self, *model, **wanted):
+        """{name: array} of the device buffers wanted, each given as name=(shape, dtype); `model`: the batch's index."""
+        out = {name: np.empty(shape, dtype) for name, (shape, dtype) in wanted.items()}
+        _lib.check(getattr(_lib.lib(), self.ENTRIES + "_read")(
+            self.handle, *(int(m) for m in model), *(_lib.pointer(out.get(name)) for name in self.READS)),
+            self.ENTRIES + "_read")
+        return out
+
+    def close(self):
+        if self.handle:
+            getattr(_lib.lib(), self.ENTRIES + "_destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ForestTrainer(_TrainerHandle):
     """xgb.train(params={max_depth, eta, min_child_weight, subsample, colsample_bytree, colsample_bylevel},
     obj=weighted_log_loss, feval=custom_error, early_stopping_rounds) on the GPU.
 
-        model = ForestTrainer().fit(features, target, eval_features, eval_target)
+        model = ForestTrainer().fit(features, target, eval_features, eval_target, max_depth=5, eta=0.1)
+
+    The data arguments may be given by position; the booster parameters (validate_parameters: its signature is their
+    list and their defaults), `init_model` and the device forms' `n_features` by keyword ONLY.  fit and fit_device
+    take all of them; begin and begin_device all but num_boost_round and early_stopping_rounds.  A name that
+    validate_parameters does not know is a TypeError.  Everything is validated, once, before the library is touched,
+    and a trainer whose begin or fit is refused keeps the state it had.
 
     After fit, `best_iteration` is the round (from 0) of the first minimum of the evaluation error and `history` the
     error of every round; the model holds the first best_iteration + 1 trees (the reference predicts with
     ntree_limit=best_ntree_limit).  Without an evaluation set every round is kept.  The step form: begin(...), then
-    step() grows one tree and returns the round's evaluation error (None without an evaluation set).
+    step() grows one tree and returns the round's evaluation error (None without an evaluation set).  `timings` has the
+    milliseconds of the last begin: "cuts", and "bin" for everything from the trainer's creation to its metrics.
 
     eval_metrics=("auc", "logloss") also reports, per round, the reference's log: `metrics_history` gains one value per
     key "train-auc", "evaluation-auc", "train-logloss", "evaluation-logloss" (evaluation keys only with an evaluation
@@ -414,6 +485,7 @@ class ForestTrainer:
     init trees followed by the first n new ones.  Early stopping looks at the new rounds only (the first minimum of
     `history`; initial_error is no candidate), and `best_iteration` counts all trees: init trees + the best new round,
     so that the model returned has best_iteration + 1 trees as ever.  See validate_init_model for what is accepted."""
+    ENTRIES, READS = "ds_trainer", ("margins", "probabilities", "gradients", "bins", "eval_margins")
 
     def __init__(self, device=0):
         self.device = device
@@ -427,88 +499,35 @@ class ForestTrainer:
         self.metrics_history = {}
         self.metric_counts = []
 
-    def begin(self, features, target, eval_features=None, eval_target=None, max_depth=5, eta=0.1,
-              min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, subsample=1.0, colsample_bytree=1.0,
-              colsample_bylevel=1.0, sample_seed=0, eval_metrics=(), init_model=None):
-        features, target, eval_features, eval_target, params = validate_fit(
-            features, target, eval_features, eval_target, max_depth=max_depth, eta=eta,
-            min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin, subsample=subsample,
-            colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, sample_seed=sample_seed,
-            eval_metrics=eval_metrics)
-        if init_model is not None:
-            validate_init_model(init_model, features.shape[1], self.device)
-        self.close()
-        self.params = params
-        self.n, self.n_features = features.shape
-        self.n_eval = 0 if eval_features is None else eval_features.shape[0]
-        self.cuts, self.cut_offsets = compute_cuts(features, params["max_bin"])
-        self.trees, self.history, self.best_iteration = [], [], None
-        handle = ctypes.c_void_p()
-        library = _lib.lib()
-        _lib.check(library.ds_trainer_create(_lib.pointer(features), self.n, self.n_features, _lib.pointer(self.cuts),
-                                             _lib.pointer(self.cut_offsets), params["max_depth"], params["eta"],
-                                             params["min_child_weight"], params["reg_lambda"], params["beta"],
-                                             self.device, ctypes.byref(handle)), "ds_trainer_create")
-        self.handle = handle
-        self._set_sampling(params)
-        _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
-        if eval_features is not None:
-            _lib.check(library.ds_trainer_set_eval(self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
-                                                   self.n_eval), "ds_trainer_set_eval")
-        self._seed(init_model, features, eval_features, False)
-        self._set_metrics(params)
-        slots = (2 << params["max_depth"]) - 1
-        self._info = np.zeros((slots, 4), np.int32)
-        self._leaf = np.zeros(slots, np.float32)
-        return self
+    def begin(self, features, target, eval_features=None, eval_target=None, **parameters):
+        return self._begin(False, (features, target, eval_features, eval_target), **_step_form(parameters))
 
-    def _set_sampling(self, params):
-        """The fractions and the seed to the library, when a fraction is below 1 (all 1: nothing to set)."""
-        if _samples(params):
-            _lib.check(_lib.lib().ds_trainer_set_sampling(self.handle, params["subsample"], params["colsample_bytree"],
-                                                          params["colsample_bylevel"], params["sample_seed"]),
-                       "ds_trainer_set_sampling")
+    def fit(self, features, target, eval_features=None, eval_target=None, **parameters):
+        self._begin(False, (features, target, eval_features, eval_target), **parameters)
+        return self._boost(self.params)
 
-    def _seed(self, init_model, features, eval_features, in_hbm):
-        """Start the margins from init_model (None: from zero, nothing to do) once labels and evaluation set are in."""
-        self.init_model, self.initial_error = init_model, None
-        if init_model is None:
-            return
-        error = ctypes.c_int64(-1)
-        library = _lib.lib()
-        if in_hbm:
-            _lib.check(library.ds_trainer_seed_device(self.handle, init_model.handle, _lib.pointer(features),
-                                                      _lib.pointer(eval_features), ctypes.byref(error), None),
-                       "ds_trainer_seed_device")
-        else:
-            _lib.check(library.ds_trainer_seed(self.handle, init_model.handle, _lib.pointer(features),
-                                               _lib.pointer(eval_features), ctypes.byref(error)), "ds_trainer_seed")
-        self.initial_error = int(error.value) if self.n_eval else None
-
-    def _set_metrics(self, params):
-        """The metrics to the library once the labels and the evaluation set are in place (none: nothing to set)."""
-        self.eval_metrics = params["eval_metrics"]
-        names = [f"{set_}-{metric}" for metric in self.eval_metrics
-                 for set_ in (("train", "evaluation") if self.n_eval else ("train",))]
-        self.metrics_history, self.metric_counts = {name: [] for name in names}, []
-        self._metric_counts = np.full((2, 6), -1, np.int64)
-        if self.eval_metrics:
-            _lib.check(_lib.lib().ds_trainer_set_metrics(self.handle, metric_flags(self.eval_metrics)),
-                       "ds_trainer_set_metrics")
-
-    def begin_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, max_depth=5,
-                     eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0, max_bin=256, n_features=None,
-                     subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=(),
-                     init_model=None):
+    def begin_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, **parameters):
         """begin for matrices that already lie in HBM: contiguous float32[n, n_features] DeviceArrays (or addresses,
         with n_features given), complete before the call; labels are host arrays.  The cuts come from
         compute_cuts_device, the bins from the same kernel as begin's, so every later call works as after begin.  The
         matrices are not kept and may be freed afterwards."""
-        n, target, n_eval, eval_target, n_features, params = validate_fit_device(
-            d_features, n, target, d_eval_features, n_eval, eval_target, max_depth=max_depth, eta=eta,
-            min_child_weight=min_child_weight, reg_lambda=reg_lambda, beta=beta, max_bin=max_bin,
-            n_features=n_features, subsample=subsample, colsample_bytree=colsample_bytree,
-            colsample_bylevel=colsample_bylevel, sample_seed=sample_seed, eval_metrics=eval_metrics)
+        return self._begin(True, (d_features, n, target, d_eval_features, n_eval, eval_target),
+                           **_step_form(parameters))
+
+    def fit_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, **parameters):
+        """fit for matrices in HBM (begin_device, then fit's rounds and early stopping)."""
+        self._begin(True, (d_features, n, target, d_eval_features, n_eval, eval_target), **parameters)
+        return self._boost(self.params)
+
+    def _begin(self, in_hbm, data, init_model=None, **parameters):
+        """The one sequence behind the four forms above; `data` are their data arguments.  Everything is validated
+        first: until that has passed the library is not touched and this trainer keeps the state it has."""
+        if in_hbm:
+            n, target, n_eval, eval_target, n_features, params = validate_fit_device(*data, **parameters)
+            features, eval_features = data[0], data[3]
+        else:
+            features, target, eval_features, eval_target, params = validate_fit(*data, **parameters)
+            (n, n_features), n_eval = features.shape, 0 if eval_features is None else eval_features.shape[0]
         if init_model is not None:
             validate_init_model(init_model, n_features, self.device)
         self.close()
@@ -516,44 +535,41 @@ class ForestTrainer:
         self.n, self.n_features, self.n_eval = n, n_features, n_eval
         self.timings = {}
         mark = time.perf_counter()
-        self.cuts, self.cut_offsets = compute_cuts_device(d_features, n, params["max_bin"], n_features, self.device)
+        self.cuts, self.cut_offsets = compute_cuts_device(features, n, params["max_bin"], n_features, self.device) \
+            if in_hbm else compute_cuts(features, params["max_bin"])
         self.timings["cuts"] = (time.perf_counter() - mark) * 1000.0
         self.trees, self.history, self.best_iteration = [], [], None
         mark = time.perf_counter()
         handle = ctypes.c_void_p()
-        library = _lib.lib()
-        _lib.check(library.ds_trainer_create_device(
-            _lib.pointer(d_features), self.n, self.n_features, _lib.pointer(self.cuts), _lib.pointer(self.cut_offsets),
-            params["max_depth"], params["eta"], params["min_child_weight"], params["reg_lambda"], params["beta"],
-            self.device, ctypes.byref(handle)), "ds_trainer_create_device")
+        _call("ds_trainer_create", in_hbm, _lib.pointer(features), n, n_features, _lib.pointer(self.cuts),
+              _lib.pointer(self.cut_offsets), params["max_depth"], params["eta"], params["min_child_weight"],
+              params["reg_lambda"], params["beta"], self.device, ctypes.byref(handle))
         self.handle = handle
-        self._set_sampling(params)
+        library = _lib.lib()
+        if _samples(params):                   # all fractions 1: nothing to set
+            _lib.check(library.ds_trainer_set_sampling(self.handle, params["subsample"], params["colsample_bytree"],
+                                                       params["colsample_bylevel"], params["sample_seed"]),
+                       "ds_trainer_set_sampling")
         _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
         if n_eval:
-            _lib.check(library.ds_trainer_set_eval_device(self.handle, _lib.pointer(d_eval_features),
-                                                          _lib.pointer(eval_target), self.n_eval),
-                       "ds_trainer_set_eval_device")
-        self._seed(init_model, d_features, d_eval_features if n_eval else None, True)
-        self._set_metrics(params)
+            _call("ds_trainer_set_eval", in_hbm, self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
+                  n_eval)
+        self.init_model, self.initial_error = init_model, None
+        if init_model is not None:             # the margins start from it, now that labels and evaluation set are in
+            error = ctypes.c_int64(-1)
+            _call("ds_trainer_seed", in_hbm, self.handle, init_model.handle, _lib.pointer(features),
+                  _lib.pointer(eval_features), ctypes.byref(error), *((None,) if in_hbm else ()))
+            self.initial_error = int(error.value) if n_eval else None
+        self.eval_metrics = params["eval_metrics"]
+        sets = ("train", "evaluation") if n_eval else ("train",)
+        self.metrics_history = {f"{set_}-{metric}": [] for metric in self.eval_metrics for set_ in sets}
+        self.metric_counts = []
+        self._set_metrics(self.eval_metrics, 2)
         self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
         slots = (2 << params["max_depth"]) - 1
         self._info = np.zeros((slots, 4), np.int32)
         self._leaf = np.zeros(slots, np.float32)
         return self
-
-    def fit_device(self, d_features, n, target, d_eval_features=None, n_eval=0, eval_target=None, num_boost_round=1000,
-                   early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-                   max_bin=256, n_features=None, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0,
-                   sample_seed=0, eval_metrics=(), init_model=None):
-        """fit for matrices in HBM (begin_device, then fit's rounds and early stopping)."""
-        rounds = validate_fit_device(d_features, n, target, d_eval_features, n_eval, eval_target, num_boost_round,
-                                     early_stopping_rounds, max_depth, eta, min_child_weight, reg_lambda, beta, max_bin,
-                                     n_features, subsample, colsample_bytree, colsample_bylevel, sample_seed,
-                                     eval_metrics)[5]
-        self.begin_device(d_features, n, target, d_eval_features, n_eval, eval_target, max_depth, eta,
-                          min_child_weight, reg_lambda, beta, max_bin, n_features, subsample, colsample_bytree,
-                          colsample_bylevel, sample_seed, eval_metrics, init_model)
-        return self._boost(rounds)
 
     def step(self):
         """Grow one tree; returns the evaluation error after it (None without an evaluation set)."""
@@ -584,42 +600,19 @@ class ForestTrainer:
     def model(self, n_trees=None):
         """ForestModel of the first n_trees trees grown here (default: all so far), after the init model's if there is
         one."""
-        trees = self.trees[:len(self.trees) if n_trees is None else n_trees]
-        if self.init_model is not None:
-            return self.init_model.extended(trees)
-        return ForestModel.from_trees(trees, self.n_features, device=self.device)
-
-    def fit(self, features, target, eval_features=None, eval_target=None, num_boost_round=1000,
-            early_stopping_rounds=50, max_depth=5, eta=0.1, min_child_weight=1.0, reg_lambda=1.0, beta=5.0,
-            max_bin=256, subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, sample_seed=0, eval_metrics=(),
-            init_model=None):
-        rounds = validate_fit(features, target, eval_features, eval_target, num_boost_round, early_stopping_rounds,
-                              max_depth, eta, min_child_weight, reg_lambda, beta, max_bin, subsample, colsample_bytree,
-                              colsample_bylevel, sample_seed, eval_metrics)[4]
-        self.begin(features, target, eval_features, eval_target, max_depth, eta, min_child_weight, reg_lambda, beta,
-                   max_bin, subsample, colsample_bytree, colsample_bylevel, sample_seed, eval_metrics, init_model)
-        return self._boost(rounds)
+        return self._model(self.trees, n_trees)
 
     def _boost(self, rounds):
-        best, best_error = None, None
+        """Step up to rounds["num_boost_round"] times under FirstMinimum(rounds["early_stopping_rounds"]) on the
+        evaluation error -> the model of the best round's trees."""
+        rule = FirstMinimum(rounds["early_stopping_rounds"])
         for round_ in range(rounds["num_boost_round"]):
             error = self.step()
-            if error is None:
-                continue
-            if best_error is None or error < best_error:
-                best, best_error = round_, error
-            if round_ - best >= rounds["early_stopping_rounds"]:
+            if error is not None and rule.see(round_, error):
                 break
-        best = best if best is not None else len(self.trees) - 1           # among the rounds grown here
+        best = rule.best if rule.best is not None else len(self.trees) - 1   # no evaluation set: every round is kept
         self.best_iteration = (self.init_model.n_trees if self.init_model is not None else 0) + best
         return self.model(best + 1)
-
-    def _read(self, **wanted):
-        out = {name: np.empty(shape, dtype) for name, (shape, dtype) in wanted.items()}
-        p = lambda name: _lib.pointer(out.get(name))
-        _lib.check(_lib.lib().ds_trainer_read(self.handle, p("margins"), p("probabilities"), p("gradients"), p("bins"),
-                                              p("eval_margins")), "ds_trainer_read")
-        return out
 
     def margins(self):
         """Training margins after the trees so far (float32[n])."""
@@ -639,17 +632,6 @@ class ForestTrainer:
     def bins(self):
         """uint8[n_features, n]: the device's bins (255 = missing)."""
         return self._read(bins=((self.n_features, self.n), np.uint8))["bins"]
-
-    def close(self):
-        if self.handle:
-            _lib.lib().ds_trainer_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def evaluation_error_matrix(model, features, target, threshold=PREDICTION_PROBABILITY_THRESHOLD):

@@ -14,10 +14,10 @@ import time
 import numpy as np
 
 from . import _lib
-from .forest import ForestModel
-from .train import (METRIC_NAMES, SAMPLING_NAMES, _device_columns, _device_labels, _matrix_and_labels, _positive_int,
-                    auc_numerator, compute_cuts, compute_cuts_device, heap_tree, metric_flags, metric_values,
-                    validate_init_model, validate_metrics, validate_parameters)
+from .train import (METRIC_NAMES, SAMPLING_NAMES, FirstMinimum, _call, _device_columns, _device_labels,
+                    _matrix_and_labels, _positive_int, _samples, _TrainerHandle, auc_numerator, compute_cuts,
+                    compute_cuts_device, heap_tree, metric_values, validate_init_model, validate_metrics,
+                    validate_parameters)
 
 MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
 FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
@@ -159,13 +159,9 @@ def _selection_score(select_by, errors, fold_counts):
 def _replay(curve, early_stopping_rounds):
     """(best_iteration, error, rounds) of one summed curve under the stepping rule: the first minimum; the set stops
     after the first round with round - best >= early_stopping_rounds (None: never), later entries are not looked at."""
-    best = 0
-    for round_, error in enumerate(curve):
-        if error < curve[best]:
-            best = round_
-        if early_stopping_rounds is not None and round_ - best >= early_stopping_rounds:
-            return best, int(curve[best]), round_ + 1
-    return best, int(curve[best]), len(curve)
+    rule = FirstMinimum(early_stopping_rounds)
+    rounds = next((round_ + 1 for round_, error in enumerate(curve) if rule.see(round_, error)), len(curve))
+    return rule.best, int(rule.value), rounds
 
 
 def select_parameters(histories, early_stopping_rounds=None, select_by="error", metric_counts=None):
@@ -268,7 +264,7 @@ def batch_option(name, value):
     _lib.check(_lib.lib().ds_trainer_batch_option(name.encode(), int(value)), "ds_trainer_batch_option")
 
 
-class ForestTrainerBatch:
+class ForestTrainerBatch(_TrainerHandle):
     """Many ForestTrainers over one binned matrix, stepped together.
 
         batch = ForestTrainerBatch().begin(features, target, fold, models)
@@ -289,6 +285,7 @@ class ForestTrainerBatch:
     model"): the forest is evaluated once per row of the raw matrix on the device, `initial_errors[m]` is its error on
     model m's held-out rows (None without a fold), trees[m] and history[m] hold the new rounds, model(m, n) the init
     trees followed by the first n new ones, and model m stays ForestTrainer(init_model=...)'s on its training rows."""
+    ENTRIES, READS = "ds_trainer_batch", ("margins", "probabilities", "gradients", "bins")
 
     def __init__(self, device=0):
         self.device = device
@@ -338,36 +335,25 @@ class ForestTrainerBatch:
         self.last_heap = [None] * len(sets)
         mark = time.perf_counter()
         handle = ctypes.c_void_p()
-        library = _lib.lib()
-        create = library.ds_trainer_batch_create_device if in_hbm else library.ds_trainer_batch_create
-        _lib.check(create(_lib.pointer(features), n, n_features, _lib.pointer(self.cuts), _lib.pointer(self.cut_offsets),
-                          _lib.pointer(target), _lib.pointer(fold), n_folds, self.n_models, _lib.pointer(params),
-                          _lib.pointer(held_out), self.device, ctypes.byref(handle)),
-                   "ds_trainer_batch_create_device" if in_hbm else "ds_trainer_batch_create")
+        _call("ds_trainer_batch_create", in_hbm, _lib.pointer(features), n, n_features, _lib.pointer(self.cuts),
+              _lib.pointer(self.cut_offsets), _lib.pointer(target), _lib.pointer(fold), n_folds, self.n_models,
+              _lib.pointer(params), _lib.pointer(held_out), self.device, ctypes.byref(handle))
         self.handle = handle
-        if any(one.get(name, 1.0) < 1 for one in sets for name in SAMPLING_NAMES[:3]):
+        if any(_samples(one) for one in sets):
             fractions = np.array([[one[name] for name in SAMPLING_NAMES[:3]] for one in sets], np.float64)
             seeds = np.array([one["sample_seed"] for one in sets], np.uint64)
-            _lib.check(library.ds_trainer_batch_set_sampling(self.handle, _lib.pointer(fractions), _lib.pointer(seeds)),
-                       "ds_trainer_batch_set_sampling")
+            _lib.check(_lib.lib().ds_trainer_batch_set_sampling(self.handle, _lib.pointer(fractions),
+                                                                _lib.pointer(seeds)), "ds_trainer_batch_set_sampling")
         self.init_model, self.initial_errors = init_model, [None] * len(sets)
         if init_model is not None:
             errors = np.full(self.n_models, -1, np.int64)
-            if in_hbm:
-                _lib.check(library.ds_trainer_batch_seed_device(self.handle, init_model.handle, _lib.pointer(features),
-                                                                _lib.pointer(errors), None),
-                           "ds_trainer_batch_seed_device")
-            else:
-                _lib.check(library.ds_trainer_batch_seed(self.handle, init_model.handle, _lib.pointer(features),
-                                                         _lib.pointer(errors)), "ds_trainer_batch_seed")
+            _call("ds_trainer_batch_seed", in_hbm, self.handle, init_model.handle, _lib.pointer(features),
+                  _lib.pointer(errors), *((None,) if in_hbm else ()))
             self.initial_errors = [int(errors[m]) if held_out[m] >= 0 else None for m in range(self.n_models)]
         self.metrics = metrics
         self.metrics_history = [{name: [] for name in metrics} for _ in sets]
         self.metric_counts = [[] for _ in sets]
-        self._metric_counts = np.full((self.n_models, 6), -1, np.int64)
-        if metrics:
-            _lib.check(library.ds_trainer_batch_set_metrics(self.handle, metric_flags(metrics)),
-                       "ds_trainer_batch_set_metrics")
+        self._set_metrics(metrics, self.n_models)
         self.timings["bin"] = (time.perf_counter() - mark) * 1000.0
         slots = (2 << self.max_depth) - 1          # the heaps of every model have the largest max_depth's slots
         self._info = np.zeros((self.n_models, slots, 4), np.int32)
@@ -409,17 +395,7 @@ class ForestTrainerBatch:
     def model(self, m, n_trees=None):
         """ForestModel of the first n_trees trees of model m grown here (default: all so far), after the init model's
         if there is one."""
-        trees = self.trees[m][:len(self.trees[m]) if n_trees is None else n_trees]
-        if self.init_model is not None:
-            return self.init_model.extended(trees)
-        return ForestModel.from_trees(trees, self.n_features, device=self.device)
-
-    def _read(self, m, **wanted):
-        out = {name: np.empty(shape, dtype) for name, (shape, dtype) in wanted.items()}
-        p = lambda name: _lib.pointer(out.get(name))
-        _lib.check(_lib.lib().ds_trainer_batch_read(self.handle, int(m), p("margins"), p("probabilities"),
-                                                    p("gradients"), p("bins")), "ds_trainer_batch_read")
-        return out
+        return self._model(self.trees[m], n_trees)
 
     def margins(self, m):
         """Model m's margins of ALL rows after its trees so far (float32[n])."""
@@ -434,17 +410,6 @@ class ForestTrainerBatch:
 
     def bins(self):
         return self._read(0, bins=((self.n_features, self.n), np.uint8))["bins"]
-
-    def close(self):
-        if self.handle:
-            _lib.lib().ds_trainer_batch_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class CrossValidation:
@@ -563,7 +528,7 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
         batch = begin([dict(one, held_out=k) for one in chunk for k in range(n_folds)], metrics)
         try:
             mark = time.perf_counter()
-            summed, best = [[] for _ in chunk], [0] * len(chunk)
+            summed, rules = [[] for _ in chunk], [FirstMinimum(early_stopping_rounds) for _ in chunk]
             running = np.ones(len(chunk), bool)
             for round_ in range(num_boost_round):
                 errors = batch.step(np.repeat(running, n_folds))
@@ -571,9 +536,7 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
                     models = range(s * n_folds, (s + 1) * n_folds)
                     summed[s].append(_selection_score(select_by, errors[s * n_folds:(s + 1) * n_folds],
                                                       [batch.metric_counts[m][-1] for m in models] if metrics else None))
-                    if summed[s][-1] < summed[s][best[s]]:
-                        best[s] = round_
-                    if round_ - best[s] >= early_stopping_rounds:
+                    if rules[s].see(round_, summed[s][-1]):
                         running[s] = False
                 if not running.any():
                     break

@@ -95,6 +95,55 @@ def test_fit_device_without_an_evaluation_set_keeps_every_round():
     assert np.array_equal(device.margins().view(np.uint32), host.margins().view(np.uint32))
 
 
+def small_sets():
+    """300 training rows x 5 features and 100 evaluation rows: more than one block of rows, no multiple of a block."""
+    return make_data(300, 5, 21) + make_data(100, 5, 22)
+
+
+@pytest.mark.parametrize("every_branch", [False, True], ids=["plain", "metrics_sampling_init_model"])
+def test_fit_and_fit_device_leave_the_same_trainer_behind(every_branch):
+    """The second case takes every optional branch of begin on both forms: metrics, subsampling, an init model."""
+    import doppel_speller_amd as ds
+    x, y, ex, ey = small_sets()
+    parameters = dict(max_depth=2, num_boost_round=3)
+    if every_branch:
+        init = ds.ForestTrainer().fit(x, y, max_depth=2, num_boost_round=2)
+        assert init.n_trees == 2
+        parameters.update(eval_metrics=("auc", "logloss"), subsample=0.5, init_model=init)
+    host, device = ds.ForestTrainer(), ds.ForestTrainer()
+    host.fit(x, y, ex, ey, **parameters)
+    device.fit_device(upload(x), 300, y, upload(ex), 100, ey, **parameters)
+    for name in ("n", "n_features", "n_eval", "params", "history", "best_iteration", "initial_error", "eval_metrics"):
+        assert getattr(device, name) == getattr(host, name), name
+    assert (host.n, host.n_features, host.n_eval, len(host.history), len(host.trees)) == (300, 5, 100, 3, 3)
+    assert device.cuts.tobytes() == host.cuts.tobytes() and device.cut_offsets.tolist() == host.cut_offsets.tolist()
+    assert list(device.metrics_history) == list(host.metrics_history) and len(device.trees) == len(host.trees)
+    assert {"cuts", "bin"} <= set(device.timings)
+    if every_branch:
+        assert host.eval_metrics == ("auc", "logloss") and isinstance(host.initial_error, int)
+        assert sorted(host.metrics_history) == ["evaluation-auc", "evaluation-logloss", "train-auc", "train-logloss"]
+        assert host.params["subsample"] == 0.5 and 2 <= host.best_iteration <= 4
+    else:
+        assert host.eval_metrics == () and host.metrics_history == {} and host.initial_error is None
+
+
+def test_a_refused_second_begin_leaves_the_trainer_stepping():
+    """A begin that is refused has touched nothing: the next step is the next round of the first begin."""
+    import doppel_speller_amd as ds
+    x, y, ex, ey = small_sets()
+    trainer, twin = (ds.ForestTrainer().begin(x, y, ex, ey, max_depth=2) for _ in range(2))
+    assert trainer.step() == twin.step()
+    handle = trainer.handle
+    with pytest.raises(ValueError, match="max_depth"):
+        trainer.begin(x, y, ex, ey, max_depth=9)
+    with pytest.raises(ValueError, match="max_depth"):
+        trainer.begin_device(upload(x), 300, y, max_depth=9)
+    assert trainer.handle is handle and len(trainer.trees) == 1 and trainer.params["max_depth"] == 2
+    assert trainer.step() == twin.step() and trainer.history == twin.history and len(trainer.trees) == 2
+    assert all(np.array_equal(trainer.trees[1][key], twin.trees[1][key]) for key in twin.trees[1])
+    assert np.array_equal(trainer.margins().view(np.uint32), twin.margins().view(np.uint32))
+
+
 def gather(source, rows, n_src=None, sentinel=-5.0):
     """(status, destination on the host with one sentinel row before and after)."""
     from doppel_speller_amd import _lib

@@ -3,6 +3,7 @@ ds_trainer_create_device, ds_trainer_set_eval_device, ds_gather_rows_device) ref
 message before they touch a device; train_model and fit_device refuse what validate_training and validate_fit refuse
 before the library is loaded; and the crafted cut-test columns reach both branches of the cut rule and its boundaries."""
 import ctypes
+import inspect
 
 import numpy as np
 import pytest
@@ -183,6 +184,61 @@ def test_fit_device_rejects_what_validate_fit_rejects(no_library):
         assert str(host.value) == str(device.value)
     assert validate_fit_device(_Matrix(4, 3), 4, y)[5] == validate_fit(x, y)[4]
     assert ds.compute_cuts_device is not None
+
+
+LEGAL = dict(num_boost_round=7, early_stopping_rounds=3, max_depth=3, eta=0.3, min_child_weight=2.0, reg_lambda=0.5,
+             beta=2.0, max_bin=16, subsample=0.5, colsample_bytree=0.6, colsample_bylevel=0.7, sample_seed=9,
+             eval_metrics=("auc",))
+ROUNDS = ("num_boost_round", "early_stopping_rounds")
+X4, Y4 = np.zeros((4, 3), np.float32), np.array([0, 1, 0, 1])
+
+
+def test_every_parameter_name_is_taken_by_keyword_at_every_entry(no_library):
+    """Each name of validate_parameters' signature, at a legal value that is not its default, alone and all together:
+    the validate_* return it, the trainer's forms get past their checks to the library (the fixture's refusal)."""
+    import doppel_speller_amd as ds
+    from doppel_speller_amd.train import validate_fit, validate_fit_device, validate_parameters
+    names = list(inspect.signature(validate_parameters).parameters)
+    assert sorted(names) == sorted(LEGAL)
+    defaults = validate_parameters()
+    for given in [{name: LEGAL[name]} for name in names] + [LEGAL]:
+        assert all(defaults[name] != value for name, value in given.items())
+        for params in (validate_parameters(**given), validate_fit(X4, Y4, **given)[4],
+                       validate_fit_device(_Matrix(4, 3), 4, Y4, **given)[5]):
+            assert params == dict(defaults, **given)
+        calls = [lambda: ds.ForestTrainer().fit(X4, Y4, **given),
+                 lambda: ds.ForestTrainer().fit_device(_Matrix(4, 3), 4, Y4, **given)]
+        stepped = {name: value for name, value in given.items() if name not in ROUNDS}
+        if stepped:
+            calls += [lambda: ds.ForestTrainer().begin(X4, Y4, **stepped),
+                      lambda: ds.ForestTrainer().begin_device(_Matrix(4, 3), 4, Y4, **stepped)]
+        for call in calls:
+            with pytest.raises(AssertionError, match="before the arguments were validated"):
+                call()
+
+
+def test_the_step_forms_do_not_know_the_round_names(no_library):
+    import doppel_speller_amd as ds
+    with pytest.raises(TypeError, match="num_boost_round"):
+        ds.ForestTrainer().begin(X4, Y4, num_boost_round=3)
+    with pytest.raises(TypeError, match="early_stopping_rounds"):
+        ds.ForestTrainer().begin_device(_Matrix(4, 3), 4, Y4, early_stopping_rounds=3)
+
+
+def test_a_refused_second_begin_keeps_the_first_state(no_library):
+    import doppel_speller_amd as ds
+    trainer = ds.ForestTrainer()
+    handle, trees, params = ctypes.c_void_p(1), [object()], dict(max_depth=2)      # stand-ins for a begun trainer's
+    trainer.handle, trainer.trees, trainer.params = handle, trees, params
+    try:
+        for again in (lambda: trainer.begin(X4, Y4, max_depth=9), lambda: trainer.fit(X4, Y4, max_depth=9),
+                      lambda: trainer.begin_device(_Matrix(4, 3), 4, Y4, max_depth=9),
+                      lambda: trainer.fit_device(_Matrix(4, 3), 4, Y4, max_depth=9)):
+            with pytest.raises(ValueError, match="max_depth"):
+                again()
+            assert trainer.handle is handle and trainer.trees is trees and trainer.params is params
+    finally:
+        trainer.handle = None                      # the stand-in is nothing the library could give back
 
 
 def test_compute_cuts_device_validates_before_the_library(no_library):

@@ -131,6 +131,41 @@ def test_select_parameters_with_a_set_that_stopped_earlier():
         ds.select_parameters([[[1, 2]]], early_stopping_rounds=0)
 
 
+# curve, then {early_stopping_rounds: (best_iteration, rounds)} worked out by hand; None never stops
+CURVES = {
+    "falling": ([9, 7, 5, 3, 1], {1: (4, 5), 3: (4, 5), None: (4, 5)}),
+    "minimum_first": ([2, 5, 6, 7, 8, 9], {1: (0, 2), 3: (0, 4), None: (0, 6)}),
+    "equal_minima": ([5, 3, 4, 3, 6, 7, 8], {1: (1, 3), 3: (1, 5), None: (1, 7)}),            # the first wins
+    "minimum_one_before_the_end": ([9, 8, 2, 5], {1: (2, 4), 3: (2, 4), None: (2, 4)}),
+    "minimum_three_before_the_end": ([9, 8, 2, 5, 5, 5], {1: (2, 4), 3: (2, 6), None: (2, 6)}),
+    "one_round": ([4], {1: (0, 1), 3: (0, 1), None: (0, 1)}),
+}
+
+
+@pytest.mark.parametrize("patience", [1, 3, None])
+@pytest.mark.parametrize("name", sorted(CURVES))
+def test_fit_stops_where_select_parameters_stops(name, patience):
+    """ForestTrainer._boost, stepped through a hand-made curve, keeps the round and grows the rounds that
+    select_parameters reports for that curve."""
+    import doppel_speller_amd as ds
+    curve, expected = CURVES[name]
+    trainer = ds.ForestTrainer()
+    errors = iter(curve)
+
+    def step():
+        trainer.trees.append(None)
+        trainer.history.append(next(errors))
+        return trainer.history[-1]
+    trainer.step, trainer.model = step, lambda n_trees: n_trees
+    kept = trainer._boost(dict(num_boost_round=len(curve),
+                               early_stopping_rounds=len(curve) + 1 if patience is None else patience))
+    chosen = ds.select_parameters([[curve]], patience)
+    assert (trainer.best_iteration, len(trainer.trees)) == expected[patience]
+    assert (chosen["best_iteration"][0], chosen["rounds"][0]) == expected[patience]
+    assert kept == trainer.best_iteration + 1 and trainer.history == chosen["history"][0]
+    assert chosen["error"][0] == curve[trainer.best_iteration]
+
+
 # ---- the oracle's own consistency --------------------------------------------------------------------------------------
 def test_zeroed_gradients_train_the_subset_trees():
     """300 rows x 4 features, 3 folds, depth 3, 5 rounds: growing on all rows with the held-out rows' (g, h) zeroed gives
