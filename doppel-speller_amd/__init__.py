@@ -44,6 +44,10 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         tune_model_parameters(..., init_model=)   -> continue boosting from an existing ForestModel (xgb.train's
         xgb_model=): k rounds continued for m more are exactly k + m rounds; `initial_error(s)` is the init model's own
         error; ForestModel.head(n) / extended(trees) cut and join forests (this project's own)
+    FeatureEngineering.generate_hard_negatives(model, hard_n) / generate_device_hard_negatives   -> for every train title
+        the wrong candidates the model likes best, scored and selected on the device; DeviceDataSets.
+        with_hard_negatives(hard) appends them to the training matrix in HBM for fit_device(..., init_model=model)
+        (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -61,7 +65,8 @@ from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMN
                          LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS, EXPLAIN_COLUMNS, Candidates, Prediction,
                          assignment_frame, duplicate_frame, predictions_accuracy, top_contributions,
                          validate_assignment, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
-from .training_set import DeviceDataSets, FeatureEngineering, generate_misspelled_names  # noqa: F401
+from .training_set import (DeviceDataSets, DeviceHardNegatives, FeatureEngineering, generate_misspelled_names,  # noqa: F401
+                           validate_hard)
 from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
                     evaluation_error_matrix, roc_auc, train_model, validate_init_model)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401

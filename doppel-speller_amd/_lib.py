@@ -10,7 +10,8 @@ _ROOT = os.path.dirname(_HERE)
 _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jaccard_narrow.hip", "ds_features.hip",
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
             "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
-            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip", "ds_assign.hip")
+            "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip", "ds_assign.hip",
+            "ds_hard.hip")
 _lib = None
 
 
@@ -216,6 +217,10 @@ def _declare(handle):
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
+        "ds_hard_negatives_device": [p, p, c.c_int64, c.c_int32, c.c_int64, p, p, c.c_int32, c.c_int32, c.c_float, c.c_int64,
+                                     p, p, c.c_int64, p, p, p, p, p],
+        "ds_hard_total": [p, c.POINTER(c.c_int64), p],
+        "ds_hard_option": [c.c_char_p, c.c_int64],
         "ds_prepare_titles": [p, p, c.c_int64, c.c_int32, c.c_int, p, c.POINTER(p), p],
         "ds_query_space_create": [p, p, p, c.c_int64, c.c_int, c.POINTER(p)],
         "ds_query_rows_device": [p, p, c.c_int64, c.c_int64, p, p, p, c.c_int64, p],
@@ -277,7 +282,7 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes",
     "ds_index_create_device", "ds_index_read", "ds_index_build_option", "ds_assign_edges_device",
     "ds_assign_solve_device", "ds_assign_option", "ds_trainer_seed", "ds_trainer_seed_device", "ds_trainer_batch_seed",
-    "ds_trainer_batch_seed_device")
+    "ds_trainer_batch_seed_device", "ds_hard_negatives_device", "ds_hard_total", "ds_hard_option")
 
 
 def lib():

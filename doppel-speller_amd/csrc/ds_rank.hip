@@ -51,7 +51,7 @@ __device__ __forceinline__ RankHead rank_head(const int32_t *exact_row, const in
 __device__ __forceinline__ uint64_t rank_key(int32_t row, float probability, int32_t j, int32_t head, int64_t n_truth)
 {
     const bool valid = row >= 0 && row < n_truth && row != head;
-    return valid ? (static_cast<uint64_t>(__float_as_uint(probability)) << 32) | static_cast<uint32_t>(~j) : 0ull;
+    return valid ? position_key(__float_as_uint(probability), j) : 0ull;
 }
 
 // slot 0 of a query with a head (one lane); first_j: the first candidate that equals the head, k when none does
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kRankThreads) void ds_rank_select_kernel(
             best = wave_max(best);
             if (best == 0) break;          // the same in every lane: the rest is exhausted
             if (lane == 0) {
-                const int32_t j = static_cast<int32_t>(~static_cast<uint32_t>(best));
+                const int32_t j = key_position(best);
                 out_row[out + filled] = rows[in + j];
                 out_probability[out + filled] = __uint_as_float(static_cast<uint32_t>(best >> 32));
                 out_ratio[out + filled] = ratios[in + j];

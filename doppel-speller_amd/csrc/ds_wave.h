@@ -1,5 +1,5 @@
 // The wave-level and workgroup-level building blocks of the device stages, in one place: reductions over the 64 lanes
-// of a wave, the exclusive scan of a workgroup and the two tile bodies of a stable LSD radix sort by 8-bit digits.
+// of a wave, the key of a ranked candidate, the exclusive scan of a workgroup and the two tile bodies of a stable LSD radix sort by 8-bit digits.
 // Device functions only, no kernels: every translation unit may include this header.
 //
 // All of them work on integers, so no result depends on the order in which values are combined, and every position
@@ -54,6 +54,15 @@ __device__ __forceinline__ T wave_and(T value)
 {
     return wave_reduce(value, [](T a, T b) { return static_cast<T>(a & b); });
 }
+
+// ---- the key of candidate j of a list: `high` decides, the smaller j wins among equals ------------------------------------
+// Distinct for distinct j and never 0 (j >= 0), so 0 can stand for "no candidate"; wave_max over the keys of a list is
+// its best candidate (ds_rank.hip, ds_hard.hip).
+__device__ __forceinline__ uint64_t position_key(uint32_t high, int32_t j)
+{
+    return (static_cast<uint64_t>(high) << 32) | static_cast<uint32_t>(~j);
+}
+__device__ __forceinline__ int32_t key_position(uint64_t key) { return static_cast<int32_t>(~static_cast<uint32_t>(key)); }
 
 // ---- exclusive scan over a workgroup ---------------------------------------------------------------------------------
 // Exclusive prefix of `value` over the Threads threads of the workgroup, and the total: an inclusive scan inside each

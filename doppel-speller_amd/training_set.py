@@ -34,13 +34,17 @@ from .distributed import slice_queries
 from .feature_engineering import (ALLOWED_CHARACTERS, FEATURES_COUNT, MAX_CHARACTERS_ALLOWED_IN_THE_TITLE, SPACE_CODE,
                                   TitleTable, encode_collection)
 from .match_maker import validate_index_build
-from .prediction import (TRAIN_NOT_FOUND_VALUE, TruthSide, _CODE_OF, _pack, _validate_chunk, check_characters,
+from .forest import ForestModel
+from .prediction import (TRAIN_NOT_FOUND_VALUE, StageClock, TruthSide, _CODE_OF, _pack, _validate_chunk, check_characters,
                          default_chunk, transform_or_keep, validate_truth)
 
 KIND_GENERATED, KIND_NEGATIVE, KIND_POSITIVE = 1, 2, 3          # constants.py:46-48
 EVALUATION_FRACTIONS = {"generated": 0.05, "negative": 0.10, "positive": 0.05}   # settings.py:47-49
 GENERATED_MIN_LENGTH = 9                                          # feature_engineering.py:183-184: longer than 9
 MAX_SAMPLE = 16                                                   # the sampler keeps its swap map in registers
+MAX_HARD = 16                                                     # mined pairs per title at most (ds_hard_negatives_device)
+HARD_COLUMNS = ("query_index", "truth_row", "position", "margin", "probability")
+HARD_STAGES = ("top_k", "features", "model", "select", "mined_features", "copy_back")
 _TEXT_OF = np.frombuffer(ALLOWED_CHARACTERS.encode("ascii"), dtype=np.uint8)
 
 
@@ -84,6 +88,32 @@ def validate_training(truth_titles, truth_title_ids, train_titles, train_title_i
     truth_rows = np.full(ids.shape[0], -1, dtype=np.int64)
     truth_rows[found] = order[at]
     return truth_ids, ids, truth_rows
+
+
+def validate_hard(model, hard_n, min_margin, exclude_sampled, top_n, sample_n, device=None):
+    """The checks of generate_hard_negatives (no library needed) -> (hard_n, min_margin as a float, -inf for None):
+    `model` an open ForestModel of 66 features (on `device`, when given), hard_n an integer in 1 .. 16 and at most
+    top_n, min_margin None or a finite real, exclude_sampled a bool."""
+    if not isinstance(model, ForestModel):
+        raise ValueError(f"model must be a ForestModel, not {type(model).__name__}")
+    if not model.handle:
+        raise ValueError("model is closed")
+    if model.n_features != FEATURES_COUNT:
+        raise ValueError(f"model has {model.n_features} features, construct_features makes {FEATURES_COUNT}")
+    if device is not None and model.device != device:
+        raise ValueError(f"model lives on device {model.device}, the training set on device {device}")
+    hard_n = _integer("hard_n", hard_n, 1, MAX_HARD)
+    if hard_n > top_n:
+        raise ValueError(f"hard_n = {hard_n} exceeds top_n = {top_n}")
+    if min_margin is not None:
+        if isinstance(min_margin, bool) or not isinstance(min_margin, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(min_margin):
+            raise ValueError(f"min_margin must be None or a finite number, not {min_margin!r}")
+    if not isinstance(exclude_sampled, (bool, np.bool_)):
+        raise ValueError(f"exclude_sampled must be a bool, not {exclude_sampled!r}")
+    if exclude_sampled and sample_n > MAX_SAMPLE:
+        raise ValueError(f"exclude_sampled holds sample_n = {sample_n} rows per title, at most {MAX_SAMPLE}")
+    return hard_n, float("-inf") if min_margin is None else float(min_margin)
 
 
 def row_plan(truth_rows):
@@ -200,6 +230,29 @@ class DeviceDataSets:
         """The queries of the kind 1 rows, in order, decoded from the device table."""
         return self._misspelled.strings() if self._misspelled is not None else []
 
+    def with_hard_negatives(self, hard):
+        """A new DeviceDataSets whose training matrix in HBM is this one's rows followed by the mined rows of `hard`
+        (a DeviceHardNegatives), its train_target extended by their zeros; the evaluation part is a copy of this one's.
+        Device copies only: ForestTrainer.fit_device(..., init_model=model) takes the result without the matrix leaving
+        HBM.  The new object owns its matrices (free() of either leaves the other whole); the misspelled titles and a
+        kept `features` stay with this one."""
+        if not isinstance(hard, DeviceHardNegatives):
+            raise ValueError(f"hard must be a DeviceHardNegatives, not {type(hard).__name__}")
+        device, row_bytes = self.train.device, FEATURES_COUNT * 4
+        if hard.features.device != device:
+            raise ValueError(f"the mined rows live on device {hard.features.device}, the training set on device {device}")
+        library, n = _lib.lib(), self.n_train + hard.n
+        train = _lib.DeviceArray((max(n, 1), FEATURES_COUNT), np.float32, device)
+        evaluation = _lib.DeviceArray((max(self.n_evaluation, 1), FEATURES_COUNT), np.float32, device)
+        for target, offset, source, rows in ((train, 0, self.train, self.n_train), (train, self.n_train, hard.features, hard.n),
+                                             (evaluation, 0, self.evaluation, self.n_evaluation)):
+            if rows:
+                _lib.check(library.ds_memcpy_d2d_async(ctypes.c_void_p(target.ptr.value + offset * row_bytes), source.ptr,
+                                                       rows * row_bytes, device, None), "ds_memcpy_d2d_async")
+        _lib.check(library.ds_stream_sync(None, device), "ds_stream_sync")
+        return DeviceDataSets(train, n, np.concatenate((self.train_target, hard.target)).astype(np.float32), evaluation,
+                              self.n_evaluation, self.evaluation_target, None, None, self.n_rows + hard.n)
+
     def free(self):
         """Frees the matrices in HBM (the labels stay)."""
         for array in (self.train, self.evaluation, self.features):
@@ -207,6 +260,23 @@ class DeviceDataSets:
                 array.free()
         if self._misspelled is not None:
             self._misspelled.close()
+
+
+class DeviceHardNegatives:
+    """The mined rows with their feature matrix in HBM (FeatureEngineering.generate_device_hard_negatives): `features`
+    is a DeviceArray float32[max(n, 1), 66] of which the first n rows count, `target` the host float32[n] labels, all
+    zeros: every mined row is a negative."""
+
+    def __init__(self, features, n):
+        self.features, self.n = features, int(n)
+        self.target = np.zeros(self.n, dtype=np.float32)
+
+    def to_host(self):
+        """(features float32[n, 66], target float32[n]) as generate_hard_negatives returns them."""
+        return self.features.to_host(self.n), self.target
+
+    def free(self):
+        self.features.free()
 
 
 class FeatureEngineering:
@@ -223,7 +293,11 @@ class FeatureEngineering:
     After a call: `rows` (DataFrame: kind, query_index = train row for kinds 2 / 3 and truth row for kind 1,
     truth_row, target, evaluation), `misspelled_titles` (the queries of the kind 1 rows, in order), `features` (every
     row's construct_features) and `timings` (milliseconds per stage).  generate_device_data_sets() is the form that
-    leaves the matrices in HBM (DeviceDataSets)."""
+    leaves the matrices in HBM (DeviceDataSets).
+
+    generate_hard_negatives(model) / generate_device_hard_negatives(model) mine, for the same train titles, the wrong
+    candidates `model` likes best (this project's own, DESIGN.md section 8 "Hard negatives"); they fill `hard_rows` and
+    `hard_timings` and leave `rows`, `features` and `timings` alone."""
 
     def __init__(self, truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0,
                  device=0, transform=True, chunk_queries=None, evaluation_fractions=None, build_index="host"):
@@ -241,9 +315,10 @@ class FeatureEngineering:
         self.device, self.transform, self.chunk_queries = device, transform, chunk_queries
         self._raw_truth, self._raw_train = truth_titles, train_titles
         self.build_index = build_index
-        self._truth = None
+        self._truth = self._queries = None
         self.rows = self.misspelled_titles = self.features = None
         self.timings = {}
+        self.hard_rows, self.hard_timings = None, {}
 
     def generate_train_and_evaluation_data_sets(self):
         """feature_engineering.py:321-378: (train, train_target, evaluation, evaluation_target)."""
@@ -306,6 +381,136 @@ class FeatureEngineering:
         return DeviceDataSets(parts[0], train_rows.shape[0], target[train_rows], parts[1], evaluation_rows.shape[0],
                               target[evaluation_rows], stage["misspelled"], d_features if keep_features else None, n_rows)
 
+    def _truth_side(self, timings, started):
+        """The TruthSide of this object, made by the first call that needs it (its times go to `timings`)."""
+        if self._truth is None:
+            self.truth_titles = transform_or_keep(self._raw_truth, self.transform)
+            self.train_titles = transform_or_keep(self._raw_train, self.transform)
+            timings["host_prepare"] += (time.perf_counter() - started) * 1000.0
+            mark = time.perf_counter()
+            self._truth = TruthSide(self.truth_titles, self.device, build_index=self.build_index)
+            timings["truth_side"] = (time.perf_counter() - mark) * 1000.0
+        return self._truth
+
+    def _selected_queries(self):
+        """The train rows that produce rows (kinds 2 and 3, in that order) as queries of the truth side, made once:
+        (negative, positive, selected, own truth rows int32, q_rowptr, q_cols, q_maxint, their TitleTable); the last
+        four are None when no train row is selected."""
+        if self._queries is None:
+            negative, positive = row_plan(self.train_truth_rows)
+            selected = np.concatenate((negative, positive))
+            own = self.train_truth_rows[selected].astype(np.int32)
+            rows = (None, None, None, None)
+            if selected.shape[0]:
+                chars, offsets = _pack([self.train_titles[i] for i in selected])
+                check_characters(chars, offsets, "train")
+                enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+                rows = self._truth.query_rows(chars, offsets) + (TitleTable(enc, lengths, None, self.device),)
+            self._queries = (negative, positive, selected, own) + rows
+        return self._queries
+
+    def generate_hard_negatives(self, model, hard_n=5, min_margin=None, exclude_sampled=True):
+        """The hard negatives of `model` -> (features float32[m, 66], target float32[m], all zeros).  For every train
+        title of the base set (the kind 2 and kind 3 rows, in that order) all top_n candidates are scored by the model
+        on the device, and the hard_n (1 .. 16) with the highest margins are kept that are not the title's own truth
+        row, whose margin is above min_margin (None: no threshold; log(9) is the margin of probability 0.9: then only
+        the false positives of the decision rule are mined) and, with exclude_sampled, that the base set did not draw
+        for the title (so base set plus mined rows hold no (title, truth row) pair twice; this needs the base set
+        generated by this object first).  Equal margins go to the candidate that is earlier in the Jaccard order.  The
+        result does not depend on chunk_queries.  Only the mined pairs and their features travel back.
+
+        After a call: `hard_rows` (DataFrame: query_index = train row, truth_row, position in the Jaccard list, margin,
+        probability = the float32 sigmoid of the margin) and `hard_timings` (milliseconds per stage); `rows`,
+        `features` and `timings` of the base set are left alone."""
+        hard = self.generate_device_hard_negatives(model, hard_n, min_margin, exclude_sampled)
+        mark = time.perf_counter()
+        out = hard.to_host()
+        hard.free()
+        self.hard_timings["copy_back"] += (time.perf_counter() - mark) * 1000.0
+        return out
+
+    def generate_device_hard_negatives(self, model, hard_n=5, min_margin=None, exclude_sampled=True):
+        """generate_hard_negatives with the mined feature matrix left in HBM -> DeviceHardNegatives, for
+        DeviceDataSets.with_hard_negatives.  Per chunk of titles every stage is enqueued on the device: the top_n rows,
+        construct_features of every (title, candidate), the model's margins, the selection
+        (ds_hard_negatives_device), which appends to four dense arrays in HBM behind a running total.  After the last
+        chunk the total is read, one construct_features call over the mined pairs makes their matrix (at most hard_n /
+        top_n of the work of the first), and the four mined arrays come back for `hard_rows`."""
+        hard_n, threshold = validate_hard(model, hard_n, min_margin, exclude_sampled, self.top_n, self.sample_n,
+                                          self.device)
+        if exclude_sampled and self.rows is None:
+            raise ValueError("exclude_sampled=True leaves out the pairs the base set drew: generate the base set with "
+                             "this object first, or pass exclude_sampled=False")
+        import pandas as pd
+        device, k = self.device, self.top_n
+        timings = dict.fromkeys(HARD_STAGES, 0.0)
+        truth = self._truth_side(dict(host_prepare=0.0), time.perf_counter())
+        n_truth = truth.table.n
+        _, _, selected, own, q_rowptr, q_cols, q_maxint, query_table = self._selected_queries()
+        n_selected = selected.shape[0]
+        n_exclude = self.sample_n if exclude_sampled else 0
+        if exclude_sampled:
+            sampled = self.rows["truth_row"].to_numpy()[:n_selected * n_exclude]
+            if self.rows.shape[0] < n_selected * n_exclude or \
+                    not np.array_equal(self.rows["query_index"].to_numpy()[:n_selected * n_exclude],
+                                       np.repeat(selected, n_exclude)):
+                raise ValueError("`rows` is not the base set of this object: generate the base set first, or pass "
+                                 "exclude_sampled=False")
+            sampled = np.ascontiguousarray(sampled.reshape(n_selected, n_exclude), dtype=np.int32)
+
+        library, clock = _lib.lib(), StageClock(timings, device)
+        capacity = n_selected * hard_n
+        d_total = _lib.DeviceArray.from_host(np.zeros(1, np.int64), device)
+        mined = [_lib.DeviceArray((max(capacity, 1),), dtype, device) for dtype in (np.int32, np.int32, np.int32, np.float32)]
+        if n_selected:
+            chunk = min(n_selected, self.chunk_queries or default_chunk(device, k * (FEATURES_COUNT * 4 + 8) + 80))
+            d_rows = _lib.DeviceArray((chunk, k), np.int32, device)
+            d_features = _lib.DeviceArray((chunk * k, FEATURES_COUNT), np.float32, device)
+            d_margins = _lib.DeviceArray((chunk * k,), np.float32, device)
+            d_offsets = _lib.DeviceArray((chunk,), np.int64, device)
+            d_own = _lib.DeviceArray.from_host(own, device)
+            for first in range(0, n_selected, chunk):
+                last = min(n_selected, first + chunk)
+                n = last - first
+                rowptr, cols, maxint = slice_queries(q_rowptr, q_cols, q_maxint, first, last)
+                d_rowptr = _lib.DeviceArray.from_host(rowptr, device)
+                d_cols = _lib.DeviceArray.from_host(cols if cols.shape[0] else np.zeros(1, np.int32), device)
+                d_maxint = _lib.DeviceArray.from_host(maxint, device)
+                d_exclude = _lib.DeviceArray.from_host(sampled[first:last], device) if n_exclude else None
+                clock.device("top_k", lambda: truth.index.top_k_device(d_rowptr, d_cols, d_maxint, n, k, d_rows))
+                truth.index.sync()
+                clock.device("features", lambda: _lib.check(library.ds_construct_features_indexed_device(
+                    query_table.handle, truth.table.handle, None, d_rows.ptr, first, k, SPACE_CODE, n_truth, n * k,
+                    d_features.ptr, None), "ds_construct_features_indexed_device"))
+                clock.device("model", lambda: model.predict_device(d_features, n * k, d_margins, None))
+                clock.device("select", lambda: _lib.check(library.ds_hard_negatives_device(
+                    d_rows.ptr, d_margins.ptr, n, k, n_truth, ctypes.c_void_p(d_own.ptr.value + 4 * first),
+                    _lib.pointer(d_exclude), n_exclude, hard_n, ctypes.c_float(threshold), first, d_offsets.ptr,
+                    d_total.ptr, capacity, *(a.ptr for a in mined), None), "ds_hard_negatives_device"))
+                clock.collect()
+            for array in (d_rows, d_features, d_margins, d_offsets, d_own):
+                array.free()
+        total = ctypes.c_int64(0)
+        _lib.check(library.ds_hard_total(d_total.ptr, ctypes.byref(total), None), "ds_hard_total")
+        m = int(total.value)
+
+        d_mined = _lib.DeviceArray((max(m, 1), FEATURES_COUNT), np.float32, device)
+        if m:
+            clock.device("mined_features", lambda: _lib.check(library.ds_construct_features_indexed_device(
+                query_table.handle, truth.table.handle, mined[0].ptr, mined[1].ptr, 0, 1, SPACE_CODE, n_truth, m,
+                d_mined.ptr, None), "ds_construct_features_indexed_device"))
+            clock.collect()
+        with clock.host("copy_back"):
+            pair_q, pair_t, position, margin = (a.to_host(m) for a in mined)
+        for array in mined + [d_total]:
+            array.free()
+        with np.errstate(over="ignore"):
+            probability = (np.float32(1.0) / (np.float32(1.0) + np.exp(-margin))).astype(np.float32)
+        self.hard_rows = pd.DataFrame(dict(zip(HARD_COLUMNS, (selected[pair_q].astype(np.int64), pair_t.astype(np.int64),
+                                                              position, margin, probability))))
+        self.hard_timings = timings
+        return DeviceHardNegatives(d_mined, m)
+
     def _pairs_to_host(self, stage):
         """The sampled pairs' truth rows and targets (8 B per row of kinds 2 and 3)."""
         if not stage["n_selected"]:
@@ -335,33 +540,17 @@ class FeatureEngineering:
         one matrix in HBM."""
         started = time.perf_counter()
         device, k, sample_n = self.device, self.top_n, self.sample_n
-        if self._truth is None:
-            self.truth_titles = transform_or_keep(self._raw_truth, self.transform)
-            self.train_titles = transform_or_keep(self._raw_train, self.transform)
-            timings["host_prepare"] += (time.perf_counter() - started) * 1000.0
-            mark = time.perf_counter()
-            self._truth = TruthSide(self.truth_titles, device, build_index=self.build_index)
-            timings["truth_side"] = (time.perf_counter() - mark) * 1000.0
-        truth = self._truth
+        truth = self._truth_side(timings, started)
         n_truth = truth.table.n
 
         # ---- which train rows, in what order (kinds 2 and 3), and which truth rows are misspelled (kind 1)
         mark = time.perf_counter()
-        negative, positive = row_plan(self.train_truth_rows)
-        selected = np.concatenate((negative, positive))
+        negative, positive, selected, own, q_rowptr, q_cols, q_maxint, query_table = self._selected_queries()
         n_selected = selected.shape[0]
-        own = self.train_truth_rows[selected].astype(np.int32)
         truth_lengths = np.array([len(t) for t in self.truth_titles], dtype=np.int64)
         generated = np.nonzero(truth_lengths > GENERATED_MIN_LENGTH)[0].astype(np.int32)
         n_pairs = n_selected * sample_n
         n_rows = n_pairs + generated.shape[0]
-        query_table = None
-        if n_selected:
-            chars, offsets = _pack([self.train_titles[i] for i in selected])
-            check_characters(chars, offsets, "train")
-            q_rowptr, q_cols, q_maxint = truth.query_rows(chars, offsets)
-            enc, lengths = encode_collection(chars, offsets, _CODE_OF)
-            query_table = TitleTable(enc, lengths, None, device)
         d_features = _lib.DeviceArray((max(n_rows, 1), FEATURES_COUNT), np.float32, device)
         timings["host_prepare"] += (time.perf_counter() - mark) * 1000.0
 

@@ -760,6 +760,38 @@ int ds_training_pairs_device(const int32_t *d_rows, int64_t n_queries, int32_t t
                              const int64_t *d_stream_index, const int32_t *d_own_row, uint64_t seed, int64_t q_first,
                              int32_t *d_pair_q, int32_t *d_pair_t, float *d_target, void *stream);
 
+/* ---- hard negatives: the wrong candidates a model likes best, mined on the device -----------------
+ * The project's own rule; the reference draws its negatives at random (feature_engineering_prepare.py:25-57).  For title
+ * i of a chunk of n_queries titles, over the candidates j = 0 .. k-1 with truth row c_j = d_rows[i*k + j] and margin m_j =
+ * d_margins[i*k + j] (finite):
+ *   eligible  0 <= c_j < n_truth, c_j != d_own_row[i] (-1: the title has no truth row), c_j not among d_exclude[i *
+ *             n_exclude .. (i + 1) * n_exclude) (entries of -1 are ignored; n_exclude = 0 is legal and d_exclude may then
+ *             be NULL), and m_j > min_margin: strict, both sides float32; -INFINITY means no threshold;
+ *   order     by the 64-bit key (ord(m_j) << 32) | (uint32)~j descending.  ord is the monotone map of the float32 bits: all
+ *             bits flipped when the sign bit is set, else the sign bit set.  So -0.0 sorts below +0.0 and equal margins go
+ *             to the smaller j.  The keys of a title are distinct and never 0; 0 stands for "not eligible";
+ *   yield     the first min(hard_n, eligible) candidates in that order; that may be none.
+ * The output is dense: titles in title order, within a title in key order.  With *d_total = T on entry, the mined pairs of
+ * this chunk take the slots T, T + 1, ... of four parallel arrays: d_pair_q = q_first + i, d_pair_t = c_j, d_position = j,
+ * d_margin = m_j; on exit *d_total = T + the pairs of this chunk, so the next chunk continues there and the result does
+ * not depend on how the titles are cut into chunks (nor on the grid: ds_hard_option("max_blocks", v), v in [0, 65536], 0 =
+ * the default of 4096, is for tests).  Every mined pair is a negative: there is no target array.  Start *d_total at 0.
+ * d_offsets: int64[n_queries] of scratch in HBM (a title's count, then its first slot).
+ * Capacity: no slot >= capacity is ever written.  A chunk that would pass it leaves *d_total negative (minus the pairs
+ * needed so far); every later chunk keeps it so and writes nothing.
+ * DS_E_ARG before any device work: a null pointer, hard_n outside 1 .. min(16, k), n_exclude outside 0 .. 16, n_exclude
+ * > 0 with a null d_exclude, a negative count, a NaN min_margin.  n_queries == 0 is DS_OK and launches nothing.
+ * ds_hard_negatives_device enqueues three kernels on `stream` and does not synchronise.
+ * ds_hard_total synchronises `stream` and reads the cell: *total = the pairs mined (needed, when the capacity was
+ * passed: then the status is DS_E_ARG). */
+int ds_hard_negatives_device(const int32_t *d_rows, const float *d_margins, int64_t n_queries, int32_t k,
+                             int64_t n_truth, const int32_t *d_own_row, const int32_t *d_exclude, int32_t n_exclude,
+                             int32_t hard_n, float min_margin, int64_t q_first, int64_t *d_offsets, int64_t *d_total,
+                             int64_t capacity, int32_t *d_pair_q, int32_t *d_pair_t, int32_t *d_position,
+                             float *d_margin, void *stream);
+int ds_hard_total(const int64_t *d_total, int64_t *total, void *stream);
+int ds_hard_option(const char *name, int64_t value);
+
 /* ---- query side of Prediction on the device ("Query preparation") ---------------------------------
  * ds_prepare_titles: the n raw titles chars[offsets[i] .. offsets[i + 1]) (host pointers, offsets[0] = 0) are uploaded and
  * put through the byte work of ds_transform_titles (transform = 1: lower case, '-' -> ' ', keep [a-z0-9] and ASCII white
