@@ -607,7 +607,8 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
     DS_HIP(hipMemset(index->signature.ptr, 0, index->signature.bytes()));
     DS_BUILD_STEP(index->row_start.allocate(static_cast<size_t>(N + 1) * 4));
     DS_HIP(hipMemset(index->row_start.ptr, 0, index->row_start.bytes()));
-    DS_BUILD_STEP(index->row_cols.allocate(std::max<size_t>(4, static_cast<size_t>(nnz) * (wide_cols ? 4 : 2))));
+    // the host's size, which ds_index_info reports: the columns themselves, 4 bytes only when there is none
+    DS_BUILD_STEP(index->row_cols.allocate(nnz > 0 ? static_cast<size_t>(nnz) * (wide_cols ? 4 : 2) : 4));
     DS_BUILD_STEP(index->col_ptr.allocate(static_cast<size_t>(cells)));
     DS_BUILD_STEP(index->tile_sums_min.allocate(static_cast<size_t>(n_tiles)));
     DS_BUILD_STEP(index->tile_sums_max.allocate(static_cast<size_t>(n_tiles)));
