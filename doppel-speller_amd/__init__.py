@@ -48,6 +48,12 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         the wrong candidates the model likes best, scored and selected on the device; DeviceDataSets.
         with_hard_negatives(hard) appends them to the training matrix in HBM for fit_device(..., init_model=model)
         (this project's own)
+    ForestTrainer.fit(..., sample_weight=w), ForestTrainerBatch.begin(..., sample_weight=w), cross_validate(...,
+        sample_weight=w), train_model(..., kind_weights={"generated": 0.5, "positive": 2}), tune_model_parameters(...,
+        kind_weights=)   -> per-row weights in the objective (xgb.DMatrix(weight=...)): a row's gradient and hessian times
+        its weight, on the device; cuts, subsample draws, errors, metrics and cover stay unweighted;
+        validate_sample_weight(w, n, beta) says what is accepted, kind_weights(rows, weights) weighs a training set's
+        rows by their kind (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -66,9 +72,9 @@ from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMN
                          assignment_frame, duplicate_frame, predictions_accuracy, top_contributions,
                          validate_assignment, validate_duplicates, validate_exhaustive, validate_rank, validate_sweep)
 from .training_set import (DeviceDataSets, DeviceHardNegatives, FeatureEngineering, generate_misspelled_names,  # noqa: F401
-                           validate_hard)
+                           kind_weights, validate_hard)
 from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
-                    evaluation_error_matrix, roc_auc, train_model, validate_init_model)
+                    evaluation_error_matrix, roc_auc, train_model, validate_init_model, validate_sample_weight)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -76,6 +76,7 @@ struct TrainModel {
 struct TrainView {   // what every kernel of a round gets
     const uint8_t *bins;
     const float *labels;
+    const float *weights;         // per-row sample weights, stride 0 like labels; null: every row weighs 1
     const uint8_t *fold;          // null without folds: the kFolds = false kernels never read it
     const int32_t *cut_offsets;
     const TrainModel *models;     // in HBM, with `active`; both null in a view of ONE model: model 0, the record `only`
@@ -140,6 +141,9 @@ int train_check_labels(const char *who, const char *what, const float *labels, i
 // the three fractions in (0, 1]; reg_lambda > 0 where rows are drawn; model as for train_check_params
 int train_check_fractions(const char *who, int32_t model, const double *fractions);
 int train_check_subsample(const char *who, int32_t model, double subsample, double reg_lambda);
+// Sample weights ("Sample weights"): every weight finite and >= 0, and the overflow guard
+// max(beta, 1) * sum(weights) <= 2^32 with the sum in double; beta is the largest among the models that share the array
+int train_check_weights(const char *who, const float *weights, int64_t n, double beta);
 // What a create entry sets up on the current device: its stream, the cuts in HBM and the compute-unit count
 int train_create_setup(const char *who, int device, int32_t n_features, const float *cuts, const int32_t *cut_offsets,
                        hipStream_t *stream, DeviceBuffer<float> &d_cuts, DeviceBuffer<int32_t> &d_cut_offsets,
@@ -177,8 +181,9 @@ int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *f
 template <bool kFolds, bool kSampled = false>
 __device__ inline void train_gradient_rows(const float *leafsum, const float *labels, int64_t n, float base_margin,
                                            double beta, float *probabilities, long long *gh, int32_t *node_of,
-                                           const uint8_t *fold, int32_t held_out, const TrainSampling *sampling = nullptr,
-                                           int64_t tree = 0, const uint32_t *held_before = nullptr)
+                                           const uint8_t *fold, int32_t held_out, const float *weights,
+                                           const TrainSampling *sampling = nullptr, int64_t tree = 0,
+                                           const uint32_t *held_before = nullptr)
 {
     for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
          r += static_cast<int64_t>(gridDim.x) * kRowThreads) {
@@ -186,8 +191,9 @@ __device__ inline void train_gradient_rows(const float *leafsum, const float *la
         const float p = 1.0f / (1.0f + expf(-margin));   // ds_forest.hip's rule
         const double y = labels[r], pd = p;
         const double w = beta + y - beta * y;
-        const double g = pd * w - y;
-        const double h = pd * (1.0 - pd) * w;
+        const double s = weights != nullptr ? weights[r] : 1.0;
+        const double g = (pd * w - y) * s;
+        const double h = (pd * (1.0 - pd) * w) * s;
         bool trains = !kFolds || static_cast<int32_t>(fold[r]) != held_out;
         if (kSampled && sampling->subsample < 1.0) {   // the same answer in every row of a model
             int64_t row = r;

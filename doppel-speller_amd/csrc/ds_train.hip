@@ -5,6 +5,7 @@
 // Data in HBM, per training matrix (n rows, nf features):
 //   bins      uint8[nf][n]   feature-major: bin b < 255 of a value, 255 = NaN (the missing bin)
 //   gh        int64[n][2]    quantized gradient and hessian of the current round, rint(g * 2^30), rint(h * 2^30)
+//   weights   float[n]       only after ds_trainer_set_weights: g and h are multiplied by the row's weight first
 //   node_of   int32[n]       heap id of the node a row sits in while a tree grows (-1: its leaf is already added)
 //   leafsum   float[n]       sum of the leaves of the trees so far, in tree order (margin = kTrainBaseMargin + leafsum)
 //   hist      int64[2^D - 1][nf][256][2]  per split candidate node (heap order, levels 0..D-1): (sum qg, sum qh)
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_gradient_kernel(TrainVie
     if (kFolds && kSampled && s.held_slot[m] >= 0) held_before = s.held_before + s.held_slot[m] * s.held_stride;
     train_gradient_rows<kFolds, kSampled>(v.leafsum + m * v.n, v.labels, v.n, kTrainBaseMargin, model.params.beta,
                                           v.probabilities + m * v.n, v.gh + 2 * m * v.n, v.node_of + m * v.n, v.fold,
-                                          model.held_out, kSampled ? &sampling : nullptr,
+                                          model.held_out, v.weights, kSampled ? &sampling : nullptr,
                                           kSampled ? s.tree_of(m) : 0, held_before);
 }
 
@@ -358,6 +359,21 @@ int train_check_subsample(const char *who, int32_t model, double subsample, doub
     return DS_OK;
 }
 
+int train_check_weights(const char *who, const float *weights, int64_t n, double beta)
+{
+    double total = 0.0;
+    for (int64_t r = 0; r < n; ++r) {
+        DS_REQUIRE(std::isfinite(weights[r]), "%s: weight %lld is not finite", who, (long long)r);
+        DS_REQUIRE(weights[r] >= 0.f, "%s: weight %lld is negative", who, (long long)r);
+        total += static_cast<double>(weights[r]);
+    }
+    // |g| <= max(beta, 1) * s_r and a histogram cell sums at most all rows: every int64 sum stays below 2^62 + n
+    DS_REQUIRE(std::max(beta, 1.0) * total <= 4294967296.0,
+               "%s: max(beta, 1) * the total weight = %g exceeds 2^32 (the integer sums could overflow)", who,
+               std::max(beta, 1.0) * total);
+    return DS_OK;
+}
+
 int train_create_setup(const char *who, int device, int32_t n_features, const float *cuts, const int32_t *cut_offsets,
                        hipStream_t *stream, DeviceBuffer<float> &d_cuts, DeviceBuffer<int32_t> &d_cut_offsets,
                        int *compute_units)
@@ -509,11 +525,13 @@ struct ds_trainer {
     int32_t nf = 0;
     ds::TrainParams params{};
     bool has_labels = false, seeded = false;      // seeded: ds_trainer_seed has started the margins from a forest
+    bool weighted = false;                        // ds_trainer_set_weights has been accepted
     int64_t rounds = 0;
     int32_t tree_base = 0;                        // the trees of that forest: the number of this trainer's first tree
     hipStream_t stream = nullptr;
     ds::DeviceBuffer<uint8_t> bins, eval_bins;
     ds::DeviceBuffer<float> labels, eval_labels, leafsum, eval_leafsum, probabilities, cuts;
+    ds::DeviceBuffer<float> weights;              // ds_trainer_set_weights: float[n], 4n more bytes
     ds::DeviceBuffer<int32_t> cut_offsets, node_of, counts;
     ds::DeviceBuffer<long long> gh, hist;
     ds::DeviceBuffer<ds::Node> nodes;
@@ -605,7 +623,7 @@ int create_trainer(const char *who, const float *features, bool in_hbm, int64_t 
         delete t;
         return status;
     }
-    t->view = ds::TrainView{t->bins.ptr, t->labels.ptr, nullptr, t->cut_offsets.ptr, nullptr, nullptr,
+    t->view = ds::TrainView{t->bins.ptr, t->labels.ptr, nullptr, nullptr, t->cut_offsets.ptr, nullptr, nullptr,
                             t->gh.ptr, t->node_of.ptr, t->leafsum.ptr, t->probabilities.ptr, t->hist.ptr, t->nodes.ptr,
                             t->counts.ptr, t->candidates.ptr, t->error.ptr, n, hist_bytes / 8,
                             ds::candidate_entries(max_depth, n_features), n_features,
@@ -725,6 +743,29 @@ int ds_trainer_set_labels(ds_trainer *trainer, const float *labels)
                           trainer->stream));
     DS_HIP(hipStreamSynchronize(trainer->stream));
     trainer->has_labels = true;
+    return DS_OK;
+}
+
+int ds_trainer_set_weights(ds_trainer *trainer, const float *weights)
+{
+    const char *who = "ds_trainer_set_weights";
+    DS_REQUIRE(trainer != nullptr, "%s: trainer is null", who);
+    DS_REQUIRE(weights != nullptr, "%s: weights is null", who);
+    ds_trainer *t = trainer;
+    DS_REQUIRE(t->has_labels, "%s: no labels (ds_trainer_set_labels)", who);
+    DS_REQUIRE(t->rounds == 0, "%s: the weights must be set before the first round", who);
+    DS_REQUIRE(!t->weighted, "%s: the weights are already set", who);
+    if (int status = ds::train_check_weights(who, weights, t->n, t->params.beta); status != DS_OK) return status;
+    bool positive = false;
+    for (int64_t r = 0; r < t->n && !positive; ++r) positive = weights[r] > 0.f;
+    DS_REQUIRE(positive, "%s: the total weight of the training rows is 0", who);
+    DS_HIP(hipSetDevice(t->device));
+    if (int status = check_free(t->n * 4, who); status != DS_OK) return status;
+    if (int status = t->weights.allocate(static_cast<size_t>(t->n)); status != DS_OK) return status;
+    DS_HIP(hipMemcpyAsync(t->weights.ptr, weights, sizeof(float) * t->n, hipMemcpyHostToDevice, t->stream));
+    DS_HIP(hipStreamSynchronize(t->stream));
+    t->view.weights = t->weights.ptr;
+    t->weighted = true;
     return DS_OK;
 }
 

@@ -32,6 +32,11 @@
 //   metric_scratch                    two key buffers and a count table per model, for the largest fold's negatives
 //   metric_counters uint64[M][6]      copied back whole with the step's other results; the host keeps the active models'
 //
+// Sample weights (ds_trainer_batch_set_weights; DESIGN.md section 9, "Sample weights"): ONE float[n] shared by the models,
+// like the labels (TrainView::weights, stride 0); the gradient kernel multiplies a row's (g, h) by its weight, and a
+// held-out row stays (0, 0) whatever it weighs.  The entry checks on the host that every model's training rows weigh
+// something and refuses by the model's number.  4n more bytes, outside ds_trainer_batch_bytes' formula.
+//
 // Continuing from a model (ds_trainer_batch_seed; DESIGN.md section 9, "Continuing from a model"): before the first step
 // ds_train_seed_kernel walks a forest over the RAW matrix once per row and writes the leaf sum into all M leafsum columns;
 // ds_batch_error_kernel then gives every model's held-out error at those margins, and every model's tree count starts at
@@ -75,6 +80,8 @@ struct ds_trainer_batch {
     hipStream_t stream = nullptr;
     ds::DeviceBuffer<uint8_t> bins, fold;
     ds::DeviceBuffer<float> labels, leafsum, probabilities, cuts;
+    ds::DeviceBuffer<float> weights;           // ds_trainer_batch_set_weights: float[n] shared by the models, 4n more bytes
+    bool weighted = false;
     ds::DeviceBuffer<int32_t> cut_offsets, node_of, counts, active;
     ds::DeviceBuffer<long long> gh, hist;
     ds::DeviceBuffer<ds::Node> nodes;
@@ -211,7 +218,7 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
         delete b;
         return status;
     }
-    b->view = ds::TrainView{b->bins.ptr, b->labels.ptr, b->fold.ptr, b->cut_offsets.ptr, b->d_models.ptr, b->active.ptr,
+    b->view = ds::TrainView{b->bins.ptr, b->labels.ptr, nullptr, b->fold.ptr, b->cut_offsets.ptr, b->d_models.ptr, b->active.ptr,
                             b->gh.ptr, b->node_of.ptr, b->leafsum.ptr, b->probabilities.ptr, b->hist.ptr, b->nodes.ptr,
                             b->counts.ptr, b->candidates.ptr, b->errors.ptr, n, hist_entries(depth, n_features),
                             candidate_entries(depth, n_features), n_features, b->slots};
@@ -374,6 +381,41 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
     b->sampling_view = ds::TrainSamplingView{b->d_sampling.ptr, b->d_trees.ptr, b->d_held_before.ptr, b->d_held_slot.ptr,
                                              b->masks.ptr, static_cast<int64_t>(waves)};
     b->sampled = true;
+    return DS_OK;
+}
+
+int ds_trainer_batch_set_weights(ds_trainer_batch *batch, const float *weights)
+{
+    const char *who = "ds_trainer_batch_set_weights";
+    DS_REQUIRE(batch != nullptr, "%s: batch is null", who);
+    DS_REQUIRE(weights != nullptr, "%s: weights is null", who);
+    ds_trainer_batch *b = batch;
+    DS_REQUIRE(!b->stepped, "%s: the weights must be set before the first step", who);
+    DS_REQUIRE(!b->weighted, "%s: the weights are already set", who);
+    double beta = 0.0;
+    for (const ds::TrainModel &model : b->models) beta = std::max(beta, model.params.beta);
+    if (int status = ds::train_check_weights(who, weights, b->n, beta); status != DS_OK) return status;
+    DS_HIP(hipSetDevice(b->device));
+    // every model's training rows must weigh something: whether a fold (slot 0: any fold) has a row of positive weight
+    std::vector<uint8_t> fold(static_cast<size_t>(b->n)), positive(ds::kBatchFoldsMax + 1, 0);
+    DS_HIP(hipMemcpy(fold.data(), b->fold.ptr, fold.size(), hipMemcpyDeviceToHost));
+    int32_t positive_folds = 0;
+    for (int64_t r = 0; r < b->n; ++r)
+        if (weights[r] > 0.f && !positive[fold[r]]) {
+            positive[fold[r]] = 1;
+            ++positive_folds;
+        }
+    for (int32_t m = 0; m < b->n_models; ++m) {
+        const int32_t held_out = b->models[m].held_out;
+        DS_REQUIRE(positive_folds - (held_out >= 0 && positive[held_out] ? 1 : 0) > 0,
+                   "%s: model %d: the total weight of its training rows is 0", who, m);
+    }
+    if (int status = ds::train_check_free(b->n * 4, who); status != DS_OK) return status;
+    if (int status = b->weights.allocate(static_cast<size_t>(b->n)); status != DS_OK) return status;
+    DS_HIP(hipMemcpyAsync(b->weights.ptr, weights, sizeof(float) * b->n, hipMemcpyHostToDevice, b->stream));
+    DS_HIP(hipStreamSynchronize(b->stream));
+    b->view.weights = b->weights.ptr;
+    b->weighted = true;
     return DS_OK;
 }
 

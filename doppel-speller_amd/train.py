@@ -333,6 +333,40 @@ def validate_init_model(init_model, n_features, device=None):
     return init_model
 
 
+WEIGHT_GUARD = float(1 << 32)           # ds_train.hip train_check_weights: max(beta, 1) * sum(weights) at most
+
+
+def validate_sample_weight(sample_weight, n, beta=5.0):
+    """The checks of a `sample_weight` argument (no library needed) -> contiguous float32[n] (DESIGN.md section 9,
+    "Sample weights").  One weight per training row: a 1-D array of n numbers, every one finite and >= 0 AS A FLOAT32
+    (what the device multiplies by), with a total above 0 and max(beta, 1) * total <= 2^32, the total taken in float64:
+    the bound that keeps the trainer's int64 sums from overflowing.  For a batch, beta is the largest of its models.
+    A weight scales the row's gradient and hessian and nothing else: not the cuts (compute_cuts and
+    compute_cuts_device see values alone), not the subsample draw (indexed by row number), not the evaluation error,
+    initial_error(s) or early stopping, not eval_metrics / metrics (counts over rows), not fit_cover (counts rows)."""
+    weights = np.asarray(sample_weight)
+    if weights.ndim != 1:
+        raise ValueError(f"sample_weight must be a 1-D array, not shape {weights.shape}")
+    if weights.shape[0] != n:
+        raise ValueError(f"{n} training rows but {weights.shape[0]} sample weights")
+    if weights.dtype == bool or not (np.issubdtype(weights.dtype, np.floating) or
+                                      np.issubdtype(weights.dtype, np.integer)):
+        raise ValueError(f"sample_weight must hold numbers, not {weights.dtype}")
+    with np.errstate(over="ignore"):
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+    if not np.isfinite(weights).all():
+        raise ValueError("sample_weight holds a NaN or an infinite value (as float32)")
+    if (weights < 0).any():
+        raise ValueError(f"sample_weight holds a negative value (row {int(np.argmax(weights < 0))})")
+    total = float(weights.astype(np.float64).sum())
+    if not total > 0:
+        raise ValueError("the total sample weight of the training rows is 0")
+    if max(float(beta), 1.0) * total > WEIGHT_GUARD:
+        raise ValueError(f"max(beta, 1) * the total sample weight = {max(float(beta), 1.0) * total!r} exceeds 2^32: the "
+                         "trainer's integer sums could overflow (scale the weights down)")
+    return weights
+
+
 def _samples(params):
     """Whether a parameter set draws rows or columns: a fraction below 1 (a set that carries none draws nothing)."""
     return any(params.get(name, 1.0) < 1 for name in SAMPLING_NAMES[:3])
@@ -461,8 +495,8 @@ class ForestTrainer(_TrainerHandle):
         model = ForestTrainer().fit(features, target, eval_features, eval_target, max_depth=5, eta=0.1)
 
     The data arguments may be given by position; the booster parameters (validate_parameters: its signature is their
-    list and their defaults), `init_model` and the device forms' `n_features` by keyword ONLY.  fit and fit_device
-    take all of them; begin and begin_device all but num_boost_round and early_stopping_rounds.  A name that
+    list and their defaults), `init_model`, `sample_weight` and the device forms' `n_features` by keyword ONLY.  fit
+    and fit_device take all of them; begin and begin_device all but num_boost_round and early_stopping_rounds.  A name that
     validate_parameters does not know is a TypeError.  Everything is validated, once, before the library is touched,
     and a trainer whose begin or fit is refused keeps the state it had.
 
@@ -484,7 +518,15 @@ class ForestTrainer(_TrainerHandle):
     NEW rounds, `initial_error` the evaluation error of the init model (None without an evaluation set), model(n) the
     init trees followed by the first n new ones.  Early stopping looks at the new rounds only (the first minimum of
     `history`; initial_error is no candidate), and `best_iteration` counts all trees: init trees + the best new round,
-    so that the model returned has best_iteration + 1 trees as ever.  See validate_init_model for what is accepted."""
+    so that the model returned has best_iteration + 1 trees as ever.  See validate_init_model for what is accepted.
+
+    sample_weight=<array of n numbers> weighs the training rows in the objective (xgb.DMatrix(weight=...); DESIGN.md
+    section 9, "Sample weights"): a row's gradient and hessian are multiplied by its weight before they are quantized,
+    so min_child_weight bounds a sum of weighted hessians and a row of weight 0 trains nothing.  It is data, like the
+    labels, a host array for all four forms, and is kept as `sample_weight` (float32, None without).  The weights do
+    NOT touch the cuts, the `subsample` draw (indexed by row number), the evaluation error, `initial_error`, early
+    stopping, `eval_metrics` (counts over rows) or ForestModel.fit_cover (counts rows).  See validate_sample_weight
+    for what is accepted; all weights 1 grows the trees of a call without the argument, bit for bit."""
     ENTRIES, READS = "ds_trainer", ("margins", "probabilities", "gradients", "bins", "eval_margins")
 
     def __init__(self, device=0):
@@ -495,6 +537,7 @@ class ForestTrainer(_TrainerHandle):
         self.best_iteration = None
         self.init_model = None
         self.initial_error = None
+        self.sample_weight = None
         self.eval_metrics = ()
         self.metrics_history = {}
         self.metric_counts = []
@@ -519,7 +562,7 @@ class ForestTrainer(_TrainerHandle):
         self._begin(True, (d_features, n, target, d_eval_features, n_eval, eval_target), **parameters)
         return self._boost(self.params)
 
-    def _begin(self, in_hbm, data, init_model=None, **parameters):
+    def _begin(self, in_hbm, data, init_model=None, sample_weight=None, **parameters):
         """The one sequence behind the four forms above; `data` are their data arguments.  Everything is validated
         first: until that has passed the library is not touched and this trainer keeps the state it has."""
         if in_hbm:
@@ -530,8 +573,11 @@ class ForestTrainer(_TrainerHandle):
             (n, n_features), n_eval = features.shape, 0 if eval_features is None else eval_features.shape[0]
         if init_model is not None:
             validate_init_model(init_model, n_features, self.device)
+        if sample_weight is not None:
+            sample_weight = validate_sample_weight(sample_weight, n, params["beta"])
         self.close()
         self.params = params
+        self.sample_weight = sample_weight
         self.n, self.n_features, self.n_eval = n, n_features, n_eval
         self.timings = {}
         mark = time.perf_counter()
@@ -551,6 +597,9 @@ class ForestTrainer(_TrainerHandle):
                                                        params["colsample_bylevel"], params["sample_seed"]),
                        "ds_trainer_set_sampling")
         _lib.check(library.ds_trainer_set_labels(self.handle, _lib.pointer(target)), "ds_trainer_set_labels")
+        if sample_weight is not None:          # none: exactly the calls of a trainer that knows no weights
+            _lib.check(library.ds_trainer_set_weights(self.handle, _lib.pointer(sample_weight)),
+                       "ds_trainer_set_weights")
         if n_eval:
             _call("ds_trainer_set_eval", in_hbm, self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
                   n_eval)
@@ -667,7 +716,7 @@ class TrainModelResult:
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
-                **fit_parameters):
+                kind_weights=None, **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -680,9 +729,12 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     (predict_contributions, Prediction.explain); `timings` then has a "cover" entry.  The trees are the same either
     way.  build_index: "host" or "device", where the truth index is built (TruthSide).
     init_model: a ForestModel of FEATURES_COUNT features to continue from (ForestTrainer; validate_init_model): the
-    device chain is the same, seeded from the matrices in HBM, and the result gains `initial_error`."""
+    device chain is the same, seeded from the matrices in HBM, and the result gains `initial_error`.
+    kind_weights: {"generated", "negative", "positive"} -> the sample weight of the training rows of that kind (a name
+    left out: 1.0; training_set.kind_weights), handed to fit_device as sample_weight.  The weights enter the objective
+    alone (ForestTrainer): the evaluation error, error_matrix and a counted cover stay counts over rows."""
     from .feature_engineering import FEATURES_COUNT
-    from .training_set import FeatureEngineering
+    from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
     unknown = set(fit_parameters) - set(inspect.signature(validate_parameters).parameters)
     if unknown:
@@ -690,6 +742,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     validate_parameters(**fit_parameters)
     if init_model is not None:
         validate_init_model(init_model, FEATURES_COUNT, device)
+    if kind_weights is not None:
+        validate_kind_weights(kind_weights)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=evaluation_fractions, build_index=build_index)
@@ -698,9 +752,14 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     trainer = ForestTrainer(device)
     mark = time.perf_counter()
     has_eval = sets.n_evaluation > 0
-    model = trainer.fit_device(sets.train, sets.n_train, sets.train_target, sets.evaluation if has_eval else None,
-                               sets.n_evaluation, sets.evaluation_target if has_eval else None, init_model=init_model,
-                               **fit_parameters)
+    weighted = {} if kind_weights is None else dict(sample_weight=weights_of_kinds(fe.rows, kind_weights))
+    try:
+        model = trainer.fit_device(sets.train, sets.n_train, sets.train_target, sets.evaluation if has_eval else None,
+                                   sets.n_evaluation, sets.evaluation_target if has_eval else None,
+                                   init_model=init_model, **weighted, **fit_parameters)
+    except ValueError:              # weights the rows of this training set cannot carry: free what the call holds
+        sets.free()
+        raise
     fit_ms = (time.perf_counter() - mark) * 1000.0
     timings["cuts"], timings["bin"] = trainer.timings["cuts"], trainer.timings["bin"]
     timings["boost"] = fit_ms - timings["cuts"] - timings["bin"]

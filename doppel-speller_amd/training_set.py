@@ -151,6 +151,43 @@ def evaluation_split(kind, seed, fractions=None):
     return train, evaluation
 
 
+KIND_CODES = {"generated": KIND_GENERATED, "negative": KIND_NEGATIVE, "positive": KIND_POSITIVE}
+
+
+def validate_kind_weights(weights):
+    """A dict over the names "generated", "negative", "positive" -> {name: float}, 1.0 for a name left out.  Every
+    weight is a finite number >= 0; an unknown name is a ValueError."""
+    if not isinstance(weights, dict):
+        raise ValueError(f"kind weights must be a dict over {sorted(KIND_CODES)}, not {weights!r}")
+    unknown = set(weights) - set(KIND_CODES)
+    if unknown:
+        raise ValueError(f"unknown kind weights {sorted(unknown, key=str)}; known: {sorted(KIND_CODES)}")
+    out = {}
+    for name in KIND_CODES:
+        value = weights.get(name, 1.0)
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(value) or value < 0:
+            raise ValueError(f"the weight of {name} rows must be a finite number >= 0, not {value!r}")
+        out[name] = float(value)
+    return out
+
+
+def kind_weights(rows, weights):
+    """The float32 sample weights of the TRAINING rows of a FeatureEngineering.rows frame, in the order of the
+    training matrix (the frame's rows outside the evaluation set, in frame order): weights[name] for a row of that kind
+    (validate_kind_weights: "generated", "negative", "positive"; a name left out weighs 1.0).  What
+    ForestTrainer.fit_device(..., sample_weight=...) takes for the matrix of generate_device_data_sets."""
+    weights = validate_kind_weights(weights)
+    kind = np.asarray(rows["kind"])
+    training = ~np.asarray(rows["evaluation"]).astype(bool)
+    table = np.ones(int(max(KIND_CODES.values())) + 1, np.float32)
+    for name, code in KIND_CODES.items():
+        table[code] = weights[name]
+    if kind.shape[0] and (kind.min() < 1 or kind.max() >= table.shape[0]):
+        raise ValueError("rows holds a kind that is not generated (1), negative (2) or positive (3)")
+    return np.ascontiguousarray(table[kind.astype(np.int64)][training])
+
+
 class _DeviceTitles:
     """A ds_titles table made on the device (ds_misspell_titles)."""
 

@@ -17,7 +17,7 @@ from . import _lib
 from .train import (METRIC_NAMES, SAMPLING_NAMES, FirstMinimum, _call, _device_columns, _device_labels,
                     _matrix_and_labels, _positive_int, _samples, _TrainerHandle, auc_numerator, compute_cuts,
                     compute_cuts_device, heap_tree, metric_values, validate_init_model, validate_metrics,
-                    validate_parameters)
+                    validate_parameters, validate_sample_weight)
 
 MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
 FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
@@ -239,6 +239,18 @@ def validate_models(models, n_folds):
     return np.ascontiguousarray(params), np.array(held, np.int32), sets
 
 
+def validate_batch_weight(sample_weight, n, fold, held_out, sets):
+    """The checks of a batch's `sample_weight` (no library needed) -> float32[n]: validate_sample_weight over all rows
+    with the largest beta among the models, and per model a total above 0 over ITS training rows (those outside its
+    held-out fold); the first model without one is named."""
+    weights = validate_sample_weight(sample_weight, n, max(one["beta"] for one in sets))
+    positive = np.bincount(fold[weights > 0], minlength=FOLDS_MAX + 1) > 0      # the folds that weigh something
+    for m, held in enumerate(held_out):
+        if not positive[np.arange(positive.shape[0]) != held].any():
+            raise ValueError(f"model {m}: the total sample weight of its training rows (outside fold {int(held)}) is 0")
+    return weights
+
+
 def _validate_fold(fold, n):
     fold = np.asarray(fold)
     if fold.ndim != 1 or fold.shape[0] != n:
@@ -284,7 +296,13 @@ class ForestTrainerBatch(_TrainerHandle):
     begin(..., init_model=<ForestModel>) starts EVERY model from that model ("Continuing from a
     model"): the forest is evaluated once per row of the raw matrix on the device, `initial_errors[m]` is its error on
     model m's held-out rows (None without a fold), trees[m] and history[m] hold the new rounds, model(m, n) the init
-    trees followed by the first n new ones, and model m stays ForestTrainer(init_model=...)'s on its training rows."""
+    trees followed by the first n new ones, and model m stays ForestTrainer(init_model=...)'s on its training rows.
+
+    begin(..., sample_weight=<array of n numbers>) weighs the rows in every model's objective (DESIGN.md section 9,
+    "Sample weights"): ONE array over all rows, like the labels; model m is ForestTrainer(sample_weight=...)'s on its
+    training rows with their weights, and a held-out row trains nothing whatever its weight.  Every model's training
+    rows need a total weight above 0 (validate_batch_weight names the model that has none).  The held-out errors and
+    the metrics stay counts over rows."""
     ENTRIES, READS = "ds_trainer_batch", ("margins", "probabilities", "gradients", "bins")
 
     def __init__(self, device=0):
@@ -293,24 +311,28 @@ class ForestTrainerBatch(_TrainerHandle):
         self.trees, self.history, self.last_heap = [], [], []
         self.metrics, self.metrics_history, self.metric_counts = (), [], []
         self.init_model, self.initial_errors = None, []
+        self.sample_weight = None
         self.timings = {}
 
-    def begin(self, features, target, fold, models, max_bin=256, cuts=None, metrics=(), init_model=None):
+    def begin(self, features, target, fold, models, max_bin=256, cuts=None, metrics=(), init_model=None,
+              sample_weight=None):
         features, target = _matrix_and_labels(features, target, "training")
         return self._begin(features, False, features.shape[0], features.shape[1], target, fold, models, max_bin, cuts,
-                           metrics, init_model)
+                           metrics, init_model, sample_weight)
 
     def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None, metrics=(),
-                     init_model=None):
+                     init_model=None, sample_weight=None):
         """begin for a contiguous float32[n, n_features] matrix that lies complete in HBM (a DeviceArray, or an address
         with n_features given).  It is read where it lies, never copied to the host, and not kept."""
         n_features = _device_columns(d_features, n_features)
         n, target = _device_labels(n, target, "training")
         if isinstance(d_features, _lib.DeviceArray) and n > d_features.shape[0]:
             raise ValueError(f"{n} training rows exceed the device matrix's {d_features.shape[0]}")
-        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts, metrics, init_model)
+        return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts, metrics, init_model,
+                           sample_weight)
 
-    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts, metrics=(), init_model=None):
+    def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts, metrics=(), init_model=None,
+               sample_weight=None):
         metrics = validate_metrics(metrics, "metrics")
         if init_model is not None:
             validate_init_model(init_model, n_features, self.device)
@@ -319,7 +341,10 @@ class ForestTrainerBatch(_TrainerHandle):
         if held_out.max() >= n_folds:
             raise ValueError(f"held_out = {int(held_out.max())} but fold holds only 0 .. {n_folds - 1}")
         max_bin = _positive_int("max_bin", max_bin, 2, 256)
+        if sample_weight is not None:
+            sample_weight = validate_batch_weight(sample_weight, n, fold, held_out, sets)
         self.close()
+        self.sample_weight = sample_weight
         self.timings = {}
         mark = time.perf_counter()
         if cuts is None:
@@ -339,6 +364,9 @@ class ForestTrainerBatch(_TrainerHandle):
               _lib.pointer(self.cut_offsets), _lib.pointer(target), _lib.pointer(fold), n_folds, self.n_models,
               _lib.pointer(params), _lib.pointer(held_out), self.device, ctypes.byref(handle))
         self.handle = handle
+        if sample_weight is not None:
+            _lib.check(_lib.lib().ds_trainer_batch_set_weights(self.handle, _lib.pointer(sample_weight)),
+                       "ds_trainer_batch_set_weights")
         if any(_samples(one) for one in sets):
             fractions = np.array([[one[name] for name in SAMPLING_NAMES[:3]] for one in sets], np.float64)
             seeds = np.array([one["sample_seed"] for one in sets], np.uint64)
@@ -448,12 +476,12 @@ def validate_cross_validation(parameters, n_folds=5, seed=0, num_boost_round=100
     return sets, None
 
 
-def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics=()):
+def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics=(), weighted=False):
     """Whole parameter sets (K models each) per batch: what 80 % of the free HBM holds, 256 models at most.  With
-    metrics their scratch (batch_metrics_bytes) comes off the budget."""
+    metrics their scratch (batch_metrics_bytes) comes off the budget, with sample weights their 4 n bytes."""
     free, total = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.check(_lib.lib().ds_device_memory(device, ctypes.byref(free), ctypes.byref(total)), "ds_device_memory")
-    budget = int(free.value * 0.8) - (0 if in_hbm else 4 * n * n_features)
+    budget = int(free.value * 0.8) - (0 if in_hbm else 4 * n * n_features) - (4 * n if weighted else 0)
     depth = max(one["max_depth"] for one in sets)
     count = max(1, min(len(sets), MODELS_MAX // n_folds))
     extra = (lambda models: batch_metrics_bytes(n, models, n_folds)) if metrics else (lambda models: 0)
@@ -464,7 +492,7 @@ def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics=()):
 
 def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0, num_boost_round=1000,
                    early_stopping_rounds=50, max_bin=256, refit=True, device=0, models_per_batch=None, metrics=(),
-                   select_by="error", init_model=None):
+                   select_by="error", init_model=None, sample_weight=None):
     """K-fold cross-validation of one parameter set or a list of them (parameter_grid) on the GPU -> CrossValidation.
 
     features: a host matrix, or a DeviceArray float32[>= n, n_features] in HBM of which the first len(target) rows
@@ -486,7 +514,13 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     init_model: every fold of every set starts from that ForestModel ("Continuing from a model").
     Rounds, curves and best_iteration count the new rounds; `initial_errors` gives the init model's pooled out-of-fold
     error per set; the refit is ForestTrainer().fit(features, target, num_boost_round=best_iteration + 1,
-    init_model=init_model, **best_parameters), bit for bit."""
+    init_model=init_model, **best_parameters), bit for bit.
+
+    sample_weight: one weight per row (train.validate_sample_weight; DESIGN.md section 9, "Sample weights").  Every fold
+    of every set trains with the weights of its training rows, and so does the refit on all rows, which is
+    ForestTrainer().fit(..., sample_weight=sample_weight, ...) as above, bit for bit.  `results`, the curves and the
+    selection stay on the UNWEIGHTED out-of-fold error and metrics.  A fold whose training rows all weigh 0 is a
+    ValueError that names the model."""
     started = time.perf_counter()
     sets, per_batch = validate_cross_validation(parameters, n_folds, seed, num_boost_round, early_stopping_rounds,
                                                 max_bin, models_per_batch, metrics, select_by)
@@ -504,8 +538,10 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     if init_model is not None:
         validate_init_model(init_model, n_features, device)
     folds = fold_assignment(groups, n_folds, seed, n)
+    if sample_weight is not None:       # every set holds the same folds out: one set's models stand for all
+        sample_weight = validate_batch_weight(sample_weight, n, folds, list(range(n_folds)) + [-1], sets)
     if per_batch is None:
-        per_batch = _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics)
+        per_batch = _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics, sample_weight is not None)
     timings = dict.fromkeys(("cuts", "bin", "boost", "refit"), 0.0)
     mark = time.perf_counter()
     cuts = compute_cuts_device(features, n, max_bin, n_features, device) if in_hbm else compute_cuts(features, max_bin)
@@ -514,9 +550,10 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     def begin(models, metrics=()):
         batch = ForestTrainerBatch(device)
         if in_hbm:
-            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts, metrics, init_model)
+            batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts, metrics, init_model,
+                               sample_weight)
         else:
-            batch.begin(features, target, folds, models, max_bin, cuts, metrics, init_model)
+            batch.begin(features, target, folds, models, max_bin, cuts, metrics, init_model, sample_weight)
         timings["bin"] += batch.timings["bin"]
         return batch
 
@@ -589,17 +626,19 @@ def row_groups(rows):
 
 def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters, n_folds=5, top_n=100,
                           sample_n=10, seed=0, device=0, transform=True, cover=False, init_model=None,
-                          **cv_arguments):
+                          kind_weights=None, **cv_arguments):
     """Parameter search from raw titles in one call: FeatureEngineering(..., no evaluation split).
     generate_device_data_sets() -> cross_validate on the matrix in HBM, folds by row_groups -> the refit model.
     cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch, metrics, select_by.  Returns cross_validate's result
     with `rows` (FeatureEngineering.rows), `feature_importance` and the FeatureEngineering stages in `timings`.
     cover: also count the model's cover on the matrix while it is in HBM (ForestModel.fit_cover_device), so that the
     model can explain its predictions; `timings` then has "cover".  init_model: cross_validate's, a ForestModel of
-    FEATURES_COUNT features that every fold, set and the refit continue from.  Everything is validated before any
-    device work and everything held in HBM is freed on every exit path."""
+    FEATURES_COUNT features that every fold, set and the refit continue from.  kind_weights: {"generated", "negative",
+    "positive"} -> the sample weight of the rows of that kind (training_set.kind_weights; a name left out: 1.0), handed
+    to cross_validate as sample_weight.  Everything is validated before any device work and everything held in HBM is
+    freed on every exit path."""
     from .feature_engineering import FEATURES_COUNT
-    from .training_set import FeatureEngineering
+    from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
     unknown = set(cv_arguments) - {"num_boost_round", "early_stopping_rounds", "max_bin", "models_per_batch", "metrics",
                                    "select_by"}
@@ -608,6 +647,8 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
     validate_cross_validation(parameters, n_folds, seed, **cv_arguments)
     if init_model is not None:
         validate_init_model(init_model, FEATURES_COUNT, device)
+    if kind_weights is not None:
+        validate_kind_weights(kind_weights)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=dict(generated=0.0, negative=0.0, positive=0.0))
@@ -615,7 +656,9 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
     try:
         matrix = _lib.DeviceArray.view(sets.train.ptr, (sets.n_train, sets.train.shape[1]), np.float32, device)
         out = cross_validate(matrix, sets.train_target, parameters, n_folds=n_folds, groups=row_groups(fe.rows),
-                             seed=seed, refit=True, device=device, init_model=init_model, **cv_arguments)
+                             seed=seed, refit=True, device=device, init_model=init_model,
+                             sample_weight=None if kind_weights is None else weights_of_kinds(fe.rows, kind_weights),
+                             **cv_arguments)
         if cover:
             mark = time.perf_counter()
             out.model.fit_cover_device(sets.train, sets.n_train)

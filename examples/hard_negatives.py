@@ -10,10 +10,12 @@ It prints the evaluation error matrix (at probability 0.9, the reference's decis
 continued one, on the same evaluation rows.  Nothing is claimed about how the two compare: that has not been measured
 here, and synthetic titles would not settle it.
 
-    python examples/hard_negatives.py [--false-positives] [n_truth] [n_queries] [hard_n] [more_rounds]
+    python examples/hard_negatives.py [--false-positives] [--mined-weight W] [n_truth] [n_queries] [hard_n] [more_rounds]
 
 --false-positives mines only candidates whose margin is above log(9), the margin of probability 0.9: the false positives
 of the decision rule.
+--mined-weight W continues with the mined rows at sample weight W and the base rows at 1 (ForestTrainer's
+sample_weight; the default, 1, is the unweighted call).
 """
 import math
 import os
@@ -27,7 +29,7 @@ import doppel_speller_amd as ds  # noqa: E402
 from doppel_speller_amd import synth  # noqa: E402
 
 
-def main(n_truth=20000, n_queries=4000, hard_n=5, more_rounds=50, false_positives=False):
+def main(n_truth=20000, n_queries=4000, hard_n=5, more_rounds=50, false_positives=False, mined_weight=None):
     w = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     truth_titles = synth._to_strings(w.t_flat, w.t_off)
     train_titles = synth._to_strings(w.q_flat, w.q_off)
@@ -53,12 +55,15 @@ def main(n_truth=20000, n_queries=4000, hard_n=5, more_rounds=50, false_positive
           + "; " + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.hard_timings.items()))
 
     joined = sets.with_hard_negatives(hard)
+    weighted = {} if mined_weight is None else dict(
+        sample_weight=np.concatenate((np.ones(sets.n_train), np.full(hard.n, mined_weight))))
     t0 = time.perf_counter()
     trainer = ds.ForestTrainer()
     continued = trainer.fit_device(joined.train, joined.n_train, joined.train_target, joined.evaluation,
                                    joined.n_evaluation, joined.evaluation_target, init_model=model,
-                                   num_boost_round=more_rounds)
-    print(f"continued on {joined.n_train} rows ({sets.n_train} base + {hard.n} mined) for {len(trainer.history)} rounds "
+                                   num_boost_round=more_rounds, **weighted)
+    print(f"continued on {joined.n_train} rows ({sets.n_train} base + {hard.n} mined"
+          + (f" at weight {mined_weight:g}" if mined_weight is not None else "") + f") for {len(trainer.history)} rounds "
           f"in {time.perf_counter() - t0:.2f}s: {continued.n_trees} trees (init model's custom error "
           f"{trainer.initial_error}, best new round's {min(trainer.history)})")
     after = ds.evaluation_error_matrix(continued, sets.evaluation.to_host(sets.n_evaluation), sets.evaluation_target)
@@ -71,4 +76,11 @@ def main(n_truth=20000, n_queries=4000, hard_n=5, more_rounds=50, false_positive
 
 if __name__ == "__main__":
     arguments = [a for a in sys.argv[1:] if a != "--false-positives"]
-    main(*[int(a) for a in arguments[:4]], false_positives="--false-positives" in sys.argv[1:])
+    weight = None
+    if "--mined-weight" in arguments:
+        at = arguments.index("--mined-weight")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--mined-weight needs a number, the sample weight of every mined row")
+        weight = float(arguments[at + 1])
+        del arguments[at:at + 2]
+    main(*[int(a) for a in arguments[:4]], false_positives="--false-positives" in sys.argv[1:], mined_weight=weight)

@@ -11,8 +11,8 @@ It prints the fraction of correct final answers of that model next to a model tr
 top-k pairs of the train queries labelled with their known source row) and the random stand-in ensemble
 (synth.make_forest) that the other examples use.
 
-    python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH] [n_truth] [n_queries]
-                                   [top_n] [model.npz]
+    python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH]
+                                   [--kind-weights generated=0.5,positive=2] [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
 --one-call trains with ds.train_model(...), the same steps in one call with the feature matrix kept in HBM; the model
@@ -23,6 +23,9 @@ the custom error, all computed on the device; the model is the same with and wit
 --init-model PATH continues boosting from the ForestModel saved at PATH (an earlier run's model.npz) instead of
 starting from an empty forest: the new trees follow that model's, and the evaluation error of the init model is
 printed next to the best new round's.
+--kind-weights NAME=W,... weighs the training rows of a kind (generated, negative, positive; a kind left out: 1) in the
+objective: ds.train_model(..., kind_weights=) with --one-call, ForestTrainer.fit(..., sample_weight=ds.kind_weights(
+fe.rows, ...)) without.  The evaluation error stays a count over rows.
 """
 import os
 import sys
@@ -61,7 +64,8 @@ def print_rounds(metrics_history, history):
         print(f"[{round_}]\t" + "\t".join(parts))
 
 
-def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None):
+def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None,
+         kind_weights=None):
     init = ds.ForestModel.load(init_model) if init_model else None
     init_trees = init.n_trees if init else 0
     if init:
@@ -77,7 +81,7 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
     if one_call:
         t0 = time.perf_counter()
         result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics),
-                                init_model=init)
+                                init_model=init, kind_weights=kind_weights)
         t1 = time.perf_counter()
         model = result.model
         if metrics:
@@ -101,7 +105,9 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
               + ", ".join(f"{k} {v:.1f} ms" for k, v in fe.timings.items()))
         t0 = time.perf_counter()
         trainer = ds.ForestTrainer()
-        model = trainer.fit(features, labels, eval_features, eval_labels, eval_metrics=tuple(metrics), init_model=init)
+        weighted = {} if kind_weights is None else dict(sample_weight=ds.kind_weights(fe.rows, kind_weights))
+        model = trainer.fit(features, labels, eval_features, eval_labels, eval_metrics=tuple(metrics), init_model=init,
+                            **weighted)
         t1 = time.perf_counter()
         if metrics:
             print_rounds(trainer.metrics_history, trainer.history)
@@ -146,5 +152,12 @@ if __name__ == "__main__":
             raise SystemExit("--init-model needs the path of a saved ForestModel")
         init_path = arguments[at + 1]
         del arguments[at:at + 2]
+    kinds = None
+    if "--kind-weights" in arguments:
+        at = arguments.index("--kind-weights")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--kind-weights needs NAME=WEIGHT,... over generated, negative, positive")
+        kinds = {name: float(value) for name, value in (pair.split("=") for pair in arguments[at + 1].split(","))}
+        del arguments[at:at + 2]
     main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted,
-         init_model=init_path)
+         init_model=init_path, kind_weights=kinds)

@@ -571,6 +571,20 @@ int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, i
 #define DS_SAMPLE_PURPOSE_LEVEL 5
 int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsample_bytree, double colsample_bylevel,
                             uint64_t sample_seed);
+/* Per-row sample weights in the objective ("Sample weights"): weights is a host float[n], like the
+ * labels.  With p the float32 probability of row r, y its label and w = beta + y - beta y, every later step quantizes
+ *   g = (p w - y) * s_r,  h = (p (1 - p) w) * s_r,  (rint(g * 2^30), rint(h * 2^30))
+ * with the parenthesised factors computed as without weights and s_r widened to double before the one multiplication.
+ * Everything after the gradients works on these integers as before: min_child_weight bounds a sum of weighted hessians.
+ * A row of weight 0 carries (0, 0), like a held-out or undrawn row.  The weights do not touch the cuts, the subsample
+ * draw (indexed by row number), the evaluation error, the metrics (counts over rows) or a forest's cover.
+ * Legal once, after ds_trainer_set_labels and before the first step.  DS_E_ARG with a message, nothing launched and the
+ * trainer still usable unweighted, for: a null pointer; a weight that is not finite or is negative; a total weight of 0
+ * (the root would divide by zero with reg_lambda = 0); max(beta, 1) * sum(weights) > 2^32 with the sum in double (the
+ * bounds |g| <= max(beta, 1) s_r, h <= max(beta, 1) s_r / 4 then keep every int64 histogram sum below 2^62 + n); a
+ * second call; a call after a step.  The array costs 4 n bytes of HBM.  ds_trainer_read's gradients are the weighted
+ * integers. */
+int ds_trainer_set_weights(ds_trainer *trainer, const float *weights);
 
 /* ---- the train-model step without a host copy of the feature matrix ("One call") ----------------
  * ds_feature_cuts_device: compute_cuts of a contiguous float32[n][n_features] matrix in HBM, bit-identical to the host
@@ -637,7 +651,8 @@ int ds_trainer_batch_read(ds_trainer_batch *batch, int32_t model, float *margins
                           int64_t *gradients, uint8_t *bins);
 /* The bytes of HBM that ds_trainer_batch_create_device needs for n_models models whose largest max_depth is max_depth:
  * n * n_features + 5 n shared, and per model 28 n + (2^max_depth - 1) * n_features * 4096 + a few KiB.  -1 for
- * arguments outside the limits above. */
+ * arguments outside the limits above.  Sample weights (ds_trainer_batch_set_weights) add 4 n bytes, shared by the
+ * models, which this formula does not count. */
 int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth);
 /* ds_trainer_set_sampling for every model of a batch, valid only before the first ds_trainer_batch_step:
  * fractions[3m .. 3m + 3) = subsample, colsample_bytree, colsample_bylevel of model m, sample_seeds[m] its seed.  Every
@@ -647,6 +662,12 @@ int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, 
  * n / 16 bytes per fold that a model with subsample < 1 holds out.  DS_E_ARG as for ds_trainer_set_sampling, with the
  * model named. */
 int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractions, const uint64_t *sample_seeds);
+/* ds_trainer_set_weights for a batch: ONE host float[n] over all rows, shared by the models like the labels, legal once
+ * and before the first ds_trainer_batch_step.  A held-out row stays (0, 0) whatever its weight, and a model's trees are
+ * those of ds_trainer with the weights of its training rows.  The guard takes the largest beta among the models, and
+ * the rows outside the held-out fold of EVERY model must have a total weight above 0: DS_E_ARG names the first model
+ * that has none.  Adds 4 n bytes of HBM to ds_trainer_batch_bytes, whose formula does not count them. */
+int ds_trainer_batch_set_weights(ds_trainer_batch *batch, const float *weights);
 /* For tests: ds_trainer_batch_option("max_blocks", b) caps every grid of a training round that runs over rows at b
  * workgroups, which stride beyond it (0: back to the default).  It also caps the round of ds_trainer_step, which launches
  * the same kernels.  The results do not depend on it. */
