@@ -54,6 +54,12 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         its weight, on the device; cuts, subsample draws, errors, metrics and cover stay unweighted;
         validate_sample_weight(w, n, beta) says what is accepted, kind_weights(rows, weights) weighs a training set's
         rows by their kind (this project's own)
+    ForestTrainer.fit(..., monotone_constraints=c), ForestTrainerBatch.begin(..., monotone_constraints=c),
+        cross_validate(..., monotone_constraints=c), train_model(..., monotone_constraints=ratio_constraints()),
+        tune_model_parameters(..., monotone_constraints=)   -> a sign per feature (xgboost's monotone_constraints): the
+        margin never falls (+1) or never rises (-1) as that feature rises, enforced in the split choice on the device;
+        RATIO_FEATURE_NAMES are the 17 similarity ratios, ForestModel.monotone_violations(c) counts the splits of any
+        model that break c, validate_monotone_constraints(c, n_features, names) says what is accepted (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -62,7 +68,7 @@ there is no CPU fallback -- importing works without the library, calling anythin
 from . import _lib  # noqa: F401
 from ._lib import DoppelError, build_library, library_path  # noqa: F401
 from .feature_engineering import (  # noqa: F401
-    FEATURES_COUNT, FEATURE_NAMES, TitleTable, construct_features, construct_features_indexed, encode_title, encode_titles,
+    FEATURES_COUNT, FEATURE_NAMES, RATIO_FEATURE_NAMES, ratio_constraints, TitleTable, construct_features, construct_features_indexed, encode_title, encode_titles,
     get_truth_words_counts, levenshtein_ratio_batch, find_close_matches, exact_matches, ALLOWED_CHARACTERS, SPACE_CODE, SORT_KEY)
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
@@ -74,7 +80,8 @@ from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMN
 from .training_set import (DeviceDataSets, DeviceHardNegatives, FeatureEngineering, generate_misspelled_names,  # noqa: F401
                            kind_weights, validate_hard)
 from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
-                    evaluation_error_matrix, roc_auc, train_model, validate_init_model, validate_sample_weight)
+                    evaluation_error_matrix, roc_auc, train_model, validate_init_model, validate_monotone_constraints,
+                    validate_sample_weight)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
 from .text import transform_title, transform_titles  # noqa: F401

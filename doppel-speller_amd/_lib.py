@@ -191,6 +191,8 @@ def _declare(handle):
         "ds_trainer_set_sampling": [p, c.c_double, c.c_double, c.c_double, c.c_uint64],
         "ds_trainer_set_weights": [p, p],
         "ds_trainer_batch_set_weights": [p, p],
+        "ds_trainer_set_monotone": [p, p],
+        "ds_trainer_batch_set_monotone": [p, p],
         "ds_feature_cuts_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_int, p],
         "ds_cuts_option": [c.c_char_p, c.c_int64],
         "ds_trainer_create_device": [p, c.c_int64, c.c_int32, p, p, c.c_int32, c.c_double, c.c_double, c.c_double,
@@ -285,7 +287,8 @@ EXPORTED_SYMBOLS = (
     "ds_index_create_device", "ds_index_read", "ds_index_build_option", "ds_assign_edges_device",
     "ds_assign_solve_device", "ds_assign_option", "ds_trainer_seed", "ds_trainer_seed_device", "ds_trainer_batch_seed",
     "ds_trainer_batch_seed_device", "ds_hard_negatives_device", "ds_hard_total", "ds_hard_option",
-    "ds_trainer_set_weights", "ds_trainer_batch_set_weights")
+    "ds_trainer_set_weights", "ds_trainer_batch_set_weights", "ds_trainer_set_monotone",
+    "ds_trainer_batch_set_monotone")
 
 
 def lib():

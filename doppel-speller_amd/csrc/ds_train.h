@@ -93,6 +93,10 @@ struct TrainView {   // what every kernel of a round gets
     int32_t nf, slots;
     TrainModel only;              // the one model of a view without `active`: read from the kernel arguments, as the
                                   // single trainer's parameters always were; at 10^5 rows its round is launch-bound
+    // monotone constraints ("Monotone constraints"): both null without; only the kMonotone split
+    // kernels and the clear kernel (the root's bounds) look at them
+    const int8_t *monotone = nullptr;   // per feature -1, 0, +1: nf entries, stride 0 like weights
+    double *bounds = nullptr;           // (lo, hi) of every heap slot's weight, stride 2 * slots
     __device__ int32_t model_index(unsigned i) const { return active != nullptr ? active[i] : 0; }
     __device__ TrainModel model(int32_t m) const
     {
@@ -144,6 +148,8 @@ int train_check_subsample(const char *who, int32_t model, double subsample, doub
 // Sample weights ("Sample weights"): every weight finite and >= 0, and the overflow guard
 // max(beta, 1) * sum(weights) <= 2^32 with the sum in double; beta is the largest among the models that share the array
 int train_check_weights(const char *who, const float *weights, int64_t n, double beta);
+// Monotone constraints ("Monotone constraints"): every entry -1, 0 or 1; *any: one is not 0
+int train_check_monotone(const char *who, const int8_t *constraints, int32_t n_features, bool *any);
 // What a create entry sets up on the current device: its stream, the cuts in HBM and the compute-unit count
 int train_create_setup(const char *who, int device, int32_t n_features, const float *cuts, const int32_t *cut_offsets,
                        hipStream_t *stream, DeviceBuffer<float> &d_cuts, DeviceBuffer<int32_t> &d_cut_offsets,
@@ -286,6 +292,22 @@ __device__ inline void train_histogram_group(const uint8_t *bins, const long lon
 
 __device__ inline double node_gain(double g, double h, double lambda) { return g * g / (h + lambda); }
 
+// ---- monotone constraints ("Monotone constraints") ---------------------------------------------
+// The weight of a node with sums (g, h) clamped to the node's bounds [lo, hi], and its gain term: node_gain while the
+// raw weight lies inside the bounds, the loss reduction at the clamped weight otherwise.  Infinite bounds give
+// node_gain and the raw weight, bit for bit.
+struct BoundedTerm {
+    double weight, term;
+};
+
+__device__ inline BoundedTerm bounded_term(double g, double h, double lambda, double lo, double hi)
+{
+    const double w = -g / (h + lambda);
+    const double clamped = fmin(fmax(w, lo), hi);
+    if (lo <= w && w <= hi) return BoundedTerm{clamped, node_gain(g, h, lambda)};
+    return BoundedTerm{clamped, -(((2.0 * g) * clamped) + (((h + lambda) * clamped) * clamped))};
+}
+
 struct Candidate {            // the best split of one (node, feature)
     double gain;              // -inf: no valid candidate
     long long left_g, left_h, total_g, total_h;
@@ -300,11 +322,15 @@ struct Candidate {            // the best split of one (node, feature)
 // kSampled: a feature with level_mask[f] == 0 (outside the level's feature set) offers no boundary, like a feature
 // with a single bin; its histogram is still completed by the subtraction and its totals still written, because a
 // later level may include the feature and the node's leaf value comes from the totals of whichever feature wins.
-template <bool kSampled = false>
+// kMonotone: the three terms of a candidate's gain are bounded_term's under the node's own bounds (bounds[2 * node],
+// bounds[2 * node + 1]), and after the min_child_weight test a candidate whose clamped child weights stand in the wrong
+// order for monotone[f] is rejected.  The candidate order, the tie order and what thread 0 writes are unchanged.
+template <bool kSampled = false, bool kMonotone = false>
 __device__ inline void train_split_feature(long long *hist, const int32_t *counts, const Node *nodes,
                                            const int32_t *cut_offsets, int32_t nf, int32_t level,
                                            const TrainParams &params, Candidate *candidates,
-                                           const uint8_t *level_mask = nullptr)
+                                           const uint8_t *level_mask = nullptr, const int8_t *monotone = nullptr,
+                                           const double *bounds = nullptr)
 {
     __shared__ long long s_g[256], s_h[256];
     __shared__ double s_gain[256];
@@ -338,7 +364,14 @@ __device__ inline void train_split_feature(long long *hist, const int32_t *count
     const long long missing_g = total_g - s_g[254], missing_h = total_h - s_h[254];
     const double lambda = params.reg_lambda, mcw = params.min_child_weight;
     const double G = static_cast<double>(total_g) / kQuantum, H = static_cast<double>(total_h) / kQuantum;
-    const double parent_gain = node_gain(G, H, lambda);
+    double lo = 0.0, hi = 0.0;
+    int sign = 0;
+    if (kMonotone) {
+        lo = bounds[2 * node];
+        hi = bounds[2 * node + 1];
+        sign = monotone[f];
+    }
+    const double parent_gain = kMonotone ? bounded_term(G, H, lambda, lo, hi).term : node_gain(G, H, lambda);
     const int b = t + 1, n_bins = cut_offsets[f + 1] - cut_offsets[f] + 1;
     double best = -INFINITY;
     int32_t key = INT32_MAX;
@@ -349,7 +382,14 @@ __device__ inline void train_split_feature(long long *hist, const int32_t *count
             const double GR = static_cast<double>(total_g - lg) / kQuantum;
             const double HR = static_cast<double>(total_h - lh) / kQuantum;
             if (HL < mcw || HR < mcw) continue;
-            const double gain = node_gain(GL, HL, lambda) + node_gain(GR, HR, lambda) - parent_gain;
+            double gain;
+            if (kMonotone) {
+                const BoundedTerm left = bounded_term(GL, HL, lambda, lo, hi), right = bounded_term(GR, HR, lambda, lo, hi);
+                if ((sign > 0 && left.weight > right.weight) || (sign < 0 && left.weight < right.weight)) continue;
+                gain = left.term + right.term - parent_gain;
+            } else {
+                gain = node_gain(GL, HL, lambda) + node_gain(GR, HR, lambda) - parent_gain;
+            }
             if (gain > best) {
                 best = gain;
                 key = 2 * b + missing_left;
@@ -382,8 +422,13 @@ __device__ inline void train_split_feature(long long *hist, const int32_t *count
 }
 
 // ---- split choice, part 2: one thread per node of the level over its features' candidates ---------------------------
+// kMonotone: every leaf written is clamped to its own bounds, and a split writes its children's bounds: with mid the
+// mean of the winner's two clamped weights (under this node's bounds), [lo, mid] and [mid, hi] for the lower and the
+// higher side of a constrained feature, [lo, hi] for both children of an unconstrained one.
+template <bool kMonotone = false>
 __device__ inline void train_split_nodes(const Candidate *candidates, Node *nodes, int32_t nf, int32_t level,
-                                         const TrainParams &params)
+                                         const TrainParams &params, const int8_t *monotone = nullptr,
+                                         double *bounds = nullptr)
 {
     const int32_t index = blockIdx.x * 64 + threadIdx.x;
     if (index >= (1 << level)) return;
@@ -394,10 +439,16 @@ __device__ inline void train_split_nodes(const Candidate *candidates, Node *node
     for (int k = 1; k < nf; ++k)   // strictly greater: a tie keeps the lower feature
         if (mine[k].gain > mine[winner].gain) winner = k;
     const double lambda = params.reg_lambda;
-    auto leaf_value = [&](long long qg, long long qh) {
+    auto leaf_value = [&](long long qg, long long qh, double lo = 0.0, double hi = 0.0) {
         const double g = static_cast<double>(qg) / kQuantum, h = static_cast<double>(qh) / kQuantum;
+        if (kMonotone) return static_cast<float>(bounded_term(g, h, lambda, lo, hi).weight * params.eta);
         return static_cast<float>((-g / (h + lambda)) * params.eta);
     };
+    double lo = 0.0, hi = 0.0;
+    if (kMonotone) {
+        lo = bounds[2 * node];
+        hi = bounds[2 * node + 1];
+    }
     const Candidate &best = mine[winner];
     const long long G = best.total_g, H = best.total_h;
     Node &out = nodes[node];
@@ -414,11 +465,32 @@ __device__ inline void train_split_nodes(const Candidate *candidates, Node *node
         Node &left = nodes[2 * node + 1], &right = nodes[2 * node + 2];
         left.state = right.state = last ? kLeaf : kPending;
         left.feature = right.feature = -1;
-        left.leaf = last ? leaf_value(best.left_g, best.left_h) : 0.f;
-        right.leaf = last ? leaf_value(G - best.left_g, H - best.left_h) : 0.f;
+        double left_lo = lo, left_hi = hi, right_lo = lo, right_hi = hi;
+        if (kMonotone) {
+            const int sign = monotone[winner];
+            const double wl = bounded_term(static_cast<double>(best.left_g) / kQuantum,
+                                           static_cast<double>(best.left_h) / kQuantum, lambda, lo, hi).weight;
+            const double wr = bounded_term(static_cast<double>(G - best.left_g) / kQuantum,
+                                           static_cast<double>(H - best.left_h) / kQuantum, lambda, lo, hi).weight;
+            const double mid = (wl + wr) / 2.0;
+            if (sign > 0) {
+                left_hi = mid;
+                right_lo = mid;
+            } else if (sign < 0) {
+                left_lo = mid;
+                right_hi = mid;
+            }
+            double *child = bounds + 2 * (2 * node + 1);   // the left child's pair, then the right child's
+            child[0] = left_lo;
+            child[1] = left_hi;
+            child[2] = right_lo;
+            child[3] = right_hi;
+        }
+        left.leaf = last ? leaf_value(best.left_g, best.left_h, left_lo, left_hi) : 0.f;
+        right.leaf = last ? leaf_value(G - best.left_g, H - best.left_h, right_lo, right_hi) : 0.f;
     } else {
         out.state = kLeaf;
-        out.leaf = leaf_value(G, H);
+        out.leaf = leaf_value(G, H, lo, hi);
     }
 }
 

@@ -68,7 +68,8 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_bin_kernel(const float *
 // The model is v.active[the last grid dimension] (model 0 of a one-model view); the blocks of a model that has passed its own max_depth return at once.
 // kFolds = false (the single trainer) reads no fold byte; kSampled = false reads nothing of the sampling view.
 
-// start of a round: zero the active models' histograms (levels below their own max_depth), heaps, counts, errors
+// start of a round: zero the active models' histograms (levels below their own max_depth), heaps, counts, errors; with
+// monotone constraints the root's bounds are set here too
 __global__ __launch_bounds__(kRowThreads) void ds_train_clear_kernel(TrainView v)
 {
     const int32_t m = v.model_index(blockIdx.y);
@@ -81,7 +82,14 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_clear_kernel(TrainView v
     for (int64_t i = at; i < int64_t(v.slots) * (sizeof(Node) / 4); i += step) nodes[i] = 0u;
     int32_t *counts = v.counts + static_cast<int64_t>(m) * v.slots;
     for (int64_t i = at; i < v.slots; i += step) counts[i] = 0;
-    if (at == 0) v.errors[m] = 0ull;
+    if (at == 0) {
+        v.errors[m] = 0ull;
+        if (v.bounds != nullptr) {   // the root's weight is unbounded
+            double *bounds = v.bounds + static_cast<int64_t>(m) * 2 * v.slots;
+            bounds[0] = -INFINITY;
+            bounds[1] = INFINITY;
+        }
+    }
 }
 
 // the feature sets of the round: blockIdx.x = the model
@@ -127,26 +135,30 @@ __global__ __launch_bounds__(kHistThreads) void ds_train_histogram_kernel(TrainV
 }
 
 // blockIdx.x = the node's index in its level, blockIdx.y = the feature, blockIdx.z = the model
-template <bool kSampled>
+// kMonotone = false reads neither v.monotone nor v.bounds
+template <bool kSampled, bool kMonotone>
 __global__ __launch_bounds__(256) void ds_train_split_feature_kernel(TrainView v, TrainSamplingView s, int32_t level)
 {
     const int32_t m = v.model_index(blockIdx.z);
     const TrainModel model = v.model(m);
     if (level >= model.params.max_depth) return;
-    train_split_feature<kSampled>(v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots,
-                                  v.nodes + int64_t(m) * v.slots, v.cut_offsets, v.nf, level, model.params,
-                                  v.candidates + m * v.candidate_stride,
-                                  kSampled ? s.masks + static_cast<int64_t>(m) * kMaskBytes + level * kTrainFeaturesMax
-                                           : nullptr);
+    train_split_feature<kSampled, kMonotone>(
+        v.hist + m * v.hist_stride, v.counts + int64_t(m) * v.slots, v.nodes + int64_t(m) * v.slots, v.cut_offsets, v.nf,
+        level, model.params, v.candidates + m * v.candidate_stride,
+        kSampled ? s.masks + static_cast<int64_t>(m) * kMaskBytes + level * kTrainFeaturesMax : nullptr,
+        kMonotone ? v.monotone : nullptr, kMonotone ? v.bounds + int64_t(m) * 2 * v.slots : nullptr);
 }
 
 // blockIdx.x = 64 nodes of the level, blockIdx.y = the model
+template <bool kMonotone>
 __global__ __launch_bounds__(64) void ds_train_split_kernel(TrainView v, int32_t level)
 {
     const int32_t m = v.model_index(blockIdx.y);
     const TrainModel model = v.model(m);
     if (level >= model.params.max_depth) return;
-    train_split_nodes(v.candidates + m * v.candidate_stride, v.nodes + int64_t(m) * v.slots, v.nf, level, model.params);
+    train_split_nodes<kMonotone>(v.candidates + m * v.candidate_stride, v.nodes + int64_t(m) * v.slots, v.nf, level,
+                                 model.params, kMonotone ? v.monotone : nullptr,
+                                 kMonotone ? v.bounds + int64_t(m) * 2 * v.slots : nullptr);
 }
 
 __global__ __launch_bounds__(kRowThreads) void ds_train_partition_kernel(TrainView v, int32_t level)
@@ -453,7 +465,7 @@ int64_t capped(int64_t blocks)
     return std::max<int64_t>(1, cap > 0 ? std::min(blocks, cap) : blocks);
 }
 
-template <bool kFolds, bool kSampled>
+template <bool kFolds, bool kSampled, bool kMonotone>
 int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingView &s, int32_t n_active, int32_t depth,
                   int compute_units)
 {
@@ -483,11 +495,11 @@ int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingVie
                            dim3(static_cast<unsigned>(chunks), feature_groups * node_groups, models), dim3(kHistThreads),
                            0, stream, v, level, n_built, nodes_per_group, features_per_group, feature_groups);
         DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_train_split_feature_kernel<kSampled>, dim3(1u << level, v.nf, models), dim3(256), 0,
-                           stream, v, s, level);
+        hipLaunchKernelGGL((ds_train_split_feature_kernel<kSampled, kMonotone>), dim3(1u << level, v.nf, models),
+                           dim3(256), 0, stream, v, s, level);
         DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_train_split_kernel, dim3(((1u << level) + 63) / 64, models), dim3(64), 0, stream, v,
-                           level);
+        hipLaunchKernelGGL(ds_train_split_kernel<kMonotone>, dim3(((1u << level) + 63) / 64, models), dim3(64), 0,
+                           stream, v, level);
         DS_HIP(hipGetLastError());
         hipLaunchKernelGGL(ds_train_partition_kernel, rows, dim3(kRowThreads), 0, stream, v, level);
         DS_HIP(hipGetLastError());
@@ -510,11 +522,29 @@ int train_round_enqueue(hipStream_t stream, const TrainView &v, const TrainSampl
                         int32_t depth, bool folds, int compute_units)
 {
     const TrainSamplingView none{};
+    if (v.monotone != nullptr) {   // the kMonotone forms of the two split kernels; every other kernel is the same one
+        if (sampling != nullptr)
+            return folds ? enqueue_round<true, true, true>(stream, v, *sampling, n_active, depth, compute_units)
+                         : enqueue_round<false, true, true>(stream, v, *sampling, n_active, depth, compute_units);
+        return folds ? enqueue_round<true, false, true>(stream, v, none, n_active, depth, compute_units)
+                     : enqueue_round<false, false, true>(stream, v, none, n_active, depth, compute_units);
+    }
     if (sampling != nullptr)
-        return folds ? enqueue_round<true, true>(stream, v, *sampling, n_active, depth, compute_units)
-                     : enqueue_round<false, true>(stream, v, *sampling, n_active, depth, compute_units);
-    return folds ? enqueue_round<true, false>(stream, v, none, n_active, depth, compute_units)
-                 : enqueue_round<false, false>(stream, v, none, n_active, depth, compute_units);
+        return folds ? enqueue_round<true, true, false>(stream, v, *sampling, n_active, depth, compute_units)
+                     : enqueue_round<false, true, false>(stream, v, *sampling, n_active, depth, compute_units);
+    return folds ? enqueue_round<true, false, false>(stream, v, none, n_active, depth, compute_units)
+                 : enqueue_round<false, false, false>(stream, v, none, n_active, depth, compute_units);
+}
+
+int train_check_monotone(const char *who, const int8_t *constraints, int32_t n_features, bool *any)
+{
+    *any = false;
+    for (int32_t f = 0; f < n_features; ++f) {
+        DS_REQUIRE(constraints[f] >= -1 && constraints[f] <= 1, "%s: constraint %d of feature %d is not -1, 0 or 1", who,
+                   constraints[f], f);
+        *any = *any || constraints[f] != 0;
+    }
+    return DS_OK;
 }
 
 }  // namespace ds
@@ -526,6 +556,9 @@ struct ds_trainer {
     ds::TrainParams params{};
     bool has_labels = false, seeded = false;      // seeded: ds_trainer_seed has started the margins from a forest
     bool weighted = false;                        // ds_trainer_set_weights has been accepted
+    bool constrained = false;                     // ds_trainer_set_monotone has been accepted (all zeros too)
+    ds::DeviceBuffer<int8_t> monotone;            // ds_trainer_set_monotone with a non-zero entry: int8[nf] and
+    ds::DeviceBuffer<double> bounds;              // double[slots][2], the weight bounds of every heap slot
     int64_t rounds = 0;
     int32_t tree_base = 0;                        // the trees of that forest: the number of this trainer's first tree
     hipStream_t stream = nullptr;
@@ -766,6 +799,32 @@ int ds_trainer_set_weights(ds_trainer *trainer, const float *weights)
     DS_HIP(hipStreamSynchronize(t->stream));
     t->view.weights = t->weights.ptr;
     t->weighted = true;
+    return DS_OK;
+}
+
+int ds_trainer_set_monotone(ds_trainer *trainer, const int8_t *constraints)
+{
+    const char *who = "ds_trainer_set_monotone";
+    DS_REQUIRE(trainer != nullptr, "%s: trainer is null", who);
+    DS_REQUIRE(constraints != nullptr, "%s: constraints is null", who);
+    ds_trainer *t = trainer;
+    DS_REQUIRE(t->has_labels, "%s: no labels (ds_trainer_set_labels)", who);
+    DS_REQUIRE(t->rounds == 0, "%s: the constraints must be set before the first round", who);
+    DS_REQUIRE(!t->constrained, "%s: the constraints are already set", who);
+    bool any = false;
+    if (int status = ds::train_check_monotone(who, constraints, t->nf, &any); status != DS_OK) return status;
+    if (any) {   // all zeros: nothing is allocated and the plain kernels keep running
+        DS_HIP(hipSetDevice(t->device));
+        const size_t slots = static_cast<size_t>(t->view.slots);
+        if (int status = t->monotone.allocate(static_cast<size_t>(t->nf)); status != DS_OK) return status;
+        if (int status = t->bounds.allocate(2 * slots); status != DS_OK) return status;
+        DS_HIP(hipMemcpyAsync(t->monotone.ptr, constraints, static_cast<size_t>(t->nf), hipMemcpyHostToDevice, t->stream));
+        DS_HIP(hipMemsetAsync(t->bounds.ptr, 0, t->bounds.bytes(), t->stream));
+        DS_HIP(hipStreamSynchronize(t->stream));
+        t->view.monotone = t->monotone.ptr;
+        t->view.bounds = t->bounds.ptr;
+    }
+    t->constrained = true;
     return DS_OK;
 }
 

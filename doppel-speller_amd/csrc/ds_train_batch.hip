@@ -37,6 +37,11 @@
 // held-out row stays (0, 0) whatever it weighs.  The entry checks on the host that every model's training rows weigh
 // something and refuses by the model's number.  4n more bytes, outside ds_trainer_batch_bytes' formula.
 //
+// Monotone constraints (ds_trainer_batch_set_monotone; DESIGN.md section 9, "Monotone constraints"): ONE int8[nf] shared by
+// the models (TrainView::monotone, stride 0) and per model the weight bounds of its heap slots (TrainView::bounds, stride
+// 2 * slots); a step then launches the kMonotone forms of the two split kernels.  16 * slots * n_models + nf more bytes,
+// outside ds_trainer_batch_bytes' formula.
+//
 // Continuing from a model (ds_trainer_batch_seed; DESIGN.md section 9, "Continuing from a model"): before the first step
 // ds_train_seed_kernel walks a forest over the RAW matrix once per row and writes the leaf sum into all M leafsum columns;
 // ds_batch_error_kernel then gives every model's held-out error at those margins, and every model's tree count starts at
@@ -82,6 +87,9 @@ struct ds_trainer_batch {
     ds::DeviceBuffer<float> labels, leafsum, probabilities, cuts;
     ds::DeviceBuffer<float> weights;           // ds_trainer_batch_set_weights: float[n] shared by the models, 4n more bytes
     bool weighted = false;
+    bool constrained = false;                  // ds_trainer_batch_set_monotone has been accepted (all zeros too)
+    ds::DeviceBuffer<int8_t> monotone;         // with a non-zero entry: int8[nf] shared by the models, and the weight
+    ds::DeviceBuffer<double> bounds;           // bounds double[n_models][slots][2]
     ds::DeviceBuffer<int32_t> cut_offsets, node_of, counts, active;
     ds::DeviceBuffer<long long> gh, hist;
     ds::DeviceBuffer<ds::Node> nodes;
@@ -416,6 +424,32 @@ int ds_trainer_batch_set_weights(ds_trainer_batch *batch, const float *weights)
     DS_HIP(hipStreamSynchronize(b->stream));
     b->view.weights = b->weights.ptr;
     b->weighted = true;
+    return DS_OK;
+}
+
+int ds_trainer_batch_set_monotone(ds_trainer_batch *batch, const int8_t *constraints)
+{
+    const char *who = "ds_trainer_batch_set_monotone";
+    DS_REQUIRE(batch != nullptr, "%s: batch is null", who);
+    DS_REQUIRE(constraints != nullptr, "%s: constraints is null", who);
+    ds_trainer_batch *b = batch;
+    DS_REQUIRE(!b->stepped, "%s: the constraints must be set before the first step", who);
+    DS_REQUIRE(!b->constrained, "%s: the constraints are already set", who);
+    bool any = false;
+    if (int status = ds::train_check_monotone(who, constraints, b->nf, &any); status != DS_OK) return status;
+    if (any) {   // all zeros: nothing is allocated and the plain kernels keep running
+        DS_HIP(hipSetDevice(b->device));
+        const size_t pairs = static_cast<size_t>(b->n_models) * b->slots;
+        if (int status = ds::train_check_free(int64_t(16 * pairs) + b->nf, who); status != DS_OK) return status;
+        if (int status = b->monotone.allocate(static_cast<size_t>(b->nf)); status != DS_OK) return status;
+        if (int status = b->bounds.allocate(2 * pairs); status != DS_OK) return status;
+        DS_HIP(hipMemcpyAsync(b->monotone.ptr, constraints, static_cast<size_t>(b->nf), hipMemcpyHostToDevice, b->stream));
+        DS_HIP(hipMemsetAsync(b->bounds.ptr, 0, b->bounds.bytes(), b->stream));
+        DS_HIP(hipStreamSynchronize(b->stream));
+        b->view.monotone = b->monotone.ptr;
+        b->view.bounds = b->bounds.ptr;
+    }
+    b->constrained = true;
     return DS_OK;
 }
 

@@ -23,6 +23,16 @@ FEATURE_NAMES = (("title_characters", "truth_characters", "title_words", "truth_
                  + tuple(f"word_{w + 1}_characters" for w in range(NUMBER_OF_WORDS_FEATURES))
                  + tuple(f"word_{w + 1}_idf" for w in range(NUMBER_OF_WORDS_FEATURES))
                  + tuple(f"word_{w + 1}_idf_rank" for w in range(NUMBER_OF_WORDS_FEATURES)))
+# the similarity ratios among them: title_ratio, rebuilt_title_ratio and the word_k_best_ratio, 17 columns
+RATIO_FEATURE_NAMES = tuple(name for name in FEATURE_NAMES if name.endswith("_ratio"))
+
+
+def ratio_constraints():
+    """{name: 1} for every ratio column: the monotone_constraints (train.validate_monotone_constraints) under which
+    the match probability never falls when a title gets more similar to its candidate."""
+    return {name: 1 for name in RATIO_FEATURE_NAMES}
+
+
 ALLOWED_CHARACTERS = "- abcdefghijklmnopqrstuvwxyz0123456789"  # feature_engineering.py:200 ('-' = fill, code 0)
 _ENCODING = {character: index for index, character in enumerate(ALLOWED_CHARACTERS)}
 SPACE_CODE = _ENCODING[" "]                                    # feature_engineering.py:203

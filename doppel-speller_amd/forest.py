@@ -197,6 +197,44 @@ class ForestModel:
         return [{key: arrays[key][int(offsets[t]):int(offsets[t + 1])] for key in ForestModel.TREE_KEYS}
                 for t in range(offsets.shape[0] - 1)]
 
+    @staticmethod
+    def monotone_violations_of(arrays, constraints):
+        """monotone_violations of flat arrays (no library needed); `constraints`: one sign per feature index."""
+        feature, value, yes, no = arrays["feature"], arrays["threshold"], arrays["yes"], arrays["no"]
+        offsets = arrays["tree_offsets"]
+        violations = 0
+        for t in range(offsets.shape[0] - 1):
+            begin, size = int(offsets[t]), int(offsets[t + 1] - offsets[t])
+            if size == 0:
+                continue
+            order, at = [0], 0                                   # parents before their children, whatever the ids
+            while at < len(order):
+                i = order[at]
+                at += 1
+                if feature[begin + i] >= 0:
+                    order += [int(yes[begin + i]), int(no[begin + i])]
+            low, high = np.zeros(size, np.float32), np.zeros(size, np.float32)     # the leaf range below each node
+            for i in reversed(order):
+                f = int(feature[begin + i])
+                if f < 0:
+                    low[i] = high[i] = value[begin + i]
+                    continue
+                left, right = int(yes[begin + i]), int(no[begin + i])            # x < threshold, x >= threshold
+                low[i], high[i] = min(low[left], low[right]), max(high[left], high[right])
+                sign = int(constraints[f]) if f < len(constraints) else 0
+                if (sign > 0 and high[left] > low[right]) or (sign < 0 and low[left] < high[right]):
+                    violations += 1
+        return violations
+
+    def monotone_violations(self, constraints):
+        """The number of splits on a constrained feature whose subtrees stand in the wrong order: for a sign of +1 the
+        largest leaf below the `yes` child (x < threshold) exceeds the smallest below the `no` child, for -1 the
+        reverse.  0 means every tree, and so the margin, is monotone in each constrained feature; a row with the
+        feature missing follows the split's default branch and is outside the claim.  A host function of the arrays
+        alone, so it judges xgboost imports too.  constraints: train.validate_monotone_constraints' sequence form."""
+        from .train import validate_monotone_constraints
+        return self.monotone_violations_of(self.arrays, validate_monotone_constraints(constraints, self.n_features))
+
     def _from_arrays(self, a):
         return type(self)(a["feature"], a["threshold"], a["yes"], a["no"], a["missing"], a["tree_offsets"],
                           self.n_features, a["base_margin"], self.device)

@@ -367,6 +367,47 @@ def validate_sample_weight(sample_weight, n, beta=5.0):
     return weights
 
 
+def validate_monotone_constraints(constraints, n_features, feature_names=None):
+    """The checks of a `monotone_constraints` argument (no library needed) -> contiguous int8[n_features] (DESIGN.md
+    section 9, "Monotone constraints"; xgboost's monotone_constraints).  Either a 1-D sequence of n_features integers,
+    each -1 (the prediction never rises with the feature), 0 (free) or +1 (it never falls): bools, floats that are not
+    whole and NaN are refused, a wrong length by name.  Or, when `feature_names` names the n_features columns, a dict
+    {feature name: sign}, a name left out being 0; an unknown name is refused, listing it."""
+    def sign(value, what):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) or \
+                value not in (-1, 0, 1):          # NaN and 0.5 are in no tuple; 1.0 is
+            raise ValueError(f"monotone_constraints: {what} must be -1, 0 or 1, not {value!r}")
+        return int(value)
+
+    out = np.zeros(n_features, np.int8)
+    if isinstance(constraints, dict):
+        if feature_names is None:
+            raise ValueError("monotone_constraints by name (a dict) needs the feature names; give a sequence of "
+                             f"{n_features} signs")
+        names = list(feature_names)
+        if len(names) != n_features:
+            raise ValueError(f"monotone_constraints: {len(names)} feature names for {n_features} features")
+        unknown = sorted(str(name) for name in constraints if name not in names)
+        if unknown:
+            raise ValueError(f"monotone_constraints names unknown features {unknown}")
+        for name, value in constraints.items():
+            out[names.index(name)] = sign(value, f"the sign of {name!r}")
+        return out
+    if isinstance(constraints, (str, bytes)) or not isinstance(constraints, (list, tuple, np.ndarray)):
+        raise ValueError(f"monotone_constraints must be a 1-D sequence of {n_features} signs or a dict by feature "
+                         f"name, not {constraints!r}")
+    if isinstance(constraints, np.ndarray) and constraints.ndim != 1:
+        raise ValueError(f"monotone_constraints must be 1-D, not shape {constraints.shape}")
+    if len(constraints) != n_features:
+        raise ValueError(f"{n_features} features but {len(constraints)} monotone_constraints")
+    if isinstance(constraints, np.ndarray) and (constraints.dtype == bool or not (
+            np.issubdtype(constraints.dtype, np.integer) or np.issubdtype(constraints.dtype, np.floating))):
+        raise ValueError(f"monotone_constraints must hold -1, 0 or 1, not {constraints.dtype}")
+    for f, value in enumerate(constraints):
+        out[f] = sign(value, f"entry {f}")
+    return out
+
+
 def _samples(params):
     """Whether a parameter set draws rows or columns: a fraction below 1 (a set that carries none draws nothing)."""
     return any(params.get(name, 1.0) < 1 for name in SAMPLING_NAMES[:3])
@@ -495,7 +536,8 @@ class ForestTrainer(_TrainerHandle):
         model = ForestTrainer().fit(features, target, eval_features, eval_target, max_depth=5, eta=0.1)
 
     The data arguments may be given by position; the booster parameters (validate_parameters: its signature is their
-    list and their defaults), `init_model`, `sample_weight` and the device forms' `n_features` by keyword ONLY.  fit
+    list and their defaults), `init_model`, `sample_weight`, `monotone_constraints` and the device forms' `n_features` by
+    keyword ONLY.  fit
     and fit_device take all of them; begin and begin_device all but num_boost_round and early_stopping_rounds.  A name that
     validate_parameters does not know is a TypeError.  Everything is validated, once, before the library is touched,
     and a trainer whose begin or fit is refused keeps the state it had.
@@ -526,7 +568,16 @@ class ForestTrainer(_TrainerHandle):
     labels, a host array for all four forms, and is kept as `sample_weight` (float32, None without).  The weights do
     NOT touch the cuts, the `subsample` draw (indexed by row number), the evaluation error, `initial_error`, early
     stopping, `eval_metrics` (counts over rows) or ForestModel.fit_cover (counts rows).  See validate_sample_weight
-    for what is accepted; all weights 1 grows the trees of a call without the argument, bit for bit."""
+    for what is accepted; all weights 1 grows the trees of a call without the argument, bit for bit.
+
+    monotone_constraints=<n_features signs> makes every new tree, and so the forest's margin, monotone in the features
+    it names (xgboost's monotone_constraints; DESIGN.md section 9, "Monotone constraints"): +1 never falls as the
+    feature rises, -1 never rises, 0 is free.  The split choice rejects candidates whose children stand in the wrong
+    order and clamps weights to the bounds a constrained split leaves its children; cuts, gradients, draws, errors,
+    metrics and cover are untouched.  It is kept as `monotone_constraints` (int8, None without); None or all zeros makes
+    exactly the calls of a trainer that knows no constraints.  With init_model the NEW trees are constrained, the init
+    trees are what they are.  ForestModel.monotone_violations(constraints) counts the splits that break it: 0 for every
+    model grown here.  See validate_monotone_constraints for what is accepted."""
     ENTRIES, READS = "ds_trainer", ("margins", "probabilities", "gradients", "bins", "eval_margins")
 
     def __init__(self, device=0):
@@ -538,6 +589,7 @@ class ForestTrainer(_TrainerHandle):
         self.init_model = None
         self.initial_error = None
         self.sample_weight = None
+        self.monotone_constraints = None
         self.eval_metrics = ()
         self.metrics_history = {}
         self.metric_counts = []
@@ -562,7 +614,7 @@ class ForestTrainer(_TrainerHandle):
         self._begin(True, (d_features, n, target, d_eval_features, n_eval, eval_target), **parameters)
         return self._boost(self.params)
 
-    def _begin(self, in_hbm, data, init_model=None, sample_weight=None, **parameters):
+    def _begin(self, in_hbm, data, init_model=None, sample_weight=None, monotone_constraints=None, **parameters):
         """The one sequence behind the four forms above; `data` are their data arguments.  Everything is validated
         first: until that has passed the library is not touched and this trainer keeps the state it has."""
         if in_hbm:
@@ -575,9 +627,12 @@ class ForestTrainer(_TrainerHandle):
             validate_init_model(init_model, n_features, self.device)
         if sample_weight is not None:
             sample_weight = validate_sample_weight(sample_weight, n, params["beta"])
+        if monotone_constraints is not None:
+            monotone_constraints = validate_monotone_constraints(monotone_constraints, n_features)
         self.close()
         self.params = params
         self.sample_weight = sample_weight
+        self.monotone_constraints = monotone_constraints
         self.n, self.n_features, self.n_eval = n, n_features, n_eval
         self.timings = {}
         mark = time.perf_counter()
@@ -600,6 +655,9 @@ class ForestTrainer(_TrainerHandle):
         if sample_weight is not None:          # none: exactly the calls of a trainer that knows no weights
             _lib.check(library.ds_trainer_set_weights(self.handle, _lib.pointer(sample_weight)),
                        "ds_trainer_set_weights")
+        if monotone_constraints is not None and monotone_constraints.any():   # none or all zeros: nothing to set
+            _lib.check(library.ds_trainer_set_monotone(self.handle, _lib.pointer(monotone_constraints)),
+                       "ds_trainer_set_monotone")
         if n_eval:
             _call("ds_trainer_set_eval", in_hbm, self.handle, _lib.pointer(eval_features), _lib.pointer(eval_target),
                   n_eval)
@@ -716,7 +774,7 @@ class TrainModelResult:
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
-                kind_weights=None, **fit_parameters):
+                kind_weights=None, monotone_constraints=None, **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -732,8 +790,10 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     device chain is the same, seeded from the matrices in HBM, and the result gains `initial_error`.
     kind_weights: {"generated", "negative", "positive"} -> the sample weight of the training rows of that kind (a name
     left out: 1.0; training_set.kind_weights), handed to fit_device as sample_weight.  The weights enter the objective
-    alone (ForestTrainer): the evaluation error, error_matrix and a counted cover stay counts over rows."""
-    from .feature_engineering import FEATURES_COUNT
+    alone (ForestTrainer): the evaluation error, error_matrix and a counted cover stay counts over rows.
+    monotone_constraints: ForestTrainer's, as FEATURES_COUNT signs or as a dict by FEATURE_NAMES
+    (feature_engineering.ratio_constraints() constrains the 17 similarity ratios upwards), handed to fit_device."""
+    from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
     unknown = set(fit_parameters) - set(inspect.signature(validate_parameters).parameters)
@@ -744,6 +804,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         validate_init_model(init_model, FEATURES_COUNT, device)
     if kind_weights is not None:
         validate_kind_weights(kind_weights)
+    if monotone_constraints is not None:
+        monotone_constraints = validate_monotone_constraints(monotone_constraints, FEATURES_COUNT, FEATURE_NAMES)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=evaluation_fractions, build_index=build_index)
@@ -756,7 +818,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     try:
         model = trainer.fit_device(sets.train, sets.n_train, sets.train_target, sets.evaluation if has_eval else None,
                                    sets.n_evaluation, sets.evaluation_target if has_eval else None,
-                                   init_model=init_model, **weighted, **fit_parameters)
+                                   init_model=init_model, monotone_constraints=monotone_constraints, **weighted,
+                                   **fit_parameters)
     except ValueError:              # weights the rows of this training set cannot carry: free what the call holds
         sets.free()
         raise

@@ -17,7 +17,7 @@ from . import _lib
 from .train import (METRIC_NAMES, SAMPLING_NAMES, FirstMinimum, _call, _device_columns, _device_labels,
                     _matrix_and_labels, _positive_int, _samples, _TrainerHandle, auc_numerator, compute_cuts,
                     compute_cuts_device, heap_tree, metric_values, validate_init_model, validate_metrics,
-                    validate_parameters, validate_sample_weight)
+                    validate_monotone_constraints, validate_parameters, validate_sample_weight)
 
 MODELS_MAX = 256          # ds_train_batch.hip kBatchModelsMax
 FOLDS_MAX = 255           # ds_train_batch.hip kBatchFoldsMax
@@ -302,7 +302,11 @@ class ForestTrainerBatch(_TrainerHandle):
     "Sample weights"): ONE array over all rows, like the labels; model m is ForestTrainer(sample_weight=...)'s on its
     training rows with their weights, and a held-out row trains nothing whatever its weight.  Every model's training
     rows need a total weight above 0 (validate_batch_weight names the model that has none).  The held-out errors and
-    the metrics stay counts over rows."""
+    the metrics stay counts over rows.
+
+    begin(..., monotone_constraints=<n_features signs>) constrains every model alike ("Monotone
+    constraints"): ONE vector for the batch, and model m is ForestTrainer(monotone_constraints=...)'s on its training
+    rows.  None or all zeros makes exactly the calls of a batch that knows no constraints."""
     ENTRIES, READS = "ds_trainer_batch", ("margins", "probabilities", "gradients", "bins")
 
     def __init__(self, device=0):
@@ -312,16 +316,17 @@ class ForestTrainerBatch(_TrainerHandle):
         self.metrics, self.metrics_history, self.metric_counts = (), [], []
         self.init_model, self.initial_errors = None, []
         self.sample_weight = None
+        self.monotone_constraints = None
         self.timings = {}
 
     def begin(self, features, target, fold, models, max_bin=256, cuts=None, metrics=(), init_model=None,
-              sample_weight=None):
+              sample_weight=None, monotone_constraints=None):
         features, target = _matrix_and_labels(features, target, "training")
         return self._begin(features, False, features.shape[0], features.shape[1], target, fold, models, max_bin, cuts,
-                           metrics, init_model, sample_weight)
+                           metrics, init_model, sample_weight, monotone_constraints)
 
     def begin_device(self, d_features, n, target, fold, models, n_features=None, max_bin=256, cuts=None, metrics=(),
-                     init_model=None, sample_weight=None):
+                     init_model=None, sample_weight=None, monotone_constraints=None):
         """begin for a contiguous float32[n, n_features] matrix that lies complete in HBM (a DeviceArray, or an address
         with n_features given).  It is read where it lies, never copied to the host, and not kept."""
         n_features = _device_columns(d_features, n_features)
@@ -329,10 +334,10 @@ class ForestTrainerBatch(_TrainerHandle):
         if isinstance(d_features, _lib.DeviceArray) and n > d_features.shape[0]:
             raise ValueError(f"{n} training rows exceed the device matrix's {d_features.shape[0]}")
         return self._begin(d_features, True, n, n_features, target, fold, models, max_bin, cuts, metrics, init_model,
-                           sample_weight)
+                           sample_weight, monotone_constraints)
 
     def _begin(self, features, in_hbm, n, n_features, target, fold, models, max_bin, cuts, metrics=(), init_model=None,
-               sample_weight=None):
+               sample_weight=None, monotone_constraints=None):
         metrics = validate_metrics(metrics, "metrics")
         if init_model is not None:
             validate_init_model(init_model, n_features, self.device)
@@ -343,8 +348,11 @@ class ForestTrainerBatch(_TrainerHandle):
         max_bin = _positive_int("max_bin", max_bin, 2, 256)
         if sample_weight is not None:
             sample_weight = validate_batch_weight(sample_weight, n, fold, held_out, sets)
+        if monotone_constraints is not None:
+            monotone_constraints = validate_monotone_constraints(monotone_constraints, n_features)
         self.close()
         self.sample_weight = sample_weight
+        self.monotone_constraints = monotone_constraints
         self.timings = {}
         mark = time.perf_counter()
         if cuts is None:
@@ -367,6 +375,9 @@ class ForestTrainerBatch(_TrainerHandle):
         if sample_weight is not None:
             _lib.check(_lib.lib().ds_trainer_batch_set_weights(self.handle, _lib.pointer(sample_weight)),
                        "ds_trainer_batch_set_weights")
+        if monotone_constraints is not None and monotone_constraints.any():   # none or all zeros: nothing to set
+            _lib.check(_lib.lib().ds_trainer_batch_set_monotone(self.handle, _lib.pointer(monotone_constraints)),
+                       "ds_trainer_batch_set_monotone")
         if any(_samples(one) for one in sets):
             fractions = np.array([[one[name] for name in SAMPLING_NAMES[:3]] for one in sets], np.float64)
             seeds = np.array([one["sample_seed"] for one in sets], np.uint64)
@@ -492,7 +503,7 @@ def _sets_per_batch(n, n_features, in_hbm, sets, n_folds, device, metrics=(), we
 
 def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0, num_boost_round=1000,
                    early_stopping_rounds=50, max_bin=256, refit=True, device=0, models_per_batch=None, metrics=(),
-                   select_by="error", init_model=None, sample_weight=None):
+                   select_by="error", init_model=None, sample_weight=None, monotone_constraints=None):
     """K-fold cross-validation of one parameter set or a list of them (parameter_grid) on the GPU -> CrossValidation.
 
     features: a host matrix, or a DeviceArray float32[>= n, n_features] in HBM of which the first len(target) rows
@@ -520,7 +531,11 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
     of every set trains with the weights of its training rows, and so does the refit on all rows, which is
     ForestTrainer().fit(..., sample_weight=sample_weight, ...) as above, bit for bit.  `results`, the curves and the
     selection stay on the UNWEIGHTED out-of-fold error and metrics.  A fold whose training rows all weigh 0 is a
-    ValueError that names the model."""
+    ValueError that names the model.
+
+    monotone_constraints: one sign per feature (train.validate_monotone_constraints; DESIGN.md section 9, "Monotone
+    constraints").  Every fold of every set and the refit grow their trees under it; the refit is
+    ForestTrainer().fit(..., monotone_constraints=monotone_constraints, ...) as above, bit for bit."""
     started = time.perf_counter()
     sets, per_batch = validate_cross_validation(parameters, n_folds, seed, num_boost_round, early_stopping_rounds,
                                                 max_bin, models_per_batch, metrics, select_by)
@@ -537,6 +552,8 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
         n, n_features = features.shape
     if init_model is not None:
         validate_init_model(init_model, n_features, device)
+    if monotone_constraints is not None:
+        monotone_constraints = validate_monotone_constraints(monotone_constraints, n_features)
     folds = fold_assignment(groups, n_folds, seed, n)
     if sample_weight is not None:       # every set holds the same folds out: one set's models stand for all
         sample_weight = validate_batch_weight(sample_weight, n, folds, list(range(n_folds)) + [-1], sets)
@@ -551,9 +568,10 @@ def cross_validate(features, target, parameters, n_folds=5, groups=None, seed=0,
         batch = ForestTrainerBatch(device)
         if in_hbm:
             batch.begin_device(features, n, target, folds, models, n_features, max_bin, cuts, metrics, init_model,
-                               sample_weight)
+                               sample_weight, monotone_constraints)
         else:
-            batch.begin(features, target, folds, models, max_bin, cuts, metrics, init_model, sample_weight)
+            batch.begin(features, target, folds, models, max_bin, cuts, metrics, init_model, sample_weight,
+                        monotone_constraints)
         timings["bin"] += batch.timings["bin"]
         return batch
 
@@ -626,7 +644,7 @@ def row_groups(rows):
 
 def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters, n_folds=5, top_n=100,
                           sample_n=10, seed=0, device=0, transform=True, cover=False, init_model=None,
-                          kind_weights=None, **cv_arguments):
+                          kind_weights=None, monotone_constraints=None, **cv_arguments):
     """Parameter search from raw titles in one call: FeatureEngineering(..., no evaluation split).
     generate_device_data_sets() -> cross_validate on the matrix in HBM, folds by row_groups -> the refit model.
     cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch, metrics, select_by.  Returns cross_validate's result
@@ -635,9 +653,10 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
     model can explain its predictions; `timings` then has "cover".  init_model: cross_validate's, a ForestModel of
     FEATURES_COUNT features that every fold, set and the refit continue from.  kind_weights: {"generated", "negative",
     "positive"} -> the sample weight of the rows of that kind (training_set.kind_weights; a name left out: 1.0), handed
-    to cross_validate as sample_weight.  Everything is validated before any device work and everything held in HBM is
+    to cross_validate as sample_weight.  monotone_constraints: cross_validate's, as FEATURES_COUNT signs or as a dict by
+    FEATURE_NAMES (feature_engineering.ratio_constraints()).  Everything is validated before any device work and everything held in HBM is
     freed on every exit path."""
-    from .feature_engineering import FEATURES_COUNT
+    from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
     unknown = set(cv_arguments) - {"num_boost_round", "early_stopping_rounds", "max_bin", "models_per_batch", "metrics",
@@ -649,6 +668,8 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
         validate_init_model(init_model, FEATURES_COUNT, device)
     if kind_weights is not None:
         validate_kind_weights(kind_weights)
+    if monotone_constraints is not None:
+        monotone_constraints = validate_monotone_constraints(monotone_constraints, FEATURES_COUNT, FEATURE_NAMES)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=dict(generated=0.0, negative=0.0, positive=0.0))
@@ -658,7 +679,7 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
         out = cross_validate(matrix, sets.train_target, parameters, n_folds=n_folds, groups=row_groups(fe.rows),
                              seed=seed, refit=True, device=device, init_model=init_model,
                              sample_weight=None if kind_weights is None else weights_of_kinds(fe.rows, kind_weights),
-                             **cv_arguments)
+                             monotone_constraints=monotone_constraints, **cv_arguments)
         if cover:
             mark = time.perf_counter()
             out.model.fit_cover_device(sets.train, sets.n_train)

@@ -12,7 +12,8 @@ top-k pairs of the train queries labelled with their known source row) and the r
 (synth.make_forest) that the other examples use.
 
     python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH]
-                                   [--kind-weights generated=0.5,positive=2] [n_truth] [n_queries] [top_n] [model.npz]
+                                   [--kind-weights generated=0.5,positive=2] [--monotone ratios]
+                                   [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
 --one-call trains with ds.train_model(...), the same steps in one call with the feature matrix kept in HBM; the model
@@ -26,6 +27,9 @@ printed next to the best new round's.
 --kind-weights NAME=W,... weighs the training rows of a kind (generated, negative, positive; a kind left out: 1) in the
 objective: ds.train_model(..., kind_weights=) with --one-call, ForestTrainer.fit(..., sample_weight=ds.kind_weights(
 fe.rows, ...)) without.  The evaluation error stays a count over rows.
+--monotone ratios constrains the 17 similarity ratios upwards (ds.ratio_constraints()): the match probability never
+falls when a ratio rises; --monotone title_ratio=1,word_1_best_ratio=1 names columns of ds.FEATURE_NAMES and their
+signs.  The number of splits that break the constraints is printed for the model (0 under them).
 """
 import os
 import sys
@@ -64,12 +68,21 @@ def print_rounds(metrics_history, history):
         print(f"[{round_}]\t" + "\t".join(parts))
 
 
+def monotone_argument(text):
+    """--monotone's value -> a dict by feature name: `ratios`, or NAME=SIGN,..."""
+    if text == "ratios":
+        return ds.ratio_constraints()
+    return {name: int(sign) for name, sign in (pair.split("=") for pair in text.split(","))}
+
+
 def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None,
-         kind_weights=None):
+         kind_weights=None, monotone=None):
     init = ds.ForestModel.load(init_model) if init_model else None
     init_trees = init.n_trees if init else 0
     if init:
         print(f"continuing from {init_model}: {init_trees} trees")
+    constraints = None if monotone is None else \
+        ds.validate_monotone_constraints(monotone, ds.FEATURES_COUNT, ds.FEATURE_NAMES)
     train = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     evaluation = synth.make_workload(n_truth, n_queries // 4, seed=11, query_seed=102)
     held_out = synth.make_workload(n_truth, n_queries, seed=11, query_seed=103)
@@ -81,7 +94,7 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
     if one_call:
         t0 = time.perf_counter()
         result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics),
-                                init_model=init, kind_weights=kind_weights)
+                                init_model=init, kind_weights=kind_weights, monotone_constraints=monotone)
         t1 = time.perf_counter()
         model = result.model
         if metrics:
@@ -107,7 +120,7 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         trainer = ds.ForestTrainer()
         weighted = {} if kind_weights is None else dict(sample_weight=ds.kind_weights(fe.rows, kind_weights))
         model = trainer.fit(features, labels, eval_features, eval_labels, eval_metrics=tuple(metrics), init_model=init,
-                            **weighted)
+                            monotone_constraints=constraints, **weighted)
         t1 = time.perf_counter()
         if metrics:
             print_rounds(trainer.metrics_history, trainer.history)
@@ -120,6 +133,9 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         top = np.argsort(-model.feature_importance())[:5]
         print("most used features:", ", ".join(f"f{f} {model.feature_importance()[f]:.3f}" for f in top))
 
+    if constraints is not None:
+        print(f"monotone constraints on {int(np.count_nonzero(constraints))} features: "
+              f"{model.monotone_violations(constraints)} splits of the model break them")
     path = path or os.path.join(tempfile.mkdtemp(prefix="ds_model_"), "model.npz")
     model.save(path)
     model = ds.ForestModel.load(path)
@@ -159,5 +175,12 @@ if __name__ == "__main__":
             raise SystemExit("--kind-weights needs NAME=WEIGHT,... over generated, negative, positive")
         kinds = {name: float(value) for name, value in (pair.split("=") for pair in arguments[at + 1].split(","))}
         del arguments[at:at + 2]
+    monotone = None
+    if "--monotone" in arguments:
+        at = arguments.index("--monotone")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--monotone needs `ratios` or NAME=SIGN,... over ds.FEATURE_NAMES")
+        monotone = monotone_argument(arguments[at + 1])
+        del arguments[at:at + 2]
     main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted,
-         init_model=init_path, kind_weights=kinds)
+         init_model=init_path, kind_weights=kinds, monotone=monotone)

@@ -9,7 +9,8 @@ It prints the `results` table (one line per parameter set: the out-of-fold custo
 set and the stages' times.
 
     python examples/tune_model.py [--subsample 0.5,1] [--colsample-bytree 0.5,1] [--metrics auc,logloss]
-                                  [--select-by auc] [--init-model PATH] [n_truth] [n_queries] [n_folds]
+                                  [--select-by auc] [--init-model PATH] [--monotone ratios]
+                                  [n_truth] [n_queries] [n_folds]
 
 --subsample and --colsample-bytree take comma-separated fractions in (0, 1] and add them to the grid as further axes
 (row and column subsampling, ForestTrainer's parameters of those names); without them the grid is the plain one.
@@ -19,6 +20,8 @@ in every round; --select-by error|auc|logloss names the curve that the rounds ar
 --init-model PATH starts every fold of every set, and the refit, from the ForestModel saved at PATH (for instance
 examples/train_model.py's model.npz): the table counts the NEW rounds, and its `initial_error` column is the init
 model's own out-of-fold error, the baseline that continuing has to beat.
+--monotone ratios constrains the 17 similarity ratios upwards in every fold, set and the refit (ds.ratio_constraints());
+--monotone title_ratio=1,word_1_best_ratio=1 names columns of ds.FEATURE_NAMES and their signs.
 """
 import os
 import sys
@@ -31,7 +34,7 @@ from doppel_speller_amd import synth  # noqa: E402
 
 
 def main(n_truth=20000, n_queries=4000, n_folds=5, subsample=None, colsample_bytree=None, metrics=(),
-         select_by="error", init_model=None):
+         select_by="error", init_model=None, monotone=None):
     init = ds.ForestModel.load(init_model) if init_model else None
     w = synth.make_workload(n_truth, n_queries, seed=11, query_seed=101)
     truth_titles = synth._to_strings(w.t_flat, w.t_off)
@@ -42,7 +45,8 @@ def main(n_truth=20000, n_queries=4000, n_folds=5, subsample=None, colsample_byt
     grid = ds.parameter_grid(max_depth=[3, 5], eta=[0.1, 0.3], beta=[2.0, 5.0], **sampling)
     tuned = ds.tune_model_parameters(truth_titles, w.title_id, train_titles, train_ids, grid, n_folds=n_folds,
                                      transform=False, num_boost_round=300, early_stopping_rounds=30,
-                                     metrics=tuple(metrics), select_by=select_by, init_model=init)
+                                     metrics=tuple(metrics), select_by=select_by, init_model=init,
+                                     monotone_constraints=monotone)
     print(tuned.results.to_string())
     print(f"{len(tuned.rows)} rows, {n_folds} folds x {len(grid)} sets; chosen: {tuned.best_parameters}, "
           f"{tuned.best_iteration + 1} trees"
@@ -51,6 +55,10 @@ def main(n_truth=20000, n_queries=4000, n_folds=5, subsample=None, colsample_byt
           + f", out-of-fold error {tuned.results['error'][tuned.chosen]}"
           + "".join(f", {name} {tuned.results[name][tuned.chosen]:.6f}" for name in metrics)
           + (f" (chosen by {select_by})" if select_by != "error" else ""))
+    if monotone is not None:
+        vector = ds.validate_monotone_constraints(monotone, ds.FEATURES_COUNT, ds.FEATURE_NAMES)
+        print(f"monotone constraints on {int(np.count_nonzero(vector))} features: "
+              f"{tuned.model.monotone_violations(vector)} splits of the refit model break them")
     print("ms:", {stage: round(ms, 1) for stage, ms in tuned.timings.items()})
     return tuned
 
@@ -70,6 +78,12 @@ def _arguments(argv):
                 raise SystemExit(f"{argument} needs a value")
             value = argv.pop(0)
             options[argument[2:].replace("-", "_")] = tuple(value.split(",")) if argument == "--metrics" else value
+        elif argument == "--monotone":
+            if not argv:
+                raise SystemExit("--monotone needs `ratios` or NAME=SIGN,... over ds.FEATURE_NAMES")
+            value = argv.pop(0)
+            options["monotone"] = ds.ratio_constraints() if value == "ratios" else \
+                {name: int(sign) for name, sign in (pair.split("=") for pair in value.split(","))}
         else:
             positional.append(int(argument))
     return positional, options

@@ -585,6 +585,21 @@ int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsam
  * second call; a call after a step.  The array costs 4 n bytes of HBM.  ds_trainer_read's gradients are the weighted
  * integers. */
 int ds_trainer_set_weights(ds_trainer *trainer, const float *weights);
+/* Monotone constraints per feature ("Monotone constraints"; xgboost's monotone_constraints):
+ * constraints is a host int8[n_features] of -1, 0 and +1.  Every node of a tree carries bounds [lo, hi] on its weight,
+ * the root's infinite, all in double.  With w = -G / (H + lambda) and w* = min(max(w, lo), hi), a node's gain term is
+ * G G / (H + lambda) while lo <= w <= hi and -(2 G w* + (H + lambda) w* w*) otherwise; a candidate's gain is the terms
+ * of its two children minus the node's, all under the node's bounds, and after the min_child_weight test a candidate on
+ * feature f is rejected when constraints[f] > 0 and wL* > wR*, or constraints[f] < 0 and wL* < wR*.  The children of a
+ * split on a constrained feature share mid = (wL* + wR*) / 2 as the bound between them, those of any other split
+ * inherit [lo, hi], and every leaf is float(w* * eta) under its own bounds.  So every tree is monotone in each
+ * constrained feature, and while no bound is finite every number is the unconstrained rule's, bit for bit.  Cuts,
+ * gradients, histograms, draws, errors, metrics and cover are untouched.
+ * Legal once, after ds_trainer_set_labels and before the first step.  DS_E_ARG with a message, nothing launched and the
+ * trainer still usable unconstrained, for: a null pointer; a value outside {-1, 0, 1}; a second call; a call after a
+ * step.  An all-zero array is accepted, allocates nothing and leaves the trainer unconstrained; any other costs
+ * n_features + 16 * (2^(max_depth + 1) - 1) bytes of HBM. */
+int ds_trainer_set_monotone(ds_trainer *trainer, const int8_t *constraints);
 
 /* ---- the train-model step without a host copy of the feature matrix ("One call") ----------------
  * ds_feature_cuts_device: compute_cuts of a contiguous float32[n][n_features] matrix in HBM, bit-identical to the host
@@ -652,7 +667,8 @@ int ds_trainer_batch_read(ds_trainer_batch *batch, int32_t model, float *margins
 /* The bytes of HBM that ds_trainer_batch_create_device needs for n_models models whose largest max_depth is max_depth:
  * n * n_features + 5 n shared, and per model 28 n + (2^max_depth - 1) * n_features * 4096 + a few KiB.  -1 for
  * arguments outside the limits above.  Sample weights (ds_trainer_batch_set_weights) add 4 n bytes, shared by the
- * models, which this formula does not count. */
+ * models, and monotone constraints (ds_trainer_batch_set_monotone) 16 * slots * n_models + n_features bytes; this
+ * formula counts neither. */
 int64_t ds_trainer_batch_bytes(int64_t n, int32_t n_features, int32_t n_models, int32_t max_depth);
 /* ds_trainer_set_sampling for every model of a batch, valid only before the first ds_trainer_batch_step:
  * fractions[3m .. 3m + 3) = subsample, colsample_bytree, colsample_bylevel of model m, sample_seeds[m] its seed.  Every
@@ -668,6 +684,11 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
  * the rows outside the held-out fold of EVERY model must have a total weight above 0: DS_E_ARG names the first model
  * that has none.  Adds 4 n bytes of HBM to ds_trainer_batch_bytes, whose formula does not count them. */
 int ds_trainer_batch_set_weights(ds_trainer_batch *batch, const float *weights);
+/* ds_trainer_set_monotone for a batch: ONE host int8[n_features] for all models, legal once and before the first
+ * ds_trainer_batch_step; a model's trees are those of ds_trainer with the same constraints on its training rows.  With
+ * slots = 2^(D + 1) - 1, D the largest max_depth of the batch, a vector that is not all zeros adds
+ * 16 * slots * n_models + n_features bytes of HBM, which ds_trainer_batch_bytes does not count. */
+int ds_trainer_batch_set_monotone(ds_trainer_batch *batch, const int8_t *constraints);
 /* For tests: ds_trainer_batch_option("max_blocks", b) caps every grid of a training round that runs over rows at b
  * workgroups, which stride beyond it (0: back to the default).  It also caps the round of ds_trainer_step, which launches
  * the same kernels.  The results do not depend on it. */

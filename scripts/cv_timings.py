@@ -11,10 +11,11 @@ batch's boost time per round, and 60 x the single trainer's per-round time.
 
 `single` is ForestTrainer on all rows at depth 5, the median of 10 rounds after 2: the figure of section 9's table.
 
-    python scripts/cv_timings.py [rows] [rounds] [--batch-only] [--once] [--single-only] [--subsample=F]
+    python scripts/cv_timings.py [rows] [rounds] [--batch-only] [--once] [--single-only] [--subsample=F] [--monotone]
 
 --batch-only leaves out the sequential path, --once runs each path a single time without a warm-up (for a kernel trace),
---single-only stops after the single trainer's figure, --subsample=F adds the single trainer's figure with subsample F.
+--single-only stops after the single trainer's figure, --subsample=F adds the single trainer's figure with subsample F,
+--monotone its figure with the first 17 of the 66 columns constrained upwards ("Monotone constraints").
 """
 import os
 import statistics
@@ -34,7 +35,7 @@ def data(n, nf=66, seed=3):
     return x, y
 
 
-def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False, subsample=None):
+def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False, subsample=None, monotone=False):
     x, y = data(n)
     grid = ds.parameter_grid(max_depth=[4, 5], eta=[0.1, 0.3], beta=[1.0, 2.0, 5.0])
     folds = ds.fold_assignment(None, 5, 0, n)
@@ -67,13 +68,17 @@ def main(n=100000, rounds=100, batch_only=False, once=False, single_only=False, 
             times.append((time.perf_counter() - mark) * 1000.0)
         trainer.close()
         times = times[2:]
-        label = "".join(f" {name}={value}" for name, value in sampling.items())
+        label = "".join(f" {name}={value}" for name, value in sampling.items() if name != "monotone_constraints")
+        if "monotone_constraints" in sampling:
+            label += f" monotone_constraints={int(np.count_nonzero(sampling['monotone_constraints']))} columns"
         print(f"single     n={n}{label}: {statistics.median(times):.3f} ms per round ({min(times):.3f}-{max(times):.3f}), "
               f"x 60 = {statistics.median(times) * 60:.1f} ms", flush=True)
 
     single()
     if subsample is not None:
         single(subsample=subsample)
+    if monotone:
+        single(monotone_constraints=[1] * 17 + [0] * (x.shape[1] - 17))
     if single_only:
         return
     runs = {"batch": [], "sequential": []}
@@ -95,4 +100,5 @@ if __name__ == "__main__":
     arguments = [a for a in sys.argv[1:] if not a.startswith("--")]
     subsamples = [float(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--subsample=")]
     main(*(int(a) for a in arguments[:2]), batch_only="--batch-only" in sys.argv, once="--once" in sys.argv,
-         single_only="--single-only" in sys.argv, subsample=subsamples[0] if subsamples else None)
+         single_only="--single-only" in sys.argv, subsample=subsamples[0] if subsamples else None,
+         monotone="--monotone" in sys.argv)
