@@ -60,6 +60,12 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         margin never falls (+1) or never rises (-1) as that feature rises, enforced in the split choice on the device;
         RATIO_FEATURE_NAMES are the 17 similarity ratios, ForestModel.monotone_violations(c) counts the splits of any
         model that break c, validate_monotone_constraints(c, n_features, names) says what is accepted (this project's own)
+    ForestModel.permutation_importance(rows, target, n_repeats=5), permutation_importance_device(d_rows, n, d_target),
+        train_model(..., permutation_repeats=5)   -> how much the evaluation error fn + beta * fp grows when a feature's
+        column is shuffled (PermutationImportance: importance, importance_std, margin_shift, frame()); ForestModel.
+        partial_dependence(rows, "title_ratio"), partial_dependence_device(...)   -> the mean margin along one feature
+        (PartialDependence); both are one launch over a matrix staged once, integer sums, the same bits run after run;
+        validate_inspection(...) says what is accepted (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -72,7 +78,8 @@ from .feature_engineering import (  # noqa: F401
     get_truth_words_counts, levenshtein_ratio_batch, find_close_matches, exact_matches, ALLOWED_CHARACTERS, SPACE_CODE, SORT_KEY)
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
-from .forest import ForestModel, validate_cover  # noqa: F401
+from .forest import (ForestModel, PartialDependence, PermutationImportance, quantile_grid, validate_cover,  # noqa: F401
+                     validate_inspection)
 from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS,  # noqa: F401
                          LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS, EXPLAIN_COLUMNS, Candidates, Prediction,
                          assignment_frame, duplicate_frame, predictions_accuracy, top_contributions,

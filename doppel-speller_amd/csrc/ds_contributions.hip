@@ -427,6 +427,12 @@ int ds_forest_option(ds_forest *forest, const char *name, int64_t value)
         forest->max_blocks = value;
         return DS_OK;
     }
+    if (std::strcmp(name, "inspect_jobs_per_block") == 0) {
+        DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_forest_option: inspect_jobs_per_block = %lld out of range [0, %d]",
+                   (long long)value, INT32_MAX);
+        forest->inspect_jobs_per_block = value;
+        return DS_OK;
+    }
     ds::set_error("ds_forest_option: unknown option '%s'", name);
     return DS_E_ARG;
 }

@@ -64,6 +64,7 @@ struct ds_forest {
     int shape_checked = 0;                          // 0 not yet, 1 every tree is a proper binary tree
     std::vector<int32_t> parent;                    // global parent node of every node, -1 for a root or an unreachable node
     int64_t max_blocks = 0;                         // ds_forest_option("max_blocks"): 0 = the default of each stage
+    int64_t inspect_jobs_per_block = 0;             // ds_forest_option("inspect_jobs_per_block"): 0 = ds_inspect.hip's choice
     // what the contributions kernels read, derived from the cover when they are first asked for
     bool prepared = false;
     int64_t n_paths = 0;

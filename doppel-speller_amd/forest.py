@@ -60,6 +60,205 @@ def cover_from_counts(counts, arrays, prior=0.0):
     return cover
 
 
+# ---- model inspection ("Model inspection"; csrc/ds_inspect.hip) ----------------------------------
+INSPECT_BASELINE, INSPECT_PERMUTE, INSPECT_OVERRIDE = 0, 1, 2      # DS_INSPECT_*
+INSPECT_COUNTERS = 5                                                 # tp, tn, fp, fn, margin_sum
+INSPECT_JOB = np.dtype([("kind", np.int32), ("feature", np.int32), ("value", np.float32), ("repeat", np.uint32)])
+INSPECT_REPEATS_MAX = 1 << 16
+INSPECT_ROWS_MAX = 1 << 31
+MARGIN_QUANTUM = 1 << 20                                             # margin_sum counts units of 2^-20
+
+
+def _whole(name, value, low, high):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not low <= value < high:
+        raise ValueError(f"{name} must be an integer in [{low}, {high}), not {value!r}")
+    return int(value)
+
+
+def _open_unit(name, value):
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number in (0, 1), not {value!r}") from None
+    if not 0 < value < 1:           # refuses NaN too
+        raise ValueError(f"{name} must be a number in (0, 1), not {value!r}")
+    return value
+
+
+def feature_index(feature, n_features, names=None, what="feature"):
+    """A feature given as an index or, with `names`, as one of them -> its index in [0, n_features)."""
+    if isinstance(feature, str):
+        if names is None or feature not in names:
+            raise ValueError(f"{what} {feature!r} is not one of the feature names")
+        feature = list(names).index(feature)
+    return _whole(what, feature, 0, n_features)
+
+
+def validate_inspection(n_features, rows=None, n=None, target=None, n_repeats=1, seed=0, features=None, feature=None,
+                        grid=None, n_grid=32, threshold=0.9, beta=5.0, names=None):
+    """The checks of permutation_importance, partial_dependence and their device forms (no library needed) -> a dict
+    of the cleaned arguments.  rows: a host [n, n_features] matrix of numbers, or None with `n` for a matrix in HBM;
+    target: None or n labels of 0 / 1; features: None (all) or unique indices / names; feature: None, an index or a
+    name; grid: None or a non-empty 1-D array of numbers (NaN and the infinities are values like any other)."""
+    if rows is not None:
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != n_features:
+            raise ValueError(f"rows must be a [n, {n_features}] matrix, not shape {rows.shape}")
+        if not (np.issubdtype(rows.dtype, np.floating) or np.issubdtype(rows.dtype, np.integer)):
+            raise ValueError(f"rows must be numbers, not {rows.dtype}")
+        if n is not None and n != rows.shape[0]:
+            raise ValueError(f"n = {n!r} but rows has {rows.shape[0]} rows")
+        rows, n = np.ascontiguousarray(rows, dtype=np.float32), rows.shape[0]
+    n = _whole("n", n, 1, INSPECT_ROWS_MAX + 1)
+    if target is not None:
+        target = np.asarray(target)
+        if target.ndim != 1 or target.shape[0] != n:
+            raise ValueError(f"target must hold {n} labels, not shape {target.shape}")
+        if target.dtype == object or not np.isin(target, (0, 1)).all():
+            raise ValueError("target labels must all be 0 or 1")
+        target = np.ascontiguousarray(target, dtype=np.float32)
+    n_repeats = _whole("n_repeats", n_repeats, 1, INSPECT_REPEATS_MAX)
+    seed = _whole("seed", seed, 0, 1 << 63)
+    n_grid = _whole("n_grid", n_grid, 1, INSPECT_REPEATS_MAX)
+    if features is None:
+        features = np.arange(n_features, dtype=np.int32)
+    else:
+        if isinstance(features, (str, bytes)) or not hasattr(features, "__len__"):
+            raise ValueError(f"features must be a sequence of indices or names, not {features!r}")
+        features = np.array([feature_index(f, n_features, names, "features") for f in features], dtype=np.int32)
+        if features.shape[0] == 0:
+            raise ValueError("features must not be empty")
+        if np.unique(features).shape[0] != features.shape[0]:
+            raise ValueError("features must be unique")
+    if feature is not None:
+        feature = feature_index(feature, n_features, names)
+    if grid is not None:
+        try:
+            grid = np.asarray(grid, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("grid must be an array of numbers") from None
+        if grid.ndim != 1 or grid.shape[0] == 0:
+            raise ValueError(f"grid must be 1-D and non-empty, not shape {grid.shape}")
+        grid = np.ascontiguousarray(grid)
+    threshold = _open_unit("threshold", threshold)
+    try:
+        beta = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"beta must be a positive number, not {beta!r}") from None
+    if not (np.isfinite(beta) and beta > 0):
+        raise ValueError(f"beta must be a finite positive number, not {beta!r}")
+    return dict(rows=rows, n=n, target=target, n_repeats=n_repeats, seed=seed, features=features, feature=feature,
+                grid=grid, n_grid=n_grid, threshold=threshold, beta=beta)
+
+
+def inspection_jobs(jobs):
+    """(kind, feature, value, repeat) tuples -> the job table of ds_forest_inspect (INSPECT_JOB records)."""
+    table = np.zeros(len(jobs), dtype=INSPECT_JOB)
+    for at, (kind, feature, value, repeat) in enumerate(jobs):
+        table[at] = (kind, feature, value, repeat)
+    return table
+
+
+def permutation_jobs(features, n_repeats):
+    """One baseline job, then for every feature of `features` its n_repeats permute jobs."""
+    table = np.zeros(1 + len(features) * n_repeats, dtype=INSPECT_JOB)
+    table["kind"][1:] = INSPECT_PERMUTE
+    table["feature"][1:] = np.repeat(np.asarray(features, dtype=np.int32), n_repeats)
+    table["repeat"][1:] = np.tile(np.arange(n_repeats, dtype=np.uint32), len(features))
+    return table
+
+
+def dependence_jobs(feature, grid):
+    """One baseline job, then one override job per grid value."""
+    table = np.zeros(1 + grid.shape[0], dtype=INSPECT_JOB)
+    table["kind"][1:] = INSPECT_OVERRIDE
+    table["feature"][1:] = feature
+    table["value"][1:] = grid
+    return table
+
+
+def quantile_grid(column, n_grid):
+    """partial_dependence's default grid, float32: the distinct values among the n_grid evenly spaced order statistics
+    v[(k * (m - 1)) // max(n_grid - 1, 1)], k = 0 .. n_grid - 1, of the column's m sorted non-NaN values, ascending, and
+    one NaN last when the column has any."""
+    column = np.asarray(column, dtype=np.float32)
+    missing = np.isnan(column)
+    values = np.sort(column[~missing])
+    grid = np.zeros(0, np.float32)
+    if values.shape[0]:
+        at = (np.arange(n_grid, dtype=np.int64) * (values.shape[0] - 1)) // max(n_grid - 1, 1)
+        grid = np.unique(values[at])
+    if missing.any():
+        grid = np.concatenate([grid, np.array([np.nan], np.float32)])
+    return grid.astype(np.float32)
+
+
+def _margin_sums(counters):
+    return counters[:, 4].astype(np.uint64).view(np.int64)
+
+
+class PermutationImportance:
+    """What ForestModel.permutation_importance returns, derived on the host in float64 from the integers of one launch
+    (`counters`: uint64[1 + n_selected * n_repeats, 5], the baseline job first):
+    baseline (tp, tn, fp, fn) and baseline_error = fn + beta * fp of the unchanged matrix; error_matrix
+    int64[n_selected, n_repeats, 4] and errors float64[n_selected, n_repeats] with feature features[s] shuffled;
+    importance = the mean over the repeats of errors - baseline_error, importance_std its population standard
+    deviation; margin_shift = the mean over the repeats of the change of the mean margin."""
+
+    def __init__(self, counters, n, features, n_repeats, seed, threshold=0.9, beta=5.0):
+        counters = np.asarray(counters, dtype=np.uint64)
+        self.counters, self.n = counters, int(n)
+        self.features, self.n_repeats, self.seed = np.asarray(features, dtype=np.int32), int(n_repeats), int(seed)
+        self.threshold, self.beta = float(threshold), float(beta)
+        selected = self.features.shape[0]
+        self.baseline = tuple(int(v) for v in counters[0, :4])
+        self.baseline_error = self.baseline[3] + self.beta * self.baseline[2]
+        self.error_matrix = counters[1:, :4].astype(np.int64).reshape(selected, self.n_repeats, 4)
+        self.errors = self.error_matrix[:, :, 3].astype(np.float64) + \
+            self.beta * self.error_matrix[:, :, 2].astype(np.float64)
+        increase = self.errors - self.baseline_error
+        self.importance = increase.mean(axis=1)
+        self.importance_std = increase.std(axis=1)
+        sums = _margin_sums(counters)
+        shift = (sums[1:] - sums[0]).astype(np.float64).reshape(selected, self.n_repeats) / MARGIN_QUANTUM / self.n
+        self.baseline_mean_margin = float(sums[0]) / MARGIN_QUANTUM / self.n
+        self.margin_shift = shift.mean(axis=1)
+
+    def order(self):
+        """The positions of `features` by importance, descending, ties to the lower feature."""
+        return np.lexsort((self.features, -self.importance))
+
+    def frame(self, names=None):
+        """A DataFrame (feature, name, importance, importance_std, margin_shift) sorted by importance, descending, ties
+        to the lower feature.  names: FEATURE_NAMES by default; a feature beyond them is called f<index>."""
+        import pandas as pd
+        if names is None:
+            from .feature_engineering import FEATURE_NAMES as names
+        order = self.order()
+        features = self.features[order]
+        return pd.DataFrame({"feature": features,
+                             "name": [names[f] if f < len(names) else f"f{f}" for f in features],
+                             "importance": self.importance[order], "importance_std": self.importance_std[order],
+                             "margin_shift": self.margin_shift[order]})
+
+
+class PartialDependence:
+    """What ForestModel.partial_dependence returns (`counters`: uint64[1 + len(grid), 5], the baseline job first):
+    `grid` float32; mean_margin float64[len(grid)] = margin_sum / 2^20 / n with the feature set to the grid value in
+    every row; positive_share = the share of rows above the threshold then; baseline_mean_margin of the unchanged
+    matrix; error_matrix int64[len(grid), 4] (with a target; all rows count as label 0 without one)."""
+
+    def __init__(self, counters, n, feature, grid, threshold=0.9):
+        counters = np.asarray(counters, dtype=np.uint64)
+        self.counters, self.n, self.feature = counters, int(n), int(feature)
+        self.grid, self.threshold = np.asarray(grid, dtype=np.float32), float(threshold)
+        sums = _margin_sums(counters)
+        self.baseline_mean_margin = float(sums[0]) / MARGIN_QUANTUM / self.n
+        self.mean_margin = sums[1:].astype(np.float64) / MARGIN_QUANTUM / self.n
+        self.error_matrix = counters[1:, :4].astype(np.int64)
+        self.positive_share = (self.error_matrix[:, 0] + self.error_matrix[:, 2]).astype(np.float64) / self.n
+
+
 class ForestModel:
     def __init__(self, feature, threshold, yes, no, missing, tree_offsets, n_features, base_margin=0.0, device=0):
         self.arrays = dict(feature=np.ascontiguousarray(feature, dtype=np.int32),
@@ -344,7 +543,8 @@ class ForestModel:
         return out
 
     def option(self, name, value):
-        """ds_forest_option, for tests: option("max_blocks", v) caps the grids of the cover and contributions kernels."""
+        """ds_forest_option, for tests: option("max_blocks", v) caps the grids of the cover, contributions and inspection
+        kernels; option("inspect_jobs_per_block", v) sets the jobs an inspection workgroup runs per staged row block."""
         _lib.check(_lib.lib().ds_forest_option(self.handle, name.encode(), int(value)), "ds_forest_option")
 
     def predict_contributions(self, rows, approximate=False):
@@ -365,6 +565,92 @@ class ForestModel:
         _lib.check(_lib.lib().ds_forest_contributions_device(self.handle, _lib.pointer(d_rows), int(n),
                                                              _lib.pointer(d_out), int(bool(approximate)),
                                                              _lib.pointer(stream)), "ds_forest_contributions_device")
+
+    def inspect(self, rows, target, jobs, seed=0, threshold=0.9):
+        """uint64[n_jobs, 5] (tp, tn, fp, fn, margin_sum in two's complement) of a job table (INSPECT_JOB records,
+        inspection_jobs) over a host float32[n, n_features] matrix: ds_forest_inspect, one launch.  target: float32[n]
+        or None (every label 0)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        assert rows.ndim == 2 and rows.shape[1] == self.n_features
+        jobs = np.ascontiguousarray(jobs, dtype=INSPECT_JOB)
+        if target is not None:
+            target = np.ascontiguousarray(target, dtype=np.float32)
+            assert target.shape == (rows.shape[0],)
+        out = np.zeros((jobs.shape[0], INSPECT_COUNTERS), dtype=np.uint64)
+        _lib.check(_lib.lib().ds_forest_inspect(self.handle, _lib.pointer(rows), rows.shape[0], _lib.pointer(target),
+                                                _lib.pointer(jobs), jobs.shape[0], int(seed), float(threshold),
+                                                _lib.pointer(out)), "ds_forest_inspect")
+        return out
+
+    def inspect_device(self, d_rows, n, d_target, jobs, seed=0, threshold=0.9, stream=None):
+        """inspect for the first n rows of a float32 matrix in HBM and a float32[n] target in HBM (or None): the job
+        table is uploaded, the counters come back behind a synchronisation of `stream`."""
+        jobs = np.ascontiguousarray(jobs, dtype=INSPECT_JOB)
+        out = np.zeros((jobs.shape[0], INSPECT_COUNTERS), dtype=np.uint64)
+        if jobs.shape[0] == 0:
+            return out
+        d_jobs = _lib.DeviceArray.from_host(jobs.view(np.uint8), self.device)
+        d_out = _lib.DeviceArray(out.shape, np.uint64, self.device)
+        try:
+            _lib.check(_lib.lib().ds_forest_inspect_device(self.handle, _lib.pointer(d_rows), int(n),
+                                                           _lib.pointer(d_target), d_jobs.ptr, jobs.shape[0], int(seed),
+                                                           float(threshold), d_out.ptr, _lib.pointer(stream)),
+                       "ds_forest_inspect_device")
+            _lib.check(_lib.lib().ds_stream_sync(_lib.pointer(stream), self.device), "ds_stream_sync")
+            return d_out.to_host()
+        finally:
+            d_jobs.free()
+            d_out.free()
+
+    def permutation_importance(self, rows, target, n_repeats=5, seed=0, features=None, threshold=0.9, beta=5.0):
+        """How much the evaluation error fn + beta * fp at `threshold` grows when a feature's column is shuffled among
+        the rows (a closed-form permutation of (seed, feature, repeat, n): DESIGN.md section 8, "Model inspection"),
+        for every feature of `features` (indices or FEATURE_NAMES; None: all) and n_repeats shuffles each ->
+        PermutationImportance.  One launch of 1 + n_selected * n_repeats jobs over the matrix, uploaded once; integer
+        counts, so the same result run after run.  validate_inspection says what is accepted."""
+        from .feature_engineering import FEATURE_NAMES
+        v = validate_inspection(self.n_features, rows=rows, target=target, n_repeats=n_repeats, seed=seed,
+                                features=features, threshold=threshold, beta=beta, names=FEATURE_NAMES)
+        counters = self.inspect(v["rows"], v["target"], permutation_jobs(v["features"], v["n_repeats"]), v["seed"],
+                                v["threshold"])
+        return PermutationImportance(counters, v["n"], v["features"], v["n_repeats"], v["seed"], v["threshold"],
+                                     v["beta"])
+
+    def permutation_importance_device(self, d_rows, n, d_target, n_repeats=5, seed=0, features=None, threshold=0.9,
+                                      beta=5.0, stream=None):
+        """permutation_importance for the first n rows of a matrix that lies in HBM (train_model's evaluation matrix,
+        DeviceDataSets) with its float32[n] target in HBM, or None for no labels."""
+        from .feature_engineering import FEATURE_NAMES
+        v = validate_inspection(self.n_features, n=n, n_repeats=n_repeats, seed=seed, features=features,
+                                threshold=threshold, beta=beta, names=FEATURE_NAMES)
+        counters = self.inspect_device(d_rows, v["n"], d_target, permutation_jobs(v["features"], v["n_repeats"]),
+                                       v["seed"], v["threshold"], stream)
+        return PermutationImportance(counters, v["n"], v["features"], v["n_repeats"], v["seed"], v["threshold"],
+                                     v["beta"])
+
+    def partial_dependence(self, rows, feature, grid=None, n_grid=32, target=None, threshold=0.9):
+        """The mean margin of the rows with `feature` (an index or one of FEATURE_NAMES) set to each value of `grid` in
+        every row -> PartialDependence.  grid=None: quantile_grid(rows[:, feature], n_grid), taken on the host.  One
+        launch of 1 + len(grid) jobs."""
+        from .feature_engineering import FEATURE_NAMES
+        v = validate_inspection(self.n_features, rows=rows, target=target, feature=0 if feature is None else feature,
+                                grid=grid, n_grid=n_grid, threshold=threshold, names=FEATURE_NAMES)
+        if feature is None:
+            raise ValueError("feature must be an index or a name, not None")
+        grid = quantile_grid(v["rows"][:, v["feature"]], v["n_grid"]) if v["grid"] is None else v["grid"]
+        counters = self.inspect(v["rows"], v["target"], dependence_jobs(v["feature"], grid), 0, v["threshold"])
+        return PartialDependence(counters, v["n"], v["feature"], grid, v["threshold"])
+
+    def partial_dependence_device(self, d_rows, n, feature, grid, d_target=None, threshold=0.9, stream=None):
+        """partial_dependence for the first n rows of a matrix in HBM; the grid must be given."""
+        from .feature_engineering import FEATURE_NAMES
+        if grid is None or feature is None:
+            raise ValueError("grid and feature must be given for a matrix in HBM")
+        v = validate_inspection(self.n_features, n=n, feature=feature, grid=grid, threshold=threshold,
+                                names=FEATURE_NAMES)
+        counters = self.inspect_device(d_rows, v["n"], d_target, dependence_jobs(v["feature"], v["grid"]), 0,
+                                       v["threshold"], stream)
+        return PartialDependence(counters, v["n"], v["feature"], v["grid"], v["threshold"])
 
     def feature_importance(self):
         """float64[n_features]: the number of splits on each feature over the sum of them (train.py

@@ -762,19 +762,22 @@ class TrainModelResult:
     eval_metrics were requested, `metrics_history` (ForestTrainer.metrics_history; None otherwise).  With init_model:
     `initial_error`, the evaluation error of the init model (None otherwise and without an evaluation set); `model`,
     `feature_importance` and a counted cover are those of the WHOLE forest, `history` that of the new rounds and
-    `best_iteration` counts all trees (ForestTrainer)."""
+    `best_iteration` counts all trees (ForestTrainer).  With permutation_repeats > 0: `permutation_importance`, the
+    model's PermutationImportance on the evaluation set (None otherwise)."""
 
     def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings,
-                 metrics_history=None, initial_error=None):
+                 metrics_history=None, initial_error=None, permutation_importance=None):
         self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
         self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
         self.metrics_history = metrics_history
         self.initial_error = initial_error
+        self.permutation_importance = permutation_importance
 
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
-                kind_weights=None, monotone_constraints=None, **fit_parameters):
+                kind_weights=None, monotone_constraints=None, permutation_repeats=0, permutation_seed=0,
+                **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -792,7 +795,10 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     left out: 1.0; training_set.kind_weights), handed to fit_device as sample_weight.  The weights enter the objective
     alone (ForestTrainer): the evaluation error, error_matrix and a counted cover stay counts over rows.
     monotone_constraints: ForestTrainer's, as FEATURES_COUNT signs or as a dict by FEATURE_NAMES
-    (feature_engineering.ratio_constraints() constrains the 17 similarity ratios upwards), handed to fit_device."""
+    (feature_engineering.ratio_constraints() constrains the 17 similarity ratios upwards), handed to fit_device.
+    permutation_repeats: 0, or the n_repeats of ForestModel.permutation_importance_device, run on the evaluation
+    matrix where it lies in HBM after the error matrix, with seed permutation_seed and the fit's beta: the result's
+    `permutation_importance`, timed as `timings["permutation"]`.  It needs an evaluation set."""
     from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
@@ -806,11 +812,18 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         validate_kind_weights(kind_weights)
     if monotone_constraints is not None:
         monotone_constraints = validate_monotone_constraints(monotone_constraints, FEATURES_COUNT, FEATURE_NAMES)
+    permutation_repeats = _positive_int("permutation_repeats", permutation_repeats, 0, (1 << 16) - 1)
+    permutation_seed = _positive_int("permutation_seed", permutation_seed, 0, (1 << 63) - 1)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=evaluation_fractions, build_index=build_index)
+    if permutation_repeats and not any(fe.evaluation_fractions.values()):
+        raise ValueError("permutation_repeats needs an evaluation set, and every evaluation fraction is 0")
     sets = fe.generate_device_data_sets()
     timings = dict(fe.timings)
+    if permutation_repeats and sets.n_evaluation == 0:
+        sets.free()
+        raise ValueError("permutation_repeats needs an evaluation set, and no row was drawn into it")
     trainer = ForestTrainer(device)
     mark = time.perf_counter()
     has_eval = sets.n_evaluation > 0
@@ -835,6 +848,17 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
                                      PREDICTION_PROBABILITY_THRESHOLD)
         d_probabilities.free()
     timings["evaluate"] = (time.perf_counter() - mark) * 1000.0
+    permutation_importance = None
+    if permutation_repeats:
+        mark = time.perf_counter()
+        d_target = _lib.DeviceArray.from_host(np.ascontiguousarray(sets.evaluation_target, dtype=np.float32), device)
+        try:
+            permutation_importance = model.permutation_importance_device(
+                sets.evaluation, sets.n_evaluation, d_target, n_repeats=permutation_repeats, seed=permutation_seed,
+                beta=validate_parameters(**fit_parameters)["beta"])
+        finally:
+            d_target.free()
+        timings["permutation"] = (time.perf_counter() - mark) * 1000.0
     if cover:
         mark = time.perf_counter()
         try:
@@ -851,4 +875,5 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     sets.free()
     timings["total"] = (time.perf_counter() - started) * 1000.0
     return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings,
-                            metrics_history=metrics_history, initial_error=initial_error)
+                            metrics_history=metrics_history, initial_error=initial_error,
+                            permutation_importance=permutation_importance)

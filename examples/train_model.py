@@ -13,6 +13,7 @@ top-k pairs of the train queries labelled with their known source row) and the r
 
     python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH]
                                    [--kind-weights generated=0.5,positive=2] [--monotone ratios]
+                                   [--permutation-repeats N]
                                    [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
@@ -30,6 +31,9 @@ fe.rows, ...)) without.  The evaluation error stays a count over rows.
 --monotone ratios constrains the 17 similarity ratios upwards (ds.ratio_constraints()): the match probability never
 falls when a ratio rises; --monotone title_ratio=1,word_1_best_ratio=1 names columns of ds.FEATURE_NAMES and their
 signs.  The number of splits that break the constraints is printed for the model (0 under them).
+--permutation-repeats N prints the ten features whose shuffling on the evaluation set raises the custom error most
+(ForestModel.permutation_importance, N shuffles per feature on the device; with --one-call from the evaluation matrix
+where it lies in HBM: ds.train_model(..., permutation_repeats=N)), next to their rank by split count.
 """
 import os
 import sys
@@ -75,8 +79,19 @@ def monotone_argument(text):
     return {name: int(sign) for name, sign in (pair.split("=") for pair in text.split(","))}
 
 
+def print_importance(importance, split_shares, count=10):
+    """The `count` most important features by permutation, with their rank by split count."""
+    split_rank = {int(f): rank for rank, f in enumerate(np.argsort(-split_shares, kind="stable"), 1)}
+    tp, tn, fp, fn = importance.baseline
+    print(f"permutation importance over {importance.n} evaluation rows, {importance.n_repeats} shuffles per feature "
+          f"(baseline custom error {importance.baseline_error:g} = FN {fn} + {importance.beta:g} x FP {fp}):")
+    for _, row in importance.frame().head(count).iterrows():
+        print(f"  {row['name']:<24} error +{row['importance']:8.1f} (std {row['importance_std']:6.1f})   mean margin "
+              f"{row['margin_shift']:+.4f}   split-count rank {split_rank[int(row['feature'])]}")
+
+
 def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None,
-         kind_weights=None, monotone=None):
+         kind_weights=None, monotone=None, permutation_repeats=0):
     init = ds.ForestModel.load(init_model) if init_model else None
     init_trees = init.n_trees if init else 0
     if init:
@@ -94,7 +109,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
     if one_call:
         t0 = time.perf_counter()
         result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics),
-                                init_model=init, kind_weights=kind_weights, monotone_constraints=monotone)
+                                init_model=init, kind_weights=kind_weights, monotone_constraints=monotone,
+                                permutation_repeats=permutation_repeats)
         t1 = time.perf_counter()
         model = result.model
         if metrics:
@@ -109,6 +125,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
         top = np.argsort(-result.feature_importance)[:5]
         print("most used features:", ", ".join(f"f{f} {result.feature_importance[f]:.3f}" for f in top))
+        if permutation_repeats:
+            print_importance(result.permutation_importance, result.feature_importance)
     else:
         fe = ds.FeatureEngineering(truth_titles, train.title_id, train_titles, train_ids)
         features, labels, eval_features, eval_labels = fe.generate_train_and_evaluation_data_sets()
@@ -132,6 +150,9 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         print(f"evaluation rows: TP {tp}  TN {tn}  FP {fp}  FN {fn}")
         top = np.argsort(-model.feature_importance())[:5]
         print("most used features:", ", ".join(f"f{f} {model.feature_importance()[f]:.3f}" for f in top))
+        if permutation_repeats:
+            print_importance(model.permutation_importance(eval_features, eval_labels, n_repeats=permutation_repeats),
+                             model.feature_importance())
 
     if constraints is not None:
         print(f"monotone constraints on {int(np.count_nonzero(constraints))} features: "
@@ -182,5 +203,12 @@ if __name__ == "__main__":
             raise SystemExit("--monotone needs `ratios` or NAME=SIGN,... over ds.FEATURE_NAMES")
         monotone = monotone_argument(arguments[at + 1])
         del arguments[at:at + 2]
+    repeats = 0
+    if "--permutation-repeats" in arguments:
+        at = arguments.index("--permutation-repeats")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--permutation-repeats needs the number of shuffles per feature")
+        repeats = int(arguments[at + 1])
+        del arguments[at:at + 2]
     main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted,
-         init_model=init_path, kind_weights=kinds, monotone=monotone)
+         init_model=init_path, kind_weights=kinds, monotone=monotone, permutation_repeats=repeats)

@@ -521,6 +521,46 @@ int ds_forest_option(ds_forest *forest, const char *name, int64_t value);
 int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64_t n, double *d_out, int approximate,
                                    void *stream);
 int ds_forest_contributions(ds_forest *forest, const float *rows, int64_t n, double *out, int approximate);
+
+/* ---- model inspection: permutation importance and partial dependence ("Model inspection") --------
+ * A JOB changes one value of every row i of a float32[n, n_features] matrix before the forest is walked:
+ *   DS_INSPECT_BASELINE  nothing (feature, value and repeat are ignored);
+ *   DS_INSPECT_PERMUTE   row[feature] = rows[perm(i)][feature];
+ *   DS_INSPECT_OVERRIDE  row[feature] = value, any float32 (a NaN takes the `missing` branches).
+ * The margin of the changed row is base_margin + the float32 leaf sum of ds_forest_predict_device, unchanged.  Per job
+ * DS_INSPECT_COUNTERS unsigned 64-bit integers are summed over the rows: tp, tn, fp, fn with
+ * p = 1.0f / (1.0f + expf(-margin)), predicted positive iff (double)p > threshold, actual positive iff target[i] != 0
+ * (a null target: every label 0), and margin_sum = the sum of llrint(clamp((double)margin, -2^11, 2^11) * 2^20) in
+ * two's complement.  A NaN margin adds 0 to margin_sum and is not positive.  Integer sums: the same bits for any grid,
+ * any split of the jobs over the workgroups and any order of the jobs.
+ * perm is a function of (seed, feature, repeat, n, i) alone.  n == 1: perm(0) = 0.  Otherwise
+ * b = max(1, ceil(bit_length(n - 1) / 2)), mask = 2^b - 1, k_j = the first kept output of the stream ("Randomness" below)
+ * of (seed, purpose DS_INSPECT_PURPOSE_PERMUTE, index (repeat << 40) | (feature << 32) | j), j = 0..3, and from x = i:
+ *   { L = x >> b; R = x & mask; for j in 0..3: (L, R) = (R, L ^ (mix64(k_j ^ R) & mask)); x = (L << b) | R } until x < n,
+ * mix64 the splitmix64 finaliser: a 4-round Feistel network over [0, 2^(2b)), 2^(2b) < 4n, walked back into [0, n).
+ * ds_forest_inspect_device: matrix, target (nullable), job table and d_out ([n_jobs][DS_INSPECT_COUNTERS], zeroed by the
+ * call) lie in HBM.  The job table is read back and checked first, which synchronises `stream`; the rest is enqueued on
+ * it.  ds_forest_inspect: the same for host arrays.  DS_E_ARG before any tree is walked: a null pointer, n_jobs < 0,
+ * n outside [0, 2^31], threshold outside (0, 1), an unknown kind, and for a job that is no baseline a feature outside
+ * [0, n_features) or (PERMUTE) a repeat of 2^16 or more.  n == 0 or n_jobs == 0 is DS_OK, the counters zeroed.
+ * The grid is row blocks x job groups: "max_blocks" of the forest's options caps the first, "inspect_jobs_per_block"
+ * (for tests; 0 = the launcher's choice) sets the jobs a workgroup runs per staged row block; no result depends on either. */
+#define DS_INSPECT_BASELINE 0
+#define DS_INSPECT_PERMUTE 1
+#define DS_INSPECT_OVERRIDE 2
+#define DS_INSPECT_COUNTERS 5
+#define DS_INSPECT_PURPOSE_PERMUTE 6
+typedef struct ds_inspect_job {
+    int32_t kind;
+    int32_t feature;
+    float value;
+    uint32_t repeat;
+} ds_inspect_job;
+int ds_forest_inspect_device(ds_forest *forest, const float *d_rows, int64_t n, const float *d_target,
+                             const ds_inspect_job *d_jobs, int32_t n_jobs, uint64_t seed, double threshold,
+                             unsigned long long *d_out, void *stream);
+int ds_forest_inspect(ds_forest *forest, const float *rows, int64_t n, const float *target, const ds_inspect_job *jobs,
+                      int32_t n_jobs, uint64_t seed, double threshold, unsigned long long *out);
 /* Per query of k consecutive candidates the one with the highest probability, the first on a tie (predict.py:239-242; a
  * NaN never replaces an earlier candidate, and a NaN in slot 0 is never replaced itself: it stays the best, with count
  * 1, whatever follows): d_best_pair[q] = q * k + its slot (an index for ds_gather_rows_device),
