@@ -66,6 +66,13 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         partial_dependence(rows, "title_ratio"), partial_dependence_device(...)   -> the mean margin along one feature
         (PartialDependence); both are one launch over a matrix staged once, integer sums, the same bits run after run;
         validate_inspection(...) says what is accepted (this project's own)
+    ForestModel.refresh(features, target, eval_features, eval_target, eta=, reg_lambda=, beta=, sample_weight=),
+        refresh_device(d_rows, n, target, ...), refresh_model(truth_titles, truth_title_ids, train_titles,
+        train_title_ids, model)   -> keep every split of a trained model and re-estimate its leaves on new rows, tree by
+        tree on the device (xgboost's updater="refresh"): RefreshResult with the new model, the exact gradient and
+        hessian sums per node, cover, the gain of every split on that data, gain_importance() and the evaluation error
+        per tree prefix; a model refreshed on its own training data comes back bit for bit; validate_refresh(...) says
+        what is accepted (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -78,8 +85,8 @@ from .feature_engineering import (  # noqa: F401
     get_truth_words_counts, levenshtein_ratio_batch, find_close_matches, exact_matches, ALLOWED_CHARACTERS, SPACE_CODE, SORT_KEY)
 from .match_maker import MatchMaker, NativeProblem, TruthIndex  # noqa: F401
 from .pipeline import CandidatePipeline  # noqa: F401
-from .forest import (ForestModel, PartialDependence, PermutationImportance, quantile_grid, validate_cover,  # noqa: F401
-                     validate_inspection)
+from .forest import (ForestModel, PartialDependence, PermutationImportance, RefreshResult, quantile_grid,  # noqa: F401
+                     split_gains, validate_cover, validate_inspection, validate_refresh)
 from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMNS, EXHAUSTIVE_COLUMNS,  # noqa: F401
                          LINK_COLUMNS, RANKED_COLUMNS, SWEEP_COLUMNS, EXPLAIN_COLUMNS, Candidates, Prediction,
                          assignment_frame, duplicate_frame, predictions_accuracy, top_contributions,
@@ -87,8 +94,8 @@ from .prediction import (ASSIGNMENT_COLUMNS, ASSIGNMENT_COUNTS, DUPLICATE_COLUMN
 from .training_set import (DeviceDataSets, DeviceHardNegatives, FeatureEngineering, generate_misspelled_names,  # noqa: F401
                            kind_weights, validate_hard)
 from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, compute_cuts_device,  # noqa: F401
-                    evaluation_error_matrix, roc_auc, train_model, validate_init_model, validate_monotone_constraints,
-                    validate_sample_weight)
+                    evaluation_error_matrix, refresh_model, roc_auc, train_model, validate_init_model,
+                    validate_monotone_constraints, validate_sample_weight)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
 from .text import transform_title, transform_titles  # noqa: F401

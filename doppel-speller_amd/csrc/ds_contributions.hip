@@ -253,12 +253,11 @@ __global__ void ds_best_pairs_kernel(const int32_t *rows, const float *probabili
 }
 
 // Every tree a proper binary tree (two different children, `missing` one of them, one parent per node): what cover
-// sums and path decomposition rest on.  Fills forest->parent.
-static int check_shape(ds_forest *forest, const char *what)
+// sums and path decomposition rest on (declared in ds_forest.h).  check_shape keeps the answer in forest->parent.
+int forest_parents(const ds_forest *forest, const char *what, std::vector<int32_t> &parent)
 {
-    if (forest->shape_checked) return DS_OK;
     DS_REQUIRE(forest->n_nodes <= INT32_MAX, "%s: %lld nodes", what, (long long)forest->n_nodes);
-    std::vector<int32_t> parent(static_cast<size_t>(forest->n_nodes), -1);
+    parent.assign(static_cast<size_t>(forest->n_nodes), -1);
     for (int32_t t = 0; t < forest->n_trees; ++t) {
         const int64_t begin = forest->h_offsets[t], end = forest->h_offsets[t + 1];
         for (int64_t i = begin; i < end; ++i) {
@@ -275,6 +274,15 @@ static int check_shape(ds_forest *forest, const char *what)
         }
         DS_REQUIRE(parent[static_cast<size_t>(begin)] < 0, "%s: the root of tree %d is somebody's child", what, t);
     }
+    return DS_OK;
+}
+
+static int check_shape(ds_forest *forest, const char *what)
+{
+    if (forest->shape_checked) return DS_OK;
+    std::vector<int32_t> parent;
+    const int status = forest_parents(forest, what, parent);
+    if (status != DS_OK) return status;
     forest->parent = std::move(parent);
     forest->shape_checked = 1;
     return DS_OK;
@@ -431,6 +439,13 @@ int ds_forest_option(ds_forest *forest, const char *name, int64_t value)
         DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_forest_option: inspect_jobs_per_block = %lld out of range [0, %d]",
                    (long long)value, INT32_MAX);
         forest->inspect_jobs_per_block = value;
+        return DS_OK;
+    }
+    if (std::strcmp(name, "refresh_lds_nodes") == 0) {
+        DS_REQUIRE(value >= 0 && value <= ds::kRefreshLdsNodesMax,
+                   "ds_forest_option: refresh_lds_nodes = %lld out of range [0, %d]", (long long)value,
+                   ds::kRefreshLdsNodesMax);
+        forest->refresh_lds_nodes = value;
         return DS_OK;
     }
     ds::set_error("ds_forest_option: unknown option '%s'", name);

@@ -179,6 +179,27 @@ int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *f
                        int64_t n, float *leafsum, int32_t n_models, int64_t stride, DeviceBuffer<float> &staged);
 
 // ---- gradients of weighted_log_loss at the current margins ---------------------------------------------------------
+// One row's quantized (g, h) at its float32 probability p: the one statement of this arithmetic, for the trainers'
+// gradient kernel below and for the refresh of a finished model (ds_refresh.hip).  weights: null, every row weighs 1.
+__device__ inline void train_row_gradient(float p, float label, const float *weights, int64_t r, double beta,
+                                          long long *qg, long long *qh)
+{
+    const double y = label, pd = p;
+    const double w = beta + y - beta * y;
+    const double s = weights != nullptr ? weights[r] : 1.0;
+    const double g = (pd * w - y) * s;
+    const double h = (pd * (1.0 - pd) * w) * s;
+    *qg = static_cast<long long>(rint(g * kQuantum));
+    *qh = static_cast<long long>(rint(h * kQuantum));
+}
+
+// The value of a leaf with the quantized sums (qg, qh), unbounded: train_split_nodes' and the refresh's
+__device__ inline float train_leaf_value(long long qg, long long qh, double lambda, double eta)
+{
+    const double g = static_cast<double>(qg) / kQuantum, h = static_cast<double>(qh) / kQuantum;
+    return static_cast<float>((-g / (h + lambda)) * eta);
+}
+
 // kFolds: a row with fold[r] == held_out does not train: its (g, h) is (0, 0); everything else is written as for any row
 // kSampled: with subsample < 1 a training row is drawn for this tree (sample_row) and an undrawn one is treated like a
 // held-out row.  The draw is indexed by the row's number among the model's TRAINING rows: r itself without folds, else
@@ -195,11 +216,8 @@ __device__ inline void train_gradient_rows(const float *leafsum, const float *la
          r += static_cast<int64_t>(gridDim.x) * kRowThreads) {
         const float margin = base_margin + leafsum[r];
         const float p = 1.0f / (1.0f + expf(-margin));   // ds_forest.hip's rule
-        const double y = labels[r], pd = p;
-        const double w = beta + y - beta * y;
-        const double s = weights != nullptr ? weights[r] : 1.0;
-        const double g = (pd * w - y) * s;
-        const double h = (pd * (1.0 - pd) * w) * s;
+        long long qg, qh;
+        train_row_gradient(p, labels[r], weights, r, beta, &qg, &qh);
         bool trains = !kFolds || static_cast<int32_t>(fold[r]) != held_out;
         if (kSampled && sampling->subsample < 1.0) {   // the same answer in every row of a model
             int64_t row = r;
@@ -210,8 +228,8 @@ __device__ inline void train_gradient_rows(const float *leafsum, const float *la
             trains = trains && sample_row(*sampling, tree, row);
         }
         probabilities[r] = p;
-        gh[2 * r] = trains ? static_cast<long long>(rint(g * kQuantum)) : 0ll;
-        gh[2 * r + 1] = trains ? static_cast<long long>(rint(h * kQuantum)) : 0ll;
+        gh[2 * r] = trains ? qg : 0ll;
+        gh[2 * r + 1] = trains ? qh : 0ll;
         node_of[r] = 0;
     }
 }
@@ -442,7 +460,7 @@ __device__ inline void train_split_nodes(const Candidate *candidates, Node *node
     auto leaf_value = [&](long long qg, long long qh, double lo = 0.0, double hi = 0.0) {
         const double g = static_cast<double>(qg) / kQuantum, h = static_cast<double>(qh) / kQuantum;
         if (kMonotone) return static_cast<float>(bounded_term(g, h, lambda, lo, hi).weight * params.eta);
-        return static_cast<float>((-g / (h + lambda)) * params.eta);
+        return train_leaf_value(qg, qh, lambda, params.eta);
     };
     double lo = 0.0, hi = 0.0;
     if (kMonotone) {

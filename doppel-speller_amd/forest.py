@@ -259,6 +259,110 @@ class PartialDependence:
         self.positive_share = (self.error_matrix[:, 0] + self.error_matrix[:, 2]).astype(np.float64) / self.n
 
 
+# ---- refreshing a model ("Refreshing a model"; csrc/ds_refresh.hip) ------------------------------
+GRADIENT_QUANTUM = float(1 << 30)                                    # node_sums count units of 2^-30
+
+
+def validate_refresh(n_features, features=None, target=None, eval_features=None, eval_target=None, *, n=None,
+                     n_eval=0, eta=0.1, reg_lambda=1.0, beta=5.0, sample_weight=None, refresh_leaf=True):
+    """The checks of ForestModel.refresh and refresh_device (no library needed) -> a dict of the cleaned arguments.
+    features: a host [n, n_features] matrix of numbers, n >= 0 (no row: the model comes back unchanged), or None with
+    `n` for a matrix in HBM; target: n labels of 0 / 1.  eval_features / eval_target go together: a host
+    [n_eval, n_features] matrix with n_eval >= 1, or, for a matrix in HBM, eval_target with n_eval given.  eta and beta
+    finite and above 0, reg_lambda finite and not negative; sample_weight: None or train.validate_sample_weight's;
+    without weights max(beta, 1) * n <= 2^32, the same bound on the integer sums; refresh_leaf a bool."""
+    from .train import WEIGHT_GUARD, _labels, _real, validate_sample_weight
+
+    def matrix(rows, rows_n, what, low):
+        if rows is None:
+            if isinstance(rows_n, bool) or not isinstance(rows_n, (int, np.integer)) or not low <= rows_n < 1 << 31:
+                raise ValueError(f"the number of {what} rows must be an integer in [{low}, 2^31), not {rows_n!r}")
+            return None, int(rows_n)
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != n_features:
+            raise ValueError(f"{what} features must be a [n, {n_features}] matrix, not shape {rows.shape}")
+        if not (np.issubdtype(rows.dtype, np.floating) or np.issubdtype(rows.dtype, np.integer)):
+            raise ValueError(f"{what} features must be numbers, not {rows.dtype}")
+        if rows.shape[0] < low:
+            raise ValueError(f"{what} features need at least {low} row")
+        return np.ascontiguousarray(rows, dtype=np.float32), rows.shape[0]
+
+    features, n = matrix(features, n, "training", 0)
+    if target is None:
+        raise ValueError("target is missing: a refresh needs one label per training row")
+    target = _labels(n, target, "training")
+    has_eval = eval_target is not None
+    if features is not None and (eval_features is None) != (eval_target is None):
+        raise ValueError("eval_features and eval_target go together")
+    if has_eval:
+        eval_features, n_eval = matrix(eval_features, n_eval, "evaluation", 1)
+        eval_target = _labels(n_eval, eval_target, "evaluation")
+    else:
+        eval_features, n_eval = None, 0
+    eta, reg_lambda = _real("eta", eta, positive=True), _real("reg_lambda", reg_lambda)
+    beta = _real("beta", beta, positive=True)
+    if sample_weight is not None:
+        sample_weight = validate_sample_weight(sample_weight, n, beta)
+    elif max(beta, 1.0) * n > WEIGHT_GUARD:
+        raise ValueError(f"max(beta, 1) * n = {max(beta, 1.0) * n!r} exceeds 2^32: the integer sums could overflow")
+    if not isinstance(refresh_leaf, (bool, np.bool_)):
+        raise ValueError(f"refresh_leaf must be True or False, not {refresh_leaf!r}")
+    return dict(features=features, n=n, target=target, eval_features=eval_features, n_eval=n_eval,
+                eval_target=eval_target, eta=eta, reg_lambda=reg_lambda, beta=beta, sample_weight=sample_weight,
+                refresh_leaf=bool(refresh_leaf))
+
+
+def split_gains(arrays, node_sums, reg_lambda):
+    """float64[n_nodes]: for every split node G_L^2 / (H_L + lambda) + G_R^2 / (H_R + lambda) - G^2 / (H + lambda) of
+    its own and its two children's (G, H) = node_sums / 2^30, the trainer's split gain on the refreshed data; 0 for a
+    leaf.  No library needed."""
+    sums = np.asarray(node_sums, dtype=np.int64).astype(np.float64) / GRADIENT_QUANTUM
+    feature, offsets = arrays["feature"], arrays["tree_offsets"]
+    tree = np.searchsorted(offsets, np.arange(feature.shape[0]), side="right") - 1
+    base = offsets[tree] if feature.shape[0] else np.zeros(0, np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        term = sums[:, 0] * sums[:, 0] / (sums[:, 1] + float(reg_lambda))
+    term = np.where(np.isfinite(term), term, 0.0)             # lambda = 0 and no hessian: no evidence, no gain
+    split = feature >= 0
+    gain = np.zeros(feature.shape[0], np.float64)
+    gain[split] = term[(base + arrays["yes"])[split]] + term[(base + arrays["no"])[split]] - term[split]
+    return gain
+
+
+class RefreshResult:
+    """What ForestModel.refresh returns.  `model`: a NEW ForestModel with the old model's splits and base margin and
+    the refreshed leaves (refresh_leaf=False: the old leaves); node_sums int64[n_nodes, 2]: the (gradient, hessian) sums
+    in units of 2^-30 of the rows that reach each node; cover float64[n_nodes] = hessian sum / 2^30 (xgboost's cover);
+    gain float64[n_nodes]: split_gains, 0 for a leaf; empty_leaves: the leaves whose hessian sum is 0, which kept their
+    value; margins float32[n]: the refreshed model's margins of the training rows.  With an evaluation set: history, the
+    custom error after every tree prefix of the refreshed model (n_trees values), best_iteration, the prefix (from 0)
+    of its first minimum, and initial_error, the error of the model as given; None otherwise."""
+
+    def __init__(self, model, node_sums, empty_leaves, margins, reg_lambda, eval_errors=None):
+        self.model, self.node_sums, self.empty_leaves, self.margins = model, node_sums, int(empty_leaves), margins
+        self.reg_lambda = float(reg_lambda)
+        self.cover = node_sums[:, 1].astype(np.float64) / GRADIENT_QUANTUM
+        self.gain = split_gains(model.arrays, node_sums, reg_lambda)
+        self.history = self.initial_error = self.best_iteration = None
+        if eval_errors is not None:
+            from .train import FirstMinimum
+            self.initial_error, self.history = int(eval_errors[0]), [int(v) for v in eval_errors[1:]]
+            rule = FirstMinimum()
+            for round_, value in enumerate(self.history):
+                rule.see(round_, value)
+            self.best_iteration = rule.best
+
+    def gain_importance(self):
+        """float64[n_features]: per feature the total gain of its splits over the sum of them, the shape of
+        ForestModel.feature_importance(); zeros when no split gains anything.  A split whose gain on this data is
+        negative counts as it is."""
+        feature = self.model.arrays["feature"]
+        split = feature >= 0
+        totals = np.bincount(feature[split], weights=self.gain[split], minlength=self.model.n_features)
+        total = totals.sum()
+        return totals / total if total else np.zeros(self.model.n_features, np.float64)
+
+
 class ForestModel:
     def __init__(self, feature, threshold, yes, no, missing, tree_offsets, n_features, base_margin=0.0, device=0):
         self.arrays = dict(feature=np.ascontiguousarray(feature, dtype=np.int32),
@@ -544,7 +648,9 @@ class ForestModel:
 
     def option(self, name, value):
         """ds_forest_option, for tests: option("max_blocks", v) caps the grids of the cover, contributions and inspection
-        kernels; option("inspect_jobs_per_block", v) sets the jobs an inspection workgroup runs per staged row block."""
+        kernels and of refresh's row kernels; option("inspect_jobs_per_block", v) sets the jobs an inspection workgroup
+        runs per staged row block; option("refresh_lds_nodes", v) the largest tree (in nodes, at most 2048) whose sums a
+        refresh workgroup keeps in LDS, a larger tree adding straight to HBM."""
         _lib.check(_lib.lib().ds_forest_option(self.handle, name.encode(), int(value)), "ds_forest_option")
 
     def predict_contributions(self, rows, approximate=False):
@@ -651,6 +757,71 @@ class ForestModel:
         counters = self.inspect_device(d_rows, v["n"], d_target, dependence_jobs(v["feature"], v["grid"]), 0,
                                        v["threshold"], stream)
         return PartialDependence(counters, v["n"], v["feature"], v["grid"], v["threshold"])
+
+    def refresh(self, features, target, eval_features=None, eval_target=None, *, eta=0.1, reg_lambda=1.0, beta=5.0,
+                sample_weight=None, refresh_leaf=True, trace=False):
+        """Re-estimate this model's leaves on rows it may never have seen and keep every split (xgboost's
+        process_type="update", updater="refresh", refresh_leaf; DESIGN.md section 9, "Refreshing a model") ->
+        RefreshResult.  The rows go through the trees in order on the device: before tree t a row's gradient pair is
+        taken at its margin under the trees refreshed so far (the trainer's weighted log loss, its 2^30 fixed point and
+        its sample_weight), the pairs are summed per leaf as exact integers, and a leaf with a hessian sum above 0 takes
+        -G / (H + reg_lambda) * eta, the trainer's leaf value; a leaf without evidence (no row, or only rows of weight
+        0) keeps its value and is counted in empty_leaves.  A model grown by ForestTrainer without subsampling or
+        constraints and refreshed on its own data and parameters comes back bit for bit.  This model is untouched: the
+        result's `model` is a new one, without a cover (the result's `cover` can be installed with set_cover where every
+        node has some).  refresh_leaf=False changes no leaf and still returns the sums, cover, gain and errors.
+        eval_features / eval_target: the custom error of the refreshed model after every tree prefix (`history`,
+        `best_iteration`) and that of this model (`initial_error`).  validate_refresh says what is accepted.
+        Not done here: subsampling; reapplying monotone bounds (monotone_violations tells afterwards whether the
+        refreshed model still satisfies them); batched or cross-validated refresh; changing any split.
+        trace=True (for tests) also returns, as the result's `trace`, float32[n_trees, n]: the probabilities the
+        gradients of every tree were taken at."""
+        v = validate_refresh(self.n_features, features, target, eval_features, eval_target, eta=eta,
+                             reg_lambda=reg_lambda, beta=beta, sample_weight=sample_weight, refresh_leaf=refresh_leaf)
+        return self._refresh(False, v["features"], v["eval_features"], v, trace, None)
+
+    def refresh_device(self, d_rows, n, target, d_eval_rows=None, n_eval=0, eval_target=None, *, eta=0.1, reg_lambda=1.0,
+                       beta=5.0, sample_weight=None, refresh_leaf=True, trace=False, stream=None):
+        """refresh for the first n rows of a contiguous float32[n, n_features] matrix that lies in HBM on this model's
+        device (and the first n_eval of d_eval_rows), read where they lie and complete on `stream`; labels and weights
+        are host arrays.  The call returns after one synchronisation of `stream`."""
+        if (d_eval_rows is None) != (eval_target is None):
+            raise ValueError("d_eval_rows and eval_target go together")
+        for array, rows, what in ((d_rows, n, "training"), (d_eval_rows, n_eval, "evaluation")):
+            if isinstance(array, _lib.DeviceArray):
+                if len(array.shape) != 2 or array.shape[1] != self.n_features or array.dtype != np.float32:
+                    raise ValueError(f"the device {what} matrix must be float32[n, {self.n_features}], not "
+                                     f"{array.dtype}{array.shape}")
+                if isinstance(rows, (int, np.integer)) and rows > array.shape[0]:
+                    raise ValueError(f"{rows} {what} rows exceed the device matrix's {array.shape[0]}")
+        if d_rows is None:
+            raise ValueError("the device feature matrix is missing")
+        v = validate_refresh(self.n_features, None, target, None, eval_target, n=n, n_eval=n_eval, eta=eta,
+                             reg_lambda=reg_lambda, beta=beta, sample_weight=sample_weight, refresh_leaf=refresh_leaf)
+        return self._refresh(True, d_rows, d_eval_rows if v["n_eval"] else None, v, trace, stream)
+
+    def _refresh(self, in_hbm, rows, eval_rows, v, trace, stream):
+        """The one call behind refresh and refresh_device, after validate_refresh."""
+        n, n_eval = v["n"], v["n_eval"]
+        leaves = np.empty(max(self.n_nodes, 1), np.float32)[:self.n_nodes]        # never a null pointer
+        node_sums = np.zeros((max(self.n_nodes, 1), 2), np.int64)[:self.n_nodes]
+        margins = np.empty(n, np.float32)
+        eval_errors = np.full(self.n_trees + 1, -1, np.int64)
+        empty = ctypes.c_int64(0)
+        probabilities = np.empty((self.n_trees, n), np.float32) if trace else None
+        entry = "ds_forest_refresh_device" if in_hbm else "ds_forest_refresh"
+        pointer = _lib.pointer
+        _lib.check(getattr(_lib.lib(), entry)(
+            self.handle, pointer(rows if n else None), n, pointer(v["target"]), pointer(v["sample_weight"]),
+            pointer(eval_rows), pointer(v["eval_target"]), n_eval, v["eta"], v["reg_lambda"], v["beta"],
+            int(v["refresh_leaf"]), pointer(leaves), pointer(node_sums), pointer(margins if n else None),
+            pointer(eval_errors), ctypes.byref(empty), pointer(probabilities if n else None),
+            *((pointer(stream),) if in_hbm else ())), entry)
+        model = self._from_arrays(dict(self.arrays, threshold=leaves))
+        result = RefreshResult(model, node_sums, empty.value, margins, v["reg_lambda"],
+                               eval_errors if n_eval else None)
+        result.trace = probabilities
+        return result
 
     def feature_importance(self):
         """float64[n_features]: the number of splits on each feature over the sum of them (train.py

@@ -774,6 +774,54 @@ class TrainModelResult:
         self.permutation_importance = permutation_importance
 
 
+def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, model, top_n=100, sample_n=10, seed=0,
+                  device=0, transform=True, evaluation_fractions=None, build_index="host", kind_weights=None, eta=0.1,
+                  reg_lambda=1.0, beta=5.0, refresh_leaf=True):
+    """ForestModel.refresh from raw titles: FeatureEngineering(...).generate_device_data_sets(), the device data sets
+    train_model trains on, then model.refresh_device on the training matrix where it lies in HBM, with the evaluation
+    matrix (when the fractions draw one) for the errors per tree prefix.  The feature matrices never leave HBM.
+    model: an open ForestModel of FEATURES_COUNT features on `device`; it is not modified.  kind_weights: as
+    train_model's, the sample weight of the training rows by kind, handed on as sample_weight.  eta, reg_lambda, beta,
+    refresh_leaf: ForestModel.refresh's.  Everything is validated before any device work.  Returns the RefreshResult
+    with two more attributes: `rows` (the DataFrame of FeatureEngineering.rows) and `timings` (milliseconds per stage
+    of the data sets, "refresh" and "total")."""
+    from .feature_engineering import FEATURES_COUNT
+    from .forest import validate_refresh
+    from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
+    started = time.perf_counter()
+    if not isinstance(model, ForestModel):
+        raise ValueError(f"model must be a ForestModel, not {type(model).__name__}")
+    if not model.handle:
+        raise ValueError("model is closed")
+    if model.n_features != FEATURES_COUNT:
+        raise ValueError(f"model has {model.n_features} features, the title features are {FEATURES_COUNT}")
+    if model.device != device:
+        raise ValueError(f"model lives on device {model.device}, the data sets on device {device}")
+    validate_refresh(FEATURES_COUNT, None, np.zeros(1, np.float32), n=1, eta=eta, reg_lambda=reg_lambda, beta=beta,
+                     refresh_leaf=refresh_leaf)
+    if kind_weights is not None:
+        validate_kind_weights(kind_weights)
+    fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
+                            sample_n=sample_n, seed=seed, device=device, transform=transform,
+                            evaluation_fractions=evaluation_fractions, build_index=build_index)
+    sets = fe.generate_device_data_sets()
+    timings = dict(fe.timings)
+    has_eval = sets.n_evaluation > 0
+    weighted = {} if kind_weights is None else dict(sample_weight=weights_of_kinds(fe.rows, kind_weights))
+    mark = time.perf_counter()
+    try:
+        result = model.refresh_device(sets.train, sets.n_train, sets.train_target,
+                                      sets.evaluation if has_eval else None, sets.n_evaluation,
+                                      sets.evaluation_target if has_eval else None, eta=eta, reg_lambda=reg_lambda,
+                                      beta=beta, refresh_leaf=refresh_leaf, **weighted)
+    finally:
+        sets.free()
+    timings["refresh"] = (time.perf_counter() - mark) * 1000.0
+    timings["total"] = (time.perf_counter() - started) * 1000.0
+    result.rows, result.timings = fe.rows, timings
+    return result
+
+
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
                 kind_weights=None, monotone_constraints=None, permutation_repeats=0, permutation_seed=0,

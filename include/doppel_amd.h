@@ -819,6 +819,52 @@ int ds_trainer_batch_seed(ds_trainer_batch *batch, const ds_forest *forest, cons
 int ds_trainer_batch_seed_device(ds_trainer_batch *batch, const ds_forest *forest, const float *d_features,
                                  int64_t *initial_errors, void *stream);
 
+/* ---- refreshing a model: xgboost's process_type="update", updater="refresh" ("Refreshing a model")
+ * ds_forest_refresh keeps every split of `forest` and re-estimates its leaves on n rows it may never have seen: the RAW
+ * float32[n][n_features] matrix, labels in {0, 1} and optional float32 weights (null: every row weighs 1).  The forest is
+ * not modified; the new values come back in leaf_out.  With b the forest's base margin, per row leafsum = 0 (float32),
+ * then for every tree t in order:
+ *   p = 1.0f / (1.0f + expf(-(b + leafsum))); (g, h) = the trainer's quantized gradient pair at p (ds_trainer_step's:
+ *   w = beta + y - beta y, g = (p w - y) s, h = (p (1 - p) w) s in double, rint(x * 2^30) to int64);
+ *   the row walks tree t by the rule of ds_forest_predict_device (NaN -> missing, else value < threshold -> yes) to a
+ *   leaf l; QG_l, QH_l = the exact integer sums of g, h over the rows that reach l;
+ *   with refresh_leaf = 1 a leaf with QH_l > 0 takes (float)((-(QG_l / 2^30) / (QH_l / 2^30 + reg_lambda)) * eta), the
+ *   trainer's leaf value; a leaf with QH_l == 0 (no row reaches it, or only rows of weight 0) keeps its value; with
+ *   refresh_leaf = 0 every leaf keeps its value;
+ *   leafsum = leafsum + the (new) value of l, a float32 add.
+ * So a forest grown by ds_trainer_step without sampling or constraints and refreshed on its own matrix, labels, weights,
+ * eta, reg_lambda and beta comes back bit for bit.  Integer sums: the same bits for any grid and any schedule.
+ * Outputs, host arrays in both forms: leaf_out float32[n_nodes], the forest's value array with the new leaves (a split
+ * node holds its unchanged threshold); node_sums int64[n_nodes][2] = (QG, QH) in the forest's node order, an inner node
+ * the sum of its two children (QH / 2^30 is xgboost's cover); margins (nullable) float32[n] = b + the final leafsum;
+ * *empty_leaves = the leaves with QH == 0; trace (nullable, for tests) float32[n_trees][n], the p of every tree.
+ * Evaluation set (eval_features null and n_eval 0 for none): raw float32[n_eval][n_features] rows and labels take the
+ * same walk and margin update without sums; eval_errors (nullable) int64[n_trees + 1]: entry 0 the custom error
+ * (ds_trainer_step's) of the forest as given, entry k that of the first k refreshed trees; all -1 without a set.
+ * A host matrix is uploaded once, whole, because every tree reads it again: DS_E_HIP with the bytes needed and the bytes
+ * free when it does not fit.  Two launches per tree on one stream, no host sync between trees, then one sync.
+ * n == 0 launches nothing over training rows: leaf_out holds the forest's values and every sum is 0.
+ * DS_E_ARG with a message naming the argument, before any device work: a null forest or output, a feature count above
+ * 96, n or n_eval outside [0, 2^31), a label that is not 0 or 1, a weight that is negative or not finite,
+ * max(beta, 1) * the total weight (without weights: * n) above 2^32 (the int64 sums could overflow), eta <= 0,
+ * reg_lambda < 0, beta <= 0, refresh_leaf that is neither 0 nor 1, and a tree that is no proper binary tree (the rule of
+ * ds_forest_cover_device).
+ * ds_forest_refresh_device: the same for matrices that lie complete in HBM on the forest's device (another device is
+ * DS_E_ARG), read where they lie; labels and weights stay host arrays.  The kernels are enqueued on `stream`, which is
+ * synchronised before returning.
+ * ds_forest_option(forest, "refresh_lds_nodes", v), v in [0, 2048], is for tests: a tree of at most v nodes sums in a
+ * workgroup's LDS table before HBM, a larger one adds straight to HBM (0 = the default, 2048); "max_blocks" caps the row
+ * grids.  No result depends on either. */
+int ds_forest_refresh(const ds_forest *forest, const float *features, int64_t n, const float *labels,
+                      const float *weights, const float *eval_features, const float *eval_labels, int64_t n_eval,
+                      double eta, double reg_lambda, double beta, int refresh_leaf, float *leaf_out, int64_t *node_sums,
+                      float *margins, int64_t *eval_errors, int64_t *empty_leaves, float *trace);
+int ds_forest_refresh_device(const ds_forest *forest, const float *d_features, int64_t n, const float *labels,
+                             const float *weights, const float *d_eval_features, const float *eval_labels, int64_t n_eval,
+                             double eta, double reg_lambda, double beta, int refresh_leaf, float *leaf_out,
+                             int64_t *node_sums, float *margins, int64_t *eval_errors, int64_t *empty_leaves, float *trace,
+                             void *stream);
+
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
  * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
