@@ -73,6 +73,13 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         hessian sums per node, cover, the gain of every split on that data, gain_importance() and the evaluation error
         per tree prefix; a model refreshed on its own training data comes back bit for bit; validate_refresh(...) says
         what is accepted (this project's own)
+    compare_models([a, b], rows, target, groups=), compare_models_device(models, d_rows, n, d_target),
+        bootstrap_accuracy({"a": ids_a, "b": ids_b}, actual_title_ids, groups=), train_model(..., bootstrap_repeats=2000)
+        -> is model B better: the evaluation error of 1 to 64 models (or sets of predicted ids) over the same rows under
+        one paired bootstrap, resampled by group on the device (ErrorBootstrap: errors, interval(), standard_error,
+        difference(a, b) with its interval and share_better, frame()); bootstrap_counts(codes, groups) for any outcome
+        codes; integer counts, the same bits run after run; validate_bootstrap(...) says what is accepted (this
+        project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -98,4 +105,6 @@ from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, c
                     validate_monotone_constraints, validate_sample_weight)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
+from .bootstrap import (BootstrapCounts, ErrorBootstrap, ErrorDifference, bootstrap_accuracy, bootstrap_counts,  # noqa: F401
+                        compare_models, compare_models_device, validate_bootstrap)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -763,15 +763,17 @@ class TrainModelResult:
     `initial_error`, the evaluation error of the init model (None otherwise and without an evaluation set); `model`,
     `feature_importance` and a counted cover are those of the WHOLE forest, `history` that of the new rounds and
     `best_iteration` counts all trees (ForestTrainer).  With permutation_repeats > 0: `permutation_importance`, the
-    model's PermutationImportance on the evaluation set (None otherwise)."""
+    model's PermutationImportance on the evaluation set (None otherwise).  With bootstrap_repeats > 0:
+    `error_bootstrap`, the ErrorBootstrap of the model (and of the init model) on the evaluation set (None otherwise)."""
 
     def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings,
-                 metrics_history=None, initial_error=None, permutation_importance=None):
+                 metrics_history=None, initial_error=None, permutation_importance=None, error_bootstrap=None):
         self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
         self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
         self.metrics_history = metrics_history
         self.initial_error = initial_error
         self.permutation_importance = permutation_importance
+        self.error_bootstrap = error_bootstrap
 
 
 def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, model, top_n=100, sample_n=10, seed=0,
@@ -825,7 +827,7 @@ def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
                 kind_weights=None, monotone_constraints=None, permutation_repeats=0, permutation_seed=0,
-                **fit_parameters):
+                bootstrap_repeats=0, bootstrap_seed=0, **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -846,7 +848,12 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     (feature_engineering.ratio_constraints() constrains the 17 similarity ratios upwards), handed to fit_device.
     permutation_repeats: 0, or the n_repeats of ForestModel.permutation_importance_device, run on the evaluation
     matrix where it lies in HBM after the error matrix, with seed permutation_seed and the fit's beta: the result's
-    `permutation_importance`, timed as `timings["permutation"]`.  It needs an evaluation set."""
+    `permutation_importance`, timed as `timings["permutation"]`.  It needs an evaluation set.
+    bootstrap_repeats: 0, or the n_boot of bootstrap.compare_models_device, run on the evaluation matrix where it lies
+    in HBM with seed bootstrap_seed, the fit's beta and the evaluation rows grouped by the train title they were
+    sampled for (tuning.row_groups): the result's `error_bootstrap`, timed as `timings["bootstrap"]`.  With init_model
+    it holds two sets, "model" and "init_model", and difference("model", "init_model") says whether the continued
+    model's gain exceeds what another evaluation sample would give.  It needs an evaluation set."""
     from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
@@ -862,16 +869,23 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         monotone_constraints = validate_monotone_constraints(monotone_constraints, FEATURES_COUNT, FEATURE_NAMES)
     permutation_repeats = _positive_int("permutation_repeats", permutation_repeats, 0, (1 << 16) - 1)
     permutation_seed = _positive_int("permutation_seed", permutation_seed, 0, (1 << 63) - 1)
+    bootstrap_repeats = _positive_int("bootstrap_repeats", bootstrap_repeats, 0, 1 << 16)
+    bootstrap_seed = _positive_int("bootstrap_seed", bootstrap_seed, 0, (1 << 63) - 1)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=evaluation_fractions, build_index=build_index)
     if permutation_repeats and not any(fe.evaluation_fractions.values()):
         raise ValueError("permutation_repeats needs an evaluation set, and every evaluation fraction is 0")
+    if bootstrap_repeats and not any(fe.evaluation_fractions.values()):
+        raise ValueError("bootstrap_repeats needs an evaluation set, and every evaluation fraction is 0")
     sets = fe.generate_device_data_sets()
     timings = dict(fe.timings)
     if permutation_repeats and sets.n_evaluation == 0:
         sets.free()
         raise ValueError("permutation_repeats needs an evaluation set, and no row was drawn into it")
+    if bootstrap_repeats and sets.n_evaluation == 0:
+        sets.free()
+        raise ValueError("bootstrap_repeats needs an evaluation set, and no row was drawn into it")
     trainer = ForestTrainer(device)
     mark = time.perf_counter()
     has_eval = sets.n_evaluation > 0
@@ -907,6 +921,22 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         finally:
             d_target.free()
         timings["permutation"] = (time.perf_counter() - mark) * 1000.0
+    error_bootstrap = None
+    if bootstrap_repeats:
+        from .bootstrap import compare_models_device
+        from .tuning import row_groups
+        mark = time.perf_counter()
+        d_target = _lib.DeviceArray.from_host(np.ascontiguousarray(sets.evaluation_target, dtype=np.float32), device)
+        compared = [model] if init_model is None else [model, init_model]
+        try:
+            error_bootstrap = compare_models_device(
+                compared, sets.evaluation, sets.n_evaluation, d_target,
+                groups=row_groups(fe.rows)[fe.rows["evaluation"].to_numpy()], n_boot=bootstrap_repeats,
+                seed=bootstrap_seed, threshold=PREDICTION_PROBABILITY_THRESHOLD,
+                beta=validate_parameters(**fit_parameters)["beta"], names=("model", "init_model")[:len(compared)])
+        finally:
+            d_target.free()
+        timings["bootstrap"] = (time.perf_counter() - mark) * 1000.0
     if cover:
         mark = time.perf_counter()
         try:
@@ -924,4 +954,4 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     timings["total"] = (time.perf_counter() - started) * 1000.0
     return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings,
                             metrics_history=metrics_history, initial_error=initial_error,
-                            permutation_importance=permutation_importance)
+                            permutation_importance=permutation_importance, error_bootstrap=error_bootstrap)

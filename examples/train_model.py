@@ -13,7 +13,7 @@ top-k pairs of the train queries labelled with their known source row) and the r
 
     python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH]
                                    [--kind-weights generated=0.5,positive=2] [--monotone ratios]
-                                   [--permutation-repeats N]
+                                   [--permutation-repeats N] [--bootstrap-repeats N]
                                    [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
@@ -34,6 +34,9 @@ signs.  The number of splits that break the constraints is printed for the model
 --permutation-repeats N prints the ten features whose shuffling on the evaluation set raises the custom error most
 (ForestModel.permutation_importance, N shuffles per feature on the device; with --one-call from the evaluation matrix
 where it lies in HBM: ds.train_model(..., permutation_repeats=N)), next to their rank by split count.
+--bootstrap-repeats N prints the evaluation error under a paired bootstrap of N replicates, the evaluation rows resampled
+by the train title they were sampled for (ds.compare_models; with --one-call ds.train_model(..., bootstrap_repeats=N) on
+the evaluation matrix in HBM): the error's interval and, with --init-model, the difference to the init model.
 """
 import os
 import sys
@@ -90,8 +93,20 @@ def print_importance(importance, split_shares, count=10):
               f"{row['margin_shift']:+.4f}   split-count rank {split_rank[int(row['feature'])]}")
 
 
+def print_bootstrap(bootstrap):
+    """The error of every compared model with its interval, and the first against each other one."""
+    print(f"paired bootstrap of the evaluation error, {bootstrap.n_boot} replicates of {bootstrap.n_units} groups:")
+    for _, row in bootstrap.frame().iterrows():
+        print(f"  {row['name']:<12} custom error {row['baseline_error']:g}   95% interval [{row['low']:.1f}, "
+              f"{row['high']:.1f}]   standard error {row['standard_error']:.1f}")
+    for other in bootstrap.names[1:]:
+        d = bootstrap.difference(0, other)
+        print(f"  {bootstrap.names[0]} - {other}: {d.baseline:+g}   95% interval [{d.interval[0]:+.1f}, "
+              f"{d.interval[1]:+.1f}]   better in {d.share_better:.3f} of the replicates")
+
+
 def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None,
-         kind_weights=None, monotone=None, permutation_repeats=0):
+         kind_weights=None, monotone=None, permutation_repeats=0, bootstrap_repeats=0):
     init = ds.ForestModel.load(init_model) if init_model else None
     init_trees = init.n_trees if init else 0
     if init:
@@ -110,7 +125,7 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         t0 = time.perf_counter()
         result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics),
                                 init_model=init, kind_weights=kind_weights, monotone_constraints=monotone,
-                                permutation_repeats=permutation_repeats)
+                                permutation_repeats=permutation_repeats, bootstrap_repeats=bootstrap_repeats)
         t1 = time.perf_counter()
         model = result.model
         if metrics:
@@ -127,6 +142,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         print("most used features:", ", ".join(f"f{f} {result.feature_importance[f]:.3f}" for f in top))
         if permutation_repeats:
             print_importance(result.permutation_importance, result.feature_importance)
+        if bootstrap_repeats:
+            print_bootstrap(result.error_bootstrap)
     else:
         fe = ds.FeatureEngineering(truth_titles, train.title_id, train_titles, train_ids)
         features, labels, eval_features, eval_labels = fe.generate_train_and_evaluation_data_sets()
@@ -153,6 +170,11 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         if permutation_repeats:
             print_importance(model.permutation_importance(eval_features, eval_labels, n_repeats=permutation_repeats),
                              model.feature_importance())
+        if bootstrap_repeats:
+            from doppel_speller_amd.tuning import row_groups
+            compared, names = ([model], ("model",)) if init is None else ([model, init], ("model", "init_model"))
+            print_bootstrap(ds.compare_models(compared, eval_features, eval_labels, n_boot=bootstrap_repeats, names=names,
+                                              groups=row_groups(fe.rows)[fe.rows["evaluation"].to_numpy()]))
 
     if constraints is not None:
         print(f"monotone constraints on {int(np.count_nonzero(constraints))} features: "
@@ -210,5 +232,13 @@ if __name__ == "__main__":
             raise SystemExit("--permutation-repeats needs the number of shuffles per feature")
         repeats = int(arguments[at + 1])
         del arguments[at:at + 2]
+    bootstrap = 0
+    if "--bootstrap-repeats" in arguments:
+        at = arguments.index("--bootstrap-repeats")
+        if at + 1 >= len(arguments):
+            raise SystemExit("--bootstrap-repeats needs the number of replicates")
+        bootstrap = int(arguments[at + 1])
+        del arguments[at:at + 2]
     main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted,
-         init_model=init_path, kind_weights=kinds, monotone=monotone, permutation_repeats=repeats)
+         init_model=init_path, kind_weights=kinds, monotone=monotone, permutation_repeats=repeats,
+         bootstrap_repeats=bootstrap)

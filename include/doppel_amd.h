@@ -865,6 +865,41 @@ int ds_forest_refresh_device(const ds_forest *forest, const float *d_features, i
                              int64_t *node_sums, float *margins, int64_t *eval_errors, int64_t *empty_leaves, float *trace,
                              void *stream);
 
+/* ---- is a difference real: the paired bootstrap of outcome counts ("Is a difference real") --------
+ * codes: uint8[n_sets][n]; row i under prediction set m has the outcome class codes[m][i] in {0, 1, 2, 3}.  unit:
+ * int32[n], the resampling unit of row i in [0, n_units), or null: then n_units must be n and every row is its own unit.
+ * A unit may hold no row.  With U = n_units:
+ *   T[u][m][c]        = the rows i with unit[i] == u and codes[m][i] == c;
+ *   baseline[m][c]    = the sum over u of T[u][m][c];
+ *   x(b, k)           = the first kept output of the stream ("Randomness" below) of (seed, purpose
+ *                       DS_BOOTSTRAP_PURPOSE_DRAW, index (b << 32) | k);
+ *   j(b, k)           = floor(x * U / 2^64), the high 64 bits of the 128-bit product;
+ *   counts[b][m][c]   = the sum over k < U of T[j(b, k)][m][c], int64: replicate b draws U units, and all sets see the
+ *                       same draws, which makes the comparison paired.
+ * Integer sums: the same bits for any grid, any split of replicates or draws over workgroups and any order.
+ * Limits: n_sets in [1, 64], n_boot in [1, 65536], n in [0, 2^31], n_units in [1, 2^31] when n > 0.
+ * ds_bootstrap_counts_device: codes, units, d_counts ([n_boot][n_sets][4]) and d_baseline ([n_sets][4]) lie in HBM on the
+ * current device.  A kernel checks every code and unit first (and builds T), and `stream` is synchronised for its verdict:
+ * a code above 3 or a unit outside [0, n_units) is DS_E_ARG with both outputs untouched.  Then the outputs are zeroed
+ * and the resampling runs; `stream` is synchronised before the call returns.  Scratch: 16 * n_units * n_sets bytes with
+ * units, none without.  n == 0 is DS_OK with zeroed counters.  DS_E_ARG before any device work: a null pointer, a limit
+ * exceeded, a null unit with n_units != n.  ds_bootstrap_counts: the same for host arrays, checked on the host.
+ * ds_bootstrap_option is for tests: "max_blocks" (0 = the default) caps the grids, which stride beyond it;
+ * "replicates_per_block" (0 = the launcher's choice) sets the replicates a workgroup runs over its staged table;
+ * "table_in_lds" 0 reads the table from HBM, 1 (the default) stages it in LDS when it fits.  No result depends on them.
+ * ds_outcome_codes_device: d_codes[i] = the outcome of margin d_margins[i] against d_target[i] by the rule of
+ * ds_forest_inspect: p = 1.0f / (1.0f + expf(-margin)), predicted positive iff (double)p > threshold (a NaN margin is
+ * not positive), actual positive iff target != 0; code 0 is tn, 1 fp, 2 fn, 3 tp.  Asynchronous on `stream`.  DS_E_ARG:
+ * a null pointer with n > 0, n outside [0, 2^31], threshold outside (0, 1). */
+#define DS_BOOTSTRAP_PURPOSE_DRAW 7
+int ds_bootstrap_counts_device(const uint8_t *d_codes, int32_t n_sets, int64_t n, const int32_t *d_unit, int64_t n_units,
+                               int32_t n_boot, uint64_t seed, long long *d_counts, long long *d_baseline, void *stream);
+int ds_bootstrap_counts(const uint8_t *codes, int32_t n_sets, int64_t n, const int32_t *unit, int64_t n_units,
+                        int32_t n_boot, uint64_t seed, long long *counts, long long *baseline);
+int ds_bootstrap_option(const char *name, int64_t value);
+int ds_outcome_codes_device(const float *d_margins, const float *d_target, int64_t n, double threshold, uint8_t *d_codes,
+                            void *stream);
+
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
  * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
