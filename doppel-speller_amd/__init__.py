@@ -80,6 +80,13 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         difference(a, b) with its interval and share_better, frame()); bootstrap_counts(codes, groups) for any outcome
         codes; integer counts, the same bits run after run; validate_bootstrap(...) says what is accepted (this
         project's own)
+    ForestModel.calibrate(rows, target), calibrate_device(d_rows, n, d_target), fit_isotonic(scores, target),
+        train_model(..., calibrate=True), Prediction(..., calibrator=c)   -> what the probability means: the isotonic fit
+        of the labels on the model's probability, on the device on exact integers (Calibrator: lo, hi, pos, neg, values,
+        transform(), transform_device(), raw_threshold(q) for a probability_threshold at a calibrated level, frame(),
+        save() / load()); a `calibrated_probability` column in ranked_matches, exhaustive_matches and explain;
+        reliability(probabilities, target, n_bins) -> ReliabilityReport (counts, frame(), ece, mce, brier);
+        validate_calibration(...) says what is accepted (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
@@ -107,4 +114,6 @@ from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_a
                      select_parameters, tune_model_parameters)
 from .bootstrap import (BootstrapCounts, ErrorBootstrap, ErrorDifference, bootstrap_accuracy, bootstrap_counts,  # noqa: F401
                         compare_models, compare_models_device, validate_bootstrap)
+from .calibration import (Calibrator, IsotonicFit, ReliabilityReport, fit_isotonic, fit_isotonic_device,  # noqa: F401
+                          reliability, reliability_device, validate_calibration)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -11,7 +11,7 @@ _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jacca
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
             "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
             "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip", "ds_assign.hip",
-            "ds_hard.hip", "ds_inspect.hip", "ds_refresh.hip", "ds_bootstrap.hip")
+            "ds_hard.hip", "ds_inspect.hip", "ds_refresh.hip", "ds_bootstrap.hip", "ds_calibrate.hip")
 _lib = None
 
 
@@ -191,6 +191,11 @@ def _declare(handle):
         "ds_bootstrap_counts": [p, c.c_int32, c.c_int64, p, c.c_int64, c.c_int32, c.c_uint64, p, p],
         "ds_bootstrap_option": [c.c_char_p, c.c_int64],
         "ds_outcome_codes_device": [p, p, c.c_int64, c.c_double, p, p],
+        "ds_isotonic_fit_device": [p, p, c.c_int64, p, p, p, p, p, p],
+        "ds_isotonic_fit": [p, p, c.c_int64, p, p, p, p, p, c.c_int],
+        "ds_calibration_apply_device": [p, p, c.c_int32, p, c.c_int64, p, p],
+        "ds_reliability_device": [p, p, c.c_int64, c.c_int32, p, p],
+        "ds_calibrate_option": [c.c_char_p, c.c_int64],
         "ds_best_pairs_device": [p, p, c.c_int64, c.c_int32, p, p, p, p, p],
         "ds_trainer_create": [p, c.c_int64, c.c_int32, p, p, c.c_int32, c.c_double, c.c_double, c.c_double, c.c_double,
                               c.c_int, c.POINTER(p)],
@@ -300,7 +305,8 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_set_weights", "ds_trainer_batch_set_weights", "ds_trainer_set_monotone",
     "ds_trainer_batch_set_monotone", "ds_forest_inspect_device", "ds_forest_inspect", "ds_forest_refresh",
     "ds_forest_refresh_device", "ds_bootstrap_counts_device", "ds_bootstrap_counts", "ds_bootstrap_option",
-    "ds_outcome_codes_device")
+    "ds_outcome_codes_device", "ds_isotonic_fit_device", "ds_isotonic_fit", "ds_calibration_apply_device",
+    "ds_reliability_device", "ds_calibrate_option")
 
 
 def lib():

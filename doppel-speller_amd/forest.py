@@ -847,6 +847,38 @@ class ForestModel:
                                                        pointer(d_probabilities), pointer(stream)),
                    "ds_forest_predict_device")
 
+    def calibrate_device(self, d_rows, n, d_target, stream=None):
+        """calibrate for the first n rows of a float32 matrix in HBM on this model's device with its float32[n] target
+        in HBM: predict_device into a probability vector that stays in HBM, then the isotonic fit there."""
+        from .calibration import calibrate_rows_device
+        if n and (d_rows is None or d_target is None):
+            raise ValueError("the device matrix and its target are missing")
+        return calibrate_rows_device(self, d_rows, n, d_target, None, stream)[0]
+
+    def calibrate(self, rows, target):
+        """What this model's probability means on labelled rows -> calibration.Calibrator: the isotonic fit of the 0/1
+        labels (target != 0) on the float32 probability of every row, on the device (calibration.fit_isotonic of
+        predict(rows), without the probabilities leaving HBM).  Rows the model never saw (a held-out set) give the
+        honest map.  calibration.validate_calibration says what is accepted."""
+        from .calibration import validate_calibration
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.n_features:
+            raise ValueError(f"rows must be a [n, {self.n_features}] matrix, not shape {rows.shape}")
+        if not (np.issubdtype(rows.dtype, np.floating) or np.issubdtype(rows.dtype, np.integer)):
+            raise ValueError(f"rows must be numbers, not {rows.dtype}")
+        v = validate_calibration(target=target, n=rows.shape[0])
+        if v["target"] is None:
+            raise ValueError("target is missing")
+        if v["n"] == 0:
+            return self.calibrate_device(None, 0, None)
+        d_rows = _lib.DeviceArray.from_host(np.ascontiguousarray(rows, dtype=np.float32), self.device)
+        d_target = _lib.DeviceArray.from_host(v["target"], self.device)
+        try:
+            return self.calibrate_device(d_rows, v["n"], d_target)
+        finally:
+            d_rows.free()
+            d_target.free()
+
     def close(self):
         if self.handle:
             _lib.lib().ds_forest_destroy(self.handle)

@@ -218,6 +218,18 @@ class CandidatePipeline:
             raise ValueError(f"the last enqueue_rank_matches ranked {self._ranked_n} slots per query, not {n}")
         return tuple(a.to_host(self.n_queries * n).reshape(self.n_queries, n) for a in self._ranked)
 
+    def ranked_probabilities_device(self):
+        """The float32[Q * n] probabilities of the last `enqueue_rank_matches` where they lie in HBM."""
+        return self._ranked[1]
+
+    def exhaustive_probabilities_device(self):
+        """The float32[Q * n] probabilities of the last `enqueue_exhaustive` where they lie in HBM."""
+        return self._exhaustive[1]
+
+    def explained_probabilities_device(self):
+        """The float32[Q] probabilities of the last `enqueue_explain` where they lie in HBM."""
+        return self._explain["probability"]
+
     def enqueue_assign_edges(self, keys, rows, probability_threshold, stream=None):
         """The one-to-one stage's view of this chunk's ranked slots (ds_assign_edges_device), after
         `enqueue_rank_matches(n)`, over its outputs: per slot the key of its edge (0: no edge) and its row, written into

@@ -135,18 +135,32 @@ def _rank_slots(count, n):
             np.zeros((count, n), dtype=np.uint8), np.zeros((count, n), dtype=np.int8))
 
 
-def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_ids):
+def _with_calibrated(frame, calibrated):
+    """The frame with `calibrated_probability` (float32, one value per line) directly after `probability`; the frame
+    as it is for None."""
+    if calibrated is not None:
+        frame.insert(list(frame.columns).index("probability") + 1, "calibrated_probability",
+                     np.asarray(calibrated, dtype=np.float32))
+    return frame
+
+
+def ranked_frame(test_index, rows, probabilities, ratios, stages, truth_title_ids, calibrated=None):
     """ranked_matches' answer from the [Q, n] slots of the rank stage: one line per filled slot (stage != 0), sorted by
-    test_index, then rank (slot + 1: the filled slots of a query come first)."""
+    test_index, then rank (slot + 1: the filled slots of a query come first).  calibrated: None, or the calibrator's
+    map of the [Q, n] probabilities; an exact or close slot, whose probability is the constant 1.0, keeps 1.0."""
     import pandas as pd
     test_index = np.asarray(test_index, dtype=np.int64)
     query, slot = _filled_slots(test_index, np.asarray(stages) != STAGE_NONE)
     match_row = np.asarray(rows)[query, slot].astype(np.int64)
-    return pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
-                         "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
-                         "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
-                         "levenshtein_ratio": np.asarray(ratios, dtype=np.uint8)[query, slot],
-                         "stage": np.asarray(stages, dtype=np.int8)[query, slot]}, columns=list(RANKED_COLUMNS))
+    stage = np.asarray(stages, dtype=np.int8)[query, slot]
+    if calibrated is not None:
+        calibrated = np.where(stage == STAGE_MODEL, np.asarray(calibrated, dtype=np.float32)[query, slot], np.float32(1))
+    return _with_calibrated(
+        pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
+                      "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
+                      "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
+                      "levenshtein_ratio": np.asarray(ratios, dtype=np.uint8)[query, slot],
+                      "stage": stage}, columns=list(RANKED_COLUMNS)), calibrated)
 
 
 def validate_exhaustive(n, n_truth):
@@ -169,19 +183,22 @@ def jaccard_positions(rows, top_rows):
     return out
 
 
-def exhaustive_frame(test_index, rows, probabilities, top_rows, truth_title_ids):
+def exhaustive_frame(test_index, rows, probabilities, top_rows, truth_title_ids, calibrated=None):
     """exhaustive_matches' answer from the [Q, n] slots of the exhaustive stage and the [Q, top_n] Jaccard rows: one line
-    per filled slot (row >= 0), sorted by test_index, then rank (slot + 1: the filled slots of a query come first)."""
+    per filled slot (row >= 0), sorted by test_index, then rank (slot + 1: the filled slots of a query come first).
+    calibrated: None, or the calibrator's map of the [Q, n] probabilities."""
     import pandas as pd
     test_index = np.asarray(test_index, dtype=np.int64)
     rows = np.asarray(rows)
     positions = jaccard_positions(rows, top_rows)
     query, slot = _filled_slots(test_index, rows >= 0)
     match_row = rows[query, slot].astype(np.int64)
-    return pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
-                         "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
-                         "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
-                         "jaccard_position": positions[query, slot]}, columns=list(EXHAUSTIVE_COLUMNS))
+    return _with_calibrated(
+        pd.DataFrame({"test_index": test_index[query], "rank": slot.astype(np.int64) + 1,
+                      "title_id": np.asarray(truth_title_ids, dtype=np.int64)[match_row], "match_row": match_row,
+                      "probability": np.asarray(probabilities, dtype=np.float32)[query, slot],
+                      "jaccard_position": positions[query, slot]}, columns=list(EXHAUSTIVE_COLUMNS)),
+        None if calibrated is None else np.asarray(calibrated, dtype=np.float32)[query, slot])
 
 
 def predictions_accuracy(predicted_title_ids, actual_title_ids):
@@ -369,17 +386,20 @@ def top_contributions(contributions, n=5):
     return order.astype(np.int64), np.take_along_axis(contributions, order, axis=1)
 
 
-def explain_frame(test_index, match_row, probability, margin, bias, stage, answer_row, truth_title_ids):
-    """explain's answer, one line per title in the order of the call."""
+def explain_frame(test_index, match_row, probability, margin, bias, stage, answer_row, truth_title_ids,
+                  calibrated=None):
+    """explain's answer, one line per title in the order of the call.  calibrated: None, or the calibrator's map of
+    `probability`, which is the model's own here whatever the stage."""
     import pandas as pd
     match_row = np.asarray(match_row, dtype=np.int64)
     ids = np.asarray(truth_title_ids, dtype=np.int64)
-    return pd.DataFrame({"test_index": np.asarray(test_index, dtype=np.int64), "match_row": match_row,
-                         "title_id": ids[match_row] if match_row.shape[0] else np.zeros(0, np.int64),
-                         "probability": np.asarray(probability, dtype=np.float32),
-                         "margin": np.asarray(margin, dtype=np.float32), "bias": np.asarray(bias, dtype=np.float64),
-                         "stage": np.asarray(stage, dtype=np.int8),
-                         "answer_row": np.asarray(answer_row, dtype=np.int64)}, columns=list(EXPLAIN_COLUMNS))
+    return _with_calibrated(
+        pd.DataFrame({"test_index": np.asarray(test_index, dtype=np.int64), "match_row": match_row,
+                      "title_id": ids[match_row] if match_row.shape[0] else np.zeros(0, np.int64),
+                      "probability": np.asarray(probability, dtype=np.float32),
+                      "margin": np.asarray(margin, dtype=np.float32), "bias": np.asarray(bias, dtype=np.float64),
+                      "stage": np.asarray(stage, dtype=np.int8),
+                      "answer_row": np.asarray(answer_row, dtype=np.int64)}, columns=list(EXPLAIN_COLUMNS)), calibrated)
 
 
 def combine_stages(exact_row, close_row, model_row):
@@ -652,12 +672,17 @@ class Prediction:
     prepare_queries: "device" (default) transforms and encodes the query titles and derives their Jaccard rows on the
     device (`prepare_queries`, CandidatePipeline.load_queries_device); "host" does it on the host (transform_titles,
     query_rows, encode_collection).  Both give the same answers, details and errors.
-    build_index: "host" (default) or "device": where the truth index is built (TruthIndex); the index is the same."""
+    build_index: "host" (default) or "device": where the truth index is built (TruthIndex); the index is the same.
+    calibrator: None, or a calibration.Calibrator of the model's probability (ForestModel.calibrate, fit_isotonic):
+    ranked_matches, exhaustive_matches and explain then carry one more column, `calibrated_probability`, directly after
+    `probability`: the calibrator's map of it, computed on the device from the chunk's probability buffer (stage
+    "calibrate" of `timings`), 1.0 for an exact or close slot.  Order, answers and thresholds are unchanged; to decide
+    at a calibrated level q pass probability_threshold=calibrator.raw_threshold(q)."""
 
     def __init__(self, truth_titles, truth_title_ids, model, top_n=100, device=0, transform=True,
                  levenshtein_threshold=LEVENSHTEIN_RATIO_THRESHOLD,
                  probability_threshold=PREDICTION_PROBABILITY_THRESHOLD, chunk_queries=None, prepare_queries="device",
-                 build_index="host"):
+                 build_index="host", calibrator=None):
         truth_titles = list(truth_titles)
         self.truth_title_ids = validate_truth(truth_titles, truth_title_ids, top_n)
         _validate_chunk(chunk_queries)
@@ -665,6 +690,9 @@ class Prediction:
         validate_index_build(build_index, "build_index")
         if model is None or not hasattr(model, "predict_device"):
             raise ValueError("model must be a ForestModel")
+        if calibrator is not None and not hasattr(calibrator, "transform_device"):
+            raise ValueError("calibrator must be a Calibrator")
+        self.calibrator = calibrator
         self.model = model
         self.top_n = int(top_n)
         self.device = device
@@ -695,6 +723,20 @@ class Prediction:
         return default_chunk(self.device, (BYTES_PER_PAIR + BYTES_PER_PARTS * parts) * self.top_n + 64 +
                              (8 + 4 * MAX_GRAMS + 8) * device_rows + BYTES_PER_RANK * rank_slots +
                              BYTES_PER_EXPLAIN * explain)
+
+    def _stage_names(self, *names):
+        """The zeroed timings of a call's stages; with a calibrator, "calibrate" among them."""
+        return dict.fromkeys(names + (("calibrate",) if self.calibrator is not None else ()), 0.0)
+
+    def _enqueue_calibrated(self, clock, d_probabilities, count):
+        """Stage "calibrate": the calibrator's map of `count` probabilities where a stage left them in HBM, into a
+        buffer of its own -> that buffer (the caller copies it back and frees it); None without a calibrator."""
+        if self.calibrator is None:
+            return None
+        d_out = _lib.DeviceArray((max(1, count),), np.float32, self.device)
+        clock.device("calibrate", lambda: self.calibrator.transform_device(d_probabilities, count, d_out, None,
+                                                                           self.device))
+        return d_out
 
     def generate_test_predictions(self, titles, test_index=None):
         """One answer per title (predict.py:274-300): DataFrame [title_id, test_index] sorted by test_index."""
@@ -746,15 +788,16 @@ class Prediction:
         n = validate_rank(n, self.top_n)
         titles = list(titles)
         test_index = validate_queries(titles, test_index)
-        timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model", "rank",
-                                 "copy_back"), 0.0)
+        timings = self._stage_names("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model",
+                                    "rank", "copy_back")
         count, k = len(titles), self.top_n
         kept = Candidates(np.empty((count, k), np.int32), np.empty((count, k), np.uint8), np.empty((count, k), np.float32),
                           np.empty(count, np.int32), np.empty(count, np.int32)) if keep_candidates else None
-        slots, _ = self._rank(titles, timings, n, kept)
+        calibrated = None if self.calibrator is None else np.full((count, n), np.nan, dtype=np.float32)
+        slots, _ = self._rank(titles, timings, n, kept, calibrated=calibrated)
         self.timings = timings
         self.candidates = kept
-        return ranked_frame(test_index, *slots, self.truth_title_ids)
+        return ranked_frame(test_index, *slots, self.truth_title_ids, calibrated=calibrated)
 
     def one_to_one_matches(self, titles, n=5, test_index=None, probability_threshold=None):
         """One answer per title, each truth title given to one title at most: the frame of generate_test_predictions,
@@ -835,21 +878,27 @@ class Prediction:
         n = validate_exhaustive(n, len(self.truth_titles))
         titles = list(titles)
         test_index = validate_queries(titles, test_index)
-        timings = dict.fromkeys(("host_prepare", "top_k", "exhaustive", "copy_back"), 0.0)
+        timings = self._stage_names("host_prepare", "top_k", "exhaustive", "copy_back")
         count = len(titles)
         rows = np.full((count, n), -1, dtype=np.int32)
         probabilities = np.full((count, n), np.nan, dtype=np.float32)
+        calibrated = None if self.calibrator is None else np.full((count, n), np.nan, dtype=np.float32)
         top_rows = np.full((count, self.top_n), -1, dtype=np.int32)
         for pipeline, clock in self._chunks(titles, timings):
             first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
             self._top_k(pipeline, clock)
             clock.device("exhaustive", lambda: pipeline.enqueue_exhaustive(self.model, n))
+            d_calibrated = self._enqueue_calibrated(clock, pipeline.exhaustive_probabilities_device(),
+                                                    pipeline.n_queries * n)
             with clock.host("copy_back"):
                 rows[first:last], probabilities[first:last] = pipeline.exhaustive(n)
                 top_rows[first:last] = pipeline.rows()
+                if d_calibrated is not None:
+                    calibrated[first:last] = d_calibrated.to_host(pipeline.n_queries * n).reshape(-1, n)
+                    d_calibrated.free()
             clock.collect()
         self.timings = timings
-        return exhaustive_frame(test_index, rows, probabilities, top_rows, self.truth_title_ids)
+        return exhaustive_frame(test_index, rows, probabilities, top_rows, self.truth_title_ids, calibrated=calibrated)
 
     def explain(self, titles, test_index=None, approximate=False):
         """For every title the model's best candidate and why the model scored it so: a DataFrame [test_index,
@@ -872,9 +921,10 @@ class Prediction:
             raise ValueError("the model has no cover: ForestModel.fit_cover, set_cover or train_model(cover=True) first")
         titles = list(titles)
         test_index = validate_queries(titles, test_index)
-        timings = dict.fromkeys(("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model",
-                                 "contributions", "copy_back"), 0.0)
+        timings = self._stage_names("host_prepare", "top_k", "close_matches", "exact_matches", "features", "model",
+                                    "contributions", "copy_back")
         count, width = len(titles), self.model.n_features
+        calibrated = None if self.calibrator is None else np.full(count, np.nan, dtype=np.float32)
         match_row, answer_row = np.full(count, -1, dtype=np.int64), np.full(count, -1, dtype=np.int64)
         probability, margin = np.full(count, np.nan, dtype=np.float32), np.full(count, np.nan, dtype=np.float32)
         stage = np.zeros(count, dtype=np.int8)
@@ -885,10 +935,14 @@ class Prediction:
             # 1.-5. every pair scored, 6. the best pair per query, its features gathered, its margin and its contributions
             self._score_chunk(pipeline, clock, self.levenshtein_threshold)
             clock.device("contributions", lambda: pipeline.enqueue_explain(self.model, approximate))
+            d_calibrated = self._enqueue_calibrated(clock, pipeline.explained_probabilities_device(), pipeline.n_queries)
             # 7. one copy back of one pair per query (synchronises the null stream the stages ran on)
             with clock.host("copy_back"):
                 rows, best, held, margins, features[first:last], contributions[first:last] = pipeline.explained()
                 exact, close = pipeline.exact_matches(), pipeline.best_rows()
+                if d_calibrated is not None:
+                    calibrated[first:last] = d_calibrated.to_host(pipeline.n_queries)
+                    d_calibrated.free()
             clock.collect()
             # the answer of generate_test_predictions: the model matches only with a single best pair above the threshold
             model_row = np.where((best > np.float32(self.probability_threshold)) & (held == 1), rows, -1)
@@ -898,7 +952,7 @@ class Prediction:
         self.contributions = np.ascontiguousarray(contributions[:, :width])
         self.explained_features = features
         return explain_frame(test_index, match_row, probability, margin, contributions[:, width], stage, answer_row,
-                             self.truth_title_ids)
+                             self.truth_title_ids, calibrated=calibrated)
 
     def threshold_sweep(self, titles, actual_title_ids, levenshtein_thresholds=None, probability_thresholds=None,
                         test_index=None):
@@ -1077,18 +1131,24 @@ class Prediction:
             clock.device("features", pipeline.enqueue_features)
             clock.device("model", lambda: pipeline.enqueue_predict(self.model))
 
-    def _rank(self, titles, timings, n, kept=None, tail=None):
+    def _rank(self, titles, timings, n, kept=None, tail=None, calibrated=None):
         """The device work of ranked_matches, which one_to_one_matches shares: per chunk every pair scored, 6. the best n
         per query in order, 7. one copy back into the [Q, n] slots (and into `kept`), then tail(pipeline, clock) while
-        the ranked buffers still hold the chunk.  -> (slots, the call's clock: None without titles)."""
+        the ranked buffers still hold the chunk.  calibrated: None, or float32[Q, n] for the calibrator's map of the
+        ranked probabilities, made on the device.  -> (slots, the call's clock: None without titles)."""
         slots, clock = _rank_slots(len(titles), n), None
         for pipeline, clock in self._chunks(titles, timings, rank_slots=n):
             first, last = pipeline.q_first, pipeline.q_first + pipeline.n_queries
             self._score_chunk(pipeline, clock, self.levenshtein_threshold)
             clock.device("rank", lambda: pipeline.enqueue_rank_matches(n))
+            d_calibrated = None if calibrated is None else \
+                self._enqueue_calibrated(clock, pipeline.ranked_probabilities_device(), pipeline.n_queries * n)
             with clock.host("copy_back"):       # n entries per query (synchronises the null stream the stages ran on)
                 for out, chunk in zip(slots, pipeline.ranked(n)):
                     out[first:last] = chunk
+                if d_calibrated is not None:
+                    calibrated[first:last] = d_calibrated.to_host(pipeline.n_queries * n).reshape(-1, n)
+                    d_calibrated.free()
                 if kept is not None:
                     exact, best = pipeline.exact_matches(), pipeline.best_rows()
                     kept.rows[first:last] = pipeline.rows()

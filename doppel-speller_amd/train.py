@@ -764,16 +764,21 @@ class TrainModelResult:
     `feature_importance` and a counted cover are those of the WHOLE forest, `history` that of the new rounds and
     `best_iteration` counts all trees (ForestTrainer).  With permutation_repeats > 0: `permutation_importance`, the
     model's PermutationImportance on the evaluation set (None otherwise).  With bootstrap_repeats > 0:
-    `error_bootstrap`, the ErrorBootstrap of the model (and of the init model) on the evaluation set (None otherwise)."""
+    `error_bootstrap`, the ErrorBootstrap of the model (and of the init model) on the evaluation set (None otherwise).
+    With calibrate=True: `calibrator`, the Calibrator of the model's probability on the evaluation set, `reliability`,
+    the ReliabilityReport of the raw probability there, and `calibrated_reliability`, that of the calibrated value (all
+    three None otherwise)."""
 
     def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings,
-                 metrics_history=None, initial_error=None, permutation_importance=None, error_bootstrap=None):
+                 metrics_history=None, initial_error=None, permutation_importance=None, error_bootstrap=None,
+                 calibrator=None, reliability=None, calibrated_reliability=None):
         self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
         self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
         self.metrics_history = metrics_history
         self.initial_error = initial_error
         self.permutation_importance = permutation_importance
         self.error_bootstrap = error_bootstrap
+        self.calibrator, self.reliability, self.calibrated_reliability = calibrator, reliability, calibrated_reliability
 
 
 def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, model, top_n=100, sample_n=10, seed=0,
@@ -827,7 +832,7 @@ def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
                 kind_weights=None, monotone_constraints=None, permutation_repeats=0, permutation_seed=0,
-                bootstrap_repeats=0, bootstrap_seed=0, **fit_parameters):
+                bootstrap_repeats=0, bootstrap_seed=0, calibrate=False, reliability_bins=10, **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -853,7 +858,13 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     in HBM with seed bootstrap_seed, the fit's beta and the evaluation rows grouped by the train title they were
     sampled for (tuning.row_groups): the result's `error_bootstrap`, timed as `timings["bootstrap"]`.  With init_model
     it holds two sets, "model" and "init_model", and difference("model", "init_model") says whether the continued
-    model's gain exceeds what another evaluation sample would give.  It needs an evaluation set."""
+    model's gain exceeds what another evaluation sample would give.  It needs an evaluation set.
+    calibrate: True fits what the model's probability means on the evaluation matrix where it lies in HBM
+    (ForestModel.calibrate_device) and bins it before and after in reliability_bins bins: the result's `calibrator`,
+    `reliability` and `calibrated_reliability`, timed as `timings["calibration"]`.  It needs an evaluation set.  That
+    set also chose best_iteration, and the calibrated report is read on the rows the map was fitted to, so it is mildly
+    optimistic: a held-out set through ForestModel.calibrate is the honest one.  False makes exactly the calls made
+    without it."""
     from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
@@ -871,6 +882,11 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     permutation_seed = _positive_int("permutation_seed", permutation_seed, 0, (1 << 63) - 1)
     bootstrap_repeats = _positive_int("bootstrap_repeats", bootstrap_repeats, 0, 1 << 16)
     bootstrap_seed = _positive_int("bootstrap_seed", bootstrap_seed, 0, (1 << 63) - 1)
+    if not isinstance(calibrate, (bool, np.bool_)):
+        raise ValueError(f"calibrate must be True or False, not {calibrate!r}")
+    if calibrate:
+        from .calibration import calibrate_rows_device, validate_calibration
+        reliability_bins = validate_calibration(n_bins=reliability_bins)["n_bins"]
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
                             evaluation_fractions=evaluation_fractions, build_index=build_index)
@@ -878,6 +894,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         raise ValueError("permutation_repeats needs an evaluation set, and every evaluation fraction is 0")
     if bootstrap_repeats and not any(fe.evaluation_fractions.values()):
         raise ValueError("bootstrap_repeats needs an evaluation set, and every evaluation fraction is 0")
+    if calibrate and not any(fe.evaluation_fractions.values()):
+        raise ValueError("calibrate needs an evaluation set, and every evaluation fraction is 0")
     sets = fe.generate_device_data_sets()
     timings = dict(fe.timings)
     if permutation_repeats and sets.n_evaluation == 0:
@@ -886,6 +904,9 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     if bootstrap_repeats and sets.n_evaluation == 0:
         sets.free()
         raise ValueError("bootstrap_repeats needs an evaluation set, and no row was drawn into it")
+    if calibrate and sets.n_evaluation == 0:
+        sets.free()
+        raise ValueError("calibrate needs an evaluation set, and no row was drawn into it")
     trainer = ForestTrainer(device)
     mark = time.perf_counter()
     has_eval = sets.n_evaluation > 0
@@ -937,6 +958,15 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         finally:
             d_target.free()
         timings["bootstrap"] = (time.perf_counter() - mark) * 1000.0
+    calibration = (None, None, None)
+    if calibrate:
+        mark = time.perf_counter()
+        d_target = _lib.DeviceArray.from_host(np.ascontiguousarray(sets.evaluation_target, dtype=np.float32), device)
+        try:
+            calibration = calibrate_rows_device(model, sets.evaluation, sets.n_evaluation, d_target, reliability_bins)
+        finally:
+            d_target.free()
+        timings["calibration"] = (time.perf_counter() - mark) * 1000.0
     if cover:
         mark = time.perf_counter()
         try:
@@ -954,4 +984,6 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     timings["total"] = (time.perf_counter() - started) * 1000.0
     return TrainModelResult(model, model.feature_importance(), error_matrix, best_iteration, history, fe.rows, timings,
                             metrics_history=metrics_history, initial_error=initial_error,
-                            permutation_importance=permutation_importance, error_bootstrap=error_bootstrap)
+                            permutation_importance=permutation_importance, error_bootstrap=error_bootstrap,
+                            calibrator=calibration[0], reliability=calibration[1],
+                            calibrated_reliability=calibration[2])

@@ -13,7 +13,7 @@ top-k pairs of the train queries labelled with their known source row) and the r
 
     python examples/train_model.py [--one-call] [--metrics auc,logloss] [--init-model PATH]
                                    [--kind-weights generated=0.5,positive=2] [--monotone ratios]
-                                   [--permutation-repeats N] [--bootstrap-repeats N]
+                                   [--permutation-repeats N] [--bootstrap-repeats N] [--calibrate]
                                    [n_truth] [n_queries] [top_n] [model.npz]
 
 top_n is the candidate count of Prediction and of the training_pairs model; the training set samples 10 of 100.
@@ -37,6 +37,10 @@ where it lies in HBM: ds.train_model(..., permutation_repeats=N)), next to their
 --bootstrap-repeats N prints the evaluation error under a paired bootstrap of N replicates, the evaluation rows resampled
 by the train title they were sampled for (ds.compare_models; with --one-call ds.train_model(..., bootstrap_repeats=N) on
 the evaluation matrix in HBM): the error's interval and, with --init-model, the difference to the init model.
+--calibrate prints what the model's probability means on the evaluation set: the reliability of the raw probability
+and of its isotonic calibration, and the raw thresholds for the calibrated levels 0.9, 0.95 and 0.99
+(ForestModel.calibrate; with --one-call ds.train_model(..., calibrate=True) on the evaluation matrix in HBM).
+examples/calibrate_model.py does the same for a saved model.
 """
 import os
 import sys
@@ -105,8 +109,19 @@ def print_bootstrap(bootstrap):
               f"{d.interval[1]:+.1f}]   better in {d.share_better:.3f} of the replicates")
 
 
+def print_calibration(calibrator, raw, calibrated):
+    """ECE before and after, both tables and the raw thresholds of three calibrated levels."""
+    print(f"isotonic calibration on {calibrator.n_rows} evaluation rows: {len(calibrator)} blocks; ECE {raw.ece:.5f} raw, "
+          f"{calibrated.ece:.5f} calibrated; Brier {raw.brier:.6f} raw, {calibrated.brier:.6f} calibrated")
+    for title, report in (("raw probability", raw), ("calibrated value", calibrated)):
+        print(f"  {title}:")
+        print("  " + report.frame().to_string(index=False, float_format=lambda v: f"{v:.4f}").replace("\n", "\n  "))
+    print("  " + ", ".join(f"calibrated level {q}: probability_threshold {calibrator.raw_threshold(q)!r}"
+                           for q in (0.9, 0.95, 0.99)))
+
+
 def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, metrics=(), init_model=None,
-         kind_weights=None, monotone=None, permutation_repeats=0, bootstrap_repeats=0):
+         kind_weights=None, monotone=None, permutation_repeats=0, bootstrap_repeats=0, calibrate=False):
     init = ds.ForestModel.load(init_model) if init_model else None
     init_trees = init.n_trees if init else 0
     if init:
@@ -125,7 +140,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
         t0 = time.perf_counter()
         result = ds.train_model(truth_titles, train.title_id, train_titles, train_ids, eval_metrics=tuple(metrics),
                                 init_model=init, kind_weights=kind_weights, monotone_constraints=monotone,
-                                permutation_repeats=permutation_repeats, bootstrap_repeats=bootstrap_repeats)
+                                permutation_repeats=permutation_repeats, bootstrap_repeats=bootstrap_repeats,
+                                calibrate=calibrate)
         t1 = time.perf_counter()
         model = result.model
         if metrics:
@@ -144,6 +160,8 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
             print_importance(result.permutation_importance, result.feature_importance)
         if bootstrap_repeats:
             print_bootstrap(result.error_bootstrap)
+        if calibrate:
+            print_calibration(result.calibrator, result.reliability, result.calibrated_reliability)
     else:
         fe = ds.FeatureEngineering(truth_titles, train.title_id, train_titles, train_ids)
         features, labels, eval_features, eval_labels = fe.generate_train_and_evaluation_data_sets()
@@ -175,6 +193,10 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
             compared, names = ([model], ("model",)) if init is None else ([model, init], ("model", "init_model"))
             print_bootstrap(ds.compare_models(compared, eval_features, eval_labels, n_boot=bootstrap_repeats, names=names,
                                               groups=row_groups(fe.rows)[fe.rows["evaluation"].to_numpy()]))
+        if calibrate:
+            calibrator, probabilities = model.calibrate(eval_features, eval_labels), model.predict(eval_features)
+            print_calibration(calibrator, ds.reliability(probabilities, eval_labels),
+                              ds.reliability(calibrator.transform(probabilities), eval_labels))
 
     if constraints is not None:
         print(f"monotone constraints on {int(np.count_nonzero(constraints))} features: "
@@ -196,7 +218,7 @@ def main(n_truth=20000, n_queries=4000, top_n=10, path=None, one_call=False, met
 
 
 if __name__ == "__main__":
-    arguments = [a for a in sys.argv[1:] if a != "--one-call"]
+    arguments = [a for a in sys.argv[1:] if a not in ("--one-call", "--calibrate")]
     wanted = ()
     if "--metrics" in arguments:
         at = arguments.index("--metrics")
@@ -241,4 +263,4 @@ if __name__ == "__main__":
         del arguments[at:at + 2]
     main(*[int(a) for a in arguments[:3]], *arguments[3:4], one_call="--one-call" in sys.argv[1:], metrics=wanted,
          init_model=init_path, kind_weights=kinds, monotone=monotone, permutation_repeats=repeats,
-         bootstrap_repeats=bootstrap)
+         bootstrap_repeats=bootstrap, calibrate="--calibrate" in sys.argv[1:])

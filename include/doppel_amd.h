@@ -900,6 +900,48 @@ int ds_bootstrap_option(const char *name, int64_t value);
 int ds_outcome_codes_device(const float *d_margins, const float *d_target, int64_t n, double threshold, uint8_t *d_codes,
                             void *stream);
 
+/* ---- what the probability means: isotonic calibration and reliability ("Calibration") -------------
+ * scores, labels: float32[n].  A row is positive iff its label != 0.  Its place is key(score), the integer order of
+ * float32 of the cuts and the metrics: -0.0 counts as +0.0, the infinities are ordinary ends, and a row whose score is a
+ * NaN is counted apart and takes no part.  Rows of equal key are one POINT of weight pos + neg.  The fit is the isotonic
+ * (non-decreasing) least-squares regression of the labels on the points, returned as its level sets: K blocks in
+ * ascending order, block k with
+ *   lo[k], hi[k]   the float32 values of its smallest and largest key,
+ *   pos[k], neg[k] its positive and negative rows (int64),
+ * and pos / (pos + neg) strictly increasing in k.  Means are compared by cross-multiplying the integer sums (counts are
+ * below 2^31, the products fit 64 bits); no floating point enters, and the solution is unique, so the blocks are the
+ * same bits for any grid, any segment width and from run to run.
+ * The map of a calibration (lo, value): a score s takes value[k] of the last block with key(lo[k]) <= key(s), 0 when
+ * key(s) < key(lo[0]), a NaN when s is a NaN or K == 0.  A look-up, no interpolation.
+ * ds_isotonic_fit_device: the inputs and the four outputs (room for n blocks each) lie in HBM on the current device.
+ * out[0] = K, out[1] = the NaN rows left out, out[2] = the distinct keys (points), out[3] = the blocks that entered the
+ * last, serial pooling level.  Stages: keys split by label, both columns sorted by the radix sort of the cuts, one
+ * point per distinct key, then pooling in two levels: segments of points pooled in LDS by a workgroup each, and the
+ * survivors pooled to the end by one thread.  Limits: n in [0, 2^31); n == 0 or only NaN scores give K = 0.  A null
+ * pointer with n > 0 or n out of range is DS_E_ARG before any device work.  Scratch: below 33 * n bytes + 1 MiB (the
+ * sort's two buffers and table, the head scan, the points; 2 * n more at segment_points 2), checked against the free HBM (with 64 MiB of head room) before anything is allocated: DS_E_HIP.  `stream` is
+ * synchronised before the call returns.  ds_isotonic_fit: the same for host arrays on `device` (32 * n bytes more).
+ * ds_calibration_apply_device: d_out[i] = the map of d_scores[i]; d_lo, d_value float32[K], K >= 0, edges ascending.
+ * The edges' keys are staged in LDS when K <= 16384 and read from HBM otherwise; one binary search per score.
+ * Asynchronous on `stream`.  DS_E_ARG: a null pointer with n > 0 (d_lo, d_value may be null when K == 0), K < 0, n
+ * outside [0, 2^31).
+ * ds_reliability_device: d_out is int64[n_bins + 1][4], zeroed first.  A probability p in [0, 1] falls in bin
+ * min(floor((double)p * n_bins), n_bins - 1) and adds 1, (label != 0), rint(p * 2^30) and rint((p - y)^2 * 2^30), the
+ * last two in float64 with y = 0 or 1; a p that is a NaN or outside [0, 1] adds 1 and (label != 0) to row n_bins.
+ * Integer sums.  n_bins in [1, 256], n in [0, 2^31); asynchronous on `stream`.
+ * ds_calibrate_option is for tests: "max_blocks" (0 = the default) caps the grids, which stride beyond it;
+ * "segment_points" (0 = the launcher's choice, else 2 .. 2048) sets the points of a first-level segment.  No result
+ * depends on them. */
+int ds_isotonic_fit_device(const float *d_scores, const float *d_labels, int64_t n, float *d_lo, float *d_hi,
+                           long long *d_pos, long long *d_neg, int64_t *out, void *stream);
+int ds_isotonic_fit(const float *scores, const float *labels, int64_t n, float *lo, float *hi, long long *pos,
+                    long long *neg, int64_t *out, int device);
+int ds_calibration_apply_device(const float *d_lo, const float *d_value, int32_t K, const float *d_scores, int64_t n,
+                                float *d_out, void *stream);
+int ds_reliability_device(const float *d_probabilities, const float *d_labels, int64_t n, int32_t n_bins, long long *d_out,
+                          void *stream);
+int ds_calibrate_option(const char *name, int64_t value);
+
 /* ---- training set of the match model: FeatureEngineering.generate_train_and_evaluation_data_sets ----------------------
  * (doppelspeller/feature_engineering.py:172-378, feature_engineering_prepare.py).  Randomness: one splitmix64 stream per
  * (seed, purpose, index), state = seed * 0x9e3779b97f4a7c15 + index * 0xd1342543de82ef95 + purpose * 0xaf251af3b0f025b5
