@@ -186,16 +186,15 @@ __global__ __launch_bounds__(kBootstrapThreads) void ds_bootstrap_kernel(Bootstr
     }
 }
 
-// p = 1.0f / (1.0f + expf(-margin)), positive iff (double)p > cut (false for a NaN): the rule of ds_forest_inspect.
+// the outcome class of every row at its margin: tn 0, fp 1, fn 2, tp 3
 __global__ __launch_bounds__(kBootstrapCheckThreads) void ds_outcome_codes_kernel(const float *margins, const float *target,
                                                                                  int64_t n, double cut, uint8_t *codes)
 {
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBootstrapCheckThreads + threadIdx.x; i < n;
          i += static_cast<int64_t>(gridDim.x) * kBootstrapCheckThreads) {
-        const float p = 1.0f / (1.0f + expf(-margins[i]));
-        const bool positive = static_cast<double>(p) > cut;
+        const bool positive = forest_positive(forest_probability(margins[i]), cut);
         const bool actual = target[i] != 0.f;
-        codes[i] = static_cast<uint8_t>((actual ? 2 : 0) + (positive ? 1 : 0));   // tn 0, fp 1, fn 2, tp 3
+        codes[i] = static_cast<uint8_t>((actual ? 2 : 0) + (positive ? 1 : 0));
     }
 }
 

@@ -1,7 +1,7 @@
 // Why the model gave a pair its margin: node cover counted on the device, and per-feature contributions of every row
 // ("Contributions").
 //
-// Cover: the rows of a workgroup are staged in LDS as in ds_forest_kernel; a row adds 1 to the 64-bit counter of the leaf
+// Cover: the rows of a workgroup are staged in LDS; a row adds 1 to the 64-bit counter of the leaf
 // it reaches in every tree (integer atomics: exact, whatever the schedule), and a second kernel sums the inner nodes from
 // their children, one thread per tree (children follow their parent in node order, so one backward sweep does it).  The
 // root of every tree therefore never sees an atomic.
@@ -29,41 +29,26 @@ constexpr int kForestBlocksLimit = 1 << 20;
 constexpr int kLaneStride = kContributionsThreads + 1;  // [feature][lane] images in LDS, padded: the transposing copies spread over the banks
 
 struct CoverArgs {
-    const int4 *nodes;
-    const float *threshold;
-    const int64_t *tree_offsets;
+    ForestView forest;
     const float *rows;
     unsigned long long *counts;
     int64_t n;
-    int32_t n_trees, n_features;
 };
 
 __global__ __launch_bounds__(kForestThreads) void ds_forest_cover_kernel(CoverArgs a)
 {
     extern __shared__ float staged[];  // [kForestThreads][n_features + 1]
-    const int stride = a.n_features + 1;
+    const int stride = a.forest.n_features + 1;
     for (int64_t first = static_cast<int64_t>(blockIdx.x) * kForestThreads; first < a.n;
          first += static_cast<int64_t>(gridDim.x) * kForestThreads) {
-        const int rows_here = static_cast<int>(a.n - first < kForestThreads ? a.n - first : kForestThreads);
-        __syncthreads();
-        for (int e = threadIdx.x; e < rows_here * a.n_features; e += kForestThreads) {
-            const int r = e / a.n_features, f = e - r * a.n_features;
-            staged[r * stride + f] = a.rows[first * a.n_features + e];
-        }
+        const int rows_here =
+            forest_stage_rows<kForestThreads>(a.rows, a.n, first, a.forest.n_features, staged, stride, 1);
         __syncthreads();
         if (static_cast<int>(threadIdx.x) < rows_here) {
             const float *row = staged + threadIdx.x * stride;
-            for (int32_t t = 0; t < a.n_trees; ++t) {
-                const int64_t root = a.tree_offsets[t];
-                int64_t node = root;
-                int4 info = a.nodes[node];
-                while (info.x >= 0) {  // the rule of ds_forest_kernel
-                    const float value = row[info.x];
-                    const int next = (value != value) ? info.w : (value < a.threshold[node] ? info.y : info.z);
-                    node = root + next;
-                    info = a.nodes[node];
-                }
-                atomicAdd(a.counts + node, 1ull);
+            for (int32_t t = 0; t < a.forest.n_trees; ++t) {
+                const int64_t leaf = forest_walk(a.forest.nodes, a.forest.threshold, a.forest.tree_offsets[t], row);
+                atomicAdd(a.counts + leaf, 1ull);
             }
         }
     }
@@ -108,9 +93,7 @@ constexpr UnwindTable make_unwind_table()
 __constant__ UnwindTable kUnwind = make_unwind_table();
 
 struct ContributionsArgs {
-    const int4 *nodes;
-    const float *threshold;
-    const int64_t *tree_offsets;
+    ForestView forest;
     const int32_t *path_start;
     const double *path_leaf;
     const PathElement *elements;
@@ -119,7 +102,6 @@ struct ContributionsArgs {
     double *out;            // [n][n_features + 1]
     double bias;
     int64_t n, n_paths;
-    int32_t n_trees, n_features;
 };
 
 // The contributions of one row over all paths, added to sums[feature * kLaneStride] (this lane's column).
@@ -182,20 +164,18 @@ __device__ __forceinline__ void shap_row(const ContributionsArgs &a, const float
 // Saabas: along the row's own path every split adds the change of the subtree mean to its feature
 __device__ __forceinline__ void saabas_row(const ContributionsArgs &a, const float *row, double *sums)
 {
-    for (int32_t t = 0; t < a.n_trees; ++t) {
-        const int64_t root = a.tree_offsets[t];
+    for (int32_t t = 0; t < a.forest.n_trees; ++t) {
+        const int64_t root = a.forest.tree_offsets[t];
         int64_t node = root;
-        int4 info = a.nodes[node];
+        int4 info = a.forest.nodes[node];
         double mean = a.node_mean[node];
         while (info.x >= 0) {
-            const float value = row[info.x * kLaneStride];
-            const int next = (value != value) ? info.w : (value < a.threshold[node] ? info.y : info.z);
-            node = root + next;
+            node = root + forest_branch(info, row[info.x * kLaneStride], a.forest.threshold + node);
             const double child = a.node_mean[node];
             double *sum = sums + info.x * kLaneStride;
             *sum = *sum + (child - mean);
             mean = child;
-            info = a.nodes[node];
+            info = a.forest.nodes[node];
         }
     }
 }
@@ -205,20 +185,16 @@ template <int M>
 __global__ __launch_bounds__(kContributionsThreads) void ds_contributions_kernel(ContributionsArgs a)
 {
     extern __shared__ double shared[];  // sums [n_features][kLaneStride] float64, then rows [n_features][kLaneStride] float32
+    const int n_features = a.forest.n_features;
     double *sums = shared;
-    float *staged = reinterpret_cast<float *>(shared + a.n_features * kLaneStride);
+    float *staged = reinterpret_cast<float *>(shared + n_features * kLaneStride);
     const int lane = threadIdx.x;
-    const int width = a.n_features + 1;
+    const int width = n_features + 1;
     for (int64_t first = static_cast<int64_t>(blockIdx.x) * kContributionsThreads; first < a.n;
          first += static_cast<int64_t>(gridDim.x) * kContributionsThreads) {
-        const int rows_here =
-            static_cast<int>(a.n - first < kContributionsThreads ? a.n - first : kContributionsThreads);
-        __syncthreads();
-        for (int e = lane; e < rows_here * a.n_features; e += kContributionsThreads) {  // coalesced copy, transposed
-            const int r = e / a.n_features, f = e - r * a.n_features;
-            staged[f * kLaneStride + r] = a.rows[first * a.n_features + e];
-        }
-        for (int f = 0; f < a.n_features; ++f) sums[f * kLaneStride + lane] = 0.0;
+        const int rows_here =   // transposed; its barrier also ends the store loop's reads of the sums
+            forest_stage_rows<kContributionsThreads>(a.rows, a.n, first, n_features, staged, 1, kLaneStride);
+        for (int f = 0; f < n_features; ++f) sums[f * kLaneStride + lane] = 0.0;
         __syncthreads();
         if (lane < rows_here) {
             if constexpr (M > 0) shap_row<M>(a, staged + lane, sums + lane);
@@ -227,7 +203,7 @@ __global__ __launch_bounds__(kContributionsThreads) void ds_contributions_kernel
         __syncthreads();
         for (int e = lane; e < rows_here * width; e += kContributionsThreads) {  // coalesced store
             const int r = e / width, f = e - r * width;
-            a.out[first * width + e] = f < a.n_features ? sums[f * kLaneStride + r] : a.bias;
+            a.out[first * width + e] = f < n_features ? sums[f * kLaneStride + r] : a.bias;
         }
     }
 }
@@ -469,15 +445,7 @@ int ds_forest_cover_device(ds_forest *forest, const float *d_rows, int64_t n, vo
     }
     ds::drop_prepared(forest);
     if (n == 0 || forest->n_trees == 0) return DS_OK;
-    ds::CoverArgs args;
-    args.nodes = forest->nodes.ptr;
-    args.threshold = forest->threshold.ptr;
-    args.tree_offsets = forest->tree_offsets.ptr;
-    args.rows = d_rows;
-    args.counts = forest->counts.ptr;
-    args.n = n;
-    args.n_trees = forest->n_trees;
-    args.n_features = forest->n_features;
+    const ds::CoverArgs args{forest->view(), d_rows, forest->counts.ptr, n};
     const int64_t blocks = (n + ds::kForestThreads - 1) / ds::kForestThreads;
     const int64_t cap = forest->max_blocks ? forest->max_blocks : ds::kCoverMaxBlocks;
     const int grid = static_cast<int>(std::min<int64_t>(blocks, cap));
@@ -543,9 +511,7 @@ int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64
     DS_REQUIRE(d_rows && d_out, "ds_forest_contributions: null pointer");
     DS_HIP(hipSetDevice(forest->device));
     ds::ContributionsArgs args;
-    args.nodes = forest->nodes.ptr;
-    args.threshold = forest->threshold.ptr;
-    args.tree_offsets = forest->tree_offsets.ptr;
+    args.forest = forest->view();
     args.path_start = forest->path_start.ptr;
     args.path_leaf = forest->path_leaf.ptr;
     args.elements = forest->elements.ptr;
@@ -555,8 +521,6 @@ int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64
     args.bias = forest->bias;
     args.n = n;
     args.n_paths = forest->n_paths;
-    args.n_trees = forest->n_trees;
-    args.n_features = forest->n_features;
     const int64_t blocks = (n + ds::kContributionsThreads - 1) / ds::kContributionsThreads;
     const int64_t cap = forest->max_blocks ? forest->max_blocks : ds::kContributionsMaxBlocks;
     const int grid = static_cast<int>(std::min<int64_t>(blocks, cap));

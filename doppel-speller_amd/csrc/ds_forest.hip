@@ -17,35 +17,26 @@
 namespace ds {
 
 struct ForestArgs {
-    const int4 *nodes;
-    const float *threshold;
-    const int64_t *tree_offsets;
+    ForestView forest;
     const float *rows;
     float *margins;        // nullable
     float *probabilities;  // nullable
     int64_t n;
-    int32_t n_trees, n_features;
-    float base_margin;
 };
 
 __global__ __launch_bounds__(kForestThreads) void ds_forest_kernel(ForestArgs a)
 {
     extern __shared__ float staged[];  // [kForestThreads][n_features + 1] (+1: bank spread)
-    const int stride = a.n_features + 1;
+    const int stride = a.forest.n_features + 1;
     for (int64_t first = static_cast<int64_t>(blockIdx.x) * kForestThreads; first < a.n;
          first += static_cast<int64_t>(gridDim.x) * kForestThreads) {
-        const int rows_here = static_cast<int>(a.n - first < kForestThreads ? a.n - first : kForestThreads);
-        __syncthreads();
-        for (int e = threadIdx.x; e < rows_here * a.n_features; e += kForestThreads) {  // coalesced copy
-            const int r = e / a.n_features, f = e - r * a.n_features;
-            staged[r * stride + f] = a.rows[first * a.n_features + e];
-        }
+        const int rows_here =
+            forest_stage_rows<kForestThreads>(a.rows, a.n, first, a.forest.n_features, staged, stride, 1);
         __syncthreads();
         if (static_cast<int>(threadIdx.x) < rows_here) {
-            const float *row = staged + threadIdx.x * stride;
-            const float margin = a.base_margin + forest_leaf_sum(a.nodes, a.threshold, a.tree_offsets, a.n_trees, row);
+            const float margin = a.forest.base_margin + forest_leaf_sum(a.forest, staged + threadIdx.x * stride);
             if (a.margins) a.margins[first + threadIdx.x] = margin;
-            if (a.probabilities) a.probabilities[first + threadIdx.x] = 1.0f / (1.0f + expf(-margin));
+            if (a.probabilities) a.probabilities[first + threadIdx.x] = forest_probability(margin);
         }
     }
 }
@@ -120,17 +111,7 @@ int ds_forest_predict_device(ds_forest *forest, const float *d_rows, int64_t n, 
     if (n == 0) return DS_OK;
     DS_REQUIRE(d_rows && (d_margins || d_probabilities), "ds_forest_predict: null pointer");
     DS_HIP(hipSetDevice(forest->device));
-    ds::ForestArgs args;
-    args.nodes = forest->nodes.ptr;
-    args.threshold = forest->threshold.ptr;
-    args.tree_offsets = forest->tree_offsets.ptr;
-    args.rows = d_rows;
-    args.margins = d_margins;
-    args.probabilities = d_probabilities;
-    args.n = n;
-    args.n_trees = forest->n_trees;
-    args.n_features = forest->n_features;
-    args.base_margin = forest->base_margin;
+    const ds::ForestArgs args{forest->view(), d_rows, d_margins, d_probabilities, n};
     const int64_t blocks = (n + ds::kForestThreads - 1) / ds::kForestThreads;
     const int grid = static_cast<int>(std::min<int64_t>(blocks, 256 * 16));
     const size_t lds = static_cast<size_t>(ds::kForestThreads) * (forest->n_features + 1) * sizeof(float);

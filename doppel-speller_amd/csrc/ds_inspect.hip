@@ -6,13 +6,12 @@
 //             repeat, n), a 4-round Feistel network over 2^(2b) >= n with cycle walking, keyed by the sampling stream
 //   OVERRIDE  row[feature] = value (any float32, NaN and the infinities included)
 //
-// One thread per row.  The rows of a workgroup are staged in LDS as in ds_forest_kernel, once per row block; the
-// workgroup then runs its share of the jobs over them: a thread saves its row's value, writes the replacement (for
-// PERMUTE one gathered float), walks the forest by the rule of forest_leaf_sum and puts the value back.  Nothing but the thread's
-// own row is touched, so the job loop holds no barrier.  Per job and wave the five terms are summed over the lanes and
-// one lane adds them to the job's 64-bit counters in HBM.  The grid is row blocks x job groups (an evaluation set of ten
-// thousand rows is only forty row blocks); both dimensions stride, and every sum is an integer sum, so no number
-// depends on the split.
+// One thread per row.  The rows of a workgroup are staged in LDS, once per row block; the workgroup then runs its share
+// of the jobs over them: a thread saves its row's value, writes the replacement (for PERMUTE one gathered float), walks
+// the forest and puts the value back.  Nothing but the thread's own row is touched, so the job loop holds no barrier.
+// Per job and wave the five terms are summed over the lanes and one lane adds them to the job's 64-bit counters in HBM.
+// The grid is row blocks x job groups (an evaluation set of ten thousand rows is only forty row blocks); both
+// dimensions stride, and every sum is an integer sum, so no number depends on the split.
 #include "ds_forest.h"
 #include "ds_metrics.h"
 #include "ds_train.h"
@@ -40,7 +39,7 @@ struct InspectArgs {
     unsigned long long *out;          // [n_jobs][5]: tp, tn, fp, fn, margin_sum (two's complement)
     int64_t n;
     uint64_t seed;
-    double cut;                       // a row is positive iff (double)p > cut
+    double cut;                       // forest_positive's
     int32_t n_trees, n_features, n_jobs, jobs_per_block, n_groups;
     float base_margin;
 };
@@ -119,6 +118,9 @@ __device__ inline float forest_leaf_sum_interleaved(const int4 *nodes, const flo
             for (int k = 0; k < K; ++k) value[k] = row[info[k].x >= 0 ? info[k].x : 0];
 #pragma unroll
             for (int k = 0; k < K; ++k) {
+                // forest_branch's rule, written out: through the function (by value, by pointer, forced inline or not)
+                // hipcc sinks a chain's LDS read and selects under a branch on its info.x, the chains no longer issue
+                // together, and the 331-job shape above measured 7.80 ms against 7.31 ms
                 const int next = (value[k] != value[k]) ? info[k].w : (value[k] < cut[k] ? info[k].y : info[k].z);
                 if (info[k].x >= 0) node[k] = root[k] + next;
             }
@@ -131,18 +133,8 @@ __device__ inline float forest_leaf_sum_interleaved(const int4 *nodes, const flo
 #pragma unroll
         for (int k = 0; k < K; ++k) sum = sum + cut[k];   // tree order
     }
-    for (; t < n_trees; ++t) {   // the rule of forest_leaf_sum for the trees left over
-        const int64_t root = tree_offsets[t];
-        int64_t node = root;
-        int4 info = nodes[node];
-        while (info.x >= 0) {
-            const float value = row[info.x];
-            const int next = (value != value) ? info.w : (value < threshold[node] ? info.y : info.z);
-            node = root + next;
-            info = nodes[node];
-        }
-        sum = sum + threshold[node];
-    }
+    for (; t < n_trees; ++t)   // the trees left over, one at a time
+        sum = sum + threshold[forest_walk(nodes, threshold, tree_offsets[t], row)];
     return sum;
 }
 
@@ -153,12 +145,8 @@ __global__ __launch_bounds__(kForestThreads) void ds_forest_inspect_kernel(Inspe
     const int lane = threadIdx.x & 63;
     for (int64_t first = static_cast<int64_t>(blockIdx.x) * kForestThreads; first < a.n;
          first += static_cast<int64_t>(gridDim.x) * kForestThreads) {
-        const int rows_here = static_cast<int>(a.n - first < kForestThreads ? a.n - first : kForestThreads);
-        __syncthreads();
-        for (int e = threadIdx.x; e < rows_here * a.n_features; e += kForestThreads) {  // coalesced copy
-            const int r = e / a.n_features, f = e - r * a.n_features;
-            staged[r * stride + f] = a.rows[first * a.n_features + e];
-        }
+        const int rows_here =
+            forest_stage_rows<kForestThreads>(a.rows, a.n, first, a.n_features, staged, stride, 1);
         __syncthreads();
         if (static_cast<int>(threadIdx.x & ~63u) >= rows_here) continue;   // a wave without rows (the barriers are above)
         const bool active = static_cast<int>(threadIdx.x) < rows_here;
@@ -185,11 +173,11 @@ __global__ __launch_bounds__(kForestThreads) void ds_forest_inspect_kernel(Inspe
                         }
                         row[job.feature] = replacement;
                     }
-                    const float margin = a.base_margin + forest_leaf_sum_interleaved<kInspectTrees>(
+                    const float margin =
+                        a.base_margin + forest_leaf_sum_interleaved<kInspectTrees>(
                                                              a.nodes, a.threshold, a.tree_offsets, a.n_trees, row);
                     if (job.kind != DS_INSPECT_BASELINE) row[job.feature] = saved;
-                    const float p = 1.0f / (1.0f + expf(-margin));   // the rule of train_row_error
-                    const bool positive = static_cast<double>(p) > a.cut;   // false for a NaN
+                    const bool positive = forest_positive(forest_probability(margin), a.cut);
                     tp = positive && actual;
                     tn = !positive && !actual;
                     fp = positive && !actual;

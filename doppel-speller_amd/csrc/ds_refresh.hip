@@ -14,8 +14,8 @@
 // A last pass adds the last tree's leaves and writes the margins.  The rows of an evaluation set run the same row
 // kernel without the sums and add train_row_error at every tree prefix to one counter per prefix.
 // The rows are read where they lie, row-major: a walk touches one value per level, eight at the most, of a row of at
-// most 384 bytes, so staging whole rows in LDS (ds_forest_kernel) would move more than the walk reads and would take the
-// LDS that the table of sums uses.
+// most 384 bytes, so staging whole rows in LDS (forest_stage_rows) would move more than the walk reads and would take
+// the LDS that the table of sums uses.
 #include "ds_forest.h"
 #include "ds_train.h"
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kRowThreads) void ds_refresh_rows_kernel(RefreshArg
         const int64_t node = forest_walk(a.nodes, a.values, a.root, a.rows + r * a.nf);
         a.leaf_of[r] = static_cast<int32_t>(node);
         if (kSums) {
-            const float p = 1.0f / (1.0f + expf(-margin));   // ds_forest.hip's rule, the trainers' too
+            const float p = forest_probability(margin);
             if (a.trace != nullptr) a.trace[r] = p;
             long long qg, qh;
             train_row_gradient(p, a.labels[r], a.weights, r, a.beta, &qg, &qh);
@@ -131,10 +131,8 @@ __global__ __launch_bounds__(kRowThreads) void ds_refresh_tail_kernel(const floa
 }
 
 // the custom error of the forest as given: forest_leaf_sum of the raw rows where they lie
-__global__ __launch_bounds__(kRowThreads) void ds_refresh_initial_kernel(const int4 *nodes, const float *threshold,
-                                                                          const int64_t *tree_offsets, const float *rows,
-                                                                          const float *labels, int64_t n, int32_t nf,
-                                                                          int32_t n_trees, float base_margin,
+__global__ __launch_bounds__(kRowThreads) void ds_refresh_initial_kernel(ForestView forest, const float *rows,
+                                                                          const float *labels, int64_t n,
                                                                           unsigned long long *error)
 {
     __shared__ unsigned long long s_error;
@@ -143,8 +141,7 @@ __global__ __launch_bounds__(kRowThreads) void ds_refresh_initial_kernel(const i
     unsigned long long mine = 0;
     for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
          r += static_cast<int64_t>(gridDim.x) * kRowThreads)
-        mine += train_row_error(base_margin + forest_leaf_sum(nodes, threshold, tree_offsets, n_trees, rows + r * nf),
-                                labels[r]);
+        mine += train_row_error(forest.base_margin + forest_leaf_sum(forest, rows + r * forest.n_features), labels[r]);
     if (mine) atomicAdd(&s_error, mine);
     __syncthreads();
     if (threadIdx.x == 0 && s_error) atomicAdd(error, s_error);
@@ -262,9 +259,8 @@ int refresh_run(const char *who, const RefreshCall &c, const float *d_rows, cons
         return forest->max_blocks ? std::min<unsigned>(blocks, static_cast<unsigned>(forest->max_blocks)) : blocks;
     };
     if (n_eval > 0) {
-        hipLaunchKernelGGL(ds_refresh_initial_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, forest->nodes.ptr,
-                           forest->threshold.ptr, forest->tree_offsets.ptr, d_eval, d_eval_labels.ptr, n_eval, nf, n_trees,
-                           forest->base_margin, errors.ptr);
+        hipLaunchKernelGGL(ds_refresh_initial_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, forest->view(),
+                           d_eval, d_eval_labels.ptr, n_eval, errors.ptr);
         DS_HIP(hipGetLastError());
     }
     for (int32_t t = 0; t < n_trees; ++t) {

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "ds_common.h"
+#include "ds_forest.h"
 
 namespace ds {
 
@@ -215,7 +216,7 @@ __device__ inline void train_gradient_rows(const float *leafsum, const float *la
     for (int64_t r = blockIdx.x * static_cast<int64_t>(kRowThreads) + threadIdx.x; r < n;
          r += static_cast<int64_t>(gridDim.x) * kRowThreads) {
         const float margin = base_margin + leafsum[r];
-        const float p = 1.0f / (1.0f + expf(-margin));   // ds_forest.hip's rule
+        const float p = forest_probability(margin);
         long long qg, qh;
         train_row_gradient(p, labels[r], weights, r, beta, &qg, &qh);
         bool trains = !kFolds || static_cast<int32_t>(fold[r]) != held_out;
@@ -593,8 +594,7 @@ __device__ inline void train_feature_masks(const TrainSampling &sampling, int64_
 // train.py:fast_custom_error of one row at its margin: 1 for a missed positive, 5 for a false positive
 __device__ inline unsigned long long train_row_error(float margin, float label)
 {
-    const float p = 1.0f / (1.0f + expf(-margin));
-    const bool positive = static_cast<double>(p) > 0.9;   // settings.py PREDICTION_PROBABILITY_THRESHOLD
+    const bool positive = forest_positive(forest_probability(margin), 0.9);  // settings.py PREDICTION_PROBABILITY_THRESHOLD
     if (label != 0.f) return positive ? 0 : 1;
     return positive ? 5 : 0;                               // FALSE_POSITIVE_PENALTY_FACTOR
 }

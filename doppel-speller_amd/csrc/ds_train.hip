@@ -199,35 +199,29 @@ __global__ __launch_bounds__(kRowThreads) void ds_train_eval_kernel(const uint8_
 
 // ---- continuing from a model: a forest's leaf sums of the RAW rows, before the first round ---------------------------
 // The init model's thresholds need not be cuts of this matrix, so it is walked over the float32 features and not over the
-// bins.  One thread per row, the rows of a workgroup staged in LDS as in ds_forest_kernel, but at an odd stride
-// (n_features | 1): thread t reads word t * stride + f, and an odd stride spreads a wave's 64 rows over all 64 banks
-// for any feature count.  The sum is forest_leaf_sum's, what ds_forest_kernel holds before it adds the base margin; it
-// goes to the leaf sums of all n_models models of the view (stride apart), held-out rows included.
+// bins.  One thread per row, the rows of a workgroup staged in LDS at an odd stride (n_features | 1): thread t reads
+// word t * stride + f, and an odd stride spreads a wave's 64 rows over all 64 banks for any feature count.  The sum is
+// the margin without the base margin; it goes to the leaf sums of all n_models models of the view (stride apart),
+// held-out rows included.
 struct SeedArgs {
-    const int4 *nodes;
-    const float *threshold;
-    const int64_t *tree_offsets;
+    ForestView forest;
     const float *rows;
     float *leafsum;
     int64_t n, stride;
-    int32_t n_trees, n_features, n_models;
+    int32_t n_models;
 };
 
 __global__ __launch_bounds__(kRowThreads) void ds_train_seed_kernel(SeedArgs a)
 {
     extern __shared__ float s_rows[];   // [kRowThreads][n_features | 1]
-    const int stride = a.n_features | 1;
+    const int stride = a.forest.n_features | 1;
     for (int64_t first = static_cast<int64_t>(blockIdx.x) * kRowThreads; first < a.n;
          first += static_cast<int64_t>(gridDim.x) * kRowThreads) {
-        const int rows_here = static_cast<int>(a.n - first < kRowThreads ? a.n - first : kRowThreads);
-        __syncthreads();
-        for (int e = threadIdx.x; e < rows_here * a.n_features; e += kRowThreads) {   // coalesced row-major read
-            const int r = e / a.n_features, f = e - r * a.n_features;
-            s_rows[r * stride + f] = a.rows[first * a.n_features + e];
-        }
+        const int rows_here =
+            forest_stage_rows<kRowThreads>(a.rows, a.n, first, a.forest.n_features, s_rows, stride, 1);
         __syncthreads();
         if (static_cast<int>(threadIdx.x) < rows_here) {
-            const float sum = forest_leaf_sum(a.nodes, a.threshold, a.tree_offsets, a.n_trees, s_rows + threadIdx.x * stride);
+            const float sum = forest_leaf_sum(a.forest, s_rows + threadIdx.x * stride);
             float *out = a.leafsum + first + threadIdx.x;
             for (int32_t m = 0; m < a.n_models; ++m) out[m * a.stride] = sum;
         }
@@ -445,8 +439,7 @@ int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *f
         const int64_t here = std::min(chunk_rows, n - first);
         if (!in_hbm)   // after the kernel of the chunk before, in stream order
             DS_HIP(hipMemcpyAsync(staged.ptr, rows + first * nf, sizeof(float) * here * nf, hipMemcpyHostToDevice, stream));
-        const SeedArgs args{forest->nodes.ptr, forest->threshold.ptr, forest->tree_offsets.ptr,
-                            in_hbm ? rows : staged.ptr, leafsum + first, here, stride, forest->n_trees, nf, n_models};
+        const SeedArgs args{forest->view(), in_hbm ? rows : staged.ptr, leafsum + first, here, stride, n_models};
         hipLaunchKernelGGL(ds_train_seed_kernel, dim3(train_row_grid(compute_units, here)), dim3(kRowThreads), lds,
                            stream, args);
         DS_HIP(hipGetLastError());

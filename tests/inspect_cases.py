@@ -1,7 +1,9 @@
 """The cases of the model-inspection tests (test_inspect_cpu.py, test_gpu_inspect.py): forests from random_dump and
 matrices from random_rows (test_forest_cpu.py), with job tables and targets, at the smallest shapes where the kernel of
 csrc/ds_inspect.hip can still go wrong: one row, one short wave, a whole wave and one more, a whole workgroup and one
-more, three row blocks; 1, 7, 66 and 96 features; no tree, stumps, depth 6 and one tree of depth 16.
+more, three row blocks; 1, 3, 7, 66 and 96 features; no tree, stumps, depth 6 and one tree of depth 16; 0, 1, 2 and 3
+trees, at which the kernel's two-trees-at-a-time walk takes no pair, only the tree left over, one pair exactly, and one
+pair and a tree left over.
 
 Every case must keep all of its probabilities (every row under every job) at least PROBABILITY_GAP away from the
 threshold, so that the float32 expf of the device (within 2 ulp of libm by the project's own bound; 1e-6 is about four
@@ -62,6 +64,7 @@ SHAPES = [
     ("three_row_blocks",  700, 66, (19, 40, 6), "mixed", 39),
     ("base_margin",       700,  7, (20, 30, 6), "null", 30),
     ("many_job_groups",     2,  1, (31, 3, 1), "mixed", 32),
+    ("two_trees",          65,  3, (33, 2, 2), "mixed", 34),
 ]
 
 

@@ -173,9 +173,15 @@ def test_three_hundred_trees_of_depth_four():
 
 
 def test_awkward_trees_and_unequal_covers():
-    """The enumerable cases of the CPU test (stump, single leaf, repeats, empty intervals, covers of 1 against 10^6)."""
+    """The enumerable cases of the CPU test (stump, single leaf, repeats, empty intervals, covers of 1 against 10^6).
+    The cover kernel counts their rows first: the single leaf is a tree whose walk takes no step."""
+    from doppel_speller_amd import _lib
     for name, forest, cover, rows in cc.enumerable_cases():
         model = _model(forest, rows.shape[1])
+        d_rows = _lib.DeviceArray.from_host(rows)
+        counted = model.count_cover_device(d_rows, rows.shape[0])
+        d_rows.free()
+        assert np.array_equal(counted, cc.node_counts(forest, rows).astype(np.float64)), name
         model.set_cover(cover)
         _check(model, forest, cover, rows)
         _check(model, forest, cover, rows, approximate=True)

@@ -84,7 +84,11 @@ def test_case_conditions(name):
 def test_cases_cover_the_shapes():
     built = [cases.case(name) for name in cases.NAMES]
     assert {c["rows"].shape[0] for c in built} == {1, 2, 63, 64, 65, 255, 256, 257, 700}
-    assert {c["n_features"] for c in built} == {1, 7, 66, 96}
+    assert {c["n_features"] for c in built} == {1, 3, 7, 66, 96}
+    # the device walks two trees at a time: no pair, only the tree left over, one pair, one pair and a tree left over
+    assert {0, 1, 2, 3} <= {c["forest"]["tree_offsets"].shape[0] - 1 for c in built}
+    two = cases.case("two_trees")
+    assert two["rows"].shape == (65, 3) and np.diff(two["forest"]["tree_offsets"]).max() <= 7   # depth 2 at most
     assert sum(not np.isnan(c["rows"]).any() for c in built if c["rows"].shape[0] > 2) == 1
     assert {("null" if c["target"] is None else "zeros" if not c["target"].any() else "ones" if c["target"].all()
              else "mixed") for c in built} == {"null", "zeros", "ones", "mixed"}
