@@ -919,7 +919,9 @@ int ds_trainer_set_metrics(ds_trainer *trainer, uint32_t flags)
                                                t->params.beta};
     }
     DS_HIP(hipMemcpy(t->metric_columns.ptr, t->metric_host, sizeof(t->metric_host), hipMemcpyHostToDevice));
-    DS_HIP(hipMemset(t->metric_counters.ptr, 0, t->metric_counters.bytes()));
+    // on the trainer's own stream: it is non-blocking, so a memset on the null stream is not ordered in front of the rounds
+    DS_HIP(hipMemsetAsync(t->metric_counters.ptr, 0, t->metric_counters.bytes(), t->stream));
+    DS_HIP(hipStreamSynchronize(t->stream));
     t->metric_flags = flags;
     return DS_OK;
 }

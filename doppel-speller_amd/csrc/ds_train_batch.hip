@@ -545,7 +545,9 @@ int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags)
         column.n_pos = static_cast<int32_t>(pos[k]);
     }
     DS_HIP(hipMemcpy(b->metric_columns.ptr, b->metric_host.data(), sizeof(ds::MetricColumn) * M, hipMemcpyHostToDevice));
-    DS_HIP(hipMemset(b->metric_counters.ptr, 0, b->metric_counters.bytes()));
+    // on the batch's own stream: it is non-blocking, so a memset on the null stream is not ordered in front of the rounds
+    DS_HIP(hipMemsetAsync(b->metric_counters.ptr, 0, b->metric_counters.bytes(), b->stream));
+    DS_HIP(hipStreamSynchronize(b->stream));
     b->metric_flags = flags;
     return DS_OK;
 }

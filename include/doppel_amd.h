@@ -176,7 +176,10 @@ int ds_construct_features_indexed(ds_titles *queries, ds_titles *truth, const in
 /* Device-resident variant for the fused pipeline: d_pair_t = the top-k rows written by ds_jaccard_topk_device,
  * pair i belongs to query row q_first + i / k when d_pair_q is NULL.  d_out = float32[n*66] in HBM.
  * A pair whose query row or truth row lies outside its table (negative, or >= the table's rows: e.g. the -1 rows of a
- * top-k that failed) is not an error: its 66 outputs are the quiet NaN 0x7fc00000, and no title is read for it. */
+ * top-k that failed) is not an error: its 66 outputs are the quiet NaN 0x7fc00000, and no title is read for it.
+ * The first call that names (n_truth, space_code) on a truth table builds its truth records on `stream` and waits for
+ * them, which synchronises `stream` once (so does a device's first features launch of the process, for the ratio table):
+ * they are then complete for a launch on any stream.  After that a call only enqueues on `stream`. */
 int ds_construct_features_indexed_device(ds_titles *queries, ds_titles *truth, const int32_t *d_pair_q,
                                          const int32_t *d_pair_t, int64_t q_first, int32_t k, uint8_t space_code,
                                          uint32_t n_truth, int64_t n, float *d_out, void *stream);
@@ -220,7 +223,7 @@ int ds_remaining_pairs_device(const int32_t *d_best_row, const int32_t *d_rows, 
                               int64_t q_first, int32_t *d_pair_q, int32_t *d_pair_t, int64_t *d_counts, void *stream);
 /* predict.py:246-252 for n_remaining queries of k consecutive pairs each: d_match_query[r] = the query row of group
  * r, d_match_row[r] = the truth row of its maximum prediction when that maximum is above `threshold`
- * (PREDICTION_PROBABILITY_THRESHOLD, settings.py:76) and a single pair holds it, else -1. */
+ * (PREDICTION_PROBABILITY_THRESHOLD, settings.py:76) and a single pair holds it, else -1.  Asynchronous on `stream`. */
 int ds_select_matches_device(const int32_t *d_pair_q, const int32_t *d_pair_t, const float *d_predictions,
                              int64_t n_remaining, int32_t k, float threshold, int32_t *d_match_query,
                              int32_t *d_match_row, void *stream);
@@ -478,6 +481,7 @@ int ds_forest_create(const int32_t *feature, const float *threshold, const int32
                      float base_margin, int device, ds_forest **out);
 void ds_forest_destroy(ds_forest *forest);
 int ds_forest_predict(ds_forest *forest, const float *rows, int64_t n, float *margins, float *probabilities);
+/* The same for a matrix and outputs that lie in HBM.  Asynchronous on `stream`. */
 int ds_forest_predict_device(ds_forest *forest, const float *d_rows, int64_t n, float *d_margins,
                              float *d_probabilities, void *stream);
 
@@ -750,7 +754,8 @@ int ds_trainer_batch_option(const char *name, int64_t value);
  * anything else positive), both in HBM, n in [1, 2^31).  The negatives' keys are sorted by the radix sort of the cuts;
  * scratch: 4 n bytes of row lists and 8 bytes + 1/8 byte of tables per negative, checked against the free HBM.
  * Enqueued on `stream` and synchronised before returning.  ds_auc does the same for host arrays on `device`.
- * ds_weighted_logloss_device: out = (fixed-point sum, rows) of d_margins[n] with d_labels[n].
+ * ds_weighted_logloss_device: out = (fixed-point sum, rows) of d_margins[n] with d_labels[n]; enqueued on `stream` and
+ * synchronised before returning, like ds_auc_device.
  * For tests: ds_metrics_option("max_blocks", b) caps every grid of the metric kernels that runs over rows at b
  * workgroups, which stride beyond it (0: back to the default; the grids of the sort are one workgroup per tile of keys).
  * The results do not depend on it. */
