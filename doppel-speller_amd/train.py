@@ -748,7 +748,9 @@ def evaluation_error_matrix(model, features, target, threshold=PREDICTION_PROBAB
 
 
 def _error_matrix(probabilities, target, threshold):
-    predicted = probabilities > threshold
+    # train.py:65-66 compares the booster's float32 predictions with a Python float, which NumPy does in float32; a
+    # threshold that arrives as a NumPy float64 must not turn that into a float64 compare
+    predicted = np.asarray(probabilities, dtype=np.float32) > np.float32(threshold)
     actual = np.asarray(target).reshape(-1) != 0
     return (int(np.count_nonzero(predicted & actual)), int(np.count_nonzero(~predicted & ~actual)),
             int(np.count_nonzero(predicted & ~actual)), int(np.count_nonzero(~predicted & actual)))

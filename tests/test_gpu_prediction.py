@@ -1,12 +1,12 @@
-"""Prediction.generate_test_predictions on the GPU against a restatement of the reference's four stages built here from
-the CPU oracle (predict.py:97-113 exact, :140-183 close, :185-254 model, :256-272 finalise)."""
+"""Prediction.generate_test_predictions on the GPU against the restatement of the reference's four stages built from the
+CPU oracle in tests/prediction_restatement.py (predict.py:97-113 exact, :140-183 close, :185-254 model, :256-272
+finalise); tests/test_reference_stages_cpu.py holds that restatement against answers captured from the reference."""
 import numpy as np
-import pandas as pd
 import pytest
 
 import doppel_speller_amd as ds
-from doppel_speller_amd import prediction, synth
-from doppel_speller_amd.match_maker import NativeProblem
+from doppel_speller_amd import synth
+from prediction_restatement import Expected as _Expected
 
 pytestmark = pytest.mark.gpu
 
@@ -29,46 +29,6 @@ def _problem():
     model = ds.ForestModel(forest["feature"], forest["threshold"], forest["yes"], forest["no"], forest["missing"],
                            forest["tree_offsets"], forest["n_features"], forest["base_margin"])
     return truth, np.array(ids, dtype=np.int64), queries, forest, model
-
-
-class _Expected:
-    """The stages restated with the oracle: exact dict, Jaccard top-k, close ratios, remaining pairs, features."""
-
-    def __init__(self, truth, queries, k, oracle):
-        n_truth = len(truth)
-        last = {}
-        for row, title in enumerate(truth):
-            last[title] = row
-        self.exact = np.array([last.get(q, -1) for q in queries], dtype=np.int64)
-        t_chars, t_offsets = prediction._pack(truth)
-        q_chars, q_offsets = prediction._pack(queries)
-        a = NativeProblem.from_flat(t_chars, t_offsets, q_chars, q_offsets, 3).arrays()
-        self.rows = oracle.jaccard_topk(a["rowptr"], a["truth_idx"], a["idf32"], a["sums32"], a["q_rowptr"],
-                                        a["q_cols"], a["q_maxint"], k)
-        t_enc, t_len = ds.encode_titles(truth)
-        q_enc, q_len = ds.encode_titles(queries)
-        t_counts = ds.feature_engineering.truth_word_counts(t_chars, t_offsets, separators=(ord(" "),))
-        pair_q = np.repeat(np.arange(len(queries)), k)
-        pair_t = self.rows.reshape(-1)
-        ratios = oracle.close_ratios(q_len[pair_q], t_len[pair_t], q_enc[pair_q], t_enc[pair_t], ds.SPACE_CODE,
-                                     ds.SORT_KEY, 94)
-        frame = pd.DataFrame({"q": pair_q, "t": pair_t, "ratio": ratios.astype(np.int64)})
-        frame = frame[frame["ratio"] > 94]                                              # predict.py:172
-        frame = frame[frame.groupby("q")["ratio"].transform("max") == frame["ratio"]]    # :173-174
-        frame = frame[~frame["q"].isin(frame.loc[frame["q"].duplicated(), "q"])]        # :176, :158-161
-        self.close = np.full(len(queries), -1, dtype=np.int64)
-        self.close[frame["q"].to_numpy()] = frame["t"].to_numpy()
-        best = np.where(self.exact >= 0, self.exact, self.close)
-        self.pair_q, self.pair_t = oracle.remaining_pairs(best, self.rows)
-        self.features = oracle.construct_features(q_len[self.pair_q], t_len[self.pair_t], q_enc[self.pair_q],
-                                                  t_enc[self.pair_t], t_counts[self.pair_t], ds.SPACE_CODE, n_truth)
-        self.k, self.n = k, len(queries)
-
-    def model_rows(self, probabilities, threshold, oracle):
-        match_q, match_t = oracle.select_matches(self.pair_q, self.pair_t, probabilities, self.k, threshold)
-        out = np.full(self.n, -1, dtype=np.int64)
-        out[match_q] = match_t
-        return out
 
 
 @pytest.fixture(scope="module")
