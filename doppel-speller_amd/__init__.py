@@ -13,7 +13,10 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
             miss of the model); closest_search_single_title(title, exhaustive=True) answers from it
         .evaluate(titles, actual_title_ids)   -> the counts of get-predictions-accuracy (cli.py) and custom_error
         .threshold_sweep(titles, actual_title_ids, levenshtein_thresholds, probability_thresholds)   -> those counts
-            for every pair of the two thresholds, from one scoring pass (this project's own)
+            for every pair of the two thresholds, from one scoring pass (this project's own); with n_boot=, groups=,
+            seed= also `sweep_bootstrap` (SweepBootstrap): every cell under one paired bootstrap of the titles, resampled
+            on the device: frame() with an interval and share_best per cell, against(cell), best();
+            validate_sweep_bootstrap(...) says what is accepted
         .duplicate_groups(levenshtein_threshold, probability_threshold)   -> the groups of truth titles that are
             duplicates of each other: the connected components of the exact, close and model links among the truth
             set's own rows, found on the device (this project's own)
@@ -112,8 +115,9 @@ from .train import (ForestTrainer, TrainModelResult, auc_counts, compute_cuts, c
                     validate_monotone_constraints, validate_sample_weight)
 from .tuning import (CrossValidation, ForestTrainerBatch, cross_validate, fold_assignment, parameter_grid,  # noqa: F401
                      select_parameters, tune_model_parameters)
-from .bootstrap import (BootstrapCounts, ErrorBootstrap, ErrorDifference, bootstrap_accuracy, bootstrap_counts,  # noqa: F401
-                        compare_models, compare_models_device, validate_bootstrap)
+from .bootstrap import (BootstrapCounts, ErrorBootstrap, ErrorDifference, SweepBootstrap, bootstrap_accuracy,  # noqa: F401
+                        bootstrap_counts, compare_models, compare_models_device, validate_bootstrap,
+                        validate_sweep_bootstrap)
 from .calibration import (Calibrator, IsotonicFit, ReliabilityReport, fit_isotonic, fit_isotonic_device,  # noqa: F401
                           reliability, reliability_device, validate_calibration)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -156,6 +156,8 @@ def _declare(handle):
         "ds_close_parts_device": [p, p, p, c.c_int64, c.c_int32, c.c_int64, c.c_uint8, p, c.c_int32, c.c_int32, p, p, p, p],
         "ds_threshold_sweep_device": [p, p, p, p, p, p, p, c.c_int64, c.c_int32, p, c.c_int32, p, c.c_int32, p, p],
         "ds_sweep_option": [c.c_char_p, c.c_int64],
+        "ds_sweep_records_device": [p, p, p, p, p, p, p, c.c_int64, c.c_int32, p, c.c_int32, p, c.c_int32, p],
+        "ds_sweep_bootstrap_device": [p, c.c_int64, c.c_int32, c.c_int32, p, c.c_int64, c.c_int32, c.c_uint64, p, p],
         "ds_duplicate_begin_device": [p, c.c_int64, p, p],
         "ds_duplicate_links_device": [p, p, p, p, c.c_int64, c.c_int64, c.c_int32, c.c_int64, c.c_int32, c.c_float, p, p, p, p],
         "ds_duplicate_finish_device": [p, c.c_int64, p, p, p],
@@ -306,7 +308,7 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_batch_set_monotone", "ds_forest_inspect_device", "ds_forest_inspect", "ds_forest_refresh",
     "ds_forest_refresh_device", "ds_bootstrap_counts_device", "ds_bootstrap_counts", "ds_bootstrap_option",
     "ds_outcome_codes_device", "ds_isotonic_fit_device", "ds_isotonic_fit", "ds_calibration_apply_device",
-    "ds_reliability_device", "ds_calibrate_option")
+    "ds_reliability_device", "ds_calibrate_option", "ds_sweep_records_device", "ds_sweep_bootstrap_device")
 
 
 def lib():

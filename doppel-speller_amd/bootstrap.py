@@ -206,6 +206,134 @@ class ErrorBootstrap:
         return pd.DataFrame(columns)
 
 
+SWEEP_CELLS_MAX = 1 << 25                          # n_boot x T x U at most: 32 bytes each, 1 GiB of counts
+SWEEP_LEVENSHTEIN_MAX, SWEEP_PROBABILITY_MAX = 101, 256
+
+
+def validate_sweep_bootstrap(n_boot=0, seed=0, groups=None, n_titles=0, n_levenshtein=1, n_probability=1):
+    """The checks of threshold_sweep's bootstrap arguments, made without the library -> dict(n_boot, seed, unit,
+    n_units).  n_boot in [0, 65536] (0: no bootstrap); seed in [0, 2^63); groups: None, or a 1-D integer or string
+    array with one value per title (`unit`: their dense numbers in order of first appearance; None: every title its own
+    unit, n_units = n_titles); n_titles below 2^31; a grid of 1..101 x 1..256 thresholds with n_boot x T x U <= 2^25,
+    which keeps the counts (int64[n_boot, T, U, 4], 32 bytes per replicate and cell) at 1 GiB at most."""
+    n_boot = _whole("n_boot", n_boot, 0, BOOT_MAX)
+    seed = _whole("seed", seed, 0, (1 << 63) - 1)
+    n_titles = _whole("n_titles", n_titles, 0, ROWS_MAX - 1)
+    T = _whole("n_levenshtein", n_levenshtein, 1, SWEEP_LEVENSHTEIN_MAX)
+    U = _whole("n_probability", n_probability, 1, SWEEP_PROBABILITY_MAX)
+    if n_boot * T * U > SWEEP_CELLS_MAX:
+        raise ValueError(f"n_boot x T x U = {n_boot} x {T} x {U} = {n_boot * T * U} is above 2^25 = {SWEEP_CELLS_MAX}: "
+                         f"the counts take 32 bytes per replicate and cell, {32 * n_boot * T * U} bytes here, and 1 GiB "
+                         f"(2^25 x 32) is the most")
+    try:
+        v = validate_bootstrap(groups=groups, n=n_titles)
+    except ValueError as error:
+        raise ValueError(str(error).replace("per row", "per title")) from None
+    return dict(n_boot=n_boot, seed=seed, unit=v["unit"], n_units=v["n_units"])
+
+
+class SweepBootstrap(ErrorBootstrap):
+    """The cells of a threshold sweep under one paired bootstrap of the titles (Prediction.threshold_sweep with
+    n_boot > 0; ds_sweep_bootstrap_device): an ErrorBootstrap whose sets are the T x U cells in the frame's order (cell
+    = t index x U + u index), with codes = ACCURACY_CODES, weight = 5 and names "t/u".  counts int64[n_boot, T, U, 4]
+    and baseline int64[T, U, 4] as the device returns them.  levenshtein_thresholds int64[T] and probability_thresholds
+    float64[U] are the shown values; `reference` is the (levenshtein_threshold, probability_threshold) of the
+    Prediction that made it, the default cell of `against` when the grid holds it.  share_best float64[C]: the share of
+    replicates in which the cell has the smallest error, a replicate's win divided equally among the cells that tie for
+    it (sums to 1)."""
+
+    def __init__(self, counts, baseline, levenshtein_thresholds, probability_thresholds, n_units=0, seed=0,
+                 reference=None):
+        self.levenshtein_thresholds = np.asarray(levenshtein_thresholds, dtype=np.int64).reshape(-1)
+        self.probability_thresholds = np.asarray(probability_thresholds, dtype=np.float64).reshape(-1)
+        T, U = self.levenshtein_thresholds.shape[0], self.probability_thresholds.shape[0]
+        counts = np.asarray(counts, dtype=np.int64)
+        names = [f"{int(t)}/{float(u)!r}" for t in self.levenshtein_thresholds for u in self.probability_thresholds]
+        super().__init__(counts.reshape(counts.shape[0], T * U, 4), np.asarray(baseline, dtype=np.int64).reshape(T * U, 4),
+                         ACCURACY_WEIGHT, names, n_units, seed, ACCURACY_CODES)
+        self.reference = None if reference is None else (int(reference[0]), float(reference[1]))
+        smallest = self.errors.min(axis=1, keepdims=True)
+        ties = self.errors == smallest
+        self.share_best = (ties / ties.sum(axis=1, keepdims=True)).sum(axis=0) / self.n_boot
+
+    def cell(self, levenshtein_threshold, probability_threshold):
+        """The position of cell (t, u); u is compared as float32, like probability_threshold."""
+        t_at = np.flatnonzero(self.levenshtein_thresholds == levenshtein_threshold)
+        with np.errstate(over="ignore"):
+            u_at = np.flatnonzero(self.probability_thresholds.astype(np.float32) == np.float32(probability_threshold))
+        if t_at.shape[0] == 0 or u_at.shape[0] == 0:
+            raise ValueError(f"the grid has no cell ({levenshtein_threshold!r}, {probability_threshold!r})")
+        return int(t_at[0]) * self.probability_thresholds.shape[0] + int(u_at[0])
+
+    def best(self):
+        """The cell with the smallest baseline error; the earlier cell wins a tie."""
+        return int(np.argmin(self.baseline_errors))
+
+    def _reference_cell(self, cell):
+        if cell is None:
+            try:
+                return self.best() if self.reference is None else self.cell(*self.reference)
+            except ValueError:
+                return self.best()
+        if isinstance(cell, tuple):
+            return self.cell(*cell)
+        return self.index(cell)
+
+    def _grid_columns(self):
+        U = self.probability_thresholds.shape[0]
+        return {"levenshtein_threshold": np.repeat(self.levenshtein_thresholds, U),
+                "probability_threshold": np.tile(self.probability_thresholds, self.levenshtein_thresholds.shape[0])}
+
+    def against(self, cell=None, level=0.95):
+        """Every cell against one reference cell, replicate by replicate: a DataFrame with one line per cell
+        [levenshtein_threshold, probability_threshold, baseline, mean, low, high, share_better], the fields of
+        difference(c, cell, level) (negative: the line's cell is better).  cell: a position, a name, a (t, u) pair, or
+        None: the instance's own thresholds when the grid holds them, else best()."""
+        import pandas as pd
+        reference, level = self._reference_cell(cell), _real("level", level, 0.0, 1.0)
+        d = self.errors - self.errors[:, reference:reference + 1]
+        low, high = np.quantile(d, [(1 - level) / 2, (1 + level) / 2], axis=0)
+        columns = self._grid_columns()
+        columns.update(baseline=self.baseline_errors - self.baseline_errors[reference], mean=d.mean(axis=0), low=low,
+                       high=high, share_better=(np.count_nonzero(d < 0, axis=0) + 0.5 * np.count_nonzero(d == 0, axis=0))
+                       / self.n_boot)
+        return pd.DataFrame(columns)
+
+    def frame(self, level=0.95):
+        """The sweep's frame (prediction.SWEEP_COLUMNS, from the baseline counts) with mean_error, standard_error, low
+        and high of interval(level), and share_best."""
+        import pandas as pd
+        from .prediction import SWEEP_COLUMNS
+        bounds = self.interval(level)
+        columns = self._grid_columns()
+        for name in SWEEP_COLUMNS[2:6]:
+            columns[name] = self.baseline_counts[:, ACCURACY_CODES.index(name)]
+        columns["custom_error"] = self.baseline_counts[:, 2] + 5 * self.baseline_counts[:, 1]
+        columns.update(mean_error=self.errors.mean(axis=0), standard_error=self.standard_error, low=bounds[:, 0],
+                       high=bounds[:, 1], share_best=self.share_best)
+        return pd.DataFrame(columns)
+
+
+def sweep_bootstrap_device(d_records, n, levenshtein_thresholds, probability_thresholds, unit, n_units, n_boot, seed,
+                           device=0, reference=None):
+    """The one call of ds_sweep_bootstrap_device -> SweepBootstrap.  d_records: uint16[n, T] in HBM as
+    CandidatePipeline.enqueue_sweep_records fills it; unit: int32[n] on the host or None; the arguments have passed
+    validate_sweep_bootstrap with n_boot > 0.  The counts come back once."""
+    T, U = len(levenshtein_thresholds), len(probability_thresholds)
+    held = [_lib.DeviceArray((n_boot, T, U, 4), np.int64, device), _lib.DeviceArray((T, U, 4), np.int64, device)]
+    try:
+        if unit is not None and n:
+            held.append(_lib.DeviceArray.from_host(unit, device))
+        _lib.check(_lib.lib().ds_sweep_bootstrap_device(
+            _lib.pointer(d_records if n else None), n, T, U, _lib.pointer(held[2] if len(held) > 2 else None),
+            n_units, n_boot, seed, held[0].ptr, held[1].ptr), "ds_sweep_bootstrap_device")
+        return SweepBootstrap(held[0].to_host(), held[1].to_host(), levenshtein_thresholds, probability_thresholds,
+                              n_units, seed, reference)
+    finally:
+        for array in held:
+            array.free()
+
+
 def bootstrap_counts(codes, groups=None, n_boot=2000, seed=0):
     """The outcome counts of every bootstrap replicate, resampled on the device (ds_bootstrap_counts) ->
     BootstrapCounts.  codes: integer [M, n], the outcome class 0..3 of row i under prediction set m; groups: the

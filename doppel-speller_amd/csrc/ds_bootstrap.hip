@@ -19,6 +19,7 @@
 // kBootstrapChunk = 2^14, so no field carries into the next.  The partials are summed over the wave (ds_wave.h) and one
 // lane adds each non-zero counter to the int64 output: one integer atomic per counter and wave.  Replicate B of the grid
 // draws j = k: it is the baseline.  Integer sums throughout, so no bit depends on the grid, the chunking or the order.
+#include "ds_bootstrap_draw.h"
 #include "ds_train.h"
 #include "ds_wave.h"
 
@@ -90,10 +91,7 @@ __global__ __launch_bounds__(kBootstrapCheckThreads) void ds_bootstrap_check_ker
 // ---- the resampling ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int64_t bootstrap_draw(const BootstrapArgs &a, int32_t b, int64_t k)
 {
-    if (b == a.n_boot) return k;   // the baseline: every unit once
-    const uint64_t x = sample_key(a.seed, DS_BOOTSTRAP_PURPOSE_DRAW,
-                                  (static_cast<uint64_t>(b) << 32) | static_cast<uint64_t>(k));
-    return static_cast<int64_t>(__umul64hi(x, static_cast<uint64_t>(a.n_units)));
+    return bootstrap_unit(a.seed, b, a.n_boot, k, a.n_units);   // replicate n_boot is the baseline: every unit once
 }
 
 __device__ __forceinline__ void bootstrap_add(unsigned long long *out, unsigned long long value)

@@ -299,6 +299,19 @@ class CandidatePipeline:
             _lib.pointer(actual_rows), self.n_queries, self.k, _lib.pointer(lev), lev.shape[0], _lib.pointer(prob),
             prob.shape[0], _lib.pointer(counts), _lib.pointer(stream)), "ds_threshold_sweep_device")
 
+    def enqueue_sweep_records(self, actual_rows, lev, prob, records):
+        """What the decision rule leaves of every query of this chunk at every Levenshtein threshold, for all probability
+        thresholds at once (ds_sweep_records_device; the encoding is in include/doppel_amd.h), over the buffers that
+        `enqueue_threshold_sweep` reads.  actual_rows, lev and prob as there; records: uint16[Q * T] in HBM, the place
+        of this chunk's first query (a DeviceArray, a c_void_p or an address).  On the null stream, like every stage
+        of Prediction."""
+        if self._parts is None:
+            raise ValueError("enqueue_close_parts comes first")
+        _lib.check(_lib.lib().ds_sweep_records_device(
+            self.rows_ptr, *(a.ptr for a in self._parts), self._predictions.ptr, self._exact.ptr,
+            _lib.pointer(actual_rows), self.n_queries, self.k, _lib.pointer(lev), lev.shape[0], _lib.pointer(prob),
+            prob.shape[0], _lib.pointer(records)), "ds_sweep_records_device")
+
     def enqueue_duplicate_links(self, parent, counts, levenshtein_threshold, probability_threshold, use_model,
                                 reasons=False, stream=None):
         """The links among this chunk's rows and their candidates joined into the union-find forest `parent`

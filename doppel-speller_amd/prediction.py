@@ -709,6 +709,7 @@ class Prediction:
         self.explained_features = None
         self.assignment = None
         self.assignment_counts = None
+        self.sweep_bootstrap = None
         self.timings = {}
 
         self.truth_titles = transform_or_keep(truth_titles, transform)
@@ -955,7 +956,7 @@ class Prediction:
                              self.truth_title_ids, calibrated=calibrated)
 
     def threshold_sweep(self, titles, actual_title_ids, levenshtein_thresholds=None, probability_thresholds=None,
-                        test_index=None):
+                        test_index=None, *, n_boot=0, groups=None, seed=0):
         """How the answers of generate_test_predictions(titles) would compare with `actual_title_ids` at every pair of
         (levenshtein_threshold, probability_threshold): a DataFrame in long form [levenshtein_threshold,
         probability_threshold, correctly_matched, incorrectly_matched, correctly_not_found, incorrectly_not_found,
@@ -967,17 +968,31 @@ class Prediction:
         compared as float32 like probability_threshold.  Every pair is scored once, whatever the grid: top-k, the close
         ratio taken apart (CandidatePipeline.enqueue_close_parts), the exact stage, features and forest on all pairs;
         then one kernel replays the decision rule for every cell and counts (enqueue_threshold_sweep).  The counters
-        stay on the device between the chunks and come back once.  `details` and `candidates` are left alone."""
+        stay on the device between the chunks and come back once.  `details` and `candidates` are left alone.
+
+        n_boot > 0 adds the paired bootstrap of every cell (bootstrap.SweepBootstrap in `sweep_bootstrap`, None
+        otherwise; the returned frame is the same): is the best cell really better than the next one, or than the
+        defaults?  Next to the counters every chunk writes one 16-bit record per (title, Levenshtein threshold)
+        (enqueue_sweep_records, stage "sweep_records") into one buffer of n x T x 2 bytes in HBM, and after the last
+        chunk one call resamples the titles n_boot times for all cells at once (ds_sweep_bootstrap_device, stage
+        "sweep_bootstrap").  groups: one value per title; titles that share one are drawn together (None: every title
+        on its own).  seed: the draws are a closed-form function of it.  bootstrap.validate_sweep_bootstrap says what
+        is accepted."""
+        from . import bootstrap
         titles = list(titles)
         validate_queries(titles, test_index)
         lev, prob, shown, actual_row = validate_sweep(
             [self.levenshtein_threshold] if levenshtein_thresholds is None else levenshtein_thresholds,
             [self.probability_threshold] if probability_thresholds is None else probability_thresholds,
             actual_title_ids, self.truth_title_ids, len(titles))
+        boot = bootstrap.validate_sweep_bootstrap(n_boot, seed, groups, len(titles), lev.shape[0], prob.shape[0])
+        self.sweep_bootstrap = None
         timings = dict.fromkeys(("host_prepare", "top_k", "close_parts", "exact_matches", "features", "model", "sweep",
                                  "copy_back"), 0.0)
+        if boot["n_boot"]:
+            timings.update(sweep_records=0.0, sweep_bootstrap=0.0)
         counts = np.zeros(lev.shape[0] * prob.shape[0] * 4, dtype=np.int64)
-        grid = None
+        grid = records = None
         for pipeline, clock in self._chunks(titles, timings, parts=True):
             if grid is None:
                 grid = (_lib.DeviceArray.from_host(lev, self.device), _lib.DeviceArray.from_host(prob, self.device),
@@ -988,17 +1003,33 @@ class Prediction:
             # synchronises once, to check the grid's values)
             self._score_chunk(pipeline, clock, parts=(int(lev[0]), int(lev[-1])))
             clock.device("sweep", lambda: pipeline.enqueue_threshold_sweep(actual, *grid))
+            if boot["n_boot"]:
+                if records is None:
+                    records = _lib.DeviceArray((len(titles), lev.shape[0]), np.uint16, self.device)
+                here = ctypes.c_void_p(records.ptr.value + pipeline.q_first * lev.shape[0] * 2)
+                clock.device("sweep_records", lambda: pipeline.enqueue_sweep_records(actual, grid[0], grid[1], here))
             clock.collect()
+        if boot["n_boot"]:
+            # one call for all cells; it returns with its counts read back, so the wall clock holds the stage
+            started = time.perf_counter()
+            self.sweep_bootstrap = bootstrap.sweep_bootstrap_device(
+                records, len(titles), lev, shown, boot["unit"], boot["n_units"], boot["n_boot"], boot["seed"], self.device,
+                (self.levenshtein_threshold, self.probability_threshold))
+            timings["sweep_bootstrap"] = (time.perf_counter() - started) * 1000.0
+            if records is not None:
+                records.free()
         if grid is not None:
             with clock.host("copy_back"):
                 counts = grid[2].to_host()            # synchronises the null stream the stages ran on
         self.timings = timings
         return sweep_frame(lev, shown, counts)
 
-    def evaluate(self, titles, actual_title_ids, test_index=None):
+    def evaluate(self, titles, actual_title_ids, test_index=None, *, n_boot=0, groups=None, seed=0):
         """The accuracy of generate_test_predictions(titles) against `actual_title_ids` at this instance's thresholds,
-        as `predictions_accuracy` reports it: the one cell of `threshold_sweep`."""
-        line = self.threshold_sweep(titles, actual_title_ids, test_index=test_index).iloc[0]
+        as `predictions_accuracy` reports it: the one cell of `threshold_sweep`.  n_boot, groups and seed are passed on:
+        with n_boot > 0 `sweep_bootstrap` holds that cell's bootstrap (its interval(level) is the error's interval)."""
+        line = self.threshold_sweep(titles, actual_title_ids, test_index=test_index, n_boot=n_boot, groups=groups,
+                                    seed=seed).iloc[0]
         return {name: int(line[name]) for name in ACCURACY_KEYS}
 
     def duplicate_groups(self, levenshtein_threshold=None, probability_threshold=None, model_links=True,

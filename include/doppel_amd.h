@@ -321,6 +321,46 @@ int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const u
                               int32_t U, int64_t *d_counts, void *stream);
 int ds_sweep_option(const char *name, int64_t value);
 
+/* ---- sweep records and the paired bootstrap of every cell ("Bootstrap of the cells") ------------
+ * ds_sweep_records_device: the inputs, the argument checks and the read-back check of the grid of
+ * ds_threshold_sweep_device, but nothing is counted: d_records[q * T + i] (uint16, a query's T records contiguous) holds
+ * what the rule leaves of query q at threshold d_lev[i] for EVERY u.  The encoding is the contract between this kernel,
+ * ds_sweep_bootstrap_device and the tests' oracle:
+ *   bits 0..2   0..3: the same outcome in every cell, in the numbering of bootstrap.ACCURACY_CODES (0 correctly not
+ *               found, 1 incorrectly matched, 2 incorrectly not found, 3 correctly matched);
+ *               4: no actual row        outcome 1 at the cells u < pos, 0 from pos on;
+ *               5: the model's row is the actual one      3 below pos, 2 from pos on;
+ *               6: the model's row is another one         1 below pos, 2 from pos on;
+ *               7 never occurs;
+ *   bits 3..15  pos for 4, 5 and 6 (the number of d_prob values below the model's maximum), 0 for 0..3.  A flip whose
+ *               pos is U has the same outcome in every cell and is written as that outcome (1 or 3), so a record is a
+ *               function of the U outcomes alone and this kernel writes pos in 1..U - 1.
+ * No stream parameter: the kernel is enqueued on the null stream, where every stage of Prediction runs, and the call
+ * synchronises that stream once, for the grid check.  n_queries == 0 launches nothing.
+ *
+ * ds_sweep_bootstrap_device: the outcome counts of every cell under a paired bootstrap of the n titles by unit.
+ * d_records: uint16[n][T] as above; d_unit: int32[n], the unit of every title in [0, n_units), or null: every title its
+ * own unit, n_units == n.  Replicate b draws n_units units, draw k the unit
+ *   j(b, k) = (x * n_units) >> 64, x = the first kept output of the stream of (seed, DS_BOOTSTRAP_PURPOSE_DRAW, (b << 32) | k),
+ * exactly the draw of ds_bootstrap_counts_device, and a drawn unit adds all its titles (a unit without titles adds
+ * nothing); the baseline takes every unit once.  d_counts: int64[n_boot][T][U][4], d_baseline: int64[T][U][4], the four
+ * classes in the numbering above; every element is written (nothing is added to), so the caller need not zero them.
+ * So d_counts[b][i][j] is what ds_bootstrap_counts_device gives for the outcome codes of cell (i, j), bit for bit.
+ * Limits: n < 2^31, n_boot in 1..65536, T <= 101, U <= 256, and n_units x the largest unit < 2^32 (what one replicate
+ * can add to a 32-bit counter).  DS_E_ARG with d_counts and d_baseline untouched for these, for a record with low bits 7,
+ * with a pos other than 0 on 0..3 or outside 1..U on 4..6, and for a unit outside [0, n_units).
+ * No stream parameter: everything is enqueued on the null stream.  The call synchronises it once for the error counters
+ * of its check kernel and, with units, once more at the end, because the member lists it built are freed on return.
+ * ds_sweep_option, for tests, no result depends on them: "bootstrap_tile" = thresholds per wave (0: what 16 KiB of LDS
+ * per wave hold, 64 at the most), "bootstrap_max_blocks" = cap of the grid (0: 4096), "bootstrap_replicates_per_group" =
+ * replicates per workgroup (0: 4). */
+int ds_sweep_records_device(const int32_t *d_rows, const uint8_t *d_d, const uint8_t *d_r, const uint8_t *d_s,
+                            const float *d_predictions, const int32_t *d_exact, const int32_t *d_actual_row,
+                            int64_t n_queries, int32_t k, const int32_t *d_lev, int32_t T, const float *d_prob, int32_t U,
+                            uint16_t *d_records);
+int ds_sweep_bootstrap_device(const uint16_t *d_records, int64_t n, int32_t T, int32_t U, const int32_t *d_unit,
+                              int64_t n_units, int32_t n_boot, uint64_t seed, int64_t *d_counts, int64_t *d_baseline);
+
 /* ---- duplicate groups: the connected components of the truth set under its own links -----------
  * The project's own stage: the truth table is its own query table, the stages above score every row against its k
  * candidates, and the rows that score as one entity are joined into groups.  The state is a union-find forest
