@@ -91,6 +91,14 @@ Public surface (mirrors the reference, doppelspeller/match_maker.py and doppelsp
         reliability(probabilities, target, n_bins) -> ReliabilityReport (counts, frame(), ece, mce, brier);
         validate_calibration(...) says what is accepted (this project's own)
     generate_misspelled_names(titles, seed)   -> generate_misspelled_name of every title (feature_engineering_prepare.py)
+    edit_operations(truth_titles, titles)   -> which characters differ between a title and its match: the edit script of
+        every pair (EditScripts: distance, ops, lengths, frame(), render(i)), aligned on the device one wave per pair;
+        fit_misspelling_profile(truth_titles, titles, max_edits=4), FeatureEngineering.fit_misspelling_profile()   -> what
+        kinds of errors labelled pairs hold (MisspellingProfile: edits_per_title(), operation_shares(), keyboard_share(),
+        frame(), merged(), save() / load()); generate_misspelled_names(..., profile=p), FeatureEngineering(...,
+        misspelling_profile=p), train_model / tune_model_parameters / refresh_model(..., misspelling_profile=p or "fit")
+        -> generated rows that follow the data's own error model; validate_misspelling_profile(p) says what is accepted
+        (this project's own)
 
 All arithmetic runs in hand-written HIP kernels (csrc/*.hip -> libdoppel_amd.so, C ABI in include/doppel_amd.h);
 there is no CPU fallback -- importing works without the library, calling anything that computes does not.
@@ -120,4 +128,6 @@ from .bootstrap import (BootstrapCounts, ErrorBootstrap, ErrorDifference, SweepB
                         validate_sweep_bootstrap)
 from .calibration import (Calibrator, IsotonicFit, ReliabilityReport, fit_isotonic, fit_isotonic_device,  # noqa: F401
                           reliability, reliability_device, validate_calibration)
+from .edits import (EditScripts, MisspellingProfile, edit_operations, fit_misspelling_profile,  # noqa: F401
+                    validate_misspelling_profile)
 from .text import transform_title, transform_titles  # noqa: F401

@@ -11,7 +11,7 @@ _SOURCES = ("ds_runtime.hip", "ds_jaccard.hip", "ds_jaccard_wide.hip", "ds_jacca
             "ds_build.hip", "ds_forest.hip", "ds_pairs.hip", "ds_exact.hip", "ds_train.hip", "ds_train_batch.hip",
             "ds_training.hip", "ds_queries.hip", "ds_cuts.hip", "ds_rank.hip", "ds_exhaustive.hip", "ds_sweep.hip",
             "ds_duplicates.hip", "ds_contributions.hip", "ds_metrics.hip", "ds_index_build.hip", "ds_assign.hip",
-            "ds_hard.hip", "ds_inspect.hip", "ds_refresh.hip", "ds_bootstrap.hip", "ds_calibrate.hip")
+            "ds_hard.hip", "ds_inspect.hip", "ds_refresh.hip", "ds_bootstrap.hip", "ds_calibrate.hip", "ds_edits.hip")
 _lib = None
 
 
@@ -237,6 +237,9 @@ def _declare(handle):
         "ds_trainer_batch_seed_device": [p, p, p, p, p],
         "ds_misspell_titles": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_titles_read": [p, p, p],
+        "ds_edit_align": [p, p, p, p, c.c_int64, c.c_int32, p, p, p, p],
+        "ds_edit_option": [c.c_char_p, c.c_int64],
+        "ds_misspell_titles_profile": [p, p, c.c_int64, c.c_uint64, p, c.POINTER(p)],
         "ds_training_pairs_device": [p, c.c_int64, c.c_int32, c.c_int32, p, p, c.c_uint64, c.c_int64, p, p, p, p],
         "ds_hard_negatives_device": [p, p, c.c_int64, c.c_int32, c.c_int64, p, p, c.c_int32, c.c_int32, c.c_float, c.c_int64,
                                      p, p, c.c_int64, p, p, p, p, p],
@@ -308,7 +311,8 @@ EXPORTED_SYMBOLS = (
     "ds_trainer_batch_set_monotone", "ds_forest_inspect_device", "ds_forest_inspect", "ds_forest_refresh",
     "ds_forest_refresh_device", "ds_bootstrap_counts_device", "ds_bootstrap_counts", "ds_bootstrap_option",
     "ds_outcome_codes_device", "ds_isotonic_fit_device", "ds_isotonic_fit", "ds_calibration_apply_device",
-    "ds_reliability_device", "ds_calibrate_option", "ds_sweep_records_device", "ds_sweep_bootstrap_device")
+    "ds_reliability_device", "ds_calibrate_option", "ds_sweep_records_device", "ds_sweep_bootstrap_device",
+    "ds_edit_align", "ds_edit_option", "ds_misspell_titles_profile")
 
 
 def lib():

@@ -18,32 +18,11 @@
 // lane; a title grows to at most 257 characters before the cut); the block writes its finished rows (stride 255) with
 // coalesced dword stores at the end.  ds_training_pairs_device: one lane per train row; the partial Fisher-Yates keeps
 // only the displaced positions (at most 16) in registers, never the top_n-slot pool.
-#include "ds_common.h"
+#include "ds_title_ops.h"
 
 namespace ds {
 
-constexpr int kMisspellBlock = 64;            // one wave per workgroup: 64 lanes x 528 bytes of LDS
-constexpr int kWorkBytes = 264;               // >= 255 + 2 insertions
 constexpr int kMaxSample = 16;
-constexpr uint8_t kSpaceCode = 1, kZeroCode = 28, kLastCode = 37;
-
-struct Rng {
-    uint64_t state;
-    __device__ Rng(uint64_t seed, uint64_t purpose, uint64_t index)
-    {
-        state = seed * 0x9e3779b97f4a7c15ull + index * 0xd1342543de82ef95ull + purpose * 0xaf251af3b0f025b5ull;
-        next();
-        next();
-    }
-    __device__ uint64_t next()
-    {
-        uint64_t z = (state += 0x9e3779b97f4a7c15ull);
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        return z ^ (z >> 31);
-    }
-    __device__ int below(int n) { return static_cast<int>(__umul64hi(next(), static_cast<uint64_t>(n))); }
-};
 
 // KEYBOARD_CARTESIAN (feature_engineering_prepare.py:14-23) per letter code 2..27 ('a'..'z'): x, y
 __constant__ int8_t kKeyX[26] = {0, 4, 2, 2, 2, 3, 4, 5, 7, 6, 7, 8, 5, 5, 8, 9, 0, 3, 1, 4, 6, 3, 1, 1, 5, 0};
@@ -68,19 +47,6 @@ __device__ uint8_t draw_neighbour(Rng &rng, uint8_t code)
 }
 
 __device__ inline bool space_or_digit(uint8_t code) { return code == kSpaceCode || code >= kZeroCode; }
-
-__device__ inline void erase_at(uint8_t *w, int &length, int at)
-{
-    for (int c = at; c < length - 1; ++c) w[c] = w[c + 1];
-    --length;
-}
-
-__device__ inline void insert_at(uint8_t *w, int &length, int at, uint8_t code)
-{
-    for (int c = length; c > at; --c) w[c] = w[c - 1];
-    w[at] = code;
-    ++length;
-}
 
 // the index of a letter the retry loops of remove_letter / add_letter / replace_letter accept (:91-99, :104-112,
 // :118-126), -1 after the 11th rejected draw ("return x")
@@ -165,29 +131,6 @@ __device__ void apply_edit(Rng &rng, int edit, uint8_t *w, uint8_t *t, int &leng
     }
 }
 
-// transform_title (common.py:28-38) from w into t: collapse runs of spaces, strip, cut to 255, strip, '0'-pad to 3;
-// t is zero-filled to 255
-__device__ int transform_into(const uint8_t *w, int length, uint8_t *t)
-{
-    int out = 0;
-    for (int c = 0; c < length; ++c) {
-        if (w[c] == kSpaceCode && (out == 0 || t[out - 1] == kSpaceCode)) continue;
-        t[out++] = w[c];
-    }
-    while (out > 0 && t[out - 1] == kSpaceCode) --out;
-    const int characters = out;
-    if (out > DS_MAX_CHARS) out = DS_MAX_CHARS;
-    while (out > 0 && t[out - 1] == kSpaceCode) --out;
-    if (characters < 3) {
-        const int pad = 3 - out;
-        for (int c = out - 1; c >= 0; --c) t[c + pad] = t[c];
-        for (int c = 0; c < pad; ++c) t[c] = kZeroCode;
-        out = 3;
-    }
-    for (int c = out; c < DS_MAX_CHARS; ++c) t[c] = 0;
-    return out;
-}
-
 // generate_misspelled_name (:165-173) of the title in w; the result (transformed) in t
 __device__ int misspell(Rng &rng, uint8_t *w, uint8_t *t, int length)
 {
@@ -247,21 +190,7 @@ __global__ __launch_bounds__(kMisspellBlock) void ds_misspell_kernel(
         out_len[i] = static_cast<uint8_t>(length);
     }
     __syncthreads();
-    // the block's rows are contiguous in the output: n_rows * 255 bytes from first * 255
-    const int64_t n_rows = n - first < kMisspellBlock ? n - first : kMisspellBlock;
-    uint8_t *out = out_enc + first * DS_MAX_CHARS;
-    if (n_rows == kMisspellBlock) {   // 16320 bytes = 4080 dwords, 4-byte aligned (first is a multiple of 64)
-        for (int d = lane; d < kMisspellBlock * DS_MAX_CHARS / 4; d += kMisspellBlock) {
-            uint32_t value = 0;
-            for (int b = 0; b < 4; ++b) {
-                const int o = 4 * d + b;
-                value |= static_cast<uint32_t>(scratch[o / DS_MAX_CHARS][o % DS_MAX_CHARS]) << (8 * b);
-            }
-            reinterpret_cast<uint32_t *>(out)[d] = value;
-        }
-    } else {
-        for (int o = lane; o < n_rows * DS_MAX_CHARS; o += kMisspellBlock) out[o] = scratch[o / DS_MAX_CHARS][o % DS_MAX_CHARS];
-    }
+    write_title_rows(scratch, first, n, out_enc);
 }
 
 __global__ void ds_training_pairs_kernel(const int32_t *rows, int64_t n, int32_t top_n, int32_t sample_n,

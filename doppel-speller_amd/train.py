@@ -769,11 +769,12 @@ class TrainModelResult:
     `error_bootstrap`, the ErrorBootstrap of the model (and of the init model) on the evaluation set (None otherwise).
     With calibrate=True: `calibrator`, the Calibrator of the model's probability on the evaluation set, `reliability`,
     the ReliabilityReport of the raw probability there, and `calibrated_reliability`, that of the calibrated value (all
-    three None otherwise)."""
+    three None otherwise).  With misspelling_profile: `misspelling_profile`, the MisspellingProfile the generated rows
+    followed (the fitted one for "fit"; None otherwise)."""
 
     def __init__(self, model, feature_importance, error_matrix, best_iteration, history, rows, timings,
                  metrics_history=None, initial_error=None, permutation_importance=None, error_bootstrap=None,
-                 calibrator=None, reliability=None, calibrated_reliability=None):
+                 calibrator=None, reliability=None, calibrated_reliability=None, misspelling_profile=None):
         self.model, self.feature_importance, self.error_matrix = model, feature_importance, error_matrix
         self.best_iteration, self.history, self.rows, self.timings = best_iteration, history, rows, timings
         self.metrics_history = metrics_history
@@ -781,19 +782,21 @@ class TrainModelResult:
         self.permutation_importance = permutation_importance
         self.error_bootstrap = error_bootstrap
         self.calibrator, self.reliability, self.calibrated_reliability = calibrator, reliability, calibrated_reliability
+        self.misspelling_profile = misspelling_profile
 
 
 def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, model, top_n=100, sample_n=10, seed=0,
                   device=0, transform=True, evaluation_fractions=None, build_index="host", kind_weights=None, eta=0.1,
-                  reg_lambda=1.0, beta=5.0, refresh_leaf=True):
+                  reg_lambda=1.0, beta=5.0, refresh_leaf=True, misspelling_profile=None):
     """ForestModel.refresh from raw titles: FeatureEngineering(...).generate_device_data_sets(), the device data sets
     train_model trains on, then model.refresh_device on the training matrix where it lies in HBM, with the evaluation
     matrix (when the fractions draw one) for the errors per tree prefix.  The feature matrices never leave HBM.
     model: an open ForestModel of FEATURES_COUNT features on `device`; it is not modified.  kind_weights: as
     train_model's, the sample weight of the training rows by kind, handed on as sample_weight.  eta, reg_lambda, beta,
-    refresh_leaf: ForestModel.refresh's.  Everything is validated before any device work.  Returns the RefreshResult
-    with two more attributes: `rows` (the DataFrame of FeatureEngineering.rows) and `timings` (milliseconds per stage
-    of the data sets, "refresh" and "total")."""
+    refresh_leaf: ForestModel.refresh's.  misspelling_profile: FeatureEngineering's (None, a MisspellingProfile or
+    "fit").  Everything is validated before any device work.  Returns the RefreshResult with more attributes: `rows`
+    (the DataFrame of FeatureEngineering.rows), `timings` (milliseconds per stage of the data sets, "refresh" and
+    "total") and `misspelling_profile` (the profile the generated rows followed, None without one)."""
     from .feature_engineering import FEATURES_COUNT
     from .forest import validate_refresh
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
@@ -812,7 +815,8 @@ def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, 
         validate_kind_weights(kind_weights)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
-                            evaluation_fractions=evaluation_fractions, build_index=build_index)
+                            evaluation_fractions=evaluation_fractions, build_index=build_index,
+                            misspelling_profile=misspelling_profile)
     sets = fe.generate_device_data_sets()
     timings = dict(fe.timings)
     has_eval = sets.n_evaluation > 0
@@ -827,14 +831,15 @@ def refresh_model(truth_titles, truth_title_ids, train_titles, train_title_ids, 
         sets.free()
     timings["refresh"] = (time.perf_counter() - mark) * 1000.0
     timings["total"] = (time.perf_counter() - started) * 1000.0
-    result.rows, result.timings = fe.rows, timings
+    result.rows, result.timings, result.misspelling_profile = fe.rows, timings, fe.misspelling_profile
     return result
 
 
 def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0, device=0,
                 transform=True, evaluation_fractions=None, cover=False, build_index="host", init_model=None,
                 kind_weights=None, monotone_constraints=None, permutation_repeats=0, permutation_seed=0,
-                bootstrap_repeats=0, bootstrap_seed=0, calibrate=False, reliability_bins=10, **fit_parameters):
+                bootstrap_repeats=0, bootstrap_seed=0, calibrate=False, reliability_bins=10, misspelling_profile=None,
+                **fit_parameters):
     """train.train_model() of the reference in one call: FeatureEngineering(...).generate_device_data_sets() ->
     ForestTrainer.fit_device -> the evaluation error matrix (ForestModel.predict_device on the evaluation matrix in
     HBM, only its probabilities come back) and the feature importances.  The feature matrix never leaves HBM.
@@ -866,7 +871,10 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
     `reliability` and `calibrated_reliability`, timed as `timings["calibration"]`.  It needs an evaluation set.  That
     set also chose best_iteration, and the calibrated report is read on the rows the map was fitted to, so it is mildly
     optimistic: a held-out set through ForestModel.calibrate is the honest one.  False makes exactly the calls made
-    without it."""
+    without it.
+    misspelling_profile: FeatureEngineering's: None, a MisspellingProfile after which the generated rows are misspelled,
+    or "fit" to learn it from this call's own labelled train pairs first; the result's `misspelling_profile` is the
+    profile that was used (None without one)."""
     from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
     started = time.perf_counter()
@@ -891,7 +899,8 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
         reliability_bins = validate_calibration(n_bins=reliability_bins)["n_bins"]
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
-                            evaluation_fractions=evaluation_fractions, build_index=build_index)
+                            evaluation_fractions=evaluation_fractions, build_index=build_index,
+                            misspelling_profile=misspelling_profile)
     if permutation_repeats and not any(fe.evaluation_fractions.values()):
         raise ValueError("permutation_repeats needs an evaluation set, and every evaluation fraction is 0")
     if bootstrap_repeats and not any(fe.evaluation_fractions.values()):
@@ -988,4 +997,4 @@ def train_model(truth_titles, truth_title_ids, train_titles, train_title_ids, to
                             metrics_history=metrics_history, initial_error=initial_error,
                             permutation_importance=permutation_importance, error_bootstrap=error_bootstrap,
                             calibrator=calibration[0], reliability=calibration[1],
-                            calibrated_reliability=calibration[2])
+                            calibrated_reliability=calibration[2], misspelling_profile=fe.misspelling_profile)

@@ -15,7 +15,8 @@ feature_engineering.py:207-274):
                         the row itself, target 1.
 
 The device stages: Jaccard top-n of the kind 2 / 3 train rows (TruthIndex), the sample of each (ds_training_pairs_device),
-the misspellings (ds_misspell_titles), construct_features of every row into one matrix (two launches).  The split
+the misspellings (ds_misspell_titles, or ds_misspell_titles_profile with a misspelling_profile), construct_features
+of every row into one matrix (two launches).  The split
 (_get_evaluation_indexes, feature_engineering.py:277-296) runs on the host with NumPy.  The reference's unseeded
 `random` is replaced by per-(seed, purpose, index) streams: the result is a function of the inputs
 and `seed`, and does not depend on `chunk_queries`.
@@ -217,9 +218,25 @@ class _DeviceTitles:
             pass
 
 
-def misspell_table(source, rows, seed, device=0, stream=None):
+def validate_profile_argument(misspelling_profile):
+    """The misspelling_profile argument of FeatureEngineering, train_model, tune_model_parameters and refresh_model (no
+    library needed): None (the reference's generator), a MisspellingProfile that validate_misspelling_profile accepts, or
+    "fit": learn it from the call's own labelled train pairs first."""
+    from .edits import MisspellingProfile, validate_misspelling_profile
+    if misspelling_profile is None or (isinstance(misspelling_profile, str) and misspelling_profile == "fit"):
+        return misspelling_profile
+    if not isinstance(misspelling_profile, MisspellingProfile):
+        raise ValueError(f'misspelling_profile must be None, "fit" or a MisspellingProfile, not {misspelling_profile!r}')
+    validate_misspelling_profile(misspelling_profile)
+    return misspelling_profile
+
+
+def misspell_table(source, rows, seed, device=0, stream=None, profile=None):
     """ds_misspell_titles: a device table whose row i misspells row rows[i] of the TitleTable `source` (rows None:
-    every row, in order)."""
+    every row, in order).  With a MisspellingProfile: ds_misspell_titles_profile (the null stream)."""
+    if profile is not None:
+        from .edits import misspell_profile_table
+        return _DeviceTitles(*misspell_profile_table(source, rows, seed, profile, device))
     n = source.n if rows is None else int(np.asarray(rows).shape[0])
     d_rows = None if rows is None else _lib.DeviceArray.from_host(np.ascontiguousarray(rows, dtype=np.int32), device)
     handle = ctypes.c_void_p()
@@ -228,11 +245,16 @@ def misspell_table(source, rows, seed, device=0, stream=None):
     return _DeviceTitles(handle, n)
 
 
-def generate_misspelled_names(titles, seed=0, device=0):
+def generate_misspelled_names(titles, seed=0, device=0, profile=None):
     """generate_misspelled_name (feature_engineering_prepare.py:165-173) of every transformed title, title i drawn from
-    the purpose-1 stream of index i: a list of str."""
+    the purpose-1 stream of index i: a list of str.  profile: a MisspellingProfile (edits.fit_misspelling_profile): the
+    titles are misspelled after it instead (ds_misspell_titles_profile, the purpose-8 stream of index i); None makes
+    exactly the call made without it."""
     titles = [str(t) for t in titles]
     _integer("seed", seed, 0, (1 << 64) - 1)
+    if profile is not None:
+        from .edits import validate_misspelling_profile
+        validate_misspelling_profile(profile)
     for title in titles:
         if not 3 <= len(title) <= MAX_CHARACTERS_ALLOWED_IN_THE_TITLE or not title.strip():
             raise ValueError(f"not a transformed title (3..255 characters, not all spaces): {title!r}")
@@ -241,7 +263,7 @@ def generate_misspelled_names(titles, seed=0, device=0):
     chars, offsets = _pack(titles)
     check_characters(chars, offsets, "the")
     enc, lengths = encode_collection(chars, offsets, _CODE_OF)
-    return misspell_table(TitleTable(enc, lengths, None, device), None, seed, device).strings()
+    return misspell_table(TitleTable(enc, lengths, None, device), None, seed, device, profile=profile).strings()
 
 
 class DeviceDataSets:
@@ -326,6 +348,10 @@ class FeatureEngineering:
     NumPy generator of the split.  chunk_queries: train titles per top-n pass (default: what a quarter of the free HBM
     holds); the result does not depend on it.  evaluation_fractions: {"generated", "negative", "positive"} -> share
     of ALL rows drawn into the evaluation set (settings.py:47-49).  build_index: "host" or "device", passed to TruthSide.
+    misspelling_profile: None, or a MisspellingProfile after which the kind 1 rows are misspelled
+    (ds_misspell_titles_profile) instead of after the reference's rule, or "fit": fit_misspelling_profile() of this
+    object's own labelled train rows, made by the first call that generates rows and kept as `misspelling_profile`.
+    `timings` then has "misspell_profile" (and "misspell_profile_fit"); the kind 2 / 3 rows do not depend on it.
 
     After a call: `rows` (DataFrame: kind, query_index = train row for kinds 2 / 3 and truth row for kind 1,
     truth_row, target, evaluation), `misspelled_titles` (the queries of the kind 1 rows, in order), `features` (every
@@ -337,8 +363,10 @@ class FeatureEngineering:
     `hard_timings` and leave `rows`, `features` and `timings` alone."""
 
     def __init__(self, truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=100, sample_n=10, seed=0,
-                 device=0, transform=True, chunk_queries=None, evaluation_fractions=None, build_index="host"):
+                 device=0, transform=True, chunk_queries=None, evaluation_fractions=None, build_index="host",
+                 misspelling_profile=None):
         validate_index_build(build_index, "build_index")
+        self.misspelling_profile = validate_profile_argument(misspelling_profile)
         truth_titles, train_titles = list(truth_titles), list(train_titles)
         unknown = set(evaluation_fractions or {}) - set(EVALUATION_FRACTIONS)
         if unknown:
@@ -428,6 +456,28 @@ class FeatureEngineering:
             self._truth = TruthSide(self.truth_titles, self.device, build_index=self.build_index)
             timings["truth_side"] = (time.perf_counter() - mark) * 1000.0
         return self._truth
+
+    def fit_misspelling_profile(self, max_edits=4):
+        """The MisspellingProfile of this object's labelled pairs: every train row with a truth id against its truth
+        row (edits.fit_misspelling_profile of those pairs), aligned on the device against the truth table that is
+        already in HBM; the labelled train titles are uploaded for it once (the query table holds only the rows that
+        produce training rows)."""
+        from .edits import COUNTS, MisspellingProfile, _max_edits, fit_tables
+        max_edits = _max_edits(max_edits)
+        truth = self._truth_side(dict(host_prepare=0.0), time.perf_counter())
+        labelled = np.nonzero(self.train_truth_rows >= 0)[0]
+        if not labelled.shape[0]:
+            return MisspellingProfile(np.zeros(COUNTS, np.int64), max_edits)
+        chars, offsets = _pack([self.train_titles[i] for i in labelled])
+        check_characters(chars, offsets, "train")
+        enc, lengths = encode_collection(chars, offsets, _CODE_OF)
+        table = TitleTable(enc, lengths, None, self.device)
+        d_rows = _lib.DeviceArray.from_host(self.train_truth_rows[labelled].astype(np.int32), self.device)
+        try:
+            return fit_tables(truth.table, d_rows, table, None, labelled.shape[0], max_edits, self.device)
+        finally:
+            d_rows.free()
+            table.close()
 
     def _selected_queries(self):
         """The train rows that produce rows (kinds 2 and 3, in that order) as queries of the truth side, made once:
@@ -622,10 +672,15 @@ class FeatureEngineering:
 
         # ---- the misspelled truth titles, on the device
         misspelled = None
+        if isinstance(self.misspelling_profile, str):          # "fit": learned once from the labelled train rows
+            mark = time.perf_counter()
+            self.misspelling_profile = validate_profile_argument(self.fit_misspelling_profile())
+            timings["misspell_profile_fit"] = (time.perf_counter() - mark) * 1000.0
         if generated.shape[0]:
             mark = time.perf_counter()
-            misspelled = misspell_table(truth.table, generated, self.seed, device)
-            timings["misspell"] = (time.perf_counter() - mark) * 1000.0
+            misspelled = misspell_table(truth.table, generated, self.seed, device, profile=self.misspelling_profile)
+            timings["misspell" if self.misspelling_profile is None else "misspell_profile"] = \
+                (time.perf_counter() - mark) * 1000.0
 
         # ---- construct_features of every row into one matrix: kinds 2 and 3 against the train titles, kind 1 against
         # the misspelled titles

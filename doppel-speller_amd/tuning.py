@@ -644,7 +644,7 @@ def row_groups(rows):
 
 def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_title_ids, parameters, n_folds=5, top_n=100,
                           sample_n=10, seed=0, device=0, transform=True, cover=False, init_model=None,
-                          kind_weights=None, monotone_constraints=None, **cv_arguments):
+                          kind_weights=None, monotone_constraints=None, misspelling_profile=None, **cv_arguments):
     """Parameter search from raw titles in one call: FeatureEngineering(..., no evaluation split).
     generate_device_data_sets() -> cross_validate on the matrix in HBM, folds by row_groups -> the refit model.
     cv_arguments: num_boost_round, early_stopping_rounds, max_bin, models_per_batch, metrics, select_by.  Returns cross_validate's result
@@ -654,7 +654,8 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
     FEATURES_COUNT features that every fold, set and the refit continue from.  kind_weights: {"generated", "negative",
     "positive"} -> the sample weight of the rows of that kind (training_set.kind_weights; a name left out: 1.0), handed
     to cross_validate as sample_weight.  monotone_constraints: cross_validate's, as FEATURES_COUNT signs or as a dict by
-    FEATURE_NAMES (feature_engineering.ratio_constraints()).  Everything is validated before any device work and everything held in HBM is
+    FEATURE_NAMES (feature_engineering.ratio_constraints()).  misspelling_profile: FeatureEngineering's (None, a
+    MisspellingProfile or "fit"); the result's `misspelling_profile` is the profile that was used.  Everything is validated before any device work and everything held in HBM is
     freed on every exit path."""
     from .feature_engineering import FEATURES_COUNT, FEATURE_NAMES
     from .training_set import FeatureEngineering, kind_weights as weights_of_kinds, validate_kind_weights
@@ -672,7 +673,8 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
         monotone_constraints = validate_monotone_constraints(monotone_constraints, FEATURES_COUNT, FEATURE_NAMES)
     fe = FeatureEngineering(truth_titles, truth_title_ids, train_titles, train_title_ids, top_n=top_n,
                             sample_n=sample_n, seed=seed, device=device, transform=transform,
-                            evaluation_fractions=dict(generated=0.0, negative=0.0, positive=0.0))
+                            evaluation_fractions=dict(generated=0.0, negative=0.0, positive=0.0),
+                            misspelling_profile=misspelling_profile)
     sets = fe.generate_device_data_sets()
     try:
         matrix = _lib.DeviceArray.view(sets.train.ptr, (sets.n_train, sets.train.shape[1]), np.float32, device)
@@ -688,5 +690,6 @@ def tune_model_parameters(truth_titles, truth_title_ids, train_titles, train_tit
         sets.free()
     out.timings = dict(fe.timings, **out.timings)
     out.rows, out.feature_importance = fe.rows, out.model.feature_importance()
+    out.misspelling_profile = fe.misspelling_profile
     out.timings["total"] = (time.perf_counter() - started) * 1000.0
     return out

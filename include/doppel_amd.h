@@ -1010,6 +1010,80 @@ int ds_training_pairs_device(const int32_t *d_rows, int64_t n_queries, int32_t t
                              const int64_t *d_stream_index, const int32_t *d_own_row, uint64_t seed, int64_t q_first,
                              int32_t *d_pair_q, int32_t *d_pair_t, float *d_target, void *stream);
 
+/* ---- edit scripts and the learned misspelling model ("Edit scripts and the learned misspelling
+ * model"; this project's own) -----------------------------------------------------------------------------------------------
+ * The alignment rule.  a is the correct title (a row of `truth`, m characters), b the observed one (a row of `observed`, n
+ * characters); both are transformed titles, 3..255 codes 1..37.  D is the optimal-string-alignment distance over prefixes:
+ * D[i][0] = i, D[0][j] = j, and D[i][j] is the least of D[i-1][j-1] + (a[i-1] != b[j-1]) (match or substitute), D[i-1][j] + 1
+ * (delete: a[i-1] is missing in b), D[i][j-1] + 1 (insert: b[j-1] is not in a) and, when i, j > 1 and a[i-1] == b[j-2] and
+ * a[i-2] == b[j-1], D[i-2][j-2] + 1 (transpose).  The traceback goes from (m, n) to (0, 0) and takes at (i, j) the first that
+ * applies of: 1 match (i, j > 0, a[i-1] == b[j-1], D[i][j] == D[i-1][j-1]); 2 substitute (i, j > 0, D[i][j] == D[i-1][j-1] + 1);
+ * 3 transpose (i, j > 1, the swap condition, D[i][j] == D[i-2][j-2] + 1); 4 delete (i > 0, D[i][j] == D[i-1][j] + 1); 5 insert.
+ * The script is the traceback reversed, one byte per operation (DS_EDIT_OP_*); its length is at most m + n.
+ *
+ * The counts are one block of DS_EDIT_COUNTS int64 that is added to, never overwritten (the caller zeroes it; calls
+ * accumulate).  A pair with D[m][n] > max_edits adds 1 to `skipped` and nothing else; every other pair adds 1 to `counted`,
+ * to edits[D[m][n]], to seen[0] (one title end) and to seen[c] for every character c of a, and per operation of its script:
+ * match[a[i-1]]; substitute[a[i-1]][b[j-1]]; delete[a[i-1]]; insert[context][b[j-1]], the context being a[i], the character in
+ * front of which the insertion stands, or 0 at the end of a; transpose[a[i-2]][a[i-1]].  The tables are indexed by code,
+ * 38 x 38 row-major.  Only integer additions: the block does not depend on the order of the pairs or on the launch.
+ *
+ * Aligns pair p = (truth row d_truth_rows[p], observed row d_observed_rows[p]) for p < n; a null row array means row p.
+ * Outputs, each of which may be NULL (d_ops and d_ops_length only together): d_distance[p] = D[m][n]; d_ops + 512 * p = the
+ * script followed by zeros, all 512 bytes written (d_ops 8-byte aligned); d_ops_length[p] = its length; d_counts = the block.
+ * A skipped pair's distance and script are still written.  max_edits in 0..32, n in [0, 2^31); n == 0 launches nothing.
+ * DS_E_ARG with nothing written: a null table, tables on two devices, n or max_edits out of range, one of d_ops and
+ * d_ops_length alone, and, found by a check kernel over all pairs before anything else runs, a row out of range or a title
+ * that is not 3..255 codes 1..37.
+ * No stream parameter: the kernels are enqueued on the null stream, which is synchronised before returning (the check
+ * kernel's verdict and the longest truth title, which sizes the LDS of the alignment kernel, come back first).
+ * The option call is for tests, no result depends on it: "pairs_per_group" = waves, each with a pair, per workgroup
+ * (0: 4; at most 16, and never more than 64 KiB of LDS hold), "max_blocks" = cap of the grids (0: 4096, at most 65536). */
+#define DS_EDIT_OP_MATCH 0
+#define DS_EDIT_OP_SUBSTITUTE 1
+#define DS_EDIT_OP_DELETE 2
+#define DS_EDIT_OP_INSERT 3
+#define DS_EDIT_OP_TRANSPOSE 4
+#define DS_EDIT_OPS_STRIDE 512
+#define DS_EDIT_CODES 38
+#define DS_EDIT_COUNTED 0                                       /* 1 */
+#define DS_EDIT_SKIPPED 1                                       /* 1 */
+#define DS_EDIT_EDITS 2                                         /* [33] */
+#define DS_EDIT_SEEN (DS_EDIT_EDITS + 33)                       /* [38] */
+#define DS_EDIT_MATCH (DS_EDIT_SEEN + DS_EDIT_CODES)            /* [38] */
+#define DS_EDIT_DELETE (DS_EDIT_MATCH + DS_EDIT_CODES)          /* [38] */
+#define DS_EDIT_SUBSTITUTE (DS_EDIT_DELETE + DS_EDIT_CODES)     /* [38][38] */
+#define DS_EDIT_INSERT (DS_EDIT_SUBSTITUTE + DS_EDIT_CODES * DS_EDIT_CODES)   /* [38][38] */
+#define DS_EDIT_TRANSPOSE (DS_EDIT_INSERT + DS_EDIT_CODES * DS_EDIT_CODES)    /* [38][38] */
+#define DS_EDIT_COUNTS (DS_EDIT_TRANSPOSE + DS_EDIT_CODES * DS_EDIT_CODES)    /* 4481 int64 */
+int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_titles *observed,
+                  const int32_t *d_observed_rows, int64_t n, int32_t max_edits, int32_t *d_distance, uint8_t *d_ops,
+                  int32_t *d_ops_length, int64_t *d_counts);
+int ds_edit_option(const char *name, int64_t value);
+/* *out = a new table (stride 255, no word counts) whose row i is source row d_rows[i] (d_rows NULL: row i) misspelled after
+ * the counts block d_profile (DS_EDIT_COUNTS int64 in HBM, read back once and checked) and transformed.  Integer steps only:
+ *   rates    with SCALE = 2^30 and S[c] the sum of a table's row c: rate_sub[c] = floor(SCALE * S_substitute[c] / seen[c]),
+ *            rate_del[c] from delete[c], rate_tr[c] from transpose[c][*], rate_ins[c] from insert[c][*], c = 0..37; 0 where
+ *            seen[c] == 0;
+ *   stream   title i draws from the stream of (seed, DS_MISSPELL_PURPOSE_PROFILE, source row), as above; below(n) = the high
+ *            64 bits of x * n with n up to 64 bits;
+ *   edits    k = the smallest d >= 1 whose edits[1] + .. + edits[d] exceeds below(edits[1] + .. + edits[32]);
+ *   an edit  of the working title w of length L: the positions p = 0 .. L in ascending order, at each the operations in the
+ *            order substitute, delete, transpose, insert, weigh rate_sub[w[p]]; rate_del[w[p]], 0 when L <= 3; rate_tr[w[p]],
+ *            0 unless p + 1 < L and w[p] != w[p+1]; rate_ins[w[p]] (rate_ins[0] at p == L), 0 when L >= 255; the first
+ *            three are 0 at p == L.  T = the sum of all weights; T == 0 ends the title's edits; else below(T) picks the first
+ *            (position, operation) whose cumulative weight exceeds it.  A substitute then draws the new code y != w[p] from
+ *            the row substitute[w[p]][*] by below(the row's sum without y == w[p]), walking y upwards; an insert draws from
+ *            insert[context][*] likewise and puts the code in front of w[p]; a transpose swaps w[p] and w[p+1];
+ *   finish   transform_title as in ds_misspell_titles.
+ * The profile is refused (DS_E_ARG, no table) when a count is negative or 2^40 or more, when edits[1..32] are all 0, when
+ * a count that no alignment produces is not 0 (match, delete, substitute or transpose of code 0, an inserted code 0, a
+ * character substituted by itself), or when a rate reaches 2^32 (4 events per seen character).  Source rows as for
+ * ds_misspell_titles.  No stream parameter: the null stream, synchronised before returning. */
+#define DS_MISSPELL_PURPOSE_PROFILE 8
+int ds_misspell_titles_profile(ds_titles *source, const int32_t *d_rows, int64_t n, uint64_t seed, const int64_t *d_profile,
+                               ds_titles **out);
+
 /* ---- hard negatives: the wrong candidates a model likes best, mined on the device -----------------
  * The project's own rule; the reference draws its negatives at random (feature_engineering_prepare.py:25-57).  For title
  * i of a chunk of n_queries titles, over the candidates j = 0 .. k-1 with truth row c_j = d_rows[i*k + j] and margin m_j =
