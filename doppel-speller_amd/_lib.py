@@ -355,6 +355,12 @@ def check(status, what=""):
         raise DoppelError(f"{what}: {message} (status {status})")
 
 
+def set_option(entry, name, value, handle=None):
+    """entry(name, value), or entry(handle, name, value) for a setter that takes a handle (include/doppel_amd.h, "Options")."""
+    arguments = (name.encode(), int(value)) if handle is None else (handle, name.encode(), int(value))
+    check(getattr(lib(), entry)(*arguments), entry)
+
+
 def device_count():
     count = ctypes.c_int(0)
     status = lib().ds_device_count(ctypes.byref(count))

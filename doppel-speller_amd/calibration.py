@@ -299,7 +299,7 @@ def reliability(probabilities, target, n_bins=10, device=0):
 
 def calibrate_option(name, value):
     """ds_calibrate_option, for tests: "max_blocks", "segment_points"."""
-    _lib.check(_lib.lib().ds_calibrate_option(name.encode(), int(value)), "ds_calibrate_option")
+    _lib.set_option("ds_calibrate_option", name, value)
 
 
 def calibrate_rows_device(model, d_rows, n, d_target, n_bins=None, stream=None):

@@ -28,10 +28,9 @@
 // enqueues "rounds_per_sync" rounds, each with its own activity counter, and reads the counters back once per batch; a round
 // that finds the counter of the round before it at zero returns at once.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -43,8 +42,9 @@ constexpr int kAssignRoundsPerSync = 8;
 constexpr int kAssignRoundsLimit = 1024;
 constexpr uint64_t kAssignTitleMask = 0x7fffffffull;
 
-static std::atomic<int64_t> g_assign_max_blocks{kAssignMaxBlocks};
-static std::atomic<int64_t> g_assign_rounds_per_sync{kAssignRoundsPerSync};
+static Option g_assign_max_blocks{"max_blocks", 0, kAssignBlocksLimit, kAssignMaxBlocks, true};
+static Option g_assign_rounds_per_sync{"rounds_per_sync", 1, kAssignRoundsLimit, kAssignRoundsPerSync};
+static Option *const g_assign_options[] = {&g_assign_max_blocks, &g_assign_rounds_per_sync};
 
 // does slot i pass the tests that need no other slot?
 __device__ __forceinline__ bool assign_eligible(int32_t row, float probability, int32_t stage, int32_t n_truth, float threshold)
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kAssignThreads) void ds_assign_finish_kernel(
 static dim3 assign_grid(int64_t items)
 {
     const int64_t blocks = (items + kAssignThreads - 1) / kAssignThreads;
-    return dim3(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, g_assign_max_blocks))));
+    return dim3(grid_cap(blocks, g_assign_max_blocks.get()));
 }
 
 }  // namespace ds
@@ -200,21 +200,7 @@ extern "C" {
 
 int ds_assign_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_assign_option: null name");
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kAssignBlocksLimit, "ds_assign_option: max_blocks = %lld out of range [0, %d]",
-                   (long long)value, ds::kAssignBlocksLimit);
-        ds::g_assign_max_blocks = value == 0 ? ds::kAssignMaxBlocks : value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "rounds_per_sync") == 0) {
-        DS_REQUIRE(value >= 1 && value <= ds::kAssignRoundsLimit, "ds_assign_option: rounds_per_sync = %lld out of range [1, %d]",
-                   (long long)value, ds::kAssignRoundsLimit);
-        ds::g_assign_rounds_per_sync = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_assign_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_assign_option", ds::g_assign_options, name, value);
 }
 
 int ds_assign_edges_device(const int32_t *d_row, const float *d_probability, const uint8_t *d_ratio, const int8_t *d_stage,
@@ -263,7 +249,7 @@ int ds_assign_solve_device(const int32_t *d_edge_row, const uint64_t *d_edge_key
     if (n_truth) DS_HIP(hipMemsetAsync(d_held, 0, static_cast<size_t>(n_truth) * sizeof(uint64_t), queue));
     DS_HIP(hipMemsetAsync(d_next, 0, static_cast<size_t>(n_queries) * sizeof(int32_t), queue));
 
-    const int batch = static_cast<int>(ds::g_assign_rounds_per_sync);
+    const int batch = static_cast<int>(ds::g_assign_rounds_per_sync.get());
     ds::DeviceBuffer<uint32_t> activity;
     int status = activity.allocate(static_cast<size_t>(batch));
     if (status != DS_OK) return status;

@@ -44,9 +44,11 @@ static_assert(kBootstrapChunk / 64 * 64 == kBootstrapChunk && kBootstrapChunk < 
               "the wave's sum of a 16-bit field over a chunk must stay below 2^16");
 
 // for tests (ds_bootstrap_option); no result depends on them
-static int g_bootstrap_max_blocks = 0;                 // 0: kBootstrapDefaultBlocks
-static int g_bootstrap_replicates_per_block = 0;       // 0: the launcher's choice
-static int g_bootstrap_table_in_lds = 1;
+static Option g_bootstrap_max_blocks{"max_blocks", 0, 65535, kBootstrapDefaultBlocks, true};
+static Option g_bootstrap_replicates_per_block{"replicates_per_block", 0, kBootstrapBootMax + 1, 0};   // 0: the launcher's choice
+static Option g_bootstrap_table_in_lds{"table_in_lds", 0, 1, 1};
+static Option *const g_bootstrap_options[] = {&g_bootstrap_max_blocks, &g_bootstrap_replicates_per_block,
+                                              &g_bootstrap_table_in_lds};
 
 struct BootstrapArgs {
     const uint8_t *codes;        // [M][n]
@@ -215,8 +217,7 @@ static int bootstrap_check_scalars(const char *what, int32_t n_sets, int64_t n, 
 
 static dim3 bootstrap_row_grid(int64_t n)
 {
-    const int64_t cap = g_bootstrap_max_blocks ? g_bootstrap_max_blocks : kBootstrapDefaultBlocks;
-    return dim3(static_cast<unsigned>(std::min<int64_t>((n + kBootstrapCheckThreads - 1) / kBootstrapCheckThreads, cap)));
+    return dim3(grid_cap((n + kBootstrapCheckThreads - 1) / kBootstrapCheckThreads, g_bootstrap_max_blocks.get()));
 }
 
 template <bool kUnits, bool kLds>
@@ -267,20 +268,21 @@ static int bootstrap_enqueue(const uint8_t *d_codes, int32_t n_sets, int64_t n, 
     args.n_boot = n_boot;
     args.padded_sets = (n_sets + kBootstrapTile - 1) / kBootstrapTile * kBootstrapTile;
     const int64_t replicates = static_cast<int64_t>(n_boot) + 1;   // and the baseline
-    int64_t per_block = g_bootstrap_replicates_per_block;
+    int64_t per_block = g_bootstrap_replicates_per_block.get();
     if (per_block <= 0)   // whole waves, and enough workgroups for every CU
         per_block = kBootstrapWaves * ((replicates + kBootstrapWaves * kBootstrapTargetBlocks - 1) /
                                        (kBootstrapWaves * kBootstrapTargetBlocks));
     per_block = std::min<int64_t>(per_block, replicates);
     args.per_block = static_cast<int32_t>(per_block);
     args.n_groups = static_cast<int32_t>((replicates + per_block - 1) / per_block);
-    const int64_t cap = g_bootstrap_max_blocks ? g_bootstrap_max_blocks : kBootstrapDefaultBlocks;
-    const int64_t grid_x = std::min<int64_t>(args.n_groups, cap);
-    const int64_t grid_y = std::min<int64_t>(args.n_chunks, g_bootstrap_max_blocks ? cap : std::max<int64_t>(1, 2 * cap / grid_x));
-    const dim3 grid(static_cast<unsigned>(grid_x), static_cast<unsigned>(std::min<int64_t>(grid_y, 65535)));
+    const int64_t cap = g_bootstrap_max_blocks.get();
+    const unsigned grid_x = grid_cap(args.n_groups, cap);
+    // a cap that was set holds for either dimension; the default leaves the grid 2 * cap workgroups in all
+    const int64_t cap_y = g_bootstrap_max_blocks.is_set() ? cap : std::max<int64_t>(1, 2 * cap / grid_x);
+    const dim3 grid(grid_x, grid_cap(args.n_chunks, cap_y, 65535));
     const bool units = d_unit != nullptr;
     const int64_t bytes = units ? n_units * n_sets * static_cast<int64_t>(sizeof(uint4)) : n_units * args.padded_sets;
-    const bool in_lds = g_bootstrap_table_in_lds != 0 && bytes <= kBootstrapLdsBytes;
+    const bool in_lds = g_bootstrap_table_in_lds.get() != 0 && bytes <= kBootstrapLdsBytes;
     const size_t lds = in_lds ? static_cast<size_t>((bytes + 15) / 16 * 16) : 0;
     int status;
     if (units)
@@ -300,27 +302,7 @@ extern "C" {
 
 int ds_bootstrap_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_bootstrap_option: null name");
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= 65535, "ds_bootstrap_option: max_blocks = %lld out of range [0, 65535]",
-                   (long long)value);
-        ds::g_bootstrap_max_blocks = static_cast<int>(value);
-        return DS_OK;
-    }
-    if (std::strcmp(name, "replicates_per_block") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kBootstrapBootMax + 1,
-                   "ds_bootstrap_option: replicates_per_block = %lld out of range [0, %d]", (long long)value,
-                   ds::kBootstrapBootMax + 1);
-        ds::g_bootstrap_replicates_per_block = static_cast<int>(value);
-        return DS_OK;
-    }
-    if (std::strcmp(name, "table_in_lds") == 0) {
-        DS_REQUIRE(value == 0 || value == 1, "ds_bootstrap_option: table_in_lds = %lld is neither 0 nor 1", (long long)value);
-        ds::g_bootstrap_table_in_lds = static_cast<int>(value);
-        return DS_OK;
-    }
-    ds::set_error("ds_bootstrap_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_bootstrap_option", ds::g_bootstrap_options, name, value);
 }
 
 int ds_bootstrap_counts_device(const uint8_t *d_codes, int32_t n_sets, int64_t n, const int32_t *d_unit, int64_t n_units,

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "ds_metrics.h"
+#include "ds_options.h"
 #include "ds_radix.h"
 
 namespace ds {
@@ -44,8 +45,9 @@ constexpr int kReliabilityBinsMax = 256;
 constexpr uint32_t kNanKey = 0xffffffffu;
 
 // for tests (ds_calibrate_option); no result depends on them
-static int g_calibrate_max_blocks = 0;                 // 0: kCalibrateDefaultBlocks
-static int g_calibrate_segment_points = 0;             // 0: kCalibrateSegmentDefault
+static Option g_calibrate_max_blocks{"max_blocks", 0, 65535, kCalibrateDefaultBlocks, true};
+static Option g_calibrate_segment_points{"segment_points", 2, kCalibrateSegmentMax, kCalibrateSegmentDefault, true};
+static Option *const g_calibrate_options[] = {&g_calibrate_max_blocks, &g_calibrate_segment_points};
 
 // the uint32 state block of a fit in HBM
 enum { kStateNeg = 0, kStatePos, kStateNan, kStatePoints, kStateBlocks, kStateSurvivors, kStateOr = 8, kStateAnd = 10,
@@ -53,8 +55,7 @@ enum { kStateNeg = 0, kStatePos, kStateNan, kStatePoints, kStateBlocks, kStateSu
 
 static unsigned calibrate_grid(int64_t items)
 {
-    const int64_t cap = g_calibrate_max_blocks ? g_calibrate_max_blocks : kCalibrateDefaultBlocks;
-    return static_cast<unsigned>(std::max<int64_t>(1, std::min(items, cap)));
+    return grid_cap(items, g_calibrate_max_blocks.get());
 }
 
 __global__ void ds_isotonic_begin_kernel(uint32_t *state)
@@ -535,7 +536,7 @@ static int isotonic_enqueue(const float *d_scores, const float *d_labels, int64_
 {
     const char *what = "ds_isotonic_fit_device";
     if (int status = train_check_free(isotonic_scratch_bytes(n), what); status != DS_OK) return status;
-    const int32_t W = g_calibrate_segment_points ? g_calibrate_segment_points : kCalibrateSegmentDefault;
+    const int32_t W = static_cast<int32_t>(g_calibrate_segment_points.get());
     const int64_t head_tiles = (n + 1 + kCalibrateHeadTile - 1) / kCalibrateHeadTile;
     const int64_t max_segments = (n + W - 1) / W;
     DeviceBuffer<uint32_t> keys_a, keys_b, table, state, S, totals, pt_key, pt_pos, pt_neg, seg_count;
@@ -612,22 +613,7 @@ extern "C" {
 
 int ds_calibrate_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_calibrate_option: null name");
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= 65535, "ds_calibrate_option: max_blocks = %lld out of range [0, 65535]",
-                   (long long)value);
-        ds::g_calibrate_max_blocks = static_cast<int>(value);
-        return DS_OK;
-    }
-    if (std::strcmp(name, "segment_points") == 0) {
-        DS_REQUIRE(value == 0 || (value >= 2 && value <= ds::kCalibrateSegmentMax),
-                   "ds_calibrate_option: segment_points = %lld is neither 0 nor in [2, %d]", (long long)value,
-                   ds::kCalibrateSegmentMax);
-        ds::g_calibrate_segment_points = static_cast<int>(value);
-        return DS_OK;
-    }
-    ds::set_error("ds_calibrate_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_calibrate_option", ds::g_calibrate_options, name, value);
 }
 
 int ds_isotonic_fit_device(const float *d_scores, const float *d_labels, int64_t n, float *d_lo, float *d_hi,

@@ -48,6 +48,7 @@ void duplicate_ranks(const int64_t *rowptr, const int32_t *truth_idx, const floa
                      uint16_t *rank_out);
 int64_t choose_tile_rows(int64_t N);   // tile size of an index of N rows (DS_GEOMETRY overrides)
 int hip_failed(hipError_t error, const char *what, const char *file, int line);
+int compute_units(int device);         // the device's compute units, 256 where the runtime cannot say
 
 #define DS_HIP(call)                                                          \
     do {                                                                      \

@@ -17,7 +17,6 @@
 // same bits whatever the grid.  approximate = 1 (Saabas) walks the row's own path and adds the change of the subtree mean.
 #include "ds_forest.h"
 
-#include <atomic>
 #include <cmath>
 
 namespace ds {
@@ -25,7 +24,6 @@ namespace ds {
 constexpr int kCoverMaxBlocks = 4096;            // default grid cap of the cover kernel (256 rows per workgroup)
 constexpr int kContributionsThreads = 64;        // one wavefront: the rows of a workgroup
 constexpr int kContributionsMaxBlocks = 8192;    // default grid cap of the contributions kernels
-constexpr int kForestBlocksLimit = 1 << 20;
 constexpr int kLaneStride = kContributionsThreads + 1;  // [feature][lane] images in LDS, padded: the transposing copies spread over the banks
 
 struct CoverArgs {
@@ -404,28 +402,9 @@ extern "C" {
 
 int ds_forest_option(ds_forest *forest, const char *name, int64_t value)
 {
-    DS_REQUIRE(forest != nullptr && name != nullptr, "ds_forest_option: null forest or name");
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kForestBlocksLimit, "ds_forest_option: max_blocks = %lld out of range [0, %d]",
-                   (long long)value, ds::kForestBlocksLimit);
-        forest->max_blocks = value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "inspect_jobs_per_block") == 0) {
-        DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_forest_option: inspect_jobs_per_block = %lld out of range [0, %d]",
-                   (long long)value, INT32_MAX);
-        forest->inspect_jobs_per_block = value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "refresh_lds_nodes") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kRefreshLdsNodesMax,
-                   "ds_forest_option: refresh_lds_nodes = %lld out of range [0, %d]", (long long)value,
-                   ds::kRefreshLdsNodesMax);
-        forest->refresh_lds_nodes = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_forest_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    DS_REQUIRE(forest != nullptr, "ds_forest_option: null forest");
+    ds::Option *const table[] = {&forest->max_blocks, &forest->inspect_jobs_per_block, &forest->refresh_lds_nodes};
+    return ds::set_option("ds_forest_option", table, name, value);
 }
 
 int ds_forest_cover_device(ds_forest *forest, const float *d_rows, int64_t n, void *stream)
@@ -447,15 +426,15 @@ int ds_forest_cover_device(ds_forest *forest, const float *d_rows, int64_t n, vo
     if (n == 0 || forest->n_trees == 0) return DS_OK;
     const ds::CoverArgs args{forest->view(), d_rows, forest->counts.ptr, n};
     const int64_t blocks = (n + ds::kForestThreads - 1) / ds::kForestThreads;
-    const int64_t cap = forest->max_blocks ? forest->max_blocks : ds::kCoverMaxBlocks;
-    const int grid = static_cast<int>(std::min<int64_t>(blocks, cap));
+    const int64_t cap = forest->max_blocks.value_or(ds::kCoverMaxBlocks);
+    const unsigned grid = ds::grid_cap(blocks, cap);
     const size_t lds = static_cast<size_t>(ds::kForestThreads) * (forest->n_features + 1) * sizeof(float);
     if (lds > 48 * 1024)
         DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds::ds_forest_cover_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     hipLaunchKernelGGL(ds::ds_forest_cover_kernel, dim3(grid), dim3(ds::kForestThreads), lds, queue, args);
     DS_HIP(hipGetLastError());
-    const int sum_grid = static_cast<int>(std::min<int64_t>((forest->n_trees + 63) / 64, cap));
+    const unsigned sum_grid = ds::grid_cap((forest->n_trees + 63) / 64, cap);
     hipLaunchKernelGGL(ds::ds_forest_cover_sum_kernel, dim3(sum_grid), dim3(64), 0, queue, forest->nodes.ptr,
                        forest->tree_offsets.ptr, forest->n_trees, forest->counts.ptr);
     DS_HIP(hipGetLastError());
@@ -522,8 +501,8 @@ int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64
     args.n = n;
     args.n_paths = forest->n_paths;
     const int64_t blocks = (n + ds::kContributionsThreads - 1) / ds::kContributionsThreads;
-    const int64_t cap = forest->max_blocks ? forest->max_blocks : ds::kContributionsMaxBlocks;
-    const int grid = static_cast<int>(std::min<int64_t>(blocks, cap));
+    const int64_t cap = forest->max_blocks.value_or(ds::kContributionsMaxBlocks);
+    const int grid = static_cast<int>(ds::grid_cap(blocks, cap));
     const size_t lds = static_cast<size_t>(forest->n_features) * ds::kLaneStride * (sizeof(double) + sizeof(float));
     hipStream_t queue = static_cast<hipStream_t>(stream);
     if (approximate) return ds::launch_contributions<0>(args, grid, lds, queue);

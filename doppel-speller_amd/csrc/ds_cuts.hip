@@ -27,8 +27,8 @@
 // group is the largest number of columns for which these stay under a QUARTER of the HBM that is free at the call
 // (at least one column); ds_cuts_option("column_group", g) forces g columns per group for tests.
 #include <algorithm>
-#include <atomic>
 
+#include "ds_options.h"
 #include "ds_radix.h"
 
 namespace ds {
@@ -137,7 +137,8 @@ __global__ __launch_bounds__(kScanThreads) void ds_cuts_pick_kernel(const uint32
 
 namespace {
 
-std::atomic<int64_t> g_column_group{0};   // 0: sized from the free HBM
+ds::Option g_column_group{"column_group", 0, ds::kCutsFeaturesMax, 0};   // 0: sized from the free HBM
+ds::Option *const g_cuts_options[] = {&g_column_group};
 
 }  // namespace
 
@@ -145,15 +146,7 @@ extern "C" {
 
 int ds_cuts_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_cuts_option: null name");
-    if (std::strcmp(name, "column_group") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kCutsFeaturesMax, "ds_cuts_option: column_group = %lld out of range [0, %d]",
-                   (long long)value, ds::kCutsFeaturesMax);
-        g_column_group = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_cuts_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_cuts_option", g_cuts_options, name, value);
 }
 
 int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_features, int32_t max_bin, float *cuts,
@@ -175,7 +168,7 @@ int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_feature
                       free_bytes);
         return DS_E_HIP;
     }
-    int64_t group = g_column_group.load();
+    int64_t group = g_column_group.get();
     if (group == 0) group = static_cast<int64_t>(free_bytes / 4) / column_bytes;
     group = std::max<int64_t>(1, std::min<int64_t>(group, n_features));
 
@@ -189,12 +182,8 @@ int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_feature
     if (status == DS_OK) status = cut_counts.allocate(n_features);
     if (status != DS_OK) return status;
     uint32_t *col_m = column_state.ptr, *col_or = col_m + ds::kCutsFeaturesMax, *col_and = col_or + ds::kCutsFeaturesMax;
-    int compute_units = 256;
-    hipDeviceProp_t props;
-    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
-        compute_units = props.multiProcessorCount;
     const int64_t row_tiles = (n + ds::kKeyTileRows - 1) / ds::kKeyTileRows;
-    const unsigned key_grid = static_cast<unsigned>(std::min<int64_t>(row_tiles, int64_t(compute_units) * 8));
+    const unsigned key_grid = ds::grid_cap(row_tiles, int64_t(ds::compute_units(device)) * 8);
     for (int32_t c0 = 0; c0 < n_features; c0 += static_cast<int32_t>(group)) {
         const int32_t g = static_cast<int32_t>(std::min<int64_t>(group, n_features - c0));
         DS_HIP(hipMemsetAsync(col_m, 0, sizeof(uint32_t) * 2 * ds::kCutsFeaturesMax, s));

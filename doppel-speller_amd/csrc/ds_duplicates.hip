@@ -26,10 +26,9 @@
 // coalesced reason store); slot 0 of a query also carries its exact link.  The grid is capped and strides; a thread
 // keeps its three counts in registers, a wave adds them up and lane 0 adds them to HBM once (integer atomics).
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -38,7 +37,8 @@ constexpr int kDuplicateThreads = 256;
 constexpr int kDuplicateMaxBlocks = 2048;     // 8 workgroups per CU on 256 CUs; more slots or rows: the grid strides
 constexpr int kDuplicateBlocksLimit = 1 << 20;
 
-static std::atomic<int64_t> g_duplicate_max_blocks{kDuplicateMaxBlocks};
+static Option g_duplicate_max_blocks{"max_blocks", 0, kDuplicateBlocksLimit, kDuplicateMaxBlocks, true};
+static Option *const g_duplicate_options[] = {&g_duplicate_max_blocks};
 
 __device__ __forceinline__ int32_t parent_load(const int32_t *parent, int32_t x)
 {
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kDuplicateThreads) void ds_duplicate_size_kernel(co
 static dim3 duplicate_grid(int64_t items)
 {
     const int64_t blocks = (items + kDuplicateThreads - 1) / kDuplicateThreads;
-    return dim3(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, g_duplicate_max_blocks))));
+    return dim3(grid_cap(blocks, g_duplicate_max_blocks.get()));
 }
 
 }  // namespace ds
@@ -185,15 +185,7 @@ extern "C" {
 
 int ds_duplicates_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_duplicates_option: null name");
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kDuplicateBlocksLimit, "ds_duplicates_option: max_blocks = %lld out of range [0, %d]",
-                   (long long)value, ds::kDuplicateBlocksLimit);
-        ds::g_duplicate_max_blocks = value == 0 ? ds::kDuplicateMaxBlocks : value;
-        return DS_OK;
-    }
-    ds::set_error("ds_duplicates_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_duplicates_option", ds::g_duplicate_options, name, value);
 }
 
 int ds_duplicate_begin_device(int32_t *d_parent, int64_t n_truth, int64_t *d_counts, void *stream)

@@ -22,8 +22,8 @@
 // ds_misspell_titles_profile: one lane per title as in ds_misspell_titles (ds_training.hip); the rates, the cumulative
 // edit histogram and the substitute / insert tables (24 KiB) sit in LDS next to the lanes' working titles.
 #include <algorithm>
-#include <atomic>
 
+#include "ds_options.h"
 #include "ds_title_ops.h"
 #include "ds_wave.h"
 
@@ -39,8 +39,9 @@ constexpr int kEditBig = 1 << 20;                 // above every distance
 constexpr int64_t kProfileMaxCount = int64_t(1) << 40;
 constexpr int kProfileScaleBits = 30;
 
-static std::atomic<int64_t> g_edit_pairs_per_group{0};   // 0: kEditPairsPerGroup
-static std::atomic<int64_t> g_edit_max_blocks{0};        // 0: kEditMaxBlocks
+static Option g_edit_pairs_per_group{"pairs_per_group", 0, kEditMaxPairsPerGroup, kEditPairsPerGroup, true};
+static Option g_edit_max_blocks{"max_blocks", 0, 65536, kEditMaxBlocks, true};
+static Option *const g_edit_options[] = {&g_edit_pairs_per_group, &g_edit_max_blocks};
 
 struct EditSide {
     const uint8_t *enc, *len;
@@ -429,20 +430,7 @@ extern "C" {
 
 int ds_edit_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_edit_option: null name");
-    if (std::strcmp(name, "pairs_per_group") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kEditMaxPairsPerGroup, "ds_edit_option: pairs_per_group = %lld out of range [0, %d]",
-                   (long long)value, ds::kEditMaxPairsPerGroup);
-        ds::g_edit_pairs_per_group = value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= 65536, "ds_edit_option: max_blocks = %lld out of range [0, 65536]", (long long)value);
-        ds::g_edit_max_blocks = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_edit_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_edit_option", ds::g_edit_options, name, value);
 }
 
 int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_titles *observed,
@@ -467,7 +455,7 @@ int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_
     args.ops = d_ops;
     args.ops_length = d_ops_length;
     args.counts = reinterpret_cast<unsigned long long *>(d_counts);
-    const int64_t max_blocks = ds::g_edit_max_blocks > 0 ? int64_t(ds::g_edit_max_blocks) : ds::kEditMaxBlocks;
+    const int64_t max_blocks = ds::g_edit_max_blocks.get();
 
     // every pair is checked before anything is written; the same pass finds the longest truth title
     ds::DeviceBuffer<int32_t> report;
@@ -475,7 +463,7 @@ int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_
     if (status != DS_OK) return status;
     int32_t found[2] = {0, 0};
     DS_HIP(hipMemsetAsync(report.ptr, 0, 2 * sizeof(int32_t), nullptr));
-    hipLaunchKernelGGL(ds::ds_edit_check_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n + 3) / 4, max_blocks))),
+    hipLaunchKernelGGL(ds::ds_edit_check_kernel, dim3(ds::grid_cap((n + 3) / 4, max_blocks)),
                        dim3(256), 0, nullptr, args, report.ptr);
     DS_HIP(hipGetLastError());
     DS_HIP(hipMemcpy(found, report.ptr, sizeof(found), hipMemcpyDeviceToHost));
@@ -484,13 +472,13 @@ int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_
 
     args.dir_words = (found[1] + 3) / 4;
     const int64_t pair_bytes = ds::kEditPairBytes + int64_t(args.dir_words) * 256;
-    int64_t pairs = ds::g_edit_pairs_per_group > 0 ? int64_t(ds::g_edit_pairs_per_group) : ds::kEditPairsPerGroup;
+    int64_t pairs = ds::g_edit_pairs_per_group.get();
     pairs = std::max<int64_t>(1, std::min(pairs, (ds::kEditLdsLimit - ds::kEditCounterBytes) / pair_bytes));
     const size_t lds = static_cast<size_t>(ds::kEditCounterBytes + pairs * pair_bytes);
     if (lds > 48 * 1024)
         DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds::ds_edit_align_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL(ds::ds_edit_align_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n + pairs - 1) / pairs, max_blocks))),
+    hipLaunchKernelGGL(ds::ds_edit_align_kernel, dim3(ds::grid_cap((n + pairs - 1) / pairs, max_blocks)),
                        dim3(static_cast<unsigned>(64 * pairs)), lds, nullptr, args);
     DS_HIP(hipGetLastError());
     DS_HIP(hipStreamSynchronize(nullptr));

@@ -19,9 +19,8 @@
 //              writes the running list.  Every level shrinks a query's keys by 4096 / n >= 64.
 // One query whose tile holds millions of rows is spread over thousands of workgroups; no atomics, no arrival order.
 #include <algorithm>
-#include <atomic>
 
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -36,7 +35,8 @@ constexpr int kExhaustiveMaxN = 64;
 constexpr int64_t kTilePairsMax = int64_t(1) << 24;
 constexpr int64_t kBytesPerPair = DS_FEATURES_COUNT * 4 + 4 + 8;   // features, probability, pair (q, t)
 
-static std::atomic<int64_t> g_tile_pairs{0};                    // 0: the default (default_tile_pairs)
+static Option g_tile_pairs{"tile_pairs", 0, kTilePairsMax, 0};   // 0: the default (default_tile_pairs)
+static Option *const g_exhaustive_options[] = {&g_tile_pairs};
 
 __device__ __forceinline__ uint64_t exhaustive_key(float probability, int64_t row)
 {
@@ -186,15 +186,7 @@ extern "C" {
 
 int ds_exhaustive_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_exhaustive_option: null name");
-    if (std::strcmp(name, "tile_pairs") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kTilePairsMax, "ds_exhaustive_option: tile_pairs = %lld out of range [0, %lld]",
-                   (long long)value, (long long)ds::kTilePairsMax);
-        ds::g_tile_pairs = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_exhaustive_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_exhaustive_option", ds::g_exhaustive_options, name, value);
 }
 
 int ds_exhaustive_fold_device(const float *d_probabilities, int64_t n_queries, int64_t tile_rows, int64_t row_first,
@@ -257,7 +249,7 @@ int ds_exhaustive_rank_device(ds_titles *queries, ds_titles *truth, ds_forest *f
     DS_HIP(hipSetDevice(truth->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t N = truth->n;
-    const int64_t chosen = ds::g_tile_pairs.load();
+    const int64_t chosen = ds::g_tile_pairs.get();
     const int64_t tile_pairs = chosen > 0 ? chosen : ds::default_tile_pairs();
     // a tile: one query x tile_pairs rows of a long table, or as many whole queries as fit x all rows of a short one
     const int64_t tile_rows = std::min(N, tile_pairs);

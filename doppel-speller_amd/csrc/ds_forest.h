@@ -7,7 +7,7 @@
 // (outcome codes).
 #pragma once
 
-#include "ds_common.h"
+#include "ds_options.h"
 
 namespace ds {
 
@@ -24,6 +24,7 @@ constexpr int kForestThreads = 256;
 constexpr int kForestFeaturesMax = 96;  // LDS staging: kForestThreads x n_features floats (66 for this reference)
 constexpr int kContributionsMaxDepth = 16;  // splits on a root-to-leaf path at most (ds_forest_contributions*)
 constexpr int kRefreshLdsNodesMax = 2048;   // nodes of a tree whose (g, h) sums a refresh workgroup keeps in LDS: 32 KiB
+constexpr int kForestBlocksLimit = 1 << 20; // ds_forest_option("max_blocks") at most
 
 // One element of a root-to-leaf path: all of the path's splits on one feature merged.  A row follows the element when
 // its value v is NaN and nan_follows, or is not NaN and !(v < lo) && !(v >= hi) (a NaN bound stands for "no bound").
@@ -119,9 +120,11 @@ struct ds_forest {
     ds::DeviceBuffer<unsigned long long> counts;    // kCoverCounted: rows that reached each node
     int shape_checked = 0;                          // 0 not yet, 1 every tree is a proper binary tree
     std::vector<int32_t> parent;                    // global parent node of every node, -1 for a root or an unreachable node
-    int64_t max_blocks = 0;                         // ds_forest_option("max_blocks"): 0 = the default of each stage
-    int64_t inspect_jobs_per_block = 0;             // ds_forest_option("inspect_jobs_per_block"): 0 = ds_inspect.hip's choice
-    int64_t refresh_lds_nodes = 0;                  // ds_forest_option("refresh_lds_nodes"): 0 = ds_refresh.hip's table size
+    // ds_forest_option: the cap of every stage's grid (0: the stage's own, max_blocks.value_or(it)), ds_inspect.hip's jobs
+    // per workgroup (0: its choice) and ds_refresh.hip's table size
+    ds::Option max_blocks{"max_blocks", 0, ds::kForestBlocksLimit, 0, true};
+    ds::Option inspect_jobs_per_block{"inspect_jobs_per_block", 0, INT32_MAX, 0};
+    ds::Option refresh_lds_nodes{"refresh_lds_nodes", 0, ds::kRefreshLdsNodesMax, ds::kRefreshLdsNodesMax, true};
     // what the contributions kernels read, derived from the cover when they are first asked for
     bool prepared = false;
     int64_t n_paths = 0;

@@ -29,9 +29,8 @@
 // Capacity: no slot >= capacity is written.  A chunk that would pass the capacity leaves -(pairs needed so far) in *total,
 // every later chunk keeps it negative and writes nothing, and ds_hard_total reports it as DS_E_ARG.
 #include <algorithm>
-#include <atomic>
 
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -45,7 +44,8 @@ constexpr int kHardMaxBlocks = 4096;            // 16 waves per CU in flight on 
 constexpr int kHardBlocksLimit = 1 << 16;
 constexpr int kHardScanThreads = 1024;
 
-static std::atomic<int64_t> g_hard_max_blocks{kHardMaxBlocks};
+static Option g_hard_max_blocks{"max_blocks", 0, kHardBlocksLimit, kHardMaxBlocks, true};
+static Option *const g_hard_options[] = {&g_hard_max_blocks};
 
 // ascending order of the result = ascending order of the (finite) values, -0.0 below +0.0; and back
 __device__ __forceinline__ uint32_t margin_order(float margin)
@@ -189,15 +189,7 @@ extern "C" {
 
 int ds_hard_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_hard_option: null name");
-    if (std::strcmp(name, "max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kHardBlocksLimit, "ds_hard_option: max_blocks = %lld out of range [0, %d]",
-                   (long long)value, ds::kHardBlocksLimit);
-        ds::g_hard_max_blocks = value == 0 ? ds::kHardMaxBlocks : value;
-        return DS_OK;
-    }
-    ds::set_error("ds_hard_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_hard_option", ds::g_hard_options, name, value);
 }
 
 int ds_hard_negatives_device(const int32_t *d_rows, const float *d_margins, int64_t n_queries, int32_t k,
@@ -227,7 +219,7 @@ int ds_hard_negatives_device(const int32_t *d_rows, const float *d_margins, int6
     a.offsets = d_offsets, a.pair_q = d_pair_q, a.pair_t = d_pair_t, a.position = d_position, a.margin = d_margin;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t passes = (n_queries + ds::kHardWaves - 1) / ds::kHardWaves;
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(passes, ds::g_hard_max_blocks)));
+    const dim3 grid(ds::grid_cap(passes, ds::g_hard_max_blocks.get()));
     hipLaunchKernelGGL(ds::ds_hard_count_kernel, grid, dim3(ds::kHardThreads), 0, s, a);
     DS_HIP(hipGetLastError());
     hipLaunchKernelGGL(ds::ds_hard_scan_kernel, dim3(1), dim3(ds::kHardScanThreads), 0, s, d_offsets, n_queries, capacity,

@@ -26,11 +26,10 @@
 //              row the group's largest; every other member is compared column by column with that row; rank = 1 +
 //              verified members behind it in the run (exclusive scan of the verified flags), saturating at 65535
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <memory>
 
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -40,7 +39,9 @@ constexpr int kBuildThreads = 256;
 constexpr int kBuildTile = 2048;   // items of one workgroup in a sort pass or a scan
 constexpr unsigned long long kNoBadColumn = ~0ull;
 
-std::atomic<int64_t> g_duplicate_hash_bits{0};   // 0: all 64 bits of both hashes
+// bits of both row hashes the device build keeps (tests: collisions); 0: all 64
+Option g_duplicate_hash_bits{"duplicate_hash_bits", 0, 64, 64, true};
+Option *const g_index_build_options[] = {&g_duplicate_hash_bits};
 
 inline unsigned blocks_for(int64_t n) { return static_cast<unsigned>((n + kBuildThreads - 1) / kBuildThreads); }
 inline int64_t build_tiles(int64_t n) { return (n + kBuildTile - 1) / kBuildTile; }
@@ -490,15 +491,7 @@ extern "C" {
 
 int ds_index_build_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_index_build_option: null name");
-    if (std::strcmp(name, "duplicate_hash_bits") == 0) {   // bits of both row hashes the device build keeps (tests: collisions)
-        DS_REQUIRE(value >= 0 && value <= 64, "ds_index_build_option: duplicate_hash_bits = %lld out of range [0, 64]",
-                   (long long)value);
-        ds::g_duplicate_hash_bits = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_index_build_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_index_build_option", ds::g_index_build_options, name, value);
 }
 
 int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, const float *idf32, const float *sums32,
@@ -586,11 +579,9 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
                    (long long)bad_column);
     }
 
-    hipDeviceProp_t properties;
-    DS_HIP(hipGetDeviceProperties(&properties, device));
     std::unique_ptr<ds_index, IndexDeleter> index(new ds_index());
     index->device = device;
-    index->compute_units = properties.multiProcessorCount > 0 ? properties.multiProcessorCount : 256;
+    index->compute_units = compute_units(device);
     index->n_truth = N;
     index->n_columns = V;
     index->nnz = nnz;
@@ -655,7 +646,7 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
     DS_BUILD_STEP(hash_a.allocate(static_cast<size_t>(N)));
     DS_BUILD_STEP(hash_b.allocate(static_cast<size_t>(N)));
     DS_BUILD_STEP(hash_bits.allocate(static_cast<size_t>(N)));
-    const int hash_bits_kept = g_duplicate_hash_bits.load() == 0 ? 64 : static_cast<int>(g_duplicate_hash_bits.load());
+    const int hash_bits_kept = static_cast<int>(g_duplicate_hash_bits.get());
     const uint64_t hash_mask = hash_bits_kept == 64 ? ~0ull : (1ull << hash_bits_kept) - 1ull;
     hipLaunchKernelGGL(ds_build_row_walk_kernel, dim3(blocks_for(N)), threads, 0, 0, row_start,
                        static_cast<const void *>(index->row_cols.ptr), wide_cols ? 1 : 0, index->idf32.ptr, index->sig_column.ptr,

@@ -251,9 +251,8 @@ static int inspect_enqueue(ds_forest *forest, const float *d_rows, int64_t n, co
     args.n_jobs = n_jobs;
     args.base_margin = forest->base_margin;
     const int64_t blocks = (n + kForestThreads - 1) / kForestThreads;
-    const int64_t cap = forest->max_blocks ? forest->max_blocks : kInspectMaxRowBlocks;
-    const int64_t row_grid = std::min<int64_t>(blocks, cap);
-    int64_t per_block = forest->inspect_jobs_per_block;
+    const int64_t row_grid = grid_cap(blocks, forest->max_blocks.value_or(kInspectMaxRowBlocks));
+    int64_t per_block = forest->inspect_jobs_per_block.get();
     if (per_block <= 0) {   // enough workgroups for every CU, and as few stagings of a row block as that allows
         const int64_t groups = std::min<int64_t>(n_jobs, (kInspectTargetBlocks + row_grid - 1) / row_grid);
         per_block = (n_jobs + groups - 1) / groups;

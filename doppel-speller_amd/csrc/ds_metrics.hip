@@ -17,9 +17,9 @@
 //                               per workgroup through LDS, then one 64-bit atomic per counter.
 // The log loss is one pass over the column's rows (ds_metric_logloss_kernel) with the same reduction.
 // Every sum is an integer sum and the sorted keys are a function of the keys alone: nothing depends on the schedule.
-#include <atomic>
 
 #include "ds_metrics.h"
+#include "ds_options.h"
 #include "ds_radix.h"
 
 namespace ds {
@@ -223,15 +223,13 @@ int MetricScratch::allocate(int64_t keys, int32_t column_count)
 
 namespace {
 
-std::atomic<int64_t> g_metric_max_blocks{0};   // ds_metrics_option("max_blocks"): 0 = no cap
+Option g_metric_max_blocks{"max_blocks", 0, INT32_MAX, 0};   // 0: no cap
+Option *const g_metrics_options[] = {&g_metric_max_blocks};
 
 unsigned metric_grid(int64_t items, int compute_units, int64_t block_cap)
 {
-    int64_t blocks = std::min<int64_t>((items + kMetricThreads - 1) / kMetricThreads, int64_t(compute_units) * 8);
-    const int64_t own = g_metric_max_blocks.load();
-    if (own > 0) blocks = std::min(blocks, own);
-    if (block_cap > 0) blocks = std::min(blocks, block_cap);
-    return static_cast<unsigned>(std::max<int64_t>(1, blocks));
+    const int64_t blocks = std::min<int64_t>((items + kMetricThreads - 1) / kMetricThreads, int64_t(compute_units) * 8);
+    return grid_cap(blocks, g_metric_max_blocks.get(), block_cap);
 }
 
 }  // namespace
@@ -304,26 +302,13 @@ int device_of(const void *pointer, int *device)
     return DS_OK;
 }
 
-int units_of(int device)
-{
-    hipDeviceProp_t props;
-    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
-        return props.multiProcessorCount;
-    return 256;
-}
-
 }  // namespace
 
 extern "C" {
 
 int ds_metrics_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_metrics_option: name is null");
-    DS_REQUIRE(std::strcmp(name, "max_blocks") == 0, "ds_metrics_option: unknown option '%s'", name);
-    DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_metrics_option: max_blocks = %lld out of range [0, 2^31)",
-               (long long)value);
-    ds::g_metric_max_blocks.store(value);
-    return DS_OK;
+    return ds::set_option("ds_metrics_option", ds::g_metrics_options, name, value);
 }
 
 int ds_auc_device(const float *d_scores, const float *d_labels, int64_t n, int64_t out[5], void *stream)
@@ -334,7 +319,7 @@ int ds_auc_device(const float *d_scores, const float *d_labels, int64_t n, int64
     if (int status = device_of(d_scores, &device); status != DS_OK) return status;
     DS_HIP(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int units = units_of(device);
+    const int units = ds::compute_units(device);
     // the row lists, then (the negatives are counted by then) the sort buffers: both against the free HBM, the second
     // for the worst case that every row is a negative
     if (int status = ds::train_check_free(4 * n + ds::MetricScratch::bytes(n, 1), "ds_auc_device"); status != DS_OK)
@@ -412,7 +397,7 @@ int ds_weighted_logloss_device(const float *d_margins, const float *d_labels, in
     ds::DeviceBuffer<unsigned long long> sum;
     if (int status = sum.allocate(1); status != DS_OK) return status;
     DS_HIP(hipMemsetAsync(sum.ptr, 0, sum.bytes(), s));
-    hipLaunchKernelGGL(ds::ds_metric_logloss_rows_kernel, dim3(ds::metric_grid(n, units_of(device), 0)),
+    hipLaunchKernelGGL(ds::ds_metric_logloss_rows_kernel, dim3(ds::metric_grid(n, ds::compute_units(device), 0)),
                        dim3(ds::kMetricThreads), 0, s, d_margins, d_labels, n, beta, sum.ptr);
     DS_HIP(hipGetLastError());
     unsigned long long host = 0ull;

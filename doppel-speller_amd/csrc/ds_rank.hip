@@ -19,9 +19,8 @@
 //                          again every round.  n * ceil(k / 64) loads per lane: cheap for the few best of a long list.
 // Both write every one of the n slots of every query exactly once, from the same keys: the result is the same.
 #include <algorithm>
-#include <atomic>
 
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -31,7 +30,8 @@ constexpr int kRankWaves = kRankThreads / 64;   // queries per workgroup and pas
 constexpr int kRankLdsKeys = 512;               // keys of one query in LDS: 4 KiB per wave, 16 KiB per workgroup
 constexpr int kRankMaxBlocks = 4096;            // 16 waves per CU in flight on 256 CUs; more queries: the grid strides
 
-static std::atomic<int> g_rank_lds_keys{kRankLdsKeys};
+static Option g_rank_lds_keys{"lds_keys", 0, kRankLdsKeys, kRankLdsKeys};   // 0: every query takes the select kernel
+static Option *const g_rank_options[] = {&g_rank_lds_keys};
 
 struct RankHead {
     int32_t row;     // -1: the query has no head
@@ -188,15 +188,7 @@ extern "C" {
 
 int ds_rank_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_rank_option: null name");
-    if (std::strcmp(name, "lds_keys") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kRankLdsKeys, "ds_rank_option: lds_keys = %lld out of range [0, %d]",
-                   (long long)value, ds::kRankLdsKeys);
-        ds::g_rank_lds_keys = static_cast<int>(value);
-        return DS_OK;
-    }
-    ds::set_error("ds_rank_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_rank_option", ds::g_rank_options, name, value);
 }
 
 int ds_rank_matches_device(const int32_t *d_rows, const float *d_predictions, const uint8_t *d_ratios,
@@ -212,8 +204,8 @@ int ds_rank_matches_device(const int32_t *d_rows, const float *d_predictions, co
     DS_REQUIRE(n_queries <= INT64_MAX / k, "ds_rank_matches_device: too many pairs");
     if (n_queries == 0) return DS_OK;
     const int64_t passes = (n_queries + ds::kRankWaves - 1) / ds::kRankWaves;
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(passes, ds::kRankMaxBlocks)));
-    if (k <= ds::g_rank_lds_keys)
+    const dim3 grid(ds::grid_cap(passes, ds::kRankMaxBlocks));
+    if (k <= ds::g_rank_lds_keys.get())
         hipLaunchKernelGGL(ds::ds_rank_lds_kernel, grid, dim3(ds::kRankThreads), 0, static_cast<hipStream_t>(stream), d_rows,
                            d_predictions, d_ratios, d_exact_row, d_best_row, n_queries, k, n, n_truth, d_out_row,
                            d_out_probability, d_out_ratio, d_out_stage);

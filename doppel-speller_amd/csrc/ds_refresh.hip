@@ -227,10 +227,7 @@ int refresh_run(const char *who, const RefreshCall &c, const float *d_rows, cons
     DS_HIP(hipSetDevice(forest->device));
     int status = train_check_free(refresh_work_bytes(c), who);
     if (status != DS_OK) return status;
-    int compute_units = 256;
-    if (hipDeviceGetAttribute(&compute_units, hipDeviceAttributeMultiprocessorCount, forest->device) != hipSuccess ||
-        compute_units <= 0)
-        compute_units = 256;
+    const int units = compute_units(forest->device);
     DeviceBuffer<float> values, leafsum, eval_leafsum, d_labels, d_eval_labels, d_weights, d_margins, d_trace;
     DeviceBuffer<int32_t> leaf_of, eval_leaf_of;
     DeviceBuffer<unsigned long long> sums, errors;
@@ -253,10 +250,9 @@ int refresh_run(const char *who, const RefreshCall &c, const float *d_rows, cons
     DS_HIP(hipMemsetAsync(sums.ptr, 0, sums.bytes(), stream));
     DS_HIP(hipMemsetAsync(errors.ptr, 0, errors.bytes(), stream));
 
-    const int64_t table = forest->refresh_lds_nodes ? forest->refresh_lds_nodes : kRefreshLdsNodesMax;
+    const int64_t table = forest->refresh_lds_nodes.get();
     auto grid = [&](int64_t items) {   // the trainers' row grid and cap, and the forest's own cap
-        const unsigned blocks = train_row_grid(compute_units, items);
-        return forest->max_blocks ? std::min<unsigned>(blocks, static_cast<unsigned>(forest->max_blocks)) : blocks;
+        return grid_cap(train_row_grid(units, items), forest->max_blocks.get());
     };
     if (n_eval > 0) {
         hipLaunchKernelGGL(ds_refresh_initial_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, forest->view(),

@@ -6,6 +6,7 @@
 
 #include "ds_common.h"
 #include "ds_host.h"
+#include "ds_options.h"
 
 namespace ds {
 
@@ -25,6 +26,28 @@ int hip_failed(hipError_t error, const char *what, const char *file, int line)
 {
     set_error("HIP error %d (%s) at %s:%d in %s", static_cast<int>(error), hipGetErrorString(error), file, line, what);
     return DS_E_HIP;
+}
+
+int compute_units(int device)
+{
+    int count = 0;
+    if (hipDeviceGetAttribute(&count, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || count <= 0) return 256;
+    return count;
+}
+
+int set_option(const char *entry, Option *const *table, int count, const char *name, int64_t value)
+{
+    DS_REQUIRE(name != nullptr, "%s: null name", entry);
+    Option *option = nullptr;
+    for (int i = 0; i < count && option == nullptr; ++i)
+        if (std::strcmp(name, table[i]->name) == 0) option = table[i];
+    DS_REQUIRE(option != nullptr, "%s: unknown option '%s'", entry, name);
+    const bool zero_allowed = option->zero_is_default && option->low > 0;
+    DS_REQUIRE((value >= option->low && value <= option->high) || (value == 0 && option->zero_is_default),
+               "%s: %s = %lld out of range %s[%lld, %lld]", entry, name, (long long)value, zero_allowed ? "0 or " : "",
+               (long long)option->low, (long long)option->high);
+    option->raw.store(value);
+    return DS_OK;
 }
 
 // fn(thread, column, first posting, last posting) for every column's postings whose rows fall into the thread's row range:
@@ -568,11 +591,9 @@ int ds_index_create(const int64_t *rowptr, const int32_t *truth_idx, const float
     std::vector<float> &tile_sums_min = image.tile_sums_min;
     std::vector<int8_t> &sig_column = image.sig_column;
     DS_HIP(hipSetDevice(device));
-    hipDeviceProp_t properties;
-    DS_HIP(hipGetDeviceProperties(&properties, device));
     ds_index *index = new ds_index();
     index->device = device;
-    index->compute_units = properties.multiProcessorCount > 0 ? properties.multiProcessorCount : 256;
+    index->compute_units = ds::compute_units(device);
     index->n_truth = N;
     index->n_columns = V;
     index->nnz = nnz;

@@ -25,11 +25,10 @@
 // reduction, no LDS traffic per candidate).  gridDim.y tiles t so that a tile's counters fit kSweepLdsBytes of LDS
 // (64 thresholds at U <= 46, 15 at U = 256: three workgroups per CU at the most); gridDim.x strides over the queries.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 #include "ds_bootstrap_draw.h"
-#include "ds_common.h"
+#include "ds_options.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -42,7 +41,7 @@ constexpr int kSweepMaxT = 101, kSweepMaxU = 256;
 constexpr int kSweepLdsBytes = 48 * 1024;
 constexpr int64_t kSweepMaxQueries = int64_t(1) << 40;   // uint32 counters in LDS: a workgroup sees < 2^32 queries
 
-static std::atomic<int64_t> g_sweep_queries_per_group{kSweepQueriesPerGroup};
+static Option g_sweep_queries_per_group{"queries_per_group", 0, int64_t(1) << 30, kSweepQueriesPerGroup, true};
 
 struct SweepArgs {
     const int32_t *rows;          // [n_queries][k]
@@ -238,9 +237,12 @@ constexpr int kSweepBootRowThreads = 256;
 constexpr int kSweepBootScanThreads = 1024;
 
 // for tests (ds_sweep_option); no result depends on them
-static std::atomic<int64_t> g_sweep_boot_tile{0};                  // thresholds per tile; 0: what kSweepBootWaveBytes holds
-static std::atomic<int64_t> g_sweep_boot_max_blocks{0};            // 0: kSweepBootMaxBlocks
-static std::atomic<int64_t> g_sweep_boot_replicates_per_group{0};  // 0: kSweepBootReplicatesPerGroup
+static Option g_sweep_boot_tile{"bootstrap_tile", 0, 64, 0};   // thresholds per tile; 0: what kSweepBootWaveBytes holds
+static Option g_sweep_boot_max_blocks{"bootstrap_max_blocks", 0, 65535, kSweepBootMaxBlocks, true};
+static Option g_sweep_boot_replicates_per_group{"bootstrap_replicates_per_group", 0, kSweepBootMax + 1,
+                                                kSweepBootReplicatesPerGroup, true};
+static Option *const g_sweep_options[] = {&g_sweep_queries_per_group, &g_sweep_boot_tile, &g_sweep_boot_max_blocks,
+                                          &g_sweep_boot_replicates_per_group};
 
 struct SweepBootArgs {
     const uint16_t *records;       // [n][T]
@@ -408,7 +410,7 @@ static int sweep_boot_tile(int32_t T, int32_t U)
 {
     const int fits = kSweepBootWaveBytes / ((4 + 3 * U) * static_cast<int>(sizeof(uint32_t)));
     int tile = std::max(1, std::min({static_cast<int>(T), 64, fits}));
-    const int64_t forced = g_sweep_boot_tile;
+    const int64_t forced = g_sweep_boot_tile.get();
     if (forced > 0) tile = static_cast<int>(std::min<int64_t>(forced, tile));
     return tile;
 }
@@ -452,10 +454,10 @@ static int sweep_check(const char *what, int64_t n_queries, int32_t k, const int
     return DS_OK;
 }
 
-static int64_t sweep_query_groups(int64_t n_queries)
+static unsigned sweep_query_groups(int64_t n_queries)
 {
-    const int64_t per_group = std::max<int64_t>(g_sweep_queries_per_group, kSweepWaves);
-    return std::min<int64_t>((n_queries + per_group - 1) / per_group, kSweepMaxBlocks);
+    const int64_t per_group = std::max<int64_t>(g_sweep_queries_per_group.get(), kSweepWaves);
+    return grid_cap((n_queries + per_group - 1) / per_group, kSweepMaxBlocks);
 }
 
 }  // namespace ds
@@ -464,33 +466,7 @@ extern "C" {
 
 int ds_sweep_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_sweep_option: null name");
-    if (std::strcmp(name, "queries_per_group") == 0) {
-        DS_REQUIRE(value >= 0 && value <= (int64_t(1) << 30),
-                   "ds_sweep_option: queries_per_group = %lld out of range [0, 2^30]", (long long)value);
-        ds::g_sweep_queries_per_group = value == 0 ? ds::kSweepQueriesPerGroup : value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "bootstrap_tile") == 0) {
-        DS_REQUIRE(value >= 0 && value <= 64, "ds_sweep_option: bootstrap_tile = %lld out of range [0, 64]", (long long)value);
-        ds::g_sweep_boot_tile = value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "bootstrap_max_blocks") == 0) {
-        DS_REQUIRE(value >= 0 && value <= 65535, "ds_sweep_option: bootstrap_max_blocks = %lld out of range [0, 65535]",
-                   (long long)value);
-        ds::g_sweep_boot_max_blocks = value;
-        return DS_OK;
-    }
-    if (std::strcmp(name, "bootstrap_replicates_per_group") == 0) {
-        DS_REQUIRE(value >= 0 && value <= ds::kSweepBootMax + 1,
-                   "ds_sweep_option: bootstrap_replicates_per_group = %lld out of range [0, %d]", (long long)value,
-                   ds::kSweepBootMax + 1);
-        ds::g_sweep_boot_replicates_per_group = value;
-        return DS_OK;
-    }
-    ds::set_error("ds_sweep_option: unknown option '%s'", name);
-    return DS_E_ARG;
+    return ds::set_option("ds_sweep_option", ds::g_sweep_options, name, value);
 }
 
 int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const uint8_t *d_r, const uint8_t *d_s,
@@ -512,7 +488,7 @@ int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const u
     args.n_queries = n_queries; args.k = k; args.T = T; args.U = U;
     const int per_t_bytes = (4 + 3 * (U + 1)) * static_cast<int>(sizeof(uint32_t));
     args.tile_t = std::max(1, std::min({static_cast<int>(T), 64, ds::kSweepLdsBytes / per_t_bytes}));
-    const dim3 grid(static_cast<unsigned>(ds::sweep_query_groups(n_queries)), static_cast<unsigned>((T + args.tile_t - 1) / args.tile_t));
+    const dim3 grid(ds::sweep_query_groups(n_queries), static_cast<unsigned>((T + args.tile_t - 1) / args.tile_t));
     hipLaunchKernelGGL(ds::ds_threshold_sweep_kernel, grid, dim3(ds::kSweepThreads),
                        static_cast<size_t>(args.tile_t) * per_t_bytes, queue, args);
     DS_HIP(hipGetLastError());
@@ -534,7 +510,7 @@ int ds_sweep_records_device(const int32_t *d_rows, const uint8_t *d_d, const uin
     args.rows = d_rows; args.d = d_d; args.r = d_r; args.s = d_s; args.predictions = d_predictions;
     args.exact = d_exact; args.actual = d_actual_row; args.lev = d_lev; args.prob = d_prob;
     args.n_queries = n_queries; args.k = k; args.T = T; args.U = U; args.tile_t = 64;
-    const dim3 grid(static_cast<unsigned>(ds::sweep_query_groups(n_queries)), static_cast<unsigned>((T + 63) / 64));
+    const dim3 grid(ds::sweep_query_groups(n_queries), static_cast<unsigned>((T + 63) / 64));
     hipLaunchKernelGGL(ds::ds_sweep_records_kernel, grid, dim3(ds::kSweepThreads), 0, nullptr, args, d_records);
     DS_HIP(hipGetLastError());
     return DS_OK;
@@ -576,9 +552,8 @@ int ds_sweep_bootstrap_device(const uint16_t *d_records, int64_t n, int32_t T, i
         if (status != DS_OK) return status;
         DS_HIP(hipMemsetAsync(sizes.ptr, 0, sizes.bytes(), nullptr));
     }
-    const int64_t cap = ds::g_sweep_boot_max_blocks ? static_cast<int64_t>(ds::g_sweep_boot_max_blocks) : ds::kSweepBootMaxBlocks;
-    const dim3 rows(static_cast<unsigned>(
-        std::min<int64_t>((n + ds::kSweepBootRowThreads - 1) / ds::kSweepBootRowThreads, cap)));
+    const int64_t cap = ds::g_sweep_boot_max_blocks.get();
+    const dim3 rows(ds::grid_cap((n + ds::kSweepBootRowThreads - 1) / ds::kSweepBootRowThreads, cap));
     hipLaunchKernelGGL(ds::ds_sweep_bootstrap_check_kernel, rows, dim3(ds::kSweepBootRowThreads), 0, nullptr, d_records,
                        d_unit, n, T, U, n_units, sizes.ptr, errors.ptr);
     DS_HIP(hipGetLastError());
@@ -614,12 +589,10 @@ int ds_sweep_bootstrap_device(const uint16_t *d_records, int64_t n, int32_t T, i
     args.tile_t = ds::sweep_boot_tile(T, U);
     args.n_tiles = (T + args.tile_t - 1) / args.tile_t;
     const int64_t replicates = static_cast<int64_t>(n_boot) + 1;   // and the baseline
-    int64_t per_group = ds::g_sweep_boot_replicates_per_group;
-    if (per_group <= 0) per_group = ds::kSweepBootReplicatesPerGroup;
-    per_group = std::min(per_group, replicates);
+    const int64_t per_group = std::min(ds::g_sweep_boot_replicates_per_group.get(), replicates);
     args.per_group = static_cast<int32_t>(per_group);
     args.n_groups = static_cast<int32_t>((replicates + per_group - 1) / per_group);
-    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(args.n_groups, cap));
+    const unsigned grid = ds::grid_cap(args.n_groups, cap);
     const size_t lds = static_cast<size_t>(ds::kSweepBootWaves) * (4 + 3 * U) * args.tile_t * sizeof(uint32_t);
     const int status = units ? ds::sweep_boot_launch<true>(args, grid, lds) : ds::sweep_boot_launch<false>(args, grid, lds);
     if (status != DS_OK) return status;

@@ -8,6 +8,7 @@
 
 #include "ds_common.h"
 #include "ds_forest.h"
+#include "ds_options.h"
 
 namespace ds {
 
@@ -157,8 +158,7 @@ int train_create_setup(const char *who, int device, int32_t n_features, const fl
                        int *compute_units);
 // The grid of a kernel that strides over `items` rows: at most 8 workgroups per CU, and at most the test cap
 // (ds_trainer_batch_option("max_blocks"), 0 = none) where one is set.  The results do not depend on it.
-void train_set_max_blocks(int64_t blocks);
-int64_t train_max_blocks();
+extern Option g_train_max_blocks;
 unsigned train_row_grid(int compute_units, int64_t items);
 // Enqueues one round for the n_active models of v.active on `stream` and does not synchronise: clear, the gradients
 // (with `sampling`: the feature masks, then the gradients of the rows drawn), then per level < depth (the largest

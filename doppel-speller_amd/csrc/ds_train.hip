@@ -19,7 +19,6 @@
 // kernels through the same launcher with the model as a further grid dimension.
 // Continuing from a model (ds_trainer_seed, DESIGN.md section 9 "Continuing from a model"): before the first round
 // ds_train_seed_kernel sets leafsum to a forest's leaf sums of the RAW rows, and the trees count on from the forest's.
-#include <atomic>
 
 #include "ds_forest.h"
 #include "ds_metrics.h"
@@ -384,9 +383,7 @@ int train_create_setup(const char *who, int device, int32_t n_features, const fl
                        hipStream_t *stream, DeviceBuffer<float> &d_cuts, DeviceBuffer<int32_t> &d_cut_offsets,
                        int *compute_units)
 {
-    hipDeviceProp_t props;
-    if (hipGetDeviceProperties(&props, device) == hipSuccess && props.multiProcessorCount > 0)
-        *compute_units = props.multiProcessorCount;
+    *compute_units = ds::compute_units(device);
     if (hipStreamCreateWithFlags(stream, hipStreamNonBlocking) != hipSuccess) {
         set_error("%s: hipStreamCreate failed", who);
         return DS_E_HIP;
@@ -448,15 +445,9 @@ int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *f
 }
 
 // ---- one round of either trainer --------------------------------------------------------------------------------------
+Option g_train_max_blocks{"max_blocks", 0, INT32_MAX, 0};   // 0: no cap
+
 namespace {
-
-std::atomic<int64_t> g_max_blocks{0};   // ds_trainer_batch_option("max_blocks"): 0 = no cap
-
-int64_t capped(int64_t blocks)
-{
-    const int64_t cap = g_max_blocks.load();
-    return std::max<int64_t>(1, cap > 0 ? std::min(blocks, cap) : blocks);
-}
 
 template <bool kFolds, bool kSampled, bool kMonotone>
 int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingView &s, int32_t n_active, int32_t depth,
@@ -482,10 +473,10 @@ int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingVie
         const int64_t groups = int64_t(feature_groups) * node_groups * n_active;
         // about 4 workgroups per CU in all, counted over the models, each over at least 2048 rows: the LDS adds dominate,
         // the flush (<= 8192 global adds per workgroup) stays a small part
-        const int64_t chunks = capped(std::min<int64_t>((v.n + 2047) / 2048,
-                                                        (int64_t(compute_units) * 4 + groups - 1) / groups));
+        const unsigned chunks = grid_cap(std::min<int64_t>((v.n + 2047) / 2048, (int64_t(compute_units) * 4 + groups - 1) / groups),
+                                         g_train_max_blocks.get());
         hipLaunchKernelGGL((ds_train_histogram_kernel<kFolds, kSampled>),
-                           dim3(static_cast<unsigned>(chunks), feature_groups * node_groups, models), dim3(kHistThreads),
+                           dim3(chunks, feature_groups * node_groups, models), dim3(kHistThreads),
                            0, stream, v, level, n_built, nodes_per_group, features_per_group, feature_groups);
         DS_HIP(hipGetLastError());
         hipLaunchKernelGGL((ds_train_split_feature_kernel<kSampled, kMonotone>), dim3(1u << level, v.nf, models),
@@ -502,13 +493,10 @@ int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingVie
 
 }  // namespace
 
-void train_set_max_blocks(int64_t blocks) { g_max_blocks.store(blocks); }
-int64_t train_max_blocks() { return g_max_blocks.load(); }
-
 unsigned train_row_grid(int compute_units, int64_t items)
 {
-    return static_cast<unsigned>(capped(std::min<int64_t>((items + kRowThreads - 1) / kRowThreads,
-                                                          int64_t(compute_units) * 8)));
+    return grid_cap(std::min<int64_t>((items + kRowThreads - 1) / kRowThreads, int64_t(compute_units) * 8),
+                    g_train_max_blocks.get());
 }
 
 int train_round_enqueue(hipStream_t stream, const TrainView &v, const TrainSamplingView *sampling, int32_t n_active,

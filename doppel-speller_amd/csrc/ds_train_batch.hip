@@ -322,12 +322,8 @@ void ds_trainer_batch_destroy(ds_trainer_batch *batch)
 
 int ds_trainer_batch_option(const char *name, int64_t value)
 {
-    DS_REQUIRE(name != nullptr, "ds_trainer_batch_option: name is null");
-    DS_REQUIRE(std::strcmp(name, "max_blocks") == 0, "ds_trainer_batch_option: unknown option '%s'", name);
-    DS_REQUIRE(value >= 0 && value <= INT32_MAX, "ds_trainer_batch_option: max_blocks = %lld out of range [0, 2^31)",
-               (long long)value);
-    ds::train_set_max_blocks(value);
-    return DS_OK;
+    ds::Option *const table[] = {&ds::g_train_max_blocks};
+    return ds::set_option("ds_trainer_batch_option", table, name, value);
 }
 
 int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractions, const uint64_t *sample_seeds)
@@ -601,7 +597,7 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     if (b->metric_flags) {   // over the margins the partition kernels have just written
         if (int status = ds::metrics_enqueue(stream, b->compute_units, b->metric_flags, b->metric_columns.ptr,
                                              b->active.ptr, n_active, b->metric_keys, b->metric_pos, b->metric_fold_rows,
-                                             b->metric_scratch, b->metric_counters.ptr, ds::train_max_blocks());
+                                             b->metric_scratch, b->metric_counters.ptr, ds::g_train_max_blocks.get());
             status != DS_OK)
             return status;
         DS_HIP(hipMemcpyAsync(b->pinned_metrics, b->metric_counters.ptr, b->metric_counters.bytes(),

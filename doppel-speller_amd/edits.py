@@ -228,7 +228,7 @@ def _table(titles, transform, device, what):
 
 def edit_option(name, value):
     """ds_edit_option, for tests: "pairs_per_group", "max_blocks" (0 = the default).  No result depends on them."""
-    _lib.check(_lib.lib().ds_edit_option(name.encode(), int(value)), "ds_edit_option")
+    _lib.set_option("ds_edit_option", name, value)
 
 
 def align_tables(truth, truth_rows, observed, observed_rows, n, max_edits, d_distance=None, d_ops=None,

@@ -161,7 +161,7 @@ class TitleTable:
 
     def option(self, name, value):
         """ds_titles_option, e.g. option("truth_records", 0): no per-row records of the truth-only features (160 B of HBM per row)."""
-        _lib.check(_lib.lib().ds_titles_option(self.handle, name.encode(), int(value)), "ds_titles_option")
+        _lib.set_option("ds_titles_option", name, value, self.handle)
 
     def close(self):
         if self.handle:

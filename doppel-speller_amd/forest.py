@@ -651,7 +651,7 @@ class ForestModel:
         kernels and of refresh's row kernels; option("inspect_jobs_per_block", v) sets the jobs an inspection workgroup
         runs per staged row block; option("refresh_lds_nodes", v) the largest tree (in nodes, at most 2048) whose sums a
         refresh workgroup keeps in LDS, a larger tree adding straight to HBM."""
-        _lib.check(_lib.lib().ds_forest_option(self.handle, name.encode(), int(value)), "ds_forest_option")
+        _lib.set_option("ds_forest_option", name, value, self.handle)
 
     def predict_contributions(self, rows, approximate=False):
         """float64[n, n_features + 1] for a host float32[n, n_features] matrix: per row the contribution of every

@@ -111,7 +111,7 @@ class TruthIndex:
 
     def option(self, name, value):
         """Diagnostics switch of the index (ds_index_option), e.g. option("count_bytes", 1)."""
-        _lib.check(_lib.lib().ds_index_option(self.handle, name.encode(), int(value)), "ds_index_option")
+        _lib.set_option("ds_index_option", name, value, self.handle)
 
     def top_k(self, q_rowptr, q_cols, q_maxint, k):
         """fast_jaccard + fast_arg_top_k for a batch: int32[Q, k] truth rows, descending row index per query."""

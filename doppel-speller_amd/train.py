@@ -80,7 +80,7 @@ def compute_cuts_device(d_features, n, max_bin=256, n_features=None, device=None
 
 def cuts_option(name, value):
     """ds_cuts_option, for tests: cuts_option("column_group", g) sorts g columns at a time (0: sized from free HBM)."""
-    _lib.check(_lib.lib().ds_cuts_option(name.encode(), int(value)), "ds_cuts_option")
+    _lib.set_option("ds_cuts_option", name, value)
 
 
 def _device_columns(d_features, n_features):
@@ -180,7 +180,7 @@ def metric_values(counts, metrics):
 
 def metrics_option(name, value):
     """ds_metrics_option, for tests: metrics_option("max_blocks", b) caps the metric kernels' row grids (0: default)."""
-    _lib.check(_lib.lib().ds_metrics_option(name.encode(), int(value)), "ds_metrics_option")
+    _lib.set_option("ds_metrics_option", name, value)
 
 
 def _scores(values, what, non_empty=False):

@@ -273,7 +273,7 @@ def batch_metrics_bytes(n, n_models, n_folds):
 
 def batch_option(name, value):
     """ds_trainer_batch_option, for tests: batch_option("max_blocks", b) caps the row grids (0: default)."""
-    _lib.check(_lib.lib().ds_trainer_batch_option(name.encode(), int(value)), "ds_trainer_batch_option")
+    _lib.set_option("ds_trainer_batch_option", name, value)
 
 
 class ForestTrainerBatch(_TrainerHandle):

@@ -15,6 +15,13 @@
  *   - a handle is bound to one device, owns its device memory, and is NOT thread-safe (one caller at a time,
  *     like the reference's single Python thread);
  *   - there is no CPU fallback: without a usable GPU every compute entry point fails with DS_E_HIP.
+ *
+ * Options
+ *   The ds_*_option(name, value) setters are for tests: they move launch decisions (grid caps, tile sizes, the
+ *   threshold between two kernels), and no result depends on an option.  An option is process-wide unless its setter
+ *   takes a handle.  0 restores the default where the option's comment below says so.  A null name, an unknown name or
+ *   a value outside the stated range changes nothing and returns DS_E_ARG, with the message
+ *   "<setter>: <option> = <value> out of range [low, high]" for the last of the three.
  */
 #ifndef DOPPEL_AMD_H
 #define DOPPEL_AMD_H
