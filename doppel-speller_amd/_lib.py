@@ -111,13 +111,10 @@ def _compile_and_link(sources, target, wanted, verbose, extra=()):
         os.replace(linked, target)
 
 
-def _declare(handle):
+def _signatures():
+    # every entry point but ds_last_error and ds_build_id: (name -> argument types, result type) per kind of result
     c = ctypes
     p = c.c_void_p
-    handle.ds_last_error.restype = c.c_char_p
-    handle.ds_last_error.argtypes = []
-    handle.ds_build_id.restype = c.c_char_p
-    handle.ds_build_id.argtypes = []
     signatures = {
         "ds_version": [],
         "ds_device_count": [c.POINTER(c.c_int)],
@@ -262,15 +259,23 @@ def _declare(handle):
         "ds_timer_stop": [p, p],
         "ds_timer_elapsed_ms": [p, c.POINTER(c.c_float)],
     }
-    # an older library named by DS_LIBRARY for an A/B measurement: entry points added since are simply absent
-    stale_allowed = os.environ.get("DS_ALLOW_STALE_LIBRARY") == "1"
     returns_int64 = {"ds_remaining_pairs_counts_size": [c.c_int64],
                      "ds_trainer_batch_bytes": [c.c_int64, c.c_int32, c.c_int32, c.c_int32],
                      "ds_trainer_batch_metrics_bytes": [c.c_int64, c.c_int32, c.c_int32]}
     returns_nothing = {name: [p] for name in (
         "ds_index_destroy", "ds_titles_destroy", "ds_timer_destroy", "ds_problem_destroy", "ds_forest_destroy",
         "ds_trainer_destroy", "ds_query_space_destroy", "ds_trainer_batch_destroy")}
-    for group, restype in ((signatures, c.c_int), (returns_int64, c.c_int64), (returns_nothing, None)):
+    return ((signatures, c.c_int), (returns_int64, c.c_int64), (returns_nothing, None))
+
+
+def _declare(handle):
+    handle.ds_last_error.restype = ctypes.c_char_p
+    handle.ds_last_error.argtypes = []
+    handle.ds_build_id.restype = ctypes.c_char_p
+    handle.ds_build_id.argtypes = []
+    # an older library named by DS_LIBRARY for an A/B measurement: entry points added since are simply absent
+    stale_allowed = os.environ.get("DS_ALLOW_STALE_LIBRARY") == "1"
+    for group, restype in _signatures():
         for name, argtypes in group.items():
             if stale_allowed and not hasattr(handle, name):
                 continue
@@ -280,39 +285,7 @@ def _declare(handle):
     return handle
 
 
-EXPORTED_SYMBOLS = (
-    "ds_last_error", "ds_version", "ds_build_id", "ds_device_count", "ds_device_name", "ds_device_memory", "ds_index_create", "ds_index_destroy",
-    "ds_index_duplicate_ranks", "ds_index_image_digest", "ds_index_option",
-    "ds_index_info", "ds_jaccard_topk", "ds_jaccard_topk_device", "ds_jaccard_sync", "ds_jaccard_status", "ds_construct_features",
-    "ds_titles_create", "ds_titles_destroy", "ds_titles_option", "ds_construct_features_indexed", "ds_construct_features_indexed_device",
-    "ds_levenshtein_ratio_batch", "ds_levenshtein_ratio", "ds_close_matches", "ds_close_matches_device", "ds_remaining_pairs_counts_size", "ds_remaining_pairs_device",
-    "ds_select_matches_device", "ds_exact_matches", "ds_exact_matches_device", "ds_problem_create",
-    "ds_problem_destroy", "ds_problem_info", "ds_problem_arrays", "ds_transform_titles", "ds_encode_titles", "ds_truth_word_counts", "ds_forest_create", "ds_forest_destroy",
-    "ds_forest_predict", "ds_forest_predict_device", "ds_trainer_create", "ds_trainer_destroy", "ds_trainer_set_labels",
-    "ds_trainer_set_eval", "ds_trainer_step", "ds_trainer_read", "ds_misspell_titles", "ds_titles_read",
-    "ds_training_pairs_device", "ds_prepare_titles", "ds_query_space_create", "ds_query_space_destroy",
-    "ds_query_rows_device", "ds_malloc", "ds_free", "ds_memcpy_h2d", "ds_memcpy_d2h", "ds_memset",
-    "ds_stream_sync", "ds_memcpy_d2d_async", "ds_stream_create", "ds_stream_destroy", "ds_timer_create", "ds_timer_destroy", "ds_timer_start", "ds_timer_stop",
-    "ds_timer_elapsed_ms", "ds_feature_cuts_device", "ds_cuts_option", "ds_trainer_create_device",
-    "ds_trainer_set_eval_device", "ds_gather_rows_device", "ds_rank_matches_device", "ds_rank_option",
-    "ds_exhaustive_fold_device", "ds_exhaustive_finish_device", "ds_exhaustive_rank_device", "ds_exhaustive_option",
-    "ds_close_parts_device", "ds_threshold_sweep_device", "ds_sweep_option", "ds_duplicate_begin_device",
-    "ds_duplicate_links_device", "ds_duplicate_finish_device", "ds_duplicates_option", "ds_forest_cover_device",
-    "ds_forest_cover_set", "ds_forest_cover_read", "ds_forest_cover_clear", "ds_forest_option",
-    "ds_forest_contributions_device", "ds_forest_contributions", "ds_best_pairs_device", "ds_trainer_batch_create",
-    "ds_trainer_batch_create_device", "ds_trainer_batch_destroy", "ds_trainer_batch_step", "ds_trainer_batch_read",
-    "ds_trainer_batch_bytes", "ds_trainer_batch_option", "ds_trainer_set_sampling", "ds_trainer_batch_set_sampling",
-    "ds_auc_device", "ds_auc", "ds_weighted_logloss_device", "ds_metrics_option", "ds_trainer_set_metrics",
-    "ds_trainer_metrics", "ds_trainer_batch_set_metrics", "ds_trainer_batch_metrics", "ds_trainer_batch_metrics_bytes",
-    "ds_index_create_device", "ds_index_read", "ds_index_build_option", "ds_assign_edges_device",
-    "ds_assign_solve_device", "ds_assign_option", "ds_trainer_seed", "ds_trainer_seed_device", "ds_trainer_batch_seed",
-    "ds_trainer_batch_seed_device", "ds_hard_negatives_device", "ds_hard_total", "ds_hard_option",
-    "ds_trainer_set_weights", "ds_trainer_batch_set_weights", "ds_trainer_set_monotone",
-    "ds_trainer_batch_set_monotone", "ds_forest_inspect_device", "ds_forest_inspect", "ds_forest_refresh",
-    "ds_forest_refresh_device", "ds_bootstrap_counts_device", "ds_bootstrap_counts", "ds_bootstrap_option",
-    "ds_outcome_codes_device", "ds_isotonic_fit_device", "ds_isotonic_fit", "ds_calibration_apply_device",
-    "ds_reliability_device", "ds_calibrate_option", "ds_sweep_records_device", "ds_sweep_bootstrap_device",
-    "ds_edit_align", "ds_edit_option", "ds_misspell_titles_profile")
+EXPORTED_SYMBOLS = ("ds_last_error", "ds_build_id") + tuple(name for group, _ in _signatures() for name in group)
 
 
 def lib():

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_wave.h"
 
@@ -223,9 +224,8 @@ int ds_assign_edges_device(const int32_t *d_row, const float *d_probability, con
     args.edge_key = d_edge_key; args.edge_row = d_edge_row;
     args.q_first = q_first; args.n_slots = n_queries * n; args.n = n; args.n_truth = static_cast<int32_t>(n_truth);
     args.threshold = probability_threshold;
-    hipLaunchKernelGGL(ds::ds_assign_edges_kernel, ds::assign_grid(args.n_slots), dim3(ds::kAssignThreads), 0,
-                       static_cast<hipStream_t>(stream), args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_assign_edges_kernel, ds::assign_grid(args.n_slots), dim3(ds::kAssignThreads), 0,
+              static_cast<hipStream_t>(stream), args);
     return DS_OK;
 }
 
@@ -251,8 +251,7 @@ int ds_assign_solve_device(const int32_t *d_edge_row, const uint64_t *d_edge_key
 
     const int batch = static_cast<int>(ds::g_assign_rounds_per_sync.get());
     ds::DeviceBuffer<uint32_t> activity;
-    int status = activity.allocate(static_cast<size_t>(batch));
-    if (status != DS_OK) return status;
+    DS_TRY(activity.allocate(static_cast<size_t>(batch)));
     std::vector<uint32_t> seen(static_cast<size_t>(batch));
     const dim3 grid = ds::assign_grid(n_queries), block(ds::kAssignThreads);
     unsigned long long *held = reinterpret_cast<unsigned long long *>(d_held);
@@ -262,9 +261,8 @@ int ds_assign_solve_device(const int32_t *d_edge_row, const uint64_t *d_edge_key
     for (bool settled = false; !settled;) {
         DS_HIP(hipMemsetAsync(activity.ptr, 0, activity.bytes(), queue));
         for (int r = 0; r < batch; ++r) {
-            hipLaunchKernelGGL(ds::ds_assign_round_kernel, grid, block, 0, queue, d_edge_row, d_edge_key, n_queries, n, truth,
-                               held, d_next, r ? activity.ptr + r - 1 : nullptr, activity.ptr + r, counts + 4);
-            DS_HIP(hipGetLastError());
+            DS_LAUNCH(ds::ds_assign_round_kernel, grid, block, 0, queue, d_edge_row, d_edge_key, n_queries, n, truth,
+                      held, d_next, r ? activity.ptr + r - 1 : nullptr, activity.ptr + r, counts + 4);
         }
         DS_HIP(hipMemcpyAsync(seen.data(), activity.ptr, activity.bytes(), hipMemcpyDeviceToHost, queue));
         DS_HIP(hipStreamSynchronize(queue));
@@ -273,9 +271,8 @@ int ds_assign_solve_device(const int32_t *d_edge_row, const uint64_t *d_edge_key
             else ++rounds;
         }
     }
-    hipLaunchKernelGGL(ds::ds_assign_finish_kernel, grid, block, 0, queue, d_edge_row, d_edge_key, n_queries, n, truth, d_next,
-                       d_match_row, d_match_slot, d_first_row, counts, rounds);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_assign_finish_kernel, grid, block, 0, queue, d_edge_row, d_edge_key, n_queries, n, truth, d_next,
+              d_match_row, d_match_slot, d_first_row, counts, rounds);
     DS_HIP(hipStreamSynchronize(queue));
     return DS_OK;
 }

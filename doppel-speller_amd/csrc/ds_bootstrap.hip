@@ -19,6 +19,7 @@
 // kBootstrapChunk = 2^14, so no field carries into the next.  The partials are summed over the wave (ds_wave.h) and one
 // lane adds each non-zero counter to the int64 output: one integer atomic per counter and wave.  Replicate B of the grid
 // draws j = k: it is the baseline.  Integer sums throughout, so no bit depends on the grid, the chunking or the order.
+#include "ds_launch.h"
 #include "ds_bootstrap_draw.h"
 #include "ds_train.h"
 #include "ds_wave.h"
@@ -223,32 +224,32 @@ static dim3 bootstrap_row_grid(int64_t n)
 template <bool kUnits, bool kLds>
 static int bootstrap_launch(const BootstrapArgs &args, dim3 grid, size_t lds, hipStream_t stream)
 {
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_bootstrap_kernel<kUnits, kLds>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL((ds_bootstrap_kernel<kUnits, kLds>), grid, dim3(kBootstrapThreads), lds, stream, args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds_bootstrap_kernel<kUnits, kLds>, lds));
+    DS_LAUNCH((ds_bootstrap_kernel<kUnits, kLds>), grid, dim3(kBootstrapThreads), lds, stream, args);
     return DS_OK;
 }
 
-// The arguments have passed bootstrap_check_scalars, no pointer is null and n > 0.
-static int bootstrap_enqueue(const uint8_t *d_codes, int32_t n_sets, int64_t n, const int32_t *d_unit, int64_t n_units,
-                             int32_t n_boot, uint64_t seed, long long *d_counts, long long *d_baseline, hipStream_t stream)
+// The arguments have passed bootstrap_check_scalars and n > 0.  Each `_at` names a pointer into HBM that is read once
+// `scratch` is allocated here: the caller's own, or a piece it has declared in `scratch`; unit_at is null without units.
+static int bootstrap_enqueue(const char *what, Scratch &scratch, const uint8_t *const *codes_at, int32_t n_sets, int64_t n,
+                             const int32_t *const *unit_at, int64_t n_units, int32_t n_boot, uint64_t seed,
+                             long long *const *counts_at, long long *const *baseline_at, hipStream_t stream)
 {
-    const char *what = "ds_bootstrap_counts_device";
-    DeviceBuffer<unsigned long long> errors;
-    DeviceBuffer<uint32_t> table;
-    if (int status = errors.allocate(2); status != DS_OK) return status;
-    DS_HIP(hipMemsetAsync(errors.ptr, 0, errors.bytes(), stream));
-    if (d_unit != nullptr) {
-        if (int status = table.allocate(static_cast<size_t>(n_units) * n_sets * 4); status != DS_OK) return status;
-        DS_HIP(hipMemsetAsync(table.ptr, 0, table.bytes(), stream));
-    }
-    hipLaunchKernelGGL(ds_bootstrap_check_kernel, bootstrap_row_grid(n), dim3(kBootstrapCheckThreads), 0, stream, d_codes,
-                       d_unit, n, n_sets, n_units, table.ptr, errors.ptr);
-    DS_HIP(hipGetLastError());
+    unsigned long long *errors = nullptr;
+    uint32_t *table = nullptr;
+    const size_t table_words = unit_at ? static_cast<size_t>(n_units) * n_sets * 4 : 0;
+    scratch.add(&errors, 2);
+    scratch.add(&table, table_words);
+    DS_TRY(scratch.allocate(what));
+    const uint8_t *d_codes = *codes_at;
+    const int32_t *d_unit = unit_at ? *unit_at : nullptr;
+    long long *d_counts = *counts_at, *d_baseline = *baseline_at;
+    DS_HIP(hipMemsetAsync(errors, 0, sizeof(unsigned long long) * 2, stream));
+    if (table_words) DS_HIP(hipMemsetAsync(table, 0, sizeof(uint32_t) * table_words, stream));
+    DS_LAUNCH(ds_bootstrap_check_kernel, bootstrap_row_grid(n), dim3(kBootstrapCheckThreads), 0, stream, d_codes,
+              d_unit, n, n_sets, n_units, table, errors);
     unsigned long long found[2] = {0, 0};
-    DS_HIP(hipMemcpyAsync(found, errors.ptr, sizeof(found), hipMemcpyDeviceToHost, stream));
+    DS_HIP(hipMemcpyAsync(found, errors, sizeof(found), hipMemcpyDeviceToHost, stream));
     DS_HIP(hipStreamSynchronize(stream));
     DS_REQUIRE(found[0] == 0, "%s: %llu codes are above 3", what, found[0]);
     DS_REQUIRE(found[1] == 0, "%s: %llu units are outside [0, %lld)", what, found[1], (long long)n_units);
@@ -258,7 +259,7 @@ static int bootstrap_enqueue(const uint8_t *d_codes, int32_t n_sets, int64_t n, 
     DS_HIP(hipMemsetAsync(d_baseline, 0, sizeof(long long) * counters, stream));
     BootstrapArgs args;
     args.codes = d_codes;
-    args.table = reinterpret_cast<const uint4 *>(table.ptr);
+    args.table = reinterpret_cast<const uint4 *>(table);
     args.counts = reinterpret_cast<unsigned long long *>(d_counts);
     args.baseline = reinterpret_cast<unsigned long long *>(d_baseline);
     args.seed = seed;
@@ -284,14 +285,12 @@ static int bootstrap_enqueue(const uint8_t *d_codes, int32_t n_sets, int64_t n, 
     const int64_t bytes = units ? n_units * n_sets * static_cast<int64_t>(sizeof(uint4)) : n_units * args.padded_sets;
     const bool in_lds = g_bootstrap_table_in_lds.get() != 0 && bytes <= kBootstrapLdsBytes;
     const size_t lds = in_lds ? static_cast<size_t>((bytes + 15) / 16 * 16) : 0;
-    int status;
     if (units)
-        status = in_lds ? bootstrap_launch<true, true>(args, grid, lds, stream)
-                        : bootstrap_launch<true, false>(args, grid, 0, stream);
+        DS_TRY(in_lds ? bootstrap_launch<true, true>(args, grid, lds, stream)
+                      : bootstrap_launch<true, false>(args, grid, 0, stream));
     else
-        status = in_lds ? bootstrap_launch<false, true>(args, grid, lds, stream)
-                        : bootstrap_launch<false, false>(args, grid, 0, stream);
-    if (status != DS_OK) return status;
+        DS_TRY(in_lds ? bootstrap_launch<false, true>(args, grid, lds, stream)
+                      : bootstrap_launch<false, false>(args, grid, 0, stream));
     DS_HIP(hipStreamSynchronize(stream));   // the table is freed on return
     return DS_OK;
 }
@@ -309,8 +308,7 @@ int ds_bootstrap_counts_device(const uint8_t *d_codes, int32_t n_sets, int64_t n
                                int32_t n_boot, uint64_t seed, long long *d_counts, long long *d_baseline, void *stream)
 {
     const char *what = "ds_bootstrap_counts_device";
-    if (int status = ds::bootstrap_check_scalars(what, n_sets, n, d_unit != nullptr, n_units, n_boot); status != DS_OK)
-        return status;
+    DS_TRY(ds::bootstrap_check_scalars(what, n_sets, n, d_unit != nullptr, n_units, n_boot));
     DS_REQUIRE(d_counts != nullptr && d_baseline != nullptr && (n == 0 || d_codes != nullptr), "%s: null pointer", what);
     hipStream_t queue = static_cast<hipStream_t>(stream);
     if (n == 0) {
@@ -319,15 +317,16 @@ int ds_bootstrap_counts_device(const uint8_t *d_codes, int32_t n_sets, int64_t n
         DS_HIP(hipStreamSynchronize(queue));
         return DS_OK;
     }
-    return ds::bootstrap_enqueue(d_codes, n_sets, n, d_unit, n_units, n_boot, seed, d_counts, d_baseline, queue);
+    ds::Scratch scratch;
+    return ds::bootstrap_enqueue(what, scratch, &d_codes, n_sets, n, d_unit ? &d_unit : nullptr, n_units, n_boot, seed,
+                                 &d_counts, &d_baseline, queue);
 }
 
 int ds_bootstrap_counts(const uint8_t *codes, int32_t n_sets, int64_t n, const int32_t *unit, int64_t n_units,
                         int32_t n_boot, uint64_t seed, long long *counts, long long *baseline)
 {
     const char *what = "ds_bootstrap_counts";
-    if (int status = ds::bootstrap_check_scalars(what, n_sets, n, unit != nullptr, n_units, n_boot); status != DS_OK)
-        return status;
+    DS_TRY(ds::bootstrap_check_scalars(what, n_sets, n, unit != nullptr, n_units, n_boot));
     DS_REQUIRE(counts != nullptr && baseline != nullptr && (n == 0 || codes != nullptr), "%s: null pointer", what);
     const size_t counters = static_cast<size_t>(n_sets) * 4;
     for (int64_t e = 0; e < n * n_sets; ++e)
@@ -342,19 +341,18 @@ int ds_bootstrap_counts(const uint8_t *codes, int32_t n_sets, int64_t n, const i
         std::memset(baseline, 0, sizeof(long long) * counters);
         return DS_OK;
     }
-    ds::DeviceBuffer<uint8_t> d_codes;
-    ds::DeviceBuffer<int32_t> d_unit;
-    ds::DeviceBuffer<long long> d_counts, d_baseline;
-    int status = d_codes.upload(codes, static_cast<size_t>(n) * n_sets);
-    if (status == DS_OK && unit) status = d_unit.upload(unit, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_counts.allocate(counters * n_boot);
-    if (status == DS_OK) status = d_baseline.allocate(counters);
-    if (status != DS_OK) return status;
-    status = ds::bootstrap_enqueue(d_codes.ptr, n_sets, n, unit ? d_unit.ptr : nullptr, n_units, n_boot, seed, d_counts.ptr,
-                                   d_baseline.ptr, nullptr);
-    if (status != DS_OK) return status;
-    DS_HIP(hipMemcpy(counts, d_counts.ptr, d_counts.bytes(), hipMemcpyDeviceToHost));
-    DS_HIP(hipMemcpy(baseline, d_baseline.ptr, d_baseline.bytes(), hipMemcpyDeviceToHost));
+    ds::Scratch scratch;
+    const uint8_t *d_codes = nullptr;
+    const int32_t *d_unit = nullptr;
+    long long *d_counts = nullptr, *d_baseline = nullptr;
+    scratch.stage(&d_codes, codes, static_cast<size_t>(n) * n_sets);
+    if (unit) scratch.stage(&d_unit, unit, static_cast<size_t>(n));
+    scratch.add(&d_counts, counters * n_boot);
+    scratch.add(&d_baseline, counters);
+    DS_TRY(ds::bootstrap_enqueue(what, scratch, &d_codes, n_sets, n, unit ? &d_unit : nullptr, n_units, n_boot, seed,
+                                 &d_counts, &d_baseline, nullptr));
+    DS_HIP(hipMemcpy(counts, d_counts, sizeof(long long) * counters * n_boot, hipMemcpyDeviceToHost));
+    DS_HIP(hipMemcpy(baseline, d_baseline, sizeof(long long) * counters, hipMemcpyDeviceToHost));
     return DS_OK;
 }
 
@@ -366,9 +364,8 @@ int ds_outcome_codes_device(const float *d_margins, const float *d_target, int64
     DS_REQUIRE(threshold > 0.0 && threshold < 1.0, "%s: threshold = %g is not in (0, 1)", what, threshold);
     if (n == 0) return DS_OK;
     DS_REQUIRE(d_margins != nullptr && d_target != nullptr && d_codes != nullptr, "%s: null pointer", what);
-    hipLaunchKernelGGL(ds::ds_outcome_codes_kernel, ds::bootstrap_row_grid(n), dim3(ds::kBootstrapCheckThreads), 0,
-                       static_cast<hipStream_t>(stream), d_margins, d_target, n, threshold, d_codes);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_outcome_codes_kernel, ds::bootstrap_row_grid(n), dim3(ds::kBootstrapCheckThreads), 0,
+              static_cast<hipStream_t>(stream), d_margins, d_target, n, threshold, d_codes);
     return DS_OK;
 }
 

@@ -24,6 +24,7 @@
 // equal mean end in one level set whatever lies around them, so the result does not depend on the windows.
 #include <algorithm>
 
+#include "ds_launch.h"
 #include "ds_metrics.h"
 #include "ds_options.h"
 #include "ds_radix.h"
@@ -524,79 +525,79 @@ __global__ __launch_bounds__(kCalibrateThreads) void ds_reliability_kernel(const
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-static int64_t isotonic_scratch_bytes(int64_t n)
+// the scalar checks of both twins; clears `out`
+static int isotonic_check_scalars(const char *what, int64_t n, int64_t out[4])
 {
-    const int64_t head_tiles = (n + 1 + kCalibrateHeadTile - 1) / kCalibrateHeadTile;
-    // two sort buffers of 2 n keys, the sort's table, S, the points, the tiles' and the segments' counts, the state
-    return 16 * n + 2 * 1024 * radix_tiles(n) + 4 * (n + 1) + 12 * n + 4 * head_tiles + 4 * ((n + 1) / 2 + 1) + 64;
+    DS_REQUIRE(out != nullptr, "%s: null out", what);
+    DS_REQUIRE(n >= 0 && n < kCalibrateRowsMax, "%s: n = %lld outside [0, 2^31)", what, (long long)n);
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    return DS_OK;
 }
 
-static int isotonic_enqueue(const float *d_scores, const float *d_labels, int64_t n, float *d_lo, float *d_hi,
-                            long long *d_pos, long long *d_neg, int64_t out[4], hipStream_t stream)
+// What the body shares with its host-pointer twin: pointers to the caller's pointers into HBM, read once `scratch` is
+// allocated (they are the caller's own arrays, or pieces that it has declared in `scratch`).
+struct IsotonicArrays {
+    const float *const *scores, *const *labels;
+    float *const *lo, *const *hi;
+    long long *const *pos, *const *neg;
+};
+
+static int isotonic_enqueue(const char *what, Scratch &scratch, const IsotonicArrays &at, int64_t n, int64_t out[4],
+                            hipStream_t stream)
 {
-    const char *what = "ds_isotonic_fit_device";
-    if (int status = train_check_free(isotonic_scratch_bytes(n), what); status != DS_OK) return status;
     const int32_t W = static_cast<int32_t>(g_calibrate_segment_points.get());
     const int64_t head_tiles = (n + 1 + kCalibrateHeadTile - 1) / kCalibrateHeadTile;
     const int64_t max_segments = (n + W - 1) / W;
-    DeviceBuffer<uint32_t> keys_a, keys_b, table, state, S, totals, pt_key, pt_pos, pt_neg, seg_count;
-    int status = keys_a.allocate(static_cast<size_t>(2 * n));
-    if (status == DS_OK) status = keys_b.allocate(static_cast<size_t>(2 * n));
-    if (status == DS_OK) status = table.allocate(static_cast<size_t>(2 * 256 * radix_tiles(n)));
-    if (status == DS_OK) status = state.allocate(kStateWords);
-    if (status == DS_OK) status = S.allocate(static_cast<size_t>(n + 1));
-    if (status == DS_OK) status = totals.allocate(static_cast<size_t>(head_tiles));
-    if (status == DS_OK) status = pt_key.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = pt_pos.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = pt_neg.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = seg_count.allocate(static_cast<size_t>(max_segments));
-    if (status != DS_OK) return status;
+    uint32_t *keys_a = nullptr, *keys_b = nullptr, *table = nullptr, *state = nullptr, *S = nullptr, *totals = nullptr,
+             *pt_key = nullptr, *pt_pos = nullptr, *pt_neg = nullptr, *seg_count = nullptr;
+    scratch.add(&keys_a, static_cast<size_t>(2 * n));   // two sort buffers of 2 n keys
+    scratch.add(&keys_b, static_cast<size_t>(2 * n));
+    scratch.add(&table, static_cast<size_t>(2 * 256 * radix_tiles(n)));
+    scratch.add(&state, kStateWords);
+    scratch.add(&S, static_cast<size_t>(n + 1));
+    scratch.add(&totals, static_cast<size_t>(head_tiles));
+    scratch.add(&pt_key, static_cast<size_t>(n));
+    scratch.add(&pt_pos, static_cast<size_t>(n));
+    scratch.add(&pt_neg, static_cast<size_t>(n));
+    scratch.add(&seg_count, static_cast<size_t>(max_segments));
+    DS_TRY(scratch.allocate(what));
+    const float *d_scores = *at.scores, *d_labels = *at.labels;
+    float *d_lo = *at.lo, *d_hi = *at.hi;
+    long long *d_pos = *at.pos, *d_neg = *at.neg;
 
     uint32_t host_state[kStateWords] = {};
     auto enqueue = [&]() -> int {
-        hipLaunchKernelGGL(ds_isotonic_begin_kernel, dim3(1), dim3(64), 0, stream, state.ptr);
-        DS_HIP(hipGetLastError());
-        DS_HIP(hipMemsetAsync(keys_a.ptr, 0xff, keys_a.bytes(), stream));   // the padding key
+        DS_LAUNCH(ds_isotonic_begin_kernel, dim3(1), dim3(64), 0, stream, state);
+        DS_HIP(hipMemsetAsync(keys_a, 0xff, sizeof(uint32_t) * 2 * n, stream));   // the padding key
         const dim3 threads(kCalibrateThreads);
         const unsigned row_grid = calibrate_grid((n + kCalibrateThreads - 1) / kCalibrateThreads);
         const int64_t split_rows = static_cast<int64_t>(kCalibrateWaves) * kSplitWaveRows;
-        hipLaunchKernelGGL(ds_isotonic_split_kernel, dim3(calibrate_grid((n + split_rows - 1) / split_rows)), threads, 0, stream, d_scores, d_labels, n, keys_a.ptr,
-                           state.ptr);
-        DS_HIP(hipGetLastError());
-        if (int sorted = radix_sort_columns(stream, keys_a.ptr, keys_b.ptr, n, 2, state.ptr + kStateOr,
-                                            state.ptr + kStateAnd, table.ptr); sorted != DS_OK)
-            return sorted;
-        hipLaunchKernelGGL(ds_isotonic_heads_kernel, dim3(calibrate_grid(head_tiles)), threads, 0, stream, keys_a.ptr,
-                           keys_b.ptr, n, state.ptr, S.ptr, totals.ptr, head_tiles);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_isotonic_tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, totals.ptr, head_tiles,
-                           state.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_isotonic_scan_kernel, dim3(calibrate_grid(head_tiles)), threads, 0, stream, state.ptr, S.ptr,
-                           totals.ptr, head_tiles);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_isotonic_points_kernel, dim3(row_grid), threads, 0, stream, keys_a.ptr, keys_b.ptr, n,
-                           state.ptr, S.ptr, pt_key.ptr, pt_pos.ptr, pt_neg.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_isotonic_split_kernel, dim3(calibrate_grid((n + split_rows - 1) / split_rows)), threads, 0, stream, d_scores, d_labels, n, keys_a,
+                  state);
+        DS_TRY(radix_sort_columns(stream, keys_a, keys_b, n, 2, state + kStateOr,
+                                  state + kStateAnd, table));
+        DS_LAUNCH(ds_isotonic_heads_kernel, dim3(calibrate_grid(head_tiles)), threads, 0, stream, keys_a,
+                  keys_b, n, state, S, totals, head_tiles);
+        DS_LAUNCH(ds_isotonic_tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, totals, head_tiles,
+                  state);
+        DS_LAUNCH(ds_isotonic_scan_kernel, dim3(calibrate_grid(head_tiles)), threads, 0, stream, state, S,
+                  totals, head_tiles);
+        DS_LAUNCH(ds_isotonic_points_kernel, dim3(row_grid), threads, 0, stream, keys_a, keys_b, n,
+                  state, S, pt_key, pt_pos, pt_neg);
         // the sorted keys are spent: the sort buffers hold the survivors from here on
-        uint32_t *sv_start = keys_a.ptr, *sv_pos = keys_a.ptr + n, *sv_neg = keys_b.ptr;
+        uint32_t *sv_start = keys_a, *sv_pos = keys_a + n, *sv_neg = keys_b;
         const size_t lds = sizeof(uint32_t) * 6 * (static_cast<size_t>(W) + 128);
-        if (lds > 48 * 1024)
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_isotonic_pool_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        hipLaunchKernelGGL(ds_isotonic_pool_kernel, dim3(calibrate_grid(max_segments)), dim3(64), lds, stream, pt_pos.ptr,
-                           pt_neg.ptr, state.ptr, W, sv_start, sv_pos, sv_neg, seg_count.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_isotonic_finish_kernel, dim3(1), threads, 0, stream, state.ptr, W, sv_start, sv_pos, sv_neg,
-                           seg_count.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_isotonic_blocks_kernel, dim3(row_grid), threads, 0, stream, state.ptr, pt_key.ptr, sv_start,
-                           sv_pos, sv_neg, d_lo, d_hi, d_pos, d_neg);
-        DS_HIP(hipGetLastError());
-        DS_HIP(hipMemcpyAsync(host_state, state.ptr, sizeof(host_state), hipMemcpyDeviceToHost, stream));
+        DS_TRY(ds::allow_dynamic_lds(ds_isotonic_pool_kernel, lds));
+        DS_LAUNCH(ds_isotonic_pool_kernel, dim3(calibrate_grid(max_segments)), dim3(64), lds, stream, pt_pos,
+                  pt_neg, state, W, sv_start, sv_pos, sv_neg, seg_count);
+        DS_LAUNCH(ds_isotonic_finish_kernel, dim3(1), threads, 0, stream, state, W, sv_start, sv_pos, sv_neg,
+                  seg_count);
+        DS_LAUNCH(ds_isotonic_blocks_kernel, dim3(row_grid), threads, 0, stream, state, pt_key, sv_start,
+                  sv_pos, sv_neg, d_lo, d_hi, d_pos, d_neg);
+        DS_HIP(hipMemcpyAsync(host_state, state, sizeof(host_state), hipMemcpyDeviceToHost, stream));
         return DS_OK;
     };
-    status = enqueue();
+    const int status = enqueue();
     const hipError_t synced = hipStreamSynchronize(stream);   // the scratch is freed on return
     if (status != DS_OK) return status;
     DS_HIP(synced);
@@ -620,45 +621,42 @@ int ds_isotonic_fit_device(const float *d_scores, const float *d_labels, int64_t
                            long long *d_pos, long long *d_neg, int64_t out[4], void *stream)
 {
     const char *what = "ds_isotonic_fit_device";
-    DS_REQUIRE(out != nullptr, "%s: null out", what);
-    DS_REQUIRE(n >= 0 && n < ds::kCalibrateRowsMax, "%s: n = %lld outside [0, 2^31)", what, (long long)n);
-    for (int i = 0; i < 4; ++i) out[i] = 0;
+    DS_TRY(ds::isotonic_check_scalars(what, n, out));
     if (n == 0) {
         DS_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
         return DS_OK;
     }
     DS_REQUIRE(d_scores && d_labels && d_lo && d_hi && d_pos && d_neg, "%s: null pointer", what);
-    return ds::isotonic_enqueue(d_scores, d_labels, n, d_lo, d_hi, d_pos, d_neg, out, static_cast<hipStream_t>(stream));
+    ds::Scratch scratch;
+    return ds::isotonic_enqueue(what, scratch, {&d_scores, &d_labels, &d_lo, &d_hi, &d_pos, &d_neg}, n, out,
+                                static_cast<hipStream_t>(stream));
 }
 
 int ds_isotonic_fit(const float *scores, const float *labels, int64_t n, float *lo, float *hi, long long *pos,
                     long long *neg, int64_t out[4], int device)
 {
     const char *what = "ds_isotonic_fit";
-    DS_REQUIRE(out != nullptr, "%s: null out", what);
-    DS_REQUIRE(n >= 0 && n < ds::kCalibrateRowsMax, "%s: n = %lld outside [0, 2^31)", what, (long long)n);
-    for (int i = 0; i < 4; ++i) out[i] = 0;
+    DS_TRY(ds::isotonic_check_scalars(what, n, out));
     if (n == 0) return DS_OK;
     DS_REQUIRE(scores && labels && lo && hi && pos && neg, "%s: null pointer", what);
     DS_HIP(hipSetDevice(device));
-    if (int status = ds::train_check_free(32 * n + ds::isotonic_scratch_bytes(n), what); status != DS_OK) return status;
-    ds::DeviceBuffer<float> d_scores, d_labels, d_lo, d_hi;
-    ds::DeviceBuffer<long long> d_pos, d_neg;
-    int status = d_scores.upload(scores, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_labels.upload(labels, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_lo.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = d_hi.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = d_pos.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = d_neg.allocate(static_cast<size_t>(n));
-    if (status != DS_OK) return status;
-    status = ds::isotonic_enqueue(d_scores.ptr, d_labels.ptr, n, d_lo.ptr, d_hi.ptr, d_pos.ptr, d_neg.ptr, out, nullptr);
-    if (status != DS_OK) return status;
+    ds::Scratch scratch;
+    const float *d_scores = nullptr, *d_labels = nullptr;
+    float *d_lo = nullptr, *d_hi = nullptr;
+    long long *d_pos = nullptr, *d_neg = nullptr;
+    scratch.stage(&d_scores, scores, static_cast<size_t>(n));
+    scratch.stage(&d_labels, labels, static_cast<size_t>(n));
+    scratch.add(&d_lo, static_cast<size_t>(n));
+    scratch.add(&d_hi, static_cast<size_t>(n));
+    scratch.add(&d_pos, static_cast<size_t>(n));
+    scratch.add(&d_neg, static_cast<size_t>(n));
+    DS_TRY(ds::isotonic_enqueue(what, scratch, {&d_scores, &d_labels, &d_lo, &d_hi, &d_pos, &d_neg}, n, out, nullptr));
     const size_t K = static_cast<size_t>(out[0]);
     if (K) {
-        DS_HIP(hipMemcpy(lo, d_lo.ptr, K * sizeof(float), hipMemcpyDeviceToHost));
-        DS_HIP(hipMemcpy(hi, d_hi.ptr, K * sizeof(float), hipMemcpyDeviceToHost));
-        DS_HIP(hipMemcpy(pos, d_pos.ptr, K * sizeof(long long), hipMemcpyDeviceToHost));
-        DS_HIP(hipMemcpy(neg, d_neg.ptr, K * sizeof(long long), hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(lo, d_lo, K * sizeof(float), hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(hi, d_hi, K * sizeof(float), hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(pos, d_pos, K * sizeof(long long), hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(neg, d_neg, K * sizeof(long long), hipMemcpyDeviceToHost));
     }
     return DS_OK;
 }
@@ -675,16 +673,13 @@ int ds_calibration_apply_device(const float *d_lo, const float *d_value, int32_t
     hipStream_t queue = static_cast<hipStream_t>(stream);
     if (K <= ds::kCalibrateEdgesInLds) {
         const size_t lds = sizeof(uint32_t) * static_cast<size_t>(K);
-        if (lds > 48 * 1024)
-            DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds::ds_calibration_apply_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        hipLaunchKernelGGL(ds::ds_calibration_apply_kernel<true>, grid, dim3(ds::kCalibrateThreads), lds, queue, d_lo,
-                           d_value, K, d_scores, n, d_out);
+        DS_TRY(ds::allow_dynamic_lds(ds::ds_calibration_apply_kernel<true>, lds));
+        DS_LAUNCH(ds::ds_calibration_apply_kernel<true>, grid, dim3(ds::kCalibrateThreads), lds, queue, d_lo,
+                  d_value, K, d_scores, n, d_out);
     } else {
-        hipLaunchKernelGGL(ds::ds_calibration_apply_kernel<false>, grid, dim3(ds::kCalibrateThreads), 0, queue, d_lo,
-                           d_value, K, d_scores, n, d_out);
+        DS_LAUNCH(ds::ds_calibration_apply_kernel<false>, grid, dim3(ds::kCalibrateThreads), 0, queue, d_lo,
+                  d_value, K, d_scores, n, d_out);
     }
-    DS_HIP(hipGetLastError());
     return DS_OK;
 }
 
@@ -699,10 +694,9 @@ int ds_reliability_device(const float *d_probabilities, const float *d_labels, i
     hipStream_t queue = static_cast<hipStream_t>(stream);
     DS_HIP(hipMemsetAsync(d_out, 0, sizeof(long long) * 4 * (static_cast<size_t>(n_bins) + 1), queue));
     if (n == 0) return DS_OK;
-    hipLaunchKernelGGL(ds::ds_reliability_kernel, dim3(ds::calibrate_grid((n + ds::kCalibrateThreads - 1) / ds::kCalibrateThreads)),
-                       dim3(ds::kCalibrateThreads), 0, queue, d_probabilities, d_labels, n, n_bins,
-                       reinterpret_cast<unsigned long long *>(d_out));
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_reliability_kernel, dim3(ds::calibrate_grid((n + ds::kCalibrateThreads - 1) / ds::kCalibrateThreads)),
+              dim3(ds::kCalibrateThreads), 0, queue, d_probabilities, d_labels, n, n_bins,
+              reinterpret_cast<unsigned long long *>(d_out));
     return DS_OK;
 }
 

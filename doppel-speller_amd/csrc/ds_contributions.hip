@@ -15,6 +15,7 @@
 // The row's sums live in LDS as float64 [feature][lane] next to the staged rows [feature][lane].  Paths are visited in
 // tree order, leaves in node order, elements in path order, and every sum is a plain sequential float64 addition: the
 // same bits whatever the grid.  approximate = 1 (Saabas) walks the row's own path and adds the change of the subtree mean.
+#include "ds_launch.h"
 #include "ds_forest.h"
 
 #include <cmath>
@@ -255,8 +256,7 @@ static int check_shape(ds_forest *forest, const char *what)
 {
     if (forest->shape_checked) return DS_OK;
     std::vector<int32_t> parent;
-    const int status = forest_parents(forest, what, parent);
-    if (status != DS_OK) return status;
+    DS_TRY(forest_parents(forest, what, parent));
     forest->parent = std::move(parent);
     forest->shape_checked = 1;
     return DS_OK;
@@ -388,11 +388,8 @@ static int prepare(ds_forest *forest, const char *what)
 template <int M>
 static int launch_contributions(const ContributionsArgs &args, int grid, size_t lds, hipStream_t stream)
 {
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_contributions_kernel<M>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL(ds_contributions_kernel<M>, dim3(grid), dim3(kContributionsThreads), lds, stream, args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds_contributions_kernel<M>, lds));
+    DS_LAUNCH(ds_contributions_kernel<M>, dim3(grid), dim3(kContributionsThreads), lds, stream, args);
     return DS_OK;
 }
 
@@ -411,13 +408,11 @@ int ds_forest_cover_device(ds_forest *forest, const float *d_rows, int64_t n, vo
 {
     DS_REQUIRE(forest != nullptr && n >= 0, "ds_forest_cover_device: bad arguments");
     DS_REQUIRE(n == 0 || d_rows != nullptr, "ds_forest_cover_device: null rows");
-    int status = ds::check_shape(forest, "ds_forest_cover_device");
-    if (status != DS_OK) return status;
+    DS_TRY(ds::check_shape(forest, "ds_forest_cover_device"));
     DS_HIP(hipSetDevice(forest->device));
     hipStream_t queue = static_cast<hipStream_t>(stream);
     if (forest->cover_state != ds_forest::kCoverCounted) {  // a fresh count replaces whatever was installed
-        status = forest->counts.allocate(static_cast<size_t>(std::max<int64_t>(forest->n_nodes, 1)));
-        if (status != DS_OK) return status;
+        DS_TRY(forest->counts.allocate(static_cast<size_t>(std::max<int64_t>(forest->n_nodes, 1))));
         DS_HIP(hipMemsetAsync(forest->counts.ptr, 0, forest->counts.bytes(), queue));
         forest->cover.clear();
         forest->cover_state = ds_forest::kCoverCounted;
@@ -429,15 +424,11 @@ int ds_forest_cover_device(ds_forest *forest, const float *d_rows, int64_t n, vo
     const int64_t cap = forest->max_blocks.value_or(ds::kCoverMaxBlocks);
     const unsigned grid = ds::grid_cap(blocks, cap);
     const size_t lds = static_cast<size_t>(ds::kForestThreads) * (forest->n_features + 1) * sizeof(float);
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds::ds_forest_cover_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL(ds::ds_forest_cover_kernel, dim3(grid), dim3(ds::kForestThreads), lds, queue, args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds::ds_forest_cover_kernel, lds));
+    DS_LAUNCH(ds::ds_forest_cover_kernel, dim3(grid), dim3(ds::kForestThreads), lds, queue, args);
     const unsigned sum_grid = ds::grid_cap((forest->n_trees + 63) / 64, cap);
-    hipLaunchKernelGGL(ds::ds_forest_cover_sum_kernel, dim3(sum_grid), dim3(64), 0, queue, forest->nodes.ptr,
-                       forest->tree_offsets.ptr, forest->n_trees, forest->counts.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_forest_cover_sum_kernel, dim3(sum_grid), dim3(64), 0, queue, forest->nodes.ptr,
+              forest->tree_offsets.ptr, forest->n_trees, forest->counts.ptr);
     return DS_OK;
 }
 
@@ -459,8 +450,7 @@ int ds_forest_cover_read(ds_forest *forest, double *cover)
 {
     DS_REQUIRE(forest != nullptr && (cover != nullptr || forest->n_nodes == 0), "ds_forest_cover_read: null pointer");
     std::vector<double> values;
-    const int status = ds::read_cover(forest, values, "ds_forest_cover_read");
-    if (status != DS_OK) return status;
+    DS_TRY(ds::read_cover(forest, values, "ds_forest_cover_read"));
     if (!values.empty()) std::memcpy(cover, values.data(), values.size() * sizeof(double));
     return DS_OK;
 }
@@ -484,8 +474,7 @@ int ds_forest_contributions_device(ds_forest *forest, const float *d_rows, int64
     DS_REQUIRE(approximate == 0 || approximate == 1, "ds_forest_contributions: approximate = %d is neither 0 nor 1",
                approximate);
     DS_REQUIRE(forest->cover_state != ds_forest::kCoverNone, "ds_forest_contributions: the forest has no cover");
-    const int status = ds::prepare(forest, "ds_forest_contributions");
-    if (status != DS_OK) return status;
+    DS_TRY(ds::prepare(forest, "ds_forest_contributions"));
     if (n == 0) return DS_OK;
     DS_REQUIRE(d_rows && d_out, "ds_forest_contributions: null pointer");
     DS_HIP(hipSetDevice(forest->device));
@@ -515,16 +504,16 @@ int ds_forest_contributions(ds_forest *forest, const float *rows, int64_t n, dou
     DS_REQUIRE(forest != nullptr && n >= 0, "ds_forest_contributions: bad arguments");
     DS_REQUIRE(n == 0 || (rows && out), "ds_forest_contributions: null pointer");
     DS_HIP(hipSetDevice(forest->device));
-    ds::DeviceBuffer<float> d_rows;
-    ds::DeviceBuffer<double> d_out;
+    ds::Scratch scratch;
+    const float *d_rows = nullptr;
+    double *d_out = nullptr;
     const size_t width = static_cast<size_t>(forest->n_features) + 1;
-    int status = d_rows.upload(rows, static_cast<size_t>(n) * forest->n_features);
-    if (status == DS_OK) status = d_out.allocate(static_cast<size_t>(n) * width);
-    if (status != DS_OK) return status;
-    status = ds_forest_contributions_device(forest, d_rows.ptr, n, d_out.ptr, approximate, nullptr);
-    if (status != DS_OK) return status;
+    scratch.stage(&d_rows, rows, static_cast<size_t>(n) * forest->n_features);
+    scratch.add(&d_out, static_cast<size_t>(n) * width);
+    DS_TRY(scratch.allocate("ds_forest_contributions"));
+    DS_TRY(ds_forest_contributions_device(forest, d_rows, n, d_out, approximate, nullptr));
     DS_HIP(hipDeviceSynchronize());
-    if (n) DS_HIP(hipMemcpy(out, d_out.ptr, sizeof(double) * static_cast<size_t>(n) * width, hipMemcpyDeviceToHost));
+    if (n) DS_HIP(hipMemcpy(out, d_out, sizeof(double) * static_cast<size_t>(n) * width, hipMemcpyDeviceToHost));
     return DS_OK;
 }
 
@@ -537,10 +526,9 @@ int ds_best_pairs_device(const int32_t *d_rows, const float *d_probabilities, in
     DS_REQUIRE(d_rows && d_probabilities && d_best_pair && d_best_row && d_best_probability && d_best_count,
                "ds_best_pairs_device: null pointer");
     const int64_t blocks = std::min<int64_t>((n_queries + 255) / 256, 4096);
-    hipLaunchKernelGGL(ds::ds_best_pairs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_rows, d_probabilities, n_queries, k, d_best_pair, d_best_row,
-                       d_best_probability, d_best_count);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_best_pairs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+              static_cast<hipStream_t>(stream), d_rows, d_probabilities, n_queries, k, d_best_pair, d_best_row,
+              d_best_probability, d_best_count);
     return DS_OK;
 }
 

@@ -28,6 +28,7 @@
 // (at least one column); ds_cuts_option("column_group", g) forces g columns per group for tests.
 #include <algorithm>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_radix.h"
 
@@ -161,26 +162,20 @@ int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_feature
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t tiles = (n + ds::kSortTile - 1) / ds::kSortTile;
     const int64_t column_bytes = 8 * n + 1024 * tiles;
-    size_t free_bytes = 0, total_bytes = 0;
-    DS_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
-    if (static_cast<size_t>(column_bytes) + (size_t(64) << 20) > free_bytes) {
-        ds::set_error("ds_feature_cuts_device: one column needs %lld bytes of HBM, %zu are free", (long long)column_bytes,
-                      free_bytes);
-        return DS_E_HIP;
-    }
+    size_t free_bytes = 0;
+    DS_TRY(ds::check_free(column_bytes, "ds_feature_cuts_device: one column", &free_bytes));
     int64_t group = g_column_group.get();
     if (group == 0) group = static_cast<int64_t>(free_bytes / 4) / column_bytes;
     group = std::max<int64_t>(1, std::min<int64_t>(group, n_features));
 
     ds::DeviceBuffer<uint32_t> keys_a, keys_b, table, column_state, cut_table;
     ds::DeviceBuffer<int32_t> cut_counts;
-    int status = keys_a.allocate(static_cast<size_t>(group * n));
-    if (status == DS_OK) status = keys_b.allocate(static_cast<size_t>(group * n));
-    if (status == DS_OK) status = table.allocate(static_cast<size_t>(group * 256 * tiles));
-    if (status == DS_OK) status = column_state.allocate(3 * ds::kCutsFeaturesMax);   // m, OR, AND of the group's columns
-    if (status == DS_OK) status = cut_table.allocate(static_cast<size_t>(n_features) * ds::kCutsMax);
-    if (status == DS_OK) status = cut_counts.allocate(n_features);
-    if (status != DS_OK) return status;
+    DS_TRY(keys_a.allocate(static_cast<size_t>(group * n)));
+    DS_TRY(keys_b.allocate(static_cast<size_t>(group * n)));
+    DS_TRY(table.allocate(static_cast<size_t>(group * 256 * tiles)));
+    DS_TRY(column_state.allocate(3 * ds::kCutsFeaturesMax)); // m, OR, AND of the group's columns
+    DS_TRY(cut_table.allocate(static_cast<size_t>(n_features) * ds::kCutsMax));
+    DS_TRY(cut_counts.allocate(n_features));
     uint32_t *col_m = column_state.ptr, *col_or = col_m + ds::kCutsFeaturesMax, *col_and = col_or + ds::kCutsFeaturesMax;
     const int64_t row_tiles = (n + ds::kKeyTileRows - 1) / ds::kKeyTileRows;
     const unsigned key_grid = ds::grid_cap(row_tiles, int64_t(ds::compute_units(device)) * 8);
@@ -188,16 +183,13 @@ int ds_feature_cuts_device(const float *d_features, int64_t n, int32_t n_feature
         const int32_t g = static_cast<int32_t>(std::min<int64_t>(group, n_features - c0));
         DS_HIP(hipMemsetAsync(col_m, 0, sizeof(uint32_t) * 2 * ds::kCutsFeaturesMax, s));
         DS_HIP(hipMemsetAsync(col_and, 0xff, sizeof(uint32_t) * ds::kCutsFeaturesMax, s));
-        hipLaunchKernelGGL(ds::ds_cuts_key_kernel, dim3(key_grid), dim3(ds::kKeyThreads), 0, s,
-                           reinterpret_cast<const uint32_t *>(d_features), n, n_features, c0, g, keys_a.ptr, col_m, col_or,
-                           col_and);
-        DS_HIP(hipGetLastError());
-        if (int sorted = ds::radix_sort_columns(s, keys_a.ptr, keys_b.ptr, n, g, col_or, col_and, table.ptr); sorted != DS_OK)
-            return sorted;
-        hipLaunchKernelGGL(ds::ds_cuts_pick_kernel, dim3(g), dim3(ds::kScanThreads), 0, s, keys_a.ptr, keys_b.ptr, n,
-                           col_or, col_and, col_m, max_bin, cut_table.ptr + static_cast<size_t>(c0) * ds::kCutsMax,
-                           cut_counts.ptr + c0);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_cuts_key_kernel, dim3(key_grid), dim3(ds::kKeyThreads), 0, s,
+                  reinterpret_cast<const uint32_t *>(d_features), n, n_features, c0, g, keys_a.ptr, col_m, col_or,
+                  col_and);
+        DS_TRY(ds::radix_sort_columns(s, keys_a.ptr, keys_b.ptr, n, g, col_or, col_and, table.ptr));
+        DS_LAUNCH(ds::ds_cuts_pick_kernel, dim3(g), dim3(ds::kScanThreads), 0, s, keys_a.ptr, keys_b.ptr, n,
+                  col_or, col_and, col_m, max_bin, cut_table.ptr + static_cast<size_t>(c0) * ds::kCutsMax,
+                  cut_counts.ptr + c0);
     }
     std::vector<uint32_t> host_table(static_cast<size_t>(n_features) * ds::kCutsMax);
     std::vector<int32_t> host_counts(n_features);

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_wave.h"
 
@@ -196,9 +197,8 @@ int ds_duplicate_begin_device(int32_t *d_parent, int64_t n_truth, int64_t *d_cou
     hipStream_t queue = static_cast<hipStream_t>(stream);
     DS_HIP(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), queue));
     if (n_truth == 0) return DS_OK;
-    hipLaunchKernelGGL(ds::ds_duplicate_begin_kernel, ds::duplicate_grid(n_truth), dim3(ds::kDuplicateThreads), 0, queue,
-                       d_parent, static_cast<int32_t>(n_truth));
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_duplicate_begin_kernel, ds::duplicate_grid(n_truth), dim3(ds::kDuplicateThreads), 0, queue,
+              d_parent, static_cast<int32_t>(n_truth));
     return DS_OK;
 }
 
@@ -226,9 +226,8 @@ int ds_duplicate_links_device(const int32_t *d_rows, const uint8_t *d_ratios, co
     args.parent = d_parent; args.reason = d_reason; args.counts = reinterpret_cast<unsigned long long *>(d_counts);
     args.q_first = q_first; args.n_slots = n_queries * k; args.k = k; args.n_truth = static_cast<int32_t>(n_truth);
     args.levenshtein_threshold = levenshtein_threshold; args.probability_threshold = probability_threshold;
-    hipLaunchKernelGGL(ds::ds_duplicate_links_kernel, ds::duplicate_grid(args.n_slots), dim3(ds::kDuplicateThreads), 0,
-                       static_cast<hipStream_t>(stream), args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_duplicate_links_kernel, ds::duplicate_grid(args.n_slots), dim3(ds::kDuplicateThreads), 0,
+              static_cast<hipStream_t>(stream), args);
     return DS_OK;
 }
 
@@ -241,12 +240,9 @@ int ds_duplicate_finish_device(int32_t *d_parent, int64_t n_truth, int32_t *d_la
     hipStream_t queue = static_cast<hipStream_t>(stream);
     const dim3 grid = ds::duplicate_grid(n_truth), block(ds::kDuplicateThreads);
     const int32_t n = static_cast<int32_t>(n_truth);
-    hipLaunchKernelGGL(ds::ds_duplicate_label_kernel, grid, block, 0, queue, d_parent, n, d_label, d_size);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_duplicate_count_kernel, grid, block, 0, queue, d_label, n, d_parent, d_size);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_duplicate_size_kernel, grid, block, 0, queue, d_label, n, d_size);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_duplicate_label_kernel, grid, block, 0, queue, d_parent, n, d_label, d_size);
+    DS_LAUNCH(ds::ds_duplicate_count_kernel, grid, block, 0, queue, d_label, n, d_parent, d_size);
+    DS_LAUNCH(ds::ds_duplicate_size_kernel, grid, block, 0, queue, d_label, n, d_size);
     return DS_OK;
 }
 

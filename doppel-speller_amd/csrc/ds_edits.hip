@@ -23,6 +23,7 @@
 // edit histogram and the substitute / insert tables (24 KiB) sit in LDS next to the lanes' working titles.
 #include <algorithm>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_title_ops.h"
 #include "ds_wave.h"
@@ -459,13 +460,11 @@ int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_
 
     // every pair is checked before anything is written; the same pass finds the longest truth title
     ds::DeviceBuffer<int32_t> report;
-    int status = report.allocate(2);
-    if (status != DS_OK) return status;
+    DS_TRY(report.allocate(2));
     int32_t found[2] = {0, 0};
     DS_HIP(hipMemsetAsync(report.ptr, 0, 2 * sizeof(int32_t), nullptr));
-    hipLaunchKernelGGL(ds::ds_edit_check_kernel, dim3(ds::grid_cap((n + 3) / 4, max_blocks)),
-                       dim3(256), 0, nullptr, args, report.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_edit_check_kernel, dim3(ds::grid_cap((n + 3) / 4, max_blocks)),
+              dim3(256), 0, nullptr, args, report.ptr);
     DS_HIP(hipMemcpy(found, report.ptr, sizeof(found), hipMemcpyDeviceToHost));
     DS_REQUIRE(found[0] == 0, "ds_edit_align: %d pairs have a row out of range or a title that is not a transformed "
                "title (3..255 codes 1..37)", found[0]);
@@ -475,12 +474,9 @@ int ds_edit_align(const ds_titles *truth, const int32_t *d_truth_rows, const ds_
     int64_t pairs = ds::g_edit_pairs_per_group.get();
     pairs = std::max<int64_t>(1, std::min(pairs, (ds::kEditLdsLimit - ds::kEditCounterBytes) / pair_bytes));
     const size_t lds = static_cast<size_t>(ds::kEditCounterBytes + pairs * pair_bytes);
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds::ds_edit_align_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL(ds::ds_edit_align_kernel, dim3(ds::grid_cap((n + pairs - 1) / pairs, max_blocks)),
-                       dim3(static_cast<unsigned>(64 * pairs)), lds, nullptr, args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds::ds_edit_align_kernel, lds));
+    DS_LAUNCH(ds::ds_edit_align_kernel, dim3(ds::grid_cap((n + pairs - 1) / pairs, max_blocks)),
+              dim3(static_cast<unsigned>(64 * pairs)), lds, nullptr, args);
     DS_HIP(hipStreamSynchronize(nullptr));
     return DS_OK;
 }
@@ -500,41 +496,25 @@ int ds_misspell_titles_profile(ds_titles *source, const int32_t *d_rows, int64_t
     const char *wrong = ds::profile_tables_build(counts.data(), tables[0]);
     DS_REQUIRE(wrong == nullptr, "ds_misspell_titles_profile: %s", wrong);
     ds::DeviceBuffer<ds::ProfileTables> d_tables;
-    int status = d_tables.upload(tables.data(), 1);
-    if (status != DS_OK) return status;
+    DS_TRY(d_tables.upload(tables.data(), 1));
 
-    ds_titles *titles = new ds_titles();
+    std::unique_ptr<ds_titles> titles(new ds_titles());
     titles->device = source->device;
     titles->n = n;
     titles->stride = DS_MAX_CHARS;
     ds::DeviceBuffer<int32_t> error;
-    status = titles->enc.allocate(static_cast<size_t>(n) * DS_MAX_CHARS);
-    if (status == DS_OK) status = titles->len.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = error.allocate(1);
-    if (status != DS_OK) {
-        delete titles;
-        return status;
-    }
+    DS_TRY(titles->enc.allocate(static_cast<size_t>(n) * DS_MAX_CHARS));
+    DS_TRY(titles->len.allocate(static_cast<size_t>(n)));
+    DS_TRY(error.allocate(1));
     int32_t errors = 0;
-    hipError_t hip = hipMemsetAsync(error.ptr, 0, sizeof(int32_t), nullptr);
-    if (hip == hipSuccess) {
-        hipLaunchKernelGGL(ds::ds_misspell_profile_kernel, dim3(static_cast<unsigned>((n + ds::kMisspellBlock - 1) / ds::kMisspellBlock)),
-                           dim3(ds::kMisspellBlock), 0, nullptr, source->enc.ptr, source->len.ptr, source->stride, source->n,
-                           d_rows, n, seed, d_tables.ptr, titles->enc.ptr, titles->len.ptr, error.ptr);
-        hip = hipGetLastError();
-    }
-    if (hip == hipSuccess) hip = hipMemcpy(&errors, error.ptr, sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (hip != hipSuccess) {
-        delete titles;
-        return ds::hip_failed(hip, "ds_misspell_profile_kernel", __FILE__, __LINE__);
-    }
-    if (errors != 0) {
-        delete titles;
-        ds::set_error("ds_misspell_titles_profile: %d rows are out of range or not transformed titles (3..255 codes 1..37, "
-                      "one letter or digit at least)", errors);
-        return DS_E_ARG;
-    }
-    *out = titles;
+    DS_HIP(hipMemsetAsync(error.ptr, 0, sizeof(int32_t), nullptr));
+    DS_LAUNCH(ds::ds_misspell_profile_kernel, dim3(static_cast<unsigned>((n + ds::kMisspellBlock - 1) / ds::kMisspellBlock)),
+              dim3(ds::kMisspellBlock), 0, nullptr, source->enc.ptr, source->len.ptr, source->stride, source->n,
+              d_rows, n, seed, d_tables.ptr, titles->enc.ptr, titles->len.ptr, error.ptr);
+    DS_HIP(hipMemcpy(&errors, error.ptr, sizeof(int32_t), hipMemcpyDeviceToHost));
+    DS_REQUIRE(errors == 0, "ds_misspell_titles_profile: %d rows are out of range or not transformed titles (3..255 codes 1..37, "
+               "one letter or digit at least)", errors);
+    *out = titles.release();
     return DS_OK;
 }
 

@@ -13,7 +13,7 @@
 //           up holding the largest row of that title whatever the order in which the lanes ran.
 //   probe   one lane per query: walk the probe sequence until an empty slot (absent) or a slot of the same title.
 // "exact_hash_bits" (ds_titles_option) keeps only the low bits of the 64-bit title hash: tests force collisions with it.
-#include "ds_common.h"
+#include "ds_launch.h"
 
 namespace ds {
 
@@ -92,16 +92,10 @@ static int ensure_exact_table(ds_titles *truth, hipStream_t stream)
     uint64_t capacity = 16;
     while (capacity < 2 * static_cast<uint64_t>(truth->n)) capacity <<= 1;
     const size_t bytes = capacity * sizeof(int32_t);
-    size_t free_bytes = 0, total_bytes = 0;
-    DS_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
-    if (bytes + (size_t(64) << 20) > free_bytes) {   // keep 64 MiB of head room for the kernels that follow
-        ds::set_error("ds_exact_matches: the exact-match table of %lld truth rows needs %zu bytes of HBM, %zu are free",
-                      (long long)truth->n, bytes, free_bytes);
-        return DS_E_HIP;
-    }
-    const int allocated = truth->exact_slots.allocate(static_cast<size_t>(capacity));
-    if (allocated != DS_OK) return allocated;
+    DS_TRY(ds::check_free(static_cast<int64_t>(bytes), "ds_exact_matches: the exact-match table"));
+    DS_TRY(truth->exact_slots.allocate(static_cast<size_t>(capacity)));
     DS_HIP(hipMemsetAsync(truth->exact_slots.ptr, 0xff, bytes, stream));   // -1 = empty
+    // spelled out: a failed launch releases the table, so that the next call builds it again
     hipLaunchKernelGGL(ds_exact_insert_kernel, dim3(static_cast<unsigned>((truth->n + 255) / 256)), dim3(256), 0, stream,
                        truth->enc.ptr, truth->stride, truth->len.ptr, truth->n, hash_mask_of(truth->exact_hash_bits),
                        truth->exact_slots.ptr, capacity - 1);
@@ -129,13 +123,11 @@ int ds_exact_matches_device(ds_titles *truth, ds_titles *queries, int64_t q_firs
     DS_REQUIRE(d_exact_row != nullptr, "ds_exact_matches: null output");
     DS_HIP(hipSetDevice(truth->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ensured = ds::ensure_exact_table(truth, s);
-    if (ensured != DS_OK) return ensured;
-    hipLaunchKernelGGL(ds::ds_exact_probe_kernel, dim3(static_cast<unsigned>((n_queries + 255) / 256)), dim3(256), 0, s,
-                       truth->enc.ptr, truth->stride, truth->len.ptr, queries->enc.ptr, queries->stride, queries->len.ptr,
-                       q_first, n_queries, ds::hash_mask_of(truth->exact_hash_bits), truth->exact_slots.ptr,
-                       static_cast<uint64_t>(truth->exact_slots.count) - 1, d_exact_row, d_best_row);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::ensure_exact_table(truth, s));
+    DS_LAUNCH(ds::ds_exact_probe_kernel, dim3(static_cast<unsigned>((n_queries + 255) / 256)), dim3(256), 0, s,
+              truth->enc.ptr, truth->stride, truth->len.ptr, queries->enc.ptr, queries->stride, queries->len.ptr,
+              q_first, n_queries, ds::hash_mask_of(truth->exact_hash_bits), truth->exact_slots.ptr,
+              static_cast<uint64_t>(truth->exact_slots.count) - 1, d_exact_row, d_best_row);
     return DS_OK;
 }
 
@@ -147,10 +139,8 @@ int ds_exact_matches(ds_titles *truth, ds_titles *queries, int64_t n_queries, in
     DS_REQUIRE(exact_row != nullptr, "ds_exact_matches: null output");
     DS_HIP(hipSetDevice(truth->device));
     ds::DeviceBuffer<int32_t> d_exact;
-    const int allocated = d_exact.allocate(static_cast<size_t>(n_queries));
-    if (allocated != DS_OK) return allocated;
-    const int status = ds_exact_matches_device(truth, queries, 0, n_queries, d_exact.ptr, nullptr, nullptr);
-    if (status != DS_OK) return status;
+    DS_TRY(d_exact.allocate(static_cast<size_t>(n_queries)));
+    DS_TRY(ds_exact_matches_device(truth, queries, 0, n_queries, d_exact.ptr, nullptr, nullptr));
     DS_HIP(hipStreamSynchronize(nullptr));
     DS_HIP(hipMemcpy(exact_row, d_exact.ptr, static_cast<size_t>(n_queries) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return DS_OK;

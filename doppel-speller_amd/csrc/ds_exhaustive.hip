@@ -20,6 +20,7 @@
 // One query whose tile holds millions of rows is spread over thousands of workgroups; no atomics, no arrival order.
 #include <algorithm>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_wave.h"
 
@@ -158,8 +159,7 @@ static int fold(const float *d_probabilities, int64_t n_queries, int64_t tile_ro
         args.n_blocks = n_queries * slices;
         args.out = slices == 1 ? d_running : buffers[level & 1];
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>(args.n_blocks, 256 * 64));
-        hipLaunchKernelGGL(ds_exhaustive_select_kernel, dim3(grid), dim3(kFoldThreads), 0, stream, args);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_exhaustive_select_kernel, dim3(grid), dim3(kFoldThreads), 0, stream, args);
         if (slices == 1) return DS_OK;
         args.probabilities = nullptr;
         args.running = nullptr;
@@ -204,8 +204,7 @@ int ds_exhaustive_fold_device(const float *d_probabilities, int64_t n_queries, i
     ds::partial_words(n_queries, tile_rows, n, &first, &second);
     ds::DeviceBuffer<uint64_t> partials;    // freed on return, behind the synchronisation below
     if (first + second) {
-        const int allocated = partials.allocate(static_cast<size_t>(first + second));
-        if (allocated != DS_OK) return allocated;
+        DS_TRY(partials.allocate(static_cast<size_t>(first + second)));
     }
     const int status = ds::fold(d_probabilities, n_queries, tile_rows, row_first, n, d_running, partials.ptr,
                                 partials.ptr ? partials.ptr + first : nullptr, s);
@@ -224,9 +223,8 @@ int ds_exhaustive_finish_device(const uint64_t *d_running, int64_t n_queries, in
     if (n_queries == 0) return DS_OK;
     const int64_t n_slots = n_queries * n;
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n_slots + 255) / 256, 256 * 16));
-    hipLaunchKernelGGL(ds::ds_exhaustive_finish_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_running,
-                       n_slots, d_out_row, d_out_probability);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_exhaustive_finish_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_running,
+              n_slots, d_out_row, d_out_probability);
     return DS_OK;
 }
 
@@ -270,8 +268,7 @@ int ds_exhaustive_rank_device(ds_titles *queries, ds_titles *truth, ds_forest *f
     const size_t at_features = carve(pairs * DS_FEATURES_COUNT * 4), at_probabilities = carve(pairs * 4);
     const size_t at_pair_q = carve(pairs * 4), at_pair_t = carve(pairs * 4);
     ds::DeviceBuffer<unsigned char> workspace;
-    const int allocated = workspace.allocate(bytes);
-    if (allocated != DS_OK) return allocated;
+    DS_TRY(workspace.allocate(bytes));
     uint64_t *d_running = reinterpret_cast<uint64_t *>(workspace.ptr + at_running);
     uint64_t *d_first = reinterpret_cast<uint64_t *>(workspace.ptr + at_first);
     uint64_t *d_second = reinterpret_cast<uint64_t *>(workspace.ptr + at_second);
@@ -288,10 +285,9 @@ int ds_exhaustive_rank_device(ds_titles *queries, ds_titles *truth, ds_forest *f
             for (int64_t r0 = 0; r0 < N; r0 += tile_rows) {
                 const int64_t rows = std::min(tile_rows, N - r0), here = nq * rows;
                 const unsigned grid = static_cast<unsigned>(std::min<int64_t>((here + 255) / 256, 256 * 16));
-                hipLaunchKernelGGL(ds::ds_exhaustive_pairs_kernel, dim3(grid), dim3(256), 0, s,
-                                   static_cast<int32_t>(q_first + q0), static_cast<int32_t>(r0),
-                                   static_cast<uint32_t>(rows), static_cast<uint32_t>(here), d_pair_q, d_pair_t);
-                DS_HIP(hipGetLastError());
+                DS_LAUNCH(ds::ds_exhaustive_pairs_kernel, dim3(grid), dim3(256), 0, s,
+                          static_cast<int32_t>(q_first + q0), static_cast<int32_t>(r0),
+                          static_cast<uint32_t>(rows), static_cast<uint32_t>(here), d_pair_q, d_pair_t);
                 int step = ds_construct_features_indexed_device(queries, truth, d_pair_q, d_pair_t, q_first + q0,
                                                                 static_cast<int32_t>(rows), space_code, n_truth, here,
                                                                 d_features, stream);

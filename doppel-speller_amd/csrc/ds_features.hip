@@ -20,7 +20,7 @@
 #include <map>
 #include <mutex>
 
-#include "ds_common.h"
+#include "ds_launch.h"
 #include "ds_host.h"
 
 namespace ds {
@@ -917,8 +917,7 @@ static int stage_chunk(const FeatureInputs &in, FeatureSlot &slot, int device, i
     args.pair_q = nullptr; args.pair_t = nullptr; args.out = slot.d_out; args.t_records = nullptr; args.unit_queue = nullptr; args.unit_pairs = 2;
     args.q_stride = 0; args.t_stride = 0; args.n_q = m; args.n_t = m; args.n = m; args.q_first = 0; args.k = 0;
     args.n_truth = in.n_truth; args.space_code = in.space_code;
-    const int status = launch_features(args, device, slot.stream);
-    if (status != DS_OK) return status;
+    DS_TRY(launch_features(args, device, slot.stream));
     const size_t out_bytes = static_cast<size_t>(m) * DS_FEATURES_COUNT * sizeof(float);
     DS_HIP(hipMemcpyAsync(slot.h_out, slot.d_out, out_bytes, hipMemcpyDeviceToHost, slot.stream));
     DS_HIP(hipStreamSynchronize(slot.stream));
@@ -932,8 +931,7 @@ static int staged_features(const FeatureInputs &in, int device)
     std::lock_guard<std::mutex> guard(staging.mutex);
     const int64_t chunks = (in.n + kStageChunk - 1) / kStageChunk;
     const int workers = static_cast<int>(std::min<int64_t>(chunks, std::min(host_threads(), kStageMaxSlots)));
-    const int ensured = staging.ensure(device, workers);
-    if (ensured != DS_OK) return ensured;
+    DS_TRY(staging.ensure(device, workers));
     std::atomic<int64_t> next{0};
     std::atomic<int> failed{DS_OK};
     FirstError error;   // ds_last_error() is thread-local: a worker's message is carried over to the calling thread
@@ -977,8 +975,7 @@ static int launch_features(const FeatureArgs &args, int device, hipStream_t stre
         static bool ready[64] = {false};
         std::lock_guard<std::mutex> guard(mutex);
         if (device >= 0 && device < 64 && !ready[device]) {
-            hipLaunchKernelGGL(ds_ratio_table_kernel, dim3((kRatioEntries + 255) / 256), dim3(256), 0, stream);
-            DS_HIP(hipGetLastError());
+            DS_LAUNCH(ds_ratio_table_kernel, dim3((kRatioEntries + 255) / 256), dim3(256), 0, stream);
             DS_HIP(hipStreamSynchronize(stream));
             ready[device] = true;
         }
@@ -998,10 +995,9 @@ static int launch_features(const FeatureArgs &args, int device, hipStream_t stre
         grid = static_cast<int>((waves + kFeatKernelWaves - 1) / kFeatKernelWaves);
     }
     if (args.t_records != nullptr)
-        hipLaunchKernelGGL(ds_construct_features_kernel<true>, dim3(grid), dim3(kFeatKernelWaves * 64), 0, stream, args);
+        DS_LAUNCH(ds_construct_features_kernel<true>, dim3(grid), dim3(kFeatKernelWaves * 64), 0, stream, args);
     else
-        hipLaunchKernelGGL(ds_construct_features_kernel<false>, dim3(grid), dim3(kFeatKernelWaves * 64), 0, stream, args);
-    DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_construct_features_kernel<false>, dim3(grid), dim3(kFeatKernelWaves * 64), 0, stream, args);
     return DS_OK;
 }
 
@@ -1020,10 +1016,9 @@ static int ensure_truth_records(ds_titles *truth, uint32_t n_truth, uint8_t spac
             return DS_OK;
         }
     }
-    hipLaunchKernelGGL(ds_truth_records_kernel, dim3(static_cast<unsigned>((truth->n + 255) / 256)), dim3(256), 0, stream,
-                       truth->enc.ptr, truth->stride, truth->len.ptr, truth->counts.ptr, truth->n, n_truth, space_code,
-                       reinterpret_cast<TruthRecord *>(truth->records.ptr));
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_truth_records_kernel, dim3(static_cast<unsigned>((truth->n + 255) / 256)), dim3(256), 0, stream,
+              truth->enc.ptr, truth->stride, truth->len.ptr, truth->counts.ptr, truth->n, n_truth, space_code,
+              reinterpret_cast<TruthRecord *>(truth->records.ptr));
     DS_HIP(hipStreamSynchronize(stream));   // once per (n_truth, space code): complete before a launch on ANY stream reads them
     truth->records_n_truth = n_truth;
     truth->records_space = space_code;
@@ -1155,8 +1150,7 @@ int ds_construct_features_indexed_device(ds_titles *queries, ds_titles *truth, c
     args.n_t = truth->n; args.n = n; args.q_first = q_first; args.k = d_pair_q ? 0 : k; args.n_truth = n_truth;
     args.space_code = space_code;
     // a caller that switches between streams orders them itself (the records are written once per (n_truth, space code))
-    const int ensured = ds::ensure_truth_records(truth, n_truth, space_code, static_cast<hipStream_t>(stream));
-    if (ensured != DS_OK) return ensured;
+    DS_TRY(ds::ensure_truth_records(truth, n_truth, space_code, static_cast<hipStream_t>(stream)));
     args.t_records = truth->records_enabled ? truth->records.ptr : nullptr;
     // the launch's work-queue head: one of 64 words of the truth table, taken in turn -- launches that overlap on the device (other
     // streams) never share a head (the CALLS are still one at a time per table: the handles are not thread-safe)
@@ -1180,13 +1174,11 @@ int ds_construct_features_indexed(ds_titles *queries, ds_titles *truth, const in
     DS_HIP(hipSetDevice(truth->device));
     ds::DeviceBuffer<int32_t> d_q, d_t;
     ds::DeviceBuffer<float> d_out;
-    int status = d_q.upload(pair_q, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_t.upload(pair_t, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_out.allocate(static_cast<size_t>(n) * DS_FEATURES_COUNT);
-    if (status != DS_OK) return status;
-    status = ds_construct_features_indexed_device(queries, truth, d_q.ptr, d_t.ptr, 0, 0, space_code, n_truth, n,
-                                                  d_out.ptr, nullptr);
-    if (status != DS_OK) return status;
+    DS_TRY(d_q.upload(pair_q, static_cast<size_t>(n)));
+    DS_TRY(d_t.upload(pair_t, static_cast<size_t>(n)));
+    DS_TRY(d_out.allocate(static_cast<size_t>(n) * DS_FEATURES_COUNT));
+    DS_TRY(ds_construct_features_indexed_device(queries, truth, d_q.ptr, d_t.ptr, 0, 0, space_code, n_truth, n,
+                                                d_out.ptr, nullptr));
     DS_HIP(hipMemcpy(out, d_out.ptr, d_out.bytes(), hipMemcpyDeviceToHost));
     return DS_OK;
 }
@@ -1207,19 +1199,17 @@ int ds_levenshtein_ratio_batch(const uint8_t *a_chars, const int64_t *a_off, con
     DS_HIP(hipSetDevice(device));
     ds::DeviceBuffer<uint8_t> d_a, d_b, d_out;
     ds::DeviceBuffer<int64_t> d_aoff, d_boff;
-    int status = d_a.upload(a_chars, static_cast<size_t>(a_off[n] > 0 ? a_off[n] : 0));
-    if (status == DS_OK && a_off[n] == 0) status = d_a.allocate(1);
-    if (status == DS_OK) status = d_b.upload(b_chars, static_cast<size_t>(b_off[n] > 0 ? b_off[n] : 0));
-    if (status == DS_OK && b_off[n] == 0) status = d_b.allocate(1);
-    if (status == DS_OK) status = d_aoff.upload(a_off, static_cast<size_t>(n + 1));
-    if (status == DS_OK) status = d_boff.upload(b_off, static_cast<size_t>(n + 1));
-    if (status == DS_OK) status = d_out.allocate(static_cast<size_t>(n));
-    if (status != DS_OK) return status;
+    DS_TRY(d_a.upload(a_chars, static_cast<size_t>(a_off[n] > 0 ? a_off[n] : 0)));
+    if (a_off[n] == 0) DS_TRY(d_a.allocate(1));
+    DS_TRY(d_b.upload(b_chars, static_cast<size_t>(b_off[n] > 0 ? b_off[n] : 0)));
+    if (b_off[n] == 0) DS_TRY(d_b.allocate(1));
+    DS_TRY(d_aoff.upload(a_off, static_cast<size_t>(n + 1)));
+    DS_TRY(d_boff.upload(b_off, static_cast<size_t>(n + 1)));
+    DS_TRY(d_out.allocate(static_cast<size_t>(n)));
     ds::LevArgs args{d_a.ptr, d_aoff.ptr, d_b.ptr, d_boff.ptr, d_out.ptr, n, method};
     const int64_t blocks_needed = (n + ds::kFeatWaves - 1) / ds::kFeatWaves;
     const int grid = static_cast<int>(std::min<int64_t>(blocks_needed, 256 * 32));
-    hipLaunchKernelGGL(ds::ds_levenshtein_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0, nullptr, args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_levenshtein_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0, nullptr, args);
     DS_HIP(hipMemcpy(out, d_out.ptr, static_cast<size_t>(n), hipMemcpyDeviceToHost));
     return DS_OK;
 }
@@ -1252,13 +1242,11 @@ int ds_close_matches_device(ds_titles *queries, ds_titles *truth, const int32_t 
     args.q_first = q_first; args.k = k; args.threshold = threshold; args.space_code = space_code;
     const int64_t blocks_needed = (args.n + ds::kFeatWaves - 1) / ds::kFeatWaves;
     const int grid = static_cast<int>(std::min<int64_t>(blocks_needed, 256 * 32));
-    hipLaunchKernelGGL(ds::ds_close_ratio_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0,
-                       static_cast<hipStream_t>(stream), args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_close_ratio_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0,
+              static_cast<hipStream_t>(stream), args);
     if (d_best_row) {
-        hipLaunchKernelGGL(ds::ds_close_best_kernel, dim3(static_cast<unsigned>((n_queries + 255) / 256)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), args);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_close_best_kernel, dim3(static_cast<unsigned>((n_queries + 255) / 256)), dim3(256), 0,
+                  static_cast<hipStream_t>(stream), args);
     }
     return DS_OK;
 }
@@ -1285,9 +1273,8 @@ int ds_close_parts_device(ds_titles *queries, ds_titles *truth, const int32_t *d
     args.d = d_d; args.r = d_r; args.s = d_s; args.t_min = t_min; args.t_max = t_max;
     const int64_t blocks_needed = (close.n + ds::kFeatWaves - 1) / ds::kFeatWaves;
     const int grid = static_cast<int>(std::min<int64_t>(blocks_needed, 256 * 32));
-    hipLaunchKernelGGL(ds::ds_close_parts_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0,
-                       static_cast<hipStream_t>(stream), args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_close_parts_kernel, dim3(grid), dim3(ds::kFeatWaves * 64), 0,
+              static_cast<hipStream_t>(stream), args);
     return DS_OK;
 }
 
@@ -1304,14 +1291,12 @@ int ds_close_matches(ds_titles *queries, ds_titles *truth, const int32_t *pair_t
     const size_t n = static_cast<size_t>(n_queries) * static_cast<size_t>(k);
     ds::DeviceBuffer<int32_t> d_t, d_best;
     ds::DeviceBuffer<uint8_t> d_key, d_ratios;
-    int status = d_t.upload(pair_t, n);
-    if (status == DS_OK) status = d_key.upload(sort_key, 256);
-    if (status == DS_OK) status = d_ratios.allocate(n);
-    if (status == DS_OK) status = d_best.allocate(static_cast<size_t>(n_queries));
-    if (status != DS_OK) return status;
-    status = ds_close_matches_device(queries, truth, d_t.ptr, 0, k, n_queries, space_code, d_key.ptr, threshold,
-                                     d_ratios.ptr, d_best.ptr, nullptr);
-    if (status != DS_OK) return status;
+    DS_TRY(d_t.upload(pair_t, n));
+    DS_TRY(d_key.upload(sort_key, 256));
+    DS_TRY(d_ratios.allocate(n));
+    DS_TRY(d_best.allocate(static_cast<size_t>(n_queries)));
+    DS_TRY(ds_close_matches_device(queries, truth, d_t.ptr, 0, k, n_queries, space_code, d_key.ptr, threshold,
+                                   d_ratios.ptr, d_best.ptr, nullptr));
     DS_HIP(hipMemcpy(ratios, d_ratios.ptr, n, hipMemcpyDeviceToHost));
     DS_HIP(hipMemcpy(best_row, d_best.ptr, static_cast<size_t>(n_queries) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return DS_OK;

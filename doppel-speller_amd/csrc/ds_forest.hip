@@ -12,6 +12,7 @@
 // One thread per row: the rows of a workgroup are staged in LDS (row-major 66-float reads would be uncoalesced), the
 // node arrays (a few hundred KiB for a typical model) stay L2-resident and are walked by all rows of a wavefront in
 // the same tree at the same time.
+#include "ds_launch.h"
 #include "ds_forest.h"
 
 namespace ds {
@@ -115,12 +116,9 @@ int ds_forest_predict_device(ds_forest *forest, const float *d_rows, int64_t n, 
     const int64_t blocks = (n + ds::kForestThreads - 1) / ds::kForestThreads;
     const int grid = static_cast<int>(std::min<int64_t>(blocks, 256 * 16));
     const size_t lds = static_cast<size_t>(ds::kForestThreads) * (forest->n_features + 1) * sizeof(float);
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds::ds_forest_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL(ds::ds_forest_kernel, dim3(grid), dim3(ds::kForestThreads), lds, static_cast<hipStream_t>(stream),
-                       args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds::ds_forest_kernel, lds));
+    DS_LAUNCH(ds::ds_forest_kernel, dim3(grid), dim3(ds::kForestThreads), lds, static_cast<hipStream_t>(stream),
+              args);
     return DS_OK;
 }
 
@@ -130,17 +128,17 @@ int ds_forest_predict(ds_forest *forest, const float *rows, int64_t n, float *ma
     if (n == 0) return DS_OK;
     DS_REQUIRE(rows && (margins || probabilities), "ds_forest_predict: null pointer");
     DS_HIP(hipSetDevice(forest->device));
-    ds::DeviceBuffer<float> d_rows, d_margins, d_probabilities;
-    int status = d_rows.upload(rows, static_cast<size_t>(n) * forest->n_features);
-    if (status == DS_OK && margins) status = d_margins.allocate(static_cast<size_t>(n));
-    if (status == DS_OK && probabilities) status = d_probabilities.allocate(static_cast<size_t>(n));
-    if (status != DS_OK) return status;
-    status = ds_forest_predict_device(forest, d_rows.ptr, n, margins ? d_margins.ptr : nullptr,
-                                      probabilities ? d_probabilities.ptr : nullptr, nullptr);
-    if (status != DS_OK) return status;
+    ds::Scratch scratch;
+    const float *d_rows = nullptr;
+    float *d_margins = nullptr, *d_probabilities = nullptr;
+    scratch.stage(&d_rows, rows, static_cast<size_t>(n) * forest->n_features);
+    if (margins) scratch.add(&d_margins, static_cast<size_t>(n));
+    if (probabilities) scratch.add(&d_probabilities, static_cast<size_t>(n));
+    DS_TRY(scratch.allocate("ds_forest_predict"));
+    DS_TRY(ds_forest_predict_device(forest, d_rows, n, d_margins, d_probabilities, nullptr));
     DS_HIP(hipDeviceSynchronize());
-    if (margins) DS_HIP(hipMemcpy(margins, d_margins.ptr, sizeof(float) * n, hipMemcpyDeviceToHost));
-    if (probabilities) DS_HIP(hipMemcpy(probabilities, d_probabilities.ptr, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (margins) DS_HIP(hipMemcpy(margins, d_margins, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (probabilities) DS_HIP(hipMemcpy(probabilities, d_probabilities, sizeof(float) * n, hipMemcpyDeviceToHost));
     return DS_OK;
 }
 

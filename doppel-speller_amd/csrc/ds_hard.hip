@@ -30,6 +30,7 @@
 // every later chunk keeps it negative and writes nothing, and ds_hard_total reports it as DS_E_ARG.
 #include <algorithm>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_wave.h"
 
@@ -220,16 +221,13 @@ int ds_hard_negatives_device(const int32_t *d_rows, const float *d_margins, int6
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t passes = (n_queries + ds::kHardWaves - 1) / ds::kHardWaves;
     const dim3 grid(ds::grid_cap(passes, ds::g_hard_max_blocks.get()));
-    hipLaunchKernelGGL(ds::ds_hard_count_kernel, grid, dim3(ds::kHardThreads), 0, s, a);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_hard_scan_kernel, dim3(1), dim3(ds::kHardScanThreads), 0, s, d_offsets, n_queries, capacity,
-                       d_total);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_hard_count_kernel, grid, dim3(ds::kHardThreads), 0, s, a);
+    DS_LAUNCH(ds::ds_hard_scan_kernel, dim3(1), dim3(ds::kHardScanThreads), 0, s, d_offsets, n_queries, capacity,
+              d_total);
     if (k <= 64 * ds::kHardRegisterKeys)
-        hipLaunchKernelGGL(ds::ds_hard_emit_kernel<true>, grid, dim3(ds::kHardThreads), 0, s, a);
+        DS_LAUNCH(ds::ds_hard_emit_kernel<true>, grid, dim3(ds::kHardThreads), 0, s, a);
     else
-        hipLaunchKernelGGL(ds::ds_hard_emit_kernel<false>, grid, dim3(ds::kHardThreads), 0, s, a);
-    DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_hard_emit_kernel<false>, grid, dim3(ds::kHardThreads), 0, s, a);
     return DS_OK;
 }
 

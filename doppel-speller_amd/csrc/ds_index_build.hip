@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <memory>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_wave.h"
 
@@ -438,14 +439,11 @@ struct BuildScratch {
 int exclusive_scan(BuildScratch &scratch, const uint32_t *in, const uint64_t *keys, int64_t n_in, uint32_t *out, int64_t n_out)
 {
     const int64_t blocks = build_tiles(n_out);
-    hipLaunchKernelGGL(ds_build_scan_reduce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBuildThreads), 0, 0, in, keys, n_in,
-                       scratch.spine.ptr);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds_build_scan_spine_kernel, dim3(1), dim3(kBuildThreads), 0, 0, scratch.spine.ptr, blocks);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds_build_scan_apply_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBuildThreads), 0, 0, in, keys, n_in, out,
-                       n_out, scratch.spine.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_build_scan_reduce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBuildThreads), 0, 0, in, keys, n_in,
+              scratch.spine.ptr);
+    DS_LAUNCH(ds_build_scan_spine_kernel, dim3(1), dim3(kBuildThreads), 0, 0, scratch.spine.ptr, blocks);
+    DS_LAUNCH(ds_build_scan_apply_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBuildThreads), 0, 0, in, keys, n_in, out,
+              n_out, scratch.spine.ptr);
     return DS_OK;
 }
 
@@ -454,14 +452,11 @@ int sort_bits(BuildScratch &scratch, uint64_t *&from, uint64_t *&to, int64_t n, 
 {
     const int64_t tiles = build_tiles(n);
     for (int shift = low; shift < high; shift += 8) {
-        hipLaunchKernelGGL(ds_build_sort_count_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kBuildThreads), 0, 0, from, n, field,
-                           shift, scratch.table.ptr, tiles);
-        DS_HIP(hipGetLastError());
-        const int scanned = exclusive_scan(scratch, scratch.table.ptr, nullptr, 256 * tiles, scratch.table.ptr, 256 * tiles);
-        if (scanned != DS_OK) return scanned;
-        hipLaunchKernelGGL(ds_build_sort_scatter_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kBuildThreads), 0, 0, from, to, n,
-                           field, shift, scratch.table.ptr, tiles);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_build_sort_count_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kBuildThreads), 0, 0, from, n, field,
+                  shift, scratch.table.ptr, tiles);
+        DS_TRY(exclusive_scan(scratch, scratch.table.ptr, nullptr, 256 * tiles, scratch.table.ptr, 256 * tiles));
+        DS_LAUNCH(ds_build_sort_scatter_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kBuildThreads), 0, 0, from, to, n,
+                  field, shift, scratch.table.ptr, tiles);
         std::swap(from, to);
     }
     return DS_OK;
@@ -477,12 +472,6 @@ int bits_of(int64_t count)   // bits that hold every value below count
 struct IndexDeleter {
     void operator()(ds_index *index) const { ds_index_destroy(index); }
 };
-
-#define DS_BUILD_STEP(call)                       \
-    do {                                          \
-        const int ds_build_status_ = (call);      \
-        if (ds_build_status_ != DS_OK) return ds_build_status_; \
-    } while (0)
 
 }  // namespace
 }  // namespace ds
@@ -550,28 +539,21 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
     const int64_t quads_max = nnz / 4 + 2 * std::min(nnz, V * n_tiles);
     const int64_t index_bytes = 4 * cells + 16 * quads_max + 5 * V + 4 * (N + 8) + 8 * n_tiles + 32 * N + 4 * (N + 1) +
                                 (wide_cols ? 4 : 2) * nnz + 4 * kControlWords;
-    size_t free_bytes = 0, total_bytes = 0;
-    DS_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
-    if (static_cast<size_t>(scratch_bytes + index_bytes) + (size_t(64) << 20) > free_bytes) {
-        set_error("ds_index_create_device: the build needs %lld bytes of scratch and %lld for the index, %zu bytes of HBM are free",
-                  (long long)scratch_bytes, (long long)index_bytes, free_bytes);
-        return DS_E_HIP;
-    }
+    DS_TRY(check_free(scratch_bytes + index_bytes, "ds_index_create_device: scratch and index together"));
 
     // ---- upload and check --------------------------------------------------------------------------------------------
     DeviceBuffer<int64_t> d_rowptr;
     DeviceBuffer<int32_t> d_idx, position;
     DeviceBuffer<float> d_sums;
     DeviceBuffer<unsigned long long> d_flags;   // [0] lowest bad column, [1] (low word) literal_only
-    DS_BUILD_STEP(d_rowptr.upload(rowptr, static_cast<size_t>(V + 1)));
-    DS_BUILD_STEP(d_idx.upload(truth_idx, static_cast<size_t>(nnz)));
-    DS_BUILD_STEP(d_sums.upload(sums32, static_cast<size_t>(N)));
+    DS_TRY(d_rowptr.upload(rowptr, static_cast<size_t>(V + 1)));
+    DS_TRY(d_idx.upload(truth_idx, static_cast<size_t>(nnz)));
+    DS_TRY(d_sums.upload(sums32, static_cast<size_t>(N)));
     const unsigned long long flags_start[2] = {kNoBadColumn, 0ull};
-    DS_BUILD_STEP(d_flags.upload(flags_start, 2));
+    DS_TRY(d_flags.upload(flags_start, 2));
     if (nnz > 0) {
-        hipLaunchKernelGGL(ds_build_check_kernel, dim3(blocks_for(nnz)), dim3(kBuildThreads), 0, 0, d_rowptr.ptr, d_idx.ptr, V, N, nnz,
-                           d_flags.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_build_check_kernel, dim3(blocks_for(nnz)), dim3(kBuildThreads), 0, 0, d_rowptr.ptr, d_idx.ptr, V, N, nnz,
+                  d_flags.ptr);
         unsigned long long bad_column = kNoBadColumn;
         DS_HIP(hipMemcpy(&bad_column, d_flags.ptr, sizeof(bad_column), hipMemcpyDeviceToHost));
         // nothing below runs on rows that have not passed this check
@@ -590,79 +572,72 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
     index->rows_sorted = sort_rows;
     index->forward_wide_start = false;
     index->forward_wide_cols = wide_cols;
-    DS_BUILD_STEP(index->idf32.upload(idf32, static_cast<size_t>(V)));
-    DS_BUILD_STEP(index->sig_column.upload(sig_column.data(), sig_column.size()));
-    DS_BUILD_STEP(index->sums32.allocate(static_cast<size_t>(N) + 8));
+    DS_TRY(index->idf32.upload(idf32, static_cast<size_t>(V)));
+    DS_TRY(index->sig_column.upload(sig_column.data(), sig_column.size()));
+    DS_TRY(index->sums32.allocate(static_cast<size_t>(N) + 8));
     DS_HIP(hipMemset(index->sums32.ptr, 0, index->sums32.bytes()));
-    DS_BUILD_STEP(index->signature.allocate(static_cast<size_t>(N) * kRowRecordWords));
+    DS_TRY(index->signature.allocate(static_cast<size_t>(N) * kRowRecordWords));
     DS_HIP(hipMemset(index->signature.ptr, 0, index->signature.bytes()));
-    DS_BUILD_STEP(index->row_start.allocate(static_cast<size_t>(N + 1) * 4));
+    DS_TRY(index->row_start.allocate(static_cast<size_t>(N + 1) * 4));
     DS_HIP(hipMemset(index->row_start.ptr, 0, index->row_start.bytes()));
     // the host's size, which ds_index_info reports: the columns themselves, 4 bytes only when there is none
-    DS_BUILD_STEP(index->row_cols.allocate(nnz > 0 ? static_cast<size_t>(nnz) * (wide_cols ? 4 : 2) : 4));
-    DS_BUILD_STEP(index->col_ptr.allocate(static_cast<size_t>(cells)));
-    DS_BUILD_STEP(index->tile_sums_min.allocate(static_cast<size_t>(n_tiles)));
-    DS_BUILD_STEP(index->tile_sums_max.allocate(static_cast<size_t>(n_tiles)));
+    DS_TRY(index->row_cols.allocate(nnz > 0 ? static_cast<size_t>(nnz) * (wide_cols ? 4 : 2) : 4));
+    DS_TRY(index->col_ptr.allocate(static_cast<size_t>(cells)));
+    DS_TRY(index->tile_sums_min.allocate(static_cast<size_t>(n_tiles)));
+    DS_TRY(index->tile_sums_max.allocate(static_cast<size_t>(n_tiles)));
 
     BuildScratch scratch;
-    DS_BUILD_STEP(scratch.keys_a.allocate(static_cast<size_t>(items_max)));
-    DS_BUILD_STEP(scratch.keys_b.allocate(static_cast<size_t>(items_max)));
-    DS_BUILD_STEP(scratch.table.allocate(static_cast<size_t>(256 * sort_tiles)));
-    DS_BUILD_STEP(scratch.spine.allocate(static_cast<size_t>(build_tiles(scan_max) + 1)));
-    DS_BUILD_STEP(position.allocate(static_cast<size_t>(N)));
+    DS_TRY(scratch.keys_a.allocate(static_cast<size_t>(items_max)));
+    DS_TRY(scratch.keys_b.allocate(static_cast<size_t>(items_max)));
+    DS_TRY(scratch.table.allocate(static_cast<size_t>(256 * sort_tiles)));
+    DS_TRY(scratch.spine.allocate(static_cast<size_t>(build_tiles(scan_max) + 1)));
+    DS_TRY(position.allocate(static_cast<size_t>(N)));
     uint64_t *from = scratch.keys_a.ptr, *to = scratch.keys_b.ptr;
     uint32_t *records = index->signature.ptr;
     uint32_t *row_start = reinterpret_cast<uint32_t *>(index->row_start.ptr);
     const dim3 threads(kBuildThreads);
 
     // ---- internal row order ------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(ds_build_row_keys_kernel, dim3(blocks_for(N)), threads, 0, 0, d_sums.ptr, N, sort_rows ? 1 : 0, from);
-    DS_HIP(hipGetLastError());
-    if (sort_rows) DS_BUILD_STEP(sort_bits(scratch, from, to, N, nullptr, 32, 64));
-    hipLaunchKernelGGL(ds_build_rows_kernel, dim3(blocks_for(N)), threads, 0, 0, from, d_sums.ptr, N, position.ptr, index->sums32.ptr,
-                       records);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_build_row_keys_kernel, dim3(blocks_for(N)), threads, 0, 0, d_sums.ptr, N, sort_rows ? 1 : 0, from);
+    if (sort_rows) DS_TRY(sort_bits(scratch, from, to, N, nullptr, 32, 64));
+    DS_LAUNCH(ds_build_rows_kernel, dim3(blocks_for(N)), threads, 0, 0, from, d_sums.ptr, N, position.ptr, index->sums32.ptr,
+              records);
 
     // ---- forward index, then every column's list in internal rows ----------------------------------------------------
     DeviceBuffer<uint32_t> cell_begin, even_before;
-    DS_BUILD_STEP(cell_begin.allocate(static_cast<size_t>(cells)));
-    DS_BUILD_STEP(even_before.allocate(static_cast<size_t>(nnz) + 1));
+    DS_TRY(cell_begin.allocate(static_cast<size_t>(cells)));
+    DS_TRY(even_before.allocate(static_cast<size_t>(nnz) + 1));
     if (nnz > 0) {
-        hipLaunchKernelGGL(ds_build_forward_keys_kernel, dim3(blocks_for(nnz)), threads, 0, 0, d_rowptr.ptr, d_idx.ptr, position.ptr, V,
-                           nnz, from);
-        DS_HIP(hipGetLastError());
-        DS_BUILD_STEP(sort_bits(scratch, from, to, nnz, nullptr, 32, 32 + bits_of(N)));
-        hipLaunchKernelGGL(ds_build_forward_kernel, dim3(blocks_for(nnz)), threads, 0, 0, from, nnz, N, wide_cols ? 1 : 0,
-                           static_cast<void *>(index->row_cols.ptr), row_start, to);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_build_forward_keys_kernel, dim3(blocks_for(nnz)), threads, 0, 0, d_rowptr.ptr, d_idx.ptr, position.ptr, V,
+                  nnz, from);
+        DS_TRY(sort_bits(scratch, from, to, nnz, nullptr, 32, 32 + bits_of(N)));
+        DS_LAUNCH(ds_build_forward_kernel, dim3(blocks_for(nnz)), threads, 0, 0, from, nnz, N, wide_cols ? 1 : 0,
+                  static_cast<void *>(index->row_cols.ptr), row_start, to);
         std::swap(from, to);
-        DS_BUILD_STEP(sort_bits(scratch, from, to, nnz, nullptr, 32, 32 + bits_of(V)));
+        DS_TRY(sort_bits(scratch, from, to, nnz, nullptr, 32, 32 + bits_of(V)));
     }
     const uint64_t *lists = from;   // (column << 32 | internal row), ascending: the permuted CSR
     uint64_t *items = to;           // the other sort buffer: free from here on (N <= its size)
 
     // ---- signatures, idf totals, hashes ------------------------------------------------------------------------------
     DeviceBuffer<uint64_t> hash_a, hash_b, hash_bits, items_other;
-    DS_BUILD_STEP(hash_a.allocate(static_cast<size_t>(N)));
-    DS_BUILD_STEP(hash_b.allocate(static_cast<size_t>(N)));
-    DS_BUILD_STEP(hash_bits.allocate(static_cast<size_t>(N)));
+    DS_TRY(hash_a.allocate(static_cast<size_t>(N)));
+    DS_TRY(hash_b.allocate(static_cast<size_t>(N)));
+    DS_TRY(hash_bits.allocate(static_cast<size_t>(N)));
     const int hash_bits_kept = static_cast<int>(g_duplicate_hash_bits.get());
     const uint64_t hash_mask = hash_bits_kept == 64 ? ~0ull : (1ull << hash_bits_kept) - 1ull;
-    hipLaunchKernelGGL(ds_build_row_walk_kernel, dim3(blocks_for(N)), threads, 0, 0, row_start,
-                       static_cast<const void *>(index->row_cols.ptr), wide_cols ? 1 : 0, index->idf32.ptr, index->sig_column.ptr,
-                       index->sums32.ptr, N, hash_mask, records, hash_a.ptr, hash_b.ptr, hash_bits.ptr, items,
-                       reinterpret_cast<uint32_t *>(d_flags.ptr + 1));
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_build_row_walk_kernel, dim3(blocks_for(N)), threads, 0, 0, row_start,
+              static_cast<const void *>(index->row_cols.ptr), wide_cols ? 1 : 0, index->idf32.ptr, index->sig_column.ptr,
+              index->sums32.ptr, N, hash_mask, records, hash_a.ptr, hash_b.ptr, hash_bits.ptr, items,
+              reinterpret_cast<uint32_t *>(d_flags.ptr + 1));
 
     // ---- list pointers -----------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(ds_build_cells_kernel, dim3(blocks_for(cells)), threads, 0, 0, d_rowptr.ptr, lists, cells, stride, tile_rows,
-                       cell_begin.ptr);
-    DS_HIP(hipGetLastError());
-    DS_BUILD_STEP(exclusive_scan(scratch, nullptr, lists, nnz, even_before.ptr, nnz + 1));
-    hipLaunchKernelGGL(ds_build_quads_kernel, dim3(blocks_for(cells)), threads, 0, 0, cell_begin.ptr, even_before.ptr, cells, stride,
-                       index->col_ptr.ptr);
-    DS_HIP(hipGetLastError());
-    DS_BUILD_STEP(exclusive_scan(scratch, index->col_ptr.ptr, nullptr, cells, index->col_ptr.ptr, cells));
+    DS_LAUNCH(ds_build_cells_kernel, dim3(blocks_for(cells)), threads, 0, 0, d_rowptr.ptr, lists, cells, stride, tile_rows,
+              cell_begin.ptr);
+    DS_TRY(exclusive_scan(scratch, nullptr, lists, nnz, even_before.ptr, nnz + 1));
+    DS_LAUNCH(ds_build_quads_kernel, dim3(blocks_for(cells)), threads, 0, 0, cell_begin.ptr, even_before.ptr, cells, stride,
+              index->col_ptr.ptr);
+    DS_TRY(exclusive_scan(scratch, index->col_ptr.ptr, nullptr, cells, index->col_ptr.ptr, cells));
     unsigned long long quads = 0ull;
     DS_HIP(hipMemcpy(&quads, scratch.spine.ptr + build_tiles(cells), sizeof(quads), hipMemcpyDeviceToHost));
     DS_REQUIRE(quads < 0xfffffff0ull, "ds_index_create: more than 2^32 posting quads");
@@ -670,50 +645,43 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
 
     // ---- postings ----------------------------------------------------------------------------------------------------
     const uint64_t n_postings = quads * 4u;
-    DS_BUILD_STEP(index->postings.allocate(std::max<size_t>(4, static_cast<size_t>(n_postings))));
-    DS_BUILD_STEP(index->posting_sums.allocate(std::max<size_t>(4, static_cast<size_t>(n_postings))));
+    DS_TRY(index->postings.allocate(std::max<size_t>(4, static_cast<size_t>(n_postings))));
+    DS_TRY(index->posting_sums.allocate(std::max<size_t>(4, static_cast<size_t>(n_postings))));
     if (nnz > 0) {
-        hipLaunchKernelGGL(ds_build_fill_kernel, dim3(blocks_for(nnz)), threads, 0, 0, lists, cell_begin.ptr, even_before.ptr,
-                           index->col_ptr.ptr, records, nnz, stride, tile_rows, n_postings, index->postings.ptr,
-                           index->posting_sums.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_build_pad_kernel, dim3(blocks_for(cells)), threads, 0, 0, cell_begin.ptr, even_before.ptr, index->col_ptr.ptr,
-                           cells, stride, static_cast<uint32_t>(tile_rows / 2), n_postings, index->postings.ptr,
-                           index->posting_sums.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_build_fill_kernel, dim3(blocks_for(nnz)), threads, 0, 0, lists, cell_begin.ptr, even_before.ptr,
+                  index->col_ptr.ptr, records, nnz, stride, tile_rows, n_postings, index->postings.ptr,
+                  index->posting_sums.ptr);
+        DS_LAUNCH(ds_build_pad_kernel, dim3(blocks_for(cells)), threads, 0, 0, cell_begin.ptr, even_before.ptr, index->col_ptr.ptr,
+                  cells, stride, static_cast<uint32_t>(tile_rows / 2), n_postings, index->postings.ptr,
+                  index->posting_sums.ptr);
     }
 
     // ---- tile bounds -------------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(ds_build_tile_bounds_kernel, dim3(static_cast<unsigned>(n_tiles)), threads, 0, 0, index->sums32.ptr, N, tile_rows,
-                       index->tile_sums_min.ptr, index->tile_sums_max.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_build_tile_bounds_kernel, dim3(static_cast<unsigned>(n_tiles)), threads, 0, 0, index->sums32.ptr, N, tile_rows,
+              index->tile_sums_min.ptr, index->tile_sums_max.ptr);
 
     // ---- duplicate ranks ---------------------------------------------------------------------------------------------
     // the sort buffer that held the lists is needed no more once the postings are filled: the rows take both buffers
     DeviceBuffer<uint32_t> head, heads_before, run_end, verified, verified_before;
-    DS_BUILD_STEP(head.allocate(static_cast<size_t>(N)));
-    DS_BUILD_STEP(heads_before.allocate(static_cast<size_t>(N)));
-    DS_BUILD_STEP(run_end.allocate(static_cast<size_t>(N)));
-    DS_BUILD_STEP(verified.allocate(static_cast<size_t>(N)));
-    DS_BUILD_STEP(verified_before.allocate(static_cast<size_t>(N) + 1));
+    DS_TRY(head.allocate(static_cast<size_t>(N)));
+    DS_TRY(heads_before.allocate(static_cast<size_t>(N)));
+    DS_TRY(run_end.allocate(static_cast<size_t>(N)));
+    DS_TRY(verified.allocate(static_cast<size_t>(N)));
+    DS_TRY(verified_before.allocate(static_cast<size_t>(N) + 1));
     {
         uint64_t *rows_from = items, *rows_to = const_cast<uint64_t *>(lists);
-        DS_BUILD_STEP(sort_bits(scratch, rows_from, rows_to, N, hash_bits.ptr, 0, 32));
-        DS_BUILD_STEP(sort_bits(scratch, rows_from, rows_to, N, hash_b.ptr, 0, hash_bits_kept));
-        DS_BUILD_STEP(sort_bits(scratch, rows_from, rows_to, N, hash_a.ptr, 0, hash_bits_kept));
-        hipLaunchKernelGGL(ds_build_heads_kernel, dim3(blocks_for(N)), threads, 0, 0, rows_from, hash_a.ptr, hash_b.ptr, hash_bits.ptr,
-                           N, head.ptr);
-        DS_HIP(hipGetLastError());
-        DS_BUILD_STEP(exclusive_scan(scratch, head.ptr, nullptr, N, heads_before.ptr, N));
-        hipLaunchKernelGGL(ds_build_run_ends_kernel, dim3(blocks_for(N)), threads, 0, 0, head.ptr, heads_before.ptr, N, run_end.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_build_verify_kernel, dim3(blocks_for(N)), threads, 0, 0, rows_from, head.ptr, heads_before.ptr, run_end.ptr,
-                           row_start, static_cast<const void *>(index->row_cols.ptr), wide_cols ? 1 : 0, N, verified.ptr);
-        DS_HIP(hipGetLastError());
-        DS_BUILD_STEP(exclusive_scan(scratch, verified.ptr, nullptr, N, verified_before.ptr, N + 1));
-        hipLaunchKernelGGL(ds_build_ranks_kernel, dim3(blocks_for(N)), threads, 0, 0, rows_from, head.ptr, heads_before.ptr, run_end.ptr,
-                           verified.ptr, verified_before.ptr, N, records);
-        DS_HIP(hipGetLastError());
+        DS_TRY(sort_bits(scratch, rows_from, rows_to, N, hash_bits.ptr, 0, 32));
+        DS_TRY(sort_bits(scratch, rows_from, rows_to, N, hash_b.ptr, 0, hash_bits_kept));
+        DS_TRY(sort_bits(scratch, rows_from, rows_to, N, hash_a.ptr, 0, hash_bits_kept));
+        DS_LAUNCH(ds_build_heads_kernel, dim3(blocks_for(N)), threads, 0, 0, rows_from, hash_a.ptr, hash_b.ptr, hash_bits.ptr,
+                  N, head.ptr);
+        DS_TRY(exclusive_scan(scratch, head.ptr, nullptr, N, heads_before.ptr, N));
+        DS_LAUNCH(ds_build_run_ends_kernel, dim3(blocks_for(N)), threads, 0, 0, head.ptr, heads_before.ptr, N, run_end.ptr);
+        DS_LAUNCH(ds_build_verify_kernel, dim3(blocks_for(N)), threads, 0, 0, rows_from, head.ptr, heads_before.ptr, run_end.ptr,
+                  row_start, static_cast<const void *>(index->row_cols.ptr), wide_cols ? 1 : 0, N, verified.ptr);
+        DS_TRY(exclusive_scan(scratch, verified.ptr, nullptr, N, verified_before.ptr, N + 1));
+        DS_LAUNCH(ds_build_ranks_kernel, dim3(blocks_for(N)), threads, 0, 0, rows_from, head.ptr, heads_before.ptr, run_end.ptr,
+                  verified.ptr, verified_before.ptr, N, records);
     }
 
     // ---- what the host keeps: literal_only, sums_min (the host's loop over the tile minima) -----------------------------
@@ -729,7 +697,7 @@ int ds_index_create_device(const int64_t *rowptr, const int32_t *truth_idx, cons
         for (int64_t b = 0; b < n_tiles; ++b) sums_min = std::min(sums_min, tile_min[static_cast<size_t>(b)]);
         index->sums_min = sums_min;
     }
-    DS_BUILD_STEP(index->control.allocate(kControlWords));
+    DS_TRY(index->control.allocate(kControlWords));
     if (hipStreamCreate(&index->stream) != hipSuccess || hipEventCreate(&index->event_begin) != hipSuccess ||
         hipEventCreate(&index->event_fast) != hipSuccess || hipEventCreate(&index->event_dense) != hipSuccess) {
         set_error("ds_index_create_device: hipStreamCreate / hipEventCreate failed");

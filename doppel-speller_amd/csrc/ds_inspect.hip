@@ -12,6 +12,7 @@
 // Per job and wave the five terms are summed over the lanes and one lane adds them to the job's 64-bit counters in HBM.
 // The grid is row blocks x job groups (an evaluation set of ten thousand rows is only forty row blocks); both
 // dimensions stride, and every sum is an integer sum, so no number depends on the split.
+#include "ds_launch.h"
 #include "ds_forest.h"
 #include "ds_metrics.h"
 #include "ds_train.h"
@@ -262,12 +263,9 @@ static int inspect_enqueue(ds_forest *forest, const float *d_rows, int64_t n, co
     args.n_groups = static_cast<int32_t>((n_jobs + per_block - 1) / per_block);
     const int group_grid = std::min<int>(args.n_groups, kInspectMaxJobGroups);
     const size_t lds = static_cast<size_t>(kForestThreads) * (forest->n_features + 1) * sizeof(float);
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_forest_inspect_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL(ds_forest_inspect_kernel, dim3(static_cast<unsigned>(row_grid), static_cast<unsigned>(group_grid)),
-                       dim3(kForestThreads), lds, stream, args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds_forest_inspect_kernel, lds));
+    DS_LAUNCH(ds_forest_inspect_kernel, dim3(static_cast<unsigned>(row_grid), static_cast<unsigned>(group_grid)),
+              dim3(kForestThreads), lds, stream, args);
     return DS_OK;
 }
 
@@ -280,8 +278,7 @@ int ds_forest_inspect_device(ds_forest *forest, const float *d_rows, int64_t n, 
                              unsigned long long *d_out, void *stream)
 {
     const char *what = "ds_forest_inspect_device";
-    int status = ds::check_scalars(what, n, n_jobs, threshold);
-    if (status != DS_OK) return status;
+    DS_TRY(ds::check_scalars(what, n, n_jobs, threshold));
     DS_REQUIRE(forest != nullptr, "%s: null forest", what);
     if (n_jobs == 0) return DS_OK;
     DS_REQUIRE(d_jobs != nullptr && d_out != nullptr && (n == 0 || d_rows != nullptr), "%s: null pointer", what);
@@ -291,8 +288,7 @@ int ds_forest_inspect_device(ds_forest *forest, const float *d_rows, int64_t n, 
     std::vector<ds_inspect_job> jobs(static_cast<size_t>(n_jobs));
     DS_HIP(hipMemcpyAsync(jobs.data(), d_jobs, jobs.size() * sizeof(ds_inspect_job), hipMemcpyDeviceToHost, queue));
     DS_HIP(hipStreamSynchronize(queue));
-    status = ds::check_jobs(what, jobs.data(), n_jobs, forest->n_features);
-    if (status != DS_OK) return status;
+    DS_TRY(ds::check_jobs(what, jobs.data(), n_jobs, forest->n_features));
     return ds::inspect_enqueue(forest, d_rows, n, d_target, d_jobs, n_jobs, seed, threshold, d_out, queue);
 }
 
@@ -316,19 +312,18 @@ int ds_forest_inspect(ds_forest *forest, const float *rows, int64_t n, const flo
         return DS_OK;
     }
     DS_HIP(hipSetDevice(forest->device));
-    ds::DeviceBuffer<float> d_rows, d_target;
-    ds::DeviceBuffer<ds_inspect_job> d_jobs;
-    ds::DeviceBuffer<unsigned long long> d_out;
-    status = d_rows.upload(rows, static_cast<size_t>(n) * forest->n_features);
-    if (status == DS_OK && target) status = d_target.upload(target, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_jobs.upload(jobs, static_cast<size_t>(n_jobs));
-    if (status == DS_OK) status = d_out.allocate(counters);
-    if (status != DS_OK) return status;
-    status = ds::inspect_enqueue(forest, d_rows.ptr, n, target ? d_target.ptr : nullptr, d_jobs.ptr, n_jobs, seed,
-                                 threshold, d_out.ptr, nullptr);
-    if (status != DS_OK) return status;
+    ds::Scratch scratch;
+    const float *d_rows = nullptr, *d_target = nullptr;
+    const ds_inspect_job *d_jobs = nullptr;
+    unsigned long long *d_out = nullptr;
+    scratch.stage(&d_rows, rows, static_cast<size_t>(n) * forest->n_features);
+    if (target) scratch.stage(&d_target, target, static_cast<size_t>(n));
+    scratch.stage(&d_jobs, jobs, static_cast<size_t>(n_jobs));
+    scratch.add(&d_out, counters);
+    DS_TRY(scratch.allocate(what));
+    DS_TRY(ds::inspect_enqueue(forest, d_rows, n, d_target, d_jobs, n_jobs, seed, threshold, d_out, nullptr));
     DS_HIP(hipDeviceSynchronize());
-    DS_HIP(hipMemcpy(out, d_out.ptr, counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    DS_HIP(hipMemcpy(out, d_out, counters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return DS_OK;
 }
 

@@ -36,7 +36,7 @@
 #include <type_traits>
 #include <cstdlib>
 
-#include "ds_common.h"
+#include "ds_launch.h"
 
 namespace ds {
 namespace DS_GEOMETRY_NAME {
@@ -2363,13 +2363,10 @@ int resolve_ties(ds_index *index, hipStream_t stream, const std::vector<int32_t>
     }
     groups = std::min(groups, index->row_scratch.count / rows);
     DeviceBuffer<int32_t> d_listed;
-    const int uploaded = d_listed.upload(listed.data(), listed.size());
-    if (uploaded != DS_OK) return uploaded;
-    DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_jaccard_rowscan_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLdsBytes));
-    hipLaunchKernelGGL(ds_jaccard_rowscan_kernel, dim3(static_cast<unsigned>(groups)), dim3(kDenseThreads), kDenseLdsBytes, stream, args,
-                       index->row_scratch.ptr, d_listed.ptr, static_cast<int>(listed.size()));
-    DS_HIP(hipGetLastError());
+    DS_TRY(d_listed.upload(listed.data(), listed.size()));
+    DS_TRY(ds::allow_dynamic_lds(ds_jaccard_rowscan_kernel, kDenseLdsBytes));
+    DS_LAUNCH(ds_jaccard_rowscan_kernel, dim3(static_cast<unsigned>(groups)), dim3(kDenseThreads), kDenseLdsBytes, stream, args,
+              index->row_scratch.ptr, d_listed.ptr, static_cast<int>(listed.size()));
     DS_HIP(hipStreamSynchronize(stream));
     // several scratch vectors (up to 2 GiB) are not kept for the life of the index: the next call that needs them allocates again
     if (groups > 1) index->row_scratch.release();
@@ -2399,16 +2396,11 @@ int launch(ds_index *index, const int64_t *d_q_rowptr, const int32_t *d_q_cols, 
         if (status != DS_OK) return status;
     }
     if (!index->attributes_set) {
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_jaccard_topk_kernel<false, false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kFastLdsBytes));
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_jaccard_topk_kernel<false, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kFastLdsBytes));
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_jaccard_topk_kernel<true, false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kFastLdsBytes));
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_jaccard_topk_kernel<true, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kFastLdsBytes));
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_jaccard_dense_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLdsBytes));
+        DS_TRY(ds::allow_dynamic_lds(ds_jaccard_topk_kernel<false, false>, kFastLdsBytes));
+        DS_TRY(ds::allow_dynamic_lds(ds_jaccard_topk_kernel<false, true>, kFastLdsBytes));
+        DS_TRY(ds::allow_dynamic_lds(ds_jaccard_topk_kernel<true, false>, kFastLdsBytes));
+        DS_TRY(ds::allow_dynamic_lds(ds_jaccard_topk_kernel<true, true>, kFastLdsBytes));
+        DS_TRY(ds::allow_dynamic_lds(ds_jaccard_dense_kernel, kDenseLdsBytes));
         index->attributes_set = true;
     }
     JaccardArgs args;
@@ -2438,12 +2430,10 @@ int launch(ds_index *index, const int64_t *d_q_rowptr, const int32_t *d_q_cols, 
         const int blocks = static_cast<int>(std::min<int64_t>((Q + 4 * kOrderThreads - 1) / (4 * kOrderThreads), 256));
         const int64_t chunk = (Q + blocks - 1) / blocks;
         DS_HIP(hipMemsetAsync(index->order_bins.ptr, 0, 2 * kOrderStride * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(ds_query_order_count_kernel, dim3(blocks), dim3(kOrderThreads), 0, stream, d_q_rowptr, Q, chunk,
-                           index->order_bins.ptr);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_query_order_place_kernel, dim3(blocks), dim3(kOrderThreads), 0, stream, d_q_rowptr, Q, chunk,
-                           index->order_bins.ptr, index->take_order.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_query_order_count_kernel, dim3(blocks), dim3(kOrderThreads), 0, stream, d_q_rowptr, Q, chunk,
+                  index->order_bins.ptr);
+        DS_LAUNCH(ds_query_order_place_kernel, dim3(blocks), dim3(kOrderThreads), 0, stream, d_q_rowptr, Q, chunk,
+                  index->order_bins.ptr, index->take_order.ptr);
         args.take_order = index->take_order.ptr;
     }
     args.phase = nullptr;
@@ -2480,8 +2470,7 @@ int launch(ds_index *index, const int64_t *d_q_rowptr, const int32_t *d_q_cols, 
         args.take_order = nullptr;
         index->last_args.assign(reinterpret_cast<const unsigned char *>(&args), reinterpret_cast<const unsigned char *>(&args) + sizeof(args));
         index->resolve_ties = &resolve_ties;
-        hipLaunchKernelGGL(ds_jaccard_mark_rowscan_kernel, dim3(static_cast<unsigned>((Q + 255) / 256)), dim3(256), 0, stream, args);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_jaccard_mark_rowscan_kernel, dim3(static_cast<unsigned>((Q + 255) / 256)), dim3(256), 0, stream, args);
         DS_HIP(hipEventRecord(index->event_fast, stream));
         DS_HIP(hipEventRecord(index->event_dense, stream));
         return DS_OK;
@@ -2494,13 +2483,10 @@ int launch(ds_index *index, const int64_t *d_q_rowptr, const int32_t *d_q_cols, 
     index->resolve_ties = &resolve_ties;
     if (index->kernel_args.count == 0 && index->kernel_args.allocate(512) != DS_OK) return DS_E_HIP;
     DS_HIP(hipMemcpyAsync(index->kernel_args.ptr, &args, sizeof(args), hipMemcpyHostToDevice, stream));  // pageable source: staged before the call returns
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), kFastLdsBytes, stream, static_cast<const void *>(index->kernel_args.ptr));
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(kernel, dim3(grid), dim3(kThreads), kFastLdsBytes, stream, static_cast<const void *>(index->kernel_args.ptr));
     DS_HIP(hipEventRecord(index->event_fast, stream));
-    hipLaunchKernelGGL(ds_jaccard_repeats_kernel, dim3(static_cast<unsigned>((Q + 3) / 4)), dim3(256), 0, stream, args);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds_jaccard_dense_kernel, dim3(index->compute_units), dim3(kDenseThreads), kDenseLdsBytes, stream, args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_jaccard_repeats_kernel, dim3(static_cast<unsigned>((Q + 3) / 4)), dim3(256), 0, stream, args);
+    DS_LAUNCH(ds_jaccard_dense_kernel, dim3(index->compute_units), dim3(kDenseThreads), kDenseLdsBytes, stream, args);
     DS_HIP(hipEventRecord(index->event_dense, stream));
     return DS_OK;
 }
@@ -2565,8 +2551,7 @@ int collect(ds_index *index, hipStream_t stream, int64_t stats[32])
         bool unresolved = false;
         for (int32_t value : status) unresolved = unresolved || value == kQueryErrorTies;
         if (unresolved && index->resolve_ties != nullptr) {  // the literal kernel's buffer could not hold a query's near-ties
-            const int resolved = index->resolve_ties(index, stream, status);
-            if (resolved != DS_OK) return resolved;
+            DS_TRY(index->resolve_ties(index, stream, status));
             DS_HIP(hipMemcpy(status.data(), index->status.ptr, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             DS_HIP(hipMemcpy(control, index->control.ptr, sizeof(control), hipMemcpyDeviceToHost));
             if (stats) stats[1] = control[kCtlErrors];

@@ -10,11 +10,9 @@
 // neither class.  All of them are integer sums: the same for any schedule and from run to run.
 #pragma once
 
-#include "ds_common.h"
+#include "ds_launch.h"
 
 namespace ds {
-
-int train_check_free(int64_t bytes, const char *what);   // ds_train.hip
 
 constexpr uint32_t kMetricAuc = DS_METRIC_AUC, kMetricLogloss = DS_METRIC_LOGLOSS;
 constexpr int kMetricCounters = 6;

@@ -18,6 +18,7 @@
 // The log loss is one pass over the column's rows (ds_metric_logloss_kernel) with the same reduction.
 // Every sum is an integer sum and the sorted keys are a function of the keys alone: nothing depends on the schedule.
 
+#include "ds_launch.h"
 #include "ds_metrics.h"
 #include "ds_options.h"
 #include "ds_radix.h"
@@ -245,28 +246,23 @@ int metrics_enqueue(hipStream_t stream, int compute_units, uint32_t flags, const
                scratch.columns, (long long)scratch.n_keys);
     uint32_t *col_or = scratch.state.ptr, *col_and = col_or + scratch.columns;
     const unsigned columns = static_cast<unsigned>(n_columns);
-    hipLaunchKernelGGL(ds_metric_clear_kernel, dim3((columns + 63) / 64), dim3(64), 0, stream, d_active, n_columns, col_or,
-                       col_and, d_counters);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_metric_clear_kernel, dim3((columns + 63) / 64), dim3(64), 0, stream, d_active, n_columns, col_or,
+              col_and, d_counters);
     if (flags & kMetricAuc) {
         if (n_keys > 0) {   // no negatives anywhere: nothing to sort, and the search reads no key
-            hipLaunchKernelGGL(ds_metric_key_kernel, dim3(metric_grid(n_keys, compute_units, block_cap), columns),
-                               dim3(kMetricThreads), 0, stream, d_columns, d_active, n_keys, scratch.keys_a.ptr, col_or,
-                               col_and, d_counters);
-            DS_HIP(hipGetLastError());
-            if (int status = radix_sort_columns(stream, scratch.keys_a.ptr, scratch.keys_b.ptr, n_keys, n_columns, col_or,
-                                                col_and, scratch.table.ptr); status != DS_OK)
-                return status;
+            DS_LAUNCH(ds_metric_key_kernel, dim3(metric_grid(n_keys, compute_units, block_cap), columns),
+                      dim3(kMetricThreads), 0, stream, d_columns, d_active, n_keys, scratch.keys_a.ptr, col_or,
+                      col_and, d_counters);
+            DS_TRY(radix_sort_columns(stream, scratch.keys_a.ptr, scratch.keys_b.ptr, n_keys, n_columns, col_or,
+                                      col_and, scratch.table.ptr));
         }
-        hipLaunchKernelGGL(ds_metric_search_kernel, dim3(metric_grid(max_pos, compute_units, block_cap), columns),
-                           dim3(kMetricThreads), 0, stream, d_columns, d_active, n_keys, scratch.keys_a.ptr,
-                           scratch.keys_b.ptr, col_or, col_and, d_counters);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_metric_search_kernel, dim3(metric_grid(max_pos, compute_units, block_cap), columns),
+                  dim3(kMetricThreads), 0, stream, d_columns, d_active, n_keys, scratch.keys_a.ptr,
+                  scratch.keys_b.ptr, col_or, col_and, d_counters);
     }
     if (flags & kMetricLogloss) {
-        hipLaunchKernelGGL(ds_metric_logloss_kernel, dim3(metric_grid(max_rows, compute_units, block_cap), columns),
-                           dim3(kMetricThreads), 0, stream, d_columns, d_active, d_counters);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_metric_logloss_kernel, dim3(metric_grid(max_rows, compute_units, block_cap), columns),
+                  dim3(kMetricThreads), 0, stream, d_columns, d_active, d_counters);
     }
     return DS_OK;
 }
@@ -304,63 +300,55 @@ int device_of(const void *pointer, int *device)
 
 }  // namespace
 
-extern "C" {
-
-int ds_metrics_option(const char *name, int64_t value)
+static int auc_check_rows(const char *what, int64_t n)
 {
-    return ds::set_option("ds_metrics_option", ds::g_metrics_options, name, value);
+    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "%s: n = %lld rows out of range [1, 2^31)", what, (long long)n);
+    return DS_OK;
 }
 
-int ds_auc_device(const float *d_scores, const float *d_labels, int64_t n, int64_t out[5], void *stream)
+// The body of both twins.  scores_at and labels_at name pointers into HBM that are read once `scratch` is allocated here:
+// the caller's own arrays, or pieces that it has declared in `scratch`.
+static int auc_run(const char *what, ds::Scratch &scratch, int device, const float *const *scores_at,
+                   const float *const *labels_at, int64_t n, int64_t out[5], hipStream_t s)
 {
-    DS_REQUIRE(d_scores && d_labels && out, "ds_auc_device: null pointer");
-    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "ds_auc_device: n = %lld rows out of range [1, 2^31)", (long long)n);
-    int device = 0;
-    if (int status = device_of(d_scores, &device); status != DS_OK) return status;
     DS_HIP(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int units = ds::compute_units(device);
-    // the row lists, then (the negatives are counted by then) the sort buffers: both against the free HBM, the second
-    // for the worst case that every row is a negative
-    if (int status = ds::train_check_free(4 * n + ds::MetricScratch::bytes(n, 1), "ds_auc_device"); status != DS_OK)
-        return status;
-    ds::DeviceBuffer<int32_t> rows;
-    ds::DeviceBuffer<uint32_t> counts;
-    ds::DeviceBuffer<unsigned long long> counters;
-    ds::DeviceBuffer<ds::MetricColumn> columns;
-    int status = rows.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = counts.allocate(2);
-    if (status == DS_OK) status = counters.allocate(ds::kMetricCounters);
-    if (status == DS_OK) status = columns.allocate(1);
-    if (status != DS_OK) return status;
-    DS_HIP(hipMemsetAsync(counts.ptr, 0, counts.bytes(), s));
-    hipLaunchKernelGGL(ds::ds_metric_split_kernel, dim3(ds::metric_grid(n, units, 0)), dim3(ds::kMetricThreads), 0, s,
-                       d_labels, n, rows.ptr, counts.ptr);
-    DS_HIP(hipGetLastError());
+    int32_t *rows = nullptr;
+    uint32_t *counts = nullptr;
+    unsigned long long *counters = nullptr;
+    ds::MetricColumn *columns = nullptr;
+    scratch.add(&rows, static_cast<size_t>(n));
+    scratch.add(&counts, 2);
+    scratch.add(&counters, ds::kMetricCounters);
+    scratch.add(&columns, 1);
+    // the sort buffers follow once the negatives are counted: checked here for the worst case that every row is one
+    DS_TRY(scratch.allocate(what, ds::MetricScratch::bytes(n, 1)));
+    const float *d_scores = *scores_at, *d_labels = *labels_at;
+    DS_HIP(hipMemsetAsync(counts, 0, sizeof(uint32_t) * 2, s));
+    DS_LAUNCH(ds::ds_metric_split_kernel, dim3(ds::metric_grid(n, units, 0)), dim3(ds::kMetricThreads), 0, s,
+              d_labels, n, rows, counts);
     uint32_t host_counts[2] = {0u, 0u};
-    DS_HIP(hipMemcpyAsync(host_counts, counts.ptr, sizeof(host_counts), hipMemcpyDeviceToHost, s));
+    DS_HIP(hipMemcpyAsync(host_counts, counts, sizeof(host_counts), hipMemcpyDeviceToHost, s));
     DS_HIP(hipStreamSynchronize(s));   // the grids and the buffers of the sort depend on the number of negatives
     const int64_t n_neg = host_counts[0], n_pos = host_counts[1];
     if (n_neg + n_pos != n) {
-        ds::set_error("ds_auc_device: %lld + %lld rows listed of %lld", (long long)n_neg, (long long)n_pos, (long long)n);
+        ds::set_error("%s: %lld + %lld rows listed of %lld", what, (long long)n_neg, (long long)n_pos, (long long)n);
         return DS_E_HIP;
     }
-    ds::MetricScratch scratch;
-    if (status = scratch.allocate(n_neg, 1); status != DS_OK) return status;
-    const ds::MetricColumn column{d_scores, rows.ptr, rows.ptr + n_neg, static_cast<int32_t>(n_neg),
+    ds::MetricScratch sort_buffers;
+    DS_TRY(sort_buffers.allocate(n_neg, 1));
+    const ds::MetricColumn column{d_scores, rows, rows + n_neg, static_cast<int32_t>(n_neg),
                                   static_cast<int32_t>(n_pos), 0.f, 0, 1.0};
     // the descriptor and the counters travel on `s` like the kernels between them; `column` and `host` are read and
     // written until that stream is synchronised, so every path below synchronises it before it returns
     unsigned long long host[ds::kMetricCounters];
     auto enqueue = [&]() -> int {
-        DS_HIP(hipMemcpyAsync(columns.ptr, &column, sizeof(column), hipMemcpyHostToDevice, s));
-        if (int queued = ds::metrics_enqueue(s, units, ds::kMetricAuc, columns.ptr, nullptr, 1, n_neg, n_pos, n, scratch,
-                                             counters.ptr, 0); queued != DS_OK)
-            return queued;
-        DS_HIP(hipMemcpyAsync(host, counters.ptr, sizeof(host), hipMemcpyDeviceToHost, s));
+        DS_HIP(hipMemcpyAsync(columns, &column, sizeof(column), hipMemcpyHostToDevice, s));
+        DS_TRY(ds::metrics_enqueue(s, units, ds::kMetricAuc, columns, nullptr, 1, n_neg, n_pos, n, sort_buffers, counters, 0));
+        DS_HIP(hipMemcpyAsync(host, counters, sizeof(host), hipMemcpyDeviceToHost, s));
         return DS_OK;
     };
-    status = enqueue();
+    const int status = enqueue();
     const hipError_t synced = hipStreamSynchronize(s);
     if (status != DS_OK) return status;
     DS_HIP(synced);
@@ -371,17 +359,32 @@ int ds_auc_device(const float *d_scores, const float *d_labels, int64_t n, int64
     return DS_OK;
 }
 
+extern "C" {
+
+int ds_metrics_option(const char *name, int64_t value)
+{
+    return ds::set_option("ds_metrics_option", ds::g_metrics_options, name, value);
+}
+
+int ds_auc_device(const float *d_scores, const float *d_labels, int64_t n, int64_t out[5], void *stream)
+{
+    DS_REQUIRE(d_scores && d_labels && out, "ds_auc_device: null pointer");
+    DS_TRY(auc_check_rows("ds_auc_device", n));
+    int device = 0;
+    DS_TRY(device_of(d_scores, &device));
+    ds::Scratch scratch;
+    return auc_run("ds_auc_device", scratch, device, &d_scores, &d_labels, n, out, static_cast<hipStream_t>(stream));
+}
+
 int ds_auc(const float *scores, const float *labels, int64_t n, int64_t out[5], int device)
 {
     DS_REQUIRE(scores && labels && out, "ds_auc: null pointer");
-    DS_REQUIRE(n >= 1 && n <= INT32_MAX, "ds_auc: n = %lld rows out of range [1, 2^31)", (long long)n);
-    DS_HIP(hipSetDevice(device));
-    if (int status = ds::train_check_free(8 * n, "ds_auc"); status != DS_OK) return status;
-    ds::DeviceBuffer<float> d_scores, d_labels;
-    int status = d_scores.upload(scores, static_cast<size_t>(n));
-    if (status == DS_OK) status = d_labels.upload(labels, static_cast<size_t>(n));
-    if (status != DS_OK) return status;
-    return ds_auc_device(d_scores.ptr, d_labels.ptr, n, out, nullptr);
+    DS_TRY(auc_check_rows("ds_auc", n));
+    ds::Scratch scratch;
+    const float *d_scores = nullptr, *d_labels = nullptr;
+    scratch.stage(&d_scores, scores, static_cast<size_t>(n));
+    scratch.stage(&d_labels, labels, static_cast<size_t>(n));
+    return auc_run("ds_auc", scratch, device, &d_scores, &d_labels, n, out, nullptr);
 }
 
 int ds_weighted_logloss_device(const float *d_margins, const float *d_labels, int64_t n, double beta, int64_t out[2],
@@ -391,15 +394,14 @@ int ds_weighted_logloss_device(const float *d_margins, const float *d_labels, in
     DS_REQUIRE(n >= 1 && n <= INT32_MAX, "ds_weighted_logloss_device: n = %lld rows out of range [1, 2^31)", (long long)n);
     DS_REQUIRE(beta > 0 && beta < 1e30, "ds_weighted_logloss_device: beta = %g must be positive", beta);
     int device = 0;
-    if (int status = device_of(d_margins, &device); status != DS_OK) return status;
+    DS_TRY(device_of(d_margins, &device));
     DS_HIP(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     ds::DeviceBuffer<unsigned long long> sum;
-    if (int status = sum.allocate(1); status != DS_OK) return status;
+    DS_TRY(sum.allocate(1));
     DS_HIP(hipMemsetAsync(sum.ptr, 0, sum.bytes(), s));
-    hipLaunchKernelGGL(ds::ds_metric_logloss_rows_kernel, dim3(ds::metric_grid(n, ds::compute_units(device), 0)),
-                       dim3(ds::kMetricThreads), 0, s, d_margins, d_labels, n, beta, sum.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_metric_logloss_rows_kernel, dim3(ds::metric_grid(n, ds::compute_units(device), 0)),
+              dim3(ds::kMetricThreads), 0, s, d_margins, d_labels, n, beta, sum.ptr);
     unsigned long long host = 0ull;
     DS_HIP(hipMemcpyAsync(&host, sum.ptr, sizeof(host), hipMemcpyDeviceToHost, s));
     DS_HIP(hipStreamSynchronize(s));

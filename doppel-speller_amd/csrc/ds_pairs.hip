@@ -12,7 +12,7 @@
 // kernels: per-block counts, scan of the block counts, per-block scan + write) that emits the (query row, truth row)
 // index pairs ds_construct_features_indexed_device consumes -- the top-k rows never leave HBM.
 // ds_select_matches_device: one thread per remaining query over its k predictions.
-#include "ds_common.h"
+#include "ds_launch.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -112,14 +112,11 @@ int ds_remaining_pairs_device(const int32_t *d_best_row, const int32_t *d_rows, 
     DS_REQUIRE(n_queries * k < (int64_t(1) << 40), "ds_remaining_pairs_device: too many pairs");
     const int64_t n_blocks = (n_queries + ds::kPairBlock - 1) / ds::kPairBlock;
     int64_t *block_counts = d_counts + 2;
-    hipLaunchKernelGGL(ds::ds_pairs_count_kernel, dim3(static_cast<unsigned>(n_blocks)), dim3(ds::kPairBlock), 0, s,
-                       d_best_row, n_queries, block_counts);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_pairs_scan_kernel, dim3(1), dim3(1024), 0, s, block_counts, n_blocks, k, d_counts);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_pairs_write_kernel, dim3(static_cast<unsigned>(n_blocks)), dim3(ds::kPairBlock), 0, s,
-                       d_best_row, d_rows, n_queries, k, q_first, block_counts, d_pair_q, d_pair_t);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_pairs_count_kernel, dim3(static_cast<unsigned>(n_blocks)), dim3(ds::kPairBlock), 0, s,
+              d_best_row, n_queries, block_counts);
+    DS_LAUNCH(ds::ds_pairs_scan_kernel, dim3(1), dim3(1024), 0, s, block_counts, n_blocks, k, d_counts);
+    DS_LAUNCH(ds::ds_pairs_write_kernel, dim3(static_cast<unsigned>(n_blocks)), dim3(ds::kPairBlock), 0, s,
+              d_best_row, d_rows, n_queries, k, q_first, block_counts, d_pair_q, d_pair_t);
     return DS_OK;
 }
 
@@ -131,10 +128,9 @@ int ds_select_matches_device(const int32_t *d_pair_q, const int32_t *d_pair_t, c
     if (n_remaining == 0) return DS_OK;
     DS_REQUIRE(d_pair_q && d_pair_t && d_predictions && d_match_query && d_match_row,
                "ds_select_matches_device: null pointer");
-    hipLaunchKernelGGL(ds::ds_select_matches_kernel, dim3(static_cast<unsigned>((n_remaining + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_pair_q, d_pair_t, d_predictions, n_remaining, k, threshold,
-                       d_match_query, d_match_row);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_select_matches_kernel, dim3(static_cast<unsigned>((n_remaining + 255) / 256)), dim3(256), 0,
+              static_cast<hipStream_t>(stream), d_pair_q, d_pair_t, d_predictions, n_remaining, k, threshold,
+              d_match_query, d_match_row);
     return DS_OK;
 }
 

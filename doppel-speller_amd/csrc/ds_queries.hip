@@ -13,7 +13,7 @@
 // them, neighbours are compared to drop repeats and the dense column table (int32[37^3], -1 = not in the truth
 // vocabulary) gives the columns.  One lane adds the float64 chain in ascending n-gram order.  The counting instance
 // writes the row lengths and q_maxint, one workgroup scans the lengths into rowptr, the fill instance writes the columns.
-#include "ds_common.h"
+#include "ds_launch.h"
 #include "ds_wave.h"
 
 #include <algorithm>
@@ -325,55 +325,34 @@ int ds_prepare_titles(const uint8_t *chars, const int64_t *offsets, int64_t n, i
     DS_REQUIRE(device >= 0, "ds_prepare_titles: negative device");
     DS_HIP(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ds_titles *titles = new ds_titles();
+    std::unique_ptr<ds_titles> titles(new ds_titles());
     titles->device = device;
     titles->n = n;
     titles->stride = DS_MAX_CHARS;
     ds::DeviceBuffer<uint8_t> d_chars;
     ds::DeviceBuffer<int64_t> d_offsets;
     ds::DeviceBuffer<ds::PrepareReport> d_report;
-    int status = titles->enc.allocate(static_cast<size_t>(n) * DS_MAX_CHARS);
-    if (status == DS_OK) status = titles->len.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = d_chars.allocate(static_cast<size_t>(std::max<int64_t>(bytes, 1)));
-    if (status == DS_OK) status = d_offsets.allocate(static_cast<size_t>(n + 1));
-    if (status == DS_OK) status = d_report.allocate(1);
-    if (status != DS_OK) {
-        delete titles;
-        return status;
-    }
+    DS_TRY(titles->enc.allocate(static_cast<size_t>(n) * DS_MAX_CHARS));
+    DS_TRY(titles->len.allocate(static_cast<size_t>(n)));
+    DS_TRY(d_chars.allocate(static_cast<size_t>(std::max<int64_t>(bytes, 1))));
+    DS_TRY(d_offsets.allocate(static_cast<size_t>(n + 1)));
+    DS_TRY(d_report.allocate(1));
     ds::PrepareReport host{{0u, 0u, 0u, 0u}, ~0ull, ~0ull};
-    hipError_t hip = bytes ? hipMemcpyAsync(d_chars.ptr, chars, static_cast<size_t>(bytes), hipMemcpyHostToDevice, s)
-                           : hipSuccess;
-    if (hip == hipSuccess)
-        hip = hipMemcpyAsync(d_offsets.ptr, offsets, static_cast<size_t>(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    if (hip == hipSuccess) hip = hipMemcpyAsync(d_report.ptr, &host, sizeof(host), hipMemcpyHostToDevice, s);
-    if (hip == hipSuccess) {
-        hipLaunchKernelGGL(ds::ds_prepare_titles_kernel, dim3(static_cast<unsigned>(n)), dim3(ds::kQueryBlock), 0, s,
-                           d_chars.ptr, d_offsets.ptr, transform, titles->enc.ptr, titles->len.ptr, d_report.ptr);
-        hip = hipGetLastError();
-    }
-    if (hip == hipSuccess) hip = hipMemcpyAsync(&host, d_report.ptr, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (hip == hipSuccess) hip = hipStreamSynchronize(s);
-    if (hip != hipSuccess) {
-        delete titles;
-        return ds::hip_failed(hip, "ds_prepare_titles_kernel", __FILE__, __LINE__);
-    }
+    if (bytes) DS_HIP(hipMemcpyAsync(d_chars.ptr, chars, static_cast<size_t>(bytes), hipMemcpyHostToDevice, s));
+    DS_HIP(hipMemcpyAsync(d_offsets.ptr, offsets, static_cast<size_t>(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    DS_HIP(hipMemcpyAsync(d_report.ptr, &host, sizeof(host), hipMemcpyHostToDevice, s));
+    DS_LAUNCH(ds::ds_prepare_titles_kernel, dim3(static_cast<unsigned>(n)), dim3(ds::kQueryBlock), 0, s,
+              d_chars.ptr, d_offsets.ptr, transform, titles->enc.ptr, titles->len.ptr, d_report.ptr);
+    DS_HIP(hipMemcpyAsync(&host, d_report.ptr, sizeof(host), hipMemcpyDeviceToHost, s));
+    DS_HIP(hipStreamSynchronize(s));
     report[0] = static_cast<int64_t>(host.bad[0] | (static_cast<uint64_t>(host.bad[1]) << 32));
     report[1] = static_cast<int64_t>(host.bad[2] | (static_cast<uint64_t>(host.bad[3]) << 32));
     report[2] = host.first_long == ~0ull ? -1 : static_cast<int64_t>(host.first_long);
     report[3] = host.first_non_ascii == ~0ull ? -1 : static_cast<int64_t>(host.first_non_ascii);
-    if (report[3] >= 0) {
-        delete titles;
-        ds::set_error("ds_prepare_titles: title %lld is not ASCII (apply the Unicode step first)", (long long)report[3]);
-        return DS_E_ARG;
-    }
-    if (report[2] >= 0) {
-        delete titles;
-        ds::set_error("ds_prepare_titles: title %lld has %lld characters (stride %d)", (long long)report[2],
-                      (long long)(offsets[report[2] + 1] - offsets[report[2]]), DS_MAX_CHARS);
-        return DS_E_ARG;
-    }
-    *out = titles;
+    DS_REQUIRE(report[3] < 0, "ds_prepare_titles: title %lld is not ASCII (apply the Unicode step first)", (long long)report[3]);
+    DS_REQUIRE(report[2] < 0, "ds_prepare_titles: title %lld has %lld characters (stride %d)", (long long)report[2],
+               (long long)(offsets[report[2] + 1] - offsets[report[2]]), DS_MAX_CHARS);
+    *out = titles.release();
     return DS_OK;
 }
 
@@ -397,16 +376,13 @@ int ds_query_rows_device(const ds_query_space *space, const ds_titles *titles, i
         return DS_OK;
     }
     const dim3 grid(static_cast<unsigned>(n)), block(ds::kQueryBlock);
-    hipLaunchKernelGGL(ds::ds_query_rows_kernel<false>, grid, block, 0, s, titles->enc.ptr, titles->len.ptr, titles->stride,
-                       first, space->dense.ptr, space->idf32.ptr, space->idf64.ptr, space->max_idf,
-                       static_cast<int>(space->unknown_counts), d_rowptr, d_cols, d_maxint);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_query_rowptr_scan_kernel, dim3(1), dim3(ds::kRowptrScanThreads), 0, s, d_rowptr, n);
-    DS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ds::ds_query_rows_kernel<true>, grid, block, 0, s, titles->enc.ptr, titles->len.ptr, titles->stride,
-                       first, space->dense.ptr, space->idf32.ptr, space->idf64.ptr, space->max_idf,
-                       static_cast<int>(space->unknown_counts), d_rowptr, d_cols, d_maxint);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_query_rows_kernel<false>, grid, block, 0, s, titles->enc.ptr, titles->len.ptr, titles->stride,
+              first, space->dense.ptr, space->idf32.ptr, space->idf64.ptr, space->max_idf,
+              static_cast<int>(space->unknown_counts), d_rowptr, d_cols, d_maxint);
+    DS_LAUNCH(ds::ds_query_rowptr_scan_kernel, dim3(1), dim3(ds::kRowptrScanThreads), 0, s, d_rowptr, n);
+    DS_LAUNCH(ds::ds_query_rows_kernel<true>, grid, block, 0, s, titles->enc.ptr, titles->len.ptr, titles->stride,
+              first, space->dense.ptr, space->idf32.ptr, space->idf64.ptr, space->max_idf,
+              static_cast<int>(space->unknown_counts), d_rowptr, d_cols, d_maxint);
     return DS_OK;
 }
 

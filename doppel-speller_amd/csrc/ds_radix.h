@@ -20,7 +20,7 @@
 
 #include <algorithm>
 
-#include "ds_common.h"
+#include "ds_launch.h"
 #include "ds_wave.h"
 
 namespace ds {
@@ -118,15 +118,12 @@ static inline int radix_sort_columns(hipStream_t stream, uint32_t *keys_a, uint3
 {
     const int64_t tiles = radix_tiles(n);
     for (int32_t pass = 0; pass < 4; ++pass) {
-        hipLaunchKernelGGL(ds_cuts_count_kernel, dim3(static_cast<unsigned>(tiles), columns), dim3(kSortThreads), 0,
-                           stream, keys_a, keys_b, n, pass, col_or, col_and, table, tiles);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_cuts_scan_kernel, dim3(columns), dim3(kScanThreads), 0, stream, table, tiles, pass, col_or,
-                           col_and);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_cuts_scatter_kernel, dim3(static_cast<unsigned>(tiles), columns), dim3(kSortThreads), 0,
-                           stream, keys_a, keys_b, n, pass, col_or, col_and, table, tiles);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_cuts_count_kernel, dim3(static_cast<unsigned>(tiles), columns), dim3(kSortThreads), 0,
+                  stream, keys_a, keys_b, n, pass, col_or, col_and, table, tiles);
+        DS_LAUNCH(ds_cuts_scan_kernel, dim3(columns), dim3(kScanThreads), 0, stream, table, tiles, pass, col_or,
+                  col_and);
+        DS_LAUNCH(ds_cuts_scatter_kernel, dim3(static_cast<unsigned>(tiles), columns), dim3(kSortThreads), 0,
+                  stream, keys_a, keys_b, n, pass, col_or, col_and, table, tiles);
     }
     return DS_OK;
 }

@@ -20,6 +20,7 @@
 // Both write every one of the n slots of every query exactly once, from the same keys: the result is the same.
 #include <algorithm>
 
+#include "ds_launch.h"
 #include "ds_options.h"
 #include "ds_wave.h"
 
@@ -206,14 +207,13 @@ int ds_rank_matches_device(const int32_t *d_rows, const float *d_predictions, co
     const int64_t passes = (n_queries + ds::kRankWaves - 1) / ds::kRankWaves;
     const dim3 grid(ds::grid_cap(passes, ds::kRankMaxBlocks));
     if (k <= ds::g_rank_lds_keys.get())
-        hipLaunchKernelGGL(ds::ds_rank_lds_kernel, grid, dim3(ds::kRankThreads), 0, static_cast<hipStream_t>(stream), d_rows,
-                           d_predictions, d_ratios, d_exact_row, d_best_row, n_queries, k, n, n_truth, d_out_row,
-                           d_out_probability, d_out_ratio, d_out_stage);
+        DS_LAUNCH(ds::ds_rank_lds_kernel, grid, dim3(ds::kRankThreads), 0, static_cast<hipStream_t>(stream), d_rows,
+                  d_predictions, d_ratios, d_exact_row, d_best_row, n_queries, k, n, n_truth, d_out_row,
+                  d_out_probability, d_out_ratio, d_out_stage);
     else
-        hipLaunchKernelGGL(ds::ds_rank_select_kernel, grid, dim3(ds::kRankThreads), 0, static_cast<hipStream_t>(stream),
-                           d_rows, d_predictions, d_ratios, d_exact_row, d_best_row, n_queries, k, n, n_truth, d_out_row,
-                           d_out_probability, d_out_ratio, d_out_stage);
-    DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_rank_select_kernel, grid, dim3(ds::kRankThreads), 0, static_cast<hipStream_t>(stream),
+                  d_rows, d_predictions, d_ratios, d_exact_row, d_best_row, n_queries, k, n, n_truth, d_out_row,
+                  d_out_probability, d_out_ratio, d_out_stage);
     return DS_OK;
 }
 

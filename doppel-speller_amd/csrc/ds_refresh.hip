@@ -16,6 +16,7 @@
 // The rows are read where they lie, row-major: a walk touches one value per level, eight at the most, of a row of at
 // most 384 bytes, so staging whole rows in LDS (forest_stage_rows) would move more than the walk reads and would take
 // the LDS that the table of sums uses.
+#include "ds_launch.h"
 #include "ds_forest.h"
 #include "ds_train.h"
 
@@ -182,12 +183,10 @@ int refresh_check(const char *who, const RefreshCall &c)
     DS_REQUIRE(c.eta > 0 && c.eta < 1e30, "%s: eta = %g must be positive", who, c.eta);
     DS_REQUIRE(c.reg_lambda >= 0 && c.reg_lambda < 1e30, "%s: reg_lambda = %g must not be negative", who, c.reg_lambda);
     DS_REQUIRE(c.beta > 0 && c.beta < 1e30, "%s: beta = %g must be positive", who, c.beta);
-    int status = train_check_labels(who, "labels: ", c.labels, c.n);
-    if (status == DS_OK) status = train_check_labels(who, "eval_labels: ", c.eval_labels, c.n_eval);
-    if (status != DS_OK) return status;
+    DS_TRY(train_check_labels(who, "labels: ", c.labels, c.n));
+    DS_TRY(train_check_labels(who, "eval_labels: ", c.eval_labels, c.n_eval));
     if (c.weights != nullptr) {
-        status = train_check_weights(who, c.weights, c.n, c.beta);
-        if (status != DS_OK) return status;
+        DS_TRY(train_check_weights(who, c.weights, c.n, c.beta));
     } else {
         DS_REQUIRE(std::max(c.beta, 1.0) * static_cast<double>(c.n) <= 4294967296.0,
                    "%s: max(beta, 1) * n = %g exceeds 2^32 (the integer sums could overflow)", who,
@@ -211,60 +210,54 @@ int refresh_check_device(const char *who, const ds_forest *forest, const float *
     return DS_OK;
 }
 
-int64_t refresh_work_bytes(const RefreshCall &c)
-{
-    const int64_t n_nodes = c.forest->n_nodes, n_trees = c.forest->n_trees;
-    return 20 * n_nodes + 8 * (n_trees + 1) + c.n * (12 + (c.weights ? 4 : 0) + (c.margins ? 4 : 0)) + c.n_eval * 12 +
-           (c.trace ? 4 * n_trees * c.n : 0);
-}
-
-// The launches and the read-back; d_rows and d_eval lie in HBM, complete in `stream`'s order.
-int refresh_run(const char *who, const RefreshCall &c, const float *d_rows, const float *d_eval, hipStream_t stream)
+// The launches and the read-back.  rows_at and eval_at name pointers into HBM, read once `scratch` is allocated here:
+// the caller's own matrices, complete in `stream`'s order, or pieces that the caller has declared in `scratch`.
+int refresh_run(const char *who, const RefreshCall &c, Scratch &scratch, const float *const *rows_at,
+                const float *const *eval_at, hipStream_t stream)
 {
     const ds_forest *forest = c.forest;
     const int64_t n = c.n, n_eval = c.n_eval, n_nodes = forest->n_nodes;
     const int32_t n_trees = forest->n_trees, nf = forest->n_features;
     DS_HIP(hipSetDevice(forest->device));
-    int status = train_check_free(refresh_work_bytes(c), who);
-    if (status != DS_OK) return status;
     const int units = compute_units(forest->device);
-    DeviceBuffer<float> values, leafsum, eval_leafsum, d_labels, d_eval_labels, d_weights, d_margins, d_trace;
-    DeviceBuffer<int32_t> leaf_of, eval_leaf_of;
-    DeviceBuffer<unsigned long long> sums, errors;
-    const size_t counters = static_cast<size_t>(n_trees) + 1;
-    status = values.allocate(static_cast<size_t>(std::max<int64_t>(n_nodes, 1)));
-    if (status == DS_OK) status = sums.allocate(2 * static_cast<size_t>(std::max<int64_t>(n_nodes, 1)));
-    if (status == DS_OK) status = errors.allocate(counters);
-    if (status == DS_OK) status = leafsum.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = leaf_of.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = d_labels.upload(c.labels, static_cast<size_t>(n));
-    if (status == DS_OK && c.weights) status = d_weights.upload(c.weights, static_cast<size_t>(n));
-    if (status == DS_OK && c.margins) status = d_margins.allocate(static_cast<size_t>(n));
-    if (status == DS_OK && c.trace) status = d_trace.allocate(static_cast<size_t>(n) * n_trees);
-    if (status == DS_OK) status = eval_leafsum.allocate(static_cast<size_t>(n_eval));
-    if (status == DS_OK) status = eval_leaf_of.allocate(static_cast<size_t>(n_eval));
-    if (status == DS_OK) status = d_eval_labels.upload(c.eval_labels, static_cast<size_t>(n_eval));
-    if (status != DS_OK) return status;
+    float *values = nullptr, *leafsum = nullptr, *eval_leafsum = nullptr, *d_labels = nullptr, *d_eval_labels = nullptr,
+          *d_weights = nullptr, *d_margins = nullptr, *d_trace = nullptr;
+    int32_t *leaf_of = nullptr, *eval_leaf_of = nullptr;
+    unsigned long long *sums = nullptr, *errors = nullptr;
+    const size_t counters = static_cast<size_t>(n_trees) + 1, value_slots = static_cast<size_t>(std::max<int64_t>(n_nodes, 1));
+    scratch.add(&values, value_slots);
+    scratch.add(&sums, 2 * value_slots);
+    scratch.add(&errors, counters);
+    scratch.add(&leafsum, static_cast<size_t>(n));
+    scratch.add(&leaf_of, static_cast<size_t>(n));
+    scratch.stage(&d_labels, c.labels, static_cast<size_t>(n));
+    if (c.weights) scratch.stage(&d_weights, c.weights, static_cast<size_t>(n));
+    if (c.margins) scratch.add(&d_margins, static_cast<size_t>(n));
+    if (c.trace) scratch.add(&d_trace, static_cast<size_t>(n) * n_trees);
+    scratch.add(&eval_leafsum, static_cast<size_t>(n_eval));
+    scratch.add(&eval_leaf_of, static_cast<size_t>(n_eval));
+    scratch.stage(&d_eval_labels, c.eval_labels, static_cast<size_t>(n_eval));
+    DS_TRY(scratch.allocate(who));
+    const float *d_rows = *rows_at, *d_eval = *eval_at;
     if (n_nodes)
-        DS_HIP(hipMemcpyAsync(values.ptr, forest->threshold.ptr, sizeof(float) * n_nodes, hipMemcpyDeviceToDevice, stream));
-    DS_HIP(hipMemsetAsync(sums.ptr, 0, sums.bytes(), stream));
-    DS_HIP(hipMemsetAsync(errors.ptr, 0, errors.bytes(), stream));
+        DS_HIP(hipMemcpyAsync(values, forest->threshold.ptr, sizeof(float) * n_nodes, hipMemcpyDeviceToDevice, stream));
+    DS_HIP(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 2 * value_slots, stream));
+    DS_HIP(hipMemsetAsync(errors, 0, sizeof(unsigned long long) * counters, stream));
 
     const int64_t table = forest->refresh_lds_nodes.get();
     auto grid = [&](int64_t items) {   // the trainers' row grid and cap, and the forest's own cap
         return grid_cap(train_row_grid(units, items), forest->max_blocks.get());
     };
     if (n_eval > 0) {
-        hipLaunchKernelGGL(ds_refresh_initial_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, forest->view(),
-                           d_eval, d_eval_labels.ptr, n_eval, errors.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_refresh_initial_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, forest->view(),
+                  d_eval, d_eval_labels, n_eval, errors);
     }
     for (int32_t t = 0; t < n_trees; ++t) {
         const int64_t root = forest->h_offsets[t], tree_nodes = forest->h_offsets[t + 1] - root;
         RefreshArgs args{};
         args.nodes = forest->nodes.ptr;
-        args.values = values.ptr;
-        args.sums = sums.ptr;
+        args.values = values;
+        args.sums = sums;
         args.root = root;
         args.nf = nf;
         args.previous = t > 0;
@@ -272,61 +265,56 @@ int refresh_run(const char *who, const RefreshCall &c, const float *d_rows, cons
         args.beta = c.beta;
         if (n > 0) {
             args.rows = d_rows;
-            args.labels = d_labels.ptr;
-            args.weights = c.weights ? d_weights.ptr : nullptr;
-            args.leaf_of = leaf_of.ptr;
-            args.leafsum = leafsum.ptr;
-            args.trace = c.trace ? d_trace.ptr + static_cast<int64_t>(t) * n : nullptr;
+            args.labels = d_labels;
+            args.weights = c.weights ? d_weights : nullptr;
+            args.leaf_of = leaf_of;
+            args.leafsum = leafsum;
+            args.trace = c.trace ? d_trace + static_cast<int64_t>(t) * n : nullptr;
             args.n = n;
             args.lds_nodes = tree_nodes <= table ? static_cast<int32_t>(tree_nodes) : 0;
-            hipLaunchKernelGGL(ds_refresh_rows_kernel<true>, dim3(grid(n)), dim3(kRowThreads),
-                               sizeof(unsigned long long) * 2 * args.lds_nodes, stream, args);
-            DS_HIP(hipGetLastError());
+            DS_LAUNCH(ds_refresh_rows_kernel<true>, dim3(grid(n)), dim3(kRowThreads),
+                      sizeof(unsigned long long) * 2 * args.lds_nodes, stream, args);
             if (c.refresh_leaf) {
-                hipLaunchKernelGGL(ds_refresh_leaf_kernel, dim3(static_cast<unsigned>((tree_nodes + 63) / 64)), dim3(64), 0,
-                                   stream, forest->nodes.ptr, sums.ptr, values.ptr, root, static_cast<int32_t>(tree_nodes),
-                                   c.reg_lambda, c.eta);
-                DS_HIP(hipGetLastError());
+                DS_LAUNCH(ds_refresh_leaf_kernel, dim3(static_cast<unsigned>((tree_nodes + 63) / 64)), dim3(64), 0,
+                          stream, forest->nodes.ptr, sums, values, root, static_cast<int32_t>(tree_nodes),
+                          c.reg_lambda, c.eta);
             }
         }
         if (n_eval > 0) {
             args.rows = d_eval;
-            args.labels = d_eval_labels.ptr;
+            args.labels = d_eval_labels;
             args.weights = nullptr;
-            args.leaf_of = eval_leaf_of.ptr;
-            args.leafsum = eval_leafsum.ptr;
+            args.leaf_of = eval_leaf_of;
+            args.leafsum = eval_leafsum;
             args.trace = nullptr;
-            args.error = t > 0 ? errors.ptr + t : nullptr;
+            args.error = t > 0 ? errors + t : nullptr;
             args.n = n_eval;
             args.lds_nodes = 0;
-            hipLaunchKernelGGL(ds_refresh_rows_kernel<false>, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, args);
-            DS_HIP(hipGetLastError());
+            DS_LAUNCH(ds_refresh_rows_kernel<false>, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, args);
         }
     }
     if (n > 0 && c.margins != nullptr) {
-        hipLaunchKernelGGL(ds_refresh_tail_kernel, dim3(grid(n)), dim3(kRowThreads), 0, stream, values.ptr, leaf_of.ptr,
-                           leafsum.ptr, d_labels.ptr, d_margins.ptr, static_cast<unsigned long long *>(nullptr), n,
-                           static_cast<int32_t>(n_trees > 0), forest->base_margin);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_refresh_tail_kernel, dim3(grid(n)), dim3(kRowThreads), 0, stream, values, leaf_of,
+                  leafsum, d_labels, d_margins, static_cast<unsigned long long *>(nullptr), n,
+                  static_cast<int32_t>(n_trees > 0), forest->base_margin);
     }
     if (n_eval > 0 && n_trees > 0) {
-        hipLaunchKernelGGL(ds_refresh_tail_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, values.ptr,
-                           eval_leaf_of.ptr, eval_leafsum.ptr, d_eval_labels.ptr, static_cast<float *>(nullptr),
-                           errors.ptr + n_trees, n_eval, 1, forest->base_margin);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_refresh_tail_kernel, dim3(grid(n_eval)), dim3(kRowThreads), 0, stream, values,
+                  eval_leaf_of, eval_leafsum, d_eval_labels, static_cast<float *>(nullptr),
+                  errors + n_trees, n_eval, 1, forest->base_margin);
     }
     DS_HIP(hipStreamSynchronize(stream));
 
     if (n_nodes) {
-        DS_HIP(hipMemcpy(c.leaf_out, values.ptr, sizeof(float) * n_nodes, hipMemcpyDeviceToHost));
-        DS_HIP(hipMemcpy(c.node_sums, sums.ptr, sizeof(int64_t) * 2 * n_nodes, hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(c.leaf_out, values, sizeof(float) * n_nodes, hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(c.node_sums, sums, sizeof(int64_t) * 2 * n_nodes, hipMemcpyDeviceToHost));
     }
-    if (n > 0 && c.margins) DS_HIP(hipMemcpy(c.margins, d_margins.ptr, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (n > 0 && c.margins) DS_HIP(hipMemcpy(c.margins, d_margins, sizeof(float) * n, hipMemcpyDeviceToHost));
     if (n > 0 && c.trace && n_trees > 0)
-        DS_HIP(hipMemcpy(c.trace, d_trace.ptr, sizeof(float) * n * n_trees, hipMemcpyDeviceToHost));
+        DS_HIP(hipMemcpy(c.trace, d_trace, sizeof(float) * n * n_trees, hipMemcpyDeviceToHost));
     if (c.eval_errors != nullptr) {
         if (n_eval > 0) {
-            DS_HIP(hipMemcpy(c.eval_errors, errors.ptr, sizeof(int64_t) * counters, hipMemcpyDeviceToHost));
+            DS_HIP(hipMemcpy(c.eval_errors, errors, sizeof(int64_t) * counters, hipMemcpyDeviceToHost));
         } else {
             for (size_t i = 0; i < counters; ++i) c.eval_errors[i] = -1;
         }
@@ -365,11 +353,11 @@ int ds_forest_refresh_device(const ds_forest *forest, const float *d_features, i
     const ds::RefreshCall call{forest, d_features, labels, weights, d_eval_features, eval_labels, n, n_eval, eta,
                                reg_lambda, beta, refresh_leaf, leaf_out, node_sums, margins, eval_errors, empty_leaves,
                                trace};
-    int status = ds::refresh_check(who, call);
-    if (status == DS_OK) status = ds::refresh_check_device(who, forest, d_features, "d_features");
-    if (status == DS_OK) status = ds::refresh_check_device(who, forest, d_eval_features, "d_eval_features");
-    if (status != DS_OK) return status;
-    return ds::refresh_run(who, call, d_features, d_eval_features, static_cast<hipStream_t>(stream));
+    DS_TRY(ds::refresh_check(who, call));
+    DS_TRY(ds::refresh_check_device(who, forest, d_features, "d_features"));
+    DS_TRY(ds::refresh_check_device(who, forest, d_eval_features, "d_eval_features"));
+    ds::Scratch scratch;
+    return ds::refresh_run(who, call, scratch, &d_features, &d_eval_features, static_cast<hipStream_t>(stream));
 }
 
 int ds_forest_refresh(const ds_forest *forest, const float *features, int64_t n, const float *labels,
@@ -380,18 +368,13 @@ int ds_forest_refresh(const ds_forest *forest, const float *features, int64_t n,
     const char *who = "ds_forest_refresh";
     const ds::RefreshCall call{forest, features, labels, weights, eval_features, eval_labels, n, n_eval, eta, reg_lambda,
                                beta, refresh_leaf, leaf_out, node_sums, margins, eval_errors, empty_leaves, trace};
-    int status = ds::refresh_check(who, call);
-    if (status != DS_OK) return status;
-    DS_HIP(hipSetDevice(forest->device));
+    DS_TRY(ds::refresh_check(who, call));
     // every tree reads the matrices again: they are uploaded once, whole
-    const int64_t matrix_bytes = static_cast<int64_t>(sizeof(float)) * forest->n_features * (n + n_eval);
-    status = ds::train_check_free(matrix_bytes + ds::refresh_work_bytes(call), who);
-    if (status != DS_OK) return status;
-    ds::DeviceBuffer<float> d_rows, d_eval;
-    status = d_rows.upload(features, static_cast<size_t>(n) * forest->n_features);
-    if (status == DS_OK) status = d_eval.upload(eval_features, static_cast<size_t>(n_eval) * forest->n_features);
-    if (status != DS_OK) return status;
-    return ds::refresh_run(who, call, d_rows.ptr, d_eval.ptr, nullptr);
+    ds::Scratch scratch;
+    const float *d_rows = nullptr, *d_eval = nullptr;
+    scratch.stage(&d_rows, features, static_cast<size_t>(n) * forest->n_features);
+    scratch.stage(&d_eval, eval_features, static_cast<size_t>(n_eval) * forest->n_features);
+    return ds::refresh_run(who, call, scratch, &d_rows, &d_eval, nullptr);
 }
 
 }  // extern "C"

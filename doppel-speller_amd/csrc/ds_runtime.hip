@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "ds_common.h"
+#include "ds_launch.h"
 #include "ds_host.h"
 #include "ds_options.h"
 
@@ -226,6 +226,18 @@ int ds_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes)
 }
 
 }  // extern "C"
+
+int ds::check_free(int64_t bytes, const char *what, size_t *free_now)
+{
+    size_t free_bytes = 0, total_bytes = 0;
+    DS_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
+    if (free_now != nullptr) *free_now = free_bytes;
+    if (static_cast<size_t>(bytes) + (size_t(64) << 20) > free_bytes) {   // 64 MiB of head room for the kernels that follow
+        set_error("%s: needs %lld bytes of HBM, %zu are free", what, (long long)bytes, free_bytes);
+        return DS_E_HIP;
+    }
+    return DS_OK;
+}
 
 // ---- tiled index ---------------------------------------------------------------------------------------------------
 // Input: the V x N inverted index of match_maker.py:122-133 in CSR form.  Output (HBM): the truth rows are cut
@@ -579,8 +591,7 @@ int ds_index_create(const int64_t *rowptr, const int32_t *truth_idx, const float
     IndexImage image;
     const auto started = std::chrono::steady_clock::now();
     {
-        const int built = build_index_image(rowptr, truth_idx, idf32, sums32, V, N, N > 0 ? ds::choose_tile_rows(N) : 0, image);
-        if (built != DS_OK) return built;
+        DS_TRY(build_index_image(rowptr, truth_idx, idf32, sums32, V, N, N > 0 ? ds::choose_tile_rows(N) : 0, image));
     }
     const int64_t n_tiles = image.n_tiles, tile_rows = image.tile_rows, nnz = image.nnz;
     const uint64_t quads = image.quads;
@@ -591,7 +602,7 @@ int ds_index_create(const int64_t *rowptr, const int32_t *truth_idx, const float
     std::vector<float> &tile_sums_min = image.tile_sums_min;
     std::vector<int8_t> &sig_column = image.sig_column;
     DS_HIP(hipSetDevice(device));
-    ds_index *index = new ds_index();
+    std::unique_ptr<ds_index> index(new ds_index());
     index->device = device;
     index->compute_units = ds::compute_units(device);
     index->n_truth = N;
@@ -603,46 +614,37 @@ int ds_index_create(const int64_t *rowptr, const int32_t *truth_idx, const float
     index->sums_min = sums_min;
     index->literal_only = literal_only;
     index->rows_sorted = image.rows_sorted;
-    int status = index->col_ptr.upload(col_ptr.data(), col_ptr.size());
-    if (status == DS_OK) status = index->postings.upload(postings.data(), postings.size());
-    if (status == DS_OK && postings.empty()) status = index->postings.allocate(4);
-    if (status == DS_OK) status = index->posting_sums.upload(posting_sums.data(), posting_sums.size());
-    if (status == DS_OK && posting_sums.empty()) status = index->posting_sums.allocate(4);
-    if (status == DS_OK) status = index->idf32.upload(idf32, static_cast<size_t>(V));
-    if (status == DS_OK) {  // padded so that the dense scan may read eight rows at once near the end
+    DS_TRY(index->col_ptr.upload(col_ptr.data(), col_ptr.size()));
+    DS_TRY(index->postings.upload(postings.data(), postings.size()));
+    if (postings.empty()) DS_TRY(index->postings.allocate(4));
+    DS_TRY(index->posting_sums.upload(posting_sums.data(), posting_sums.size()));
+    if (posting_sums.empty()) DS_TRY(index->posting_sums.allocate(4));
+    DS_TRY(index->idf32.upload(idf32, static_cast<size_t>(V)));
+    {  // padded so that the dense scan may read eight rows at once near the end
         std::vector<float> padded(static_cast<size_t>(N) + 8, 0.f);
         std::memcpy(padded.data(), image.sums.data(), sizeof(float) * static_cast<size_t>(N));
-        status = index->sums32.upload(padded.data(), padded.size());
+        DS_TRY(index->sums32.upload(padded.data(), padded.size()));
     }
-    if (status == DS_OK) status = index->tile_sums_min.upload(tile_sums_min.data(), tile_sums_min.size());
-    if (status == DS_OK) status = index->tile_sums_max.upload(image.tile_sums_max.data(), image.tile_sums_max.size());
-    if (status == DS_OK) status = index->signature.upload(records.data(), records.size());
-    if (status == DS_OK) status = index->sig_column.upload(sig_column.data(), sig_column.size());
+    DS_TRY(index->tile_sums_min.upload(tile_sums_min.data(), tile_sums_min.size()));
+    DS_TRY(index->tile_sums_max.upload(image.tile_sums_max.data(), image.tile_sums_max.size()));
+    DS_TRY(index->signature.upload(records.data(), records.size()));
+    DS_TRY(index->sig_column.upload(sig_column.data(), sig_column.size()));
     index->forward_wide_start = image.wide_start;
     index->forward_wide_cols = image.wide_cols;
-    if (status == DS_OK)
-        status = image.wide_start ? index->row_start.upload(reinterpret_cast<const unsigned char *>(image.row_start64.data()), image.row_start64.size() * 8)
-                                  : index->row_start.upload(reinterpret_cast<const unsigned char *>(image.row_start32.data()), image.row_start32.size() * 4);
-    if (status == DS_OK)
-        status = image.wide_cols ? index->row_cols.upload(reinterpret_cast<const unsigned char *>(image.row_cols32.data()), image.row_cols32.size() * 4)
-                                 : index->row_cols.upload(reinterpret_cast<const unsigned char *>(image.row_cols16.data()), image.row_cols16.size() * 2);
-    if (status == DS_OK && index->row_cols.count == 0) status = index->row_cols.allocate(4);
-    if (status == DS_OK) status = index->control.allocate(ds::kControlWords);
-    if (status == DS_OK && (hipStreamCreate(&index->stream) != hipSuccess ||
-                            hipEventCreate(&index->event_begin) != hipSuccess ||
-                            hipEventCreate(&index->event_fast) != hipSuccess ||
-                            hipEventCreate(&index->event_dense) != hipSuccess)) {
-        ds::set_error("ds_index_create: hipStreamCreate / hipEventCreate failed");
-        status = DS_E_HIP;
-    }
-    if (status != DS_OK) {
-        delete index;
-        return status;
-    }
+    DS_TRY(image.wide_start ? index->row_start.upload(reinterpret_cast<const unsigned char *>(image.row_start64.data()), image.row_start64.size() * 8)
+                            : index->row_start.upload(reinterpret_cast<const unsigned char *>(image.row_start32.data()), image.row_start32.size() * 4));
+    DS_TRY(image.wide_cols ? index->row_cols.upload(reinterpret_cast<const unsigned char *>(image.row_cols32.data()), image.row_cols32.size() * 4)
+                           : index->row_cols.upload(reinterpret_cast<const unsigned char *>(image.row_cols16.data()), image.row_cols16.size() * 2));
+    if (index->row_cols.count == 0) DS_TRY(index->row_cols.allocate(4));
+    DS_TRY(index->control.allocate(ds::kControlWords));
+    DS_HIP(hipStreamCreate(&index->stream));
+    DS_HIP(hipEventCreate(&index->event_begin));
+    DS_HIP(hipEventCreate(&index->event_fast));
+    DS_HIP(hipEventCreate(&index->event_dense));
     if (getenv("DS_BUILD_LOG") != nullptr)
         fprintf(stderr, "ds_index_create: %-28s %7.3f s (host build + upload, %d threads)\n", "total",
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count(), ds::host_threads());
-    *out = index;
+    *out = index.release();
     return DS_OK;
 }
 
@@ -654,8 +656,7 @@ int ds_index_image_digest(const int64_t *rowptr, const int32_t *truth_idx, const
 {
     DS_REQUIRE(digest != nullptr, "ds_index_image_digest: null digest");
     IndexImage image;
-    const int built = build_index_image(rowptr, truth_idx, idf32, sums32, V, N, tile_rows, image);
-    if (built != DS_OK) return built;
+    DS_TRY(build_index_image(rowptr, truth_idx, idf32, sums32, V, N, tile_rows, image));
     auto fnv = [](const void *data, size_t bytes) {
         const uint8_t *at = static_cast<const uint8_t *>(data);
         uint64_t h = 0xcbf29ce484222325ull;

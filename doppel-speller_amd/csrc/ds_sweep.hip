@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ds_launch.h"
 #include "ds_bootstrap_draw.h"
 #include "ds_options.h"
 #include "ds_wave.h"
@@ -418,11 +419,8 @@ static int sweep_boot_tile(int32_t T, int32_t U)
 template <bool kUnits>
 static int sweep_boot_launch(const SweepBootArgs &args, unsigned grid, size_t lds)
 {
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_sweep_bootstrap_kernel<kUnits>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL((ds_sweep_bootstrap_kernel<kUnits>), dim3(grid), dim3(kSweepBootThreads), lds, nullptr, args);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::allow_dynamic_lds(ds_sweep_bootstrap_kernel<kUnits>, lds));
+    DS_LAUNCH((ds_sweep_bootstrap_kernel<kUnits>), dim3(grid), dim3(kSweepBootThreads), lds, nullptr, args);
     return DS_OK;
 }
 
@@ -475,9 +473,7 @@ int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const u
                               int32_t U, int64_t *d_counts, void *stream)
 {
     hipStream_t queue = static_cast<hipStream_t>(stream);
-    if (int status = ds::sweep_check("ds_threshold_sweep_device", n_queries, k, d_lev, T, d_prob, U, d_counts, queue);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::sweep_check("ds_threshold_sweep_device", n_queries, k, d_lev, T, d_prob, U, d_counts, queue));
     if (n_queries == 0) return DS_OK;
     DS_REQUIRE(d_rows && d_d && d_r && d_s && d_predictions && d_exact && d_actual_row,
                "ds_threshold_sweep_device: null pointer");
@@ -489,9 +485,8 @@ int ds_threshold_sweep_device(const int32_t *d_rows, const uint8_t *d_d, const u
     const int per_t_bytes = (4 + 3 * (U + 1)) * static_cast<int>(sizeof(uint32_t));
     args.tile_t = std::max(1, std::min({static_cast<int>(T), 64, ds::kSweepLdsBytes / per_t_bytes}));
     const dim3 grid(ds::sweep_query_groups(n_queries), static_cast<unsigned>((T + args.tile_t - 1) / args.tile_t));
-    hipLaunchKernelGGL(ds::ds_threshold_sweep_kernel, grid, dim3(ds::kSweepThreads),
-                       static_cast<size_t>(args.tile_t) * per_t_bytes, queue, args);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_threshold_sweep_kernel, grid, dim3(ds::kSweepThreads),
+              static_cast<size_t>(args.tile_t) * per_t_bytes, queue, args);
     return DS_OK;
 }
 
@@ -500,9 +495,7 @@ int ds_sweep_records_device(const int32_t *d_rows, const uint8_t *d_d, const uin
                             int64_t n_queries, int32_t k, const int32_t *d_lev, int32_t T, const float *d_prob, int32_t U,
                             uint16_t *d_records)
 {
-    if (int status = ds::sweep_check("ds_sweep_records_device", n_queries, k, d_lev, T, d_prob, U, d_records, nullptr);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::sweep_check("ds_sweep_records_device", n_queries, k, d_lev, T, d_prob, U, d_records, nullptr));
     if (n_queries == 0) return DS_OK;
     DS_REQUIRE(d_rows && d_d && d_r && d_s && d_predictions && d_exact && d_actual_row,
                "ds_sweep_records_device: null pointer");
@@ -511,8 +504,7 @@ int ds_sweep_records_device(const int32_t *d_rows, const uint8_t *d_d, const uin
     args.exact = d_exact; args.actual = d_actual_row; args.lev = d_lev; args.prob = d_prob;
     args.n_queries = n_queries; args.k = k; args.T = T; args.U = U; args.tile_t = 64;
     const dim3 grid(ds::sweep_query_groups(n_queries), static_cast<unsigned>((T + 63) / 64));
-    hipLaunchKernelGGL(ds::ds_sweep_records_kernel, grid, dim3(ds::kSweepThreads), 0, nullptr, args, d_records);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_sweep_records_kernel, grid, dim3(ds::kSweepThreads), 0, nullptr, args, d_records);
     return DS_OK;
 }
 
@@ -542,25 +534,22 @@ int ds_sweep_bootstrap_device(const uint16_t *d_records, int64_t n, int32_t T, i
     ds::DeviceBuffer<unsigned long long> errors;
     ds::DeviceBuffer<uint32_t> sizes, cursor;
     ds::DeviceBuffer<int32_t> offsets, members;
-    if (int status = errors.allocate(3); status != DS_OK) return status;
+    DS_TRY(errors.allocate(3));
     DS_HIP(hipMemsetAsync(errors.ptr, 0, errors.bytes(), nullptr));
     if (units) {
-        int status = sizes.allocate(static_cast<size_t>(n_units));
-        if (status == DS_OK) status = cursor.allocate(static_cast<size_t>(n_units));
-        if (status == DS_OK) status = offsets.allocate(static_cast<size_t>(n_units) + 1);
-        if (status == DS_OK) status = members.allocate(static_cast<size_t>(n));
-        if (status != DS_OK) return status;
+        DS_TRY(sizes.allocate(static_cast<size_t>(n_units)));
+        DS_TRY(cursor.allocate(static_cast<size_t>(n_units)));
+        DS_TRY(offsets.allocate(static_cast<size_t>(n_units) + 1));
+        DS_TRY(members.allocate(static_cast<size_t>(n)));
         DS_HIP(hipMemsetAsync(sizes.ptr, 0, sizes.bytes(), nullptr));
     }
     const int64_t cap = ds::g_sweep_boot_max_blocks.get();
     const dim3 rows(ds::grid_cap((n + ds::kSweepBootRowThreads - 1) / ds::kSweepBootRowThreads, cap));
-    hipLaunchKernelGGL(ds::ds_sweep_bootstrap_check_kernel, rows, dim3(ds::kSweepBootRowThreads), 0, nullptr, d_records,
-                       d_unit, n, T, U, n_units, sizes.ptr, errors.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_sweep_bootstrap_check_kernel, rows, dim3(ds::kSweepBootRowThreads), 0, nullptr, d_records,
+              d_unit, n, T, U, n_units, sizes.ptr, errors.ptr);
     if (units) {   // the scan reads sizes of valid units only; its offsets are used only when the check has passed
-        hipLaunchKernelGGL(ds::ds_sweep_bootstrap_scan_kernel, dim3(1), dim3(ds::kSweepBootScanThreads), 0, nullptr,
-                           sizes.ptr, n_units, offsets.ptr, cursor.ptr, errors.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_sweep_bootstrap_scan_kernel, dim3(1), dim3(ds::kSweepBootScanThreads), 0, nullptr,
+                  sizes.ptr, n_units, offsets.ptr, cursor.ptr, errors.ptr);
     }
     unsigned long long found[3] = {0, 0, 0};
     DS_HIP(hipMemcpyAsync(found, errors.ptr, sizeof(found), hipMemcpyDeviceToHost, nullptr));
@@ -573,9 +562,8 @@ int ds_sweep_bootstrap_device(const uint16_t *d_records, int64_t n, int32_t T, i
                "%s: %lld units x %llu titles in the largest unit is 2^32 or more, what one replicate may add", what,
                (long long)n_units, largest);
     if (units) {
-        hipLaunchKernelGGL(ds::ds_sweep_bootstrap_fill_kernel, rows, dim3(ds::kSweepBootRowThreads), 0, nullptr, d_unit, n,
-                           cursor.ptr, members.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_sweep_bootstrap_fill_kernel, rows, dim3(ds::kSweepBootRowThreads), 0, nullptr, d_unit, n,
+                  cursor.ptr, members.ptr);
     }
     ds::SweepBootArgs args{};
     args.records = d_records;
@@ -594,8 +582,7 @@ int ds_sweep_bootstrap_device(const uint16_t *d_records, int64_t n, int32_t T, i
     args.n_groups = static_cast<int32_t>((replicates + per_group - 1) / per_group);
     const unsigned grid = ds::grid_cap(args.n_groups, cap);
     const size_t lds = static_cast<size_t>(ds::kSweepBootWaves) * (4 + 3 * U) * args.tile_t * sizeof(uint32_t);
-    const int status = units ? ds::sweep_boot_launch<true>(args, grid, lds) : ds::sweep_boot_launch<false>(args, grid, lds);
-    if (status != DS_OK) return status;
+    DS_TRY(units ? ds::sweep_boot_launch<true>(args, grid, lds) : ds::sweep_boot_launch<false>(args, grid, lds));
     if (units) DS_HIP(hipStreamSynchronize(nullptr));   // the member lists are freed on return
     return DS_OK;
 }

@@ -6,7 +6,7 @@
 // both trainers.  The single trainer is a view of one model with nothing held out and no fold array.
 #pragma once
 
-#include "ds_common.h"
+#include "ds_launch.h"
 #include "ds_forest.h"
 #include "ds_options.h"
 
@@ -134,8 +134,6 @@ inline int64_t candidate_entries(int32_t depth, int32_t nf) { return (int64_t(1)
 // returns.
 int train_bin_matrix(hipStream_t stream, int compute_units, const float *rows, bool in_hbm, int64_t n, int32_t nf,
                      const float *d_cuts, const int32_t *d_cut_offsets, DeviceBuffer<uint8_t> &out);
-// DS_E_HIP with both numbers in the message when `bytes` (+ 64 MiB of head room) are not free on the current device
-int train_check_free(int64_t bytes, const char *what);
 // The checks that every create entry (`who`) makes.  train_check_params names the batch's model, model < 0: no model;
 // max_depth is checked by the entry, whose argument it is (an integer in one, a double of the params array in the other).
 int train_check_shape(const char *who, int64_t n, int32_t n_features);

@@ -20,6 +20,7 @@
 // Continuing from a model (ds_trainer_seed, DESIGN.md section 9 "Continuing from a model"): before the first round
 // ds_train_seed_kernel sets leafsum to a forest's leaf sums of the RAW rows, and the trees count on from the forest's.
 
+#include "ds_launch.h"
 #include "ds_forest.h"
 #include "ds_metrics.h"
 #include "ds_train.h"
@@ -270,26 +271,13 @@ int train_bin_matrix(hipStream_t stream, int compute_units, const float *rows, b
                      const float *d_cuts, const int32_t *d_cut_offsets, DeviceBuffer<uint8_t> &out)
 {
     DeviceBuffer<float> staged;
-    int status = in_hbm ? DS_OK : staged.upload(rows, static_cast<size_t>(n) * nf);
-    if (status == DS_OK) status = out.allocate(static_cast<size_t>(n) * nf);
-    if (status != DS_OK) return status;
+    DS_TRY(in_hbm ? DS_OK : staged.upload(rows, static_cast<size_t>(n) * nf));
+    DS_TRY(out.allocate(static_cast<size_t>(n) * nf));
     const int64_t tiles = (n + kBinTileRows - 1) / kBinTileRows;
     const int grid = static_cast<int>(std::min<int64_t>(tiles, int64_t(compute_units) * 4));
-    hipLaunchKernelGGL(ds_train_bin_kernel, dim3(grid), dim3(kRowThreads), 0, stream, in_hbm ? rows : staged.ptr, n, nf,
-                       d_cuts, d_cut_offsets, out.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_train_bin_kernel, dim3(grid), dim3(kRowThreads), 0, stream, in_hbm ? rows : staged.ptr, n, nf,
+              d_cuts, d_cut_offsets, out.ptr);
     DS_HIP(hipStreamSynchronize(stream));   // `staged` is freed on return; the caller's matrix is no longer read
-    return DS_OK;
-}
-
-int train_check_free(int64_t bytes, const char *what)
-{
-    size_t free_bytes = 0, total_bytes = 0;
-    DS_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
-    if (static_cast<size_t>(bytes) + (size_t(64) << 20) > free_bytes) {   // 64 MiB of head room, as ds_exact
-        set_error("%s: needs %lld bytes of HBM, %zu are free", what, (long long)bytes, free_bytes);
-        return DS_E_HIP;
-    }
     return DS_OK;
 }
 
@@ -426,20 +414,17 @@ int train_seed_enqueue(hipStream_t stream, int compute_units, const ds_forest *f
     const int32_t nf = forest->n_features;
     const int64_t chunk_rows = in_hbm ? n : std::min<int64_t>(n, std::max<int64_t>(1, kSeedChunkBytes / (4 * int64_t(nf))));
     if (!in_hbm) {
-        if (int status = staged.allocate(static_cast<size_t>(chunk_rows) * nf); status != DS_OK) return status;
+        DS_TRY(staged.allocate(static_cast<size_t>(chunk_rows) * nf));
     }
     const size_t lds = static_cast<size_t>(kRowThreads) * (nf | 1) * sizeof(float);
-    if (lds > 48 * 1024)
-        DS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ds_train_seed_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    DS_TRY(ds::allow_dynamic_lds(ds_train_seed_kernel, lds));
     for (int64_t first = 0; first < n; first += chunk_rows) {
         const int64_t here = std::min(chunk_rows, n - first);
         if (!in_hbm)   // after the kernel of the chunk before, in stream order
             DS_HIP(hipMemcpyAsync(staged.ptr, rows + first * nf, sizeof(float) * here * nf, hipMemcpyHostToDevice, stream));
         const SeedArgs args{forest->view(), in_hbm ? rows : staged.ptr, leafsum + first, here, stride, n_models};
-        hipLaunchKernelGGL(ds_train_seed_kernel, dim3(train_row_grid(compute_units, here)), dim3(kRowThreads), lds,
-                           stream, args);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_train_seed_kernel, dim3(train_row_grid(compute_units, here)), dim3(kRowThreads), lds,
+                  stream, args);
     }
     return DS_OK;
 }
@@ -455,15 +440,12 @@ int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingVie
 {
     const unsigned models = static_cast<unsigned>(n_active);
     const dim3 rows(train_row_grid(compute_units, v.n), models);
-    hipLaunchKernelGGL(ds_train_clear_kernel, dim3(train_row_grid(compute_units, v.hist_stride / 2), models),
-                       dim3(kRowThreads), 0, stream, v);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds_train_clear_kernel, dim3(train_row_grid(compute_units, v.hist_stride / 2), models),
+              dim3(kRowThreads), 0, stream, v);
     if (kSampled) {   // the feature sets of this tree's levels, before the gradients of the rows drawn for it
-        hipLaunchKernelGGL(ds_train_feature_mask_kernel, dim3(models), dim3(kMaskThreads), 0, stream, v, s);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds_train_feature_mask_kernel, dim3(models), dim3(kMaskThreads), 0, stream, v, s);
     }
-    hipLaunchKernelGGL((ds_train_gradient_kernel<kFolds, kSampled>), rows, dim3(kRowThreads), 0, stream, v, s);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH((ds_train_gradient_kernel<kFolds, kSampled>), rows, dim3(kRowThreads), 0, stream, v, s);
     for (int32_t level = 0; level < depth; ++level) {
         const int32_t n_built = level == 0 ? 1 : 1 << (level - 1);
         const int32_t nodes_per_group = std::min(n_built, kHistSlots);
@@ -475,18 +457,14 @@ int enqueue_round(hipStream_t stream, const TrainView &v, const TrainSamplingVie
         // the flush (<= 8192 global adds per workgroup) stays a small part
         const unsigned chunks = grid_cap(std::min<int64_t>((v.n + 2047) / 2048, (int64_t(compute_units) * 4 + groups - 1) / groups),
                                          g_train_max_blocks.get());
-        hipLaunchKernelGGL((ds_train_histogram_kernel<kFolds, kSampled>),
-                           dim3(chunks, feature_groups * node_groups, models), dim3(kHistThreads),
-                           0, stream, v, level, n_built, nodes_per_group, features_per_group, feature_groups);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL((ds_train_split_feature_kernel<kSampled, kMonotone>), dim3(1u << level, v.nf, models),
-                           dim3(256), 0, stream, v, s, level);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_train_split_kernel<kMonotone>, dim3(((1u << level) + 63) / 64, models), dim3(64), 0,
-                           stream, v, level);
-        DS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ds_train_partition_kernel, rows, dim3(kRowThreads), 0, stream, v, level);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH((ds_train_histogram_kernel<kFolds, kSampled>),
+                  dim3(chunks, feature_groups * node_groups, models), dim3(kHistThreads),
+                  0, stream, v, level, n_built, nodes_per_group, features_per_group, feature_groups);
+        DS_LAUNCH((ds_train_split_feature_kernel<kSampled, kMonotone>), dim3(1u << level, v.nf, models),
+                  dim3(256), 0, stream, v, s, level);
+        DS_LAUNCH(ds_train_split_kernel<kMonotone>, dim3(((1u << level) + 63) / 64, models), dim3(64), 0,
+                  stream, v, level);
+        DS_LAUNCH(ds_train_partition_kernel, rows, dim3(kRowThreads), 0, stream, v, level);
     }
     return DS_OK;
 }
@@ -586,7 +564,7 @@ int bin_matrix(ds_trainer *t, const float *rows, bool in_hbm, int64_t n, ds::Dev
     return ds::train_bin_matrix(t->stream, t->compute_units, rows, in_hbm, n, t->nf, t->cuts.ptr, t->cut_offsets.ptr, out);
 }
 
-int check_free(int64_t bytes, const char *what) { return ds::train_check_free(bytes, what); }
+using ds::check_free;
 
 // ds_trainer_create (`who`, features on the host) and ds_trainer_create_device (features in HBM)
 int create_trainer(const char *who, const float *features, bool in_hbm, int64_t n, int32_t n_features, const float *cuts,
@@ -596,53 +574,46 @@ int create_trainer(const char *who, const float *features, bool in_hbm, int64_t 
     DS_REQUIRE(out != nullptr, "%s: out is null", who);
     *out = nullptr;
     DS_REQUIRE(features && cuts && cut_offsets, "%s: null input", who);
-    if (int status = ds::train_check_shape(who, n, n_features); status != DS_OK) return status;
+    DS_TRY(ds::train_check_shape(who, n, n_features));
     DS_REQUIRE(max_depth >= 1 && max_depth <= ds::kTrainMaxDepth, "%s: max_depth = %d out of range [1, %d]", who,
                max_depth, ds::kTrainMaxDepth);
-    if (int status = ds::train_check_params(who, -1, eta, min_child_weight, reg_lambda, beta); status != DS_OK)
-        return status;
-    if (int status = ds::train_check_cuts(who, n_features, cuts, cut_offsets); status != DS_OK) return status;
+    DS_TRY(ds::train_check_params(who, -1, eta, min_child_weight, reg_lambda, beta));
+    DS_TRY(ds::train_check_cuts(who, n_features, cuts, cut_offsets));
     const int64_t hist_bytes = ds::hist_entries(max_depth, n_features) * 8;
     // bins (+ the staged rows of a host matrix), per-row state, histograms
     const int64_t bytes = n * n_features * (in_hbm ? 1 : 5) + n * 36 + hist_bytes;
     DS_HIP(hipSetDevice(device));
-    if (int status = check_free(bytes, who); status != DS_OK) return status;
-    ds_trainer *t = new ds_trainer();
+    DS_TRY(check_free(bytes, who));
+    std::unique_ptr<ds_trainer> owner(new ds_trainer());
+    ds_trainer *t = owner.get();
     t->device = device;
     t->n = n;
     t->nf = n_features;
     t->params = ds::TrainParams{max_depth, eta, min_child_weight, reg_lambda, beta};
     t->host_offsets.assign(cut_offsets, cut_offsets + n_features + 1);
-    int status = ds::train_create_setup(who, device, n_features, cuts, cut_offsets, &t->stream, t->cuts, t->cut_offsets,
-                                        &t->compute_units);
-    if (status == DS_OK) status = bin_matrix(t, features, in_hbm, n, t->bins);
-    if (status == DS_OK) status = t->labels.allocate(n);
-    if (status == DS_OK) status = t->leafsum.allocate(n);
-    if (status == DS_OK) status = t->probabilities.allocate(n);
-    if (status == DS_OK) status = t->node_of.allocate(n);
-    if (status == DS_OK) status = t->gh.allocate(2 * n);
-    if (status == DS_OK) status = t->hist.allocate(static_cast<size_t>(hist_bytes / 8));
-    if (status == DS_OK) status = t->counts.allocate(heap_nodes(max_depth));
-    if (status == DS_OK) status = t->nodes.allocate(heap_nodes(max_depth));
-    if (status == DS_OK) status = t->candidates.allocate(static_cast<size_t>(ds::candidate_entries(max_depth, n_features)));
-    if (status == DS_OK) status = t->error.allocate(1);
-    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&t->pinned_nodes),
-                                         sizeof(ds::Node) * heap_nodes(max_depth)) != hipSuccess) status = DS_E_HIP;
-    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&t->pinned_error), sizeof(unsigned long long)) !=
-                               hipSuccess) status = DS_E_HIP;
-    if (status == DS_OK && hipMemsetAsync(t->leafsum.ptr, 0, sizeof(float) * n, t->stream) != hipSuccess)
-        status = DS_E_HIP;
-    if (status == DS_OK && hipStreamSynchronize(t->stream) != hipSuccess) status = DS_E_HIP;
-    if (status != DS_OK) {
-        delete t;
-        return status;
-    }
+    DS_TRY(ds::train_create_setup(who, device, n_features, cuts, cut_offsets, &t->stream, t->cuts, t->cut_offsets,
+                                  &t->compute_units));
+    DS_TRY(bin_matrix(t, features, in_hbm, n, t->bins));
+    DS_TRY(t->labels.allocate(n));
+    DS_TRY(t->leafsum.allocate(n));
+    DS_TRY(t->probabilities.allocate(n));
+    DS_TRY(t->node_of.allocate(n));
+    DS_TRY(t->gh.allocate(2 * n));
+    DS_TRY(t->hist.allocate(static_cast<size_t>(hist_bytes / 8)));
+    DS_TRY(t->counts.allocate(heap_nodes(max_depth)));
+    DS_TRY(t->nodes.allocate(heap_nodes(max_depth)));
+    DS_TRY(t->candidates.allocate(static_cast<size_t>(ds::candidate_entries(max_depth, n_features))));
+    DS_TRY(t->error.allocate(1));
+    DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pinned_nodes), sizeof(ds::Node) * heap_nodes(max_depth)));
+    DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pinned_error), sizeof(unsigned long long)));
+    DS_HIP(hipMemsetAsync(t->leafsum.ptr, 0, sizeof(float) * n, t->stream));
+    DS_HIP(hipStreamSynchronize(t->stream));
     t->view = ds::TrainView{t->bins.ptr, t->labels.ptr, nullptr, nullptr, t->cut_offsets.ptr, nullptr, nullptr,
                             t->gh.ptr, t->node_of.ptr, t->leafsum.ptr, t->probabilities.ptr, t->hist.ptr, t->nodes.ptr,
                             t->counts.ptr, t->candidates.ptr, t->error.ptr, n, hist_bytes / 8,
                             ds::candidate_entries(max_depth, n_features), n_features,
                             static_cast<int32_t>(heap_nodes(max_depth)), ds::TrainModel{t->params, -1, 0}};
-    *out = t;
+    *out = owner.release();
     return DS_OK;
 }
 
@@ -654,13 +625,12 @@ int set_eval(const char *who, ds_trainer *trainer, const float *features, bool i
     DS_REQUIRE(trainer->rounds == 0, "%s: the evaluation set must be given before the first round", who);
     DS_REQUIRE(!trainer->seeded, "%s: the evaluation set must be given before the trainer is seeded", who);
     DS_REQUIRE(trainer->metric_flags == 0, "%s: the evaluation set must be given before ds_trainer_set_metrics", who);
-    if (int status = ds::train_check_labels(who, "", labels, n); status != DS_OK) return status;
+    DS_TRY(ds::train_check_labels(who, "", labels, n));
     DS_HIP(hipSetDevice(trainer->device));
-    if (int status = check_free(n * trainer->nf * (in_hbm ? 1 : 5) + n * 8, who); status != DS_OK) return status;
-    int status = bin_matrix(trainer, features, in_hbm, n, trainer->eval_bins);
-    if (status == DS_OK) status = trainer->eval_labels.upload(labels, n);
-    if (status == DS_OK) status = trainer->eval_leafsum.allocate(n);
-    if (status != DS_OK) return status;
+    DS_TRY(check_free(n * trainer->nf * (in_hbm ? 1 : 5) + n * 8, who));
+    DS_TRY(bin_matrix(trainer, features, in_hbm, n, trainer->eval_bins));
+    DS_TRY(trainer->eval_labels.upload(labels, n));
+    DS_TRY(trainer->eval_leafsum.allocate(n));
     DS_HIP(hipMemsetAsync(trainer->eval_leafsum.ptr, 0, sizeof(float) * n, trainer->stream));
     DS_HIP(hipStreamSynchronize(trainer->stream));
     trainer->n_eval = n;
@@ -671,20 +641,14 @@ int set_eval(const char *who, ds_trainer *trainer, const float *features, bool i
 int enqueue_seed(ds_trainer *t, const ds_forest *forest, const float *features, const float *eval_features, bool in_hbm,
                  hipStream_t stream, ds::DeviceBuffer<float> &staged, ds::DeviceBuffer<float> &eval_staged)
 {
-    if (int status = ds::train_seed_enqueue(stream, t->compute_units, forest, features, in_hbm, t->n, t->leafsum.ptr, 1,
-                                            t->n, staged);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::train_seed_enqueue(stream, t->compute_units, forest, features, in_hbm, t->n, t->leafsum.ptr, 1, t->n, staged));
     if (t->n_eval == 0) return DS_OK;
-    if (int status = ds::train_seed_enqueue(stream, t->compute_units, forest, eval_features, in_hbm, t->n_eval,
-                                            t->eval_leafsum.ptr, 1, t->n_eval, eval_staged);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::train_seed_enqueue(stream, t->compute_units, forest, eval_features, in_hbm, t->n_eval,
+                                  t->eval_leafsum.ptr, 1, t->n_eval, eval_staged));
     DS_HIP(hipMemsetAsync(t->error.ptr, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(ds::ds_train_error_kernel, dim3(ds::train_row_grid(t->compute_units, t->n_eval)),
-                       dim3(ds::kRowThreads), 0, stream, t->eval_leafsum.ptr, t->eval_labels.ptr, t->n_eval,
-                       ds::kTrainBaseMargin, t->error.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_train_error_kernel, dim3(ds::train_row_grid(t->compute_units, t->n_eval)),
+              dim3(ds::kRowThreads), 0, stream, t->eval_leafsum.ptr, t->eval_labels.ptr, t->n_eval,
+              ds::kTrainBaseMargin, t->error.ptr);
     DS_HIP(hipMemcpyAsync(t->pinned_error, t->error.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     return DS_OK;
 }
@@ -694,7 +658,7 @@ int seed_trainer(const char *who, ds_trainer *t, const ds_forest *forest, const 
                  bool in_hbm, int64_t *initial_error, hipStream_t stream)
 {
     DS_REQUIRE(t != nullptr, "%s: trainer is null", who);
-    if (int status = ds::train_check_seed_forest(who, forest, t->device, t->nf); status != DS_OK) return status;
+    DS_TRY(ds::train_check_seed_forest(who, forest, t->device, t->nf));
     DS_REQUIRE(features != nullptr, "%s: features is null", who);
     DS_REQUIRE(t->has_labels, "%s: no labels (ds_trainer_set_labels)", who);
     DS_REQUIRE((eval_features != nullptr) == (t->n_eval > 0),
@@ -705,8 +669,7 @@ int seed_trainer(const char *who, ds_trainer *t, const ds_forest *forest, const 
     if (!in_hbm) {   // one chunk per set at the most
         stream = t->stream;
         const int64_t rows = t->n + t->n_eval;
-        if (int status = check_free(std::min(rows * t->nf * 4, 2 * ds::kSeedChunkBytes), who); status != DS_OK)
-            return status;
+        DS_TRY(check_free(std::min(rows * t->nf * 4, 2 * ds::kSeedChunkBytes), who));
     }
     ds::DeviceBuffer<float> staged, eval_staged;
     t->seeded = true;   // whatever happens below: a trainer whose margins may be partly written is not seeded again
@@ -750,8 +713,7 @@ int ds_trainer_set_labels(ds_trainer *trainer, const float *labels)
 {
     DS_REQUIRE(trainer && labels, "ds_trainer_set_labels: null argument");
     DS_REQUIRE(trainer->metric_flags == 0, "ds_trainer_set_labels: the labels must be set before ds_trainer_set_metrics");
-    if (int status = ds::train_check_labels("ds_trainer_set_labels", "", labels, trainer->n); status != DS_OK)
-        return status;
+    DS_TRY(ds::train_check_labels("ds_trainer_set_labels", "", labels, trainer->n));
     DS_HIP(hipSetDevice(trainer->device));
     DS_HIP(hipMemcpyAsync(trainer->labels.ptr, labels, sizeof(float) * trainer->n, hipMemcpyHostToDevice,
                           trainer->stream));
@@ -769,13 +731,13 @@ int ds_trainer_set_weights(ds_trainer *trainer, const float *weights)
     DS_REQUIRE(t->has_labels, "%s: no labels (ds_trainer_set_labels)", who);
     DS_REQUIRE(t->rounds == 0, "%s: the weights must be set before the first round", who);
     DS_REQUIRE(!t->weighted, "%s: the weights are already set", who);
-    if (int status = ds::train_check_weights(who, weights, t->n, t->params.beta); status != DS_OK) return status;
+    DS_TRY(ds::train_check_weights(who, weights, t->n, t->params.beta));
     bool positive = false;
     for (int64_t r = 0; r < t->n && !positive; ++r) positive = weights[r] > 0.f;
     DS_REQUIRE(positive, "%s: the total weight of the training rows is 0", who);
     DS_HIP(hipSetDevice(t->device));
-    if (int status = check_free(t->n * 4, who); status != DS_OK) return status;
-    if (int status = t->weights.allocate(static_cast<size_t>(t->n)); status != DS_OK) return status;
+    DS_TRY(check_free(t->n * 4, who));
+    DS_TRY(t->weights.allocate(static_cast<size_t>(t->n)));
     DS_HIP(hipMemcpyAsync(t->weights.ptr, weights, sizeof(float) * t->n, hipMemcpyHostToDevice, t->stream));
     DS_HIP(hipStreamSynchronize(t->stream));
     t->view.weights = t->weights.ptr;
@@ -793,12 +755,12 @@ int ds_trainer_set_monotone(ds_trainer *trainer, const int8_t *constraints)
     DS_REQUIRE(t->rounds == 0, "%s: the constraints must be set before the first round", who);
     DS_REQUIRE(!t->constrained, "%s: the constraints are already set", who);
     bool any = false;
-    if (int status = ds::train_check_monotone(who, constraints, t->nf, &any); status != DS_OK) return status;
+    DS_TRY(ds::train_check_monotone(who, constraints, t->nf, &any));
     if (any) {   // all zeros: nothing is allocated and the plain kernels keep running
         DS_HIP(hipSetDevice(t->device));
         const size_t slots = static_cast<size_t>(t->view.slots);
-        if (int status = t->monotone.allocate(static_cast<size_t>(t->nf)); status != DS_OK) return status;
-        if (int status = t->bounds.allocate(2 * slots); status != DS_OK) return status;
+        DS_TRY(t->monotone.allocate(static_cast<size_t>(t->nf)));
+        DS_TRY(t->bounds.allocate(2 * slots));
         DS_HIP(hipMemcpyAsync(t->monotone.ptr, constraints, static_cast<size_t>(t->nf), hipMemcpyHostToDevice, t->stream));
         DS_HIP(hipMemsetAsync(t->bounds.ptr, 0, t->bounds.bytes(), t->stream));
         DS_HIP(hipStreamSynchronize(t->stream));
@@ -825,15 +787,13 @@ int ds_trainer_set_sampling(ds_trainer *trainer, double subsample, double colsam
     DS_REQUIRE(trainer != nullptr, "ds_trainer_set_sampling: trainer is null");
     ds_trainer *t = trainer;
     const double fractions[3] = {subsample, colsample_bytree, colsample_bylevel};
-    if (int status = ds::train_check_fractions("ds_trainer_set_sampling", -1, fractions); status != DS_OK) return status;
+    DS_TRY(ds::train_check_fractions("ds_trainer_set_sampling", -1, fractions));
     DS_REQUIRE(t->rounds == 0, "ds_trainer_set_sampling: the sampling must be set before the first round");
-    if (int status = ds::train_check_subsample("ds_trainer_set_sampling", -1, subsample, t->params.reg_lambda);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::train_check_subsample("ds_trainer_set_sampling", -1, subsample, t->params.reg_lambda));
     const ds::TrainSampling sampling{subsample, colsample_bytree, colsample_bylevel, sample_seed};
     if (sampling.any() && t->masks.ptr == nullptr) {
         DS_HIP(hipSetDevice(t->device));
-        if (int status = t->masks.allocate(ds::kMaskBytes); status != DS_OK) return status;
+        DS_TRY(t->masks.allocate(ds::kMaskBytes));
     }
     t->sampling_view = ds::TrainSamplingView{nullptr, nullptr, nullptr, nullptr, t->masks.ptr, 0, sampling, 0};
     t->sampled = sampling.any();   // every fraction 1: the plain kernels, whatever was set before
@@ -885,20 +845,13 @@ int ds_trainer_set_metrics(ds_trainer *trainer, uint32_t flags)
         for (int64_t r = 0; r < sizes[set]; ++r) rows[labels[r] == 0.f ? at_neg++ : at_pos++] = static_cast<int32_t>(r);
     }
     const int64_t n_keys = (flags & ds::kMetricAuc) ? std::max(negatives[0], negatives[1]) : 0;
-    if (int status = check_free(4 * int64_t(rows.size()) + ds::MetricScratch::bytes(n_keys, 1), "ds_trainer_set_metrics");
-        status != DS_OK)
-        return status;
-    int status = t->metric_rows.upload(rows.data(), rows.size());
-    if (status == DS_OK) status = t->metric_columns.allocate(2);
-    if (status == DS_OK) status = t->metric_counters.allocate(2 * ds::kMetricCounters);
-    if (status == DS_OK) status = t->metric_scratch.allocate(n_keys, 1);
-    if (status == DS_OK && t->pinned_metrics == nullptr &&
-        hipHostMalloc(reinterpret_cast<void **>(&t->pinned_metrics), sizeof(unsigned long long) * 2 * ds::kMetricCounters) !=
-            hipSuccess) {
-        ds::set_error("ds_trainer_set_metrics: hipHostMalloc failed");
-        status = DS_E_HIP;
-    }
-    if (status != DS_OK) return status;
+    DS_TRY(check_free(4 * int64_t(rows.size()) + ds::MetricScratch::bytes(n_keys, 1), "ds_trainer_set_metrics"));
+    DS_TRY(t->metric_rows.upload(rows.data(), rows.size()));
+    DS_TRY(t->metric_columns.allocate(2));
+    DS_TRY(t->metric_counters.allocate(2 * ds::kMetricCounters));
+    DS_TRY(t->metric_scratch.allocate(n_keys, 1));
+    if (t->pinned_metrics == nullptr)
+        DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->pinned_metrics), sizeof(unsigned long long) * 2 * ds::kMetricCounters));
     for (int set = 0; set < 2; ++set) {
         const int32_t *list = t->metric_rows.ptr + first[set];
         t->metric_host[set] = ds::MetricColumn{d_scores[set], list, list + negatives[set],
@@ -936,25 +889,23 @@ int ds_gather_rows_device(const float *d_src, int32_t n_features, const int64_t 
     DS_REQUIRE(d_src && d_rows && d_dst, "ds_gather_rows_device: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ds::DeviceBuffer<int32_t> error;
-    if (int status = error.allocate(1); status != DS_OK) return status;
+    DS_TRY(error.allocate(1));
     int32_t errors = 0;
     DS_HIP(hipMemsetAsync(error.ptr, 0, sizeof(int32_t), s));
     const auto grid = [](int64_t items) {
         return dim3(static_cast<unsigned>(std::min<int64_t>((items + ds::kRowThreads - 1) / ds::kRowThreads, 256 * 16)));
     };
-    hipLaunchKernelGGL(ds::ds_gather_check_kernel, grid(n_rows), dim3(ds::kRowThreads), 0, s, d_rows, n_rows, n_src,
-                       error.ptr);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_gather_check_kernel, grid(n_rows), dim3(ds::kRowThreads), 0, s, d_rows, n_rows, n_src,
+              error.ptr);
     DS_HIP(hipMemcpyAsync(&errors, error.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     DS_HIP(hipStreamSynchronize(s));
     if (errors != 0) {
         ds::set_error("ds_gather_rows_device: %d row indexes are out of range [0, %lld)", errors, (long long)n_src);
         return DS_E_ARG;
     }
-    hipLaunchKernelGGL(ds::ds_gather_rows_kernel, grid(n_rows * n_features), dim3(ds::kRowThreads), 0, s,
-                       reinterpret_cast<const uint32_t *>(d_src), n_features, d_rows, n_rows, n_src,
-                       reinterpret_cast<uint32_t *>(d_dst));
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_gather_rows_kernel, grid(n_rows * n_features), dim3(ds::kRowThreads), 0, s,
+              reinterpret_cast<const uint32_t *>(d_src), n_features, d_rows, n_rows, n_src,
+              reinterpret_cast<uint32_t *>(d_dst));
     DS_HIP(hipStreamSynchronize(s));
     return DS_OK;
 }
@@ -969,27 +920,20 @@ int ds_trainer_step(ds_trainer *trainer, int32_t *node_info, float *node_leaf, i
     hipStream_t stream = t->stream;
     // this tree's number indexes its streams: a seeded trainer counts on from the forest's trees
     if (t->sampled) t->sampling_view.tree = t->tree_base + static_cast<int32_t>(t->rounds);
-    if (int status = ds::train_round_enqueue(stream, t->view, t->sampled ? &t->sampling_view : nullptr, 1, depth, false,
-                                             t->compute_units);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::train_round_enqueue(stream, t->view, t->sampled ? &t->sampling_view : nullptr, 1, depth, false, t->compute_units));
     if (t->n_eval > 0) {
-        hipLaunchKernelGGL(ds::ds_train_eval_kernel, dim3(ds::train_row_grid(t->compute_units, t->n_eval)),
-                           dim3(ds::kRowThreads), 0, stream, t->eval_bins.ptr, t->nodes.ptr, t->n_eval,
-                           t->eval_labels.ptr, ds::kTrainBaseMargin, t->eval_leafsum.ptr, t->error.ptr);
-        DS_HIP(hipGetLastError());
+        DS_LAUNCH(ds::ds_train_eval_kernel, dim3(ds::train_row_grid(t->compute_units, t->n_eval)),
+                  dim3(ds::kRowThreads), 0, stream, t->eval_bins.ptr, t->nodes.ptr, t->n_eval,
+                  t->eval_labels.ptr, ds::kTrainBaseMargin, t->eval_leafsum.ptr, t->error.ptr);
     }
     DS_HIP(hipMemcpyAsync(t->pinned_nodes, t->nodes.ptr, t->nodes.bytes(), hipMemcpyDeviceToHost, stream));
     DS_HIP(hipMemcpyAsync(t->pinned_error, t->error.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     if (t->metric_flags) {   // over the margins the partition and eval kernels have just written
         for (int set = 0; set < (t->n_eval > 0 ? 2 : 1); ++set) {
             const ds::MetricColumn &column = t->metric_host[set];
-            if (int status = ds::metrics_enqueue(stream, t->compute_units, t->metric_flags, t->metric_columns.ptr + set,
-                                                 nullptr, 1, column.n_neg, column.n_pos,
-                                                 int64_t(column.n_neg) + column.n_pos, t->metric_scratch,
-                                                 t->metric_counters.ptr + set * ds::kMetricCounters, 0);
-                status != DS_OK)
-                return status;
+            DS_TRY(ds::metrics_enqueue(stream, t->compute_units, t->metric_flags, t->metric_columns.ptr + set, nullptr,
+                                       1, column.n_neg, column.n_pos, int64_t(column.n_neg) + column.n_pos,
+                                       t->metric_scratch, t->metric_counters.ptr + set * ds::kMetricCounters, 0));
         }
         DS_HIP(hipMemcpyAsync(t->pinned_metrics, t->metric_counters.ptr, t->metric_counters.bytes(),
                               hipMemcpyDeviceToHost, stream));
@@ -1023,11 +967,10 @@ int ds_trainer_read(ds_trainer *trainer, float *margins, float *probabilities, i
         return DS_OK;
     };
     if (margins) {
-        if (int status = add_base(margins, t->leafsum.ptr, n); status != DS_OK) return status;
+        DS_TRY(add_base(margins, t->leafsum.ptr, n));
     }
     if (eval_margins) {
-        if (int status = add_base(eval_margins, t->eval_leafsum.ptr, static_cast<size_t>(t->n_eval)); status != DS_OK)
-            return status;
+        DS_TRY(add_base(eval_margins, t->eval_leafsum.ptr, static_cast<size_t>(t->n_eval)));
     }
     return DS_OK;
 }

@@ -46,6 +46,7 @@
 // ds_train_seed_kernel walks a forest over the RAW matrix once per row and writes the leaf sum into all M leafsum columns;
 // ds_batch_error_kernel then gives every model's held-out error at those margins, and every model's tree count starts at
 // the forest's.
+#include "ds_launch.h"
 #include "ds_forest.h"
 #include "ds_metrics.h"
 #include "ds_train.h"
@@ -156,7 +157,7 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
     DS_REQUIRE(fold != nullptr, "%s: fold is null", who);
     DS_REQUIRE(params != nullptr, "%s: params is null", who);
     DS_REQUIRE(held_out != nullptr, "%s: held_out is null", who);
-    if (int status = ds::train_check_shape(who, n, n_features); status != DS_OK) return status;
+    DS_TRY(ds::train_check_shape(who, n, n_features));
     DS_REQUIRE(n_models >= 1 && n_models <= ds::kBatchModelsMax, "%s: n_models = %d out of range [1, %d]", who, n_models,
                ds::kBatchModelsMax);
     DS_REQUIRE(n_folds >= 1 && n_folds <= ds::kBatchFoldsMax, "%s: n_folds = %d out of range [1, %d]", who, n_folds,
@@ -168,21 +169,22 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
         DS_REQUIRE(p[0] >= 1 && p[0] <= ds::kTrainMaxDepth && p[0] == static_cast<double>(static_cast<int32_t>(p[0])),
                    "%s: params of model %d: max_depth = %g is not an integer in [1, %d]", who, m, p[0],
                    ds::kTrainMaxDepth);
-        if (int status = ds::train_check_params(who, m, p[1], p[2], p[3], p[4]); status != DS_OK) return status;
+        DS_TRY(ds::train_check_params(who, m, p[1], p[2], p[3], p[4]));
         DS_REQUIRE(held_out[m] >= -1 && held_out[m] < n_folds, "%s: held_out[%d] = %d out of range [-1, %d)", who, m,
                    held_out[m], n_folds);
         models[m] = ds::TrainModel{ds::TrainParams{static_cast<int32_t>(p[0]), p[1], p[2], p[3], p[4]}, held_out[m], 0};
         depth = std::max(depth, models[m].params.max_depth);
     }
-    if (int status = ds::train_check_cuts(who, n_features, cuts, cut_offsets); status != DS_OK) return status;
-    if (int status = ds::train_check_labels(who, "labels: ", labels, n); status != DS_OK) return status;
+    DS_TRY(ds::train_check_cuts(who, n_features, cuts, cut_offsets));
+    DS_TRY(ds::train_check_labels(who, "labels: ", labels, n));
     for (int64_t r = 0; r < n; ++r)
         DS_REQUIRE(fold[r] < n_folds, "%s: fold[%lld] = %d is not below n_folds = %d", who, (long long)r, fold[r],
                    n_folds);
     const int64_t bytes = ds_trainer_batch_bytes(n, n_features, n_models, depth) + (in_hbm ? 0 : n * n_features * 4);
     DS_HIP(hipSetDevice(device));
-    if (int status = ds::train_check_free(bytes, who); status != DS_OK) return status;
-    ds_trainer_batch *b = new ds_trainer_batch();
+    DS_TRY(ds::check_free(bytes, who));
+    std::unique_ptr<ds_trainer_batch> owner(new ds_trainer_batch());
+    ds_trainer_batch *b = owner.get();
     b->device = device;
     b->n = n;
     b->nf = n_features;
@@ -192,45 +194,36 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
     b->models = models;
     b->tree_count.assign(n_models, 0);
     const size_t M = static_cast<size_t>(n_models), rows = static_cast<size_t>(n);
-    int status = ds::train_create_setup(who, device, n_features, cuts, cut_offsets, &b->stream, b->cuts, b->cut_offsets,
-                                        &b->compute_units);
-    if (status == DS_OK)
-        status = ds::train_bin_matrix(b->stream, b->compute_units, features, in_hbm, n, n_features, b->cuts.ptr,
-                                      b->cut_offsets.ptr, b->bins);
-    if (status == DS_OK) status = b->labels.upload(labels, rows);
-    if (status == DS_OK) status = b->fold.upload(fold, rows);
-    if (status == DS_OK) status = b->d_models.upload(models.data(), M);
-    if (status == DS_OK) status = b->active.allocate(M);
-    if (status == DS_OK) status = b->leafsum.allocate(M * rows);
-    if (status == DS_OK) status = b->probabilities.allocate(M * rows);
-    if (status == DS_OK) status = b->node_of.allocate(M * rows);
-    if (status == DS_OK) status = b->gh.allocate(2 * M * rows);
-    if (status == DS_OK) status = b->hist.allocate(M * static_cast<size_t>(hist_entries(depth, n_features)));
-    if (status == DS_OK) status = b->counts.allocate(M * b->slots);
-    if (status == DS_OK) status = b->nodes.allocate(M * b->slots);
-    if (status == DS_OK) status = b->candidates.allocate(M * static_cast<size_t>(candidate_entries(depth, n_features)));
-    if (status == DS_OK) status = b->errors.allocate(M);
-    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&b->pinned_nodes), sizeof(ds::Node) * M * b->slots) !=
-                               hipSuccess) status = DS_E_HIP;
-    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&b->pinned_errors), sizeof(unsigned long long) * M) !=
-                               hipSuccess) status = DS_E_HIP;
-    if (status == DS_OK && hipHostMalloc(reinterpret_cast<void **>(&b->pinned_active), sizeof(int32_t) * M) != hipSuccess)
-        status = DS_E_HIP;
+    DS_TRY(ds::train_create_setup(who, device, n_features, cuts, cut_offsets, &b->stream, b->cuts, b->cut_offsets,
+                                  &b->compute_units));
+    DS_TRY(ds::train_bin_matrix(b->stream, b->compute_units, features, in_hbm, n, n_features, b->cuts.ptr,
+                                b->cut_offsets.ptr, b->bins));
+    DS_TRY(b->labels.upload(labels, rows));
+    DS_TRY(b->fold.upload(fold, rows));
+    DS_TRY(b->d_models.upload(models.data(), M));
+    DS_TRY(b->active.allocate(M));
+    DS_TRY(b->leafsum.allocate(M * rows));
+    DS_TRY(b->probabilities.allocate(M * rows));
+    DS_TRY(b->node_of.allocate(M * rows));
+    DS_TRY(b->gh.allocate(2 * M * rows));
+    DS_TRY(b->hist.allocate(M * static_cast<size_t>(hist_entries(depth, n_features))));
+    DS_TRY(b->counts.allocate(M * b->slots));
+    DS_TRY(b->nodes.allocate(M * b->slots));
+    DS_TRY(b->candidates.allocate(M * static_cast<size_t>(candidate_entries(depth, n_features))));
+    DS_TRY(b->errors.allocate(M));
+    DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->pinned_nodes), sizeof(ds::Node) * M * b->slots));
+    DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->pinned_errors), sizeof(unsigned long long) * M));
+    DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->pinned_active), sizeof(int32_t) * M));
     // every per-row array starts defined: the read-back of a model that has not stepped yet returns zeros
-    if (status == DS_OK && hipMemsetAsync(b->leafsum.ptr, 0, b->leafsum.bytes(), b->stream) != hipSuccess) status = DS_E_HIP;
-    if (status == DS_OK && hipMemsetAsync(b->probabilities.ptr, 0, b->probabilities.bytes(), b->stream) != hipSuccess)
-        status = DS_E_HIP;
-    if (status == DS_OK && hipMemsetAsync(b->gh.ptr, 0, b->gh.bytes(), b->stream) != hipSuccess) status = DS_E_HIP;
-    if (status == DS_OK && hipStreamSynchronize(b->stream) != hipSuccess) status = DS_E_HIP;
-    if (status != DS_OK) {
-        delete b;
-        return status;
-    }
+    DS_HIP(hipMemsetAsync(b->leafsum.ptr, 0, b->leafsum.bytes(), b->stream));
+    DS_HIP(hipMemsetAsync(b->probabilities.ptr, 0, b->probabilities.bytes(), b->stream));
+    DS_HIP(hipMemsetAsync(b->gh.ptr, 0, b->gh.bytes(), b->stream));
+    DS_HIP(hipStreamSynchronize(b->stream));
     b->view = ds::TrainView{b->bins.ptr, b->labels.ptr, nullptr, b->fold.ptr, b->cut_offsets.ptr, b->d_models.ptr, b->active.ptr,
                             b->gh.ptr, b->node_of.ptr, b->leafsum.ptr, b->probabilities.ptr, b->hist.ptr, b->nodes.ptr,
                             b->counts.ptr, b->candidates.ptr, b->errors.ptr, n, hist_entries(depth, n_features),
                             candidate_entries(depth, n_features), n_features, b->slots};
-    *out = b;
+    *out = owner.release();
     return DS_OK;
 }
 
@@ -238,17 +231,14 @@ int create_batch(const char *who, const float *features, bool in_hbm, int64_t n,
 int enqueue_seed(ds_trainer_batch *b, const ds_forest *forest, const float *features, bool in_hbm, hipStream_t stream,
                  ds::DeviceBuffer<float> &staged)
 {
-    if (int status = ds::train_seed_enqueue(stream, b->compute_units, forest, features, in_hbm, b->n, b->leafsum.ptr,
-                                            b->n_models, b->n, staged);
-        status != DS_OK)
-        return status;
+    DS_TRY(ds::train_seed_enqueue(stream, b->compute_units, forest, features, in_hbm, b->n, b->leafsum.ptr, b->n_models,
+                                  b->n, staged));
     for (int32_t m = 0; m < b->n_models; ++m) b->pinned_active[m] = m;   // the error kernel reads its models from here
     DS_HIP(hipMemcpyAsync(b->active.ptr, b->pinned_active, sizeof(int32_t) * b->n_models, hipMemcpyHostToDevice, stream));
     DS_HIP(hipMemsetAsync(b->errors.ptr, 0, b->errors.bytes(), stream));
-    hipLaunchKernelGGL(ds::ds_batch_error_kernel,
-                       dim3(ds::train_row_grid(b->compute_units, b->n), static_cast<unsigned>(b->n_models)),
-                       dim3(ds::kRowThreads), 0, stream, b->view);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_batch_error_kernel,
+              dim3(ds::train_row_grid(b->compute_units, b->n), static_cast<unsigned>(b->n_models)),
+              dim3(ds::kRowThreads), 0, stream, b->view);
     DS_HIP(hipMemcpyAsync(b->pinned_errors, b->errors.ptr, b->errors.bytes(), hipMemcpyDeviceToHost, stream));
     return DS_OK;
 }
@@ -258,15 +248,14 @@ int seed_batch(const char *who, ds_trainer_batch *b, const ds_forest *forest, co
                int64_t *initial_errors, hipStream_t stream)
 {
     DS_REQUIRE(b != nullptr, "%s: batch is null", who);
-    if (int status = ds::train_check_seed_forest(who, forest, b->device, b->nf); status != DS_OK) return status;
+    DS_TRY(ds::train_check_seed_forest(who, forest, b->device, b->nf));
     DS_REQUIRE(features != nullptr, "%s: features is null", who);
     DS_REQUIRE(!b->stepped, "%s: the batch must be seeded before the first step", who);
     DS_REQUIRE(!b->seeded, "%s: the batch is already seeded", who);
     DS_HIP(hipSetDevice(b->device));
     if (!in_hbm) {
         stream = b->stream;
-        if (int status = ds::train_check_free(std::min(b->n * b->nf * 4, ds::kSeedChunkBytes), who); status != DS_OK)
-            return status;
+        DS_TRY(ds::check_free(std::min(b->n * b->nf * 4, ds::kSeedChunkBytes), who));
     }
     ds::DeviceBuffer<float> staged;
     b->seeded = true;   // whatever happens below: a batch whose margins may be partly written is not seeded again
@@ -337,10 +326,8 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
     bool any = false;
     for (int32_t m = 0; m < b->n_models; ++m) {
         const double *f = fractions + 3 * m;
-        if (int status = ds::train_check_fractions("ds_trainer_batch_set_sampling", m, f); status != DS_OK) return status;
-        if (int status = ds::train_check_subsample("ds_trainer_batch_set_sampling", m, f[0], b->models[m].params.reg_lambda);
-            status != DS_OK)
-            return status;
+        DS_TRY(ds::train_check_fractions("ds_trainer_batch_set_sampling", m, f));
+        DS_TRY(ds::train_check_subsample("ds_trainer_batch_set_sampling", m, f[0], b->models[m].params.reg_lambda));
         sampling[m] = ds::TrainSampling{f[0], f[1], f[2], sample_seeds[m]};
         any = any || sampling[m].any();
         const int32_t held_out = b->models[m].held_out;
@@ -371,17 +358,13 @@ int ds_trainer_batch_set_sampling(ds_trainer_batch *batch, const double *fractio
             ++seen[fold[r]];
         }
     }
-    int status = b->d_sampling.upload(sampling.data(), M);
-    if (status == DS_OK) status = b->d_held_slot.upload(held_slot.data(), M);
-    if (status == DS_OK) status = b->d_held_before.upload(held_before.data(), held_before.size());
-    if (status == DS_OK && b->d_trees.ptr == nullptr) status = b->d_trees.allocate(M);
-    if (status == DS_OK && b->masks.ptr == nullptr) status = b->masks.allocate(M * ds::kMaskBytes);
-    if (status == DS_OK && b->pinned_trees == nullptr &&
-        hipHostMalloc(reinterpret_cast<void **>(&b->pinned_trees), sizeof(int32_t) * M) != hipSuccess) {
-        ds::set_error("ds_trainer_batch_set_sampling: hipHostMalloc failed");
-        status = DS_E_HIP;
-    }
-    if (status != DS_OK) return status;
+    DS_TRY(b->d_sampling.upload(sampling.data(), M));
+    DS_TRY(b->d_held_slot.upload(held_slot.data(), M));
+    DS_TRY(b->d_held_before.upload(held_before.data(), held_before.size()));
+    if (b->d_trees.ptr == nullptr) DS_TRY(b->d_trees.allocate(M));
+    if (b->masks.ptr == nullptr) DS_TRY(b->masks.allocate(M * ds::kMaskBytes));
+    if (b->pinned_trees == nullptr)
+        DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->pinned_trees), sizeof(int32_t) * M));
     b->sampling_view = ds::TrainSamplingView{b->d_sampling.ptr, b->d_trees.ptr, b->d_held_before.ptr, b->d_held_slot.ptr,
                                              b->masks.ptr, static_cast<int64_t>(waves)};
     b->sampled = true;
@@ -398,7 +381,7 @@ int ds_trainer_batch_set_weights(ds_trainer_batch *batch, const float *weights)
     DS_REQUIRE(!b->weighted, "%s: the weights are already set", who);
     double beta = 0.0;
     for (const ds::TrainModel &model : b->models) beta = std::max(beta, model.params.beta);
-    if (int status = ds::train_check_weights(who, weights, b->n, beta); status != DS_OK) return status;
+    DS_TRY(ds::train_check_weights(who, weights, b->n, beta));
     DS_HIP(hipSetDevice(b->device));
     // every model's training rows must weigh something: whether a fold (slot 0: any fold) has a row of positive weight
     std::vector<uint8_t> fold(static_cast<size_t>(b->n)), positive(ds::kBatchFoldsMax + 1, 0);
@@ -414,8 +397,8 @@ int ds_trainer_batch_set_weights(ds_trainer_batch *batch, const float *weights)
         DS_REQUIRE(positive_folds - (held_out >= 0 && positive[held_out] ? 1 : 0) > 0,
                    "%s: model %d: the total weight of its training rows is 0", who, m);
     }
-    if (int status = ds::train_check_free(b->n * 4, who); status != DS_OK) return status;
-    if (int status = b->weights.allocate(static_cast<size_t>(b->n)); status != DS_OK) return status;
+    DS_TRY(ds::check_free(b->n * 4, who));
+    DS_TRY(b->weights.allocate(static_cast<size_t>(b->n)));
     DS_HIP(hipMemcpyAsync(b->weights.ptr, weights, sizeof(float) * b->n, hipMemcpyHostToDevice, b->stream));
     DS_HIP(hipStreamSynchronize(b->stream));
     b->view.weights = b->weights.ptr;
@@ -432,13 +415,13 @@ int ds_trainer_batch_set_monotone(ds_trainer_batch *batch, const int8_t *constra
     DS_REQUIRE(!b->stepped, "%s: the constraints must be set before the first step", who);
     DS_REQUIRE(!b->constrained, "%s: the constraints are already set", who);
     bool any = false;
-    if (int status = ds::train_check_monotone(who, constraints, b->nf, &any); status != DS_OK) return status;
+    DS_TRY(ds::train_check_monotone(who, constraints, b->nf, &any));
     if (any) {   // all zeros: nothing is allocated and the plain kernels keep running
         DS_HIP(hipSetDevice(b->device));
         const size_t pairs = static_cast<size_t>(b->n_models) * b->slots;
-        if (int status = ds::train_check_free(int64_t(16 * pairs) + b->nf, who); status != DS_OK) return status;
-        if (int status = b->monotone.allocate(static_cast<size_t>(b->nf)); status != DS_OK) return status;
-        if (int status = b->bounds.allocate(2 * pairs); status != DS_OK) return status;
+        DS_TRY(ds::check_free(int64_t(16 * pairs) + b->nf, who));
+        DS_TRY(b->monotone.allocate(static_cast<size_t>(b->nf)));
+        DS_TRY(b->bounds.allocate(2 * pairs));
         DS_HIP(hipMemcpyAsync(b->monotone.ptr, constraints, static_cast<size_t>(b->nf), hipMemcpyHostToDevice, b->stream));
         DS_HIP(hipMemsetAsync(b->bounds.ptr, 0, b->bounds.bytes(), b->stream));
         DS_HIP(hipStreamSynchronize(b->stream));
@@ -512,21 +495,13 @@ int ds_trainer_batch_set_metrics(ds_trainer_batch *batch, uint32_t flags)
     for (int k = 0; k <= ds::kBatchFoldsMax; ++k) at_pos[k] += neg[k];
     for (size_t r = 0; r < rows; ++r)
         if (wanted[fold[r]]) lists[(labels[r] == 0.f ? at_neg : at_pos)[fold[r]]++] = static_cast<int32_t>(r);
-    if (int status = ds::train_check_free(4 * listed + ds::MetricScratch::bytes(b->metric_keys, b->n_models),
-                                          "ds_trainer_batch_set_metrics");
-        status != DS_OK)
-        return status;
-    int status = b->metric_rows.upload(lists.data(), lists.size());
-    if (status == DS_OK) status = b->metric_columns.allocate(M);
-    if (status == DS_OK) status = b->metric_counters.allocate(M * ds::kMetricCounters);
-    if (status == DS_OK) status = b->metric_scratch.allocate(b->metric_keys, b->n_models);
-    if (status == DS_OK && b->pinned_metrics == nullptr &&
-        hipHostMalloc(reinterpret_cast<void **>(&b->pinned_metrics), sizeof(unsigned long long) * M * ds::kMetricCounters) !=
-            hipSuccess) {
-        ds::set_error("ds_trainer_batch_set_metrics: hipHostMalloc failed");
-        status = DS_E_HIP;
-    }
-    if (status != DS_OK) return status;
+    DS_TRY(ds::check_free(4 * listed + ds::MetricScratch::bytes(b->metric_keys, b->n_models), "ds_trainer_batch_set_metrics"));
+    DS_TRY(b->metric_rows.upload(lists.data(), lists.size()));
+    DS_TRY(b->metric_columns.allocate(M));
+    DS_TRY(b->metric_counters.allocate(M * ds::kMetricCounters));
+    DS_TRY(b->metric_scratch.allocate(b->metric_keys, b->n_models));
+    if (b->pinned_metrics == nullptr)
+        DS_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->pinned_metrics), sizeof(unsigned long long) * M * ds::kMetricCounters));
     b->metric_host.assign(M, ds::MetricColumn{});
     for (size_t m = 0; m < M; ++m) {
         const int32_t k = b->models[m].held_out;
@@ -577,14 +552,10 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
         DS_HIP(hipMemcpyAsync(b->d_trees.ptr, b->pinned_trees, sizeof(int32_t) * b->n_models, hipMemcpyHostToDevice,
                               stream));
     }
-    if (int status = ds::train_round_enqueue(stream, v, b->sampled ? &b->sampling_view : nullptr, n_active, depth, true,
-                                             b->compute_units);
-        status != DS_OK)
-        return status;
-    hipLaunchKernelGGL(ds::ds_batch_error_kernel,
-                       dim3(ds::train_row_grid(b->compute_units, b->n), static_cast<unsigned>(n_active)),
-                       dim3(ds::kRowThreads), 0, stream, v);
-    DS_HIP(hipGetLastError());
+    DS_TRY(ds::train_round_enqueue(stream, v, b->sampled ? &b->sampling_view : nullptr, n_active, depth, true, b->compute_units));
+    DS_LAUNCH(ds::ds_batch_error_kernel,
+              dim3(ds::train_row_grid(b->compute_units, b->n), static_cast<unsigned>(n_active)),
+              dim3(ds::kRowThreads), 0, stream, v);
     for (int32_t a = 0; a < n_active;) {   // the active models' heaps only: one copy per run of neighbouring models
         int32_t end = a + 1;
         while (end < n_active && b->pinned_active[end] == b->pinned_active[end - 1] + 1) ++end;
@@ -595,11 +566,9 @@ int ds_trainer_batch_step(ds_trainer_batch *batch, const uint8_t *active, int32_
     }
     DS_HIP(hipMemcpyAsync(b->pinned_errors, b->errors.ptr, b->errors.bytes(), hipMemcpyDeviceToHost, stream));
     if (b->metric_flags) {   // over the margins the partition kernels have just written
-        if (int status = ds::metrics_enqueue(stream, b->compute_units, b->metric_flags, b->metric_columns.ptr,
-                                             b->active.ptr, n_active, b->metric_keys, b->metric_pos, b->metric_fold_rows,
-                                             b->metric_scratch, b->metric_counters.ptr, ds::g_train_max_blocks.get());
-            status != DS_OK)
-            return status;
+        DS_TRY(ds::metrics_enqueue(stream, b->compute_units, b->metric_flags, b->metric_columns.ptr, b->active.ptr,
+                                   n_active, b->metric_keys, b->metric_pos, b->metric_fold_rows, b->metric_scratch,
+                                   b->metric_counters.ptr, ds::g_train_max_blocks.get()));
         DS_HIP(hipMemcpyAsync(b->pinned_metrics, b->metric_counters.ptr, b->metric_counters.bytes(),
                               hipMemcpyDeviceToHost, stream));
     }

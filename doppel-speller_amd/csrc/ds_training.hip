@@ -18,6 +18,7 @@
 // lane; a title grows to at most 257 characters before the cut); the block writes its finished rows (stride 255) with
 // coalesced dword stores at the end.  ds_training_pairs_device: one lane per train row; the partial Fisher-Yates keeps
 // only the displaced positions (at most 16) in registers, never the top_n-slot pool.
+#include "ds_launch.h"
 #include "ds_title_ops.h"
 
 namespace ds {
@@ -249,39 +250,24 @@ int ds_misspell_titles(ds_titles *source, const int32_t *d_rows, int64_t n, uint
                "ds_misspell_titles: too many titles");
     DS_HIP(hipSetDevice(source->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ds_titles *titles = new ds_titles();
+    std::unique_ptr<ds_titles> titles(new ds_titles());
     titles->device = source->device;
     titles->n = n;
     titles->stride = DS_MAX_CHARS;
     ds::DeviceBuffer<int32_t> error;
-    int status = titles->enc.allocate(static_cast<size_t>(n) * DS_MAX_CHARS);
-    if (status == DS_OK) status = titles->len.allocate(static_cast<size_t>(n));
-    if (status == DS_OK) status = error.allocate(1);
-    if (status != DS_OK) {
-        delete titles;
-        return status;
-    }
+    DS_TRY(titles->enc.allocate(static_cast<size_t>(n) * DS_MAX_CHARS));
+    DS_TRY(titles->len.allocate(static_cast<size_t>(n)));
+    DS_TRY(error.allocate(1));
     int32_t errors = 0;
-    hipError_t hip = hipMemsetAsync(error.ptr, 0, sizeof(int32_t), s);
-    if (hip == hipSuccess) {
-        hipLaunchKernelGGL(ds::ds_misspell_kernel, dim3(static_cast<unsigned>((n + ds::kMisspellBlock - 1) / ds::kMisspellBlock)),
-                           dim3(ds::kMisspellBlock), 0, s, source->enc.ptr, source->len.ptr, source->stride, source->n,
-                           d_rows, n, seed, titles->enc.ptr, titles->len.ptr, error.ptr);
-        hip = hipGetLastError();
-    }
-    if (hip == hipSuccess) hip = hipMemcpyAsync(&errors, error.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (hip == hipSuccess) hip = hipStreamSynchronize(s);
-    if (hip != hipSuccess) {
-        delete titles;
-        return ds::hip_failed(hip, "ds_misspell_kernel", __FILE__, __LINE__);
-    }
-    if (errors != 0) {
-        delete titles;
-        ds::set_error("ds_misspell_titles: %d rows are out of range or not transformed titles (3..255 codes 1..37, "
-                      "one letter or digit at least)", errors);
-        return DS_E_ARG;
-    }
-    *out = titles;
+    DS_HIP(hipMemsetAsync(error.ptr, 0, sizeof(int32_t), s));
+    DS_LAUNCH(ds::ds_misspell_kernel, dim3(static_cast<unsigned>((n + ds::kMisspellBlock - 1) / ds::kMisspellBlock)),
+              dim3(ds::kMisspellBlock), 0, s, source->enc.ptr, source->len.ptr, source->stride, source->n,
+              d_rows, n, seed, titles->enc.ptr, titles->len.ptr, error.ptr);
+    DS_HIP(hipMemcpyAsync(&errors, error.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DS_HIP(hipStreamSynchronize(s));
+    DS_REQUIRE(errors == 0, "ds_misspell_titles: %d rows are out of range or not transformed titles (3..255 codes 1..37, "
+               "one letter or digit at least)", errors);
+    *out = titles.release();
     return DS_OK;
 }
 
@@ -305,10 +291,9 @@ int ds_training_pairs_device(const int32_t *d_rows, int64_t n_queries, int32_t t
     if (n_queries == 0) return DS_OK;
     DS_REQUIRE(d_rows && d_stream_index && d_own_row && d_pair_q && d_pair_t && d_target,
                "ds_training_pairs_device: null pointer");
-    hipLaunchKernelGGL(ds::ds_training_pairs_kernel, dim3(static_cast<unsigned>((n_queries + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_rows, n_queries, top_n, sample_n, d_stream_index, d_own_row,
-                       seed, q_first, d_pair_q, d_pair_t, d_target);
-    DS_HIP(hipGetLastError());
+    DS_LAUNCH(ds::ds_training_pairs_kernel, dim3(static_cast<unsigned>((n_queries + 255) / 256)), dim3(256), 0,
+              static_cast<hipStream_t>(stream), d_rows, n_queries, top_n, sample_n, d_stream_index, d_own_row,
+              seed, q_first, d_pair_q, d_pair_t, d_target);
     return DS_OK;
 }
 

@@ -118,11 +118,11 @@ def test_the_caps_the_gpu_tests_reach_past_are_the_sources():
         return caps[0][0], 256 * int(caps[0][1])
 
     assert len(re.findall(r"std::min<int64_t>\([^;]*, 256 \* \d+\)", source)) == 3
-    assert grid_cap("static int fold(", "hipLaunchKernelGGL(ds_exhaustive_select_kernel") == \
+    assert grid_cap("static int fold(", "DS_LAUNCH(ds_exhaustive_select_kernel") == \
         ("args.n_blocks", kernel_tests.SELECT_BLOCKS_MAX)
-    assert grid_cap("int ds_exhaustive_finish_device(", "hipLaunchKernelGGL(ds::ds_exhaustive_finish_kernel") == \
+    assert grid_cap("int ds_exhaustive_finish_device(", "DS_LAUNCH(ds::ds_exhaustive_finish_kernel") == \
         ("(n_slots + 255) / 256", kernel_tests.FINISH_SLOTS_MAX // 256)
-    assert grid_cap("int ds_exhaustive_rank_device(", "hipLaunchKernelGGL(ds::ds_exhaustive_pairs_kernel") == \
+    assert grid_cap("int ds_exhaustive_rank_device(", "DS_LAUNCH(ds::ds_exhaustive_pairs_kernel") == \
         ("(here + 255) / 256", stage_tests.PAIRS_KERNEL_PAIRS_MAX // 256)
     assert (kernel_tests.SELECT_BLOCKS_MAX, kernel_tests.FINISH_SLOTS_MAX, stage_tests.PAIRS_KERNEL_PAIRS_MAX) == \
         (16384, 1048576, 1048576)
